@@ -312,6 +312,8 @@ def bench_videoresnet(a, world, rank, local_rank):
         res = eng.step(x, labels, crit)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(res.host(), logits=eng._logits, perturbation=eng.pert_model.perturbation))
     value = B * a.steps / elapsed
     tf = VRN_GFLOP[a.model] * (T / 16.0) * value / 1e3
     out = {"metric": f"attack-iters/sec ({a.model} {T}x112x112, bs={B} single-video attack) + 3D-conv TFLOP/s", "value": value,
@@ -330,6 +332,29 @@ def bench_videoresnet(a, world, rank, local_rank):
                        "unit": "TFLOP/s", "frac": fl / ms / 1e9 / PEAK_TFLOPS[a.dtype], "traffic": None, "launches_per_step": len(conv),
                        "conv_ms_per_step": ms}
     print(json.dumps(out))
+
+
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write what the timed path returned in its last timed step as out_dir/<name>.npy (float32 and bf16 as float32, every
+    other dtype -- integers, booleans, float64 -- as float64), so that two builds run with the same arguments can be compared output
+    for output.  The inputs are seeded: the same arguments give the same clips, labels and weights on every run."""
+    conv = {}
+    for name, v in arrays.items():
+        if torch.is_tensor(v):
+            v = v.detach()
+            v = (v.float() if v.dtype == torch.bfloat16 else v).cpu().numpy()
+        v = np.asarray(v)
+        conv[name] = v if v.dtype == np.float32 else v.astype(np.float64)
+    total = sum(v.nbytes for v in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return sorted(conv)
 
 
 def _self_launch(n):
@@ -356,7 +381,11 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2 and 3 (single-video bs=1 timings)")
     ap.add_argument("--autotune", action="store_true", help="time the candidate launch layouts of every convolution once before the warm-up "
                     "(measured: no gain over the built-in heuristics, which is why it is off by default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return _self_launch(a.gpus)
@@ -414,6 +443,9 @@ def main():
         torch.distributed.all_reduce(tt, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(tt.item())
     last = res.host()
+    if a.dump_outputs and rank == 0:
+        # before the roofline's extra steps move the perturbation and overwrite the logits
+        dump_outputs(a.dump_outputs, dict(last, logits=eng._logits, perturbation=eng.perturbation, delta_gradient=eng.delta_gradient()))
 
     ms_per_step = elapsed / a.steps * 1e3
     value = B * world * a.steps / elapsed
@@ -528,7 +560,7 @@ def main():
         del eng, x
         torch.cuda.empty_cache()
         if not a.no_other_configs:
-            out["other_configs"] = other_configs(local_rank)
+            out["other_configs"] = other_configs(local_rank, steps=a.steps, warmup=a.warmup)
         if not a.no_parity:
             out["parity"] = parity_check(local_rank)
             if not out["parity"]["ok"]:

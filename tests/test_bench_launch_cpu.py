@@ -37,3 +37,37 @@ def test_self_launch_starts_ranks_and_propagates_failure():
     assert not [l for l in r.stdout.splitlines() if l.startswith("{")]
     seen = sorted(l for l in (r.stdout + r.stderr).splitlines() if l.startswith("[bench] rank "))
     assert seen == ["[bench] rank 0 of 2", "[bench] rank 1 of 2"], r.stdout[-1500:] + r.stderr[-1500:]
+
+
+def test_steps_below_one_is_refused():
+    """--steps is the number of timed steps: zero timed steps would time nothing, so the argument is refused before any work"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0", "--warmup", "0"],
+                       capture_output=True, text=True, timeout=300, env=_env(), cwd=ROOT)
+    assert r.returncode == 2, (r.returncode, r.stderr[-1000:])
+    assert "--steps" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per returned value; float32 and bf16 as float32, integers / booleans as float64"""
+    import numpy as np
+    import torch
+    import bench
+    names = bench.dump_outputs(str(tmp_path / "out"), {"softmax": torch.full((2, 3), 0.25), "argmax": torch.tensor([7, 399]),
+                                                       "is_adversarial": np.bool_(True), "adv_loss": 0.5,
+                                                       "logits": torch.tensor([1.5, -2.0], dtype=torch.bfloat16)})
+    assert names == ["adv_loss", "argmax", "is_adversarial", "logits", "softmax"]
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in names}
+    assert got["softmax"].dtype == np.float32 and got["softmax"].shape == (2, 3) and (got["softmax"] == 0.25).all()
+    assert got["argmax"].dtype == np.float64 and got["argmax"].tolist() == [7.0, 399.0]
+    assert got["is_adversarial"].dtype == np.float64 and got["is_adversarial"] == 1.0
+    assert got["adv_loss"].dtype == np.float64 and got["adv_loss"] == 0.5
+    assert got["logits"].dtype == np.float32 and got["logits"].tolist() == [1.5, -2.0]
+
+
+def test_dump_outputs_refuses_more_than_64_mb(tmp_path):
+    import numpy as np
+    import pytest
+    import bench
+    with pytest.raises(ValueError, match="limit"):
+        bench.dump_outputs(str(tmp_path / "out"), {"big": np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / "out").exists()
