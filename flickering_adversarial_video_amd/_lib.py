@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FLK_LIB_PATH") or os.path.join(HERE, "libflicker_hip.so")     # FLK_LIB_PATH: A/B a second build of the library
 
 FLK_F32, FLK_BF16 = 0, 1
-FLK_NET_I3D, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18, FLK_NET_MC3_18 = 0, 1, 2, 3
+FLK_NET_I3D, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18, FLK_NET_MC3_18, FLK_NET_R2PLUS1D_34 = 0, 1, 2, 3, 4
 
 
 class FlickerHipError(RuntimeError):

@@ -925,19 +925,24 @@ __global__ __launch_bounds__(256, 2) void conv1x1_dma_kernel(const ConvKP p) {
 // -- 16 one-KiB DMA pieces, one per (group, frame): 16 positions x 64 bytes, contiguous in memory but for the channel stride -- plus the
 // slab's three taps of weights; tap dt of output frame t reads piece t + dt - 1 of its group, the pieces for t = -1 and t = T are zeros
 // written once per slot and never fetched: no halo bytes at all, 48 NF / 4 MFMAs per wave between two barriers, R - 1 slabs in flight.
-template <int NF, int R>
+// TL (temporal tiles, T a multiple of 16: the 32-frame R(2+1)D-34 / sample_length 32 clips): a workgroup owns frames [t0, t0 + 16) of ONE
+// group -- the G = 1 layout, 18 pieces -- and pieces 0 / 17 hold frames t0 - 1 / t0 + 16: fetched with the slab inside the clip (wave 0 /
+// wave 1, one extra DMA each), the zero pieces at a clip edge, where that DMA still goes out (from frame t0, in bounds) but lands in a
+// discard piece (18): every wave issues the same number of DMAs per slab on every tile, so the vmcnt immediates stay per-wave constants.
+// Same (slab, tap) K order per output as the halo kernels: the same bits.
+template <int NF, int R, bool TL>
 __global__ __launch_bounds__(256, 1) void conv_t3_dma_kernel(const ConvKP p) {
   typedef Prec<bf16_t> PR;
   typedef typename PR::frag frag;
   constexpr int EPL = 8;
   constexpr int NWP = 3 * NF / 4;                // weight pieces per wave per slab (three taps)
-  constexpr int NPW = 4 + NWP;                   // DMA instructions per wave per slab
+  constexpr int NPW = 4 + NWP;                   // DMA instructions per wave per slab (TL: waves 0 / 1 one more, the halo piece)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int q = lane >> 4, m = lane & 15;
-  const int T = p.Ti, G = 16 / T, HW = p.Hi * p.Wi, nch = HW >> 4;     // nch 16-position chunks per frame
-  const int WOFF = (16 + 2 * G) * 1024, SLOT = WOFF + 3 * NF * 1024;
+  const int Tc = p.Ti, T = TL ? 16 : Tc, G = 16 / T, HW = p.Hi * p.Wi, nch = HW >> 4;     // nch 16-position chunks per frame; T frames per tile
+  const int WOFF = (16 + 2 * G + (TL ? 1 : 0)) * 1024, SLOT = WOFF + 3 * NF * 1024;
   int ptile, ntile;
   {
     const int per = 8 * p.ntile_n, id = blockIdx.x;
@@ -945,14 +950,17 @@ __global__ __launch_bounds__(256, 1) void conv_t3_dma_kernel(const ConvKP p) {
     ntile = r >> 3;
     ptile = grp * 8 + (r & 7);
   }
-  const int tpc = (nch + G - 1) / G;             // tiles per clip
+  const int tps = (nch + G - 1) / G, tpc = TL ? tps * (Tc >> 4) : tps;       // tiles per clip: spatial x (TL) temporal
   if (ptile >= p.B * tpc) return;
-  const int b = ptile / tpc, sp = ptile - b * tpc;
+  const int b = ptile / tpc, spt = ptile - b * tpc, tt = TL ? spt / tps : 0, sp = spt - tt * tps;
+  const int t0 = 16 * tt;                        // (TL) first frame of the tile
   const unsigned lds0 = lds_addr32(smem);
 
-  // zero pieces (frames -1 and T of every group) of every slot: written once, never overwritten by a DMA
+  // zero pieces (frames -1 and T of every group) of every slot: written once, never overwritten by a DMA (TL: only at a clip edge;
+  // the pieces inside the clip are fetched)
   for (int i = tid; i < R * 2 * G * 64; i += 256) {
     const int slot = i / (2 * G * 64), r = i - slot * (2 * G * 64), g = r / 128, e = r - g * 128;
+    if (TL && ((e >> 6) ? t0 + 16 < Tc : t0 > 0)) continue;
     const int piece = g * (T + 2) + (e >> 6) * (T + 1);
     *(uint4*)(smem + slot * SLOT + piece * 1024 + (e & 63) * 16) = make_uint4(0u, 0u, 0u, 0u);
   }
@@ -970,10 +978,21 @@ __global__ __launch_bounds__(256, 1) void conv_t3_dma_kernel(const ConvKP p) {
     int c16 = sp * G + g;
     fvalid[i] = c16 < nch;
     c16 = c16 < nch ? c16 : nch - 1;
-    const unsigned base = (unsigned)((b * T + t) * HW + c16 * 16);
+    const unsigned base = (unsigned)((b * Tc + t0 + t) * HW + c16 * 16);
     voff[i] = ((base + (unsigned)(lane >> 2)) * (unsigned)p.in_ld + (unsigned)(p.in_coff + cs * EPL)) * 2u;
     fpos[i] = base + (unsigned)m;
     lpiece[i] = __builtin_amdgcn_readfirstlane(g * (T + 2) + t + 1);      // (wave-uniform: it goes into m0)
+  }
+  // (TL) the halo piece of waves 0 / 1: frame t0 - 1 into piece 0 / frame t0 + 16 into piece 17 -- at a clip edge frame t0 (any in-bounds
+  // source) into the discard piece 18, so that the zero piece stays zero and the DMA count does not depend on the tile
+  unsigned hvoff = 0u;
+  int hpiece = 0;
+  if (TL && wave < 2) {
+    const int th = wave == 0 ? t0 - 1 : t0 + 16;
+    const bool inside = th >= 0 && th < Tc;
+    const unsigned base = (unsigned)((b * Tc + (inside ? th : t0)) * HW + sp * 16);
+    hvoff = ((base + (unsigned)(lane >> 2)) * (unsigned)p.in_ld + (unsigned)(p.in_coff + cs * EPL)) * 2u;
+    hpiece = __builtin_amdgcn_readfirstlane(inside ? (wave == 0 ? 0 : 17) : 18);
   }
   const size_t wstep = (size_t)p.cout_frags * 1024;
   const int nslab = p.nslab;
@@ -989,6 +1008,7 @@ __global__ __launch_bounds__(256, 1) void conv_t3_dma_kernel(const ConvKP p) {
     const unsigned sb = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)(slot * SLOT)));
 #pragma unroll
     for (int i = 0; i < 4; ++i) glds16(voff[i] + adj, base, sb + (unsigned)(lpiece[i] * 1024));
+    if (TL && wave < 2) glds16(hvoff + adj, base, sb + (unsigned)(hpiece * 1024));
     // weights of (slab sl, tap dt), fragment f of this channel tile: piece j = wave + 4 k of the 3 NF pieces (dt = j / NF, f = j % NF)
     const char* const wb = p.w + (size_t)sl * 3 * wstep;
 #pragma unroll
@@ -1015,9 +1035,15 @@ __global__ __launch_bounds__(256, 1) void conv_t3_dma_kernel(const ConvKP p) {
   for (int k = 0; k < nslab; ++k) {
     // this wave's pieces of slab k have landed once at most the pieces of the min(R - 2, nslab - 1 - k) younger slabs are outstanding
     const int younger = nslab - 1 - k < R - 2 ? nslab - 1 - k : R - 2;
-    if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NPW) : "memory");
-    else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (TL && wave < 2) {
+      if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * (NPW + 1)) : "memory");
+      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPW + 1) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    } else {
+      if (younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * NPW) : "memory");
+      else if (younger == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(NPW) : "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
     __syncthreads();                              // everybody's pieces (and, first time, the zero pieces) are visible; the slot issued into next is free
     if (k + R - 1 < nslab) issue(k + R - 1, islot);
     islot = islot + 1 == R ? 0 : islot + 1;
@@ -1157,6 +1183,7 @@ constexpr int FLK_MAX_KSPLIT = 8;
 static int pc_route_on() { static const int on = getenv("FLK_CONV_PC") ? atoi(getenv("FLK_CONV_PC")) : 2; return on; }
 
 static int launch_any(const ConvKP& kp, dim3 grid, size_t lds, hipStream_t s, int dtype, int nf, int wn, int mode);
+static int t3_route_on() { static const int on = getenv("FLK_CONV_T3") ? atoi(getenv("FLK_CONV_T3")) : 1; return on; }
 static bool dbg_on() { static const bool d = getenv("FLK_CONV_DBG") != nullptr; return d; }      // print every launch's layout
 // FLK_CONV_KSPLIT=k: every split-K-eligible launch in k slices (tests: the split path on small shapes); 0 = the heuristic
 static int ksplit_forced() { static const int k = getenv("FLK_CONV_KSPLIT") ? atoi(getenv("FLK_CONV_KSPLIT")) : 0; return k; }
@@ -1340,7 +1367,8 @@ static int conv3d_impl(const flk_conv_args* a, const flk_conv_weights* w, int dt
   // (3,1,1) convolutions, stride 1, pad 1 (the temporal half of a (2+1)D unit) whose frames split into 16-position chunks: the LDS-DMA
   // ring over whole-T tiles (conv_t3_dma_kernel).  Measured (r2plus1d_18, bs 8, same box): halo kernels 4.72 ms per step; R = 2 ring slots
   // (60 KB of LDS at nf 4: two workgroups per CU) 4.42; R = 3 / 4 (one per CU, two / three slabs in flight) 4.82 / 4.89 -- once more the
-  // second resident workgroup is worth more than the deeper pipeline
+  // second resident workgroup is worth more than the deeper pipeline.  T a multiple of 16 (32-frame clips): temporal tiles of 16 frames
+  // (conv_t3_dma_kernel<.., TL = true>).  FLK_CONV_T3=0 sends these launches to the halo kernels (A/B measurements).
   {
     const bool flat3 = a->kt == 3 && a->kh == 1 && a->kw == 1 && a->st == 1 && a->sh == 1 && a->sw == 1 && a->pt == 1 && a->ph == 0 && a->pw == 0 &&
                        a->ost == 1 && a->osh == 1 && a->osw == 1 && a->oot == 0 && a->ooh == 0 && a->oow == 0 && a->To == a->Ti && a->Ho == a->Hi &&
@@ -1350,23 +1378,26 @@ static int conv3d_impl(const flk_conv_args* a, const flk_conv_weights* w, int dt
     // (the kernel builds its global byte offsets in 32 bits: position * in_ld * 2 + channel offset must stay below 2^32)
     const bool off32 = ((unsigned long long)npos * (unsigned)a->in_ld + (unsigned)a->in_coff + 32ull) * 2ull < (1ull << 32);
     if (!plan && off32 && dtype == FLK_BF16 && flat3 && !a->in2 && !a->out2 && !a->pos_bias && kp.ksplit == 1 && force_wn == 0 && force_da < 0 &&
-        (nf == 8 || nf == 4) && npos >= 2048 && npos < (1l << 23) && (Tn == 2 || Tn == 4 || Tn == 8 || Tn == 16) && hw % 16 == 0) {
-      const int Gn = 16 / Tn;
-      const long pt = (long)a->B * ((hw / 16 + Gn - 1) / Gn);
+        (nf == 8 || nf == 4) && npos >= 2048 && npos < (1l << 23) && (Tn == 2 || Tn == 4 || Tn == 8 || Tn % 16 == 0) && hw % 16 == 0 &&
+        t3_route_on()) {
+      const bool tl = Tn > 16;
+      const int Gn = tl ? 1 : 16 / Tn;
+      const long pt = (long)a->B * ((hw / 16 + Gn - 1) / Gn) * (tl ? Tn / 16 : 1);
       dim3 g((unsigned)((pt + 7) / 8 * 8 * ntile_n));
-      static bool attr_t3[2][FLK_MAX_DEVICES] = {};
+      static bool attr_t3[4][FLK_MAX_DEVICES] = {};
       constexpr int Rr = 2;
-      const size_t l5 = (size_t)Rr * ((16 + 2 * Gn) * 1024 + 3 * nf * 1024);
-      if (dbg_on()) fprintf(stderr, "conv 3x1x1 cin %d cout %d positions %ld | nf %d LDS-DMA ring over whole-T tiles, R %d, lds %zu, wgs %ld\n", a->cin, a->cout, npos, nf, Rr, l5, pt * ntile_n);
-#define FLK_LAUNCH_T3(NFv, Rv, idx)                                                                                                \
-      if (nf == NFv && Rr == Rv && l5 <= 160 * 1024) {                                                                              \
-        if (int rc = flk_raise_lds_limit((const void*)conv_t3_dma_kernel<NFv, Rv>, 160 * 1024, attr_t3[idx])) return rc;           \
-        FLK_LAUNCH_KERNEL((conv_t3_dma_kernel<NFv, Rv>), g, dim3(256), l5, s, kp);                                                 \
+      const size_t l5 = (size_t)Rr * ((16 + 2 * Gn + (tl ? 1 : 0)) * 1024 + 3 * nf * 1024);
+      if (dbg_on()) fprintf(stderr, "conv 3x1x1 cin %d cout %d positions %ld | nf %d LDS-DMA ring over whole-T tiles%s, R %d, lds %zu, wgs %ld\n", a->cin, a->cout, npos, nf,
+                            tl ? " (16-frame temporal tiles)" : "", Rr, l5, pt * ntile_n);
+#define FLK_LAUNCH_T3(NFv, Rv, TLv, idx)                                                                                           \
+      if (nf == NFv && Rr == Rv && tl == TLv && l5 <= 160 * 1024) {                                                                 \
+        if (int rc = flk_raise_lds_limit((const void*)conv_t3_dma_kernel<NFv, Rv, TLv>, 160 * 1024, attr_t3[idx])) return rc;      \
+        FLK_LAUNCH_KERNEL((conv_t3_dma_kernel<NFv, Rv, TLv>), g, dim3(256), l5, s, kp);                                            \
         flk_last_kernel_tag = "conv_t3_dma_kernel";                                                                                 \
         FLK_CHECK_HIP(hipGetLastError());                                                                                           \
         return FLK_OK;                                                                                                              \
       }
-      FLK_LAUNCH_T3(4, 2, 0) FLK_LAUNCH_T3(8, 2, 1)
+      FLK_LAUNCH_T3(4, 2, false, 0) FLK_LAUNCH_T3(8, 2, false, 1) FLK_LAUNCH_T3(4, 2, true, 2) FLK_LAUNCH_T3(8, 2, true, 3)
 #undef FLK_LAUNCH_T3
     }
   }

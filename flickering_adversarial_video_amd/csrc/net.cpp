@@ -96,6 +96,7 @@ int choose_nf(int cout, int taps, bool nf6 = false) {
 struct flk_net {
   int arch = 0, dtype = 0, B = 0, T = 0, H = 0, W = 0, device = 0;
   int num_classes = 400;
+  float tv_bn_eps = 1e-5f;                        // BatchNorm3d eps of the VideoResNet plans (make_conv_tv)
   bool finalized = false, fwd_done = false;
   std::map<std::string, std::vector<float>> weights;
   std::vector<std::unique_ptr<ConvLayer>> convs;
@@ -876,7 +877,7 @@ int flk_net::make_conv_tv(const std::string& wname, const std::string& bnname, i
         L->w[((size_t)t * cip + ci) * cop + co] = (*w)[((size_t)co * cin + ci) * kt * kh * kw + t];
   L->scale.assign(cop, 0.f); L->bias.assign(cop, 0.f);
   for (int c = 0; c < cout; ++c) {
-    const float a = (*g)[c] / sqrtf((*var)[c] + 1e-5f);                      // BatchNorm3d eval, eps 1e-5
+    const float a = (*g)[c] / sqrtf((*var)[c] + tv_bn_eps);                  // BatchNorm3d eval (eps 1e-5; R(2+1)D-34 1e-3)
     L->scale[c] = a; L->bias[c] = (*b)[c] - (*mean)[c] * a;
   }
   *out = L.get();
@@ -972,7 +973,21 @@ void flk_net::emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const voi
 
 int flk_net::build_videoresnet() {
   FLK_REQUIRE(H % 2 == 0 && W % 2 == 0 && T >= 1, "VideoResNet: H and W must be even");
-  const bool r21 = arch == FLK_NET_R2PLUS1D_18;
+  // R(2+1)D-34 (the IG65M / Kinetics models of moabitcoin/ig65m-pytorch, models.py: torchvision VideoResNet(BasicBlock,
+  // [Conv2Plus1D] * 4, [3, 4, 6, 3], R2Plus1dStem) with layer{2,3,4}[0].conv2[0] = Conv2Plus1D(c, c, 288 / 576 / 1152) -- the Caffe2
+  // checkpoints' midplanes -- and every BatchNorm3d built with eps 1e-3).  The midplanes are what a converted state_dict's shapes show;
+  // the eps is not in a state_dict and cannot be checked from the weights: it is taken from that models.py.
+  const bool r34 = arch == FLK_NET_R2PLUS1D_34;
+  const bool r21 = arch == FLK_NET_R2PLUS1D_18 || r34;
+  const int nblocks[4] = {r34 ? 3 : 2, r34 ? 4 : 2, r34 ? 6 : 2, r34 ? 3 : 2};
+  tv_bn_eps = r34 ? 1e-3f : 1e-5f;
+  // the class count is the fc head's: the pretrained 400 / 359 / 487 or a fine-tuned replacement (model.py:436-437); the head kernels take <= 1024
+  {
+    auto it = weights.find("fc.bias");
+    FLK_REQUIRE(it != weights.end(), "flk_net_finalize: missing weight 'fc.bias'");
+    FLK_REQUIRE(it->second.size() >= 1 && it->second.size() <= 1024, "flk_net_finalize: fc.bias has %zu classes (1..1024)", it->second.size());
+    num_classes = (int)it->second.size();
+  }
   int rc;
   std::vector<std::function<void()>> bwd_emit;
   const int H2 = H / 2, W2 = W / 2;
@@ -1066,18 +1081,20 @@ int flk_net::build_videoresnet() {
   for (int li = 1; li <= 4; ++li) {
     const int planes = planes_of[li - 1];
     const int kind = r21 ? 2 : ((arch == FLK_NET_R3D_18 || li == 1) ? 0 : 1);   // 0: 3x3x3, 1: 1x3x3 (no temporal), 2: (2+1)D
-    for (int bi = 0; bi < 2; ++bi) {
+    for (int bi = 0; bi < nblocks[li - 1]; ++bi) {
       const int stride = (li > 1 && bi == 0) ? 2 : 1;
       const bool has_ds = stride != 1 || inpl != planes;
       const std::string pre = "layer" + std::to_string(li) + "." + std::to_string(bi);
       const int mid = (inpl * planes * 27) / (inpl * 9 + 3 * planes);
+      // (R(2+1)D-34: conv2 of the first block of layer2-4 has 288 / 576 / 1152 midplanes, not the formula's 230 / 460 / 921)
+      const int mid2 = (r34 && li > 1 && bi == 0) ? planes * 9 / 4 : mid;     // (torchvision: one midplanes value per block)
       const int dst = kind == 1 ? 1 : stride;        // temporal stride of the block (and of its downsample)
       Act out, Gout;
       if ((rc = new_act(out, out_dim(cur.T, 1, dst, 0), out_dim(cur.H, 1, stride, 0), out_dim(cur.W, 1, stride, 0), planes)) ||
           (rc = new_act(Gout, out.T, out.H, out.W, planes))) return rc;
       // builds conv_builder(cin -> cout, stride s) + BN; returns the layers (1 or 2) and the intermediate tensors
       struct Unit { ConvLayer* a = nullptr; ConvLayer* b = nullptr; Act midact, Gmid; };
-      auto make_unit = [&](const std::string& up, const std::string& bnp, int ci, int co, int s, Unit& u) -> int {
+      auto make_unit = [&](const std::string& up, const std::string& bnp, int ci, int co, int s, int mid, Unit& u) -> int {
         int r;
         if (kind == 2) {
           if ((r = make_conv_tv(up + ".0", up + ".1", mid, ci, 1, 3, 3, 1, s, s, 0, 1, 1, &u.a)) || (r = pack_generic(u.a))) return r;
@@ -1091,8 +1108,8 @@ int flk_net::build_videoresnet() {
         return FLK_OK;
       };
       Unit u1, u2;
-      if ((rc = make_unit(pre + ".conv1.0", pre + ".conv1.1", inpl, planes, stride, u1))) return rc;
-      if ((rc = make_unit(pre + ".conv2.0", pre + ".conv2.1", planes, planes, 1, u2))) return rc;
+      if ((rc = make_unit(pre + ".conv1.0", pre + ".conv1.1", inpl, planes, stride, mid, u1))) return rc;
+      if ((rc = make_unit(pre + ".conv2.0", pre + ".conv2.1", planes, planes, 1, mid2, u2))) return rc;
       Act h1, Gh1;
       if ((rc = new_act(h1, out.T, out.H, out.W, planes)) || (rc = new_act(Gh1, out.T, out.H, out.W, planes))) return rc;
       ConvLayer* ds = nullptr;
@@ -1185,7 +1202,7 @@ int flk_net::build_videoresnet() {
 // ---------------------------------------------------------------------------------------------------
 extern "C" int flk_net_create(int arch, int dtype, int B, int T, int H, int W, int device, flk_net** out) {
   FLK_REQUIRE(out, "flk_net_create: null out");
-  FLK_REQUIRE(arch == FLK_NET_I3D || arch == FLK_NET_R2PLUS1D_18 || arch == FLK_NET_R3D_18 || arch == FLK_NET_MC3_18,
+  FLK_REQUIRE(arch == FLK_NET_I3D || arch == FLK_NET_R2PLUS1D_18 || arch == FLK_NET_R3D_18 || arch == FLK_NET_MC3_18 || arch == FLK_NET_R2PLUS1D_34,
               "flk_net_create: unknown arch %d", arch);
   FLK_REQUIRE(dtype == FLK_F32 || dtype == FLK_BF16, "flk_net_create: bad dtype %d", dtype);
   FLK_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0, "flk_net_create: bad dims");

@@ -9,10 +9,10 @@ import numpy as np
 import torch
 
 from . import ops, parallel
-from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18
-from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD
+from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
+from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, resolve_model
 
-ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18}
+ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 
 
 class Perturbation:
@@ -229,18 +229,32 @@ class Adversarial_metrics:
 
 
 class FlickerVideoResNet:
-    """Attack engine for torchvision-0.5.0 r2plus1d_18 / r3d_18 / mc3_18 (model.py:337-399,984-1205)."""
+    """Attack engine for torchvision-0.5.0 r2plus1d_18 / r3d_18 / mc3_18 and R(2+1)D-34 (model.py:337-399,418-441,984-1205).
+
+    ``base_model``: an architecture of ARCH_CODES, ``"ig65m"`` / ``"kinetics"`` (R(2+1)D-34 at sample_length 8 or 32, model.py:341,373) or a
+    model name of videoresnet_spec.MODELS (videoresnet_spec.resolve_model).  The class count is the weights' ``fc`` head; ``num_classes``,
+    when given, must agree with it (a fine-tuned victim brings its own ``fc``, model.py:436-437)."""
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
-                 cyclic_pert=False, num_classes=400, process_group=None, attack_type="flickering", per_clip=False):
-        if base_model not in ARCH_CODES:
-            raise ValueError(f"base_model must be one of {sorted(ARCH_CODES)} (model.py:47-56), got {base_model!r}")
+                 cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False):
+        if base_model in ARCH_CODES:
+            arch, name = base_model, base_model
+        else:
+            try:
+                arch, name, _ = resolve_model(base_model, sample_length)
+            except ValueError as e:
+                raise ValueError(f"base_model must be one of {sorted(ARCH_CODES)}, 'ig65m' / 'kinetics' or an r2plus1d_34_* model name "
+                                 f"(model.py:47-56): {e}") from None
         if not torch.cuda.is_available():
             raise RuntimeError("FlickerVideoResNet needs an MI355X (HIP) device; there is no CPU fallback")
         torch.cuda.set_device(device)
-        self.model_name, self.B, self.T, self.H, self.W, self.dtype = base_model, batch_size, sample_length, image_size, image_size, dtype
+        self.arch = arch
+        self.model_name, self.B, self.T, self.H, self.W, self.dtype = name, batch_size, sample_length, image_size, image_size, dtype
         self.pg, self.world = process_group, parallel.world_size(process_group)
-        self.net = ops.Net(ARCH_CODES[base_model], dtype, self.B, self.T, self.H, self.W, weights, device)
+        self.net = ops.Net(ARCH_CODES[arch], dtype, self.B, self.T, self.H, self.W, weights, device)
+        if num_classes is not None and int(num_classes) != self.net.num_classes:
+            raise ValueError(f"num_classes {num_classes} disagrees with the weights' fc head ({self.net.num_classes} classes)")
+        self.num_classes = self.net.num_classes
         if attack_type not in ("flickering", "L12"):
             raise ValueError(f"attack_type must be 'flickering' or 'L12', got {attack_type!r}")
         self.attack_type = attack_type
@@ -258,7 +272,7 @@ class FlickerVideoResNet:
         # bf16 per value swallowed |delta| = 1e-4 outright; the reference STARTS at U(+-1e-6), model.py:71); gradients: 16 channels
         self._xs = torch.empty((self.B, self.T, self.H // 2, self.W // 2, self.net.input_channels), dtype=tdt, device=dev)
         self._gx = torch.empty((self.B, self.T, self.H // 2, self.W // 2, 16), dtype=tdt, device=dev)
-        self._logits = torch.empty((self.B, num_classes), dtype=torch.float32, device=dev)
+        self._logits = torch.empty((self.B, self.num_classes), dtype=torch.float32, device=dev)
         self._red = torch.zeros(parallel.payload_size(self.T), dtype=torch.float32, device=dev)
         self._scratch = torch.empty(max(1, ops.load().flk_perturb_grad_scratch_bytes(self.B, self.T, self.H, self.W) // 4), dtype=torch.float32, device=dev)
         self._scalars = torch.empty(8, dtype=torch.float32, device=dev)
@@ -622,17 +636,17 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     ``state_dict`` arrays or a ``.pth`` / ``.npz`` path (videoresnet_spec.load_weights) replaces ``pretrained=True``.
     ``.pert_model``, ``.model_name``, ``.results``, ``.fit``, ``.fit_many_videos``, ``.fit_single_video_attack`` as in the reference."""
 
-    def __init__(self, dataset=None, num_classes=400, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
+    def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
                  process_group=None):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
                              "the pretrained checkpoint the reference uses (model.py:421)")
-        if isinstance(weights, (str, bytes)):
-            weights = vs.load_weights(weights, base_model)
         if sample_length is None:
             sample_length = getattr(dataset, "sample_length", 16)
+        if isinstance(weights, (str, bytes)):
+            weights = vs.load_weights(weights, base_model if base_model in vs.ARCHS else vs.resolve_model(base_model, sample_length)[0])
         if batch_size is None:
             batch_size = getattr(dataset, "batch_size", 1)
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,

@@ -1,4 +1,9 @@
-"""torchvision-0.5.0 VideoResNet (r2plus1d_18 / r3d_18 / mc3_18) layer tables and seeded synthetic weights.
+"""torchvision-0.5.0 VideoResNet (r2plus1d_18 / r3d_18 / mc3_18) and R(2+1)D-34 layer tables and seeded synthetic weights.
+
+R(2+1)D-34 is the victim the reference attacks by default (utils_cv/action_recognition/model.py:341, 418-441): the IG65M / Kinetics
+models of moabitcoin/ig65m-pytorch (models.py there): torchvision ``VideoResNet(BasicBlock, [Conv2Plus1D] * 4, [3, 4, 6, 3], R2Plus1dStem)``
+with ``layer{2,3,4}[0].conv2[0] = Conv2Plus1D(c, c, 288 / 576 / 1152)`` (the midplanes of the Caffe2 checkpoints) and every
+``BatchNorm3d`` built with eps 1e-3 (the plan, net.cpp, applies that eps; a state_dict does not record it).
 
 The reference loads pretrained weights through torchvision (utils_cv/action_recognition/model.py:421); neither
 torchvision nor the checkpoints are available here, so benchmarks and tests use seeded synthetic weights under the
@@ -8,8 +13,31 @@ import numpy as np
 
 DEFAULT_MEAN = (0.43216, 0.394666, 0.37645)      # dataset.py:28
 DEFAULT_STD = (0.22803, 0.22145, 0.216989)       # dataset.py:29
-ARCHS = ("r2plus1d_18", "r3d_18", "mc3_18")
+ARCHS = ("r2plus1d_18", "r3d_18", "mc3_18", "r2plus1d_34")
 PLANES = (64, 128, 256, 512)
+# model name -> class count of its pretrained head (model.py:46-56)
+MODELS = {"r2plus1d_34_32_ig65m": 359, "r2plus1d_34_32_kinetics": 400, "r2plus1d_34_8_ig65m": 487, "r2plus1d_34_8_kinetics": 400,
+          "mc3_18": 400, "r2plus1d_18": 400, "r3d_18": 400}
+
+
+def blocks_per_stage(arch):
+    return (3, 4, 6, 3) if arch == "r2plus1d_34" else (2, 2, 2, 2)
+
+
+def resolve_model(base_model, sample_length, num_classes=None):
+    """``VideoLearnerAdversarial.init_model``'s choice (model.py:373, 418-441): ``(base_model, sample_length, num_classes)`` ->
+    ``(arch, model name, class count)``.  ``ig65m`` / ``kinetics`` name ``r2plus1d_34_{8|32}_{base_model}`` (8 or 32 frames only); a
+    model name of MODELS stands for itself; ``num_classes`` (a replaced ``fc`` head, model.py:436-437) overrides the table's count."""
+    if base_model in ("ig65m", "kinetics"):
+        if sample_length not in (8, 32):
+            raise ValueError(f"base_model {base_model!r} needs sample_length 8 or 32 (model.py:373), got {sample_length!r}")
+        name = f"r2plus1d_34_{sample_length}_{base_model}"
+    elif base_model in MODELS:
+        name = base_model
+    else:
+        raise ValueError(f"base_model must be 'ig65m', 'kinetics' or one of {sorted(MODELS)}, got {base_model!r}")
+    arch = "r2plus1d_34" if name.startswith("r2plus1d_34_") else name
+    return arch, name, int(num_classes) if num_classes is not None else MODELS[name]
 
 
 def midplanes(inplanes, planes):
@@ -17,7 +45,7 @@ def midplanes(inplanes, planes):
 
 
 def _kind(arch, layer):
-    if arch == "r2plus1d_18":
+    if arch in ("r2plus1d_18", "r2plus1d_34"):
         return "2plus1d"
     return "3d" if (arch == "r3d_18" or layer == 1) else "notemporal"
 
@@ -25,16 +53,18 @@ def _kind(arch, layer):
 def conv_table(arch):
     """[(weight prefix, cout, cin, (kt,kh,kw), bn prefix)] in forward order"""
     assert arch in ARCHS, arch
-    t = [("stem.0", 45, 3, (1, 7, 7), "stem.1"), ("stem.3", 64, 45, (3, 1, 1), "stem.4")] if arch == "r2plus1d_18" else \
+    t = [("stem.0", 45, 3, (1, 7, 7), "stem.1"), ("stem.3", 64, 45, (3, 1, 1), "stem.4")] if _kind(arch, 2) == "2plus1d" else \
         [("stem.0", 64, 3, (3, 7, 7), "stem.1")]
     inpl = 64
     for li, planes in enumerate(PLANES, start=1):
         kind = _kind(arch, li)
-        for bi in range(2):
+        for bi in range(blocks_per_stage(arch)[li - 1]):
             stride = 2 if (li > 1 and bi == 0) else 1
             pre = f"layer{li}.{bi}"
             mid = midplanes(inpl, planes)
             for cname, ci, co in ((".conv1", inpl, planes), (".conv2", planes, planes)):
+                if arch == "r2plus1d_34" and cname == ".conv2" and li > 1 and bi == 0:
+                    mid = planes * 9 // 4            # 288 / 576 / 1152 (ig65m-pytorch's Caffe2 midplanes) instead of 230 / 460 / 921
                 if kind == "2plus1d":
                     t += [(pre + cname + ".0.0", mid, ci, (1, 3, 3), pre + cname + ".0.1"),
                           (pre + cname + ".0.3", co, mid, (3, 1, 1), pre + cname + ".1")]
@@ -94,7 +124,9 @@ def load_weights(path, arch=None):
             want[pre + ".weight"] = (co, ci, *k)
             for s in (".weight", ".bias", ".running_mean", ".running_var"):
                 want[bnp + s] = (co,)
-        want["fc.weight"], want["fc.bias"] = (W.get("fc.bias", np.zeros(400)).shape[0], 512), W.get("fc.bias", np.zeros(400)).shape
+        ncls = int(np.asarray(W["fc.bias"]).shape[0]) if "fc.bias" in W and np.asarray(W["fc.bias"]).ndim == 1 else None
+        want["fc.bias"] = (ncls,)                  # the class count is the checkpoint's own (400 / 359 / 487 or a fine-tuned head)
+        want["fc.weight"] = (ncls, 512)
         missing = sorted(set(want) - set(W))
         if missing:
             raise KeyError(f"{path}: not a {arch} state_dict, missing {missing[:4]}{' ...' if len(missing) > 4 else ''}")

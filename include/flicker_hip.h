@@ -332,6 +332,7 @@ typedef struct flk_net flk_net;
 #define FLK_NET_R2PLUS1D_18 1
 #define FLK_NET_R3D_18 2
 #define FLK_NET_MC3_18 3
+#define FLK_NET_R2PLUS1D_34 4                /* R(2+1)D-34 (IG65M / Kinetics, ig65m-pytorch): blocks 3-4-6-3, BN eps 1e-3 */
 
 int flk_net_create(int arch, int dtype, int B, int T, int H, int W, int device, flk_net** out);
 int flk_net_destroy(flk_net* n);

@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from flickering_adversarial_video_amd import videoresnet_spec as vs  # noqa: E402
 from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet, Losses  # noqa: E402
 
-BASE_MODEL = "r2plus1d_18"       # "mc3_18", "r2plus1d_18", "r3d_18"
+BASE_MODEL = "r2plus1d_18"       # "mc3_18", "r2plus1d_18", "r3d_18", "ig65m", "kinetics"
 USE_LOGITS = True
 IMPROVE_LOSS = True
 CYCLIC_PERT = False
@@ -36,7 +36,8 @@ def main():
                          "'' = seeded synthetic weights")
     ap.add_argument("--attack-type", default=ATTACK_TYPE, choices=["flickering", "L12"], help="L12: dense [3,T,H,W] perturbation (model.py:380-384)")
     ap.add_argument("--results-root", default=os.path.join(os.getcwd(), "results"))
-    ap.add_argument("--base-model", default=BASE_MODEL)
+    ap.add_argument("--base-model", default=BASE_MODEL, help="r2plus1d_18 / r3d_18 / mc3_18, ig65m / kinetics (R(2+1)D-34 at 8 or 32 "
+                    "frames, model.py:341,418-441) or an r2plus1d_34_{8|32}_{ig65m|kinetics} name")
     ap.add_argument("--n-iter", type=int, default=N_ITER)
     ap.add_argument("--restart-after", type=int, default=3000)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
@@ -52,7 +53,10 @@ def main():
         clips = (clips.astype(np.float32) / 255.0 - np.array(vs.DEFAULT_MEAN, np.float32)) / np.array(vs.DEFAULT_STD, np.float32)
     clips = np.ascontiguousarray(clips, dtype=np.float32)
     classes = [l.strip() for l in open(a.label_map)] if a.label_map else None
-    W = vs.load_weights(a.weights_npz) if a.weights_npz else vs.synthetic_weights(a.base_model, 42)
+    # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
+    # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
+    arch, _, ncls = vs.resolve_model(a.base_model, clips.shape[1])
+    W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=clips.shape[2], dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,

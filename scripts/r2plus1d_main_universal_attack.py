@@ -26,7 +26,7 @@ LR = 0.001
 LAMBDA = 1.0
 BETA_1 = 0.5
 L_INF_PERT_NORM = 0.1
-BASE_MODEL = "mc3_18"            # "mc3_18", "r2plus1d_18", "r3d_18"
+BASE_MODEL = "mc3_18"            # "mc3_18", "r2plus1d_18", "r3d_18", "ig65m", "kinetics"
 USE_LOGITS = False
 IMPROVE_LOSS = True
 CYCLIC_PERT = False
@@ -63,7 +63,8 @@ def main():
                          "'' = seeded synthetic weights")
     ap.add_argument("--attack-type", default=ATTACK_TYPE, choices=["flickering", "L12"], help="L12: dense [3,T,H,W] perturbation (model.py:380-384)")
     ap.add_argument("--results-root", default=os.path.join(os.getcwd(), "results"))
-    ap.add_argument("--base-model", default=BASE_MODEL)
+    ap.add_argument("--base-model", default=BASE_MODEL, help="r2plus1d_18 / r3d_18 / mc3_18, ig65m / kinetics (R(2+1)D-34 at 8 or 32 "
+                    "frames, model.py:341,418-441) or an r2plus1d_34_{8|32}_{ig65m|kinetics} name")
     ap.add_argument("--epochs", type=int, default=EPOCHS)
     ap.add_argument("--batch-size", type=int, default=BATCH_SIZE)
     ap.add_argument("--lr", type=float, default=LR)
@@ -82,7 +83,10 @@ def main():
     xtr, ytr = load_clips(a.train_npz)
     xva, yva = load_clips(a.val_npz)
     T, HW = xtr.shape[1], xtr.shape[2]
-    W = vs.load_weights(a.weights_npz) if a.weights_npz else vs.synthetic_weights(a.base_model, 42)
+    # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
+    # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
+    arch, _, ncls = vs.resolve_model(a.base_model, T)
+    W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type)
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
