@@ -29,6 +29,28 @@ struct ConvKP {
   int wn;            // grouped launches (conv_igemm_group_kernel): waves along N of THIS member (1 / 2 / 4), a run-time value there
 };
 
+// ---- the persistent producer / consumer launch (conv_pc.hip), routed to by conv_igemm.hip's flk_conv3d / flk_conv3d_group ----------------
+constexpr int PC_MAX_MEMBERS = 3;
+struct PcKP {
+  ConvKP m[PC_MAX_MEMBERS];          // members of the launch (a grouped launch: Branch_1 and Branch_2 of an Inception block)
+  int nmem;
+  int cnt[PC_MAX_MEMBERS];           // items of member i per XCD: its xcd_chunk position tiles x its channel tiles
+  int per_xcd;                       // sum of cnt
+  int slots;                         // workgroups per XCD (gridDim.x / 8)
+  int halo_bytes;                    // one LDS halo image (the largest member's)
+};
+// a planned launch: the kernel's arguments, the position fragments per consumer wave (the template argument) and the round model's figures
+struct PcPlan {
+  PcKP kp;
+  int ni;
+  double eff, steps;                 // useful share of (busiest workgroup x workgroups); K steps of the busiest workgroup
+  int no_fit;                        // > 0: no tile fits the LDS image (the halo of the one that did not); the plan is void
+};
+// 1 when the persistent kernel takes these n convolutions (eligible, planned, within the routing bounds), p = its plan; 0 otherwise.
+// Never touches flk_last_error.
+int pc_route(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, PcPlan& p);
+int pc_launch(const PcPlan& p, void* stream);
+
 template <typename T> struct Prec;
 template <> struct Prec<bf16_t> {
   static constexpr int EPL = 8;

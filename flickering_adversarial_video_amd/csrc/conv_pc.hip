@@ -34,7 +34,6 @@
 #include "flk_internal.h"
 #include "conv_common.h"
 
-constexpr int PC_MAX_MEMBERS = 3;
 constexpr int PC_R = 6;             // weight ring slots of 4 KiB (one K step of a 64-channel tile)
 constexpr int PC_D = 4;             // weight look-ahead in K steps; PC_R >= PC_D + 2 (a slot is re-filled two barriers after its step)
 constexpr int PC_MAX_HALO = 1024;   // halo slots per image (16 DMA blocks of 64 per chunk plane): 2 x (4 planes x 16 KiB + 64) + 6 x 4 KiB + 4 KiB (scale / bias) = 159 872 B of the 160 KiB
@@ -65,15 +64,6 @@ __device__ unsigned long long pc_stamps[512][8];
 
 // 16 bytes of zeros in device memory: the source of every halo cell that holds no data
 // (conv_common.h flk_zero16)
-
-struct PcKP {
-  ConvKP m[PC_MAX_MEMBERS];          // members of the launch (a grouped launch: Branch_1 and Branch_2 of an Inception block)
-  int nmem;
-  int cnt[PC_MAX_MEMBERS];           // items of member i per XCD: its xcd_chunk position tiles x its channel tiles
-  int per_xcd;                       // sum of cnt
-  int slots;                         // workgroups per XCD (gridDim.x / 8)
-  int halo_bytes;                    // one LDS halo image (the largest member's)
-};
 
 // The items of a workgroup, in the order every wave of it walks them: XCD x (= blockIdx.x % 8 under round-robin dispatch; speed only)
 // owns, per member, the position tiles [x * chunk, (x + 1) * chunk) with all their channel tiles back to back; its `slots` workgroups
@@ -695,8 +685,8 @@ __global__ __launch_bounds__(PC_THREADS, 2) void conv_pc_kernel(const PcKP kp) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side.  A member is eligible when: bf16; 3x3x3 taps, stride 1, logical == physical output grid; one input and one output segment; no
-// position-class bias; weights packed with 64-channel tiles (nf = 4).
+// Host side.  A member is eligible when: bf16; 3x3x3 or 1x3x3 taps, stride 1, logical == physical output grid; one input and one output
+// segment; no position-class bias; weights packed with 64-channel tiles (nf = 4).
 static const char* pc_ineligible(const flk_conv_args* a, const flk_conv_weights* w, int dtype) {
   if (dtype != FLK_BF16 || w->dtype != FLK_BF16) return "bf16 only";
   if (!((a->kt == 3 || a->kt == 1) && a->kh == 3 && a->kw == 3 && w->kt == a->kt && w->kh == 3 && w->kw == 3)) return "3x3x3 or 1x3x3 taps only";
@@ -708,43 +698,30 @@ static const char* pc_ineligible(const flk_conv_args* a, const flk_conv_weights*
   return nullptr;
 }
 
-static int pc_plan_member(const flk_conv_args* a, const flk_conv_weights* w, int max_rows, ConvKP& kp, int& ni, int force_fp = 0, int force_tfast = 0) {
-  kp = ConvKP{};
-  kp.in = (const char*)a->in; kp.w = (const char*)w->dev; kp.out = (char*)a->out; kp.in2 = kp.in; kp.out2 = kp.out;
-  kp.scale = a->scale; kp.bias = a->bias; kp.add = (const char*)a->add; kp.mask = (const char*)a->mask;
-  kp.in_ld = a->in_ld; kp.in_coff = a->in_coff; kp.cin = a->cin; kp.in2_ld = a->in_ld; kp.in2_coff = a->in_coff; kp.cin1 = a->cin;
-  kp.B = a->B; kp.Ti = a->Ti; kp.Hi = a->Hi; kp.Wi = a->Wi;
-  kp.kt = a->kt; kp.kh = kp.kw = 3; kp.st = kp.sh = kp.sw = 1; kp.pt = a->pt; kp.ph = a->ph; kp.pw = a->pw;
-  kp.To = a->To; kp.Ho = a->Ho; kp.Wo = a->Wo;
-  kp.out_ld = a->out_ld; kp.out_coff = a->out_coff; kp.cout = a->cout; kp.cout1 = a->cout;
-  kp.OT = a->OT; kp.OH = a->OH; kp.OW = a->OW; kp.ost = kp.osh = kp.osw = 1;
-  kp.add_ld = a->add_ld; kp.add_coff = a->add_coff; kp.mask_ld = a->mask_ld; kp.mask_coff = a->mask_coff; kp.relu = a->relu;
-  kp.nslab = w->nslab; kp.nslab1 = w->nslab; kp.ntaps = w->ntaps; kp.cout_frags = w->cout_frags; kp.ntile_n = w->cout_frags / 4;
-  kp.ksplit = 1; kp.wn = 1;
-  // the tile: the box of <= max_rows rows flk_choose_tile scores best under this kernel's halo budget
-  const flk_tile t = flk_choose_tile(a->To, a->Ho, a->Wo, a->kt, 3, 3, 1, 1, 1, max_rows, 1008);      // (unpadded cells; the padded image is checked below)
-  kp.Tt = t.Tt; kp.Ht = t.Ht; kp.Wt = t.Wt; kp.rows = t.Tt * t.Ht * t.Wt;
-  kp.nTt = (a->To + t.Tt - 1) / t.Tt; kp.nTh = (a->Ho + t.Ht - 1) / t.Ht; kp.nTw = (a->Wo + t.Wt - 1) / t.Wt;
-  kp.Th = t.Tt + a->kt - 1; kp.Hh = t.Ht + 2; kp.Wh = t.Wt + 2;
-  const int cells = kp.Hh * kp.Wh;
-  // frame pitch / row enumeration with the fewest extra LDS passes per position-fragment read (conv_halo_extra_passes) that fits the image
-  int best = force_fp ? 0 : conv_halo_extra_passes(kp, 0, cells), best_t = force_fp ? force_tfast : 0, best_fp = force_fp ? force_fp : cells;
-  for (int pad = 0; pad < 16 && best > 0; ++pad)
-    for (int tfast = 0; tfast < 2 && best > 0; ++tfast) {
-      const int FP = cells + pad;
-      if ((kp.Th - 1) * FP + cells > PC_MAX_HALO) continue;
-      const int c = conv_halo_extra_passes(kp, tfast, FP);
-      if (c < best) { best = c; best_t = tfast; best_fp = FP; }
-    }
-  kp.tfast = best_t; kp.FP = best_fp; kp.P = (kp.Th - 1) * best_fp + cells;
-  FLK_REQUIRE(kp.P <= PC_MAX_HALO && kp.rows <= 512, "flk_conv3d_pc: no tile fits (halo %d)", kp.P);
-  kp.plane_b = (kp.P + 63) / 64 * 1024;      // whole DMA blocks: a block's 64 cells never reach into the next plane
-  auto magic = [](int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); };
-  kp.m_HW = magic(kp.FP); kp.m_Wh = magic(kp.Wh); kp.m_hw = magic((kp.tfast ? kp.Tt : kp.Ht) * kp.Wt); kp.m_Wt = magic(kp.Wt);
-  const long ptiles = (long)a->B * kp.nTt * kp.nTh * kp.nTw;
-  kp.xcd_chunk = (int)((ptiles + 7) / 8);
-  ni = (kp.rows + 63) / 64;
-  return FLK_OK;
+// The reason the members cannot go to the persistent kernel (nullptr: they can), formatted into a per-thread buffer.  flk_last_error is left
+// alone: the routing asks this of every launch and takes another kernel when the answer is no.
+static thread_local char pc_why[256];
+#define PC_CHECK(cond, ...) do { if (!(cond)) { snprintf(pc_why, sizeof(pc_why), __VA_ARGS__); return pc_why; } } while (0)
+static const char* pc_invalid(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype) {
+  PC_CHECK(a && w && n >= 1 && n <= PC_MAX_MEMBERS, "flk_conv3d_pc: 1..%d members", PC_MAX_MEMBERS);
+  for (int i = 0; i < n; ++i) {
+    PC_CHECK(a[i] && w[i] && w[i]->dev, "flk_conv3d_pc: null member %d", i);
+    PC_CHECK(!pc_ineligible(a[i], w[i], dtype), "flk_conv3d_pc: member %d: %s", i, pc_ineligible(a[i], w[i], dtype));
+    PC_CHECK(a[i]->cin % 8 == 0 && a[i]->cout % 8 == 0 && a[i]->in_ld % 8 == 0 && a[i]->in_coff % 8 == 0 && a[i]->out_ld % 8 == 0 && a[i]->out_coff % 8 == 0 &&
+                 a[i]->in_coff + a[i]->cin <= a[i]->in_ld && a[i]->out_coff + a[i]->cout <= a[i]->out_ld,
+             "flk_conv3d_pc: channel counts / strides / offsets must be multiples of 8 and slices inside their rows");
+    PC_CHECK(!a[i]->add || (a[i]->add_ld % 8 == 0 && a[i]->add_coff % 8 == 0), "flk_conv3d_pc: add ld/coff %% 8");
+    PC_CHECK(!a[i]->mask || (a[i]->mask_ld % 8 == 0 && a[i]->mask_coff % 8 == 0), "flk_conv3d_pc: mask ld/coff %% 8");
+    PC_CHECK(a[i]->B > 0 && a[i]->To > 0 && a[i]->Ho > 0 && a[i]->Wo > 0, "flk_conv3d_pc: bad dims");
+    PC_CHECK((long)a[i]->B * a[i]->Ti * a[i]->Hi * a[i]->Wi < (1l << 24) && (long)a[i]->B * a[i]->OT * a[i]->OH * a[i]->OW < (1l << 24) && a[i]->in_ld < 4096 &&
+                 a[i]->out_ld < (1 << 24) && a[i]->mask_ld < (1 << 24),
+             "flk_conv3d_pc: more than 2^24 positions (the kernel multiplies with 24-bit instructions)");
+    PC_CHECK((size_t)a[i]->B * a[i]->Ti * a[i]->Hi * a[i]->Wi * a[i]->in_ld < (1ull << 31) && (size_t)a[i]->B * a[i]->OT * a[i]->OH * a[i]->OW * a[i]->out_ld < (1ull << 31),
+             "flk_conv3d_pc: tensor too large for 32-bit element offsets");
+  }
+  for (int i = 1; i < n; ++i)
+    PC_CHECK(a[i]->B == a[0]->B && a[i]->To == a[0]->To && a[i]->Ho == a[0]->Ho && a[i]->Wo == a[0]->Wo, "flk_conv3d_pc: the members of a launch share one output grid");
+  return nullptr;
 }
 
 static bool pc_dbg() { static const bool d = getenv("FLK_CONV_DBG") != nullptr; return d; }
@@ -762,55 +739,60 @@ static int pc_cus() {
   return ncu;
 }
 
-// The launch for n members: validation, then the tile size.  A workgroup's life is its items back to back, an item costs its K steps at the
-// launch's fragments-per-wave (NI, the largest member's: the template argument) plus an epilogue of about seven full steps, and the launch
-// lasts as long as its busiest workgroup: with few rounds of long items the rounding of items / workgroups decides (Conv3d_2c's
-// data-gradient at half the batch: 784 tiles of 8x8x8 on 256 workgroups are FOUR rounds of 162 steps for 3.06 rounds of work; 896 tiles of
-// 8x8x7 are four rounds of seven eighths the length).  Candidates: boxes of at most 512, 448 and 384 rows; the cheapest busiest workgroup wins.
-// *eff = the launch's useful share of (busiest workgroup x workgroups) under that model.
-static int pc_plan(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, PcKP& best, int& ni_best, double* eff, double* steps = nullptr) {
-  FLK_REQUIRE(a && w && n >= 1 && n <= PC_MAX_MEMBERS, "flk_conv3d_pc: 1..%d members", PC_MAX_MEMBERS);
-  for (int i = 0; i < n; ++i) {
-    FLK_REQUIRE(a[i] && w[i] && w[i]->dev, "flk_conv3d_pc: null member %d", i);
-    if (const char* why = pc_ineligible(a[i], w[i], dtype)) { flk_set_error("flk_conv3d_pc: member %d: %s", i, why); return FLK_EINVAL; }
-    FLK_REQUIRE(a[i]->cin % 8 == 0 && a[i]->cout % 8 == 0 && a[i]->in_ld % 8 == 0 && a[i]->in_coff % 8 == 0 && a[i]->out_ld % 8 == 0 && a[i]->out_coff % 8 == 0 &&
-                    a[i]->in_coff + a[i]->cin <= a[i]->in_ld && a[i]->out_coff + a[i]->cout <= a[i]->out_ld,
-                "flk_conv3d_pc: channel counts / strides / offsets must be multiples of 8 and slices inside their rows");
-    FLK_REQUIRE(!a[i]->add || (a[i]->add_ld % 8 == 0 && a[i]->add_coff % 8 == 0), "flk_conv3d_pc: add ld/coff % 8");
-    FLK_REQUIRE(!a[i]->mask || (a[i]->mask_ld % 8 == 0 && a[i]->mask_coff % 8 == 0), "flk_conv3d_pc: mask ld/coff % 8");
-    FLK_REQUIRE(a[i]->B > 0 && a[i]->To > 0 && a[i]->Ho > 0 && a[i]->Wo > 0, "flk_conv3d_pc: bad dims");
-    FLK_REQUIRE((long)a[i]->B * a[i]->Ti * a[i]->Hi * a[i]->Wi < (1l << 24) && (long)a[i]->B * a[i]->OT * a[i]->OH * a[i]->OW < (1l << 24) && a[i]->in_ld < 4096 &&
-                    a[i]->out_ld < (1 << 24) && a[i]->mask_ld < (1 << 24),
-                "flk_conv3d_pc: more than 2^24 positions (the kernel multiplies with 24-bit instructions)");
-    FLK_REQUIRE((size_t)a[i]->B * a[i]->Ti * a[i]->Hi * a[i]->Wi * a[i]->in_ld < (1ull << 31) && (size_t)a[i]->B * a[i]->OT * a[i]->OH * a[i]->OW * a[i]->out_ld < (1ull << 31),
-                "flk_conv3d_pc: tensor too large for 32-bit element offsets");
-  }
-  const int ncu = pc_cus();
-  // the search below (three tile sizes x the bank-conflict model over 32 image layouts) costs tens of microseconds: its outcome depends on the
-  // geometry only and is remembered per geometry (a plan launches the same few geometries every iteration)
-  struct Geo { int max_rows, fp[PC_MAX_MEMBERS], tfast[PC_MAX_MEMBERS]; double eff; };
-  static thread_local std::map<std::array<int, 4 + 2 * PC_MAX_MEMBERS>, Geo> cache;
-  std::array<int, 4 + 2 * PC_MAX_MEMBERS> key{};
-  key[0] = a[0]->B; key[1] = a[0]->To; key[2] = a[0]->Ho; key[3] = a[0]->Wo;
-  for (int i = 0; i < n; ++i) { key[4 + 2 * i] = a[i]->cin; key[5 + 2 * i] = a[i]->cout + (a[i]->To != a[0]->To || a[i]->Ho != a[0]->Ho || a[i]->Wo != a[0]->Wo || a[i]->B != a[0]->B ? 1 << 20 : 0); }
-  for (int i = 1; i < n; ++i)
-    FLK_REQUIRE(a[i]->B == a[0]->B && a[i]->To == a[0]->To && a[i]->Ho == a[0]->Ho && a[i]->Wo == a[0]->Wo, "flk_conv3d_pc: the members of a launch share one output grid");
-  const auto hit = cache.find(key);
+// Member m's tile (m holds its taps along T, the output grid and the strides): the box of <= max_rows rows flk_choose_tile scores best under
+// this kernel's halo budget, then the frame pitch / row enumeration with the fewest extra LDS passes per position-fragment read
+// (conv_halo_extra_passes) that fits the image.  false: no tile fits.
+static bool pc_tile(ConvKP& m, int max_rows) {
+  const flk_tile t = flk_choose_tile(m.To, m.Ho, m.Wo, m.kt, 3, 3, 1, 1, 1, max_rows, 1008);      // (unpadded cells; the padded image is checked below)
+  m.Tt = t.Tt; m.Ht = t.Ht; m.Wt = t.Wt; m.rows = t.Tt * t.Ht * t.Wt;
+  m.nTt = (m.To + t.Tt - 1) / t.Tt; m.nTh = (m.Ho + t.Ht - 1) / t.Ht; m.nTw = (m.Wo + t.Wt - 1) / t.Wt;
+  m.Th = t.Tt + m.kt - 1; m.Hh = t.Ht + 2; m.Wh = t.Wt + 2;
+  const int cells = m.Hh * m.Wh;
+  int best = conv_halo_extra_passes(m, 0, cells), best_t = 0, best_fp = cells;
+  for (int pad = 0; pad < 16 && best > 0; ++pad)
+    for (int tfast = 0; tfast < 2 && best > 0; ++tfast) {
+      const int FP = cells + pad;
+      if ((m.Th - 1) * FP + cells > PC_MAX_HALO) continue;
+      const int c = conv_halo_extra_passes(m, tfast, FP);
+      if (c < best) { best = c; best_t = tfast; best_fp = FP; }
+    }
+  m.tfast = best_t; m.FP = best_fp; m.P = (m.Th - 1) * best_fp + cells;
+  if (m.P > PC_MAX_HALO || m.rows > 512) return false;
+  m.plane_b = (m.P + 63) / 64 * 1024;      // whole DMA blocks: a block's 64 cells never reach into the next plane
+  auto magic = [](int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); };
+  m.m_HW = magic(m.FP); m.m_Wh = magic(m.Wh); m.m_hw = magic((m.tfast ? m.Tt : m.Ht) * m.Wt); m.m_Wt = magic(m.Wt);
+  const long ptiles = (long)m.B * m.nTt * m.nTh * m.nTw;
+  m.xcd_chunk = (int)((ptiles + 7) / 8);
+  return true;
+}
+
+// Every input of the geometry planner: members, the shared output grid B x To x Ho x Wo, the device's CUs, and per member its taps along T,
+// input slabs and channel fragments.
+typedef std::array<int, 6 + 3 * PC_MAX_MEMBERS> PcKey;
+
+// The launch for one key: the tile size.  A workgroup's life is its items back to back, an item costs its K steps at the launch's
+// fragments-per-wave (NI, the largest member's: the template argument) plus an epilogue of about seven full steps, and the launch lasts as long
+// as its busiest workgroup: with few rounds of long items the rounding of items / workgroups decides (Conv3d_2c's data-gradient at half the
+// batch: 784 tiles of 8x8x8 on 256 workgroups are FOUR rounds of 162 steps for 3.06 rounds of work; 896 tiles of 8x8x7 are four rounds of
+// seven eighths the length).  Candidates: boxes of at most 512, 448 and 384 rows; the cheapest busiest workgroup wins.  eff = the launch's
+// useful share of (busiest workgroup x workgroups) under that model.  Fills the geometry of the members only (no pointers, no epilogue).
+static PcPlan pc_geometry(const PcKey& k) {
+  const int n = k[0], ncu = k[5];
+  PcPlan best{};
   double best_cost = 1e300;
-  const int cand[3] = {512, 448, 384};
-  for (int max_rows : cand) {
-    if (hit != cache.end() && max_rows != hit->second.max_rows) continue;
+  for (int max_rows : {512, 448, 384}) {
     PcKP kp{};
     kp.nmem = n;
     int ni_max = 0;
     for (int i = 0; i < n; ++i) {
-      int ni = 0;
-      if (int rc = hit != cache.end() ? pc_plan_member(a[i], w[i], max_rows, kp.m[i], ni, hit->second.fp[i], hit->second.tfast[i])
-                                      : pc_plan_member(a[i], w[i], max_rows, kp.m[i], ni)) return rc;
-      ni_max = std::max(ni_max, ni);
-      kp.cnt[i] = kp.m[i].xcd_chunk * kp.m[i].ntile_n;
+      ConvKP& m = kp.m[i];
+      m.B = k[1]; m.To = k[2]; m.Ho = k[3]; m.Wo = k[4]; m.kh = m.kw = 3; m.st = m.sh = m.sw = 1;
+      m.kt = k[6 + 3 * i]; m.nslab = k[7 + 3 * i]; m.cout_frags = k[8 + 3 * i]; m.ntile_n = m.cout_frags / 4;
+      if (!pc_tile(m, max_rows)) return PcPlan{{}, 0, 0.0, 0.0, m.P};
+      ni_max = std::max(ni_max, (m.rows + 63) / 64);
+      kp.cnt[i] = m.xcd_chunk * m.ntile_n;
       kp.per_xcd += kp.cnt[i];
-      kp.halo_bytes = std::max(kp.halo_bytes, 4 * kp.m[i].plane_b + 64);
+      kp.halo_bytes = std::max(kp.halo_bytes, 4 * m.plane_b + 64);
     }
     ni_max = ni_max <= 7 ? 7 : 8;
     // one workgroup per CU (the grid a multiple of 8: blockIdx.x % 8 labels the XCD), never more workgroups than an XCD has items
@@ -826,46 +808,74 @@ static int pc_plan(const flk_conv_args* const* a, const flk_conv_weights* const*
       }
       busiest = std::max(busiest, t);
     }
-    for (int i = 0; i < n; ++i) useful += (double)a[i]->B * a[i]->To * a[i]->Ho * a[i]->Wo / 512.0 * kp.m[i].ntile_n * kp.m[i].nslab * PC_ROW * kp.m[i].kt / 8.0;
+    for (int i = 0; i < n; ++i) useful += (double)kp.m[i].B * kp.m[i].To * kp.m[i].Ho * kp.m[i].Wo / 512.0 * kp.m[i].ntile_n * kp.m[i].nslab * PC_ROW * kp.m[i].kt / 8.0;
     if (busiest < best_cost) {
-      best_cost = busiest; best = kp; ni_best = ni_max;
-      if (eff) *eff = useful / (busiest * kp.slots);
-      if (steps) *steps = busiest;
+      best_cost = busiest;
+      best.kp = kp; best.ni = ni_max; best.eff = useful / (busiest * kp.slots); best.steps = busiest;
     }
   }
-  if (hit == cache.end()) {
-    Geo g{};
-    g.max_rows = best.m[0].rows <= 384 ? 384 : best.m[0].rows <= 448 ? 448 : 512;
-    for (int i = 0; i < n; ++i) { g.fp[i] = best.m[i].FP; g.tfast[i] = best.m[i].tfast; }
-    // (max_rows as the candidate that produced the plan: re-derive it from the winning plan by re-planning member 0)
-    for (int max_rows : cand) {
-      ConvKP t{}; int ni = 0;
-      if (pc_plan_member(a[0], w[0], max_rows, t, ni, best.m[0].FP, best.m[0].tfast) == FLK_OK && t.Tt == best.m[0].Tt && t.Ht == best.m[0].Ht && t.Wt == best.m[0].Wt) { g.max_rows = max_rows; break; }
-    }
-    cache[key] = g;
-  }
-  return FLK_OK;
+  return best;
 }
 
-// n <= 3 eligible convolutions in one persistent launch (one: a plain layer; two: Branch_1 + Branch_2 of an Inception block).  Members in
-// the order given: put the longest K loops first -- the short members' items then fill the last round of the long ones.
-extern "C" int flk_conv3d_pc(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, void* stream) {
-  PcKP kp{};
-  int ni = 8;
-  double eff = 0;
-  if (int rc = pc_plan(a, w, n, dtype, kp, ni, &eff)) return rc;
+// Validation, then the plan: nullptr and p filled, or the reason there is none.  The search of pc_geometry costs tens of microseconds and a
+// network launches the same few geometries every iteration: its plans are remembered per key, per thread; what comes from the arguments
+// (pointers, leading dimensions, channel offsets, the epilogue) is copied into the plan on every call.
+static const char* pc_prepare(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, PcPlan& p) {
+  if (const char* why = pc_invalid(a, w, n, dtype)) return why;
+  PcKey key{};
+  key[0] = n; key[1] = a[0]->B; key[2] = a[0]->To; key[3] = a[0]->Ho; key[4] = a[0]->Wo; key[5] = pc_cus();
+  for (int i = 0; i < n; ++i) { key[6 + 3 * i] = a[i]->kt; key[7 + 3 * i] = w[i]->nslab; key[8 + 3 * i] = w[i]->cout_frags; }
+  static thread_local std::map<PcKey, PcPlan> cache;
+  const auto hit = cache.find(key);
+  p = hit != cache.end() ? hit->second : cache.emplace(key, pc_geometry(key)).first->second;
+  PC_CHECK(!p.no_fit, "flk_conv3d_pc: no tile fits (halo %d)", p.no_fit);
+  for (int i = 0; i < n; ++i) {
+    const flk_conv_args* ai = a[i];
+    ConvKP& m = p.kp.m[i];
+    m.in = (const char*)ai->in; m.w = (const char*)w[i]->dev; m.out = (char*)ai->out; m.in2 = m.in; m.out2 = m.out;
+    m.scale = ai->scale; m.bias = ai->bias; m.add = (const char*)ai->add; m.mask = (const char*)ai->mask;
+    m.in_ld = ai->in_ld; m.in_coff = ai->in_coff; m.cin = ai->cin; m.in2_ld = ai->in_ld; m.in2_coff = ai->in_coff; m.cin1 = ai->cin;
+    m.Ti = ai->Ti; m.Hi = ai->Hi; m.Wi = ai->Wi; m.pt = ai->pt; m.ph = ai->ph; m.pw = ai->pw;
+    m.out_ld = ai->out_ld; m.out_coff = ai->out_coff; m.cout = ai->cout; m.cout1 = ai->cout;
+    m.OT = ai->OT; m.OH = ai->OH; m.OW = ai->OW; m.ost = m.osh = m.osw = 1;
+    m.add_ld = ai->add_ld; m.add_coff = ai->add_coff; m.mask_ld = ai->mask_ld; m.mask_coff = ai->mask_coff; m.relu = ai->relu;
+    m.nslab1 = w[i]->nslab; m.ntaps = w[i]->ntaps; m.ksplit = 1; m.wn = 1;
+  }
+  return nullptr;
+}
+#undef PC_CHECK
+
+// Should these convolutions go to the persistent kernel?  A modelled efficiency (useful share of busiest workgroup x workgroups, the channel
+// tiles' padding included) of at least 0.65 and a busiest workgroup of at least 150 full K steps (~0.3 us each).  The persistent kernel pays
+// where it keeps the chip busy for a while; one 160-KB workgroup per CU cannot start beside the previous kernel's tail and its first halo image
+// and weights are staged with nothing to hide them.  With the register-staged halo of the first form the bounds were 0.8 / 300 (Conv3d_2c at
+// batch 1, ~160 steps, lost 0.05 ms per launch); since the LDS-DMA staging (cheaper start, a third of the producers' work) the same sweep reads:
+// I3D bs 8 5.38 -> 5.35 ms per step, I3D bs 1 2.05 -> 1.88, mc3_18 bs 16 4.47 -> 4.37, r2plus1d_18 bs 8 4.17 -> 4.09 (its (1,3,3) layers), and
+// the same within noise for 0.5-0.65 / 60-180.  FLK_PC_MIN_STEPS / FLK_PC_MIN_EFF override the bounds for A/B runs.
+static bool pc_bounds_met(const PcPlan& p) {
+  static const double min_steps = getenv("FLK_PC_MIN_STEPS") ? atof(getenv("FLK_PC_MIN_STEPS")) : 150.0;
+  static const double min_eff = getenv("FLK_PC_MIN_EFF") ? atof(getenv("FLK_PC_MIN_EFF")) : 0.65;
+  return p.eff >= min_eff && p.steps >= min_steps;
+}
+
+int pc_route(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, PcPlan& p) {
+  return !pc_prepare(a, w, n, dtype, p) && pc_bounds_met(p);
+}
+
+int pc_launch(const PcPlan& p, void* stream) {
+  const PcKP& kp = p.kp;
   if (pc_dbg())
-    for (int i = 0; i < n; ++i)
-      fprintf(stderr, "pc member %d: conv 3x3x3 cin %d cout %d out %dx%dx%dx%d | tile %dx%dx%d rows %d halo %d (frame pitch %d + %d, rows %s) items per XCD %d (%d slabs)\n", i,
-              a[i]->cin, a[i]->cout, a[i]->B, a[i]->To, a[i]->Ho, a[i]->Wo, kp.m[i].Tt, kp.m[i].Ht, kp.m[i].Wt, kp.m[i].rows, kp.m[i].P, kp.m[i].Hh * kp.m[i].Wh,
-              kp.m[i].FP - kp.m[i].Hh * kp.m[i].Wh, kp.m[i].tfast ? "w-T-h" : "w-h-T", kp.cnt[i], kp.m[i].nslab);
+    for (int i = 0; i < kp.nmem; ++i)
+      fprintf(stderr, "pc member %d: conv %dx3x3 cin %d cout %d out %dx%dx%dx%d | tile %dx%dx%d rows %d halo %d (frame pitch %d + %d, rows %s) items per XCD %d (%d slabs)\n", i,
+              kp.m[i].kt, kp.m[i].cin, kp.m[i].cout, kp.m[i].B, kp.m[i].To, kp.m[i].Ho, kp.m[i].Wo, kp.m[i].Tt, kp.m[i].Ht, kp.m[i].Wt, kp.m[i].rows, kp.m[i].P,
+              kp.m[i].Hh * kp.m[i].Wh, kp.m[i].FP - kp.m[i].Hh * kp.m[i].Wh, kp.m[i].tfast ? "w-T-h" : "w-h-T", kp.cnt[i], kp.m[i].nslab);
   const size_t lds = 2 * (size_t)kp.halo_bytes + (size_t)PC_R * 4096 + 4096;
   FLK_REQUIRE(lds <= 160 * 1024, "flk_conv3d_pc: %zu bytes of LDS", lds);
   hipStream_t s = (hipStream_t)stream;
   static bool attr[2][FLK_MAX_DEVICES] = {};
   const dim3 grid((unsigned)(8 * kp.slots));
-  if (pc_dbg()) fprintf(stderr, "pc launch: %d members, %d items per XCD on %d workgroups each, NI %d, lds %zu, modelled efficiency %.2f\n", n, kp.per_xcd, kp.slots, ni, lds, eff);
-  if (ni <= 7) {
+  if (pc_dbg()) fprintf(stderr, "pc launch: %d members, %d items per XCD on %d workgroups each, NI %d, lds %zu, modelled efficiency %.2f\n", kp.nmem, kp.per_xcd, kp.slots, p.ni, lds, p.eff);
+  if (p.ni <= 7) {
     if (int rc = flk_raise_lds_limit((const void*)conv_pc_kernel<7>, 160 * 1024, attr[0])) return rc;
     FLK_LAUNCH_KERNEL(conv_pc_kernel<7>, grid, dim3(PC_THREADS), lds, s, kp);
   } else {
@@ -877,25 +887,17 @@ extern "C" int flk_conv3d_pc(const flk_conv_args* const* a, const flk_conv_weigh
   return FLK_OK;
 }
 
-// Should a plan send these convolutions to flk_conv3d_pc?  Eligible members, a modelled efficiency (pc_plan: useful share of busiest workgroup x
-// workgroups, the channel tiles' padding included) of at least 0.65 and a busiest workgroup of at least 150 full K steps (~0.3 us each).  The
-// persistent kernel pays where it keeps the chip busy for a while; one 160-KB workgroup per CU cannot start beside the previous kernel's tail and
-// its first halo image and weights are staged with nothing to hide them.  With the register-staged halo of the first form the bounds were 0.8 / 300
-// (Conv3d_2c at batch 1, ~160 steps, lost 0.05 ms per launch); since the LDS-DMA staging (cheaper start, a third of the producers' work) the
-// same sweep reads: I3D bs 8 5.38 -> 5.35 ms per step, I3D bs 1 2.05 -> 1.88, mc3_18 bs 16 4.47 -> 4.37, r2plus1d_18 bs 8 4.17 -> 4.09 (its (1,3,3)
-// layers), and the same within noise for 0.5-0.65 / 60-180.  FLK_PC_MIN_STEPS / FLK_PC_MIN_EFF override the bounds for A/B runs.
+// n <= 3 eligible convolutions in one persistent launch (one: a plain layer; two: Branch_1 + Branch_2 of an Inception block).  Members in
+// the order given: put the longest K loops first -- the short members' items then fill the last round of the long ones.
+extern "C" int flk_conv3d_pc(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, void* stream) {
+  PcPlan p;
+  if (const char* why = pc_prepare(a, w, n, dtype, p)) { flk_set_error("%s", why); return FLK_EINVAL; }
+  return pc_launch(p, stream);
+}
+
 extern "C" int flk_conv3d_pc_worthwhile(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype) {
-  if (!a || !w || n < 1 || n > PC_MAX_MEMBERS) return 0;
-  for (int i = 0; i < n; ++i)
-    if (!a[i] || !w[i] || pc_ineligible(a[i], w[i], dtype)) return 0;
-  PcKP kp{};
-  int ni = 8;
-  double eff = 0;
-  double steps = 0;
-  if (pc_plan(a, w, n, dtype, kp, ni, &eff, &steps) != FLK_OK) return 0;
-  static const double min_steps = getenv("FLK_PC_MIN_STEPS") ? atof(getenv("FLK_PC_MIN_STEPS")) : 150.0;
-  static const double min_eff = getenv("FLK_PC_MIN_EFF") ? atof(getenv("FLK_PC_MIN_EFF")) : 0.65;
-  return eff >= min_eff && steps >= min_steps;
+  PcPlan p;
+  return pc_route(a, w, n, dtype, p);
 }
 
 // The launch flk_conv3d_pc would make for these geometries, without weights or a device (plan builders, tests): member 0's tile, the
@@ -913,15 +915,13 @@ extern "C" int flk_conv3d_pc_query(const flk_conv_args* const* a, int n, int dty
     wp[i] = &w;
     if (const char* why = pc_ineligible(a[i], &w, dtype)) { flk_set_error("flk_conv3d_pc_query: member %d: %s", i, why); return FLK_EINVAL; }
   }
-  PcKP kp{};
-  int ni = 8;
-  double eff = 0, steps = 0;
-  if (int rc = pc_plan(a, wp, n, dtype, kp, ni, &eff, &steps)) return rc;
-  if (tile3) { tile3[0] = kp.m[0].Tt; tile3[1] = kp.m[0].Ht; tile3[2] = kp.m[0].Wt; }
-  if (ni_out) *ni_out = ni;
-  if (eff_out) *eff_out = eff;
-  if (steps_out) *steps_out = steps;
-  return flk_conv3d_pc_worthwhile(a, wp, n, dtype);
+  PcPlan p;
+  if (const char* why = pc_prepare(a, wp, n, dtype, p)) { flk_set_error("%s", why); return FLK_EINVAL; }
+  if (tile3) { tile3[0] = p.kp.m[0].Tt; tile3[1] = p.kp.m[0].Ht; tile3[2] = p.kp.m[0].Wt; }
+  if (ni_out) *ni_out = p.ni;
+  if (eff_out) *eff_out = p.eff;
+  if (steps_out) *steps_out = p.steps;
+  return pc_bounds_met(p);
 }
 
 // does flk_conv3d_pc take this convolution (0) -- or why not (a static string; plan builders decide packing and launch form with it)

@@ -83,8 +83,8 @@ def conv3d_group(members, nfw, ring=False):
 
 
 def conv3d_pc(members):
-    """members: [(x, w, kwargs)] -- up to three 3x3x3 stride-1 bf16 convolutions (weights packed with nf = 4) in ONE persistent launch of
-    the producer / consumer kernel (flk_conv3d_pc); returns their outputs.  Bitwise the outputs of conv3d."""
+    """members: [(x, w, kwargs)] -- up to three 3x3x3 or 1x3x3 stride-1 bf16 convolutions (weights packed with nf = 4) in ONE persistent
+    launch of the producer / consumer kernel (flk_conv3d_pc); returns their outputs.  Bitwise the outputs of conv3d."""
     built = [conv3d_args(x, w, **kw) for x, w, kw in members]
     n = len(built)
     ap = (C.POINTER(ConvArgs) * n)(*[C.pointer(a) for a, _ in built])

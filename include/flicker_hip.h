@@ -119,15 +119,17 @@ int64_t flk_conv_splitk_bytes(const flk_conv_args* a, const flk_conv_weights* w)
  * one template argument the members share; every w[i] must have been packed with nf in {nfw, 2 nfw, 4 nfw}.  ring != 0: the members
  * take the LDS weight ring instead (the large launches' path): all packed with nf == nfw (4 or 8), 256-row tiles.  Longest K loops first. */
 int flk_conv3d_group(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int nfw, int ring, int dtype, void* stream);
-/* n <= 3 convolutions of 3x3x3 taps, stride 1, bf16, weights packed with nf = 4 (i3d.py:183-186 Conv3d_2c_3x3; 200-209 / 229-238 Branch_1 and
- * Branch_2 of the Mixed_3* blocks; forward and data-gradient) in ONE persistent launch with wave-specialised producers (csrc/conv_pc.hip: one
- * 512-thread workgroup per CU; four consumer waves that only read fragments and issue MFMAs, two waves streaming the weights by LDS-DMA, two
- * staging the next halo).  Bitwise the outputs of flk_conv3d.  Members in the order given, longest K loops first.
+/* n <= 3 convolutions of 3x3x3 or 1x3x3 taps, stride 1, bf16, weights packed with nf = 4 (i3d.py:183-186 Conv3d_2c_3x3; 200-209 / 229-238
+ * Branch_1 and Branch_2 of the Mixed_3* blocks; the 3x3x3 layers of r3d_18 / mc3_18 and the (1,3,3) spatial halves of r2plus1d_18's layer1
+ * units; forward and data-gradient) in ONE persistent launch with wave-specialised producers (csrc/conv_pc.hip: one 512-thread workgroup per
+ * CU; four consumer waves that only read fragments and issue MFMAs, two waves streaming the weights by LDS-DMA, two staging the next halo).
+ * Bitwise the outputs of flk_conv3d.  Members in the order given, longest K loops first.
  * flk_conv3d_pc_why_not: NULL when flk_conv3d_pc takes the convolution, else the reason (a static string). */
 int flk_conv3d_pc(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype, void* stream);
 const char* flk_conv3d_pc_why_not(const flk_conv_args* a, const flk_conv_weights* w, int dtype);
-/* 1 when a plan should send these convolutions to flk_conv3d_pc: eligible, at least two rounds of items per workgroup and a modelled
- * efficiency >= 0.8 (the large layers at the benchmark batch); flk_conv3d and flk_conv3d_group route by it themselves */
+/* 1 when flk_conv3d / flk_conv3d_group send these convolutions to flk_conv3d_pc: eligible, plannable, a modelled efficiency (useful share of
+ * busiest workgroup x workgroups) >= 0.65 and a busiest workgroup of >= 150 K steps; the environment variables FLK_PC_MIN_EFF / FLK_PC_MIN_STEPS
+ * override the two bounds (read once).  0 otherwise; never sets flk_last_error. */
 int flk_conv3d_pc_worthwhile(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int dtype);
 /* the same decision from the geometries alone (no weights, no device), with the launch behind it: member 0's tile (tile3[3] = Tt, Ht, Wt), the
  * position fragments per consumer wave, the modelled efficiency and the K steps of the busiest workgroup; returns 1 / 0 or a negative FLK_E* */

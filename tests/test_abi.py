@@ -139,3 +139,47 @@ def test_producer_consumer_routing_model_without_gpu(lib):
     assert rc == 1 and tile[0] * tile[1] * tile[2] == 448 and ni == 7 and eff > 0.65 and steps > 150, (rc, tile, ni, eff, steps)
     assert query(conv(4, 32, 56, 56, 64, 192, k=1))[0] == -1 and b"3x3x3" in lib.flk_last_error()
     assert query(conv(4, 32, 56, 56, 64, 192, stride=2))[0] == -1 and b"stride" in lib.flk_last_error()
+
+
+def test_producer_consumer_plan_cache_keyed_on_taps_without_gpu(lib):
+    """The persistent kernel's plans are remembered per thread and per geometry, and (1,3,3) and 3x3x3 taps at the same output grid and
+    channels are different geometries (tile, halo depth, frame pitch): a query answers the same after the other tap shape was planned in its
+    thread as on a fresh thread, whose cache is empty."""
+    import ctypes as C
+    import threading
+    from flickering_adversarial_video_amd import _lib
+
+    def conv(B, T, H, W, cin, cout, kt):
+        a = _lib.ConvArgs()
+        a.B, a.Ti, a.Hi, a.Wi = B, T, H, W
+        a.To, a.Ho, a.Wo, a.OT, a.OH, a.OW = T, H, W, T, H, W
+        a.kt, a.kh, a.kw = kt, 3, 3
+        a.st = a.sh = a.sw = a.ost = a.osh = a.osw = 1
+        a.pt, a.ph, a.pw = (kt - 1) // 2, 1, 1
+        a.cin, a.cout, a.in_ld, a.out_ld = cin, cout, cin, cout
+        return a
+
+    def query(a):
+        ap = (C.POINTER(_lib.ConvArgs) * 1)(C.pointer(a))
+        tile, ni, eff, steps = (C.c_int * 3)(), C.c_int(), C.c_double(), C.c_double()
+        rc = lib.flk_conv3d_pc_query(ap, 1, _lib.FLK_BF16, tile, C.byref(ni), C.byref(eff), C.byref(steps))
+        return rc, tuple(tile), ni.value, eff.value, steps.value
+
+    def in_thread(f, *args):
+        out = []
+        t = threading.Thread(target=lambda: out.append(f(*args)))
+        t.start()
+        t.join()
+        return out[0]
+
+    def sequence(geo, kts):
+        return [query(conv(*geo, kt)) for kt in kts]
+
+    for geo in ((8, 16, 56, 56, 64, 64), (16, 16, 28, 28, 128, 128)):
+        fresh = {kt: in_thread(query, conv(*geo, kt)) for kt in (1, 3)}
+        assert fresh[1][0] >= 0 and fresh[3][0] >= 0, fresh
+        assert fresh[1][1] != fresh[3][1] or fresh[1][3:] != fresh[3][3:], fresh      # the two tap shapes plan differently
+        for kts in ((1, 3), (3, 1)):
+            got = in_thread(sequence, geo, kts)
+            assert got == [fresh[kt] for kt in kts], (geo, kts, got, fresh)
+    assert in_thread(query, conv(8, 16, 56, 56, 64, 64, 3))[:2] == (1, (8, 7, 8))

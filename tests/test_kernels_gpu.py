@@ -747,6 +747,11 @@ def test_conv_pc(ops, case):
         singles.append((pw, dict(kw, out=out_s)))
         in_off += cin
         out_off += cout
+    import ctypes as C
+    from flickering_adversarial_video_amd._lib import FLK_BF16, load
+    for pw, kw in singles:      # flk_conv3d keeps each member on conv_igemm_kernel: the bitwise comparison below is between two kernels
+        a, _ = ops.conv3d_args(xg, pw, **kw)
+        assert load().flk_conv3d_pc_worthwhile((C.POINTER(ops.ConvArgs) * 1)(C.pointer(a)), (C.c_void_p * 1)(pw.handle), 1, FLK_BF16) == 0
     ops.conv3d_pc(members)
     for pw, kw in singles:
         ops.conv3d(xg, pw, **kw)
@@ -758,3 +763,28 @@ def test_conv_pc(ops, case):
     again = torch.zeros_like(out_p)
     ops.conv3d_pc([(x_, w_, dict(k_, out=again)) for x_, w_, k_ in members])
     assert torch.equal(again, out_p)
+
+
+def test_conv_pc_refusal_keeps_last_error(ops):
+    """A convolution the persistent kernel is eligible for but cannot plan (a 64-channel slice of a 4096-wide input: more than its 24-bit
+    address products allow) runs on conv_igemm_kernel: the call succeeds and flk_last_error still holds the message from before it."""
+    import ctypes as C
+    from flickering_adversarial_video_amd._lib import FLK_BF16, load
+    lib = load()
+    dtype = torch.bfloat16
+    B, T, H, W, cin, cout = 1, 4, 8, 8, 64, 64
+    x = q(rnd((B, T, H, W, 4096), 11), dtype)
+    w = q(rnd((3, 3, 3, cin, cout), 20, (2.0 / (27 * cin)) ** 0.5), dtype)
+    pw = ops.ConvWeights(w.numpy(), dtype, 4)
+    xg = x.to(dtype).cuda()
+    a, _ = ops.conv3d_args(xg, pw, in_coff=64, cin=cin)
+    assert lib.flk_conv3d_pc_why_not(C.byref(a), pw.handle, FLK_BF16) is None
+    assert lib.flk_conv3d(None, None, FLK_BF16, None) == -1
+    before = lib.flk_last_error()
+    assert b"null argument" in before
+    out = ops.conv3d(xg, pw, in_coff=64, cin=cin)
+    torch.cuda.synchronize()
+    assert lib.flk_last_error() == before
+    ref = ref_conv(x[..., 64:128].contiguous(), w, (1, 1, 1), (1, 1, 1), (T, H, W))
+    r, at = tol(dtype, ref)
+    torch.testing.assert_close(out.float().cpu(), ref, rtol=r, atol=at)
