@@ -11,6 +11,10 @@ One "step" = one attack iteration on one batch of synthetic clips resident in HB
 
 Prints ONE JSON line on rank 0.  value = clip attack-iterations per second, whole job (B clips x N ranks per step);
 conv TFLOP/s uses the algorithmic work of SURVEY.md 8(d): 444.6 GFLOP per clip per iteration at T=64 (fwd + dgrad).
+
+A plain run does only what that line needs: set up, warm up, time the K steps, write --dump-outputs, print.  --full adds, after the
+timed steps, everything else the benchmark measures or checks: the roofline of the per-launch profile, BASELINE configs 2 and 3 with
+the reference's own shapes, the in-run parity against the oracle and the CPU baseline (each of them can be left out with its --no-*).
 """
 import argparse
 import json
@@ -323,14 +327,15 @@ def bench_videoresnet(a, world, rank, local_rank):
            "conv_frac_of_mfma_peak": tf / PEAK_TFLOPS[a.dtype],
            "config": {"workload": f"{a.model} flickering attack iteration, {T}x112x112, bs={B}", "parallelism": "single (replicas only)"},
            "adv_loss_last": float(res["adv_loss"])}
-    eng.net.profile(True)
-    eng.step(x, labels, crit)
-    prof = eng.net.profile_read()
-    conv = [r for r in prof if r["kind"] == "conv"]
-    ms, fl = sum(r["ms"] for r in conv), sum(r["flops"] for r in conv)
-    out["roofline"] = {"kernel": "conv_igemm_kernel", "bound": "mfma", "achieved": fl / ms / 1e9, "peak": PEAK_TFLOPS[a.dtype],
-                       "unit": "TFLOP/s", "frac": fl / ms / 1e9 / PEAK_TFLOPS[a.dtype], "traffic": None, "launches_per_step": len(conv),
-                       "conv_ms_per_step": ms}
+    if a.full and not a.no_roofline:
+        eng.net.profile(True)
+        eng.step(x, labels, crit)
+        prof = eng.net.profile_read()
+        conv = [r for r in prof if r["kind"] == "conv"]
+        ms, fl = sum(r["ms"] for r in conv), sum(r["flops"] for r in conv)
+        out["roofline"] = {"kernel": "conv_igemm_kernel", "bound": "mfma", "achieved": fl / ms / 1e9, "peak": PEAK_TFLOPS[a.dtype],
+                           "unit": "TFLOP/s", "frac": fl / ms / 1e9 / PEAK_TFLOPS[a.dtype], "traffic": None, "launches_per_step": len(conv),
+                           "conv_ms_per_step": ms}
     print(json.dumps(out))
 
 
@@ -375,10 +380,12 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--model", default="i3d", choices=["i3d", "r2plus1d_18", "r3d_18", "mc3_18"],
                     help="i3d = the headline config; the VideoResNet models are BASELINE config 3 (use --batch 1 --frames 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity check against the oracle")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2 and 3 (single-video bs=1 timings)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the roofline profile, BASELINE configs 2 and 3, "
+                    "the in-run parity check against the oracle and the CPU baseline (off: the line carries the timed steps' figures alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline profile")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the in-run parity check against the oracle")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE configs 2 and 3 (single-video bs=1 timings)")
     ap.add_argument("--autotune", action="store_true", help="time the candidate launch layouts of every convolution once before the warm-up "
                     "(measured: no gain over the built-in heuristics, which is why it is off by default)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -464,7 +471,7 @@ def main():
         "adv_loss_last": float(last["adv_loss"]), "workspace_GiB": eng.net.workspace_bytes / 2**30,
     }
 
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         # dominant kernel = conv_igemm (all convolutions, forward and data-gradient): HIP events around every launch,
         # on the stream the kernels run on, over 3 extra (untimed) steps.  EVERY rank runs these steps (each step ends in
         # the delta-gradient all-reduce: a rank that skipped them would leave rank 0 waiting in a collective nobody joins);
@@ -555,7 +562,7 @@ def main():
             out["pool_GBps"] = pk["bytes"] / (pk["ms"] * 1e-3) / 1e9
 
     parity_failed = []
-    if rank == 0 and world == 1:
+    if a.full and rank == 0 and world == 1:
         x_host = x.cpu()
         del eng, x
         torch.cuda.empty_cache()
@@ -576,7 +583,8 @@ def main():
 
     if rank == 0:
         # a throughput line from a numerically broken build must not read as a result: the line says so and the process fails
-        out["parity_ok"] = not parity_failed
+        if a.full:
+            out["parity_ok"] = not parity_failed
         print(json.dumps(out), flush=True)
     if world > 1:
         torch.distributed.destroy_process_group()

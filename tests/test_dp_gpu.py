@@ -211,7 +211,7 @@ def test_dense_delta_two_ranks_equal_one_process():
 
 
 def test_bench_two_ranks_rehearsal():
-    """plain `python bench.py --gpus 2` (bench.py launches its own ranks through torch.distributed.run, one process per rank), rehearsed
+    """plain `python bench.py --gpus 2 --full` (bench.py launches its own ranks through torch.distributed.run, one process per rank), rehearsed
     on the one test GPU with FLK_DIST_BACKEND=gloo: the roofline leg runs on EVERY rank (its steps end in the all-reduce), rank 0 prints one JSON line."""
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -224,7 +224,7 @@ def test_bench_two_ranks_rehearsal():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "1",
-           "--frames", "16", "--no-cpu-baseline"]
+           "--frames", "16", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Turn gpurun_out/prof_<tag>/ (written by tools/profile_round.sh on the MI355X box) into the tracked files profiles/<tag>_*.
 
-  <tag>_bench_i3d_bs8_full.json      the default bench line (value, roofline, cpu_baseline, parity, other_configs)
+  <tag>_bench_i3d_bs8_full.json      the bench.py --full line (value, roofline, cpu_baseline, parity, other_configs)
   <tag>_per_layer_serial.txt         tools/profile_ops.py: every plan launch timed alone with HIP events
   <tag>_kernel_stats_{single,multi}_stream.csv   rocprofv3 --kernel-trace --stats
   <tag>_pmc_hbm_traffic.json         FETCH_SIZE / WRITE_SIZE passes (tools/pmc_summary.py: gfx950 corrections), state label = git HEAD

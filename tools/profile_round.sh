@@ -10,7 +10,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/prof_$TAG
 rm -rf $O; mkdir -p $O
 cd $R
-timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
+timeout -k 10 600 python bench.py --full --steps 20 --warmup 5 > $O/bench_full.json 2> $O/bench_full.err
 echo bench done
 timeout -k 10 200 python tools/profile_ops.py > $O/per_layer_serial.txt 2> $O/per_layer.err
 echo per-layer done
