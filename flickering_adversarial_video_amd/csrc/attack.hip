@@ -58,8 +58,13 @@ __device__ static inline void load6(const flk_apply_args& a, size_t off, float* 
     const uint16_t* p = (const uint16_t*)((const uint8_t*)a.x + off);   // off = 6*k: 2-byte aligned
     const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
     const uint32_t by[6] = {w0 & 255, w0 >> 8, w1 & 255, w1 >> 8, w2 & 255, w2 >> 8};
+    if (a.x_lut) {                                                      // per-channel table: value i is channel i % 3
 #pragma unroll
-    for (int i = 0; i < 6; ++i) x[i] = (float)by[i] * a.x_scale + a.x_bias;
+      for (int i = 0; i < 6; ++i) x[i] = a.x_lut[by[i] * 3 + i % 3];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 6; ++i) x[i] = (float)by[i] * a.x_scale + a.x_bias;
+    }
   } else {
     const float2* p = (const float2*)((const float*)a.x + off);        // off = 6*k: 8-byte aligned
     const float2 a0 = p[0], a1 = p[1], a2 = p[2];
@@ -212,6 +217,60 @@ __global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_app
   }
 }
 
+// fold_t = 4 from a uint8 clip with the decode table (W % 8 == 0): the input of the bf16 VideoResNet plans read straight from the
+// resident uint8 clip.  Laid out like apply_s2d_u8_flicker_kernel: one thread = 4 consecutive output positions of one (clip, frame,
+// row pair), each of its two source rows read as three aligned 8-byte loads (24 bytes = 8 pixels); the 768-entry table is staged in
+// LDS once per workgroup.  Per element the arithmetic of apply_s2d_hilo_kernel on the decoded value, so the bytes written equal
+// that kernel's on the fp32 clip x_lut[u8].  DENSE: the [T,H,W,3] perturbation (per element); else [T,3] / [B,T,3] (3 values).
+template <bool DENSE>
+__global__ __launch_bounds__(256) void apply_s2d_hilo_u8_kernel(const flk_apply_args a, char* out) {
+  __shared__ float lut[768];
+  for (int i = threadIdx.x; i < 768; i += 256) lut[i] = a.x_lut[i];
+  __syncthreads();
+  const int H2 = a.H / 2, W2 = a.W / 2, WG = W2 / 4;
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)(H2 * WG)) return;
+  const int h2 = i / WG, wg = i - h2 * WG;
+  const int t = blockIdx.y, b = blockIdx.z;
+  const int tx = wrap(t - a.shift_x, a.T);
+  float pv[3];
+  if constexpr (!DENSE) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pv[c] = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, 0, 0, c) : 0.f;
+  }
+  uint2 raw[2][3];
+#pragma unroll
+  for (int qh = 0; qh < 2; ++qh) {
+    const uint2* src = (const uint2*)((const uint8_t*)a.x + ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 8 * wg) * 3);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) raw[qh][k] = src[k];
+  }
+  char* dst = out + ((((size_t)b * a.T + t) * H2 + h2) * W2 + 4 * wg) * 32 * sizeof(bf16_t);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {                   // output position 4*wg + j: source pixels 2j, 2j+1 of the 8-pixel run
+    float v[32];
+#pragma unroll
+    for (int k = 0; k < 32; ++k) v[k] = 0.f;
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh) {
+      const uint32_t w[6] = {raw[qh][0].x, raw[qh][0].y, raw[qh][1].x, raw[qh][1].y, raw[qh][2].x, raw[qh][2].y};
+#pragma unroll
+      for (int e = 0; e < 6; ++e) {              // byte 6j + e of the 24-byte run: pixel 8wg + 2j + e/3, channel e % 3
+        const int bi = 6 * j + e;
+        const float x = lut[((w[bi >> 2] >> (8 * (bi & 3))) & 255u) * 3 + e % 3];
+        float p;
+        if constexpr (DENSE) p = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, 2 * h2 + qh, 8 * wg + 2 * j + e / 3, e % 3) : 0.f;
+        else p = pv[e % 3];
+        const float u = applied(a, x, p);
+        const float hi = (float)(bf16_t)u;
+        v[S2D<1>::ch(0, qh, e)] = hi;
+        v[16 + S2D<1>::ch(0, qh, e)] = u - hi;
+      }
+    }
+    store_ch<bf16_t, 32>(dst + (size_t)j * 32 * sizeof(bf16_t), v);
+  }
+}
+
 static int check_apply(const flk_apply_args* a) {
   FLK_REQUIRE(a && a->x && a->delta, "flk_perturb: null argument");
   FLK_REQUIRE(a->fold_t >= 0 && a->fold_t <= 4, "flk_perturb: fold_t must be 0 .. 4");
@@ -221,6 +280,7 @@ static int check_apply(const flk_apply_args* a) {
   FLK_REQUIRE(!(a->center && a->delta_dense), "flk_perturb: center = 1 is defined for the flicker perturbation [T,3] only");
   FLK_REQUIRE(!(a->delta_per_clip && a->delta_dense), "flk_perturb: delta_per_clip is defined for the flicker perturbation only");
   FLK_REQUIRE(!a->dclip_dev || a->delta_per_clip, "flk_perturb: dclip_dev (per-clip clamp bounds) needs delta_per_clip");
+  FLK_REQUIRE(!a->x_lut || (a->x_is_u8 && !a->center), "flk_perturb: x_lut (per-channel decode table) needs a uint8 clip and center = 0");
   return FLK_OK;
 }
 
@@ -235,12 +295,18 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_perturb_apply_s2d: bad dtype");
   if (a->fold_t == 4) {
     FLK_REQUIRE(dtype == FLK_BF16 && !a->center, "flk_perturb_apply_s2d: fold_t = 4 (two bf16 numbers per value) writes bf16, uncentred");
-    FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel, dim3(grid), dim3(256), 0, st, *a, (char*)out);
+    if (a->x_lut && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T < 65536 && a->B < 65536) {
+      const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)a->T, (unsigned)a->B);
+      if (a->delta_dense) FLK_LAUNCH_KERNEL(apply_s2d_hilo_u8_kernel<true>, g3, dim3(256), 0, st, *a, (char*)out);
+      else FLK_LAUNCH_KERNEL(apply_s2d_hilo_u8_kernel<false>, g3, dim3(256), 0, st, *a, (char*)out);
+    } else {
+      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel, dim3(grid), dim3(256), 0, st, *a, (char*)out);
+    }
     FLK_CHECK_HIP(hipGetLastError());
     return FLK_OK;
   }
   const bool bf = dtype == FLK_BF16;
-  if (ft == 2 && a->x_is_u8 && !a->delta_dense && a->W % 8 == 0 && a->T / 2 < 65536 && a->B < 65536) {
+  if (ft == 2 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && a->T / 2 < 65536 && a->B < 65536) {
     const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)(a->T / 2), (unsigned)a->B);
     if (bf && ftl == 2) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<bf16_t, 2>), g3, dim3(256), 0, st, *a, (char*)out);
     else if (bf) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<bf16_t, 3>), g3, dim3(256), 0, st, *a, (char*)out);

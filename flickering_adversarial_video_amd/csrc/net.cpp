@@ -1463,7 +1463,7 @@ static bool same_mask_args(const flk_apply_args& p, const flk_apply_args& q) {
          p.delta_dense == q.delta_dense && p.dclip == q.dclip && p.inv_std[0] == q.inv_std[0] && p.inv_std[1] == q.inv_std[1] &&
          p.inv_std[2] == q.inv_std[2] && p.lo == q.lo && p.hi == q.hi && p.adv_flag == q.adv_flag && p.shift_x == q.shift_x &&
          p.shift_p == q.shift_p && p.B == q.B && p.T == q.T && p.H == q.H && p.W == q.W && p.delta_per_clip == q.delta_per_clip &&
-         p.dclip_dev == q.dclip_dev;
+         p.dclip_dev == q.dclip_dev && p.x_lut == q.x_lut;
 }
 
 // backward to the flickering perturbation: the stem's data-gradient op is replaced by the fused delta-gradient kernel

@@ -206,15 +206,21 @@ I3D_FOLD = 3   # space-to-depth layout the I3D plan (flk_net, FLK_NET_I3D) expec
 
 
 def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0),
-                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None):
+                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None, x_lut=None):
     """x: uint8 or fp32 [B,T,H,W,3] on the GPU; delta fp32 [T,3] (flicker, shared by the batch), [B,T,3] (one flicker perturbation PER
-    CLIP: independent single-video attacks advancing in one batch) or [T,H,W,3] (dense)."""
+    CLIP: independent single-video attacks advancing in one batch) or [T,H,W,3] (dense).  x_lut: fp32 [256,3] on the device (uint8 x
+    only): byte v of channel c decodes to x_lut[v, c] (videoresnet_spec.u8_decode_table) instead of the dialect's scalar decode."""
     B, T, H, W, c3 = x.shape
     assert c3 == 3 and x.is_contiguous() and delta.is_contiguous() and delta.dtype == torch.float32
+    assert x.dtype in (torch.uint8, torch.float32)
+    if x_lut is not None:
+        assert x.dtype == torch.uint8 and not center, "x_lut: uint8 clips, center = False"
+        assert x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda, "x_lut: fp32 [256,3] on the device"
+    # the torch dialect's clips are normalised per channel: a uint8 clip without its table would be read as values 0..255
+    assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
     a = ApplyArgs()
     a.x = ptr(x)
     a.x_is_u8 = int(x.dtype == torch.uint8)
-    assert x.dtype in (torch.uint8, torch.float32)
     # TFRecord path: x = u8/128 - 1 (pre_process_rgb_flow.py:226-234)
     a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
     a.delta = ptr(delta)
@@ -232,7 +238,8 @@ def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=
     if dclip_dev is not None:   # per-clip clamp bounds (fp32 [B] on the device), per-clip perturbations only
         assert a.delta_per_clip and dclip_dev.dtype == torch.float32 and dclip_dev.shape == (B,) and dclip_dev.is_cuda
     a.dclip_dev = ptr(dclip_dev)
-    a._keepalive = (x, delta, dclip_dev)   # the struct holds raw pointers only
+    a.x_lut = ptr(x_lut)
+    a._keepalive = (x, delta, dclip_dev, x_lut)   # the struct holds raw pointers only
     return a
 
 

@@ -10,9 +10,20 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, resolve_model
+from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, resolve_model, u8_decode_table
 
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
+CLIP_DTYPES = (torch.float32, torch.uint8)
+_DECODE_TABLES = {}
+
+
+def decode_table(device):
+    """the uint8 decode table (videoresnet_spec.u8_decode_table, fp32 [256,3]) on ``device``: one copy per device"""
+    dev = torch.device(device)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _DECODE_TABLES:
+        _DECODE_TABLES[key] = torch.from_numpy(u8_decode_table()).to(torch.device(dev.type, key[1]))
+    return _DECODE_TABLES[key]
 
 
 class Perturbation:
@@ -82,22 +93,27 @@ class Perturbation:
         self.perturbation = torch.from_numpy(self._to_dev(p)).cuda()
 
     def apply_args(self, x, adversarial=True, fold_t=1):
-        """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans)"""
+        """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans).
+        x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
+        ``videoresnet_spec.normalize_u8`` makes on the host)"""
         shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
         inf = float("inf")
         return ops.make_apply_args(x, self.perturbation, dialect="torch", dclip=self.dynamic_max_norm,
                                    adv_flag=1.0 if adversarial else 0.0, shift_p=shift,
                                    inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                    lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf, fold_t=fold_t,
-                                   dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None)
+                                   dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
+                                   x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None)
 
     def forward(self, input):
         """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip.  ``x`` is the
         reference's NCDHW tensor [B,3,T,H,W] or the channels-last [B,T,H,W,3] the engine works on; the result has x's layout.  The
-        kernel writes the (h,w)-folded tensor the network consumes (flk_perturb_apply_s2d); it is unfolded here."""
+        kernel writes the (h,w)-folded tensor the network consumes (flk_perturb_apply_s2d); it is unfolded here.  A uint8 ``x`` holds
+        the frames themselves: they are normalised on the device (dataset.py:28-29), the result is the fp32 clip of the normalised input."""
         x, adversarial = input
         ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
-        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous().float().cuda()
+        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
+        xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
         B, T, H, W, _ = xcl.shape
         if T != self.T:
             raise ValueError(f"clip has {T} frames, the perturbation {self.T}")
@@ -290,9 +306,20 @@ class FlickerVideoResNet:
         return a
 
     def _check_x(self, x):
-        if tuple(x.shape) != (self.B, self.T, self.H, self.W, 3) or x.dtype != torch.float32 or not x.is_cuda:
-            raise ValueError(f"clip must be a CUDA float32 channels-last tensor {(self.B, self.T, self.H, self.W, 3)}, got {tuple(x.shape)} {x.dtype}")
+        """a clip is the normalised fp32 tensor or its uint8 frames (decoded on the device, bitwise the same clip)"""
+        if tuple(x.shape) != (self.B, self.T, self.H, self.W, 3) or x.dtype not in CLIP_DTYPES or not x.is_cuda:
+            raise ValueError(f"clip must be a CUDA float32 or uint8 channels-last tensor {(self.B, self.T, self.H, self.W, 3)}, "
+                             f"got {tuple(x.shape)} {x.dtype}")
         return x.contiguous()
+
+    @staticmethod
+    def _same_dtype(dtype, x, what):
+        """the dtype every clip of one call shares (``dtype`` None: x's); a mixture is refused"""
+        if x.dtype not in CLIP_DTYPES:
+            raise ValueError(f"{what}: clips must be float32 or uint8, got {x.dtype}")
+        if dtype is not None and x.dtype != dtype:
+            raise ValueError(f"{what}: clips of one call must share a dtype, got {dtype} and {x.dtype}")
+        return x.dtype
 
     def logits(self, x, adversarial=False):
         """model([x, adversarial]) (model.py:1028,1073)"""
@@ -451,7 +478,9 @@ class FlickerVideoResNet:
         for phase in ("train", "valid"):
             t0 = time.time()
             n, loss_sum, miss, valid = 0, 0.0, 0.0, 0.0
+            xdt = None
             for inputs, target, *_ in data_loaders[phase]:
+                xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
                 clean = self.logits(inputs, False).clone()
                 r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
                 adv_logits = self._logits
@@ -501,13 +530,18 @@ class FlickerVideoResNet:
         video the iterations are those of the one-by-one loop (bitwise in fp32 when the optimiser state is reset per video; the
         reference's single Adam instance carried from video to video, SURVEY D.5, becomes one carried state PER SLOT here)."""
         import os
+        import itertools
         assert self.per_clip
         B, T = self.B, self.T
         dev = self._logits.device
-        x = torch.zeros((B, T, self.H, self.W, 3), dtype=torch.float32, device=dev)
+        it = iter(videos)
+        first = next(it, None)
+        # the slot buffer keeps the videos' dtype: uint8 frames stay uint8 (decoded on the device by the apply kernel)
+        xdt = self._same_dtype(None, first[0], "fit_many_videos") if first is not None else torch.float32
+        it = itertools.chain([first] if first is not None else [], it)
+        x = torch.zeros((B, T, self.H, self.W, 3), dtype=xdt, device=dev)
         labels = torch.zeros(B, dtype=torch.int64, device=dev)
         rng = np.random.default_rng(0)
-        it = iter(videos)
         slots, out = [None] * B, {}
 
         def refill(b):
@@ -518,6 +552,7 @@ class FlickerVideoResNet:
                     self.active[b] = 0
                     return
                 inputs, target, name = nxt
+                self._same_dtype(xdt, inputs, "fit_many_videos")
                 cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
                 dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy") if model_dir else None
                 if dest and os.path.exists(dest):
@@ -606,7 +641,9 @@ class FlickerVideoResNet:
                                                  target_class_id, reset_optimizer_per_video=reset_optimizer_per_video, **kw)
         out = {}
         rng = np.random.default_rng(0)
+        xdt = None
         for inputs, target, name in videos:
+            xdt = self._same_dtype(xdt, inputs, "fit_many_videos")
             cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
             dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy") if model_dir else None
             if dest and os.path.exists(dest):

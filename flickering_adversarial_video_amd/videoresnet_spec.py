@@ -91,10 +91,28 @@ def synthetic_weights(arch, seed=42, num_classes=400):
     return W
 
 
+def normalize_u8(u8):
+    """uint8 frames [...,3] -> the normalised fp32 clip ``(u8 / 255 - mean) / std`` (dataset.py:28-29 transforms), evaluated in float32:
+    the expression of the scripts' host route, of ``synthetic_clip`` and of ``u8_decode_table``.  (A float64 or fused multiply-add
+    evaluation rounds to a different float32 in over half of the 768 (byte, channel) entries.)"""
+    x = np.asarray(u8).astype(np.float32)
+    return ((x / 255.0 - np.array(DEFAULT_MEAN, np.float32)) / np.array(DEFAULT_STD, np.float32)).astype(np.float32)
+
+
+def u8_decode_table():
+    """fp32 [256,3]: entry [v, c] is the normalised value of byte v in channel c -- ``normalize_u8`` of every byte, so a uint8 clip
+    decoded through it (flk_apply_args.x_lut) is bitwise the host-normalised fp32 clip"""
+    return np.ascontiguousarray(normalize_u8(np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)))
+
+
+def synthetic_clip_u8(B, T=16, H=112, W=112, seed=1234):
+    """uint8 frames [B,T,H,W,3] channels-last: the bytes ``synthetic_clip`` normalises for the same seed"""
+    return np.random.default_rng(seed).integers(0, 256, (B, T, H, W, 3)).astype(np.uint8)
+
+
 def synthetic_clip(B, T=16, H=112, W=112, seed=1234):
     """normalised fp32 clip [B,T,H,W,3] channels-last ((u8/255 - mean)/std, dataset.py transforms)"""
-    u8 = np.random.default_rng(seed).integers(0, 256, (B, T, H, W, 3)).astype(np.float32)
-    return ((u8 / 255.0 - np.array(DEFAULT_MEAN, np.float32)) / np.array(DEFAULT_STD, np.float32)).astype(np.float32)
+    return normalize_u8(synthetic_clip_u8(B, T, H, W, seed))
 
 
 def load_weights(path, arch=None):

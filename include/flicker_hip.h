@@ -181,7 +181,7 @@ int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int g_ld, int 
 /* Perturbation apply fused with the stem's space-to-depth staging.
  * kinetics_i3d_utils.py:100-142:  x_adv = clip(x + a * clip(delta[t,c], +-dclip), lo, hi)
  * model.py:80-101 (torch dialect): same with delta/std[c] and scalar clamp bounds.
- * x: uint8 (x = u8*x_scale + x_bias, the TFRecord path pre_process_rgb_flow.py:226-234) or fp32,
+ * x: uint8 (x = u8*x_scale + x_bias, the TFRecord path pre_process_rgb_flow.py:226-234, or x = x_lut[u8][c]) or fp32,
  *    [B,T,H,W,3]; delta: fp32 [T,3] (flicker) or [T,H,W,3] (dense, "L12" baseline).
  * out: [B,T/2,H/2,W/2,32] of dtype: channel (qt*4+qh*2+qw)*3+c, channels 24..31 zero -- the
  * 7x7x7/2 stem (i3d.py:169) then runs as a 4x4x4/1 convolution on MFMA.  T,H,W must be even. */
@@ -213,6 +213,10 @@ typedef struct {
                                 one batch; the delta-gradient then comes back per clip, [B,T,3].  0: one delta [T,3] shared by the batch */
   const float* dclip_dev;    /* delta_per_clip only, or NULL: per-clip clamp bounds [B] on the device replacing `dclip` -- the torch loop grows a
                                 video's bound by 1.3 when it restarts (model.py:1061-1066), independently per video */
+  const float* x_lut;        /* uint8 x only, or NULL: per-channel decode table fp32 [256][3] on the device, x = x_lut[u8 * 3 + c], replacing
+                                x_scale / x_bias -- the VideoResNet decode (u8 / 255 - mean[c]) / std[c] (dataset.py:28-29), whose float32
+                                value no scalar multiply-add reproduces bit for bit (videoresnet_spec.u8_decode_table).  Refused with
+                                center = 1 and by the I3D-only entry points (flk_stem_fwd_u8, flk_stem_delta_grad*, flk_stem_delta_bias) */
 } flk_apply_args;
 int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dtype, void* stream);
 

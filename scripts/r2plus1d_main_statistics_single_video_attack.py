@@ -2,7 +2,9 @@
 """Single-video flickering attacks on a list of clips with per-video result files -- the MI355X counterpart of the reference's
 r2plus1d_main_statistics_single_video_attack.py (knobs :28-48, `learner.fit_many_videos` :190-200, result files
 model.py:917-921).  Clips come pre-decoded (no mp4 decoder here): `--videos-npz` holds `clips` [N,T,112,112,3] (uint8 or
-normalised float32), `labels` [N] and optionally `names` [N]; class names from `--label-map` (one per line)."""
+normalised float32), `labels` [N] and optionally `names` [N]; class names from `--label-map` (one per line).  uint8 clips are
+uploaded once and stay uint8 (`--decode device`, the default: the attack's apply kernel normalises them, bitwise the host route);
+`--decode host` normalises them on the host into float32 and copies each video on its turn, like float32 files."""
 import argparse
 import os
 import sys
@@ -43,15 +45,20 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--batch", type=int, default=1, help="videos attacked at once, each with its own perturbation / clamp bound / Adam state "
                     "(flickering attack; 1 = the reference's one-by-one loop)")
+    ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
+                    "uint8 copy (default), or on the host into float32 (float32 files always take the host route)")
     ap.add_argument("--reset-optimizer-per-video", action="store_true", help="fresh Adam state for every video (the reference carries one "
                     "state from video to video, model.py:946; with --batch > 1 the carried state is per batch slot)")
     a = ap.parse_args()
     z = np.load(a.videos_npz, allow_pickle=True)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
     names = [str(n) for n in z["names"]] if "names" in z else [f"video_{i:05d}" for i in range(len(clips))]
-    if clips.dtype == np.uint8:
-        clips = (clips.astype(np.float32) / 255.0 - np.array(vs.DEFAULT_MEAN, np.float32)) / np.array(vs.DEFAULT_STD, np.float32)
-    clips = np.ascontiguousarray(clips, dtype=np.float32)
+    if clips.dtype == np.uint8 and a.decode == "device":
+        clips = np.ascontiguousarray(clips)
+    else:
+        if clips.dtype == np.uint8:
+            clips = vs.normalize_u8(clips)
+        clips = np.ascontiguousarray(clips, dtype=np.float32)
     classes = [l.strip() for l in open(a.label_map)] if a.label_map else None
     # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
     # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
@@ -62,7 +69,11 @@ def main():
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
-    videos = ((torch.from_numpy(clips[i:i + 1]).cuda(), torch.from_numpy(labels[i:i + 1]).cuda(), names[i]) for i in range(len(clips)))
+    if clips.dtype == np.uint8:          # resident: one upload, every video is a slice of it
+        xd, yd = torch.from_numpy(clips).cuda(), torch.from_numpy(labels).cuda()
+        videos = ((xd[i:i + 1], yd[i:i + 1], names[i]) for i in range(len(clips)))
+    else:
+        videos = ((torch.from_numpy(clips[i:i + 1]).cuda(), torch.from_numpy(labels[i:i + 1]).cuda(), names[i]) for i in range(len(clips)))
     out = learner.fit_many_videos(videos, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
                                   reset_optimizer_per_video=a.reset_optimizer_per_video)
     for name, r in out.items():

@@ -7,7 +7,11 @@ What differs: clips come PRE-DECODED (the reference decodes mp4 with decord, whi
 `--val-npz` hold `clips` ([N,T,112,112,3]; uint8 frames or float32 already normalised with dataset.py:28-29 mean / std)
 and `labels` ([N] int).  Weights: `--weights-npz` with torchvision state_dict names, else seeded synthetic weights.
 One process per GPU (torch.distributed.run); every rank takes its shard of the training clips, the perturbation is
-replicated (parallel.py)."""
+replicated (parallel.py).
+
+uint8 clips stay uint8 (`--decode device`, the default): each rank uploads its shard once and every batch is a slice of that
+resident tensor; the attack's apply kernel normalises the frames (bitwise the host route's float32 values).  `--decode host`
+normalises on the host and copies every batch, as float32, per step -- the route of float32 files."""
 import argparse
 import glob
 import os
@@ -38,20 +42,43 @@ MODEL_INPUT_SIZE = 16            # frames per clip for the three VideoResNets
 BATCH_SIZE = 8                   # BATCH_SIZE_ARRAY[1] (one device per process here)
 
 
-def load_clips(path):
+def load_clips(path, decode="device"):
+    """clips as the file holds them when they are uint8 and decode == "device", else normalised float32 on the host"""
     z = np.load(path)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
+    if clips.dtype == np.uint8 and decode == "device":
+        return np.ascontiguousarray(clips), labels
     if clips.dtype == np.uint8:      # get_normalize_transforms (dataset.py:212-243): /255, mean / std
-        clips = (clips.astype(np.float32) / 255.0 - np.array(vs.DEFAULT_MEAN, np.float32)) / np.array(vs.DEFAULT_STD, np.float32)
+        clips = vs.normalize_u8(clips)
     return np.ascontiguousarray(clips, dtype=np.float32), labels
 
 
+def batch_ids(n, batch_size, rank=0, world=1):
+    """the batches rank takes, dropping the ragged tail; ranks take alternating batches"""
+    nb = n // batch_size
+    return range(rank, nb - nb % world if world > 1 else nb, world)
+
+
 def loader(clips, labels, batch_size, rank=0, world=1):
-    """batches of (clip [B,T,H,W,3] on the GPU, label, None), dropping the ragged tail; ranks take alternating batches"""
-    nb = len(clips) // batch_size
-    for i in range(rank, nb - nb % world if world > 1 else nb, world):
+    """batches of (clip [B,T,H,W,3] on the GPU, label, None), copied from the host per step"""
+    for i in batch_ids(len(clips), batch_size, rank, world):
         sl = slice(i * batch_size, (i + 1) * batch_size)
         yield torch.from_numpy(clips[sl]).cuda(), torch.from_numpy(labels[sl]).cuda(), None
+
+
+class ResidentShard:
+    """uint8 clips of the batches one rank takes, uploaded once; every epoch's batches are slices of the device tensor"""
+
+    def __init__(self, clips, labels, batch_size, rank=0, world=1):
+        ids = list(batch_ids(len(clips), batch_size, rank, world))
+        rows = np.concatenate([np.arange(i * batch_size, (i + 1) * batch_size) for i in ids]) if ids else np.zeros(0, np.int64)
+        self.bs, self.n = batch_size, len(ids)
+        self.x = torch.from_numpy(np.ascontiguousarray(clips[rows])).cuda()
+        self.y = torch.from_numpy(labels[rows]).cuda()
+
+    def __iter__(self):
+        for k in range(self.n):
+            yield self.x[k * self.bs:(k + 1) * self.bs], self.y[k * self.bs:(k + 1) * self.bs], None
 
 
 def main():
@@ -69,6 +96,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=BATCH_SIZE)
     ap.add_argument("--lr", type=float, default=LR)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
+                    "uint8 copy (default), or on the host with a float32 copy per step (float32 files always take the host route)")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
     a = ap.parse_args()
@@ -80,8 +109,8 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    xtr, ytr = load_clips(a.train_npz)
-    xva, yva = load_clips(a.val_npz)
+    xtr, ytr = load_clips(a.train_npz, a.decode)
+    xva, yva = load_clips(a.val_npz, a.decode)
     T, HW = xtr.shape[1], xtr.shape[2]
     # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
     # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
@@ -101,10 +130,17 @@ def main():
         print(f"Success! to continue from last epoch. init with {start_epoch}")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
 
+    resident = {}
+
     class Loaders(dict):                          # fresh iterators every epoch
         def __getitem__(self, phase):
             x, y = (xtr, ytr) if phase == "train" else (xva, yva)
-            return loader(x, y, a.batch_size, rank if phase == "train" else 0, world if phase == "train" else 1)
+            r, w = (rank, world) if phase == "train" else (0, 1)
+            if x.dtype == np.uint8:               # --decode device: the shard is uploaded on first use, then sliced
+                if phase not in resident:
+                    resident[phase] = ResidentShard(x, y, a.batch_size, r, w)
+                return iter(resident[phase])
+            return loader(x, y, a.batch_size, r, w)
     results = learner.fit(Loaders(), crit, Adversarial_metrics(targeted=TARGETED_ATTACK), lr=a.lr, epochs=a.epochs, model_dir=dest if rank == 0 else None,
                           model_name=learner.model_name, save_model=rank == 0, start_epoch=start_epoch)
     if rank == 0:
