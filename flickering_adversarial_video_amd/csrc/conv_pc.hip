@@ -584,7 +584,10 @@ __global__ __launch_bounds__(PC_THREADS, 2) void conv_pc_kernel(const PcKP kp) {
     const unsigned lds0 = lds_addr32(smem);
     // what each image holds: (position tile, slab).  A member of TWO slabs alternates its images in step with its channel tiles -- the slab
     // the next channel tile starts with is still there (Conv3d_2c forward: 64 -> 192, three channel tiles per position tile: two stagings
-    // in three skipped; the (1,3,3) 64 -> 144 of r2plus1d_18 likewise)
+    // in three skipped; the (1,3,3) 64 -> 144 of r2plus1d_18 likewise).  On 256 CUs the skip never fires: a workgroup's consecutive items
+    // are `slots` = 32 XCD-local indices apart and a position tile has ceil(cout / 64) <= 3 channel tiles back to back, so its next item is
+    // always on another position tile (the item order of Conv3d_2c and r2plus1d_18's layer1, simulated: no skip).  It takes slots < channel
+    // tiles -- a device of fewer than 8 x 3 CUs.  Unreachable, not wrong; reordering the items to use it is a performance question.
     int held0 = -1, held1 = -1;
     auto begin_slab = [&](const Slab& zn) {
       fresh = pc_u(zn.key != z.key) != 0;

@@ -690,10 +690,12 @@ def test_conv_ring_weights_a_row_ahead(ops, transpose):
 
 
 PC_CASES = [
-    # name, B, T, H, W, [(cin, cout), ...] members, data-gradient form?   -- flk_conv3d_pc: 3x3x3 stride 1, weights packed with nf = 4
-    ("fwd_64_192_8x8x8_tiles", 1, 16, 16, 24, [(64, 192)], False),              # 512-row tiles, two slabs, three channel tiles (Conv3d_2c's shape class)
+    # name, B, T, H, W, [(cin, cout), ...] members, data-gradient form?   -- flk_conv3d_pc: 3x3x3 stride 1, weights packed with nf = 4.
+    # Every case plans NI = 7 (conv_pc_kernel<7>) and gives each workgroup ONE item (at most 32 items per XCD on 256 CUs): the multi-item
+    # path, the <8> instance and three-member launches are tests/test_conv_pc_scale_gpu.py's
+    ("fwd_64_192_8x8x8_tiles", 1, 16, 16, 24, [(64, 192)], False),              # 8x8x6 tiles (384 rows), two slabs, three channel tiles (Conv3d_2c's shape class)
     ("dgrad_192_64", 1, 8, 16, 16, [(192, 64)], True),                          # six slabs; ReLU mask in the epilogue
-    ("fwd_96_128_28x28_448_row_tiles", 1, 16, 28, 28, [(96, 128)], False),      # 16x4x7 tiles: seven fragments per consumer wave (NI = 7), three slabs (odd step count)
+    ("fwd_96_128_28x28_448_row_tiles", 1, 16, 28, 28, [(96, 128)], False),      # 8x4x14 tiles (448 rows): seven fragments per consumer wave, three slabs (odd step count)
     ("group_128_192+32_96", 2, 8, 14, 14, [(128, 192), (32, 96)], False),       # two members (Mixed_3c Branch_1 + Branch_2): different K loops, 96 = 1.5 channel tiles
     ("group_dgrad_128_96+32_16", 1, 16, 14, 14, [(128, 96), (32, 16)], True),   # narrow outputs: 16 channels in a 64-wide tile
     ("ragged_40_72_partial_tiles", 3, 5, 9, 11, [(40, 72)], False),             # 40 input channels (a half-valid slab), grid not a multiple of any tile, several clips
@@ -720,8 +722,14 @@ def test_conv_pc(ops, case):
     xin = q(rnd((B, T, H, W, ci_tot), 11), dtype)
     xg = xin.to(dtype).cuda()
     maskt = q(rnd((B, T, H, W, co_tot), 12), dtype)
-    out_p = torch.zeros((B, T, H, W, co_tot), dtype=dtype, device="cuda")
-    out_s = torch.zeros_like(out_p)
+    # outputs poisoned: NaN in the channels a member writes, a finite sentinel in the 8 nobody owns -- a store that never happens or lands
+    # outside its slice shows (zeros would hide a missing store wherever the ReLU / mask gives 0)
+    def poisoned():
+        o = torch.full((B, T, H, W, co_tot), -1536.0, dtype=dtype, device="cuda")
+        o[..., 8:] = float("nan")
+        return o
+    out_p = poisoned()
+    out_s = poisoned()
     members, singles, refs = [], [], []
     in_off, out_off = 0, 8
     for i, (cin, cout) in enumerate(mem):
@@ -759,10 +767,12 @@ def test_conv_pc(ops, case):
     for ref, off, cout in refs:
         r, a = tol(dtype, ref)
         torch.testing.assert_close(out_p[..., off:off + cout].float().cpu(), ref, rtol=r * (2 if tr else 1), atol=a * (2 if tr else 1))   # (a * W is rounded once more when folded)
-    assert torch.equal(out_p, out_s)                                    # bitwise flk_conv3d (untouched channels stay zero)
-    again = torch.zeros_like(out_p)
+    assert not bool(out_p[..., 8:].isnan().any())                      # every output element stored
+    assert bool((out_p[..., :8] == -1536.0).all())                     # nothing stored outside the members' slices
+    assert torch.equal(out_p.view(torch.int16), out_s.view(torch.int16))      # bitwise flk_conv3d
+    again = poisoned()
     ops.conv3d_pc([(x_, w_, dict(k_, out=again)) for x_, w_, k_ in members])
-    assert torch.equal(again, out_p)
+    assert torch.equal(again.view(torch.int16), out_p.view(torch.int16))
 
 
 def test_conv_pc_refusal_keeps_last_error(ops):
