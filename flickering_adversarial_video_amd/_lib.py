@@ -60,13 +60,13 @@ class AdamArgs(C.Structure):
                 ("beta0", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("beta3", C.c_float),
                 ("dyn_max_norm", C.c_float), ("g_scale", C.c_float),
                 ("lr", C.c_float), ("adam_b1", C.c_float), ("adam_b2", C.c_float), ("adam_eps", C.c_float),
-                ("step", C.c_int)]
+                ("step", C.c_int), ("pgd_eps", C.c_float)]
 
 
 class DenseAdamArgs(C.Structure):
     _fields_ = [("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("torch_dialect", C.c_int), ("beta", C.c_float), ("g_scale", C.c_float),
                 ("lr", C.c_float), ("adam_b1", C.c_float), ("adam_b2", C.c_float), ("adam_eps", C.c_float), ("step", C.c_int),
-                ("dyn_max_norm", C.c_float)]
+                ("dyn_max_norm", C.c_float), ("pgd_eps", C.c_float)]
 
 
 class LossArgs(C.Structure):
@@ -98,9 +98,13 @@ _SIGS = {
     "flk_perturb_reg_adam": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_perturb_reg_pgd": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_perturb_reg_pgd_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
     "flk_dense_adam_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "flk_perturb_dense_l12_adam": (C.c_int, [C.POINTER(DenseAdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p]),
+    "flk_perturb_dense_l12_pgd": (C.c_int, [C.POINTER(DenseAdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_softmax_adv_loss": (C.c_int, [C.POINTER(LossArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_net_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "flk_net_destroy": (C.c_int, [C.c_void_p]),

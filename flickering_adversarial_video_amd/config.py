@@ -25,6 +25,11 @@ class Cfg(dict):
 
 
 DEFAULT_MODEL = {"FRAMES": 90, "DTYPE": "bf16", "WEIGHTS_NPZ": ""}
+ATTACK_SECTIONS = ("SINGLE_VIDEO_ATTACK", "CLASS_GEN_ATTACK", "UNIVERSAL_ATTACK")
+# [new] per attack section: OPTIMIZER adam (the reference's) | pgd (projected sign-gradient); PGD_EPS: its l-infinity radius
+# (None: 0.4, the apply clip, for the flickering perturbation; required for the dense one)
+DEFAULT_ATTACK = {"OPTIMIZER": "adam", "PGD_EPS": None}
+OPTIMIZERS = ("adam", "pgd")
 
 
 def load_config(yml_path):
@@ -33,6 +38,13 @@ def load_config(yml_path):
     cfg.setdefault("MODEL", Cfg())
     for k, v in DEFAULT_MODEL.items():
         cfg.MODEL.setdefault(k, v)
+    for sec in ATTACK_SECTIONS:
+        if sec not in cfg:
+            continue
+        for k, v in DEFAULT_ATTACK.items():
+            cfg[sec].setdefault(k, v)
+        if cfg[sec].OPTIMIZER not in OPTIMIZERS:
+            raise ValueError(f"{sec}.OPTIMIZER must be one of {OPTIMIZERS}, got {cfg[sec].OPTIMIZER!r}")
     return cfg
 
 

@@ -508,7 +508,7 @@ extern "C" int flk_pack_batch_sums(const float* per_clip, int B, float prob_scal
   return FLK_OK;
 }
 
-// ---- regulariser gradient + Adam: one workgroup, delta is [T,3] ----------------------------------
+// ---- regulariser gradient + Adam / projected sign-gradient step: one workgroup, delta is [T,3] ----------------------------------
 __device__ static inline float block_sum(float v, float* sh) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
@@ -528,15 +528,29 @@ __device__ static inline float block_max(float v, float* sh) {
 
 constexpr int ADAM_PER = 8;  // 256 threads x 8 >= 3*T  (T <= 682)
 
+// the optimiser that consumes g_tot (template argument of the update kernels: everything up to g_tot is one body)
+enum { OPT_ADAM = 0, OPT_PGD = 1 };
+// l-infinity PGD: clamp(d - alpha * sgn(g), -eps, +eps).  sgn(0) = 0 (the element stays); a NaN gradient gives a NaN delta like
+// torch.sign / torch.clamp do -- hence comparisons instead of fminf / fmaxf, which would swallow it.  alpha * s is exact (+-alpha, 0),
+// so the subtraction rounds once whether or not it is contracted to an fma.
+__device__ static inline float pgd_step(float d, float g, float alpha, float eps) {
+  const float s = g > 0.f ? 1.f : g < 0.f ? -1.f : g;      // g itself where it is +-0 or NaN
+  const float n = d - alpha * s;
+  return n < -eps ? -eps : n > eps ? eps : n;
+}
+
 // blockIdx.x = clip (flk_perturb_reg_adam_batched: B independent perturbations, each with its own Adam state, step counter and
 // "still attacking" flag, all on the device -- no host value changes between iterations, so the loop can be replayed as a graph)
+// OPT_PGD: m, v are not touched (NULL); the counter is still advanced for active clips (the drivers read it as iterations spent)
+template <int OPT>
 __global__ __launch_bounds__(256) void reg_adam_kernel(const flk_adam_args a, const float* g_adv, float* delta, float* m, float* v,
                                                        float* scalars, int* steps, const int* active, const float* dyn_dev) {
   __shared__ float sh[4];
   const int T = a.T, N = 3 * T;
   {
     const size_t o = (size_t)blockIdx.x * N;
-    g_adv += o; delta += o; m += o; v += o;
+    g_adv += o; delta += o;
+    if constexpr (OPT == OPT_ADAM) { m += o; v += o; }
     if (scalars) scalars += (size_t)blockIdx.x * 8;
   }
   const int step = steps ? steps[blockIdx.x] + 1 : a.step;        // 1-based step of THIS update
@@ -568,11 +582,15 @@ __global__ __launch_bounds__(256) void reg_adam_kernel(const flk_adam_args a, co
     float greg = a.beta1 * 2.f * x0 / N + a.beta2 * 2.f * (-l0) / N + a.beta3 * 2.f * (-2.f * l0 + lm + lp) / N;
     if (a.torch_dialect && !(raw >= -dyn && raw <= dyn)) greg = 0.f;   // clamp gradient, inclusive
     const float g = a.g_scale * g_adv[i] + a.beta0 * greg;
-    const float mi = a.adam_b1 * m[i] + (1.f - a.adam_b1) * g;
-    const float vi = a.adam_b2 * v[i] + (1.f - a.adam_b2) * g * g;
-    nm[k] = mi; nv[k] = vi;
-    if (a.torch_dialect) nd[k] = raw - (a.lr / bc1) * mi / (sqrtf(vi) / bc2s + a.adam_eps);   // torch-1.4 Adam
-    else nd[k] = raw - lr_tf * mi / (sqrtf(vi) + a.adam_eps);                                   // TF-1.15 AdamOptimizer
+    if constexpr (OPT == OPT_PGD) {
+      nd[k] = pgd_step(raw, g, a.lr, a.torch_dialect ? dyn : a.pgd_eps);
+    } else {
+      const float mi = a.adam_b1 * m[i] + (1.f - a.adam_b1) * g;
+      const float vi = a.adam_b2 * v[i] + (1.f - a.adam_b2) * g * g;
+      nm[k] = mi; nv[k] = vi;
+      if (a.torch_dialect) nd[k] = raw - (a.lr / bc1) * mi / (sqrtf(vi) / bc2s + a.adam_eps);   // torch-1.4 Adam
+      else nd[k] = raw - lr_tf * mi / (sqrtf(vi) + a.adam_eps);                                   // TF-1.15 AdamOptimizer
+    }
   }
   const float t_norm = block_sum(s_norm, sh), t_diff = block_sum(s_diff, sh), t_lap = block_sum(s_lap, sh);
   const float t_abs = block_sum(s_abs, sh), t_rough = block_sum(s_rough, sh);
@@ -583,7 +601,8 @@ __global__ __launch_bounds__(256) void reg_adam_kernel(const flk_adam_args a, co
     for (int k = 0; k < ADAM_PER; ++k) {
       const int i = threadIdx.x + 256 * k;
       if (i >= N) continue;
-      delta[i] = nd[k]; m[i] = nm[k]; v[i] = nv[k];
+      delta[i] = nd[k];
+      if constexpr (OPT == OPT_ADAM) { m[i] = nm[k]; v[i] = nv[k]; }
     }
     if (threadIdx.x == 0 && steps) steps[blockIdx.x] = step;
   }
@@ -600,7 +619,7 @@ extern "C" int flk_perturb_reg_adam(const flk_adam_args* a, const float* g_adv, 
   FLK_REQUIRE(a && g_adv && delta && m && v, "flk_perturb_reg_adam: null argument");
   FLK_REQUIRE(a->T > 0 && 3 * a->T <= 256 * ADAM_PER, "flk_perturb_reg_adam: T out of range (%d)", a->T);
   FLK_REQUIRE(a->step >= 1, "flk_perturb_reg_adam: step is 1-based");
-  FLK_LAUNCH_KERNEL(reg_adam_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, m, v, scalars, (int*)nullptr, (const int*)nullptr, (const float*)nullptr);
+  FLK_LAUNCH_KERNEL(reg_adam_kernel<OPT_ADAM>, dim3(1), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, m, v, scalars, (int*)nullptr, (const int*)nullptr, (const float*)nullptr);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -610,12 +629,37 @@ extern "C" int flk_perturb_reg_adam_batched(const flk_adam_args* a, int nclip, c
   FLK_REQUIRE(a && g_adv && delta && m && v && steps_dev, "flk_perturb_reg_adam_batched: null argument");
   FLK_REQUIRE(nclip > 0 && nclip < 65536, "flk_perturb_reg_adam_batched: bad clip count %d", nclip);
   FLK_REQUIRE(a->T > 0 && 3 * a->T <= 256 * ADAM_PER, "flk_perturb_reg_adam_batched: T out of range (%d)", a->T);
-  FLK_LAUNCH_KERNEL(reg_adam_kernel, dim3((unsigned)nclip), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, m, v, scalars, steps_dev, active_dev, dyn_max_norm_dev);
+  FLK_LAUNCH_KERNEL(reg_adam_kernel<OPT_ADAM>, dim3((unsigned)nclip), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, m, v, scalars, steps_dev, active_dev, dyn_max_norm_dev);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
 
-// ---- dense delta: L12 regulariser + Adam (kinetics_i3d_L12) ------------------------------------------------------------
+extern "C" int flk_perturb_reg_pgd(const flk_adam_args* a, const float* g_adv, float* delta, float* scalars, void* stream) {
+  FLK_REQUIRE(a && g_adv && delta, "flk_perturb_reg_pgd: null argument");
+  FLK_REQUIRE(a->T > 0 && 3 * a->T <= 256 * ADAM_PER, "flk_perturb_reg_pgd: T out of range (%d)", a->T);
+  const float eps = a->torch_dialect ? a->dyn_max_norm : a->pgd_eps;
+  FLK_REQUIRE(eps > 0.f, "flk_perturb_reg_pgd: the l-infinity radius (%s) must be positive (got %g)", a->torch_dialect ? "dyn_max_norm" : "pgd_eps", (double)eps);
+  FLK_LAUNCH_KERNEL(reg_adam_kernel<OPT_PGD>, dim3(1), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, (float*)nullptr, (float*)nullptr, scalars,
+                     (int*)nullptr, (const int*)nullptr, (const float*)nullptr);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_perturb_reg_pgd_batched(const flk_adam_args* a, int nclip, const float* g_adv, float* delta, int* steps_dev,
+                                           const int* active_dev, const float* dyn_max_norm_dev, float* scalars, void* stream) {
+  FLK_REQUIRE(a && g_adv && delta && steps_dev, "flk_perturb_reg_pgd_batched: null argument");
+  FLK_REQUIRE(nclip > 0 && nclip < 65536, "flk_perturb_reg_pgd_batched: bad clip count %d", nclip);
+  FLK_REQUIRE(a->T > 0 && 3 * a->T <= 256 * ADAM_PER, "flk_perturb_reg_pgd_batched: T out of range (%d)", a->T);
+  const float eps = a->torch_dialect ? a->dyn_max_norm : a->pgd_eps;      // (per-clip radii on the device replace dyn_max_norm)
+  FLK_REQUIRE(eps > 0.f || (a->torch_dialect && dyn_max_norm_dev), "flk_perturb_reg_pgd_batched: the l-infinity radius (%s) must be positive (got %g)",
+              a->torch_dialect ? "dyn_max_norm" : "pgd_eps", (double)eps);
+  FLK_LAUNCH_KERNEL(reg_adam_kernel<OPT_PGD>, dim3((unsigned)nclip), dim3(256), 0, (hipStream_t)stream, *a, g_adv, delta, (float*)nullptr, (float*)nullptr,
+                     scalars, steps_dev, active_dev, dyn_max_norm_dev);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// ---- dense delta: L12 regulariser + Adam / projected sign-gradient step (kinetics_i3d_L12) -----------------------------
 // d/d(delta_t) sqrt(mean_{hwc} delta_t^2) = delta_t / (N_f * sqrt(mean_t)),  N_f = H*W*3.
 constexpr int DENSE_CHUNKS = 64;     // workgroups per frame in the reduction pass
 
@@ -668,6 +712,8 @@ __global__ void dense_frame_finish(const float* part, int T, int frame_elems, fl
   }
 }
 
+// OPT_PGD: streams g_adv and delta in, delta out (16 bytes per lane over the contiguous frame, like the Adam form); m, v NULL
+template <int OPT>
 __global__ __launch_bounds__(256) void dense_adam_kernel(const flk_dense_adam_args a, int frame_elems, const float* frame_rms,
                                                          const float* g_adv, float* delta, float* m, float* v) {
   const int t = blockIdx.y;
@@ -680,7 +726,9 @@ __global__ __launch_bounds__(256) void dense_adam_kernel(const flk_dense_adam_ar
   const int n4 = frame_elems / 4;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n4; i += gridDim.x * 256) {
     const float4 d = ((const float4*)(delta + base))[i], g4 = ((const float4*)(g_adv + base))[i];
-    float4 mm = ((const float4*)(m + base))[i], vv = ((const float4*)(v + base))[i];
+    float4 mm, vv;
+    if constexpr (OPT == OPT_ADAM) { mm = ((const float4*)(m + base))[i]; vv = ((const float4*)(v + base))[i]; }
+    else mm = vv = make_float4(0.f, 0.f, 0.f, 0.f);
     float dd[4] = {d.x, d.y, d.z, d.w};
     const float gg[4] = {g4.x, g4.y, g4.z, g4.w};
     float mv[4] = {mm.x, mm.y, mm.z, mm.w}, vvv[4] = {vv.x, vv.y, vv.z, vv.w};
@@ -688,14 +736,20 @@ __global__ __launch_bounds__(256) void dense_adam_kernel(const flk_dense_adam_ar
     for (int k = 0; k < 4; ++k) {
       // d(L12)/d(delta) through the clamp: passes where |delta| <= dyn_max_norm (torch.clamp gradient, bounds inclusive)
       const float g = a.g_scale * gg[k] + ((a.dyn_max_norm > 0.f && fabsf(dd[k]) > a.dyn_max_norm) ? 0.f : rcoef * dd[k]);
-      mv[k] = a.adam_b1 * mv[k] + (1.f - a.adam_b1) * g;
-      vvv[k] = a.adam_b2 * vvv[k] + (1.f - a.adam_b2) * g * g;
-      dd[k] = a.torch_dialect ? dd[k] - (a.lr / bc1) * mv[k] / (sqrtf(vvv[k]) / bc2s + a.adam_eps)
-                              : dd[k] - lr_tf * mv[k] / (sqrtf(vvv[k]) + a.adam_eps);
+      if constexpr (OPT == OPT_PGD) {
+        dd[k] = pgd_step(dd[k], g, a.lr, a.torch_dialect ? a.dyn_max_norm : a.pgd_eps);
+      } else {
+        mv[k] = a.adam_b1 * mv[k] + (1.f - a.adam_b1) * g;
+        vvv[k] = a.adam_b2 * vvv[k] + (1.f - a.adam_b2) * g * g;
+        dd[k] = a.torch_dialect ? dd[k] - (a.lr / bc1) * mv[k] / (sqrtf(vvv[k]) / bc2s + a.adam_eps)
+                                : dd[k] - lr_tf * mv[k] / (sqrtf(vvv[k]) + a.adam_eps);
+      }
     }
     ((float4*)(delta + base))[i] = make_float4(dd[0], dd[1], dd[2], dd[3]);
-    ((float4*)(m + base))[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
-    ((float4*)(v + base))[i] = make_float4(vvv[0], vvv[1], vvv[2], vvv[3]);
+    if constexpr (OPT == OPT_ADAM) {
+      ((float4*)(m + base))[i] = make_float4(mv[0], mv[1], mv[2], mv[3]);
+      ((float4*)(v + base))[i] = make_float4(vvv[0], vvv[1], vvv[2], vvv[3]);
+    }
   }
 }
 
@@ -716,7 +770,25 @@ extern "C" int flk_perturb_dense_l12_adam(const flk_dense_adam_args* a, const fl
   FLK_LAUNCH_KERNEL(dense_frame_stats, dim3(DENSE_CHUNKS, a->T), dim3(256), 0, s, delta, fe, part,
                      a->dyn_max_norm > 0.f ? a->dyn_max_norm : INFINITY);
   FLK_LAUNCH_KERNEL(dense_frame_finish, dim3(1), dim3(1024), 0, s, part, a->T, fe, frame_rms, scalars);
-  FLK_LAUNCH_KERNEL(dense_adam_kernel, dim3(64, a->T), dim3(256), 0, s, *a, fe, frame_rms, g_adv, delta, m, v);
+  FLK_LAUNCH_KERNEL(dense_adam_kernel<OPT_ADAM>, dim3(64, a->T), dim3(256), 0, s, *a, fe, frame_rms, g_adv, delta, m, v);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_perturb_dense_l12_pgd(const flk_dense_adam_args* a, const float* g_adv, float* delta, float* scalars, float* scratch,
+                                         void* stream) {
+  FLK_REQUIRE(a && g_adv && delta && scratch, "flk_perturb_dense_l12_pgd: null argument");
+  FLK_REQUIRE(a->T > 0 && a->T <= 1024 && a->H > 0 && a->W > 0 && (a->H * a->W * 3) % 4 == 0, "flk_perturb_dense_l12_pgd: bad dims");
+  const float eps = a->torch_dialect ? a->dyn_max_norm : a->pgd_eps;
+  FLK_REQUIRE(eps > 0.f, "flk_perturb_dense_l12_pgd: the l-infinity radius (%s) must be positive (got %g)", a->torch_dialect ? "dyn_max_norm" : "pgd_eps", (double)eps);
+  const int fe = a->H * a->W * 3;
+  float* part = scratch;
+  float* frame_rms = scratch + (size_t)a->T * DENSE_CHUNKS * 4;
+  hipStream_t s = (hipStream_t)stream;
+  FLK_LAUNCH_KERNEL(dense_frame_stats, dim3(DENSE_CHUNKS, a->T), dim3(256), 0, s, delta, fe, part,
+                     a->dyn_max_norm > 0.f ? a->dyn_max_norm : INFINITY);
+  FLK_LAUNCH_KERNEL(dense_frame_finish, dim3(1), dim3(1024), 0, s, part, a->T, fe, frame_rms, scalars);
+  FLK_LAUNCH_KERNEL(dense_adam_kernel<OPT_PGD>, dim3(64, a->T), dim3(256), 0, s, *a, fe, frame_rms, g_adv, delta, (float*)nullptr, (float*)nullptr);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

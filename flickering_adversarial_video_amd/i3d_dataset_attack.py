@@ -40,11 +40,14 @@ ADAM_B1, ADAM_B2 = 0.9, 0.999        # tf.train.AdamOptimizer defaults (i3d_adve
 def checkpoint_tensors(eng, step, weights=None, with_global_step=False):
     """{variable name: array} of one reference-format checkpoint"""
     shp = tuple(eng.perturbation.shape)
-    t = {"RGB/eps": eng.perturbation.cpu().numpy().reshape(shp),
-         "RGB/eps/Adam": eng.adam_m.cpu().numpy().reshape(shp),
-         "RGB/eps/Adam_1": eng.adam_v.cpu().numpy().reshape(shp),
-         "beta1_power": np.array(ADAM_B1 ** eng.adam_t, np.float32),
-         "beta2_power": np.array(ADAM_B2 ** eng.adam_t, np.float32)}
+    t = {"RGB/eps": eng.perturbation.cpu().numpy().reshape(shp)}
+    if eng.optimizer == "pgd":           # no optimiser state: the perturbation and a marker variable naming the optimiser
+        t["pgd_steps"] = np.array(step, np.int64)
+    else:
+        t.update({"RGB/eps/Adam": eng.adam_m.cpu().numpy().reshape(shp),
+                  "RGB/eps/Adam_1": eng.adam_v.cpu().numpy().reshape(shp),
+                  "beta1_power": np.array(ADAM_B1 ** eng.adam_t, np.float32),
+                  "beta2_power": np.array(ADAM_B2 ** eng.adam_t, np.float32)})
     if with_global_step:
         t["global_step"] = np.array(step, np.int64)
     if weights:
@@ -52,10 +55,19 @@ def checkpoint_tensors(eng, step, weights=None, with_global_step=False):
     return t
 
 
+def check_checkpoint_optimizer(eng, ck_opt, where):
+    """a checkpoint resumes under the optimiser that wrote it (``ck_opt``: "adam" -- it carries the moments --, "pgd" -- it carries the
+    ``pgd_steps`` marker -- or None: a bare perturbation, e.g. CKPT_PATH_WITH_ZERO_PERT, accepted by both)"""
+    if ck_opt is not None and ck_opt != eng.optimizer:
+        raise ValueError(f"{where} was written with OPTIMIZER: {ck_opt} and cannot be resumed with OPTIMIZER: {eng.optimizer} "
+                         f"(adam checkpoints carry the moments RGB/eps/Adam*, pgd checkpoints none)")
+
+
 def restore(eng, prefix):
     """load (delta, Adam m, v, t) from a bundle written by ``checkpoint_tensors`` -- or by the reference itself.
-    The Adam step count is recovered from beta1_power = 0.9 ** t."""
-    ck = tf_checkpoint.read_bundle(prefix, names=lambda n: n.startswith("RGB/eps") or n in ("beta1_power", "beta2_power", "global_step"))
+    The Adam step count is recovered from beta1_power = 0.9 ** t.  A pgd bundle holds the perturbation and the ``pgd_steps`` marker: no optimiser state."""
+    ck = tf_checkpoint.read_bundle(prefix, names=lambda n: n.startswith("RGB/eps") or n in ("beta1_power", "beta2_power", "global_step", "pgd_steps"))
+    check_checkpoint_optimizer(eng, "adam" if "RGB/eps/Adam" in ck else "pgd" if "pgd_steps" in ck else None, prefix)
     eng.reset_perturbation(ck["RGB/eps"])
     if "RGB/eps/Adam" in ck:
         eng.adam_m.copy_(torch.from_numpy(np.ascontiguousarray(ck["RGB/eps/Adam"])).reshape(eng.adam_m.shape))
@@ -119,7 +131,8 @@ def main(default_section, argv=None):
         print(f"I3D weights: {wsrc}", flush=True)
     eng = FlickerI3D(W, batch_size=B, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, device=local_rank, dense_delta=dense,
                      cyclic_flag_default_c=float(bool(c.CYCLIC_ATTACK)),
-                     cyclic_pert_flag_default_c=float(bool(c.get("CYCLIC_PERTURBATION_ATTACK", False))))
+                     cyclic_pert_flag_default_c=float(bool(c.get("CYCLIC_PERTURBATION_ATTACK", False))),
+                     optimizer=c.OPTIMIZER, pgd_eps=c.PGD_EPS if c.OPTIMIZER == "pgd" else None)
     train_files = tio.list_tfrecords(c.TF_RECORDS_TRAIN_PATH, c.get("NUM_OF_TRAIN_TF_RECORDS"))
     val_files = tio.list_tfrecords(c.TF_RECORDS_VAL_PATH, c.get("NUM_OF_VAL_TF_RECORDS"))
     if not train_files:
@@ -158,9 +171,12 @@ def main(default_section, argv=None):
             print(f"resumed from {last[1]} at step {step}", flush=True)
     elif old:
         ck = np.load(old[-1])
+        check_checkpoint_optimizer(eng, "adam" if "m" in ck else None, old[-1])
         eng.reset_perturbation(ck["delta"])
-        eng.adam_m.copy_(torch.from_numpy(ck["m"]).reshape(eng.adam_m.shape)); eng.adam_v.copy_(torch.from_numpy(ck["v"]).reshape(eng.adam_v.shape))
-        eng.adam_t, step = int(ck["t"]), int(ck["step"])
+        if "m" in ck:
+            eng.adam_m.copy_(torch.from_numpy(ck["m"]).reshape(eng.adam_m.shape)); eng.adam_v.copy_(torch.from_numpy(ck["v"]).reshape(eng.adam_v.shape))
+            eng.adam_t = int(ck["t"])
+        step = int(ck["step"])
         if rank == 0:
             print(f"resumed from {old[-1]} at step {step}", flush=True)
     if world > 1:

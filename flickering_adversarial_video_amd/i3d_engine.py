@@ -71,6 +71,14 @@ class StepResult(dict):
 
 
 RESULT_SLOTS = 4
+OPTIMIZERS = ("adam", "pgd")
+
+
+def check_optimizer(name):
+    """the optimiser keyword of the engines: "adam" (the reference's) or "pgd" (projected sign-gradient, l-infinity)"""
+    if name not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {name!r}")
+    return name
 
 
 class FlickerI3D:
@@ -80,17 +88,32 @@ class FlickerI3D:
     ``batch_size``, ``cyclic_flag_default_c``, ``cyclic_pert_flag_default_c``, ``default_adv_flag_c``;
     ``weights`` replaces ``ckpt_path`` (a {checkpoint variable name: ndarray} dict, see i3d_spec.py) and
     ``frames`` / ``dtype`` are new optional knobs (defaults reproduce the reference: 90 frames).
+
+    ``optimizer="pgd"`` replaces Adam by the projected sign-gradient step ``delta <- clamp(delta - lr * sgn(g), +-pgd_eps)``
+    (``lr`` is the step size alpha; ``pgd_eps`` defaults to 0.4, the apply clip of kinetics_i3d_utils.py:104, and is required for
+    the dense perturbation, which has no apply clip).  It keeps no state: there are no moment buffers (``adam_m`` / ``adam_v`` are
+    None).  Data-parallel: the sign is taken after the all-reduce, so every rank takes the identical step.
     """
 
     def __init__(self, weights, batch_size=1, frames=SAMPLE_VIDEO_FRAMES, dtype="bf16", device=0, dense_delta=False,
                  cyclic_flag_default_c=0.0, cyclic_pert_flag_default_c=0.0, default_adv_flag_c=1.0, process_group=None,
-                 seed=0, kinetics_classes=None, per_clip_delta=False):
+                 seed=0, kinetics_classes=None, per_clip_delta=False, optimizer="adam", pgd_eps=None):
+        self.optimizer = check_optimizer(optimizer)
         if not torch.cuda.is_available():
             raise RuntimeError("FlickerI3D needs an MI355X (HIP) device; there is no CPU fallback")
         torch.cuda.set_device(device)
         self.B, self.T, self.H, self.W = batch_size, frames, IMAGE_SIZE, IMAGE_SIZE
         self.dtype = dtype
         self.dense = dense_delta
+        self.pgd = optimizer == "pgd"
+        if pgd_eps is not None and not self.pgd:
+            raise ValueError("pgd_eps is the radius of optimizer='pgd'")
+        if self.pgd:
+            if pgd_eps is None and dense_delta:
+                raise ValueError("optimizer='pgd' with a dense perturbation needs pgd_eps (it has no apply clip to take the radius from)")
+            self.pgd_eps = 0.4 if pgd_eps is None else float(pgd_eps)
+            if not self.pgd_eps > 0:
+                raise ValueError(f"pgd_eps must be positive, got {pgd_eps!r}")
         # per_clip_delta: B INDEPENDENT single-video attacks in one batch (the reference runs them one after another,
         # i3d_adversarial_main_single_video_npy.py:103-337): eps_rgb, the Adam state, the step counter and the "still attacking" flag
         # are per clip; clip b follows exactly the trajectory it would follow alone (bit for bit in fp32).  Replicas only: no collective.
@@ -105,10 +128,10 @@ class FlickerI3D:
         dshape = (self.T, self.H, self.W, 3) if dense_delta else (self.B, self.T, 3) if self.per_clip else (self.T, 3)
         # eps_rgb: zeros [T,1,1,3] (kinetics_i3d_utils.py:100); dense L12 variant: 1e-8 (:333)
         self.eps_rgb = torch.full(dshape, 1e-8 if dense_delta else 0.0, dtype=torch.float32, device=dev)
-        self.adam_m, self.adam_v = torch.zeros_like(self.eps_rgb), torch.zeros_like(self.eps_rgb)
+        self.adam_m, self.adam_v = (None, None) if self.pgd else (torch.zeros_like(self.eps_rgb), torch.zeros_like(self.eps_rgb))
         self.adam_t = 0
         if self.per_clip:
-            self.adam_steps = torch.zeros(self.B, dtype=torch.int32, device=dev)      # Adam step counters, advanced by the kernel
+            self.adam_steps = torch.zeros(self.B, dtype=torch.int32, device=dev)      # per-clip step counters, advanced by the kernel
             self.active = torch.ones(self.B, dtype=torch.int32, device=dev)           # 0: this clip's attack has ended (frozen)
         self._xs2d = torch.empty((self.B, self.T // 2, self.H // 2, self.W // 2, 32), dtype=self.net_torch_dtype, device=dev)
         self._gx = torch.empty_like(self._xs2d)
@@ -154,8 +177,9 @@ class FlickerI3D:
             self.eps_rgb[b].zero_()
         else:
             self.eps_rgb[b].copy_(torch.as_tensor(delta, dtype=torch.float32).reshape(self.T, 3))
-        self.adam_m[b].zero_()
-        self.adam_v[b].zero_()
+        if not self.pgd:
+            self.adam_m[b].zero_()
+            self.adam_v[b].zero_()
         self.adam_steps[b] = 0
         self.active[b] = 1
 
@@ -168,8 +192,9 @@ class FlickerI3D:
             self.eps_rgb.fill_(1e-8 if self.dense else 0.0)
         else:
             self.eps_rgb.copy_(torch.as_tensor(delta, dtype=torch.float32).reshape(self.eps_rgb.shape))
-        self.adam_m.zero_()
-        self.adam_v.zero_()
+        if not self.pgd:
+            self.adam_m.zero_()
+            self.adam_v.zero_()
         self.adam_t = 0
 
     @property
@@ -285,8 +310,12 @@ class FlickerI3D:
         if update:
             self.adam_t += 1
             sc = slot["scalars"]
-            ops.perturb_reg_adam(red[:n], self.eps_rgb, self.adam_m, self.adam_v, self.adam_t, dialect="tf", beta0=beta0,
-                                 beta1=beta1, beta2=beta2, beta3=beta3, lr=lr, scalars=sc)
+            if self.pgd:
+                ops.perturb_reg_pgd(red[:n], self.eps_rgb, dialect="tf", beta0=beta0, beta1=beta1, beta2=beta2, beta3=beta3, lr=lr,
+                                    eps=self.pgd_eps, scalars=sc)
+            else:
+                ops.perturb_reg_adam(red[:n], self.eps_rgb, self.adam_m, self.adam_v, self.adam_t, dialect="tf", beta0=beta0,
+                                     beta1=beta1, beta2=beta2, beta3=beta3, lr=lr, scalars=sc)
             res.update(reg_loss=sc[0], norm_reg=sc[1], diff_norm_reg=sc[2], laplacian_norm_reg=sc[3], thickness=sc[4],
                        roughness=sc[5], pert_max=sc[6], pert_min=sc[7], _reg_weight=beta0)
         self.last_result = res
@@ -322,8 +351,12 @@ class FlickerI3D:
         res["is_adversarial"] = (am == labels) if targeted else (am != labels)          # per clip
         if update:
             sc = slot["scalars"]
-            ops.perturb_reg_adam_batched(g, self.eps_rgb, self.adam_m, self.adam_v, self.adam_steps, self.active, dialect="tf", beta0=beta0,
-                                         beta1=beta1, beta2=beta2, beta3=beta3, lr=lr, scalars=sc)
+            if self.pgd:
+                ops.perturb_reg_pgd_batched(g, self.eps_rgb, self.adam_steps, self.active, dialect="tf", beta0=beta0, beta1=beta1, beta2=beta2,
+                                            beta3=beta3, lr=lr, eps=self.pgd_eps, scalars=sc)
+            else:
+                ops.perturb_reg_adam_batched(g, self.eps_rgb, self.adam_m, self.adam_v, self.adam_steps, self.active, dialect="tf", beta0=beta0,
+                                             beta1=beta1, beta2=beta2, beta3=beta3, lr=lr, scalars=sc)
             res.update(reg_loss=sc[:, 0], norm_reg=sc[:, 1], diff_norm_reg=sc[:, 2], laplacian_norm_reg=sc[:, 3], thickness=sc[:, 4],
                        roughness=sc[:, 5], pert_max=sc[:, 6], pert_min=sc[:, 7], _reg_weight=beta0)
         self.last_result = res
@@ -351,8 +384,11 @@ class FlickerI3D:
         res["is_adversarial"] = (res["argmax"] == labels).all() if targeted else (res["argmax"] != labels).all()
         if update:
             self.adam_t += 1
-            sc = ops.perturb_dense_l12_adam(self._gdense, self.eps_rgb, self.adam_m, self.adam_v, self.adam_t, dialect="tf", beta=beta0 * beta1,
-                                            lr=lr).clone()
+            if self.pgd:
+                sc = ops.perturb_dense_l12_pgd(self._gdense, self.eps_rgb, dialect="tf", beta=beta0 * beta1, lr=lr, eps=self.pgd_eps).clone()
+            else:
+                sc = ops.perturb_dense_l12_adam(self._gdense, self.eps_rgb, self.adam_m, self.adam_v, self.adam_t, dialect="tf", beta=beta0 * beta1,
+                                                lr=lr).clone()
             res.update(reg_loss=beta1 * sc[0], L12=sc[0], thickness=sc[1], roughness=sc[2], pert_max=sc[3],
                        total_loss=res["adv_loss"] + beta0 * beta1 * sc[0], thickness_relative=sc[1] / 2 * 100, roughness_relative=sc[2] / 2 * 100)
         return res

@@ -399,6 +399,61 @@ def perturb_dense_l12_adam(g_adv, delta, m, v, step, *, dialect="tf", beta=1.0, 
     return scalars
 
 
+def _pgd_args(T, dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps):
+    a = AdamArgs()
+    a.T = T
+    a.torch_dialect = int(dialect == "torch")
+    a.beta0, a.beta1, a.beta2, a.beta3 = beta0, beta1, beta2, beta3
+    a.dyn_max_norm, a.g_scale, a.lr = dyn_max_norm, g_scale, lr
+    a.pgd_eps = float(eps)
+    return a
+
+
+def perturb_reg_pgd(g_adv, delta, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0.5, beta3=0.5, dyn_max_norm=0.0, g_scale=1.0, lr=1e-3,
+                    eps=0.0, scalars=None):
+    """projected sign-gradient step on the flicker delta [T,3]: delta <- clamp(delta - lr * sgn(g_tot), +-radius), g_tot formed as
+    perturb_reg_adam forms it.  Radius: ``eps`` (TF dialect) or ``dyn_max_norm`` (torch dialect).  Returns the 8 scalars of the
+    pre-update delta."""
+    a = _pgd_args(delta.shape[0], dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps)
+    if scalars is None:
+        scalars = torch.empty(8, dtype=torch.float32, device="cuda")
+    check(load().flk_perturb_reg_pgd(C.byref(a), ptr(g_adv), ptr(delta), ptr(scalars), stream_ptr()))
+    return scalars
+
+
+def perturb_reg_pgd_batched(g_adv, delta, steps, active=None, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0.5, beta3=0.5, dyn_max_norm=0.0,
+                            g_scale=1.0, lr=1e-3, eps=0.0, scalars=None, dyn_max_norm_dev=None):
+    """B independent perturbations [B,T,3] under the projected sign-gradient step; ``steps`` (int32 [B]) is advanced for the clips with
+    ``active[b] != 0``, the others are frozen.  Returns scalars [B,8] of the pre-update perturbations."""
+    B, T, _ = delta.shape
+    assert steps.dtype == torch.int32 and steps.shape == (B,) and steps.is_cuda and (active is None or (active.dtype == torch.int32 and active.shape == (B,)))
+    for t in (g_adv, delta):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * T * 3
+    a = _pgd_args(T, dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps)
+    if scalars is None:
+        scalars = torch.empty((B, 8), dtype=torch.float32, device="cuda")
+    assert dyn_max_norm_dev is None or (dyn_max_norm_dev.dtype == torch.float32 and dyn_max_norm_dev.shape == (B,) and dyn_max_norm_dev.is_cuda)
+    check(load().flk_perturb_reg_pgd_batched(C.byref(a), B, ptr(g_adv), ptr(delta), ptr(steps), ptr(active), ptr(dyn_max_norm_dev),
+                                             ptr(scalars), stream_ptr()))
+    return scalars
+
+
+def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, lr=1e-3, eps=0.0, scalars=None, scratch=None, dyn_max_norm=0.0):
+    """dense delta [T,H,W,3]: L12 regulariser gradient + projected sign-gradient step; radius ``eps`` (TF dialect, required) or
+    ``dyn_max_norm`` (torch dialect).  Returns scalars {L12, thickness, roughness, max} of the pre-update delta."""
+    T, H, W, _ = delta.shape
+    a = DenseAdamArgs()
+    a.T, a.H, a.W, a.torch_dialect = T, H, W, int(dialect == "torch")
+    a.beta, a.g_scale, a.lr = beta, g_scale, lr
+    a.dyn_max_norm, a.pgd_eps = float(dyn_max_norm), float(eps)
+    if scalars is None:
+        scalars = torch.empty(4, dtype=torch.float32, device="cuda")
+    if scratch is None:
+        scratch = torch.empty(load().flk_dense_adam_scratch_bytes(T, H, W) // 4, dtype=torch.float32, device="cuda")
+    check(load().flk_perturb_dense_l12_pgd(C.byref(a), ptr(g_adv), ptr(delta), ptr(scalars), ptr(scratch), stream_ptr()))
+    return scalars
+
+
 def pack_batch_sums(per_clip, prob_scale, out3):
     """out3 = [sum loss_b, prob_scale * sum p_label, prob_scale * sum p_max_other] from softmax_adv_loss's per-clip table"""
     assert per_clip.dtype == torch.float32 and per_clip.is_contiguous() and per_clip.shape[1] == 4 and out3.dtype == torch.float32

@@ -252,7 +252,12 @@ class FlickerVideoResNet:
     when given, must agree with it (a fine-tuned victim brings its own ``fc``, model.py:436-437)."""
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
-                 cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False):
+                 cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam"):
+        from .i3d_engine import check_optimizer
+        # "pgd": delta <- clamp(delta - lr * sgn(g), +-dynamic_max_norm) instead of torch Adam (model.py:868) -- the radius is the clamp
+        # bound the perturbation already has, so the restart schedule (model.py:1061-1066) widens it; no optimiser state
+        self.optimizer = check_optimizer(optimizer)
+        self.pgd = optimizer == "pgd"
         if base_model in ARCH_CODES:
             arch, name = base_model, base_model
         else:
@@ -292,8 +297,8 @@ class FlickerVideoResNet:
         self._red = torch.zeros(parallel.payload_size(self.T), dtype=torch.float32, device=dev)
         self._scratch = torch.empty(max(1, ops.load().flk_perturb_grad_scratch_bytes(self.B, self.T, self.H, self.W) // 4), dtype=torch.float32, device=dev)
         self._scalars = torch.empty(8, dtype=torch.float32, device=dev)
-        self.adam_m = torch.zeros(self.pert_model._dev_shape, device=dev)
-        self.adam_v = torch.zeros(self.pert_model._dev_shape, device=dev)
+        self.adam_m = None if self.pgd else torch.zeros(self.pert_model._dev_shape, device=dev)
+        self.adam_v = None if self.pgd else torch.zeros(self.pert_model._dev_shape, device=dev)
         self.adam_t = 0      # the reference keeps ONE Adam instance across videos: not reset by init_perturbation
         if self.per_clip:
             self.adam_steps = torch.zeros(self.B, dtype=torch.int32, device=dev)
@@ -361,9 +366,13 @@ class FlickerVideoResNet:
             self.adam_t += 1
             b1 = criterion.beta_1
             sc = slot["scalars"]
-            ops.perturb_reg_adam(red[:n], self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_t, dialect="torch",
-                                 beta0=criterion.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1,
-                                 dyn_max_norm=self.pert_model.dynamic_max_norm, lr=lr, scalars=sc)
+            if self.pgd:
+                ops.perturb_reg_pgd(red[:n], self.pert_model.perturbation, dialect="torch", beta0=criterion.lambda_, beta1=b1, beta2=1 - b1,
+                                    beta3=1 - b1, dyn_max_norm=self.pert_model.dynamic_max_norm, lr=lr, scalars=sc)
+            else:
+                ops.perturb_reg_adam(red[:n], self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_t, dialect="torch",
+                                     beta0=criterion.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1,
+                                     dyn_max_norm=self.pert_model.dynamic_max_norm, lr=lr, scalars=sc)
             res.update(reg_loss=sc[0], _reg_weight=criterion.lambda_, _thickness=sc[4], _roughness=sc[5])
         else:
             res.update(reg_loss=criterion.regularization_loss(self.pert_model.get_perturbation()[0]), _reg_weight=criterion.lambda_)
@@ -394,9 +403,14 @@ class FlickerVideoResNet:
         if update:
             b1 = criterion.beta_1
             sc = slot["scalars"]
-            ops.perturb_reg_adam_batched(g, self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_steps, self.active, dialect="torch",
-                                         beta0=criterion.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1, lr=lr, scalars=sc,
-                                         dyn_max_norm_dev=self.pert_model.dyn_max_norm_dev)
+            if self.pgd:
+                ops.perturb_reg_pgd_batched(g, self.pert_model.perturbation, self.adam_steps, self.active, dialect="torch",
+                                            beta0=criterion.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1, lr=lr, scalars=sc,
+                                            dyn_max_norm_dev=self.pert_model.dyn_max_norm_dev)
+            else:
+                ops.perturb_reg_adam_batched(g, self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_steps, self.active, dialect="torch",
+                                             beta0=criterion.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1, lr=lr, scalars=sc,
+                                             dyn_max_norm_dev=self.pert_model.dyn_max_norm_dev)
             res.update(reg_loss=sc[:, 0], _thickness=sc[:, 4], _roughness=sc[:, 5])
         else:
             pc_ = self.pert_model.clamp_perturbation()
@@ -422,8 +436,12 @@ class FlickerVideoResNet:
                          _targeted=bool(criterion.targeted), _reg_weight=criterion.lambda_)
         if update:
             self.adam_t += 1
-            sc = ops.perturb_dense_l12_adam(self._gdense, self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_t, dialect="torch",
-                                            beta=criterion.lambda_, lr=lr, dyn_max_norm=self.pert_model.dynamic_max_norm).clone()
+            if self.pgd:
+                sc = ops.perturb_dense_l12_pgd(self._gdense, self.pert_model.perturbation, dialect="torch", beta=criterion.lambda_, lr=lr,
+                                               dyn_max_norm=self.pert_model.dynamic_max_norm).clone()
+            else:
+                sc = ops.perturb_dense_l12_adam(self._gdense, self.pert_model.perturbation, self.adam_m, self.adam_v, self.adam_t, dialect="torch",
+                                                beta=criterion.lambda_, lr=lr, dyn_max_norm=self.pert_model.dynamic_max_norm).clone()
             res.update(reg_loss=sc[0], _thickness=sc[1], _roughness=sc[2])
         else:
             res.update(reg_loss=criterion.L12_regularization_loss(self.pert_model.get_perturbation()[0]))
@@ -563,8 +581,10 @@ class FlickerVideoResNet:
                     os.makedirs(model_dir, exist_ok=True)
                     np.save(dest, None)
                 self.pert_model.init_clip(b, (rng.random(self.pert_model.size, dtype=np.float32) * 2 - 1) * 0.005)     # model.py:938-947
-                if reset_optimizer_per_video:
-                    self.adam_m[b].zero_(); self.adam_v[b].zero_(); self.adam_steps[b] = 0
+                if reset_optimizer_per_video:                # (pgd keeps no moments: only the counter is reset)
+                    if not self.pgd:
+                        self.adam_m[b].zero_(); self.adam_v[b].zero_()
+                    self.adam_steps[b] = 0
                 self.active[b] = 1
                 x[b].copy_(inputs[0])
                 labels[b] = int(target[0])
@@ -656,7 +676,9 @@ class FlickerVideoResNet:
             self.pert_model.init_perturbation(((rng.random(self.pert_model.size, dtype=np.float32) * 2 - 1) * 0.005))
             self.pert_model.dynamic_max_norm = self.pert_model.max_norm
             if reset_optimizer_per_video:                       # (the reference carries ONE Adam state from video to video, SURVEY D.5: default)
-                self.adam_m.zero_(); self.adam_v.zero_(); self.adam_t = 0
+                if not self.pgd:                                # (pgd keeps no state between videos: nothing to reset)
+                    self.adam_m.zero_(); self.adam_v.zero_()
+                self.adam_t = 0
             res = self.fit_single_video_attack(inputs, target, criterion, lr=lr, n_iter=n_iter, targeted_attack=targeted_attack,
                                                target_class_id=target_class_id, **kw)
             out[str(name)] = res
@@ -675,7 +697,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None):
+                 process_group=None, optimizer="adam"):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -688,6 +710,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
             batch_size = getattr(dataset, "batch_size", 1)
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
-                         process_group=process_group, attack_type=attack_type)
+                         process_group=process_group, attack_type=attack_type, optimizer=optimizer)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -284,6 +284,7 @@ typedef struct {
   float g_scale;             /* multiplies g_adv (1/(global batch) for mean losses) */
   float lr, adam_b1, adam_b2, adam_eps;
   int step;                  /* 1-based Adam step of THIS update */
+  float pgd_eps;             /* flk_perturb_reg_pgd* only, TF dialect: the l-infinity radius (torch dialect: dyn_max_norm is the radius) */
 } flk_adam_args;
 int flk_perturb_reg_adam(const flk_adam_args* a, const float* g_adv, float* delta, float* m, float* v,
                          float* scalars, void* stream);
@@ -295,6 +296,23 @@ int flk_perturb_reg_adam(const flk_adam_args* a, const float* g_adv, float* delt
  * Per clip the arithmetic is exactly flk_perturb_reg_adam's. */
 int flk_perturb_reg_adam_batched(const flk_adam_args* a, int nclip, const float* g_adv, float* delta, float* m, float* v,
                                  int* steps_dev, const int* active_dev, const float* dyn_max_norm_dev, float* scalars, void* stream);
+
+/* Regulariser gradient + projected sign-gradient (l-infinity PGD) step on the flicker delta: the update BASELINE.json's north star
+ * names beside Adam (the reference optimises with Adam only, i3d_adversarial_main_single_video_npy.py:79-84 / model.py:868; this is
+ * the baseline attack its comparisons are run against).  g_tot = g_scale * g_adv + beta0 * d(reg)/d(delta) is formed by the SAME
+ * code as flk_perturb_reg_adam (TF dialect: regulariser of the raw delta; torch dialect: of the clamped one, zero outside the clamp), then
+ *   delta' = clamp(delta - lr * sgn(g_tot), -eps, +eps)      in fp32; sgn(0) = 0 (the element does not move); NaN stays NaN
+ * with eps = dyn_max_norm (torch dialect: the clamp of model.py:1078, so the restart schedule of model.py:1061-1066 widens the
+ * projection with it) or pgd_eps (TF dialect; 0.4 = the apply clip of kinetics_i3d_utils.py:104 makes raw and clipped delta
+ * coincide); eps <= 0 is FLK_EINVAL.  No optimiser state; adam_b1 / adam_b2 / adam_eps / step are ignored.  scalars[8] as
+ * flk_perturb_reg_adam writes them (bitwise, for the same delta).  One launch, deterministic. */
+int flk_perturb_reg_pgd(const flk_adam_args* a, const float* g_adv, float* delta, float* scalars, void* stream);
+/* The same step for nclip INDEPENDENT perturbations (delta, g_adv: [nclip,T,3]; scalars: [nclip,8]), the sibling of
+ * flk_perturb_reg_adam_batched: clips with active_dev[b] == 0 keep delta and counter (scalars still written); steps_dev[b] is advanced
+ * for active clips ("iterations spent on this video" -- it does not enter the arithmetic); dyn_max_norm_dev (torch dialect) holds
+ * one radius per clip or is NULL.  Per clip the arithmetic is exactly flk_perturb_reg_pgd's. */
+int flk_perturb_reg_pgd_batched(const flk_adam_args* a, int nclip, const float* g_adv, float* delta, int* steps_dev,
+                                const int* active_dev, const float* dyn_max_norm_dev, float* scalars, void* stream);
 
 /* Dense-delta ("sparse adversarial perturbations" baseline, kinetics_i3d_L12, kinetics_i3d_utils.py:308-521): delta is
  * [T,H,W,3] (init 1e-8, no +-0.4 clip), regulariser L12 = sum_t sqrt(mean_{hwc} delta_t^2) + 1e-12 (:409; torch dialect
@@ -311,10 +329,19 @@ typedef struct {
   int step;
   float dyn_max_norm;        /* > 0 (torch dialect): L12 is taken on clamp(delta, +-dyn_max_norm), as Losses receives the CLAMPED
                               * perturbation (model.py:1078,211-214); its gradient vanishes where |delta| > dyn_max_norm.  0: raw delta */
+  float pgd_eps;             /* flk_perturb_dense_l12_pgd only, TF dialect: the l-infinity radius (torch dialect: dyn_max_norm) */
 } flk_dense_adam_args;
 int64_t flk_dense_adam_scratch_bytes(int T, int H, int W);
 int flk_perturb_dense_l12_adam(const flk_dense_adam_args* a, const float* g_adv, float* delta, float* m, float* v,
                                float* scalars, float* scratch, void* stream);
+/* The dense delta under the projected sign-gradient step (the standard l-infinity video PGD attack next to the kinetics_i3d_L12
+ * baseline, kinetics_i3d_utils.py:308-521): the two reduction passes of flk_perturb_dense_l12_adam, then ONE streaming pass
+ *   delta' = clamp(delta - lr * sgn(g_scale * g_adv + d(beta * L12)/d(delta)), -eps, +eps)
+ * reading g_adv and delta and writing delta (3 fp32 streams = 115 MB at T=64; no m, v).  eps = dyn_max_norm (torch dialect) or
+ * pgd_eps (TF dialect: this form has no apply clip, kinetics_i3d_utils.py:333, so the radius is required); eps <= 0 is FLK_EINVAL.
+ * sgn(0) = 0, NaN stays NaN.  scalars[4] and scratch as flk_perturb_dense_l12_adam; adam_b1 / adam_b2 / adam_eps / step are ignored. */
+int flk_perturb_dense_l12_pgd(const flk_dense_adam_args* a, const float* g_adv, float* delta, float* scalars, float* scratch,
+                              void* stream);
 
 /* Loss head: softmax + adversarial loss + d(loss)/d(logits) (kinetics_i3d_utils.py:152-169,253-307;
  * model.py:177-250).  per_clip[b*4..] = {loss_b, label_prob, max_non_label_prob, argmax}. */

@@ -194,8 +194,10 @@ def main():
     os.makedirs(c.PKL_RESULT_PATH, exist_ok=True)
     target_id = classes.index(c.TARGETED_CLASS) if c.TARGETED_ATTACK else None
     max_steps = a.max_steps if a.max_steps is not None else c.MAX_NUM_STEP
+    # [new] OPTIMIZER: pgd -- projected sign-gradient steps of radius PGD_EPS instead of Adam
+    opt = dict(optimizer=c.OPTIMIZER, pgd_eps=c.PGD_EPS if c.OPTIMIZER == "pgd" else None)
     if a.batch > 1:
-        eng = FlickerI3D(W, batch_size=a.batch, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, per_clip_delta=True)
+        eng = FlickerI3D(W, batch_size=a.batch, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, per_clip_delta=True, **opt)
         meta = {}
 
         def videos():
@@ -215,7 +217,7 @@ def main():
                 pickle.dump(res, f)
             print(f"{path}: class {cls!r} ({label_id}) -> {out}  ({res['total_steps']} steps, thickness {res['fatness']:.2f}% roughness {res['smoothness']:.2f}%)", flush=True)
         return
-    eng = FlickerI3D(W, batch_size=1, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE)
+    eng = FlickerI3D(W, batch_size=1, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, **opt)
     for path in sorted(glob.glob(os.path.join(c.NPY_PATH, "*.npy"))):
         cls, label_id = cfgmod.label_from_npy_name(path, classes)
         clip = np.load(path)[0, -T:][None].astype(np.float32)          # reference :121

@@ -43,12 +43,15 @@ def main():
     ap.add_argument("--n-iter", type=int, default=N_ITER)
     ap.add_argument("--restart-after", type=int, default=3000)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "pgd"], help="pgd: projected sign-gradient steps, delta <- clamp(delta - "
+                    "lr * sgn(grad), +-clamp bound), instead of Adam (model.py:868); the restart schedule grows the radius with the clamp bound")
     ap.add_argument("--batch", type=int, default=1, help="videos attacked at once, each with its own perturbation / clamp bound / Adam state "
                     "(flickering attack; 1 = the reference's one-by-one loop)")
     ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
                     "uint8 copy (default), or on the host into float32 (float32 files always take the host route)")
     ap.add_argument("--reset-optimizer-per-video", action="store_true", help="fresh Adam state for every video (the reference carries one "
-                    "state from video to video, model.py:946; with --batch > 1 the carried state is per batch slot)")
+                    "state from video to video, model.py:946; with --batch > 1 the carried state is per batch slot; --optimizer pgd keeps no "
+                    "state, so there is nothing to reset)")
     a = ap.parse_args()
     z = np.load(a.videos_npz, allow_pickle=True)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
@@ -65,7 +68,8 @@ def main():
     arch, _, ncls = vs.resolve_model(a.base_model, clips.shape[1])
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=clips.shape[2], dtype=a.dtype,
-                                 l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1)
+                                 l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
+                                 optimizer=a.optimizer)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -96,6 +96,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=BATCH_SIZE)
     ap.add_argument("--lr", type=float, default=LR)
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
+    ap.add_argument("--optimizer", default="adam", choices=["adam", "pgd"], help="pgd: projected sign-gradient steps, delta <- clamp(delta - "
+                    "lr * sgn(grad), +-l_inf norm), instead of Adam (model.py:868); --lr is the step size and StepLR scales it")
     ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
                     "uint8 copy (default), or on the host with a float32 copy per step (float32 files always take the host route)")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
@@ -117,7 +119,8 @@ def main():
     arch, _, ncls = vs.resolve_model(a.base_model, T)
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
-                                 device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type)
+                                 device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
+                                 optimizer=a.optimizer)
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     start_epoch = 1
