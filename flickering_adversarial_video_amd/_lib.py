@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get("FLK_LIB_PATH") or os.path.join(HERE, "libflicker_hip.
 
 FLK_F32, FLK_BF16 = 0, 1
 FLK_NET_I3D, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18, FLK_NET_MC3_18, FLK_NET_R2PLUS1D_34 = 0, 1, 2, 3, 4
+FLK_PREP_MAX_CLIPS = 64      # clips per flk_clip_prepare launch
 
 
 class FlickerHipError(RuntimeError):
@@ -74,6 +75,16 @@ class LossArgs(C.Structure):
                 ("use_logits", C.c_int), ("targeted", C.c_int), ("margin", C.c_float), ("mean_scale", C.c_float)]
 
 
+class PrepClip(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("T", C.c_int), ("Hs", C.c_int), ("Ws", C.c_int), ("pitch_t", C.c_int64), ("pitch_h", C.c_int64),
+                ("Hr", C.c_int), ("Wr", C.c_int), ("step_h", C.c_float), ("step_w", C.c_float), ("crop_i", C.c_int), ("crop_j", C.c_int)]
+
+
+class PrepareArgs(C.Structure):
+    _fields_ = [("nclip", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("mean", C.c_float * 3), ("std", C.c_float * 3),
+                ("out_clip_offset", C.c_int64), ("out_clip_stride", C.c_int64), ("clips", C.POINTER(PrepClip))]
+
+
 _SIGS = {
     "flk_version": (C.c_int, []),
     "flk_last_error": (C.c_char_p, []),
@@ -94,6 +105,7 @@ _SIGS = {
     "flk_perturb_apply_s2d": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p]),
     "flk_perturb_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_pack_batch_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

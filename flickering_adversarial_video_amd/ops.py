@@ -1,6 +1,7 @@
 """Thin host-side wrappers over the C ABI (include/flicker_hip.h): torch tensors are used for device
 memory and streams only; every computation happens in libflicker_hip.so."""
 import ctypes as C
+import functools
 import json
 import weakref
 
@@ -8,8 +9,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, LossArgs, PoolArgs, check, dtype_code, load, ptr,
-                   stream_ptr, torch_dtype)
+from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, LossArgs, PoolArgs, PrepareArgs,
+                   PrepClip, check, dtype_code, load, ptr, stream_ptr, torch_dtype)
+from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, prepare_geometry
 
 
 def same_pad(n, k, s):
@@ -452,6 +454,76 @@ def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, 
         scratch = torch.empty(load().flk_dense_adam_scratch_bytes(T, H, W) // 4, dtype=torch.float32, device="cuda")
     check(load().flk_perturb_dense_l12_pgd(C.byref(a), ptr(g_adv), ptr(delta), ptr(scalars), ptr(scratch), stream_ptr()))
     return scalars
+
+
+def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+    """Raw decoded frames -> normalised clips on the device (flk_clip_prepare): the reference's evaluation transform
+    ``ToTensorVideo -> ResizeVideo(im_scale) -> CenterCropVideo(input_size) -> NormalizeVideo(mean, std)`` (dataset.py:84-123) in one
+    kernel launch per ``FLK_PREP_MAX_CLIPS`` clips.
+
+    ``frames``: a CUDA uint8 tensor ``[N,T,H,W,3]`` or a list of ``[T,H,W,3]`` tensors whose ``H x W`` may differ (same ``T``).  Views
+    are read in place when a pixel's three bytes and a row's pixels are adjacent (frames sliced out of a longer video are).
+    ``out``: fp32 ``[>= out_offset + N, T, Ho, Wo, 3]`` contiguous; clip k goes to ``out[out_offset + k]``, other rows are left alone.
+    Without ``out`` a tensor ``[N,T,Ho,Wo,3]`` is allocated.  Returns the rows written.
+    ``rule``: ``"sizes"`` (default: the arithmetic of torch 1.4.0, which the reference pins) or ``"scale_factor"`` (current torch);
+    see ``videoresnet_spec.prepare_geometry``."""
+    plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule)
+    for a in plan:
+        check(load().flk_clip_prepare(C.byref(a), ptr(out), stream_ptr()))
+    return out[out_offset:out_offset + n]
+
+
+_prep_geometry = functools.lru_cache(maxsize=512)(prepare_geometry)
+
+
+def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+    """the host half of ``prepare_clips``: ``([flk_prepare_args per launch], out, N)`` -- every check and every descriptor, no GPU call.
+    (A caller that repeats one preparation, such as a timing loop, launches the arguments itself.)"""
+    Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
+    clips = list(frames) if isinstance(frames, (list, tuple)) else [frames]        # a 5-d tensor is one group of equal clips
+    if not clips or (torch.is_tensor(clips[0]) and clips[0].dim() == 5 and clips[0].shape[0] == 0):
+        raise ValueError("prepare_clips: no clips")
+    keep, descs, T = [], [], None
+    for k, x in enumerate(clips):
+        group = torch.is_tensor(x) and x.dim() == 5 and not isinstance(frames, (list, tuple))
+        if not torch.is_tensor(x) or not x.is_cuda or x.dtype != torch.uint8 or x.dim() != (5 if group else 4) or x.shape[-1] != 3:
+            desc = f"{tuple(x.shape)} {x.dtype} {x.device}" if torch.is_tensor(x) else type(x).__name__
+            raise ValueError(f"prepare_clips: {'frames' if group else f'clip {k}'} must be a CUDA uint8 tensor [{'N,' if group else ''}T,H,W,3], got {desc}")
+        Tk, Hs, Ws = (int(v) for v in x.shape[-4:-1])
+        T = Tk if T is None else T
+        if Tk != T:
+            raise ValueError(f"prepare_clips: clip {k} has {Tk} frames, clip 0 has {T}")
+        # read in place when a pixel's bytes and a row's pixels are adjacent; anything else is copied once
+        if x.stride(-1) != 1 or x.stride(-2) != 3 or x.stride(-3) < 3 * Ws or (T > 1 and x.stride(-4) <= 0) or (group and x.stride(0) < 0):
+            x = x.contiguous()
+        keep.append(x)
+        Hr, Wr, sh, sw, ci, cj = _prep_geometry(Hs, Ws, im_scale, (Ho, Wo), rule)
+        base, nstride = x.data_ptr(), (x.stride(0) if group else 0)
+        for j in range(x.shape[0] if group else 1):
+            d = PrepClip()
+            d.src, d.T, d.Hs, d.Ws = base + j * nstride, T, Hs, Ws
+            d.pitch_t, d.pitch_h = max(int(x.stride(-4)), 1), int(x.stride(-3))
+            d.Hr, d.Wr, d.step_h, d.step_w, d.crop_i, d.crop_j = Hr, Wr, sh, sw, ci, cj
+            descs.append(d)
+    n = len(descs)
+    if out is None:
+        out = torch.empty((out_offset + n, T, Ho, Wo, 3), dtype=torch.float32, device=keep[0].device)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 5
+            or tuple(out.shape[1:]) != (T, Ho, Wo, 3) or out_offset < 0 or out.shape[0] < out_offset + n):
+        desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"prepare_clips: out must be a contiguous CUDA float32 tensor [>= {out_offset + n},{T},{Ho},{Wo},3], got {desc}")
+    plan = []
+    for first in range(0, n, FLK_PREP_MAX_CLIPS):
+        part = descs[first:first + FLK_PREP_MAX_CLIPS]
+        arr = (PrepClip * len(part))(*part)
+        a = PrepareArgs()
+        a.nclip, a.Ho, a.Wo = len(part), Ho, Wo
+        a.mean, a.std = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
+        a.out_clip_offset, a.out_clip_stride = out_offset + first, T * Ho * Wo * 3
+        a.clips = arr
+        a._keepalive = (arr, keep)          # the struct holds raw pointers only
+        plan.append(a)
+    return plan, out, n
 
 
 def pack_batch_sums(per_clip, prob_scale, out3):

@@ -10,7 +10,7 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, resolve_model, u8_decode_table
+from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, resolve_model, u8_decode_table
 
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 CLIP_DTYPES = (torch.float32, torch.uint8)
@@ -252,8 +252,14 @@ class FlickerVideoResNet:
     when given, must agree with it (a fine-tuned victim brings its own ``fc``, model.py:436-437)."""
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
-                 cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam"):
+                 cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
+                 im_scale=128, resize_rule="sizes"):
         from .i3d_engine import check_optimizer
+        # raw-size uint8 frames are prepared on the device (``prepare``): ResizeVideo(im_scale) -> CenterCropVideo(image_size), dataset.py:84-123;
+        # resize_rule: "sizes" = the arithmetic of torch 1.4.0 (the reference's pin), "scale_factor" = current torch (videoresnet_spec.prepare_geometry)
+        if resize_rule not in RESIZE_RULES:
+            raise ValueError(f"resize_rule must be one of {RESIZE_RULES}, got {resize_rule!r}")
+        self.im_scale, self.resize_rule = im_scale, resize_rule
         # "pgd": delta <- clamp(delta - lr * sgn(g), +-dynamic_max_norm) instead of torch Adam (model.py:868) -- the radius is the clamp
         # bound the perturbation already has, so the restart schedule (model.py:1061-1066) widens it; no optimiser state
         self.optimizer = check_optimizer(optimizer)
@@ -316,6 +322,29 @@ class FlickerVideoResNet:
             raise ValueError(f"clip must be a CUDA float32 or uint8 channels-last tensor {(self.B, self.T, self.H, self.W, 3)}, "
                              f"got {tuple(x.shape)} {x.dtype}")
         return x.contiguous()
+
+    def prepare(self, frames, out=None, out_offset=0):
+        """raw decoded uint8 frames -- a CUDA tensor ``[N,T,H,W,3]`` or a list of ``[T,H,W,3]`` tensors of any (differing) ``H x W`` -- to
+        the normalised fp32 clips ``[N,T,self.H,self.W,3]`` this engine takes: the reference's evaluation transform (dataset.py:84-123) in
+        one kernel (ops.prepare_clips), at the engine's ``im_scale`` / ``resize_rule``.  ``out``: rows ``out_offset ...`` of a batch buffer."""
+        clips = list(frames) if isinstance(frames, (list, tuple)) else frames
+        for k in range(len(clips)):
+            if torch.is_tensor(clips[k]) and clips[k].dim() == 4 and int(clips[k].shape[0]) != self.T:
+                raise ValueError(f"clip {k} has {int(clips[k].shape[0])} frames, the engine takes {self.T}")
+        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                 rule=self.resize_rule)
+
+    def _is_raw(self, x):
+        """uint8 frames that are not at the engine's H x W yet (clips that are take today's path: decoded by the apply kernel)"""
+        return torch.is_tensor(x) and x.dtype == torch.uint8 and x.dim() == 5 and tuple(x.shape[2:4]) != (self.H, self.W)
+
+    def _prepared(self, x):
+        """``x`` itself, or -- raw-size uint8 frames -- their clips prepared into the engine's one reused fp32 buffer (valid until the next call)"""
+        if not self._is_raw(x):
+            return x
+        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < x.shape[0]:
+            self._prep_buf = torch.empty((max(int(x.shape[0]), self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=x.device)
+        return self.prepare(x, out=self._prep_buf)
 
     @staticmethod
     def _same_dtype(dtype, x, what):
@@ -456,7 +485,8 @@ class FlickerVideoResNet:
         ``while step < n_iter or not is_adversarial`` (model.py:1056); whenever ``step > restart_after`` the clamp norm
         grows by ``norm_growth`` and the step counter restarts, giving up after ``max_restarts`` (model.py:1061-1066:
         3000 / 1.3 / 4).  The result dict has the reference's keys (model.py:1193-1203); per-iteration values are host
-        floats (the reference syncs every iteration as well: ``loss.item()``)."""
+        floats (the reference syncs every iteration as well: ``loss.item()``).  Raw-size uint8 frames are prepared on the device first."""
+        inputs = self._prepared(inputs)
         outputs_no_adv = self.logits(inputs, False).clone()
         if not bool((outputs_no_adv.argmax(1) == target).all()):
             return None
@@ -499,6 +529,7 @@ class FlickerVideoResNet:
             xdt = None
             for inputs, target, *_ in data_loaders[phase]:
                 xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
+                inputs = self._prepared(inputs)              # raw-size uint8 frames: this batch's clips, in the reused fp32 buffer
                 clean = self.logits(inputs, False).clone()
                 r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
                 adv_logits = self._logits
@@ -557,7 +588,9 @@ class FlickerVideoResNet:
         # the slot buffer keeps the videos' dtype: uint8 frames stay uint8 (decoded on the device by the apply kernel)
         xdt = self._same_dtype(None, first[0], "fit_many_videos") if first is not None else torch.float32
         it = itertools.chain([first] if first is not None else [], it)
-        x = torch.zeros((B, T, self.H, self.W, 3), dtype=xdt, device=dev)
+        # raw-size uint8 frames are prepared on the device straight into their slot of an fp32 buffer
+        raw = first is not None and self._is_raw(first[0])
+        x = torch.zeros((B, T, self.H, self.W, 3), dtype=torch.float32 if raw else xdt, device=dev)
         labels = torch.zeros(B, dtype=torch.int64, device=dev)
         rng = np.random.default_rng(0)
         slots, out = [None] * B, {}
@@ -586,7 +619,12 @@ class FlickerVideoResNet:
                         self.adam_m[b].zero_(); self.adam_v[b].zero_()
                     self.adam_steps[b] = 0
                 self.active[b] = 1
-                x[b].copy_(inputs[0])
+                if self._is_raw(inputs) != raw:
+                    raise ValueError("fit_many_videos: raw-size and engine-size clips cannot be mixed in one call")
+                if raw:
+                    self.prepare(inputs[:1], out=x, out_offset=b)
+                else:
+                    x[b].copy_(inputs[0])
                 labels[b] = int(target[0])
                 clean = self.logits(x, False)[b:b + 1].clone()
                 if int(clean.argmax(1)) != int(target[0]):

@@ -115,6 +115,73 @@ def synthetic_clip(B, T=16, H=112, W=112, seed=1234):
     return normalize_u8(synthetic_clip_u8(B, T, H, W, seed))
 
 
+RESIZE_RULES = ("sizes", "scale_factor")
+
+
+def _pair(v):
+    return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+
+
+def prepare_geometry(Hs, Ws, im_scale=128, input_size=112, rule="sizes"):
+    """Geometry of the reference's evaluation transform (dataset.py:84-123: ``ResizeVideo(im_scale, keep_ratio=True)`` then
+    ``CenterCropVideo(input_size)``) for ``Hs x Ws`` source frames: ``(Hr, Wr, step_h, step_w, crop_i, crop_j)``.  The one place
+    on the host where these rules are written down; flk_clip_prepare and ``prepare_host`` both take their numbers from here.
+
+    ``scale = im_scale / min(Hs, Ws)`` (a Python double); resized size ``Hr = floor(Hs * scale)``, ``Wr = floor(Ws * scale)`` -- what
+    ``F.interpolate(scale_factor=scale)`` computes.  The source step per resized pixel, a float32, follows ``rule``:
+
+    * ``"sizes"`` (default): ``float32(in) / float32(out)`` per axis -- ``F.interpolate(size=(Hr, Wr))``, and what torch 1.4.0, the
+      version the reference pins (requirements.txt), did with ``scale_factor``: it only derived the output size from it.  This is the
+      arithmetic of the paper's software, hence the default.
+    * ``"scale_factor"``: ``float32(1.0 / scale)`` on both axes -- what a current torch does when ``ResizeVideo`` hands it
+      ``scale_factor``.
+
+    The two agree whenever ``in * scale`` is an integer (256x340, 128x171) and differ visibly otherwise (240x320).
+    Crop offsets: ``round((Hr - Ho) / 2.0)``, Python's round-half-to-even (functional_video.py:60-61).  A resized image smaller than
+    the crop raises ValueError (the reference asserts)."""
+    if rule not in RESIZE_RULES:
+        raise ValueError(f"rule must be one of {RESIZE_RULES}, got {rule!r}")
+    Hs, Ws = int(Hs), int(Ws)
+    Ho, Wo = _pair(input_size)
+    if Hs <= 0 or Ws <= 0 or Ho <= 0 or Wo <= 0 or im_scale <= 0:
+        raise ValueError(f"sizes must be positive: source {Hs} x {Ws}, im_scale {im_scale}, input_size {Ho} x {Wo}")
+    scale = im_scale / min(Hs, Ws)
+    Hr, Wr = int(np.floor(Hs * scale)), int(np.floor(Ws * scale))
+    if Hr < Ho or Wr < Wo:
+        raise ValueError(f"resized image {Hr} x {Wr} (from {Hs} x {Ws} at im_scale {im_scale}) is smaller than the crop {Ho} x {Wo}")
+    if rule == "sizes":
+        step_h, step_w = np.float32(Hs) / np.float32(Hr), np.float32(Ws) / np.float32(Wr)
+    else:
+        step_h = step_w = np.float32(1.0 / scale)
+    return Hr, Wr, float(step_h), float(step_w), int(round((Hr - Ho) / 2.0)), int(round((Wr - Wo) / 2.0))
+
+
+def prepare_host(frames, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+    """The evaluation transform with torch on the CPU, the A/B route of ``ops.prepare_clips``: uint8 frames ``[T,H,W,3]`` (tensor
+    or array) -> the normalised float32 clip ``[T,Ho,Wo,3]``.  Four steps in float32: ``/255``, bilinear ``F.interpolate``
+    (``align_corners=False``; ``size=`` or ``scale_factor=`` by ``rule``), centre crop, ``(v - mean) / std``.  Geometry from
+    ``prepare_geometry``."""
+    import torch
+    import torch.nn.functional as F
+    x = torch.as_tensor(np.ascontiguousarray(frames) if isinstance(frames, np.ndarray) else frames).cpu()
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(x.shape)} {x.dtype}")
+    Hs, Ws = int(x.shape[1]), int(x.shape[2])
+    Ho, Wo = _pair(input_size)
+    Hr, Wr, _, _, ci, cj = prepare_geometry(Hs, Ws, im_scale, input_size, rule)
+    clip = x.float().permute(3, 0, 1, 2) / 255.0                                     # [C,T,H,W]
+    if rule == "sizes":
+        clip = F.interpolate(clip, size=(Hr, Wr), mode="bilinear", align_corners=False)
+    else:
+        clip = F.interpolate(clip, scale_factor=im_scale / min(Hs, Ws), mode="bilinear", align_corners=False)
+    assert tuple(clip.shape[-2:]) == (Hr, Wr), (tuple(clip.shape), Hr, Wr)
+    clip = clip[..., ci:ci + Ho, cj:cj + Wo].clone()
+    m = torch.as_tensor(mean, dtype=clip.dtype)
+    s = torch.as_tensor(std, dtype=clip.dtype)
+    clip.sub_(m[:, None, None, None]).div_(s[:, None, None, None])
+    return clip.permute(1, 2, 3, 0).contiguous()
+
+
 def load_weights(path, arch=None):
     """Victim weights for FlickerVideoResNet as ``{state_dict name: float32 ndarray}``.
 

@@ -263,6 +263,42 @@ int flk_stem_fwd_u8_weights_create(const float* w7_dhwio, flk_conv_weights** out
 int flk_stem_fwd_u8(const flk_apply_args* a, const flk_conv_weights* w, const float* bn_scale, const float* bn_bias,
                     const float* pos_bias, int64_t pos_bias_bstride, void* out, int out_ld, void* stream);
 
+/* Clip preparation: raw decoded frames -> the normalised clip the VideoResNet engines take.  ONE kernel (csrc/prepare.hip) for the
+ * reference's get_transforms(train=False) (dataset.py:84-123; references/transforms_video.py, references/functional_video.py), which
+ * its attack scripts apply to every video (r2plus1d_main_universal_attack.py:169-170):
+ *   ToTensorVideo (/255) -> ResizeVideo(im_scale, keep_ratio: bilinear, align_corners=False) -> CenterCropVideo -> NormalizeVideo
+ * all in fp32, the interpolation between the /255 and the normalisation.  Only the crop window is computed.  Per axis
+ *   src(d) = max(fma(step, d + 0.5f, -0.5f), 0) (the multiply-subtract fused, as torch's CPU kernels evaluate it: DESIGN.md 5.2.2),
+ *   i0 = int(src), i1 = min(i0 + 1, in - 1), lambda = src - i0;   blend along W within each of the two rows, then along H;
+ *   out = (v - mean[c]) / std[c] (true division).
+ * The host supplies the geometry (videoresnet_spec.prepare_geometry is where the rules are written down): the resized size
+ * (Hr, Wr) = floor(in * scale), scale = im_scale / min(Hs, Ws); the per-axis step -- float(in) / float(out) (F.interpolate(size=...),
+ * also what the reference's pinned torch 1.4.0 did with its scale_factor) or float(1 / scale) (current torch given scale_factor);
+ * the crop offsets round((Hr - Ho) / 2.0), round half to even.
+ * One launch for up to FLK_PREP_MAX_CLIPS clips, which may differ in source resolution and pitches.  Clip k of the call is written
+ * to out + (out_clip_offset + k) * out_clip_stride as [T][Ho][Wo][3] fp32, so a call can fill rows of a batch buffer.
+ * No allocation, no synchronisation, no atomics; the result does not depend on the launch geometry.
+ * FLK_EINVAL (before any GPU call): null pointers, nclip outside 1..FLK_PREP_MAX_CLIPS, non-positive sizes / pitches / steps, a crop
+ * window outside the resized image, std <= 0, out_clip_stride smaller than a clip. */
+#define FLK_PREP_MAX_CLIPS 64
+typedef struct {
+  const uint8_t* src;        /* device: uint8 [T][Hs][Ws][3], the 3 bytes of a pixel adjacent */
+  int T, Hs, Ws;
+  int64_t pitch_t, pitch_h;  /* bytes between consecutive frames / rows (a view into a longer or wider video is fine) */
+  int Hr, Wr;                /* size of the resized image (never materialised): the bounds of the crop window */
+  float step_h, step_w;      /* source step per resized pixel */
+  int crop_i, crop_j;        /* top-left corner of the crop window in the resized image */
+} flk_prep_clip;
+typedef struct {
+  int nclip;
+  int Ho, Wo;                /* crop = output size */
+  float mean[3], std[3];     /* dataset.py:28-29 as fp32 */
+  int64_t out_clip_offset;   /* first clip row of `out` this call writes */
+  int64_t out_clip_stride;   /* floats between clip rows of `out` (>= T*Ho*Wo*3) */
+  const flk_prep_clip* clips; /* HOST array [nclip]; copied into the kernel argument */
+} flk_prepare_args;
+int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

@@ -4,7 +4,12 @@ r2plus1d_main_statistics_single_video_attack.py (knobs :28-48, `learner.fit_many
 model.py:917-921).  Clips come pre-decoded (no mp4 decoder here): `--videos-npz` holds `clips` [N,T,112,112,3] (uint8 or
 normalised float32), `labels` [N] and optionally `names` [N]; class names from `--label-map` (one per line).  uint8 clips are
 uploaded once and stay uint8 (`--decode device`, the default: the attack's apply kernel normalises them, bitwise the host route);
-`--decode host` normalises them on the host into float32 and copies each video on its turn, like float32 files."""
+`--decode host` normalises them on the host into float32 and copies each video on its turn, like float32 files.
+uint8 clips may also be RAW decoded frames of any H x W (what the reference's loader hands its transform, dataset.py:84-123): each
+video is resized (shorter side to `--im-scale`), centre-cropped to `--image-size` and normalised by one kernel from the resident raw
+upload (`--prepare device`, the default for such files) or on the host with torch (`--prepare host`); `--resize-rule` picks the
+coordinate rule (videoresnet_spec.prepare_geometry).  Clips are raw when they are not square, or not `--image-size` when that is
+given, or whenever `--prepare` is given (the engine then is 112 x 112 unless `--image-size` says otherwise)."""
 import argparse
 import os
 import sys
@@ -49,6 +54,13 @@ def main():
                     "(flickering attack; 1 = the reference's one-by-one loop)")
     ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
                     "uint8 copy (default), or on the host into float32 (float32 files always take the host route)")
+    ap.add_argument("--prepare", default=None, choices=["device", "host"], help="raw uint8 frames (not at the engine's H x W): resize, centre "
+                    "crop and normalise each video on the device from the resident raw upload (default for such files), or on the host with "
+                    "torch; ignored for clips already at the engine's size")
+    ap.add_argument("--resize-rule", default="sizes", choices=list(vs.RESIZE_RULES), help="coordinate rule of the bilinear resize: sizes = step in / "
+                    "out per axis (F.interpolate(size=...); torch 1.4.0, the reference's pin), scale_factor = step 1 / scale (current torch)")
+    ap.add_argument("--image-size", type=int, default=None, help="engine H = W (default: the clips' own size; 112 for raw frames)")
+    ap.add_argument("--im-scale", type=int, default=128, help="raw frames: the shorter side after the resize (dataset.py's im_scale)")
     ap.add_argument("--reset-optimizer-per-video", action="store_true", help="fresh Adam state for every video (the reference carries one "
                     "state from video to video, model.py:946; with --batch > 1 the carried state is per batch slot; --optimizer pgd keeps no "
                     "state, so there is nothing to reset)")
@@ -56,7 +68,14 @@ def main():
     z = np.load(a.videos_npz, allow_pickle=True)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
     names = [str(n) for n in z["names"]] if "names" in z else [f"video_{i:05d}" for i in range(len(clips))]
-    if clips.dtype == np.uint8 and a.decode == "device":
+    # engine H = W: the clips' own size, as ever, unless they are uint8 and not square, or --image-size / --prepare say otherwise
+    S, raw = clips.shape[2], False
+    if clips.dtype == np.uint8:
+        S = a.image_size or (112 if (a.prepare or clips.shape[2] != clips.shape[3]) else clips.shape[2])
+        raw = tuple(clips.shape[2:4]) != (S, S)
+    if raw and a.prepare == "host":      # the four steps of the evaluation transform with torch on the CPU (videoresnet_spec.prepare_host)
+        clips = np.stack([vs.prepare_host(c, im_scale=a.im_scale, input_size=S, rule=a.resize_rule).numpy() for c in clips])
+    elif raw or (clips.dtype == np.uint8 and a.decode == "device"):
         clips = np.ascontiguousarray(clips)
     else:
         if clips.dtype == np.uint8:
@@ -67,9 +86,9 @@ def main():
     # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
     arch, _, ncls = vs.resolve_model(a.base_model, clips.shape[1])
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
-    learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=clips.shape[2], dtype=a.dtype,
+    learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
-                                 optimizer=a.optimizer)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -11,7 +11,14 @@ replicated (parallel.py).
 
 uint8 clips stay uint8 (`--decode device`, the default): each rank uploads its shard once and every batch is a slice of that
 resident tensor; the attack's apply kernel normalises the frames (bitwise the host route's float32 values).  `--decode host`
-normalises on the host and copies every batch, as float32, per step -- the route of float32 files."""
+normalises on the host and copies every batch, as float32, per step -- the route of float32 files.
+
+uint8 clips may also be RAW decoded frames of any H x W (what the reference's loader hands its transform, dataset.py:84-123): they are
+resized (bilinear, shorter side to `--im-scale`), centre-cropped to `--image-size` and normalised per batch by one kernel from the
+resident raw shard (`--prepare device`, the default for such files), or once on the host with torch (`--prepare host`, the A/B
+route).  `--resize-rule` picks the coordinate rule of the resize (videoresnet_spec.prepare_geometry).  Clips are raw when they are
+not square, or not `--image-size` when that is given, or whenever `--prepare` is given (the engine then is 112 x 112 unless
+`--image-size` says otherwise); files of clips at the engine's size behave as before."""
 import argparse
 import glob
 import os
@@ -42,10 +49,31 @@ MODEL_INPUT_SIZE = 16            # frames per clip for the three VideoResNets
 BATCH_SIZE = 8                   # BATCH_SIZE_ARRAY[1] (one device per process here)
 
 
-def load_clips(path, decode="device"):
-    """clips as the file holds them when they are uint8 and decode == "device", else normalised float32 on the host"""
+def engine_size(clips, image_size=None, prepare=None):
+    """(engine H = W, whether the clips are raw frames still to be resized / cropped): the clips' own size, as ever, unless they are
+    uint8 and not square, or --image-size / --prepare say otherwise (then 112, dataset.py's input_size, or --image-size)"""
+    H, W = clips.shape[2], clips.shape[3]
+    if clips.dtype != np.uint8:
+        return H, False
+    S = image_size or (112 if (prepare or H != W) else H)
+    return S, (H, W) != (S, S)
+
+
+def prepare_host_clips(clips, S, im_scale, rule):
+    """--prepare host: the four steps of the evaluation transform with torch on the CPU, clip by clip (videoresnet_spec.prepare_host)"""
+    return np.stack([vs.prepare_host(c, im_scale=im_scale, input_size=S, rule=rule).numpy() for c in clips])
+
+
+def load_clips(path, decode="device", image_size=None, prepare=None, im_scale=128, rule="sizes"):
+    """clips as the file holds them when they are uint8 and decode == "device" (or raw with prepare != "host"), else normalised float32
+    on the host"""
     z = np.load(path)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
+    S, raw = engine_size(clips, image_size, prepare)
+    if raw:
+        if prepare == "host":
+            return prepare_host_clips(clips, S, im_scale, rule), labels
+        return np.ascontiguousarray(clips), labels
     if clips.dtype == np.uint8 and decode == "device":
         return np.ascontiguousarray(clips), labels
     if clips.dtype == np.uint8:      # get_normalize_transforms (dataset.py:212-243): /255, mean / std
@@ -100,6 +128,13 @@ def main():
                     "lr * sgn(grad), +-l_inf norm), instead of Adam (model.py:868); --lr is the step size and StepLR scales it")
     ap.add_argument("--decode", default="device", choices=["device", "host"], help="uint8 clips: normalise on the device from a resident "
                     "uint8 copy (default), or on the host with a float32 copy per step (float32 files always take the host route)")
+    ap.add_argument("--prepare", default=None, choices=["device", "host"], help="raw uint8 frames (not at the engine's H x W): resize, centre "
+                    "crop and normalise every batch on the device from the resident raw shard (default for such files), or once on the host "
+                    "with torch; ignored for clips already at the engine's size")
+    ap.add_argument("--resize-rule", default="sizes", choices=list(vs.RESIZE_RULES), help="coordinate rule of the bilinear resize: sizes = step in / "
+                    "out per axis (F.interpolate(size=...); torch 1.4.0, the reference's pin), scale_factor = step 1 / scale (current torch)")
+    ap.add_argument("--image-size", type=int, default=None, help="engine H = W (default: the clips' own size; 112 for raw frames)")
+    ap.add_argument("--im-scale", type=int, default=128, help="raw frames: the shorter side after the resize (dataset.py's im_scale)")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
     a = ap.parse_args()
@@ -111,16 +146,16 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    xtr, ytr = load_clips(a.train_npz, a.decode)
-    xva, yva = load_clips(a.val_npz, a.decode)
-    T, HW = xtr.shape[1], xtr.shape[2]
+    xtr, ytr = load_clips(a.train_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule)
+    xva, yva = load_clips(a.val_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule)
+    T, HW = xtr.shape[1], engine_size(xtr, a.image_size, a.prepare)[0]
     # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
     # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
     arch, _, ncls = vs.resolve_model(a.base_model, T)
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
-                                 optimizer=a.optimizer)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule)
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     start_epoch = 1
@@ -139,7 +174,7 @@ def main():
         def __getitem__(self, phase):
             x, y = (xtr, ytr) if phase == "train" else (xva, yva)
             r, w = (rank, world) if phase == "train" else (0, 1)
-            if x.dtype == np.uint8:               # --decode device: the shard is uploaded on first use, then sliced
+            if x.dtype == np.uint8:               # --decode device / --prepare device: the shard is uploaded on first use, then sliced
                 if phase not in resident:
                     resident[phase] = ResidentShard(x, y, a.batch_size, r, w)
                 return iter(resident[phase])
