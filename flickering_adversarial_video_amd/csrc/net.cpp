@@ -274,58 +274,72 @@ struct flk_net {
   // run beside the MFMA-bound convolutions of the other (per-sample arithmetic is unchanged: tiles never span clips).
   int bs_b0 = 0, bs_nb = 0;         // bs_nb == 0: the whole batch
   int nbatch() const { return bs_nb ? bs_nb : B; }
-  char* bp(const Act& a) const { return (char*)a.p + (size_t)bs_b0 * a.T * a.H * a.W * a.ld * esz(); }
-  const char* bp(const void* p, const Act& geom, int ld) const { return p ? (const char*)p + (size_t)bs_b0 * geom.T * geom.H * geom.W * ld * esz() : nullptr; }
+  char* bp(const Act& a) const { return a.p ? (char*)a.p + (size_t)bs_b0 * a.numel(1) * esz() : nullptr; }
+  // ---- lane: the stream the operators pushed below will run on (Op::lane), builder state like the batch slice
+  int lane = 0;
+  void push(std::vector<Op>& ops, Op op) {
+    op.lane = lane;
+    ops.push_back(std::move(op));
+  }
 
+  // ---- convolution arguments and operators -------------------------------------------------------
+  struct V3 { int t, h, w; };
+  // out[:, out_coff : out_coff + cout] = conv(in[:, in_coff : in_coff + cin]) on the current batch slice, the output grid being the
+  // whole of `out` (unit output stride).  The one place a flk_conv_args starts from; a caller sets what is special to it on the result:
+  // epilogue operands, second segments, a strided output grid, per-call pointers (an Act with p = nullptr is geometry only).
+  flk_conv_args conv_args(const Act& in, int in_coff, int cin, const Act& out, int out_coff, int cout, V3 k, V3 stride, V3 pad) const {
+    flk_conv_args a{};
+    a.in = bp(in); a.in_ld = in.ld; a.in_coff = in_coff; a.cin = cin;
+    a.B = nbatch(); a.Ti = in.T; a.Hi = in.H; a.Wi = in.W;
+    a.kt = k.t; a.kh = k.h; a.kw = k.w; a.st = stride.t; a.sh = stride.h; a.sw = stride.w;
+    a.pt = pad.t; a.ph = pad.h; a.pw = pad.w;
+    a.To = out.T; a.Ho = out.H; a.Wo = out.W;
+    a.out = bp(out); a.out_ld = out.ld; a.out_coff = out_coff; a.cout = cout;
+    a.OT = out.T; a.OH = out.H; a.OW = out.W; a.ost = a.osh = a.osw = 1;
+    return a;
+  }
+  void set_mask(flk_conv_args& a, const Act* mask, int mask_coff = 0) const {
+    if (mask) { a.mask = bp(*mask); a.mask_ld = mask->ld; a.mask_coff = mask_coff; }
+  }
+  // arguments of a stride-1 SAME Unit3D: out[:, coff:coff+cout] = relu(conv(in[:, in_coff:in_coff+cin]) * scale + bias)
+  flk_conv_args conv_fwd_args(ConvLayer* L, const Act& in, int in_coff, const Act& out, int out_coff) const {
+    flk_conv_args a = conv_args(in, in_coff, L->cin, out, out_coff, L->cout, {L->kt, L->kh, L->kw}, {1, 1, 1},
+                                {(L->kt - 1) / 2, (L->kh - 1) / 2, (L->kw - 1) / 2});
+    a.scale = L->d_scale; a.bias = L->d_bias; a.relu = 1;
+    return a;
+  }
+  // ... and of its data gradient: gin[:, gin_coff..] = conv_T(G[:, g_coff..]) masked
+  flk_conv_args conv_bwd_args(ConvLayer* L, const Act& G, int g_coff, const Act& gin, int gin_coff, const Act* mask, int mask_coff) const {
+    flk_conv_args a = conv_args(G, g_coff, L->cout, gin, gin_coff, L->cin, {L->kt, L->kh, L->kw}, {1, 1, 1},
+                                {L->kt - 1 - (L->kt - 1) / 2, L->kh - 1 - (L->kh - 1) / 2, L->kw - 1 - (L->kw - 1) / 2});
+    set_mask(a, mask, mask_coff);
+    return a;
+  }
+  static double conv_macs(const flk_conv_args& a) { return (double)a.B * a.To * a.Ho * a.Wo * a.kt * a.kh * a.kw * a.cin * a.cout; }
   // compulsory HBM bytes of a convolution launch: input once, output once, plus the epilogue's add / mask operands (reported beside
   // the flops by the per-layer profile: the 1x1x1 layers are bound by these, the 3x3x3 / 7x7x7 ones by MFMA)
   double conv_bytes(const flk_conv_args& a) const {
     const double in = (double)a.B * a.Ti * a.Hi * a.Wi * a.cin, out = (double)a.B * a.To * a.Ho * a.Wo * a.cout;
     return (in + out * (1 + (a.add != nullptr) + (a.mask != nullptr))) * esz();
   }
+  // one convolution operator; `run` replaces the plain launch where pointers are bound per call (the stems)
+  void push_conv(std::vector<Op>& ops, const std::string& name, const flk_conv_args& a, const flk_conv_weights* w, double macs,
+                 std::function<int(hipStream_t)> run = nullptr) {
+    const int dt = dtype;
+    if (!run) run = [a, w, dt](hipStream_t s) { return flk_conv3d(&a, w, dt, s); };
+    push(ops, Op{name, K_CONV, 2.0 * macs, conv_bytes(a), std::move(run)});
+  }
 
   // ---- op emitters -------------------------------------------------------------------------------
-  // forward Unit3D: out[:, coff:coff+cout] = relu(conv(in[:, in_coff:in_coff+cin]) * scale + bias), stride 1 SAME
-  void emit_conv_fwd(ConvLayer* L, const Act& in, int in_coff, const Act& out, int out_coff, const void* const* in_ptr = nullptr) {
-    flk_conv_args a{};
-    a.in = bp(in); a.in_ld = in.ld; a.in_coff = in_coff; a.cin = L->cin;
-    a.B = nbatch(); a.Ti = in.T; a.Hi = in.H; a.Wi = in.W;
-    a.kt = L->kt; a.kh = L->kh; a.kw = L->kw; a.st = a.sh = a.sw = 1;
-    a.pt = (L->kt - 1) / 2; a.ph = (L->kh - 1) / 2; a.pw = (L->kw - 1) / 2;
-    a.To = out.T; a.Ho = out.H; a.Wo = out.W;
-    a.out = bp(out); a.out_ld = out.ld; a.out_coff = out_coff; a.cout = L->cout;
-    a.OT = out.T; a.OH = out.H; a.OW = out.W; a.ost = a.osh = a.osw = 1;
-    a.scale = L->d_scale; a.bias = L->d_bias; a.relu = 1;
-    const double macs = (double)nbatch() * out.T * out.H * out.W * L->kt * L->kh * L->kw * L->cin * L->cout;
-    flk_conv_weights* wf = L->wf;
-    const int dt = dtype;
-    attach_splitk(a, wf);
-    fwd.push_back(Op{L->name, K_CONV, 2.0 * macs, conv_bytes(a), [a, wf, dt, in_ptr](hipStream_t s) mutable {
-                       if (in_ptr) a.in = *in_ptr;
-                       return flk_conv3d(&a, wf, dt, s);
-                     }});
+  void emit_conv_fwd(ConvLayer* L, const Act& in, int in_coff, const Act& out, int out_coff) {
+    flk_conv_args a = conv_fwd_args(L, in, in_coff, out, out_coff);
+    attach_splitk(a, L->wf);
+    push_conv(fwd, L->name, a, L->wf, conv_macs(a));
   }
-  // data gradient of a stride-1 SAME Unit3D: gin[:, gin_coff..] = (conv_T(G[:, g_coff..]) + add) masked
-  void emit_conv_bwd(ConvLayer* L, const Act& G, int g_coff, const Act& gin, int gin_coff, const void* add, int add_ld,
-                     int add_coff, const Act* mask, int mask_coff, void* const* out_ptr = nullptr) {
-    flk_conv_args a{};
-    a.in = bp(G); a.in_ld = G.ld; a.in_coff = g_coff; a.cin = L->cout;
-    a.B = nbatch(); a.Ti = G.T; a.Hi = G.H; a.Wi = G.W;
-    a.kt = L->kt; a.kh = L->kh; a.kw = L->kw; a.st = a.sh = a.sw = 1;
-    a.pt = L->kt - 1 - (L->kt - 1) / 2; a.ph = L->kh - 1 - (L->kh - 1) / 2; a.pw = L->kw - 1 - (L->kw - 1) / 2;
-    a.To = gin.T; a.Ho = gin.H; a.Wo = gin.W;
-    a.out = bp(gin); a.out_ld = gin.ld; a.out_coff = gin_coff; a.cout = L->cin;
-    a.OT = gin.T; a.OH = gin.H; a.OW = gin.W; a.ost = a.osh = a.osw = 1;
-    a.add = bp(add, gin, add_ld); a.add_ld = add_ld; a.add_coff = add_coff;
-    if (mask) { a.mask = bp(*mask); a.mask_ld = mask->ld; a.mask_coff = mask_coff; }
-    const double macs = (double)nbatch() * gin.T * gin.H * gin.W * L->kt * L->kh * L->kw * L->cin * L->cout;
-    flk_conv_weights* wb = L->wb;
-    const int dt = dtype;
-    attach_splitk(a, wb);
-    bwd.push_back(Op{L->name + "/dgrad", K_CONV, 2.0 * macs, conv_bytes(a), [a, wb, dt, out_ptr](hipStream_t s) mutable {
-                       if (out_ptr) a.out = *out_ptr;
-                       return flk_conv3d(&a, wb, dt, s);
-                     }});
+  void emit_conv_bwd(ConvLayer* L, const Act& G, int g_coff, const Act& gin, int gin_coff, const Act* mask, int mask_coff) {
+    flk_conv_args a = conv_bwd_args(L, G, g_coff, gin, gin_coff, mask, mask_coff);
+    attach_splitk(a, L->wb);
+    push_conv(bwd, L->name + "/dgrad", a, L->wb, conv_macs(a));
   }
   struct PoolRec { flk_pool_args a; uint8_t* idx_base = nullptr; };
   int emit_pool_fwd(const std::string& name, const Act& in, int C, int kt, int kh, int kw, int st, int sh, int sw, Act& out,
@@ -347,22 +361,20 @@ struct flk_net {
     rec.a = a;
     const int dt = dtype;
     const double bytes = ((double)in.numel(nbatch()) + out.numel(nbatch())) * esz() + (double)nbatch() * a.To * a.Ho * a.Wo * C;
-    fwd.push_back(Op{name, K_POOL, 0.0, bytes, [a, dt](hipStream_t s) { return flk_maxpool3d_fwd(&a, dt, s); }});
+    push(fwd, Op{name, K_POOL, 0.0, bytes, [a, dt](hipStream_t s) { return flk_maxpool3d_fwd(&a, dt, s); }});
     return FLK_OK;
   }
-  void emit_pool_bwd(const std::string& name, const PoolRec& rec, const Act& gout, const Act& gin, const Act* mask) {
+  void emit_pool_bwd(const std::string& name, const PoolRec& rec, const Act& gout, const Act& gin) {
     const flk_pool_args a = rec.a;
     const int dt = dtype;
-    const void* mp = mask ? mask->p : nullptr;
-    const int mld = mask ? mask->ld : 0;
     const int nb = a.B;                                  // the slice the forward operator was built for (bs_b0 must match)
-    const double bytes = ((double)gout.numel(nb) + gin.numel(nb) + (mask ? gin.numel(nb) : 0)) * esz() + (double)nb * a.To * a.Ho * a.Wo * a.C;
+    const double bytes = ((double)gout.numel(nb) + gin.numel(nb)) * esz() + (double)nb * a.To * a.Ho * a.Wo * a.C;
     const void* gop = bp(gout);
     void* gip = bp(gin);
-    if (mask) mp = bp(*mask);
-    bwd.push_back(Op{name + "/grad", K_POOL, 0.0, bytes, [a, dt, gop, gip, gout, gin, mp, mld](hipStream_t s) {
-                       return flk_maxpool3d_bwd(&a, gop, gout.ld, 0, gip, gin.ld, 0, mp, mld, 0, dt, s);
-                     }});
+    const int gold = gout.ld, gild = gin.ld;
+    push(bwd, Op{name + "/grad", K_POOL, 0.0, bytes, [a, dt, gop, gold, gip, gild](hipStream_t s) {
+           return flk_maxpool3d_bwd(&a, gop, gold, 0, gip, gild, 0, nullptr, 0, 0, dt, s);
+         }});
   }
 
   // ---- grouped launches: Branch_1's and Branch_2's 3x3x3 units of an Inception block in ONE grid (flk_conv3d_group) ----
@@ -375,10 +387,9 @@ struct flk_net {
   GroupLayout plan_group(const Act& geom, int cin1, int cout1, int cout2) const {
     GroupLayout g;
     if (dtype != FLK_BF16) return g;
-    flk_conv_args a{};
-    a.B = B; a.Ti = a.To = a.OT = geom.T; a.Hi = a.Ho = a.OH = geom.H; a.Wi = a.Wo = a.OW = geom.W;
-    a.kt = a.kh = a.kw = 3; a.st = a.sh = a.sw = 1; a.pt = a.ph = a.pw = 1; a.ost = a.osh = a.osw = 1;
-    a.cin = cin1; a.cout = cout1; a.in_ld = cin1; a.out_ld = cout1;
+    Act in, out;      // geometry only
+    in.T = out.T = geom.T; in.H = out.H = geom.H; in.W = out.W = geom.W; in.ld = cin1; out.ld = cout1;
+    const flk_conv_args a = conv_args(in, 0, cin1, out, 0, cout1, {3, 3, 3}, {1, 1, 1}, {1, 1, 1});
     const long rows = (long)B * geom.T * geom.H * geom.W;
     int nf1 = nf_for(cout1, 27, rows);
     if (nf1 == 6) nf1 = 4;
@@ -403,36 +414,10 @@ struct flk_net {
     g.nfw = nfw; g.nf1 = nf1; g.nf2 = nfw * wn2;
     return g;
   }
-  // arguments of a stride-1 SAME Unit3D forward / data-gradient (emit_conv_fwd / emit_conv_bwd without the launch)
-  flk_conv_args conv_fwd_args(ConvLayer* L, const Act& in, int in_coff, const Act& out, int out_coff) const {
-    flk_conv_args a{};
-    a.in = bp(in); a.in_ld = in.ld; a.in_coff = in_coff; a.cin = L->cin;
-    a.B = nbatch(); a.Ti = in.T; a.Hi = in.H; a.Wi = in.W;
-    a.kt = L->kt; a.kh = L->kh; a.kw = L->kw; a.st = a.sh = a.sw = 1;
-    a.pt = (L->kt - 1) / 2; a.ph = (L->kh - 1) / 2; a.pw = (L->kw - 1) / 2;
-    a.To = out.T; a.Ho = out.H; a.Wo = out.W;
-    a.out = bp(out); a.out_ld = out.ld; a.out_coff = out_coff; a.cout = L->cout;
-    a.OT = out.T; a.OH = out.H; a.OW = out.W; a.ost = a.osh = a.osw = 1;
-    a.scale = L->d_scale; a.bias = L->d_bias; a.relu = 1;
-    return a;
-  }
-  flk_conv_args conv_bwd_args(ConvLayer* L, const Act& G, int g_coff, const Act& gin, int gin_coff, const Act* mask, int mask_coff) const {
-    flk_conv_args a{};
-    a.in = bp(G); a.in_ld = G.ld; a.in_coff = g_coff; a.cin = L->cout;
-    a.B = nbatch(); a.Ti = G.T; a.Hi = G.H; a.Wi = G.W;
-    a.kt = L->kt; a.kh = L->kh; a.kw = L->kw; a.st = a.sh = a.sw = 1;
-    a.pt = L->kt - 1 - (L->kt - 1) / 2; a.ph = L->kh - 1 - (L->kh - 1) / 2; a.pw = L->kw - 1 - (L->kw - 1) / 2;
-    a.To = gin.T; a.Ho = gin.H; a.Wo = gin.W;
-    a.out = bp(gin); a.out_ld = gin.ld; a.out_coff = gin_coff; a.cout = L->cin;
-    a.OT = gin.T; a.OH = gin.H; a.OW = gin.W; a.ost = a.osh = a.osw = 1;
-    if (mask) { a.mask = bp(*mask); a.mask_ld = mask->ld; a.mask_coff = mask_coff; }
-    return a;
-  }
   // one operator = the two members in one launch (the large member first: its long K loops start first, the small member's
   // workgroups fill the tail)
   void emit_group(std::vector<Op>& ops, const std::string& name, const flk_conv_args& a1, const flk_conv_weights* w1, const flk_conv_args& a2,
                   const flk_conv_weights* w2, int nfw, int ring = 0) {
-    auto macs = [](const flk_conv_args& a) { return (double)a.B * a.To * a.Ho * a.Wo * a.kt * a.kh * a.kw * a.cin * a.cout; };
     const int dt = dtype;
     {
       // plan_group decided layout and packing through flk_conv_layout_query; flk_conv3d_group re-plans every member at launch.  Checked
@@ -442,19 +427,18 @@ struct flk_net {
       const flk_conv_weights* wv[2] = {w1, w2};
       if (flk_conv3d_group_check(av, wv, 2, nfw, ring, dt) != FLK_OK) {
         fprintf(stderr, "[flicker_hip] %s: grouped launch refused (%s); running its members as two launches\n", name.c_str(), flk_last_error());
-        ops.push_back(Op{name + "/member0", K_CONV, 2.0 * macs(a1), conv_bytes(a1), [a1, w1, dt](hipStream_t s) { return flk_conv3d(&a1, w1, dt, s); }});
-        ops.push_back(Op{name + "/member1", K_CONV, 2.0 * macs(a2), conv_bytes(a2), [a2, w2, dt](hipStream_t s) { return flk_conv3d(&a2, w2, dt, s); }});
+        push_conv(ops, name + "/member0", a1, w1, conv_macs(a1));
+        push_conv(ops, name + "/member1", a2, w2, conv_macs(a2));
         return;
       }
     }
-    ops.push_back(Op{name, K_CONV, 2.0 * (macs(a1) + macs(a2)), conv_bytes(a1) + conv_bytes(a2), [a1, w1, a2, w2, nfw, ring, dt](hipStream_t s) {
-                       const flk_conv_args* av[2] = {&a1, &a2};
-                       const flk_conv_weights* wv[2] = {w1, w2};
-                       return flk_conv3d_group(av, wv, 2, nfw, ring, dt, s);
-                     }});
+    push(ops, Op{name, K_CONV, 2.0 * (conv_macs(a1) + conv_macs(a2)), conv_bytes(a1) + conv_bytes(a2), [a1, w1, a2, w2, nfw, ring, dt](hipStream_t s) {
+           const flk_conv_args* av[2] = {&a1, &a2};
+           const flk_conv_weights* wv[2] = {w1, w2};
+           return flk_conv3d_group(av, wv, 2, nfw, ring, dt, s);
+         }});
   }
 
-  static void set_lane(std::vector<Op>& v, size_t from, int lane) { for (size_t i = from; i < v.size(); ++i) v[i].lane = lane; }
   static void push_sync(std::vector<Op>& v, int kind, int mask = ~0) {
     v.push_back(Op{kind == K_FORK ? "@fork" : "@join", kind, 0.0, 0.0, nullptr});
     v.back().mask = mask;
@@ -465,7 +449,9 @@ struct flk_net {
                    int st_, int sh_, int sw_, int pt_, int ph_, int pw_, ConvLayer** out);
   int pack_generic(ConvLayer* L);
   void emit_gen_fwd(ConvLayer* L, const Act& in, const Act& out, bool relu, const Act* add);
-  void emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const void* add, int add_ld, const Act* mask);
+  void emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const Act* add, const Act* mask);
+  int emit_head(const char* name, const Act& y, const Act& Gy, int C, std::vector<std::function<void()>>& bwd_emit);
+  int input_fold() const { return arch == FLK_NET_I3D ? 3 : in_ch == 32 ? 4 : 1; }      // flk_apply_args.fold_t of the plan's input tensor
 };
 
 // ---------------------------------------------------------------------------------------------------
@@ -511,7 +497,7 @@ int flk_net::build_i3d() {
     if ((rc = dmalloc((void**)&d_stem_tab, (size_t)B * (T / 2) * 16 * 64 * sizeof(float), true))) return rc;   // (one table per clip: per-clip perturbations)
   }
   const int T1 = T / 2, H1 = H / 2, W1 = W / 2;
-  Act xin; xin.T = T1; xin.H = H1; xin.W = W1; xin.ld = 32;       // bound per call
+  Act xin; xin.T = T1; xin.H = H1; xin.W = W1; xin.ld = 32;       // the space-to-depth clip / its gradient: geometry only, bound per call
   Act a1, G1;
   if ((rc = new_act(a1, T1, H1, W1, 64)) || (rc = new_act(G1, T1, H1, W1, 64))) return rc;
   named["Conv3d_1a_7x7"] = {a1, 64};
@@ -536,30 +522,26 @@ int flk_net::build_i3d() {
   if (split) push_sync(fwd, K_FORK, 1);
   for (int h = 0; h < nhalf; ++h) {
     if (split) { bs_b0 = h * (B / 2); bs_nb = B / 2; }
-    const size_t m0 = fwd.size();
+    lane = h;
     {
       // SAME padding of the 7/2 conv on an even size is (2,3) -> in s2d space taps j=0..3 read o-1+j: pad-before 1
-      flk_conv_args a{};
-      a.in_ld = 32; a.in_coff = 0; a.cin = 32; a.B = nbatch(); a.Ti = T1; a.Hi = H1; a.Wi = W1;
-      a.kt = a.kh = a.kw = 4; a.st = a.sh = a.sw = 1; a.pt = a.ph = a.pw = 1;
-      a.To = T1; a.Ho = H1; a.Wo = W1; a.out = bp(a1); a.out_ld = 64; a.cout = 64;
-      a.OT = T1; a.OH = H1; a.OW = W1; a.ost = a.osh = a.osw = 1;
+      flk_conv_args a = conv_args(xin, 0, 32, a1, 0, 64, {4, 4, 4}, {1, 1, 1}, {1, 1, 1});
       a.scale = stem->d_scale; a.bias = stem->d_bias; a.relu = 1;
       flk_conv_weights* wf = stem->wf;
       const int dt = dtype;
-      const size_t in_off = (size_t)bs_b0 * T1 * H1 * W1 * 32 * esz();
+      const size_t in_off = (size_t)bs_b0 * xin.numel(1) * esz();
       const int b0 = bs_b0;
-      fwd.push_back(Op{"Conv3d_1a_7x7", K_CONV, 2.0 * stem_macs, conv_bytes(a), [this, a, wf, dt, in_off, b0](hipStream_t s) mutable {
-                         a.in = (const char*)x_in + in_off;
-                         a.pos_bias_bstride = cur_pos_bias_bstride;
-                         a.pos_bias = cur_pos_bias ? cur_pos_bias + (size_t)b0 * cur_pos_bias_bstride : nullptr;   // flk_net_forward_flicker: the perturbation enters here, in fp32
-                         if (stem_from_u8()) {
-                           const flk_apply_args sl = apply_args_slice(b0, a.B);
-                           return flk_stem_fwd_u8(&sl, stem_u8_w, a.scale, a.bias, a.pos_bias, a.pos_bias_bstride, a.out, a.out_ld, s);
-                         }
-                         if (int rc = apply_slice(b0, a.B, (char*)x_in + in_off, s)) return rc;
-                         return flk_conv3d(&a, wf, dt, s);
-                       }});
+      push_conv(fwd, "Conv3d_1a_7x7", a, wf, stem_macs, [this, a, wf, dt, in_off, b0](hipStream_t s) mutable {
+        a.in = (const char*)x_in + in_off;
+        a.pos_bias_bstride = cur_pos_bias_bstride;
+        a.pos_bias = cur_pos_bias ? cur_pos_bias + (size_t)b0 * cur_pos_bias_bstride : nullptr;   // flk_net_forward_flicker: the perturbation enters here, in fp32
+        if (stem_from_u8()) {
+          const flk_apply_args sl = apply_args_slice(b0, a.B);
+          return flk_stem_fwd_u8(&sl, stem_u8_w, a.scale, a.bias, a.pos_bias, a.pos_bias_bstride, a.out, a.out_ld, s);
+        }
+        if (int rc = apply_slice(b0, a.B, (char*)x_in + in_off, s)) return rc;
+        return flk_conv3d(&a, wf, dt, s);
+      });
     }
     // main pools read ReLU outputs whose gradient is masked by (input > 0): relu_input makes the mask read unnecessary
     if (h) { r2a[h].idx_base = r2a[0].idx_base; r3a[h].idx_base = r3a[0].idx_base; }
@@ -573,9 +555,8 @@ int flk_net::build_i3d() {
     emit_conv_fwd(c2c, a2b, 0, a2c, 0);
     if ((rc = emit_pool_fwd("MaxPool3d_3a_3x3", a2c, 192, 1, 3, 3, 1, 2, 2, p3a, r3a[h], true))) return rc;
     if (h == 0 && (rc = new_act(Gp3a, p3a.T, p3a.H, p3a.W, 192))) return rc;
-    set_lane(fwd, m0, h);
   }
-  bs_b0 = bs_nb = 0;
+  bs_b0 = bs_nb = lane = 0;
   if (split) push_sync(fwd, K_JOIN, 1);
   named["MaxPool3d_2a_3x3"] = {p2a, 64};
   named["grad:MaxPool3d_2a_3x3"] = {Gp2a, 64};
@@ -587,40 +568,35 @@ int flk_net::build_i3d() {
   named["grad:MaxPool3d_3a_3x3"] = {Gp3a, 192};
   {
     // backward of the segment (emitters run in reverse: this block's second emitter runs first)
-    flk_conv_args g{};
-    g.in = G1.p; g.in_ld = 64; g.cin = 64; g.B = B; g.Ti = T1; g.Hi = H1; g.Wi = W1;
-    g.kt = g.kh = g.kw = 4; g.st = g.sh = g.sw = 1; g.pt = g.ph = g.pw = 2;   // k-1-pad
-    g.To = T1; g.Ho = H1; g.Wo = W1; g.out_ld = 32; g.cout = 32;
-    g.OT = T1; g.OH = H1; g.OW = W1; g.ost = g.osh = g.osw = 1;
+    flk_conv_args g = conv_args(G1, 0, 64, xin, 0, 32, {4, 4, 4}, {1, 1, 1}, {2, 2, 2});   // k-1-pad
     flk_conv_weights* wb = stem->wb;
     const int dt = dtype;
     const double macs = stem_macs * nhalf;
     bwd_emit.push_back([this, g, wb, dt, macs]() {
-      bwd.push_back(Op{"Conv3d_1a_7x7/dgrad", K_CONV, 2.0 * macs, conv_bytes(g), [this, g, wb, dt](hipStream_t s) mutable {
-                         g.out = gx_in;
-                         return flk_conv3d(&g, wb, dt, s);
-                       }});
+      push_conv(bwd, "Conv3d_1a_7x7/dgrad", g, wb, macs, [this, g, wb, dt](hipStream_t s) mutable {
+        g.out = gx_in;
+        return flk_conv3d(&g, wb, dt, s);
+      });
     });
     const PoolRec r2a0 = r2a[0], r2a1 = r2a[1], r3a0 = r3a[0], r3a1 = r3a[1];
     bwd_emit.push_back([=]() {
       if (split) push_sync(bwd, K_FORK, 1);
       for (int h = 0; h < nhalf; ++h) {
         if (split) { bs_b0 = h * (B / 2); bs_nb = B / 2; }
-        const size_t m0 = bwd.size();
-        emit_pool_bwd("MaxPool3d_3a_3x3", h ? r3a1 : r3a0, Gp3a, G2c, nullptr);
-        emit_conv_bwd(c2c, G2c, 0, G2b, 0, nullptr, 0, 0, &a2b, 0);
-        emit_conv_bwd(c2b, G2b, 0, Gp2a, 0, nullptr, 0, 0, nullptr, 0);
-        emit_pool_bwd("MaxPool3d_2a_3x3", h ? r2a1 : r2a0, Gp2a, G1, nullptr);
+        lane = h;
+        emit_pool_bwd("MaxPool3d_3a_3x3", h ? r3a1 : r3a0, Gp3a, G2c);
+        emit_conv_bwd(c2c, G2c, 0, G2b, 0, &a2b, 0);
+        emit_conv_bwd(c2b, G2b, 0, Gp2a, 0, nullptr, 0);
+        emit_pool_bwd("MaxPool3d_2a_3x3", h ? r2a1 : r2a0, Gp2a, G1);
         if (split) {
           // the half's share of the fused stem delta-gradient, right behind the gradient it consumes: the MFMA-bound GEMM of one half
           // runs beside the HBM-bound tail (1x1x1 data-gradient, pool backward) of the other instead of after both
           // (flk_net_backward_delta; a no-op in every other run of this list)
           const int b0 = bs_b0, nb = bs_nb;
-          bwd.push_back(Op{"Conv3d_1a_7x7/dgrad/half", K_CONV, 0.0, 0.0, [this, b0, nb](hipStream_t st) { return delta_part ? delta_part(b0, nb, st) : FLK_OK; }});
+          push(bwd, Op{"Conv3d_1a_7x7/dgrad/half", K_CONV, 0.0, 0.0, [this, b0, nb](hipStream_t st) { return delta_part ? delta_part(b0, nb, st) : FLK_OK; }});
         }
-        set_lane(bwd, m0, h);
       }
-      bs_b0 = bs_nb = 0;
+      bs_b0 = bs_nb = lane = 0;
       if (split) push_sync(bwd, K_JOIN, 1);
       stem_halves = nhalf;
     });
@@ -650,10 +626,9 @@ int flk_net::build_i3d() {
       if ((rc = new_act(Gpo, po.T, po.H, po.W, cur_c))) return rc;
       named[bk.pool_name] = {po, cur_c};
       named[std::string("grad:") + bk.pool_name] = {Gpo, cur_c};
-      const Act prev = cur, Gprev = Gcur;
+      const Act Gprev = Gcur;
       const std::string pn = bk.pool_name;
-      bwd_emit.push_back([this, pn, pr, Gpo, Gprev]() { emit_pool_bwd(pn, pr, Gpo, Gprev, nullptr); });
-      (void)prev;
+      bwd_emit.push_back([this, pn, pr, Gpo, Gprev]() { emit_pool_bwd(pn, pr, Gpo, Gprev); });
       cur = po; Gcur = Gpo; cur_is_relu = false;
     }
     const int c0 = bk.c[0], c1a = bk.c[1], c1b = bk.c[2], c2a = bk.c[3], c2b_ = bk.c[4], c3 = bk.c[5];
@@ -712,32 +687,20 @@ int flk_net::build_i3d() {
     if ((rc = new_act(Gpl, cur.T, cur.H, cur.W, cur_c)) || (rc = new_act(gxa, cur.T, cur.H, cur.W, cur_c))) return rc;
     PoolRec pr3;
     // forward: [b0 | b1 | b2 | b3] slices of `out` (tf.concat axis 4, i3d.py:219)
-    {
-      flk_conv_args a{};
-      a.in = cur.p; a.in_ld = cur.ld; a.cin = cur_c; a.B = B; a.Ti = cur.T; a.Hi = cur.H; a.Wi = cur.W;
-      a.kt = a.kh = a.kw = 1; a.st = a.sh = a.sw = 1;
-      a.To = cur.T; a.Ho = cur.H; a.Wo = cur.W; a.OT = cur.T; a.OH = cur.H; a.OW = cur.W; a.ost = a.osh = a.osw = 1;
-      a.out = out.p; a.out_ld = out.ld; a.out_coff = 0; a.cout = c0 + c1a + c2a;
-      a.out2 = mid.p; a.out2_ld = mid.ld; a.out2_coff = 0; a.cout1 = c0;
-      a.scale = Lf->d_scale; a.bias = Lf->d_bias; a.relu = 1;
-      const double macs = (double)B * cur.T * cur.H * cur.W * cur_c * (c0 + c1a + c2a);
-      flk_conv_weights* wf = Lf->wf;
-      const int dt = dtype;
-      fwd.push_back(Op{Lf->name, K_CONV, 2.0 * macs, conv_bytes(a), [a, wf, dt](hipStream_t s) { return flk_conv3d(&a, wf, dt, s); }});
-    }
     // The Branch_3 pool reads the block input only: it starts beside the fused 1x1x1 GEMM (98-392 workgroups, which leave CUs
     // idle) on side stream 2 and Branch_3's 1x1x1 follows it there.  The two 3x3x3 branches fork after the GEMM (disjoint
     // channel slices of `out`).
-    Op fused = std::move(fwd.back());
-    fwd.pop_back();
     push_sync(fwd, K_FORK, 2);
-    {
-      const size_t m0 = fwd.size();
-      if ((rc = emit_pool_fwd(bn + "/Branch_3/MaxPool3d_0a_3x3", cur, cur_c, 3, 3, 3, 1, 1, 1, pl, pr3))) return rc;
-      set_lane(fwd, m0, 2);
-    }
+    lane = 2;
+    if ((rc = emit_pool_fwd(bn + "/Branch_3/MaxPool3d_0a_3x3", cur, cur_c, 3, 3, 3, 1, 1, 1, pl, pr3))) return rc;
+    lane = 0;
     const bool grp_f = gf.nfw > 0, grp_b = gb.nfw > 0;
-    fwd.push_back(std::move(fused));
+    {
+      flk_conv_args a = conv_args(cur, 0, cur_c, out, 0, c0 + c1a + c2a, {1, 1, 1}, {1, 1, 1}, {0, 0, 0});
+      a.out2 = mid.p; a.out2_ld = mid.ld; a.out2_coff = 0; a.cout1 = c0;
+      a.scale = Lf->d_scale; a.bias = Lf->d_bias; a.relu = 1;
+      push_conv(fwd, Lf->name, a, Lf->wf, conv_macs(a));
+    }
     if (!grp_f) push_sync(fwd, K_FORK, 1);
     if (grp_f) {
       // Branch_1 and Branch_2 in one launch on the caller's stream; only Branch_3's pool -> 1x1x1 chain runs beside it (side stream 2)
@@ -745,9 +708,12 @@ int flk_net::build_i3d() {
                  L2b->wf, gf.nfw, gf.ring);
     } else {
       emit_conv_fwd(L1b, mid, 0, out, c0);
-      { const size_t m0 = fwd.size(); emit_conv_fwd(L2b, mid, c1a, out, c0 + c1b); set_lane(fwd, m0, 1); }
+      lane = 1;
+      emit_conv_fwd(L2b, mid, c1a, out, c0 + c1b);
     }
-    { const size_t m0 = fwd.size(); emit_conv_fwd(L3, pl, 0, out, c0 + c1b + c2b_); set_lane(fwd, m0, 2); }
+    lane = 2;
+    emit_conv_fwd(L3, pl, 0, out, c0 + c1b + c2b_);
+    lane = 0;
     push_sync(fwd, K_JOIN, grp_f ? 2 : ~0);
     named[bn] = {out, cout_total};
     named["grad:" + bn] = {Gout, cout_total};
@@ -773,8 +739,8 @@ int flk_net::build_i3d() {
     const int cur_c_blk = cur_c;
     bwd_emit.push_back([=]() {
       push_sync(bwd, K_FORK, grp_b ? 2 : ~0);
+      lane = 2;
       {
-        const size_t m0 = bwd.size();
         if (b3_fused) {
           // ONE kernel: the 1x1x1 data-gradient on MFMA inside the pool's scatter backward (pool.hip: maxpool_scatter_gemm_bwd)
           const flk_pool_args pa = pr3.a;
@@ -782,37 +748,31 @@ int flk_net::build_i3d() {
           const int gld = Gout.ld, gco = c0 + c1b + c2b_, gild = gxa.ld, K = c3;
           const double macs = (double)B * Gout.T * Gout.H * Gout.W * cur_c_blk * c3;
           const double bytes = ((double)B * Gout.T * Gout.H * Gout.W * (c3 + cur_c_blk)) * esz() + (double)B * Gout.T * Gout.H * Gout.W * cur_c_blk;
-          bwd.push_back(Op{pname + "/grad+Conv3d_0b_1x1/dgrad", K_POOL, 2.0 * macs, bytes, [pa, gp, gld, gco, K, wpg, gip, gild](hipStream_t s) {
-                             return flk_maxpool3d_bwd_gemm(&pa, gp, gld, gco, K, wpg, gip, gild, 0, FLK_BF16, s);
-                           }});
+          push(bwd, Op{pname + "/grad+Conv3d_0b_1x1/dgrad", K_POOL, 2.0 * macs, bytes, [pa, gp, gld, gco, K, wpg, gip, gild](hipStream_t s) {
+                 return flk_maxpool3d_bwd_gemm(&pa, gp, gld, gco, K, wpg, gip, gild, 0, FLK_BF16, s);
+               }});
         } else {
-          emit_conv_bwd(L3, Gout, c0 + c1b + c2b_, Gpl, 0, nullptr, 0, 0, nullptr, 0);
-          emit_pool_bwd(pname, pr3, Gpl, gxa, nullptr);
+          emit_conv_bwd(L3, Gout, c0 + c1b + c2b_, Gpl, 0, nullptr, 0);
+          emit_pool_bwd(pname, pr3, Gpl, gxa);
         }
-        set_lane(bwd, m0, 2);
       }
+      lane = 0;
       if (grp_b) {
         emit_group(bwd, bn + "/Branch_1+2/Conv3d_0b_3x3/dgrad", conv_bwd_args(L1b, Gout, c0, Gmid, 0, &mid, 0), L1b->wb,
                    conv_bwd_args(L2b, Gout, c0 + c1b, Gmid, c1a, &mid, c1a), L2b->wb, gb.nfw, gb.ring);
       } else {
-        { const size_t m0 = bwd.size(); emit_conv_bwd(L2b, Gout, c0 + c1b, Gmid, c1a, nullptr, 0, 0, &mid, c1a); set_lane(bwd, m0, 1); }
-        emit_conv_bwd(L1b, Gout, c0, Gmid, 0, nullptr, 0, 0, &mid, 0);
+        lane = 1;
+        emit_conv_bwd(L2b, Gout, c0 + c1b, Gmid, c1a, &mid, c1a);
+        lane = 0;
+        emit_conv_bwd(L1b, Gout, c0, Gmid, 0, &mid, 0);
       }
       push_sync(bwd, K_JOIN, grp_b ? 2 : ~0);
       {
-        flk_conv_args a{};
-        a.in = Gout.p; a.in_ld = Gout.ld; a.in_coff = 0; a.cin = c0 + c1a + c2a; a.cin1 = c0;
-        a.in2 = Gmid.p; a.in2_ld = Gmid.ld; a.in2_coff = 0;
-        a.B = B; a.Ti = Gout.T; a.Hi = Gout.H; a.Wi = Gout.W;
-        a.kt = a.kh = a.kw = 1; a.st = a.sh = a.sw = 1;
-        a.To = Gin.T; a.Ho = Gin.H; a.Wo = Gin.W; a.OT = Gin.T; a.OH = Gin.H; a.OW = Gin.W; a.ost = a.osh = a.osw = 1;
-        a.out = Gin.p; a.out_ld = Gin.ld; a.out_coff = 0; a.cout = Lf->cin;
+        flk_conv_args a = conv_args(Gout, 0, c0 + c1a + c2a, Gin, 0, Lf->cin, {1, 1, 1}, {1, 1, 1}, {0, 0, 0});
+        a.cin1 = c0; a.in2 = Gmid.p; a.in2_ld = Gmid.ld; a.in2_coff = 0;
         a.add = gxa.p; a.add_ld = gxa.ld; a.add_coff = 0;
-        if (in_relu) { a.mask = in_act.p; a.mask_ld = in_act.ld; a.mask_coff = 0; }
-        const double macs = (double)B * Gin.T * Gin.H * Gin.W * Lf->cin * (c0 + c1a + c2a);
-        flk_conv_weights* wb = Lf->wb;
-        const int dt = dtype;
-        bwd.push_back(Op{Lf->name + "/dgrad", K_CONV, 2.0 * macs, conv_bytes(a), [a, wb, dt](hipStream_t s) { return flk_conv3d(&a, wb, dt, s); }});
+        set_mask(a, in_relu ? &in_act : nullptr);
+        push_conv(bwd, Lf->name + "/dgrad", a, Lf->wb, conv_macs(a));
       }
     });
     cur = out; Gcur = Gout; cur_c = cout_total; cur_is_relu = true;
@@ -832,21 +792,9 @@ int flk_net::build_i3d() {
       wt[t] = (float)cover / (2.0f * 49.0f * (float)Tp);
     }
     if ((rc = upload(&d_wt, wt))) return rc;
-    if ((rc = dmalloc((void**)&d_feat, (size_t)B * cur_c * 4)) || (rc = dmalloc((void**)&d_dfeat, (size_t)B * cur_c * 4))) return rc;
-    const Act y = cur, Gy = Gcur;
-    const int C = cur_c, N = num_classes, dt = dtype;
-    fwd.push_back(Op{"Logits", K_HEAD, 0.0, (double)y.numel(B) * esz(), [this, y, C, N, Tn, dt](hipStream_t s) {
-                       return flk_head_forward(y.p, y.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, d_fcb, N, d_feat, logits_out, dt, s);
-                     }});
-    bwd_emit.push_back([this, y, Gy, C, N, Tn, dt]() {
-      bwd.push_back(Op{"Logits/grad", K_HEAD, 0.0, 2.0 * (double)y.numel(B) * esz(), [this, y, Gy, C, N, Tn, dt](hipStream_t s) {
-                         return flk_head_backward(y.p, y.ld, 0, Gy.p, Gy.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, N, dlogits_in,
-                                                  d_dfeat, 1, dt, s);
-                       }});
-    });
+    if ((rc = emit_head("Logits", cur, Gcur, cur_c, bwd_emit))) return rc;
   }
   for (auto it = bwd_emit.rbegin(); it != bwd_emit.rend(); ++it) (*it)();
-  (void)xin;
   for (size_t i = 0; i < bwd.size(); ++i)
     if (bwd[i].name == "Conv3d_1a_7x7/dgrad") stem_dgrad_op = (int)i;
   return FLK_OK;
@@ -928,21 +876,14 @@ int flk_net::pack_generic(ConvLayer* L) {
 }
 
 void flk_net::emit_gen_fwd(ConvLayer* L, const Act& in, const Act& out, bool relu, const Act* add) {
-  flk_conv_args a{};
-  a.in = in.p; a.in_ld = in.ld; a.cin = L->cin; a.B = B; a.Ti = in.T; a.Hi = in.H; a.Wi = in.W;
-  a.kt = L->kt; a.kh = L->kh; a.kw = L->kw; a.st = L->st; a.sh = L->sh; a.sw = L->sw; a.pt = L->pt; a.ph = L->ph; a.pw = L->pw;
-  a.To = out.T; a.Ho = out.H; a.Wo = out.W; a.OT = out.T; a.OH = out.H; a.OW = out.W; a.ost = a.osh = a.osw = 1;
-  a.out = out.p; a.out_ld = out.ld; a.cout = L->cout;
+  flk_conv_args a = conv_args(in, 0, L->cin, out, 0, L->cout, {L->kt, L->kh, L->kw}, {L->st, L->sh, L->sw}, {L->pt, L->ph, L->pw});
   a.scale = L->d_scale; a.bias = L->d_bias; a.relu = relu;
   if (add) { a.add = add->p; a.add_ld = add->ld; }
-  const double macs = (double)B * out.T * out.H * out.W * L->kt * L->kh * L->kw * L->cin * L->cout;
-  flk_conv_weights* wf = L->wf;
-  const int dt = dtype;
-  attach_splitk(a, wf);
-  fwd.push_back(Op{L->name, K_CONV, 2.0 * macs, conv_bytes(a), [a, wf, dt](hipStream_t s) { return flk_conv3d(&a, wf, dt, s); }});
+  attach_splitk(a, L->wf);
+  push_conv(fwd, L->name, a, L->wf, conv_macs(a));
 }
 
-void flk_net::emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const void* add, int add_ld, const Act* mask) {
+void flk_net::emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const Act* add, const Act* mask) {
   // The parity classes of a strided layer's data-gradient write disjoint output cells and are small launches on their latency floor.  The
   // EIGHT classes of a 3x3x3 / 2 layer (r3d_18 layer2-4.0) run side by side on the caller's stream and the two side streams: r3d_18 bs 8 2.91 ->
   // 2.81 ms per iteration.  With two or four classes ((3,1,1) / (2,1,1), (1,3,3) / (1,2,2): r2plus1d_18, mc3_18) the fork / join pair costs
@@ -951,24 +892,36 @@ void flk_net::emit_gen_bwd(ConvLayer* L, const Act& G, const Act& gin, const voi
   if (par) push_sync(bwd, K_FORK, ~0);
   int ci = 0;
   for (const auto& bc : L->bcls) {
-    flk_conv_args a{};
-    a.in = G.p; a.in_ld = G.ld; a.cin = L->cout; a.B = B; a.Ti = G.T; a.Hi = G.H; a.Wi = G.W;
-    a.kt = bc.kt; a.kh = bc.kh; a.kw = bc.kw; a.st = a.sh = a.sw = 1; a.pt = bc.pbt; a.ph = bc.pbh; a.pw = bc.pbw;
+    flk_conv_args a = conv_args(G, 0, L->cout, gin, 0, L->cin, {bc.kt, bc.kh, bc.kw}, {1, 1, 1}, {bc.pbt, bc.pbh, bc.pbw});
+    // the class's cells of the output: o * stride + class offset
     a.To = (gin.T - bc.ot + L->st - 1) / L->st; a.Ho = (gin.H - bc.oh + L->sh - 1) / L->sh; a.Wo = (gin.W - bc.ow + L->sw - 1) / L->sw;
     if (a.To <= 0 || a.Ho <= 0 || a.Wo <= 0) continue;
-    a.OT = gin.T; a.OH = gin.H; a.OW = gin.W; a.ost = L->st; a.osh = L->sh; a.osw = L->sw; a.oot = bc.ot; a.ooh = bc.oh; a.oow = bc.ow;
-    a.out = gin.p; a.out_ld = gin.ld; a.cout = L->cin;
-    a.add = add; a.add_ld = add_ld;
-    if (mask) { a.mask = mask->p; a.mask_ld = mask->ld; }
-    const double macs = (double)B * a.To * a.Ho * a.Wo * bc.kt * bc.kh * bc.kw * L->cin * L->cout;
-    flk_conv_weights* wb = bc.w;
-    const int dt = dtype;
-    attach_splitk(a, wb);
-    const size_t m0 = bwd.size();
-    bwd.push_back(Op{L->name + "/dgrad", K_CONV, 2.0 * macs, conv_bytes(a), [a, wb, dt](hipStream_t s) { return flk_conv3d(&a, wb, dt, s); }});
-    if (par) set_lane(bwd, m0, ci++ % (kSideStreams + 1));
+    a.ost = L->st; a.osh = L->sh; a.osw = L->sw; a.oot = bc.ot; a.ooh = bc.oh; a.oow = bc.ow;
+    if (add) { a.add = add->p; a.add_ld = add->ld; }
+    set_mask(a, mask);
+    attach_splitk(a, bc.w);
+    if (par) lane = ci++ % (kSideStreams + 1);
+    push_conv(bwd, L->name + "/dgrad", a, bc.w, conv_macs(a));
   }
+  lane = 0;
   if (par) push_sync(bwd, K_JOIN, ~0);
+}
+
+// the classifier head on `y` (time-weighted average pool + linear layer; d_wt, d_fcw and d_fcb are uploaded) and its gradient into Gy
+int flk_net::emit_head(const char* name, const Act& y, const Act& Gy, int C, std::vector<std::function<void()>>& bwd_emit) {
+  int rc;
+  if ((rc = dmalloc((void**)&d_feat, (size_t)B * C * 4)) || (rc = dmalloc((void**)&d_dfeat, (size_t)B * C * 4))) return rc;
+  const std::string nm = name;
+  const int N = num_classes, Tn = y.T, dt = dtype;
+  push(fwd, Op{nm, K_HEAD, 0.0, (double)y.numel(B) * esz(), [this, y, C, N, Tn, dt](hipStream_t s) {
+         return flk_head_forward(y.p, y.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, d_fcb, N, d_feat, logits_out, dt, s);
+       }});
+  bwd_emit.push_back([this, nm, y, Gy, C, N, Tn, dt]() {
+    push(bwd, Op{nm + "/grad", K_HEAD, 0.0, 2.0 * (double)y.numel(B) * esz(), [this, y, Gy, C, N, Tn, dt](hipStream_t s) {
+           return flk_head_backward(y.p, y.ld, 0, Gy.p, Gy.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, N, dlogits_in, d_dfeat, 1, dt, s);
+         }});
+  });
+  return FLK_OK;
 }
 
 int flk_net::build_videoresnet() {
@@ -1037,28 +990,23 @@ int flk_net::build_videoresnet() {
   if ((rc = new_act(a_st, T, H2, W2, stem->cout)) || (rc = new_act(G_st, T, H2, W2, stem->cout))) return rc;
   named[r21 ? "stem.mid" : "stem"] = {a_st, sc_out};
   {
-    flk_conv_args a{};
-    a.in_ld = in_ch; a.cin = in_ch; a.B = B; a.Ti = T; a.Hi = H2; a.Wi = W2;
-    a.kt = skt; a.kh = a.kw = 4; a.st = a.sh = a.sw = 1; a.pt = (skt - 1) / 2; a.ph = a.pw = 2;
-    a.To = T; a.Ho = H2; a.Wo = W2; a.OT = T; a.OH = H2; a.OW = W2; a.ost = a.osh = a.osw = 1;
-    a.out = a_st.p; a.out_ld = a_st.ld; a.cout = stem->cout; a.scale = stem->d_scale; a.bias = stem->d_bias; a.relu = 1;
+    Act xin, gxin;      // the folded clip and its gradient: geometry only, bound per call
+    xin.T = gxin.T = T; xin.H = gxin.H = H2; xin.W = gxin.W = W2; xin.ld = in_ch; gxin.ld = 16;
+    flk_conv_args a = conv_args(xin, 0, in_ch, a_st, 0, stem->cout, {skt, 4, 4}, {1, 1, 1}, {(skt - 1) / 2, 2, 2});
+    a.scale = stem->d_scale; a.bias = stem->d_bias; a.relu = 1;
     const double macs = (double)B * T * H2 * W2 * skt * 49.0 * 3 * sc_out;
     flk_conv_weights* wf = stem_wf;
     const int dt = dtype;
-    fwd.push_back(Op{"stem.0", K_CONV, 2.0 * macs, conv_bytes(a), [this, a, wf, dt](hipStream_t s) mutable {
-                       a.in = x_in;
-                       if (int rc = apply_slice(0, a.B, (void*)x_in, s)) return rc;
-                       return flk_conv3d(&a, wf, dt, s);
-                     }});
+    push_conv(fwd, "stem.0", a, wf, macs, [this, a, wf, dt](hipStream_t s) mutable {
+      a.in = x_in;
+      if (int rc = apply_slice(0, a.B, (void*)x_in, s)) return rc;
+      return flk_conv3d(&a, wf, dt, s);
+    });
     const ConvLayer::BwdClass bc = stem->bcls[0];
-    flk_conv_args g{};
-    g.in = G_st.p; g.in_ld = G_st.ld; g.cin = stem->cout; g.B = B; g.Ti = T; g.Hi = H2; g.Wi = W2;
-    g.kt = bc.kt; g.kh = bc.kh; g.kw = bc.kw; g.st = g.sh = g.sw = 1; g.pt = bc.pbt; g.ph = bc.pbh; g.pw = bc.pbw;
-    g.To = T; g.Ho = H2; g.Wo = W2; g.OT = T; g.OH = H2; g.OW = W2; g.ost = g.osh = g.osw = 1;
-    g.out_ld = 16; g.cout = 16;
+    flk_conv_args g = conv_args(G_st, 0, stem->cout, gxin, 0, 16, {bc.kt, bc.kh, bc.kw}, {1, 1, 1}, {bc.pbt, bc.pbh, bc.pbw});
     flk_conv_weights* wb = bc.w;
     bwd_emit.push_back([this, g, wb, dt, macs]() {
-      bwd.push_back(Op{"stem.0/dgrad", K_CONV, 2.0 * macs, conv_bytes(g), [this, g, wb, dt](hipStream_t s) mutable { g.out = gx_in; return flk_conv3d(&g, wb, dt, s); }});
+      push_conv(bwd, "stem.0/dgrad", g, wb, macs, [this, g, wb, dt](hipStream_t s) mutable { g.out = gx_in; return flk_conv3d(&g, wb, dt, s); });
     });
   }
   Act cur = a_st, Gcur = G_st;
@@ -1070,7 +1018,7 @@ int flk_net::build_videoresnet() {
     emit_gen_fwd(s3, cur, a2, true, nullptr);
     named["stem"] = {a2, 64};
     const Act prev = cur, Gprev = Gcur;
-    bwd_emit.push_back([this, s3, G2, Gprev, prev]() { emit_gen_bwd(s3, G2, Gprev, nullptr, 0, &prev); });
+    bwd_emit.push_back([this, s3, G2, Gprev, prev]() { emit_gen_bwd(s3, G2, Gprev, nullptr, &prev); });
     cur = a2; Gcur = G2;
   }
   named["grad:stem"] = {Gcur, 64};
@@ -1140,30 +1088,27 @@ int flk_net::build_videoresnet() {
       const bool k2 = kind == 2;
       bwd_emit.push_back([=]() {
         if (k2) {
-          emit_gen_bwd(u2.b, Gout, u2.Gmid, nullptr, 0, &u2.midact);
-          emit_gen_bwd(u2.a, u2.Gmid, Gh1, nullptr, 0, &h1);
+          emit_gen_bwd(u2.b, Gout, u2.Gmid, nullptr, &u2.midact);
+          emit_gen_bwd(u2.a, u2.Gmid, Gh1, nullptr, &h1);
         } else {
-          emit_gen_bwd(u2.a, Gout, Gh1, nullptr, 0, &h1);
+          emit_gen_bwd(u2.a, Gout, Gh1, nullptr, &h1);
         }
         // shortcut gradient first (plain), conv1's data-gradient then accumulates onto it and applies the ReLU mask
-        const void* addp; int addld;
         if (has_ds) {
           const size_t bytes = Gin.numel(B) * esz();
           void* gp = Gin.p;
-          bwd.push_back(Op{pre + ".downsample/zero", K_OTHER, 0.0, (double)bytes, [gp, bytes](hipStream_t s) {
-                             FLK_CHECK_HIP(hipMemsetAsync(gp, 0, bytes, s));
-                             return FLK_OK;
-                           }});
-          emit_gen_bwd(ds, Gout, Gin, nullptr, 0, nullptr);
-          addp = Gin.p; addld = Gin.ld;
-        } else {
-          addp = Gout.p; addld = Gout.ld;
+          push(bwd, Op{pre + ".downsample/zero", K_OTHER, 0.0, (double)bytes, [gp, bytes](hipStream_t s) {
+                 FLK_CHECK_HIP(hipMemsetAsync(gp, 0, bytes, s));
+                 return FLK_OK;
+               }});
+          emit_gen_bwd(ds, Gout, Gin, nullptr, nullptr);
         }
+        const Act& shortcut = has_ds ? Gin : Gout;
         if (k2) {
-          emit_gen_bwd(u1.b, Gh1, u1.Gmid, nullptr, 0, &u1.midact);
-          emit_gen_bwd(u1.a, u1.Gmid, Gin, addp, addld, &in_act);
+          emit_gen_bwd(u1.b, Gh1, u1.Gmid, nullptr, &u1.midact);
+          emit_gen_bwd(u1.a, u1.Gmid, Gin, &shortcut, &in_act);
         } else {
-          emit_gen_bwd(u1.a, Gh1, Gin, addp, addld, &in_act);
+          emit_gen_bwd(u1.a, Gh1, Gin, &shortcut, &in_act);
         }
       });
       cur = out; Gcur = Gout; inpl = planes;
@@ -1179,21 +1124,9 @@ int flk_net::build_videoresnet() {
     for (int n = 0; n < num_classes; ++n)
       for (int c = 0; c < 512; ++c) wT[(size_t)c * num_classes + n] = (*fw)[(size_t)n * 512 + c];
     if ((rc = upload(&d_fcw, wT)) || (rc = upload(&d_fcb, *fb))) return rc;
-    const int Tn = cur.T;
-    std::vector<float> wt(Tn, 1.0f / (float)(cur.T * cur.H * cur.W));
+    std::vector<float> wt(cur.T, 1.0f / (float)(cur.T * cur.H * cur.W));
     if ((rc = upload(&d_wt, wt))) return rc;
-    if ((rc = dmalloc((void**)&d_feat, (size_t)B * 512 * 4)) || (rc = dmalloc((void**)&d_dfeat, (size_t)B * 512 * 4))) return rc;
-    const Act y = cur, Gy = Gcur;
-    const int C = 512, N = num_classes, dt = dtype;
-    fwd.push_back(Op{"fc", K_HEAD, 0.0, (double)y.numel(B) * esz(), [this, y, C, N, Tn, dt](hipStream_t s) {
-                       return flk_head_forward(y.p, y.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, d_fcb, N, d_feat, logits_out, dt, s);
-                     }});
-    bwd_emit.push_back([this, y, Gy, N, Tn, dt]() {
-      const int C = 512;
-      bwd.push_back(Op{"fc/grad", K_HEAD, 0.0, 2.0 * (double)y.numel(B) * esz(), [this, y, Gy, C, N, Tn, dt](hipStream_t s) {
-                         return flk_head_backward(y.p, y.ld, 0, Gy.p, Gy.ld, 0, C, B, Tn, y.H * y.W, d_wt, d_fcw, N, dlogits_in, d_dfeat, 1, dt, s);
-                       }});
-    });
+    if ((rc = emit_head("fc", cur, Gcur, 512, bwd_emit))) return rc;
   }
   for (auto it = bwd_emit.rbegin(); it != bwd_emit.rend(); ++it) (*it)();
   return FLK_OK;
@@ -1284,7 +1217,7 @@ extern "C" int64_t flk_net_input_numel(const flk_net* n) {
 }
 extern "C" int flk_net_num_classes(const flk_net* n) { return n ? n->num_classes : 0; }
 extern "C" int flk_net_input_channels(const flk_net* n) { return !n ? 0 : n->arch == FLK_NET_I3D ? 32 : n->in_ch; }
-extern "C" int flk_net_input_fold(const flk_net* n) { return !n ? 0 : n->arch == FLK_NET_I3D ? 3 : n->in_ch == 32 ? 4 : 1; }
+extern "C" int flk_net_input_fold(const flk_net* n) { return n ? n->input_fold() : 0; }
 
 static int run_ops(flk_net* n, std::vector<Op>& ops, std::vector<std::pair<hipEvent_t, hipEvent_t>>& ev, bool& ev_valid, hipStream_t s,
                    int replace_op = -1, const std::function<int(hipStream_t)>* replacement = nullptr) {
@@ -1403,6 +1336,13 @@ static int run_ops(flk_net* n, std::vector<Op>& ops, std::vector<std::pair<hipEv
   return FLK_OK;
 }
 
+// do the apply arguments describe this plan's clips? (`fn`: the entry point, for the message)
+static int check_apply_geometry(const flk_net* n, const flk_apply_args* a, const char* fn) {
+  FLK_REQUIRE(a->B == n->B && a->T == n->T && a->H == n->H && a->W == n->W, "%s: apply args (%d,%d,%d,%d) do not match the "
+              "net (%d,%d,%d,%d)", fn, a->B, a->T, a->H, a->W, n->B, n->T, n->H, n->W);
+  return FLK_OK;
+}
+
 extern "C" int flk_net_has_forward_flicker(const flk_net* n) {
   static const bool off = getenv("FLK_STEM_CENTER") && atoi(getenv("FLK_STEM_CENTER")) == 0;
   return n && n->finalized && n->d_stem_sums && n->d_stem_tab && !off;
@@ -1426,9 +1366,8 @@ extern "C" int flk_net_forward_flicker(flk_net* n, const void* x_in, const flk_a
 
 extern "C" int flk_net_forward_apply(flk_net* n, const flk_apply_args* a, void* x_s2d_out, float* logits, void* stream) {
   FLK_REQUIRE(n && n->finalized && a && x_s2d_out && logits, "flk_net_forward_apply: bad argument / not finalized");
-  FLK_REQUIRE(a->B == n->B && a->T == n->T && a->H == n->H && a->W == n->W, "flk_net_forward_apply: apply args (%d,%d,%d,%d) do not match the "
-              "net (%d,%d,%d,%d)", a->B, a->T, a->H, a->W, n->B, n->T, n->H, n->W);
-  FLK_REQUIRE(a->fold_t == (n->arch == FLK_NET_I3D ? 3 : n->in_ch == 32 ? 4 : 1), "flk_net_forward_apply: fold_t %d is not this plan's input layout", a->fold_t);
+  if (int rc = check_apply_geometry(n, a, "flk_net_forward_apply")) return rc;
+  FLK_REQUIRE(a->fold_t == n->input_fold(), "flk_net_forward_apply: fold_t %d is not this plan's input layout", a->fold_t);
   n->cur_apply = a;
   const int rc = a->center ? flk_net_forward_flicker(n, x_s2d_out, a, logits, stream) : flk_net_forward(n, x_s2d_out, logits, 1, stream);
   n->cur_apply = nullptr;
@@ -1466,13 +1405,22 @@ static bool same_mask_args(const flk_apply_args& p, const flk_apply_args& q) {
          p.dclip_dev == q.dclip_dev && p.x_lut == q.x_lut;
 }
 
+// start the clip-mask pre-pass of the fused stem delta-gradient on the net's mask stream, behind everything queued on `s` so far (the
+// previous update of delta, the previous GEMM's reads of the scratch); ev_mask_done fires when the mask is in `scratch`
+static int start_mask_prepass(flk_net* n, const flk_apply_args* a, float* scratch, hipStream_t s) {
+  FLK_CHECK_HIP(hipEventRecord(n->ev_mask_fork, s));
+  FLK_CHECK_HIP(hipStreamWaitEvent(n->mask_stream, n->ev_mask_fork, 0));
+  if (int rc = flk_stem_delta_grad_mask(a, scratch, n->mask_stream)) return rc;
+  FLK_CHECK_HIP(hipEventRecord(n->ev_mask_done, n->mask_stream));
+  return FLK_OK;
+}
+
 // backward to the flickering perturbation: the stem's data-gradient op is replaced by the fused delta-gradient kernel
 // (stem_grad.hip), which runs in its place in the plan (same stream, same profile slot "Conv3d_1a_7x7/dgrad")
 extern "C" int flk_net_backward_delta(flk_net* n, const float* dlogits, const flk_apply_args* a, float* gdelta, float* partials, void* stream) {
   FLK_REQUIRE(n && n->finalized && dlogits && a && gdelta && partials, "flk_net_backward_delta: bad argument / not finalized");
   FLK_REQUIRE(n->d_stem_wf && n->stem_dgrad_op >= 0, "flk_net_backward_delta: only the I3D plan in bf16 has the fused stem delta-gradient");
-  FLK_REQUIRE(a->B == n->B && a->T == n->T && a->H == n->H && a->W == n->W, "flk_net_backward_delta: apply args (%d,%d,%d,%d) do not match the "
-              "net (%d,%d,%d,%d)", a->B, a->T, a->H, a->W, n->B, n->T, n->H, n->W);
+  if (int rc = check_apply_geometry(n, a, "flk_net_backward_delta")) return rc;
   if (!n->fwd_done) { flk_set_error("flk_net_backward_delta: no forward pass to differentiate"); return FLK_ESTATE; }
   n->dlogits_in = dlogits; n->gx_in = nullptr;
   const flk_apply_args ac = *a;
@@ -1487,13 +1435,8 @@ extern "C" int flk_net_backward_delta(flk_net* n, const float* dlogits, const fl
   // (flk_net_prepare_backward_delta with the same arguments and scratch: the mask has been on its way since before the forward pass)
   const bool prepared = n->premask && beside && n->premask_scratch == partials && same_mask_args(n->premask_args, ac);
   n->premask = false;
-  if (beside && !prepared) {
-    FLK_CHECK_HIP(hipEventRecord(n->ev_mask_fork, s));
-    FLK_CHECK_HIP(hipStreamWaitEvent(n->mask_stream, n->ev_mask_fork, 0));
-    int rc = flk_stem_delta_grad_mask(&ac, partials, n->mask_stream);
-    if (rc) return rc;
-    FLK_CHECK_HIP(hipEventRecord(n->ev_mask_done, n->mask_stream));
-  }
+  if (beside && !prepared)
+    if (int rc = start_mask_prepass(n, &ac, partials, s)) return rc;
   // the GEMM per half of the batch on the halves' own streams (multi-stream runs with the mask on its side stream only; as one launch
   // behind the join: 5.567 against 5.536 ms per step)
   const bool halves = beside && n->stem_halves == 2;
@@ -1520,15 +1463,10 @@ extern "C" int flk_net_backward_delta(flk_net* n, const float* dlogits, const fl
 extern "C" int flk_net_prepare_backward_delta(flk_net* n, const flk_apply_args* a, float* scratch, void* stream) {
   FLK_REQUIRE(n && n->finalized && a && scratch, "flk_net_prepare_backward_delta: bad argument / not finalized");
   FLK_REQUIRE(n->d_stem_wf && n->stem_dgrad_op >= 0, "flk_net_prepare_backward_delta: only the I3D plan in bf16 has the fused stem delta-gradient");
-  FLK_REQUIRE(a->B == n->B && a->T == n->T && a->H == n->H && a->W == n->W, "flk_net_prepare_backward_delta: apply args (%d,%d,%d,%d) do not match "
-              "the net (%d,%d,%d,%d)", a->B, a->T, a->H, a->W, n->B, n->T, n->H, n->W);
+  if (int rc = check_apply_geometry(n, a, "flk_net_prepare_backward_delta")) return rc;
   n->premask = false;
   if (!(n->multi_stream && n->mask_stream && !n->profile)) return FLK_OK;
-  hipStream_t s = (hipStream_t)stream;
-  FLK_CHECK_HIP(hipEventRecord(n->ev_mask_fork, s));          // behind everything queued so far: the previous update of delta, the previous GEMM's reads
-  FLK_CHECK_HIP(hipStreamWaitEvent(n->mask_stream, n->ev_mask_fork, 0));
-  if (int rc = flk_stem_delta_grad_mask(a, scratch, n->mask_stream)) return rc;
-  FLK_CHECK_HIP(hipEventRecord(n->ev_mask_done, n->mask_stream));
+  if (int rc = start_mask_prepass(n, a, scratch, (hipStream_t)stream)) return rc;
   n->premask = true; n->premask_scratch = scratch; n->premask_args = *a;
   return FLK_OK;
 }

@@ -3,6 +3,7 @@
 // for all four architectures, and one forward / backward launch sequence each (launches are dropped by the stub) --
 // so that every host-side index computation, upload size and free() runs under ASan + LeakSanitizer.
 //   abi_driver <weights file>...   (file: records of  int32 name_len | name | int64 numel | float[numel] , written by the test)
+// With FLK_STUB_TRACE set (hip_stub.cpp traces the launches) every plan's workspace size and operator table are printed as well.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -156,6 +157,7 @@ static void plan(int arch, int dtype, int B, int T, int HW, const std::map<std::
          flk_net_backward(n, dl.data(), gx.data(), nullptr) == FLK_OK, "%s profiled pass", tag);
   std::vector<char> js(1 << 20);
   EXPECT(flk_net_profile_read(n, js.data(), (int64_t)js.size()) == FLK_OK && js[0] == '[', "%s profile_read", tag);
+  if (getenv("FLK_STUB_TRACE")) printf("%s: workspace %lld bytes\n%s\n", tag, (long long)flk_net_workspace_bytes(n), js.data());
   EXPECT(flk_net_profile_read(n, js.data(), 16) == FLK_EINVAL, "%s profile_read small buffer", tag);
   flk_net_profile(n, 0);
   int64_t dims[5];
@@ -230,11 +232,16 @@ int main(int argc, char** argv) {
       plan(FLK_NET_I3D, FLK_BF16, 2, 16, 224, W, "i3d bf16 bs2");
       plan(FLK_NET_I3D, FLK_BF16, 4, 16, 224, W, "i3d bf16 bs4 (stem split)");
       plan(FLK_NET_I3D, FLK_F32, 1, 18, 224, W, "i3d f32 T18");
+      // the benchmark geometries: grouped, producer / consumer and split-K launches, 96-channel tiles
+      plan(FLK_NET_I3D, FLK_BF16, 8, 64, 224, W, "i3d bf16 bs8 T64");
+      plan(FLK_NET_I3D, FLK_BF16, 1, 64, 224, W, "i3d bf16 bs1 T64");
+      plan(FLK_NET_I3D, FLK_BF16, 8, 90, 224, W, "i3d bf16 bs8 T90");
     } else {
       const bool r21 = W.count("stem.3.weight") > 0, mc3 = !r21 && W.at("layer2.0.conv1.0.weight").size() == (size_t)128 * 64 * 9;
       const int arch = r21 ? FLK_NET_R2PLUS1D_18 : mc3 ? FLK_NET_MC3_18 : FLK_NET_R3D_18;
       plan(arch, FLK_BF16, 1, 16, 112, W, r21 ? "r2plus1d_18 bf16" : mc3 ? "mc3_18 bf16" : "r3d_18 bf16");
       plan(arch, FLK_F32, 2, 8, 112, W, r21 ? "r2plus1d_18 f32" : mc3 ? "mc3_18 f32" : "r3d_18 f32");
+      plan(arch, FLK_BF16, 8, 16, 112, W, r21 ? "r2plus1d_18 bf16 bs8" : mc3 ? "mc3_18 bf16 bs8" : "r3d_18 bf16 bs8");
     }
   }
   EXPECT(flk_stub_live_allocs() == 0, "%ld device allocations alive at exit", flk_stub_live_allocs());
