@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("FLK_LIB_PATH") or os.path.join(HERE, "libflicker_hip.
 
 FLK_F32, FLK_BF16 = 0, 1
 FLK_NET_I3D, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18, FLK_NET_MC3_18, FLK_NET_R2PLUS1D_34 = 0, 1, 2, 3, 4
-FLK_PREP_MAX_CLIPS = 64      # clips per flk_clip_prepare launch
+FLK_PREP_MAX_CLIPS = 64      # clips per flk_clip_prepare / flk_clip_prepare_train launch
 
 
 class FlickerHipError(RuntimeError):
@@ -85,6 +85,10 @@ class PrepareArgs(C.Structure):
                 ("out_clip_offset", C.c_int64), ("out_clip_stride", C.c_int64), ("clips", C.POINTER(PrepClip))]
 
 
+class PrepBox(C.Structure):
+    _fields_ = [("i", C.c_int), ("j", C.c_int), ("h", C.c_int), ("w", C.c_int), ("flip", C.c_int)]
+
+
 _SIGS = {
     "flk_version": (C.c_int, []),
     "flk_last_error": (C.c_char_p, []),
@@ -106,6 +110,7 @@ _SIGS = {
     "flk_perturb_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
     "flk_pack_batch_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

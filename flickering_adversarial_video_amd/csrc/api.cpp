@@ -152,28 +152,49 @@ extern "C" int flk_conv_weights_destroy(flk_conv_weights* w) {
 
 // Clip preparation (csrc/prepare.hip): every argument is checked here, on the host, before anything touches the device.
 int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t stream);
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, hipStream_t stream);
 
-extern "C" int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream) {
-  FLK_REQUIRE(a && out, "flk_clip_prepare: null argument");
-  FLK_REQUIRE(a->clips, "flk_clip_prepare: null clip list");
-  FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "flk_clip_prepare: nclip %d outside 1..%d", a->nclip, FLK_PREP_MAX_CLIPS);
-  FLK_REQUIRE(a->Ho > 0 && a->Wo > 0, "flk_clip_prepare: output size %d x %d", a->Ho, a->Wo);
+// the checks the two entries share; `boxes`: the training entry's crop boxes, which take the place of the centre-crop window
+static int check_prepare_args(const char* fn, const flk_prepare_args* a, const float* out, const flk_prep_box* boxes) {
+  FLK_REQUIRE(a && out, "%s: null argument", fn);
+  FLK_REQUIRE(a->clips, "%s: null clip list", fn);
+  FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", fn, a->nclip, FLK_PREP_MAX_CLIPS);
+  FLK_REQUIRE(a->Ho > 0 && a->Wo > 0, "%s: output size %d x %d", fn, a->Ho, a->Wo);
   for (int k = 0; k < 3; ++k) {
-    FLK_REQUIRE(a->std[k] > 0.f && a->std[k] <= 3.4e38f, "flk_clip_prepare: std[%d] must be positive", k);
-    FLK_REQUIRE(a->mean[k] >= -3.4e38f && a->mean[k] <= 3.4e38f, "flk_clip_prepare: mean[%d] is not finite", k);
+    FLK_REQUIRE(a->std[k] > 0.f && a->std[k] <= 3.4e38f, "%s: std[%d] must be positive", fn, k);
+    FLK_REQUIRE(a->mean[k] >= -3.4e38f && a->mean[k] <= 3.4e38f, "%s: mean[%d] is not finite", fn, k);
   }
-  FLK_REQUIRE(a->out_clip_offset >= 0, "flk_clip_prepare: negative out_clip_offset");
+  FLK_REQUIRE(a->out_clip_offset >= 0, "%s: negative out_clip_offset", fn);
   for (int i = 0; i < a->nclip; ++i) {
     const flk_prep_clip& c = a->clips[i];
-    FLK_REQUIRE(c.src, "flk_clip_prepare: clip %d: null source", i);
-    FLK_REQUIRE(c.T > 0 && c.Hs > 0 && c.Ws > 0, "flk_clip_prepare: clip %d: source size %d x %d x %d", i, c.T, c.Hs, c.Ws);
+    FLK_REQUIRE(c.src, "%s: clip %d: null source", fn, i);
+    FLK_REQUIRE(c.T > 0 && c.Hs > 0 && c.Ws > 0, "%s: clip %d: source size %d x %d x %d", fn, i, c.T, c.Hs, c.Ws);
     FLK_REQUIRE(c.pitch_h >= (int64_t)c.Ws * 3 && c.pitch_h <= 0x7fffffff && c.pitch_t > 0,
-                "flk_clip_prepare: clip %d: pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", i, (long long)c.pitch_t, (long long)c.pitch_h);
-    FLK_REQUIRE(c.step_h > 0.f && c.step_w > 0.f && c.step_h <= 3.4e38f && c.step_w <= 3.4e38f, "flk_clip_prepare: clip %d: steps must be positive and finite", i);
-    FLK_REQUIRE(c.Hr > 0 && c.Wr > 0, "flk_clip_prepare: clip %d: resized size %d x %d", i, c.Hr, c.Wr);
-    FLK_REQUIRE(c.crop_i >= 0 && c.crop_j >= 0 && (int64_t)c.crop_i + a->Ho <= c.Hr && (int64_t)c.crop_j + a->Wo <= c.Wr,
-                "flk_clip_prepare: clip %d: crop window (%d,%d)+%dx%d outside the resized image %d x %d", i, c.crop_i, c.crop_j, a->Ho, a->Wo, c.Hr, c.Wr);
-    FLK_REQUIRE(a->out_clip_stride >= (int64_t)c.T * a->Ho * a->Wo * 3, "flk_clip_prepare: clip %d: out_clip_stride %lld smaller than the clip", i, (long long)a->out_clip_stride);
+                "%s: clip %d: pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i, (long long)c.pitch_t, (long long)c.pitch_h);
+    FLK_REQUIRE(c.step_h > 0.f && c.step_w > 0.f && c.step_h <= 3.4e38f && c.step_w <= 3.4e38f, "%s: clip %d: steps must be positive and finite", fn, i);
+    FLK_REQUIRE(c.Hr > 0 && c.Wr > 0, "%s: clip %d: resized size %d x %d", fn, i, c.Hr, c.Wr);
+    if (boxes) {
+      const flk_prep_box& b = boxes[i];
+      FLK_REQUIRE(b.h >= 1 && b.w >= 1, "%s: clip %d: box size %d x %d", fn, i, b.h, b.w);
+      FLK_REQUIRE(b.i >= 0 && b.j >= 0 && (int64_t)b.i + b.h <= c.Hr && (int64_t)b.j + b.w <= c.Wr,
+                  "%s: clip %d: box (%d,%d)+%dx%d outside the resized image %d x %d", fn, i, b.i, b.j, b.h, b.w, c.Hr, c.Wr);
+      FLK_REQUIRE(b.flip == 0 || b.flip == 1, "%s: clip %d: flip %d is not 0 / 1", fn, i, b.flip);
+    } else {
+      FLK_REQUIRE(c.crop_i >= 0 && c.crop_j >= 0 && (int64_t)c.crop_i + a->Ho <= c.Hr && (int64_t)c.crop_j + a->Wo <= c.Wr,
+                  "%s: clip %d: crop window (%d,%d)+%dx%d outside the resized image %d x %d", fn, i, c.crop_i, c.crop_j, a->Ho, a->Wo, c.Hr, c.Wr);
+    }
+    FLK_REQUIRE(a->out_clip_stride >= (int64_t)c.T * a->Ho * a->Wo * 3, "%s: clip %d: out_clip_stride %lld smaller than the clip", fn, i, (long long)a->out_clip_stride);
   }
+  return FLK_OK;
+}
+
+extern "C" int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream) {
+  if (int rc = check_prepare_args("flk_clip_prepare", a, out, nullptr)) return rc;
   return flk_clip_prepare_launch(a, out, (hipStream_t)stream);
+}
+
+extern "C" int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, void* stream) {
+  FLK_REQUIRE(boxes, "flk_clip_prepare_train: null box list");
+  if (int rc = check_prepare_args("flk_clip_prepare_train", a, out, boxes)) return rc;
+  return flk_clip_prepare_train_launch(a, boxes, out, (hipStream_t)stream);
 }

@@ -18,6 +18,8 @@
 // clip at 240x320 about 2 MB of source bytes under the window are read and 2.4 MB written.
 // Every output element is a pure function of its own coordinates: the result does not depend on `rows` or on the grid.
 // No atomics, no allocation, no host synchronisation.
+//
+// Second kernel, further down: clip_prepare_train_kernel, the training transform (a resampled crop box and a flip per clip).
 #include <math.h>
 #include "flk_internal.h"
 
@@ -177,6 +179,325 @@ int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t s
   const size_t lds = (size_t)(256 + 2 * rows) * 4 + (size_t)2 * rows * seg_stride;
   const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
   FLK_LAUNCH_KERNEL(clip_prepare_kernel, grid, dim3(256), lds, stream, p);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The training transform (dataset.py:105-118): ToTensorVideo -> ResizeVideo -> RandomResizedCropVideo / RandomCropVideo ->
+// RandomHorizontalFlipVideo -> NormalizeVideo.  The random draws are the host's (videoresnet_spec.train_crop_params); the kernel takes a
+// box (i, j, h, w) in the resized image and a flip per clip.  Two bilinear resamplings fused: neither the resized image nor the
+// cropped box reaches HBM.
+//
+// Arithmetic (fp32):
+//   stage 1   R[y, x] = the resized image at (i + y, j + x): clip_prepare_kernel's own sequence before its normalisation -- prep_src, the
+//             /255 table, blend along W within the two source rows, then along H; every blend w0 * v0 + w1 * v1 is fma(w0, v0, w1 * v1)
+//             (prep_blend), in both stages
+//   stage 2   step2 = float(h) / float(Ho) per axis (a float32 division: F.interpolate(size=...)); src = prep_src(step2, d);
+//             y0 = min(int(src), h - 1), y1 = min(y0 + 1, h - 1), lambda = clamp(src - y0, 0, 1);
+//             v = (1-lh) * ((1-lw) R[y0,x0] + lw R[y0,x1]) + lh * ((1-lw) R[y1,x0] + lw R[y1,x1])
+//   flip      output column ow takes the value computed for column Wo - 1 - ow
+//   out       (v - mean[c]) / std[c], true division
+//
+// Layout chosen: workgroup = (`rows` consecutive output rows, frame t, clip), 256 threads, three phases with a barrier between them.
+//   A  stage the source-row byte segments under the box (columns [x0, x0 + span), aligned dwords, the misalignment kept per row as
+//      clip_prepare_kernel does): two source rows per intermediate row.
+//   B  one thread per intermediate pixel: R[y, 0..w) for the workgroup's intermediate rows, float32, into LDS (3 floats per thread at
+//      a stride of 3 words: no bank conflicts).
+//   C  four consecutive output floats per thread and pass from R, one 16-byte store.
+// Intermediate rows: when the rows y0(first output row) .. y1(last output row) of the box are no more than the 2 * rows slots, the
+// workgroup computes that contiguous range once (neighbouring output rows share rows whenever the box is resampled by a step below 2:
+// at the default sampler's steps of 1.0 .. 1.3 and 3 rows per workgroup about 5 rows instead of 6); otherwise slot 2r + s holds row y_s of output row r.  R[y, x]
+// is a pure function of (y, x) and the clip's parameters, so the two forms, any `rows` and any grid give the same bits.
+// A box of the output size skips B and the second stage: C then is clip_prepare_kernel's own loop on the staged bytes (the reason is
+// written at that loop).
+// LDS at 240x320 -> 128x170 with the whole width under the box: 6 slots x (2 x 968 source bytes + 2040 bytes of R) = 24 KB, 6
+// workgroups per CU.  No atomics, no allocation, no host synchronisation; all addressing inside [0, Hs) x [0, Ws) of the clip's view.
+namespace {
+
+struct PrepTrainClipDev {     // 56 bytes; FLK_PREP_MAX_CLIPS of them travel by value in the kernel argument
+  const uint8_t* src;
+  long long pitch_t;          // bytes between frames
+  int pitch_h;                // bytes between rows
+  int T, Hs, Ws;
+  float step_h, step_w;       // stage 1: source step per resized pixel
+  int i, j, h, w;             // the box in the resized image
+};
+
+struct PrepTrainLaunch {
+  float* out;                 // already offset to the first clip row written
+  long long clip_stride;      // floats between clips
+  unsigned long long flips;   // bit k: clip k is flipped along W
+  int Ho, Wo, rows, seg_stride, r_stride, vec;       // r_stride: floats between intermediate rows in LDS
+  float mean[3], std_[3];
+  PrepTrainClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(FLK_PREP_MAX_CLIPS <= 64, "one flip bit per clip");
+static_assert(sizeof(PrepTrainLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+// source columns under the box: [x0, x0 + span); the same fp32 sequence on the host (LDS sizing) and in the kernel
+__host__ __device__ inline void prep_train_span(float step_w, int j, int w, int Ws, int* x0, int* span) {
+#ifdef __HIP_DEVICE_COMPILE__
+  const float s0 = prep_src(step_w, j), s1 = prep_src(step_w, j + w - 1);
+#else
+  const float s0 = prep_src_host(step_w, j), s1 = prep_src_host(step_w, j + w - 1);
+#endif
+  const int a = s0 >= (float)(Ws - 1) ? Ws - 1 : (int)s0;
+  const int l = s1 >= (float)(Ws - 1) ? Ws - 1 : (int)s1;
+  *x0 = a;
+  *span = (l + 1 < Ws ? l + 1 : Ws - 1) - a + 1;
+}
+
+// w0 * v0 + w1 * v1 as ONE fixed sequence, fma(w0, v0, w1 * v1).  Left as a plain expression the compiler fuses it one way for some
+// of a thread's four unrolled elements and another way for the rest (it does in clip_prepare_kernel): a flipped clip, whose values
+// are computed at other positions of the loop, would then not be the unflipped clip reversed.
+__device__ __forceinline__ float prep_blend(float w0, float v0, float w1, float v1) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(w0, v0, w1 * v1);
+}
+
+__global__ __launch_bounds__(256) void clip_prepare_train_kernel(const PrepTrainLaunch p) {
+  // [256] fp32 table u8 / 255 | [2 * cap] segment misalignments | 2 * cap source-row segments | cap intermediate rows (cap = 2 * rows)
+  extern __shared__ unsigned prep_train_lds[];
+  const PrepTrainClipDev& c = p.clip[blockIdx.z];
+  const int t = blockIdx.y;
+  if (t >= c.T) return;
+  const int cap = 2 * p.rows;
+  float* tab = (float*)prep_train_lds;
+  int* mis_of = (int*)(prep_train_lds + 256);
+  unsigned* seg = prep_train_lds + 256 + 2 * cap;
+  const uint8_t* segb = (const uint8_t*)seg;
+  const int ndw = p.seg_stride >> 2;
+  float* R = (float*)(seg + 2 * cap * ndw);
+  tab[threadIdx.x] = (float)threadIdx.x / 255.0f;
+  const int oh0 = blockIdx.x * p.rows;
+  const int nrow = min(p.rows, p.Ho - oh0);
+  const float step2_h = __fdiv_rn((float)c.h, (float)p.Ho), step2_w = __fdiv_rn((float)c.w, (float)p.Wo);
+  const bool flip = (p.flips >> blockIdx.z) & 1ull;
+  // ---- the workgroup's intermediate rows (rows of the box): the range [ya, yb] when it fits the slots, else a pair per output row ----
+  auto y0_of = [&](int oh) { return min((int)prep_src(step2_h, oh), c.h - 1); };
+  // a box of the output size (RandomCropVideo; the evaluation transform's own window): stage 2 is the identity and is not run -- the
+  // output rows are the resized rows i + oh themselves, computed straight from the staged bytes (see below)
+  const bool direct = c.h == p.Ho && c.w == p.Wo;
+  const int ya = direct ? oh0 : y0_of(oh0), yb = direct ? oh0 + nrow - 1 : min(y0_of(oh0 + nrow - 1) + 1, c.h - 1);
+  const bool range = yb - ya + 1 <= cap;
+  const int ni = range ? yb - ya + 1 : 2 * nrow;
+  auto slot_y = [&](int s) {
+    if (range) return ya + s;
+    const int y = y0_of(oh0 + (s >> 1));
+    return (s & 1) ? min(y + 1, c.h - 1) : y;
+  };
+  int x0, span;
+  prep_train_span(c.step_w, c.j, c.w, c.Ws, &x0, &span);
+  const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+  const int nbytes = span * 3;
+  // ---- A: segment 2s + v = source row v (0 top, 1 bottom) of intermediate slot s; columns [x0, x0 + span) ----
+  for (int k = threadIdx.x; k < 2 * ni * ndw; k += 256) {
+    const int q = k / ndw, w = k - q * ndw;
+    int h = min((int)prep_src(c.step_h, c.i + slot_y(q >> 1)), c.Hs - 1);
+    if (q & 1) h = min(h + 1, c.Hs - 1);
+    const uint8_t* row = frame + (long long)h * c.pitch_h + x0 * 3;
+    const int mis = (int)((size_t)row & 3);
+    if (w == 0) mis_of[q] = mis;
+    // aligned dwords that hold at least one byte of the segment: never beyond the dword of its last byte
+    if (4 * w < mis + nbytes) seg[q * ndw + w] = *(const unsigned*)(row - mis + 4 * w);
+  }
+  __syncthreads();
+  if (direct) {
+    // ---- the evaluation kernel's compute loop on the box's rows: slot r of the range is output row oh0 + r.  This is
+    // clip_prepare_kernel's loop statement for statement, on purpose: its blend is written as plain expressions, which the compiler
+    // contracts into fused multiply-adds differently for the four unrolled elements, so only the same statements reproduce its bits
+    // (the identity tests/test_clip_prepare_train_gpu.py pins).  Every value is computed at its UNFLIPPED position and stored
+    // mirrored, so a flipped clip is the unflipped one reversed, bit for bit. ----
+    const int rowlen = p.Wo * 3, nfl = nrow * rowlen;
+    float* dst = p.out + (long long)blockIdx.z * p.clip_stride + ((long long)t * p.Ho + oh0) * rowlen;
+    for (int e = threadIdx.x * 4; e < nfl; e += 1024) {
+      int r = e / rowlen;
+      const int rem = e - r * rowlen;
+      int ow = rem / 3, ch = rem - ow * 3;
+      float lh = 0.f, lw = 0.f;
+      const uint8_t *top = segb, *bot = segb;
+      int o0 = 0, o1 = 0;
+      auto row_state = [&]() {
+        const float sh = prep_src(c.step_h, c.i + oh0 + r);
+        const int h0 = min((int)sh, c.Hs - 1);
+        lh = clamp01(sh - (float)h0);
+        top = segb + (2 * r) * p.seg_stride + mis_of[2 * r];
+        bot = segb + (2 * r + 1) * p.seg_stride + mis_of[2 * r + 1];
+      };
+      auto col_state = [&]() {
+        const float sw = prep_src(c.step_w, c.j + ow);
+        const int i0 = min((int)sw, c.Ws - 1), i1 = min(i0 + 1, c.Ws - 1);
+        lw = clamp01(sw - (float)i0);
+        o0 = min(max(i0 - x0, 0), span - 1) * 3;
+        o1 = min(max(i1 - x0, 0), span - 1) * 3;
+      };
+      row_state();
+      col_state();
+      float v[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        v[j] = 0.f;
+        if (e + j < nfl) {
+          const float w0 = 1.f - lw, h0w = 1.f - lh;
+          const float a = w0 * tab[top[o0 + ch]] + lw * tab[top[o1 + ch]];
+          const float b = w0 * tab[bot[o0 + ch]] + lw * tab[bot[o1 + ch]];
+          const float x = h0w * a + lh * b;
+          const float mean = ch == 0 ? p.mean[0] : ch == 1 ? p.mean[1] : p.mean[2];
+          const float sd = ch == 0 ? p.std_[0] : ch == 1 ? p.std_[1] : p.std_[2];
+          v[j] = (x - mean) / sd;
+          if (++ch == 3) {
+            ch = 0;
+            if (++ow == p.Wo) {
+              ow = 0;
+              ++r;
+              if (e + j + 1 < nfl) row_state();
+            }
+            if (e + j + 1 < nfl) col_state();
+          }
+        }
+      }
+      if (flip) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (e + j < nfl) {
+            const int fr = (e + j) / rowlen, frem = (e + j) - fr * rowlen, fw = frem / 3;
+            dst[fr * rowlen + (p.Wo - 1 - fw) * 3 + (frem - fw * 3)] = v[j];
+          }
+      } else if (p.vec && e + 3 < nfl) {
+        *(f32x4*)(dst + e) = f32x4{v[0], v[1], v[2], v[3]};
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (e + j < nfl) dst[e + j] = v[j];
+      }
+    }
+    return;
+  }
+  // ---- B: R[slot][x][ch] = the resized image at (i + y, j + x), one pixel per thread and pass ----
+  for (int k = threadIdx.x; k < ni * c.w; k += 256) {
+    const int s = k / c.w, x = k - s * c.w;
+    const float sh = prep_src(c.step_h, c.i + slot_y(s));
+    const float lh = clamp01(sh - (float)min((int)sh, c.Hs - 1));
+    const uint8_t* top = segb + (2 * s) * p.seg_stride + mis_of[2 * s];
+    const uint8_t* bot = segb + (2 * s + 1) * p.seg_stride + mis_of[2 * s + 1];
+    const float sw = prep_src(c.step_w, c.j + x);
+    const int i0 = min((int)sw, c.Ws - 1), i1 = min(i0 + 1, c.Ws - 1);
+    const float lw = clamp01(sw - (float)i0);
+    const int o0 = min(max(i0 - x0, 0), span - 1) * 3;
+    const int o1 = min(max(i1 - x0, 0), span - 1) * 3;
+    float* r = R + s * p.r_stride + x * 3;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float w0 = 1.f - lw, h0w = 1.f - lh;
+      const float a = prep_blend(w0, tab[top[o0 + ch]], lw, tab[top[o1 + ch]]);
+      const float b = prep_blend(w0, tab[bot[o0 + ch]], lw, tab[bot[o1 + ch]]);
+      r[ch] = prep_blend(h0w, a, lh, b);
+    }
+  }
+  __syncthreads();
+  // ---- C: four consecutive floats of the workgroup's contiguous output run per thread and pass ----
+  const int rowlen = p.Wo * 3, nfl = nrow * rowlen;
+  float* dst = p.out + (long long)blockIdx.z * p.clip_stride + ((long long)t * p.Ho + oh0) * rowlen;
+  for (int e = threadIdx.x * 4; e < nfl; e += 1024) {
+    int r = e / rowlen;
+    const int rem = e - r * rowlen;
+    int ow = rem / 3, ch = rem - ow * 3;
+    float lh = 0.f, lw = 0.f;
+    const float *top = R, *bot = R;
+    int o0 = 0, o1 = 0;
+    auto row_state = [&]() {
+      const float sy = prep_src(step2_h, oh0 + r);
+      const int y0 = min((int)sy, c.h - 1), y1 = min(y0 + 1, c.h - 1);
+      lh = clamp01(sy - (float)y0);
+      top = R + (range ? y0 - ya : 2 * r) * p.r_stride;
+      bot = R + (range ? y1 - ya : 2 * r + 1) * p.r_stride;
+    };
+    auto col_state = [&]() {
+      const float sx = prep_src(step2_w, flip ? p.Wo - 1 - ow : ow);
+      const int b0 = min((int)sx, c.w - 1), b1 = min(b0 + 1, c.w - 1);
+      lw = clamp01(sx - (float)b0);
+      o0 = b0 * 3;
+      o1 = b1 * 3;
+    };
+    row_state();
+    col_state();
+    float v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[j] = 0.f;
+      if (e + j < nfl) {
+        const float w0 = 1.f - lw, h0w = 1.f - lh;
+        const float a = prep_blend(w0, top[o0 + ch], lw, top[o1 + ch]);
+        const float b = prep_blend(w0, bot[o0 + ch], lw, bot[o1 + ch]);
+        const float x = prep_blend(h0w, a, lh, b);
+        const float mean = ch == 0 ? p.mean[0] : ch == 1 ? p.mean[1] : p.mean[2];
+        const float sd = ch == 0 ? p.std_[0] : ch == 1 ? p.std_[1] : p.std_[2];
+        v[j] = (x - mean) / sd;
+        if (++ch == 3) {
+          ch = 0;
+          if (++ow == p.Wo) {
+            ow = 0;
+            ++r;
+            if (e + j + 1 < nfl) row_state();
+          }
+          if (e + j + 1 < nfl) col_state();
+        }
+      }
+    }
+    if (p.vec && e + 3 < nfl) {
+      *(f32x4*)(dst + e) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j < nfl) dst[e + j] = v[j];
+    }
+  }
+}
+
+}  // namespace
+
+#ifndef FLK_PREP_TRAIN_ROWS
+#define FLK_PREP_TRAIN_ROWS 3       // output rows per workgroup (the result does not depend on it).  3 rows of 112 x 3 floats are 252 four-float
+                                    // items, one full pass of the 256 threads in phase C; measured 62.7 us against 65.3 (4 rows) and 82.8 (6 rows)
+                                    // per launch of 16 clips of 16 x 240 x 320 (tools/prepare_time.py)
+#endif
+
+// arguments already validated (api.cpp: flk_clip_prepare_train); everything here up to the launch is host arithmetic
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, hipStream_t stream) {
+  PrepTrainLaunch p;
+  int max_span = 1, max_T = 1, max_w = 1;
+  p.flips = 0;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_prep_clip& s = a->clips[i];
+    const flk_prep_box& b = boxes[i];
+    PrepTrainClipDev& d = p.clip[i];
+    d.src = s.src; d.pitch_t = s.pitch_t; d.pitch_h = (int)s.pitch_h;
+    d.T = s.T; d.Hs = s.Hs; d.Ws = s.Ws;
+    d.step_h = s.step_h; d.step_w = s.step_w;
+    d.i = b.i; d.j = b.j; d.h = b.h; d.w = b.w;
+    if (b.flip) p.flips |= 1ull << i;
+    int x0, span;
+    prep_train_span(s.step_w, b.j, b.w, s.Ws, &x0, &span);
+    if (span > max_span) max_span = span;
+    if (b.w > max_w) max_w = b.w;
+    if (s.T > max_T) max_T = s.T;
+  }
+  const size_t seg_stride = ((size_t)max_span * 3 + 3 + 3) / 4 * 4;       // the segment, up to 3 bytes of misalignment, whole dwords
+  const size_t r_stride = (size_t)max_w * 3;
+  auto lds_of = [&](int rows) { return (size_t)(256 + 4 * rows) * 4 + (size_t)2 * rows * (2 * seg_stride + 4 * r_stride); };
+  int rows = FLK_PREP_TRAIN_ROWS;
+  while (rows > 1 && lds_of(rows) > 48 * 1024) rows >>= 1;
+  FLK_REQUIRE(lds_of(rows) <= 60 * 1024, "flk_clip_prepare_train: a box %d resized columns wide over %d source columns is more than one workgroup stages",
+              max_w, max_span);
+  FLK_REQUIRE(max_T <= 65535, "flk_clip_prepare_train: more than 65535 frames");
+  p.out = out + a->out_clip_offset * a->out_clip_stride;
+  p.clip_stride = a->out_clip_stride;
+  p.Ho = a->Ho; p.Wo = a->Wo; p.rows = rows; p.seg_stride = (int)seg_stride; p.r_stride = (int)r_stride;
+  p.vec = ((size_t)p.out % 16 == 0) && a->out_clip_stride % 4 == 0 && (a->Wo * 3) % 4 == 0;
+  for (int k = 0; k < 3; ++k) { p.mean[k] = a->mean[k]; p.std_[k] = a->std[k]; }
+  const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
+  FLK_LAUNCH_KERNEL(clip_prepare_train_kernel, grid, dim3(256), lds_of(rows), stream, p);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, LossArgs, PoolArgs, PrepareArgs,
+from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, LossArgs, PoolArgs, PrepareArgs, PrepBox,
                    PrepClip, check, dtype_code, load, ptr, stream_ptr, torch_dtype)
 from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, prepare_geometry
 
@@ -456,7 +456,8 @@ def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, 
     return scalars
 
 
-def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
+                  flips=None):
     """Raw decoded frames -> normalised clips on the device (flk_clip_prepare): the reference's evaluation transform
     ``ToTensorVideo -> ResizeVideo(im_scale) -> CenterCropVideo(input_size) -> NormalizeVideo(mean, std)`` (dataset.py:84-123) in one
     kernel launch per ``FLK_PREP_MAX_CLIPS`` clips.
@@ -466,23 +467,38 @@ def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, 
     ``out``: fp32 ``[>= out_offset + N, T, Ho, Wo, 3]`` contiguous; clip k goes to ``out[out_offset + k]``, other rows are left alone.
     Without ``out`` a tensor ``[N,T,Ho,Wo,3]`` is allocated.  Returns the rows written.
     ``rule``: ``"sizes"`` (default: the arithmetic of torch 1.4.0, which the reference pins) or ``"scale_factor"`` (current torch);
-    see ``videoresnet_spec.prepare_geometry``."""
-    plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule)
+    see ``videoresnet_spec.prepare_geometry``.
+    ``boxes`` and ``flips`` (both or neither; sequences of length N): the training transform instead (flk_clip_prepare_train; dataset.py:105-118) --
+    clip k's box ``(i, j, h, w)`` of its resized image is resampled to ``input_size`` (RandomResizedCropVideo; RandomCropVideo when the
+    box has that size) and mirrored along W when ``flips[k]``; ``videoresnet_spec.train_crop_params`` draws them as the reference does."""
+    plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule, boxes, flips)
     for a in plan:
-        check(load().flk_clip_prepare(C.byref(a), ptr(out), stream_ptr()))
+        if a._boxes is None:
+            check(load().flk_clip_prepare(C.byref(a), ptr(out), stream_ptr()))
+        else:
+            check(load().flk_clip_prepare_train(C.byref(a), a._boxes, ptr(out), stream_ptr()))
     return out[out_offset:out_offset + n]
 
 
 _prep_geometry = functools.lru_cache(maxsize=512)(prepare_geometry)
 
 
-def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
+                       flips=None):
     """the host half of ``prepare_clips``: ``([flk_prepare_args per launch], out, N)`` -- every check and every descriptor, no GPU call.
-    (A caller that repeats one preparation, such as a timing loop, launches the arguments itself.)"""
+    (A caller that repeats one preparation, such as a timing loop, launches the arguments itself.)  With ``boxes`` / ``flips`` each
+    launch's ``_boxes`` is its flk_prep_box array (None otherwise)."""
+    if (boxes is None) != (flips is None):
+        raise ValueError("prepare_clips: boxes and flips go together, got only " + ("boxes" if flips is None else "flips"))
     Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
     clips = list(frames) if isinstance(frames, (list, tuple)) else [frames]        # a 5-d tensor is one group of equal clips
     if not clips or (torch.is_tensor(clips[0]) and clips[0].dim() == 5 and clips[0].shape[0] == 0):
         raise ValueError("prepare_clips: no clips")
+    if boxes is not None:                      # one box and one flip per clip: checked before anything else looks at the clips
+        boxes, flips = list(boxes), list(flips)
+        n = sum(int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 5 and not isinstance(frames, (list, tuple)) else 1 for x in clips)
+        if len(boxes) != n or len(flips) != n:
+            raise ValueError(f"prepare_clips: {n} clips, {len(boxes)} boxes and {len(flips)} flips")
     keep, descs, T = [], [], None
     for k, x in enumerate(clips):
         group = torch.is_tensor(x) and x.dim() == 5 and not isinstance(frames, (list, tuple))
@@ -506,6 +522,10 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
             d.Hr, d.Wr, d.step_h, d.step_w, d.crop_i, d.crop_j = Hr, Wr, sh, sw, ci, cj
             descs.append(d)
     n = len(descs)
+    if boxes is not None:
+        for k, (b, d) in enumerate(zip(boxes, descs)):
+            if len(b) != 4 or min(b[2], b[3]) < 1 or min(b[0], b[1]) < 0 or b[0] + b[2] > d.Hr or b[1] + b[3] > d.Wr:
+                raise ValueError(f"prepare_clips: clip {k}: box {tuple(b)} is not (i, j, h, w) inside the resized image {d.Hr} x {d.Wr}")
     if out is None:
         out = torch.empty((out_offset + n, T, Ho, Wo, 3), dtype=torch.float32, device=keep[0].device)
     if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 5
@@ -522,6 +542,10 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
         a.out_clip_offset, a.out_clip_stride = out_offset + first, T * Ho * Wo * 3
         a.clips = arr
         a._keepalive = (arr, keep)          # the struct holds raw pointers only
+        a._boxes = None
+        if boxes is not None:
+            a._boxes = (PrepBox * len(part))(*[PrepBox(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(bool(f)))
+                                               for b, f in zip(boxes[first:first + len(part)], flips[first:first + len(part)])])
         plan.append(a)
     return plan, out, n
 

@@ -5,12 +5,14 @@ libflicker_hip.so: ``Perturbation``, ``Losses``, ``Adversarial_metrics`` and a V
 Same names, argument meaning and error behaviour as the reference classes; the arithmetic runs in the HIP kernels
 (torch dialect flags), pinned by the reference's own golden vectors (tests/golden/torch_attack_golden.npz).
 Clips are channels-last ``[B,T,H,W,3]`` on the device (the reference's NCDHW ``[B,3,T,H,W]`` permuted once at load)."""
+import random
+
 import numpy as np
 import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, resolve_model, u8_decode_table
+from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, resolve_model, train_crop_params, u8_decode_table
 
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 CLIP_DTYPES = (torch.float32, torch.uint8)
@@ -253,13 +255,19 @@ class FlickerVideoResNet:
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
-                 im_scale=128, resize_rule="sizes"):
+                 im_scale=128, resize_rule="sizes", augment=None):
         from .i3d_engine import check_optimizer
         # raw-size uint8 frames are prepared on the device (``prepare``): ResizeVideo(im_scale) -> CenterCropVideo(image_size), dataset.py:84-123;
         # resize_rule: "sizes" = the arithmetic of torch 1.4.0 (the reference's pin), "scale_factor" = current torch (videoresnet_spec.prepare_geometry)
         if resize_rule not in RESIZE_RULES:
             raise ValueError(f"resize_rule must be one of {RESIZE_RULES}, got {resize_rule!r}")
         self.im_scale, self.resize_rule = im_scale, resize_rule
+        # augment: the reference's training transform for raw frames (dataset.py:105-118; ``prepare(..., train=True)``, train_an_epoch's
+        # "train" phase): {"scales": (0.6, 1.0) | None (RandomCropVideo), "ratio": (3/4, 4/3), "flip_ratio": 0.5, "seed": 0}; the engine owns
+        # ONE generator, random.Random(seed + rank), drawn from in clip order
+        self.augment = self._check_augment(augment)
+        self.last_augment = None
+        self._aug_rng = None if self.augment is None else random.Random(self.augment["seed"] + parallel.rank(process_group))
         # "pgd": delta <- clamp(delta - lr * sgn(g), +-dynamic_max_norm) instead of torch Adam (model.py:868) -- the radius is the clamp
         # bound the perturbation already has, so the restart schedule (model.py:1061-1066) widens it; no optimiser state
         self.optimizer = check_optimizer(optimizer)
@@ -323,28 +331,65 @@ class FlickerVideoResNet:
                              f"got {tuple(x.shape)} {x.dtype}")
         return x.contiguous()
 
-    def prepare(self, frames, out=None, out_offset=0):
+    @staticmethod
+    def _check_augment(augment):
+        """the ``augment`` dict with its defaults filled in (None stays None); anything malformed is a ValueError"""
+        if augment is None:
+            return None
+        known = {"scales": (0.6, 1.0), "ratio": (3 / 4, 4 / 3), "flip_ratio": 0.5, "seed": 0}
+        if not isinstance(augment, dict) or set(augment) - set(known):
+            raise ValueError(f"augment must be a dict with keys among {sorted(known)}, got {augment!r}")
+        a = {**known, **augment}
+        for key in ("scales", "ratio"):
+            v = a[key]
+            if v is None and key == "scales":
+                continue
+            if not (isinstance(v, (tuple, list)) and len(v) == 2 and 0 < float(v[0]) <= float(v[1])):
+                raise ValueError(f"augment[{key!r}] must be an increasing pair of positive numbers{' or None' if key == 'scales' else ''}, got {v!r}")
+            a[key] = (float(v[0]), float(v[1]))
+        if not 0.0 <= float(a["flip_ratio"]) <= 1.0:
+            raise ValueError(f"augment['flip_ratio'] must be a probability, got {a['flip_ratio']!r}")
+        a["flip_ratio"], a["seed"] = float(a["flip_ratio"]), int(a["seed"])
+        return a
+
+    def prepare(self, frames, out=None, out_offset=0, train=False):
         """raw decoded uint8 frames -- a CUDA tensor ``[N,T,H,W,3]`` or a list of ``[T,H,W,3]`` tensors of any (differing) ``H x W`` -- to
         the normalised fp32 clips ``[N,T,self.H,self.W,3]`` this engine takes: the reference's evaluation transform (dataset.py:84-123) in
-        one kernel (ops.prepare_clips), at the engine's ``im_scale`` / ``resize_rule``.  ``out``: rows ``out_offset ...`` of a batch buffer."""
+        one kernel (ops.prepare_clips), at the engine's ``im_scale`` / ``resize_rule``.  ``out``: rows ``out_offset ...`` of a batch buffer.
+        ``train=True`` (an engine built with ``augment``): the training transform -- one ``(box, flip)`` per clip drawn in clip order
+        from the engine's generator (videoresnet_spec.train_crop_params) and kept, as ``{"boxes": [...], "flips": [...]}``, on
+        ``last_augment``."""
+        if train and self.augment is None:
+            raise ValueError("prepare(train=True) needs an engine built with augment={...}")
         clips = list(frames) if isinstance(frames, (list, tuple)) else frames
         for k in range(len(clips)):
             if torch.is_tensor(clips[k]) and clips[k].dim() == 4 and int(clips[k].shape[0]) != self.T:
                 raise ValueError(f"clip {k} has {int(clips[k].shape[0])} frames, the engine takes {self.T}")
+        boxes = flips = None
+        if train:
+            boxes, flips = [], []
+            for x in clips:                                          # a 5-d tensor iterates over its clips
+                Hr, Wr = ops._prep_geometry(int(x.shape[-3]), int(x.shape[-2]), self.im_scale, (self.H, self.W), self.resize_rule)[:2]
+                *box, flip = train_crop_params(Hr, Wr, (self.H, self.W), self.augment["scales"], self.augment["ratio"],
+                                               self.augment["flip_ratio"], self._aug_rng)
+                boxes.append(tuple(box))
+                flips.append(flip)
+            self.last_augment = {"boxes": boxes, "flips": flips}
         return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                 rule=self.resize_rule)
+                                 rule=self.resize_rule, boxes=boxes, flips=flips)
 
     def _is_raw(self, x):
         """uint8 frames that are not at the engine's H x W yet (clips that are take today's path: decoded by the apply kernel)"""
         return torch.is_tensor(x) and x.dtype == torch.uint8 and x.dim() == 5 and tuple(x.shape[2:4]) != (self.H, self.W)
 
-    def _prepared(self, x):
-        """``x`` itself, or -- raw-size uint8 frames -- their clips prepared into the engine's one reused fp32 buffer (valid until the next call)"""
+    def _prepared(self, x, train=False):
+        """``x`` itself, or -- raw-size uint8 frames -- their clips prepared into the engine's one reused fp32 buffer (valid until the next
+        call).  ``train``: with the training transform (an engine built with ``augment`` only)."""
         if not self._is_raw(x):
             return x
         if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < x.shape[0]:
             self._prep_buf = torch.empty((max(int(x.shape[0]), self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=x.device)
-        return self.prepare(x, out=self._prep_buf)
+        return self.prepare(x, out=self._prep_buf, train=train)
 
     @staticmethod
     def _same_dtype(dtype, x, what):
@@ -529,7 +574,11 @@ class FlickerVideoResNet:
             xdt = None
             for inputs, target, *_ in data_loaders[phase]:
                 xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
-                inputs = self._prepared(inputs)              # raw-size uint8 frames: this batch's clips, in the reused fp32 buffer
+                augmenting = phase == "train" and self.augment is not None
+                if augmenting and not self._is_raw(inputs):
+                    raise ValueError("augment is set but the train clips are at the engine's size already: there is nothing to prepare "
+                                     "(the training transform applies to raw uint8 frames)")
+                inputs = self._prepared(inputs, train=augmenting)   # raw-size uint8 frames: this batch's clips, in the reused fp32 buffer
                 clean = self.logits(inputs, False).clone()
                 r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
                 adv_logits = self._logits

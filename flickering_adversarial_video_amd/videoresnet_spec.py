@@ -182,6 +182,93 @@ def prepare_host(frames, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DE
     return clip.permute(1, 2, 3, 0).contiguous()
 
 
+def train_crop_params(Hr, Wr, input_size=112, scales=(0.6, 1.0), ratio=(3 / 4, 4 / 3), flip_ratio=0.5, rng=None):
+    """The random draws of the reference's training transform (dataset.py:105-118) for one clip whose resized image is ``Hr x Wr``:
+    ``(i, j, h, w, flip)``, the crop box in the resized image and whether the clip is mirrored along W.  ``rng``: a ``random.Random``
+    (None: a fresh unseeded one); the draws are made in the reference's order, so ``random.Random(s)`` gives the boxes the reference
+    gives under ``random.seed(s)``.
+
+    ``scales`` given: ``RandomResizedCropVideo.get_params`` (transforms_video.py:137-179) -- up to 10 attempts of ``uniform(*scales)``
+    times the area, ``exp(uniform(log r0, log r1))`` as aspect ratio, ``w = round(sqrt(area * aspect))``, ``h = round(sqrt(area /
+    aspect))``; the first box that fits draws ``randint(0, Hr - h)``, ``randint(0, Wr - w)``.  After 10 misses the central fallback:
+    the whole width at ratio ``min(ratio)`` when the image is narrower than that, the whole height at ``max(ratio)`` when wider, else
+    the whole image.  ``scales=None``: ``RandomCropVideo.get_params`` (:77-95) -- a box of ``input_size``, no draw when the image has
+    that size already, else two ``randint``s.  Then ``rng.random() < flip_ratio`` (:272), a draw the reference makes whatever p is."""
+    import math
+    import random
+    rng = random.Random() if rng is None else rng
+    Hr, Wr = int(Hr), int(Wr)
+    if scales is None:
+        th, tw = _pair(input_size)
+        if Hr < th or Wr < tw:
+            raise ValueError(f"resized image {Hr} x {Wr} is smaller than the crop {th} x {tw}")
+        if (Hr, Wr) == (th, tw):
+            box = (0, 0, Hr, Wr)
+        else:
+            i = rng.randint(0, Hr - th)
+            box = (i, rng.randint(0, Wr - tw), th, tw)
+    else:
+        area, box = Wr * Hr, None
+        for _ in range(10):
+            target_area = rng.uniform(*scales) * area
+            aspect_ratio = math.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1])))
+            w = int(round(math.sqrt(target_area * aspect_ratio)))
+            h = int(round(math.sqrt(target_area / aspect_ratio)))
+            if w <= Wr and h <= Hr:
+                i = rng.randint(0, Hr - h)
+                box = (i, rng.randint(0, Wr - w), h, w)
+                break
+        if box is None:                          # central fallback
+            in_ratio = Wr / Hr
+            if in_ratio < min(ratio):
+                w = Wr
+                h = int(round(w / min(ratio)))
+            elif in_ratio > max(ratio):
+                h = Hr
+                w = int(round(h * max(ratio)))
+            else:
+                w, h = Wr, Hr
+            box = ((Hr - h) // 2, (Wr - w) // 2, h, w)
+    flip = rng.random() < flip_ratio
+    return box + (bool(flip),)
+
+
+def prepare_host_train(frames, box, flip, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes"):
+    """The training transform with torch on the CPU for a given ``box = (i, j, h, w)`` and ``flip`` (``train_crop_params`` draws them),
+    the A/B route of ``ops.prepare_clips(..., boxes=, flips=)``: uint8 frames ``[T,H,W,3]`` -> the normalised float32 clip
+    ``[T,Ho,Wo,3]``.  ``prepare_host``'s ``/255`` and resize (by ``rule``), then the box sliced out of the resized image and resampled
+    with ``F.interpolate(size=(Ho, Wo), mode="bilinear", align_corners=False)`` (functional_video.py:33-49, resized_crop; on a box of the
+    output size, the RandomCropVideo route, that resampling is the identity), ``flip(-1)`` when flagged, ``(v - mean) / std``."""
+    import torch
+    import torch.nn.functional as F
+    x = torch.as_tensor(np.ascontiguousarray(frames) if isinstance(frames, np.ndarray) else frames).cpu()
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"frames must be uint8 [T,H,W,3], got {tuple(x.shape)} {x.dtype}")
+    Hs, Ws = int(x.shape[1]), int(x.shape[2])
+    Ho, Wo = _pair(input_size)
+    if rule not in RESIZE_RULES:
+        raise ValueError(f"rule must be one of {RESIZE_RULES}, got {rule!r}")
+    scale = im_scale / min(Hs, Ws)
+    Hr, Wr = int(np.floor(Hs * scale)), int(np.floor(Ws * scale))
+    i, j, h, w = (int(v) for v in box)
+    if h < 1 or w < 1 or i < 0 or j < 0 or i + h > Hr or j + w > Wr:
+        raise ValueError(f"box ({i},{j})+{h}x{w} outside the resized image {Hr} x {Wr}")
+    clip = x.float().permute(3, 0, 1, 2) / 255.0                                     # [C,T,H,W]
+    if rule == "sizes":
+        clip = F.interpolate(clip, size=(Hr, Wr), mode="bilinear", align_corners=False)
+    else:
+        clip = F.interpolate(clip, scale_factor=scale, mode="bilinear", align_corners=False)
+    assert tuple(clip.shape[-2:]) == (Hr, Wr), (tuple(clip.shape), Hr, Wr)
+    clip = clip[..., i:i + h, j:j + w]
+    clip = F.interpolate(clip, size=(Ho, Wo), mode="bilinear", align_corners=False)
+    if flip:
+        clip = clip.flip(-1)
+    m = torch.as_tensor(mean, dtype=clip.dtype)
+    s = torch.as_tensor(std, dtype=clip.dtype)
+    clip = clip.clone().sub_(m[:, None, None, None]).div_(s[:, None, None, None])
+    return clip.permute(1, 2, 3, 0).contiguous()
+
+
 def load_weights(path, arch=None):
     """Victim weights for FlickerVideoResNet as ``{state_dict name: float32 ndarray}``.
 

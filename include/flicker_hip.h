@@ -299,6 +299,29 @@ typedef struct {
 } flk_prepare_args;
 int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream);
 
+/* The training transform on the device (csrc/prepare.hip, clip_prepare_train_kernel): the reference's get_transforms(train=True)
+ * (dataset.py:105-118):
+ *   ToTensorVideo -> ResizeVideo(im_scale, keep_ratio) -> RandomResizedCropVideo(input_size, scale, ratio) | RandomCropVideo(input_size)
+ *   -> RandomHorizontalFlipVideo(p) -> NormalizeVideo
+ * with the random draws made by the host (videoresnet_spec.train_crop_params draws them in the reference's order): per clip a box
+ * (i, j, h, w) in the RESIZED image and a flip.  Two bilinear resamplings fused in one kernel, fp32 throughout:
+ *   stage 1  R[y, x] = the resized image at (i + y, j + x), exactly as flk_clip_prepare computes a value before its normalisation
+ *            (same source index, same /255, same blend order, the clip's step_h / step_w);
+ *   stage 2  the box resampled to Ho x Wo as F.interpolate(size=(Ho, Wo), bilinear, align_corners=False) does: per axis
+ *            step2 = float(h) / float(Ho) (a float32 division), src(d) = max(fma(step2, d + 0.5f, -0.5f), 0), y0 = min(int(src), h - 1),
+ *            y1 = min(y0 + 1, h - 1), lambda = clamp(src - y0, 0, 1);
+ *            v = (1-lh) * ((1-lw) R[y0,x0] + lw R[y0,x1]) + lh * ((1-lw) R[y1,x0] + lw R[y1,x1]);
+ *   flip     output column ow takes the value computed for column Wo - 1 - ow when the clip's flip is set;
+ *   out      (v - mean[c]) / std[c], true division.
+ * A box of Ho x Wo (RandomCropVideo) makes stage 2 the identity: with the box at (crop_i, crop_j) and no flip the output is bitwise
+ * flk_clip_prepare's.  `a` as for flk_clip_prepare, crop_i / crop_j ignored; boxes: HOST array [a->nclip].  One launch for up to
+ * FLK_PREP_MAX_CLIPS clips of differing resolution, pitches, boxes and flips; rows of a batch buffer are written as by flk_clip_prepare.
+ * No allocation, no synchronisation, no atomics; the result does not depend on the launch geometry.
+ * FLK_EINVAL (before any GPU call): everything flk_clip_prepare refuses except the crop window, a null `boxes`, h < 1 or w < 1, a box
+ * outside Hr x Wr, a flip that is not 0 / 1; and a box too wide for one workgroup to stage (never truncated). */
+typedef struct { int i, j, h, w; int flip; } flk_prep_box;   /* box in the RESIZED image; flip 0/1 */
+int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes /* HOST [nclip] */, float* out, void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

@@ -18,10 +18,17 @@ resized (bilinear, shorter side to `--im-scale`), centre-cropped to `--image-siz
 resident raw shard (`--prepare device`, the default for such files), or once on the host with torch (`--prepare host`, the A/B
 route).  `--resize-rule` picks the coordinate rule of the resize (videoresnet_spec.prepare_geometry).  Clips are raw when they are
 not square, or not `--image-size` when that is given, or whenever `--prepare` is given (the engine then is 112 x 112 unless
-`--image-size` says otherwise); files of clips at the engine's size behave as before."""
+`--image-size` says otherwise); files of clips at the engine's size behave as before.
+
+`--train-transforms train` prepares the TRAINING batches of raw frames with the reference's training transform (dataset.py:105-118:
+RandomResizedCropVideo with `--aug-scales`, or RandomCropVideo with `--aug-no-resize`, then RandomHorizontalFlipVideo with `--flip-ratio`),
+a fresh box and flip per clip and epoch from `random.Random(--aug-seed + rank)`: on the device by the second preparation kernel, or
+with `--prepare host` per batch with torch (videoresnet_spec.prepare_host_train, same sampler).  The validation split and the default
+(`eval`, what the reference's own attack scripts pass for both splits) keep the evaluation transform."""
 import argparse
 import glob
 import os
+import random
 import sys
 
 import numpy as np
@@ -64,14 +71,26 @@ def prepare_host_clips(clips, S, im_scale, rule):
     return np.stack([vs.prepare_host(c, im_scale=im_scale, input_size=S, rule=rule).numpy() for c in clips])
 
 
-def load_clips(path, decode="device", image_size=None, prepare=None, im_scale=128, rule="sizes"):
-    """clips as the file holds them when they are uint8 and decode == "device" (or raw with prepare != "host"), else normalised float32
-    on the host"""
+def host_train_loader(clips, labels, batch_size, S, im_scale, rule, augment, rng, rank=0, world=1):
+    """--prepare host with --train-transforms train: every batch of raw frames through videoresnet_spec.prepare_host_train, one (box, flip)
+    per clip in clip order from `rng` -- the draws the engine makes on the device route"""
+    for i in batch_ids(len(clips), batch_size, rank, world):
+        out = []
+        for c in clips[i * batch_size:(i + 1) * batch_size]:
+            Hr, Wr = vs.prepare_geometry(c.shape[1], c.shape[2], im_scale, S, rule)[:2]
+            *box, flip = vs.train_crop_params(Hr, Wr, S, augment["scales"], augment["ratio"], augment["flip_ratio"], rng)
+            out.append(vs.prepare_host_train(c, box, flip, im_scale=im_scale, input_size=S, rule=rule))
+        yield torch.stack(out).cuda(), torch.from_numpy(labels[i * batch_size:(i + 1) * batch_size]).cuda(), None
+
+
+def load_clips(path, decode="device", image_size=None, prepare=None, im_scale=128, rule="sizes", keep_raw=False):
+    """clips as the file holds them when they are uint8 and decode == "device" (or raw with prepare != "host", or keep_raw: the host
+    route's training transform prepares per batch), else normalised float32 on the host"""
     z = np.load(path)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
     S, raw = engine_size(clips, image_size, prepare)
     if raw:
-        if prepare == "host":
+        if prepare == "host" and not keep_raw:
             return prepare_host_clips(clips, S, im_scale, rule), labels
         return np.ascontiguousarray(clips), labels
     if clips.dtype == np.uint8 and decode == "device":
@@ -135,6 +154,14 @@ def main():
                     "out per axis (F.interpolate(size=...); torch 1.4.0, the reference's pin), scale_factor = step 1 / scale (current torch)")
     ap.add_argument("--image-size", type=int, default=None, help="engine H = W (default: the clips' own size; 112 for raw frames)")
     ap.add_argument("--im-scale", type=int, default=128, help="raw frames: the shorter side after the resize (dataset.py's im_scale)")
+    ap.add_argument("--train-transforms", default="eval", choices=["eval", "train"], help="raw frames of the training split: eval = resize, centre "
+                    "crop (what the reference's attack scripts use for both splits), train = the reference's training transform: random resized "
+                    "crop and horizontal flip, new draws every epoch (dataset.py:105-118)")
+    ap.add_argument("--aug-scales", type=float, nargs=2, default=[0.6, 1.0], metavar=("LO", "HI"), help="train: area range of the random "
+                    "resized crop (dataset.py's random_crop_scales)")
+    ap.add_argument("--aug-no-resize", action="store_true", help="train: RandomCropVideo(image size) instead of the resized crop (random_crop_scales=None)")
+    ap.add_argument("--flip-ratio", type=float, default=0.5, help="train: probability of the horizontal flip")
+    ap.add_argument("--aug-seed", type=int, default=0, help="train: the sampler is random.Random(seed + rank)")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
     a = ap.parse_args()
@@ -146,16 +173,24 @@ def main():
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
         torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local_rank))
-    xtr, ytr = load_clips(a.train_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule)
+    augment = None
+    if a.train_transforms == "train":
+        augment = {"scales": None if a.aug_no_resize else tuple(a.aug_scales), "ratio": (3 / 4, 4 / 3), "flip_ratio": a.flip_ratio, "seed": a.aug_seed}
+    xtr, ytr = load_clips(a.train_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule, keep_raw=augment is not None)
     xva, yva = load_clips(a.val_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule)
-    T, HW = xtr.shape[1], engine_size(xtr, a.image_size, a.prepare)[0]
+    T, (HW, raw_train) = xtr.shape[1], engine_size(xtr, a.image_size, a.prepare)
+    if augment is not None and not raw_train:
+        raise ValueError("--train-transforms train applies to raw uint8 frames; the training clips are at the engine's size already")
+    host_aug = augment is not None and a.prepare == "host"      # the host draws and prepares per batch; the engine then gets finished clips
     # --base-model: an architecture, "ig65m" / "kinetics" (R(2+1)D-34, 8 or 32 frames) or an r2plus1d_34_* name; the class count is the
     # weights' fc head (the synthetic stand-in takes the pretrained model's, model.py:46-56)
     arch, _, ncls = vs.resolve_model(a.base_model, T)
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
-                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
+                                 augment=None if host_aug else augment)
+    host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     start_epoch = 1
@@ -174,6 +209,8 @@ def main():
         def __getitem__(self, phase):
             x, y = (xtr, ytr) if phase == "train" else (xva, yva)
             r, w = (rank, world) if phase == "train" else (0, 1)
+            if phase == "train" and host_aug:
+                return host_train_loader(x, y, a.batch_size, HW, a.im_scale, a.resize_rule, FlickerVideoResNet._check_augment(augment), host_rng, r, w)
             if x.dtype == np.uint8:               # --decode device / --prepare device: the shard is uploaded on first use, then sliced
                 if phase not in resident:
                     resident[phase] = ResidentShard(x, y, a.batch_size, r, w)
