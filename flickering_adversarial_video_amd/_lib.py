@@ -8,7 +8,7 @@ LIB_PATH = os.environ.get("FLK_LIB_PATH") or os.path.join(HERE, "libflicker_hip.
 
 FLK_F32, FLK_BF16 = 0, 1
 FLK_NET_I3D, FLK_NET_R2PLUS1D_18, FLK_NET_R3D_18, FLK_NET_MC3_18, FLK_NET_R2PLUS1D_34 = 0, 1, 2, 3, 4
-FLK_PREP_MAX_CLIPS = 64      # clips per flk_clip_prepare / flk_clip_prepare_train launch
+FLK_PREP_MAX_CLIPS = 64      # clips per flk_clip_prepare / flk_clip_prepare_train / flk_clip_prepare_sampled launch
 
 
 class FlickerHipError(RuntimeError):
@@ -111,6 +111,7 @@ _SIGS = {
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare_sampled": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "flk_pack_batch_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -151,11 +151,13 @@ extern "C" int flk_conv_weights_destroy(flk_conv_weights* w) {
 }
 
 // Clip preparation (csrc/prepare.hip): every argument is checked here, on the host, before anything touches the device.
-int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t stream);
-int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, hipStream_t stream);
+int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, float* out, hipStream_t stream);
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
+                                  hipStream_t stream);
 
-// the checks the two entries share; `boxes`: the training entry's crop boxes, which take the place of the centre-crop window
-static int check_prepare_args(const char* fn, const flk_prepare_args* a, const float* out, const flk_prep_box* boxes) {
+// the checks the entries share; `boxes`: the training transform's crop boxes, which take the place of the centre-crop window;
+// `T_out`: frames per clip written by the sampled entry (0: the clip's own T)
+static int check_prepare_args(const char* fn, const flk_prepare_args* a, const float* out, const flk_prep_box* boxes, int T_out = 0) {
   FLK_REQUIRE(a && out, "%s: null argument", fn);
   FLK_REQUIRE(a->clips, "%s: null clip list", fn);
   FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", fn, a->nclip, FLK_PREP_MAX_CLIPS);
@@ -183,18 +185,27 @@ static int check_prepare_args(const char* fn, const flk_prepare_args* a, const f
       FLK_REQUIRE(c.crop_i >= 0 && c.crop_j >= 0 && (int64_t)c.crop_i + a->Ho <= c.Hr && (int64_t)c.crop_j + a->Wo <= c.Wr,
                   "%s: clip %d: crop window (%d,%d)+%dx%d outside the resized image %d x %d", fn, i, c.crop_i, c.crop_j, a->Ho, a->Wo, c.Hr, c.Wr);
     }
-    FLK_REQUIRE(a->out_clip_stride >= (int64_t)c.T * a->Ho * a->Wo * 3, "%s: clip %d: out_clip_stride %lld smaller than the clip", fn, i, (long long)a->out_clip_stride);
+    FLK_REQUIRE(a->out_clip_stride >= (int64_t)(T_out ? T_out : c.T) * a->Ho * a->Wo * 3, "%s: clip %d: out_clip_stride %lld smaller than the clip", fn, i, (long long)a->out_clip_stride);
   }
   return FLK_OK;
 }
 
 extern "C" int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream) {
   if (int rc = check_prepare_args("flk_clip_prepare", a, out, nullptr)) return rc;
-  return flk_clip_prepare_launch(a, out, (hipStream_t)stream);
+  return flk_clip_prepare_launch(a, nullptr, 0, out, (hipStream_t)stream);
 }
 
 extern "C" int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, void* stream) {
   FLK_REQUIRE(boxes, "flk_clip_prepare_train: null box list");
   if (int rc = check_prepare_args("flk_clip_prepare_train", a, out, boxes)) return rc;
-  return flk_clip_prepare_train_launch(a, boxes, out, (hipStream_t)stream);
+  return flk_clip_prepare_train_launch(a, boxes, nullptr, 0, out, (hipStream_t)stream);
+}
+
+extern "C" int flk_clip_prepare_sampled(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
+                                        void* stream) {
+  FLK_REQUIRE(frame_idx, "flk_clip_prepare_sampled: null frame_idx");
+  FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "flk_clip_prepare_sampled: T_out %d outside 1..65535", T_out);
+  if (int rc = check_prepare_args("flk_clip_prepare_sampled", a, out, boxes, T_out)) return rc;
+  if (boxes) return flk_clip_prepare_train_launch(a, boxes, frame_idx, T_out, out, (hipStream_t)stream);
+  return flk_clip_prepare_launch(a, frame_idx, T_out, out, (hipStream_t)stream);
 }

@@ -20,7 +20,17 @@
 // No atomics, no allocation, no host synchronisation.
 //
 // Second kernel, further down: clip_prepare_train_kernel, the training transform (a resampled crop box and a flip per clip).
+//
+// Sampled form of both kernels (flk_clip_prepare_sampled): the clip is cut from a whole resident video on the way.  Output frame t of
+// clip k reads source frame idx[k][t] of the view instead of frame t; idx is a device int32 [nclip][T_out] table (8 KB at 64 clips of
+// 32 frames: it does not fit the kernel-argument segment, so its pointer travels in the descriptor), the grid's frame dimension is
+// T_out, and PrepClipDev.T is the number of source frames: every index read is clamped into [0, T - 1], so no table makes the kernel
+// read outside the view.  Addressing only -- one uniform load per workgroup; staging, arithmetic, blend order, flip and box handling
+// are the same statements, so a sampled launch gives bit for bit what the plain launch gives on the frames gathered beforehand.
+// A frame that a table repeats (jitter step 0, padding with the last frame) is computed again.  Both kernels are templates on their
+// descriptor type: the plain instantiations take the descriptor they always took and compile to the code they always were.
 #include <math.h>
+#include <type_traits>
 #include "flk_internal.h"
 
 namespace {
@@ -42,7 +52,21 @@ struct PrepLaunch {
   float mean[3], std_[3];
   PrepClipDev clip[FLK_PREP_MAX_CLIPS];
 };
-static_assert(sizeof(PrepLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+// what a sampled descriptor adds to its plain one (both kernels)
+struct PrepFrameTable {
+  const int* idx;             // device int32 [nclip][gridDim.y]: source frame of every output frame
+};
+struct PrepLaunchSampled : PrepLaunch, PrepFrameTable {};
+static_assert(sizeof(PrepLaunchSampled) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+template <class L>
+constexpr bool prep_sampled = std::is_base_of<PrepFrameTable, L>::value;
+
+// the source frame of output frame t of the workgroup's clip: t itself, or the table's entry clamped into the view's [0, T - 1]
+template <class L>
+__device__ __forceinline__ int prep_source_frame(const L& p, int t, int T) {
+  if constexpr (prep_sampled<L>) return min(max(p.idx[(size_t)blockIdx.z * gridDim.y + t], 0), T - 1);
+  else return t;
+}
 
 // torch's area_pixel_compute_source_index (align_corners = False): scale * (dst + 0.5) - 0.5 with the multiply-subtract fused, as the
 // vectorised CPU builds of torch evaluate it (separately rounded operations land up to 5.5e-5 away from F.interpolate at 239x317,
@@ -59,11 +83,12 @@ inline float prep_src_host(float step, int d) {
 
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
-__global__ __launch_bounds__(256) void clip_prepare_kernel(const PrepLaunch p) {
+template <class L>
+__global__ __launch_bounds__(256) void clip_prepare_kernel(const L p) {
   extern __shared__ unsigned prep_lds[];      // [256] fp32 table u8 / 255 | [2 * rows] segment misalignments | 2 * rows row segments
   const PrepClipDev& c = p.clip[blockIdx.z];
-  const int t = blockIdx.y;
-  if (t >= c.T) return;
+  const int t = blockIdx.y;                   // the output frame
+  if (!prep_sampled<L> && t >= c.T) return;         // sampled: the grid's frame dimension is T_out, the same for every clip
   float* tab = (float*)prep_lds;
   int* mis_of = (int*)(prep_lds + 256);
   unsigned* seg = prep_lds + 256 + 2 * p.rows;
@@ -72,7 +97,7 @@ __global__ __launch_bounds__(256) void clip_prepare_kernel(const PrepLaunch p) {
   const int oh0 = blockIdx.x * p.rows;
   const int nrow = min(p.rows, p.Ho - oh0);
   const int ndw = p.seg_stride >> 2;
-  const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+  const uint8_t* frame = c.src + (long long)prep_source_frame(p, t, c.T) * c.pitch_t;
   const int nbytes = c.span * 3;
   // ---- stage: slot 2r + s = source row s (0 top, 1 bottom) of output row oh0 + r; columns [x0, x0 + span) ----
   for (int k = threadIdx.x; k < 2 * nrow * ndw; k += 256) {
@@ -147,9 +172,10 @@ __global__ __launch_bounds__(256) void clip_prepare_kernel(const PrepLaunch p) {
 
 }  // namespace
 
-// arguments already validated (api.cpp: flk_clip_prepare); everything here up to the launch is host arithmetic
-int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t stream) {
-  PrepLaunch p;
+// arguments already validated (api.cpp: flk_clip_prepare, flk_clip_prepare_sampled); everything here up to the launch is host arithmetic.
+// frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one
+int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, float* out, hipStream_t stream) {
+  PrepLaunchSampled p;
   int max_span = 1, max_T = 1;
   for (int i = 0; i < a->nclip; ++i) {
     const flk_prep_clip& s = a->clips[i];
@@ -170,6 +196,7 @@ int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t s
   int rows = 4;
   while (rows > 1 && (size_t)2 * rows * seg_stride > 48 * 1024) rows >>= 1;
   FLK_REQUIRE((size_t)2 * rows * seg_stride <= 60 * 1024, "flk_clip_prepare: the crop window spans %d source columns, more than one workgroup stages", max_span);
+  if (frame_idx) max_T = T_out;                // the grid's frame dimension: output frames
   FLK_REQUIRE(max_T <= 65535, "flk_clip_prepare: more than 65535 frames");
   p.out = out + a->out_clip_offset * a->out_clip_stride;
   p.clip_stride = a->out_clip_stride;
@@ -178,7 +205,12 @@ int flk_clip_prepare_launch(const flk_prepare_args* a, float* out, hipStream_t s
   for (int k = 0; k < 3; ++k) { p.mean[k] = a->mean[k]; p.std_[k] = a->std[k]; }
   const size_t lds = (size_t)(256 + 2 * rows) * 4 + (size_t)2 * rows * seg_stride;
   const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
-  FLK_LAUNCH_KERNEL(clip_prepare_kernel, grid, dim3(256), lds, stream, p);
+  if (frame_idx) {
+    p.idx = frame_idx;
+    FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunchSampled>, grid, dim3(256), lds, stream, p);
+  } else {
+    FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunch>, grid, dim3(256), lds, stream, static_cast<const PrepLaunch&>(p));
+  }
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -233,7 +265,8 @@ struct PrepTrainLaunch {
   PrepTrainClipDev clip[FLK_PREP_MAX_CLIPS];
 };
 static_assert(FLK_PREP_MAX_CLIPS <= 64, "one flip bit per clip");
-static_assert(sizeof(PrepTrainLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+struct PrepTrainLaunchSampled : PrepTrainLaunch, PrepFrameTable {};
+static_assert(sizeof(PrepTrainLaunchSampled) <= 4096, "the launch descriptor must fit the kernel-argument segment");
 
 // source columns under the box: [x0, x0 + span); the same fp32 sequence on the host (LDS sizing) and in the kernel
 __host__ __device__ inline void prep_train_span(float step_w, int j, int w, int Ws, int* x0, int* span) {
@@ -256,12 +289,13 @@ __device__ __forceinline__ float prep_blend(float w0, float v0, float w1, float 
   return __builtin_fmaf(w0, v0, w1 * v1);
 }
 
-__global__ __launch_bounds__(256) void clip_prepare_train_kernel(const PrepTrainLaunch p) {
+template <class L>
+__global__ __launch_bounds__(256) void clip_prepare_train_kernel(const L p) {
   // [256] fp32 table u8 / 255 | [2 * cap] segment misalignments | 2 * cap source-row segments | cap intermediate rows (cap = 2 * rows)
   extern __shared__ unsigned prep_train_lds[];
   const PrepTrainClipDev& c = p.clip[blockIdx.z];
-  const int t = blockIdx.y;
-  if (t >= c.T) return;
+  const int t = blockIdx.y;                   // the output frame
+  if (!prep_sampled<L> && t >= c.T) return;         // sampled: the grid's frame dimension is T_out, the same for every clip
   const int cap = 2 * p.rows;
   float* tab = (float*)prep_train_lds;
   int* mis_of = (int*)(prep_train_lds + 256);
@@ -289,7 +323,7 @@ __global__ __launch_bounds__(256) void clip_prepare_train_kernel(const PrepTrain
   };
   int x0, span;
   prep_train_span(c.step_w, c.j, c.w, c.Ws, &x0, &span);
-  const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+  const uint8_t* frame = c.src + (long long)prep_source_frame(p, t, c.T) * c.pitch_t;
   const int nbytes = span * 3;
   // ---- A: segment 2s + v = source row v (0 top, 1 bottom) of intermediate slot s; columns [x0, x0 + span) ----
   for (int k = threadIdx.x; k < 2 * ni * ndw; k += 256) {
@@ -463,9 +497,11 @@ __global__ __launch_bounds__(256) void clip_prepare_train_kernel(const PrepTrain
                                     // per launch of 16 clips of 16 x 240 x 320 (tools/prepare_time.py)
 #endif
 
-// arguments already validated (api.cpp: flk_clip_prepare_train); everything here up to the launch is host arithmetic
-int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, hipStream_t stream) {
-  PrepTrainLaunch p;
+// arguments already validated (api.cpp: flk_clip_prepare_train, flk_clip_prepare_sampled); everything here up to the launch is host
+// arithmetic.  frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
+                                  hipStream_t stream) {
+  PrepTrainLaunchSampled p;
   int max_span = 1, max_T = 1, max_w = 1;
   p.flips = 0;
   for (int i = 0; i < a->nclip; ++i) {
@@ -490,6 +526,7 @@ int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box*
   while (rows > 1 && lds_of(rows) > 48 * 1024) rows >>= 1;
   FLK_REQUIRE(lds_of(rows) <= 60 * 1024, "flk_clip_prepare_train: a box %d resized columns wide over %d source columns is more than one workgroup stages",
               max_w, max_span);
+  if (frame_idx) max_T = T_out;                // the grid's frame dimension: output frames
   FLK_REQUIRE(max_T <= 65535, "flk_clip_prepare_train: more than 65535 frames");
   p.out = out + a->out_clip_offset * a->out_clip_stride;
   p.clip_stride = a->out_clip_stride;
@@ -497,7 +534,12 @@ int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box*
   p.vec = ((size_t)p.out % 16 == 0) && a->out_clip_stride % 4 == 0 && (a->Wo * 3) % 4 == 0;
   for (int k = 0; k < 3; ++k) { p.mean[k] = a->mean[k]; p.std_[k] = a->std[k]; }
   const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
-  FLK_LAUNCH_KERNEL(clip_prepare_train_kernel, grid, dim3(256), lds_of(rows), stream, p);
+  if (frame_idx) {
+    p.idx = frame_idx;
+    FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunchSampled>, grid, dim3(256), lds_of(rows), stream, p);
+  } else {
+    FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunch>, grid, dim3(256), lds_of(rows), stream, static_cast<const PrepTrainLaunch&>(p));
+  }
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

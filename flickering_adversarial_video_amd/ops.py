@@ -457,7 +457,7 @@ def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, 
 
 
 def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
-                  flips=None):
+                  flips=None, frame_idx=None):
     """Raw decoded frames -> normalised clips on the device (flk_clip_prepare): the reference's evaluation transform
     ``ToTensorVideo -> ResizeVideo(im_scale) -> CenterCropVideo(input_size) -> NormalizeVideo(mean, std)`` (dataset.py:84-123) in one
     kernel launch per ``FLK_PREP_MAX_CLIPS`` clips.
@@ -470,10 +470,20 @@ def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, 
     see ``videoresnet_spec.prepare_geometry``.
     ``boxes`` and ``flips`` (both or neither; sequences of length N): the training transform instead (flk_clip_prepare_train; dataset.py:105-118) --
     clip k's box ``(i, j, h, w)`` of its resized image is resampled to ``input_size`` (RandomResizedCropVideo; RandomCropVideo when the
-    box has that size) and mirrored along W when ``flips[k]``; ``videoresnet_spec.train_crop_params`` draws them as the reference does."""
-    plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule, boxes, flips)
+    box has that size) and mirrored along W when ``flips[k]``; ``videoresnet_spec.train_crop_params`` draws them as the reference does.
+    ``frame_idx``: cut the clips from whole videos on the way (flk_clip_prepare_sampled; the temporal sampling of dataset.py:500-586).
+    ``frames`` is then a list of videos ``[N_k,H_k,W_k,3]`` whose lengths and resolutions may differ -- the same tensor may be listed
+    several times, once per clip cut from it -- and ``frame_idx`` holds one row of ``T_out`` frame numbers per clip (host integers: nested
+    lists, an array or a CPU tensor ``[N, T_out]``; ``videoresnet_spec.sample_frame_indices`` draws them as the reference does).  Frame t of
+    clip k is prepared from ``frames[k][frame_idx[k][t]]``: bitwise what the call without ``frame_idx`` gives on ``frames[k][frame_idx[k]]``,
+    without that gathered copy.  Every index is checked against its video here, before anything is launched; the table is uploaded once
+    per call as one int32 tensor.  ``out`` rows are ``[T_out,Ho,Wo,3]``; ``boxes`` / ``flips``, ``out`` / ``out_offset``, views and long
+    lists work as without it."""
+    plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule, boxes, flips, frame_idx)
     for a in plan:
-        if a._boxes is None:
+        if a._frame_idx is not None:
+            check(load().flk_clip_prepare_sampled(C.byref(a), a._boxes, ptr(a._frame_idx), a._frame_idx.shape[1], ptr(out), stream_ptr()))
+        elif a._boxes is None:
             check(load().flk_clip_prepare(C.byref(a), ptr(out), stream_ptr()))
         else:
             check(load().flk_clip_prepare_train(C.byref(a), a._boxes, ptr(out), stream_ptr()))
@@ -484,10 +494,11 @@ _prep_geometry = functools.lru_cache(maxsize=512)(prepare_geometry)
 
 
 def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
-                       flips=None):
+                       flips=None, frame_idx=None):
     """the host half of ``prepare_clips``: ``([flk_prepare_args per launch], out, N)`` -- every check and every descriptor, no GPU call.
     (A caller that repeats one preparation, such as a timing loop, launches the arguments itself.)  With ``boxes`` / ``flips`` each
-    launch's ``_boxes`` is its flk_prep_box array (None otherwise)."""
+    launch's ``_boxes`` is its flk_prep_box array (None otherwise); with ``frame_idx`` its ``_frame_idx`` is its rows of the uploaded int32
+    table (None otherwise) -- the upload is the one thing here that touches the device, after every check has passed."""
     if (boxes is None) != (flips is None):
         raise ValueError("prepare_clips: boxes and flips go together, got only " + ("boxes" if flips is None else "flips"))
     Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
@@ -499,6 +510,24 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
         n = sum(int(x.shape[0]) if torch.is_tensor(x) and x.dim() == 5 and not isinstance(frames, (list, tuple)) else 1 for x in clips)
         if len(boxes) != n or len(flips) != n:
             raise ValueError(f"prepare_clips: {n} clips, {len(boxes)} boxes and {len(flips)} flips")
+    table = None
+    if frame_idx is not None:
+        if not isinstance(frames, (list, tuple)):
+            raise ValueError("prepare_clips: with frame_idx, frames is a list of whole videos [N_k,H_k,W_k,3], one entry per clip")
+        rows = frame_idx.numpy() if torch.is_tensor(frame_idx) and not frame_idx.is_cuda else frame_idx
+        if torch.is_tensor(rows):
+            raise ValueError("prepare_clips: frame_idx must be host integers (it is checked against the videos before anything is launched)")
+        rows = [np.asarray(r) for r in rows]
+        if len(rows) != len(clips):
+            raise ValueError(f"prepare_clips: {len(clips)} clips and {len(rows)} rows of frame_idx")
+        if any(r.ndim != 1 or r.shape != rows[0].shape for r in rows) or rows[0].size < 1:
+            raise ValueError(f"prepare_clips: the rows of frame_idx must be equally long, at least one frame each; got lengths "
+                             f"{[tuple(r.shape) for r in rows][:8]}")
+        if any(r.dtype.kind not in "iu" for r in rows):
+            raise ValueError(f"prepare_clips: frame_idx must hold integers, got {sorted({str(r.dtype) for r in rows})}")
+        if rows[0].size > 65535:
+            raise ValueError(f"prepare_clips: {rows[0].size} frames per clip, more than 65535")
+        table = np.stack(rows).astype(np.int64)
     keep, descs, T = [], [], None
     for k, x in enumerate(clips):
         group = torch.is_tensor(x) and x.dim() == 5 and not isinstance(frames, (list, tuple))
@@ -506,18 +535,23 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
             desc = f"{tuple(x.shape)} {x.dtype} {x.device}" if torch.is_tensor(x) else type(x).__name__
             raise ValueError(f"prepare_clips: {'frames' if group else f'clip {k}'} must be a CUDA uint8 tensor [{'N,' if group else ''}T,H,W,3], got {desc}")
         Tk, Hs, Ws = (int(v) for v in x.shape[-4:-1])
-        T = Tk if T is None else T
-        if Tk != T:
-            raise ValueError(f"prepare_clips: clip {k} has {Tk} frames, clip 0 has {T}")
+        if table is not None:                  # a whole video: its length bounds the clip's row of the table, the clip is T_out long
+            if Tk < 1 or table[k].min() < 0 or table[k].max() >= Tk:
+                raise ValueError(f"prepare_clips: clip {k}: frame_idx holds {int(table[k].min())} .. {int(table[k].max())}, the video has {Tk} frames")
+            T = table.shape[1]
+        else:
+            T = Tk if T is None else T
+            if Tk != T:
+                raise ValueError(f"prepare_clips: clip {k} has {Tk} frames, clip 0 has {T}")
         # read in place when a pixel's bytes and a row's pixels are adjacent; anything else is copied once
-        if x.stride(-1) != 1 or x.stride(-2) != 3 or x.stride(-3) < 3 * Ws or (T > 1 and x.stride(-4) <= 0) or (group and x.stride(0) < 0):
+        if x.stride(-1) != 1 or x.stride(-2) != 3 or x.stride(-3) < 3 * Ws or (Tk > 1 and x.stride(-4) <= 0) or (group and x.stride(0) < 0):
             x = x.contiguous()
         keep.append(x)
         Hr, Wr, sh, sw, ci, cj = _prep_geometry(Hs, Ws, im_scale, (Ho, Wo), rule)
         base, nstride = x.data_ptr(), (x.stride(0) if group else 0)
         for j in range(x.shape[0] if group else 1):
             d = PrepClip()
-            d.src, d.T, d.Hs, d.Ws = base + j * nstride, T, Hs, Ws
+            d.src, d.T, d.Hs, d.Ws = base + j * nstride, Tk, Hs, Ws
             d.pitch_t, d.pitch_h = max(int(x.stride(-4)), 1), int(x.stride(-3))
             d.Hr, d.Wr, d.step_h, d.step_w, d.crop_i, d.crop_j = Hr, Wr, sh, sw, ci, cj
             descs.append(d)
@@ -532,6 +566,8 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
             or tuple(out.shape[1:]) != (T, Ho, Wo, 3) or out_offset < 0 or out.shape[0] < out_offset + n):
         desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
         raise ValueError(f"prepare_clips: out must be a contiguous CUDA float32 tensor [>= {out_offset + n},{T},{Ho},{Wo},3], got {desc}")
+    if table is not None:                      # one upload per call; each launch takes its rows
+        table = torch.from_numpy(table.astype(np.int32)).to(keep[0].device)
     plan = []
     for first in range(0, n, FLK_PREP_MAX_CLIPS):
         part = descs[first:first + FLK_PREP_MAX_CLIPS]
@@ -541,8 +577,9 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
         a.mean, a.std = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
         a.out_clip_offset, a.out_clip_stride = out_offset + first, T * Ho * Wo * 3
         a.clips = arr
-        a._keepalive = (arr, keep)          # the struct holds raw pointers only
+        a._keepalive = (arr, keep, table)   # the struct holds raw pointers only
         a._boxes = None
+        a._frame_idx = None if table is None else table[first:first + len(part)]
         if boxes is not None:
             a._boxes = (PrepBox * len(part))(*[PrepBox(int(b[0]), int(b[1]), int(b[2]), int(b[3]), int(bool(f)))
                                                for b, f in zip(boxes[first:first + len(part)], flips[first:first + len(part)])])

@@ -12,7 +12,8 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, resolve_model, train_crop_params, u8_decode_table
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, check_sampling, resolve_model, sample_frame_indices, split_sampling,
+                               train_crop_params, u8_decode_table)
 
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 CLIP_DTYPES = (torch.float32, torch.uint8)
@@ -255,7 +256,7 @@ class FlickerVideoResNet:
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
-                 im_scale=128, resize_rule="sizes", augment=None):
+                 im_scale=128, resize_rule="sizes", augment=None, sampling=None):
         from .i3d_engine import check_optimizer
         # raw-size uint8 frames are prepared on the device (``prepare``): ResizeVideo(im_scale) -> CenterCropVideo(image_size), dataset.py:84-123;
         # resize_rule: "sizes" = the arithmetic of torch 1.4.0 (the reference's pin), "scale_factor" = current torch (videoresnet_spec.prepare_geometry)
@@ -268,6 +269,14 @@ class FlickerVideoResNet:
         self.augment = self._check_augment(augment)
         self.last_augment = None
         self._aug_rng = None if self.augment is None else random.Random(self.augment["seed"] + parallel.rank(process_group))
+        # sampling: how clips are cut from whole videos (``prepare_videos``, ``evaluate_videos``, loaders that yield lists of videos) -- the
+        # reference's VideoDataset settings (dataset.py:254-259, 500-586): {"sample_step": 1, "temporal_jitter": False, "temporal_jitter_step": 2,
+        # "random_shift": False, "seed": 0}, the defaults being its scripts' (r2plus1d_main_universal_attack.py:155-163).  The temporal draws
+        # come from a generator of their own, numpy.random.RandomState(seed + rank), as in the reference (numpy.random for the frames,
+        # random for the crop boxes)
+        self.sampling = check_sampling(sampling)
+        self.last_sampling = None
+        self._samp_rng = np.random.RandomState(self.sampling["seed"] + parallel.rank(process_group))
         # "pgd": delta <- clamp(delta - lr * sgn(g), +-dynamic_max_norm) instead of torch Adam (model.py:868) -- the radius is the clamp
         # bound the perturbation already has, so the restart schedule (model.py:1061-1066) widens it; no optimiser state
         self.optimizer = check_optimizer(optimizer)
@@ -377,6 +386,98 @@ class FlickerVideoResNet:
             self.last_augment = {"boxes": boxes, "flips": flips}
         return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
                                  rule=self.resize_rule, boxes=boxes, flips=flips)
+
+    def prepare_videos(self, videos, train=False, num_samples=1, out=None, out_offset=0):
+        """whole decoded videos -- a list of CUDA uint8 tensors ``[N_k,H_k,W_k,3]`` of any (differing) length and resolution -- to
+        ``len(videos) * num_samples`` normalised fp32 clips ``[T,self.H,self.W,3]``, video-major and sample-minor, in ONE launch per
+        ``FLK_PREP_MAX_CLIPS`` clips: the frame-index tables are drawn on the host (videoresnet_spec.sample_frame_indices, in video order
+        from the engine's temporal generator) and the kernel reads the resident videos through them (ops.prepare_clips(frame_idx=)).
+        ``train=False``: the test split's settings (no shift, no jitter) and the evaluation transform.  ``train=True``: the training
+        split's (videoresnet_spec.split_sampling) and, on an engine built with ``augment``, the training transform with one
+        ``(box, flip)`` per clip as ``prepare(train=True)`` draws them.  The tables are kept, one int64 ``[num_samples, T]`` per video,
+        on ``last_sampling``; boxes and flips on ``last_augment``."""
+        videos = list(videos) if isinstance(videos, (list, tuple)) else None
+        if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
+            raise ValueError("prepare_videos: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+        if int(num_samples) < 1:
+            raise ValueError(f"prepare_videos: num_samples must be >= 1, got {num_samples!r}")
+        kw = split_sampling(self.sampling, self.T, train)
+        tables = [sample_frame_indices(int(v.shape[0]), num_samples=int(num_samples), rng=self._samp_rng, **kw) for v in videos]
+        self.last_sampling = tables
+        clips = [v for v in videos for _ in range(int(num_samples))]
+        boxes = flips = None
+        if train and self.augment is not None:
+            boxes, flips = [], []
+            for x in clips:
+                Hr, Wr = ops._prep_geometry(int(x.shape[-3]), int(x.shape[-2]), self.im_scale, (self.H, self.W), self.resize_rule)[:2]
+                *box, flip = train_crop_params(Hr, Wr, (self.H, self.W), self.augment["scales"], self.augment["ratio"],
+                                               self.augment["flip_ratio"], self._aug_rng)
+                boxes.append(tuple(box))
+                flips.append(flip)
+            self.last_augment = {"boxes": boxes, "flips": flips}
+        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                 rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=np.concatenate(tables))
+
+    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False):
+        """``VideoLearnerAdversarial.evaluate(num_samples)`` (model.py:1227-1317) on whole videos resident on the device: every video is
+        scored by the argmax of the summed logits of ``num_samples`` clips cut at uniform offsets (the test split: no shift, no jitter)
+        and prepared with the evaluation transform.  ``videos``: a list of CUDA uint8 ``[N_k,H_k,W_k,3]``; ``labels``: one class per video.
+
+        Packing: the ``V * num_samples`` clips are taken video-major and sample-minor and packed into consecutive batches of the
+        engine's ``B``; the last batch is padded by repeating its last clip and the padded rows are dropped.  The per-video sums are
+        taken in fp32, clip after clip.  ``adversarial=True`` runs every batch clean and through the engine's perturbation.
+        Returns a dict of host arrays: ``clip_logits`` fp32 ``[V * num_samples, classes]`` and ``video_logits`` fp32 ``[V, classes]`` (the
+        perturbed ones when ``adversarial``), ``video_preds``, ``video_trues``, ``clip_preds``, ``clip_trues`` (int64), ``video_accuracy``,
+        ``clip_accuracy``; with ``adversarial`` also ``clean_clip_logits``, ``clean_video_logits``, ``clean_clip_preds``,
+        ``clean_video_preds``, ``clean_video_accuracy``, ``clean_clip_accuracy`` and ``video_fooling_ratio`` -- among the videos
+        classified correctly when clean, the share whose adversarial video prediction differs from the label (nan when there is none).
+        Known difference from the reference: its loop starts at video 1 (``range(1, len(ds))``, model.py:1279-1281) and so never
+        scores the first video; this one evaluates every video."""
+        videos = list(videos) if isinstance(videos, (list, tuple)) else None
+        if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
+            raise ValueError("evaluate_videos: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+        trues = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels, dtype=np.int64).reshape(-1)
+        S, V, B = int(num_samples), len(videos), self.B
+        if S < 1 or trues.shape[0] != V:
+            raise ValueError(f"evaluate_videos: {V} videos, {trues.shape[0]} labels, num_samples {num_samples!r}")
+        kw = split_sampling(self.sampling, self.T, False)
+        tables = [sample_frame_indices(int(v.shape[0]), num_samples=S, rng=self._samp_rng, **kw) for v in videos]
+        self.last_sampling = tables
+        rows = np.concatenate(tables)
+        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < B:
+            self._prep_buf = torch.empty((B, self.T, self.H, self.W, 3), dtype=torch.float32, device=videos[0].device)
+        x = self._prep_buf[:B]
+        clean, adv = [], []
+        for first in range(0, V * S, B):
+            ks = [min(first + b, V * S - 1) for b in range(B)]          # the last batch repeats its last clip
+            ops.prepare_clips([videos[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                              frame_idx=rows[ks])
+            n = min(B, V * S - first)
+            clean.append(self.logits(x, False)[:n].cpu())
+            if adversarial:
+                adv.append(self.logits(x, True)[:n].cpu())
+
+        def score(parts):
+            clip = torch.cat(parts).numpy()
+            video = np.zeros((V, clip.shape[1]), np.float32)
+            for j in range(S):                                       # fp32, clip after clip
+                video += clip[j::S]
+            return clip, video, clip.argmax(1).astype(np.int64), video.argmax(1).astype(np.int64)
+
+        clip_trues = np.repeat(trues, S)
+        c_clip, c_video, c_cp, c_vp = score(clean)
+        res = {"video_trues": trues, "clip_trues": clip_trues}
+        if adversarial:
+            clip, video, cp, vp = score(adv)
+            ok = c_vp == trues
+            res.update(clean_clip_logits=c_clip, clean_video_logits=c_video, clean_clip_preds=c_cp, clean_video_preds=c_vp,
+                       clean_video_accuracy=float((c_vp == trues).mean()), clean_clip_accuracy=float((c_cp == clip_trues).mean()),
+                       video_fooling_ratio=float(((vp != trues) & ok).sum() / ok.sum()) if ok.any() else float("nan"))
+        else:
+            clip, video, cp, vp = c_clip, c_video, c_cp, c_vp
+        res.update(clip_logits=clip, video_logits=video, clip_preds=cp, video_preds=vp,
+                   video_accuracy=float((vp == trues).mean()), clip_accuracy=float((cp == clip_trues).mean()))
+        return res
 
     def _is_raw(self, x):
         """uint8 frames that are not at the engine's H x W yet (clips that are take today's path: decoded by the apply kernel)"""
@@ -565,7 +666,10 @@ class FlickerVideoResNet:
 
     def train_an_epoch(self, data_loaders, criterion, metric, lr):
         """``train_an_epoch`` (model.py:627-789): 'train' then 'valid' over iterables of (inputs, target, _); the valid phase
-        evaluates the same loss without an update.  Result keys as model.py:780-786."""
+        evaluates the same loss without an update.  Result keys as model.py:780-786.  A loader may yield ``inputs`` as a LIST of whole
+        uint8 videos ``[N_k,H_k,W_k,3]`` (one per clip of the batch): the train phase then cuts a clip from each with the training split's
+        sampling settings (and the training transform when the engine has ``augment``), the valid phase one clip with no shift and no
+        jitter (``prepare_videos``)."""
         import time
         result = {}
         for phase in ("train", "valid"):
@@ -573,8 +677,13 @@ class FlickerVideoResNet:
             n, loss_sum, miss, valid = 0, 0.0, 0.0, 0.0
             xdt = None
             for inputs, target, *_ in data_loaders[phase]:
+                whole = isinstance(inputs, (list, tuple))           # whole videos: sampled and prepared in one launch
+                if whole:
+                    if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < len(inputs):
+                        self._prep_buf = torch.empty((max(len(inputs), self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
+                    inputs = self.prepare_videos(inputs, train=(phase == "train"), out=self._prep_buf)
                 xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
-                augmenting = phase == "train" and self.augment is not None
+                augmenting = phase == "train" and self.augment is not None and not whole
                 if augmenting and not self._is_raw(inputs):
                     raise ValueError("augment is set but the train clips are at the engine's size already: there is nothing to prepare "
                                      "(the training transform applies to raw uint8 frames)")
@@ -784,7 +893,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None, optimizer="adam"):
+                 process_group=None, optimizer="adam", sampling=None):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -797,6 +906,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
             batch_size = getattr(dataset, "batch_size", 1)
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
-                         process_group=process_group, attack_type=attack_type, optimizer=optimizer)
+                         process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -269,6 +269,127 @@ def prepare_host_train(frames, box, flip, im_scale=128, input_size=112, mean=DEF
     return clip.permute(1, 2, 3, 0).contiguous()
 
 
+SAMPLING_DEFAULTS = {"sample_step": 1, "temporal_jitter": False, "temporal_jitter_step": 2, "random_shift": False, "seed": 0}
+
+
+def check_sampling(sampling):
+    """``sampling`` (None or a dict with keys of ``SAMPLING_DEFAULTS``) completed with the defaults -- the reference *scripts'* settings
+    (r2plus1d_main_universal_attack.py:155-163: step 1, no jitter, no shift).  Anything malformed is a ValueError."""
+    if sampling is None:
+        sampling = {}
+    if not isinstance(sampling, dict):
+        raise ValueError(f"sampling must be a dict with keys {sorted(SAMPLING_DEFAULTS)}, got {type(sampling).__name__}")
+    unknown = sorted(set(sampling) - set(SAMPLING_DEFAULTS))
+    if unknown:
+        raise ValueError(f"sampling: unknown keys {unknown}; known: {sorted(SAMPLING_DEFAULTS)}")
+    s = dict(SAMPLING_DEFAULTS, **sampling)
+    for key in ("sample_step", "temporal_jitter_step"):
+        v = s[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError(f"sampling[{key!r}] must be an integer >= 1, got {v!r}")
+        s[key] = int(v)
+    for key in ("temporal_jitter", "random_shift"):
+        if not isinstance(s[key], (bool, np.bool_)):
+            raise ValueError(f"sampling[{key!r}] must be a bool, got {s[key]!r}")
+        s[key] = bool(s[key])
+    if isinstance(s["seed"], bool) or not isinstance(s["seed"], (int, np.integer)) or not 0 <= s["seed"] < 2 ** 32 - 4096:
+        raise ValueError(f"sampling['seed'] must be an integer in [0, 2**32 - 4096) (a RandomState seed; the rank is added to it), got {s['seed']!r}")
+    s["seed"] = int(s["seed"])
+    return s
+
+
+def split_sampling(sampling, sample_length, train):
+    """The keyword arguments of ``sample_frame_indices`` for one side of the reference's train / test split (``split_train_test``,
+    dataset.py:459-475) of the dataset settings ``sampling``.  The training split steps by ``temporal_jitter_step`` when jittering but
+    keeps ``presample_length`` at the unjittered ``sample_length * sample_step``; the test split has no shift and no jitter."""
+    s = check_sampling(sampling)
+    presample = int(sample_length) * s["sample_step"]
+    if train:
+        return dict(sample_length=int(sample_length), sample_step=s["temporal_jitter_step"] if s["temporal_jitter"] else s["sample_step"],
+                    temporal_jitter=s["temporal_jitter"], random_shift=s["random_shift"], presample_length=presample)
+    return dict(sample_length=int(sample_length), sample_step=s["sample_step"], temporal_jitter=False, random_shift=False,
+                presample_length=presample)
+
+
+def sample_frame_indices(num_frames, sample_length, sample_step=1, num_samples=1, temporal_jitter=False, random_shift=False,
+                         presample_length=None, rng=None):
+    """Frame numbers of the ``num_samples`` clips the reference's ``VideoDataset`` cuts from a video of ``num_frames`` frames:
+    ``_sample_indices`` then ``_get_frames`` (dataset.py:500-586) restated, int64 ``[num_samples, sample_length]``.  ``rng``: a
+    ``numpy.random.RandomState`` (None: a fresh unseeded one); the draws are made in the reference's order, so ``RandomState(s)`` gives
+    the tables the reference gives under ``np.random.seed(s)`` (it draws with ``numpy.random.randint``).
+
+    Offsets: a video longer than ``presample_length`` (default ``sample_length * sample_step``; ``split_sampling`` says why it is an
+    argument of its own) draws ONE ``randint(num_frames - presample_length + 1, size=num_samples)``, sorted, when ``random_shift``;
+    otherwise offset x is ``int(d / 2 + d * x)`` with ``d = (num_frames - presample_length + 1) / num_samples``.  A video not longer
+    than that starts every clip at frame 0.
+    Frames, per clip in clip order: the offset, then ``sample_length - 1`` times a step -- ``randint(sample_step + 1)`` when
+    ``temporal_jitter`` (0 repeats the previous frame), else ``sample_step``.  The first step that would pass the last frame ends the
+    clip: no further draw is made and the rest of the clip repeats its last frame.
+
+    The model of decord this rests on (decord is not available where this was written, so it is an assumption): after
+    ``seek_accurate(o)`` a ``next()`` yields frame ``o``; ``skip_frames(k)`` advances by ``k`` without raising; a ``next()`` past the
+    last frame raises ``StopIteration``."""
+    N, T, step, S = int(num_frames), int(sample_length), int(sample_step), int(num_samples)
+    P = T * step if presample_length is None else int(presample_length)
+    if N < 1 or T < 1 or step < 1 or S < 1 or P < 1:
+        raise ValueError(f"sample_frame_indices: num_frames {N}, sample_length {T}, sample_step {step}, num_samples {S} and "
+                         f"presample_length {P} must all be >= 1")
+    rng = np.random.RandomState() if rng is None else rng
+    if N > P:
+        if random_shift:
+            offsets = np.sort(rng.randint(N - P + 1, size=S))
+        else:
+            d = (N - P + 1) / S
+            offsets = np.array([int(d / 2.0 + d * x) for x in range(S)])
+    else:
+        offsets = np.zeros((S,), dtype=int)
+    table = np.empty((S, T), np.int64)
+    ramp = step * np.arange(T)
+    for k, o in enumerate(offsets):
+        cur, n = int(o), 1
+        if not temporal_jitter:                    # o, o + step, ... while inside the video, then its last frame inside
+            table[k] = np.minimum(cur + ramp, cur + (N - 1 - cur) // step * step)
+            continue
+        if cur + step * (T - 1) <= N - 1:          # no step can pass the last frame: all T - 1 draws are made -- as one call, which
+            table[k, 0] = cur                      # leaves a RandomState where T - 1 single draws leave it
+            table[k, 1:] = cur + np.cumsum(rng.randint(step + 1, size=T - 1))
+            continue
+        table[k, 0] = cur
+        while n < T:
+            st = int(rng.randint(step + 1))
+            if st and cur + st > N - 1:
+                break
+            cur += st
+            table[k, n] = cur
+            n += 1
+        table[k, n:] = cur
+    return table
+
+
+def is_video_file(path):
+    """whether an ``.npz`` holds whole videos (``video_00000``, ...) and not a ``clips`` array"""
+    with np.load(path, allow_pickle=True) as z:
+        return "clips" not in z.files and "video_00000" in z.files
+
+
+def load_video_file(path):
+    """A whole-video ``.npz``: ``labels`` int64 ``[V]`` and ``video_00000``, ``video_00001``, ... each uint8 ``[N_k,H_k,W_k,3]`` (lengths and
+    resolutions may differ), optionally ``names`` ``[V]`` -> ``(list of contiguous uint8 arrays, labels int64, names)``."""
+    z = np.load(path, allow_pickle=True)
+    labels = z["labels"].astype(np.int64).reshape(-1)
+    videos = []
+    for k in range(len(labels)):
+        key = f"video_{k:05d}"
+        if key not in z.files:
+            raise ValueError(f"{path}: {len(labels)} labels but no {key}")
+        v = z[key]
+        if v.dtype != np.uint8 or v.ndim != 4 or v.shape[-1] != 3 or v.shape[0] < 1:
+            raise ValueError(f"{path}: {key} must be uint8 [N,H,W,3], got {v.shape} {v.dtype}")
+        videos.append(np.ascontiguousarray(v))
+    names = [str(n) for n in z["names"]] if "names" in z.files else [f"video_{k:05d}" for k in range(len(labels))]
+    return videos, labels, names
+
+
 def load_weights(path, arch=None):
     """Victim weights for FlickerVideoResNet as ``{state_dict name: float32 ndarray}``.
 

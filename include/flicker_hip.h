@@ -322,6 +322,21 @@ int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream);
 typedef struct { int i, j, h, w; int flip; } flk_prep_box;   /* box in the RESIZED image; flip 0/1 */
 int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes /* HOST [nclip] */, float* out, void* stream);
 
+/* Either transform through a frame-index table: the clips are cut from whole resident videos on the way (the temporal sampling of the
+ * reference's VideoDataset, dataset.py:500-586; videoresnet_spec.sample_frame_indices draws the tables as the reference does).
+ * Output frame t of clip k is computed from source frame frame_idx[k * T_out + t] of clips[k] instead of frame t; nothing else differs,
+ * so the result is bitwise what flk_clip_prepare (boxes NULL) or flk_clip_prepare_train (boxes given) writes for the frames gathered
+ * beforehand, and with the identity table what they write for the view itself.  A frame the table repeats is computed again.
+ * `a` as for those calls, except: clips[k].T is the number of SOURCE frames in the view (any positive count), clip k is written as
+ * [T_out][Ho][Wo][3] and out_clip_stride >= T_out*Ho*Wo*3.  frame_idx: DEVICE int32 [nclip][T_out], read by the kernel when it runs;
+ * its validity is the caller's: the kernel clamps every index it reads into [0, clips[k].T - 1], so a bad table gives wrong frames
+ * but never a read outside the view (ops.prepare_clips refuses such a table before it launches).
+ * No allocation, no synchronisation, no atomics; the result does not depend on the launch geometry.
+ * FLK_EINVAL (before any GPU call): everything flk_clip_prepare (boxes NULL) / flk_clip_prepare_train (boxes given) refuses, a null
+ * frame_idx, T_out outside 1..65535. */
+int flk_clip_prepare_sampled(const flk_prepare_args* a, const flk_prep_box* boxes /* HOST [nclip], or NULL: the evaluation transform */,
+                             const int32_t* frame_idx /* DEVICE [nclip][T_out] */, int T_out, float* out, void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

@@ -9,7 +9,12 @@ uint8 clips may also be RAW decoded frames of any H x W (what the reference's lo
 video is resized (shorter side to `--im-scale`), centre-cropped to `--image-size` and normalised by one kernel from the resident raw
 upload (`--prepare device`, the default for such files) or on the host with torch (`--prepare host`); `--resize-rule` picks the
 coordinate rule (videoresnet_spec.prepare_geometry).  Clips are raw when they are not square, or not `--image-size` when that is
-given, or whenever `--prepare` is given (the engine then is 112 x 112 unless `--image-size` says otherwise)."""
+given, or whenever `--prepare` is given (the engine then is 112 x 112 unless `--image-size` says otherwise).
+WHOLE-VIDEO files: `labels` (int64 [V]) and `video_00000`, `video_00001`, ... (each uint8 [N_k,H_k,W_k,3]) instead of `clips`.  The
+videos stay resident as uint8 and the clip of `--sample-length` frames attacked in each is cut as the reference's VideoDataset cuts
+it (dataset.py:500-586: `--sample-step`, `--temporal-jitter`, `--temporal-jitter-step`, `--random-shift`, generator
+`numpy.random.RandomState(--sample-seed)`) and prepared in the same kernel launch; the defaults are the reference script's settings
+(one clip at the uniform offset, step 1, no jitter, no shift)."""
 import argparse
 import os
 import sys
@@ -32,6 +37,40 @@ LR = 0.001
 LAMBDA = 1.0
 BETA_1 = 0.5
 N_ITER = 3000                    # fit_single_video_attack(n_iter=3000), model.py:962
+MODEL_INPUT_SIZE = 16            # frames per clip for the three VideoResNets
+
+
+def run_whole_videos(a):
+    """main() for whole-video files: one clip per video, cut and prepared on the device, then the loop of clips at the engine's size"""
+    if a.prepare == "host":
+        raise ValueError("--prepare host applies to files of clips; whole videos are sampled and prepared on the device")
+    videos, labels, names = vs.load_video_file(a.videos_npz)
+    T, S = a.sample_length, a.image_size or 112
+    sampling = {"sample_step": a.sample_step, "temporal_jitter": a.temporal_jitter, "temporal_jitter_step": a.temporal_jitter_step,
+                "random_shift": a.random_shift, "seed": a.sample_seed}
+    classes = [l.strip() for l in open(a.label_map)] if a.label_map else None
+    arch, _, ncls = vs.resolve_model(a.base_model, T)
+    W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
+    learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=T, image_size=S, dtype=a.dtype,
+                                 l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling)
+    dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
+                        f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
+    crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
+    xd, yd = [torch.from_numpy(v).cuda() for v in videos], torch.from_numpy(labels).cuda()
+    # train=True: fit_many_videos iterates the dataset's TRAINING loader (model.py:832); with the default flags the two splits sample alike
+    clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
+    return learner.fit_many_videos(clips, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
+                                   reset_optimizer_per_video=a.reset_optimizer_per_video)
+
+
+def report(out):
+    for name, r in out.items():
+        if r is None:
+            print(f"{name}: clean clip misclassified, skipped")
+        else:
+            print(f"{name}: {len(r['loss/total'])} iterations, adversarial {bool(r['is_adversarial'][-1])}, thickness "
+                  f"{r['perturbation/thickness'][-1]:.4f}, roughness {r['perturbation/roughness'][-1]:.4f}, restarts {r['restarts']}", flush=True)
 
 
 def main():
@@ -64,7 +103,16 @@ def main():
     ap.add_argument("--reset-optimizer-per-video", action="store_true", help="fresh Adam state for every video (the reference carries one "
                     "state from video to video, model.py:946; with --batch > 1 the carried state is per batch slot; --optimizer pgd keeps no "
                     "state, so there is nothing to reset)")
+    ap.add_argument("--sample-length", type=int, default=MODEL_INPUT_SIZE, help="whole-video files: frames per clip (files of clips bring their own)")
+    ap.add_argument("--sample-step", type=int, default=1, help="whole-video files: frames between the frames of a clip (dataset.py's sample_step)")
+    ap.add_argument("--temporal-jitter", action="store_true", help="whole-video files, training split: a random step of 0 .. "
+                    "--temporal-jitter-step frames between the frames of a clip (step 0 repeats the frame)")
+    ap.add_argument("--temporal-jitter-step", type=int, default=2)
+    ap.add_argument("--random-shift", action="store_true", help="whole-video files, training split: clips start at random offsets, not uniform ones")
+    ap.add_argument("--sample-seed", type=int, default=0, help="whole-video files: the frame sampler is numpy.random.RandomState(seed + rank)")
     a = ap.parse_args()
+    if vs.is_video_file(a.videos_npz):
+        return report(run_whole_videos(a))
     z = np.load(a.videos_npz, allow_pickle=True)
     clips, labels = z["clips"], z["labels"].astype(np.int64)
     names = [str(n) for n in z["names"]] if "names" in z else [f"video_{i:05d}" for i in range(len(clips))]
@@ -99,12 +147,7 @@ def main():
         videos = ((torch.from_numpy(clips[i:i + 1]).cuda(), torch.from_numpy(labels[i:i + 1]).cuda(), names[i]) for i in range(len(clips)))
     out = learner.fit_many_videos(videos, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
                                   reset_optimizer_per_video=a.reset_optimizer_per_video)
-    for name, r in out.items():
-        if r is None:
-            print(f"{name}: clean clip misclassified, skipped")
-        else:
-            print(f"{name}: {len(r['loss/total'])} iterations, adversarial {bool(r['is_adversarial'][-1])}, thickness "
-                  f"{r['perturbation/thickness'][-1]:.4f}, roughness {r['perturbation/roughness'][-1]:.4f}, restarts {r['restarts']}", flush=True)
+    report(out)
 
 
 if __name__ == "__main__":

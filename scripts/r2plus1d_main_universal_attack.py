@@ -24,7 +24,17 @@ not square, or not `--image-size` when that is given, or whenever `--prepare` is
 RandomResizedCropVideo with `--aug-scales`, or RandomCropVideo with `--aug-no-resize`, then RandomHorizontalFlipVideo with `--flip-ratio`),
 a fresh box and flip per clip and epoch from `random.Random(--aug-seed + rank)`: on the device by the second preparation kernel, or
 with `--prepare host` per batch with torch (videoresnet_spec.prepare_host_train, same sampler).  The validation split and the default
-(`eval`, what the reference's own attack scripts pass for both splits) keep the evaluation transform."""
+(`eval`, what the reference's own attack scripts pass for both splits) keep the evaluation transform.
+
+WHOLE-VIDEO files: an `.npz` with `labels` (int64 [V]) and `video_00000`, `video_00001`, ... (each uint8 [N_k,H_k,W_k,3], lengths and
+resolutions free) instead of `clips`.  The videos of a rank's batches stay resident as uint8; every training batch cuts a new clip of
+`--sample-length` frames from each of its videos as the reference's VideoDataset does (dataset.py:500-586; `--sample-step`,
+`--temporal-jitter`, `--temporal-jitter-step`, `--random-shift`, generator `numpy.random.RandomState(--sample-seed + rank)`) and prepares it in
+the same kernel launch; the validation split takes one clip per video with no shift and no jitter.  The default flags are the
+reference script's settings (step 1, no jitter, no shift: r2plus1d_main_universal_attack.py:155-163).  `--eval-num-samples N` scores
+whole validation videos after training as the reference's `evaluate(num_samples=N)` does (the argmax of the summed logits of N clips),
+clean and under the trained perturbation, prints the video-level accuracy and fooling ratio and stores them in `video_eval.npz`
+beside the checkpoints.  Both files of a run are of the same kind; files with a `clips` array behave exactly as before."""
 import argparse
 import glob
 import os
@@ -113,6 +123,60 @@ def loader(clips, labels, batch_size, rank=0, world=1):
         yield torch.from_numpy(clips[sl]).cuda(), torch.from_numpy(labels[sl]).cuda(), None
 
 
+class ResidentVideos:
+    """whole uint8 videos of the batches one rank takes, uploaded once; a batch is the LIST of its videos (the engine cuts the clips)"""
+
+    def __init__(self, videos, labels, batch_size, rank=0, world=1):
+        self.batches = []
+        for i in batch_ids(len(videos), batch_size, rank, world):
+            sl = slice(i * batch_size, (i + 1) * batch_size)
+            self.batches.append(([torch.from_numpy(v).cuda() for v in videos[sl]], torch.from_numpy(labels[sl]).cuda(), None))
+
+    def __iter__(self):
+        return iter(self.batches)
+
+
+def run_whole_videos(a, world, rank, local_rank, augment):
+    """main() for whole-video files"""
+    if a.prepare == "host":
+        raise ValueError("--prepare host applies to files of clips; whole videos are sampled and prepared on the device")
+    vtr, ytr, _ = vs.load_video_file(a.train_npz)
+    vva, yva, _ = vs.load_video_file(a.val_npz)
+    T, HW = a.sample_length, a.image_size or 112
+    sampling = {"sample_step": a.sample_step, "temporal_jitter": a.temporal_jitter, "temporal_jitter_step": a.temporal_jitter_step,
+                "random_shift": a.random_shift, "seed": a.sample_seed}
+    arch, _, ncls = vs.resolve_model(a.base_model, T)
+    W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
+    learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
+                                 device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling)
+    dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
+                        f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
+    start_epoch = 1
+    ckpts = sorted(glob.glob(os.path.join(dest, "*.npy")), key=os.path.getmtime)
+    if INIT_PERT_FROM_LAST_CKPT and ckpts:
+        learner.pert_model.init_perturbation(np.load(ckpts[-1], allow_pickle=True)[-1]["valid/perturbation"])
+        print("Success! init from last ckpt")
+    if CONTINUE_TRAIN and ckpts:
+        start_epoch = int(ckpts[-1].split("_")[-1].split(".")[0]) + 1
+        print(f"Success! to continue from last epoch. init with {start_epoch}")
+    crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
+    resident = {"train": ResidentVideos(vtr, ytr, a.batch_size, rank, world), "valid": ResidentVideos(vva, yva, a.batch_size)}
+    results = learner.fit(resident, crit, Adversarial_metrics(targeted=TARGETED_ATTACK), lr=a.lr, epochs=a.epochs, model_dir=dest if rank == 0 else None,
+                          model_name=learner.model_name, save_model=rank == 0, start_epoch=start_epoch)
+    if rank == 0:
+        for e, r in enumerate(results, start_epoch):
+            print(f"epoch {e}: train loss {r['train/loss']:.5f} fooling {r['train/fooling_ratio']:.4f} | valid loss {r['valid/loss']:.5f} "
+                  f"fooling {r['valid/fooling_ratio']:.4f} | thickness {r['valid/pert_thickness']:.5f} roughness {r['valid/pert_roughness']:.5f}", flush=True)
+        if a.eval_num_samples > 0:
+            ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=a.eval_num_samples, adversarial=True)
+            print(f"video evaluation, {a.eval_num_samples} clips per video, {len(vva)} videos: clean video accuracy {ev['clean_video_accuracy']:.4f} | "
+                  f"adversarial video accuracy {ev['video_accuracy']:.4f} clip accuracy {ev['clip_accuracy']:.4f} | "
+                  f"video fooling ratio {ev['video_fooling_ratio']:.4f}", flush=True)
+            os.makedirs(dest, exist_ok=True)
+            np.savez(os.path.join(dest, "video_eval.npz"), num_samples=np.int64(a.eval_num_samples), **ev)
+
+
 class ResidentShard:
     """uint8 clips of the batches one rank takes, uploaded once; every epoch's batches are slices of the device tensor"""
 
@@ -162,6 +226,15 @@ def main():
     ap.add_argument("--aug-no-resize", action="store_true", help="train: RandomCropVideo(image size) instead of the resized crop (random_crop_scales=None)")
     ap.add_argument("--flip-ratio", type=float, default=0.5, help="train: probability of the horizontal flip")
     ap.add_argument("--aug-seed", type=int, default=0, help="train: the sampler is random.Random(seed + rank)")
+    ap.add_argument("--sample-length", type=int, default=MODEL_INPUT_SIZE, help="whole-video files: frames per clip (files of clips bring their own)")
+    ap.add_argument("--sample-step", type=int, default=1, help="whole-video files: frames between the frames of a clip (dataset.py's sample_step)")
+    ap.add_argument("--temporal-jitter", action="store_true", help="whole-video files, training split: a random step of 0 .. "
+                    "--temporal-jitter-step frames between the frames of a clip (step 0 repeats the frame)")
+    ap.add_argument("--temporal-jitter-step", type=int, default=2)
+    ap.add_argument("--random-shift", action="store_true", help="whole-video files, training split: clips start at random offsets, not uniform ones")
+    ap.add_argument("--sample-seed", type=int, default=0, help="whole-video files: the frame sampler is numpy.random.RandomState(seed + rank)")
+    ap.add_argument("--eval-num-samples", type=int, default=0, help="whole-video files: after training, score every validation video by N clips "
+                    "(the reference's evaluate(num_samples=N)) clean and perturbed; 0 = skip")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
     a = ap.parse_args()
@@ -176,6 +249,14 @@ def main():
     augment = None
     if a.train_transforms == "train":
         augment = {"scales": None if a.aug_no_resize else tuple(a.aug_scales), "ratio": (3 / 4, 4 / 3), "flip_ratio": a.flip_ratio, "seed": a.aug_seed}
+    whole = vs.is_video_file(a.train_npz)
+    if whole != vs.is_video_file(a.val_npz):
+        raise ValueError("--train-npz and --val-npz must both hold clips or both hold whole videos")
+    if whole:
+        run_whole_videos(a, world, rank, local_rank, augment)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
     xtr, ytr = load_clips(a.train_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule, keep_raw=augment is not None)
     xva, yva = load_clips(a.val_npz, a.decode, a.image_size, a.prepare, a.im_scale, a.resize_rule)
     T, (HW, raw_train) = xtr.shape[1], engine_size(xtr, a.image_size, a.prepare)
