@@ -2,12 +2,22 @@
 // HBM-bound kernels: one thread = one position x one 16-byte channel group.
 //   forward : first maximum in (t,h,w) scan order wins (strict >), padded cells never win
 //             (i3d.py:174,189,212,252,398); the winning window index is kept as one byte.
-//   backward: default = scatter form (maxpool_scatter_bwd): a workgroup owns a tile of INPUT cells in LDS and every
-//             window that reaches the tile adds its gradient to the cell its saved argmax names.  bf16 mode sums in
-//             32-bit fixed point with integer LDS atomics (order-independent, bitwise reproducible).  fp32 (the parity mode)
-//             takes the gather forms (every input cell scans the windows containing it; fixed summation order), as does
-//             FLK_POOL_GATHER=1 in bf16; the scatter form in fp32 (float LDS atomics, last-ulp run-to-run differences) only
-//             with FLK_POOL_SCATTER_F32=1.  Optional relu mask of the producing layer (mask > 0) fused in.
+//             Values are compared as numbers: -0.0 == +0.0 (the first of them in scan order wins), a window of -inf only records
+//             tap 0.  relu_input: windows whose maximum is <= 0 record 255 ("no cell").  One deviation: the bf16 sortable-key
+//             kernels (3x3x3 / 1) rank +0.0 above -0.0, so among tied zeros of both signs the first +0.0 wins (see bf16x2_to_keys).
+//             Dispatch: stride-1 SAME windows of >= 8 taps stage a halo box in LDS (maxpool_s1_tiled_fwd; bf16 3x3x3 takes the
+//             sortable-key kernels maxpool_s1_wrun_fwd_bf16 / maxpool_s1_tiled_fwd_bf16); every other geometry takes one thread per
+//             output (maxpool_fwd_kernel_k for the I3D windows, maxpool_fwd_kernel for the rest).
+//   backward: the three strided I3D geometries take the owner form (maxpool_strided_bwd, both dtypes: every cell written once, fixed
+//             order).  Everything else: bf16 takes the scatter form (maxpool_scatter_bwd): a workgroup owns a tile of INPUT cells in
+//             LDS and every window that reaches the tile adds its gradient to the cell its saved argmax names, in 32-bit fixed point
+//             with integer LDS atomics (order-independent, bitwise reproducible); the fixed-point exponent E depends on the number n
+//             of windows that can cover one cell (E = 24 for n <= 64, 23 up to 128, 22 up to 255: n addends never leave an int32).
+//             fp32 (the parity mode) takes the gather forms (every input cell scans the windows containing it; fixed summation
+//             order): maxpool_s1_tiled_bwd for the LDS-tiled stride-1 windows, maxpool_bwd_kernel otherwise.  There is no switch
+//             between the forms.  Optional relu mask of the producing layer (mask > 0) fused in.
+//   fused   : flk_maxpool3d_bwd_gemm (bf16) = the scatter form fed by an MFMA product, same fixed point.
+//   Channel slices: in / out / gout / gin / mask are channels [coff, coff + C) of rows ld wide; nothing outside the slice is written.
 #include <stdlib.h>
 #include <string.h>
 #include "flk_internal.h"
@@ -314,7 +324,7 @@ static bool strided_owner_ok(const flk_pool_args* a, int kt, int kh, int kw, int
 }
 
 // ------------------------------------------------------------------------------------------------
-// LDS-tiled variants for stride-1 SAME pooling with an odd window (the Inception branch-3 pool, i3d.py:212):
+// LDS-tiled variants for stride-1 SAME pooling with a window of at least 8 taps, odd or even (the Inception branch-3 pool, i3d.py:212):
 // every cell is touched by kt*kh*kw windows, so the simple kernels above read each byte 27x through L1/L2.
 // Here a workgroup stages the halo box of ONE 64-byte channel slab once (same 4-plane LDS image as
 // conv_igemm.hip) and all window taps are LDS reads.
@@ -322,6 +332,7 @@ struct PoolTP {
   PoolKP k;
   int Tt, Ht, Wt, nTt, nTh, nTw, Th, Hh, Wh, P, plane_b, rows, ntiles, nslab;
   int dbg;             // timing experiments only (FLK_PF_DBG, W-run forward): 1 = no halo loads, 2 = no column maxima, 4 = no stores
+  int fx_e;            // fixed-point exponent E of the bf16 scatter backward (fixed_point_exponent)
 };
 
 __device__ static inline int pplane_off(int c, int plane_b) { return c * plane_b + (c >> 1) * 32; }
@@ -410,6 +421,10 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd(const PoolTP p) {
 // bf16 fast path of the tiled forward: the halo holds SORTABLE 16-bit keys (key = bits ^ (sign ? 0xffff : 0x8000): unsigned
 // order == float order); one element-tap costs 2 VALU ops: pack (key << 16 | 255 - tap) and v_max_u32 -- the larger low
 // byte wins among equal keys, i.e. the FIRST maximum in scan order.  Taps are compile-time so the LDS reads batch.
+// DEVIATION from "values compare as numbers": key(-0.0) = 0x7fff < key(+0.0) = 0x8000, so in a window whose maximum is zero a +0.0
+// beats an EARLIER -0.0 (the float kernels and torch take the first of the two).  The recorded tap still names an in-bounds cell whose
+// value equals the window maximum, and out is a zero; only which of the tied zero cells receives the gradient differs.  Inputs here
+// are ReLU outputs (+0.0 only), where the two rules agree.
 __device__ static inline uint32_t bf16x2_to_keys(uint32_t w) {
   const uint32_t sign = w & 0x80008000u;                 // per half: 0x8000 if negative
   const uint32_t flip = (sign >> 15) * 0x7fffu;          // 0x7fff for negative halves
@@ -758,9 +773,12 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
   // bf16 mode accumulates in 32-bit FIXED POINT with a per-workgroup power-of-two scale: ds_add_f32 (and
   // ds_cmpst_rtn_b32) run ~10x slower than the integer LDS atomics on gfx950 (measured: 0.28 ms vs 0.12 ms for the
   // Mixed_3c pool), and integer sums are associative, so the result does not depend on the order the waves arrive in.
-  // Scale = 2^24 / 2^floor(log2 max|gout|) over the windows this workgroup reads: |v * scale| < 2^25, <= 27 addends
-  // < 2^30; a bf16 gradient (8 significant bits) within 2^-17 of the largest one is represented exactly and the
-  // absolute error of a cell is < 27 * 2^-25 * max|gout|, far below the bf16 rounding of the stored result.
+  // Scale = 2^E / 2^floor(log2 max|gout|) over the windows this workgroup reads: |v * scale| < 2^(E+1) (a bf16 value times a power
+  // of two: an integer multiple of 2^(E-7), never rounded up to 2^(E+1)).  A cell receives at most n = ceil(kt/st) * ceil(kh/sh) *
+  // ceil(kw/sw) addends, and the host picks E = min(24, 30 - ceil(log2 n)) (fixed_point_exponent), so |sum| < n * 2^(E+1) <= 2^31:
+  // E = 24 for n <= 64 (every I3D pool: 27 addends < 2^30), 23 for n <= 128, 22 for n <= 255.  A bf16 gradient (8 significant bits)
+  // within 2^-(E-7) of the largest one is represented exactly; every addend is off by at most 2^-(E+1) * max|gout| and a cell by
+  // less than n * 2^-(E+1) * max|gout| (27 * 2^-25 * max|gout| for 3x3x3 / 1), far below the bf16 rounding of the stored result.
   // fp32 mode (the parity mode) keeps exact float atomics.
   constexpr bool FIXED = sizeof(T) == 2;
   float scale = 1.f, inv_scale = 1.f;
@@ -786,8 +804,8 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
     __syncthreads();
     int ex = (int)(*smax >> 23);                               // biased exponent of the largest magnitude
     ex = min(max(ex, 26), 254);                                // (inf/nan gradients are not representable; clamp)
-    scale = __uint_as_float((unsigned)(127 + 24 + 127 - ex) << 23);
-    inv_scale = __uint_as_float((unsigned)(127 - 24 - 127 + ex) << 23);
+    scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
+    inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
   }
   __syncthreads();
   const int khkw = k.kh * k.kw;
@@ -861,6 +879,10 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
 // each to the cell its saved argmax names, in 32-bit fixed point with integer LDS atomics exactly like maxpool_scatter_bwd
 // (order-independent: bitwise reproducible).  The per-workgroup scale needs max |value| first: the product pass runs twice
 // (max, then scatter); its MFMAs are ~1 % of the kernel.
+// Fixed-point range with fp32 products: |v * scale| < 2^(E+1) is exact in fp32 (power-of-two scale) and fp32 values of 2^23 and above
+// are integers, so __float2int_rn can round a product UP to 2^(E+1) only where 2^(E+1) <= 2^23, i.e. E = 22 (n <= 255 addends of at
+// most 2^23: < 2^31).  For E = 23 and 24 an addend is an integer below 2^(E+1), and n <= 2^(30-E) of them stay below 2^31.  The
+// error of a cell is below n * 2^-(E+1) * max|product|, as in maxpool_scatter_bwd.
 struct PoolGemmP {
   PoolTP t;
   const char* g; int g_ld, g_coff, KS;       // KS = K / 32 k-steps
@@ -943,8 +965,8 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
   __syncthreads();
   int ex = (int)(*smax >> 23);
   ex = min(max(ex, 26), 254);
-  const float scale = __uint_as_float((unsigned)(127 + 24 + 127 - ex) << 23);
-  const float inv_scale = __uint_as_float((unsigned)(127 - 24 - 127 + ex) << 23);
+  const float scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
+  const float inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
   // ---- pass 2: the same products, scattered ----
   const int khkw = k.kh * k.kw;
   for (int base = wave * 16; base < P; base += 64) {
@@ -1096,8 +1118,8 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
   __syncthreads();
   int ex = (int)(*smax >> 23);
   ex = min(max(ex, 26), 254);
-  const float scale = __uint_as_float((unsigned)(127 + 24 + 127 - ex) << 23);
-  const float inv_scale = __uint_as_float((unsigned)(127 - 24 - 127 + ex) << 23);
+  const float scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
+  const float inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
   if (P > 0) {
     // Branch-free: the 8 table reads of a window are requested together, and an element whose cell is outside the tile adds into a
     // dummy word of its own thread instead of being skipped.  (Written as  if (inside) atomicAdd(.. + lut[tap] ..)  hipcc emitted, per
@@ -1165,11 +1187,21 @@ static flk_tile choose_scatter_tile(const flk_pool_args* a, long max_reach = 0) 
   return best;
 }
 
+// fixed-point exponent of the bf16 scatter forms: a cell is covered by at most n = ceil(kt/st) * ceil(kh/sh) * ceil(kw/sw) windows, each
+// adding less than 2^(E+1) in magnitude; E = min(24, 30 - ceil(log2 n)) keeps n of them inside an int32 (n <= 255 taps: E >= 22)
+static int fixed_point_exponent(const flk_pool_args* a) {
+  const int n = ((a->kt + a->st - 1) / a->st) * ((a->kh + a->sh - 1) / a->sh) * ((a->kw + a->sw - 1) / a->sw);
+  int lg = 0;
+  while ((1 << lg) < n) ++lg;
+  return 30 - lg < 24 ? 30 - lg : 24;
+}
+
 template <typename T>
 static int launch_scatter_bwd(const PoolKP& kp, const flk_pool_args* a, hipStream_t s) {
   constexpr int EPL = PV<T>::EPL;
   PoolTP tp{};
   tp.k = kp;
+  tp.fx_e = fixed_point_exponent(a);
   const flk_tile t = choose_scatter_tile(a);
   tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
   tp.nTt = (a->Ti + t.Tt - 1) / t.Tt; tp.nTh = (a->Hi + t.Ht - 1) / t.Ht; tp.nTw = (a->Wi + t.Wt - 1) / t.Wt;
@@ -1183,7 +1215,8 @@ static int launch_scatter_bwd(const PoolKP& kp, const flk_pool_args* a, hipStrea
   return FLK_OK;
 }
 
-// stride-1 SAME pooling with an odd window and enough reuse to pay for the LDS staging
+// stride-1 pooling whose output grid equals the input grid (SAME; odd or even window) with at least 8 taps: enough reuse to pay for the
+// LDS staging
 static bool use_tiled(const flk_pool_args* a) {
   return a->st == 1 && a->sh == 1 && a->sw == 1 && a->kt * a->kh * a->kw >= 8 && a->To == a->Ti && a->Ho == a->Hi &&
          a->Wo == a->Wi && a->pt < a->kt && a->ph < a->kh && a->pw < a->kw;
@@ -1368,6 +1401,7 @@ extern "C" int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int
   const bool reg_able = reg_form && a->kt == 3 && a->kh == 3 && a->kw == 3;
   const flk_tile t = choose_scatter_tile(a, reg_able ? 512 : 0);
   PoolTP& tp = pg.t;
+  tp.fx_e = fixed_point_exponent(a);
   tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
   tp.nTt = (a->Ti + t.Tt - 1) / t.Tt; tp.nTh = (a->Hi + t.Ht - 1) / t.Ht; tp.nTw = (a->Wi + t.Wt - 1) / t.Wt;
   tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + 31) / 32;

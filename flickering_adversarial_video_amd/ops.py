@@ -156,25 +156,33 @@ def _pool_args(x, C_, k, s, pad, out, idx, in_coff=0, out_coff=0):
     return a
 
 
-def maxpool3d(x, k, s, C_=None, relu_input=False):
-    """tf.nn.max_pool3d SAME.  Returns (out, idx uint8, ctx) with ctx for maxpool3d_bwd."""
+def maxpool3d(x, k, s, C_=None, relu_input=False, *, in_coff=0, out=None, out_coff=0):
+    """tf.nn.max_pool3d SAME of channels [in_coff, in_coff + C_) of x.  Returns (out, idx uint8, ctx) with ctx for maxpool3d_bwd.
+    out: a [B,To,Ho,Wo,ld] buffer whose channels [out_coff, out_coff + C_) are filled (default: a fresh [.., C_] tensor)."""
     B, Ti, Hi, Wi, ld = x.shape
-    C_ = ld if C_ is None else C_
+    C_ = ld - in_coff if C_ is None else C_
     og, pad = zip(*(same_pad(n, kk, ss) for n, kk, ss in zip((Ti, Hi, Wi), k, s)))
-    out = torch.empty((B, *og, C_), dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((B, *og, C_ + out_coff), dtype=x.dtype, device=x.device)
+    assert tuple(out.shape[:4]) == (B, *og) and out.dtype == x.dtype and in_coff + C_ <= ld and out_coff + C_ <= out.shape[4]
     idx = torch.empty((B, *og, C_), dtype=torch.uint8, device=x.device)
-    a = _pool_args(x, C_, k, s, pad, out, idx)
+    a = _pool_args(x, C_, k, s, pad, out, idx, in_coff, out_coff)
     a.relu_input = int(relu_input)
     check(load().flk_maxpool3d_fwd(C.byref(a), dtype_code(x.dtype), stream_ptr()))
-    return out, idx, (x, C_, k, s, pad, out, idx)
+    return out, idx, (x, C_, k, s, pad, out, idx, in_coff, out_coff)
 
 
-def maxpool3d_bwd(ctx, gout, mask=None):
-    x, C_, k, s, pad, out, idx = ctx
-    gin = torch.empty((*x.shape[:4], C_), dtype=x.dtype, device=x.device)
-    a = _pool_args(x, C_, k, s, pad, out, idx)
-    check(load().flk_maxpool3d_bwd(C.byref(a), ptr(gout), gout.shape[4], 0, ptr(gin), C_, 0, ptr(mask),
-                                   0 if mask is None else mask.shape[4], 0, dtype_code(x.dtype), stream_ptr()))
+def maxpool3d_bwd(ctx, gout, mask=None, *, gout_coff=0, gin=None, gin_coff=0, mask_coff=0):
+    """MaxPool3DGrad: gout[..., gout_coff:gout_coff+C_] scattered by ctx's argmax bytes into gin[..., gin_coff:gin_coff+C_] (default: a
+    fresh [.., C_] tensor), masked by mask[..., mask_coff:mask_coff+C_] > 0 if a mask is given."""
+    x, C_, k, s, pad, out, idx, in_coff, out_coff = ctx
+    if gin is None:
+        gin = torch.empty((*x.shape[:4], C_ + gin_coff), dtype=x.dtype, device=x.device)
+    assert gin.shape[:4] == x.shape[:4] and gin.dtype == x.dtype and gin_coff + C_ <= gin.shape[4] and gout_coff + C_ <= gout.shape[4]
+    assert mask is None or mask_coff + C_ <= mask.shape[4]
+    a = _pool_args(x, C_, k, s, pad, out, idx, in_coff, out_coff)
+    check(load().flk_maxpool3d_bwd(C.byref(a), ptr(gout), gout.shape[4], gout_coff, ptr(gin), gin.shape[4], gin_coff, ptr(mask),
+                                   0 if mask is None else mask.shape[4], mask_coff, dtype_code(x.dtype), stream_ptr()))
     return gin
 
 
@@ -193,13 +201,16 @@ class PoolGemmWeights:
             self.handle = C.c_void_p()
 
 
-def maxpool3d_bwd_gemm(ctx, g, weights, g_coff=0):
-    """Branch_3 backward in one kernel (bf16): gin = MaxPool3DGrad(idx, g[..., g_coff:g_coff+K] @ Wt); ctx from maxpool3d"""
-    x, C_, k, s, pad, out, idx = ctx
+def maxpool3d_bwd_gemm(ctx, g, weights, g_coff=0, *, gin=None, gin_coff=0):
+    """Branch_3 backward in one kernel (bf16): gin[..., gin_coff:gin_coff+C_] = MaxPool3DGrad(idx, g[..., g_coff:g_coff+K] @ Wt); ctx from
+    maxpool3d"""
+    x, C_, k, s, pad, out, idx, in_coff, out_coff = ctx
     assert x.dtype == torch.bfloat16 and g.dtype == torch.bfloat16 and weights.C == C_
-    gin = torch.empty((*x.shape[:4], C_), dtype=x.dtype, device=x.device)
-    a = _pool_args(x, C_, k, s, pad, out, idx)
-    check(load().flk_maxpool3d_bwd_gemm(C.byref(a), ptr(g), g.shape[4], g_coff, weights.K, weights.handle, ptr(gin), C_, 0,
+    if gin is None:
+        gin = torch.empty((*x.shape[:4], C_ + gin_coff), dtype=x.dtype, device=x.device)
+    assert gin.shape[:4] == x.shape[:4] and gin.dtype == x.dtype and gin_coff + C_ <= gin.shape[4]
+    a = _pool_args(x, C_, k, s, pad, out, idx, in_coff, out_coff)
+    check(load().flk_maxpool3d_bwd_gemm(C.byref(a), ptr(g), g.shape[4], g_coff, weights.K, weights.handle, ptr(gin), gin.shape[4], gin_coff,
                                         dtype_code(x.dtype), stream_ptr()))
     return gin
 

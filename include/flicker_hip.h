@@ -143,10 +143,19 @@ int flk_conv3d_group_check(const flk_conv_args* const* a, const flk_conv_weights
 int flk_conv_layout_query(const flk_conv_args* a, int nf, int dtype, int force_da, int* wn_out, int* mode_out);
 
 /* tf.nn.max_pool3d SAME (i3d.py:174,189,212,252,398): padded cells never win; argmax = FIRST
- * maximum in (t,h,w) scan order, stored as a uint8 window index for the backward pass.
- * MaxPool3DGrad: gather form (bitwise reproducible) for strided windows; stride-1 odd windows (the Inception branch-3 pool)
- * use an LDS scatter with float atomics (<= kt*kh*kw fp32 additions per cell in arbitrary order; FLK_POOL_GATHER=1 selects
- * the reproducible gather form).  Optional relu-mask like flk_conv3d. */
+ * maximum in (t,h,w) scan order (strict >), stored as a uint8 window index (tap = (dt*kh + dh)*kw + dw) for the backward pass.
+ * Values are compared as numbers: -0.0 and +0.0 tie and the first of them wins; a window that holds only -inf records tap 0 and
+ * out = -inf.  One deviation: the bf16 kernels of the 3x3x3 / 1 window order values by an integer key in which +0.0 ranks above -0.0,
+ * so among tied zeros of both signs they record the first +0.0 (still an in-bounds cell whose value equals the window maximum).  in / out / gout / gin / mask are channel slices
+ * [coff, coff + C) of rows ld channels wide (all multiples of 8); channels outside a slice are never written.
+ * MaxPool3DGrad: the strided I3D windows (1x3x3 / 1x2x2, 3x3x3 / 2, 2x2x2 / 2) take an owner form in both dtypes (every cell written
+ * once, fixed order).  Every other geometry: fp32 takes a gather form (fixed summation order, bitwise reproducible); bf16 takes an
+ * LDS scatter that sums in 32-bit fixed point with integer atomics (order-independent, bitwise reproducible as well).  Its scale is
+ * 2^E / 2^floor(log2 max|gout|) per workgroup with E = min(24, 30 - ceil(log2 n)), n = ceil(kt/st) * ceil(kh/sh) * ceil(kw/sw) the
+ * number of windows that can cover one cell (E = 24 for n <= 64: every I3D pool), so n addends never leave an int32 for any
+ * accepted window (<= 255 taps); the sum of a cell is within n * 2^-(E+1) * max|gout| of exact before its one rounding to bf16.
+ * A gradient that a -inf window sends to a padded cell is dropped.  Optional relu-mask like flk_conv3d.  There is no environment
+ * switch between the forms. */
 typedef struct {
   const void* in; int in_ld, in_coff; int C;
   int B, Ti, Hi, Wi;
@@ -159,7 +168,7 @@ typedef struct {
                               mask tensor (pass mask = NULL): identical result, ~40 % less traffic */
 } flk_pool_args;
 int flk_maxpool3d_fwd(const flk_pool_args* a, int dtype, void* stream);
-/* gin[pos,c] = (add?add:0) + sum_{windows containing pos with argmax == pos} gout[window,c];
+/* gin[pos,c] = sum_{windows containing pos with argmax == pos} gout[window,c];
  * then masked by mask[pos,c] > 0 if mask != NULL.  a->in/out describe the FORWARD tensors'
  * geometry: gout has the `out` geometry (ld/coff given here), gin the `in` geometry. */
 int flk_maxpool3d_bwd(const flk_pool_args* a, const void* gout, int gout_ld, int gout_coff,
@@ -172,7 +181,8 @@ int flk_maxpool3d_bwd(const flk_pool_args* a, const void* gout, int gout_ld, int
  * instead of flk_conv3d (transposed 1x1x1) -> HBM -> flk_maxpool3d_bwd.  `a` describes the FORWARD pool (a->C = C channels, a->idx its
  * argmax bytes); g: [B,To,Ho,Wo,g_ld] gradient of the unit's pre-ReLU output (K = 32, 64, 96 or 128 channels at g_coff); wpack: from
  * flk_pool_gemm_weights_create(Wt [K][C] = unit weight transposed x batch-norm scale).  Products stay in fp32 (no bf16 rounding of the
- * intermediate), the scatter sums in 32-bit fixed point like flk_maxpool3d_bwd: bitwise reproducible. */
+ * intermediate), the scatter sums in 32-bit fixed point like flk_maxpool3d_bwd (same window-dependent exponent E, any window the pool
+ * accepts; FLK_POOL_GEMM_REG=0 selects the loop form where the register form would run): bitwise reproducible. */
 int flk_pool_gemm_weights_create(const float* wt_kc, int K, int C, void** out_dev);
 int flk_pool_gemm_weights_destroy(void* dev);
 int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int g_ld, int g_coff, int K, const void* wpack,
