@@ -186,16 +186,18 @@ __device__ static inline void block_argmax(float v, int i, float* sv, int* si, f
   __syncthreads();
 }
 
-__global__ __launch_bounds__(256) void softmax_adv_loss_kernel(const flk_loss_args a, const float* logits, const int64_t* labels,
-                                                               float* softmax, float* dlogits, float* per_clip) {
+// The loss of ONE row of logits z[0..C): a clip's (softmax_adv_loss_kernel: z = its row of the logits in global memory, G = 1) or a video's
+// (softmax_adv_loss_video_kernel: z = the video logits, held in LDS).  Row b of softmax / per_clip is written; VIDEO: d(loss)/dz * scale goes to
+// the G clip rows b*G .. b*G+G-1 of dlogits (z = scale * sum of those clips' logits), otherwise d(loss)/dz to row b.
+template <bool VIDEO>
+__device__ __forceinline__ void adv_loss_row(const flk_loss_args& a, const float* z, const int64_t y_raw, const int b, float* softmax,
+                                             float* dlogits, float* per_clip, const int G, const float scale) {
   __shared__ float sv[256];
   __shared__ int si[256];
   __shared__ float coef[8];
-  const int b = blockIdx.x, tid = threadIdx.x, C = a.C;
-  const float* z = logits + (size_t)b * C;
+  const int tid = threadIdx.x, C = a.C;
   // a label outside [0, C) must not index z[]: clamp it for the reads and poison this clip's outputs with NaN so that the
   // error is visible in the loss instead of being a silent out-of-bounds read (the host wrapper validates the range too)
-  const int64_t y_raw = labels[b];
   const bool y_bad = y_raw < 0 || y_raw >= (int64_t)C;
   const int y = y_bad ? 0 : (int)y_raw;
   constexpr int PER = 4;  // C <= 1024
@@ -279,6 +281,9 @@ __global__ __launch_bounds__(256) void softmax_adv_loss_kernel(const flk_loss_ar
       else { loss = -(zy - zmax - logf(1.f / inv)) * ms; gy = -ms / py; }
     }
     if (y_bad) { loss = NAN; alpha = NAN; gy = NAN; }
+    // NaN logits: the gradient below is NaN through py, but the improve-loss variants' "u > 0" is false for a NaN u and would report a loss
+    // of 0; the video head reports NaN (the clip head keeps the value it always returned)
+    if constexpr (VIDEO) { if (py != py) loss = NAN; }
     coef[0] = alpha; coef[1] = beta; coef[2] = gy * py; coef[3] = gP * Pm;
     per_clip[b * 4 + 0] = loss; per_clip[b * 4 + 1] = py; per_clip[b * 4 + 2] = Pm; per_clip[b * 4 + 3] = (float)amax;
   }
@@ -293,8 +298,39 @@ __global__ __launch_bounds__(256) void softmax_adv_loss_kernel(const flk_loss_ar
     if (j == mz) d += beta;
     if (j == mp) d += cP;
     if (softmax) softmax[(size_t)b * C + j] = pl[k];
-    dlogits[(size_t)b * C + j] = d;
+    if constexpr (VIDEO) {
+      const float ds = scale * d;
+      for (int g = 0; g < G; ++g) dlogits[((size_t)b * G + g) * C + j] = ds;
+    } else {
+      dlogits[(size_t)b * C + j] = d;
+    }
   }
+}
+
+__global__ __launch_bounds__(256) void softmax_adv_loss_kernel(const flk_loss_args a, const float* logits, const int64_t* labels,
+                                                               float* softmax, float* dlogits, float* per_clip) {
+  const int b = blockIdx.x;
+  adv_loss_row<false>(a, logits + (size_t)b * a.C, labels[b], b, softmax, dlogits, per_clip, 1, 1.f);
+}
+
+// The loss on a video's aggregated logits (the decision rule of the reference's evaluate(num_samples), model.py:1227-1317): one 256-thread
+// workgroup per video v forms z[j] = scale * (((l[vG][j] + l[vG+1][j]) + l[vG+2][j]) + ...) in fp32, strictly in clip order, keeps it in
+// LDS and runs the clip head's arithmetic on it; every clip of the video receives scale * d(loss_v)/dz.
+__global__ __launch_bounds__(256) void softmax_adv_loss_video_kernel(const flk_loss_args a, const int G, const float scale, const float* logits,
+                                                                     const int64_t* labels, float* softmax, float* video_logits,
+                                                                     float* dlogits, float* per_video) {
+  __shared__ float zs[1024];  // C <= 1024
+  const int v = blockIdx.x, C = a.C;
+  for (int j = threadIdx.x; j < C; j += 256) {
+    const float* l = logits + (size_t)v * G * C + j;
+    float acc = l[0];
+    for (int g = 1; g < G; ++g) acc = acc + l[(size_t)g * C];
+    const float zj = scale * acc;
+    zs[j] = zj;
+    if (video_logits) video_logits[(size_t)v * C + j] = zj;
+  }
+  __syncthreads();
+  adv_loss_row<true>(a, zs, labels[v], v, softmax, dlogits, per_video, G, scale);
 }
 
 extern "C" int flk_softmax_adv_loss(const flk_loss_args* a, const float* logits, const int64_t* labels, float* softmax,
@@ -306,6 +342,23 @@ extern "C" int flk_softmax_adv_loss(const flk_loss_args* a, const float* logits,
               "(model.py:223-225 references undefined names); refusing to guess");
   FLK_REQUIRE(a->margin > 0.f || !a->improve_loss, "flk_softmax_adv_loss: margin must be > 0");
   FLK_LAUNCH_KERNEL(softmax_adv_loss_kernel, dim3(a->B), dim3(256), 0, (hipStream_t)stream, *a, logits, labels, softmax, dlogits, per_clip);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_softmax_adv_loss_video(const flk_loss_args* a, int G, float scale, const float* logits, const int64_t* labels,
+                                          float* softmax, float* video_logits, float* dlogits, float* per_video, void* stream) {
+  FLK_REQUIRE(a && logits && labels && dlogits && per_video, "flk_softmax_adv_loss_video: null argument");
+  FLK_REQUIRE(G >= 1, "flk_softmax_adv_loss_video: G (clips per video) must be >= 1, got %d", G);
+  FLK_REQUIRE(a->B > 0 && a->B % G == 0, "flk_softmax_adv_loss_video: B = %d clips is not a multiple of G = %d", a->B, G);
+  FLK_REQUIRE(scale > 0.f, "flk_softmax_adv_loss_video: scale must be > 0, got %g", (double)scale);
+  FLK_REQUIRE(a->C > 1 && a->C <= 1024, "flk_softmax_adv_loss_video: need 1 < C <= 1024");
+  FLK_REQUIRE(!(a->torch_dialect && a->improve_loss && a->targeted),
+              "flk_softmax_adv_loss_video: the reference's targeted improve-loss is non-functional in the torch dialect "
+              "(model.py:223-225 references undefined names); refusing to guess");
+  FLK_REQUIRE(a->margin > 0.f || !a->improve_loss, "flk_softmax_adv_loss_video: margin must be > 0");
+  FLK_LAUNCH_KERNEL(softmax_adv_loss_video_kernel, dim3(a->B / G), dim3(256), 0, (hipStream_t)stream, *a, G, scale, logits, labels, softmax,
+                    video_logits, dlogits, per_video);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

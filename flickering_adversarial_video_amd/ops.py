@@ -663,6 +663,48 @@ def softmax_adv_loss(logits, labels, *, dialect="tf", improve_loss=True, use_log
     return sm, dl, pc
 
 
+VIDEO_REDUCES = ("mean", "sum")
+
+
+def video_scale(clips_per_video, reduce):
+    """the factor on a video's summed clip logits: "sum" = 1 (the reference's evaluate), "mean" = 1/G (same argmax; the margin and CE
+    hyper-parameters stay on the scale of one clip's logits)"""
+    if reduce not in VIDEO_REDUCES:
+        raise ValueError(f"reduce must be one of {VIDEO_REDUCES}, got {reduce!r}")
+    if int(clips_per_video) < 1:
+        raise ValueError(f"clips_per_video must be >= 1, got {clips_per_video!r}")
+    return 1.0 if reduce == "sum" else 1.0 / int(clips_per_video)
+
+
+def softmax_adv_loss_video(logits, labels, clips_per_video, *, reduce="mean", dialect="tf", improve_loss=True, use_logits=False,
+                           targeted=False, margin=0.05, mean_scale=1.0, out=None):
+    """the loss head on a video's aggregated logits (flk_softmax_adv_loss_video): ``logits`` [B = V*G, C] video-major and clip-minor,
+    ``labels`` [V] -> (softmax [V,C], dlogits [B,C], per_video [V,4], video_logits [V,C]).  out: optional buffers, in that order"""
+    B, Cn = logits.shape
+    G = int(clips_per_video)
+    scale = video_scale(G, reduce)
+    if B % G:
+        raise ValueError(f"{B} clips are not a multiple of clips_per_video = {G}")
+    V = B // G
+    check_labels(labels, V, Cn)
+    a = LossArgs()
+    a.B, a.C = B, Cn
+    a.torch_dialect, a.improve_loss, a.use_logits, a.targeted = int(dialect == "torch"), int(improve_loss), int(use_logits), int(targeted)
+    a.margin, a.mean_scale = margin, mean_scale
+    if out is None:
+        sm = torch.empty((V, Cn), dtype=torch.float32, device=logits.device)
+        dl = torch.empty_like(logits)
+        pv = torch.empty((V, 4), dtype=torch.float32, device=logits.device)
+        vl = torch.empty((V, Cn), dtype=torch.float32, device=logits.device)
+    else:
+        sm, dl, pv, vl = out
+        assert tuple(sm.shape) == (V, Cn) and tuple(dl.shape) == (B, Cn) and tuple(pv.shape) == (V, 4) and tuple(vl.shape) == (V, Cn)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in (sm, dl, pv, vl))
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.is_cuda
+    check(load().flk_softmax_adv_loss_video(C.byref(a), G, scale, ptr(logits), ptr(labels), ptr(sm), ptr(vl), ptr(dl), ptr(pv), stream_ptr()))
+    return sm, dl, pv, vl
+
+
 class Net:
     """flk_net: whole-network forward + backward-to-input plan with resident packed weights."""
 

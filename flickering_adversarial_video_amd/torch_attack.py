@@ -191,6 +191,16 @@ class Losses:
         self.label_prob = pc[:, 1]
         return sm, dl, pc
 
+    def adv_video(self, labels, model_logits, global_videos, clips_per_video, reduce="mean", out=None):
+        """``adv`` on the videos' aggregated logits (the decision rule of evaluate(num_samples), model.py:1227-1317): ``model_logits``
+        [V*G, classes] video-major and clip-minor, ``labels`` [V] -> (softmax [V,C], dlogits [V*G,C], per_video [V,4], video_logits [V,C])"""
+        lab = labels if not self.targeted else torch.full_like(labels, self.target_class)
+        sm, dl, pv, vl = ops.softmax_adv_loss_video(model_logits, lab, clips_per_video, reduce=reduce, dialect="torch",
+                                                    improve_loss=self.improve_loss, use_logits=self.logits, targeted=self.targeted,
+                                                    margin=self.margin, mean_scale=1.0 / global_videos, out=out)
+        self.label_prob = pv[:, 1]
+        return sm, dl, pv, vl
+
     def flickering_regularization_loss(self, perturbation):
         """model.py:198-209 on the CLAMPED perturbation [3,T,1,1] (model.py:1078): value only -- the gradient and the same
         value during an update come from flk_perturb_reg_adam.  Used for evaluation passes (no Adam step)."""
@@ -256,8 +266,18 @@ class FlickerVideoResNet:
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
-                 im_scale=128, resize_rule="sizes", augment=None, sampling=None):
+                 im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean"):
         from .i3d_engine import check_optimizer
+        # clips_per_video = G > 1: the batch holds V = B / G videos of G clips each (video-major, sample-minor, as ``prepare_videos`` cuts
+        # them) and the adversarial loss is taken on every video's aggregated logits -- video_reduce "sum" (what ``evaluate_videos``
+        # decides on) or "mean" (the sum / G: same argmax, margin and CE on the scale of one clip's logits) -- with one label per video
+        G = int(clips_per_video)
+        self.video_scale = ops.video_scale(G, video_reduce)
+        if int(batch_size) % G:
+            raise ValueError(f"batch_size {batch_size} is not a multiple of clips_per_video {G}")
+        if per_clip and G > 1:
+            raise ValueError("per_clip (independent perturbations per clip) and clips_per_video > 1 (one loss per video) contradict each other")
+        self.clips_per_video, self.video_reduce, self.V = G, video_reduce, int(batch_size) // G
         # raw-size uint8 frames are prepared on the device (``prepare``): ResizeVideo(im_scale) -> CenterCropVideo(image_size), dataset.py:84-123;
         # resize_rule: "sizes" = the arithmetic of torch 1.4.0 (the reference's pin), "scale_factor" = current torch (videoresnet_spec.prepare_geometry)
         if resize_rule not in RESIZE_RULES:
@@ -506,6 +526,30 @@ class FlickerVideoResNet:
         self._forward(x, adversarial)
         return self._logits
 
+    def _check_video_labels(self, labels):
+        """clips_per_video > 1: one label per VIDEO"""
+        if not torch.is_tensor(labels) or labels.dim() != 1 or int(labels.shape[0]) != self.V:
+            got = tuple(labels.shape) if torch.is_tensor(labels) else type(labels).__name__
+            raise ValueError(f"clips_per_video = {self.clips_per_video}: labels must hold one class per video, shape ({self.V},), got {got}")
+
+    def video_logits(self, clip_logits):
+        """the videos' aggregated logits [V,classes] from clip logits [V*G,classes] (video-major, sample-minor) with torch: fp32 sums clip
+        after clip, then the scale of ``video_reduce`` -- bitwise what the loss head forms and, for "sum", what ``evaluate_videos`` sums"""
+        G = self.clips_per_video
+        z = clip_logits.view(-1, G, clip_logits.shape[-1])
+        acc = z[:, 0].clone()
+        for g in range(1, G):
+            acc = acc + z[:, g]
+        return acc * self.video_scale
+
+    def _whole_video(self, inputs):
+        """fit_single_video_attack, clips_per_video > 1: ``inputs`` as ONE whole uint8 video [N,H,W,3] (or a one-element list of it), else None"""
+        if isinstance(inputs, (list, tuple)) and len(inputs) == 1:
+            inputs = inputs[0]
+        if torch.is_tensor(inputs) and inputs.dim() == 4 and inputs.dtype == torch.uint8:
+            return inputs
+        return None
+
     def step(self, x, labels, criterion, lr=1e-3, update=True):
         """one iteration of fit_single_video_attack (model.py:1073-1101): forward, Losses, backward, torch-Adam step.
         The kernels write into one of ``RESULT_SLOTS`` result slots (valid for the next RESULT_SLOTS - 1 iterations);
@@ -517,11 +561,18 @@ class FlickerVideoResNet:
             return self._step_dense(x, labels, criterion, lr, update)
         if self.per_clip:
             return self._step_per_clip(x, labels, criterion, lr, update)
+        G, V = self.clips_per_video, self.V                     # G = 1: V = B, every clip its own "video"
+        if G > 1:
+            self._check_video_labels(labels)
         if not hasattr(self, "_slots"):
             dev = self._logits.device
             self._slots = [dict(payload=torch.zeros(parallel.payload_size(self.T), dtype=torch.float32, device=dev),
-                                sm=torch.empty_like(self._logits), pc=torch.empty((self.B, 4), dtype=torch.float32, device=dev),
+                                sm=torch.empty((V, self.num_classes), dtype=torch.float32, device=dev),
+                                pc=torch.empty((V, 4), dtype=torch.float32, device=dev),
                                 scalars=torch.zeros(8, dtype=torch.float32, device=dev)) for _ in range(RESULT_SLOTS)]
+            if G > 1:
+                for s in self._slots:
+                    s["vl"] = torch.empty((V, self.num_classes), dtype=torch.float32, device=dev)
             self._dl = torch.empty_like(self._logits)
             self._it = 0
         slot = self._slots[self._it % RESULT_SLOTS]
@@ -529,14 +580,19 @@ class FlickerVideoResNet:
         red, sm, pc = slot["payload"], slot["sm"], slot["pc"]
         self._red = red
         a = self._forward(x, True)
-        gbatch = self.B * self.world
-        criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
+        gbatch = V * self.world
+        if G > 1:
+            criterion.adv_video(labels, self._logits, gbatch, G, self.video_reduce, out=(sm, self._dl, pc, slot["vl"]))
+        else:
+            criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
         self.net.backward(self._dl, self._gx)
         n = 3 * self.T
         ops.perturb_grad_reduce(a, self._gx, red[:n].view(self.T, 3), self._scratch)
         ops.pack_batch_sums(pc, 1.0 / gbatch, red[n:])
         parallel.allreduce_sum_(red, self.pg)
         res = StepResult(adv_loss=red[n], softmax=sm, label_prob=pc[:, 1], _argmax_f=pc[:, 3], _labels=labels, _targeted=bool(criterion.targeted))
+        if G > 1:
+            res["video_logits"] = slot["vl"]
         if update:
             self.adam_t += 1
             b1 = criterion.beta_1
@@ -596,9 +652,15 @@ class FlickerVideoResNet:
         """the dense "L12" attack (model.py:211-214,380-384): loss = adv + lambda * L12(clamped delta); the data-parallel payload
         is the dense gradient [T,H,W,3] (2.4 MB at 16 x 112 x 112)"""
         from .i3d_engine import StepResult
+        G, vl = self.clips_per_video, None
+        if G > 1:
+            self._check_video_labels(labels)
         a = self._forward(x, True)
-        gbatch = self.B * self.world
-        sm, dl, pc = criterion.adv(labels, self._logits, gbatch)
+        gbatch = self.V * self.world
+        if G > 1:
+            sm, dl, pc, vl = criterion.adv_video(labels, self._logits, gbatch, G, self.video_reduce)
+        else:
+            sm, dl, pc = criterion.adv(labels, self._logits, gbatch)
         self._dl = dl
         self.net.backward(dl, self._gx)
         if not hasattr(self, "_gdense"):
@@ -609,6 +671,8 @@ class FlickerVideoResNet:
         parallel.allreduce_sum_(tail, self.pg)
         res = StepResult(adv_loss=tail[0].clone(), softmax=sm, label_prob=pc[:, 1], _argmax_f=pc[:, 3], _labels=labels,
                          _targeted=bool(criterion.targeted), _reg_weight=criterion.lambda_)
+        if vl is not None:
+            res["video_logits"] = vl
         if update:
             self.adam_t += 1
             if self.pgd:
@@ -631,9 +695,25 @@ class FlickerVideoResNet:
         ``while step < n_iter or not is_adversarial`` (model.py:1056); whenever ``step > restart_after`` the clamp norm
         grows by ``norm_growth`` and the step counter restarts, giving up after ``max_restarts`` (model.py:1061-1066:
         3000 / 1.3 / 4).  The result dict has the reference's keys (model.py:1193-1203); per-iteration values are host
-        floats (the reference syncs every iteration as well: ``loss.item()``).  Raw-size uint8 frames are prepared on the device first."""
+        floats (the reference syncs every iteration as well: ``loss.item()``).  Raw-size uint8 frames are prepared on the device first.
+        ``clips_per_video = G > 1``: ``inputs`` are B clips (V = B / G videos, video-major and sample-minor) or, on an engine with B == G, one
+        whole uint8 video ``[N,H,W,3]`` (or a one-element list of it) whose G test-split clips are attacked; ``target`` holds one class per
+        video and ``prob_clean_input``, ``is_adversarial``, ``max_prob`` and ``correct_cls_prob`` are the video's (aggregated logits)."""
+        G = self.clips_per_video
+        video = self._whole_video(inputs) if G > 1 else None
+        if video is not None:
+            # one whole video: its G test-split clips (uniform offsets, no shift, no jitter -- the clips evaluate_videos(num_samples=G)
+            # scores) are cut once, into a buffer of their own, and kept for the whole attack
+            if self.B != G:
+                raise ValueError(f"a whole video needs an engine with batch_size == clips_per_video, got {self.B} and {G}")
+            inputs = self.prepare_videos([video], train=False, num_samples=G)
+        elif isinstance(inputs, (list, tuple)):
+            raise ValueError("fit_single_video_attack: inputs must be clips [B,T,H,W,3] or (clips_per_video > 1) one whole uint8 video [N,H,W,3]")
         inputs = self._prepared(inputs)
         outputs_no_adv = self.logits(inputs, False).clone()
+        if G > 1:                                            # the decision attacked is the video's: clean video logits [V,classes]
+            self._check_video_labels(target)
+            outputs_no_adv = self.video_logits(outputs_no_adv)
         if not bool((outputs_no_adv.argmax(1) == target).all()):
             return None
         tot, adv_l, reg_l, thick_l, rough_l, maxp_l, corr_l, isadv_l, pert_l = [], [], [], [], [], [], [], [], []
@@ -669,8 +749,11 @@ class FlickerVideoResNet:
         evaluates the same loss without an update.  Result keys as model.py:780-786.  A loader may yield ``inputs`` as a LIST of whole
         uint8 videos ``[N_k,H_k,W_k,3]`` (one per clip of the batch): the train phase then cuts a clip from each with the training split's
         sampling settings (and the training transform when the engine has ``augment``), the valid phase one clip with no shift and no
-        jitter (``prepare_videos``)."""
+        jitter (``prepare_videos``).  With ``clips_per_video = G > 1`` a batch is V = B / G whole videos (G clips are cut from each: the train
+        phase with the training split's settings, the valid phase at the test split's uniform offsets) or B clips already video-major and
+        sample-minor, with V labels; the fooling metric compares the adversarial with the clean VIDEO logits and ``n`` counts videos."""
         import time
+        G = self.clips_per_video
         result = {}
         for phase in ("train", "valid"):
             t0 = time.time()
@@ -679,9 +762,9 @@ class FlickerVideoResNet:
             for inputs, target, *_ in data_loaders[phase]:
                 whole = isinstance(inputs, (list, tuple))           # whole videos: sampled and prepared in one launch
                 if whole:
-                    if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < len(inputs):
-                        self._prep_buf = torch.empty((max(len(inputs), self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
-                    inputs = self.prepare_videos(inputs, train=(phase == "train"), out=self._prep_buf)
+                    if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < len(inputs) * G:
+                        self._prep_buf = torch.empty((max(len(inputs) * G, self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
+                    inputs = self.prepare_videos(inputs, train=(phase == "train"), num_samples=G, out=self._prep_buf)
                 xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
                 augmenting = phase == "train" and self.augment is not None and not whole
                 if augmenting and not self._is_raw(inputs):
@@ -691,12 +774,14 @@ class FlickerVideoResNet:
                 clean = self.logits(inputs, False).clone()
                 r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
                 adv_logits = self._logits
+                if G > 1:
+                    clean, adv_logits = self.video_logits(clean), r["video_logits"]
                 m = metric.accuracy_for_eval(adv_logits, target, topk=(1,), clean_pred=clean)
                 if isinstance(m, tuple):
                     miss += float(m[0]); valid += float(m[1])
                 else:                                           # targeted: a percentage (model.py:300-302)
                     miss += float(m) / 100.0 * target.numel(); valid += target.numel()
-                bs = inputs.shape[0]
+                bs = inputs.shape[0] // G
                 loss_sum += float(r["loss"]) * bs
                 n += bs
             p = self.pert_model.get_perturbation()[0].cpu().numpy()
@@ -859,7 +944,8 @@ class FlickerVideoResNet:
         rng = np.random.default_rng(0)
         xdt = None
         for inputs, target, name in videos:
-            xdt = self._same_dtype(xdt, inputs, "fit_many_videos")
+            # (clips_per_video > 1: a whole uint8 video, possibly as a one-element list, goes through to fit_single_video_attack)
+            xdt = self._same_dtype(xdt, inputs[0] if isinstance(inputs, (list, tuple)) and len(inputs) else inputs, "fit_many_videos")
             cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
             dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy") if model_dir else None
             if dest and os.path.exists(dest):
@@ -893,7 +979,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None, optimizer="adam", sampling=None):
+                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean"):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -906,6 +992,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
             batch_size = getattr(dataset, "batch_size", 1)
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
-                         process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling)
+                         process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
+                         clips_per_video=clips_per_video, video_reduce=video_reduce)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -437,6 +437,19 @@ typedef struct {
 } flk_loss_args;
 int flk_softmax_adv_loss(const flk_loss_args* a, const float* logits, const int64_t* labels,
                          float* softmax, float* dlogits, float* per_clip, void* stream);
+/* The same loss on a VIDEO's aggregated logits -- the quantity the reference's evaluate(num_samples) decides on (model.py:1227-1317: the
+ * argmax of the summed logits of a video's clips).  logits holds a->B = V*G clip rows, video-major and clip-minor; one workgroup per
+ * video forms, in fp32 and strictly in clip order,
+ *   z[v][j] = scale * (((l[vG+0][j] + l[vG+1][j]) + l[vG+2][j]) + ...)          (scale = 1: the sum; 1/G: the mean, same argmax)
+ * and applies flk_softmax_adv_loss's arithmetic (same code) to z[v] with labels[v]; a->mean_scale is 1/(global number of VIDEOS).
+ * Outputs: softmax [V,C] of z and video_logits [V,C] = z (either may be NULL), per_video [V,4] = {loss_v, label_prob, max_non_label_prob,
+ * argmax} of z, and dlogits [V*G,C] with dlogits[vG+g][j] = scale * d(loss_v)/dz[v][j] for every clip g of the video.
+ * With G = 1 and scale = 1 every output is bitwise flk_softmax_adv_loss's (finite logits).  NaN logits and labels outside [0,C) end in a
+ * NaN loss and NaN gradient rows for that video alone (flk_softmax_adv_loss reports a loss of 0 beside the NaN gradient for NaN logits
+ * under the improve-loss variants; this entry reports NaN in every variant).  FLK_EINVAL: G < 1, a->B % G != 0, scale <= 0, and everything
+ * flk_softmax_adv_loss refuses. */
+int flk_softmax_adv_loss_video(const flk_loss_args* a, int G, float scale, const float* logits, const int64_t* labels,
+                               float* softmax, float* video_logits, float* dlogits, float* per_video, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Whole-network plan: the victim classifier forward + backward-to-input as one call

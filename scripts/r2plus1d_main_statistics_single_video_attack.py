@@ -14,7 +14,10 @@ WHOLE-VIDEO files: `labels` (int64 [V]) and `video_00000`, `video_00001`, ... (e
 videos stay resident as uint8 and the clip of `--sample-length` frames attacked in each is cut as the reference's VideoDataset cuts
 it (dataset.py:500-586: `--sample-step`, `--temporal-jitter`, `--temporal-jitter-step`, `--random-shift`, generator
 `numpy.random.RandomState(--sample-seed)`) and prepared in the same kernel launch; the defaults are the reference script's settings
-(one clip at the uniform offset, step 1, no jitter, no shift)."""
+(one clip at the uniform offset, step 1, no jitter, no shift).
+`--clips-per-video G` (whole-video files, `--batch 1`) attacks the video-level decision of the reference's evaluate(num_samples=G): the G
+clips at the evaluation's uniform offsets are cut from each video once and the adversarial loss is taken on their aggregated logits
+(`--video-reduce sum`, or `mean` = sum / G: same argmax); a video counts as adversarial when the argmax of those logits leaves its label."""
 import argparse
 import os
 import sys
@@ -51,15 +54,22 @@ def run_whole_videos(a):
     classes = [l.strip() for l in open(a.label_map)] if a.label_map else None
     arch, _, ncls = vs.resolve_model(a.base_model, T)
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
-    learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=T, image_size=S, dtype=a.dtype,
+    G = a.clips_per_video
+    if G > 1 and a.batch > 1:
+        raise ValueError("--clips-per-video > 1 attacks one video (its G clips) at a time: it does not combine with --batch > 1")
+    learner = FlickerVideoResNet(a.base_model, W, batch_size=G if G > 1 else a.batch, sample_length=T, image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
-                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
+                                 clips_per_video=G, video_reduce=a.video_reduce)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
     xd, yd = [torch.from_numpy(v).cuda() for v in videos], torch.from_numpy(labels).cuda()
     # train=True: fit_many_videos iterates the dataset's TRAINING loader (model.py:832); with the default flags the two splits sample alike
-    clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
+    if G > 1:        # whole videos go through: fit_single_video_attack cuts each one's G evaluation clips
+        clips = ((xd[i], yd[i:i + 1], names[i]) for i in range(len(videos)))
+    else:
+        clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
     return learner.fit_many_videos(clips, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
                                    reset_optimizer_per_video=a.reset_optimizer_per_video)
 
@@ -110,7 +120,16 @@ def main():
     ap.add_argument("--temporal-jitter-step", type=int, default=2)
     ap.add_argument("--random-shift", action="store_true", help="whole-video files, training split: clips start at random offsets, not uniform ones")
     ap.add_argument("--sample-seed", type=int, default=0, help="whole-video files: the frame sampler is numpy.random.RandomState(seed + rank)")
+    ap.add_argument("--clips-per-video", type=int, default=1, help="whole-video files: attack the decision on the aggregated logits of the G "
+                    "evaluation clips of each video (the reference's evaluate(num_samples=G)); 1 = one clip, per-clip loss")
+    ap.add_argument("--video-reduce", default="mean", choices=["mean", "sum"], help="--clips-per-video > 1: the loss takes the mean (default) or "
+                    "the sum of a video's clip logits")
     a = ap.parse_args()
+    if a.clips_per_video < 1:
+        raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
+    if a.clips_per_video > 1 and not vs.is_video_file(a.videos_npz):
+        raise ValueError("--clips-per-video > 1 needs a whole-video .npz file (labels and video_00000, video_00001, ...): the clips of a "
+                         "video are cut from it")
     if vs.is_video_file(a.videos_npz):
         return report(run_whole_videos(a))
     z = np.load(a.videos_npz, allow_pickle=True)

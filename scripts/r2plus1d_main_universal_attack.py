@@ -34,7 +34,12 @@ the same kernel launch; the validation split takes one clip per video with no sh
 reference script's settings (step 1, no jitter, no shift: r2plus1d_main_universal_attack.py:155-163).  `--eval-num-samples N` scores
 whole validation videos after training as the reference's `evaluate(num_samples=N)` does (the argmax of the summed logits of N clips),
 clean and under the trained perturbation, prints the video-level accuracy and fooling ratio and stores them in `video_eval.npz`
-beside the checkpoints.  Both files of a run are of the same kind; files with a `clips` array behave exactly as before."""
+beside the checkpoints.  Both files of a run are of the same kind; files with a `clips` array behave exactly as before.
+
+`--clips-per-video G` (whole-video files only) attacks that video-level decision: a batch of `--batch-size` clips holds `--batch-size / G`
+videos, G clips are cut from each (training split: the sampling flags above; validation: the uniform offsets of the evaluation) and the
+adversarial loss is taken on each video's aggregated logits -- `--video-reduce sum` (the evaluation's own sum) or `mean` (the sum / G:
+same argmax, margin on the scale of one clip's logits).  Loss averages and fooling ratios then count videos."""
 import argparse
 import glob
 import os
@@ -149,7 +154,9 @@ def run_whole_videos(a, world, rank, local_rank, augment):
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
-                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
+                                 clips_per_video=a.clips_per_video, video_reduce=a.video_reduce)
+    nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     start_epoch = 1
@@ -161,7 +168,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
         start_epoch = int(ckpts[-1].split("_")[-1].split(".")[0]) + 1
         print(f"Success! to continue from last epoch. init with {start_epoch}")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
-    resident = {"train": ResidentVideos(vtr, ytr, a.batch_size, rank, world), "valid": ResidentVideos(vva, yva, a.batch_size)}
+    resident = {"train": ResidentVideos(vtr, ytr, nvid, rank, world), "valid": ResidentVideos(vva, yva, nvid)}
     results = learner.fit(resident, crit, Adversarial_metrics(targeted=TARGETED_ATTACK), lr=a.lr, epochs=a.epochs, model_dir=dest if rank == 0 else None,
                           model_name=learner.model_name, save_model=rank == 0, start_epoch=start_epoch)
     if rank == 0:
@@ -235,9 +242,18 @@ def main():
     ap.add_argument("--sample-seed", type=int, default=0, help="whole-video files: the frame sampler is numpy.random.RandomState(seed + rank)")
     ap.add_argument("--eval-num-samples", type=int, default=0, help="whole-video files: after training, score every validation video by N clips "
                     "(the reference's evaluate(num_samples=N)) clean and perturbed; 0 = skip")
+    ap.add_argument("--clips-per-video", type=int, default=1, help="whole-video files: G clips per video in every batch and the adversarial loss "
+                    "on each video's aggregated logits (what --eval-num-samples G decides on); --batch-size must be a multiple of G; 1 = per-clip loss")
+    ap.add_argument("--video-reduce", default="mean", choices=["mean", "sum"], help="--clips-per-video > 1: the loss takes the mean (default) or "
+                    "the sum of a video's clip logits")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
     a = ap.parse_args()
+    if a.clips_per_video < 1:
+        raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
+    if a.clips_per_video > 1 and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
+        raise ValueError("--clips-per-video > 1 needs whole-video .npz files (labels and video_00000, video_00001, ...): the clips of "
+                         "a video are cut from it; files with a `clips` array do not say which clips share a video")
     if a.gpus and a.gpus > 1 and "WORLD_SIZE" not in os.environ:      # before anything touches the GPU
         sys.exit(parallel.launch_ranks(a.gpus, __file__, sys.argv[1:]))
     world, rank, local_rank = parallel.ranks_from_env(a.gpus)

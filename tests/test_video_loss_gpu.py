@@ -1,0 +1,372 @@
+"""The adversarial loss on a video's aggregated clip logits (flk_softmax_adv_loss_video) and its way up: ops.softmax_adv_loss_video,
+Losses.adv_video, FlickerVideoResNet(clips_per_video=G) and its drivers.
+
+The head is checked against the unmodified functions of oracle/attack_math.py applied to ``zv = scale * z.view(V,G,C).sum(1)`` (autograd back
+to the clip logits) at the tolerances of tests/test_attack_gpu.py::test_loss_head_vs_oracle, and bitwise against the existing clip head
+run on video logits formed with torch; the engine against a gradient / trajectory built by hand from the existing pieces."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import attack_math as am
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# the loss-mode list of tests/test_attack_gpu.py::test_loss_head_vs_oracle: (dialect, improve_loss, use_logits, targeted)
+LOSS_MODES = [("tf", True, False, False), ("tf", True, True, False), ("tf", True, False, True), ("tf", True, True, True),
+              ("tf", False, False, False), ("tf", False, False, True),
+              ("torch", True, False, False), ("torch", True, True, False), ("torch", False, False, False),
+              ("torch", False, False, True)]
+MODE_IDS = ["-".join([d, "improve" if i else "ce", "logits" if u else "prob", "targeted" if t else "untargeted"]) for d, i, u, t in LOSS_MODES]
+CLASSES = (5, 257, 400, 1024)              # 257 crosses the 256-thread stride, 1024 is the limit
+GROUPS = ((1, 1), (3, 3), (2, 10))         # (videos, clips per video)
+TARGET = 3                                 # the torch dialect's target class (< every C used)
+T, H = 8, 112
+
+
+def need_gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+
+
+@pytest.fixture(scope="module")
+def ops():
+    need_gpu()
+    from flickering_adversarial_video_amd import ops as o
+    return o
+
+
+def noise(shape, seed):
+    return torch.from_numpy(np.random.default_rng(seed).integers(0, 256, shape, dtype=np.uint8))
+
+
+def scale_of(G, reduce):
+    return 1.0 if reduce == "sum" else 1.0 / G
+
+
+def seq_sum(z, G, scale):
+    """video logits with torch: fp32 adds clip after clip, then the scale"""
+    zz = z.view(-1, G, z.shape[-1])
+    acc = zz[:, 0].clone()
+    for g in range(1, G):
+        acc = acc + zz[:, g]
+    return acc * scale
+
+
+def make_case(V, G, Cn, scale, seed, targeted_torch=False):
+    """clip logits whose VIDEO logits have the spread of test_loss_head_vs_oracle's inputs (standard normal * 2): the tolerances taken
+    over from that test were set for logits of that spread -- ten summed clips of spread 2 each would give softmaxes so peaked that
+    1 - p_label cancels to nothing in fp32, in the oracle as much as in the kernel.  Video 0 is labelled with its argmax (margin branch
+    u > m), video 1 with its runner-up, the rest at random."""
+    rng = np.random.default_rng(seed)
+    z = torch.from_numpy((rng.standard_normal((V * G, Cn)) * 2.0 / (scale * np.sqrt(G))).astype(np.float32))
+    zv = scale * z.view(V, G, Cn).sum(1)
+    labels = torch.from_numpy(rng.integers(0, Cn, V))
+    labels[0] = int(zv[0].argmax())
+    if V > 1:
+        labels[1] = int(zv[1].argsort()[-2])
+    if targeted_torch:
+        labels[:] = TARGET
+    return z, labels
+
+
+def oracle(z, labels, V, G, scale, dialect, improve, use_logits, targeted):
+    zc = z.clone().requires_grad_(True)
+    zv = scale * zc.view(V, G, -1).sum(1)
+    if dialect == "tf":
+        loss = (am.tf_improve_adversarial_loss(zv, labels, 0.05, targeted, use_logits) if improve else am.tf_ce_adversarial_loss(zv, labels, targeted))[0]
+    else:
+        p = torch.softmax(zv, 1)
+        loss = am.torch_improve_loss(zv, p, labels, 0.05, use_logits) if improve else am.torch_ce_loss(p, labels, targeted, TARGET)
+    (g,) = torch.autograd.grad(loss, zc)
+    return loss.item(), g, zv.detach()
+
+
+def check_against_oracle(out, z, labels, V, G, scale, mode):
+    sm, dl, pv, vl = out
+    loss, gref, zv = oracle(z, labels, V, G, scale, *mode)
+    print(f"mode {mode} V {V} G {G} C {z.shape[1]} scale {scale:.4f}: loss {pv[:, 0].sum().item():.6g} / oracle {loss:.6g}, "
+          f"max |dlogits - oracle| {float((dl.cpu() - gref).abs().max()):.3g}")
+    torch.testing.assert_close(vl.cpu(), zv, rtol=1e-6, atol=1e-6)
+    torch.testing.assert_close(sm.cpu(), torch.softmax(zv, 1), rtol=1e-5, atol=1e-8)
+    assert pv[:, 0].sum().item() == pytest.approx(loss, rel=1e-4, abs=1e-7)
+    torch.testing.assert_close(dl.cpu(), gref, rtol=2e-4, atol=1e-7)
+    np.testing.assert_array_equal(pv[:, 3].cpu().numpy().astype(int), zv.argmax(1).numpy())
+    np.testing.assert_allclose(pv[:, 1].cpu().numpy(), torch.softmax(zv, 1).gather(1, labels.view(-1, 1))[:, 0].numpy(), rtol=1e-5)
+
+
+@pytest.mark.parametrize("mode", LOSS_MODES, ids=MODE_IDS)
+def test_video_head_vs_oracle(ops, mode):
+    dialect, improve, use_logits, targeted = mode
+    for Cn in CLASSES:
+        for V, G in GROUPS:
+            for reduce in ("sum", "mean"):
+                scale = scale_of(G, reduce)
+                z, labels = make_case(V, G, Cn, scale, seed=Cn + 7 * G, targeted_torch=targeted and dialect == "torch")
+                out = ops.softmax_adv_loss_video(z.cuda(), labels.cuda(), G, reduce=reduce, dialect=dialect, improve_loss=improve,
+                                                 use_logits=use_logits, targeted=targeted, margin=0.05, mean_scale=1.0 / V)
+                assert tuple(out[0].shape) == (V, Cn) and tuple(out[1].shape) == (V * G, Cn) and tuple(out[2].shape) == (V, 4)
+                check_against_oracle(out, z, labels, V, G, scale, mode)
+
+
+@pytest.mark.parametrize("mode", LOSS_MODES, ids=MODE_IDS)
+def test_reduces_to_the_clip_head_bitwise(ops, mode):
+    dialect, improve, use_logits, targeted = mode
+    kw = dict(dialect=dialect, improve_loss=improve, use_logits=use_logits, targeted=targeted, margin=0.05)
+    # G = 1, scale = 1: the existing head, bit for bit (both reduces: 1/1 = 1)
+    for Cn in CLASSES:
+        z, labels = make_case(4, 1, Cn, 1.0, seed=Cn, targeted_torch=targeted and dialect == "torch")
+        z, labels = z.cuda(), labels.cuda()
+        sm0, dl0, pc0 = ops.softmax_adv_loss(z, labels, mean_scale=0.25, **kw)
+        for reduce in ("sum", "mean"):
+            sm, dl, pv, vl = ops.softmax_adv_loss_video(z, labels, 1, reduce=reduce, mean_scale=0.25, **kw)
+            assert torch.equal(vl, z) and torch.equal(sm, sm0) and torch.equal(dl, dl0) and torch.equal(pv, pc0), (Cn, reduce)
+    # G > 1: the existing head on video logits formed with torch (sequential fp32 adds, then * scale); sum, and mean at power-of-two G,
+    # where the scale is exact
+    for reduce, G in (("sum", 2), ("sum", 3), ("mean", 2), ("mean", 4)):
+        for Cn in (257, 400):
+            V, scale = 3, scale_of(G, reduce)
+            z, labels = make_case(V, G, Cn, scale, seed=Cn + G, targeted_torch=targeted and dialect == "torch")
+            z, labels = z.cuda(), labels.cuda()
+            zv = seq_sum(z, G, scale)
+            sm0, dl0, pc0 = ops.softmax_adv_loss(zv, labels, mean_scale=1.0 / V, **kw)
+            sm, dl, pv, vl = ops.softmax_adv_loss_video(z, labels, G, reduce=reduce, mean_scale=1.0 / V, **kw)
+            assert torch.equal(vl, zv), (reduce, G, Cn)
+            assert torch.equal(sm, sm0) and torch.equal(pv, pc0), (reduce, G, Cn)
+            want = scale * dl0
+            for g in range(G):
+                assert torch.equal(dl.view(V, G, Cn)[:, g], want), (reduce, G, Cn, g)
+    # mean with G = 3: 1/3 is not exact, so within the oracle tolerances
+    V, G, Cn = 3, 3, 400
+    z, labels = make_case(V, G, Cn, 1.0 / 3, seed=11, targeted_torch=targeted and dialect == "torch")
+    out = ops.softmax_adv_loss_video(z.cuda(), labels.cuda(), G, reduce="mean", mean_scale=1.0 / V, **kw)
+    check_against_oracle(out, z, labels, V, G, 1.0 / 3, mode)
+
+
+def test_nan_logits_poison_their_video_only(ops):
+    """a NaN row (corrupt weights upstream) in one clip of video 0: that video's loss and all G of its gradient rows are NaN, video 1 is
+    finite, nothing is read outside the rows (mirrors test_loss_head_nan_logits_do_not_index_out_of_bounds)"""
+    G = 3
+    lg = torch.randn(2 * G, 400)
+    lg[1] = float("nan")
+    labels = torch.tensor([3, 7])
+    for dialect, improve, use_logits in (("tf", True, False), ("tf", True, True), ("torch", True, False), ("tf", False, False)):
+        for reduce in ("sum", "mean"):
+            sm, dl, pv, vl = ops.softmax_adv_loss_video(lg.cuda(), labels.cuda(), G, reduce=reduce, dialect=dialect, improve_loss=improve,
+                                                        use_logits=use_logits, margin=0.05)
+            torch.cuda.synchronize()
+            assert torch.isnan(pv[0, 0]) and torch.isnan(dl[:G]).all(), (dialect, improve, use_logits)
+            assert torch.isfinite(dl[G:]).all() and torch.isfinite(pv[1]).all() and torch.isfinite(sm[1]).all()
+
+
+def test_out_of_range_label_poisons_its_video_only(ops):
+    """the host wrapper refuses the label; the kernel's own guard (the wrapper bypassed) turns it into a NaN loss for that video alone"""
+    from flickering_adversarial_video_amd import _lib
+    G, V, Cn = 2, 3, 400
+    lg = torch.randn(V * G, Cn, device="cuda")
+    for bad in (400, -1):
+        lab = torch.tensor([3, bad, 5], device="cuda")
+        with pytest.raises(ValueError):
+            ops.softmax_adv_loss_video(lg, lab, G)
+        sm, dl, pv, vl = (torch.empty(V, Cn, device="cuda"), torch.empty_like(lg), torch.empty(V, 4, device="cuda"), torch.empty(V, Cn, device="cuda"))
+        a = _lib.LossArgs()
+        a.B, a.C, a.improve_loss, a.margin, a.mean_scale = V * G, Cn, 1, 0.05, 1.0
+        _lib.check(_lib.load().flk_softmax_adv_loss_video(ctypes.byref(a), G, 1.0, _lib.ptr(lg), _lib.ptr(lab), _lib.ptr(sm), _lib.ptr(vl),
+                                                          _lib.ptr(dl), _lib.ptr(pv), _lib.stream_ptr()))
+        torch.cuda.synchronize()
+        d3 = dl.view(V, G, Cn)
+        assert torch.isnan(pv[1, 0]) and torch.isnan(d3[1]).all()
+        assert torch.isfinite(pv[[0, 2]]).all() and torch.isfinite(d3[[0, 2]]).all() and torch.isfinite(vl).all()
+    with pytest.raises(ValueError):
+        ops.softmax_adv_loss_video(lg, torch.tensor([3, 4, 5, 6, 7, 8], device="cuda"), G)       # one label per CLIP
+    with pytest.raises(ValueError):
+        ops.softmax_adv_loss_video(lg[:5], torch.tensor([3, 4], device="cuda"), G)                # 5 clips, G = 2
+
+
+def test_torch_targeted_improve_loss_refused(ops):
+    from flickering_adversarial_video_amd._lib import FlickerHipError
+    with pytest.raises(FlickerHipError):
+        ops.softmax_adv_loss_video(torch.zeros(2, 400).cuda(), torch.zeros(1, dtype=torch.int64).cuda(), 2, dialect="torch",
+                                   improve_loss=True, targeted=True)
+
+
+# ---- engine ---------------------------------------------------------------------------------------------------------------------
+def make_engine(B, G, reduce="sum", **kw):
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet
+    return FlickerVideoResNet("r3d_18", vs.synthetic_weights("r3d_18", 42), batch_size=B, sample_length=T, dtype="f32",
+                              clips_per_video=G, video_reduce=reduce, **kw)
+
+
+@pytest.fixture(scope="module")
+def setup():
+    """(engine B = 4, G = 2, sum; four prepared clips = two videos of two clips; the perturbation every test starts from)"""
+    need_gpu()
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    eng = make_engine(4, 2)
+    x = torch.from_numpy(vs.synthetic_clip(4, T, seed=21)).cuda()
+    d0 = ((np.random.default_rng(2).random(eng.pert_model.size, dtype=np.float32) * 2 - 1) * 0.05)
+    return eng, x, d0
+
+
+def restart(eng, d0):
+    eng.pert_model.init_perturbation(d0)
+    eng.adam_t = 0
+    if eng.adam_m is not None:
+        eng.adam_m.zero_(); eng.adam_v.zero_()
+
+
+def hand_payload(eng, x, labels, crit):
+    """the step's payload from the existing pieces: clip logits, sequential sum, the CLIP head on [V,C], every row repeated G times,
+    backward, delta-gradient reduction, batch sums over the [V,4] table"""
+    from flickering_adversarial_video_amd import ops, parallel
+    G, V = eng.clips_per_video, eng.V
+    a = eng._forward(x, True)
+    zv = seq_sum(eng._logits, G, 1.0)
+    sm, dlv, pc = ops.softmax_adv_loss(zv, labels, dialect="torch", improve_loss=crit.improve_loss, use_logits=crit.logits,
+                                       targeted=False, margin=crit.margin, mean_scale=1.0 / V)
+    eng.net.backward(dlv.repeat_interleave(G, 0).contiguous(), eng._gx)
+    n = 3 * T
+    red = torch.zeros(parallel.payload_size(T), dtype=torch.float32, device=x.device)
+    ops.perturb_grad_reduce(a, eng._gx, red[:n].view(T, 3), eng._scratch)
+    ops.pack_batch_sums(pc, 1.0 / V, red[n:])
+    return red, pc, zv, sm
+
+
+def video_labels(eng, x):
+    """label video 0 with its clean argmax and video 1 with its runner-up"""
+    zv = seq_sum(eng.logits(x, False), eng.clips_per_video, 1.0)
+    return torch.stack([zv[0].argmax(), zv[1].argsort()[-2]]).to(torch.int64)
+
+
+@pytest.mark.parametrize("improve,use_logits", [(True, True), (True, False), (False, False)], ids=["improve-logits", "improve-prob", "ce"])
+def test_engine_gradient_is_the_hand_built_one(setup, improve, use_logits):
+    from flickering_adversarial_video_amd.torch_attack import Losses
+    eng, x, d0 = setup
+    restart(eng, d0)
+    labels = video_labels(eng, x)
+    crit = Losses(beta_1=0.5, lambda_=1.0, improve_loss=improve, logits=use_logits)
+    r = eng.step(x, labels, crit, update=False)
+    got = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in dict(payload=eng._red, adv=r["adv_loss"], am=r["argmax"], sm=r["softmax"],
+                                                                        lp=r["label_prob"], vl=r["video_logits"], dl=eng._dl).items()}
+    assert tuple(got["sm"].shape) == (2, eng.num_classes) and tuple(got["lp"].shape) == (2,) and tuple(got["am"].shape) == (2,)
+    red, pc, zv, sm = hand_payload(eng, x, labels, crit)
+    assert float(red[:3 * T].abs().max()) > 0
+    assert torch.equal(got["payload"], red)
+    assert torch.equal(got["adv"], red[3 * T]) and torch.equal(got["am"], pc[:, 3].to(torch.int64))
+    assert torch.equal(got["vl"], zv) and torch.equal(got["sm"], sm) and torch.equal(got["lp"], pc[:, 1])
+    assert eng.adam_t == 0                                   # update=False moved nothing
+
+
+@pytest.mark.parametrize("optimizer", ["adam", "pgd"])
+def test_trajectory_is_the_hand_built_loop(setup, optimizer):
+    from flickering_adversarial_video_amd import ops
+    from flickering_adversarial_video_amd.torch_attack import Losses
+    eng0, x, d0 = setup
+    eng = eng0 if optimizer == "adam" else make_engine(4, 2, optimizer="pgd")
+    labels = video_labels(eng, x)
+    crit = Losses(beta_1=0.5, lambda_=1.0, improve_loss=True, logits=True)
+    lr, b1 = 1e-2, crit.beta_1
+    restart(eng, d0)
+    start = eng.pert_model.perturbation.clone()
+    for _ in range(3):
+        eng.step(x, labels, crit, lr=lr)
+    got = eng.pert_model.perturbation.clone()
+    assert not torch.equal(got, start)
+    # the same three iterations by hand, on the same engine's network, with an optimiser state of its own
+    restart(eng, d0)
+    delta = eng.pert_model.perturbation
+    m, v = torch.zeros_like(delta), torch.zeros_like(delta)
+    kw = dict(dialect="torch", beta0=crit.lambda_, beta1=b1, beta2=1 - b1, beta3=1 - b1, dyn_max_norm=eng.pert_model.dynamic_max_norm, lr=lr)
+    for t in range(1, 4):
+        red = hand_payload(eng, x, labels, crit)[0]
+        if optimizer == "pgd":
+            ops.perturb_reg_pgd(red[:3 * T], delta, **kw)
+        else:
+            ops.perturb_reg_adam(red[:3 * T], delta, m, v, t, **kw)
+    assert torch.equal(delta, got)
+
+
+def test_attack_and_evaluation_agree(setup):
+    """the clips fit_single_video_attack cuts from a whole video are the clips evaluate_videos(num_samples=G) scores, and the video
+    logits the loss sees are the ones the evaluation sums"""
+    need_gpu()
+    from flickering_adversarial_video_amd.torch_attack import Losses
+    G = 2
+    eng = make_engine(G, G)
+    video = noise((20, 120, 160, 3), 31).cuda()
+    x = eng.prepare_videos([video], num_samples=G).clone()
+    clean = eng.video_logits(eng.logits(x, False))
+    target = clean.argmax(1)
+    crit = Losses(beta_1=0.5, lambda_=1.0, improve_loss=True, logits=True)
+    # restarts disabled: at most restart_after + 1 iterations, the clamp bound never grows
+    res = eng.fit_single_video_attack(video, target, crit, lr=1e-2, n_iter=4, restart_after=4, max_restarts=1, norm_growth=1.0)
+    assert res is not None and 4 <= len(res["loss/total"]) <= 5 and len(res["is_adversarial"]) == len(res["loss/total"])
+    assert res["perturbation"][0].shape == (3, T, 1, 1) and tuple(res["prob_clean_input"].shape) == (1, eng.num_classes)
+    assert [t.shape for t in eng.last_sampling] == [(G, T)]
+    ev = eng.evaluate_videos([video], target, num_samples=G, adversarial=True)
+    assert np.array_equal(ev["clean_video_logits"], res["prob_clean_input"].cpu().numpy())
+    assert np.array_equal(ev["clean_video_logits"], clean.cpu().numpy())
+    final = eng.video_logits(eng.logits(x, True)).cpu().numpy()
+    assert np.array_equal(ev["video_logits"], final)
+    r = eng.step(x, target, crit, update=False)
+    assert np.array_equal(r["video_logits"].cpu().numpy(), final)                # the kernel's sum is the evaluation's
+    with pytest.raises(ValueError):
+        setup[0].fit_single_video_attack([video], target, crit, n_iter=1)         # a whole video (here as a one-element list) needs B == G
+
+
+def test_drivers_count_videos(setup):
+    from flickering_adversarial_video_amd.torch_attack import Adversarial_metrics, Losses
+    eng, _, d0 = setup
+    G = 2
+    restart(eng, (np.random.default_rng(5).random(eng.pert_model.size, dtype=np.float32) * 2 - 1) * 0.1)
+    vids = [noise((20, 120, 160, 3), 31).cuda(), noise((9, 117, 133, 3), 32).cuda(), noise((31, 128, 171, 3), 33).cuda()]
+    batches = [[vids[0], vids[1]], [vids[2], vids[0]]]
+    labs, fooled, losses = [], 0, []
+    crit = Losses(beta_1=0.5, lambda_=1.0, improve_loss=True, logits=False)
+    for b in batches:                        # by hand: the valid phase's clips (uniform offsets), clean video argmax as the label
+        x = eng.prepare_videos(b, num_samples=G).clone()
+        lab = eng.video_logits(eng.logits(x, False)).argmax(1)
+        fooled += int((eng.video_logits(eng.logits(x, True)).argmax(1) != lab).sum())
+        r = eng.step(x, lab, crit, update=False)
+        losses.append(float(r["loss"]))
+        labs.append(lab)
+    loaders = {ph: [(b, l, None) for b, l in zip(batches, labs)] for ph in ("train", "valid")}
+    res = eng.train_an_epoch(loaders, crit, Adversarial_metrics(targeted=False), lr=0.0)        # lr = 0: the perturbation stays
+    assert [t.shape for t in eng.last_sampling] == [(G, T), (G, T)]
+    for ph in ("train", "valid"):                          # default sampling, no augment: both phases cut the same clips
+        assert res[f"{ph}/fooling_ratio"] == fooled / 4    # four videos, all classified correctly when clean (eight clips)
+        assert res[f"{ph}/loss"] == pytest.approx(sum(l * 2 for l in losses) / 4, rel=1e-5) and np.isfinite(res[f"{ph}/loss"])
+    # the same epoch on the clips cut beforehand: B clips, video-major and sample-minor, with V labels
+    pre = [(eng.prepare_videos(b, num_samples=G).clone(), l, None) for b, l in zip(batches, labs)]
+    res2 = eng.fit({"train": pre, "valid": pre}, crit, Adversarial_metrics(targeted=False), lr=0.0, epochs=1)[0]
+    assert res2["valid/loss"] == res["valid/loss"] and res2["valid/fooling_ratio"] == res["valid/fooling_ratio"]
+
+
+def test_value_errors(setup, tmp_path):
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet, Losses
+    eng, x, _ = setup
+    W = vs.synthetic_weights("r3d_18", 42)
+    with pytest.raises(ValueError, match="multiple"):
+        FlickerVideoResNet("r3d_18", W, batch_size=3, sample_length=T, dtype="f32", clips_per_video=2)
+    with pytest.raises(ValueError, match="per_clip"):
+        FlickerVideoResNet("r3d_18", W, batch_size=4, sample_length=T, dtype="f32", clips_per_video=2, per_clip=True)
+    with pytest.raises(ValueError, match="reduce"):
+        FlickerVideoResNet("r3d_18", W, batch_size=4, sample_length=T, dtype="f32", clips_per_video=2, video_reduce="max")
+    t0 = eng.adam_t
+    with pytest.raises(ValueError, match="one class per video"):
+        eng.step(x, torch.zeros(4, dtype=torch.int64, device="cuda"), Losses(improve_loss=True))       # B labels instead of V
+    assert eng.adam_t == t0
+    # the script flag without whole-video input: refused before the script touches the device (a fresh process, the smallest files)
+    np.savez(tmp_path / "clips.npz", clips=np.zeros((2, T, 2, 2, 3), np.uint8), labels=np.zeros(2, np.int64))
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "r2plus1d_main_universal_attack.py"), "--train-npz", str(tmp_path / "clips.npz"),
+                        "--val-npz", str(tmp_path / "clips.npz"), "--results-root", str(tmp_path / "out"), "--clips-per-video", "2"],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "ValueError" in r.stderr and "whole-video" in r.stderr, r.stdout + r.stderr
