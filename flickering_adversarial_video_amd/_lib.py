@@ -106,6 +106,11 @@ _SIGS = {
     "flk_pool_gemm_weights_destroy": (C.c_int, [C.c_void_p]),
     "flk_maxpool3d_bwd_gemm": (C.c_int, [C.POINTER(PoolArgs), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                          C.c_int, C.c_void_p]),
+    "flk_maxpool3d_conv1x1_eligible": (C.c_int, [C.POINTER(PoolArgs), C.c_int, C.c_int, C.c_int, C.c_int]),
+    "flk_maxpool3d_fwd_conv1x1": (C.c_int, [C.POINTER(PoolArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p]),
+    "flk_maxpool3d_bwd_conv1x1": (C.c_int, [C.POINTER(PoolArgs), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "flk_perturb_apply_s2d": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p]),
     "flk_perturb_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -105,6 +105,9 @@ struct flk_net {
   size_t alloc_bytes = 0;
   std::vector<Op> fwd, bwd;
   std::map<std::string, std::pair<Act, int>> named;   // endpoint name -> (tensor, channels)
+  // endpoints the plan itself does not write (the pooled map and its gradient where MaxPool3d_2a runs fused with Conv3d_2b): filled on
+  // demand by flk_net_get_activation through the stand-alone operators, from tensors the plan keeps (valid after the pass that feeds them)
+  std::map<std::string, std::function<int(hipStream_t)>> lazy;
   // bound per call
   const void* x_in = nullptr;
   void* gx_in = nullptr;
@@ -342,8 +345,9 @@ struct flk_net {
     push_conv(bwd, L->name + "/dgrad", a, L->wb, conv_macs(a));
   }
   struct PoolRec { flk_pool_args a; uint8_t* idx_base = nullptr; };
+  // (emit = false: buffers and arguments only -- the caller pushes an operator of its own)
   int emit_pool_fwd(const std::string& name, const Act& in, int C, int kt, int kh, int kw, int st, int sh, int sw, Act& out,
-                    PoolRec& rec, bool relu_input = false) {
+                    PoolRec& rec, bool relu_input = false, bool emit = true) {
     flk_pool_args a{};
     a.relu_input = relu_input;
     a.in = bp(in); a.in_ld = in.ld; a.in_coff = 0; a.C = C;
@@ -359,6 +363,7 @@ struct flk_net {
     }
     a.out = bp(out); a.out_ld = C; a.out_coff = 0; a.idx = rec.idx_base + (size_t)bs_b0 * a.To * a.Ho * a.Wo * C;
     rec.a = a;
+    if (!emit) return FLK_OK;
     const int dt = dtype;
     const double bytes = ((double)in.numel(nbatch()) + out.numel(nbatch())) * esz() + (double)nbatch() * a.To * a.Ho * a.Wo * C;
     push(fwd, Op{name, K_POOL, 0.0, bytes, [a, dt](hipStream_t s) { return flk_maxpool3d_fwd(&a, dt, s); }});
@@ -515,6 +520,11 @@ int flk_net::build_i3d() {
   const bool split = B >= 4 && B % 2 == 0;
   const int nhalf = split ? 2 : 1;
   PoolRec r2a[2], r3a[2];
+  // MaxPool3d_2a_3x3 + Conv3d_2b_1x1 as one kernel per pass where flk_maxpool3d_conv1x1_eligible says yes (bf16, the I3D geometry);
+  // FLK_POOL_CONV_FUSED=0 (read when the plan is built) keeps the four operators -- A/B runs, the plan-level test
+  const bool fuse_switch = !(getenv("FLK_POOL_CONV_FUSED") && atoi(getenv("FLK_POOL_CONV_FUSED")) == 0);
+  bool fuse2a = false;
+  std::vector<std::function<int(hipStream_t)>> lazy_p2a, lazy_Gp2a;      // per batch slice: the stand-alone pool forward / 1x1x1 data-gradient
   const double stem_macs = (double)(B / nhalf) * T1 * H1 * W1 * 343.0 * 3 * 64;   // algorithmic (7x7x7x3), not the padded 4x4x4x32
   // Measured (bs 8): both halves started together 6.94 ms per step against 6.99 unsplit; the second half started one kernel late
   // (so that a pool always meets a convolution) 7.00 -- a convolution and a pool slow each other about as much as they overlap,
@@ -545,13 +555,34 @@ int flk_net::build_i3d() {
     }
     // main pools read ReLU outputs whose gradient is masked by (input > 0): relu_input makes the mask read unnecessary
     if (h) { r2a[h].idx_base = r2a[0].idx_base; r3a[h].idx_base = r3a[0].idx_base; }
-    if ((rc = emit_pool_fwd("MaxPool3d_2a_3x3", a1, 64, 1, 3, 3, 1, 2, 2, p2a, r2a[h], true))) return rc;
+    if ((rc = emit_pool_fwd("MaxPool3d_2a_3x3", a1, 64, 1, 3, 3, 1, 2, 2, p2a, r2a[h], true, false))) return rc;
     if (h == 0) {
       if ((rc = new_act(Gp2a, p2a.T, p2a.H, p2a.W, 64))) return rc;
       if ((rc = new_act(a2b, p2a.T, p2a.H, p2a.W, 64)) || (rc = new_act(G2b, p2a.T, p2a.H, p2a.W, 64))) return rc;
       if ((rc = new_act(a2c, p2a.T, p2a.H, p2a.W, 192)) || (rc = new_act(G2c, p2a.T, p2a.H, p2a.W, 192))) return rc;
+      fuse2a = fuse_switch && flk_maxpool3d_conv1x1_eligible(&r2a[0].a, c2b->cin, c2b->cout, 0, dtype) && c2b->wf->cout_frags == 4 &&
+               c2b->wb->cout_frags == 4;
     }
-    emit_conv_fwd(c2b, p2a, 0, a2b, 0);
+    {
+      const flk_pool_args pa = r2a[h].a;
+      const flk_conv_args ca = conv_fwd_args(c2b, p2a, 0, a2b, 0);
+      const int dt = dtype;
+      const double idx_bytes = (double)nbatch() * pa.To * pa.Ho * pa.Wo * 64;
+      auto pool_alone = [pa, dt](hipStream_t s) { return flk_maxpool3d_fwd(&pa, dt, s); };
+      if (fuse2a) {
+        // MaxPool3d_2a with Conv3d_2b inside (pool.hip): the pooled map is neither written nor read; compulsory bytes: the stem output in,
+        // the unit's output and the index bytes out
+        const flk_conv_weights* wf = c2b->wf;
+        const double bytes = ((double)a1.numel(nbatch()) + a2b.numel(nbatch())) * esz() + idx_bytes;
+        push(fwd, Op{"MaxPool3d_2a_3x3+Conv3d_2b_1x1", K_CONV, 2.0 * conv_macs(ca), bytes, [pa, ca, wf, dt](hipStream_t s) {
+               return flk_maxpool3d_fwd_conv1x1(&pa, wf, ca.scale, ca.bias, ca.relu, ca.out, ca.out_ld, ca.out_coff, 0, dt, s);
+             }});
+        lazy_p2a.push_back(pool_alone);
+      } else {
+        push(fwd, Op{"MaxPool3d_2a_3x3", K_POOL, 0.0, ((double)a1.numel(nbatch()) + p2a.numel(nbatch())) * esz() + idx_bytes, pool_alone});
+        emit_conv_fwd(c2b, p2a, 0, a2b, 0);
+      }
+    }
     emit_conv_fwd(c2c, a2b, 0, a2c, 0);
     if ((rc = emit_pool_fwd("MaxPool3d_3a_3x3", a2c, 192, 1, 3, 3, 1, 2, 2, p3a, r3a[h], true))) return rc;
     if (h == 0 && (rc = new_act(Gp3a, p3a.T, p3a.H, p3a.W, 192))) return rc;
@@ -560,6 +591,22 @@ int flk_net::build_i3d() {
   if (split) push_sync(fwd, K_JOIN, 1);
   named["MaxPool3d_2a_3x3"] = {p2a, 64};
   named["grad:MaxPool3d_2a_3x3"] = {Gp2a, 64};
+  if (fuse2a) {
+    // the fused operators write neither tensor: their endpoints are filled when asked for, over all batch slices
+    for (int h = 0; h < nhalf; ++h) {
+      if (split) { bs_b0 = h * (B / 2); bs_nb = B / 2; }
+      const flk_conv_args g = conv_bwd_args(c2b, G2b, 0, Gp2a, 0, nullptr, 0);
+      const flk_conv_weights* wb = c2b->wb;
+      const int dt = dtype;
+      lazy_Gp2a.push_back([g, wb, dt](hipStream_t s) { return flk_conv3d(&g, wb, dt, s); });
+    }
+    bs_b0 = bs_nb = 0;
+    auto all = [](std::vector<std::function<int(hipStream_t)>> v) {
+      return [v](hipStream_t s) { for (auto& f : v) if (int rc = f(s)) return rc; return (int)FLK_OK; };
+    };
+    lazy["MaxPool3d_2a_3x3"] = all(lazy_p2a);
+    lazy["grad:MaxPool3d_2a_3x3"] = all(lazy_Gp2a);
+  }
   named["Conv3d_2b_1x1"] = {a2b, 64};
   named["Conv3d_2c_3x3"] = {a2c, 192};
   named["grad:Conv3d_2b_1x1"] = {G2b, 64};
@@ -586,8 +633,21 @@ int flk_net::build_i3d() {
         lane = h;
         emit_pool_bwd("MaxPool3d_3a_3x3", h ? r3a1 : r3a0, Gp3a, G2c);
         emit_conv_bwd(c2c, G2c, 0, G2b, 0, &a2b, 0);
-        emit_conv_bwd(c2b, G2b, 0, Gp2a, 0, nullptr, 0);
-        emit_pool_bwd("MaxPool3d_2a_3x3", h ? r2a1 : r2a0, Gp2a, G1);
+        if (fuse2a) {
+          // Conv3d_2b's data-gradient inside MaxPool3d_2a's backward (pool.hip): the pooled map's gradient is neither written nor read
+          const flk_pool_args pa = (h ? r2a1 : r2a0).a;
+          const flk_conv_args g = conv_bwd_args(c2b, G2b, 0, Gp2a, 0, nullptr, 0);
+          const flk_conv_weights* wb = c2b->wb;
+          void* gin = bp(G1);
+          const int dt = dtype, gin_ld = G1.ld;
+          const double bytes = ((double)G2b.numel(pa.B) + G1.numel(pa.B)) * esz() + (double)pa.B * pa.To * pa.Ho * pa.Wo * 64;
+          push(bwd, Op{"Conv3d_2b_1x1/dgrad+MaxPool3d_2a_3x3/grad", K_CONV, 2.0 * conv_macs(g), bytes, [pa, g, wb, gin, gin_ld, dt](hipStream_t s) {
+                 return flk_maxpool3d_bwd_conv1x1(&pa, g.in, g.in_ld, g.in_coff, wb, gin, gin_ld, 0, nullptr, 0, 0, dt, s);
+               }});
+        } else {
+          emit_conv_bwd(c2b, G2b, 0, Gp2a, 0, nullptr, 0);
+          emit_pool_bwd("MaxPool3d_2a_3x3", h ? r2a1 : r2a0, Gp2a, G1);
+        }
         if (split) {
           // the half's share of the fused stem delta-gradient, right behind the gradient it consumes: the MFMA-bound GEMM of one half
           // runs beside the HBM-bound tail (1x1x1 data-gradient, pool backward) of the other instead of after both
@@ -1535,6 +1595,13 @@ extern "C" int flk_net_get_activation(flk_net* n, const char* name, float* host_
   if (!host_out) return FLK_OK;
   FLK_REQUIRE((int64_t)(npos * C) <= cap_numel, "flk_net_get_activation: buffer too small");
   FLK_CHECK_HIP(hipDeviceSynchronize());
+  {
+    auto lz = n->lazy.find(name);
+    if (lz != n->lazy.end()) {
+      if (int rc = lz->second(nullptr)) return rc;
+      FLK_CHECK_HIP(hipDeviceSynchronize());
+    }
+  }
   const size_t esz = n->esz();
   std::vector<char> tmp(npos * a.ld * esz);
   FLK_CHECK_HIP(hipMemcpy(tmp.data(), a.p, tmp.size(), hipMemcpyDeviceToHost));

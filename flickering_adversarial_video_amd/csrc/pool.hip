@@ -17,10 +17,13 @@
 //             order): maxpool_s1_tiled_bwd for the LDS-tiled stride-1 windows, maxpool_bwd_kernel otherwise.  There is no switch
 //             between the forms.  Optional relu mask of the producing layer (mask > 0) fused in.
 //   fused   : flk_maxpool3d_bwd_gemm (bf16) = the scatter form fed by an MFMA product, same fixed point.
+//             flk_maxpool3d_fwd_conv1x1 / flk_maxpool3d_bwd_conv1x1 (bf16, 1x3x3 / 1x2x2, 64 -> 64): MaxPool3d_2a with Conv3d_2b_1x1 inside,
+//             forward and backward, bitwise the two launches they replace (end of this file).
 //   Channel slices: in / out / gout / gin / mask are channels [coff, coff + C) of rows ld wide; nothing outside the slice is written.
 #include <stdlib.h>
 #include <string.h>
 #include "flk_internal.h"
+#include "conv_common.h"
 
 // Timing ablations (skip loads / atomics / stores: WRONG results) exist only in -DFLK_ABLATE builds (tools/*_time.py pass it through
 // FLK_HIPCC_EXTRA); in the product library the switches are compile-time zeros and the kernels carry no such branch.
@@ -123,6 +126,36 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolKP p) {
   PV<T>::stidx(p.idx + opos * p.C + cg * EPL, bi);
 }
 
+// The window scan of one (position, channel group) over its NT raw 16-byte taps (ok[tap]: the tap is an in-bounds cell): first maximum in
+// scan order (strict >), padded cells never win, relu_input turns a maximum <= 0 into 255 ("no cell").  Shared by maxpool_fwd_kernel_k and
+// the fused MaxPool3d_2a + Conv3d_2b forward (maxpool133_conv1x1_fwd): one comparison sequence, the same bits.
+template <typename T, int NT>
+__device__ static inline void pool_window_scan(const uint4 (&raw)[NT], const bool (&ok)[NT], int relu_input, float (&best)[PV<T>::EPL], int (&bi)[PV<T>::EPL]) {
+  constexpr int EPL = PV<T>::EPL;
+#pragma unroll
+  for (int e = 0; e < EPL; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+#pragma unroll
+  for (int tap = 0; tap < NT; ++tap) {
+    float v[EPL];
+    if constexpr (sizeof(T) == 2) {
+      const uint32_t w[4] = {raw[tap].x, raw[tap].y, raw[tap].z, raw[tap].w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { v[2 * k] = __uint_as_float(w[k] << 16); v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
+    } else {
+      v[0] = __uint_as_float(raw[tap].x); v[1] = __uint_as_float(raw[tap].y); v[2] = __uint_as_float(raw[tap].z); v[3] = __uint_as_float(raw[tap].w);
+    }
+    if (ok[tap]) {
+#pragma unroll
+      for (int e = 0; e < EPL; ++e)
+        if (v[e] > best[e]) { best[e] = v[e]; bi[e] = tap; }
+    }
+  }
+  if (relu_input) {
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) bi[e] = best[e] > 0.f ? bi[e] : 255;
+  }
+}
+
 // The same with the window as template arguments (the I3D pools: 1x3x3, 3x3x3, 2x2x2): the tap loop unrolls and ALL tap loads of a thread
 // are requested before the first compare -- with run-time loop bounds hipcc emits load -> wait -> compare per tap, KT*KH*KW exposed memory
 // round trips per thread.  Same scan order, same tie rule (strict >), same bits.
@@ -146,33 +179,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel_k(const PoolKP p) {
         const int it = ot * p.st - p.pt + dt, ih = oh * p.sh - p.ph + dh, iw = ow * p.sw - p.pw + dw;
         ok[tap] = (unsigned)it < (unsigned)p.Ti && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi;
         const size_t pos = ok[tap] ? (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw) : 0;      // (position 0 is always readable)
-        if constexpr (sizeof(T) == 2) raw[tap] = *(const uint4*)(p.in + (pos * p.in_ld + p.in_coff + cg * EPL) * sizeof(T));
-        else raw[tap] = *(const uint4*)(p.in + (pos * p.in_ld + p.in_coff + cg * EPL) * sizeof(T));
+        raw[tap] = *(const uint4*)(p.in + (pos * p.in_ld + p.in_coff + cg * EPL) * sizeof(T));
       }
   float best[EPL];
   int bi[EPL];
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) { best[e] = -INFINITY; bi[e] = 0; }
-#pragma unroll
-  for (int tap = 0; tap < NT; ++tap) {
-    float v[EPL];
-    if constexpr (sizeof(T) == 2) {
-      const uint32_t w[4] = {raw[tap].x, raw[tap].y, raw[tap].z, raw[tap].w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { v[2 * k] = __uint_as_float(w[k] << 16); v[2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
-    } else {
-      v[0] = __uint_as_float(raw[tap].x); v[1] = __uint_as_float(raw[tap].y); v[2] = __uint_as_float(raw[tap].z); v[3] = __uint_as_float(raw[tap].w);
-    }
-    if (ok[tap]) {
-#pragma unroll
-      for (int e = 0; e < EPL; ++e)
-        if (v[e] > best[e]) { best[e] = v[e]; bi[e] = tap; }
-    }
-  }
-  if (p.relu_input) {
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) bi[e] = best[e] > 0.f ? bi[e] : 255;
-  }
+  pool_window_scan<T, NT>(raw, ok, p.relu_input, best, bi);
   const size_t opos = (((size_t)(b * p.To + ot) * p.Ho + oh) * p.Wo + ow);
   PV<T>::st(p.out + (opos * p.out_ld + p.out_coff + cg * EPL) * sizeof(T), best);
   PV<T>::stidx(p.idx + opos * p.C + cg * EPL, bi);
@@ -231,34 +242,20 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const PoolKP p) {
 // a + s): every thread loads the index bytes and gradients of its <= 8 candidate windows up front (independent loads,
 // shared with its neighbours through L1/L2), then resolves its cells in registers in a fixed order -- no atomics,
 // no dependent load chains, and each gradient cell is written exactly once (64-byte runs per thread).
-template <typename T, int KT, int KH, int KW, int ST, int SH, int SW>
-__global__ __launch_bounds__(256) void maxpool_strided_bwd(const PoolKP p) {
+// The owner's part once the index bytes id[w] and gradients go[w] of its candidate windows w = (dt * NH + dh) * NW + dw (window o - d per
+// dimension; ok[w]: it exists) are in registers: every owned cell sums its candidates in a fixed order and is stored once.  Shared by
+// maxpool_strided_bwd (candidates from global memory) and the fused Conv3d_2b data-gradient + MaxPool3d_2a backward
+// (maxpool133_conv1x1_bwd: candidates from the LDS tile its GEMM phase wrote, MASKABLE = false): one summation sequence, the same bits.
+template <typename T, int KT, int KH, int KW, int ST, int SH, int SW, bool MASKABLE>
+__device__ static inline void strided_owner_resolve(const PoolKP& p, int b, int ot, int oh, int ow, int cg,
+                                                    const int (&id)[(KT > ST ? 2 : 1) * (KH > SH ? 2 : 1) * (KW > SW ? 2 : 1)][PV<T>::EPL],
+                                                    const float (&go)[(KT > ST ? 2 : 1) * (KH > SH ? 2 : 1) * (KW > SW ? 2 : 1)][PV<T>::EPL],
+                                                    const bool (&ok)[(KT > ST ? 2 : 1) * (KH > SH ? 2 : 1) * (KW > SW ? 2 : 1)]) {
   constexpr int EPL = PV<T>::EPL;
   constexpr int NT = KT > ST ? 2 : 1, NH = KH > SH ? 2 : 1, NW = KW > SW ? 2 : 1;     // candidate windows per dimension
-  static_assert(KT <= 2 * ST && KH <= 2 * SH && KW <= 2 * SW, "a cell may see at most two windows per dimension");
-  const int ng = p.C / EPL;
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= (unsigned)(p.Wo * ng)) return;
-  const int ow = i / ng, cg = i - ow * ng;
-  const int oh = blockIdx.y, ot = blockIdx.z % p.To, b = blockIdx.z / p.To;
-  int id[NT * NH * NW][EPL];
-  float go[NT * NH * NW][EPL];
-  bool ok[NT * NH * NW];
-#pragma unroll
-  for (int dt = 0; dt < NT; ++dt)
-#pragma unroll
-    for (int dh = 0; dh < NH; ++dh)
-#pragma unroll
-      for (int dw = 0; dw < NW; ++dw) {
-        const int w = (dt * NH + dh) * NW + dw;
-        ok[w] = ot - dt >= 0 && oh - dh >= 0 && ow - dw >= 0;
-        const size_t opos = (((size_t)(b * p.To + max(ot - dt, 0)) * p.Ho + max(oh - dh, 0)) * p.Wo + max(ow - dw, 0));
-        PV<T>::ldidx(p.idx + opos * p.C + cg * EPL, id[w]);
-        PV<T>::ld(p.gout + (opos * p.gout_ld + p.gout_coff + cg * EPL) * sizeof(T), go[w]);
-      }
   // the ReLU-mask operand of every owned cell, requested with the loads above (inside the cell loop each was load -> wait -> store):
   // 1x3x3 / 2 (4 cells) 57.9 -> 54.4 us; with 8 cells the registers cost more than the round trips (3x3x3 / 2: 64.1 -> 67.6 us): not there
-  constexpr bool HOIST = ST * SH * SW <= 4;
+  constexpr bool HOIST = MASKABLE && ST * SH * SW <= 4;
   float mk[HOIST ? ST * SH * SW : 1][EPL];
   if (HOIST && p.mask) {
 #pragma unroll
@@ -298,13 +295,41 @@ __global__ __launch_bounds__(256) void maxpool_strided_bwd(const PoolKP p) {
               for (int e = 0; e < EPL; ++e) g[e] += id[w][e] == tap ? go[w][e] : 0.f;
             }
         const size_t ipos = (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw);
-        if (p.mask) {
+        if (MASKABLE && p.mask) {
           if (!HOIST) PV<T>::ld(p.mask + (ipos * p.mask_ld + p.mask_coff + cg * EPL) * sizeof(T), mk[0]);
 #pragma unroll
           for (int e = 0; e < EPL; ++e) g[e] = mk[HOIST ? (at * SH + ah) * SW + aw : 0][e] > 0.f ? g[e] : 0.f;
         }
         PV<T>::st(p.gin + (ipos * p.gin_ld + p.gin_coff + cg * EPL) * sizeof(T), g);
       }
+}
+
+template <typename T, int KT, int KH, int KW, int ST, int SH, int SW>
+__global__ __launch_bounds__(256) void maxpool_strided_bwd(const PoolKP p) {
+  constexpr int EPL = PV<T>::EPL;
+  constexpr int NT = KT > ST ? 2 : 1, NH = KH > SH ? 2 : 1, NW = KW > SW ? 2 : 1;     // candidate windows per dimension
+  static_assert(KT <= 2 * ST && KH <= 2 * SH && KW <= 2 * SW, "a cell may see at most two windows per dimension");
+  const int ng = p.C / EPL;
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= (unsigned)(p.Wo * ng)) return;
+  const int ow = i / ng, cg = i - ow * ng;
+  const int oh = blockIdx.y, ot = blockIdx.z % p.To, b = blockIdx.z / p.To;
+  int id[NT * NH * NW][EPL];
+  float go[NT * NH * NW][EPL];
+  bool ok[NT * NH * NW];
+#pragma unroll
+  for (int dt = 0; dt < NT; ++dt)
+#pragma unroll
+    for (int dh = 0; dh < NH; ++dh)
+#pragma unroll
+      for (int dw = 0; dw < NW; ++dw) {
+        const int w = (dt * NH + dh) * NW + dw;
+        ok[w] = ot - dt >= 0 && oh - dh >= 0 && ow - dw >= 0;
+        const size_t opos = (((size_t)(b * p.To + max(ot - dt, 0)) * p.Ho + max(oh - dh, 0)) * p.Wo + max(ow - dw, 0));
+        PV<T>::ldidx(p.idx + opos * p.C + cg * EPL, id[w]);
+        PV<T>::ld(p.gout + (opos * p.gout_ld + p.gout_coff + cg * EPL) * sizeof(T), go[w]);
+      }
+  strided_owner_resolve<T, KT, KH, KW, ST, SH, SW, true>(p, b, ot, oh, ow, cg, id, go, ok);
 }
 
 template <typename T, int KT, int KH, int KW, int ST, int SH, int SW>
@@ -1434,6 +1459,354 @@ extern "C" int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int
     case 3: FLK_LAUNCH_KERNEL(maxpool_scatter_gemm_bwd<3>, grid, dim3(256), lds, s, pg, m1, m2); break;
     default: FLK_LAUNCH_KERNEL(maxpool_scatter_gemm_bwd<4>, grid, dim3(256), lds, s, pg, m1, m2); break;
   }
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------------------------------------------
+// MaxPool3d_2a_3x3 + Conv3d_2b_1x1 in one kernel per pass (i3d.py:174-180; bf16, window (1,3,3) / stride (1,2,2) over even H, W, 64 -> 64).
+// The pooled map has one consumer, the 1x1x1 unit, and so has its gradient: between producer and consumer each is a 64 x 64 GEMM per
+// position, 16 MFMAs per 256 positions.  Run inside the pool kernels neither tensor crosses HBM.  Both kernels repeat the arithmetic of the
+// launches they replace -- the pool bodies are the shared inlines above, the MFMA instruction, its K order (slab 0, then slab 1) and the
+// epilogue (conv_common.h) are conv1x1_dma_kernel's -- so out / idx / gin are bitwise what the two launches write.
+struct PoolConvFP {
+  PoolKP k;            // the pool; k.out = the pooled map (written only with write_pool)
+  ConvKP c;            // the 1x1x1 unit's epilogue operands and output slice; c.w = its packed A fragments [2 slabs][4][64 lanes][16 B]
+  unsigned npos;
+  int write_pool;
+};
+
+// Workgroup = 256 consecutive pooled positions of the flat [B,T,Ho,Wo] grid x all 64 channels.
+//   pool phase: a task is (position, 8-channel group), 2048 per tile, 8 per thread, consecutive lanes = consecutive channel groups of a
+//               position (maxpool_fwd_kernel_k's order).  The 18 tap loads of two tasks are requested together, then consumed; the index
+//               bytes go to global memory, the pooled bf16 x 8 into LDS in conv1x1_dma_kernel's slab layout: [slab][256 positions x 64 B],
+//               slot = chunk ^ g[(position >> 2) & 3], g = {0,3,2,1}.
+//   GEMM phase: after one barrier, conv1x1_dma_kernel's compute: wave w owns rows [64 w, 64 w + 64), fragments bf / af, slab 0 then slab 1,
+//               and its epilogue (finish_store_row_ops: scale and bias in two roundings, ReLU, one 16-byte store per 8 channels).
+// LDS: 2 x 16 KiB slabs + 8 KiB weights: three workgroups per CU.
+__global__ __launch_bounds__(256, 3) void maxpool133_conv1x1_fwd(const PoolConvFP p) {
+  typedef Prec<bf16_t> PR;
+  typedef typename PR::frag frag;
+  constexpr int EPL = 8, NF = 4, NTAP = 9, TB = 2;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q = lane >> 4, m = lane & 15;
+  const PoolKP& k = p.k;
+  const unsigned npos = p.npos, pos0 = blockIdx.x * 256u;
+  const int gsw[4] = {0, 3, 2, 1};
+  // the unit's A fragments, once per workgroup
+  {
+    const uint4 w0 = *(const uint4*)(p.c.w + tid * 16), w1 = *(const uint4*)(p.c.w + (tid + 256) * 16);
+    *(uint4*)(smem + 32768 + tid * 16) = w0;
+    *(uint4*)(smem + 32768 + (tid + 256) * 16) = w1;
+  }
+  // ---- pool phase ----
+  const int cg = tid & 7;
+  const unsigned hw = (unsigned)(k.Ho * k.Wo);
+#pragma unroll 1
+  for (int it0 = 0; it0 < 8; it0 += TB) {
+    uint4 raw[TB][NTAP];
+    bool ok[TB][NTAP];
+    unsigned posv[TB];
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      posv[u] = pos0 + (unsigned)((it0 + u) * 32 + (tid >> 3));
+      const unsigned pos = posv[u] < npos ? posv[u] : npos - 1;      // rows past the end: a valid window, never stored
+      const unsigned bt = pos / hw, rem = pos - bt * hw;               // (kt = st = 1, pt = 0: input frame b * Ti + it = b * To + ot)
+      const int oh = (int)(rem / (unsigned)k.Wo), ow = (int)(rem - (unsigned)oh * (unsigned)k.Wo);
+#pragma unroll
+      for (int dh = 0; dh < 3; ++dh)
+#pragma unroll
+        for (int dw = 0; dw < 3; ++dw) {
+          const int tap = dh * 3 + dw;
+          const int ih = oh * 2 - k.ph + dh, iw = ow * 2 - k.pw + dw;
+          ok[u][tap] = (unsigned)ih < (unsigned)k.Hi && (unsigned)iw < (unsigned)k.Wi;
+          const size_t ipos = ok[u][tap] ? (((size_t)bt * k.Hi + ih) * k.Wi + iw) : 0;      // (position 0 is always readable)
+          raw[u][tap] = *(const uint4*)(k.in + (ipos * k.in_ld + k.in_coff + cg * EPL) * 2);
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < TB; ++u) {
+      float best[EPL];
+      int bi[EPL];
+      pool_window_scan<bf16_t, NTAP>(raw[u], ok[u], k.relu_input, best, bi);
+      bf16x8 pv;
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) pv[e] = (bf16_t)best[e];        // (PV<bf16_t>::st's conversion: exact, the values are bf16 numbers)
+      if (posv[u] < npos) {
+        PV<bf16_t>::stidx(k.idx + (size_t)posv[u] * k.C + cg * EPL, bi);
+        if (p.write_pool) *(bf16x8*)(k.out + ((size_t)posv[u] * k.out_ld + k.out_coff + cg * EPL) * 2) = pv;
+      }
+      const int pl = (it0 + u) * 32 + (tid >> 3);
+      *(bf16x8*)(smem + (cg >> 2) * 16384 + pl * 64 + (((cg & 3) ^ gsw[(pl >> 2) & 3]) * 16)) = pv;
+    }
+  }
+  __syncthreads();
+  // ---- GEMM phase: conv1x1_dma_kernel's compute plan ----
+  int boff[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) boff[i] = (64 * wave + 16 * i + m) * 64 + ((q ^ gsw[(m >> 2) & 3]) * 16);
+  f32x4 acc[NF][4];
+#pragma unroll
+  for (int f = 0; f < NF; ++f)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[f][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const char* const sb = smem + s * 16384;
+    frag bf[4], af[NF];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) bf[i] = *(const frag*)(sb + boff[i]);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) af[f] = *(const frag*)(smem + 32768 + ((s * NF + f) * 64 + lane) * 16);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int f = 0; f < NF; ++f)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) PR::mma(af[f], bf[i], acc[f][i]);
+  }
+  // ---- epilogue (conv1x1_dma_kernel's, no add / mask operand) ----
+  constexpr int NG = 4 * NF / EPL;
+  const int cbase = q * EPL;
+  float4 sc[NG][2], bi[NG][2];
+  epi_scale_bias_regs<bf16_t, NG>(p.c, cbase, sc, bi);
+  uint4 none[NG];
+#pragma unroll
+  for (int g = 0; g < NG; ++g) none[g] = make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned pos = pos0 + (unsigned)(64 * wave + 16 * i + m);
+    if (pos >= npos) continue;
+    float v[NG][EPL];
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+      for (int e = 0; e < EPL; ++e) v[g][e] = acc[(g * EPL + e) >> 2][i][(g * EPL + e) & 3];
+    finish_store_row_ops<bf16_t, NG>(p.c, (size_t)pos, nullptr, cbase, v, sc, bi, none, none);
+  }
+}
+
+struct PoolConvBP {
+  PoolKP k;            // the pool (k.gin = the stem output's gradient)
+  const char* w;       // the unit's data-gradient A fragments (batch-norm scale folded in) [2 slabs][4][64 lanes][16 B]
+  const char* g;       // gradient of the unit's pre-ReLU output, already masked by its producer
+  char* gp;            // the pooled map's gradient, written only when not NULL
+  int g_ld, g_coff, gp_ld, gp_coff;
+  int Hb, Wb, lgWb, nTh, nTw;
+};
+constexpr int POOL_CONV_BWD_MAXFRAG = 20;      // position fragments of the largest box with its halo: (8 + 1) x (32 + 1) = 297 positions -> 19
+
+// Workgroup = a box of 1 x Hb x Wb windows (Hb * Wb = 256, Wb a power of two) of one frame, plus the previous row and column: an owned cell
+// can be covered by window oh - 1 / ow - 1.
+//   GEMM phase: Gp = W2b^T . G2b for the (Hb + 1)(Wb + 1) positions, 16 per fragment, fragments dealt round-robin to the waves.  B fragments
+//               straight from global memory (rows are K-contiguous: lane (q, m) = 16 bytes of position m), all of a wave's requested before
+//               the first MFMA; K = two 32-channel steps in slab order; each value rounded to bf16 exactly as the stand-alone data-gradient
+//               stores it (no scale / bias / ReLU / mask: the pooled map is not a ReLU output) into the LDS tile [position][128 B].
+//   pool phase: after one barrier, maxpool_strided_bwd<bf16, 1,3,3, 1,2,2>'s body (strided_owner_resolve) with the candidate gradients read
+//               from the tile; the index bytes come from global memory, half of them requested before the GEMM phase.
+// Positions outside the frame (the halo of boxes at oh = 0 / ow = 0, boxes cut at the right or bottom edge) compute on position 0's row and
+// are never read: ok[] and the window bounds gate them exactly as in the stand-alone kernel.
+__global__ __launch_bounds__(256, 3) void maxpool133_conv1x1_bwd(const PoolConvBP p) {
+  typedef Prec<bf16_t> PR;
+  typedef typename PR::frag frag;
+  constexpr int EPL = 8;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int q = lane >> 4, m = lane & 15;
+  const PoolKP& k = p.k;
+  int bid = blockIdx.x;
+  const int tw = bid % p.nTw; bid /= p.nTw;
+  const int th = bid % p.nTh;
+  const int bt = bid / p.nTh;                    // b * To + ot
+  const int b = bt / k.To, ot = bt - b * k.To;
+  const int oh0 = th * p.Hb, ow0 = tw * p.Wb;
+  const int Wp = p.Wb + 1, P = (p.Hb + 1) * Wp, nfrag = (P + 15) >> 4;
+  const int cg = tid & 7;
+
+  // ---- the index bytes of this thread's 8 (window, channel group) tasks, 4 candidate windows each: requested in two halves ----
+  auto task_window = [&](int it, int& wh, int& ww) {
+    const int wl = it * 32 + (tid >> 3);
+    wh = wl >> p.lgWb; ww = wl & (p.Wb - 1);
+    return oh0 + wh < k.Ho && ow0 + ww < k.Wo;
+  };
+  auto load_idx = [&](int it, uint2 (&r)[4]) {
+    int wh, ww;
+    if (!task_window(it, wh, ww)) { r[0] = r[1] = r[2] = r[3] = make_uint2(0u, 0u); return; }
+    const int oh = oh0 + wh, ow = ow0 + ww;
+#pragma unroll
+    for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+      for (int dw = 0; dw < 2; ++dw) {
+        const size_t opos = ((size_t)bt * k.Ho + max(oh - dh, 0)) * k.Wo + max(ow - dw, 0);
+        r[dh * 2 + dw] = *(const uint2*)(k.idx + opos * k.C + cg * EPL);
+      }
+  };
+  uint2 ia[4][4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) load_idx(it, ia[it]);
+
+  // ---- GEMM phase ----
+  {
+    frag af[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int f = 0; f < 4; ++f) af[s][f] = *(const frag*)(p.w + ((s * 4 + f) * 64 + lane) * 16);
+    constexpr int NJ = POOL_CONV_BWD_MAXFRAG / 4;
+    frag bq[NJ][2];
+    size_t gpos[NJ];
+    bool own[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int fr = wave + 4 * j;
+      own[j] = false; gpos[j] = 0;
+      if (fr < nfrag) {
+        const int pl = fr * 16 + m;
+        const int hh = pl / Wp, wp = pl - hh * Wp;
+        const int oh = oh0 - 1 + hh, ow = ow0 - 1 + wp;
+        const bool inb = pl < P && (unsigned)oh < (unsigned)k.Ho && (unsigned)ow < (unsigned)k.Wo;
+        gpos[j] = inb ? ((size_t)bt * k.Ho + oh) * k.Wo + ow : 0;                             // (position 0 is always readable)
+        own[j] = inb && hh >= 1 && wp >= 1;                                                 // a window of this box, not its halo
+        const char* gp = p.g + (gpos[j] * p.g_ld + p.g_coff + q * EPL) * 2;
+        bq[j][0] = *(const frag*)gp;
+        bq[j][1] = *(const frag*)(gp + 64);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const int fr = wave + 4 * j;
+      if (fr < nfrag) {
+        f32x4 acc[4];
+#pragma unroll
+        for (int f = 0; f < 4; ++f) acc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int f = 0; f < 4; ++f) PR::mma(af[s][f], bq[j][s], acc[f]);
+        const int pl = fr * 16 + m;
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          float v[EPL];
+#pragma unroll
+          for (int e = 0; e < EPL; ++e) v[e] = acc[(g * EPL + e) >> 2][(g * EPL + e) & 3];
+          const uint4 r = PR::from_f32(v);
+          *(uint4*)(smem + pl * 128 + g * 64 + q * 16) = r;
+          if (p.gp && own[j]) *(uint4*)(p.gp + (gpos[j] * p.gp_ld + p.gp_coff + g * 32 + q * EPL) * 2) = r;
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- pool phase ----
+  uint2 ib[4][4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) load_idx(4 + it, ib[it]);
+  auto resolve = [&](int it, const uint2 (&r)[4]) {
+    int wh, ww;
+    if (!task_window(it, wh, ww)) return;
+    const int oh = oh0 + wh, ow = ow0 + ww;
+    int id[4][EPL];
+    float go[4][EPL];
+    bool ok[4];
+#pragma unroll
+    for (int dh = 0; dh < 2; ++dh)
+#pragma unroll
+      for (int dw = 0; dw < 2; ++dw) {
+        const int w = dh * 2 + dw;
+        ok[w] = oh - dh >= 0 && ow - dw >= 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { id[w][e] = (r[w].x >> (8 * e)) & 255; id[w][4 + e] = (r[w].y >> (8 * e)) & 255; }      // (PV<bf16_t>::ldidx)
+        const uint4 gv = *(const uint4*)(smem + ((wh + 1 - dh) * Wp + (ww + 1 - dw)) * 128 + cg * 16);
+        PR::to_f32(gv, go[w]);
+      }
+    strided_owner_resolve<bf16_t, 1, 3, 3, 1, 2, 2, false>(k, b, ot, oh, ow, cg, id, go, ok);
+  };
+#pragma unroll
+  for (int it = 0; it < 4; ++it) resolve(it, ia[it]);
+#pragma unroll
+  for (int it = 0; it < 4; ++it) resolve(4 + it, ib[it]);
+}
+
+// why the fused kernels do not take this pool + 1x1x1 pair (a static string), or nullptr when they do
+static const char* pool_conv_why_not(const flk_pool_args* a, int cin, int cout, int has_mask, int dtype) {
+  if (!a) return "null pool arguments";
+  if (dtype != FLK_BF16) return "bf16 only (fp32, the parity mode, keeps the two launches)";
+  if (!(a->kt == 1 && a->kh == 3 && a->kw == 3 && a->st == 1 && a->sh == 2 && a->sw == 2)) return "the window must be (1,3,3) with stride (1,2,2)";
+  if (!(a->B > 0 && a->To > 0 && a->Ho > 0 && a->Wo > 0)) return "bad dims";
+  if (!strided_owner_ok(a, 1, 3, 3, 1, 2, 2)) return "the pool does not fit the owner-form backward";
+  if (!(a->To == a->Ti && a->Hi == 2 * a->Ho && a->Wi == 2 * a->Wo && a->ph == 0 && a->pw == 0)) return "H and W must be even (SAME pad-before 0) and To == Ti";
+  if (!(a->C == 64 && cin == 64 && cout == 64)) return "C, cin and cout must all be 64 (two 32-channel slabs in, one 64-channel tile out)";
+  if (has_mask) return "the 1x1x1 data-gradient must not carry a mask operand";
+  if ((size_t)a->B * a->To * a->Ho * a->Wo >= (1ull << 29)) return "too many positions";
+  return nullptr;
+}
+extern "C" int flk_maxpool3d_conv1x1_eligible(const flk_pool_args* a, int cin, int cout, int has_mask, int dtype) {
+  return pool_conv_why_not(a, cin, cout, has_mask, dtype) ? 0 : 1;
+}
+// the unit's packed weights as the kernels index them: [2 slabs][1 tap][4 fragments][64 lanes][16 B]
+static int check_pool_conv_weights(const flk_conv_weights* w, const char* who) {
+  FLK_REQUIRE(w && w->dev, "%s: null weights", who);
+  FLK_REQUIRE(w->dtype == FLK_BF16 && w->kt == 1 && w->kh == 1 && w->kw == 1 && w->cin == 64 && w->cout == 64 && w->nslab == 2 && w->ntaps == 1 &&
+                  w->cout_frags == 4 && w->cin_split == 0 && !w->stem4,
+              "%s: the weights must be a bf16 1x1x1 64 -> 64 operator of exactly two slabs and four output fragments (nf 2 or 4)", who);
+  return FLK_OK;
+}
+
+extern "C" int flk_maxpool3d_fwd_conv1x1(const flk_pool_args* a, const flk_conv_weights* w, const float* scale, const float* bias, int relu,
+                                         void* out, int out_ld, int out_coff, int write_pool, int dtype, void* stream) {
+  FLK_REQUIRE(a && a->in && a->idx && out, "flk_maxpool3d_fwd_conv1x1: null argument");
+  if (int rc = check_pool_conv_weights(w, "flk_maxpool3d_fwd_conv1x1")) return rc;
+  if (const char* why = pool_conv_why_not(a, w->cin, w->cout, 0, dtype)) { flk_set_error("flk_maxpool3d_fwd_conv1x1: %s", why); return FLK_EINVAL; }
+  if (int rc = check_pool(a)) return rc;
+  FLK_REQUIRE(a->in_ld % 8 == 0 && a->in_coff % 8 == 0 && a->in_coff + 64 <= a->in_ld && out_ld % 8 == 0 && out_coff % 8 == 0 && out_coff >= 0 &&
+                  out_coff + 64 <= out_ld, "flk_maxpool3d_fwd_conv1x1: bad ld / coff");
+  FLK_REQUIRE(!write_pool || (a->out && a->out_ld % 8 == 0 && a->out_coff % 8 == 0 && a->out_coff >= 0 && a->out_coff + 64 <= a->out_ld),
+              "flk_maxpool3d_fwd_conv1x1: write_pool needs the pooled map's buffer (a->out, ld / coff multiples of 8)");
+  PoolConvFP p{};
+  fill(p.k, a);
+  p.npos = (unsigned)((size_t)a->B * a->To * a->Ho * a->Wo);
+  p.write_pool = write_pool ? 1 : 0;
+  p.c.w = (const char*)w->dev; p.c.out = (char*)out; p.c.out2 = (char*)out;
+  p.c.scale = scale; p.c.bias = bias; p.c.relu = relu ? 1 : 0;
+  p.c.out_ld = out_ld; p.c.out_coff = out_coff; p.c.cout = 64; p.c.cout1 = 64; p.c.cin = 64;
+  const unsigned grid = (p.npos + 255u) / 256u;
+  FLK_LAUNCH_KERNEL(maxpool133_conv1x1_fwd, dim3(grid), dim3(256), 2 * 16384 + 8192, (hipStream_t)stream, p);
+  flk_last_kernel_tag = "maxpool133_conv1x1_fwd";
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_maxpool3d_bwd_conv1x1(const flk_pool_args* a, const void* g, int g_ld, int g_coff, const flk_conv_weights* wb,
+                                         void* gin, int gin_ld, int gin_coff, void* gpool, int gpool_ld, int gpool_coff, int dtype, void* stream) {
+  FLK_REQUIRE(a && a->idx && g && gin, "flk_maxpool3d_bwd_conv1x1: null argument");
+  if (int rc = check_pool_conv_weights(wb, "flk_maxpool3d_bwd_conv1x1")) return rc;
+  if (const char* why = pool_conv_why_not(a, wb->cout, wb->cin, 0, dtype)) { flk_set_error("flk_maxpool3d_bwd_conv1x1: %s", why); return FLK_EINVAL; }
+  if (int rc = check_pool(a)) return rc;
+  FLK_REQUIRE(g_ld % 8 == 0 && g_coff % 8 == 0 && g_coff >= 0 && g_coff + 64 <= g_ld && gin_ld % 8 == 0 && gin_coff % 8 == 0 && gin_coff >= 0 &&
+                  gin_coff + 64 <= gin_ld, "flk_maxpool3d_bwd_conv1x1: bad ld / coff");
+  FLK_REQUIRE(!gpool || (gpool_ld % 8 == 0 && gpool_coff % 8 == 0 && gpool_coff >= 0 && gpool_coff + 64 <= gpool_ld), "flk_maxpool3d_bwd_conv1x1: bad gpool ld / coff");
+  PoolConvBP p{};
+  fill(p.k, a);
+  p.k.in = nullptr; p.k.out = nullptr;
+  p.k.gin = (char*)gin; p.k.gin_ld = gin_ld; p.k.gin_coff = gin_coff;
+  p.w = (const char*)wb->dev; p.g = (const char*)g; p.g_ld = g_ld; p.g_coff = g_coff;
+  p.gp = (char*)gpool; p.gp_ld = gpool_ld; p.gp_coff = gpool_coff;
+  // the box: 8 x 32 or 16 x 16 windows, whichever covers the frame in fewer boxes
+  const long n832 = (long)((a->Ho + 7) / 8) * ((a->Wo + 31) / 32), n1616 = (long)((a->Ho + 15) / 16) * ((a->Wo + 15) / 16);
+  if (n832 <= n1616) { p.Hb = 8; p.Wb = 32; p.lgWb = 5; } else { p.Hb = 16; p.Wb = 16; p.lgWb = 4; }
+  p.nTh = (a->Ho + p.Hb - 1) / p.Hb; p.nTw = (a->Wo + p.Wb - 1) / p.Wb;
+  const int nfrag = ((p.Hb + 1) * (p.Wb + 1) + 15) / 16;
+  FLK_REQUIRE(nfrag <= POOL_CONV_BWD_MAXFRAG, "flk_maxpool3d_bwd_conv1x1: box too large");
+  const long grid = (long)a->B * a->To * p.nTh * p.nTw;
+  FLK_REQUIRE(grid < (1l << 31), "flk_maxpool3d_bwd_conv1x1: grid too large");
+  FLK_LAUNCH_KERNEL(maxpool133_conv1x1_bwd, dim3((unsigned)grid), dim3(256), (size_t)nfrag * 16 * 128, (hipStream_t)stream, p);
+  flk_last_kernel_tag = "maxpool133_conv1x1_bwd";
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

@@ -215,6 +215,56 @@ def maxpool3d_bwd_gemm(ctx, g, weights, g_coff=0, *, gin=None, gin_coff=0):
     return gin
 
 
+def maxpool3d_conv1x1_eligible(shape, C_, cin, cout, dtype, *, k=(1, 3, 3), s=(1, 2, 2), has_mask=False):
+    """host-only: do the fused MaxPool3d_2a + Conv3d_2b kernels take a k / s SAME pool over C_ channels of a [B,T,H,W] grid followed by a
+    1x1x1 cin -> cout unit?  (flk_maxpool3d_conv1x1_eligible; no GPU needed)"""
+    B, Ti, Hi, Wi = shape
+    a = PoolArgs()
+    a.C = C_
+    a.B, a.Ti, a.Hi, a.Wi = B, Ti, Hi, Wi
+    a.kt, a.kh, a.kw = k
+    a.st, a.sh, a.sw = s
+    (a.To, a.pt), (a.Ho, a.ph), (a.Wo, a.pw) = (same_pad(n, kk, ss) for n, kk, ss in zip((Ti, Hi, Wi), k, s))
+    return bool(load().flk_maxpool3d_conv1x1_eligible(C.byref(a), cin, cout, int(has_mask), dtype_code(dtype)))
+
+
+def maxpool3d_conv1x1(x, w, *, scale=None, bias=None, relu=False, relu_input=False, in_coff=0, out=None, out_coff=0, pool_out=None,
+                      pool_out_coff=0):
+    """(1,3,3) / (1,2,2) SAME max-pool of channels [in_coff, in_coff + 64) of x followed by the 1x1x1 unit w (64 -> 64) in ONE kernel
+    (flk_maxpool3d_fwd_conv1x1).  Returns (out, idx, ctx): out[..., out_coff:out_coff+64] the unit's output, idx the pool's argmax bytes,
+    ctx for maxpool3d_bwd / maxpool3d_bwd_conv1x1.  pool_out: a buffer whose channels [pool_out_coff, +64) also receive the pooled map."""
+    B, Ti, Hi, Wi, ld = x.shape
+    k, s = (1, 3, 3), (1, 2, 2)
+    og, pad = zip(*(same_pad(n, kk, ss) for n, kk, ss in zip((Ti, Hi, Wi), k, s)))
+    if out is None:
+        out = torch.empty((B, *og, 64 + out_coff), dtype=x.dtype, device=x.device)
+    idx = torch.empty((B, *og, 64), dtype=torch.uint8, device=x.device)
+    assert tuple(out.shape[:4]) == (B, *og) and out.dtype == x.dtype
+    assert pool_out is None or (tuple(pool_out.shape[:4]) == (B, *og) and pool_out.dtype == x.dtype)
+    a = _pool_args(x, 64, k, s, pad, out if pool_out is None else pool_out, idx, in_coff, pool_out_coff)
+    if pool_out is None:
+        a.out, a.out_ld, a.out_coff = None, 64, 0
+    a.relu_input = int(relu_input)
+    check(load().flk_maxpool3d_fwd_conv1x1(C.byref(a), w.handle, ptr(scale), ptr(bias), int(relu), ptr(out), out.shape[4], out_coff,
+                                           int(pool_out is not None), dtype_code(x.dtype), stream_ptr()))
+    return out, idx, (x, 64, k, s, pad, out if pool_out is None else pool_out, idx, in_coff, pool_out_coff)
+
+
+def maxpool3d_bwd_conv1x1(ctx, g, wb, *, g_coff=0, gin=None, gin_coff=0, gpool=None, gpool_coff=0):
+    """the 1x1x1 unit's data-gradient (wb: its transposed weights, 64 -> 64, no mask) followed by the (1,3,3) / (1,2,2) MaxPool3DGrad in ONE
+    kernel (flk_maxpool3d_bwd_conv1x1): g[..., g_coff:g_coff+64] -> gin[..., gin_coff:gin_coff+64].  gpool: a buffer whose channels
+    [gpool_coff, +64) also receive the pooled map's gradient.  ctx from maxpool3d or maxpool3d_conv1x1."""
+    x, C_, k, s, pad, out, idx, in_coff, out_coff = ctx
+    if gin is None:
+        gin = torch.empty((*x.shape[:4], C_ + gin_coff), dtype=x.dtype, device=x.device)
+    assert gin.shape[:4] == x.shape[:4] and gin.dtype == x.dtype and g.shape[:4] == idx.shape[:4]
+    assert gpool is None or (gpool.shape[:4] == idx.shape[:4] and gpool.dtype == x.dtype)
+    a = _pool_args(x, C_, k, s, pad, out, idx, in_coff, out_coff)
+    check(load().flk_maxpool3d_bwd_conv1x1(C.byref(a), ptr(g), g.shape[4], g_coff, wb.handle, ptr(gin), gin.shape[4], gin_coff, ptr(gpool),
+                                           0 if gpool is None else gpool.shape[4], gpool_coff, dtype_code(x.dtype), stream_ptr()))
+    return gin
+
+
 I3D_FOLD = 3   # space-to-depth layout the I3D plan (flk_net, FLK_NET_I3D) expects: chunk-aligned (t,h,w) fold
 
 

@@ -188,6 +188,30 @@ int flk_pool_gemm_weights_destroy(void* dev);
 int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int g_ld, int g_coff, int K, const void* wpack,
                            void* gin, int gin_ld, int gin_coff, int dtype, void* stream);
 
+/* MaxPool3d_2a_3x3 with Conv3d_2b_1x1 inside (i3d.py:174-180), one kernel per pass, bf16 only.  The pooled map and its gradient each have
+ * one consumer -- the 1x1x1 unit and its data-gradient -- so run inside the pool kernels neither crosses HBM.
+ *
+ * flk_maxpool3d_conv1x1_eligible: host-only (no device work, never sets flk_last_error).  1 when the two entry points below take the pair:
+ * dtype bf16; window (1,3,3), stride (1,2,2) over even H and W (SAME pad-before 0) and passing the owner-form backward's conditions;
+ * a->C == cin == cout == 64 (exactly two 32-channel slabs); has_mask == 0 (the unit's data-gradient carries no ReLU mask: the pooled map
+ * is not a ReLU output).  0 otherwise.  Only the geometry fields of `a` are read.
+ *
+ * flk_maxpool3d_fwd_conv1x1: out[pos, out_coff + n] = epilogue(sum_c maxpool(in)[pos, c] * W[c, n]) with flk_conv3d's epilogue
+ * (scale, bias, relu; each optional); a->idx receives the argmax bytes.  w: the unit's forward weights (flk_conv_weights_create, 1x1x1,
+ * 64 -> 64, nf 2 or 4).  write_pool != 0: the pooled map is also written to a->out (else a->out is not touched and may be NULL).
+ * out and idx -- and a->out where written -- are BITWISE what flk_maxpool3d_fwd followed by flk_conv3d write.
+ *
+ * flk_maxpool3d_bwd_conv1x1: gin = MaxPool3DGrad(idx, Gp) with Gp[pos, c] = bf16(sum_k g[pos, g_coff + k] * Wb[k, c]); wb: the unit's
+ * data-gradient weights (transpose = 1, batch-norm scale folded in).  gpool != NULL: Gp is also written there.  gin -- and gpool -- are
+ * BITWISE what flk_conv3d (data-gradient, no mask) followed by flk_maxpool3d_bwd write.  No atomics, every cell written once.
+ *
+ * Both entry points return FLK_EINVAL with the reason for anything the query refuses. */
+int flk_maxpool3d_conv1x1_eligible(const flk_pool_args* a, int cin, int cout, int has_mask, int dtype);
+int flk_maxpool3d_fwd_conv1x1(const flk_pool_args* a, const flk_conv_weights* w, const float* scale, const float* bias, int relu,
+                              void* out, int out_ld, int out_coff, int write_pool, int dtype, void* stream);
+int flk_maxpool3d_bwd_conv1x1(const flk_pool_args* a, const void* g, int g_ld, int g_coff, const flk_conv_weights* wb,
+                              void* gin, int gin_ld, int gin_coff, void* gpool, int gpool_ld, int gpool_coff, int dtype, void* stream);
+
 /* Perturbation apply fused with the stem's space-to-depth staging.
  * kinetics_i3d_utils.py:100-142:  x_adv = clip(x + a * clip(delta[t,c], +-dclip), lo, hi)
  * model.py:80-101 (torch dialect): same with delta/std[c] and scalar clamp bounds.
