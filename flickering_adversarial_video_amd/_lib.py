@@ -56,6 +56,11 @@ class ApplyArgs(C.Structure):
                 ("delta_per_clip", C.c_int), ("dclip_dev", C.c_void_p), ("x_lut", C.c_void_p)]
 
 
+class ExportArgs(C.Structure):
+    _fields_ = [("mul", C.c_float * 3), ("add", C.c_float * 3), ("levels", C.c_float), ("delta_T", C.c_int),
+                ("out_clip_offset", C.c_int64), ("out_clip_stride", C.c_int64)]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [("T", C.c_int), ("torch_dialect", C.c_int),
                 ("beta0", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("beta3", C.c_float),
@@ -112,6 +117,7 @@ _SIGS = {
     "flk_maxpool3d_bwd_conv1x1": (C.c_int, [C.POINTER(PoolArgs), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "flk_perturb_apply_s2d": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p]),
+    "flk_adv_export_u8": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(ExportArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),

@@ -28,7 +28,9 @@ DEFAULT_MODEL = {"FRAMES": 90, "DTYPE": "bf16", "WEIGHTS_NPZ": ""}
 ATTACK_SECTIONS = ("SINGLE_VIDEO_ATTACK", "CLASS_GEN_ATTACK", "UNIVERSAL_ATTACK")
 # [new] per attack section: OPTIMIZER adam (the reference's) | pgd (projected sign-gradient); PGD_EPS: its l-infinity radius
 # (None: 0.4, the apply clip, for the flickering perturbation; required for the dense one)
-DEFAULT_ATTACK = {"OPTIMIZER": "adam", "PGD_EPS": None}
+# SAVE_ADV_U8: also store the adversarial clip as 8-bit frames (uint8, one kernel launch); EVAL_QUANTISED: also score those frames -- is
+# the STORED video still adversarial?  Both off by default: the result files then keep the reference's keys
+DEFAULT_ATTACK = {"OPTIMIZER": "adam", "PGD_EPS": None, "SAVE_ADV_U8": False, "EVAL_QUANTISED": False}
 OPTIMIZERS = ("adam", "pgd")
 
 

@@ -323,6 +323,138 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   return FLK_OK;
 }
 
+// ---- 8-bit export: x_adv of the apply kernels encoded to the bytes of a frame (include/flicker_hip.h) ---------------------------
+// y = x_adv * mul + add; z = y * levels; q = z >= 0 ? min(rint(z), 255) : 0 -- every operation rounded on its own; NaN -> 0
+__device__ static inline int encode_q(float v, float mul, float add, float levels) {
+  const float z = __fmul_rn(__fadd_rn(__fmul_rn(v, mul), add), levels);
+  return z >= 0.f ? (int)fminf(rintf(z), 255.f) : 0;
+}
+// one value of the clip, as load6 decodes it: byte `by` of channel c
+__device__ static inline float decode1(const flk_apply_args& a, uint32_t by, int c) {
+  return a.x_lut ? a.x_lut[by * 3 + c] : (float)by * a.x_scale + a.x_bias;
+}
+
+// Work item = (clip b, frame t, chunk of 256 units of that frame); one thread = one unit of the DESTINATION frame: unit 0 the bytes in
+// front of its first 4-byte boundary (0..3), units 1..nw its aligned words, unit nw + 1 the bytes behind the last whole word (0..3).
+// A word is built in a register and stored once; the source is read as one word / float4 where it is aligned too, else per value.
+// Workgroups stride over the items, so the bytes do not depend on the grid.  STATS: per item the 12 sums (3 channels x 4 statistics)
+// are reduced in the wave, then through LDS, and thread k adds sum k to stats[b][t][k] with one integer atomic.
+template <bool STATS>
+__global__ __launch_bounds__(256) void adv_export_u8_kernel(const flk_apply_args a, const flk_export_args e, uint8_t* out, int32_t* stats, int chunks,
+                                                            long nitems) {
+  flk_apply_args ap = a;          // what pert_at sees: the perturbation's own period
+  ap.T = e.delta_T;
+  const int F = a.H * a.W * 3;
+  __shared__ int red[4][12];
+  for (long item = blockIdx.x; item < nitems; item += gridDim.x) {
+    long r = item;
+    const int chunk = (int)(r % chunks); r /= chunks;
+    const int t = (int)(r % a.T);
+    const int b = (int)(r / a.T);
+    uint8_t* dst = out + (size_t)(e.out_clip_offset + b) * (size_t)e.out_clip_stride + (size_t)t * F;
+    int head = (4 - (int)((uintptr_t)dst & 3)) & 3;
+    if (head > F) head = F;
+    const int nw = (F - head) >> 2, tail = (F - head) & 3;
+    const int u = chunk * 256 + (int)threadIdx.x;
+    int start = 0, cnt = 0;
+    if (u == 0) cnt = head;
+    else if (u <= nw) { start = head + 4 * (u - 1); cnt = 4; }
+    else if (u == nw + 1) { start = head + 4 * nw; cnt = tail; }
+    int acc[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
+    if (cnt > 0) {
+      const int tx = wrap(t - a.shift_x, a.T);      // x'[t] = x[(t - shift_x) mod T]
+      const size_t soff = ((size_t)b * a.T + tx) * F + start;
+      int pix = start / 3, c = start - pix * 3;
+      int h = pix / a.W, w = pix - h * a.W;
+      float pvf[3] = {0.f, 0.f, 0.f};
+      if (!a.delta_dense) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) pvf[k] = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, 0, 0, k) : 0.f;
+      }
+      uint32_t by[4] = {0, 0, 0, 0};
+      float xs[4] = {0.f, 0.f, 0.f, 0.f};
+      if (a.x_is_u8) {
+        const uint8_t* s = (const uint8_t*)a.x + soff;
+        if (cnt == 4 && ((uintptr_t)s & 3) == 0) {
+          const uint32_t v = *(const uint32_t*)s;
+          by[0] = v & 255; by[1] = (v >> 8) & 255; by[2] = (v >> 16) & 255; by[3] = v >> 24;
+        } else {
+          for (int j = 0; j < cnt; ++j) by[j] = s[j];
+        }
+      } else {
+        const float* s = (const float*)a.x + soff;
+        if (cnt == 4 && ((uintptr_t)s & 15) == 0) {
+          const float4 v = *(const float4*)s;
+          xs[0] = v.x; xs[1] = v.y; xs[2] = v.z; xs[3] = v.w;
+        } else {
+          for (int j = 0; j < cnt; ++j) xs[j] = s[j];
+        }
+      }
+      uint32_t packed = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (j < cnt) {
+          const float x = a.x_is_u8 ? decode1(a, by[j], c) : xs[j];
+          float pv;
+          if (a.delta_dense) pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, h, w, c) : 0.f;
+          else pv = c == 0 ? pvf[0] : c == 1 ? pvf[1] : pvf[2];
+          const float mul = c == 0 ? e.mul[0] : c == 1 ? e.mul[1] : e.mul[2];
+          const float add = c == 0 ? e.add[0] : c == 1 ? e.add[1] : e.add[2];
+          const int q = encode_q(applied(a, x, pv), mul, add, e.levels);
+          if (cnt == 4) packed |= (uint32_t)q << (8 * j);
+          else dst[start + j] = (uint8_t)q;
+          if constexpr (STATS) {
+            const int qc = a.x_is_u8 ? (int)by[j] : encode_q(x, mul, add, e.levels);
+            const int d = q - qc;
+            // the sum applied() clamps.  Exactly that sum for adv_flag 0 or 1 (adv_flag * p is then exact, so a contraction at either site
+            // changes nothing); for other adv_flag values the two sites may round adv_flag * p + x differently in the last bit
+            const float uu = x + pv;
+            const int cl = (uu < a.lo || uu > a.hi) ? 1 : 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+              if (c == k) { acc[k][0] += d; acc[k][1] += d < 0 ? -d : d; acc[k][2] += d != 0; acc[k][3] += cl; }
+          }
+          if (++c == 3) { c = 0; if (++w == a.W) { w = 0; ++h; } }
+        }
+      }
+      if (cnt == 4) *(uint32_t*)(dst + start) = packed;
+    }
+    if constexpr (STATS) {
+#pragma unroll
+      for (int k = 0; k < 12; ++k) {
+        int v = acc[k >> 2][k & 3];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
+      }
+      __syncthreads();
+      if (threadIdx.x < 12) {
+        const int s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (s != 0) atomicAdd(stats + ((size_t)b * a.T + t) * 12 + threadIdx.x, s);
+      }
+      __syncthreads();            // red is reused by the next item
+    }
+  }
+}
+
+// arguments checked by flk_adv_export_u8 (api.cpp)
+int flk_adv_export_u8_launch(const flk_apply_args* a, const flk_export_args* e, uint8_t* out, int32_t* stats, hipStream_t stream) {
+  flk_export_args ee = *e;
+  if (ee.delta_T == 0) ee.delta_T = a->T;
+  const int F = a->H * a->W * 3;
+  const int chunks = (F / 4 + 2 + 255) / 256;       // units of a frame: at most F / 4 words, a head and a tail
+  const long nitems = (long)a->B * a->T * chunks;
+  const unsigned grid = (unsigned)(nitems > (1L << 20) ? (1L << 20) : nitems);
+  if (stats) {
+    FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->B * a->T * 12 * sizeof(int32_t), stream));
+    FLK_LAUNCH_KERNEL(adv_export_u8_kernel<true>, dim3(grid), dim3(256), 0, stream, *a, ee, out, stats, chunks, nitems);
+  } else {
+    FLK_LAUNCH_KERNEL(adv_export_u8_kernel<false>, dim3(grid), dim3(256), 0, stream, *a, ee, out, stats, chunks, nitems);
+  }
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
 // ---- delta gradient --------------------------------------------------------------------------
 // stage 1: workgroup (b, t2, chunk of h2 rows) -> partials[wg][qt][c] = sum over its cells of
 //          g * 1[lo <= x' + a p' <= hi]      (both clip gradients are inclusive at the bounds)

@@ -199,10 +199,10 @@ def main(default_section, argv=None):
             return x, ops.mark_labels_validated(torch.full_like(y, target_id), len(classes))      # target_id = classes.index(...)
         return x, y
 
-    def evaluate():
+    def evaluate(quantise=False):
         it = (to_dev(b, true_labels=True) for b in prefetch.DeviceBatches(val_files, B, T, rank, world))
         # the reference evaluates with cyclic=0 (single_class_gen.py:202,340)
-        return eng.evaluate(it, bool(c.TARGETED_ATTACK), target_id, cyclic=0.0)
+        return eng.evaluate(it, bool(c.TARGETED_ATTACK), target_id, cyclic=0.0, quantise=quantise)
 
     def save_checkpoint():
         if rank != 0:
@@ -228,6 +228,11 @@ def main(default_section, argv=None):
             if tb_eval is not None:
                 tb_eval.add_scalars(step, {"ACC: 1- FOOLING_RATIO": 1.0 - rate})
                 tb_eval.flush()
+        if c.EVAL_QUANTISED:                           # [new] the same pass over the perturbed clips written as 8-bit frames
+            qrate, _ = evaluate(quantise=True)
+            lists.setdefault("fool_rate_quantised", []).append(qrate)
+            if rank == 0:
+                print("step: {:05d} ,fool_rate as 8-bit frames: {:.5f}".format(step, qrate), flush=True)
         return rate
 
     if val_files and not universal:
@@ -280,6 +285,8 @@ def main(default_section, argv=None):
             res = {k: lists[k] for k in ("total_loss_l", "adv_loss_l", "reg_loss_l", "norm_reg_loss_l", "diff_norm_reg_loss_l", "perturbation",
                                          "fatness", "smoothness", "fool_rate")}
             res.update(total_steps=step, beta_1=c.BETA_1, beta_2=c.BETA_2)            # the keys of single_class_gen.py:353-367
+            if c.EVAL_QUANTISED:
+                res["fool_rate_quantised"] = lists.get("fool_rate_quantised", [])
             with open(os.path.join(out_dir, "res.pkl"), "wb") as f:
                 pickle.dump(res, f)
         if world > 1:
@@ -287,6 +294,9 @@ def main(default_section, argv=None):
     if rank == 0 and universal:
         # Estimator PREDICT mode returns the perturbation (universal.py:112-117): keep it beside the checkpoints
         np.save(os.path.join(out_dir, "perturbation.npy"), eng.perturbation.cpu().numpy())
+    if rank == 0 and c.SAVE_ADV_U8 and getattr(eng, "_last_x", None) is not None:
+        # [new] the last clip seen under the final perturbation, as the 8-bit frames a video file holds: uint8 [B,T,224,224,3]
+        np.save(os.path.join(out_dir, "adversarial_inputs_u8.npy"), eng.adversarial_inputs_u8.cpu().numpy())
     if world > 1:
         torch.distributed.destroy_process_group()
     return eng

@@ -425,6 +425,30 @@ class FlickerI3D:
         B, T2, H2, W2 = f.shape[:4]
         return f[..., :24].reshape(B, T2, H2, W2, 2, 2, 2, 3).permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, 2 * T2, 2 * H2, 2 * W2, 3).contiguous()
 
+    def _export_u8(self, x, adv_flag, sx, sp, dclip, stats=False):
+        """x perturbed by the current eps_rgb under the rolls (sx, sp), written as 8-bit frames uint8 [B,T,H,W,3] (``u8 = rint(128 * (x_adv + 1))``
+        saturated to 0..255: the inverse of the TFRecord decode) -- one launch of flk_adv_export_u8"""
+        a = ops.make_export_apply_args(x, self.eps_rgb, dialect="tf", dclip=dclip, adv_flag=adv_flag, shift_x=sx, shift_p=sp)
+        return ops.export_adversarial_u8(a, "tf", stats=stats)
+
+    @property
+    def adversarial_inputs_u8(self):
+        """``adversarial_inputs_rgb`` as the 8-bit frames a file holds: uint8 [B,T,224,224,3] of the last clip seen, under the CURRENT
+        perturbation and the last call's rolls, written by one kernel (no fp32 clip, no unfold)"""
+        if getattr(self, "_last_x", None) is None:
+            raise AttributeError("adversarial_inputs_u8: no clip has been seen yet")
+        sx, sp = self._last_shifts
+        return self._export_u8(self._last_x, 1.0, sx, sp, 0.0 if self.dense else 0.4)
+
+    def quantised_logits(self, x, cyclic=None):
+        """the logits of the STORED adversarial clip: x perturbed (adv_flag 1, the roll ``cyclic`` asks for) and written as 8-bit frames,
+        which then take the existing uint8 path with adv_flag = 0"""
+        x = self._check_x(x)
+        sx = int(self._rng.integers(0, self.T)) if (self.cyclic_flag if cyclic is None else cyclic) else 0
+        out = self.logits(self._export_u8(x, 1.0, sx, 0, 0.0 if self.dense else 0.4), 0.0, 0)
+        self._last_x, self._last_shifts = x, (sx, 0)         # the clip seen is x, not its frames: adversarial_inputs_* keep describing x
+        return out
+
     def delta_gradient(self):
         """last all-reduced adversarial gradient d(adv)/d(delta), [T,3] ([B,T,3] in per-clip mode)"""
         if self.per_clip:
@@ -432,12 +456,13 @@ class FlickerI3D:
         return self._red[:self.T * 3].view(self.T, 3)
 
     # ---- fooling rate --------------------------------------------------------------------------------
-    def evaluate(self, batches, targeted_attack=False, target_class_id=None, cyclic=0, exclude_misclassify=True):
+    def evaluate(self, batches, targeted_attack=False, target_class_id=None, cyclic=0, exclude_misclassify=True, quantise=False):
         """kinetics_i3d.evaluate (kinetics_i3d_utils.py:217-250) over an iterable of (clip, labels) batches.
-        Returns (miss_rate, total_valid) aggregated over all ranks."""
+        Returns (miss_rate, total_valid) aggregated over all ranks.  ``quantise``: the adversarial prediction is taken from the
+        perturbed clip written as 8-bit frames (``quantised_logits``) -- the fooling rate of the attack as a video delivers it."""
         cnt = parallel.FoolingCounter(self.eps_rgb.device)
         for x, y in batches:
-            adv = self.logits(x, 1.0, cyclic).argmax(-1)
+            adv = (self.quantised_logits(x, cyclic) if quantise else self.logits(x, 1.0, cyclic)).argmax(-1)
             clean = self.logits(x, 0.0, 0).argmax(-1) if exclude_misclassify else None
             cnt.update(adv, clean, y, targeted_attack, target_class_id, exclude_misclassify)
         return cnt.result(self.pg)
@@ -453,10 +478,15 @@ class FlickerI3DInference(FlickerI3D):
         """load eps_rgb ([T,1,1,3] or [T,3]), e.g. ``tf_checkpoint.read_bundle(ckpt)['RGB/eps']``"""
         self.reset_perturbation(delta)
 
-    def __call__(self, inputs, adv_flag=0, cyclic_input_flag=0, cyclic_eps_flag=0):
+    def __call__(self, inputs, adv_flag=0, cyclic_input_flag=0, cyclic_eps_flag=0, quantise=False):
+        """``quantise``: the perturbed (and rolled) clip is written as 8-bit frames first and those are scored with adv_flag = 0"""
         x = self._check_x(inputs)
         self.last_shift_x = int(self._rng.integers(0, self.T)) if cyclic_input_flag else 0
         self.last_shift_p = int(self._rng.integers(0, self.T)) if cyclic_eps_flag else 0
+        if quantise:
+            frames = self._export_u8(x, float(adv_flag), self.last_shift_x, self.last_shift_p, 0.0)
+            a = ops.make_apply_args(frames, self.eps_rgb, dialect="tf", dclip=0.0, adv_flag=0.0, fold_t=ops.I3D_FOLD, center=self.exact_delta_forward)
+            return torch.softmax(self._forward(a), -1)
         a = ops.make_apply_args(x, self.eps_rgb, dialect="tf", dclip=0.0, adv_flag=float(adv_flag), shift_x=self.last_shift_x,
                                 shift_p=self.last_shift_p, fold_t=ops.I3D_FOLD, center=self.exact_delta_forward)
         return torch.softmax(self._forward(a), -1)

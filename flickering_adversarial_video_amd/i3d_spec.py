@@ -74,6 +74,18 @@ def synthetic_clip_u8(B, T, H=224, W=224, seed=1234):
     return np.random.default_rng(seed).integers(0, 256, (B, T, H, W, 3), dtype=np.uint8)
 
 
+def encode_u8(x):
+    """fp32 values in the TFRecord range -> the bytes of a frame, the inverse of ``u8 / 128 - 1``: ``y = x * 1 + 1; z = y * 128;
+    q = min(rint(z), 255) where z >= 0, else 0`` in float32, one rounded operation per step (rint: half to even; NaN -> 0) -- the
+    arithmetic of flk_adv_export_u8 in the TF dialect, restated on the host.  (+1 encodes to 255: there is no byte 256.)"""
+    y = np.asarray(x, dtype=np.float32) * np.float32(1.0)
+    y = y + np.float32(1.0)
+    z = y * np.float32(128.0)
+    with np.errstate(invalid="ignore"):
+        q = np.where(z >= 0, np.minimum(np.rint(z), np.float32(255.0)), np.float32(0.0))
+    return q.astype(np.uint8)
+
+
 def load_i3d_weights(model_cfg):
     """Weights for FlickerI3D from the MODEL section of run_config.yml: ``WEIGHTS_NPZ`` ({variable name: array} archive) if
     set, else the TF checkpoint ``CKPT_PATH`` (the reference's ``init_model``, kinetics_i3d_utils.py:41-62, read without

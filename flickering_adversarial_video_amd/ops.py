@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, LossArgs, PoolArgs, PrepareArgs, PrepBox,
+from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, ExportArgs, LossArgs, PoolArgs, PrepareArgs, PrepBox,
                    PrepClip, check, dtype_code, load, ptr, stream_ptr, torch_dtype)
 from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, prepare_geometry
 
@@ -313,6 +313,122 @@ def perturb_apply_s2d(args, dtype, out=None):
                           device="cuda")
     check(load().flk_perturb_apply_s2d(C.byref(args), ptr(out), dtype_code(dtype), stream_ptr()))
     return out
+
+
+# 8-bit export (flk_adv_export_u8): dialect -> (mul[3], add[3], levels), the inverse of the dialect's decode
+EXPORT_DIALECTS = {"torch": (DEFAULT_STD, DEFAULT_MEAN, 255.0),          # inverse of (u8 / 255 - mean) / std
+                   "tf": ((1.0, 1.0, 1.0), (1.0, 1.0, 1.0), 128.0)}      # inverse of u8 / 128 - 1
+
+
+def make_export_args(dialect, out_clip_stride, out_offset=0, delta_T=0):
+    """flk_export_args of a dialect: clip b of the call goes to row ``out_offset + b`` of a buffer whose rows are ``out_clip_stride``
+    bytes apart; ``delta_T``: the period of a flicker perturbation [delta_T,3] laid over a longer (or shorter) clip, 0 = the clip's T"""
+    if dialect not in EXPORT_DIALECTS:
+        raise ValueError(f"dialect must be one of {sorted(EXPORT_DIALECTS)}, got {dialect!r}")
+    mul, add, levels = EXPORT_DIALECTS[dialect]
+    e = ExportArgs()
+    e.mul, e.add, e.levels = (C.c_float * 3)(*mul), (C.c_float * 3)(*add), levels
+    e.delta_T, e.out_clip_offset, e.out_clip_stride = int(delta_T), int(out_offset), int(out_clip_stride)
+    return e
+
+
+def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0), lo=-1.0, hi=1.0,
+                           dclip_dev=None, x_lut=None, delta_T=0):
+    """the flk_apply_args of an 8-bit export: ``make_apply_args`` without a fold (T, H and W may be odd) and, with ``delta_T``, with a
+    flicker perturbation [delta_T,3] whose length is its period instead of the clip's T.  (The fields are filled as ``make_apply_args``
+    fills them -- a change to one belongs in the other; only the fold, ``center`` and the shape rule of ``delta`` differ.)  The period is
+    remembered on the result (``_delta_T``): ``export_adversarial_u8`` takes it from there."""
+    B, T, H, W, c3 = x.shape
+    assert c3 == 3 and x.is_contiguous() and x.is_cuda and delta.is_contiguous() and delta.is_cuda and delta.dtype == torch.float32
+    assert x.dtype in (torch.uint8, torch.float32) and min(B, T, H, W) > 0
+    if x_lut is not None:
+        assert x.dtype == torch.uint8 and x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda
+    assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
+    if delta_T:
+        assert tuple(delta.shape) == (int(delta_T), 3), f"delta_T = {delta_T}: the perturbation must be [{delta_T},3], got {tuple(delta.shape)}"
+    else:
+        assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
+    a = ApplyArgs()
+    a.x, a.x_is_u8 = ptr(x), int(x.dtype == torch.uint8)
+    a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
+    a.delta, a.delta_dense, a.delta_per_clip = ptr(delta), int(delta.dim() == 4), int(delta.dim() == 3)
+    a.dclip = float(dclip)
+    a.inv_std = (C.c_float * 3)(*inv_std)
+    a.lo, a.hi, a.adv_flag = float(lo), float(hi), float(adv_flag)
+    a.shift_x, a.shift_p = int(shift_x), int(shift_p)
+    a.B, a.T, a.H, a.W = B, T, H, W
+    if dclip_dev is not None:
+        assert a.delta_per_clip and dclip_dev.dtype == torch.float32 and dclip_dev.shape == (B,) and dclip_dev.is_cuda
+    a.dclip_dev, a.x_lut = ptr(dclip_dev), ptr(x_lut)
+    a._keepalive = (x, delta, dclip_dev, x_lut)   # the struct holds raw pointers only
+    a._delta_T = int(delta_T)                     # the kernel must wrap by the length delta really has
+    return a
+
+
+def export_adversarial_u8(args, dialect="tf", out=None, out_offset=0, stats=False, delta_T=None):
+    """the perturbed clip of ``args`` (make_export_apply_args, or make_apply_args: the fold is ignored) as uint8 frames [B,T,H,W,3] in one
+    launch (flk_adv_export_u8).  ``out``: a contiguous CUDA uint8 buffer [>= out_offset + B, T, H, W, 3] whose rows ``out_offset ...`` are
+    written (the others are left alone); without it a tensor [B,T,H,W,3] is allocated.  Returns the rows written; with ``stats`` also the
+    int32 [B,T,3,4] table of per (clip, frame, channel) sums: q - q_clean, |q - q_clean|, [q != q_clean], [clamp active].
+    ``delta_T``: the period the arguments were built with (default); naming another one is an error -- the kernel would read past a
+    perturbation of ``delta_T`` rows."""
+    B, T, H, W = args.B, args.T, args.H, args.W
+    built = getattr(args, "_delta_T", 0)
+    if delta_T is None:
+        delta_T = built
+    if int(delta_T) != built:
+        raise ValueError(f"export_adversarial_u8: delta_T = {delta_T}, but the arguments were built for delta_T = {built}")
+    dev = args._keepalive[0].device
+    if out is None:
+        out = torch.empty((out_offset + B, T, H, W, 3), dtype=torch.uint8, device=dev)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 5
+            or tuple(out.shape[1:]) != (T, H, W, 3) or out_offset < 0 or out.shape[0] < out_offset + B):
+        desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"export_adversarial_u8: out must be a contiguous CUDA uint8 tensor [>= {out_offset + B},{T},{H},{W},3], got {desc}")
+    e = make_export_args(dialect, T * H * W * 3, out_offset, delta_T)
+    st = torch.empty((B, T, 3, 4), dtype=torch.int32, device=dev) if stats else None
+    check(load().flk_adv_export_u8(C.byref(args), C.byref(e), ptr(out), ptr(st), stream_ptr()))
+    rows = out[out_offset:out_offset + B]
+    return (rows, st) if stats else rows
+
+
+def encode_u8_host(v, dialect):
+    """numpy float32 restatement of the encode of flk_adv_export_u8 (one rounded operation per step): fp32 [...,3] -> uint8"""
+    from . import i3d_spec, videoresnet_spec
+    return {"torch": videoresnet_spec.encode_u8, "tf": i3d_spec.encode_u8}[dialect](v)
+
+
+def export_adversarial_u8_host(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0), lo=-1.0, hi=1.0,
+                               dclip_clip=None, x_lut=None, delta_T=0, stats=False):
+    """the host A/B route of ``export_adversarial_u8``: the same arithmetic in numpy float32, one rounded operation per step (exact for
+    adv_flag 0 / 1, where no contraction can change the apply).  x: uint8 or fp32 [B,T,H,W,3]; delta: [T,3], [B,T,3], [T,H,W,3] or, with
+    ``delta_T``, [delta_T,3]; ``dclip_clip``: per-clip clamp bounds [B]; ``x_lut``: fp32 [256,3].  Returns the frames uint8 [B,T,H,W,3]
+    and, with ``stats``, the int64 [B,T,3,4] sums of flk_adv_export_u8."""
+    x, d = np.asarray(x), np.asarray(delta, dtype=np.float32)
+    B, T = x.shape[:2]
+    f32 = np.float32
+    if x.dtype == np.uint8:
+        xf = np.asarray(x_lut, f32)[x, np.arange(3)] if x_lut is not None else \
+            (x.astype(f32) * (f32(1.0 / 128.0) if dialect == "tf" else f32(1.0)) + (f32(-1.0) if dialect == "tf" else f32(0.0))).astype(f32)
+    else:
+        xf = x.astype(f32)
+    xf, xsrc = np.roll(xf, shift_x, axis=1), np.roll(x, shift_x, axis=1)         # x'[t] = x[(t - shift_x) mod T]
+    rows = (np.arange(T) - shift_p) % (int(delta_T) or T)                        # p'[t] = p[(t - shift_p) mod period]
+    p = d[rows] if d.ndim == 4 else d[:, rows][:, :, None, None, :] if d.ndim == 3 else d[rows][None, :, None, None, :]
+    dc = np.asarray(dclip_clip, f32).reshape(B, 1, 1, 1, 1) if dclip_clip is not None else f32(dclip)
+    if dclip_clip is not None or dclip > 0:
+        p = np.minimum(np.maximum(p, -dc), dc)
+    p = (p * np.array(inv_std, f32)).astype(f32)
+    pv = f32(adv_flag) * p if adv_flag != 0 else np.zeros_like(p)
+    u = (xf + pv).astype(f32)
+    q = encode_u8_host(np.minimum(np.maximum(u, f32(lo)), f32(hi)), dialect)
+    if not stats:
+        return q
+    qc = xsrc if x.dtype == np.uint8 else encode_u8_host(xf, dialect)
+    dq = q.astype(np.int64) - qc.astype(np.int64)
+    active = (u < f32(lo)) | (u > f32(hi))
+    st = np.stack([dq.sum((2, 3)), np.abs(dq).sum((2, 3)), (dq != 0).sum((2, 3)), active.sum((2, 3))], axis=-1)
+    return q, st.astype(np.int64)
 
 
 def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):

@@ -108,6 +108,30 @@ class Perturbation:
                                    dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
                                    x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None)
 
+    def export_args(self, x, adversarial=True, shift_p=0, delta_T=0):
+        """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
+        frames of a cyclic perturbation are exported at the phase ``shift_p`` the caller names"""
+        inf = float("inf")
+        return ops.make_export_apply_args(x, self.perturbation, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
+                                          shift_p=shift_p, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
+                                          lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf,
+                                          dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
+                                          x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None, delta_T=delta_T)
+
+    def export_u8(self, x, adversarial=True, stats=False, out=None, out_offset=0, shift_p=0):
+        """the clip ``forward([x, adversarial])`` makes, as the 8-bit frames a file or a display holds: uint8 ``[B,T,H,W,3]`` on the device,
+        ``rint(255 * (x_adv * std + mean))`` saturated to 0..255 (ops.export_adversarial_u8, one kernel launch; the host route
+        ``apply_perturbation`` goes through the folded fp32 tensor, a permute and numpy).  ``x`` as in ``forward`` (NCDHW or channels-last,
+        fp32 or uint8; any T, H, W -- odd ones too).  ``adversarial=False``: the frames of the clean clip, i.e. a uint8 ``x`` itself.
+        ``stats``: also int32 ``[B,T,3,4]``, per (clip, frame, channel) the sums of q - q_clean, |q - q_clean|, [q != q_clean] and
+        [clamp active]; entry 0 / (H * W) is the flicker the frames really carry, in levels."""
+        ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
+        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
+        xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
+        if xcl.shape[1] != self.T:
+            raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.T}")
+        return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p), "torch", out=out, out_offset=out_offset, stats=stats)
+
     def forward(self, input):
         """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip.  ``x`` is the
         reference's NCDHW tensor [B,3,T,H,W] or the channels-last [B,T,H,W,3] the engine works on; the result has x's layout.  The
@@ -438,7 +462,7 @@ class FlickerVideoResNet:
         return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
                                  rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=np.concatenate(tables))
 
-    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False):
+    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None):
         """``VideoLearnerAdversarial.evaluate(num_samples)`` (model.py:1227-1317) on whole videos resident on the device: every video is
         scored by the argmax of the summed logits of ``num_samples`` clips cut at uniform offsets (the test split: no shift, no jitter)
         and prepared with the evaluation transform.  ``videos``: a list of CUDA uint8 ``[N_k,H_k,W_k,3]``; ``labels``: one class per video.
@@ -451,6 +475,12 @@ class FlickerVideoResNet:
         ``clip_accuracy``; with ``adversarial`` also ``clean_clip_logits``, ``clean_video_logits``, ``clean_clip_preds``,
         ``clean_video_preds``, ``clean_video_accuracy``, ``clean_clip_accuracy`` and ``video_fooling_ratio`` -- among the videos
         classified correctly when clean, the share whose adversarial video prediction differs from the label (nan when there is none).
+        ``quantise`` (implies ``adversarial``): score the attack as it is DELIVERED, in 8 bits per channel.  ``"clip"``: the adversarial
+        logits are those of each prepared clip perturbed and exported to 8-bit frames at the engine's size (``logits(adversarial_frames(x),
+        False)``).  ``"video"``: every whole video is flickered at its native resolution (``export_video``) and scored by the ordinary clean
+        evaluation -- the exported videos are made batch by batch and no more of them are held than one batch needs.  Both add
+        ``realised_flicker``: the mean of (frame byte - source byte) per frame and channel, in levels -- fp64 ``[V * num_samples, T, 3]``
+        ("clip"; the source being the 8-bit encoding of the prepared clip) or a list of ``[N_k, 3]`` per video ("video").
         Known difference from the reference: its loop starts at video 1 (``range(1, len(ds))``, model.py:1279-1281) and so never
         scores the first video; this one evaluates every video."""
         videos = list(videos) if isinstance(videos, (list, tuple)) else None
@@ -467,14 +497,31 @@ class FlickerVideoResNet:
         if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < B:
             self._prep_buf = torch.empty((B, self.T, self.H, self.W, 3), dtype=torch.float32, device=videos[0].device)
         x = self._prep_buf[:B]
-        clean, adv = [], []
+        if quantise not in (None, "clip", "video"):
+            raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
+        adversarial = adversarial or quantise is not None
+        clean, adv, flick = [], [], []
+        exported = {}                                                   # quantise = "video": the flickered videos of the current batch
         for first in range(0, V * S, B):
             ks = [min(first + b, V * S - 1) for b in range(B)]          # the last batch repeats its last clip
             ops.prepare_clips([videos[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
                               frame_idx=rows[ks])
             n = min(B, V * S - first)
             clean.append(self.logits(x, False)[:n].cpu())
-            if adversarial:
+            if quantise == "clip":
+                frames, st = self.adversarial_frames(x, stats=True)
+                adv.append(self.logits(frames, False)[:n].cpu())
+                flick.append(st[:n, :, :, 0].cpu().numpy() / float(self.H * self.W))
+            elif quantise == "video":
+                exported = {v: exported[v] for v in {k // S for k in ks} if v in exported}
+                for v in sorted({k // S for k in ks}):
+                    if v not in exported:
+                        exported[v], st = self.export_video(videos[v], stats=True)
+                        flick.append(st[:, :, 0].cpu().numpy() / float(videos[v].shape[1] * videos[v].shape[2]))
+                ops.prepare_clips([exported[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                  frame_idx=rows[ks])
+                adv.append(self.logits(x, False)[:n].cpu())
+            elif adversarial:
                 adv.append(self.logits(x, True)[:n].cpu())
 
         def score(parts):
@@ -497,6 +544,8 @@ class FlickerVideoResNet:
             clip, video, cp, vp = c_clip, c_video, c_cp, c_vp
         res.update(clip_logits=clip, video_logits=video, clip_preds=cp, video_preds=vp,
                    video_accuracy=float((vp == trues).mean()), clip_accuracy=float((cp == clip_trues).mean()))
+        if quantise is not None:
+            res["realised_flicker"] = np.concatenate(flick) if quantise == "clip" else flick
         return res
 
     def _is_raw(self, x):
@@ -525,6 +574,35 @@ class FlickerVideoResNet:
         """model([x, adversarial]) (model.py:1028,1073)"""
         self._forward(x, adversarial)
         return self._logits
+
+    def adversarial_frames(self, x, out=None, stats=False, adversarial=True):
+        """the perturbed clips as 8-bit frames: uint8 ``[N,T,H,W,3]`` of the engine's perturbation over ``x`` (fp32 or uint8 clips at the
+        engine's size; per-clip engines: N == B), one kernel launch (Perturbation.export_u8).  ``out``: a uint8 buffer to fill.
+        ``stats``: also the int32 ``[N,T,3,4]`` table of ops.export_adversarial_u8.  ``adversarial=False``: the frames of the clean clips."""
+        if x.dim() != 5 or tuple(x.shape[1:]) != (self.T, self.H, self.W, 3) or x.dtype not in CLIP_DTYPES or not x.is_cuda:
+            raise ValueError(f"clips must be CUDA float32 or uint8 channels-last tensors [N,{self.T},{self.H},{self.W},3], got {tuple(x.shape)} {x.dtype}")
+        return self.pert_model.export_u8(x, adversarial, stats=stats, out=out)
+
+    def quantised_logits(self, x, adversarial=True):
+        """the logits of the STORED adversarial video: ``x`` perturbed and written as 8-bit frames (``adversarial_frames``, into a buffer the
+        engine reuses), then scored by the clean uint8 path -- ``logits(frames, False)``"""
+        x = self._check_x(x)
+        if getattr(self, "_q_buf", None) is None:
+            self._q_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.uint8, device=x.device)
+        return self.logits(self.adversarial_frames(x, out=self._q_buf, adversarial=adversarial), False)
+
+    def export_video(self, video_u8, phase=0, stats=False):
+        """the engine's flicker laid over a WHOLE video at its own resolution: ``video_u8`` uint8 ``[N,H,W,3]`` on the device -> uint8
+        ``[N,H,W,3]``, frame n perturbed by row ``(n - phase) mod T`` of the perturbation (period = the engine's T; the flicker is uniform
+        over a frame, so it needs no resize).  One kernel launch.  Flicker attacks with one shared perturbation only.  ``stats``: also the
+        int32 ``[N,3,4]`` table of ops.export_adversarial_u8."""
+        if self.attack_type != "flickering" or self.per_clip:
+            raise ValueError("export_video: the flickering attack with one shared perturbation only (a dense or per-clip perturbation belongs to its clip)")
+        if not torch.is_tensor(video_u8) or video_u8.dim() != 4 or video_u8.dtype != torch.uint8 or video_u8.shape[-1] != 3 or not video_u8.is_cuda or video_u8.shape[0] < 1:
+            raise ValueError("export_video: a CUDA uint8 tensor [N,H,W,3]")
+        a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.T)
+        res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.T)
+        return (res[0][0], res[1][0]) if stats else res[0]
 
     def _check_video_labels(self, labels):
         """clips_per_video > 1: one label per VIDEO"""
@@ -688,8 +766,11 @@ class FlickerVideoResNet:
 
     # ---- drivers around step(): VideoLearnerAdversarial's loops without the plotting ------------------------------------
     def fit_single_video_attack(self, inputs, target, criterion, lr=1e-3, n_iter=3000, targeted_attack=False, target_class_id=None,
-                                restart_after=3000, norm_growth=1.3, max_restarts=4, log_every=0):
+                                restart_after=3000, norm_growth=1.3, max_restarts=4, log_every=0, export_u8=False):
         """``VideoLearnerAdversarial.fit_single_video_attack`` (model.py:984-1205).
+        ``export_u8``: the result also holds ``adv_video_u8`` (the attacked clips under the final perturbation as 8-bit frames, uint8
+        ``[B,T,H,W,3]``), ``quantised_pred`` (the class those frames are given, per clip or -- clips_per_video > 1 -- per video) and
+        ``quantised_is_adversarial`` (is the STORED video still adversarial?); ``export_u8="verdict"`` leaves the frames out.
 
         Returns None when the clean clip is misclassified (model.py:1030-1032).  Otherwise iterates
         ``while step < n_iter or not is_adversarial`` (model.py:1056); whenever ``step > restart_after`` the clamp norm
@@ -739,10 +820,25 @@ class FlickerVideoResNet:
                       f"pert_thickness = {thick_l[-1]:.4f} | pert_roughness = {rough_l[-1]:.4f}", flush=True)
             step += 1
         p = self.pert_model.get_perturbation()[0].cpu().numpy()
-        return {"loss/total": tot, "loss/adv_loss": adv_l, "loss/reg_loss": reg_l, "perturbation/thickness": thick_l,
-                "perturbation/roughness": rough_l, "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": pert_l,
-                "prob_clean_input": outputs_no_adv, "label": target.cpu().numpy(), "is_adversarial": isadv_l,
-                "max_prob": maxp_l, "correct_cls_prob": corr_l, "restarts": new_chance}
+        res = {"loss/total": tot, "loss/adv_loss": adv_l, "loss/reg_loss": reg_l, "perturbation/thickness": thick_l,
+               "perturbation/roughness": rough_l, "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": pert_l,
+               "prob_clean_input": outputs_no_adv, "label": target.cpu().numpy(), "is_adversarial": isadv_l,
+               "max_prob": maxp_l, "correct_cls_prob": corr_l, "restarts": new_chance}
+        if export_u8:
+            frames = self.adversarial_frames(inputs)
+            ql = self.logits(frames, False)
+            res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
+        return res
+
+    @staticmethod
+    def _quantised_verdict(frames, logits, target, targeted_attack, target_class_id, export_u8=True):
+        """the result keys of ``export_u8``: the frames on the host (unless "verdict") and what the network makes of them"""
+        pred = logits.argmax(1)
+        is_adv = bool((pred == target_class_id).all()) if targeted_attack else not bool(pred.equal(target))
+        res = {"quantised_pred": pred.cpu().numpy(), "quantised_is_adversarial": is_adv}
+        if export_u8 != "verdict":
+            res["adv_video_u8"] = frames.cpu().numpy()
+        return res
 
     def train_an_epoch(self, data_loaders, criterion, metric, lr):
         """``train_an_epoch`` (model.py:627-789): 'train' then 'valid' over iterables of (inputs, target, _); the valid phase
@@ -815,7 +911,7 @@ class FlickerVideoResNet:
         return results
 
     def _fit_many_videos_batched(self, videos, criterion, lr, model_dir, label_id_to_text, save_model, n_iter, targeted_attack, target_class_id,
-                                 restart_after=3000, norm_growth=1.3, max_restarts=4, reset_optimizer_per_video=False, log_every=0):
+                                 restart_after=3000, norm_growth=1.3, max_restarts=4, reset_optimizer_per_video=False, log_every=0, export_u8=False):
         """``fit_many_videos`` with B = batch_size videos attacked AT ONCE (engine built with ``per_clip=True``): every slot runs the loop of
         ``fit_single_video_attack`` (model.py:1056-1101: while step < n_iter or not adversarial; restart with 1.3x clamp bound, give up
         after 4) on its own video with its own perturbation / clamp bound / step counters; a finished slot takes the next video.  Per
@@ -884,6 +980,12 @@ class FlickerVideoResNet:
                    "perturbation/roughness": st["rough"], "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": st["pert"],
                    "prob_clean_input": st["clean"], "label": st["target"].cpu().numpy(), "is_adversarial": st["isadv"],
                    "max_prob": st["maxp"], "correct_cls_prob": st["corr"], "restarts": st["new_chance"]}
+            # slot b's frames under its own perturbation, scored by the clean uint8 path.  The plan's batch is fixed, so the clean forward
+            # runs over all B slots and row b is kept: one extra forward per finished video, off the default path
+            if export_u8:
+                frames = self.adversarial_frames(x)
+                res.update(self._quantised_verdict(frames[b:b + 1], self.logits(frames, False)[b:b + 1], st["target"], targeted_attack, target_class_id,
+                                                   export_u8))
             out[st["name"]] = res
             if st["dest"] and save_model:
                 np.save(st["dest"], dict(res, prob_clean_input=res["prob_clean_input"].cpu().numpy()), allow_pickle=True)

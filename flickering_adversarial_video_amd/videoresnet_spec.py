@@ -105,6 +105,18 @@ def u8_decode_table():
     return np.ascontiguousarray(normalize_u8(np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)))
 
 
+def encode_u8(x):
+    """normalised fp32 values [...,3] -> the bytes of a frame, the inverse of ``normalize_u8``: ``y = x * std + mean; z = y * 255;
+    q = min(rint(z), 255) where z >= 0, else 0`` in float32, one rounded operation per step (rint: half to even; NaN -> 0) -- the
+    arithmetic of flk_adv_export_u8 in the torch dialect, restated on the host.  ``encode_u8(u8_decode_table())`` is every byte."""
+    y = np.asarray(x, dtype=np.float32) * np.array(DEFAULT_STD, np.float32)
+    y = y + np.array(DEFAULT_MEAN, np.float32)
+    z = y * np.float32(255.0)
+    with np.errstate(invalid="ignore"):
+        q = np.where(z >= 0, np.minimum(np.rint(z), np.float32(255.0)), np.float32(0.0))
+    return q.astype(np.uint8)
+
+
 def synthetic_clip_u8(B, T=16, H=112, W=112, seed=1234):
     """uint8 frames [B,T,H,W,3] channels-last: the bytes ``synthetic_clip`` normalises for the same seed"""
     return np.random.default_rng(seed).integers(0, 256, (B, T, H, W, 3)).astype(np.uint8)

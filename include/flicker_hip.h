@@ -254,6 +254,32 @@ typedef struct {
 } flk_apply_args;
 int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dtype, void* stream);
 
+/* The adversarial clip as 8-bit frames: what a file or a display can hold (model.py:103-112 de-normalises the perturbed clip to [0,1]
+ * on the host; a video is that times 255, rounded).  Per value of x_adv -- the value flk_perturb_apply_s2d writes in fp32, computed by
+ * the same device functions: every source form (uint8 through x_lut or x_scale / x_bias, fp32), flicker / per-clip / dense delta, dclip
+ * and dclip_dev, shift_x and shift_p, adv_flag, lo and hi -- each operation rounded separately (no contraction):
+ *   y = x_adv * mul[c] + add[c];   z = y * levels;   q = z >= 0 ? min(rint(z), 255) : 0        (rint: half to even; NaN -> 0)
+ * torch dialect: mul = std, add = mean, levels = 255 (inverse of (u8/255 - mean)/std); TF dialect: mul = 1, add = 1, levels = 128
+ * (inverse of u8/128 - 1).  out: uint8 [B,T,H,W,3], plain layout; clip b at out + (out_clip_offset + b) * out_clip_stride BYTES, so a
+ * call can fill rows of a batch buffer.  a->fold_t is ignored, a->center must be 0, T, H and W may be any positive numbers.  One
+ * launch, no allocation, no synchronisation; 4-byte stores wherever the destination is aligned, bytes at the heads and tails of a
+ * frame; the result does not depend on the launch geometry.
+ * delta_T (0: a->T; flicker delta [delta_T,3] only): frame t takes row (t - shift_p) mod delta_T -- a universal flicker of period
+ * delta_T laid over a clip or a whole video of any length, at its own resolution.
+ * stats (NULL, or int32 [B][T][3][4], zeroed here by one hipMemsetAsync): per (clip, frame, channel) the sums over the frame of
+ * q - q_clean, |q - q_clean|, [q != q_clean] and [the lo / hi clamp was active], q_clean = the source byte (uint8 x) or the encoding
+ * of the unperturbed x (fp32 x).  Integer sums: exact in any order.  Entry 0 / (H*W) is the flicker the frames carry, in levels.
+ * FLK_EINVAL before any GPU call: null a / e / x / delta / out, non-positive sizes, center != 0, levels <= 0, out_clip_stride smaller
+ * than a clip, delta_T with a dense or per-clip delta, stats with H*W > 8388607 (255*H*W must fit an int32). */
+typedef struct {
+  float mul[3], add[3];
+  float levels;
+  int delta_T;
+  int64_t out_clip_offset;   /* first clip row of `out` written */
+  int64_t out_clip_stride;   /* bytes between clip rows of `out` (>= T*H*W*3) */
+} flk_export_args;
+int flk_adv_export_u8(const flk_apply_args* a, const flk_export_args* e, uint8_t* out, int32_t* stats, void* stream);
+
 /* d(loss)/d(delta): reduce the stem's input gradient (space-to-depth layout, from flk_conv3d) over
  * (B,H,W) with the clip masks of flk_perturb_apply_s2d.  gdelta: fp32 [T,3]
  * (flicker; deterministic two-stage reduction) or [T,H,W,3] (dense).  `partials` is caller scratch

@@ -172,8 +172,23 @@ def attack_clips_batched(eng, videos, c, max_steps, target_id=None, log_every=10
                 res.update(correct_cls_prob=float(st["clean"][st["label"]]), softmax_init=st["clean"].cpu().numpy(), total_steps=st["step"],
                            fatness=float(np.abs(d).mean() / 2 * 100), smoothness=float(np.abs(d - np.roll(d, 1, 0)).mean() / 2 * 100),
                            adv_video=eng.adversarial_inputs_rgb[b:b + 1].cpu().numpy(), beta_0=c.LAMBDA, beta_1=c.BETA_1, beta_2=c.BETA_2, beta_3=beta3)
+                add_u8_results(eng, res, c, st["label"], target_id if targeted else None, b)
                 yield st["tag"], res
                 yield from refill(b)
+
+
+def add_u8_results(eng, res, c, label_id, target_id, b=None):
+    """[new] SAVE_ADV_U8 / EVAL_QUANTISED: the adversarial clip as 8-bit frames (one kernel launch) and what the network makes of them --
+    result keys adv_video_u8, quantised_pred, quantised_is_adversarial (clip b of a batch).  Off: the result keeps the reference's keys."""
+    if not (c.SAVE_ADV_U8 or c.EVAL_QUANTISED):
+        return
+    sl = slice(None) if b is None else slice(b, b + 1)
+    if c.SAVE_ADV_U8:
+        res["adv_video_u8"] = eng.adversarial_inputs_u8[sl].cpu().numpy()
+    if c.EVAL_QUANTISED:
+        pred = int(eng.quantised_logits(eng.rgb_input)[0 if b is None else b].argmax())
+        res["quantised_pred"] = pred
+        res["quantised_is_adversarial"] = bool(pred == target_id) if target_id is not None else bool(pred != label_id)
 
 
 def main():
@@ -229,6 +244,7 @@ def main():
             continue
         res.update(correct_cls=cls, correct_cls_id=label_id, rgb_sample=clip)
         res["adv_video"] = eng.adversarial_inputs_rgb.cpu().numpy()        # sess.run(adversarial_inputs_rgb), :61,325 -- the apply kernel's output
+        add_u8_results(eng, res, c, label_id, target_id)
         out = os.path.join(c.PKL_RESULT_PATH, cfgmod.result_filename(cls, c.BETA_1, res["fatness"], res["smoothness"]))
         with open(out, "wb") as f:
             pickle.dump(res, f)

@@ -70,8 +70,33 @@ def run_whole_videos(a):
         clips = ((xd[i], yd[i:i + 1], names[i]) for i in range(len(videos)))
     else:
         clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
-    return learner.fit_many_videos(clips, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
-                                   reset_optimizer_per_video=a.reset_optimizer_per_video)
+    out = learner.fit_many_videos(clips, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
+                                  reset_optimizer_per_video=a.reset_optimizer_per_video, **export_kw(a))
+    if a.eval_quantised == "video":
+        # the attack as a whole video delivers it: each video's final flicker laid over ALL its frames at their own resolution
+        # (export_video), the stored video then scored by the ordinary clean evaluation over its G clips
+        for i, name in enumerate(names):
+            r = out.get(str(name))
+            if r is None:
+                continue
+            learner.pert_model.init_perturbation(r["perturbation"][-1])              # the clamped final perturbation of this video ...
+            learner.pert_model.dynamic_max_norm = max(learner.pert_model.max_norm, r["perturbation/inf_norm"])      # ... under its own bound
+            exported, st = learner.export_video(xd[i], stats=True)
+            ev = learner.evaluate_videos([exported], labels[i:i + 1], num_samples=G, adversarial=False)
+            r["quantised_video_pred"] = ev["video_preds"]
+            r["quantised_video_is_adversarial"] = bool(ev["video_preds"][0] != labels[i])
+            r["realised_flicker"] = st[:, :, 0].cpu().numpy() / float(xd[i].shape[1] * xd[i].shape[2])
+            cls = (classes[int(labels[i])] if classes is not None else str(int(labels[i]))).replace(" ", "_")
+            np.save(os.path.join(dest, f"{os.path.basename(str(name))}_@{cls}.npy"), dict(r, prob_clean_input=r["prob_clean_input"].cpu().numpy()),
+                    allow_pickle=True)
+    return out
+
+
+def export_kw(a):
+    """fit_many_videos keywords of --save-adversarial-u8 / --eval-quantised clip (none when both are off: the result files keep today's keys)"""
+    if a.save_adversarial_u8:
+        return {"export_u8": True}
+    return {"export_u8": "verdict"} if a.eval_quantised == "clip" else {}
 
 
 def report(out):
@@ -79,8 +104,9 @@ def report(out):
         if r is None:
             print(f"{name}: clean clip misclassified, skipped")
         else:
+            q = "".join(f", {k.replace('_', ' ')} {bool(r[k])}" for k in ("quantised_is_adversarial", "quantised_video_is_adversarial") if k in r)
             print(f"{name}: {len(r['loss/total'])} iterations, adversarial {bool(r['is_adversarial'][-1])}, thickness "
-                  f"{r['perturbation/thickness'][-1]:.4f}, roughness {r['perturbation/roughness'][-1]:.4f}, restarts {r['restarts']}", flush=True)
+                  f"{r['perturbation/thickness'][-1]:.4f}, roughness {r['perturbation/roughness'][-1]:.4f}, restarts {r['restarts']}{q}", flush=True)
 
 
 def main():
@@ -124,7 +150,16 @@ def main():
                     "evaluation clips of each video (the reference's evaluate(num_samples=G)); 1 = one clip, per-clip loss")
     ap.add_argument("--video-reduce", default="mean", choices=["mean", "sum"], help="--clips-per-video > 1: the loss takes the mean (default) or "
                     "the sum of a video's clip logits")
+    ap.add_argument("--save-adversarial-u8", action="store_true", help="the result files also hold adv_video_u8 -- the attacked clip under its "
+                    "final perturbation as 8-bit frames, uint8 [B,T,H,W,3], written by one kernel -- with quantised_pred and quantised_is_adversarial")
+    ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="is the STORED video still adversarial?  clip: the result "
+                    "files hold quantised_pred / quantised_is_adversarial of the clip's 8-bit frames; video (whole-video files, --batch 1): the "
+                    "final flicker over the whole video at its own resolution, scored by the clean evaluation -- quantised_video_pred, "
+                    "quantised_video_is_adversarial, realised_flicker (levels per frame and channel)")
     a = ap.parse_args()
+    if a.eval_quantised == "video" and (not vs.is_video_file(a.videos_npz) or a.batch > 1 or a.attack_type != "flickering"):
+        raise ValueError("--eval-quantised video needs a whole-video .npz file, --batch 1 and the flickering attack (one flicker per video, laid "
+                         "over all its frames)")
     if a.clips_per_video < 1:
         raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
     if a.clips_per_video > 1 and not vs.is_video_file(a.videos_npz):
@@ -165,7 +200,7 @@ def main():
     else:
         videos = ((torch.from_numpy(clips[i:i + 1]).cuda(), torch.from_numpy(labels[i:i + 1]).cuda(), names[i]) for i in range(len(clips)))
     out = learner.fit_many_videos(videos, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
-                                  reset_optimizer_per_video=a.reset_optimizer_per_video)
+                                  reset_optimizer_per_video=a.reset_optimizer_per_video, **export_kw(a))
     report(out)
 
 

@@ -182,6 +182,42 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                   f"video fooling ratio {ev['video_fooling_ratio']:.4f}", flush=True)
             os.makedirs(dest, exist_ok=True)
             np.savez(os.path.join(dest, "video_eval.npz"), num_samples=np.int64(a.eval_num_samples), **ev)
+        if a.eval_quantised:                    # the attack as 8-bit frames deliver it: video_eval_quantised.npz beside video_eval.npz
+            S = max(a.eval_num_samples, 1)
+            ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=S, quantise=a.eval_quantised)
+            print(f"quantised ({a.eval_quantised}) video evaluation, {S} clips per video: adversarial video accuracy {ev['video_accuracy']:.4f} | "
+                  f"video fooling ratio {ev['video_fooling_ratio']:.4f}", flush=True)
+            if a.eval_quantised == "video":     # one [N_k,3] table per video: stored end to end, with the videos' lengths
+                ev["realised_flicker_frames"] = np.array([len(f) for f in ev["realised_flicker"]], np.int64)
+                ev["realised_flicker"] = np.concatenate(ev["realised_flicker"])
+            os.makedirs(dest, exist_ok=True)
+            np.savez(os.path.join(dest, "video_eval_quantised.npz"), num_samples=np.int64(S), quantise=a.eval_quantised, **ev)
+        if a.save_adversarial_u8:               # the validation videos under the universal flicker, whole and at their own resolution
+            os.makedirs(dest, exist_ok=True)
+            np.savez(os.path.join(dest, "adversarial_u8.npz"), labels=yva,
+                     **{f"video_{i:05d}": learner.export_video(torch.from_numpy(v).cuda()).cpu().numpy() for i, v in enumerate(vva)})
+
+
+def quantised_clip_report(learner, clips, labels, batch_size, keep_frames):
+    """the validation clips under the learner's perturbation as 8-bit frames, batch by batch (the ragged tail is dropped, as in training):
+    what the network makes of the clean clips, of the float adversarial clips and of the frames"""
+    out = {k: [] for k in ("clean_preds", "adv_preds", "quantised_preds", "realised_flicker", "adv_clips_u8")}
+    for i in batch_ids(len(clips), batch_size):
+        x = learner._prepared(torch.from_numpy(clips[i * batch_size:(i + 1) * batch_size]).cuda())
+        out["clean_preds"].append(learner.logits(x, False).argmax(1).cpu().numpy())
+        out["adv_preds"].append(learner.logits(x, True).argmax(1).cpu().numpy())
+        frames, st = learner.adversarial_frames(x, stats=True)
+        out["quantised_preds"].append(learner.logits(frames, False).argmax(1).cpu().numpy())
+        out["realised_flicker"].append(st[..., 0].cpu().numpy() / float(learner.H * learner.W))
+        if keep_frames:
+            out["adv_clips_u8"].append(frames.cpu().numpy())
+    out = {k: np.concatenate(v) for k, v in out.items() if v}
+    y = labels[:len(out["clean_preds"])]
+    ok = out["clean_preds"] == y
+    out["labels"] = y
+    out["fooling_ratio"] = float(((out["adv_preds"] != y) & ok).sum() / ok.sum()) if ok.any() else float("nan")
+    out["quantised_fooling_ratio"] = float(((out["quantised_preds"] != y) & ok).sum() / ok.sum()) if ok.any() else float("nan")
+    return out
 
 
 class ResidentShard:
@@ -248,7 +284,18 @@ def main():
                     "the sum of a video's clip logits")
     ap.add_argument("--gpus", type=int, default=None, help="data-parallel ranks, one process per GPU (the reference's DEVICES_IDS, "
                     "r2plus1d_main_universal_attack.py:30-33); without a launcher in the environment the script starts them itself")
+    ap.add_argument("--save-adversarial-u8", action="store_true", help="after training, write the validation set under the universal perturbation "
+                    "as 8-bit frames: quantised_eval.npz gains adv_clips_u8 uint8 [N,T,H,W,3] (files of clips); adversarial_u8.npz holds every "
+                    "whole validation video flickered at its own resolution (whole-video files)")
+    ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="after training, score the attack as 8-bit frames deliver "
+                    "it.  clip: every validation clip exported at the engine's size (quantised_eval.npz; whole-video files: "
+                    "video_eval_quantised.npz); video (whole-video files): every validation video flickered whole at its own resolution, "
+                    "then the clean evaluation (video_eval_quantised.npz)")
     a = ap.parse_args()
+    if a.eval_quantised == "video" and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
+        raise ValueError("--eval-quantised video needs whole-video .npz files: a file of clips holds no whole video to flicker")
+    if (a.eval_quantised == "video" or (a.save_adversarial_u8 and vs.is_video_file(a.val_npz))) and a.attack_type != "flickering":
+        raise ValueError("whole videos take the flickering perturbation only (a dense perturbation belongs to the clip's size)")
     if a.clips_per_video < 1:
         raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
     if a.clips_per_video > 1 and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
@@ -319,6 +366,12 @@ def main():
         for e, r in enumerate(results, start_epoch):
             print(f"epoch {e}: train loss {r['train/loss']:.5f} fooling {r['train/fooling_ratio']:.4f} | valid loss {r['valid/loss']:.5f} "
                   f"fooling {r['valid/fooling_ratio']:.4f} | thickness {r['valid/pert_thickness']:.5f} roughness {r['valid/pert_roughness']:.5f}", flush=True)
+        if a.save_adversarial_u8 or a.eval_quantised:           # quantised_eval.npz: the validation clips as 8-bit frames and their verdict
+            rep = quantised_clip_report(learner, xva, yva, a.batch_size, a.save_adversarial_u8)
+            print(f"quantised evaluation, {len(rep['labels'])} validation clips: fooling ratio {rep['fooling_ratio']:.4f} as float clips, "
+                  f"{rep['quantised_fooling_ratio']:.4f} as 8-bit frames", flush=True)
+            os.makedirs(dest, exist_ok=True)
+            np.savez(os.path.join(dest, "quantised_eval.npz"), **rep)
     if world > 1:
         torch.distributed.destroy_process_group()
 

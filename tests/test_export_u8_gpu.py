@@ -1,0 +1,501 @@
+"""flk_adv_export_u8 on the GPU: the frames are bitwise the encode of what flk_perturb_apply_s2d writes in fp32, for every source form and
+perturbation; odd shapes, misaligned clips and rows of a batch buffer against the host restatement; exact integer statistics; integer
+levels; a perturbation of period delta_T; the engines' quantised routes; the scripts' options."""
+import glob
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def same_bits(a, b):
+    a, b = (t.detach().cpu().contiguous() if torch.is_tensor(t) else torch.from_numpy(np.ascontiguousarray(t)) for t in (a, b))
+    return a.dtype == b.dtype and a.shape == b.shape and bool(torch.equal(a.view(torch.uint8), b.view(torch.uint8)))
+
+
+def clip_u8(B, T, H, W, seed):
+    """random bytes with rows of 0 and of 255 planted (tests/test_vrn_u8_gpu.py::clips): the clamp bounds are hit"""
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    u8 = vs.synthetic_clip_u8(B, T, H, W, seed=seed)
+    u8[:, :, :2] = 0
+    u8[:, :, 2:4] = 255
+    return u8
+
+
+def torch_kw():
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    lo = float(np.max((0.0 - np.array(vs.DEFAULT_MEAN)) / vs.DEFAULT_STD))
+    hi = float(np.min((1.0 - np.array(vs.DEFAULT_MEAN)) / vs.DEFAULT_STD))
+    return dict(dialect="torch", dclip=0.2, inv_std=tuple(1.0 / s for s in vs.DEFAULT_STD), lo=lo, hi=hi)
+
+
+TF_KW = dict(dialect="tf", dclip=0.4, inv_std=(1.0, 1.0, 1.0), lo=-1.0, hi=1.0)
+
+
+def sources(u8):
+    """[(name, device clip, host clip, keywords, decode table or None)]: fp32, uint8 through the table, uint8 through scale and bias"""
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import decode_table
+    xf = vs.normalize_u8(u8)
+    xu = torch.from_numpy(u8).cuda()
+    return [("fp32", torch.from_numpy(xf).cuda(), xf, torch_kw(), None),
+            ("u8_lut", xu, u8, dict(torch_kw(), x_lut=decode_table("cuda")), vs.u8_decode_table()),
+            ("u8_scale_bias", xu, u8, dict(TF_KW), None)]
+
+
+def perturbations(B, T, H, W, rng, amp, shift_p=3):
+    """shared, per-clip (own bounds) and dense (rolled: the clip by 1, the perturbation by shift_p -- no multiple of T) perturbations"""
+    assert shift_p % T
+    shared = rng.uniform(-amp, amp, (T, 3)).astype(np.float32)
+    per_clip = rng.uniform(-amp, amp, (B, T, 3)).astype(np.float32)
+    dense = rng.uniform(-amp, amp, (T, H, W, 3)).astype(np.float32)
+    bounds = np.linspace(0.15, 0.25, B).astype(np.float32)
+    return [("shared", shared, {}, {}), ("per_clip", per_clip, dict(dclip_dev=torch.from_numpy(bounds).cuda()), dict(dclip_clip=bounds)),
+            ("dense_rolled", dense, dict(shift_x=1, shift_p=shift_p), dict(shift_x=1, shift_p=shift_p))]
+
+
+def unfold(f, fold_t):
+    """the apply kernel's fp32 space-to-depth output back to [B,T,H,W,3] (data movement only)"""
+    if fold_t == 1:
+        B, T, H2, W2 = f.shape[:4]
+        return f[..., :12].reshape(B, T, H2, W2, 2, 2, 3).permute(0, 1, 2, 4, 3, 5, 6).reshape(B, T, 2 * H2, 2 * W2, 3).contiguous()
+    B, T2, H2, W2 = f.shape[:4]
+    return f[..., :24].reshape(B, T2, H2, W2, 2, 2, 2, 3).permute(0, 1, 4, 2, 5, 3, 6, 7).reshape(B, 2 * T2, 2 * H2, 2 * W2, 3).contiguous()
+
+
+@pytest.mark.parametrize("shape,fold_t", [((2, 4, 6, 100), 1), ((2, 4, 6, 112), 1), ((1, 4, 8, 8), 2)])
+def test_bytes_are_the_encode_of_the_apply_kernel(shape, fold_t):
+    from flickering_adversarial_video_amd import ops
+    B, T, H, W = shape
+    rng = np.random.default_rng(3)
+    u8 = clip_u8(B, T, H, W, seed=7)
+    for sname, xd, _, kw, _ in sources(u8):
+        amp = 0.3 if kw["dialect"] == "torch" else 0.6
+        for pname, d, dev_kw, _ in perturbations(B, T, H, W, rng, amp):
+            dd = torch.from_numpy(d).cuda()
+            for adv in (1.0, 0.0):
+                a = ops.make_apply_args(xd, dd, fold_t=fold_t, adv_flag=adv, **kw, **dev_kw)
+                want = ops.encode_u8_host(unfold(ops.perturb_apply_s2d(a, torch.float32), fold_t).cpu().numpy(), kw["dialect"])
+                got = ops.export_adversarial_u8(a, kw["dialect"])
+                assert got.dtype == torch.uint8 and tuple(got.shape) == (B, T, H, W, 3)
+                assert np.array_equal(got.cpu().numpy(), want), (shape, sname, pname, adv)
+                if adv and sname != "fp32":
+                    assert (got.cpu().numpy() != u8).mean() > 0.5          # the perturbation is in the frames
+
+
+def test_odd_shapes_misaligned_clips_and_batch_buffer_rows():
+    """2 x 3 x 5 x 7: 315 bytes per clip, so the second clip starts off a 4-byte boundary; written at row 1 of a 4-row buffer, rows 0 and 3
+    stay as they were.  Expected: the host restatement (adv_flag 0 / 1: no contraction can change the apply arithmetic)"""
+    from flickering_adversarial_video_amd import ops
+    B, T, H, W = 2, 3, 5, 7
+    rng = np.random.default_rng(5)
+    u8 = clip_u8(B, T, H, W, seed=9)
+    for sname, xd, xh, kw, lut in sources(u8):
+        amp = 0.3 if kw["dialect"] == "torch" else 0.6
+        host_kw = {k: v for k, v in kw.items() if k != "x_lut"}
+        for pname, d, dev_kw, host_extra in perturbations(B, T, H, W, rng, amp, shift_p=2):
+            dd = torch.from_numpy(d).cuda()
+            for adv in (1.0, 0.0):
+                a = ops.make_export_apply_args(xd, dd, adv_flag=adv, **kw, **dev_kw)
+                want = ops.export_adversarial_u8_host(xh, d, adv_flag=adv, x_lut=lut, **host_kw, **host_extra)
+                got = ops.export_adversarial_u8(a, kw["dialect"])
+                assert np.array_equal(got.cpu().numpy(), want), (sname, pname, adv)
+                buf = torch.full((4, T, H, W, 3), 0xAB, dtype=torch.uint8, device="cuda")
+                rows = ops.export_adversarial_u8(a, kw["dialect"], out=buf, out_offset=1)
+                assert rows.data_ptr() == buf[1].data_ptr()
+                b = buf.cpu().numpy()
+                assert np.array_equal(b[1:3], want), (sname, pname, adv)
+                assert (b[0] == 0xAB).all() and (b[3] == 0xAB).all()
+
+
+@pytest.mark.parametrize("shape", [(2, 4, 112, 112), (2, 3, 5, 7)])
+def test_statistics_are_exact_integer_sums(shape):
+    """all four statistics against numpy int64 sums; 112 x 112 takes 37 workgroups per frame; two launches agree"""
+    from flickering_adversarial_video_amd import ops
+    B, T, H, W = shape
+    rng = np.random.default_rng(11)
+    u8 = clip_u8(B, T, H, W, seed=13)
+    for sname, xd, xh, kw, lut in sources(u8):
+        amp = 0.3 if kw["dialect"] == "torch" else 0.6
+        host_kw = {k: v for k, v in kw.items() if k != "x_lut"}
+        for pname, d, dev_kw, host_extra in perturbations(B, T, H, W, rng, amp, shift_p=3 if T == 4 else 2)[:: 2 if H > 100 else 1]:
+            a = ops.make_export_apply_args(xd, torch.from_numpy(d).cuda(), **kw, **dev_kw)
+            want_q, want_st = ops.export_adversarial_u8_host(xh, d, x_lut=lut, stats=True, **host_kw, **host_extra)
+            got_q, got_st = ops.export_adversarial_u8(a, kw["dialect"], stats=True)
+            again_q, again_st = ops.export_adversarial_u8(a, kw["dialect"], stats=True)
+            assert got_st.dtype == torch.int32 and tuple(got_st.shape) == (B, T, 3, 4)
+            assert np.array_equal(got_q.cpu().numpy(), want_q), (sname, pname)
+            assert np.array_equal(got_st.cpu().numpy().astype(np.int64), want_st), (sname, pname)
+            assert torch.equal(got_st, again_st) and torch.equal(got_q, again_q)
+            assert want_st[..., 2].sum() > 0 and want_st[..., 3].sum() > 0           # values moved, the clamp was active somewhere
+            if sname != "fp32":                                                      # the first three straight from the bytes
+                dq = got_q.cpu().numpy().astype(np.int64) - np.roll(u8, host_extra.get("shift_x", 0), axis=1)
+                assert np.array_equal(got_st[..., 0].cpu().numpy(), dq.sum((2, 3))) and np.array_equal(got_st[..., 1].cpu().numpy(), np.abs(dq).sum((2, 3)))
+
+
+def test_integer_levels_reach_the_frames_exactly():
+    """bytes in 30..200, a delta of whole levels k[t,c] / 255: the frames hold byte + k, the first statistic is k * H * W, the fourth 0"""
+    from flickering_adversarial_video_amd import ops
+    from flickering_adversarial_video_amd.torch_attack import decode_table
+    B, T, H, W = 2, 5, 9, 11
+    rng = np.random.default_rng(17)
+    u8 = rng.integers(30, 201, (B, T, H, W, 3)).astype(np.uint8)
+    k = rng.integers(-20, 21, (T, 3))
+    d = (k.astype(np.float32) / np.float32(255.0)).astype(np.float32)
+    a = ops.make_export_apply_args(torch.from_numpy(u8).cuda(), torch.from_numpy(d).cuda(), **dict(torch_kw(), dclip=0.1), x_lut=decode_table("cuda"))
+    q, st = ops.export_adversarial_u8(a, "torch", stats=True)
+    assert np.array_equal(q.cpu().numpy().astype(np.int64), u8.astype(np.int64) + k[None, :, None, None, :])
+    st = st.cpu().numpy()
+    assert np.array_equal(st[..., 0], np.broadcast_to(k * H * W, (B, T, 3))) and (st[..., 3] == 0).all()
+    assert np.array_equal(st[..., 1], np.broadcast_to(np.abs(k) * H * W, (B, T, 3)))
+    assert np.array_equal(st[..., 2], np.broadcast_to((k != 0) * H * W, (B, T, 3)))
+
+
+def test_delta_T_lays_a_period_over_any_length():
+    """10 frames under a perturbation of period 4: bitwise the plain export with delta tiled and cut to 10 rows (a phase rolls the period
+    first); delta_T equal to T changes nothing"""
+    from flickering_adversarial_video_amd import ops
+    from flickering_adversarial_video_amd.torch_attack import decode_table
+    N, P, H, W = 10, 4, 6, 9
+    rng = np.random.default_rng(19)
+    xu = torch.from_numpy(clip_u8(1, N, H, W, seed=21)).cuda()
+    d = rng.uniform(-0.3, 0.3, (P, 3)).astype(np.float32)
+    kw = dict(torch_kw(), x_lut=decode_table("cuda"))
+    for phase in (0, 3):
+        a = ops.make_export_apply_args(xu, torch.from_numpy(d).cuda(), shift_p=phase, delta_T=P, **kw)
+        got = ops.export_adversarial_u8(a, "torch")
+        with pytest.raises(ValueError, match="delta_T"):
+            ops.export_adversarial_u8(a, "torch", delta_T=0)
+        tiled = np.ascontiguousarray(np.tile(np.roll(d, phase, axis=0), (3, 1))[:N])
+        plain = ops.export_adversarial_u8(ops.make_export_apply_args(xu, torch.from_numpy(tiled).cuda(), **kw), "torch")
+        assert torch.equal(got, plain), phase
+        assert not torch.equal(got, xu)
+    full = torch.from_numpy(rng.uniform(-0.3, 0.3, (N, 3)).astype(np.float32)).cuda()
+    for phase in (0, 3):
+        a0 = ops.make_export_apply_args(xu, full, shift_p=phase, **kw)
+        a1 = ops.make_export_apply_args(xu, full, shift_p=phase, delta_T=N, **kw)
+        assert torch.equal(ops.export_adversarial_u8(a0, "torch"), ops.export_adversarial_u8(a1, "torch", delta_T=N))
+
+
+# ---- engines ---------------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def vrn():
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet
+    return FlickerVideoResNet("r3d_18", vs.synthetic_weights("r3d_18", 42), batch_size=2, sample_length=8, image_size=64, dtype="bf16", l_inf_pert_norm=0.2)
+
+
+def set_delta(eng, d):
+    eng.pert_model.perturbation.copy_(torch.as_tensor(d, dtype=torch.float32).reshape(eng.pert_model.perturbation.shape))
+
+
+def test_videoresnet_frames_and_quantised_logits(vrn):
+    xu = torch.from_numpy(clip_u8(2, 8, 64, 64, seed=23)).cuda()
+    set_delta(vrn, np.zeros((8, 3), np.float32))
+    clean = vrn.logits(xu, False).clone()
+    # delta = 0, adversarial = False: the frames are the source bytes (every byte value, 0 and 255 included)
+    assert torch.equal(vrn.pert_model.export_u8(xu, adversarial=False), xu)
+    assert same_bits(vrn.quantised_logits(xu, adversarial=False), clean)
+    # |delta| = 1e-3 (a quarter of a level) on bytes inside the clamp, 10..233: nothing reaches the frames, but the float clip moves the logits
+    mid = torch.from_numpy(np.random.default_rng(29).integers(10, 234, (2, 8, 64, 64, 3)).astype(np.uint8)).cuda()
+    clean_mid = vrn.logits(mid, False).clone()
+    set_delta(vrn, 1e-3 * np.where(np.random.default_rng(31).random((8, 3)) < 0.5, -1.0, 1.0))
+    frames, st = vrn.adversarial_frames(mid, stats=True)
+    assert torch.equal(frames, mid) and int(st.abs().sum()) == 0
+    assert same_bits(vrn.quantised_logits(mid), clean_mid)
+    assert not same_bits(vrn.logits(mid, True), clean_mid)
+    # a perturbation of whole levels does reach them
+    set_delta(vrn, np.random.default_rng(37).integers(-12, 13, (8, 3)) / 255.0)
+    assert not torch.equal(vrn.adversarial_frames(mid), mid)
+    assert not same_bits(vrn.quantised_logits(mid), clean_mid)
+
+
+def videos_and_labels():
+    rng = np.random.default_rng(41)
+    vids = [torch.from_numpy(rng.integers(0, 256, s).astype(np.uint8)).cuda() for s in ((12, 80, 96, 3), (9, 70, 70, 3), (20, 96, 72, 3))]
+    return vids, np.array([3, 1, 2], np.int64)
+
+
+def same_results(a, b):
+    assert a.keys() == b.keys(), a.keys() ^ b.keys()
+    for k in a:
+        va, vb = a[k], b[k]
+        if isinstance(va, list):
+            assert len(va) == len(vb) and all(same_bits(np.asarray(p), np.asarray(q)) for p, q in zip(va, vb)), k
+        elif isinstance(va, float) and np.isnan(va):
+            assert isinstance(vb, float) and np.isnan(vb), k
+        else:
+            assert same_bits(np.asarray(va), np.asarray(vb)), k
+
+
+def test_evaluate_videos_quantised(vrn):
+    vids, labels = videos_and_labels()
+    S = 2
+    set_delta(vrn, np.random.default_rng(43).uniform(-0.15, 0.15, (8, 3)))
+    # quantise = None: exactly today's keys and values
+    today = vrn.evaluate_videos(vids, labels, num_samples=S, adversarial=True)
+    same_results(vrn.evaluate_videos(vids, labels, num_samples=S, adversarial=True, quantise=None), today)
+    assert "realised_flicker" not in today
+    clean_only = vrn.evaluate_videos(vids, labels, num_samples=S)
+    same_results(vrn.evaluate_videos(vids, labels, num_samples=S, quantise=None), clean_only)
+    # "video": the ordinary clean evaluation of the videos export_video makes
+    rv = vrn.evaluate_videos(vids, labels, num_samples=S, quantise="video")
+    exported = [vrn.export_video(v) for v in vids]
+    assert all(e.dtype == torch.uint8 and e.shape == v.shape and not torch.equal(e, v) for e, v in zip(exported, vids))
+    of_exported = vrn.evaluate_videos(exported, labels, num_samples=S, adversarial=False)
+    for k in ("clip_logits", "video_logits", "clip_preds", "video_preds", "video_accuracy", "clip_accuracy"):
+        assert same_bits(np.asarray(rv[k]), np.asarray(of_exported[k])), k
+        assert same_bits(np.asarray(rv["clean_" + k]), np.asarray(clean_only[k])), k
+    assert set(rv) == set(today) | {"realised_flicker"}
+    assert [f.shape for f in rv["realised_flicker"]] == [(12, 3), (9, 3), (20, 3)]
+    for v, e, f in zip(vids, exported, rv["realised_flicker"]):
+        assert np.array_equal(f, (e.cpu().numpy().astype(np.int64) - v.cpu().numpy()).sum((1, 2)) / float(v.shape[1] * v.shape[2]))
+    # "clip": the logits of each prepared clip's 8-bit frames
+    rc = vrn.evaluate_videos(vids, labels, num_samples=S, quantise="clip")
+    x = vrn.prepare_videos(vids, train=False, num_samples=S).clone()
+    want = torch.cat([vrn.logits(vrn.adversarial_frames(x[i:i + 2]), False).clone() for i in range(0, 6, 2)])
+    assert same_bits(rc["clip_logits"], want.cpu().numpy())
+    assert same_bits(rc["clean_clip_logits"], clean_only["clip_logits"])
+    assert set(rc) == set(today) | {"realised_flicker"} and rc["realised_flicker"].shape == (6, 8, 3)
+    assert not same_bits(rc["clip_logits"], today["clip_logits"])                   # 8 bits are not the float clip
+    assert np.abs(rc["realised_flicker"]).max() > 1.0                                  # levels: +-0.15 is tens of them
+
+
+def test_single_video_results_hold_the_frames_and_the_quantised_verdict(vrn):
+    from flickering_adversarial_video_amd.torch_attack import Losses
+    xu = torch.from_numpy(clip_u8(2, 8, 64, 64, seed=47)).cuda()
+    lab = vrn.logits(xu, False).argmax(1).clone()
+    crit = Losses(beta_1=0.5, lambda_=1.0, margin=0.05, improve_loss=True, logits=True)
+    set_delta(vrn, np.zeros((8, 3), np.float32))
+    plain = vrn.fit_single_video_attack(xu, lab, crit, n_iter=2, restart_after=3, max_restarts=1)
+    set_delta(vrn, np.zeros((8, 3), np.float32))
+    vrn.pert_model.dynamic_max_norm = vrn.pert_model.max_norm
+    res = vrn.fit_single_video_attack(xu, lab, crit, n_iter=2, restart_after=3, max_restarts=1, export_u8=True)
+    assert set(res) == set(plain) | {"adv_video_u8", "quantised_pred", "quantised_is_adversarial"}
+    assert res["adv_video_u8"].dtype == np.uint8 and res["adv_video_u8"].shape == (2, 8, 64, 64, 3)
+    assert np.array_equal(res["adv_video_u8"], vrn.adversarial_frames(xu).cpu().numpy())
+    pred = vrn.quantised_logits(xu).argmax(1).cpu().numpy()
+    assert np.array_equal(res["quantised_pred"], pred) and res["quantised_is_adversarial"] == (not np.array_equal(pred, lab.cpu().numpy()))
+
+
+def test_i3d_quantised_routes():
+    from flickering_adversarial_video_amd import i3d_spec
+    from flickering_adversarial_video_amd.i3d_engine import FlickerI3D, FlickerI3DInference
+    T = 16                                       # the smallest clip the topology admits
+    W = i3d_spec.synthetic_i3d_weights(42)
+    eng = FlickerI3D(W, batch_size=1, frames=T, dtype="bf16")
+    xu = torch.from_numpy(i3d_spec.synthetic_clip_u8(1, T, seed=53)).cuda()
+    clean = eng.logits(xu, 0.0, 0).clone()
+    # delta = 0: the frames are the source bytes (u8 / 128 - 1 lies inside [-1, 1] for every byte), the quantised logits the clean ones
+    assert torch.equal(eng.adversarial_inputs_u8, xu)
+    assert same_bits(eng.quantised_logits(xu), clean)
+    # |delta| = 1e-3 (an eighth of a level): nothing reaches the frames, the float clip moves the logits
+    eng.reset_perturbation(1e-3 * np.where(np.random.default_rng(59).random((T, 3)) < 0.5, -1.0, 1.0))
+    adv = eng.logits(xu, 1.0, 0).clone()
+    assert torch.equal(eng.adversarial_inputs_u8, xu) and same_bits(eng.quantised_logits(xu), clean) and not same_bits(adv, clean)
+    # whole levels reach them: the frames are the encode of adversarial_inputs_rgb, and evaluate(quantise=True) scores those frames
+    eng.reset_perturbation(np.random.default_rng(61).integers(-30, 31, (T, 3)) / 128.0)
+    eng.logits(xu, 1.0, 0)
+    frames = eng.adversarial_inputs_u8
+    assert np.array_equal(frames.cpu().numpy(), i3d_spec.encode_u8(eng.adversarial_inputs_rgb.cpu().numpy())) and not torch.equal(frames, xu)
+    ql = eng.quantised_logits(xu).clone()
+    assert same_bits(ql, eng.logits(frames, 0.0, 0))
+    lab = clean.argmax(-1)
+    miss, valid = eng.evaluate([(xu, lab)], quantise=True)
+    assert valid == 1 and miss == float(int(ql.argmax(-1)) != int(lab))
+    inf = FlickerI3DInference(W, batch_size=1, frames=T, dtype="bf16")
+    inf.set_perturbation(eng.eps_rgb)
+    p = inf(xu, adv_flag=1, quantise=True).clone()
+    fr = inf._export_u8(xu, 1.0, 0, 0, 0.0)
+    assert same_bits(p, inf(fr, adv_flag=0)) and not same_bits(p, inf(xu, adv_flag=0))
+
+
+# ---- scripts ---------------------------------------------------------------------------------------------------------------------
+def _run(cmd):
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return r
+
+
+@pytest.mark.parametrize("batch", [[], ["--batch", "2"]], ids=["one_by_one", "batched"])
+def test_r2plus1d_single_video_script_saves_frames_and_verdict(tmp_path, batch):
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet
+    T, HW = 8, 64
+    u8 = vs.synthetic_clip_u8(2, T, HW, HW, seed=67)
+    eng = FlickerVideoResNet("r3d_18", vs.synthetic_weights("r3d_18", 42), batch_size=1, sample_length=T, image_size=HW, dtype="f32")
+    lab = [int(eng.logits(torch.from_numpy(u8[i:i + 1]).cuda(), False).argmax()) for i in range(2)]
+    del eng
+    np.savez(tmp_path / "v.npz", clips=u8, labels=np.array(lab), names=np.array(["a", "b"]))
+    cmd = [sys.executable, os.path.join(ROOT, "scripts", "r2plus1d_main_statistics_single_video_attack.py"), "--videos-npz", str(tmp_path / "v.npz"),
+           "--base-model", "r3d_18", "--dtype", "f32", "--n-iter", "3", "--restart-after", "40"]
+    cmd += batch                                # --batch 2: both videos at once, each slot under its own perturbation
+    _run(cmd + ["--results-root", str(tmp_path / "plain")])
+    r = _run(cmd + ["--results-root", str(tmp_path / "u8"), "--save-adversarial-u8", "--eval-quantised", "clip"])
+    assert "quantised is adversarial" in r.stdout
+    plain = sorted(glob.glob(str(tmp_path / "plain" / "**" / "*.npy"), recursive=True))
+    files = sorted(glob.glob(str(tmp_path / "u8" / "**" / "*.npy"), recursive=True))
+    assert len(files) == 2 and len(plain) == 2
+    for f, g, y in zip(files, plain, lab):
+        res, base = np.load(f, allow_pickle=True).tolist(), np.load(g, allow_pickle=True).tolist()
+        assert set(res) == set(base) | {"adv_video_u8", "quantised_pred", "quantised_is_adversarial"}       # off: today's keys
+        assert res["adv_video_u8"].dtype == np.uint8 and res["adv_video_u8"].shape == (1, T, HW, HW, 3)
+        assert res["quantised_pred"].shape == (1,) and res["quantised_is_adversarial"] == bool(res["quantised_pred"][0] != y)
+        # the frames are the encode of the clip under the saved final perturbation (the host restatement)
+        from flickering_adversarial_video_amd import ops
+        p = np.ascontiguousarray(res["perturbation"][-1].reshape(3, T).T)
+        kw = torch_kw()
+        want = ops.export_adversarial_u8_host(u8[files.index(f):files.index(f) + 1], p, x_lut=vs.u8_decode_table(), **dict(kw, dclip=0.0))
+        assert np.array_equal(res["adv_video_u8"], want)
+
+
+def test_i3d_single_video_script_saves_frames_and_verdict(tmp_path):
+    import pickle
+    from flickering_adversarial_video_amd import config as cfgmod, i3d_spec
+    from flickering_adversarial_video_amd.i3d_engine import FlickerI3D
+    T = 16
+    clip = i3d_spec.synthetic_clip_u8(1, T, seed=71).astype(np.float32) / 128 - 1
+    eng = FlickerI3D(i3d_spec.synthetic_i3d_weights(42), batch_size=1, frames=T, dtype="f32")
+    cls_id = int(eng(torch.from_numpy(clip).cuda(), adv_flag=0).argmax())
+    del eng
+    (tmp_path / "npy").mkdir()
+    (tmp_path / "labels.txt").write_text("\n".join(f"class {i}" for i in range(400)))
+    np.save(tmp_path / "npy" / f"rgb_0001@class_{cls_id}.npy", clip)
+    cfg = open(os.path.join(ROOT, "run_config.yml")).read()
+    cfg = cfg.replace("'data/label_map.txt'", f"'{tmp_path}/labels.txt'").replace("NPY_PATH: 'data/videos_for_tests/npy/'", f"NPY_PATH: '{tmp_path}/npy/'", 1)
+    cfg = cfg.replace("PKL_RESULT_PATH: 'result/videos_for_tests/npy/'", f"PKL_RESULT_PATH: '{tmp_path}/out/'")
+    assert cfg.count("SAVE_ADV_U8: False") == 3 and cfg.count("EVAL_QUANTISED: False") == 3
+    cfg = cfg.replace("SAVE_ADV_U8: False", "SAVE_ADV_U8: True", 1).replace("EVAL_QUANTISED: False", "EVAL_QUANTISED: True", 1)
+    (tmp_path / "cfg.yml").write_text(cfg)
+    _run([sys.executable, os.path.join(ROOT, "scripts", "i3d_adversarial_main_single_video_npy.py"), str(tmp_path / "cfg.yml"),
+          "--max-steps", "3", "--frames", str(T), "--dtype", "f32"])
+    outs = os.listdir(tmp_path / "out")
+    assert len(outs) == 1
+    res = pickle.load(open(tmp_path / "out" / outs[0], "rb"))
+    assert set(res) == set(cfgmod.RESULT_KEYS) | {"adv_video_u8", "quantised_pred", "quantised_is_adversarial"}
+    assert res["adv_video_u8"].dtype == np.uint8 and res["adv_video_u8"].shape == (1, T, 224, 224, 3)
+    assert np.array_equal(res["adv_video_u8"], i3d_spec.encode_u8(res["adv_video"]))             # the frames of the saved float clip
+    assert res["quantised_is_adversarial"] == (res["quantised_pred"] != cls_id)
+
+
+def whole_video_files(tmp_path, eng_kw, n_train=4, n_val=2):
+    """whole-video .npz files of differing lengths and resolutions; labels = the clean one-clip video prediction, so that attacks run"""
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from flickering_adversarial_video_amd.torch_attack import FlickerVideoResNet
+    rng = np.random.default_rng(73)
+    shapes = [(12, 80, 96, 3), (10, 72, 72, 3), (14, 96, 80, 3), (9, 70, 90, 3)]
+    vids = [rng.integers(0, 256, shapes[i % 4]).astype(np.uint8) for i in range(n_train)]
+    eng = FlickerVideoResNet("r3d_18", vs.synthetic_weights("r3d_18", 42), batch_size=1, **eng_kw)
+    labels = eng.evaluate_videos([torch.from_numpy(v).cuda() for v in vids], np.zeros(n_train, np.int64), num_samples=1)["video_preds"]
+    del eng
+    np.savez(tmp_path / "train.npz", labels=labels, **{f"video_{i:05d}": v for i, v in enumerate(vids)})
+    np.savez(tmp_path / "val.npz", labels=labels[:n_val], **{f"video_{i:05d}": v for i, v in enumerate(vids[:n_val])})
+    return vids, labels
+
+
+def test_r2plus1d_universal_script_on_whole_videos_quantised(tmp_path):
+    """--eval-quantised video and --save-adversarial-u8 on whole-video files: the stored videos and their evaluation"""
+    T, HW = 8, 64
+    vids, labels = whole_video_files(tmp_path, dict(sample_length=T, image_size=HW, dtype="bf16"))
+    cmd = [sys.executable, os.path.join(ROOT, "scripts", "r2plus1d_main_universal_attack.py"), "--train-npz", str(tmp_path / "train.npz"),
+           "--val-npz", str(tmp_path / "val.npz"), "--results-root", str(tmp_path / "results"), "--base-model", "r3d_18", "--batch-size", "2",
+           "--sample-length", str(T), "--image-size", str(HW), "--epochs", "1", "--eval-num-samples", "2"]
+    r = _run(cmd + ["--eval-quantised", "video", "--save-adversarial-u8"])
+    assert "quantised (video) video evaluation" in r.stdout
+    dest = os.path.dirname(glob.glob(str(tmp_path / "results" / "**" / "video_eval.npz"), recursive=True)[0])
+    today, q, stored = (np.load(os.path.join(dest, f), allow_pickle=True) for f in ("video_eval.npz", "video_eval_quantised.npz", "adversarial_u8.npz"))
+    assert "realised_flicker" not in today.files and set(q.files) == set(today.files) | {"realised_flicker", "realised_flicker_frames", "quantise"}
+    assert str(q["quantise"]) == "video" and q["realised_flicker_frames"].tolist() == [12, 10] and q["realised_flicker"].shape == (22, 3)
+    assert same_bits(q["clean_video_logits"], today["clean_video_logits"]) and q["video_logits"].shape == today["video_logits"].shape
+    want = []
+    for i, v in enumerate(vids[:2]):
+        e = stored[f"video_{i:05d}"]
+        assert e.dtype == np.uint8 and e.shape == v.shape and not np.array_equal(e, v)
+        want.append((e.astype(np.int64) - v).sum((1, 2)) / float(v.shape[1] * v.shape[2]))
+    assert np.array_equal(q["realised_flicker"], np.concatenate(want))                 # the flicker the stored videos carry
+    # "clip" on the same files: every prepared clip exported at the engine's size
+    r = _run(cmd + ["--eval-quantised", "clip", "--results-root", str(tmp_path / "results_clip")])
+    qc = np.load(glob.glob(str(tmp_path / "results_clip" / "**" / "video_eval_quantised.npz"), recursive=True)[0], allow_pickle=True)
+    assert str(qc["quantise"]) == "clip" and qc["realised_flicker"].shape == (4, T, 3) and "realised_flicker_frames" not in qc.files
+
+
+def test_r2plus1d_universal_script_on_clips_quantised(tmp_path):
+    """files of clips: quantised_eval.npz holds the validation clips as 8-bit frames and the verdicts"""
+    from flickering_adversarial_video_amd import ops, videoresnet_spec as vs
+    T, HW = 8, 64
+    u8 = vs.synthetic_clip_u8(4, T, HW, HW, seed=79)
+    np.savez(tmp_path / "train.npz", clips=u8, labels=np.arange(4) % 3)
+    np.savez(tmp_path / "val.npz", clips=u8[:2], labels=np.arange(2))
+    _run([sys.executable, os.path.join(ROOT, "scripts", "r2plus1d_main_universal_attack.py"), "--train-npz", str(tmp_path / "train.npz"),
+          "--val-npz", str(tmp_path / "val.npz"), "--results-root", str(tmp_path / "results"), "--base-model", "r3d_18", "--batch-size", "2",
+          "--epochs", "1", "--save-adversarial-u8", "--eval-quantised", "clip"])
+    f = glob.glob(str(tmp_path / "results" / "**" / "quantised_eval.npz"), recursive=True)
+    assert len(f) == 1
+    q = np.load(f[0])
+    assert set(q.files) == {"clean_preds", "adv_preds", "quantised_preds", "realised_flicker", "adv_clips_u8", "labels", "fooling_ratio",
+                            "quantised_fooling_ratio"}
+    assert q["adv_clips_u8"].dtype == np.uint8 and q["adv_clips_u8"].shape == (2, T, HW, HW, 3) and q["realised_flicker"].shape == (2, T, 3)
+    assert q["quantised_preds"].shape == (2,) and q["labels"].tolist() == [0, 1]
+    res = np.load(glob.glob(os.path.join(os.path.dirname(f[0]), "r3d_18_001.npy"))[0], allow_pickle=True)
+    p = np.ascontiguousarray(res[-1]["valid/perturbation"].reshape(3, T).T)                # the clamped final perturbation
+    want = ops.export_adversarial_u8_host(u8[:2], p, x_lut=vs.u8_decode_table(), **dict(torch_kw(), dclip=0.0))
+    assert np.array_equal(q["adv_clips_u8"], want)
+
+
+def test_r2plus1d_single_video_script_whole_video_verdict(tmp_path):
+    """--eval-quantised video: each video's final flicker over ALL its frames at their own resolution, then the clean evaluation"""
+    T, HW = 8, 64
+    vids, labels = whole_video_files(tmp_path, dict(sample_length=T, image_size=HW, dtype="f32"), n_train=2)
+    _run([sys.executable, os.path.join(ROOT, "scripts", "r2plus1d_main_statistics_single_video_attack.py"), "--videos-npz", str(tmp_path / "train.npz"),
+          "--base-model", "r3d_18", "--dtype", "f32", "--n-iter", "3", "--restart-after", "40", "--sample-length", str(T), "--image-size", str(HW),
+          "--results-root", str(tmp_path / "out"), "--eval-quantised", "video"])
+    files = sorted(glob.glob(str(tmp_path / "out" / "**" / "*.npy"), recursive=True))
+    assert len(files) == 2
+    for f, v, y in zip(files, vids, labels):
+        res = np.load(f, allow_pickle=True).tolist()
+        assert res is not None and res["realised_flicker"].shape == (v.shape[0], 3) and np.abs(res["realised_flicker"]).max() > 0
+        assert res["quantised_video_pred"].shape == (1,) and res["quantised_video_is_adversarial"] == bool(res["quantised_video_pred"][0] != y)
+        assert "adv_video_u8" not in res and "quantised_pred" not in res
+        # the realised flicker is that of the saved perturbation laid over the whole video with period T: the host restatement's statistics
+        from flickering_adversarial_video_amd import ops, videoresnet_spec as vs
+        p = np.ascontiguousarray(res["perturbation"][-1].reshape(3, T).T)                    # [T,3], clamped
+        _, st = ops.export_adversarial_u8_host(v[None], p, x_lut=vs.u8_decode_table(), delta_T=T, stats=True, **dict(torch_kw(), dclip=0.0))
+        assert np.array_equal(res["realised_flicker"], st[0, :, :, 0] / float(v.shape[1] * v.shape[2]))
+
+
+def test_i3d_class_generalisation_script_reports_the_quantised_fooling_rate(tmp_path):
+    import pickle
+    from flickering_adversarial_video_amd import i3d_spec, tfrecord_io as tio
+    from flickering_adversarial_video_amd.i3d_engine import FlickerI3D
+    T, B = 16, 2
+    (tmp_path / "rec").mkdir()
+    u8 = i3d_spec.synthetic_clip_u8(4, T, seed=83)
+    eng = FlickerI3D(i3d_spec.synthetic_i3d_weights(42), batch_size=1, frames=T, dtype="bf16")
+    labels = [int(eng(torch.from_numpy(u8[i:i + 1]).cuda(), adv_flag=0).argmax()) for i in range(4)]
+    del eng
+    tio.write_records(str(tmp_path / "rec" / "a.tfrecords"), [tio.make_example(u8[i], labels[i]) for i in range(4)], with_payload_crc=False)
+    (tmp_path / "labels.txt").write_text("\n".join(f"class {i}" for i in range(400)))
+    cfg = open(os.path.join(ROOT, "run_config.yml")).read().replace("'data/label_map.txt'", f"'{tmp_path}/labels.txt'")
+    cfg = cfg.replace("['data/kinetics/database/tfrecord/test/hula hooping']", f"['{tmp_path}/rec']")
+    cfg = cfg.replace("PKL_RESULT_PATH: 'result/generalization/model_gen_one_class/'", f"PKL_RESULT_PATH: '{tmp_path}/out/'")
+    cfg = cfg.replace("BATCH_SIZE: 8\n    MAX_NUM_STEP: 10000\n    TARGETED_ATTACK: False\n    TARGETED_CLASS: 'javelin throw'", f"BATCH_SIZE: {B}\n    MAX_NUM_STEP: 10000\n    TARGETED_ATTACK: False\n    TARGETED_CLASS: 'javelin throw'", 1)
+    head, sec, tail = cfg.partition("CLASS_GEN_ATTACK:")
+    cfg = head + sec + tail.replace("SAVE_ADV_U8: False", "SAVE_ADV_U8: True", 1).replace("EVAL_QUANTISED: False", "EVAL_QUANTISED: True", 1)
+    (tmp_path / "cfg.yml").write_text(cfg)
+    r = _run([sys.executable, os.path.join(ROOT, "scripts", "i3d_adversarial_main_single_class_gen.py"), str(tmp_path / "cfg.yml"),
+              "--frames", str(T), "--no-weights-in-checkpoint", "--max-steps", "2"])
+    assert "fool_rate as 8-bit frames" in r.stdout
+    res = pickle.load(open(tmp_path / "out" / "res.pkl", "rb"))
+    assert len(res["fool_rate_quantised"]) == len(res["fool_rate"]) >= 2 and all(0.0 <= v <= 1.0 for v in res["fool_rate_quantised"])
+    frames = np.load(tmp_path / "out" / "adversarial_inputs_u8.npy")
+    assert frames.dtype == np.uint8 and frames.shape == (B, T, 224, 224, 3)
+    # the frames are the last clip seen under the final perturbation: the host restatement from the last saved perturbation
+    from flickering_adversarial_video_amd import ops
+    p = res["perturbation"][-1].reshape(T, 3)
+    assert any(np.array_equal(frames, ops.export_adversarial_u8_host(u8[i:i + B], p, dialect="tf")) for i in (0, 2))
