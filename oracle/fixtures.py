@@ -14,6 +14,8 @@ convolution output, like real BN statistics), which keeps about half of the unit
 max-pool masks are as non-trivial as on the random fixture.  The logits layer favours one class so that the clean prediction has
 a comfortable margin.  Measured: torch-CPU fp32 reproduces the fp64 delta after 6 Adam steps to 3e-6.
 """
+import functools
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -104,3 +106,117 @@ def coherent_videoresnet_weights(W_base, x_ncdhw, arch, label=233, seed=5):
     wfc[label] += np.float32(0.02)
     W["fc.weight"], W["fc.bias"] = wfc, np.zeros(C, np.float32)
     return W
+
+
+def videoresnet_relu_inputs(x, W, arch, visit=None):
+    """Walk a VideoResNet forward (the structure of videoresnet_ref.videoresnet_logits; x NCDHW, W a dict of tensors of x's dtype)
+    and hand every ReLU's input to ``visit(name, pre_fn, bn, ds_bn)``: ``pre_fn()`` evaluates the pre-activation from W as it is NOW
+    (so a visitor may change the batch norm ``bn`` -- and ``ds_bn``, the downsample's, at a block's last ReLU -- and evaluate
+    again) and the visitor returns the pre-activation the walk continues from.  Without a visitor: returns [(name, pre)]."""
+    from . import videoresnet_ref as vr
+    seen = []
+
+    def record(name, pre_fn, bn, ds_bn):
+        seen.append((name, pre_fn()))
+        return seen[-1][1]
+
+    visit = visit or record
+    if arch == "r2plus1d_18":
+        y = F.relu(visit("stem.1", lambda: vr.bn(F.conv3d(x, W["stem.0.weight"], None, (1, 2, 2), (0, 3, 3)), W, "stem.1"), "stem.1", None))
+        y = F.relu(visit("stem.4", lambda y=y: vr.bn(F.conv3d(y, W["stem.3.weight"], None, 1, (1, 0, 0)), W, "stem.4"), "stem.4", None))
+    else:
+        y = F.relu(visit("stem.1", lambda: vr.bn(F.conv3d(x, W["stem.0.weight"], None, (1, 2, 2), (1, 3, 3)), W, "stem.1"), "stem.1", None))
+
+    def unit(inp, pre, kind, stride, bnp, shortcut=None, ds_bn=None):
+        """conv_builder + the block's batch norm (+ shortcut); (2+1)D units hold a ReLU of their own in the middle"""
+        if kind == "2plus1d":
+            mid = F.relu(visit(pre + ".0.1", lambda: vr.bn(F.conv3d(inp, W[pre + ".0.0.weight"], None, (1, stride, stride), (0, 1, 1)), W, pre + ".0.1"),
+                               pre + ".0.1", None))
+            conv = lambda: F.conv3d(mid, W[pre + ".0.3.weight"], None, (stride, 1, 1), (1, 0, 0))
+        else:
+            conv = lambda: vr.conv_unit(inp, W, pre + ".0", kind, stride)
+        if shortcut is None:
+            return visit(bnp, lambda: vr.bn(conv(), W, bnp), bnp, None)
+        return visit(bnp, lambda: vr.bn(conv(), W, bnp) + shortcut(), bnp, ds_bn)
+
+    for name, kind, stride, has_ds in vr.blocks(arch):
+        h1 = F.relu(unit(y, name + ".conv1", kind, stride, name + ".conv1.1"))
+        if has_ds:
+            shortcut = lambda y=y, name=name, kind=kind, stride=stride: vr.bn(
+                F.conv3d(y, W[name + ".downsample.0.weight"], None, vr.ds_stride(kind, stride)), W, name + ".downsample.1")
+        else:
+            shortcut = lambda y=y: y
+        y = F.relu(unit(h1, name + ".conv2", kind, 1, name + ".conv2.1", shortcut, name + ".downsample.1" if has_ds else None))
+    return seen
+
+
+SETTLED_MARGIN = 0.05
+
+
+def settled_videoresnet_weights(arch, x_adv, seed=42):
+    """VideoResNet weights on which NO ReLU can flip for the clip ``x_adv`` (the perturbed, normalised clip, NCDHW): every ReLU input
+    is at least SETTLED_MARGIN of its tensor's maximum, so the network is affine around the clip and two implementations of it differ
+    by rounding alone -- whole-plan tests at tiny extents, where one flipped unit would be percent of a tensor, can then bound every
+    element.  From videoresnet_spec.synthetic_weights(arch, seed), walking forward in fp64; at every batch norm that feeds a ReLU, in
+    order: its weight and bias are divided by max|its output| (at a block's last batch norm the downsample's by max|its output| as
+    well, the ReLU's input being their sum), and where min(pre) < m * max|pre| (m = SETTLED_MARGIN) its bias is raised by
+    (m * max|pre| - min(pre)) / (1 - m) * 1.01.  Returns {state_dict name: float32 array}."""
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    W = {k: torch.from_numpy(np.asarray(v)).double() for k, v in vs.synthetic_weights(arch, seed).items()}
+    m = SETTLED_MARGIN
+
+    def rescale(bn, by):
+        W[bn + ".weight"] = W[bn + ".weight"] / by
+        W[bn + ".bias"] = W[bn + ".bias"] / by
+
+    def settle(name, pre_fn, bn, ds_bn):
+        pre = pre_fn()
+        if name.endswith(".conv2.1"):    # a block's last batch norm: pre = its output + the shortcut (identity or downsample batch norm)
+            keep = W[bn + ".weight"], W[bn + ".bias"]
+            W[bn + ".weight"], W[bn + ".bias"] = torch.zeros_like(keep[0]), torch.zeros_like(keep[1])
+            short = pre_fn()             # (with its weight and bias at zero the batch norm's output is zero)
+            W[bn + ".weight"], W[bn + ".bias"] = keep
+            rescale(bn, (pre - short).abs().max())
+            if ds_bn is not None:
+                rescale(ds_bn, short.abs().max())
+        else:
+            rescale(bn, pre.abs().max())
+        pre = pre_fn()
+        lo, top = float(pre.min()), float(pre.abs().max())
+        if lo < m * top:
+            W[bn + ".bias"] = W[bn + ".bias"] + (m * top - lo) / (1 - m) * 1.01
+            pre = pre_fn()
+        return pre
+
+    with torch.no_grad():
+        videoresnet_relu_inputs(x_adv.double(), W, arch, settle)
+    return {k: v.numpy().astype(np.float32) for k, v in W.items()}
+
+
+@functools.lru_cache(maxsize=2)      # (a weight set is 50-130 MB: the cases of one fixture run back to back, no more are kept)
+def settled_case(arch, T, HW, B=1):
+    """one odd-extent plan case: (settled weights, clip [B,T,HW,HW,3] fp32 channels-last, delta [3,T,1,1] fp32) -- the clip and delta of
+    tests/test_videoresnet_gpu.py::test_videoresnet_forward_backward at the case's size, the weights settled on the perturbed clip"""
+    from flickering_adversarial_video_amd import videoresnet_spec as vs
+    from . import attack_math as am
+    x_cl = torch.from_numpy(vs.synthetic_clip(B, T, HW, HW, seed=5))
+    delta = torch.from_numpy(np.random.default_rng(2).uniform(-0.05, 0.05, (3, T, 1, 1)).astype(np.float32))
+    delta[:, 2] = 0.25                                      # beyond dynamic_max_norm = 0.2: no gradient through the clamp
+    x_adv = am.torch_apply(x_cl.double().permute(0, 4, 1, 2, 3).contiguous(), delta.double(), 0.2)
+    return settled_videoresnet_weights(arch, x_adv), x_cl, delta
+
+
+def videoresnet_attack_pass(W, x_cl, delta, arch, dt, bf16_conv_weights=False):
+    """oracle of one attack iteration in dtype ``dt``: forward, adversarial loss (improve loss on logits, as the engine's Losses) and its
+    gradient at every named endpoint and at delta; ``bf16_conv_weights``: the convolution weights rounded to bf16 first"""
+    from . import attack_math as am
+    from . import videoresnet_ref as vr
+    Wd = {k: (torch.from_numpy(v).to(torch.bfloat16).to(dt) if (bf16_conv_weights and v.ndim == 5) else torch.from_numpy(v).to(dt)) for k, v in W.items()}
+    x = x_cl.to(dt).permute(0, 4, 1, 2, 3).contiguous()
+    d = delta.to(dt).clone().requires_grad_(True)
+    logits, ep = vr.videoresnet_logits(am.torch_apply(x, d, 0.2), Wd, arch, return_endpoints=True)
+    label = logits.argmax(-1)
+    _, adv, _ = am.torch_losses(label, logits, torch.softmax(logits, 1), d.clamp(-0.2, 0.2), 0.5, 1.0, 0.05, True, True, "flickering")
+    names = [n for n in ep if n != "stem.mid"]
+    g, *ge = torch.autograd.grad(adv, [d] + [ep[n] for n in names])
+    return dict(logits=logits.detach(), ep={k: v.detach() for k, v in ep.items()}, adv=adv.item(), label=label, g=g, ge=dict(zip(names, ge)))

@@ -3,7 +3,12 @@
 
 Tolerances: fp32 mode (exact-fp32 MFMA) 1e-4 relative -- accumulation order only; the north-star bar is
 1e-3.  bf16 mode: inputs/weights are rounded to bf16 on both sides, so the difference is fp32
-accumulation order plus one bf16 rounding of the output: 1e-2 relative to the output scale."""
+accumulation order plus one bf16 rounding of the output: 1e-2 relative to the output scale.
+
+Not here: the four strided geometries of the VideoResNet plans with torch's SYMMETRIC padding -- 3x3x3 / 2 pad 1, (1,3,3) / (1,2,2)
+pad (0,1,1), (3,1,1) / (2,1,1) pad (1,0,0) and the 1x1x1 strided downsample -- forward and as parity-class data-gradients
+(out_stride / out_offset, 2-tap boxes) at odd extents: tests/test_conv_strided_gpu.py.  The strided CONV_CASES below use TF SAME
+padding (pad-before 0 at stride 2 over an even extent), and test_conv_data_gradient is stride 1."""
 import numpy as np
 import pytest
 import torch
