@@ -82,6 +82,27 @@ __device__ static inline float applied(const flk_apply_args& a, float x, float p
 }
 __device__ static inline int wrap(int t, int T) { t %= T; return t < 0 ? t + T : t; }
 
+// ---- 8-bit encode (flk_export_args; include/flicker_hip.h): the export kernel's quantiser, and the quantised apply's -------------
+// y = x_adv * mul + add; z = y * levels; q = z >= 0 ? min(rint(z), 255) : 0 -- every operation rounded on its own; NaN -> 0
+__device__ static inline int encode_q(float v, float mul, float add, float levels) {
+  const float z = __fmul_rn(__fadd_rn(__fmul_rn(v, mul), add), levels);
+  return z >= 0.f ? (int)fminf(rintf(z), 255.f) : 0;
+}
+// Quantised apply (flk_apply_args.q_lut, template QUANT of the apply kernels): the value a kernel writes is the one the STORED video
+// decodes to -- v = applied(...) encoded to its byte, the byte decoded through the table.  NO second clamp: a value the clamp holds at a
+// bound is stored as the level nearest the bound, and a clean forward of the stored frames (clamp bounds -inf / +inf) sees that level.
+// ql: the 768-entry table in LDS (stage_q_lut); c: the value's channel.  QUANT = false is the identity: the plain instantiations
+// contain none of this.
+template <bool QUANT> __device__ static inline float quantised(const flk_apply_args& a, const float* ql, float v, int c) {
+  if constexpr (QUANT) return ql[encode_q(v, a.q_mul[c], a.q_add[c], a.q_levels) * 3 + c];
+  else return v;
+}
+// every thread of the workgroup calls this once, before any early return
+__device__ static inline void stage_q_lut(const flk_apply_args& a, float* ql) {
+  for (int i = threadIdx.x; i < 768; i += 256) ql[i] = a.q_lut[i];
+  __syncthreads();
+}
+
 // perturbation added at frame t (before adv_flag): p'[t] = p[(t - shift_p) mod T] (tf.roll), p = clip(delta)/std
 // (delta_per_clip: clip b has its own [T,3] perturbation)
 __device__ static inline float pert_at(const flk_apply_args& a, int b, int t, int h, int w, int c) {
@@ -93,9 +114,11 @@ __device__ static inline float pert_at(const flk_apply_args& a, int b, int t, in
 }
 
 // ---- apply: one thread = one space-to-depth output position (FT x 2 x 2 input cells x 3 channels) ----
-template <typename TO, int FTL>
+template <typename TO, int FTL, bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_kernel(const flk_apply_args a, char* out) {
   constexpr int FT = S2D<FTL>::F, NCH = S2D<FTL>::NCH;
+  __shared__ float ql[QUANT ? 768 : 1];
+  if constexpr (QUANT) stage_q_lut(a, ql);
   const int T2 = a.T / FT, H2 = a.H / 2, W2 = a.W / 2;
   const long total = (long)a.B * T2 * H2 * W2;
   for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
@@ -121,7 +144,7 @@ __global__ __launch_bounds__(256) void apply_s2d_kernel(const flk_apply_args a, 
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
             const float pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, h, 2 * w2 + qw, c) : 0.f;
-            v[S2D<FTL>::ch(qt, qh, qw * 3 + c)] = applied(a, x[qw * 3 + c], pv);
+            v[S2D<FTL>::ch(qt, qh, qw * 3 + c)] = quantised<QUANT>(a, ql, applied(a, x[qw * 3 + c], pv), c);
           }
       }
     }
@@ -136,7 +159,10 @@ __global__ __launch_bounds__(256) void apply_s2d_kernel(const flk_apply_args a, 
 // centred-clip + position-bias form of the I3D stem is exact only where the clamp bounds are bf16 numbers -- here 5-8 % of the
 // values of a clip sit AT a bound, and bf16(bound - p) jumps by a whole ulp for all of them at once (measured: wrong sign at
 // |delta| = 5e-4).
+template <bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_hilo_kernel(const flk_apply_args a, char* out) {
+  __shared__ float ql[QUANT ? 768 : 1];
+  if constexpr (QUANT) stage_q_lut(a, ql);
   const int H2 = a.H / 2, W2 = a.W / 2;
   const long total = (long)a.B * a.T * H2 * W2;
   for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
@@ -157,7 +183,7 @@ __global__ __launch_bounds__(256) void apply_s2d_hilo_kernel(const flk_apply_arg
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
         const float pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, h, 2 * w2 + k / 3, k % 3) : 0.f;
-        const float u = applied(a, x[k], pv);
+        const float u = quantised<QUANT>(a, ql, applied(a, x[k], pv), k % 3);
         const float hi = (float)(bf16_t)u;
         v[S2D<1>::ch(0, qh, k)] = hi;                    // (stored again as bf16: exact)
         v[16 + S2D<1>::ch(0, qh, k)] = u - hi;
@@ -171,9 +197,11 @@ __global__ __launch_bounds__(256) void apply_s2d_hilo_kernel(const flk_apply_arg
 // consecutive output positions.  It reads its 24 source bytes of each of the 4 (frame, row) pairs as three aligned
 // 8-byte loads (the generic kernel above issues 2-byte loads), evaluates the 6 perturbation values (2 frames x RGB) once,
 // and decodes its position with 32-bit arithmetic from a 3-D grid.  Same arithmetic per element as the generic kernel.
-template <typename TO, int FTL>
+template <typename TO, int FTL, bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_apply_args a, char* out) {
   constexpr int NCH = 32;
+  __shared__ float ql[QUANT ? 768 : 1];
+  if constexpr (QUANT) stage_q_lut(a, ql);
   const int H2 = a.H / 2, W2 = a.W / 2, WG = W2 / 4;
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned)(H2 * WG)) return;
@@ -210,7 +238,7 @@ __global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_app
         for (int e = 0; e < 6; ++e) {              // byte 6j + e of the 24-byte run
           const int bi = 6 * j + e;
           const float x = (float)((w[bi >> 2] >> (8 * (bi & 3))) & 255u) * a.x_scale + a.x_bias;
-          v[S2D<FTL>::ch(qt, qh, e)] = applied(a, x, pv[qt][e % 3]);
+          v[S2D<FTL>::ch(qt, qh, e)] = quantised<QUANT>(a, ql, applied(a, x, pv[qt][e % 3]), e % 3);
         }
       }
     store_ch<TO, NCH>(dst + (size_t)j * NCH * sizeof(TO), v);
@@ -222,11 +250,13 @@ __global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_app
 // row pair), each of its two source rows read as three aligned 8-byte loads (24 bytes = 8 pixels); the 768-entry table is staged in
 // LDS once per workgroup.  Per element the arithmetic of apply_s2d_hilo_kernel on the decoded value, so the bytes written equal
 // that kernel's on the fp32 clip x_lut[u8].  DENSE: the [T,H,W,3] perturbation (per element); else [T,3] / [B,T,3] (3 values).
-template <bool DENSE>
+template <bool DENSE, bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_hilo_u8_kernel(const flk_apply_args a, char* out) {
   __shared__ float lut[768];
+  __shared__ float ql[QUANT ? 768 : 1];
   for (int i = threadIdx.x; i < 768; i += 256) lut[i] = a.x_lut[i];
-  __syncthreads();
+  if constexpr (QUANT) stage_q_lut(a, ql);        // (its barrier covers lut too)
+  else __syncthreads();
   const int H2 = a.H / 2, W2 = a.W / 2, WG = W2 / 4;
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned)(H2 * WG)) return;
@@ -261,7 +291,7 @@ __global__ __launch_bounds__(256) void apply_s2d_hilo_u8_kernel(const flk_apply_
         float p;
         if constexpr (DENSE) p = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, 2 * h2 + qh, 8 * wg + 2 * j + e / 3, e % 3) : 0.f;
         else p = pv[e % 3];
-        const float u = applied(a, x, p);
+        const float u = quantised<QUANT>(a, ql, applied(a, x, p), e % 3);
         const float hi = (float)(bf16_t)u;
         v[S2D<1>::ch(0, qh, e)] = hi;
         v[16 + S2D<1>::ch(0, qh, e)] = u - hi;
@@ -281,6 +311,7 @@ static int check_apply(const flk_apply_args* a) {
   FLK_REQUIRE(!(a->delta_per_clip && a->delta_dense), "flk_perturb: delta_per_clip is defined for the flicker perturbation only");
   FLK_REQUIRE(!a->dclip_dev || a->delta_per_clip, "flk_perturb: dclip_dev (per-clip clamp bounds) needs delta_per_clip");
   FLK_REQUIRE(!a->x_lut || (a->x_is_u8 && !a->center), "flk_perturb: x_lut (per-channel decode table) needs a uint8 clip and center = 0");
+  FLK_REQUIRE(!a->q_lut || (!a->center && a->q_levels > 0.f), "flk_perturb: q_lut (quantised apply) needs center = 0 and q_levels > 0");
   return FLK_OK;
 }
 
@@ -292,15 +323,20 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   const long total = (long)a->B * (a->T / ft) * (a->H / 2) * (a->W / 2);
   const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
+  const bool quant = a->q_lut != nullptr;          // the QUANT instantiations: the plain ones are untouched by the option
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_perturb_apply_s2d: bad dtype");
   if (a->fold_t == 4) {
     FLK_REQUIRE(dtype == FLK_BF16 && !a->center, "flk_perturb_apply_s2d: fold_t = 4 (two bf16 numbers per value) writes bf16, uncentred");
     if (a->x_lut && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T < 65536 && a->B < 65536) {
       const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)a->T, (unsigned)a->B);
-      if (a->delta_dense) FLK_LAUNCH_KERNEL(apply_s2d_hilo_u8_kernel<true>, g3, dim3(256), 0, st, *a, (char*)out);
-      else FLK_LAUNCH_KERNEL(apply_s2d_hilo_u8_kernel<false>, g3, dim3(256), 0, st, *a, (char*)out);
+#define FLK_HILO_U8(D) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, true>), g3, dim3(256), 0, st, *a, (char*)out); \
+                           else FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
+      if (a->delta_dense) FLK_HILO_U8(true); else FLK_HILO_U8(false);
+#undef FLK_HILO_U8
+    } else if (quant) {
+      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel<true>, dim3(grid), dim3(256), 0, st, *a, (char*)out);
     } else {
-      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel, dim3(grid), dim3(256), 0, st, *a, (char*)out);
+      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel<false>, dim3(grid), dim3(256), 0, st, *a, (char*)out);
     }
     FLK_CHECK_HIP(hipGetLastError());
     return FLK_OK;
@@ -308,14 +344,18 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   const bool bf = dtype == FLK_BF16;
   if (ft == 2 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && a->T / 2 < 65536 && a->B < 65536) {
     const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)(a->T / 2), (unsigned)a->B);
-    if (bf && ftl == 2) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<bf16_t, 2>), g3, dim3(256), 0, st, *a, (char*)out);
-    else if (bf) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<bf16_t, 3>), g3, dim3(256), 0, st, *a, (char*)out);
-    else if (ftl == 2) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<float, 2>), g3, dim3(256), 0, st, *a, (char*)out);
-    else FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<float, 3>), g3, dim3(256), 0, st, *a, (char*)out);
+#define FLK_U8F(TT, L) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, true>), g3, dim3(256), 0, st, *a, (char*)out); \
+                            else FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
+    if (bf && ftl == 2) FLK_U8F(bf16_t, 2);
+    else if (bf) FLK_U8F(bf16_t, 3);
+    else if (ftl == 2) FLK_U8F(float, 2);
+    else FLK_U8F(float, 3);
+#undef FLK_U8F
     FLK_CHECK_HIP(hipGetLastError());
     return FLK_OK;
   }
-#define FLK_APPLY(TT, L) FLK_LAUNCH_KERNEL((apply_s2d_kernel<TT, L>), dim3(grid), dim3(256), 0, st, *a, (char*)out)
+#define FLK_APPLY(TT, L) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_kernel<TT, L, true>), dim3(grid), dim3(256), 0, st, *a, (char*)out); \
+                              else FLK_LAUNCH_KERNEL((apply_s2d_kernel<TT, L, false>), dim3(grid), dim3(256), 0, st, *a, (char*)out); } while (0)
   if (bf) { if (ftl == 1) FLK_APPLY(bf16_t, 1); else if (ftl == 2) FLK_APPLY(bf16_t, 2); else FLK_APPLY(bf16_t, 3); }
   else { if (ftl == 1) FLK_APPLY(float, 1); else if (ftl == 2) FLK_APPLY(float, 2); else FLK_APPLY(float, 3); }
 #undef FLK_APPLY
@@ -323,12 +363,8 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   return FLK_OK;
 }
 
-// ---- 8-bit export: x_adv of the apply kernels encoded to the bytes of a frame (include/flicker_hip.h) ---------------------------
-// y = x_adv * mul + add; z = y * levels; q = z >= 0 ? min(rint(z), 255) : 0 -- every operation rounded on its own; NaN -> 0
-__device__ static inline int encode_q(float v, float mul, float add, float levels) {
-  const float z = __fmul_rn(__fadd_rn(__fmul_rn(v, mul), add), levels);
-  return z >= 0.f ? (int)fminf(rintf(z), 255.f) : 0;
-}
+// ---- 8-bit export: x_adv of the apply kernels encoded to the bytes of a frame (include/flicker_hip.h; encode_q is above, shared with
+// the quantised apply) -----------------------------------------------------------------------------------------------------------
 // one value of the clip, as load6 decodes it: byte `by` of channel c
 __device__ static inline float decode1(const flk_apply_args& a, uint32_t by, int c) {
   return a.x_lut ? a.x_lut[by * 3 + c] : (float)by * a.x_scale + a.x_bias;

@@ -268,11 +268,55 @@ def maxpool3d_bwd_conv1x1(ctx, g, wb, *, g_coff=0, gin=None, gin_coff=0, gpool=N
 I3D_FOLD = 3   # space-to-depth layout the I3D plan (flk_net, FLK_NET_I3D) expects: chunk-aligned (t,h,w) fold
 
 
+def quant_table_host(dialect):
+    """fp32 [256,3]: what byte v of channel c decodes to in a dialect of EXPORT_DIALECTS -- torch: videoresnet_spec.u8_decode_table
+    ((v / 255 - mean) / std); TF: v / 128 - 1 (exact in float32)"""
+    if dialect not in EXPORT_DIALECTS:
+        raise ValueError(f"dialect must be one of {sorted(EXPORT_DIALECTS)}, got {dialect!r}")
+    if dialect == "torch":
+        from .videoresnet_spec import u8_decode_table
+        return u8_decode_table()
+    return np.ascontiguousarray(np.repeat((np.arange(256, dtype=np.float32) / np.float32(128.0) - np.float32(1.0))[:, None], 3, axis=1))
+
+
+_QUANT_TABLES = {}
+
+
+def quant_table(dialect, device):
+    """``quant_table_host(dialect)`` on ``device`` (flk_apply_args.q_lut): one copy per device -- the torch dialect's is the decode table
+    the uint8 clips already go through (torch_attack.decode_table)"""
+    if dialect not in EXPORT_DIALECTS:
+        raise ValueError(f"dialect must be one of {sorted(EXPORT_DIALECTS)}, got {dialect!r}")
+    if dialect == "torch":
+        from .torch_attack import decode_table
+        return decode_table(device)
+    dev = torch.device(device)
+    key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+    if key not in _QUANT_TABLES:
+        _QUANT_TABLES[key] = torch.from_numpy(quant_table_host("tf")).to(torch.device(dev.type, key[1]))
+    return _QUANT_TABLES[key]
+
+
 def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0),
-                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None, x_lut=None):
+                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None, x_lut=None, quantise=None, q_lut=None):
     """x: uint8 or fp32 [B,T,H,W,3] on the GPU; delta fp32 [T,3] (flicker, shared by the batch), [B,T,3] (one flicker perturbation PER
     CLIP: independent single-video attacks advancing in one batch) or [T,H,W,3] (dense).  x_lut: fp32 [256,3] on the device (uint8 x
-    only): byte v of channel c decodes to x_lut[v, c] (videoresnet_spec.u8_decode_table) instead of the dialect's scalar decode."""
+    only): byte v of channel c decodes to x_lut[v, c] (videoresnet_spec.u8_decode_table) instead of the dialect's scalar decode.
+    quantise: None, or the dialect ("torch" | "tf") of EXPORT_DIALECTS whose 8-bit round trip the apply kernels put every value through
+    (flk_apply_args.q_lut: the clip the network sees is the STORED video; the gradient is the straight-through estimator, which the
+    gradient kernels already compute).  q_lut: its decode table, fp32 [256,3] on the device (default: ``quant_table``)."""
+    if quantise is not None:
+        if quantise not in EXPORT_DIALECTS:
+            raise ValueError(f"quantise must be None or one of {sorted(EXPORT_DIALECTS)}, got {quantise!r}")
+        if center:
+            raise ValueError("quantise: the centred clip (center=True) carries the perturbation in the stem's position bias -- there is no "
+                             "per-pixel value to round")
+        if q_lut is None:
+            q_lut = quant_table(quantise, x.device)
+        if not (torch.is_tensor(q_lut) and q_lut.dtype == torch.float32 and tuple(q_lut.shape) == (256, 3) and q_lut.is_contiguous() and q_lut.is_cuda):
+            raise ValueError("q_lut: fp32 [256,3] on the device")
+    elif q_lut is not None:
+        raise ValueError("q_lut without quantise: name the dialect whose encode goes with the table")
     B, T, H, W, c3 = x.shape
     assert c3 == 3 and x.is_contiguous() and delta.is_contiguous() and delta.dtype == torch.float32
     assert x.dtype in (torch.uint8, torch.float32)
@@ -302,7 +346,10 @@ def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=
         assert a.delta_per_clip and dclip_dev.dtype == torch.float32 and dclip_dev.shape == (B,) and dclip_dev.is_cuda
     a.dclip_dev = ptr(dclip_dev)
     a.x_lut = ptr(x_lut)
-    a._keepalive = (x, delta, dclip_dev, x_lut)   # the struct holds raw pointers only
+    if quantise is not None:    # the encode of make_export_args(quantise), the decode of q_lut
+        mul, add, levels = EXPORT_DIALECTS[quantise]
+        a.q_lut, a.q_mul, a.q_add, a.q_levels = ptr(q_lut), (C.c_float * 3)(*mul), (C.c_float * 3)(*add), levels
+    a._keepalive = (x, delta, dclip_dev, x_lut, q_lut)   # the struct holds raw pointers only
     return a
 
 
@@ -336,7 +383,8 @@ def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, s
                            dclip_dev=None, x_lut=None, delta_T=0):
     """the flk_apply_args of an 8-bit export: ``make_apply_args`` without a fold (T, H and W may be odd) and, with ``delta_T``, with a
     flicker perturbation [delta_T,3] whose length is its period instead of the clip's T.  (The fields are filled as ``make_apply_args``
-    fills them -- a change to one belongs in the other; only the fold, ``center`` and the shape rule of ``delta`` differ.)  The period is
+    fills them -- a change to one belongs in the other; only the fold, ``center`` and the shape rule of ``delta`` differ, and there is no
+    ``quantise``: the export is the quantiser itself, and ``make_apply_args(quantise=dialect)`` applies the clip these bytes decode to.)  The period is
     remembered on the result (``_delta_T``): ``export_adversarial_u8`` takes it from there."""
     B, T, H, W, c3 = x.shape
     assert c3 == 3 and x.is_contiguous() and x.is_cuda and delta.is_contiguous() and delta.is_cuda and delta.dtype == torch.float32
@@ -429,6 +477,16 @@ def export_adversarial_u8_host(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.
     active = (u < f32(lo)) | (u > f32(hi))
     st = np.stack([dq.sum((2, 3)), np.abs(dq).sum((2, 3)), (dq != 0).sum((2, 3)), active.sum((2, 3))], axis=-1)
     return q, st.astype(np.int64)
+
+
+def perturb_apply_quantised_host(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0), lo=-1.0,
+                                 hi=1.0, dclip_clip=None, x_lut=None, delta_T=0):
+    """the host A/B route of a quantised apply (``make_apply_args(quantise=dialect)``), unfolded: numpy float32 [B,T,H,W,3], the bytes of
+    ``export_adversarial_u8_host`` (same keywords) decoded through ``quant_table_host(dialect)`` -- what a clean forward of the stored
+    video sees (no second clamp: a value held at lo / hi is stored as the level nearest the bound and comes back as that level)"""
+    q = export_adversarial_u8_host(x, delta, dialect=dialect, dclip=dclip, adv_flag=adv_flag, shift_x=shift_x, shift_p=shift_p, inv_std=inv_std,
+                                   lo=lo, hi=hi, dclip_clip=dclip_clip, x_lut=x_lut, delta_T=delta_T)
+    return np.ascontiguousarray(quant_table_host(dialect)[q, np.arange(3)], dtype=np.float32)
 
 
 def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):

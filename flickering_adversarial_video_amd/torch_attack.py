@@ -95,10 +95,11 @@ class Perturbation:
             p = perturbation
         self.perturbation = torch.from_numpy(self._to_dev(p)).cuda()
 
-    def apply_args(self, x, adversarial=True, fold_t=1):
+    def apply_args(self, x, adversarial=True, fold_t=1, quantise=False):
         """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans).
         x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
-        ``videoresnet_spec.normalize_u8`` makes on the host)"""
+        ``videoresnet_spec.normalize_u8`` makes on the host).  quantise: every value goes through the 8-bit round trip of ``export_u8``
+        inside the apply kernel (flk_apply_args.q_lut) -- the clip applied is the one the exported frames decode to, bit for bit"""
         shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
         inf = float("inf")
         return ops.make_apply_args(x, self.perturbation, dialect="torch", dclip=self.dynamic_max_norm,
@@ -106,7 +107,8 @@ class Perturbation:
                                    inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                    lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf, fold_t=fold_t,
                                    dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
-                                   x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None)
+                                   x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None,
+                                   quantise="torch" if quantise else None, q_lut=decode_table(x.device) if quantise else None)
 
     def export_args(self, x, adversarial=True, shift_p=0, delta_T=0):
         """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
@@ -132,8 +134,9 @@ class Perturbation:
             raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.T}")
         return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p), "torch", out=out, out_offset=out_offset, stats=stats)
 
-    def forward(self, input):
-        """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip.  ``x`` is the
+    def forward(self, input, quantise=False):
+        """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip; ``quantise``:
+        the normalised clip its 8-bit frames (``export_u8``) decode to -- what a stored video delivers.  ``x`` is the
         reference's NCDHW tensor [B,3,T,H,W] or the channels-last [B,T,H,W,3] the engine works on; the result has x's layout.  The
         kernel writes the (h,w)-folded tensor the network consumes (flk_perturb_apply_s2d); it is unfolded here.  A uint8 ``x`` holds
         the frames themselves: they are normalised on the device (dataset.py:28-29), the result is the fp32 clip of the normalised input."""
@@ -144,7 +147,7 @@ class Perturbation:
         B, T, H, W, _ = xcl.shape
         if T != self.T:
             raise ValueError(f"clip has {T} frames, the perturbation {self.T}")
-        folded = ops.perturb_apply_s2d(self.apply_args(xcl, bool(adversarial)), torch.float32)      # [B,T,H/2,W/2,16]
+        folded = ops.perturb_apply_s2d(self.apply_args(xcl, bool(adversarial), quantise=bool(quantise)), torch.float32)      # [B,T,H/2,W/2,16]
         out = folded[..., :12].reshape(B, T, H // 2, W // 2, 2, 2, 3).permute(0, 1, 2, 4, 3, 5, 6).reshape(B, T, H, W, 3)
         return out.permute(0, 4, 1, 2, 3).contiguous() if ncdhw else out.contiguous()
 
@@ -290,8 +293,15 @@ class FlickerVideoResNet:
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
-                 im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean"):
+                 im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False):
         from .i3d_engine import check_optimizer
+        # quantise_train: the attack is optimised on the STORED video.  Every adversarial forward (``step`` in all its variants,
+        # ``logits(x, True)``) applies decode(encode_u8(x_adv)) -- the 8-bit round trip inside the apply kernel, straight-through gradient --
+        # so its logits are bit for bit ``quantised_logits(x)`` for the delta the step ran with, and the ``argmax`` / ``is_adversarial``
+        # that ``step``, ``fit_single_video_attack``, ``fit_many_videos`` and ``train_an_epoch`` act on is the stored video's verdict: a
+        # quantised stopping rule at no extra forward pass.  Clean forwards are not quantised (a uint8 clip is its own round trip).
+        # (With cyclic_pert the step draws a roll; ``quantised_logits`` exports at phase 0 -- the identity is per roll.)
+        self.quantise_train = bool(quantise_train)
         # clips_per_video = G > 1: the batch holds V = B / G videos of G clips each (video-major, sample-minor, as ``prepare_videos`` cuts
         # them) and the adversarial loss is taken on every video's aggregated logits -- video_reduce "sum" (what ``evaluate_videos``
         # decides on) or "mean" (the sum / G: same argmax, margin and CE on the scale of one clip's logits) -- with one label per video
@@ -373,7 +383,7 @@ class FlickerVideoResNet:
 
     def _forward(self, x, adversarial):
         """Perturbation -> network: the apply arguments of this call (the backward pass masks with the same) ; logits in self._logits"""
-        a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold)
+        a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold, quantise=self.quantise_train and bool(adversarial))
         self.net.forward_apply(a, self._xs, self._logits)           # the plan applies the perturbation in front of its stem
         return a
 
@@ -1081,7 +1091,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean"):
+                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1095,6 +1105,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
-                         clips_per_video=clips_per_video, video_reduce=video_reduce)
+                         clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -247,6 +247,24 @@ typedef struct {
                                 one batch; the delta-gradient then comes back per clip, [B,T,3].  0: one delta [T,3] shared by the batch */
   const float* dclip_dev;    /* delta_per_clip only, or NULL: per-clip clamp bounds [B] on the device replacing `dclip` -- the torch loop grows a
                                 video's bound by 1.3 when it restarts (model.py:1061-1066), independently per video */
+  const float* q_lut;        /* NULL = off.  Quantised apply (8-bit straight-through): fp32 [256][3] on the device, byte v of channel c decodes
+                                to q_lut[v * 3 + c].  Every value flk_perturb_apply_s2d writes becomes the value the STORED video holds:
+                                  x_adv = the value written today (center = 0);   q = the encode of flk_export_args on x_adv with q_mul[c],
+                                  q_add[c], q_levels (the same device function: each operation rounded on its own, half to even,
+                                  saturating, NaN -> 0);   x_q = q_lut[q * 3 + c]
+                                and x_q goes through the fold, the bf16 rounding and the split of fold_t = 4 as x_adv does, whatever adv_flag
+                                is.  So a quantised apply is, bit for bit, the clean apply (adv_flag = 0, lo = -inf, hi = +inf: what a clean
+                                forward uses) of the bytes flk_adv_export_u8 writes for the same arguments, decoded through x_lut = q_lut
+                                (TF: x_scale / x_bias).  x_q is NOT clamped again: a value the clamp holds at lo or hi is stored as the
+                                level nearest the bound (the torch dialect's bounds are byte values of one channel only), and the stored
+                                video decodes to that level, up to half a level outside [lo, hi].
+                                FLK_EINVAL before any GPU call with center != 0 or q_levels <= 0; refused by the I3D-only entry points as
+                                x_lut is.  flk_adv_export_u8 ignores the four fields: it already is the quantiser.
+                                Gradient: the straight-through estimator d(x_q)/d(u) := 1[lo <= u <= hi], u = x + a p' -- exactly the mask
+                                flk_perturb_grad_reduce computes from x, delta and the clamp bounds; its kernels do not read the four
+                                fields and give the same bits with and without them.  (The four fields sit in front of x_lut, which
+                                stays the struct's last field; a zero-initialised struct keeps its meaning) */
+  float q_mul[3], q_add[3], q_levels;   /* the encode of flk_export_args: mul, add, levels (torch: std, mean, 255; TF: 1, 1, 128) */
   const float* x_lut;        /* uint8 x only, or NULL: per-channel decode table fp32 [256][3] on the device, x = x_lut[u8 * 3 + c], replacing
                                 x_scale / x_bias -- the VideoResNet decode (u8 / 255 - mean[c]) / std[c] (dataset.py:28-29), whose float32
                                 value no scalar multiply-add reproduces bit for bit (videoresnet_spec.u8_decode_table).  Refused with
@@ -261,7 +279,8 @@ int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dtype, void* s
  *   y = x_adv * mul[c] + add[c];   z = y * levels;   q = z >= 0 ? min(rint(z), 255) : 0        (rint: half to even; NaN -> 0)
  * torch dialect: mul = std, add = mean, levels = 255 (inverse of (u8/255 - mean)/std); TF dialect: mul = 1, add = 1, levels = 128
  * (inverse of u8/128 - 1).  out: uint8 [B,T,H,W,3], plain layout; clip b at out + (out_clip_offset + b) * out_clip_stride BYTES, so a
- * call can fill rows of a batch buffer.  a->fold_t is ignored, a->center must be 0, T, H and W may be any positive numbers.  One
+ * call can fill rows of a batch buffer.  a->fold_t and a->q_lut / q_mul / q_add / q_levels are ignored (this IS the quantiser: the encode
+ * is e's), a->center must be 0, T, H and W may be any positive numbers.  One
  * launch, no allocation, no synchronisation; 4-byte stores wherever the destination is aligned, bytes at the heads and tails of a
  * frame; the result does not depend on the launch geometry.
  * delta_T (0: a->T; flicker delta [delta_T,3] only): frame t takes row (t - shift_p) mod delta_T -- a universal flicker of period

@@ -60,7 +60,7 @@ def run_whole_videos(a):
     learner = FlickerVideoResNet(a.base_model, W, batch_size=G if G > 1 else a.batch, sample_length=T, image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
-                                 clips_per_video=G, video_reduce=a.video_reduce)
+                                 clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
@@ -152,6 +152,9 @@ def main():
                     "the sum of a video's clip logits")
     ap.add_argument("--save-adversarial-u8", action="store_true", help="the result files also hold adv_video_u8 -- the attacked clip under its "
                     "final perturbation as 8-bit frames, uint8 [B,T,H,W,3], written by one kernel -- with quantised_pred and quantised_is_adversarial")
+    ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
+                    "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
+                    "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
     ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="is the STORED video still adversarial?  clip: the result "
                     "files hold quantised_pred / quantised_is_adversarial of the clip's 8-bit frames; video (whole-video files, --batch 1): the "
                     "final flicker over the whole video at its own resolution, scored by the clean evaluation -- quantised_video_pred, "
@@ -190,7 +193,7 @@ def main():
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
-                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

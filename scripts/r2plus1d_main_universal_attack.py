@@ -155,7 +155,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
-                                 clips_per_video=a.clips_per_video, video_reduce=a.video_reduce)
+                                 clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train)
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -287,6 +287,9 @@ def main():
     ap.add_argument("--save-adversarial-u8", action="store_true", help="after training, write the validation set under the universal perturbation "
                     "as 8-bit frames: quantised_eval.npz gains adv_clips_u8 uint8 [N,T,H,W,3] (files of clips); adversarial_u8.npz holds every "
                     "whole validation video flickered at its own resolution (whole-video files)")
+    ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
+                    "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
+                    "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
     ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="after training, score the attack as 8-bit frames deliver "
                     "it.  clip: every validation clip exported at the engine's size (quantised_eval.npz; whole-video files: "
                     "video_eval_quantised.npz); video (whole-video files): every validation video flickered whole at its own resolution, "
@@ -333,7 +336,7 @@ def main():
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
-                                 augment=None if host_aug else augment)
+                                 augment=None if host_aug else augment, quantise_train=a.quantise_train)
     host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
