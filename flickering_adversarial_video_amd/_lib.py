@@ -122,6 +122,8 @@ _SIGS = {
     "flk_adv_export_u8": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(ExportArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_perturb_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_flicker_rows_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "flk_flicker_rows_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_sampled": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

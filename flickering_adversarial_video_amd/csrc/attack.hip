@@ -960,3 +960,62 @@ extern "C" int flk_perturb_dense_l12_pgd(const flk_dense_adam_args* a, const flo
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
+
+// ---- flicker on video time: per-frame rows of a period-P perturbation (include/flicker_hip.h) ------------------------------------
+// rows[b*T + t] names the row of the shared delta [P,3] that frame t of clip b carries.  The gather hands the apply / export / gradient
+// kernels a per-clip delta [B,T,3] (flk_apply_args.delta_per_clip); the row gradient folds their per-clip gradient back to [P,3].
+constexpr int ROWS_MAX_P = (256 * ADAM_PER) / 3;      // 682: what reg_adam_kernel holds
+constexpr int ROWS_PIECE = 2048;                      // entries of `rows` staged in LDS at a time (8 KiB)
+
+// one thread = one value of delta_clip; raw values (the clamp and 1/std stay in pert_at); a row outside [0,P) is clamped into it
+__global__ __launch_bounds__(256) void flicker_rows_gather_kernel(const float* delta, int P, const int32_t* rows, int n, float* delta_clip) {
+  const long total = 3L * n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int f = (int)(i / 3), c = (int)(i - 3L * f);
+    int r = rows[f];
+    r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
+    delta_clip[i] = delta[r * 3 + c];
+  }
+}
+
+// one thread = one output (row r, channel c): it walks the table in ascending i and adds the frames that carry its row, so every sum has
+// ONE fixed order whatever the grid.  The table is staged in LDS piece by piece by the whole workgroup (one HBM read of `rows` per
+// workgroup, at most 8 workgroups); all lanes of a wave read the same LDS entry (a broadcast).  g_clip is read only on a hit: 3*n
+// loads over the launch.  Threads past the last output still stage and meet every barrier.
+__global__ __launch_bounds__(256) void flicker_rows_grad_kernel(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows) {
+  __shared__ int32_t sh[ROWS_PIECE];
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const bool live = o < 3 * P;
+  const int r = o / 3, c = o - 3 * r;
+  float s = 0.f;
+  for (int base = 0; base < n; base += ROWS_PIECE) {
+    const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
+    for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
+    __syncthreads();
+    if (live)
+      for (int j = 0; j < m; ++j)
+        if (sh[j] == r) s += g_clip[(size_t)(base + j) * 3 + c];
+    __syncthreads();            // sh is refilled by the next piece
+  }
+  if (live) g_rows[o] = s;
+}
+
+extern "C" int flk_flicker_rows_gather(const float* delta, int P, const int32_t* rows, int n, float* delta_clip, void* stream) {
+  FLK_REQUIRE(delta && rows && delta_clip, "flk_flicker_rows_gather: null argument");
+  FLK_REQUIRE(n >= 1, "flk_flicker_rows_gather: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_gather: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  const long blocks = (3L * n + 255) / 256;
+  FLK_LAUNCH_KERNEL(flicker_rows_gather_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
+                     delta_clip);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows, void* stream) {
+  FLK_REQUIRE(g_clip && rows && g_rows, "flk_flicker_rows_grad: null argument");
+  FLK_REQUIRE(n >= 1, "flk_flicker_rows_grad: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  FLK_LAUNCH_KERNEL(flicker_rows_grad_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, P, g_rows);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}

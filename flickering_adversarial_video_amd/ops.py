@@ -500,6 +500,63 @@ def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):
     return gdelta
 
 
+FLICKER_MAX_PERIOD = 682      # 3 * P values are what flk_perturb_reg_adam holds (256 threads x 8)
+
+
+def _check_rows(what, rows, P, rows_host):
+    """the device table of flk_flicker_rows_*: int32, contiguous, on the device, any shape (n = its element count).  ``rows_host``: the
+    host copy it was uploaded from -- same shape, every entry inside [0,P) (the kernels clamp / skip a bad entry; here it is refused)"""
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 1 <= P <= FLICKER_MAX_PERIOD:
+        raise ValueError(f"{what}: the period must be an integer in 1..{FLICKER_MAX_PERIOD}, got {P!r}")
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dtype == torch.int32 and rows.is_contiguous() and rows.numel() >= 1):
+        desc = f"{tuple(rows.shape)} {rows.dtype} on {rows.device}" if torch.is_tensor(rows) else type(rows).__name__
+        raise ValueError(f"{what}: rows must be a non-empty contiguous int32 tensor on the device, got {desc}")
+    if rows_host is not None:
+        h = np.asarray(rows_host)
+        if tuple(h.shape) != tuple(rows.shape) or h.dtype.kind not in "iu":
+            raise ValueError(f"{what}: rows_host must be the integer table {tuple(rows.shape)} the device rows were uploaded from, got {h.shape} {h.dtype}")
+        if h.min() < 0 or h.max() >= P:
+            raise ValueError(f"{what}: rows must lie in [0,{P}), got {int(h.min())} .. {int(h.max())}")
+
+
+def _check_f32(what, name, t, shape, like):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.device == like.device):
+        desc = f"{tuple(t.shape)} {t.dtype} on {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor {tuple(shape)} on {like.device}, got {desc}")
+
+
+def flicker_rows_gather(delta, rows, out=None, rows_host=None):
+    """delta_clip[..., c] = delta[rows[...], c] (flk_flicker_rows_gather, one launch): the shared flicker perturbation ``delta`` fp32 [P,3]
+    spread over the frames of a batch by their ``rows`` (int32 on the device, e.g. [B,T]; videoresnet_spec.flicker_rows makes the table)
+    -> fp32 ``rows.shape + (3,)``, the per-clip perturbation ``make_apply_args`` takes.  Raw values.  ``out``: the buffer to fill."""
+    what = "flicker_rows_gather"
+    if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
+        raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
+    P = int(delta.shape[0])
+    _check_rows(what, rows, P, rows_host)
+    _check_f32(what, "delta", delta, (P, 3), rows)
+    if out is None:
+        out = torch.empty((*rows.shape, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (*rows.shape, 3), rows)
+    check(load().flk_flicker_rows_gather(ptr(delta), P, ptr(rows), rows.numel(), ptr(out), stream_ptr()))
+    return out
+
+
+def flicker_rows_grad(g_clip, rows, period, out=None, rows_host=None):
+    """g_rows[r, c] = the sum of g_clip[i, c] over the frames i with rows[i] == r (flk_flicker_rows_grad, one launch): the per-clip gradient
+    of ``perturb_grad_reduce`` (fp32 ``rows.shape + (3,)``) folded back onto the rows of the shared perturbation -> fp32 [period,3].
+    fp32 additions in ascending frame order from +0; a row no frame carries is 0.  ``out``: the buffer to fill."""
+    what = "flicker_rows_grad"
+    _check_rows(what, rows, period, rows_host)
+    _check_f32(what, "g_clip", g_clip, (*rows.shape, 3), rows)
+    P = int(period)
+    if out is None:
+        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (P, 3), rows)
+    check(load().flk_flicker_rows_grad(ptr(g_clip), ptr(rows), rows.numel(), P, ptr(out), stream_ptr()))
+    return out
+
+
 class StemDeltaGradWeights:
     """fp32 weights of flk_stem_delta_grad: canonical stem weights [7,7,7,3,64] x folded batch-norm scale [64]"""
 

@@ -12,8 +12,29 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, check_sampling, resolve_model, sample_frame_indices, split_sampling,
-                               train_crop_params, u8_decode_table)
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, check_sampling, flicker_rows, resolve_model, sample_frame_indices,
+                               split_sampling, train_crop_params, u8_decode_table)
+
+FLICKER_TIMES = ("clip", "video")
+
+
+def check_flicker_time(flicker_time, flicker_period, sample_length, attack_type="flickering", per_clip=False):
+    """the period of the perturbation (its row count) for a ``flicker_time`` / ``flicker_period`` pair: ``sample_length`` on clip time; on
+    video time ``flicker_period`` (None: ``sample_length``), 1..ops.FLICKER_MAX_PERIOD.  Host-only; anything else is a ValueError"""
+    if flicker_time not in FLICKER_TIMES:
+        raise ValueError(f"flicker_time must be one of {FLICKER_TIMES}, got {flicker_time!r}")
+    if flicker_time == "clip":
+        if flicker_period is not None:
+            raise ValueError("flicker_period needs flicker_time='video': on clip time the perturbation has one row per frame of the clip")
+        return int(sample_length)
+    if attack_type != "flickering" or per_clip:
+        raise ValueError("flicker_time='video': the flickering attack with one shared perturbation only (a dense or per-clip perturbation "
+                         "belongs to its clip, not to the video's frame numbers)")
+    P = sample_length if flicker_period is None else flicker_period
+    if isinstance(P, bool) or not isinstance(P, (int, np.integer)) or not 1 <= P <= ops.FLICKER_MAX_PERIOD:
+        raise ValueError(f"flicker_period must be an integer in 1..{ops.FLICKER_MAX_PERIOD} (3 * period values are what the update kernel holds), got {P!r}")
+    return int(P)
+
 
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 CLIP_DTYPES = (torch.float32, torch.uint8)
@@ -31,14 +52,30 @@ def decode_table(device):
 
 class Perturbation:
     """model.py:58-129.  size = [3,T,1,1] (flickering) or [3,T,H,W] (the dense "L12" attack, model.py:380-384); the parameter
-    is stored time-major / channels-last on the device: [T,3] or [T,H,W,3]."""
+    is stored time-major / channels-last on the device: [T,3] or [T,H,W,3].
 
-    def __init__(self, size, requires_grad=True, device="cuda", max_value=None, min_value=None, max_norm=1.0, cyclic_pert=False, batch=None):
+    ``clip_length`` (flickering, one shared perturbation): the flicker runs on VIDEO time.  ``size`` is then [3,P,1,1], P the flicker's period
+    (``self.T``, the row count of everything the optimiser sees), ``clip_length`` the frames of a clip (``self.clip_T``), and frame t of
+    clip b carries row ``(frame_numbers[b,t] - phase) mod P`` (videoresnet_spec.flicker_rows; ``set_frame_numbers``, default ``arange``):
+    every adversarial apply gathers its per-clip perturbation [B,clip_T,3] through that table (ops.flicker_rows_gather) and goes through
+    the per-clip path of the kernels.  ``cyclic_pert`` then draws one phase per VIDEO (``clips_per_video`` consecutive clips) per
+    adversarial forward -- a flicker not synchronised with the video's start; the phases last used are kept on ``last_phases``."""
+
+    def __init__(self, size, requires_grad=True, device="cuda", max_value=None, min_value=None, max_norm=1.0, cyclic_pert=False, batch=None,
+                 clip_length=None, clips_per_video=1):
         if len(size) != 4 or size[0] != 3:
             raise ValueError(f"perturbation size must be [3,T,1,1] or [3,T,H,W], got {tuple(size)}")
         self.size, self.device, self.requires_grad = tuple(size), device, requires_grad
         self.T = size[1]
         self.dense = not (size[2] == 1 and size[3] == 1)
+        self.video_time = clip_length is not None
+        self.clip_T = int(clip_length) if self.video_time else self.T          # frames of a clip (T rows on clip time, by definition)
+        if self.video_time and (self.dense or batch is not None):
+            raise ValueError("clip_length (flicker on video time): flickering perturbations shared by the batch only")
+        self.clips_per_video = int(clips_per_video)
+        self.frame_numbers = None        # video time: int64 [B,clip_T] of the current batch, None = arange(clip_T) for every clip
+        self.last_phases = None          # video time: the phases (one per video) of the last adversarial apply
+        self.rows_host = self.rows_dev = self._delta_clip = None      # the rows table last uploaded, its device copy, the gathered perturbation
         # batch = B (flickering only): B INDEPENDENT perturbations [B,T,3], one per clip of the batch, each with its own clamp bound
         # (``dyn_max_norm_dev`` [B]) -- single-video attacks advancing together (fit_many_videos, model.py:791-982)
         self.batch = batch
@@ -95,14 +132,61 @@ class Perturbation:
             p = perturbation
         self.perturbation = torch.from_numpy(self._to_dev(p)).cuda()
 
-    def apply_args(self, x, adversarial=True, fold_t=1, quantise=False):
+    def set_frame_numbers(self, table):
+        """video time: the frame numbers of the clips the next applies see -- integers ``[B,clip_T]`` (a table of
+        videoresnet_spec.sample_frame_indices, stacked video-major and sample-minor), or None: ``arange(clip_T)`` for every clip"""
+        if table is not None:
+            table = np.asarray(table)
+            if table.ndim != 2 or table.shape[1] != self.clip_T or table.dtype.kind not in "iu":
+                raise ValueError(f"frame numbers must be an integer table [B,{self.clip_T}], got {table.shape} {table.dtype}")
+            table = np.ascontiguousarray(table, dtype=np.int64)
+        self.frame_numbers = table
+
+    def delta_clip(self, B, phases="draw"):
+        """video time: the per-clip perturbation [B,clip_T,3] of the current frame numbers (a buffer reused from call to call, valid
+        until the next one).  ``phases``: "draw" = one per video from the generator when ``cyclic_pert`` (else 0), or an integer / one
+        integer per video; None: the buffer as it is, nothing gathered (a clean apply reads no perturbation).  The table goes to the
+        device only when it differs from the one already there."""
+        if self.frame_numbers is not None and self.frame_numbers.shape[0] != B:
+            raise ValueError(f"{B} clips, but the frame numbers set are for {self.frame_numbers.shape[0]} (set_frame_numbers)")
+        if self._delta_clip is None or self._delta_clip.shape[0] != B:
+            self._delta_clip = torch.zeros((B, self.clip_T, 3), dtype=torch.float32, device=self.perturbation.device)
+        if phases is None:
+            return self._delta_clip
+        G = self.clips_per_video
+        if isinstance(phases, str):
+            if phases != "draw":
+                raise ValueError(f"phases must be 'draw', an integer or one integer per video, got {phases!r}")
+            phases = self._rng.integers(0, self.T, size=-(-B // G)) if self.cyclic_pert else 0
+        ph = np.asarray(phases, dtype=np.int64)
+        if ph.ndim:
+            if ph.shape != (-(-B // G),):
+                raise ValueError(f"{ph.shape} phases for {B} clips of {G} per video: one per video, or a scalar")
+            ph = np.repeat(ph, G)[:B]
+        self.last_phases = np.broadcast_to(np.asarray(phases, dtype=np.int64), (-(-B // G),)).copy()
+        fn = self.frame_numbers if self.frame_numbers is not None else np.broadcast_to(np.arange(self.clip_T, dtype=np.int64), (B, self.clip_T))
+        rows = flicker_rows(fn, self.T, ph)
+        if self.rows_host is None or rows.shape != self.rows_host.shape:
+            self.rows_dev = torch.from_numpy(rows).to(self.perturbation.device)
+            self.rows_host = rows
+        elif not np.array_equal(rows, self.rows_host):
+            self.rows_dev.copy_(torch.from_numpy(rows))
+            self.rows_host = rows
+        return ops.flicker_rows_gather(self.perturbation, self.rows_dev, out=self._delta_clip)
+
+    def apply_args(self, x, adversarial=True, fold_t=1, quantise=False, phases="draw"):
         """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans).
         x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
         ``videoresnet_spec.normalize_u8`` makes on the host).  quantise: every value goes through the 8-bit round trip of ``export_u8``
         inside the apply kernel (flk_apply_args.q_lut) -- the clip applied is the one the exported frames decode to, bit for bit"""
-        shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
+        delta = self.perturbation
+        if self.video_time:
+            # the roll is in the rows; a clean apply reads no perturbation (adv_flag 0), so it gathers nothing and keeps the table
+            delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None), 0
+        else:
+            shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
         inf = float("inf")
-        return ops.make_apply_args(x, self.perturbation, dialect="torch", dclip=self.dynamic_max_norm,
+        return ops.make_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm,
                                    adv_flag=1.0 if adversarial else 0.0, shift_p=shift,
                                    inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                    lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf, fold_t=fold_t,
@@ -112,9 +196,14 @@ class Perturbation:
 
     def export_args(self, x, adversarial=True, shift_p=0, delta_T=0):
         """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
-        frames of a cyclic perturbation are exported at the phase ``shift_p`` the caller names"""
+        frames of a cyclic perturbation are exported at the phase ``shift_p`` the caller names.  Video time: clips (``delta_T`` 0) take
+        their rows at that phase (one per video, or a scalar) through the per-clip path; a whole video (``delta_T`` = the period) takes
+        the shared perturbation itself -- the kernel's own rule IS the one the rows follow"""
         inf = float("inf")
-        return ops.make_export_apply_args(x, self.perturbation, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
+        delta = self.perturbation
+        if self.video_time and not delta_T:
+            delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None), 0
+        return ops.make_export_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
                                           shift_p=shift_p, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                           lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf,
                                           dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
@@ -130,8 +219,8 @@ class Perturbation:
         ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
         xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
         xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
-        if xcl.shape[1] != self.T:
-            raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.T}")
+        if xcl.shape[1] != self.clip_T:
+            raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.clip_T}")
         return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p), "torch", out=out, out_offset=out_offset, stats=stats)
 
     def forward(self, input, quantise=False):
@@ -145,8 +234,8 @@ class Perturbation:
         xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
         xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
         B, T, H, W, _ = xcl.shape
-        if T != self.T:
-            raise ValueError(f"clip has {T} frames, the perturbation {self.T}")
+        if T != self.clip_T:
+            raise ValueError(f"clip has {T} frames, the perturbation {self.clip_T}")
         folded = ops.perturb_apply_s2d(self.apply_args(xcl, bool(adversarial), quantise=bool(quantise)), torch.float32)      # [B,T,H/2,W/2,16]
         out = folded[..., :12].reshape(B, T, H // 2, W // 2, 2, 2, 3).permute(0, 1, 2, 4, 3, 5, 6).reshape(B, T, H, W, 3)
         return out.permute(0, 4, 1, 2, 3).contiguous() if ncdhw else out.contiguous()
@@ -293,8 +382,16 @@ class FlickerVideoResNet:
 
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
-                 im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False):
+                 im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
+                 flicker_time="clip", flicker_period=None):
         from .i3d_engine import check_optimizer
+        # flicker_time "video": the flicker runs on VIDEO time, as ``export_video`` delivers it -- a perturbation of period P =
+        # ``flicker_period`` (default: sample_length) rows, frame t of clip b carrying row (frame number - phase) mod P, the frame numbers
+        # being those the clips were cut at (``prepare_videos`` / whole-video loaders: ``last_sampling``; pre-cut clips:
+        # ``set_frame_numbers``; nothing set: 0..T-1).  "clip" (default): row t for frame t of every clip, as ever.  Checked before
+        # anything touches the device
+        self.P = check_flicker_time(flicker_time, flicker_period, sample_length, attack_type, per_clip)
+        self.flicker_time, self.video_time = flicker_time, flicker_time == "video"
         # quantise_train: the attack is optimised on the STORED video.  Every adversarial forward (``step`` in all its variants,
         # ``logits(x, True)``) applies decode(encode_u8(x_adv)) -- the 8-bit round trip inside the apply kernel, straight-through gradient --
         # so its logits are bit for bit ``quantised_logits(x)`` for the delta the step ran with, and the ``argmax`` / ``is_adversarial``
@@ -362,8 +459,9 @@ class FlickerVideoResNet:
         self.per_clip = bool(per_clip)
         if self.per_clip and (attack_type != "flickering" or cyclic_pert or self.world > 1):
             raise ValueError("per_clip: flickering attack, no cyclic roll, one rank")
-        self.pert_model = Perturbation((3, self.T, 1, 1) if attack_type == "flickering" else (3, self.T, self.H, self.W),
-                                       max_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, batch=self.B if self.per_clip else None)
+        self.pert_model = Perturbation((3, self.P, 1, 1) if attack_type == "flickering" else (3, self.T, self.H, self.W),
+                                       max_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, batch=self.B if self.per_clip else None,
+                                       clip_length=self.T if self.video_time else None, clips_per_video=G)
         dev = torch.device("cuda", device)
         tdt = torch.bfloat16 if dtype in ("bf16", torch.bfloat16) else torch.float32
         # bf16 plans take the clip as TWO bf16 numbers per value (32 channels, fold_t = 4: the stem sees x + delta/std to ~16 bits -- one
@@ -371,7 +469,9 @@ class FlickerVideoResNet:
         self._xs = torch.empty((self.B, self.T, self.H // 2, self.W // 2, self.net.input_channels), dtype=tdt, device=dev)
         self._gx = torch.empty((self.B, self.T, self.H // 2, self.W // 2, 16), dtype=tdt, device=dev)
         self._logits = torch.empty((self.B, self.num_classes), dtype=torch.float32, device=dev)
-        self._red = torch.zeros(parallel.payload_size(self.T), dtype=torch.float32, device=dev)
+        self._red = torch.zeros(parallel.payload_size(self.P), dtype=torch.float32, device=dev)
+        # video time: the per-clip gradient [B,T,3] the rows fold back to [P,3] (reused every step, like the rows and the gathered delta)
+        self._g_clip = torch.zeros((self.B, self.T, 3), dtype=torch.float32, device=dev) if self.video_time else None
         self._scratch = torch.empty(max(1, ops.load().flk_perturb_grad_scratch_bytes(self.B, self.T, self.H, self.W) // 4), dtype=torch.float32, device=dev)
         self._scalars = torch.empty(8, dtype=torch.float32, device=dev)
         self.adam_m = None if self.pgd else torch.zeros(self.pert_model._dev_shape, device=dev)
@@ -381,9 +481,10 @@ class FlickerVideoResNet:
             self.adam_steps = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.active = torch.ones(self.B, dtype=torch.int32, device=dev)
 
-    def _forward(self, x, adversarial):
+    def _forward(self, x, adversarial, phases="draw"):
         """Perturbation -> network: the apply arguments of this call (the backward pass masks with the same) ; logits in self._logits"""
-        a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold, quantise=self.quantise_train and bool(adversarial))
+        a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold, quantise=self.quantise_train and bool(adversarial),
+                                       phases=phases)
         self.net.forward_apply(a, self._xs, self._logits)           # the plan applies the perturbation in front of its stem
         return a
 
@@ -393,6 +494,21 @@ class FlickerVideoResNet:
             raise ValueError(f"clip must be a CUDA float32 or uint8 channels-last tensor {(self.B, self.T, self.H, self.W, 3)}, "
                              f"got {tuple(x.shape)} {x.dtype}")
         return x.contiguous()
+
+    def set_frame_numbers(self, table):
+        """flicker_time "video": the frame numbers of the batch the next forwards see -- integers ``[B,T]``, clip b's frame t being frame
+        ``table[b,t]`` of its video (pre-cut clips; ``prepare_videos`` sets it itself), or None: 0..T-1 for every clip.  The table stays
+        until the next one is set: clips from another source want their own"""
+        if not self.video_time:
+            raise ValueError("set_frame_numbers: an engine built with flicker_time='video' only (on clip time frame t takes row t)")
+        if table is not None and np.asarray(table).shape != (self.B, self.T):
+            raise ValueError(f"set_frame_numbers: an integer table {(self.B, self.T)}, got {np.asarray(table).shape}")
+        self.pert_model.set_frame_numbers(table)
+
+    @property
+    def last_phases(self):
+        """flicker_time "video": the phases, one per video of the batch, the last adversarial forward ran at"""
+        return self.pert_model.last_phases
 
     @staticmethod
     def _check_augment(augment):
@@ -458,6 +574,8 @@ class FlickerVideoResNet:
         kw = split_sampling(self.sampling, self.T, train)
         tables = [sample_frame_indices(int(v.shape[0]), num_samples=int(num_samples), rng=self._samp_rng, **kw) for v in videos]
         self.last_sampling = tables
+        if self.video_time:                                          # the batch's frame numbers, video-major and sample-minor like its clips
+            self.pert_model.set_frame_numbers(np.concatenate(tables))
         clips = [v for v in videos for _ in range(int(num_samples))]
         boxes = flips = None
         if train and self.augment is not None:
@@ -510,6 +628,7 @@ class FlickerVideoResNet:
         if quantise not in (None, "clip", "video"):
             raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
         adversarial = adversarial or quantise is not None
+        kept = self.pert_model.frame_numbers                            # video time: every batch below brings its own frame numbers
         clean, adv, flick = [], [], []
         exported = {}                                                   # quantise = "video": the flickered videos of the current batch
         for first in range(0, V * S, B):
@@ -518,6 +637,8 @@ class FlickerVideoResNet:
                               frame_idx=rows[ks])
             n = min(B, V * S - first)
             clean.append(self.logits(x, False)[:n].cpu())
+            if self.video_time:                                         # the rows of these clips' own frames, at phase 0 like the export
+                self.pert_model.set_frame_numbers(rows[ks])
             if quantise == "clip":
                 frames, st = self.adversarial_frames(x, stats=True)
                 adv.append(self.logits(frames, False)[:n].cpu())
@@ -532,7 +653,8 @@ class FlickerVideoResNet:
                                   frame_idx=rows[ks])
                 adv.append(self.logits(x, False)[:n].cpu())
             elif adversarial:
-                adv.append(self.logits(x, True)[:n].cpu())
+                adv.append(self.logits(x, True, phases=0)[:n].cpu())       # (phases: video time only -- clip time draws its roll as ever)
+        self.pert_model.frame_numbers = kept
 
         def score(parts):
             clip = torch.cat(parts).numpy()
@@ -580,9 +702,10 @@ class FlickerVideoResNet:
             raise ValueError(f"{what}: clips of one call must share a dtype, got {dtype} and {x.dtype}")
         return x.dtype
 
-    def logits(self, x, adversarial=False):
-        """model([x, adversarial]) (model.py:1028,1073)"""
-        self._forward(x, adversarial)
+    def logits(self, x, adversarial=False, phases="draw"):
+        """model([x, adversarial]) (model.py:1028,1073).  ``phases`` (flicker_time "video"): "draw" -- one per video when ``cyclic_pert``,
+        else 0 -- or the phase(s) to apply at"""
+        self._forward(x, adversarial, phases)
         return self._logits
 
     def adversarial_frames(self, x, out=None, stats=False, adversarial=True):
@@ -603,15 +726,15 @@ class FlickerVideoResNet:
 
     def export_video(self, video_u8, phase=0, stats=False):
         """the engine's flicker laid over a WHOLE video at its own resolution: ``video_u8`` uint8 ``[N,H,W,3]`` on the device -> uint8
-        ``[N,H,W,3]``, frame n perturbed by row ``(n - phase) mod T`` of the perturbation (period = the engine's T; the flicker is uniform
-        over a frame, so it needs no resize).  One kernel launch.  Flicker attacks with one shared perturbation only.  ``stats``: also the
-        int32 ``[N,3,4]`` table of ops.export_adversarial_u8."""
+        ``[N,H,W,3]``, frame n perturbed by row ``(n - phase) mod P`` of the perturbation (period P = the engine's T, or the ``flicker_period``
+        of an engine on video time; the flicker is uniform over a frame, so it needs no resize).  One kernel launch.  Flicker attacks with
+        one shared perturbation only.  ``stats``: also the int32 ``[N,3,4]`` table of ops.export_adversarial_u8."""
         if self.attack_type != "flickering" or self.per_clip:
             raise ValueError("export_video: the flickering attack with one shared perturbation only (a dense or per-clip perturbation belongs to its clip)")
         if not torch.is_tensor(video_u8) or video_u8.dim() != 4 or video_u8.dtype != torch.uint8 or video_u8.shape[-1] != 3 or not video_u8.is_cuda or video_u8.shape[0] < 1:
             raise ValueError("export_video: a CUDA uint8 tensor [N,H,W,3]")
-        a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.T)
-        res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.T)
+        a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.P)
+        res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.P)
         return (res[0][0], res[1][0]) if stats else res[0]
 
     def _check_video_labels(self, labels):
@@ -654,7 +777,7 @@ class FlickerVideoResNet:
             self._check_video_labels(labels)
         if not hasattr(self, "_slots"):
             dev = self._logits.device
-            self._slots = [dict(payload=torch.zeros(parallel.payload_size(self.T), dtype=torch.float32, device=dev),
+            self._slots = [dict(payload=torch.zeros(parallel.payload_size(self.P), dtype=torch.float32, device=dev),
                                 sm=torch.empty((V, self.num_classes), dtype=torch.float32, device=dev),
                                 pc=torch.empty((V, 4), dtype=torch.float32, device=dev),
                                 scalars=torch.zeros(8, dtype=torch.float32, device=dev)) for _ in range(RESULT_SLOTS)]
@@ -674,8 +797,13 @@ class FlickerVideoResNet:
         else:
             criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
         self.net.backward(self._dl, self._gx)
-        n = 3 * self.T
-        ops.perturb_grad_reduce(a, self._gx, red[:n].view(self.T, 3), self._scratch)
+        n = 3 * self.P                                          # (clip time: P == T)
+        if self.video_time:
+            # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame), then its frames folded onto their rows
+            ops.perturb_grad_reduce(a, self._gx, self._g_clip, self._scratch)
+            ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
+        else:
+            ops.perturb_grad_reduce(a, self._gx, red[:n].view(self.T, 3), self._scratch)
         ops.pack_batch_sums(pc, 1.0 / gbatch, red[n:])
         parallel.allreduce_sum_(red, self.pg)
         res = StepResult(adv_loss=red[n], softmax=sm, label_prob=pc[:, 1], _argmax_f=pc[:, 3], _labels=labels, _targeted=bool(criterion.targeted))
@@ -834,6 +962,8 @@ class FlickerVideoResNet:
                "perturbation/roughness": rough_l, "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": pert_l,
                "prob_clean_input": outputs_no_adv, "label": target.cpu().numpy(), "is_adversarial": isadv_l,
                "max_prob": maxp_l, "correct_cls_prob": corr_l, "restarts": new_chance}
+        if self.video_time:                                  # the perturbations above have flicker_period rows, not sample_length
+            res.update(flicker_time=self.flicker_time, flicker_period=self.P)
         if export_u8:
             frames = self.adversarial_frames(inputs)
             ql = self.logits(frames, False)
@@ -898,6 +1028,8 @@ class FlickerVideoResNet:
             result[f"{phase}/pert_roughness"] = float(np.abs(np.roll(p, 1, 1) - p).mean())
             result[f"{phase}/inf_norm"] = float(np.abs(p).max())
             result[f"{phase}/perturbation"] = p
+            if self.video_time:
+                result[f"{phase}/flicker_period"] = self.P
         return result
 
     def fit(self, data_loaders, criterion, metric, lr=1e-3, epochs=1, lr_gamma=0.1, lr_step_size=None, model_dir=None,
@@ -1091,7 +1223,8 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False):
+                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
+                 flicker_time="clip", flicker_period=None):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1105,6 +1238,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
         super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
-                         clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train)
+                         clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
+                         flicker_time=flicker_time, flicker_period=flicker_period)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -378,6 +378,27 @@ def sample_frame_indices(num_frames, sample_length, sample_step=1, num_samples=1
     return table
 
 
+def flicker_rows(frame_numbers, period, phase=0):
+    """The row of a period-``period`` flicker perturbation each frame carries on VIDEO time: ``rows = (frame_numbers - phase) mod period``,
+    int32 of ``frame_numbers``' shape, never negative whatever the sign of ``phase``.  ``frame_numbers``: integers of any shape -- a table
+    ``[clips, T]`` of ``sample_frame_indices`` or the numbers of a whole video; ``phase``: a scalar, or one value per clip (per leading row).
+    By definition this is the rule of ``flk_adv_export_u8`` with ``delta_T = period`` and ``shift_p = phase`` (include/flicker_hip.h:
+    "frame t takes row (t - shift_p) mod delta_T"), so a clip perturbed by these rows carries what the exported video shows at its frames."""
+    n = np.asarray(frame_numbers)
+    if n.dtype.kind not in "iu":
+        raise ValueError(f"flicker_rows: frame numbers must be integers, got {n.dtype}")
+    if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or period < 1:
+        raise ValueError(f"flicker_rows: period must be an integer >= 1, got {period!r}")
+    ph = np.asarray(phase)
+    if ph.dtype.kind not in "iu":
+        raise ValueError(f"flicker_rows: phase must be an integer or one integer per clip, got {ph.dtype}")
+    if ph.ndim:
+        if ph.ndim != 1 or n.ndim < 1 or ph.shape[0] != n.shape[0]:
+            raise ValueError(f"flicker_rows: {ph.shape} phases for frame numbers {n.shape}: one per clip (leading row) or a scalar")
+        ph = ph.reshape((-1,) + (1,) * (n.ndim - 1))
+    return np.mod(n.astype(np.int64) - ph.astype(np.int64), np.int64(period)).astype(np.int32, order="C")      # numpy's mod takes the divisor's sign
+
+
 def is_video_file(path):
     """whether an ``.npz`` holds whole videos (``video_00000``, ...) and not a ``clips`` array"""
     with np.load(path, allow_pickle=True) as z:

@@ -307,6 +307,23 @@ int64_t flk_perturb_grad_scratch_bytes(int B, int T, int H, int W);
 int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s2d, int dtype,
                             float* gdelta, float* partials, void* stream);
 
+/* Flicker on VIDEO time: a shared flicker perturbation delta [P,3] of period P (independent of the clip length T) laid over clips
+ * whose frames name their rows.  rows: DEVICE int32 [n], n = B*T clip-major -- rows[b*T + t] is the row of delta that frame t of clip b
+ * carries; for a clip cut from a video it is (frame number - phase) mod P, the rule flk_adv_export_u8 applies to a whole video with
+ * delta_T = P and shift_p = phase (videoresnet_spec.flicker_rows states it on the host).  Both kernels feed the per-clip-delta path the
+ * apply, export and gradient kernels already have (flk_apply_args.delta_per_clip); none of those kernels knows about the table.
+ *   flk_flicker_rows_gather: delta_clip[i][c] = delta[rows[i]][c], fp32 [n][3] -- RAW values: the clamp and 1/std stay in the apply.  A
+ *     row outside [0,P) is clamped into it (wrong data, never a wild read: the rule of flk_clip_prepare_sampled).
+ *   flk_flicker_rows_grad:   g_rows[r][c] = sum of g_clip[i][c] over the i with rows[i] == r, fp32 [P][3], added in ASCENDING i starting
+ *     from +0; a row no frame carries is written as 0 and an entry of rows outside [0,P) contributes nothing.  g_clip [n][3] is what
+ *     flk_perturb_grad_reduce writes with the per-clip arguments the clips were applied with: its stage 2 has applied adv_flag, 1/std
+ *     and the delta-clamp mask per (b,t) already, which is right here because all frames that share a row share its delta value.
+ *     Every element of g_rows is written exactly once, by one thread; no atomics; the table is staged in LDS in pieces.
+ * One launch each, no allocation, no synchronisation; the results do not depend on the launch geometry.
+ * FLK_EINVAL before any GPU call: null pointers, n < 1, P outside 1..682 (3*P values are what flk_perturb_reg_adam holds). */
+int flk_flicker_rows_gather(const float* delta, int P, const int32_t* rows, int n, float* delta_clip, void* stream);
+int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows, void* stream);
+
 /* Fused form of (stem data-gradient + flk_perturb_grad_reduce) for the flickering perturbation of I3D: d(loss)/d(delta[t,c]) straight
  * from G = d(loss)/d(pre-ReLU output of Conv3d_1a_7x7) (bf16 [B,T/2,H/2,W/2,g_ld], 64 channels) -- replaces Conv3DBackpropInputV2 of
  * i3d.py:169 and the clip_by_value / reduce_sum gradients of kinetics_i3d_utils.py:100-142 with ONE MFMA kernel in the weight-gradient

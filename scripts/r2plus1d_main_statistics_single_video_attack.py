@@ -17,7 +17,9 @@ it (dataset.py:500-586: `--sample-step`, `--temporal-jitter`, `--temporal-jitter
 (one clip at the uniform offset, step 1, no jitter, no shift).
 `--clips-per-video G` (whole-video files, `--batch 1`) attacks the video-level decision of the reference's evaluate(num_samples=G): the G
 clips at the evaluation's uniform offsets are cut from each video once and the adversarial loss is taken on their aggregated logits
-(`--video-reduce sum`, or `mean` = sum / G: same argmax); a video counts as adversarial when the argmax of those logits leaves its label."""
+(`--video-reduce sum`, or `mean` = sum / G: same argmax); a video counts as adversarial when the argmax of those logits leaves its label.
+`--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame carrying the row of
+its frame number in the video, which is what `--eval-quantised video` lays over the whole video; the result files hold `flicker_period`."""
 import argparse
 import os
 import sys
@@ -60,7 +62,8 @@ def run_whole_videos(a):
     learner = FlickerVideoResNet(a.base_model, W, batch_size=G if G > 1 else a.batch, sample_length=T, image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
-                                 clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train)
+                                 clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
@@ -155,6 +158,12 @@ def main():
     ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
                     "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
                     "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
+    ap.add_argument("--flicker-time", default="clip", choices=["clip", "video"], help="which row of the perturbation a frame carries.  clip: row t "
+                    "for frame t of every clip.  video: row (frame number - phase) mod period, the frame numbers being those the clip was cut "
+                    "at in its video -- the flicker the whole-video export lays over the video, so the loop trains on what is delivered "
+                    "(flickering attack, one shared perturbation; files of clips count their frames from 0)")
+    ap.add_argument("--flicker-period", type=int, default=None, help="--flicker-time video: rows of the perturbation = the flicker's period in "
+                    "frames (default: the clip length; 1..682)")
     ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="is the STORED video still adversarial?  clip: the result "
                     "files hold quantised_pred / quantised_is_adversarial of the clip's 8-bit frames; video (whole-video files, --batch 1): the "
                     "final flicker over the whole video at its own resolution, scored by the clean evaluation -- quantised_video_pred, "
@@ -193,7 +202,8 @@ def main():
     W = vs.load_weights(a.weights_npz, arch) if a.weights_npz else vs.synthetic_weights(arch, 42, num_classes=ncls)
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
-                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train)
+                                 optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train,
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -39,7 +39,11 @@ beside the checkpoints.  Both files of a run are of the same kind; files with a 
 `--clips-per-video G` (whole-video files only) attacks that video-level decision: a batch of `--batch-size` clips holds `--batch-size / G`
 videos, G clips are cut from each (training split: the sampling flags above; validation: the uniform offsets of the evaluation) and the
 adversarial loss is taken on each video's aggregated logits -- `--video-reduce sum` (the evaluation's own sum) or `mean` (the sum / G:
-same argmax, margin on the scale of one clip's logits).  Loss averages and fooling ratios then count videos."""
+same argmax, margin on the scale of one clip's logits).  Loss averages and fooling ratios then count videos.
+
+`--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame of every clip
+carrying the row of its frame number in its video -- what `--eval-quantised video` and `--save-adversarial-u8` lay over whole videos.
+The epoch results hold `flicker_period`."""
 import argparse
 import glob
 import os
@@ -155,7 +159,8 @@ def run_whole_videos(a, world, rank, local_rank, augment):
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
-                                 clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train)
+                                 clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -290,6 +295,12 @@ def main():
     ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
                     "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
                     "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
+    ap.add_argument("--flicker-time", default="clip", choices=["clip", "video"], help="which row of the perturbation a frame carries.  clip: row t "
+                    "for frame t of every clip.  video: row (frame number - phase) mod period, the frame numbers being those the clip was cut "
+                    "at in its video -- the flicker the whole-video export lays over the video, so the loop trains on what is delivered "
+                    "(flickering attack, one shared perturbation; files of clips count their frames from 0)")
+    ap.add_argument("--flicker-period", type=int, default=None, help="--flicker-time video: rows of the perturbation = the flicker's period in "
+                    "frames (default: the clip length; 1..682)")
     ap.add_argument("--eval-quantised", default=None, choices=["clip", "video"], help="after training, score the attack as 8-bit frames deliver "
                     "it.  clip: every validation clip exported at the engine's size (quantised_eval.npz; whole-video files: "
                     "video_eval_quantised.npz); video (whole-video files): every validation video flickered whole at its own resolution, "
@@ -336,7 +347,8 @@ def main():
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch_size, sample_length=T, image_size=HW, dtype=a.dtype,
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
-                                 augment=None if host_aug else augment, quantise_train=a.quantise_train)
+                                 augment=None if host_aug else augment, quantise_train=a.quantise_train,
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
     host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
