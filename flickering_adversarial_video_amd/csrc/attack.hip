@@ -312,6 +312,9 @@ static int check_apply(const flk_apply_args* a) {
   FLK_REQUIRE(!a->dclip_dev || a->delta_per_clip, "flk_perturb: dclip_dev (per-clip clamp bounds) needs delta_per_clip");
   FLK_REQUIRE(!a->x_lut || (a->x_is_u8 && !a->center), "flk_perturb: x_lut (per-channel decode table) needs a uint8 clip and center = 0");
   FLK_REQUIRE(!a->q_lut || (!a->center && a->q_levels > 0.f), "flk_perturb: q_lut (quantised apply) needs center = 0 and q_levels > 0");
+  // load6 reads a uint8 clip with 2-byte loads and an fp32 clip with 8-byte loads (every pixel pair starts at a multiple of 6 values)
+  if (a->x_is_u8) FLK_REQUIRE(((size_t)a->x & 1) == 0, "flk_perturb: a uint8 clip must be 2-byte aligned (got %p)", a->x);
+  else FLK_REQUIRE(((size_t)a->x & 7) == 0, "flk_perturb: an fp32 clip must be 8-byte aligned (got %p)", a->x);
   return FLK_OK;
 }
 
@@ -319,6 +322,7 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
   int rc = check_apply(a);
   if (rc) return rc;
   FLK_REQUIRE(out, "flk_perturb_apply_s2d: null out");
+  FLK_REQUIRE(((size_t)out & 15) == 0, "flk_perturb_apply_s2d: out must be 16-byte aligned (got %p)", out);
   const int ftl = (a->fold_t == 1 || a->fold_t == 4) ? 1 : a->fold_t == 3 ? 3 : 2, ft = ftl == 1 ? 1 : 2;
   const long total = (long)a->B * (a->T / ft) * (a->H / 2) * (a->W / 2);
   const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
@@ -342,7 +346,7 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
     return FLK_OK;
   }
   const bool bf = dtype == FLK_BF16;
-  if (ft == 2 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && a->T / 2 < 65536 && a->B < 65536) {
+  if (ft == 2 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T / 2 < 65536 && a->B < 65536) {
     const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)(a->T / 2), (unsigned)a->B);
 #define FLK_U8F(TT, L) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, true>), g3, dim3(256), 0, st, *a, (char*)out); \
                             else FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
@@ -633,6 +637,7 @@ extern "C" int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s
   int rc = check_apply(a);
   if (rc) return rc;
   FLK_REQUIRE(gx_s2d && gdelta, "flk_perturb_grad_reduce: null argument");
+  FLK_REQUIRE(((size_t)gx_s2d & 15) == 0, "flk_perturb_grad_reduce: gx_s2d must be 16-byte aligned (got %p)", gx_s2d);
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_perturb_grad_reduce: bad dtype");
   hipStream_t s = (hipStream_t)stream;
   // (fold_t = 4: the clip went in as two bf16 numbers per value; its gradient comes back in the 16-channel fold_t = 1 layout)
@@ -931,6 +936,8 @@ extern "C" int flk_perturb_dense_l12_adam(const flk_dense_adam_args* a, const fl
   FLK_REQUIRE(a && g_adv && delta && m && v && scratch, "flk_perturb_dense_l12_adam: null argument");
   FLK_REQUIRE(a->T > 0 && a->T <= 1024 && a->H > 0 && a->W > 0 && (a->H * a->W * 3) % 4 == 0, "flk_perturb_dense_l12_adam: bad dims");
   FLK_REQUIRE(a->step >= 1, "flk_perturb_dense_l12_adam: step is 1-based");
+  FLK_REQUIRE((((size_t)g_adv | (size_t)delta | (size_t)m | (size_t)v) & 15) == 0,
+              "flk_perturb_dense_l12_adam: g_adv, delta, m and v must be 16-byte aligned (got %p, %p, %p, %p)", (const void*)g_adv, (void*)delta, (void*)m, (void*)v);
   const int fe = a->H * a->W * 3;
   float* part = scratch;
   float* frame_rms = scratch + (size_t)a->T * DENSE_CHUNKS * 4;
@@ -949,6 +956,8 @@ extern "C" int flk_perturb_dense_l12_pgd(const flk_dense_adam_args* a, const flo
   FLK_REQUIRE(a->T > 0 && a->T <= 1024 && a->H > 0 && a->W > 0 && (a->H * a->W * 3) % 4 == 0, "flk_perturb_dense_l12_pgd: bad dims");
   const float eps = a->torch_dialect ? a->dyn_max_norm : a->pgd_eps;
   FLK_REQUIRE(eps > 0.f, "flk_perturb_dense_l12_pgd: the l-infinity radius (%s) must be positive (got %g)", a->torch_dialect ? "dyn_max_norm" : "pgd_eps", (double)eps);
+  FLK_REQUIRE((((size_t)g_adv | (size_t)delta) & 15) == 0, "flk_perturb_dense_l12_pgd: g_adv and delta must be 16-byte aligned (got %p, %p)",
+              (const void*)g_adv, (void*)delta);
   const int fe = a->H * a->W * 3;
   float* part = scratch;
   float* frame_rms = scratch + (size_t)a->T * DENSE_CHUNKS * 4;

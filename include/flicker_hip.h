@@ -218,7 +218,12 @@ int flk_maxpool3d_bwd_conv1x1(const flk_pool_args* a, const void* g, int g_ld, i
  * x: uint8 (x = u8*x_scale + x_bias, the TFRecord path pre_process_rgb_flow.py:226-234, or x = x_lut[u8][c]) or fp32,
  *    [B,T,H,W,3]; delta: fp32 [T,3] (flicker) or [T,H,W,3] (dense, "L12" baseline).
  * out: [B,T/2,H/2,W/2,32] of dtype: channel (qt*4+qh*2+qw)*3+c, channels 24..31 zero -- the
- * 7x7x7/2 stem (i3d.py:169) then runs as a 4x4x4/1 convolution on MFMA.  T,H,W must be even. */
+ * 7x7x7/2 stem (i3d.py:169) then runs as a 4x4x4/1 convolution on MFMA.  T,H,W must be even.
+ * Pointer contract (flk_perturb_apply_s2d and flk_perturb_grad_reduce; FLK_EINVAL naming the alignment, before any GPU call): a uint8
+ * clip x is 2-byte aligned and an fp32 clip 8-byte aligned (the kernels read a pixel pair at a time); out and gx_s2d are 16-byte
+ * aligned.  A uint8 clip that is not 8-byte aligned is served by the generic kernels instead of the 8-byte-load fast paths (fold_t 2 / 3
+ * flicker, fold_t 4 with x_lut): same bits, more load instructions.  delta, gdelta, partials and the tables are read and written
+ * one float at a time (4-byte aligned, as any float array is). */
 typedef struct {
   const void* x; int x_is_u8; float x_scale, x_bias;
   const float* delta; int delta_dense;
@@ -489,7 +494,9 @@ int flk_perturb_reg_pgd_batched(const flk_adam_args* a, int nclip, const float* 
  * model.py:211-214), loss = adv + beta1 * L12 (i3d_adversarial_main_universal.py:129-133), TF or torch Adam.
  * Two HBM-bound passes: per-frame sum of squares (deterministic two-stage reduction into frame_sq[T], fp32), then the
  * fused gradient + Adam update streaming delta, m, v, g_adv once (5 fp32 streams = 193 MB at T=64).
- * scalars[4] = {L12, thickness, roughness, max|delta|} of the PRE-update delta.  scratch: flk_dense_adam_scratch_bytes(). */
+ * scalars[4] = {L12, thickness, roughness, max|delta|} of the PRE-update delta.  scratch: flk_dense_adam_scratch_bytes().
+ * Pointer contract: g_adv, delta, m and v (flk_perturb_dense_l12_pgd: g_adv and delta) are 16-byte aligned -- the kernels stream them
+ * four floats at a time; anything else is FLK_EINVAL naming the alignment, before any GPU call. */
 typedef struct {
   int T, H, W;
   int torch_dialect;

@@ -99,31 +99,79 @@ LOSS_MODES = [("tf", True, False, False), ("tf", True, True, False), ("tf", True
               ("torch", False, False, True)]
 
 
-@pytest.mark.parametrize("dialect,improve,use_logits,targeted", LOSS_MODES)
-def test_loss_head_vs_oracle(ops, golden, dialect, improve, use_logits, targeted):
-    rng = np.random.default_rng(9)
-    lg = torch.from_numpy(np.concatenate([golden["loss_logits"], (rng.standard_normal((4, 400)) * 2).astype(np.float32)]))
-    labels = torch.from_numpy(np.concatenate([golden["loss_labels"], rng.integers(0, 400, 4)]))
-    labels[5] = int(lg[5].argmax())              # margin region u > m
-    labels[6] = int(lg[6].argsort()[-2])
-    if targeted:
-        labels[:] = 17 if dialect == "torch" else labels
-    B = lg.shape[0]
-    z = lg.clone().requires_grad_(True)
-    if dialect == "tf":
-        if improve:
-            loss, to_min, to_max = am.tf_improve_adversarial_loss(z, labels, 0.05, targeted, use_logits)
-        else:
-            loss, to_min, to_max = am.tf_ce_adversarial_loss(z, labels, targeted)
+# C = 400 (Kinetics) keeps its golden rows and its test ids; beside it the class counts the engines take from other weights -- 51 (a
+# replaced HMDB51 head), 359 and 487 (the IG65M tables) -- and the edges of adv_loss_row's PER = 4 trips of 256 threads: C < 256,
+# 256 / 257, and the limit 1024
+LOSS_CLASSES = (2, 51, 256, 257, 359, 487, 1024)
+SEED_BASE = 20               # rows of class count C are drawn with seed SEED_BASE + C (every case passes its conditioning check)
+HEAD_CASES = [(400,) + m for m in LOSS_MODES] + [(Cn,) + m for Cn in LOSS_CLASSES for m in LOSS_MODES]
+HEAD_IDS = ["-".join(str(v) for v in m) for m in LOSS_MODES] + [f"C{Cn}-" + "-".join(str(v) for v in m) for Cn in LOSS_CLASSES for m in LOSS_MODES]
+
+
+def planted_rows(Cn, seed):
+    """random logits [8,C] (standard normal * 2) with labels planted where the loss changes branch or the kernel indexes an edge: row 0
+    at its arg-max, row 1 at its runner-up, row 2 at class C-1, row 3 at class 0, row 4 a confident row (its label's logit raised to
+    6 above the row's maximum: 1 - p_label stays above 2e-3, so fp32 does not lose it); rows 4-7 labelled at random"""
+    rng = np.random.default_rng(seed)
+    lg = torch.from_numpy((rng.standard_normal((8, Cn)) * 2).astype(np.float32))
+    labels = torch.from_numpy(rng.integers(0, Cn, 8))
+    labels[0] = int(lg[0].argmax())
+    labels[1] = int(lg[1].argsort()[-2])
+    labels[2], labels[3] = Cn - 1, 0
+    lg[4, labels[4]] = lg[4].max() + 6.0
+    return lg, labels
+
+
+def assert_rows_on_both_sides(gref, what):
+    """an improve-loss case tests something only if the loss is active on some rows and flat on others"""
+    live = (gref != 0).flatten(1).any(1)
+    assert int(live.sum()) >= 2 and int((~live).sum()) >= 1, f"{what}: gradient rows non-zero {int(live.sum())}, zero {int((~live).sum())}"
+
+
+@pytest.mark.parametrize("Cn,dialect,improve,use_logits,targeted", HEAD_CASES, ids=HEAD_IDS)
+def test_loss_head_vs_oracle(ops, golden, Cn, dialect, improve, use_logits, targeted):
+    target = min(17, Cn - 1)                     # the torch dialect's target class
+    fp64 = Cn != 400                             # the new class counts: the oracle in fp64
+    if Cn == 400:
+        rng = np.random.default_rng(9)
+        lg = torch.from_numpy(np.concatenate([golden["loss_logits"], (rng.standard_normal((4, 400)) * 2).astype(np.float32)]))
+        labels = torch.from_numpy(np.concatenate([golden["loss_labels"], rng.integers(0, 400, 4)]))
+        labels[5] = int(lg[5].argmax())              # margin region u > m
+        labels[6] = int(lg[6].argsort()[-2])
     else:
-        p = torch.softmax(z, 1)
-        loss = am.torch_improve_loss(z, p, labels, 0.05, use_logits) if improve else am.torch_ce_loss(p, labels, targeted, 17)
-    (gref,) = torch.autograd.grad(loss, z)
+        lg, labels = planted_rows(Cn, SEED_BASE + Cn)
+    if targeted:
+        labels[:] = target if dialect == "torch" else labels
+    B = lg.shape[0]
+
+    def oracle(z):
+        z = z.requires_grad_(True)
+        if dialect == "tf":
+            if improve:
+                loss, to_min, to_max = am.tf_improve_adversarial_loss(z, labels, 0.05, targeted, use_logits)
+            else:
+                loss, to_min, to_max = am.tf_ce_adversarial_loss(z, labels, targeted)
+        else:
+            p = torch.softmax(z, 1)
+            loss = am.torch_improve_loss(z, p, labels, 0.05, use_logits) if improve else am.torch_ce_loss(p, labels, targeted, target)
+        (g,) = torch.autograd.grad(loss, z)
+        return loss, g
+
+    loss, gref = oracle(lg.double() if fp64 else lg.clone())
+    assert bool(torch.isfinite(gref).all()) and np.isfinite(loss.item())
+    if fp64:
+        # conditioning, from the oracle alone: the same formulas evaluated in fp32 must reach HALF the tolerances below -- where they do
+        # not (a margin that cancels, 1 - p next to 1), a difference says nothing about the kernel
+        loss32, g32 = oracle(lg.clone())
+        assert loss32.item() == pytest.approx(loss.item(), rel=5e-5, abs=5e-8)
+        torch.testing.assert_close(g32, gref.float(), rtol=1e-4, atol=5e-8)
+        if improve:
+            assert_rows_on_both_sides(gref, f"C {Cn} {dialect} logits {use_logits} targeted {targeted}")
     sm, dl, pc = ops.softmax_adv_loss(lg.cuda(), labels.cuda(), dialect=dialect, improve_loss=improve, use_logits=use_logits,
                                       targeted=targeted, margin=0.05, mean_scale=1.0 / B)
     torch.testing.assert_close(sm.cpu(), torch.softmax(lg, 1), rtol=1e-5, atol=1e-8)
     assert pc[:, 0].sum().item() == pytest.approx(loss.item(), rel=1e-4, abs=1e-7)
-    torch.testing.assert_close(dl.cpu(), gref, rtol=2e-4, atol=1e-7)
+    torch.testing.assert_close(dl.cpu(), gref.float(), rtol=2e-4, atol=1e-7)
     np.testing.assert_array_equal(pc[:, 3].cpu().numpy().astype(int), lg.argmax(1).numpy())
     np.testing.assert_allclose(pc[:, 1].cpu().numpy(), torch.softmax(lg, 1).gather(1, labels.view(-1, 1))[:, 0].numpy(), rtol=1e-5)
 

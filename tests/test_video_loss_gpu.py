@@ -26,7 +26,13 @@ LOSS_MODES = [("tf", True, False, False), ("tf", True, True, False), ("tf", True
 MODE_IDS = ["-".join([d, "improve" if i else "ce", "logits" if u else "prob", "targeted" if t else "untargeted"]) for d, i, u, t in LOSS_MODES]
 CLASSES = (5, 257, 400, 1024)              # 257 crosses the 256-thread stride, 1024 is the limit
 GROUPS = ((1, 1), (3, 3), (2, 10))         # (videos, clips per video)
-TARGET = 3                                 # the torch dialect's target class (< every C used)
+TARGET = 3                                 # the torch dialect's target class (< every C of CLASSES)
+# the class counts of tests/test_attack_gpu.py::test_loss_head_vs_oracle beside 400: the engines take C from the weights (51, 359, 487
+# occur), and adv_loss_row spreads C over 4 trips of 256 threads (C < 256, 256 / 257, 1024)
+OTHER_CLASSES = (2, 51, 256, 257, 359, 487, 1024)
+PLANTED_GROUPS = ((5, 1), (5, 3))          # five videos: the planted labels of make_planted_case
+SEED_BASE = 100                            # a planted case of C classes and G clips is drawn with seed SEED_BASE + C + 7 * G
+                                           # (every case passes its conditioning check)
 T, H = 8, 112
 
 
@@ -76,21 +82,46 @@ def make_case(V, G, Cn, scale, seed, targeted_torch=False):
     return z, labels
 
 
-def oracle(z, labels, V, G, scale, dialect, improve, use_logits, targeted):
-    zc = z.clone().requires_grad_(True)
+def make_planted_case(V, G, Cn, scale, seed, target=None):
+    """make_case with labels planted on the VIDEO logits where the loss changes branch or the kernel indexes an edge: video 0 at its
+    arg-max, video 1 at its runner-up, video 2 at class C-1, video 3 at class 0, video 4 confident (a random label whose video logit is
+    raised to 6 above the video's maximum -- 1 - p_label stays above 2e-3, so fp32 does not lose it; every clip carries its share)"""
+    assert V == 5
+    rng = np.random.default_rng(seed)
+    z = torch.from_numpy((rng.standard_normal((V * G, Cn)) * 2.0 / (scale * np.sqrt(G))).astype(np.float32))
+    zv = scale * z.view(V, G, Cn).sum(1)
+    labels = torch.tensor([int(zv[0].argmax()), int(zv[1].argsort()[-2]), Cn - 1, 0, int(rng.integers(0, Cn))])
+    z.view(V, G, Cn)[4, :, labels[4]] += float(zv[4].max() + 6.0 - zv[4, labels[4]]) / (scale * G)
+    if target is not None:
+        labels[:] = target
+    return z, labels
+
+
+def oracle(z, labels, V, G, scale, dialect, improve, use_logits, targeted, target=TARGET, fp64=False):
+    zc = (z.double() if fp64 else z.clone()).requires_grad_(True)
     zv = scale * zc.view(V, G, -1).sum(1)
     if dialect == "tf":
         loss = (am.tf_improve_adversarial_loss(zv, labels, 0.05, targeted, use_logits) if improve else am.tf_ce_adversarial_loss(zv, labels, targeted))[0]
     else:
         p = torch.softmax(zv, 1)
-        loss = am.torch_improve_loss(zv, p, labels, 0.05, use_logits) if improve else am.torch_ce_loss(p, labels, targeted, TARGET)
+        loss = am.torch_improve_loss(zv, p, labels, 0.05, use_logits) if improve else am.torch_ce_loss(p, labels, targeted, target)
     (g,) = torch.autograd.grad(loss, zc)
-    return loss.item(), g, zv.detach()
+    return loss.item(), g.float(), zv.detach().float()
 
 
-def check_against_oracle(out, z, labels, V, G, scale, mode):
+def check_against_oracle(out, z, labels, V, G, scale, mode, target=TARGET, fp64=False, both_sides=False):
     sm, dl, pv, vl = out
-    loss, gref, zv = oracle(z, labels, V, G, scale, *mode)
+    loss, gref, zv = oracle(z, labels, V, G, scale, *mode, target=target, fp64=fp64)
+    assert np.isfinite(loss) and bool(torch.isfinite(gref).all())
+    if fp64:
+        # conditioning, from the oracle alone: the same formulas evaluated in fp32 must reach HALF the tolerances below -- where they do
+        # not (a margin that cancels, 1 - p next to 1), a difference says nothing about the kernel
+        loss32, g32, _ = oracle(z, labels, V, G, scale, *mode, target=target)
+        assert loss32 == pytest.approx(loss, rel=5e-5, abs=5e-8)
+        torch.testing.assert_close(g32, gref, rtol=1e-4, atol=5e-8)
+    if both_sides:            # an improve-loss case tests something only if the loss is active on some videos and flat on others
+        live = (gref != 0).flatten(1).any(1).view(V, G).any(1)
+        assert int(live.sum()) >= 2 and int((~live).sum()) >= 1, f"C {z.shape[1]} {mode}: videos with a gradient {int(live.sum())}, without {int((~live).sum())}"
     print(f"mode {mode} V {V} G {G} C {z.shape[1]} scale {scale:.4f}: loss {pv[:, 0].sum().item():.6g} / oracle {loss:.6g}, "
           f"max |dlogits - oracle| {float((dl.cpu() - gref).abs().max()):.3g}")
     torch.testing.assert_close(vl.cpu(), zv, rtol=1e-6, atol=1e-6)
@@ -101,9 +132,25 @@ def check_against_oracle(out, z, labels, V, G, scale, mode):
     np.testing.assert_allclose(pv[:, 1].cpu().numpy(), torch.softmax(zv, 1).gather(1, labels.view(-1, 1))[:, 0].numpy(), rtol=1e-5)
 
 
-@pytest.mark.parametrize("mode", LOSS_MODES, ids=MODE_IDS)
-def test_video_head_vs_oracle(ops, mode):
+# the C = 400 cases keep their ids and run the whole of CLASSES, as before; the other class counts are cases of their own
+VIDEO_CASES = [(400, m) for m in LOSS_MODES] + [(Cn, m) for Cn in OTHER_CLASSES for m in LOSS_MODES]
+VIDEO_IDS = MODE_IDS + [f"C{Cn}-{i}" for Cn in OTHER_CLASSES for i in MODE_IDS]
+
+
+@pytest.mark.parametrize("Cn,mode", VIDEO_CASES, ids=VIDEO_IDS)
+def test_video_head_vs_oracle(ops, Cn, mode):
     dialect, improve, use_logits, targeted = mode
+    if Cn != 400:             # planted labels, fp64 oracle
+        target = min(TARGET, Cn - 1)
+        for V, G in PLANTED_GROUPS:
+            for reduce in ("sum", "mean"):
+                scale = scale_of(G, reduce)
+                z, labels = make_planted_case(V, G, Cn, scale, seed=SEED_BASE + Cn + 7 * G, target=target if targeted and dialect == "torch" else None)
+                out = ops.softmax_adv_loss_video(z.cuda(), labels.cuda(), G, reduce=reduce, dialect=dialect, improve_loss=improve,
+                                                 use_logits=use_logits, targeted=targeted, margin=0.05, mean_scale=1.0 / V)
+                assert tuple(out[0].shape) == (V, Cn) and tuple(out[1].shape) == (V * G, Cn) and tuple(out[2].shape) == (V, 4)
+                check_against_oracle(out, z, labels, V, G, scale, mode, target=target, fp64=True, both_sides=improve)
+        return
     for Cn in CLASSES:
         for V, G in GROUPS:
             for reduce in ("sum", "mean"):
