@@ -1028,3 +1028,112 @@ extern "C" int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, i
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
+
+// ---- capture channel: the flicker as a camera records it (include/flicker_hip.h) -------------------------------------------------------
+// Frame i of clip b = i / clip_T records a mix of the K <= 4 consecutive rows rows[i], rows[i] + 1, ... (mod P) of delta, weighted by
+// the clip's taps [K] and scaled per channel by its gain [3] (null: none).  A linear map at the per-clip seam of the two kernels above:
+// the mix takes the place of the gather, its transpose the place of the row gradient.  Every product and every sum is rounded on its
+// own (mul_rn / add_rn below: nothing contracts to an fma), in one fixed order, so videoresnet_spec.flicker_rows_mix / _mix_grad
+// restate both bit for bit; with K = 1, tap 1 and no gain (or gain 1) they are the two kernels above, bit for bit (1 * x = x).
+constexpr int ROWS_MIX_MAX_K = 4;
+
+// one rounded product / sum: hipcc contracts a * b + c into one fma wherever BOTH operations allow it, and its headers define
+// __fmul_rn / __fadd_rn as the plain operators, so the two are spelt out here with contraction switched off for their own operation
+__device__ static inline float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ static inline float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// one thread = one value of delta_clip; raw values; the first product starts the sum (not 0 + product: a -0 stays -0)
+__global__ __launch_bounds__(256) void flicker_rows_mix_kernel(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps,
+                                                               int K, const float* gain, float* delta_clip) {
+  const long total = 3L * n;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const int f = (int)(i / 3), c = (int)(i - 3L * f), b = f / clip_T;
+    int r = rows[f];
+    r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
+    const float* w = taps + (size_t)b * K;
+    float acc = mul_rn(w[0], delta[r * 3 + c]);
+    for (int k = 1; k < K; ++k) {
+      r = r + 1 == P ? 0 : r + 1;
+      acc = add_rn(acc, mul_rn(w[k], delta[r * 3 + c]));
+    }
+    delta_clip[i] = gain ? mul_rn(gain[(size_t)b * 3 + c], acc) : acc;
+  }
+}
+
+// The transpose, in the form of flicker_rows_grad_kernel: one thread = one output (row r, channel c), the table staged in LDS piece by
+// piece, frames in ascending i and within a frame taps in ascending k, from +0.  Frame i (row q) reaches row r through the taps
+// k = (r - q) mod P, + P, + 2P, ... below K: more than one when P < K, and then all of them are added.  The clip index and the frame's
+// place in its clip are carried along (uniform over the workgroup: no division per frame).  g_clip is read only on a hit.  Threads
+// past the last output still stage and meet every barrier.
+__global__ __launch_bounds__(256) void flicker_rows_mix_grad_kernel(const float* g_clip, const int32_t* rows, int n, int clip_T, const float* taps,
+                                                                    int K, const float* gain, int P, float* g_rows) {
+  __shared__ int32_t sh[ROWS_PIECE];
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const bool live = o < 3 * P;
+  const int r = o / 3, c = o - 3 * r;
+  float s = 0.f;
+  for (int base = 0; base < n; base += ROWS_PIECE) {
+    const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
+    for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
+    __syncthreads();
+    if (live) {
+      int b = base / clip_T, t = base - b * clip_T;
+      for (int j = 0; j < m; ++j) {
+        const int q = sh[j];
+        if (q >= 0 && q < P) {
+          int k = r - q;
+          k = k < 0 ? k + P : k;
+          if (k < K) {
+            const float g = g_clip[(size_t)(base + j) * 3 + c];
+            for (; k < K; k += P) {
+              const float w = taps[(size_t)b * K + k];
+              s = add_rn(s, mul_rn(gain ? mul_rn(gain[(size_t)b * 3 + c], w) : w, g));
+            }
+          }
+        }
+        if (++t == clip_T) { t = 0; ++b; }
+      }
+    }
+    __syncthreads();            // sh is refilled by the next piece
+  }
+  if (live) g_rows[o] = s;
+}
+
+extern "C" int flk_flicker_rows_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain,
+                                    float* delta_clip, void* stream) {
+  FLK_REQUIRE(delta, "flk_flicker_rows_mix: delta is null");
+  FLK_REQUIRE(rows, "flk_flicker_rows_mix: rows is null");
+  FLK_REQUIRE(taps, "flk_flicker_rows_mix: taps is null");
+  FLK_REQUIRE(delta_clip, "flk_flicker_rows_mix: delta_clip is null");
+  FLK_REQUIRE(n >= 1, "flk_flicker_rows_mix: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_rows_mix: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
+  FLK_REQUIRE(K >= 1 && K <= ROWS_MIX_MAX_K, "flk_flicker_rows_mix: K (taps per clip) must be 1 .. %d (got %d)", ROWS_MIX_MAX_K, K);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_mix: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  const long blocks = (3L * n + 255) / 256;
+  FLK_LAUNCH_KERNEL(flicker_rows_mix_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
+                     clip_T, taps, K, gain, delta_clip);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_flicker_rows_mix_grad(const float* g_clip, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain,
+                                         int P, float* g_rows, void* stream) {
+  FLK_REQUIRE(g_clip, "flk_flicker_rows_mix_grad: g_clip is null");
+  FLK_REQUIRE(rows, "flk_flicker_rows_mix_grad: rows is null");
+  FLK_REQUIRE(taps, "flk_flicker_rows_mix_grad: taps is null");
+  FLK_REQUIRE(g_rows, "flk_flicker_rows_mix_grad: g_rows is null");
+  FLK_REQUIRE(n >= 1, "flk_flicker_rows_mix_grad: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_rows_mix_grad: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
+  FLK_REQUIRE(K >= 1 && K <= ROWS_MIX_MAX_K, "flk_flicker_rows_mix_grad: K (taps per clip) must be 1 .. %d (got %d)", ROWS_MIX_MAX_K, K);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_mix_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  FLK_LAUNCH_KERNEL(flicker_rows_mix_grad_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, clip_T,
+                     taps, K, gain, P, g_rows);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}

@@ -557,6 +557,61 @@ def flicker_rows_grad(g_clip, rows, period, out=None, rows_host=None):
     return out
 
 
+FLICKER_MIX_MAX_TAPS = 4      # rows of the perturbation one captured frame mixes (flk_flicker_rows_mix's K)
+
+
+def _check_mix(what, rows, taps, gain):
+    """the channel tables of flk_flicker_rows_mix*: ``rows`` [B,clip_T] (or [clip_T]: one clip), fp32 ``taps`` [B,K] with K in 1..4 and
+    fp32 ``gain`` [B,3] or None, contiguous on rows' device -> (clips, clip_T, K)"""
+    if rows.dim() not in (1, 2):
+        raise ValueError(f"{what}: rows must be [clips,clip_T] (or [clip_T] for one clip), got {tuple(rows.shape)}")
+    nb, clip_T = (1, int(rows.shape[0])) if rows.dim() == 1 else (int(rows.shape[0]), int(rows.shape[1]))
+    if not (torch.is_tensor(taps) and taps.dim() == 2 and 1 <= taps.shape[1] <= FLICKER_MIX_MAX_TAPS):
+        desc = f"{tuple(taps.shape)}" if torch.is_tensor(taps) else type(taps).__name__
+        raise ValueError(f"{what}: taps must be fp32 [{nb},K] with K in 1..{FLICKER_MIX_MAX_TAPS} (one row per clip), got {desc}")
+    _check_f32(what, "taps", taps, (nb, int(taps.shape[1])), rows)
+    if gain is not None:
+        _check_f32(what, "gain", gain, (nb, 3), rows)
+    return nb, clip_T, int(taps.shape[1])
+
+
+def flicker_rows_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
+    """the flicker as a camera records it (flk_flicker_rows_mix, one launch, in ``flicker_rows_gather``'s place): frame t of clip b takes
+    ``gain[b] * sum_k taps[b,k] * delta[(rows[b,t] + k) mod P]`` -- ``delta`` fp32 [P,3], ``rows`` int32 [B,clip_T] on the device, ``taps``
+    fp32 [B,K] (K <= 4, videoresnet_spec.capture_taps / CaptureChannel.tables), ``gain`` fp32 [B,3] or None -> fp32 ``rows.shape + (3,)``.
+    Raw values; every product and sum rounded on its own (videoresnet_spec.flicker_rows_mix restates it bit for bit)."""
+    what = "flicker_rows_mix"
+    if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
+        raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
+    P = int(delta.shape[0])
+    _check_rows(what, rows, P, rows_host)
+    _check_f32(what, "delta", delta, (P, 3), rows)
+    _, clip_T, K = _check_mix(what, rows, taps, gain)
+    if out is None:
+        out = torch.empty((*rows.shape, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (*rows.shape, 3), rows)
+    check(load().flk_flicker_rows_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain) if gain is not None else None,
+                                      ptr(out), stream_ptr()))
+    return out
+
+
+def flicker_rows_mix_grad(g_clip, rows, period, taps, gain=None, out=None, rows_host=None):
+    """the transpose of ``flicker_rows_mix`` (flk_flicker_rows_mix_grad, one launch, in ``flicker_rows_grad``'s place): the per-clip
+    gradient fp32 ``rows.shape + (3,)`` folded onto the rows of the shared perturbation through the same tables -> fp32 [period,3].
+    One fixed order (frames ascending, taps ascending, from +0), no atomics; a row nothing reaches is 0."""
+    what = "flicker_rows_mix_grad"
+    _check_rows(what, rows, period, rows_host)
+    _check_f32(what, "g_clip", g_clip, (*rows.shape, 3), rows)
+    _, clip_T, K = _check_mix(what, rows, taps, gain)
+    P = int(period)
+    if out is None:
+        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (P, 3), rows)
+    check(load().flk_flicker_rows_mix_grad(ptr(g_clip), ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain) if gain is not None else None,
+                                           P, ptr(out), stream_ptr()))
+    return out
+
+
 class StemDeltaGradWeights:
     """fp32 weights of flk_stem_delta_grad: canonical stem weights [7,7,7,3,64] x folded batch-norm scale [64]"""
 

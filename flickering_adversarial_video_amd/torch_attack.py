@@ -12,17 +12,24 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, check_sampling, flicker_rows, resolve_model, sample_frame_indices,
-                               split_sampling, train_crop_params, u8_decode_table)
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, CaptureChannel, check_sampling, flicker_rows, resolve_model,
+                               sample_frame_indices, split_sampling, train_crop_params, u8_decode_table)
 
 FLICKER_TIMES = ("clip", "video")
 
 
-def check_flicker_time(flicker_time, flicker_period, sample_length, attack_type="flickering", per_clip=False):
+def check_flicker_time(flicker_time, flicker_period, sample_length, attack_type="flickering", per_clip=False, capture=None):
     """the period of the perturbation (its row count) for a ``flicker_time`` / ``flicker_period`` pair: ``sample_length`` on clip time; on
-    video time ``flicker_period`` (None: ``sample_length``), 1..ops.FLICKER_MAX_PERIOD.  Host-only; anything else is a ValueError"""
+    video time ``flicker_period`` (None: ``sample_length``), 1..ops.FLICKER_MAX_PERIOD.  ``capture`` (a videoresnet_spec.CaptureChannel): on
+    video time with one shared flickering perturbation only.  Host-only; anything else is a ValueError"""
     if flicker_time not in FLICKER_TIMES:
         raise ValueError(f"flicker_time must be one of {FLICKER_TIMES}, got {flicker_time!r}")
+    if capture is not None:
+        if not isinstance(capture, CaptureChannel):
+            raise ValueError(f"capture must be a videoresnet_spec.CaptureChannel or None, got {type(capture).__name__}")
+        if flicker_time != "video" or attack_type != "flickering" or per_clip:
+            raise ValueError("capture needs flicker_time='video' and the flickering attack with one shared perturbation: the channel mixes the "
+                             "rows a video's frames carry (clip time, dense and per-clip perturbations have none)")
     if flicker_time == "clip":
         if flicker_period is not None:
             raise ValueError("flicker_period needs flicker_time='video': on clip time the perturbation has one row per frame of the clip")
@@ -59,10 +66,14 @@ class Perturbation:
     clip b carries row ``(frame_numbers[b,t] - phase) mod P`` (videoresnet_spec.flicker_rows; ``set_frame_numbers``, default ``arange``):
     every adversarial apply gathers its per-clip perturbation [B,clip_T,3] through that table (ops.flicker_rows_gather) and goes through
     the per-clip path of the kernels.  ``cyclic_pert`` then draws one phase per VIDEO (``clips_per_video`` consecutive clips) per
-    adversarial forward -- a flicker not synchronised with the video's start; the phases last used are kept on ``last_phases``."""
+    adversarial forward -- a flicker not synchronised with the video's start; the phases last used are kept on ``last_phases``.
+
+    ``capture`` (video time only; a videoresnet_spec.CaptureChannel): the distribution ``delta_clip(capture="draw")`` draws one capture
+    channel per video from -- the per-clip perturbation is then the mix of rows a camera records (ops.flicker_rows_mix) instead of the
+    gathered rows; the channels last used, with their tables, are kept on ``last_capture``."""
 
     def __init__(self, size, requires_grad=True, device="cuda", max_value=None, min_value=None, max_norm=1.0, cyclic_pert=False, batch=None,
-                 clip_length=None, clips_per_video=1):
+                 clip_length=None, clips_per_video=1, capture=None):
         if len(size) != 4 or size[0] != 3:
             raise ValueError(f"perturbation size must be [3,T,1,1] or [3,T,H,W], got {tuple(size)}")
         self.size, self.device, self.requires_grad = tuple(size), device, requires_grad
@@ -72,6 +83,11 @@ class Perturbation:
         self.clip_T = int(clip_length) if self.video_time else self.T          # frames of a clip (T rows on clip time, by definition)
         if self.video_time and (self.dense or batch is not None):
             raise ValueError("clip_length (flicker on video time): flickering perturbations shared by the batch only")
+        if capture is not None and not (self.video_time and isinstance(capture, CaptureChannel)):
+            raise ValueError("capture: a videoresnet_spec.CaptureChannel, with clip_length (flicker on video time) only")
+        self.capture = capture
+        self.last_capture = None         # the channels of the last adversarial apply that went through one: the draw + its "taps", "gain_rows"
+        self.taps_dev = self.gain_dev = None                          # their tables on the device: fp32 [B,K] and [B,3]
         self.clips_per_video = int(clips_per_video)
         self.frame_numbers = None        # video time: int64 [B,clip_T] of the current batch, None = arange(clip_T) for every clip
         self.last_phases = None          # video time: the phases (one per video) of the last adversarial apply
@@ -142,11 +158,43 @@ class Perturbation:
             table = np.ascontiguousarray(table, dtype=np.int64)
         self.frame_numbers = table
 
-    def delta_clip(self, B, phases="draw"):
+    def _capture_tables(self, B, capture):
+        """the channel tables of a batch of B clips on the device (``taps_dev`` [B,K], ``gain_dev`` [B,3]), uploaded only when they differ
+        from those already there.  ``capture``: "draw" -- one channel per video from ``self.capture`` -- or a dict ``subframe``,
+        ``exposure``, ``gain`` holding one channel per video ([V], [V], [V,3]), one per clip ([B], ...) or one for all (scalars, ``gain`` [3])"""
+        G = self.clips_per_video
+        V = -(-B // G)
+        if isinstance(capture, str):
+            if capture != "draw" or self.capture is None:
+                raise ValueError(f"capture must be a channel dict, None or -- on a perturbation built with capture=CaptureChannel(...) -- 'draw', got {capture!r}")
+            capture = self.capture.draw(V)
+        if not isinstance(capture, dict) or set(capture) != {"subframe", "exposure", "gain"}:
+            raise ValueError(f"capture must be a dict with the keys subframe, exposure and gain, got {capture!r}")
+        if np.ndim(capture["subframe"]) == 0:                          # one channel for every video of the batch
+            capture = {"subframe": np.full(V, float(capture["subframe"])), "exposure": np.full(V, float(capture["exposure"])),
+                       "gain": np.broadcast_to(np.asarray(capture["gain"], np.float32).reshape(-1, 3)[:1], (V, 3)).copy()}
+        if G > 1 and np.shape(capture["subframe"]) == (B,):              # one channel per CLIP (evaluate_videos packs clips, not videos)
+            G, V = 1, B
+        taps, gain = CaptureChannel.tables(capture, G)
+        if taps.shape[0] != V * G:
+            raise ValueError(f"{taps.shape[0] // G} capture channels for {B} clips of {G} per video: one per video, or one for all")
+        taps, gain = np.ascontiguousarray(taps[:B]), np.ascontiguousarray(gain[:B])
+        last = self.last_capture
+        if last is None or self.taps_dev is None or last["taps"].shape != taps.shape:
+            self.taps_dev, self.gain_dev = (torch.from_numpy(t).to(self.perturbation.device) for t in (taps, gain))
+        else:
+            if not np.array_equal(taps, last["taps"]):
+                self.taps_dev.copy_(torch.from_numpy(taps))
+            if not np.array_equal(gain, last["gain_rows"]):
+                self.gain_dev.copy_(torch.from_numpy(gain))
+        self.last_capture = {**capture, "taps": taps, "gain_rows": gain}
+
+    def delta_clip(self, B, phases="draw", capture=None):
         """video time: the per-clip perturbation [B,clip_T,3] of the current frame numbers (a buffer reused from call to call, valid
         until the next one).  ``phases``: "draw" = one per video from the generator when ``cyclic_pert`` (else 0), or an integer / one
         integer per video; None: the buffer as it is, nothing gathered (a clean apply reads no perturbation).  The table goes to the
-        device only when it differs from the one already there."""
+        device only when it differs from the one already there.  ``capture``: None -- the rows themselves (ops.flicker_rows_gather) --
+        or the capture channels the frames are recorded through (``_capture_tables``: "draw" or a dict): ops.flicker_rows_mix."""
         if self.frame_numbers is not None and self.frame_numbers.shape[0] != B:
             raise ValueError(f"{B} clips, but the frame numbers set are for {self.frame_numbers.shape[0]} (set_frame_numbers)")
         if self._delta_clip is None or self._delta_clip.shape[0] != B:
@@ -172,17 +220,25 @@ class Perturbation:
         elif not np.array_equal(rows, self.rows_host):
             self.rows_dev.copy_(torch.from_numpy(rows))
             self.rows_host = rows
-        return ops.flicker_rows_gather(self.perturbation, self.rows_dev, out=self._delta_clip)
+        if capture is None:
+            return ops.flicker_rows_gather(self.perturbation, self.rows_dev, out=self._delta_clip)
+        self._capture_tables(B, capture)
+        return ops.flicker_rows_mix(self.perturbation, self.rows_dev, self.taps_dev, self.gain_dev, out=self._delta_clip)
 
-    def apply_args(self, x, adversarial=True, fold_t=1, quantise=False, phases="draw"):
+    def _no_capture_on_clip_time(self, capture):
+        if capture is not None and not self.video_time:
+            raise ValueError("capture: a perturbation on video time only (clip_length / flicker_time='video')")
+
+    def apply_args(self, x, adversarial=True, fold_t=1, quantise=False, phases="draw", capture=None):
         """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans).
         x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
         ``videoresnet_spec.normalize_u8`` makes on the host).  quantise: every value goes through the 8-bit round trip of ``export_u8``
         inside the apply kernel (flk_apply_args.q_lut) -- the clip applied is the one the exported frames decode to, bit for bit"""
         delta = self.perturbation
+        self._no_capture_on_clip_time(capture)
         if self.video_time:
             # the roll is in the rows; a clean apply reads no perturbation (adv_flag 0), so it gathers nothing and keeps the table
-            delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None), 0
+            delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None, capture), 0
         else:
             shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
         inf = float("inf")
@@ -194,22 +250,38 @@ class Perturbation:
                                    x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None,
                                    quantise="torch" if quantise else None, q_lut=decode_table(x.device) if quantise else None)
 
-    def export_args(self, x, adversarial=True, shift_p=0, delta_T=0):
+    def export_args(self, x, adversarial=True, shift_p=0, delta_T=0, capture=None):
         """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
         frames of a cyclic perturbation are exported at the phase ``shift_p`` the caller names.  Video time: clips (``delta_T`` 0) take
         their rows at that phase (one per video, or a scalar) through the per-clip path; a whole video (``delta_T`` = the period) takes
-        the shared perturbation itself -- the kernel's own rule IS the one the rows follow"""
+        the shared perturbation itself -- the kernel's own rule IS the one the rows follow.  ``capture``: the channel(s) the flicker is
+        recorded through -- clips: as ``delta_clip`` takes them; a whole video: ONE channel, the perturbation exported being its mix
+        over ``rows = arange(P)`` (``captured_perturbation``; the mix commutes with the row shift)"""
         inf = float("inf")
         delta = self.perturbation
+        self._no_capture_on_clip_time(capture)
         if self.video_time and not delta_T:
-            delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None), 0
+            delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None, capture), 0
+        elif capture is not None and adversarial:
+            delta = self.captured_perturbation(capture)
         return ops.make_export_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
                                           shift_p=shift_p, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                           lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf,
                                           dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
                                           x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None, delta_T=delta_T)
 
-    def export_u8(self, x, adversarial=True, stats=False, out=None, out_offset=0, shift_p=0):
+    def captured_perturbation(self, capture):
+        """video time: the shared perturbation as ONE capture channel records it, fp32 [P,3] -- one ops.flicker_rows_mix launch over
+        ``rows = arange(P)`` as one clip of P frames: row r of the result is what a frame that carries row r records.  ``capture``: a dict
+        ``subframe``, ``exposure`` (scalars) and ``gain`` [3].  Nothing of the batch's own tables is touched."""
+        if not isinstance(capture, dict) or set(capture) != {"subframe", "exposure", "gain"} or np.ndim(capture["subframe"]) != 0:
+            raise ValueError(f"capture must be ONE channel: a dict of the scalars subframe and exposure and gain [3], got {capture!r}")
+        taps, gain = CaptureChannel.tables(capture, 1)
+        dev = self.perturbation.device
+        rows = torch.arange(self.T, dtype=torch.int32, device=dev)
+        return ops.flicker_rows_mix(self.perturbation, rows, torch.from_numpy(taps).to(dev), torch.from_numpy(gain).to(dev))
+
+    def export_u8(self, x, adversarial=True, stats=False, out=None, out_offset=0, shift_p=0, capture=None):
         """the clip ``forward([x, adversarial])`` makes, as the 8-bit frames a file or a display holds: uint8 ``[B,T,H,W,3]`` on the device,
         ``rint(255 * (x_adv * std + mean))`` saturated to 0..255 (ops.export_adversarial_u8, one kernel launch; the host route
         ``apply_perturbation`` goes through the folded fp32 tensor, a permute and numpy).  ``x`` as in ``forward`` (NCDHW or channels-last,
@@ -221,7 +293,8 @@ class Perturbation:
         xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
         if xcl.shape[1] != self.clip_T:
             raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.clip_T}")
-        return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p), "torch", out=out, out_offset=out_offset, stats=stats)
+        return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p, capture=capture), "torch", out=out, out_offset=out_offset,
+                                         stats=stats)
 
     def forward(self, input, quantise=False):
         """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip; ``quantise``:
@@ -383,15 +456,21 @@ class FlickerVideoResNet:
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
                  im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None):
+                 flicker_time="clip", flicker_period=None, capture=None):
         from .i3d_engine import check_optimizer
         # flicker_time "video": the flicker runs on VIDEO time, as ``export_video`` delivers it -- a perturbation of period P =
         # ``flicker_period`` (default: sample_length) rows, frame t of clip b carrying row (frame number - phase) mod P, the frame numbers
         # being those the clips were cut at (``prepare_videos`` / whole-video loaders: ``last_sampling``; pre-cut clips:
         # ``set_frame_numbers``; nothing set: 0..T-1).  "clip" (default): row t for frame t of every clip, as ever.  Checked before
         # anything touches the device
-        self.P = check_flicker_time(flicker_time, flicker_period, sample_length, attack_type, per_clip)
+        self.P = check_flicker_time(flicker_time, flicker_period, sample_length, attack_type, per_clip, capture)
         self.flicker_time, self.video_time = flicker_time, flicker_time == "video"
+        # capture (flicker_time "video"; a videoresnet_spec.CaptureChannel): the attack is trained OVER THE AIR.  Every adversarial training
+        # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
+        # of rows a camera records (ops.flicker_rows_mix in the gather's place); the step folds its gradient through the same tables
+        # (ops.flicker_rows_mix_grad).  Evaluation and export (``logits``, ``adversarial_frames``, ``quantised_logits``, ``export_video``,
+        # ``evaluate_videos``) go through a channel only when they are given one: their default is none
+        self.capture = capture
         # quantise_train: the attack is optimised on the STORED video.  Every adversarial forward (``step`` in all its variants,
         # ``logits(x, True)``) applies decode(encode_u8(x_adv)) -- the 8-bit round trip inside the apply kernel, straight-through gradient --
         # so its logits are bit for bit ``quantised_logits(x)`` for the delta the step ran with, and the ``argmax`` / ``is_adversarial``
@@ -461,7 +540,7 @@ class FlickerVideoResNet:
             raise ValueError("per_clip: flickering attack, no cyclic roll, one rank")
         self.pert_model = Perturbation((3, self.P, 1, 1) if attack_type == "flickering" else (3, self.T, self.H, self.W),
                                        max_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, batch=self.B if self.per_clip else None,
-                                       clip_length=self.T if self.video_time else None, clips_per_video=G)
+                                       clip_length=self.T if self.video_time else None, clips_per_video=G, capture=capture)
         dev = torch.device("cuda", device)
         tdt = torch.bfloat16 if dtype in ("bf16", torch.bfloat16) else torch.float32
         # bf16 plans take the clip as TWO bf16 numbers per value (32 channels, fold_t = 4: the stem sees x + delta/std to ~16 bits -- one
@@ -481,10 +560,10 @@ class FlickerVideoResNet:
             self.adam_steps = torch.zeros(self.B, dtype=torch.int32, device=dev)
             self.active = torch.ones(self.B, dtype=torch.int32, device=dev)
 
-    def _forward(self, x, adversarial, phases="draw"):
+    def _forward(self, x, adversarial, phases="draw", capture=None):
         """Perturbation -> network: the apply arguments of this call (the backward pass masks with the same) ; logits in self._logits"""
         a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold, quantise=self.quantise_train and bool(adversarial),
-                                       phases=phases)
+                                       phases=phases, capture=capture)
         self.net.forward_apply(a, self._xs, self._logits)           # the plan applies the perturbation in front of its stem
         return a
 
@@ -509,6 +588,12 @@ class FlickerVideoResNet:
     def last_phases(self):
         """flicker_time "video": the phases, one per video of the batch, the last adversarial forward ran at"""
         return self.pert_model.last_phases
+
+    @property
+    def last_capture(self):
+        """the capture channels, one per video of the batch, of the last adversarial forward that went through one: ``subframe`` [V],
+        ``exposure`` [V], ``gain`` [V,3] and the tables made from them, one row per clip: ``taps`` fp32 [B,K], ``gain_rows`` fp32 [B,3]"""
+        return self.pert_model.last_capture
 
     @staticmethod
     def _check_augment(augment):
@@ -590,7 +675,7 @@ class FlickerVideoResNet:
         return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
                                  rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=np.concatenate(tables))
 
-    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None):
+    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None, capture=None, capture_draws=1):
         """``VideoLearnerAdversarial.evaluate(num_samples)`` (model.py:1227-1317) on whole videos resident on the device: every video is
         scored by the argmax of the summed logits of ``num_samples`` clips cut at uniform offsets (the test split: no shift, no jitter)
         and prepared with the evaluation transform.  ``videos``: a list of CUDA uint8 ``[N_k,H_k,W_k,3]``; ``labels``: one class per video.
@@ -609,6 +694,13 @@ class FlickerVideoResNet:
         evaluation -- the exported videos are made batch by batch and no more of them are held than one batch needs.  Both add
         ``realised_flicker``: the mean of (frame byte - source byte) per frame and channel, in levels -- fp64 ``[V * num_samples, T, 3]``
         ("clip"; the source being the 8-bit encoding of the prepared clip) or a list of ``[N_k, 3]`` per video ("video").
+        ``capture`` (a videoresnet_spec.CaptureChannel; flicker_time "video", with ``adversarial`` or ``quantise``) and ``capture_draws`` = N:
+        the attack as N random cameras record it.  N times, one capture channel per video is drawn from ``capture`` (N ``draw(V)`` calls,
+        made before anything is scored) and the adversarial scoring above is repeated with every video's flicker going through its
+        channel (``logits(x, True, phases=0, capture=)``, ``adversarial_frames(capture=)`` or ``export_video(capture=)``).  Adds
+        ``capture_draws`` (the list of the N draws), ``capture_clip_logits`` fp32 ``[N, V * num_samples, classes]``, ``capture_video_logits``
+        fp32 ``[N, V, classes]``, ``capture_video_fooling_ratios`` fp64 ``[N]`` and their ``capture_video_fooling_ratio_mean`` /
+        ``capture_video_fooling_ratio_min``.  Everything else in the result is what it is without ``capture`` (no channel).
         Known difference from the reference: its loop starts at video 1 (``range(1, len(ds))``, model.py:1279-1281) and so never
         scores the first video; this one evaluates every video."""
         videos = list(videos) if isinstance(videos, (list, tuple)) else None
@@ -628,6 +720,14 @@ class FlickerVideoResNet:
         if quantise not in (None, "clip", "video"):
             raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
         adversarial = adversarial or quantise is not None
+        draws = []
+        if capture is not None:
+            if not (isinstance(capture, CaptureChannel) and self.video_time and adversarial):
+                raise ValueError("evaluate_videos: capture must be a videoresnet_spec.CaptureChannel, on an engine built with flicker_time='video', "
+                                 "with adversarial=True or quantise")
+            if isinstance(capture_draws, bool) or not isinstance(capture_draws, (int, np.integer)) or capture_draws < 1:
+                raise ValueError(f"evaluate_videos: capture_draws must be an integer >= 1, got {capture_draws!r}")
+            draws = [capture.draw(V) for _ in range(int(capture_draws))]
         kept = self.pert_model.frame_numbers                            # video time: every batch below brings its own frame numbers
         clean, adv, flick = [], [], []
         exported = {}                                                   # quantise = "video": the flickered videos of the current batch
@@ -654,6 +754,29 @@ class FlickerVideoResNet:
                 adv.append(self.logits(x, False)[:n].cpu())
             elif adversarial:
                 adv.append(self.logits(x, True, phases=0)[:n].cpu())       # (phases: video time only -- clip time draws its roll as ever)
+        cap_adv = []
+        for d in draws:                                                 # the adversarial scoring again, every video through its channel
+            parts = []
+            for first in range(0, V * S, B):
+                ks = [min(first + b, V * S - 1) for b in range(B)]
+                vs_ = np.asarray([k // S for k in ks])
+                n = min(B, V * S - first)
+                self.pert_model.set_frame_numbers(rows[ks])
+                if quantise == "video":
+                    exp = {v: self.export_video(videos[v], capture={"subframe": float(d["subframe"][v]), "exposure": float(d["exposure"][v]),
+                                                                    "gain": d["gain"][v]}) for v in sorted(set(vs_.tolist()))}
+                    ops.prepare_clips([exp[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                      rule=self.resize_rule, frame_idx=rows[ks])
+                    parts.append(self.logits(x, False)[:n].cpu())
+                    continue
+                ops.prepare_clips([videos[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                  rule=self.resize_rule, frame_idx=rows[ks])
+                per_clip = {"subframe": d["subframe"][vs_], "exposure": d["exposure"][vs_], "gain": d["gain"][vs_]}      # one channel per clip
+                if quantise == "clip":
+                    parts.append(self.logits(self.adversarial_frames(x, capture=per_clip), False)[:n].cpu())
+                else:
+                    parts.append(self.logits(x, True, phases=0, capture=per_clip)[:n].cpu())
+            cap_adv.append(parts)
         self.pert_model.frame_numbers = kept
 
         def score(parts):
@@ -678,6 +801,12 @@ class FlickerVideoResNet:
                    video_accuracy=float((vp == trues).mean()), clip_accuracy=float((cp == clip_trues).mean()))
         if quantise is not None:
             res["realised_flicker"] = np.concatenate(flick) if quantise == "clip" else flick
+        if draws:
+            scored = [score(parts) for parts in cap_adv]
+            ratios = np.asarray([float(((s[3] != trues) & ok).sum() / ok.sum()) if ok.any() else float("nan") for s in scored], np.float64)
+            res.update(capture_draws=draws, capture_clip_logits=np.stack([s[0] for s in scored]), capture_video_logits=np.stack([s[1] for s in scored]),
+                       capture_video_fooling_ratios=ratios, capture_video_fooling_ratio_mean=float(ratios.mean()),
+                       capture_video_fooling_ratio_min=float(ratios.min()))
         return res
 
     def _is_raw(self, x):
@@ -702,38 +831,42 @@ class FlickerVideoResNet:
             raise ValueError(f"{what}: clips of one call must share a dtype, got {dtype} and {x.dtype}")
         return x.dtype
 
-    def logits(self, x, adversarial=False, phases="draw"):
+    def logits(self, x, adversarial=False, phases="draw", capture=None):
         """model([x, adversarial]) (model.py:1028,1073).  ``phases`` (flicker_time "video"): "draw" -- one per video when ``cyclic_pert``,
-        else 0 -- or the phase(s) to apply at"""
-        self._forward(x, adversarial, phases)
+        else 0 -- or the phase(s) to apply at.  ``capture`` (flicker_time "video"): None -- no capture channel -- or the channel(s) the
+        flicker is recorded through: "draw" (an engine built with ``capture``) or a dict (Perturbation.delta_clip)"""
+        self._forward(x, adversarial, phases, capture)
         return self._logits
 
-    def adversarial_frames(self, x, out=None, stats=False, adversarial=True):
+    def adversarial_frames(self, x, out=None, stats=False, adversarial=True, capture=None):
         """the perturbed clips as 8-bit frames: uint8 ``[N,T,H,W,3]`` of the engine's perturbation over ``x`` (fp32 or uint8 clips at the
         engine's size; per-clip engines: N == B), one kernel launch (Perturbation.export_u8).  ``out``: a uint8 buffer to fill.
         ``stats``: also the int32 ``[N,T,3,4]`` table of ops.export_adversarial_u8.  ``adversarial=False``: the frames of the clean clips."""
         if x.dim() != 5 or tuple(x.shape[1:]) != (self.T, self.H, self.W, 3) or x.dtype not in CLIP_DTYPES or not x.is_cuda:
             raise ValueError(f"clips must be CUDA float32 or uint8 channels-last tensors [N,{self.T},{self.H},{self.W},3], got {tuple(x.shape)} {x.dtype}")
-        return self.pert_model.export_u8(x, adversarial, stats=stats, out=out)
+        return self.pert_model.export_u8(x, adversarial, stats=stats, out=out, capture=capture)
 
-    def quantised_logits(self, x, adversarial=True):
+    def quantised_logits(self, x, adversarial=True, capture=None):
         """the logits of the STORED adversarial video: ``x`` perturbed and written as 8-bit frames (``adversarial_frames``, into a buffer the
         engine reuses), then scored by the clean uint8 path -- ``logits(frames, False)``"""
         x = self._check_x(x)
         if getattr(self, "_q_buf", None) is None:
             self._q_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.uint8, device=x.device)
-        return self.logits(self.adversarial_frames(x, out=self._q_buf, adversarial=adversarial), False)
+        return self.logits(self.adversarial_frames(x, out=self._q_buf, adversarial=adversarial, capture=capture), False)
 
-    def export_video(self, video_u8, phase=0, stats=False):
+    def export_video(self, video_u8, phase=0, stats=False, capture=None):
         """the engine's flicker laid over a WHOLE video at its own resolution: ``video_u8`` uint8 ``[N,H,W,3]`` on the device -> uint8
         ``[N,H,W,3]``, frame n perturbed by row ``(n - phase) mod P`` of the perturbation (period P = the engine's T, or the ``flicker_period``
         of an engine on video time; the flicker is uniform over a frame, so it needs no resize).  One kernel launch.  Flicker attacks with
-        one shared perturbation only.  ``stats``: also the int32 ``[N,3,4]`` table of ops.export_adversarial_u8."""
+        one shared perturbation only.  ``stats``: also the int32 ``[N,3,4]`` table of ops.export_adversarial_u8.  ``capture`` (video time):
+        ONE capture channel, a dict of the scalars ``subframe`` and ``exposure`` and ``gain`` [3] -- the video a camera with that channel
+        records: the perturbation exported is the channel's mix of the rows (Perturbation.captured_perturbation, one launch), so frame n
+        carries what a training step under that channel at that phase gives frame number n."""
         if self.attack_type != "flickering" or self.per_clip:
             raise ValueError("export_video: the flickering attack with one shared perturbation only (a dense or per-clip perturbation belongs to its clip)")
         if not torch.is_tensor(video_u8) or video_u8.dim() != 4 or video_u8.dtype != torch.uint8 or video_u8.shape[-1] != 3 or not video_u8.is_cuda or video_u8.shape[0] < 1:
             raise ValueError("export_video: a CUDA uint8 tensor [N,H,W,3]")
-        a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.P)
+        a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.P, capture=capture)
         res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.P)
         return (res[0][0], res[1][0]) if stats else res[0]
 
@@ -790,7 +923,8 @@ class FlickerVideoResNet:
         self._it += 1
         red, sm, pc = slot["payload"], slot["sm"], slot["pc"]
         self._red = red
-        a = self._forward(x, True)
+        cap = "draw" if self.capture is not None else None     # one capture channel per video, fresh every step
+        a = self._forward(x, True, capture=cap)
         gbatch = V * self.world
         if G > 1:
             criterion.adv_video(labels, self._logits, gbatch, G, self.video_reduce, out=(sm, self._dl, pc, slot["vl"]))
@@ -801,7 +935,11 @@ class FlickerVideoResNet:
         if self.video_time:
             # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame), then its frames folded onto their rows
             ops.perturb_grad_reduce(a, self._gx, self._g_clip, self._scratch)
-            ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
+            if cap is None:
+                ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
+            else:                                               # the transpose of the mix the forward ran, on the same tables
+                ops.flicker_rows_mix_grad(self._g_clip, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
+                                          out=red[:n].view(self.P, 3))
         else:
             ops.perturb_grad_reduce(a, self._gx, red[:n].view(self.T, 3), self._scratch)
         ops.pack_batch_sums(pc, 1.0 / gbatch, red[n:])
@@ -1224,7 +1362,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
                  process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None):
+                 flicker_time="clip", flicker_period=None, capture=None):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1239,6 +1377,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
                          clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
-                         flicker_time=flicker_time, flicker_period=flicker_period)
+                         flicker_time=flicker_time, flicker_period=flicker_period, capture=capture)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -399,6 +399,177 @@ def flicker_rows(frame_numbers, period, phase=0):
     return np.mod(n.astype(np.int64) - ph.astype(np.int64), np.int64(period)).astype(np.int32, order="C")      # numpy's mod takes the divisor's sign
 
 
+# ---- capture channel: the flicker as a camera records it ----------------------------------------------------------------------------
+CAPTURE_MAX_EXPOSURE = 3.0      # emitter rows: with a sub-frame phase below 1 a frame then mixes at most 4 rows (flk_flicker_rows_mix's K)
+CAPTURE_GAIN_MODES = ("common", "per_channel")
+
+
+def capture_taps(subframe, exposure):
+    """The weights a camera frame gives the rows of the flicker: frame n integrates the emitter over ``[n + subframe, n + subframe +
+    exposure)`` (both in emitter rows), so it records ``sum_k w_k * delta[row(n) + k]`` with ``w_k = |[phi, phi + e) n [k, k + 1)| / e`` --
+    fp32 ``[K]``, ``K = max(1, ceil(phi + e))``, computed in float64 and rounded once.  ``exposure`` 0: an instantaneous sample, ``[1]``.
+    ``subframe`` must lie in [0,1) and ``exposure`` in [0,3]; anything else, or a non-finite value, is a ValueError."""
+    try:
+        phi, e = float(subframe), float(exposure)
+    except (TypeError, ValueError):
+        raise ValueError(f"capture_taps: subframe and exposure must be numbers, got {subframe!r} and {exposure!r}") from None
+    if not (np.isfinite(phi) and 0.0 <= phi < 1.0):
+        raise ValueError(f"capture_taps: the sub-frame phase must lie in [0,1), got {subframe!r}")
+    if not (np.isfinite(e) and 0.0 <= e <= CAPTURE_MAX_EXPOSURE):
+        raise ValueError(f"capture_taps: the exposure must lie in [0,{CAPTURE_MAX_EXPOSURE:g}] emitter rows, got {exposure!r}")
+    if e == 0.0:
+        return np.ones(1, np.float32)
+    K = max(1, int(np.ceil(phi + e)))
+    k = np.arange(K, dtype=np.float64)
+    w = np.maximum(0.0, np.minimum(phi + e, k + 1.0) - np.maximum(phi, k)) / e
+    return w.astype(np.float32)
+
+
+def _mix_tables(what, rows, clip_T, taps, gain):
+    rows = np.asarray(rows)
+    if rows.dtype.kind not in "iu" or rows.size < 1:
+        raise ValueError(f"{what}: rows must be a non-empty integer table, got {rows.shape} {rows.dtype}")
+    if isinstance(clip_T, bool) or not isinstance(clip_T, (int, np.integer)) or clip_T < 1 or rows.size % clip_T:
+        raise ValueError(f"{what}: clip_T must be an integer >= 1 that divides the {rows.size} frames, got {clip_T!r}")
+    nb = rows.size // int(clip_T)
+    taps = np.asarray(taps)
+    if taps.dtype != np.float32 or taps.ndim != 2 or taps.shape[0] != nb or not 1 <= taps.shape[1] <= 4:
+        raise ValueError(f"{what}: taps must be float32 [{nb},K] with K in 1..4 (one row per clip), got {taps.shape} {taps.dtype}")
+    if gain is not None:
+        gain = np.asarray(gain)
+        if gain.dtype != np.float32 or gain.shape != (nb, 3):
+            raise ValueError(f"{what}: gain must be float32 [{nb},3] (one row per clip) or None, got {gain.shape} {gain.dtype}")
+    return rows, nb, taps, gain
+
+
+def flicker_rows_mix(delta, rows, clip_T, taps, gain=None):
+    """``flk_flicker_rows_mix`` restated in numpy float32, operation for operation: ``delta`` fp32 ``[P,3]``, ``rows`` integers of any shape
+    (frame i of the flattened table belongs to clip ``i // clip_T``), ``taps`` fp32 ``[clips,K]``, ``gain`` fp32 ``[clips,3]`` or None ->
+    fp32 ``rows.shape + (3,)``.  ``r0 = clamp(rows[i], 0, P-1); acc = taps[b,0] * delta[r0]`` (the first product itself: a -0 stays -0), then
+    ``acc = acc + taps[b,k] * delta[(r0 + k) mod P]`` for k = 1 .. K-1, then ``gain[b] * acc`` -- every product and sum rounded on its own."""
+    what = "flicker_rows_mix"
+    delta = np.asarray(delta)
+    if delta.dtype != np.float32 or delta.ndim != 2 or delta.shape[1] != 3 or delta.shape[0] < 1:
+        raise ValueError(f"{what}: delta must be float32 [P,3], got {delta.shape} {delta.dtype}")
+    rows, nb, taps, gain = _mix_tables(what, rows, clip_T, taps, gain)
+    P = delta.shape[0]
+    r0 = np.clip(rows.reshape(-1).astype(np.int64), 0, P - 1)
+    b = np.arange(r0.shape[0]) // int(clip_T)
+    acc = taps[b, 0][:, None] * delta[r0]
+    for k in range(1, taps.shape[1]):
+        acc = acc + taps[b, k][:, None] * delta[(r0 + k) % P]
+    if gain is not None:
+        acc = gain[b] * acc
+    assert acc.dtype == np.float32
+    return np.ascontiguousarray(acc.reshape(rows.shape + (3,)))
+
+
+def flicker_rows_mix_grad(g_clip, rows, clip_T, taps, gain, period):
+    """``flk_flicker_rows_mix_grad`` restated in numpy float32, the transpose of ``flicker_rows_mix``: ``g_clip`` fp32 ``rows.shape + (3,)`` ->
+    fp32 ``[period,3]``.  From +0, over the frames i ascending and within a frame the taps k ascending:
+    ``g_rows[(rows[i] + k) mod P] += (gain[b] * taps[b,k]) * g_clip[i]`` (without a gain: ``taps[b,k] * g_clip[i]``), every product and sum
+    rounded on its own; frames whose row lies outside [0,P) are skipped; a row nothing reaches stays +0.  ``period < K`` is legal."""
+    what = "flicker_rows_mix_grad"
+    rows, nb, taps, gain = _mix_tables(what, rows, clip_T, taps, gain)
+    if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or period < 1:
+        raise ValueError(f"{what}: period must be an integer >= 1, got {period!r}")
+    g = np.asarray(g_clip)
+    if g.dtype != np.float32 or g.shape != rows.shape + (3,):
+        raise ValueError(f"{what}: g_clip must be float32 {rows.shape + (3,)}, got {g.shape} {g.dtype}")
+    P, K = int(period), taps.shape[1]
+    g, r = g.reshape(-1, 3), rows.reshape(-1).astype(np.int64)
+    b = np.arange(r.shape[0]) // int(clip_T)
+    coef = taps[b][:, :, None] if gain is None else gain[b][:, None, :] * taps[b][:, :, None]          # [n,K,1 or 3]
+    prod = coef * g[:, None, :]                                                                        # [n,K,3], one rounding each
+    assert prod.dtype == np.float32
+    target = (r[:, None] + np.arange(K)) % P
+    out = np.zeros((P, 3), np.float32)
+    for i in np.flatnonzero((r >= 0) & (r < P)):
+        for k in range(K):
+            out[target[i, k]] = out[target[i, k]] + prod[i, k]
+    return out
+
+
+def _capture_range(name, v, lo_bound, hi_bound):
+    pair = (v, v) if np.ndim(v) == 0 else tuple(v)
+    if len(pair) != 2:
+        raise ValueError(f"CaptureChannel: {name} must be a number or a (lo, hi) pair, got {v!r}")
+    lo, hi = float(pair[0]), float(pair[1])
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo_bound <= lo <= hi <= hi_bound):
+        raise ValueError(f"CaptureChannel: {name} must satisfy {lo_bound:g} <= lo <= hi <= {hi_bound:g}, got {v!r}")
+    return lo, hi
+
+
+class CaptureChannel:
+    """The distribution a capture channel is drawn from (host only): a camera that is not synchronised with the emitter records frame n
+    as the emitter integrated over ``[n + subframe, n + subframe + exposure)`` (``capture_taps``), each channel scaled by a gain (the
+    emitter's colour response, white balance, ambient dilution).  ``subframe`` in [0,1] (a drawn value stays below 1), ``exposure`` in
+    [0,3] emitter rows and ``gain`` >= 0 are ``(lo, hi)`` ranges drawn uniformly, or scalars; equal bounds fix the value.  ``gain_mode``
+    "common": one gain for the three channels; "per_channel": one each -- and then ``gain`` may also be three numbers, the fixed gains of
+    R, G and B (a known colour cast).  The channel acts on the flicker only -- not on the scene.
+
+    ``draw(V)``: V channels from the instance's ONE generator ``numpy.random.default_rng(seed)``, in this order: the V subframes, then
+    the V exposures, then the gains (V values, or V x 3 in row-major order; none for three fixed gains) -- each a ``Generator.uniform``
+    call, made whether or not the bounds are equal, so that fixing a range does not shift the other draws."""
+
+    def __init__(self, subframe=(0.0, 1.0), exposure=(1.0, 1.0), gain=(1.0, 1.0), gain_mode="common", seed=0):
+        self.subframe = _capture_range("subframe", subframe, 0.0, 1.0)
+        self.exposure = _capture_range("exposure", exposure, 0.0, CAPTURE_MAX_EXPOSURE)
+        fmax = float(np.finfo(np.float32).max)
+        self.gain_rgb = None                                           # three fixed gains (per_channel only): nothing is drawn for them
+        if np.ndim(gain) == 1 and len(gain) == 3:
+            if gain_mode != "per_channel":
+                raise ValueError(f"CaptureChannel: three gains (one per colour channel) need gain_mode='per_channel', got {gain_mode!r}")
+            self.gain_rgb = np.asarray([_capture_range("gain", g, 0.0, fmax)[0] for g in gain], np.float32)
+            self.gain = (float(self.gain_rgb.min()), float(self.gain_rgb.max()))
+        else:
+            self.gain = _capture_range("gain", gain, 0.0, fmax)
+        if self.subframe[0] >= 1.0:
+            raise ValueError(f"CaptureChannel: the sub-frame phase lies in [0,1): its lower bound must be below 1, got {subframe!r}")
+        if gain_mode not in CAPTURE_GAIN_MODES:
+            raise ValueError(f"CaptureChannel: gain_mode must be one of {CAPTURE_GAIN_MODES}, got {gain_mode!r}")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+            raise ValueError(f"CaptureChannel: seed must be an integer, got {seed!r}")
+        self.gain_mode, self.seed = gain_mode, int(seed)
+        self._rng = np.random.default_rng(self.seed)
+
+    def draw(self, V):
+        """``V`` channels: ``{"subframe": float64 [V], "exposure": float64 [V], "gain": float32 [V,3]}`` (order of the draws: class docstring)"""
+        if isinstance(V, bool) or not isinstance(V, (int, np.integer)) or V < 1:
+            raise ValueError(f"CaptureChannel.draw: the number of channels must be an integer >= 1, got {V!r}")
+        V = int(V)
+        sub = np.minimum(self._rng.uniform(*self.subframe, size=V), np.nextafter(1.0, 0.0))
+        exp = np.clip(self._rng.uniform(*self.exposure, size=V), *self.exposure)
+        if self.gain_rgb is not None:
+            gain = np.repeat(self.gain_rgb[None], V, axis=0)
+        elif self.gain_mode == "common":
+            gain = np.repeat(self._rng.uniform(*self.gain, size=V)[:, None], 3, axis=1)
+        else:
+            gain = self._rng.uniform(*self.gain, size=(V, 3))
+        return {"subframe": sub, "exposure": exp, "gain": np.ascontiguousarray(gain, dtype=np.float32)}
+
+    @staticmethod
+    def tables(draw, G=1):
+        """the tables ``flicker_rows_mix`` takes for ``draw`` (a dict as ``draw`` returns; one channel may give scalars and ``gain [3]``):
+        fp32 ``taps [V * G, Kmax]`` -- every video's ``capture_taps`` padded with zeros to the longest -- and fp32 ``gain [V * G, 3]``.  The
+        ``G`` clips of a video share their video's channel, as they share its phase."""
+        if not isinstance(draw, dict) or set(draw) != {"subframe", "exposure", "gain"}:
+            raise ValueError(f"CaptureChannel.tables: a dict with the keys subframe, exposure and gain, got {draw!r}")
+        if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or G < 1:
+            raise ValueError(f"CaptureChannel.tables: clips per video must be an integer >= 1, got {G!r}")
+        sub, exp = np.atleast_1d(np.asarray(draw["subframe"], np.float64)), np.atleast_1d(np.asarray(draw["exposure"], np.float64))
+        gain = np.asarray(draw["gain"], np.float32)
+        gain = gain[None] if gain.ndim == 1 else gain
+        V = sub.shape[0]
+        if sub.ndim != 1 or exp.shape != (V,) or gain.shape != (V, 3) or not np.isfinite(gain).all():
+            raise ValueError(f"CaptureChannel.tables: subframe [V], exposure [V] and finite gain [V,3], got {sub.shape}, {exp.shape}, {gain.shape}")
+        per_video = [capture_taps(s, e) for s, e in zip(sub, exp)]
+        taps = np.zeros((V, max(len(w) for w in per_video)), np.float32)
+        for v, w in enumerate(per_video):
+            taps[v, :len(w)] = w
+        return np.repeat(taps, int(G), axis=0), np.ascontiguousarray(np.repeat(gain, int(G), axis=0))
+
+
 def is_video_file(path):
     """whether an ``.npz`` holds whole videos (``video_00000``, ...) and not a ``clips`` array"""
     with np.load(path, allow_pickle=True) as z:
@@ -460,3 +631,40 @@ def load_weights(path, arch=None):
         if bad:
             raise ValueError(f"{path}: shape mismatch for {arch}: {bad[0]} is {W[bad[0]].shape}, expected {want[bad[0]]}")
     return W
+
+
+def add_capture_arguments(ap):
+    """the command-line surface of the capture channel, shared by the two r2plus1d scripts; everything off by default"""
+    ap.add_argument("--capture-subframe", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="--flicker-time video: train through a "
+                    "camera's capture channel, its sub-frame phase (where in the emitter's row a camera frame starts) drawn uniformly "
+                    "from [LO, HI) within [0, 1] per video and step.  Any --capture-* option switches the channel on; the others keep "
+                    "the identity (phase 0, exposure 1 row, gain 1)")
+    ap.add_argument("--capture-exposure", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="the camera's exposure in emitter rows, "
+                    "within [0, 3] (0: an instantaneous sample): a frame records the mix of the 1..4 rows its exposure window covers")
+    ap.add_argument("--capture-gain", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="the gain the captured flicker is scaled by "
+                    "(emitter colour response, white balance, ambient dilution), >= 0")
+    ap.add_argument("--capture-gain-mode", default=None, choices=list(CAPTURE_GAIN_MODES), help="one gain for the three colour channels (common, "
+                    "the default) or one each (per_channel)")
+    ap.add_argument("--capture-seed", type=int, default=None, help="the channels are drawn from numpy.random.default_rng(seed) (default 0)")
+    ap.add_argument("--eval-capture-draws", type=int, default=0, metavar="N", help="after training, score the attack over N random captures per "
+                    "video drawn from the channel (evaluate_videos(capture=, capture_draws=N)): the fooling ratio of every draw, their mean "
+                    "and minimum")
+
+
+def capture_from_arguments(ap, a):
+    """the CaptureChannel the ``--capture-*`` options of ``add_capture_arguments`` describe, or None when none of them is given.  Any of them
+    without ``--flicker-time video`` is an argparse error, and so are values a channel cannot take"""
+    given = [o for o, v in (("--capture-subframe", a.capture_subframe), ("--capture-exposure", a.capture_exposure), ("--capture-gain", a.capture_gain),
+                            ("--capture-gain-mode", a.capture_gain_mode), ("--capture-seed", a.capture_seed),
+                            ("--eval-capture-draws", a.eval_capture_draws or None)) if v is not None]
+    if not given:
+        return None
+    if a.flicker_time != "video":
+        ap.error(f"{', '.join(given)}: the capture channel needs --flicker-time video (it mixes the rows a video's frames carry)")
+    if a.eval_capture_draws < 0:
+        ap.error(f"--eval-capture-draws must be >= 0, got {a.eval_capture_draws}")
+    try:
+        return CaptureChannel(subframe=tuple(a.capture_subframe or (0.0, 0.0)), exposure=tuple(a.capture_exposure or (1.0, 1.0)),
+                              gain=tuple(a.capture_gain or (1.0, 1.0)), gain_mode=a.capture_gain_mode or "common", seed=a.capture_seed or 0)
+    except ValueError as e:
+        ap.error(str(e))

@@ -329,6 +329,28 @@ int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s2d, int dty
 int flk_flicker_rows_gather(const float* delta, int P, const int32_t* rows, int n, float* delta_clip, void* stream);
 int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows, void* stream);
 
+/* Capture channel: the flicker as a CAMERA records it.  Frame i integrates the emitter over an exposure window that starts a sub-frame
+ * phase after its own row, so it records a convex mix of K = 1..4 consecutive rows of delta, and the emitter / white balance / ambient
+ * light scale each channel by a gain.  Frame i belongs to clip b = i / clip_T (n % clip_T == 0); taps: DEVICE fp32 [n/clip_T][K], one
+ * row per clip (videoresnet_spec.capture_taps makes one; rows padded with 0 to a common K); gain: DEVICE fp32 [n/clip_T][3], or null
+ * for none.  A linear map at the same seam as the pair above -- the mix in the gather's place, its transpose in the row gradient's:
+ *   flk_flicker_rows_mix:      r0 = clamp(rows[i], 0, P-1);  acc = taps[b][0] * delta[r0][c];
+ *                              for k = 1 .. K-1: acc = acc + taps[b][k] * delta[(r0 + k) mod P][c];
+ *                              delta_clip[i][c] = gain ? gain[b][c] * acc : acc.            RAW values, as the gather's.
+ *   flk_flicker_rows_mix_grad: g_rows[r][c] = the sum, from +0, over the frames i ASCENDING and within a frame the taps k ASCENDING with
+ *                              (rows[i] + k) mod P == r, of (gain ? gain[b][c] * taps[b][k] : taps[b][k]) * g_clip[i][c].  P < K is legal
+ *                              (a frame then reaches one row through two taps: both are added); entries of rows outside [0,P) are
+ *                              skipped; a row nothing reaches is written as 0.  One thread per output, no atomics, rows staged in LDS.
+ * Every product and every sum is rounded to fp32 on its own (no fused multiply-add), in that one order: videoresnet_spec.flicker_rows_mix
+ * and flicker_rows_mix_grad restate both on the host bit for bit.  With K = 1, taps = 1 and gain null or all ones the two launches give the
+ * bits of flk_flicker_rows_gather / flk_flicker_rows_grad.  One launch each, no allocation, no synchronisation.
+ * FLK_EINVAL before any GPU call: a null delta / g_clip, rows, taps or output, n < 1, clip_T < 1 or n % clip_T != 0, K outside 1..4,
+ * P outside 1..682. */
+int flk_flicker_rows_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain,
+                         float* delta_clip, void* stream);
+int flk_flicker_rows_mix_grad(const float* g_clip, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain, int P,
+                              float* g_rows, void* stream);
+
 /* Fused form of (stem data-gradient + flk_perturb_grad_reduce) for the flickering perturbation of I3D: d(loss)/d(delta[t,c]) straight
  * from G = d(loss)/d(pre-ReLU output of Conv3d_1a_7x7) (bf16 [B,T/2,H/2,W/2,g_ld], 64 channels) -- replaces Conv3DBackpropInputV2 of
  * i3d.py:169 and the clip_by_value / reduce_sum gradients of kinetics_i3d_utils.py:100-142 with ONE MFMA kernel in the weight-gradient

@@ -19,7 +19,10 @@ it (dataset.py:500-586: `--sample-step`, `--temporal-jitter`, `--temporal-jitter
 clips at the evaluation's uniform offsets are cut from each video once and the adversarial loss is taken on their aggregated logits
 (`--video-reduce sum`, or `mean` = sum / G: same argmax); a video counts as adversarial when the argmax of those logits leaves its label.
 `--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame carrying the row of
-its frame number in the video, which is what `--eval-quantised video` lays over the whole video; the result files hold `flicker_period`."""
+its frame number in the video, which is what `--eval-quantised video` lays over the whole video; the result files hold `flicker_period`.
+`--capture-subframe / --capture-exposure / --capture-gain LO HI` (with `--capture-gain-mode`, `--capture-seed`; video time only) train the
+flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` scores the final flicker over N random
+captures (`capture_video_preds`, `capture_video_is_adversarial` [N], `capture_draws`)."""
 import argparse
 import os
 import sys
@@ -63,7 +66,7 @@ def run_whole_videos(a):
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
                                  clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
@@ -75,6 +78,23 @@ def run_whole_videos(a):
         clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
     out = learner.fit_many_videos(clips, crit, lr=LR, model_dir=dest, label_id_to_text=classes, n_iter=a.n_iter, restart_after=a.restart_after,
                                   reset_optimizer_per_video=a.reset_optimizer_per_video, **export_kw(a))
+    if a.eval_capture_draws:
+        # the attack as N random cameras record it: each video's final flicker through N channels drawn from --capture-*
+        for i, name in enumerate(names):
+            r = out.get(str(name))
+            if r is None:
+                continue
+            learner.pert_model.init_perturbation(r["perturbation"][-1])
+            learner.pert_model.dynamic_max_norm = max(learner.pert_model.max_norm, r["perturbation/inf_norm"])
+            ev = learner.evaluate_videos([xd[i]], labels[i:i + 1], num_samples=G, adversarial=True, quantise=a.eval_quantised, capture=a.capture,
+                                         capture_draws=a.eval_capture_draws)
+            r["capture_draws"] = ev["capture_draws"]
+            r["capture_video_preds"] = ev["capture_video_logits"].argmax(-1)[:, 0]
+            r["capture_video_is_adversarial"] = r["capture_video_preds"] != labels[i]
+            if a.eval_quantised != "video":          # (that branch below saves the file itself)
+                cls = (classes[int(labels[i])] if classes is not None else str(int(labels[i]))).replace(" ", "_")
+                np.save(os.path.join(dest, f"{os.path.basename(str(name))}_@{cls}.npy"), dict(r, prob_clean_input=r["prob_clean_input"].cpu().numpy()),
+                        allow_pickle=True)
     if a.eval_quantised == "video":
         # the attack as a whole video delivers it: each video's final flicker laid over ALL its frames at their own resolution
         # (export_video), the stored video then scored by the ordinary clean evaluation over its G clips
@@ -108,6 +128,8 @@ def report(out):
             print(f"{name}: clean clip misclassified, skipped")
         else:
             q = "".join(f", {k.replace('_', ' ')} {bool(r[k])}" for k in ("quantised_is_adversarial", "quantised_video_is_adversarial") if k in r)
+            if "capture_video_is_adversarial" in r:
+                q += f", adversarial in {int(r['capture_video_is_adversarial'].sum())} of {len(r['capture_video_is_adversarial'])} captures"
             print(f"{name}: {len(r['loss/total'])} iterations, adversarial {bool(r['is_adversarial'][-1])}, thickness "
                   f"{r['perturbation/thickness'][-1]:.4f}, roughness {r['perturbation/roughness'][-1]:.4f}, restarts {r['restarts']}{q}", flush=True)
 
@@ -168,7 +190,11 @@ def main():
                     "files hold quantised_pred / quantised_is_adversarial of the clip's 8-bit frames; video (whole-video files, --batch 1): the "
                     "final flicker over the whole video at its own resolution, scored by the clean evaluation -- quantised_video_pred, "
                     "quantised_video_is_adversarial, realised_flicker (levels per frame and channel)")
+    vs.add_capture_arguments(ap)
     a = ap.parse_args()
+    a.capture = vs.capture_from_arguments(ap, a)
+    if a.eval_capture_draws and not vs.is_video_file(a.videos_npz):
+        ap.error("--eval-capture-draws needs a whole-video .npz file: the captures are scored on the video's evaluation clips")
     if a.eval_quantised == "video" and (not vs.is_video_file(a.videos_npz) or a.batch > 1 or a.attack_type != "flickering"):
         raise ValueError("--eval-quantised video needs a whole-video .npz file, --batch 1 and the flickering attack (one flicker per video, laid "
                          "over all its frames)")
@@ -203,7 +229,7 @@ def main():
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -43,7 +43,10 @@ same argmax, margin on the scale of one clip's logits).  Loss averages and fooli
 
 `--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame of every clip
 carrying the row of its frame number in its video -- what `--eval-quantised video` and `--save-adversarial-u8` lay over whole videos.
-The epoch results hold `flicker_period`."""
+The epoch results hold `flicker_period`.
+`--capture-subframe / --capture-exposure / --capture-gain LO HI` (with `--capture-gain-mode`, `--capture-seed`; video time only) train the
+flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` (whole-video files) scores the trained
+flicker over N random captures of the validation videos (`video_eval_capture.npz`)."""
 import argparse
 import glob
 import os
@@ -160,7 +163,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -197,6 +200,18 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                 ev["realised_flicker"] = np.concatenate(ev["realised_flicker"])
             os.makedirs(dest, exist_ok=True)
             np.savez(os.path.join(dest, "video_eval_quantised.npz"), num_samples=np.int64(S), quantise=a.eval_quantised, **ev)
+        if a.eval_capture_draws:                # the attack as N random cameras record it: video_eval_capture.npz
+            S = max(a.eval_num_samples, 1)
+            ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=S, adversarial=True, quantise=a.eval_quantised,
+                                         capture=a.capture, capture_draws=a.eval_capture_draws)
+            print(f"capture evaluation, {a.eval_capture_draws} draws, {S} clips per video: video fooling ratio mean "
+                  f"{ev['capture_video_fooling_ratio_mean']:.4f} min {ev['capture_video_fooling_ratio_min']:.4f} (no channel: "
+                  f"{ev['video_fooling_ratio']:.4f})", flush=True)
+            draws = ev.pop("capture_draws")
+            ev.pop("realised_flicker", None)
+            os.makedirs(dest, exist_ok=True)
+            np.savez(os.path.join(dest, "video_eval_capture.npz"), num_samples=np.int64(S), capture_subframe=np.stack([d["subframe"] for d in draws]),
+                     capture_exposure=np.stack([d["exposure"] for d in draws]), capture_gain=np.stack([d["gain"] for d in draws]), **ev)
         if a.save_adversarial_u8:               # the validation videos under the universal flicker, whole and at their own resolution
             os.makedirs(dest, exist_ok=True)
             np.savez(os.path.join(dest, "adversarial_u8.npz"), labels=yva,
@@ -305,7 +320,11 @@ def main():
                     "it.  clip: every validation clip exported at the engine's size (quantised_eval.npz; whole-video files: "
                     "video_eval_quantised.npz); video (whole-video files): every validation video flickered whole at its own resolution, "
                     "then the clean evaluation (video_eval_quantised.npz)")
+    vs.add_capture_arguments(ap)
     a = ap.parse_args()
+    a.capture = vs.capture_from_arguments(ap, a)
+    if a.eval_capture_draws and not vs.is_video_file(a.val_npz):
+        ap.error("--eval-capture-draws needs whole-video .npz files: the captures are scored on the validation videos' evaluation clips")
     if a.eval_quantised == "video" and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
         raise ValueError("--eval-quantised video needs whole-video .npz files: a file of clips holds no whole video to flicker")
     if (a.eval_quantised == "video" or (a.save_adversarial_u8 and vs.is_video_file(a.val_npz))) and a.attack_type != "flickering":
@@ -348,7 +367,7 @@ def main():
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
                                  augment=None if host_aug else augment, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
     host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
