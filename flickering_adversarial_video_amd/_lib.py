@@ -53,7 +53,7 @@ class ApplyArgs(C.Structure):
                 ("lo", C.c_float), ("hi", C.c_float), ("adv_flag", C.c_float),
                 ("shift_x", C.c_int), ("shift_p", C.c_int),
                 ("B", C.c_int), ("T", C.c_int), ("H", C.c_int), ("W", C.c_int), ("fold_t", C.c_int), ("center", C.c_int),
-                ("delta_per_clip", C.c_int), ("dclip_dev", C.c_void_p),
+                ("delta_per_clip", C.c_int), ("delta_per_line", C.c_int), ("dclip_dev", C.c_void_p),
                 ("q_lut", C.c_void_p), ("q_mul", C.c_float * 3), ("q_add", C.c_float * 3), ("q_levels", C.c_float),
                 ("x_lut", C.c_void_p)]
 
@@ -127,6 +127,10 @@ _SIGS = {
     "flk_flicker_rows_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_flicker_rows_mix_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                             C.c_void_p]),
+    "flk_flicker_lines_mix": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                        C.c_void_p]),
+    "flk_flicker_lines_mix_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                             C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_sampled": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -223,13 +223,14 @@ extern "C" int flk_adv_export_u8(const flk_apply_args* a, const flk_export_args*
   FLK_REQUIRE(a->lo <= a->hi, "flk_adv_export_u8: lo > hi");
   FLK_REQUIRE(!(a->delta_per_clip && a->delta_dense), "flk_adv_export_u8: delta_per_clip is defined for the flicker perturbation only");
   FLK_REQUIRE(!a->dclip_dev || a->delta_per_clip, "flk_adv_export_u8: dclip_dev (per-clip clamp bounds) needs delta_per_clip");
+  FLK_REQUIRE(!(a->delta_per_line && a->delta_dense), "flk_adv_export_u8: delta_per_line (one value per line of a frame) excludes delta_dense");
   FLK_REQUIRE(!a->x_lut || a->x_is_u8, "flk_adv_export_u8: x_lut (per-channel decode table) needs a uint8 clip");
   FLK_REQUIRE(e->levels > 0.f && e->levels <= 3.4e38f, "flk_adv_export_u8: levels must be positive");
   FLK_REQUIRE(e->out_clip_offset >= 0, "flk_adv_export_u8: negative out_clip_offset");
   FLK_REQUIRE(e->out_clip_stride >= (int64_t)a->T * a->H * a->W * 3, "flk_adv_export_u8: out_clip_stride %lld smaller than the clip",
               (long long)e->out_clip_stride);
   FLK_REQUIRE(e->delta_T >= 0, "flk_adv_export_u8: negative delta_T");
-  FLK_REQUIRE(e->delta_T == 0 || !(a->delta_dense || a->delta_per_clip), "flk_adv_export_u8: delta_T (a period) is defined for the shared flicker perturbation [delta_T,3] only");
+  FLK_REQUIRE(e->delta_T == 0 || !(a->delta_dense || a->delta_per_clip), "flk_adv_export_u8: delta_T (a period) is defined for the shared flicker perturbation [delta_T,3] (delta_per_line: [delta_T,H,3]) only");
   FLK_REQUIRE(!stats || (int64_t)a->H * a->W <= 8388607, "flk_adv_export_u8: stats need H * W <= 8388607 (255 * H * W must fit an int32), got %d x %d", a->H, a->W);
   return flk_adv_export_u8_launch(a, e, out, stats, (hipStream_t)stream);
 }

@@ -104,10 +104,13 @@ __device__ static inline void stage_q_lut(const flk_apply_args& a, float* ql) {
 }
 
 // perturbation added at frame t (before adv_flag): p'[t] = p[(t - shift_p) mod T] (tf.roll), p = clip(delta)/std
-// (delta_per_clip: clip b has its own [T,3] perturbation)
+// (delta_per_clip: clip b has its own [T,3] perturbation; delta_per_line: one value per line of a frame, [Bd,T,H,3] -- a branch that
+// is uniform over the launch; the callers that hoist the three values of a frame take the per-element route for it, as for dense)
 __device__ static inline float pert_at(const flk_apply_args& a, int b, int t, int h, int w, int c) {
   const int ts = wrap(t - a.shift_p, a.T);
-  float d = a.delta_dense ? a.delta[(((size_t)ts * a.H + h) * a.W + w) * 3 + c] : a.delta[(a.delta_per_clip ? b * a.T : 0) * 3 + ts * 3 + c];
+  float d;
+  if (a.delta_per_line) d = a.delta[(((size_t)(a.delta_per_clip ? b : 0) * a.T + ts) * a.H + h) * 3 + c];
+  else d = a.delta_dense ? a.delta[(((size_t)ts * a.H + h) * a.W + w) * 3 + c] : a.delta[(a.delta_per_clip ? b * a.T : 0) * 3 + ts * 3 + c];
   const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;       // (per-clip clamp bound)
   if (dc > 0.f) d = clipf(d, -dc, dc);
   return d * a.inv_std[c];
@@ -249,7 +252,8 @@ __global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_app
 // resident uint8 clip.  Laid out like apply_s2d_u8_flicker_kernel: one thread = 4 consecutive output positions of one (clip, frame,
 // row pair), each of its two source rows read as three aligned 8-byte loads (24 bytes = 8 pixels); the 768-entry table is staged in
 // LDS once per workgroup.  Per element the arithmetic of apply_s2d_hilo_kernel on the decoded value, so the bytes written equal
-// that kernel's on the fp32 clip x_lut[u8].  DENSE: the [T,H,W,3] perturbation (per element); else [T,3] / [B,T,3] (3 values).
+// that kernel's on the fp32 clip x_lut[u8].  DENSE: the [T,H,W,3] or per-line [Bd,T,H,3] perturbation (per element); else [T,3] /
+// [B,T,3] (3 values).
 template <bool DENSE, bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_hilo_u8_kernel(const flk_apply_args a, char* out) {
   __shared__ float lut[768];
@@ -310,6 +314,8 @@ static int check_apply(const flk_apply_args* a) {
   FLK_REQUIRE(!(a->center && a->delta_dense), "flk_perturb: center = 1 is defined for the flicker perturbation [T,3] only");
   FLK_REQUIRE(!(a->delta_per_clip && a->delta_dense), "flk_perturb: delta_per_clip is defined for the flicker perturbation only");
   FLK_REQUIRE(!a->dclip_dev || a->delta_per_clip, "flk_perturb: dclip_dev (per-clip clamp bounds) needs delta_per_clip");
+  FLK_REQUIRE(!(a->delta_per_line && (a->delta_dense || a->center)), "flk_perturb: delta_per_line (one value per line of a frame) excludes delta_dense and center = 1");
+  FLK_REQUIRE(!a->delta_per_line || a->fold_t == 1 || a->fold_t == 4, "flk_perturb: delta_per_line is defined for fold_t 1 and 4 (the VideoResNet layouts), got fold_t %d", a->fold_t);
   FLK_REQUIRE(!a->x_lut || (a->x_is_u8 && !a->center), "flk_perturb: x_lut (per-channel decode table) needs a uint8 clip and center = 0");
   FLK_REQUIRE(!a->q_lut || (!a->center && a->q_levels > 0.f), "flk_perturb: q_lut (quantised apply) needs center = 0 and q_levels > 0");
   // load6 reads a uint8 clip with 2-byte loads and an fp32 clip with 8-byte loads (every pixel pair starts at a multiple of 6 values)
@@ -335,7 +341,7 @@ extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dty
       const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)a->T, (unsigned)a->B);
 #define FLK_HILO_U8(D) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, true>), g3, dim3(256), 0, st, *a, (char*)out); \
                            else FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
-      if (a->delta_dense) FLK_HILO_U8(true); else FLK_HILO_U8(false);
+      if (a->delta_dense || a->delta_per_line) FLK_HILO_U8(true); else FLK_HILO_U8(false);
 #undef FLK_HILO_U8
     } else if (quant) {
       FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel<true>, dim3(grid), dim3(256), 0, st, *a, (char*)out);
@@ -407,7 +413,8 @@ __global__ __launch_bounds__(256) void adv_export_u8_kernel(const flk_apply_args
       int pix = start / 3, c = start - pix * 3;
       int h = pix / a.W, w = pix - h * a.W;
       float pvf[3] = {0.f, 0.f, 0.f};
-      if (!a.delta_dense) {
+      const bool per_element = a.delta_dense || a.delta_per_line;     // (per line: a unit of four bytes may span two lines)
+      if (!per_element) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) pvf[k] = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, 0, 0, k) : 0.f;
       }
@@ -436,7 +443,7 @@ __global__ __launch_bounds__(256) void adv_export_u8_kernel(const flk_apply_args
         if (j < cnt) {
           const float x = a.x_is_u8 ? decode1(a, by[j], c) : xs[j];
           float pv;
-          if (a.delta_dense) pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, h, w, c) : 0.f;
+          if (per_element) pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, h, w, c) : 0.f;
           else pv = c == 0 ? pvf[0] : c == 1 ? pvf[1] : pvf[2];
           const float mul = c == 0 ? e.mul[0] : c == 1 ? e.mul[1] : e.mul[2];
           const float add = c == 0 ? e.add[0] : c == 1 ? e.add[1] : e.add[2];
@@ -626,6 +633,60 @@ __global__ __launch_bounds__(256) void grad_dense_kernel(const flk_apply_args a,
   }
 }
 
+// per-line delta (delta_per_line with delta_per_clip; fold_t 1 / 4: the 16-channel gradient): one wave owns one (clip b, frame t, row
+// pair h2) of the space-to-depth gradient and produces its 2 lines x 3 channels.  Lane l walks the positions w2 = l, l + 64, ... in
+// ascending order (per position pixel 2*w2, then 2*w2 + 1), then the 64 partial sums are folded by the shuffle tree 32, 16, .., 1: one
+// fixed order, no atomics, no scratch.  The mask is stage 1's (the same expression); the tail is stage 2's, per line.
+template <typename TI>
+__global__ __launch_bounds__(256) void grad_lines_kernel(const flk_apply_args a, const char* gx, float* gdelta) {
+  const int H2 = a.H / 2, W2 = a.W / 2;
+  const long nwork = (long)a.B * a.T * H2;
+  const int lane = threadIdx.x & 63;
+  for (long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6); item < nwork; item += (long)gridDim.x * 4) {      // uniform over the wave
+    long r = item;
+    const int h2 = (int)(r % H2); r /= H2;
+    const int t = (int)(r % a.T);
+    const int b = (int)(r / a.T);
+    const int tx = wrap(t - a.shift_x, a.T);
+    float p[2][3];
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) p[qh][c] = pert_at(a, b, t, 2 * h2 + qh, 0, c);
+    float acc[2][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+    for (int w2 = lane; w2 < W2; w2 += 64) {
+      float g[12];
+      load_ch<TI, 12>(gx + ((((size_t)b * a.T + t) * H2 + h2) * W2 + w2) * 16 * sizeof(TI), g);
+#pragma unroll
+      for (int qh = 0; qh < 2; ++qh) {
+        float x[6];
+        load6(a, ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 2 * w2) * 3, x);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+          const float u = x[k] + a.adv_flag * p[qh][k % 3];
+          if (u >= a.lo && u <= a.hi) acc[qh][k % 3] += g[S2D<1>::ch(0, qh, k)];
+        }
+      }
+    }
+    const int ts = wrap(t - a.shift_p, a.T);
+    const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float v = acc[qh][c];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) {
+          const size_t di = ((((size_t)b * a.T + ts) * a.H) + 2 * h2 + qh) * 3 + c;
+          const float d = a.delta[di];
+          const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
+          gdelta[di] = pass ? v * a.adv_flag * a.inv_std[c] : 0.f;
+        }
+      }
+  }
+}
+
 extern "C" int64_t flk_perturb_grad_scratch_bytes(int B, int T, int H, int W) {
   (void)W;
   if (B <= 0 || T <= 0 || H <= 0) return 0;
@@ -643,7 +704,13 @@ extern "C" int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s
   // (fold_t = 4: the clip went in as two bf16 numbers per value; its gradient comes back in the 16-channel fold_t = 1 layout)
   const int ftl = (a->fold_t == 1 || a->fold_t == 4) ? 1 : a->fold_t == 3 ? 3 : 2, ft = ftl == 1 ? 1 : 2;
   const bool bf = dtype == FLK_BF16;
-  if (a->delta_dense) {
+  if (a->delta_per_line) {
+    FLK_REQUIRE(a->delta_per_clip, "flk_perturb_grad_reduce: delta_per_line needs delta_per_clip (the gradient comes back per clip, [B,T,H,3])");
+    const long waves = (long)a->B * a->T * (a->H / 2);
+    const unsigned grid = (unsigned)((waves + 3) / 4 > 262144 ? 262144 : (waves + 3) / 4);
+    if (bf) FLK_LAUNCH_KERNEL(grad_lines_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta);
+    else FLK_LAUNCH_KERNEL(grad_lines_kernel<float>, dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta);
+  } else if (a->delta_dense) {
     const long total = (long)(a->T / ft) * (a->H / 2) * (a->W / 2);
     const unsigned grid = (unsigned)((total + 255) / 256);
 #define FLK_GD(TT, L) FLK_LAUNCH_KERNEL((grad_dense_kernel<TT, L>), dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta)
@@ -1134,6 +1201,115 @@ extern "C" int flk_flicker_rows_mix_grad(const float* g_clip, const int32_t* row
   FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_mix_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
   FLK_LAUNCH_KERNEL(flicker_rows_mix_grad_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, clip_T,
                      taps, K, gain, P, g_rows);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// ---- rolling shutter: the capture channel per line of a frame (include/flicker_hip.h) ---------------------------------------------------
+// Line h of a frame has its own taps [K <= 5] (it starts its exposure later than line 0): the mix writes the per-line perturbation
+// [n][H][3] that flk_apply_args.delta_per_line takes; its transpose folds the per-line gradient back to [P][3].  The arithmetic and its
+// order are the rows pair's above (mul_rn / add_rn: nothing contracts), so videoresnet_spec.flicker_lines_mix / _mix_grad restate both.
+constexpr int LINES_MIX_MAX_K = 5;
+
+// one thread = one output value (frame i, line h, channel c)
+__global__ __launch_bounds__(256) void flicker_lines_mix_kernel(const float* delta, int P, const int32_t* rows, int n, int clip_T, int H,
+                                                                const float* taps, int K, const float* gain, float* out) {
+  const long total = 3L * n * H;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long fh = i / 3;
+    const int c = (int)(i - 3 * fh), f = (int)(fh / H), h = (int)(fh - (long)f * H), b = f / clip_T;
+    int r = rows[f];
+    r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
+    const float* w = taps + ((size_t)b * H + h) * K;
+    float acc = mul_rn(w[0], delta[r * 3 + c]);
+    for (int k = 1; k < K; ++k) {
+      r = r + 1 == P ? 0 : r + 1;
+      acc = add_rn(acc, mul_rn(w[k], delta[r * 3 + c]));
+    }
+    out[i] = gain ? mul_rn(gain[(size_t)b * 3 + c], acc) : acc;
+  }
+}
+
+// transpose, stage 1: one thread = one (frame i, tap k, channel c); the lines of the frame in ascending order, from +0
+__global__ __launch_bounds__(256) void flicker_lines_mix_grad_stage1(const float* g_lines, int n, int clip_T, int H, const float* taps, int K,
+                                                                     const float* gain, float* sbuf) {
+  const long total = 3L * n * K;
+  for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < total; o += (long)gridDim.x * 256) {
+    const long ik = o / 3;
+    const int c = (int)(o - 3 * ik), i = (int)(ik / K), k = (int)(ik - (long)i * K), b = i / clip_T;
+    const float* w = taps + (size_t)b * H * K + k;
+    const float* g = g_lines + (size_t)i * H * 3 + c;
+    const float gn = gain ? gain[(size_t)b * 3 + c] : 1.f;
+    float s = 0.f;
+    for (int h = 0; h < H; ++h) {
+      const float wk = w[(size_t)h * K];
+      s = add_rn(s, mul_rn(gain ? mul_rn(gn, wk) : wk, g[(size_t)h * 3]));
+    }
+    sbuf[o] = s;
+  }
+}
+
+// transpose, stage 2: flicker_rows_mix_grad_kernel's fold over s[n][K][3] (the coefficients are inside s already): one thread = one
+// output (row r, channel c), rows staged in LDS piece by piece, frames ascending, taps ascending, from +0
+__global__ __launch_bounds__(256) void flicker_lines_mix_grad_stage2(const float* sbuf, const int32_t* rows, int n, int K, int P, float* g_rows) {
+  __shared__ int32_t sh[ROWS_PIECE];
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const bool live = o < 3 * P;
+  const int r = o / 3, c = o - 3 * r;
+  float s = 0.f;
+  for (int base = 0; base < n; base += ROWS_PIECE) {
+    const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
+    for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
+    __syncthreads();
+    if (live)
+      for (int j = 0; j < m; ++j) {
+        const int q = sh[j];
+        if (q >= 0 && q < P) {
+          int k = r - q;
+          k = k < 0 ? k + P : k;
+          for (; k < K; k += P) s = add_rn(s, sbuf[((size_t)(base + j) * K + k) * 3 + c]);
+        }
+      }
+    __syncthreads();            // sh is refilled by the next piece
+  }
+  if (live) g_rows[o] = s;
+}
+
+extern "C" int flk_flicker_lines_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K,
+                                     const float* gain, float* out, void* stream) {
+  FLK_REQUIRE(delta, "flk_flicker_lines_mix: delta is null");
+  FLK_REQUIRE(rows, "flk_flicker_lines_mix: rows is null");
+  FLK_REQUIRE(taps, "flk_flicker_lines_mix: taps is null");
+  FLK_REQUIRE(out, "flk_flicker_lines_mix: out is null");
+  FLK_REQUIRE(n >= 1, "flk_flicker_lines_mix: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_lines_mix: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
+  FLK_REQUIRE(H >= 1, "flk_flicker_lines_mix: H (lines of a frame) must be >= 1 (got %d)", H);
+  FLK_REQUIRE(K >= 1 && K <= LINES_MIX_MAX_K, "flk_flicker_lines_mix: K (taps per line) must be 1 .. %d (got %d)", LINES_MIX_MAX_K, K);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_lines_mix: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  const long blocks = (3L * n * H + 255) / 256;
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
+                     clip_T, H, taps, K, gain, out);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+extern "C" int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K,
+                                          const float* gain, int P, float* scratch, float* g_rows, void* stream) {
+  FLK_REQUIRE(g_lines, "flk_flicker_lines_mix_grad: g_lines is null");
+  FLK_REQUIRE(rows, "flk_flicker_lines_mix_grad: rows is null");
+  FLK_REQUIRE(taps, "flk_flicker_lines_mix_grad: taps is null");
+  FLK_REQUIRE(scratch, "flk_flicker_lines_mix_grad: scratch is null");
+  FLK_REQUIRE(g_rows, "flk_flicker_lines_mix_grad: g_rows is null");
+  FLK_REQUIRE(n >= 1, "flk_flicker_lines_mix_grad: n must be >= 1 (got %d)", n);
+  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_lines_mix_grad: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
+  FLK_REQUIRE(H >= 1, "flk_flicker_lines_mix_grad: H (lines of a frame) must be >= 1 (got %d)", H);
+  FLK_REQUIRE(K >= 1 && K <= LINES_MIX_MAX_K, "flk_flicker_lines_mix_grad: K (taps per line) must be 1 .. %d (got %d)", LINES_MIX_MAX_K, K);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_lines_mix_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
+  const long blocks = (3L * n * K + 255) / 256;
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage1, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, g_lines, n,
+                     clip_T, H, taps, K, gain, scratch);
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage2, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch, rows, n, K, P,
+                     g_rows);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

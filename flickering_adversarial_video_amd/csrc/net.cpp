@@ -133,7 +133,7 @@ struct flk_net {
     sl.x = (const char*)sl.x + (size_t)b0 * sl.T * sl.H * sl.W * 3 * (sl.x_is_u8 ? 1 : 4);
     sl.B = nb;
     if (sl.delta_per_clip) {
-      sl.delta += (size_t)b0 * sl.T * 3;
+      sl.delta += (size_t)b0 * sl.T * (sl.delta_per_line ? sl.H : 1) * 3;
       if (sl.dclip_dev) sl.dclip_dev += b0;
     }
     return sl;
@@ -1462,7 +1462,7 @@ static bool same_mask_args(const flk_apply_args& p, const flk_apply_args& q) {
          p.delta_dense == q.delta_dense && p.dclip == q.dclip && p.inv_std[0] == q.inv_std[0] && p.inv_std[1] == q.inv_std[1] &&
          p.inv_std[2] == q.inv_std[2] && p.lo == q.lo && p.hi == q.hi && p.adv_flag == q.adv_flag && p.shift_x == q.shift_x &&
          p.shift_p == q.shift_p && p.B == q.B && p.T == q.T && p.H == q.H && p.W == q.W && p.delta_per_clip == q.delta_per_clip &&
-         p.dclip_dev == q.dclip_dev && p.x_lut == q.x_lut;
+         p.dclip_dev == q.dclip_dev && p.x_lut == q.x_lut && p.delta_per_line == q.delta_per_line;
 }
 
 // start the clip-mask pre-pass of the fused stem delta-gradient on the net's mask stream, behind everything queued on `s` so far (the
@@ -1480,6 +1480,7 @@ static int start_mask_prepass(flk_net* n, const flk_apply_args* a, float* scratc
 extern "C" int flk_net_backward_delta(flk_net* n, const float* dlogits, const flk_apply_args* a, float* gdelta, float* partials, void* stream) {
   FLK_REQUIRE(n && n->finalized && dlogits && a && gdelta && partials, "flk_net_backward_delta: bad argument / not finalized");
   FLK_REQUIRE(n->d_stem_wf && n->stem_dgrad_op >= 0, "flk_net_backward_delta: only the I3D plan in bf16 has the fused stem delta-gradient");
+  FLK_REQUIRE(!a->delta_per_line, "flk_net_backward_delta: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   if (int rc = check_apply_geometry(n, a, "flk_net_backward_delta")) return rc;
   if (!n->fwd_done) { flk_set_error("flk_net_backward_delta: no forward pass to differentiate"); return FLK_ESTATE; }
   n->dlogits_in = dlogits; n->gx_in = nullptr;

@@ -377,6 +377,7 @@ extern "C" int flk_stem_fwd_u8(const flk_apply_args* a, const flk_conv_weights* 
                                const float* pos_bias, int64_t pos_bias_bstride, void* out, int out_ld, void* stream) {
   FLK_REQUIRE(!a || !a->x_lut, "flk_stem_fwd_u8: x_lut (per-channel decode table) is not supported: the I3D stem decodes x_scale / x_bias");
   FLK_REQUIRE(!a || !a->q_lut, "flk_stem_fwd_u8: q_lut (quantised apply) is not supported: the I3D stem takes the centred clip");
+  FLK_REQUIRE(!a || !a->delta_per_line, "flk_stem_fwd_u8: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   FLK_REQUIRE(a && w && w->dev && bn_scale && bn_bias && out, "flk_stem_fwd_u8: null argument");
   FLK_REQUIRE(a->x && a->delta && a->x_is_u8 && a->center == 1 && !a->delta_dense, "flk_stem_fwd_u8: needs a uint8 clip and a flicker "
               "perturbation applied with center = 1");

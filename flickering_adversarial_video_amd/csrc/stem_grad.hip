@@ -479,6 +479,7 @@ static int sg_check(const flk_apply_args* a) {
   FLK_REQUIRE(!a->delta_dense, "flk_stem_delta_grad: flicker perturbation [T,3] only (the dense attack needs the per-pixel gradient)");
   FLK_REQUIRE(!a->x_lut, "flk_stem_delta_grad: x_lut (per-channel decode table) is not supported: the I3D stem decodes x_scale / x_bias");
   FLK_REQUIRE(!a->q_lut, "flk_stem_delta_grad: q_lut (quantised apply) is not supported: the I3D stem takes the centred clip");
+  FLK_REQUIRE(!a->delta_per_line, "flk_stem_delta_grad: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   FLK_REQUIRE(a->B > 0 && a->T >= 2 && a->T % 2 == 0 && a->H > 0 && a->H % 2 == 0 && a->W == 224,
               "flk_stem_delta_grad: T, H must be even and W = 224 (the I3D stem; got %d, %d, %d)", a->T, a->H, a->W);
   FLK_REQUIRE(a->lo <= a->hi, "flk_stem_delta_grad: lo > hi");
@@ -605,6 +606,7 @@ extern "C" int flk_stem_delta_bias(const flk_apply_args* a, const float* sums_de
   FLK_REQUIRE(!a->delta_dense && a->T >= 2 && a->T % 2 == 0, "flk_stem_delta_bias: flicker perturbation [T,3], even T");
   FLK_REQUIRE(!a->x_lut, "flk_stem_delta_bias: x_lut (per-channel decode table) is not supported by the I3D stem");
   FLK_REQUIRE(!a->q_lut, "flk_stem_delta_bias: q_lut (quantised apply) is not supported by the I3D stem");
+  FLK_REQUIRE(!a->delta_per_line, "flk_stem_delta_bias: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   FLK_LAUNCH_KERNEL(stem_delta_bias_kernel, dim3((unsigned)(a->T / 2 * 16), (unsigned)(a->delta_per_clip ? a->B : 1)), dim3(64), 0, (hipStream_t)stream,
                      *a, sums_dev, table_out);
   FLK_CHECK_HIP(hipGetLastError());

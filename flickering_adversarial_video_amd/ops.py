@@ -298,9 +298,11 @@ def quant_table(dialect, device):
 
 
 def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0),
-                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None, x_lut=None, quantise=None, q_lut=None):
+                    lo=-1.0, hi=1.0, fold_t=2, center=False, dclip_dev=None, x_lut=None, quantise=None, q_lut=None, per_line=False):
     """x: uint8 or fp32 [B,T,H,W,3] on the GPU; delta fp32 [T,3] (flicker, shared by the batch), [B,T,3] (one flicker perturbation PER
-    CLIP: independent single-video attacks advancing in one batch) or [T,H,W,3] (dense).  x_lut: fp32 [256,3] on the device (uint8 x
+    CLIP: independent single-video attacks advancing in one batch) or [T,H,W,3] (dense).  per_line=True (fold_t 1 and 4, no centre):
+    delta is fp32 [T,H,3] or [B,T,H,3] -- one value per LINE of a frame (flk_apply_args.delta_per_line, ``flicker_lines_mix`` makes it);
+    named by the keyword because a 4-D delta means dense.  x_lut: fp32 [256,3] on the device (uint8 x
     only): byte v of channel c decodes to x_lut[v, c] (videoresnet_spec.u8_decode_table) instead of the dialect's scalar decode.
     quantise: None, or the dialect ("torch" | "tf") of EXPORT_DIALECTS whose 8-bit round trip the apply kernels put every value through
     (flk_apply_args.q_lut: the clip the network sees is the STORED video; the gradient is the straight-through estimator, which the
@@ -331,9 +333,16 @@ def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=
     # TFRecord path: x = u8/128 - 1 (pre_process_rgb_flow.py:226-234)
     a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
     a.delta = ptr(delta)
-    a.delta_dense = int(delta.dim() == 4)
-    a.delta_per_clip = int(delta.dim() == 3)
-    assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
+    if per_line:
+        if tuple(delta.shape) not in ((T, H, 3), (B, T, H, 3)):
+            raise ValueError(f"per_line: delta must be fp32 [{T},{H},3] or [{B},{T},{H},3], got {tuple(delta.shape)}")
+        if center or fold_t not in (1, 4):
+            raise ValueError(f"per_line: fold_t 1 or 4 without center (the VideoResNet layouts), got fold_t {fold_t}, center {center}")
+        a.delta_dense, a.delta_per_clip, a.delta_per_line = 0, int(delta.dim() == 4), 1
+    else:
+        a.delta_dense = int(delta.dim() == 4)
+        a.delta_per_clip = int(delta.dim() == 3)
+        assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
     assert not (a.delta_per_clip and (shift_x or shift_p)), "per-clip perturbations: cyclic rolls are drawn per run in the reference; not batched"
     a.dclip = float(dclip)
     a.inv_std = (C.c_float * 3)(*inv_std)
@@ -380,19 +389,24 @@ def make_export_args(dialect, out_clip_stride, out_offset=0, delta_T=0):
 
 
 def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0), lo=-1.0, hi=1.0,
-                           dclip_dev=None, x_lut=None, delta_T=0):
+                           dclip_dev=None, x_lut=None, delta_T=0, per_line=False):
     """the flk_apply_args of an 8-bit export: ``make_apply_args`` without a fold (T, H and W may be odd) and, with ``delta_T``, with a
     flicker perturbation [delta_T,3] whose length is its period instead of the clip's T.  (The fields are filled as ``make_apply_args``
     fills them -- a change to one belongs in the other; only the fold, ``center`` and the shape rule of ``delta`` differ, and there is no
     ``quantise``: the export is the quantiser itself, and ``make_apply_args(quantise=dialect)`` applies the clip these bytes decode to.)  The period is
-    remembered on the result (``_delta_T``): ``export_adversarial_u8`` takes it from there."""
+    remembered on the result (``_delta_T``): ``export_adversarial_u8`` takes it from there.  per_line=True: delta is fp32 [T,H,3], [B,T,H,3]
+    or, with ``delta_T``, [delta_T,H,3] -- one value per line of a frame (flk_apply_args.delta_per_line)."""
     B, T, H, W, c3 = x.shape
     assert c3 == 3 and x.is_contiguous() and x.is_cuda and delta.is_contiguous() and delta.is_cuda and delta.dtype == torch.float32
     assert x.dtype in (torch.uint8, torch.float32) and min(B, T, H, W) > 0
     if x_lut is not None:
         assert x.dtype == torch.uint8 and x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda
     assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
-    if delta_T:
+    if per_line:
+        want = ((int(delta_T), H, 3),) if delta_T else ((T, H, 3), (B, T, H, 3))
+        if tuple(delta.shape) not in want:
+            raise ValueError(f"per_line (delta_T = {delta_T}): delta must be fp32 {' or '.join(str(list(w)) for w in want)}, got {tuple(delta.shape)}")
+    elif delta_T:
         assert tuple(delta.shape) == (int(delta_T), 3), f"delta_T = {delta_T}: the perturbation must be [{delta_T},3], got {tuple(delta.shape)}"
     else:
         assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
@@ -400,6 +414,8 @@ def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, s
     a.x, a.x_is_u8 = ptr(x), int(x.dtype == torch.uint8)
     a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
     a.delta, a.delta_dense, a.delta_per_clip = ptr(delta), int(delta.dim() == 4), int(delta.dim() == 3)
+    if per_line:
+        a.delta_dense, a.delta_per_clip, a.delta_per_line = 0, int(delta.dim() == 4), 1
     a.dclip = float(dclip)
     a.inv_std = (C.c_float * 3)(*inv_std)
     a.lo, a.hi, a.adv_flag = float(lo), float(hi), float(adv_flag)
@@ -491,9 +507,10 @@ def perturb_apply_quantised_host(x, delta, *, dialect="tf", dclip=0.4, adv_flag=
 
 def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):
     if gdelta is None:
-        shape = (args.T, args.H, args.W, 3) if args.delta_dense else (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
+        shape = (args.B, args.T, args.H, 3) if args.delta_per_line else (args.T, args.H, args.W, 3) if args.delta_dense else \
+            (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
         gdelta = torch.empty(shape, dtype=torch.float32, device="cuda")
-    if scratch is None and not args.delta_dense:
+    if scratch is None and not args.delta_dense and not args.delta_per_line:
         n = load().flk_perturb_grad_scratch_bytes(args.B, args.T, args.H, args.W)
         scratch = torch.empty(n // 4, dtype=torch.float32, device="cuda")
     check(load().flk_perturb_grad_reduce(C.byref(args), ptr(gx_s2d), dtype_code(gx_s2d.dtype), ptr(gdelta), ptr(scratch), stream_ptr()))
@@ -609,6 +626,68 @@ def flicker_rows_mix_grad(g_clip, rows, period, taps, gain=None, out=None, rows_
     _check_f32(what, "out", out, (P, 3), rows)
     check(load().flk_flicker_rows_mix_grad(ptr(g_clip), ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain) if gain is not None else None,
                                            P, ptr(out), stream_ptr()))
+    return out
+
+
+FLICKER_LINES_MAX_TAPS = 5    # rows of the perturbation one LINE of a rolling-shutter frame mixes (flk_flicker_lines_mix's K)
+
+
+def _check_lines(what, rows, taps, gain):
+    """the tables of flk_flicker_lines_mix*: ``rows`` [B,clip_T] (or [clip_T]: one clip), fp32 ``taps`` [B,H,K] with K in 1..5 and fp32
+    ``gain`` [B,3] or None, contiguous on rows' device -> (clips, clip_T, H, K)"""
+    if rows.dim() not in (1, 2):
+        raise ValueError(f"{what}: rows must be [clips,clip_T] (or [clip_T] for one clip), got {tuple(rows.shape)}")
+    nb, clip_T = (1, int(rows.shape[0])) if rows.dim() == 1 else (int(rows.shape[0]), int(rows.shape[1]))
+    if not (torch.is_tensor(taps) and taps.dim() == 3 and taps.shape[1] >= 1 and 1 <= taps.shape[2] <= FLICKER_LINES_MAX_TAPS):
+        desc = f"{tuple(taps.shape)}" if torch.is_tensor(taps) else type(taps).__name__
+        raise ValueError(f"{what}: taps must be fp32 [{nb},H,K] with K in 1..{FLICKER_LINES_MAX_TAPS} (one table per clip), got {desc}")
+    _check_f32(what, "taps", taps, (nb, int(taps.shape[1]), int(taps.shape[2])), rows)
+    if gain is not None:
+        _check_f32(what, "gain", gain, (nb, 3), rows)
+    return nb, clip_T, int(taps.shape[1]), int(taps.shape[2])
+
+
+def flicker_lines_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
+    """the flicker as a ROLLING-SHUTTER camera records it (flk_flicker_lines_mix, one launch): line h of frame t of clip b takes
+    ``gain[b] * sum_k taps[b,h,k] * delta[(rows[b,t] + k) mod P]`` -- ``delta`` fp32 [P,3], ``rows`` int32 [B,clip_T] on the device, ``taps``
+    fp32 [B,H,K] (K <= 5; videoresnet_spec.capture_line_taps / CaptureChannel.line_tables), ``gain`` fp32 [B,3] or None -> fp32
+    ``rows.shape + (H,3)``, the per-line perturbation ``make_apply_args(per_line=True)`` takes.  Raw values; every product and sum rounded
+    on its own (videoresnet_spec.flicker_lines_mix restates it bit for bit)."""
+    what = "flicker_lines_mix"
+    if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
+        raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
+    P = int(delta.shape[0])
+    _check_rows(what, rows, P, rows_host)
+    _check_f32(what, "delta", delta, (P, 3), rows)
+    _, clip_T, H, K = _check_lines(what, rows, taps, gain)
+    if out is None:
+        out = torch.empty((*rows.shape, H, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (*rows.shape, H, 3), rows)
+    check(load().flk_flicker_lines_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain) if gain is not None else None,
+                                       ptr(out), stream_ptr()))
+    return out
+
+
+def flicker_lines_mix_grad(g_lines, rows, period, taps, gain=None, out=None, rows_host=None, scratch=None):
+    """the transpose of ``flicker_lines_mix`` (flk_flicker_lines_mix_grad, two launches): the per-line gradient fp32 ``rows.shape + (H,3)``
+    (``perturb_grad_reduce`` of per-line arguments) folded onto the rows of the shared perturbation through the same tables -> fp32
+    [period,3].  One fixed order (per frame and tap the lines ascending from +0; then frames ascending, taps ascending, from +0), no
+    atomics.  ``scratch``: fp32 with at least ``rows.numel() * K * 3`` elements on the device (allocated when None)."""
+    what = "flicker_lines_mix_grad"
+    _check_rows(what, rows, period, rows_host)
+    _, clip_T, H, K = _check_lines(what, rows, taps, gain)
+    _check_f32(what, "g_lines", g_lines, (*rows.shape, H, 3), rows)
+    P = int(period)
+    if out is None:
+        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
+    _check_f32(what, "out", out, (P, 3), rows)
+    need = rows.numel() * K * 3
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=rows.device)
+    if not (torch.is_tensor(scratch) and scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.device == rows.device and scratch.numel() >= need):
+        raise ValueError(f"{what}: scratch must be a contiguous fp32 tensor of at least {need} elements on {rows.device}")
+    check(load().flk_flicker_lines_mix_grad(ptr(g_lines), ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain) if gain is not None else None,
+                                            P, ptr(scratch), ptr(out), stream_ptr()))
     return out
 
 

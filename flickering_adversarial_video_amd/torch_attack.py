@@ -70,7 +70,10 @@ class Perturbation:
 
     ``capture`` (video time only; a videoresnet_spec.CaptureChannel): the distribution ``delta_clip(capture="draw")`` draws one capture
     channel per video from -- the per-clip perturbation is then the mix of rows a camera records (ops.flicker_rows_mix) instead of the
-    gathered rows; the channels last used, with their tables, are kept on ``last_capture``."""
+    gathered rows; the channels last used, with their tables, are kept on ``last_capture``.  A channel with a ``readout`` (a rolling
+    shutter; a drawn or given dict then holds a ``"readout"``) gives every LINE of a frame its own mix: ``delta_clip`` returns
+    ``[B,clip_T,H,3]`` (ops.flicker_lines_mix, tables from ``CaptureChannel.line_tables`` at the clips' height) and the apply / export
+    arguments name it per line (flk_apply_args.delta_per_line)."""
 
     def __init__(self, size, requires_grad=True, device="cuda", max_value=None, min_value=None, max_norm=1.0, cyclic_pert=False, batch=None,
                  clip_length=None, clips_per_video=1, capture=None):
@@ -92,6 +95,7 @@ class Perturbation:
         self.frame_numbers = None        # video time: int64 [B,clip_T] of the current batch, None = arange(clip_T) for every clip
         self.last_phases = None          # video time: the phases (one per video) of the last adversarial apply
         self.rows_host = self.rows_dev = self._delta_clip = None      # the rows table last uploaded, its device copy, the gathered perturbation
+        self._delta_lines = None         # rolling shutter: the per-line perturbation [B,clip_T,H,3] (reused like _delta_clip)
         # batch = B (flickering only): B INDEPENDENT perturbations [B,T,3], one per clip of the batch, each with its own clamp bound
         # (``dyn_max_norm_dev`` [B]) -- single-video attacks advancing together (fit_many_videos, model.py:791-982)
         self.batch = batch
@@ -158,24 +162,36 @@ class Perturbation:
             table = np.ascontiguousarray(table, dtype=np.int64)
         self.frame_numbers = table
 
-    def _capture_tables(self, B, capture):
+    @staticmethod
+    def _is_channel_dict(capture):
+        return isinstance(capture, dict) and set(capture) - {"readout"} == {"subframe", "exposure", "gain"}
+
+    def _capture_tables(self, B, capture, H=None):
         """the channel tables of a batch of B clips on the device (``taps_dev`` [B,K], ``gain_dev`` [B,3]), uploaded only when they differ
         from those already there.  ``capture``: "draw" -- one channel per video from ``self.capture`` -- or a dict ``subframe``,
-        ``exposure``, ``gain`` holding one channel per video ([V], [V], [V,3]), one per clip ([B], ...) or one for all (scalars, ``gain`` [3])"""
+        ``exposure``, ``gain`` holding one channel per video ([V], [V], [V,3]), one per clip ([B], ...) or one for all (scalars, ``gain`` [3]).
+        A dict that also holds ``readout`` (a rolling shutter) gives per-line tables for frames of ``H`` lines, ``taps_dev`` [B,H,K]; returns
+        whether it did."""
         G = self.clips_per_video
         V = -(-B // G)
         if isinstance(capture, str):
             if capture != "draw" or self.capture is None:
                 raise ValueError(f"capture must be a channel dict, None or -- on a perturbation built with capture=CaptureChannel(...) -- 'draw', got {capture!r}")
             capture = self.capture.draw(V)
-        if not isinstance(capture, dict) or set(capture) != {"subframe", "exposure", "gain"}:
-            raise ValueError(f"capture must be a dict with the keys subframe, exposure and gain, got {capture!r}")
+        if not self._is_channel_dict(capture):
+            raise ValueError(f"capture must be a dict with the keys subframe, exposure and gain (and, for a rolling shutter, readout), got {capture!r}")
+        lines = "readout" in capture
+        if lines and (isinstance(H, bool) or not isinstance(H, (int, np.integer)) or H < 1):
+            raise ValueError(f"capture with a readout: the height of the clips must be known, got {H!r}")
         if np.ndim(capture["subframe"]) == 0:                          # one channel for every video of the batch
-            capture = {"subframe": np.full(V, float(capture["subframe"])), "exposure": np.full(V, float(capture["exposure"])),
-                       "gain": np.broadcast_to(np.asarray(capture["gain"], np.float32).reshape(-1, 3)[:1], (V, 3)).copy()}
+            one = capture
+            capture = {"subframe": np.full(V, float(one["subframe"])), "exposure": np.full(V, float(one["exposure"])),
+                       "gain": np.broadcast_to(np.asarray(one["gain"], np.float32).reshape(-1, 3)[:1], (V, 3)).copy()}
+            if lines:
+                capture["readout"] = np.full(V, float(one["readout"]))
         if G > 1 and np.shape(capture["subframe"]) == (B,):              # one channel per CLIP (evaluate_videos packs clips, not videos)
             G, V = 1, B
-        taps, gain = CaptureChannel.tables(capture, G)
+        taps, gain = CaptureChannel.line_tables(capture, G, int(H)) if lines else CaptureChannel.tables(capture, G)
         if taps.shape[0] != V * G:
             raise ValueError(f"{taps.shape[0] // G} capture channels for {B} clips of {G} per video: one per video, or one for all")
         taps, gain = np.ascontiguousarray(taps[:B]), np.ascontiguousarray(gain[:B])
@@ -188,13 +204,15 @@ class Perturbation:
             if not np.array_equal(gain, last["gain_rows"]):
                 self.gain_dev.copy_(torch.from_numpy(gain))
         self.last_capture = {**capture, "taps": taps, "gain_rows": gain}
+        return lines
 
-    def delta_clip(self, B, phases="draw", capture=None):
+    def delta_clip(self, B, phases="draw", capture=None, H=None):
         """video time: the per-clip perturbation [B,clip_T,3] of the current frame numbers (a buffer reused from call to call, valid
         until the next one).  ``phases``: "draw" = one per video from the generator when ``cyclic_pert`` (else 0), or an integer / one
         integer per video; None: the buffer as it is, nothing gathered (a clean apply reads no perturbation).  The table goes to the
         device only when it differs from the one already there.  ``capture``: None -- the rows themselves (ops.flicker_rows_gather) --
-        or the capture channels the frames are recorded through (``_capture_tables``: "draw" or a dict): ops.flicker_rows_mix."""
+        or the capture channels the frames are recorded through (``_capture_tables``: "draw" or a dict): ops.flicker_rows_mix -- or, for
+        channels with a readout (a rolling shutter) and clips of ``H`` lines, ops.flicker_lines_mix: the result is then ``[B,clip_T,H,3]``."""
         if self.frame_numbers is not None and self.frame_numbers.shape[0] != B:
             raise ValueError(f"{B} clips, but the frame numbers set are for {self.frame_numbers.shape[0]} (set_frame_numbers)")
         if self._delta_clip is None or self._delta_clip.shape[0] != B:
@@ -222,8 +240,11 @@ class Perturbation:
             self.rows_host = rows
         if capture is None:
             return ops.flicker_rows_gather(self.perturbation, self.rows_dev, out=self._delta_clip)
-        self._capture_tables(B, capture)
-        return ops.flicker_rows_mix(self.perturbation, self.rows_dev, self.taps_dev, self.gain_dev, out=self._delta_clip)
+        if not self._capture_tables(B, capture, H):
+            return ops.flicker_rows_mix(self.perturbation, self.rows_dev, self.taps_dev, self.gain_dev, out=self._delta_clip)
+        if self._delta_lines is None or tuple(self._delta_lines.shape) != (B, self.clip_T, int(H), 3):
+            self._delta_lines = torch.zeros((B, self.clip_T, int(H), 3), dtype=torch.float32, device=self.perturbation.device)
+        return ops.flicker_lines_mix(self.perturbation, self.rows_dev, self.taps_dev, self.gain_dev, out=self._delta_lines)
 
     def _no_capture_on_clip_time(self, capture):
         if capture is not None and not self.video_time:
@@ -238,7 +259,7 @@ class Perturbation:
         self._no_capture_on_clip_time(capture)
         if self.video_time:
             # the roll is in the rows; a clean apply reads no perturbation (adv_flag 0), so it gathers nothing and keeps the table
-            delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None, capture), 0
+            delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None, capture, int(x.shape[2])), 0
         else:
             shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
         inf = float("inf")
@@ -248,7 +269,8 @@ class Perturbation:
                                    lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf, fold_t=fold_t,
                                    dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
                                    x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None,
-                                   quantise="torch" if quantise else None, q_lut=decode_table(x.device) if quantise else None)
+                                   quantise="torch" if quantise else None, q_lut=decode_table(x.device) if quantise else None,
+                                   per_line=self.video_time and delta.dim() == 4)      # (video time has no dense delta: 4-D = per line)
 
     def export_args(self, x, adversarial=True, shift_p=0, delta_T=0, capture=None):
         """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
@@ -261,24 +283,29 @@ class Perturbation:
         delta = self.perturbation
         self._no_capture_on_clip_time(capture)
         if self.video_time and not delta_T:
-            delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None, capture), 0
+            delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None, capture, int(x.shape[2])), 0
         elif capture is not None and adversarial:
-            delta = self.captured_perturbation(capture)
+            delta = self.captured_perturbation(capture, int(x.shape[2]))
         return ops.make_export_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
                                           shift_p=shift_p, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
                                           lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf,
                                           dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
-                                          x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None, delta_T=delta_T)
+                                          x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None, delta_T=delta_T,
+                                          per_line=self.video_time and delta.dim() - (0 if delta_T else 1) == 3)
 
-    def captured_perturbation(self, capture):
+    def captured_perturbation(self, capture, H=None):
         """video time: the shared perturbation as ONE capture channel records it, fp32 [P,3] -- one ops.flicker_rows_mix launch over
         ``rows = arange(P)`` as one clip of P frames: row r of the result is what a frame that carries row r records.  ``capture``: a dict
-        ``subframe``, ``exposure`` (scalars) and ``gain`` [3].  Nothing of the batch's own tables is touched."""
-        if not isinstance(capture, dict) or set(capture) != {"subframe", "exposure", "gain"} or np.ndim(capture["subframe"]) != 0:
+        ``subframe``, ``exposure`` (scalars) and ``gain`` [3].  Nothing of the batch's own tables is touched.  A channel that also holds a
+        scalar ``readout`` (a rolling shutter) is recorded per line of a frame of ``H`` lines: fp32 [P,H,3], ops.flicker_lines_mix."""
+        if not self._is_channel_dict(capture) or np.ndim(capture["subframe"]) != 0:
             raise ValueError(f"capture must be ONE channel: a dict of the scalars subframe and exposure and gain [3], got {capture!r}")
-        taps, gain = CaptureChannel.tables(capture, 1)
         dev = self.perturbation.device
         rows = torch.arange(self.T, dtype=torch.int32, device=dev)
+        if "readout" in capture:
+            taps, gain = CaptureChannel.line_tables(capture, 1, H)
+            return ops.flicker_lines_mix(self.perturbation, rows, torch.from_numpy(taps).to(dev), torch.from_numpy(gain).to(dev))
+        taps, gain = CaptureChannel.tables(capture, 1)
         return ops.flicker_rows_mix(self.perturbation, rows, torch.from_numpy(taps).to(dev), torch.from_numpy(gain).to(dev))
 
     def export_u8(self, x, adversarial=True, stats=False, out=None, out_offset=0, shift_p=0, capture=None):
@@ -469,7 +496,9 @@ class FlickerVideoResNet:
         # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
         # of rows a camera records (ops.flicker_rows_mix in the gather's place); the step folds its gradient through the same tables
         # (ops.flicker_rows_mix_grad).  Evaluation and export (``logits``, ``adversarial_frames``, ``quantised_logits``, ``export_video``,
-        # ``evaluate_videos``) go through a channel only when they are given one: their default is none
+        # ``evaluate_videos``) go through a channel only when they are given one: their default is none.  A channel with a ``readout`` is a
+        # rolling shutter: every LINE of a frame gets its own mix (ops.flicker_lines_mix, the per-line apply and gradient,
+        # ops.flicker_lines_mix_grad back to the same [P,3] payload); everything else is as for a channel without one
         self.capture = capture
         # quantise_train: the attack is optimised on the STORED video.  Every adversarial forward (``step`` in all its variants,
         # ``logits(x, True)``) applies decode(encode_u8(x_adv)) -- the 8-bit round trip inside the apply kernel, straight-through gradient --
@@ -592,7 +621,8 @@ class FlickerVideoResNet:
     @property
     def last_capture(self):
         """the capture channels, one per video of the batch, of the last adversarial forward that went through one: ``subframe`` [V],
-        ``exposure`` [V], ``gain`` [V,3] and the tables made from them, one row per clip: ``taps`` fp32 [B,K], ``gain_rows`` fp32 [B,3]"""
+        ``exposure`` [V], ``gain`` [V,3] and the tables made from them, one row per clip: ``taps`` fp32 [B,K], ``gain_rows`` fp32 [B,3]; a
+        channel with a readout (rolling shutter) adds ``readout`` [V], and ``taps`` is then per line, fp32 [B,H,K]"""
         return self.pert_model.last_capture
 
     @staticmethod
@@ -763,15 +793,15 @@ class FlickerVideoResNet:
                 n = min(B, V * S - first)
                 self.pert_model.set_frame_numbers(rows[ks])
                 if quantise == "video":
-                    exp = {v: self.export_video(videos[v], capture={"subframe": float(d["subframe"][v]), "exposure": float(d["exposure"][v]),
-                                                                    "gain": d["gain"][v]}) for v in sorted(set(vs_.tolist()))}
+                    exp = {v: self.export_video(videos[v], capture={k: (d[k][v] if k == "gain" else float(d[k][v])) for k in d})
+                           for v in sorted(set(vs_.tolist()))}
                     ops.prepare_clips([exp[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
                                       rule=self.resize_rule, frame_idx=rows[ks])
                     parts.append(self.logits(x, False)[:n].cpu())
                     continue
                 ops.prepare_clips([videos[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
                                   rule=self.resize_rule, frame_idx=rows[ks])
-                per_clip = {"subframe": d["subframe"][vs_], "exposure": d["exposure"][vs_], "gain": d["gain"][vs_]}      # one channel per clip
+                per_clip = {k: d[k][vs_] for k in d}                     # one channel per clip (with its readout, if the channel has one)
                 if quantise == "clip":
                     parts.append(self.logits(self.adversarial_frames(x, capture=per_clip), False)[:n].cpu())
                 else:
@@ -932,7 +962,17 @@ class FlickerVideoResNet:
             criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
         self.net.backward(self._dl, self._gx)
         n = 3 * self.P                                          # (clip time: P == T)
-        if self.video_time:
+        if self.video_time and a.delta_per_line:
+            # rolling shutter: the per-line gradient [B,T,H,3] (summed over w only; adv_flag, 1/std and the clamp mask applied per line),
+            # then the transpose of the lines mix the forward ran, on the same tables, to the same [P,3] payload
+            if getattr(self, "_g_lines", None) is None:
+                dev = self._logits.device
+                self._g_lines = torch.zeros((self.B, self.T, self.H, 3), dtype=torch.float32, device=dev)
+                self._lines_scratch = torch.empty(self.B * self.T * ops.FLICKER_LINES_MAX_TAPS * 3, dtype=torch.float32, device=dev)
+            ops.perturb_grad_reduce(a, self._gx, self._g_lines, self._scratch)
+            ops.flicker_lines_mix_grad(self._g_lines, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
+                                       out=red[:n].view(self.P, 3), scratch=self._lines_scratch)
+        elif self.video_time:
             # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame), then its frames folded onto their rows
             ops.perturb_grad_reduce(a, self._gx, self._g_clip, self._scratch)
             if cap is None:

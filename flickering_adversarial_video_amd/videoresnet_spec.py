@@ -425,6 +425,39 @@ def capture_taps(subframe, exposure):
     return w.astype(np.float32)
 
 
+def capture_line_taps(subframe, exposure, readout, H):
+    """``capture_taps`` per LINE of a rolling-shutter frame of ``H`` lines: line h starts its exposure ``(readout * h) / H`` emitter rows
+    after line 0 (``readout`` rho in [0,1]: the time from the start of line 0 to the start of a line one frame height further down), so it
+    integrates the emitter over ``[n + psi_h, n + psi_h + e)`` with ``psi_h = subframe + (readout * h) / H`` -- float64, in exactly that
+    order, in [0,2) -- and its taps follow ``capture_taps``' rule with psi_h in phi's place: ``w_k(h) = |[psi_h, psi_h + e) n [k, k + 1)| / e``.
+    fp32 ``[H,K]``, ``K = max(1, ceil(max_h psi_h + e))`` <= 5, computed in float64 for all lines at once and rounded once; a line with
+    psi_h < 1 holds the bits of ``capture_taps(psi_h, e)``, zero-padded.  ``exposure`` 0: an instantaneous sample, tap ``floor(psi_h)`` is 1
+    (``K = floor(max_h psi_h) + 1``: the same number except where max psi_h is exactly 1).  Arguments as ``capture_taps``; ``readout``
+    outside [0,1] or non-finite, or ``H < 1``, is a ValueError."""
+    try:
+        phi, e, rho = float(subframe), float(exposure), float(readout)
+    except (TypeError, ValueError):
+        raise ValueError(f"capture_line_taps: subframe, exposure and readout must be numbers, got {subframe!r}, {exposure!r} and {readout!r}") from None
+    if not (np.isfinite(phi) and 0.0 <= phi < 1.0):
+        raise ValueError(f"capture_line_taps: the sub-frame phase must lie in [0,1), got {subframe!r}")
+    if not (np.isfinite(e) and 0.0 <= e <= CAPTURE_MAX_EXPOSURE):
+        raise ValueError(f"capture_line_taps: the exposure must lie in [0,{CAPTURE_MAX_EXPOSURE:g}] emitter rows, got {exposure!r}")
+    if not (np.isfinite(rho) and 0.0 <= rho <= 1.0):
+        raise ValueError(f"capture_line_taps: the readout must lie in [0,1] emitter rows per frame height, got {readout!r}")
+    if isinstance(H, bool) or not isinstance(H, (int, np.integer)) or H < 1:
+        raise ValueError(f"capture_line_taps: the number of lines H must be an integer >= 1, got {H!r}")
+    psi = phi + (rho * np.arange(int(H), dtype=np.float64)) / np.float64(int(H))
+    if e == 0.0:
+        at = np.floor(psi).astype(np.int64)
+        w = np.zeros((int(H), int(at.max()) + 1), np.float32)
+        w[np.arange(int(H)), at] = 1.0
+        return w
+    K = max(1, int(np.ceil(psi.max() + e)))
+    k = np.arange(K, dtype=np.float64)[None, :]
+    w = np.maximum(0.0, np.minimum((psi + e)[:, None], k + 1.0) - np.maximum(psi[:, None], k)) / e
+    return w.astype(np.float32)
+
+
 def _mix_tables(what, rows, clip_T, taps, gain):
     rows = np.asarray(rows)
     if rows.dtype.kind not in "iu" or rows.size < 1:
@@ -490,6 +523,75 @@ def flicker_rows_mix_grad(g_clip, rows, clip_T, taps, gain, period):
     return out
 
 
+def _lines_tables(what, rows, clip_T, taps, gain):
+    rows = np.asarray(rows)
+    if rows.dtype.kind not in "iu" or rows.size < 1:
+        raise ValueError(f"{what}: rows must be a non-empty integer table, got {rows.shape} {rows.dtype}")
+    if isinstance(clip_T, bool) or not isinstance(clip_T, (int, np.integer)) or clip_T < 1 or rows.size % clip_T:
+        raise ValueError(f"{what}: clip_T must be an integer >= 1 that divides the {rows.size} frames, got {clip_T!r}")
+    nb = rows.size // int(clip_T)
+    taps = np.asarray(taps)
+    if taps.dtype != np.float32 or taps.ndim != 3 or taps.shape[0] != nb or taps.shape[1] < 1 or not 1 <= taps.shape[2] <= 5:
+        raise ValueError(f"{what}: taps must be float32 [{nb},H,K] with K in 1..5 (one table per clip), got {taps.shape} {taps.dtype}")
+    if gain is not None:
+        gain = np.asarray(gain)
+        if gain.dtype != np.float32 or gain.shape != (nb, 3):
+            raise ValueError(f"{what}: gain must be float32 [{nb},3] (one row per clip) or None, got {gain.shape} {gain.dtype}")
+    return rows, nb, taps, gain
+
+
+def flicker_lines_mix(delta, rows, clip_T, taps, gain=None):
+    """``flk_flicker_lines_mix`` restated in numpy float32, operation for operation: ``delta`` fp32 ``[P,3]``, ``rows`` integers of any shape
+    (frame i of the flattened table belongs to clip ``i // clip_T``), ``taps`` fp32 ``[clips,H,K]``, ``gain`` fp32 ``[clips,3]`` or None ->
+    fp32 ``rows.shape + (H,3)``.  Per line h the arithmetic of ``flicker_rows_mix`` with the line's taps: ``acc = taps[b,h,0] * delta[r0]``
+    (the first product itself), then ``acc = acc + taps[b,h,k] * delta[(r0 + k) mod P]``, then ``gain[b] * acc`` -- each rounded on its own."""
+    what = "flicker_lines_mix"
+    delta = np.asarray(delta)
+    if delta.dtype != np.float32 or delta.ndim != 2 or delta.shape[1] != 3 or delta.shape[0] < 1:
+        raise ValueError(f"{what}: delta must be float32 [P,3], got {delta.shape} {delta.dtype}")
+    rows, nb, taps, gain = _lines_tables(what, rows, clip_T, taps, gain)
+    P, H = delta.shape[0], taps.shape[1]
+    r0 = np.clip(rows.reshape(-1).astype(np.int64), 0, P - 1)
+    b = np.arange(r0.shape[0]) // int(clip_T)
+    acc = taps[b, :, 0][:, :, None] * delta[r0][:, None, :]                                            # [n,H,3]
+    for k in range(1, taps.shape[2]):
+        acc = acc + taps[b, :, k][:, :, None] * delta[(r0 + k) % P][:, None, :]
+    if gain is not None:
+        acc = gain[b][:, None, :] * acc
+    assert acc.dtype == np.float32
+    return np.ascontiguousarray(acc.reshape(rows.shape + (H, 3)))
+
+
+def flicker_lines_mix_grad(g_lines, rows, clip_T, taps, gain, period):
+    """``flk_flicker_lines_mix_grad`` restated in numpy float32, the transpose of ``flicker_lines_mix`` in the kernels' two stages:
+    ``g_lines`` fp32 ``rows.shape + (H,3)`` -> fp32 ``[period,3]``.  Stage 1: ``s[i,k] = sum over the lines h ascending, from +0, of
+    (gain[b] * taps[b,h,k]) * g_lines[i,h]`` (without a gain: ``taps[b,h,k] * g_lines[i,h]``).  Stage 2: from +0, over the frames i
+    ascending and within a frame the taps k ascending, ``g_rows[(rows[i] + k) mod P] += s[i,k]``; frames whose row lies outside [0,P)
+    are skipped, a row nothing reaches stays +0, ``period < K`` is legal.  Every product and sum rounded on its own."""
+    what = "flicker_lines_mix_grad"
+    rows, nb, taps, gain = _lines_tables(what, rows, clip_T, taps, gain)
+    if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or period < 1:
+        raise ValueError(f"{what}: period must be an integer >= 1, got {period!r}")
+    H, K = taps.shape[1], taps.shape[2]
+    g = np.asarray(g_lines)
+    if g.dtype != np.float32 or g.shape != rows.shape + (H, 3):
+        raise ValueError(f"{what}: g_lines must be float32 {rows.shape + (H, 3)}, got {g.shape} {g.dtype}")
+    P = int(period)
+    g, r = g.reshape(-1, H, 3), rows.reshape(-1).astype(np.int64)
+    b = np.arange(r.shape[0]) // int(clip_T)
+    s = np.zeros((r.shape[0], K, 3), np.float32)
+    for h in range(H):
+        coef = taps[b, h][:, :, None] if gain is None else gain[b][:, None, :] * taps[b, h][:, :, None]      # [n,K,1 or 3]
+        s = s + coef * g[:, h][:, None, :]
+    assert s.dtype == np.float32
+    target = (r[:, None] + np.arange(K)) % P
+    out = np.zeros((P, 3), np.float32)
+    for i in np.flatnonzero((r >= 0) & (r < P)):
+        for k in range(K):
+            out[target[i, k]] = out[target[i, k]] + s[i, k]
+    return out
+
+
 def _capture_range(name, v, lo_bound, hi_bound):
     pair = (v, v) if np.ndim(v) == 0 else tuple(v)
     if len(pair) != 2:
@@ -510,10 +612,17 @@ class CaptureChannel:
 
     ``draw(V)``: V channels from the instance's ONE generator ``numpy.random.default_rng(seed)``, in this order: the V subframes, then
     the V exposures, then the gains (V values, or V x 3 in row-major order; none for three fixed gains) -- each a ``Generator.uniform``
-    call, made whether or not the bounds are equal, so that fixing a range does not shift the other draws."""
+    call, made whether or not the bounds are equal, so that fixing a range does not shift the other draws.
 
-    def __init__(self, subframe=(0.0, 1.0), exposure=(1.0, 1.0), gain=(1.0, 1.0), gain_mode="common", seed=0):
+    ``readout`` (None, a number or a ``(lo, hi)`` range within [0,1]): a ROLLING shutter -- the time, in emitter rows, from the start of
+    line 0 to the start of a line one frame height further down (``capture_line_taps``).  With a readout ``draw(V)`` draws the V readouts
+    AFTER the gains (every earlier value of a seed is unchanged) and returns them under ``"readout"``; ``line_tables`` makes the per-line
+    tables.  None: a global shutter -- the same calls and the same three keys as ever."""
+
+    def __init__(self, subframe=(0.0, 1.0), exposure=(1.0, 1.0), gain=(1.0, 1.0), gain_mode="common", seed=0, readout=None):
         self.subframe = _capture_range("subframe", subframe, 0.0, 1.0)
+        # rolling shutter: None -- a global shutter, nothing below changes -- or the range of the readout time (capture_line_taps)
+        self.readout = None if readout is None else _capture_range("readout", readout, 0.0, 1.0)
         self.exposure = _capture_range("exposure", exposure, 0.0, CAPTURE_MAX_EXPOSURE)
         fmax = float(np.finfo(np.float32).max)
         self.gain_rgb = None                                           # three fixed gains (per_channel only): nothing is drawn for them
@@ -546,7 +655,33 @@ class CaptureChannel:
             gain = np.repeat(self._rng.uniform(*self.gain, size=V)[:, None], 3, axis=1)
         else:
             gain = self._rng.uniform(*self.gain, size=(V, 3))
-        return {"subframe": sub, "exposure": exp, "gain": np.ascontiguousarray(gain, dtype=np.float32)}
+        out = {"subframe": sub, "exposure": exp, "gain": np.ascontiguousarray(gain, dtype=np.float32)}
+        if self.readout is not None:
+            out["readout"] = np.clip(self._rng.uniform(*self.readout, size=V), *self.readout)
+        return out
+
+    @staticmethod
+    def line_tables(draw, G, H):
+        """the tables ``flicker_lines_mix`` takes for a ``draw`` with a ``"readout"`` (one channel may give scalars and ``gain [3]``), for frames
+        of ``H`` lines: fp32 ``taps [V * G, H, Kmax]`` -- every video's ``capture_line_taps`` padded with zeros to the longest -- and fp32
+        ``gain [V * G, 3]``.  The ``G`` clips of a video share their video's channel."""
+        if not isinstance(draw, dict) or set(draw) != {"subframe", "exposure", "gain", "readout"}:
+            raise ValueError(f"CaptureChannel.line_tables: a dict with the keys subframe, exposure, gain and readout, got {draw!r}")
+        if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or G < 1:
+            raise ValueError(f"CaptureChannel.line_tables: clips per video must be an integer >= 1, got {G!r}")
+        sub, exp = np.atleast_1d(np.asarray(draw["subframe"], np.float64)), np.atleast_1d(np.asarray(draw["exposure"], np.float64))
+        ro = np.atleast_1d(np.asarray(draw["readout"], np.float64))
+        gain = np.asarray(draw["gain"], np.float32)
+        gain = gain[None] if gain.ndim == 1 else gain
+        V = sub.shape[0]
+        if sub.ndim != 1 or exp.shape != (V,) or ro.shape != (V,) or gain.shape != (V, 3) or not np.isfinite(gain).all():
+            raise ValueError(f"CaptureChannel.line_tables: subframe [V], exposure [V], readout [V] and finite gain [V,3], got {sub.shape}, {exp.shape}, "
+                             f"{ro.shape}, {gain.shape}")
+        per_video = [capture_line_taps(s, e, r, H) for s, e, r in zip(sub, exp, ro)]
+        taps = np.zeros((V, int(H), max(w.shape[1] for w in per_video)), np.float32)
+        for v, w in enumerate(per_video):
+            taps[v, :, :w.shape[1]] = w
+        return np.repeat(taps, int(G), axis=0), np.ascontiguousarray(np.repeat(gain, int(G), axis=0))
 
     @staticmethod
     def tables(draw, G=1):
@@ -643,6 +778,9 @@ def add_capture_arguments(ap):
                     "within [0, 3] (0: an instantaneous sample): a frame records the mix of the 1..4 rows its exposure window covers")
     ap.add_argument("--capture-gain", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="the gain the captured flicker is scaled by "
                     "(emitter colour response, white balance, ambient dilution), >= 0")
+    ap.add_argument("--capture-readout", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="a rolling-shutter camera: the time from the "
+                    "start of line 0 to the start of a line one frame height further down, in emitter rows, drawn uniformly from [LO, HI] within "
+                    "[0, 1] per video and step -- every line of a frame then records its own mix of rows (default: absent, a global shutter)")
     ap.add_argument("--capture-gain-mode", default=None, choices=list(CAPTURE_GAIN_MODES), help="one gain for the three colour channels (common, "
                     "the default) or one each (per_channel)")
     ap.add_argument("--capture-seed", type=int, default=None, help="the channels are drawn from numpy.random.default_rng(seed) (default 0)")
@@ -655,6 +793,7 @@ def capture_from_arguments(ap, a):
     """the CaptureChannel the ``--capture-*`` options of ``add_capture_arguments`` describe, or None when none of them is given.  Any of them
     without ``--flicker-time video`` is an argparse error, and so are values a channel cannot take"""
     given = [o for o, v in (("--capture-subframe", a.capture_subframe), ("--capture-exposure", a.capture_exposure), ("--capture-gain", a.capture_gain),
+                            ("--capture-readout", a.capture_readout),
                             ("--capture-gain-mode", a.capture_gain_mode), ("--capture-seed", a.capture_seed),
                             ("--eval-capture-draws", a.eval_capture_draws or None)) if v is not None]
     if not given:
@@ -665,6 +804,7 @@ def capture_from_arguments(ap, a):
         ap.error(f"--eval-capture-draws must be >= 0, got {a.eval_capture_draws}")
     try:
         return CaptureChannel(subframe=tuple(a.capture_subframe or (0.0, 0.0)), exposure=tuple(a.capture_exposure or (1.0, 1.0)),
-                              gain=tuple(a.capture_gain or (1.0, 1.0)), gain_mode=a.capture_gain_mode or "common", seed=a.capture_seed or 0)
+                              gain=tuple(a.capture_gain or (1.0, 1.0)), gain_mode=a.capture_gain_mode or "common", seed=a.capture_seed or 0,
+                              readout=None if a.capture_readout is None else tuple(a.capture_readout))
     except ValueError as e:
         ap.error(str(e))

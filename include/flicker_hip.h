@@ -216,7 +216,7 @@ int flk_maxpool3d_bwd_conv1x1(const flk_pool_args* a, const void* g, int g_ld, i
  * kinetics_i3d_utils.py:100-142:  x_adv = clip(x + a * clip(delta[t,c], +-dclip), lo, hi)
  * model.py:80-101 (torch dialect): same with delta/std[c] and scalar clamp bounds.
  * x: uint8 (x = u8*x_scale + x_bias, the TFRecord path pre_process_rgb_flow.py:226-234, or x = x_lut[u8][c]) or fp32,
- *    [B,T,H,W,3]; delta: fp32 [T,3] (flicker) or [T,H,W,3] (dense, "L12" baseline).
+ *    [B,T,H,W,3]; delta: fp32 [T,3] (flicker), [T,H,W,3] (dense, "L12" baseline) or [Bd,T,H,3] (per line: delta_per_line).
  * out: [B,T/2,H/2,W/2,32] of dtype: channel (qt*4+qh*2+qw)*3+c, channels 24..31 zero -- the
  * 7x7x7/2 stem (i3d.py:169) then runs as a 4x4x4/1 convolution on MFMA.  T,H,W must be even.
  * Pointer contract (flk_perturb_apply_s2d and flk_perturb_grad_reduce; FLK_EINVAL naming the alignment, before any GPU call): a uint8
@@ -250,6 +250,20 @@ typedef struct {
   int delta_per_clip;        /* 1 (flicker delta only): delta is [B,T,3] and clip b is perturbed by ITS OWN delta[b] -- B independent
                                 single-video attacks (i3d_adversarial_main_single_video_npy.py:103-337, model.py:791-982) advancing in
                                 one batch; the delta-gradient then comes back per clip, [B,T,3].  0: one delta [T,3] shared by the batch */
+  int delta_per_line;        /* 1 (VideoResNet layouts, fold_t 1 and 4, and flk_adv_export_u8): the perturbation has one value PER LINE of a frame --
+                                delta is fp32 [Bd,T,H,3], Bd = B with delta_per_clip, else 1 -- what a rolling-shutter camera records of a
+                                flickering emitter (flk_flicker_lines_mix makes it).  The value added at (b,t,h,w,c) is that of
+                                (b or 0, (t - shift_p) mod T, h, c), through the same clamp (dclip / dclip_dev) and 1/std as any other value.
+                                flk_adv_export_u8 with delta_T = P (Bd = 1): delta is [P,H,3], frame t takes row (t - shift_p) mod P.
+                                flk_perturb_grad_reduce (with delta_per_clip only): gdelta comes back fp32 [B,T,H,3], entry (b,ts,h,c) the
+                                masked sum of the input gradient over w ONLY (one wave per (b, t, row pair), lanes stride over W/2, sums
+                                added per lane in ascending w, then the 64 lanes folded by a fixed shuffle tree: no atomics, one fixed
+                                order; `partials` is not used), times adv_flag * inv_std[c], zero where that delta value lies outside its clamp.
+                                FLK_EINVAL before any GPU call: with delta_dense or center = 1; fold_t 0, 2, 3; the gradient without
+                                delta_per_clip; delta_T with delta_per_clip; every I3D-only entry point (flk_stem_fwd_u8, flk_stem_delta_grad*,
+                                flk_stem_delta_bias, flk_net_backward_delta).  0: today's behaviour, bit for bit.  (The field fills the four
+                                bytes of padding behind delta_per_clip: no other field moves, the struct keeps its size, and a
+                                zero-initialised struct keeps its meaning) */
   const float* dclip_dev;    /* delta_per_clip only, or NULL: per-clip clamp bounds [B] on the device replacing `dclip` -- the torch loop grows a
                                 video's bound by 1.3 when it restarts (model.py:1061-1066), independently per video */
   const float* q_lut;        /* NULL = off.  Quantised apply (8-bit straight-through): fp32 [256][3] on the device, byte v of channel c decodes
@@ -350,6 +364,32 @@ int flk_flicker_rows_mix(const float* delta, int P, const int32_t* rows, int n, 
                          float* delta_clip, void* stream);
 int flk_flicker_rows_mix_grad(const float* g_clip, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain, int P,
                               float* g_rows, void* stream);
+
+/* Rolling shutter: the capture channel per LINE of a frame.  Line h of a frame of H lines starts its exposure later than line 0, so it
+ * has taps of its own (videoresnet_spec.capture_line_taps: the rule of capture_taps with psi_h = phi + (rho * h) / H in phi's place,
+ * K = 1..5), and a frame that carries row r records on line h  gain[c] * sum_k w_k(h) * delta[(r + k) mod P][c]: horizontal bands.
+ * taps: DEVICE fp32 [n/clip_T][H][K], one table per clip (lines padded with 0 to a common K); gain: DEVICE fp32 [n/clip_T][3] or null.
+ *   flk_flicker_lines_mix:      out[i][h][c], fp32 [n][H][3] -- the per-line perturbation flk_apply_args.delta_per_line takes, RAW values.
+ *                               One thread per output value; the arithmetic of flk_flicker_rows_mix with the line's taps:
+ *                               r0 = clamp(rows[i], 0, P-1);  acc = taps[b][h][0] * delta[r0][c];
+ *                               for k = 1 .. K-1: acc = acc + taps[b][h][k] * delta[(r0 + k) mod P][c];   out = gain ? gain[b][c] * acc : acc.
+ *   flk_flicker_lines_mix_grad: the transpose, g_lines fp32 [n][H][3] -> g_rows fp32 [P][3], in two launches and ONE fixed order:
+ *                               stage 1  s[i][k][c] = the sum, from +0, over the lines h ASCENDING of
+ *                                        (gain ? gain[b][c] * taps[b][h][k] : taps[b][h][k]) * g_lines[i][h][c]      (one thread per (i,k,c));
+ *                               stage 2  g_rows[r][c] = the sum, from +0, over the frames i ASCENDING and within a frame the taps k ASCENDING
+ *                                        with (rows[i] + k) mod P == r, of s[i][k][c] -- the fold of flk_flicker_rows_mix_grad: P < K legal
+ *                                        (both taps added), entries of rows outside [0,P) skipped, a row nothing reaches written as 0;
+ *                                        one thread per output, rows staged in LDS in pieces.  No atomics.
+ *                               scratch: DEVICE fp32 [n][K][3] (s), the caller's.
+ * Every product and every sum is rounded to fp32 on its own (no fused multiply-add): videoresnet_spec.flicker_lines_mix and
+ * flicker_lines_mix_grad restate both on the host bit for bit.  With the same taps on every line the mix gives the bits of
+ * flk_flicker_rows_mix on every line.  No allocation, no synchronisation; the results do not depend on the launch geometry.
+ * FLK_EINVAL before any GPU call: a null delta / g_lines, rows, taps, scratch or output, n < 1, clip_T < 1 or n % clip_T != 0, H < 1,
+ * K outside 1..5, P outside 1..682. */
+int flk_flicker_lines_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K, const float* gain,
+                          float* out, void* stream);
+int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K, const float* gain,
+                               int P, float* scratch, float* g_rows, void* stream);
 
 /* Fused form of (stem data-gradient + flk_perturb_grad_reduce) for the flickering perturbation of I3D: d(loss)/d(delta[t,c]) straight
  * from G = d(loss)/d(pre-ReLU output of Conv3d_1a_7x7) (bf16 [B,T/2,H/2,W/2,g_ld], 64 channels) -- replaces Conv3DBackpropInputV2 of

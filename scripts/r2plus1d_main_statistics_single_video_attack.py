@@ -20,7 +20,8 @@ clips at the evaluation's uniform offsets are cut from each video once and the a
 (`--video-reduce sum`, or `mean` = sum / G: same argmax); a video counts as adversarial when the argmax of those logits leaves its label.
 `--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame carrying the row of
 its frame number in the video, which is what `--eval-quantised video` lays over the whole video; the result files hold `flicker_period`.
-`--capture-subframe / --capture-exposure / --capture-gain LO HI` (with `--capture-gain-mode`, `--capture-seed`; video time only) train the
+`--capture-subframe / --capture-exposure / --capture-gain / --capture-readout LO HI` (with `--capture-gain-mode`, `--capture-seed`; video
+time only; `--capture-readout`: a rolling shutter, every line of a frame records its own mix of rows) train the
 flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` scores the final flicker over N random
 captures (`capture_video_preds`, `capture_video_is_adversarial` [N], `capture_draws`)."""
 import argparse

@@ -44,7 +44,8 @@ same argmax, margin on the scale of one clip's logits).  Loss averages and fooli
 `--flicker-time video` (with `--flicker-period P`) trains the flicker on video time: a perturbation of P rows, every frame of every clip
 carrying the row of its frame number in its video -- what `--eval-quantised video` and `--save-adversarial-u8` lay over whole videos.
 The epoch results hold `flicker_period`.
-`--capture-subframe / --capture-exposure / --capture-gain LO HI` (with `--capture-gain-mode`, `--capture-seed`; video time only) train the
+`--capture-subframe / --capture-exposure / --capture-gain / --capture-readout LO HI` (with `--capture-gain-mode`, `--capture-seed`; video
+time only; `--capture-readout`: a rolling shutter, every line of a frame records its own mix of rows) train the
 flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` (whole-video files) scores the trained
 flicker over N random captures of the validation videos (`video_eval_capture.npz`)."""
 import argparse
@@ -211,7 +212,8 @@ def run_whole_videos(a, world, rank, local_rank, augment):
             ev.pop("realised_flicker", None)
             os.makedirs(dest, exist_ok=True)
             np.savez(os.path.join(dest, "video_eval_capture.npz"), num_samples=np.int64(S), capture_subframe=np.stack([d["subframe"] for d in draws]),
-                     capture_exposure=np.stack([d["exposure"] for d in draws]), capture_gain=np.stack([d["gain"] for d in draws]), **ev)
+                     capture_exposure=np.stack([d["exposure"] for d in draws]), capture_gain=np.stack([d["gain"] for d in draws]),
+                     **({"capture_readout": np.stack([d["readout"] for d in draws])} if "readout" in draws[0] else {}), **ev)
         if a.save_adversarial_u8:               # the validation videos under the universal flicker, whole and at their own resolution
             os.makedirs(dest, exist_ok=True)
             np.savez(os.path.join(dest, "adversarial_u8.npz"), labels=yva,
