@@ -63,6 +63,10 @@ class ExportArgs(C.Structure):
                 ("out_clip_offset", C.c_int64), ("out_clip_stride", C.c_int64)]
 
 
+class IllumArgs(C.Structure):
+    _fields_ = [("dec", C.c_void_p), ("enc", C.c_void_p), ("enc_n", C.c_int), ("out_mul", C.c_float * 3), ("out_add", C.c_float * 3)]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [("T", C.c_int), ("torch_dialect", C.c_int),
                 ("beta0", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("beta3", C.c_float),
@@ -131,6 +135,9 @@ _SIGS = {
                                         C.c_void_p]),
     "flk_flicker_lines_mix_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "flk_illum_apply_s2d": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(IllumArgs), C.c_void_p, C.c_int, C.c_void_p]),
+    "flk_illum_export_u8": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(IllumArgs), C.POINTER(ExportArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_illum_grad_reduce": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(IllumArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_sampled": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

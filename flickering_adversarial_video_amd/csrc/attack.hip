@@ -5,6 +5,7 @@
 // i3d_adversarial_main_single_video_npy.py:56-59,79-84 (loss, TF Adam); torch dialect model.py:80-101,
 // 198-209, 868.  Closed forms: SURVEY Appendix C.
 #include "flk_internal.h"
+#include "perturb_common.h"
 
 // Space-to-depth layouts (template FT = flk_apply_args.fold_t, 0 -> 2):
 //   FT = 1: fold (h,w) only,   16 channels: (qh*2+qw)*3 + c, 12..15 zero          (VideoResNet stems)
@@ -20,37 +21,6 @@ template <int FT> struct S2D {
     return FT == 3 ? (qt * 2 + qh) * 8 + k : (qt * 4 + qh * 2) * 3 + k;
   }
 };
-template <typename TO, int NCH> __device__ static inline void store_ch(char* dst, const float* v) {
-  if constexpr (sizeof(TO) == 4) {
-#pragma unroll
-    for (int i = 0; i < NCH / 4; ++i) ((float4*)dst)[i] = make_float4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < NCH / 8; ++i) {
-      bf16x8 o;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) o[e] = (bf16_t)v[8 * i + e];
-      ((bf16x8*)dst)[i] = o;
-    }
-  }
-}
-template <typename TI, int NUSED> __device__ static inline void load_ch(const char* src, float* v) {   // NUSED = 24 | 12
-  if constexpr (sizeof(TI) == 4) {
-#pragma unroll
-    for (int i = 0; i < NUSED / 4; ++i) { const float4 f = ((const float4*)src)[i]; v[4 * i] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w; }
-  } else {
-    float t[(NUSED + 7) / 8 * 8];
-#pragma unroll
-    for (int i = 0; i < (NUSED + 7) / 8; ++i) {
-      const uint4 u = ((const uint4*)src)[i];
-      const uint32_t w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { t[8 * i + 2 * k] = __uint_as_float(w[k] << 16); t[8 * i + 2 * k + 1] = __uint_as_float(w[k] & 0xffff0000u); }
-    }
-#pragma unroll
-    for (int i = 0; i < NUSED; ++i) v[i] = t[i];
-  }
-}
 
 // six consecutive values x[b,t,h,2*w2 .. 2*w2+1, 0..2]
 __device__ static inline void load6(const flk_apply_args& a, size_t off, float* x) {
@@ -72,7 +42,6 @@ __device__ static inline void load6(const flk_apply_args& a, size_t off, float* 
   }
 }
 
-__device__ static inline float clipf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 // value written for a pixel x with perturbation pv: the clipped sum, or (flk_apply_args.center) the sum minus pv -- i.e. x itself
 // wherever the clip is inactive
 __device__ static inline float applied(const flk_apply_args& a, float x, float pv) {
@@ -80,7 +49,6 @@ __device__ static inline float applied(const flk_apply_args& a, float x, float p
   if (!a.center) return clipf(u, a.lo, a.hi);
   return (u < a.lo || u > a.hi) ? clipf(u, a.lo, a.hi) - pv : x;
 }
-__device__ static inline int wrap(int t, int T) { t %= T; return t < 0 ? t + T : t; }
 
 // ---- 8-bit encode (flk_export_args; include/flicker_hip.h): the export kernel's quantiser, and the quantised apply's -------------
 // y = x_adv * mul + add; z = y * levels; q = z >= 0 ? min(rint(z), 255) : 0 -- every operation rounded on its own; NaN -> 0
@@ -1100,20 +1068,9 @@ extern "C" int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, i
 // Frame i of clip b = i / clip_T records a mix of the K <= 4 consecutive rows rows[i], rows[i] + 1, ... (mod P) of delta, weighted by
 // the clip's taps [K] and scaled per channel by its gain [3] (null: none).  A linear map at the per-clip seam of the two kernels above:
 // the mix takes the place of the gather, its transpose the place of the row gradient.  Every product and every sum is rounded on its
-// own (mul_rn / add_rn below: nothing contracts to an fma), in one fixed order, so videoresnet_spec.flicker_rows_mix / _mix_grad
+// own (mul_rn / add_rn of perturb_common.h: nothing contracts to an fma), in one fixed order, so videoresnet_spec.flicker_rows_mix / _mix_grad
 // restate both bit for bit; with K = 1, tap 1 and no gain (or gain 1) they are the two kernels above, bit for bit (1 * x = x).
 constexpr int ROWS_MIX_MAX_K = 4;
-
-// one rounded product / sum: hipcc contracts a * b + c into one fma wherever BOTH operations allow it, and its headers define
-// __fmul_rn / __fadd_rn as the plain operators, so the two are spelt out here with contraction switched off for their own operation
-__device__ static inline float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ static inline float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
 
 // one thread = one value of delta_clip; raw values; the first product starts the sum (not 0 + product: a -0 stays -0)
 __global__ __launch_bounds__(256) void flicker_rows_mix_kernel(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps,

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, ExportArgs, LossArgs, PoolArgs, PrepareArgs, PrepBox,
+from ._lib import (FLK_BF16, FLK_F32, FLK_NET_I3D, FLK_PREP_MAX_CLIPS, AdamArgs, ApplyArgs, ConvArgs, DenseAdamArgs, ExportArgs, IllumArgs, LossArgs, PoolArgs, PrepareArgs, PrepBox,
                    PrepClip, check, dtype_code, load, ptr, stream_ptr, torch_dtype)
 from .videoresnet_spec import DEFAULT_MEAN, DEFAULT_STD, prepare_geometry
 
@@ -517,7 +517,75 @@ def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):
     return gdelta
 
 
-FLICKER_MAX_PERIOD = 682      # 3 * P values are what flk_perturb_reg_adam holds (256 threads x 8)
+# ---- the flicker as scene illumination (flk_illum_*): a second pixel model beside the additive one ----------------------------------
+def make_illum_args(tables, device="cuda", out_mul=None, out_add=None):
+    """flk_illum_args of a pair of camera tables (``videoresnet_spec.illum_tables``: dec float32 [256,3], enc float32 [N+1]; numpy
+    arrays are copied to ``device``, CUDA tensors are taken as they are).  ``out_mul`` / ``out_add``: the affine map from a display
+    value in [0,1] to the network's input (default: the torch dialect's 1 / std and -mean / std)."""
+    from .videoresnet_spec import ILLUM_MAX_N, illum_out_affine
+    dec, enc = tables
+    dec = dec if torch.is_tensor(dec) else torch.from_numpy(np.ascontiguousarray(dec)).to(device)
+    enc = enc if torch.is_tensor(enc) else torch.from_numpy(np.ascontiguousarray(enc)).to(device)
+    if not (dec.dtype == torch.float32 and tuple(dec.shape) == (256, 3) and dec.is_contiguous() and enc.dtype == torch.float32 and enc.dim() == 1
+            and 3 <= enc.shape[0] <= ILLUM_MAX_N + 1 and enc.is_contiguous() and dec.device == enc.device):
+        raise ValueError(f"make_illum_args: dec fp32 [256,3] and enc fp32 [N+1] (N in 2..{ILLUM_MAX_N}) on one device, got {tuple(dec.shape)} {dec.dtype} "
+                         f"and {tuple(enc.shape)} {enc.dtype}")
+    mul0, add0 = illum_out_affine()
+    m = IllumArgs()
+    m.dec, m.enc, m.enc_n = ptr(dec), ptr(enc), int(enc.shape[0]) - 1
+    m.out_mul = (C.c_float * 3)(*(mul0 if out_mul is None else out_mul))
+    m.out_add = (C.c_float * 3)(*(add0 if out_add is None else out_add))
+    m._keepalive = (dec, enc)      # the struct holds raw pointers only
+    return m
+
+
+def illum_apply_s2d(args, illum, dtype, out=None):
+    """the clip of ``args`` (make_apply_args: uint8 with x_lut, fold_t 1 or 4; dclip = the largest relative modulation) lit by its
+    flicker, in the folded layout of ``perturb_apply_s2d`` (flk_illum_apply_s2d)"""
+    if out is None:
+        out = torch.empty((args.B, args.T, args.H // 2, args.W // 2, 32 if args.fold_t == 4 else 16), dtype=torch_dtype(dtype_code(dtype)),
+                          device=args._keepalive[0].device)
+    check(load().flk_illum_apply_s2d(C.byref(args), C.byref(illum), ptr(out), dtype_code(dtype), stream_ptr()))
+    return out
+
+
+def illum_export_u8(args, illum, out=None, out_offset=0, stats=False, delta_T=None):
+    """the bytes a camera stores of the clip of ``args`` (make_export_apply_args, or make_apply_args) lit by its flicker
+    (flk_illum_export_u8); ``out`` / ``out_offset`` / ``stats`` / ``delta_T`` as ``export_adversarial_u8``"""
+    B, T, H, W = args.B, args.T, args.H, args.W
+    built = getattr(args, "_delta_T", 0)
+    if delta_T is None:
+        delta_T = built
+    if int(delta_T) != built:
+        raise ValueError(f"illum_export_u8: delta_T = {delta_T}, but the arguments were built for delta_T = {built}")
+    dev = args._keepalive[0].device
+    if out is None:
+        out = torch.empty((out_offset + B, T, H, W, 3), dtype=torch.uint8, device=dev)
+    if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 5
+            or tuple(out.shape[1:]) != (T, H, W, 3) or out_offset < 0 or out.shape[0] < out_offset + B):
+        desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
+        raise ValueError(f"illum_export_u8: out must be a contiguous CUDA uint8 tensor [>= {out_offset + B},{T},{H},{W},3], got {desc}")
+    e = make_export_args("torch", T * H * W * 3, out_offset, delta_T)       # (the encode fields are not read: the tables are the encode)
+    st = torch.empty((B, T, 3, 4), dtype=torch.int32, device=dev) if stats else None
+    check(load().flk_illum_export_u8(C.byref(args), C.byref(illum), C.byref(e), ptr(out), ptr(st), stream_ptr()))
+    rows = out[out_offset:out_offset + B]
+    return (rows, st) if stats else rows
+
+
+def illum_grad_reduce(args, illum, gx_s2d, gdelta=None, scratch=None):
+    """d(loss)/d(delta) under the illumination model from the 16-channel input gradient (flk_illum_grad_reduce): fp32 in the shape of
+    the delta of ``args`` -- [T,3], [B,T,3] or, per line (per-clip only), [B,T,H,3]"""
+    dev = args._keepalive[0].device
+    if gdelta is None:
+        shape = (args.B, args.T, args.H, 3) if args.delta_per_line else (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
+        gdelta = torch.empty(shape, dtype=torch.float32, device=dev)
+    if scratch is None and not args.delta_per_line:
+        scratch = torch.empty(load().flk_perturb_grad_scratch_bytes(args.B, args.T, args.H, args.W) // 4, dtype=torch.float32, device=dev)
+    check(load().flk_illum_grad_reduce(C.byref(args), C.byref(illum), ptr(gx_s2d), dtype_code(gx_s2d.dtype), ptr(gdelta), ptr(scratch), stream_ptr()))
+    return gdelta
+
+
+FLICKER_MAX_PERIOD = 682     # 3 * P values are what flk_perturb_reg_adam holds (256 threads x 8)
 
 
 def _check_rows(what, rows, P, rows_host):

@@ -12,8 +12,8 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, RESIZE_RULES, CaptureChannel, check_sampling, flicker_rows, resolve_model,
-                               sample_frame_indices, split_sampling, train_crop_params, u8_decode_table)
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, FLICKER_MODELS, RESIZE_RULES, CaptureChannel, check_sampling, flicker_rows, illum_tables,
+                               resolve_model, sample_frame_indices, split_sampling, train_crop_params, u8_decode_table)
 
 FLICKER_TIMES = ("clip", "video")
 
@@ -48,6 +48,19 @@ CLIP_DTYPES = (torch.float32, torch.uint8)
 _DECODE_TABLES = {}
 
 
+def check_flicker_model(flicker_model, response="srgb", attack_type="flickering", dense=False):
+    """the pixel model of the flicker: "additive" (the reference's: one offset per frame, in normalised display space) or "illumination"
+    (the flicker lights the scene: multiplicative in linear light, through the camera curves ``videoresnet_spec.illum_tables(response)``).
+    Returns the tables (None for "additive").  Host-only; anything else is a ValueError"""
+    if flicker_model not in FLICKER_MODELS:
+        raise ValueError(f"flicker_model must be one of {FLICKER_MODELS}, got {flicker_model!r}")
+    if flicker_model == "additive":
+        return None
+    if attack_type != "flickering" or dense:
+        raise ValueError("flicker_model='illumination': the flickering attack only (a lamp has one value per frame, or per line under a rolling shutter)")
+    return illum_tables(response)
+
+
 def decode_table(device):
     """the uint8 decode table (videoresnet_spec.u8_decode_table, fp32 [256,3]) on ``device``: one copy per device"""
     dev = torch.device(device)
@@ -76,9 +89,13 @@ class Perturbation:
     arguments name it per line (flk_apply_args.delta_per_line)."""
 
     def __init__(self, size, requires_grad=True, device="cuda", max_value=None, min_value=None, max_norm=1.0, cyclic_pert=False, batch=None,
-                 clip_length=None, clips_per_video=1, capture=None):
+                 clip_length=None, clips_per_video=1, capture=None, flicker_model="additive", response="srgb"):
         if len(size) != 4 or size[0] != 3:
             raise ValueError(f"perturbation size must be [3,T,1,1] or [3,T,H,W], got {tuple(size)}")
+        # flicker_model "illumination": the perturbation is a relative modulation of the scene's light (``max_norm`` its largest value),
+        # applied, exported and differentiated by the flk_illum_* kernels through the camera tables of ``response``; uint8 clips only
+        self.illum_tables = check_flicker_model(flicker_model, response, dense=not (size[2] == 1 and size[3] == 1))
+        self.flicker_model, self.illumination, self._illum = flicker_model, flicker_model == "illumination", None
         self.size, self.device, self.requires_grad = tuple(size), device, requires_grad
         self.T = size[1]
         self.dense = not (size[2] == 1 and size[3] == 1)
@@ -250,6 +267,17 @@ class Perturbation:
         if capture is not None and not self.video_time:
             raise ValueError("capture: a perturbation on video time only (clip_length / flicker_time='video')")
 
+    @property
+    def illum(self):
+        """the flk_illum_args of an illumination model (tables uploaded on first use)"""
+        if self._illum is None:
+            self._illum = ops.make_illum_args(self.illum_tables, self.perturbation.device)
+        return self._illum
+
+    def _check_illum_clip(self, x, adversarial):
+        if self.illumination and adversarial and x.dtype != torch.uint8:
+            raise ValueError(f"flicker_model='illumination' takes uint8 clips (the camera curves are tables over the stored bytes), got {x.dtype}")
+
     def apply_args(self, x, adversarial=True, fold_t=1, quantise=False, phases="draw", capture=None):
         """fold_t: 1 = the (h,w)-folded 16-channel tensor; 4 = the same as two bf16 numbers per value (the input of bf16 plans).
         x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
@@ -257,6 +285,7 @@ class Perturbation:
         inside the apply kernel (flk_apply_args.q_lut) -- the clip applied is the one the exported frames decode to, bit for bit"""
         delta = self.perturbation
         self._no_capture_on_clip_time(capture)
+        self._check_illum_clip(x, adversarial)
         if self.video_time:
             # the roll is in the rows; a clean apply reads no perturbation (adv_flag 0), so it gathers nothing and keeps the table
             delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None, capture, int(x.shape[2])), 0
@@ -282,6 +311,7 @@ class Perturbation:
         inf = float("inf")
         delta = self.perturbation
         self._no_capture_on_clip_time(capture)
+        self._check_illum_clip(x, adversarial)
         if self.video_time and not delta_T:
             delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None, capture, int(x.shape[2])), 0
         elif capture is not None and adversarial:
@@ -320,8 +350,10 @@ class Perturbation:
         xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
         if xcl.shape[1] != self.clip_T:
             raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.clip_T}")
-        return ops.export_adversarial_u8(self.export_args(xcl, bool(adversarial), shift_p, capture=capture), "torch", out=out, out_offset=out_offset,
-                                         stats=stats)
+        a = self.export_args(xcl, bool(adversarial), shift_p, capture=capture)
+        if self.illumination and adversarial:           # the bytes a camera stores of the lit scene (clean frames: the existing call)
+            return ops.illum_export_u8(a, self.illum, out=out, out_offset=out_offset, stats=stats)
+        return ops.export_adversarial_u8(a, "torch", out=out, out_offset=out_offset, stats=stats)
 
     def forward(self, input, quantise=False):
         """model.py:80-101: ``input = [x, adversarial]`` -> the perturbed (or, with adversarial False, the untouched) clip; ``quantise``:
@@ -336,7 +368,11 @@ class Perturbation:
         B, T, H, W, _ = xcl.shape
         if T != self.clip_T:
             raise ValueError(f"clip has {T} frames, the perturbation {self.clip_T}")
-        folded = ops.perturb_apply_s2d(self.apply_args(xcl, bool(adversarial), quantise=bool(quantise)), torch.float32)      # [B,T,H/2,W/2,16]
+        a = self.apply_args(xcl, bool(adversarial), quantise=bool(quantise))
+        if self.illumination and adversarial:
+            folded = ops.illum_apply_s2d(a, self.illum, torch.float32)
+        else:
+            folded = ops.perturb_apply_s2d(a, torch.float32)      # [B,T,H/2,W/2,16]
         out = folded[..., :12].reshape(B, T, H // 2, W // 2, 2, 2, 3).permute(0, 1, 2, 4, 3, 5, 6).reshape(B, T, H, W, 3)
         return out.permute(0, 4, 1, 2, 3).contiguous() if ncdhw else out.contiguous()
 
@@ -483,8 +519,15 @@ class FlickerVideoResNet:
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
                  im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb"):
         from .i3d_engine import check_optimizer
+        # flicker_model "illumination": the flicker LIGHTS THE SCENE instead of being added to the displayed pixels -- a pixel of linear
+        # light L becomes L * (1 + m), then goes through the camera's response and 8 bits (videoresnet_spec.illum_tables(response); the
+        # flk_illum_* kernels).  ``l_inf_pert_norm`` is then the largest relative modulation.  Flickering attack, uint8 clips only; the
+        # rows / capture / rolling-shutter seams, the optimisers, ``quantise_train`` and the video loss compose with it unchanged.
+        # "additive" (default): the reference's model, every launch as before.  Checked before anything touches the device
+        check_flicker_model(flicker_model, response, attack_type)
+        self.flicker_model, self.illumination = flicker_model, flicker_model == "illumination"
         # flicker_time "video": the flicker runs on VIDEO time, as ``export_video`` delivers it -- a perturbation of period P =
         # ``flicker_period`` (default: sample_length) rows, frame t of clip b carrying row (frame number - phase) mod P, the frame numbers
         # being those the clips were cut at (``prepare_videos`` / whole-video loaders: ``last_sampling``; pre-cut clips:
@@ -569,7 +612,8 @@ class FlickerVideoResNet:
             raise ValueError("per_clip: flickering attack, no cyclic roll, one rank")
         self.pert_model = Perturbation((3, self.P, 1, 1) if attack_type == "flickering" else (3, self.T, self.H, self.W),
                                        max_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, batch=self.B if self.per_clip else None,
-                                       clip_length=self.T if self.video_time else None, clips_per_video=G, capture=capture)
+                                       clip_length=self.T if self.video_time else None, clips_per_video=G, capture=capture,
+                                       flicker_model=flicker_model, response=response)
         dev = torch.device("cuda", device)
         tdt = torch.bfloat16 if dtype in ("bf16", torch.bfloat16) else torch.float32
         # bf16 plans take the clip as TWO bf16 numbers per value (32 channels, fold_t = 4: the stem sees x + delta/std to ~16 bits -- one
@@ -593,8 +637,18 @@ class FlickerVideoResNet:
         """Perturbation -> network: the apply arguments of this call (the backward pass masks with the same) ; logits in self._logits"""
         a = self.pert_model.apply_args(self._check_x(x), adversarial, fold_t=self.net.input_fold, quantise=self.quantise_train and bool(adversarial),
                                        phases=phases, capture=capture)
-        self.net.forward_apply(a, self._xs, self._logits)           # the plan applies the perturbation in front of its stem
+        if self.illumination and adversarial:                       # the illumination apply in front of the plan, then the plain forward
+            ops.illum_apply_s2d(a, self.pert_model.illum, self._xs.dtype, out=self._xs)
+            self.net.forward(self._xs, self._logits)
+        else:
+            self.net.forward_apply(a, self._xs, self._logits)       # the plan applies the perturbation in front of its stem
         return a
+
+    def _grad_reduce(self, a, out):
+        """d(loss)/d(delta) of the apply ``a`` from the input gradient of the last backward, under the engine's pixel model"""
+        if self.illumination:
+            return ops.illum_grad_reduce(a, self.pert_model.illum, self._gx, out, self._scratch)
+        return ops.perturb_grad_reduce(a, self._gx, out, self._scratch)
 
     def _check_x(self, x):
         """a clip is the normalised fp32 tensor or its uint8 frames (decoded on the device, bitwise the same clip)"""
@@ -750,6 +804,9 @@ class FlickerVideoResNet:
         if quantise not in (None, "clip", "video"):
             raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
         adversarial = adversarial or quantise is not None
+        if self.illumination and adversarial and quantise != "video":
+            raise ValueError("evaluate_videos: flicker_model='illumination' lights the stored bytes of a video -- score it with quantise='video' "
+                             "(the clips prepared here are resampled fp32 values, which the camera tables do not take)")
         draws = []
         if capture is not None:
             if not (isinstance(capture, CaptureChannel) and self.video_time and adversarial):
@@ -897,7 +954,10 @@ class FlickerVideoResNet:
         if not torch.is_tensor(video_u8) or video_u8.dim() != 4 or video_u8.dtype != torch.uint8 or video_u8.shape[-1] != 3 or not video_u8.is_cuda or video_u8.shape[0] < 1:
             raise ValueError("export_video: a CUDA uint8 tensor [N,H,W,3]")
         a = self.pert_model.export_args(video_u8.contiguous()[None], True, shift_p=int(phase), delta_T=self.P, capture=capture)
-        res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.P)
+        if self.illumination:
+            res = ops.illum_export_u8(a, self.pert_model.illum, stats=stats, delta_T=self.P)
+        else:
+            res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.P)
         return (res[0][0], res[1][0]) if stats else res[0]
 
     def _check_video_labels(self, labels):
@@ -969,19 +1029,19 @@ class FlickerVideoResNet:
                 dev = self._logits.device
                 self._g_lines = torch.zeros((self.B, self.T, self.H, 3), dtype=torch.float32, device=dev)
                 self._lines_scratch = torch.empty(self.B * self.T * ops.FLICKER_LINES_MAX_TAPS * 3, dtype=torch.float32, device=dev)
-            ops.perturb_grad_reduce(a, self._gx, self._g_lines, self._scratch)
+            self._grad_reduce(a, self._g_lines)
             ops.flicker_lines_mix_grad(self._g_lines, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
                                        out=red[:n].view(self.P, 3), scratch=self._lines_scratch)
         elif self.video_time:
             # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame), then its frames folded onto their rows
-            ops.perturb_grad_reduce(a, self._gx, self._g_clip, self._scratch)
+            self._grad_reduce(a, self._g_clip)
             if cap is None:
                 ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
             else:                                               # the transpose of the mix the forward ran, on the same tables
                 ops.flicker_rows_mix_grad(self._g_clip, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
                                           out=red[:n].view(self.P, 3))
         else:
-            ops.perturb_grad_reduce(a, self._gx, red[:n].view(self.T, 3), self._scratch)
+            self._grad_reduce(a, red[:n].view(self.T, 3))
         ops.pack_batch_sums(pc, 1.0 / gbatch, red[n:])
         parallel.allreduce_sum_(red, self.pg)
         res = StepResult(adv_loss=red[n], softmax=sm, label_prob=pc[:, 1], _argmax_f=pc[:, 3], _labels=labels, _targeted=bool(criterion.targeted))
@@ -1020,7 +1080,7 @@ class FlickerVideoResNet:
         a = self._forward(x, True)
         criterion.adv(labels, self._logits, 1, out=(sm, self._dl, pc))            # every clip is its own batch of one
         self.net.backward(self._dl, self._gx)
-        ops.perturb_grad_reduce(a, self._gx, g, self._scratch)
+        self._grad_reduce(a, g)
         self._gclip = g
         am = pc[:, 3].to(torch.int64)
         res = StepResult(adv_loss=pc[:, 0], softmax=sm, label_prob=pc[:, 1], argmax=am, _labels=labels, _targeted=bool(criterion.targeted),
@@ -1402,7 +1462,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
                  process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb"):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1417,6 +1477,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
                          device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
                          clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
-                         flicker_time=flicker_time, flicker_period=flicker_period, capture=capture)
+                         flicker_time=flicker_time, flicker_period=flicker_period, capture=capture, flicker_model=flicker_model,
+                         response=response)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

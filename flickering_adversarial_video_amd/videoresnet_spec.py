@@ -592,6 +592,196 @@ def flicker_lines_mix_grad(g_lines, rows, clip_T, taps, gain, period):
     return out
 
 
+# ---- the flicker as scene illumination (include/flicker_hip.h: flk_illum_*) ---------------------------------------------------------
+FLICKER_MODELS = ("additive", "illumination")
+ILLUM_RESPONSES = ("srgb", "linear")
+ILLUM_N = 4096                  # segments of the built-in encode tables
+ILLUM_MAX_N = 16384             # what the kernels stage in LDS
+
+
+def illum_out_affine():
+    """(out_mul, out_add) of the torch dialect, float32 [3] each: a display value e in [0,1] becomes ``e * (1 / std) + (-mean / std)``"""
+    mean, std = np.array(DEFAULT_MEAN, np.float32), np.array(DEFAULT_STD, np.float32)
+    return (np.float32(1.0) / std).astype(np.float32), (-mean / std).astype(np.float32)
+
+
+def illum_tables(response="srgb"):
+    """The camera curves of the illumination model as tables: ``dec`` float32 [256,3], the linear light in [0,1] of byte v of channel c,
+    and ``enc`` float32 [N+1], the display value in [0,1] of linear light i / N, non-decreasing, interpolated linearly in between.
+    ``response``: "srgb" (IEC 61966-2-1, N = 4096), "linear" (dec = v / 255, enc = i / N, N = 4096), or a pair of arrays (dec, enc) --
+    a measured curve, N = len(enc) - 1 in 2..16384.  Every pair must give every byte back under no modulation (the round trip of
+    ``illum_export_host`` with delta = 0 over all 256 levels x 3 channels); a pair that does not raises ValueError."""
+    if isinstance(response, str):
+        if response not in ILLUM_RESPONSES:
+            raise ValueError(f"illum_tables: response must be one of {ILLUM_RESPONSES} or a (dec, enc) pair of arrays, got {response!r}")
+        v, g = np.arange(256, dtype=np.float64) / 255.0, np.arange(ILLUM_N + 1, dtype=np.float64) / ILLUM_N
+        if response == "srgb":
+            lin = np.where(v <= 0.04045, v / 12.92, ((v + 0.055) / 1.055) ** 2.4)
+            enc = np.where(g <= 0.0031308, 12.92 * g, 1.055 * g ** (1.0 / 2.4) - 0.055)
+        else:
+            lin, enc = v, g
+        dec = np.repeat(lin[:, None], 3, axis=1)
+    else:
+        try:
+            dec, enc = response
+            dec, enc = np.asarray(dec, dtype=np.float64), np.asarray(enc, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("illum_tables: response must be \"srgb\", \"linear\" or a (dec, enc) pair of arrays") from None
+        if dec.shape != (256, 3) or enc.ndim != 1 or not 3 <= enc.shape[0] <= ILLUM_MAX_N + 1:
+            raise ValueError(f"illum_tables: dec must be [256,3] and enc [N+1] with N in 2..{ILLUM_MAX_N}, got {dec.shape} and {enc.shape}")
+    dec, enc = np.ascontiguousarray(dec, dtype=np.float32), np.ascontiguousarray(np.clip(enc, 0.0, 1.0) if isinstance(response, str) else enc, dtype=np.float32)
+    if not (np.isfinite(dec).all() and np.isfinite(enc).all() and dec.min() >= 0 and dec.max() <= 1 and enc.min() >= 0 and enc.max() <= 1):
+        raise ValueError("illum_tables: the values of dec and enc must lie in [0,1]")
+    if (np.diff(enc) < 0).any():
+        raise ValueError("illum_tables: enc must be non-decreasing")
+    levels = np.ascontiguousarray(np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1).reshape(1, 1, 16, 16, 3))
+    back = illum_export_host(levels, np.zeros((1, 3), np.float32), (dec, enc))
+    if not np.array_equal(back, levels):
+        miss = int((back != levels).sum())
+        raise ValueError(f"illum_tables: the pair does not give every byte back under no modulation ({miss} of 768 (level, channel) entries miss)")
+    return dec, enc
+
+
+def _illum_tables_checked(tables):
+    dec, enc = tables
+    dec, enc = np.asarray(dec), np.asarray(enc)
+    if dec.dtype != np.float32 or dec.shape != (256, 3) or enc.dtype != np.float32 or enc.ndim != 1 or not 3 <= enc.shape[0] <= ILLUM_MAX_N + 1:
+        raise ValueError(f"illumination tables: dec float32 [256,3] and enc float32 [N+1], N in 2..{ILLUM_MAX_N}, got {dec.shape} {dec.dtype} and {enc.shape} {enc.dtype}")
+    return dec, enc
+
+
+def _illum_factor(x, delta, dclip, dclip_clip, adv_flag, shift_p, delta_T, per_line):
+    """s = 1 + adv_flag * clamp(delta), float32, broadcastable against [B,T,H,W,3]"""
+    f32 = np.float32
+    B, T, H = x.shape[:3]
+    d = np.asarray(delta)
+    if d.dtype != np.float32:
+        raise ValueError(f"illumination: delta must be float32, got {d.dtype}")
+    period = int(delta_T) or T
+    rows = (np.arange(T) - int(shift_p)) % period                   # frame t carries row (t - shift_p) mod period
+    if per_line:
+        if d.shape == (period, H, 3):
+            m = d[rows][None, :, :, None, :]
+        elif d.shape == (B, T, H, 3) and not delta_T:
+            m = d[:, rows][:, :, :, None, :]
+        else:
+            raise ValueError(f"illumination: a per-line delta is [{period},{H},3] or [{B},{T},{H},3], got {d.shape}")
+    elif d.shape == (period, 3):
+        m = d[rows][None, :, None, None, :]
+    elif d.shape == (B, T, 3) and not delta_T:
+        m = d[:, rows][:, :, None, None, :]
+    else:
+        raise ValueError(f"illumination: delta is [{period},3] or [{B},{T},3] (per_line: [{period},{H},3] or [{B},{T},{H},3]), got {d.shape}")
+    dc = np.asarray(dclip_clip, f32).reshape(B, 1, 1, 1, 1) if dclip_clip is not None else f32(dclip)
+    inside = np.ones(m.shape, bool)
+    if dclip_clip is not None or dclip > 0:
+        with np.errstate(invalid="ignore"):
+            inside = np.broadcast_to((m >= -dc) & (m <= dc), np.broadcast_shapes(m.shape, np.shape(dc)))
+        m = np.fmin(np.fmax(m, -dc), dc)
+    s = (f32(1.0) + (f32(adv_flag) * m).astype(f32)).astype(f32)
+    return s, inside, rows
+
+
+def _illum_display(by, s, dec, enc):
+    """per value: (e, p, L, d) of the header's formulas, float32, one rounded operation per step"""
+    f32 = np.float32
+    N = enc.shape[0] - 1
+    L = dec[by, np.arange(3)]
+    p = (L * s).astype(f32)
+    u = np.fmin(np.fmax(p, f32(0.0)), f32(1.0))                     # (fmax / fmin: a NaN becomes 0, as on the device)
+    z = (u * f32(N)).astype(f32)
+    i = np.minimum(z.astype(np.int64), N - 1)
+    f = (z - i.astype(f32)).astype(f32)
+    e0 = enc[i]
+    d = (enc[i + 1] - e0).astype(f32)
+    e = (e0 + (f * d).astype(f32)).astype(f32)
+    return e, p, L, d
+
+
+def _illum_byte(e):
+    z = (e * np.float32(255.0)).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        return np.where(z >= 0, np.minimum(np.rint(z), np.float32(255.0)), np.float32(0.0)).astype(np.uint8)
+
+
+def _illum_clip(x):
+    x = np.asarray(x)
+    if x.dtype != np.uint8 or x.ndim != 5 or x.shape[4] != 3:
+        raise ValueError(f"illumination: the clip must be uint8 [B,T,H,W,3], got {x.shape} {x.dtype}")
+    return x
+
+
+def illum_export_host(x, delta, tables, *, dclip=0.0, adv_flag=1.0, shift_x=0, shift_p=0, dclip_clip=None, delta_T=0, per_line=False, stats=False):
+    """``flk_illum_export_u8`` restated in numpy float32 (one rounded operation per step): the bytes a camera stores of the uint8 clip
+    ``x`` [B,T,H,W,3] lit by the flicker ``delta`` ([T,3], [B,T,3], with ``delta_T`` [delta_T,3]; ``per_line``: [T,H,3], [B,T,H,3] or
+    [delta_T,H,3]).  With ``stats`` also the int64 [B,T,3,4] sums of q - v, |q - v|, [q != v] and [p outside [0,1]]."""
+    x = _illum_clip(x)
+    dec, enc = _illum_tables_checked(tables)
+    s, _, _ = _illum_factor(x, delta, dclip, dclip_clip, adv_flag, shift_p, delta_T, per_line)
+    src = np.roll(x, int(shift_x), axis=1)                           # x'[t] = x[(t - shift_x) mod T]
+    e, p, _, _ = _illum_display(src, s, dec, enc)
+    q = _illum_byte(e)
+    if not stats:
+        return q
+    dq = q.astype(np.int64) - src.astype(np.int64)
+    with np.errstate(invalid="ignore"):
+        outside = (p < 0) | (p > 1)
+    return q, np.stack([dq.sum((2, 3)), np.abs(dq).sum((2, 3)), (dq != 0).sum((2, 3)), outside.sum((2, 3))], axis=-1).astype(np.int64)
+
+
+def illum_apply_host(x, delta, tables, *, dclip=0.0, adv_flag=1.0, shift_x=0, shift_p=0, dclip_clip=None, per_line=False, out_mul=None, out_add=None,
+                     q_lut=None):
+    """``flk_illum_apply_s2d`` restated in numpy float32, unfolded: the fp32 clip [B,T,H,W,3] the network sees.  Plain: ``e * out_mul +
+    out_add`` (default ``illum_out_affine``); with ``q_lut`` (float32 [256,3]) the decode of the stored byte.  ``adv_flag`` = 0 is the
+    clean clip of the additive entry point and is not restated here."""
+    if adv_flag == 0:
+        raise ValueError("illum_apply_host: adv_flag = 0 is the clean clip (flk_perturb_apply_s2d), not restated here")
+    x = _illum_clip(x)
+    dec, enc = _illum_tables_checked(tables)
+    s, _, _ = _illum_factor(x, delta, dclip, dclip_clip, adv_flag, shift_p, 0, per_line)
+    e, _, _, _ = _illum_display(np.roll(x, int(shift_x), axis=1), s, dec, enc)
+    if q_lut is not None:
+        return np.ascontiguousarray(np.asarray(q_lut, np.float32)[_illum_byte(e), np.arange(3)])
+    mul, add = illum_out_affine()
+    mul, add = (mul if out_mul is None else np.asarray(out_mul, np.float32)), (add if out_add is None else np.asarray(out_add, np.float32))
+    return np.ascontiguousarray(((e * mul).astype(np.float32) + add).astype(np.float32))
+
+
+def illum_grad_host(x, delta, tables, gx, *, dclip=0.0, adv_flag=1.0, shift_x=0, shift_p=0, dclip_clip=None, per_line=False, out_mul=None,
+                    bound=False):
+    """``flk_illum_grad_reduce`` restated: d(loss)/d(delta) from ``gx`` = d(loss)/d(x_adv), [B,T,H,W,3] unfolded.  The per-value weight
+    ``(d * N) * L`` is the kernel's (float32, two rounded products); the products with ``gx``, the sums and the finishing factor
+    ``adv_flag * out_mul[c]`` are float64.  Returns float64 in the shape of ``delta`` ([T,3], [B,T,3]; ``per_line``: [B,T,H,3] from a
+    per-clip delta); with ``bound`` also the sum of the magnitudes of each output's terms and their number."""
+    x = _illum_clip(x)
+    dec, enc = _illum_tables_checked(tables)
+    B, T, H, W = x.shape[:4]
+    gx = np.asarray(gx, dtype=np.float64)
+    if gx.shape != x.shape:
+        raise ValueError(f"illum_grad_host: gx must have the clip's shape {x.shape}, got {gx.shape}")
+    s, inside, rows = _illum_factor(x, delta, dclip, dclip_clip, adv_flag, shift_p, 0, per_line)
+    d_shape = np.asarray(delta).shape
+    per_clip = len(d_shape) == (4 if per_line else 3)
+    if per_line and not per_clip:
+        raise ValueError("illum_grad_host: the per-line gradient needs a per-clip delta [B,T,H,3]")
+    _, p, L, d = _illum_display(np.roll(x, int(shift_x), axis=1), s, dec, enc)
+    w = ((d * np.float32(enc.shape[0] - 1)).astype(np.float32) * L).astype(np.float32)
+    with np.errstate(invalid="ignore"):
+        live = (p >= 0) & (p <= 1)
+    mul = illum_out_affine()[0] if out_mul is None else np.asarray(out_mul, np.float32)
+    terms = np.where(live, gx * w.astype(np.float64), 0.0) * (float(np.float32(adv_flag)) * mul.astype(np.float64))
+    axes = (3,) if per_line else (2, 3) if per_clip else (0, 2, 3)
+    n = W if per_line else H * W if per_clip else B * H * W
+    keep = np.broadcast_to(inside, (B if per_clip else 1, T, H if per_line else 1, 1, 3)).reshape(d_shape)     # by frame t: rolled back below
+    g_t, mag_t = terms.sum(axes), np.abs(terms).sum(axes)                # indexed by frame t; delta row rows[t] receives it
+    g, mag = np.zeros(d_shape), np.zeros(d_shape)
+    t_axis = 1 if per_clip else 0
+    idx = [slice(None)] * len(d_shape)
+    idx[t_axis] = rows
+    g[tuple(idx)], mag[tuple(idx)] = np.where(keep, g_t, 0.0), np.where(keep, mag_t, 0.0)
+    return (g, mag, n) if bound else g
+
+
 def _capture_range(name, v, lo_bound, hi_bound):
     pair = (v, v) if np.ndim(v) == 0 else tuple(v)
     if len(pair) != 2:
@@ -787,6 +977,14 @@ def add_capture_arguments(ap):
     ap.add_argument("--eval-capture-draws", type=int, default=0, metavar="N", help="after training, score the attack over N random captures per "
                     "video drawn from the channel (evaluate_videos(capture=, capture_draws=N)): the fooling ratio of every draw, their mean "
                     "and minimum")
+
+
+def add_flicker_model_arguments(ap):
+    """the scripts' options of the flicker's pixel model (FlickerVideoResNet(flicker_model=, response=))"""
+    ap.add_argument("--flicker-model", default="additive", choices=list(FLICKER_MODELS), help="additive: one offset per frame added to every "
+                    "normalised pixel (the reference's model).  illumination: the flicker lights the scene -- linear light times (1 + m), then "
+                    "the camera's response and 8 bits; the norm bound is the largest relative modulation; uint8 clips only")
+    ap.add_argument("--response", default="srgb", choices=list(ILLUM_RESPONSES), help="--flicker-model illumination: the camera's response curve")
 
 
 def capture_from_arguments(ap, a):

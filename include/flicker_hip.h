@@ -391,6 +391,46 @@ int flk_flicker_lines_mix(const float* delta, int P, const int32_t* rows, int n,
 int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K, const float* gain,
                                int P, float* scratch, float* g_rows, void* stream);
 
+/* The flicker as SCENE ILLUMINATION (csrc/illum.hip): a second pixel model beside the additive one of flk_perturb_apply_s2d.  A lamp
+ * multiplies the linear light of a pixel, the camera then applies its response curve and stores 8 bits; both curves are TABLES, so the
+ * kernels equal a numpy float32 restatement bit for bit (videoresnet_spec.illum_apply_host / illum_export_host / illum_grad_host), the
+ * slope the gradient uses is exact, and a measured camera curve can be supplied.  Per source byte v of channel c at (b,t,h,w), every
+ * product and every sum rounded to fp32 on its own (no fused multiply-add):
+ *   m = clamp(delta value of (b, (t - shift_p) mod T, [h], c), +-dclip)     dclip / dclip_dev as flk_apply_args; inv_std is NOT applied:
+ *                                                                          m is a relative modulation of the light
+ *   L = dec[v * 3 + c]                                                      linear light in [0,1]
+ *   s = 1 + adv_flag * m;   p = L * s;   u = min(max(p, 0), 1)
+ *   z = u * N;   i = min(int(z), N - 1);   f = z - i;   d = enc[i + 1] - enc[i];   e = enc[i] + f * d       display value in [0,1]
+ *   plain:      x_adv = e * out_mul[c] + out_add[c]                         (torch dialect: 1 / std, -mean / std)
+ *   quantised:  q = min(rint(e * 255), 255) (NaN -> 0);   x_adv = q_lut[q * 3 + c]      (a->q_lut != NULL; q_mul / q_add / q_levels unused)
+ *   export:     the byte q
+ * dec: DEVICE fp32 [256][3]; enc: DEVICE fp32 [enc_n + 1], non-decreasing, N = enc_n in 2..16384 (both staged in LDS by every kernel).
+ * `a` is read as by the additive entry points, except: lo, hi, x_scale, x_bias, inv_std and the encode fields are not used; the clip is
+ * uint8 with x_lut given (x_lut itself is read only by the adv_flag = 0 delegation below); delta is the shared [T,3], the per-clip
+ * [B,T,3] or the per-line [Bd,T,H,3] form.
+ *   flk_illum_apply_s2d:   x_adv in the layouts of fold_t 1 (fp32 / bf16, 16 channels) and 4 (bf16, hi | lo), as flk_perturb_apply_s2d
+ *                          lays out its values; adv_flag == 0 is DELEGATED to flk_perturb_apply_s2d(a): the clean clip, bit for bit.
+ *   flk_illum_export_u8:   the bytes q, out / e->out_clip_offset / out_clip_stride / delta_T as flk_adv_export_u8 (T, H, W any positive
+ *                          numbers; e->mul / add / levels unused); stats as there with q_clean = the source byte and the fourth sum
+ *                          counting the values with p outside [0,1].
+ *   flk_illum_grad_reduce: d(loss)/d(m), straight-through under quantisation: per output the sum over its pixels of
+ *                          gx * ((d * N) * L) * 1[0 <= p <= 1] (the weight two rounded products, the term a third, terms added in one
+ *                          fixed order, fp32, no atomics), then once per output  * adv_flag * out_mul[c], zero where the delta value lies
+ *                          outside its clamp.  gx_s2d: the 16-channel gradient of fold_t 1 (also for fold_t 4), fp32 or bf16.  gdelta:
+ *                          [T,3], [B,T,3] or (per line, needs delta_per_clip) [B,T,H,3].  partials: scratch of
+ *                          flk_perturb_grad_scratch_bytes (unused per line).  The chunking depends on the shapes only, and per clip it
+ *                          is the batch-1 call's: a per-clip result equals the batch-1 call on that clip, bit for bit.
+ * No allocation, no synchronisation; results do not depend on the launch geometry.
+ * FLK_EINVAL before any GPU call, naming the field: null a / m / x / delta / out; an fp32 clip or a null x_lut; center != 0; delta_dense;
+ * fold_t other than 1 and 4 (apply and gradient; fold_t 4 writes bf16 only); null dec / enc; enc_n outside 2..16384; dclip_dev without
+ * delta_per_clip; the per-line gradient without delta_per_clip; the pointer-alignment contract of flk_perturb_apply_s2d (x 2-byte,
+ * out and gx_s2d 16-byte aligned); for the export what flk_adv_export_u8 refuses of the fields it shares. */
+typedef struct { const float* dec; const float* enc; int enc_n; float out_mul[3], out_add[3]; } flk_illum_args;
+int flk_illum_apply_s2d(const flk_apply_args* a, const flk_illum_args* m, void* out, int dtype, void* stream);
+int flk_illum_export_u8(const flk_apply_args* a, const flk_illum_args* m, const flk_export_args* e, uint8_t* out, int32_t* stats, void* stream);
+int flk_illum_grad_reduce(const flk_apply_args* a, const flk_illum_args* m, const void* gx_s2d, int dtype, float* gdelta, float* partials,
+                          void* stream);
+
 /* Fused form of (stem data-gradient + flk_perturb_grad_reduce) for the flickering perturbation of I3D: d(loss)/d(delta[t,c]) straight
  * from G = d(loss)/d(pre-ReLU output of Conv3d_1a_7x7) (bf16 [B,T/2,H/2,W/2,g_ld], 64 channels) -- replaces Conv3DBackpropInputV2 of
  * i3d.py:169 and the clip_by_value / reduce_sum gradients of kinetics_i3d_utils.py:100-142 with ONE MFMA kernel in the weight-gradient

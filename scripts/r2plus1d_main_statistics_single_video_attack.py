@@ -23,7 +23,9 @@ its frame number in the video, which is what `--eval-quantised video` lays over 
 `--capture-subframe / --capture-exposure / --capture-gain / --capture-readout LO HI` (with `--capture-gain-mode`, `--capture-seed`; video
 time only; `--capture-readout`: a rolling shutter, every line of a frame records its own mix of rows) train the
 flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` scores the final flicker over N random
-captures (`capture_video_preds`, `capture_video_is_adversarial` [N], `capture_draws`)."""
+captures (`capture_video_preds`, `capture_video_is_adversarial` [N], `capture_draws`).
+`--flicker-model illumination` (with `--response srgb|linear`) trains and scores the flicker as scene illumination -- multiplicative in
+linear light, through the camera's response tables -- instead of an additive pixel offset; uint8 clips at the engine's size only."""
 import argparse
 import os
 import sys
@@ -67,7 +69,8 @@ def run_whole_videos(a):
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
                                  clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
+                                 flicker_model=a.flicker_model, response=a.response)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
@@ -192,6 +195,7 @@ def main():
                     "final flicker over the whole video at its own resolution, scored by the clean evaluation -- quantised_video_pred, "
                     "quantised_video_is_adversarial, realised_flicker (levels per frame and channel)")
     vs.add_capture_arguments(ap)
+    vs.add_flicker_model_arguments(ap)
     a = ap.parse_args()
     a.capture = vs.capture_from_arguments(ap, a)
     if a.eval_capture_draws and not vs.is_video_file(a.videos_npz):
@@ -230,7 +234,8 @@ def main():
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
+                                 flicker_model=a.flicker_model, response=a.response)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -47,7 +47,9 @@ The epoch results hold `flicker_period`.
 `--capture-subframe / --capture-exposure / --capture-gain / --capture-readout LO HI` (with `--capture-gain-mode`, `--capture-seed`; video
 time only; `--capture-readout`: a rolling shutter, every line of a frame records its own mix of rows) train the
 flicker through a camera's capture channel, one drawn per video and step; `--eval-capture-draws N` (whole-video files) scores the trained
-flicker over N random captures of the validation videos (`video_eval_capture.npz`)."""
+flicker over N random captures of the validation videos (`video_eval_capture.npz`).
+`--flicker-model illumination` (with `--response srgb|linear`) trains and scores the flicker as scene illumination -- multiplicative in
+linear light, through the camera's response tables -- instead of an additive pixel offset; uint8 clips at the engine's size only."""
 import argparse
 import glob
 import os
@@ -164,7 +166,8 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
+                                 flicker_model=a.flicker_model, response=a.response)
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -323,6 +326,7 @@ def main():
                     "video_eval_quantised.npz); video (whole-video files): every validation video flickered whole at its own resolution, "
                     "then the clean evaluation (video_eval_quantised.npz)")
     vs.add_capture_arguments(ap)
+    vs.add_flicker_model_arguments(ap)
     a = ap.parse_args()
     a.capture = vs.capture_from_arguments(ap, a)
     if a.eval_capture_draws and not vs.is_video_file(a.val_npz):
@@ -369,7 +373,8 @@ def main():
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
                                  augment=None if host_aug else augment, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture)
+                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
+                                 flicker_model=a.flicker_model, response=a.response)
     host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
