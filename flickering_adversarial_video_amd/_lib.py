@@ -185,6 +185,7 @@ _SIGS = {
     "flk_net_backward_delta": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ApplyArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_net_prepare_backward_delta": (C.c_int, [C.c_void_p, C.POINTER(ApplyArgs), C.c_void_p, C.c_void_p]),
     "flk_stem_delta_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "flk_stem_delta_grad_chunks": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "flk_stem_delta_grad_weights_create": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "flk_stem_delta_grad_weights_destroy": (C.c_int, [C.c_void_p]),
     "flk_stem_delta_grad_mask": (C.c_int, [C.POINTER(ApplyArgs), C.c_void_p, C.c_void_p]),

@@ -474,15 +474,50 @@ extern "C" int flk_stem_delta_grad_weights_destroy(float* dev) {
   return FLK_OK;
 }
 
+static int sg_check_sizes(int B, int T, int H, int W) {
+  FLK_REQUIRE(B > 0 && T >= 2 && T % 2 == 0 && H > 0 && H % 2 == 0 && W == 224,
+              "flk_stem_delta_grad: T, H must be even and W = 224 (the I3D stem; got %d, %d, %d)", T, H, W);
+  return FLK_OK;
+}
+
 static int sg_check(const flk_apply_args* a) {
   FLK_REQUIRE(a && a->x && a->delta, "flk_stem_delta_grad: null argument");
   FLK_REQUIRE(!a->delta_dense, "flk_stem_delta_grad: flicker perturbation [T,3] only (the dense attack needs the per-pixel gradient)");
   FLK_REQUIRE(!a->x_lut, "flk_stem_delta_grad: x_lut (per-channel decode table) is not supported: the I3D stem decodes x_scale / x_bias");
   FLK_REQUIRE(!a->q_lut, "flk_stem_delta_grad: q_lut (quantised apply) is not supported: the I3D stem takes the centred clip");
   FLK_REQUIRE(!a->delta_per_line, "flk_stem_delta_grad: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
-  FLK_REQUIRE(a->B > 0 && a->T >= 2 && a->T % 2 == 0 && a->H > 0 && a->H % 2 == 0 && a->W == 224,
-              "flk_stem_delta_grad: T, H must be even and W = 224 (the I3D stem; got %d, %d, %d)", a->T, a->H, a->W);
+  if (int rc = sg_check_sizes(a->B, a->T, a->H, a->W)) return rc;
   FLK_REQUIRE(a->lo <= a->hi, "flk_stem_delta_grad: lo > hi");
+  // stem_mask_kernel reads a row of the clip (672 values: a multiple of 16 bytes in either type) as dwords (uint8) / float4 (fp32)
+  if (a->x_is_u8) FLK_REQUIRE(((size_t)a->x & 3) == 0, "flk_stem_delta_grad: a uint8 clip must be 4-byte aligned (got %p)", a->x);
+  else FLK_REQUIRE(((size_t)a->x & 15) == 0, "flk_stem_delta_grad: an fp32 clip must be 16-byte aligned (got %p)", a->x);
+  return FLK_OK;
+}
+
+// the scratch holds the stage-1 partials (floats) and, a multiple of 256 bytes behind its base, the clip mask: written as uint4, read as
+// 16-byte LDS-DMA pieces
+static int sg_check_scratch(const float* scratch) {
+  FLK_REQUIRE(scratch, "flk_stem_delta_grad: null scratch");
+  FLK_REQUIRE(((size_t)scratch & 15) == 0, "flk_stem_delta_grad: scratch must be 16-byte aligned (got %p)", (const void*)scratch);
+  return FLK_OK;
+}
+
+// what the GEMM reads: G in 16-byte LDS-DMA pieces (8 channels; with g_ld % 8 == 0 every piece is aligned when the base is), the weights
+// as float4 in the epilogue and their zero page as DMA pieces
+static int sg_check_gemm(const flk_apply_args* a, const void* G, int g_ld, const float* wf_dev, const float* scratch) {
+  FLK_REQUIRE(G && wf_dev, "flk_stem_delta_grad: null argument");
+  if (int rc = sg_check_scratch(scratch)) return rc;
+  FLK_REQUIRE(g_ld >= SG_CO && g_ld % 8 == 0, "flk_stem_delta_grad: bad channel stride %d", g_ld);
+  FLK_REQUIRE(((size_t)G & 15) == 0, "flk_stem_delta_grad: G must be 16-byte aligned (got %p)", G);
+  FLK_REQUIRE(((size_t)wf_dev & 15) == 0, "flk_stem_delta_grad: wf_dev must be 16-byte aligned (got %p)", (const void*)wf_dev);
+  FLK_REQUIRE((size_t)a->B * (a->T / 2) * (a->H / 2) * (a->W / 2) * g_ld < (1ull << 31), "flk_stem_delta_grad: tensor too large");
+  return FLK_OK;
+}
+
+// stage 2 writes gdelta one float at a time
+static int sg_check_gdelta(const float* gdelta) {
+  FLK_REQUIRE(gdelta, "flk_stem_delta_grad: null gdelta");
+  FLK_REQUIRE(((size_t)gdelta & 3) == 0, "flk_stem_delta_grad: gdelta must be 4-byte aligned (got %p)", (const void*)gdelta);
   return FLK_OK;
 }
 
@@ -491,7 +526,7 @@ static int sg_check(const flk_apply_args* a) {
 extern "C" int flk_stem_delta_grad_mask(const flk_apply_args* a, float* scratch, void* stream) {
   int rc = sg_check(a);
   if (rc) return rc;
-  FLK_REQUIRE(scratch, "flk_stem_delta_grad_mask: null scratch");
+  if ((rc = sg_check_scratch(scratch))) return rc;
   char* const mask = (char*)scratch + sg_partial_bytes(a->B, a->T, a->H);
   FLK_LAUNCH_KERNEL(stem_mask_kernel, dim3((unsigned)((long)a->B * a->T * ((a->H + SM_ROWS - 1) / SM_ROWS))), dim3(256), 0, (hipStream_t)stream, *a, mask);
   FLK_CHECK_HIP(hipGetLastError());
@@ -508,18 +543,26 @@ static void sg_chunks(const flk_apply_args* a, int nb, int Ho, int& nchunk, int&
   nchunk = (Ho + rows_per_chunk - 1) / rows_per_chunk;       // no empty chunks
 }
 
+// host only: the chunking flk_stem_delta_grad gives a batch of B clips of T frames x H rows (per_clip != 0: with per-clip perturbations)
+extern "C" int flk_stem_delta_grad_chunks(int B, int T, int H, int per_clip, int* nchunk, int* rows_per_chunk) {
+  FLK_REQUIRE(nchunk && rows_per_chunk, "flk_stem_delta_grad_chunks: null output");
+  if (int rc = sg_check_sizes(B, T, H, 2 * SG_WO)) return rc;
+  flk_apply_args a{};
+  a.B = B; a.T = T; a.H = H; a.W = 2 * SG_WO; a.delta_per_clip = per_clip != 0;
+  sg_chunks(&a, B, H / 2, *nchunk, *rows_per_chunk);
+  return FLK_OK;
+}
+
 // the GEMM for clips [b0, b0 + nb) of the batch (mask in the scratch already; stage-1 partials of those clips into their slots of the scratch).
 // A batch may be covered by several such launches of EQUAL nb (on different streams), followed by ONE flk_stem_delta_grad_finish with the same nb.
 int flk_stem_delta_grad_part(const flk_apply_args* a, int b0, int nb, const void* G, int g_ld, const float* wf_dev, float* scratch, hipStream_t s) {
   int rc = sg_check(a);
   if (rc) return rc;
-  FLK_REQUIRE(G && wf_dev && scratch, "flk_stem_delta_grad: null argument");
-  FLK_REQUIRE(g_ld >= SG_CO && g_ld % 8 == 0, "flk_stem_delta_grad: bad channel stride %d", g_ld);
+  if ((rc = sg_check_gemm(a, G, g_ld, wf_dev, scratch))) return rc;
   FLK_REQUIRE(b0 >= 0 && nb > 0 && b0 + nb <= a->B, "flk_stem_delta_grad: clips [%d, %d) of %d", b0, b0 + nb, a->B);
   StemGradKP kp{};
   kp.B = nb; kp.T = a->T; kp.H = a->H;
   kp.To = a->T / 2; kp.Ho = a->H / 2; kp.Wo = a->W / 2;
-  FLK_REQUIRE((size_t)a->B * kp.To * kp.Ho * kp.Wo * g_ld < (1ull << 31), "flk_stem_delta_grad: tensor too large");
   sg_chunks(a, nb, kp.Ho, kp.nchunk, kp.rows_per_chunk);
   // every use of the clip index in the kernel is linear in it: a slice is the same kernel on shifted bases
   kp.G = (const char*)G + (size_t)b0 * kp.To * kp.Ho * kp.Wo * g_ld * 2; kp.g_ld = g_ld; kp.Wf = wf_dev;
@@ -540,7 +583,8 @@ int flk_stem_delta_grad_part(const flk_apply_args* a, int b0, int nb, const void
 int flk_stem_delta_grad_finish(const flk_apply_args* a, int nb, float* scratch, float* gdelta, hipStream_t s) {
   int rc = sg_check(a);
   if (rc) return rc;
-  FLK_REQUIRE(scratch && gdelta && nb > 0 && a->B % nb == 0, "flk_stem_delta_grad_finish: bad argument");
+  if ((rc = sg_check_scratch(scratch)) || (rc = sg_check_gdelta(gdelta))) return rc;
+  FLK_REQUIRE(nb > 0 && a->B % nb == 0, "flk_stem_delta_grad_finish: bad argument");
   int nchunk, rows;
   sg_chunks(a, nb, a->H / 2, nchunk, rows);
   flk_apply_args a2 = *a;
@@ -554,7 +598,8 @@ extern "C" int flk_stem_delta_grad(const flk_apply_args* a, const void* G, int g
                                    float* scratch, int mask_done, void* stream) {
   int rc = sg_check(a);
   if (rc) return rc;
-  FLK_REQUIRE(G && wf_dev && gdelta && scratch, "flk_stem_delta_grad: null argument");
+  // everything the three launches would refuse, before the first of them
+  if ((rc = sg_check_gemm(a, G, g_ld, wf_dev, scratch)) || (rc = sg_check_gdelta(gdelta))) return rc;
   if (!mask_done && (rc = flk_stem_delta_grad_mask(a, scratch, stream))) return rc;
   if ((rc = flk_stem_delta_grad_part(a, 0, a->B, G, g_ld, wf_dev, scratch, (hipStream_t)stream))) return rc;
   return flk_stem_delta_grad_finish(a, a->B, scratch, gdelta, (hipStream_t)stream);

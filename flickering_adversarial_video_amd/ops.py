@@ -779,6 +779,14 @@ class StemDeltaGradWeights:
             pass
 
 
+def stem_delta_grad_chunks(B, T, H, per_clip=False):
+    """(nchunk, rows_per_chunk): how flk_stem_delta_grad cuts the H/2 output rows of each (clip, frame pair) of a [B,T,H,224,3] batch
+    (flk_stem_delta_grad_chunks; host only, needs no GPU).  per_clip: the chunking of per-clip perturbations (the batch-1 call's)"""
+    n, rows = C.c_int(), C.c_int()
+    check(load().flk_stem_delta_grad_chunks(int(B), int(T), int(H), int(bool(per_clip)), C.byref(n), C.byref(rows)))
+    return n.value, rows.value
+
+
 def stem_delta_grad(args, G, weights, gdelta=None, scratch=None):
     """G: bf16 [B,T/2,H/2,W/2,ld] gradient of the stem's pre-ReLU output; returns d(loss)/d(delta) [T,3]"""
     assert G.dtype == torch.bfloat16 and G.is_contiguous() and G.dim() == 5

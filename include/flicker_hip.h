@@ -439,8 +439,21 @@ int flk_illum_grad_reduce(const flk_apply_args* a, const flk_illum_args* m, cons
  * [7,7,7,3,64] stem weights x the folded batch-norm scale, fp32); scratch: flk_stem_delta_grad_scratch_bytes() of caller scratch
  * (stage-1 partials + the de-interleaved clip mask, 768 bytes per clip row).  Two launches: the mask pre-pass (HBM-bound;
  * mask_done != 0 skips it when flk_stem_delta_grad_mask already ran for the same arguments) and the GEMM.
- * Deterministic (fixed summation order); bf16 gradients only -- the fp32 parity mode keeps the two-kernel path. */
+ * Deterministic (fixed summation order); bf16 gradients only -- the fp32 parity mode keeps the two-kernel path.
+ * Pointer contract (flk_stem_delta_grad and flk_stem_delta_grad_mask; FLK_EINVAL naming the alignment, before any GPU call -- a refused
+ * flk_stem_delta_grad launches nothing, not even the mask pre-pass): a uint8 clip x is 4-byte aligned and an fp32 clip 16-byte aligned
+ * (the mask pre-pass reads a row of the clip as dwords / float4: stricter than flk_perturb_apply_s2d asks); G, wf_dev and scratch are
+ * 16-byte aligned (G and the mask inside the scratch move by 16-byte LDS-DMA pieces -- with g_ld % 8 == 0 every piece of G is aligned
+ * when its base is -- and the weights are read as float4); gdelta is 4-byte aligned.  delta, dclip_dev and the stage-1 partials at the head of the
+ * scratch are read and written one float at a time.  g_ld >= 64, g_ld % 8 == 0; channels [64, g_ld) of G are never read.
+ * flk_stem_delta_grad_chunks (host only: no device work, callable without a GPU): how flk_stem_delta_grad cuts the work of a batch of B
+ * clips of T frames x H rows -- one workgroup per (clip, frame pair, chunk of output rows): *nchunk chunks of *rows_per_chunk output
+ * rows (H/2 in all), the last chunk H/2 - (*nchunk - 1) * *rows_per_chunk rows.  per_clip != 0: for per-clip perturbations
+ * (flk_apply_args.delta_per_clip), whose chunking is that of a batch-1 call whatever B is -- a per-clip result equals the batch-1 call
+ * on that clip, bit for bit.  The rule depends on the sizes only.  (flk_net_backward_delta may run the GEMM per half of the batch: its
+ * chunking is then that of B/2 clips.)  FLK_EINVAL: null outputs, and the sizes flk_stem_delta_grad refuses (B < 1, T or H odd or < 2). */
 int64_t flk_stem_delta_grad_scratch_bytes(int B, int T, int H);
+int flk_stem_delta_grad_chunks(int B, int T, int H, int per_clip, int* nchunk, int* rows_per_chunk);
 int flk_stem_delta_grad_weights_create(const float* w7_dhwio, const float* bn_scale, float** out_dev);
 int flk_stem_delta_grad_weights_destroy(float* dev);
 int flk_stem_delta_grad_mask(const flk_apply_args* a, float* scratch, void* stream);   /* step 1 alone (clip mask; needs x and delta only) */
