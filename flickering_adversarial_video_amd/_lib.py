@@ -141,6 +141,11 @@ _SIGS = {
     "flk_clip_prepare": (C.c_int, [C.POINTER(PrepareArgs), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_train": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_void_p]),
     "flk_clip_prepare_sampled": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare_toned": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_flicker_tone_slopes": (C.c_int, [C.POINTER(ApplyArgs), C.POINTER(IllumArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare_grad_scratch_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "flk_clip_prepare_grad": (C.c_int, [C.POINTER(PrepareArgs), C.POINTER(PrepBox), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_pack_batch_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_perturb_reg_adam_batched": (C.c_int, [C.POINTER(AdamArgs), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -151,9 +151,10 @@ extern "C" int flk_conv_weights_destroy(flk_conv_weights* w) {
 }
 
 // Clip preparation (csrc/prepare.hip): every argument is checked here, on the host, before anything touches the device.
-int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, float* out, hipStream_t stream);
-int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
-                                  hipStream_t stream);
+int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, float* out,
+                            hipStream_t stream);
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const uint8_t* tone,
+                                  float* out, hipStream_t stream);
 
 // the checks the entries share; `boxes`: the training transform's crop boxes, which take the place of the centre-crop window;
 // `T_out`: frames per clip written by the sampled entry (0: the clip's own T)
@@ -192,13 +193,13 @@ static int check_prepare_args(const char* fn, const flk_prepare_args* a, const f
 
 extern "C" int flk_clip_prepare(const flk_prepare_args* a, float* out, void* stream) {
   if (int rc = check_prepare_args("flk_clip_prepare", a, out, nullptr)) return rc;
-  return flk_clip_prepare_launch(a, nullptr, 0, out, (hipStream_t)stream);
+  return flk_clip_prepare_launch(a, nullptr, 0, nullptr, out, (hipStream_t)stream);
 }
 
 extern "C" int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes, float* out, void* stream) {
   FLK_REQUIRE(boxes, "flk_clip_prepare_train: null box list");
   if (int rc = check_prepare_args("flk_clip_prepare_train", a, out, boxes)) return rc;
-  return flk_clip_prepare_train_launch(a, boxes, nullptr, 0, out, (hipStream_t)stream);
+  return flk_clip_prepare_train_launch(a, boxes, nullptr, 0, nullptr, out, (hipStream_t)stream);
 }
 
 extern "C" int flk_clip_prepare_sampled(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
@@ -206,8 +207,59 @@ extern "C" int flk_clip_prepare_sampled(const flk_prepare_args* a, const flk_pre
   FLK_REQUIRE(frame_idx, "flk_clip_prepare_sampled: null frame_idx");
   FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "flk_clip_prepare_sampled: T_out %d outside 1..65535", T_out);
   if (int rc = check_prepare_args("flk_clip_prepare_sampled", a, out, boxes, T_out)) return rc;
-  if (boxes) return flk_clip_prepare_train_launch(a, boxes, frame_idx, T_out, out, (hipStream_t)stream);
-  return flk_clip_prepare_launch(a, frame_idx, T_out, out, (hipStream_t)stream);
+  if (boxes) return flk_clip_prepare_train_launch(a, boxes, frame_idx, T_out, nullptr, out, (hipStream_t)stream);
+  return flk_clip_prepare_launch(a, frame_idx, T_out, nullptr, out, (hipStream_t)stream);
+}
+
+extern "C" int flk_clip_prepare_toned(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const uint8_t* tone,
+                                      float* out, void* stream) {
+  FLK_REQUIRE(frame_idx, "flk_clip_prepare_toned: null frame_idx");
+  FLK_REQUIRE(tone, "flk_clip_prepare_toned: null tone");
+  FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "flk_clip_prepare_toned: T_out %d outside 1..65535", T_out);
+  if (int rc = check_prepare_args("flk_clip_prepare_toned", a, out, boxes, T_out)) return rc;
+  if (boxes) return flk_clip_prepare_train_launch(a, boxes, frame_idx, T_out, tone, out, (hipStream_t)stream);
+  return flk_clip_prepare_launch(a, frame_idx, T_out, tone, out, (hipStream_t)stream);
+}
+
+// The gradient of a toned preparation (csrc/prepare.hip) and the slope tables it resamples (csrc/attack.hip, csrc/illum.hip)
+int flk_clip_prepare_grad_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
+                                 const float* scale, const void* gx_s2d, int dtype, float* gdelta, float* partials, hipStream_t stream);
+int flk_tone_slopes_launch(const flk_apply_args* a, float* slope, float* scale, hipStream_t stream);
+int flk_illum_tone_slopes_launch(const flk_apply_args* a, const flk_illum_args* m, float* slope, float* scale, hipStream_t stream);
+
+extern "C" int64_t flk_clip_prepare_grad_scratch_bytes(int nclip, int T_out, int Ho) {
+  if (nclip <= 0 || T_out <= 0 || Ho <= 0) return 0;
+  return (int64_t)nclip * T_out * Ho * 3 * (int64_t)sizeof(float);
+}
+
+extern "C" int flk_clip_prepare_grad(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
+                                     const float* scale, const void* gx_s2d, int dtype, float* gdelta, float* partials, void* stream) {
+  static const char* who = "flk_clip_prepare_grad";
+  FLK_REQUIRE(frame_idx, "%s: null frame_idx", who);
+  FLK_REQUIRE(slope && scale, "%s: null slope or scale", who);
+  FLK_REQUIRE(gx_s2d && gdelta && partials, "%s: null gx_s2d, gdelta or partials", who);
+  FLK_REQUIRE(((size_t)gx_s2d & 15) == 0, "%s: gx_s2d must be 16-byte aligned (got %p)", who, gx_s2d);
+  FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "%s: bad dtype", who);
+  FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "%s: T_out %d outside 1..65535", who, T_out);
+  if (int rc = check_prepare_args(who, a, gdelta, boxes, T_out)) return rc;
+  FLK_REQUIRE(a->Ho % 2 == 0 && a->Wo % 2 == 0, "%s: Ho and Wo must be even (the folded gradient layout), got %d x %d", who, a->Ho, a->Wo);
+  return flk_clip_prepare_grad_launch(a, boxes, frame_idx, T_out, slope, scale, gx_s2d, dtype, gdelta, partials, (hipStream_t)stream);
+}
+
+extern "C" int flk_flicker_tone_slopes(const flk_apply_args* a, const flk_illum_args* m, float* slope, float* scale, void* stream) {
+  static const char* who = "flk_flicker_tone_slopes";
+  FLK_REQUIRE(a, "%s: null argument structure", who);
+  FLK_REQUIRE(slope && scale, "%s: null slope or scale", who);
+  FLK_REQUIRE(a->x && a->delta, "%s: null x (the ramp clip) or delta", who);
+  FLK_REQUIRE(a->x_is_u8 && a->x_lut, "%s: a uint8 clip with its decode table (x_is_u8 = 1, x_lut non-null)", who);
+  FLK_REQUIRE(a->B > 0 && a->T > 0, "%s: B and T must be positive (got %d,%d)", who, a->B, a->T);
+  FLK_REQUIRE(!a->delta_per_line, "%s: delta_per_line is not supported (a per-line flicker is not a per-frame byte map)", who);
+  FLK_REQUIRE(!a->delta_dense, "%s: delta_dense is not supported", who);
+  FLK_REQUIRE(a->center == 0, "%s: center must be 0", who);
+  FLK_REQUIRE(a->delta_per_clip, "%s: delta_per_clip = 1 (delta is the per-clip [B,T,3] of video time)", who);
+  FLK_REQUIRE(a->shift_x == 0 && a->shift_p == 0, "%s: no cyclic rolls (shift_x = shift_p = 0)", who);
+  if (m) return flk_illum_tone_slopes_launch(a, m, slope, scale, (hipStream_t)stream);
+  return flk_tone_slopes_launch(a, slope, scale, (hipStream_t)stream);
 }
 
 // 8-bit export of the adversarial clip (csrc/attack.hip): checked here, on the host, before anything touches the device.

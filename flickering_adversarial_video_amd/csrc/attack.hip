@@ -1270,3 +1270,30 @@ extern "C" int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* r
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
+
+// ---- slope tables of a toned preparation, additive model (flk_flicker_tone_slopes; csrc/prepare.hip resamples them) ----------------
+// slope[b][t][v][c] = 1 where the clamp of grad_reduce_stage1 is inactive for source byte v: lo <= u <= hi, u = x_lut[v][c] +
+// adv_flag * pert_at(...) -- the same expression; scale[b][t][c] = grad_reduce_stage2's finishing factors adv_flag * inv_std[c], 0 where
+// the delta value lies outside its clamp.  One workgroup per (clip, frame), thread v.
+__global__ __launch_bounds__(256) void tone_slopes_kernel(const flk_apply_args a, float* slope, float* scale) {
+  const int bt = blockIdx.x, b = bt / a.T, t = bt - b * a.T, v = threadIdx.x;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float u = a.x_lut[v * 3 + c] + a.adv_flag * pert_at(a, b, t, 0, 0, c);
+    slope[((size_t)bt * 256 + v) * 3 + c] = (u >= a.lo && u <= a.hi) ? 1.f : 0.f;
+  }
+  if (v < 3) {
+    const float d = a.delta[(size_t)bt * 3 + v];
+    const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
+    const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
+    scale[(size_t)bt * 3 + v] = pass ? a.adv_flag * a.inv_std[v] : 0.f;
+  }
+}
+
+// arguments already validated (api.cpp: flk_flicker_tone_slopes)
+int flk_tone_slopes_launch(const flk_apply_args* a, float* slope, float* scale, hipStream_t stream) {
+  FLK_REQUIRE(a->lo <= a->hi, "flk_flicker_tone_slopes: lo > hi");
+  FLK_LAUNCH_KERNEL(tone_slopes_kernel, dim3((unsigned)(a->B * a->T)), dim3(256), 0, stream, *a, slope, scale);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}

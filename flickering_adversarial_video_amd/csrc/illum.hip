@@ -367,6 +367,32 @@ __global__ __launch_bounds__(256) void illum_grad_lines_kernel(const flk_apply_a
   }
 }
 
+// ---- slope tables of a toned preparation (flk_flicker_tone_slopes; csrc/prepare.hip resamples them): slope[b][t][v][c] = the weight
+// illum_weight gives source byte v under the frame's factor, 0 where p leaves [0,1]; scale[b][t][c] = illum_grad_stage2's finishing
+// factors adv_flag * out_mul[c], 0 where the delta value lies outside its clamp.  Item = (clip, frame), thread v; workgroups stride
+__global__ __launch_bounds__(256) void illum_tone_slopes_kernel(const flk_apply_args a, const flk_illum_args m, float* slope, float* scale) {
+  extern __shared__ float smem[];
+  float* dec = smem;
+  float* enc = smem + 768;
+  stage_tables(m, nullptr, dec, nullptr, enc);
+  const Curve cv{dec, enc, m.enc_n, (float)m.enc_n};
+  const int v = threadIdx.x;
+  for (int bt = blockIdx.x; bt < a.B * a.T; bt += gridDim.x) {
+    const int b = bt / a.T, t = bt - b * a.T;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float w;
+      slope[((size_t)bt * 256 + v) * 3 + c] = illum_weight(cv, (uint32_t)v, c, illum_s(a, a.T, b, t, 0, c), &w) ? w : 0.f;
+    }
+    if (v < 3) {
+      const float d = a.delta[(size_t)bt * 3 + v];
+      const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
+      const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
+      scale[(size_t)bt * 3 + v] = pass ? mul_rn(a.adv_flag, m.out_mul[v]) : 0.f;
+    }
+  }
+}
+
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 // what the three entry points share (who: the entry point's name)
 int check_illum(const char* who, const flk_apply_args* a, const flk_illum_args* m) {
@@ -500,6 +526,18 @@ extern "C" int flk_illum_grad_reduce(const flk_apply_args* a, const flk_illum_ar
     }
     FLK_LAUNCH_KERNEL(illum_grad_stage2, dim3((a->T * 3 + 127) / 128, a->delta_per_clip ? a->B : 1), dim3(128), 0, st, *a, *m, nchunk, partials, gdelta);
   }
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// arguments shared with the additive form already validated (api.cpp: flk_flicker_tone_slopes)
+int flk_illum_tone_slopes_launch(const flk_apply_args* a, const flk_illum_args* m, float* slope, float* scale, hipStream_t stream) {
+  static const char* who = "flk_flicker_tone_slopes";
+  int rc = check_illum(who, a, m);
+  if (rc) return rc;
+  const int lds = (768 + m->enc_n + 1) * (int)sizeof(float);
+  if ((rc = raise_lds<illum_tone_slopes_kernel>(lds))) return rc;
+  FLK_LAUNCH_KERNEL(illum_tone_slopes_kernel, dim3(capped((long)a->B * a->T)), dim3(256), lds, stream, *a, *m, slope, scale);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

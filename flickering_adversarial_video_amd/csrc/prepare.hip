@@ -60,6 +60,17 @@ struct PrepLaunchSampled : PrepLaunch, PrepFrameTable {};
 static_assert(sizeof(PrepLaunchSampled) <= 4096, "the launch descriptor must fit the kernel-argument segment");
 template <class L>
 constexpr bool prep_sampled = std::is_base_of<PrepFrameTable, L>::value;
+// what a toned descriptor adds to its sampled one (both kernels): the clip is prepared from the DELIVERED video -- the source bytes
+// after the 8-bit export of a per-frame flicker -- without that video ever being written.  A flicker is uniform over a frame, so
+// the delivered frame is the raw frame through a byte -> byte map per (clip, output frame, channel)
+struct PrepToneTable {
+  const uint8_t* tone;        // device uint8 [nclip][gridDim.y][256][3]: tone[k][t][v][c] = the stored byte of source byte v, channel c
+};
+struct PrepLaunchToned : PrepLaunchSampled, PrepToneTable {};
+static_assert(sizeof(PrepLaunchToned) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+template <class L>
+constexpr bool prep_toned = std::is_base_of<PrepToneTable, L>::value;
+constexpr int kPrepToneBytes = 768;        // one (clip, frame) table, staged in LDS behind everything the untoned kernels keep there
 
 // the source frame of output frame t of the workgroup's clip: t itself, or the table's entry clamped into the view's [0, T - 1]
 template <class L>
@@ -83,6 +94,29 @@ inline float prep_src_host(float step, int d) {
 
 __device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
 
+// toned launches, before phase A: the workgroup's table tone[clip][output frame] into LDS (bytes: no alignment asked of `tone`)
+template <class L>
+__device__ __forceinline__ void prep_stage_tone(const L& p, int t, uint8_t* tone_lds) {
+  if constexpr (prep_toned<L>) {
+    const uint8_t* g = p.tone + ((size_t)blockIdx.z * gridDim.y + t) * kPrepToneBytes;
+    for (int k = threadIdx.x; k < kPrepToneBytes; k += 256) tone_lds[k] = g[k];
+    __syncthreads();
+  }
+}
+// the staged dword `w` of a row segment whose first byte sits `mis` bytes into dword 0, through the tone: byte b of the dword is at
+// position 4w + b of the slot and its channel is (position - mis) mod 3.  The up to three bytes in front of the segment and those
+// behind it are mapped too (through some channel's column: any byte is in range); no compute loop reads them
+__device__ __forceinline__ unsigned prep_tone_dword(const uint8_t* tone_lds, unsigned v, int w, int mis) {
+  int ch = (4 * w - mis + 3) % 3;            // mis <= 3: never negative
+  unsigned r = 0;
+#pragma unroll
+  for (int b = 0; b < 4; ++b) {
+    r |= (unsigned)tone_lds[((v >> (8 * b)) & 255u) * 3 + ch] << (8 * b);
+    ch = ch == 2 ? 0 : ch + 1;
+  }
+  return r;
+}
+
 template <class L>
 __global__ __launch_bounds__(256) void clip_prepare_kernel(const L p) {
   extern __shared__ unsigned prep_lds[];      // [256] fp32 table u8 / 255 | [2 * rows] segment misalignments | 2 * rows row segments
@@ -99,6 +133,8 @@ __global__ __launch_bounds__(256) void clip_prepare_kernel(const L p) {
   const int ndw = p.seg_stride >> 2;
   const uint8_t* frame = c.src + (long long)prep_source_frame(p, t, c.T) * c.pitch_t;
   const int nbytes = c.span * 3;
+  uint8_t* tone_lds = (uint8_t*)(seg + 2 * p.rows * ndw);      // toned launches only: 768 bytes more than the untoned ones ask for
+  prep_stage_tone(p, t, tone_lds);
   // ---- stage: slot 2r + s = source row s (0 top, 1 bottom) of output row oh0 + r; columns [x0, x0 + span) ----
   for (int k = threadIdx.x; k < 2 * nrow * ndw; k += 256) {
     const int slot = k / ndw, w = k - slot * ndw;
@@ -108,7 +144,10 @@ __global__ __launch_bounds__(256) void clip_prepare_kernel(const L p) {
     const int mis = (int)((size_t)row & 3);
     if (w == 0) mis_of[slot] = mis;
     // aligned dwords that hold at least one byte of the segment: never beyond the dword of its last byte
-    if (4 * w < mis + nbytes) seg[slot * ndw + w] = *(const unsigned*)(row - mis + 4 * w);
+    if (4 * w < mis + nbytes) {
+      if constexpr (prep_toned<L>) seg[slot * ndw + w] = prep_tone_dword(tone_lds, *(const unsigned*)(row - mis + 4 * w), w, mis);
+      else seg[slot * ndw + w] = *(const unsigned*)(row - mis + 4 * w);
+    }
   }
   __syncthreads();
   // ---- compute: four consecutive floats of the workgroup's contiguous output run per thread and pass ----
@@ -173,9 +212,11 @@ __global__ __launch_bounds__(256) void clip_prepare_kernel(const L p) {
 }  // namespace
 
 // arguments already validated (api.cpp: flk_clip_prepare, flk_clip_prepare_sampled); everything here up to the launch is host arithmetic.
-// frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one
-int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, float* out, hipStream_t stream) {
-  PrepLaunchSampled p;
+// frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one; tone (with frame_idx only): null, or
+// the device tables [nclip][T_out][256][3] of the toned one
+int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, float* out,
+                            hipStream_t stream) {
+  PrepLaunchToned p;
   int max_span = 1, max_T = 1;
   for (int i = 0; i < a->nclip; ++i) {
     const flk_prep_clip& s = a->clips[i];
@@ -205,9 +246,13 @@ int flk_clip_prepare_launch(const flk_prepare_args* a, const int32_t* frame_idx,
   for (int k = 0; k < 3; ++k) { p.mean[k] = a->mean[k]; p.std_[k] = a->std[k]; }
   const size_t lds = (size_t)(256 + 2 * rows) * 4 + (size_t)2 * rows * seg_stride;
   const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
-  if (frame_idx) {
+  if (frame_idx && tone) {
     p.idx = frame_idx;
-    FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunchSampled>, grid, dim3(256), lds, stream, p);
+    p.tone = tone;
+    FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunchToned>, grid, dim3(256), lds + kPrepToneBytes, stream, p);
+  } else if (frame_idx) {
+    p.idx = frame_idx;
+    FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunchSampled>, grid, dim3(256), lds, stream, static_cast<const PrepLaunchSampled&>(p));
   } else {
     FLK_LAUNCH_KERNEL(clip_prepare_kernel<PrepLaunch>, grid, dim3(256), lds, stream, static_cast<const PrepLaunch&>(p));
   }
@@ -267,6 +312,8 @@ struct PrepTrainLaunch {
 static_assert(FLK_PREP_MAX_CLIPS <= 64, "one flip bit per clip");
 struct PrepTrainLaunchSampled : PrepTrainLaunch, PrepFrameTable {};
 static_assert(sizeof(PrepTrainLaunchSampled) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+struct PrepTrainLaunchToned : PrepTrainLaunchSampled, PrepToneTable {};
+static_assert(sizeof(PrepTrainLaunchToned) <= 4096, "the launch descriptor must fit the kernel-argument segment");
 
 // source columns under the box: [x0, x0 + span); the same fp32 sequence on the host (LDS sizing) and in the kernel
 __host__ __device__ inline void prep_train_span(float step_w, int j, int w, int Ws, int* x0, int* span) {
@@ -325,6 +372,8 @@ __global__ __launch_bounds__(256) void clip_prepare_train_kernel(const L p) {
   prep_train_span(c.step_w, c.j, c.w, c.Ws, &x0, &span);
   const uint8_t* frame = c.src + (long long)prep_source_frame(p, t, c.T) * c.pitch_t;
   const int nbytes = span * 3;
+  uint8_t* tone_lds = (uint8_t*)(R + cap * p.r_stride);        // toned launches only: 768 bytes more than the untoned ones ask for
+  prep_stage_tone(p, t, tone_lds);
   // ---- A: segment 2s + v = source row v (0 top, 1 bottom) of intermediate slot s; columns [x0, x0 + span) ----
   for (int k = threadIdx.x; k < 2 * ni * ndw; k += 256) {
     const int q = k / ndw, w = k - q * ndw;
@@ -334,7 +383,10 @@ __global__ __launch_bounds__(256) void clip_prepare_train_kernel(const L p) {
     const int mis = (int)((size_t)row & 3);
     if (w == 0) mis_of[q] = mis;
     // aligned dwords that hold at least one byte of the segment: never beyond the dword of its last byte
-    if (4 * w < mis + nbytes) seg[q * ndw + w] = *(const unsigned*)(row - mis + 4 * w);
+    if (4 * w < mis + nbytes) {
+      if constexpr (prep_toned<L>) seg[q * ndw + w] = prep_tone_dword(tone_lds, *(const unsigned*)(row - mis + 4 * w), w, mis);
+      else seg[q * ndw + w] = *(const unsigned*)(row - mis + 4 * w);
+    }
   }
   __syncthreads();
   if (direct) {
@@ -498,10 +550,11 @@ __global__ __launch_bounds__(256) void clip_prepare_train_kernel(const L p) {
 #endif
 
 // arguments already validated (api.cpp: flk_clip_prepare_train, flk_clip_prepare_sampled); everything here up to the launch is host
-// arithmetic.  frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one
-int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, float* out,
-                                  hipStream_t stream) {
-  PrepTrainLaunchSampled p;
+// arithmetic.  frame_idx: null for the plain launch, else the device table [nclip][T_out] of the sampled one; tone (with frame_idx
+// only): null, or the device tables [nclip][T_out][256][3] of the toned one
+int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const uint8_t* tone,
+                                  float* out, hipStream_t stream) {
+  PrepTrainLaunchToned p;
   int max_span = 1, max_T = 1, max_w = 1;
   p.flips = 0;
   for (int i = 0; i < a->nclip; ++i) {
@@ -534,12 +587,175 @@ int flk_clip_prepare_train_launch(const flk_prepare_args* a, const flk_prep_box*
   p.vec = ((size_t)p.out % 16 == 0) && a->out_clip_stride % 4 == 0 && (a->Wo * 3) % 4 == 0;
   for (int k = 0; k < 3; ++k) { p.mean[k] = a->mean[k]; p.std_[k] = a->std[k]; }
   const dim3 grid((unsigned)((a->Ho + rows - 1) / rows), (unsigned)max_T, (unsigned)a->nclip);
-  if (frame_idx) {
+  if (frame_idx && tone) {
     p.idx = frame_idx;
-    FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunchSampled>, grid, dim3(256), lds_of(rows), stream, p);
+    p.tone = tone;
+    FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunchToned>, grid, dim3(256), lds_of(rows) + kPrepToneBytes, stream, p);
+  } else if (frame_idx) {
+    p.idx = frame_idx;
+    FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunchSampled>, grid, dim3(256), lds_of(rows), stream,
+                      static_cast<const PrepTrainLaunchSampled&>(p));
   } else {
     FLK_LAUNCH_KERNEL(clip_prepare_train_kernel<PrepTrainLaunch>, grid, dim3(256), lds_of(rows), stream, static_cast<const PrepTrainLaunch&>(p));
   }
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The gradient of a toned preparation with respect to the flicker (flk_clip_prepare_grad).  The delivered value of an output pixel
+// is the resampling of tone-mapped source bytes; straight through the 8-bit rounding, its derivative with respect to the frame's
+// delta value is the SAME resampling of the per-byte slopes slope[k][t][byte][c] (flk_flicker_tone_slopes) -- J(oh, ow, c): the
+// indices, taps and lambdas of clip_prepare_train_kernel (prep_src; stage 1 within two source rows then along H; stage 2 on the box;
+// a flipped clip pairs g at column ow with J of column Wo - 1 - ow), every blend the fixed prep_blend sequence, no mean and no std.
+// The evaluation transform is the box (crop_i, crop_j, Ho, Wo) without a flip; a box of the output size makes stage 2 the identity
+// (lambda = 0 exactly: prep_blend(1, v, 0, .) = v), so it is not run.
+//   gdelta[k][t][c] = scale[k][t][c] * sum over (oh, ow) of g[k][t][oh][ow][c] * J(oh, ow, c)
+// Order (fixed; no atomics; independent of the grid, of the rows a workgroup takes and of the other clips of the call): ONE WAVE per
+// (clip, frame, output row) -- lane l adds the rounded products of columns l, l + 64, ... ascending from +0, each sum rounded on its
+// own; the 64 lanes fold by the shuffle tree 32, .., 1; partials[k][t][oh][c].  The finishing launch adds a (clip, frame, channel)'s
+// rows ascending from +0 and multiplies by scale once.  A clip's result is that of a call holding that clip alone.
+// Layout: workgroup = (kPrepGradRows output rows, frame, clip), 4 waves striding over the rows; the 3 KB of slopes of (clip, frame)
+// staged in LDS; the source bytes are read in place (all addressing clamped into [0, Hs) x [0, Ws) of the view, the frame index into
+// [0, T - 1]): 16 taps of 3 bytes per output pixel at most, neighbours sharing cache lines.
+namespace {
+
+constexpr int kPrepGradRows = 16;
+
+struct PrepGradLaunch : PrepFrameTable {
+  const float* slope;         // device fp32 [nclip][T_out][256][3]
+  const void* gx;             // device [nclip][T_out][Ho/2][Wo/2][16], fp32 or bf16
+  float* partials;            // device fp32 [nclip][T_out][Ho][3]
+  unsigned long long flips;
+  int Ho, Wo;
+  PrepTrainClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(sizeof(PrepGradLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+__device__ __forceinline__ float prep_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float prep_add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+template <typename TI> __device__ __forceinline__ float prep_grad_load(const void* gx, size_t i) {
+  if constexpr (sizeof(TI) == 4) return ((const float*)gx)[i];
+  else return __uint_as_float((unsigned)((const unsigned short*)gx)[i] << 16);
+}
+
+template <typename TI>
+__global__ __launch_bounds__(256) void clip_prepare_grad_kernel(const PrepGradLaunch p) {
+  __shared__ float S[768];
+  const PrepTrainClipDev& c = p.clip[blockIdx.z];
+  const int t = blockIdx.y, T_out = gridDim.y;
+  const size_t kt = (size_t)blockIdx.z * T_out + t;
+  for (int i = threadIdx.x; i < 768; i += 256) S[i] = p.slope[kt * 768 + i];
+  __syncthreads();
+  const uint8_t* frame = c.src + (long long)prep_source_frame(p, t, c.T) * c.pitch_t;
+  const bool flip = (p.flips >> blockIdx.z) & 1ull;
+  const bool direct = c.h == p.Ho && c.w == p.Wo;
+  const float step2_h = __fdiv_rn((float)c.h, (float)p.Ho), step2_w = __fdiv_rn((float)c.w, (float)p.Wo);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int oh_end = min((int)(blockIdx.x + 1) * kPrepGradRows, p.Ho);
+  // R[y, x][0..2] on slopes: the resized image at (i + y, j + x) of the box
+  auto resized = [&](int y, int x, float* r) {
+    const float sh = prep_src(c.step_h, c.i + y);
+    const int h0 = min((int)sh, c.Hs - 1), h1 = min(h0 + 1, c.Hs - 1);
+    const float lh = clamp01(sh - (float)h0);
+    const float sw = prep_src(c.step_w, c.j + x);
+    const int i0 = min((int)sw, c.Ws - 1), i1 = min(i0 + 1, c.Ws - 1);
+    const float lw = clamp01(sw - (float)i0);
+    const uint8_t* top = frame + (long long)h0 * c.pitch_h;
+    const uint8_t* bot = frame + (long long)h1 * c.pitch_h;
+    const float w0 = 1.f - lw, h0w = 1.f - lh;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const float a = prep_blend(w0, S[top[i0 * 3 + ch] * 3 + ch], lw, S[top[i1 * 3 + ch] * 3 + ch]);
+      const float b = prep_blend(w0, S[bot[i0 * 3 + ch] * 3 + ch], lw, S[bot[i1 * 3 + ch] * 3 + ch]);
+      r[ch] = prep_blend(h0w, a, lh, b);
+    }
+  };
+  for (int oh = blockIdx.x * kPrepGradRows + wave; oh < oh_end; oh += 4) {      // uniform over the wave
+    const float sy = prep_src(step2_h, oh);
+    const int y0 = direct ? oh : min((int)sy, c.h - 1), y1 = min(y0 + 1, c.h - 1);
+    const float lh2 = clamp01(sy - (float)y0);
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int ow = lane; ow < p.Wo; ow += 64) {
+      const int oc = flip ? p.Wo - 1 - ow : ow;        // the column whose value the forward stores at ow
+      float J[3];
+      if (direct) {
+        resized(y0, oc, J);
+      } else {
+        const float sx = prep_src(step2_w, oc);
+        const int b0 = min((int)sx, c.w - 1), b1 = min(b0 + 1, c.w - 1);
+        const float lw2 = clamp01(sx - (float)b0);
+        float r00[3], r01[3], r10[3], r11[3];
+        resized(y0, b0, r00);
+        resized(y0, b1, r01);
+        resized(y1, b0, r10);
+        resized(y1, b1, r11);
+        const float w0 = 1.f - lw2, h0w = 1.f - lh2;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+          J[ch] = prep_blend(h0w, prep_blend(w0, r00[ch], lw2, r01[ch]), lh2, prep_blend(w0, r10[ch], lw2, r11[ch]));
+      }
+      const size_t gi = (((kt * (p.Ho >> 1) + (oh >> 1)) * (p.Wo >> 1) + (ow >> 1)) << 4) + ((oh & 1) * 2 + (ow & 1)) * 3;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) acc[ch] = prep_add_rn(acc[ch], prep_mul_rn(prep_grad_load<TI>(p.gx, gi + ch), J[ch]));
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      float v = acc[ch];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) v = prep_add_rn(v, __shfl_down(v, o, 64));
+      if (lane == 0) p.partials[(kt * p.Ho + oh) * 3 + ch] = v;
+    }
+  }
+}
+
+// one thread per (clip, frame, channel): its rows ascending from +0, then the finishing factor
+__global__ __launch_bounds__(256) void clip_prepare_grad_finish(const float* partials, const float* scale, int n3, int Ho, float* gdelta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n3) return;
+  const size_t kt = i / 3;
+  const int ch = i - (int)kt * 3;
+  float s = 0.f;
+  for (int oh = 0; oh < Ho; ++oh) s = prep_add_rn(s, partials[(kt * Ho + oh) * 3 + ch]);
+  const float sc = scale[i];
+  gdelta[i] = sc == 0.f ? 0.f : prep_mul_rn(s, sc);       // a masked value is +0 whatever the sum is, as in grad_reduce_stage2
+}
+
+}  // namespace
+
+// arguments already validated (api.cpp: flk_clip_prepare_grad); boxes null: the evaluation transform's window, unflipped
+int flk_clip_prepare_grad_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
+                                 const float* scale, const void* gx_s2d, int dtype, float* gdelta, float* partials, hipStream_t stream) {
+  PrepGradLaunch p;
+  p.idx = frame_idx;
+  p.slope = slope; p.gx = gx_s2d; p.partials = partials;
+  p.flips = 0;
+  p.Ho = a->Ho; p.Wo = a->Wo;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_prep_clip& s = a->clips[i];
+    PrepTrainClipDev& d = p.clip[i];
+    d.src = s.src; d.pitch_t = s.pitch_t; d.pitch_h = (int)s.pitch_h;
+    d.T = s.T; d.Hs = s.Hs; d.Ws = s.Ws;
+    d.step_h = s.step_h; d.step_w = s.step_w;
+    if (boxes) {
+      d.i = boxes[i].i; d.j = boxes[i].j; d.h = boxes[i].h; d.w = boxes[i].w;
+      if (boxes[i].flip) p.flips |= 1ull << i;
+    } else {
+      d.i = s.crop_i; d.j = s.crop_j; d.h = a->Ho; d.w = a->Wo;
+    }
+  }
+  const dim3 grid((unsigned)((a->Ho + kPrepGradRows - 1) / kPrepGradRows), (unsigned)T_out, (unsigned)a->nclip);
+  if (dtype == FLK_BF16) FLK_LAUNCH_KERNEL(clip_prepare_grad_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
+  else FLK_LAUNCH_KERNEL(clip_prepare_grad_kernel<float>, grid, dim3(256), 0, stream, p);
+  const int n3 = a->nclip * T_out * 3;
+  FLK_LAUNCH_KERNEL(clip_prepare_grad_finish, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream, (const float*)partials, scale, n3, a->Ho,
+                    gdelta);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

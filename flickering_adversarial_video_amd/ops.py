@@ -585,6 +585,59 @@ def illum_grad_reduce(args, illum, gx_s2d, gdelta=None, scratch=None):
     return gdelta
 
 
+# ---- training on the delivered video: tone tables and their slopes (flk_clip_prepare_toned / flk_clip_prepare_grad take them) -------
+def tone_ramp(n, T, device="cuda"):
+    """the constant ramp clip the tone tables are exported from: uint8 ``[n,T,16,16,3]``, pixel p of every frame holding level p in its
+    three channels -- a clip that holds every (byte, channel) once per frame"""
+    ramp = torch.arange(256, dtype=torch.uint8, device=device).view(1, 1, 16, 16, 1)
+    return ramp.expand(int(n), int(T), 16, 16, 3).contiguous()
+
+
+def _check_ramp_args(what, args):
+    if (args.H, args.W) != (16, 16) or not args.x_is_u8 or not args.delta_per_clip or args.delta_per_line or args.delta_dense:
+        raise ValueError(f"{what}: args must describe the ramp clip (tone_ramp: uint8 [n,T,16,16,3]) with a per-clip delta [n,T,3]")
+
+
+def flicker_tone_tables(args, illum=None, out=None, dialect="torch"):
+    """The tone tables of a batch of clips: uint8 ``[n,T,256,3]``, ``tone[k,t,v,c]`` = the byte the export kernel of the pixel model
+    writes for source byte ``v`` of channel ``c`` under the delta row of frame ``t`` of clip ``k``.  No kernel of its own: the existing
+    export launch (``export_adversarial_u8`` in ``dialect``; with ``illum`` -- ``make_illum_args`` -- ``illum_export_u8``) run on the ramp,
+    so the table equals the export of a whole video bit for bit.  ``args``: ``make_export_apply_args(tone_ramp(n, T), delta_clip, ...)``
+    with the per-clip delta ``[n,T,3]`` of video time (``flicker_rows_gather`` / ``flicker_rows_mix``).  ``out``: the buffer to fill."""
+    _check_ramp_args("flicker_tone_tables", args)
+    B, T = args.B, args.T
+    dev = args._keepalive[0].device
+    if out is None:
+        out = torch.empty((B, T, 256, 3), dtype=torch.uint8, device=dev)
+    _check_tone("flicker_tone_tables", "out", out, torch.uint8, (B, T, 256, 3), dev)
+    frames = out.view(B, T, 16, 16, 3)
+    if illum is not None:
+        illum_export_u8(args, illum, out=frames)
+    else:
+        export_adversarial_u8(args, dialect, out=frames)
+    return out
+
+
+def flicker_tone_slopes(args, illum=None, slope=None, scale=None):
+    """``(slope, scale)`` of the tone tables of ``args`` (as for ``flicker_tone_tables``; flk_flicker_tone_slopes): ``slope`` fp32
+    ``[n,T,256,3]``, the straight-through derivative of the display value of source byte v with respect to the frame's delta value --
+    additive: 1 where the clamp to [lo, hi] is inactive, else 0; illumination (``illum``): the weight ``(d * N) * L`` of
+    ``illum_grad_reduce``, 0 where the lit value leaves [0,1] -- and ``scale`` fp32 ``[n,T,3]``, the finishing factors
+    (``adv_flag * inv_std[c]`` / ``adv_flag * out_mul[c]``; 0 where the delta value lies outside its clamp).  ``prepare_clips_grad``
+    resamples them."""
+    _check_ramp_args("flicker_tone_slopes", args)
+    B, T = args.B, args.T
+    dev = args._keepalive[0].device
+    if slope is None:
+        slope = torch.empty((B, T, 256, 3), dtype=torch.float32, device=dev)
+    if scale is None:
+        scale = torch.empty((B, T, 3), dtype=torch.float32, device=dev)
+    _check_tone("flicker_tone_slopes", "slope", slope, torch.float32, (B, T, 256, 3), dev)
+    _check_tone("flicker_tone_slopes", "scale", scale, torch.float32, (B, T, 3), dev)
+    check(load().flk_flicker_tone_slopes(C.byref(args), C.byref(illum) if illum is not None else None, ptr(slope), ptr(scale), stream_ptr()))
+    return slope, scale
+
+
 FLICKER_MAX_PERIOD = 682     # 3 * P values are what flk_perturb_reg_adam holds (256 threads x 8)
 
 
@@ -959,7 +1012,7 @@ def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, 
 
 
 def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
-                  flips=None, frame_idx=None):
+                  flips=None, frame_idx=None, tone=None):
     """Raw decoded frames -> normalised clips on the device (flk_clip_prepare): the reference's evaluation transform
     ``ToTensorVideo -> ResizeVideo(im_scale) -> CenterCropVideo(input_size) -> NormalizeVideo(mean, std)`` (dataset.py:84-123) in one
     kernel launch per ``FLK_PREP_MAX_CLIPS`` clips.
@@ -980,8 +1033,20 @@ def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, 
     clip k is prepared from ``frames[k][frame_idx[k][t]]``: bitwise what the call without ``frame_idx`` gives on ``frames[k][frame_idx[k]]``,
     without that gathered copy.  Every index is checked against its video here, before anything is launched; the table is uploaded once
     per call as one int32 tensor.  ``out`` rows are ``[T_out,Ho,Wo,3]``; ``boxes`` / ``flips``, ``out`` / ``out_offset``, views and long
-    lists work as without it."""
+    lists work as without it.
+    ``tone`` (with ``frame_idx``): prepare the clips of the DELIVERED videos (flk_clip_prepare_toned) -- a CUDA uint8 tensor
+    ``[N,T_out,256,3]``, ``tone[k,t,v,c]`` the byte that source byte ``v`` of channel ``c`` is stored as in output frame ``t`` of clip ``k``
+    (``flicker_tone_tables``): bitwise the call without ``tone`` on the videos after their 8-bit export, which are never written."""
     plan, out, n = prepare_clips_plan(frames, out, out_offset, im_scale, input_size, mean, std, rule, boxes, flips, frame_idx)
+    if tone is not None:
+        if frame_idx is None:
+            raise ValueError("prepare_clips: tone needs frame_idx (the tables belong to the frames of whole videos)")
+        T_out = plan[0]._frame_idx.shape[1]
+        _check_tone("prepare_clips", "tone", tone, torch.uint8, (n, T_out, 256, 3), out.device)
+        for j, a in enumerate(plan):
+            check(load().flk_clip_prepare_toned(C.byref(a), a._boxes, ptr(a._frame_idx), T_out, ptr(tone[j * FLK_PREP_MAX_CLIPS:]), ptr(out),
+                                                stream_ptr()))
+        return out[out_offset:out_offset + n]
     for a in plan:
         if a._frame_idx is not None:
             check(load().flk_clip_prepare_sampled(C.byref(a), a._boxes, ptr(a._frame_idx), a._frame_idx.shape[1], ptr(out), stream_ptr()))
@@ -992,15 +1057,60 @@ def prepare_clips(frames, out=None, out_offset=0, im_scale=128, input_size=112, 
     return out[out_offset:out_offset + n]
 
 
+def _check_tone(what, name, t, dtype, shape, device):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous() and t.device == device):
+        desc = f"{tuple(t.shape)} {t.dtype} {t.device}" if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what}: {name} must be a contiguous {dtype} tensor {list(shape)} on {device}, got {desc}")
+
+
+def prepare_clips_grad(frames, gx_s2d, slope, scale, im_scale=128, input_size=112, rule="sizes", boxes=None, flips=None, frame_idx=None, gdelta=None,
+                       scratch=None):
+    """d(loss)/d(delta_clip) through the resampling of a toned preparation (flk_clip_prepare_grad): fp32 ``[N,T_out,3]``.  ``frames``,
+    ``im_scale`` / ``input_size`` / ``rule``, ``boxes`` / ``flips`` and ``frame_idx`` (required) exactly as the ``prepare_clips(tone=)`` call
+    whose clips went into the network; ``gx_s2d``: the input gradient ``[N,T_out,Ho/2,Wo/2,16]`` (fp32 or bf16, the layout
+    ``perturb_grad_reduce`` reads); ``slope`` fp32 ``[N,T_out,256,3]`` and ``scale`` fp32 ``[N,T_out,3]`` from ``flicker_tone_slopes``.
+    ``gdelta``: the result's buffer; ``scratch``: fp32, ``flk_clip_prepare_grad_scratch_bytes`` / 4 elements per launch.  One fixed
+    summation order: repeats are bitwise equal and a clip's rows are those of a call with that clip alone."""
+    if frame_idx is None:
+        raise ValueError("prepare_clips_grad: frame_idx is required (the clips are cut from whole videos)")
+    if not torch.is_tensor(gx_s2d) or not gx_s2d.is_cuda:
+        raise ValueError("prepare_clips_grad: gx_s2d must be a CUDA tensor")
+    dev = gx_s2d.device
+    Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
+    if Ho % 2 or Wo % 2:
+        raise ValueError(f"prepare_clips_grad: the output size must be even (the folded gradient layout), got {Ho} x {Wo}")
+    plan, _, n = prepare_clips_plan(frames, None, 0, im_scale, (Ho, Wo), DEFAULT_MEAN, DEFAULT_STD, rule, boxes, flips, frame_idx, need_out=False)
+    T_out = plan[0]._frame_idx.shape[1]
+    if gx_s2d.dtype not in (torch.float32, torch.bfloat16) or tuple(gx_s2d.shape) != (n, T_out, Ho // 2, Wo // 2, 16) or not gx_s2d.is_contiguous():
+        raise ValueError(f"prepare_clips_grad: gx_s2d must be a contiguous fp32 or bf16 tensor [{n},{T_out},{Ho // 2},{Wo // 2},16], got "
+                         f"{tuple(gx_s2d.shape)} {gx_s2d.dtype}")
+    _check_tone("prepare_clips_grad", "slope", slope, torch.float32, (n, T_out, 256, 3), dev)
+    _check_tone("prepare_clips_grad", "scale", scale, torch.float32, (n, T_out, 3), dev)
+    if gdelta is None:
+        gdelta = torch.empty((n, T_out, 3), dtype=torch.float32, device=dev)
+    _check_tone("prepare_clips_grad", "gdelta", gdelta, torch.float32, (n, T_out, 3), dev)
+    need = int(load().flk_clip_prepare_grad_scratch_bytes(min(n, FLK_PREP_MAX_CLIPS), T_out, Ho)) // 4
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=dev)
+    if not (torch.is_tensor(scratch) and scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.device == dev and scratch.numel() >= need):
+        raise ValueError(f"prepare_clips_grad: scratch must be a contiguous fp32 tensor of at least {need} elements on {dev}")
+    for j, a in enumerate(plan):
+        f = j * FLK_PREP_MAX_CLIPS
+        check(load().flk_clip_prepare_grad(C.byref(a), a._boxes, ptr(a._frame_idx), T_out, ptr(slope[f:]), ptr(scale[f:]), ptr(gx_s2d[f:]),
+                                           dtype_code(gx_s2d.dtype), ptr(gdelta[f:]), ptr(scratch), stream_ptr()))
+    return gdelta
+
+
 _prep_geometry = functools.lru_cache(maxsize=512)(prepare_geometry)
 
 
 def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=112, mean=DEFAULT_MEAN, std=DEFAULT_STD, rule="sizes", boxes=None,
-                       flips=None, frame_idx=None):
+                       flips=None, frame_idx=None, need_out=True):
     """the host half of ``prepare_clips``: ``([flk_prepare_args per launch], out, N)`` -- every check and every descriptor, no GPU call.
     (A caller that repeats one preparation, such as a timing loop, launches the arguments itself.)  With ``boxes`` / ``flips`` each
     launch's ``_boxes`` is its flk_prep_box array (None otherwise); with ``frame_idx`` its ``_frame_idx`` is its rows of the uploaded int32
-    table (None otherwise) -- the upload is the one thing here that touches the device, after every check has passed."""
+    table (None otherwise) -- the upload is the one thing here that touches the device, after every check has passed.
+    ``need_out=False`` (``prepare_clips_grad``, which writes no clips): no output buffer is made or checked, ``out`` comes back as given."""
     if (boxes is None) != (flips is None):
         raise ValueError("prepare_clips: boxes and flips go together, got only " + ("boxes" if flips is None else "flips"))
     Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
@@ -1062,9 +1172,9 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
         for k, (b, d) in enumerate(zip(boxes, descs)):
             if len(b) != 4 or min(b[2], b[3]) < 1 or min(b[0], b[1]) < 0 or b[0] + b[2] > d.Hr or b[1] + b[3] > d.Wr:
                 raise ValueError(f"prepare_clips: clip {k}: box {tuple(b)} is not (i, j, h, w) inside the resized image {d.Hr} x {d.Wr}")
-    if out is None:
+    if out is None and need_out:
         out = torch.empty((out_offset + n, T, Ho, Wo, 3), dtype=torch.float32, device=keep[0].device)
-    if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 5
+    if need_out and (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.float32 or not out.is_contiguous() or out.dim() != 5
             or tuple(out.shape[1:]) != (T, Ho, Wo, 3) or out_offset < 0 or out.shape[0] < out_offset + n):
         desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
         raise ValueError(f"prepare_clips: out must be a contiguous CUDA float32 tensor [>= {out_offset + n},{T},{Ho},{Wo},3], got {desc}")

@@ -519,7 +519,7 @@ class FlickerVideoResNet:
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
                  im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb"):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False):
         from .i3d_engine import check_optimizer
         # flicker_model "illumination": the flicker LIGHTS THE SCENE instead of being added to the displayed pixels -- a pixel of linear
         # light L becomes L * (1 + m), then goes through the camera's response and 8 bits (videoresnet_spec.illum_tables(response); the
@@ -535,6 +535,20 @@ class FlickerVideoResNet:
         # anything touches the device
         self.P = check_flicker_time(flicker_time, flicker_period, sample_length, attack_type, per_clip, capture)
         self.flicker_time, self.video_time = flicker_time, flicker_time == "video"
+        # train_delivered: the attack is trained on the DELIVERED video at its native resolution (``step_videos``; whole-video loaders and
+        # ``fit_single_video_attack`` on a whole video route through it).  The flicker is laid over the raw frames in 8 bits as
+        # ``export_video`` lays it (per frame a byte -> byte tone table, ops.flicker_tone_tables), the stored bytes are resized and cropped
+        # (ops.prepare_clips(tone=)) and scored clean -- the chain ``evaluate_videos(quantise="video")`` scores, bit for bit -- and the
+        # gradient goes back through the resampling (ops.prepare_clips_grad).  ``quantise_train`` is implied.  A per-line flicker (a
+        # capture channel with a readout) is not a per-frame byte map; dense and per-clip perturbations belong to their clips
+        self.train_delivered = bool(train_delivered)
+        if self.train_delivered:
+            if not self.video_time or attack_type != "flickering" or per_clip:
+                raise ValueError("train_delivered needs flicker_time='video' and the flickering attack with one shared perturbation (not per_clip, "
+                                 "not L12): the delivered video carries the flicker on its own frame numbers")
+            if capture is not None and capture.readout is not None:
+                raise ValueError("train_delivered: a capture channel with a readout (rolling shutter) gives every line of a frame its own "
+                                 "flicker, which is not a per-frame byte map")
         # capture (flicker_time "video"; a videoresnet_spec.CaptureChannel): the attack is trained OVER THE AIR.  Every adversarial training
         # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
         # of rows a camera records (ops.flicker_rows_mix in the gather's place); the step folds its gradient through the same tables
@@ -735,11 +749,19 @@ class FlickerVideoResNet:
         split's (videoresnet_spec.split_sampling) and, on an engine built with ``augment``, the training transform with one
         ``(box, flip)`` per clip as ``prepare(train=True)`` draws them.  The tables are kept, one int64 ``[num_samples, T]`` per video,
         on ``last_sampling``; boxes and flips on ``last_augment``."""
+        clips, rows, boxes, flips = self._draw_video_clips(videos, train, num_samples, "prepare_videos")
+        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                 rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=rows)
+
+    def _draw_video_clips(self, videos, train, num_samples, who):
+        """the host half of ``prepare_videos`` (and of ``step_videos``): the frame tables, boxes and flips of ``len(videos) * num_samples``
+        clips drawn from the engine's generators, kept on ``last_sampling`` / ``last_augment`` and (video time) set as the batch's frame
+        numbers -> ``(clips, rows, boxes, flips)``: the video of every clip, the tables stacked ``[n,T]``, the boxes / flips or None"""
         videos = list(videos) if isinstance(videos, (list, tuple)) else None
         if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
-            raise ValueError("prepare_videos: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+            raise ValueError(f"{who}: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
         if int(num_samples) < 1:
-            raise ValueError(f"prepare_videos: num_samples must be >= 1, got {num_samples!r}")
+            raise ValueError(f"{who}: num_samples must be >= 1, got {num_samples!r}")
         kw = split_sampling(self.sampling, self.T, train)
         tables = [sample_frame_indices(int(v.shape[0]), num_samples=int(num_samples), rng=self._samp_rng, **kw) for v in videos]
         self.last_sampling = tables
@@ -756,8 +778,7 @@ class FlickerVideoResNet:
                 boxes.append(tuple(box))
                 flips.append(flip)
             self.last_augment = {"boxes": boxes, "flips": flips}
-        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                 rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=np.concatenate(tables))
+        return clips, np.concatenate(tables), boxes, flips
 
     def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None, capture=None, capture_draws=1):
         """``VideoLearnerAdversarial.evaluate(num_samples)`` (model.py:1227-1317) on whole videos resident on the device: every video is
@@ -984,10 +1005,52 @@ class FlickerVideoResNet:
             return inputs
         return None
 
-    def step(self, x, labels, criterion, lr=1e-3, update=True):
+    def step_videos(self, videos, labels, criterion, lr=1e-3, update=True, train=True, _drawn=None):
+        """one iteration on the DELIVERED videos (an engine built with ``train_delivered``): ``videos`` is a list of V = B /
+        clips_per_video whole raw uint8 videos ``[N_k,H_k,W_k,3]`` on the device, of any length and resolution.  The frame tables, boxes
+        and flips are drawn exactly as ``prepare_videos(videos, train, clips_per_video)`` draws them (same generators, same order, kept
+        on ``last_sampling`` / ``last_augment``); the frame numbers are set; the per-clip perturbation of those frames is gathered (or
+        mixed through a capture channel drawn per video) and turned into tone tables by the export kernel of the engine's pixel model
+        on a ramp clip; the toned preparation writes the clips of the flickered, 8-bit videos into the engine's fp32 buffer; the CLEAN
+        forward scores them -- the logits are bit for bit those of ``prepare_clips(export_video(v, phase), ...)`` -- and the backward's
+        input gradient goes through the slopes of the tone tables and the resampling (ops.prepare_clips_grad) to the per-clip gradient
+        the existing row fold and update kernels take.  ``train=False``: the test split's sampling and the evaluation transform (what
+        ``evaluate_videos(quantise="video")`` scores).  ``StepResult`` as ``step``'s."""
+        if not self.train_delivered:
+            raise ValueError("step_videos: an engine built with train_delivered=True only")
+        if criterion.attack_type != self.attack_type:
+            raise ValueError(f"criterion.attack_type {criterion.attack_type!r} != engine attack_type {self.attack_type!r}")
+        if _drawn is None:
+            _drawn = self._draw_video_clips(videos, train, self.clips_per_video, "step_videos")
+        if len(_drawn[0]) != self.B:
+            raise ValueError(f"step_videos: {len(_drawn[0]) // self.clips_per_video} videos of {self.clips_per_video} clips, the engine takes {self.V}")
+        return self.step(None, labels, criterion, lr=lr, update=update, _delivered=_drawn)
+
+    def _forward_delivered(self, drawn, capture):
+        """``step_videos``' forward: tone tables of the batch's frames, the toned preparation, the clean forward.  Returns the apply
+        arguments of the ramp: the step takes the slopes from the same"""
+        clips, rows, boxes, flips = drawn
+        pm, dev = self.pert_model, self._logits.device
+        if getattr(self, "_tone", None) is None:
+            self._ramp = ops.tone_ramp(self.B, self.T, dev)
+            self._tone = torch.empty((self.B, self.T, 256, 3), dtype=torch.uint8, device=dev)
+            self._slope = torch.empty((self.B, self.T, 256, 3), dtype=torch.float32, device=dev)
+            self._scale = torch.empty((self.B, self.T, 3), dtype=torch.float32, device=dev)
+            self._pg_scratch = torch.empty(max(1, ops.load().flk_clip_prepare_grad_scratch_bytes(min(self.B, ops.FLK_PREP_MAX_CLIPS), self.T, self.H) // 4),
+                                           dtype=torch.float32, device=dev)
+        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < self.B:
+            self._prep_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.float32, device=dev)
+        ta = pm.export_args(self._ramp, True, shift_p="draw", capture=capture)      # the per-clip delta of this batch's frame numbers
+        ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=self._tone)
+        x = ops.prepare_clips(clips, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                              boxes=boxes, flips=flips, frame_idx=rows, tone=self._tone)
+        self._forward(x, False)
+        return ta
+
+    def step(self, x, labels, criterion, lr=1e-3, update=True, _delivered=None):
         """one iteration of fit_single_video_attack (model.py:1073-1101): forward, Losses, backward, torch-Adam step.
         The kernels write into one of ``RESULT_SLOTS`` result slots (valid for the next RESULT_SLOTS - 1 iterations);
-        ``loss`` / ``argmax`` are derived on first access (i3d_engine.StepResult)."""
+        ``loss`` / ``argmax`` are derived on first access (i3d_engine.StepResult).  (``_delivered``: ``step_videos``' clips.)"""
         from .i3d_engine import RESULT_SLOTS, StepResult
         if criterion.attack_type != self.attack_type:
             raise ValueError(f"criterion.attack_type {criterion.attack_type!r} != engine attack_type {self.attack_type!r}")
@@ -1014,7 +1077,7 @@ class FlickerVideoResNet:
         red, sm, pc = slot["payload"], slot["sm"], slot["pc"]
         self._red = red
         cap = "draw" if self.capture is not None else None     # one capture channel per video, fresh every step
-        a = self._forward(x, True, capture=cap)
+        a = self._forward(x, True, capture=cap) if _delivered is None else self._forward_delivered(_delivered, cap)
         gbatch = V * self.world
         if G > 1:
             criterion.adv_video(labels, self._logits, gbatch, G, self.video_reduce, out=(sm, self._dl, pc, slot["vl"]))
@@ -1022,7 +1085,19 @@ class FlickerVideoResNet:
             criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
         self.net.backward(self._dl, self._gx)
         n = 3 * self.P                                          # (clip time: P == T)
-        if self.video_time and a.delta_per_line:
+        if _delivered is not None:
+            # the delivered video: the slopes of this step's tone tables, resampled as the clips were, give the per-clip gradient
+            # [B,T,3] with its finishing factors; its frames fold onto their rows as on any video-time step
+            ops.flicker_tone_slopes(a, self.pert_model.illum if self.illumination else None, self._slope, self._scale)
+            ops.prepare_clips_grad(_delivered[0], self._gx, self._slope, self._scale, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                   rule=self.resize_rule, boxes=_delivered[2], flips=_delivered[3], frame_idx=_delivered[1], gdelta=self._g_clip,
+                                   scratch=self._pg_scratch)
+            if cap is None:
+                ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
+            else:
+                ops.flicker_rows_mix_grad(self._g_clip, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
+                                          out=red[:n].view(self.P, 3))
+        elif self.video_time and a.delta_per_line:
             # rolling shutter: the per-line gradient [B,T,H,3] (summed over w only; adv_flag, 1/std and the clamp mask applied per line),
             # then the transpose of the lines mix the forward ran, on the same tables, to the same [P,3] payload
             if getattr(self, "_g_lines", None) is None:
@@ -1157,7 +1232,11 @@ class FlickerVideoResNet:
         whole uint8 video ``[N,H,W,3]`` (or a one-element list of it) whose G test-split clips are attacked; ``target`` holds one class per
         video and ``prob_clean_input``, ``is_adversarial``, ``max_prob`` and ``correct_cls_prob`` are the video's (aggregated logits)."""
         G = self.clips_per_video
-        video = self._whole_video(inputs) if G > 1 else None
+        video = self._whole_video(inputs) if (G > 1 or self.train_delivered) else None
+        delivered = self.train_delivered and video is not None      # one whole video on a train_delivered engine: every step is step_videos
+        if self.train_delivered and video is None:
+            raise ValueError("fit_single_video_attack: an engine built with train_delivered attacks one whole uint8 video [N,H,W,3] (clips at "
+                             "the engine's size have no native resolution: build the engine with quantise_train instead)")
         if video is not None:
             # one whole video: its G test-split clips (uniform offsets, no shift, no jitter -- the clips evaluate_videos(num_samples=G)
             # scores) are cut once, into a buffer of their own, and kept for the whole attack
@@ -1182,7 +1261,7 @@ class FlickerVideoResNet:
                 step = 0
             if new_chance == max_restarts:
                 break
-            r = self.step(inputs, target, criterion, lr=lr)
+            r = self.step_videos([video], target, criterion, lr=lr, train=False) if delivered else self.step(inputs, target, criterion, lr=lr)
             adv_class = r["argmax"]
             is_adversarial = bool((adv_class == target_class_id).all()) if targeted_attack else not bool(adv_class.equal(target))
             isadv_l.append(is_adversarial)
@@ -1202,7 +1281,13 @@ class FlickerVideoResNet:
                "max_prob": maxp_l, "correct_cls_prob": corr_l, "restarts": new_chance}
         if self.video_time:                                  # the perturbations above have flicker_period rows, not sample_length
             res.update(flicker_time=self.flicker_time, flicker_period=self.P)
-        if export_u8:
+        if export_u8 and delivered:
+            # the delivered video itself: flickered whole at its own resolution, its test-split clips cut from the stored bytes
+            frames = self.export_video(video)
+            ql = self.logits(ops.prepare_clips([frames] * G, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W),
+                                               rule=self.resize_rule, frame_idx=np.concatenate(self.last_sampling)), False)
+            res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
+        elif export_u8:
             frames = self.adversarial_frames(inputs)
             ql = self.logits(frames, False)
             res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
@@ -1235,7 +1320,18 @@ class FlickerVideoResNet:
             xdt = None
             for inputs, target, *_ in data_loaders[phase]:
                 whole = isinstance(inputs, (list, tuple))           # whole videos: sampled and prepared in one launch
-                if whole:
+                if self.train_delivered and not whole:
+                    raise ValueError("train_an_epoch: an engine built with train_delivered takes loaders of whole uint8 videos (lists of "
+                                     "[N,H,W,3]); for clips at the engine's size build it with quantise_train instead")
+                drawn = None
+                if whole and self.train_delivered:
+                    # the delivered chain: ONE draw of tables / boxes / flips serves the clean reference (the untoned preparation) and the step
+                    if getattr(self, "_clean_buf", None) is None or self._clean_buf.shape[0] < len(inputs) * G:
+                        self._clean_buf = torch.empty((max(len(inputs) * G, self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
+                    drawn = self._draw_video_clips(inputs, phase == "train", G, "train_an_epoch")
+                    inputs = ops.prepare_clips(drawn[0], out=self._clean_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                               boxes=drawn[2], flips=drawn[3], frame_idx=drawn[1])
+                elif whole:
                     if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < len(inputs) * G:
                         self._prep_buf = torch.empty((max(len(inputs) * G, self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
                     inputs = self.prepare_videos(inputs, train=(phase == "train"), num_samples=G, out=self._prep_buf)
@@ -1246,7 +1342,10 @@ class FlickerVideoResNet:
                                      "(the training transform applies to raw uint8 frames)")
                 inputs = self._prepared(inputs, train=augmenting)   # raw-size uint8 frames: this batch's clips, in the reused fp32 buffer
                 clean = self.logits(inputs, False).clone()
-                r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
+                if drawn is not None:
+                    r = self.step_videos(None, target, criterion, lr=lr, update=(phase == "train"), train=(phase == "train"), _drawn=drawn)
+                else:
+                    r = self.step(inputs, target, criterion, lr=lr, update=(phase == "train"))
                 adv_logits = self._logits
                 if G > 1:
                     clean, adv_logits = self.video_logits(clean), r["video_logits"]
@@ -1462,7 +1561,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
                  process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb"):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1478,6 +1577,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
                          clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
                          flicker_time=flicker_time, flicker_period=flicker_period, capture=capture, flicker_model=flicker_model,
-                         response=response)
+                         response=response, train_delivered=train_delivered)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -782,6 +782,151 @@ def illum_grad_host(x, delta, tables, gx, *, dclip=0.0, adv_flag=1.0, shift_x=0,
     return (g, mag, n) if bound else g
 
 
+# ---- training on the delivered video at its native resolution: tone tables, their slopes, the gradient through the resampling ------
+def tone_ramp_host(n, T):
+    """uint8 [n,T,16,16,3]: pixel p of every frame holds level p in its three channels (ops.tone_ramp on the host)"""
+    ramp = np.arange(256, dtype=np.uint8).reshape(1, 1, 16, 16, 1)
+    return np.ascontiguousarray(np.broadcast_to(ramp, (int(n), int(T), 16, 16, 3)))
+
+
+def additive_bounds():
+    """(lo, hi) of the torch dialect's additive clamp: the largest normalised value of byte 0 and the smallest of byte 255 over the
+    channels (model.py:72-75) -- what ``Perturbation`` clamps the perturbed clip to"""
+    mean, std = np.array(DEFAULT_MEAN), np.array(DEFAULT_STD)
+    return float(np.max((0.0 - mean) / std)), float(np.min((1 - mean) / std))
+
+
+def _tone_delta(delta_clip):
+    d = np.asarray(delta_clip)
+    if d.dtype != np.float32 or d.ndim != 3 or d.shape[2] != 3:
+        raise ValueError(f"tone tables: the per-clip delta must be float32 [n,T,3], got {d.shape} {d.dtype}")
+    return d
+
+
+def tone_tables_host(delta_clip, tables=None, *, dclip=0.0, adv_flag=1.0, lo=None, hi=None, dclip_clip=None):
+    """``ops.flicker_tone_tables`` restated: uint8 [n,T,256,3], the byte source byte v of channel c is stored as under the delta row of
+    frame t of clip k -- the host export of the pixel model (``ops.export_adversarial_u8_host`` in the torch dialect; with ``tables`` =
+    ``illum_tables(...)``, ``illum_export_host``) on the ramp clip.  ``delta_clip``: float32 [n,T,3] (flicker_rows / flicker_rows_mix);
+    ``lo`` / ``hi``: the additive clamp (default ``additive_bounds``)."""
+    d = _tone_delta(delta_clip)
+    n, T = d.shape[:2]
+    ramp = tone_ramp_host(n, T)
+    if tables is not None:
+        q = illum_export_host(ramp, d, tables, dclip=dclip, adv_flag=adv_flag, dclip_clip=dclip_clip)
+    else:
+        from .ops import export_adversarial_u8_host
+        lo0, hi0 = additive_bounds()
+        q = export_adversarial_u8_host(ramp, d, dialect="torch", dclip=dclip, adv_flag=adv_flag, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
+                                       lo=lo0 if lo is None else lo, hi=hi0 if hi is None else hi, dclip_clip=dclip_clip, x_lut=u8_decode_table())
+    return np.ascontiguousarray(q.reshape(n, T, 256, 3))
+
+
+def tone_slopes_host(delta_clip, tables=None, *, dclip=0.0, adv_flag=1.0, lo=None, hi=None, dclip_clip=None, out_mul=None):
+    """flk_flicker_tone_slopes restated in numpy float32: ``(slope [n,T,256,3], scale [n,T,3])``.  Additive (``tables`` None): slope = 1
+    where ``lo <= x_lut[v,c] + adv_flag * clamp(delta) / std <= hi``, scale = ``adv_flag / std``; illumination: slope = the weight
+    ``(d * N) * L`` of ``illum_grad_host``, 0 where the lit value leaves [0,1], scale = ``adv_flag * out_mul``.  scale is 0 where the
+    delta value lies outside its clamp."""
+    f32 = np.float32
+    d = _tone_delta(delta_clip)
+    n, T = d.shape[:2]
+    dc = np.asarray(dclip_clip, f32).reshape(n, 1, 1) if dclip_clip is not None else f32(dclip)
+    clamped = dclip_clip is not None or dclip > 0
+    with np.errstate(invalid="ignore"):
+        inside = ((d >= -dc) & (d <= dc)) if clamped else np.ones(d.shape, bool)
+    if tables is not None:
+        dec, enc = _illum_tables_checked(tables)
+        ramp = tone_ramp_host(n, T)
+        s, _, _ = _illum_factor(ramp, d, dclip, dclip_clip, adv_flag, 0, 0, False)
+        _, p, L, dd = _illum_display(ramp, s, dec, enc)
+        w = ((dd * f32(enc.shape[0] - 1)).astype(f32) * L).astype(f32)
+        with np.errstate(invalid="ignore"):
+            slope = np.where((p >= 0) & (p <= 1), w, f32(0.0)).astype(f32).reshape(n, T, 256, 3)
+        mul = illum_out_affine()[0] if out_mul is None else np.asarray(out_mul, f32)
+        factor = (f32(adv_flag) * mul).astype(f32)
+    else:
+        inv_std = np.array([1.0 / s for s in DEFAULT_STD]).astype(f32)
+        lo0, hi0 = additive_bounds()
+        lo, hi = f32(lo0 if lo is None else lo), f32(hi0 if hi is None else hi)
+        m = np.fmin(np.fmax(d, -dc), dc) if clamped else d
+        p = (m * inv_std).astype(f32)
+        u = (u8_decode_table()[None, None] + (f32(adv_flag) * p).astype(f32)[:, :, None, :]).astype(f32)
+        slope = ((u >= lo) & (u <= hi)).astype(f32)
+        factor = (f32(adv_flag) * inv_std).astype(f32)
+    scale = np.where(inside, np.broadcast_to(factor, d.shape), f32(0.0)).astype(f32)
+    return np.ascontiguousarray(slope), np.ascontiguousarray(scale)
+
+
+def _prep_axis(step, d, n_in):
+    """source indices and the weight of the second one along an axis, as csrc/prepare.hip evaluates them in float32: src =
+    max(fma(step, d + 0.5, -0.5), 0), i0 = min(int(src), n_in - 1), i1 = min(i0 + 1, n_in - 1), lambda = clamp(src - i0, 0, 1).  (The
+    fused multiply-subtract is formed in float64, where it is exact, and rounded once.)"""
+    d = np.asarray(d, dtype=np.int64)
+    s = (np.float64(np.float32(step)) * (d.astype(np.float64) + 0.5) - 0.5).astype(np.float32)
+    s = np.maximum(s, np.float32(0.0))
+    i0 = np.minimum(s.astype(np.int64), n_in - 1)
+    i1 = np.minimum(i0 + 1, n_in - 1)
+    lam = np.clip((s - i0.astype(np.float32)).astype(np.float32), np.float32(0.0), np.float32(1.0))
+    return i0, i1, lam
+
+
+def _blend_axis(v, i0, i1, lam, axis):
+    """(1 - lambda) * v[i0] + lambda * v[i1] along ``axis``: the weights are the kernels' float32 values (1 - lambda rounded to float32
+    as there), the products and the sum float64"""
+    w1 = lam.astype(np.float64)
+    w0 = (np.float32(1.0) - lam).astype(np.float32).astype(np.float64)
+    shape = [1] * v.ndim
+    shape[axis] = -1
+    return w0.reshape(shape) * np.take(v, i0, axis=axis) + w1.reshape(shape) * np.take(v, i1, axis=axis)
+
+
+def prepare_resample_host(values, box=None, flip=False, im_scale=128, input_size=112, rule="sizes"):
+    """The resampling of csrc/prepare.hip on per-pixel VALUES, in float64: ``values`` [Hs,Ws,3] (any real numbers: decoded pixels, or
+    slopes) -> [Ho,Wo,3].  The source indices and the interpolation weights are the kernels' own float32 numbers; the blends --
+    along W within the two source rows, then along H; then, for a ``box = (i, j, h, w)`` of the resized image that is not of the
+    output size, the second bilinear stage -- are float64.  ``box`` None: the evaluation transform's crop window.  ``flip``: mirrored
+    along W.  No mean, no std: the map is linear in ``values``."""
+    v = np.asarray(values, dtype=np.float64)
+    if v.ndim != 3 or v.shape[2] != 3:
+        raise ValueError(f"prepare_resample_host: values must be [Hs,Ws,3], got {v.shape}")
+    Hs, Ws = v.shape[:2]
+    Ho, Wo = _pair(input_size)
+    Hr, Wr, step_h, step_w, ci, cj = prepare_geometry(Hs, Ws, im_scale, input_size, rule)
+    i, j, h, w = (ci, cj, Ho, Wo) if box is None else (int(b) for b in box)
+    if h < 1 or w < 1 or i < 0 or j < 0 or i + h > Hr or j + w > Wr:
+        raise ValueError(f"prepare_resample_host: box ({i},{j})+{h}x{w} outside the resized image {Hr} x {Wr}")
+    c0, c1, lw = _prep_axis(step_w, j + np.arange(w), Ws)
+    r0, r1, lh = _prep_axis(step_h, i + np.arange(h), Hs)
+    R = _blend_axis(_blend_axis(v, c0, c1, lw, 1), r0, r1, lh, 0)               # [h,w,3]: the resized image under the box
+    if (h, w) != (Ho, Wo):
+        step2_h, step2_w = np.float32(h) / np.float32(Ho), np.float32(w) / np.float32(Wo)
+        x0, x1, lw2 = _prep_axis(step2_w, np.arange(Wo), w)
+        y0, y1, lh2 = _prep_axis(step2_h, np.arange(Ho), h)
+        R = _blend_axis(_blend_axis(R, x0, x1, lw2, 1), y0, y1, lh2, 0)
+    return np.ascontiguousarray(R[:, ::-1] if flip else R)
+
+
+def prepare_grad_host(video, frame_idx, gx, slope, scale, box=None, flip=False, im_scale=128, input_size=112, rule="sizes", bound=False):
+    """flk_clip_prepare_grad restated in float64 for ONE clip: ``video`` uint8 [N,Hs,Ws,3], ``frame_idx`` the clip's T_out frame numbers,
+    ``gx`` = d(loss)/d(prepared clip) [T_out,Ho,Wo,3] (unfolded), ``slope`` [T_out,256,3] and ``scale`` [T_out,3] of the clip
+    (``tone_slopes_host``).  Returns float64 [T_out,3]: ``scale[t,c] * sum over (oh, ow) of gx * J``, J = ``prepare_resample_host`` of
+    the frame's per-byte slopes.  ``bound``: also the sum of the magnitudes of each output's terms (times |scale|) and their number."""
+    video, gx = np.asarray(video), np.asarray(gx, dtype=np.float64)
+    if video.dtype != np.uint8 or video.ndim != 4 or video.shape[3] != 3:
+        raise ValueError(f"prepare_grad_host: video must be uint8 [N,Hs,Ws,3], got {video.shape} {video.dtype}")
+    idx = np.asarray(frame_idx, dtype=np.int64).reshape(-1)
+    Ho, Wo = _pair(input_size)
+    slope, scale = np.asarray(slope, dtype=np.float64), np.asarray(scale, dtype=np.float64)
+    if gx.shape != (idx.size, Ho, Wo, 3) or slope.shape != (idx.size, 256, 3) or scale.shape != (idx.size, 3):
+        raise ValueError(f"prepare_grad_host: gx [{idx.size},{Ho},{Wo},3], slope [{idx.size},256,3], scale [{idx.size},3]; got {gx.shape}, "
+                         f"{slope.shape}, {scale.shape}")
+    g, mag = np.zeros((idx.size, 3)), np.zeros((idx.size, 3))
+    for t, f in enumerate(idx):
+        J = prepare_resample_host(slope[t][video[f], np.arange(3)], box, flip, im_scale, input_size, rule)
+        terms = gx[t] * J
+        g[t], mag[t] = terms.sum((0, 1)) * scale[t], np.abs(terms).sum((0, 1)) * np.abs(scale[t])
+    return (g, mag, Ho * Wo) if bound else g
+
+
 def _capture_range(name, v, lo_bound, hi_bound):
     pair = (v, v) if np.ndim(v) == 0 else tuple(v)
     if len(pair) != 2:

@@ -553,6 +553,55 @@ int flk_clip_prepare_train(const flk_prepare_args* a, const flk_prep_box* boxes 
 int flk_clip_prepare_sampled(const flk_prepare_args* a, const flk_prep_box* boxes /* HOST [nclip], or NULL: the evaluation transform */,
                              const int32_t* frame_idx /* DEVICE [nclip][T_out] */, int T_out, float* out, void* stream);
 
+/* Training on the DELIVERED video at its native resolution.  A per-frame flicker is uniform over a frame, so the delivered frame -- the
+ * raw frame after the 8-bit export of the flicker (flk_adv_export_u8 / flk_illum_export_u8) -- is the raw frame through a byte -> byte
+ * map per (clip, frame, channel), the TONE TABLE: tone[k][t][v][c], uint8 [nclip][T_out][256][3], the byte the export writes for source
+ * byte v of channel c under the delta row of output frame t of clip k.  It is made by the export launch itself on a constant ramp clip
+ * (uint8 [n][T][16][16][3], pixel p holding level p in its three channels) with the per-clip delta [n][T][3] of video time
+ * (flk_flicker_rows_gather / flk_flicker_rows_mix), so it equals the export of a whole video bit for bit; there is no kernel of its own.
+ *
+ * flk_clip_prepare_toned: flk_clip_prepare_sampled on the delivered video, which is never written.  The workgroup of (clip k, output
+ *   frame t) stages tone[k][t] (768 bytes) in LDS and maps every source byte as it stages the row segments; everything after that is
+ *   the sampled kernels' own statements, so the result is bit for bit what flk_clip_prepare_sampled writes for the exported video:
+ *   both transforms (two-stage and box-of-the-output-size paths, flips), clips of differing resolution, tables that repeat frames.
+ *   With the identity table (tone[v] = v) it is bit for bit the untoned launch.  tone: DEVICE, any alignment.
+ *   FLK_EINVAL (before any GPU call): everything flk_clip_prepare_sampled refuses, a null tone.
+ *
+ * flk_flicker_tone_slopes: the straight-through derivative of the display value of source byte v with respect to the frame's delta
+ *   value, before its finishing factors -- slope fp32 [B][T][256][3] -- and those factors, scale fp32 [B][T][3].  `a` is the apply
+ *   description of the ramp: uint8 through x_lut, delta_per_clip (delta [B][T][3]), no rolls; m NULL: the additive model.
+ *     additive:      slope = 1 where lo <= u <= hi, u = x_lut[v][c] + adv_flag * p (p the clamped delta value times inv_std[c]: the
+ *                    mask expression of flk_perturb_grad_reduce), else 0;            scale = adv_flag * inv_std[c]
+ *     illumination:  slope = (d * N) * L of flk_illum_grad_reduce (two rounded products), 0 where p leaves [0,1];
+ *                                                                                    scale = adv_flag * out_mul[c]
+ *   scale is 0 where the delta value lies outside its clamp (dclip / dclip_dev).  One launch.
+ *   FLK_EINVAL (before any GPU call): null a / slope / scale / x / delta, an fp32 clip or a null x_lut, delta_per_line, delta_dense,
+ *   center = 1, delta_per_clip = 0, a roll; with m what flk_illum_grad_reduce refuses of m.
+ *
+ * flk_clip_prepare_grad: d(loss)/d(delta_clip) through the resampling of a toned preparation,
+ *     gdelta[k][t][c] = scale[k][t][c] * sum over output pixels (oh, ow) of g(k,t,oh,ow,c) * J(oh,ow,c)        fp32 [nclip][T_out][3]
+ *   J: the forward's own resampling run on slopes instead of pixel values -- the same source indices, taps and lambdas, the one- or
+ *   two-stage blend (a box of the output size skips stage 2), every blend the fixed sequence fma(w0, v0, w1 * v1), every tap read
+ *   through slope[k][t][byte][c]; no mean, no std; a flipped clip pairs g at column ow with J of column Wo - 1 - ow.  boxes NULL: the
+ *   evaluation transform (the box (crop_i, crop_j, Ho, Wo), no flip).  g: gx_s2d, the layout flk_perturb_grad_reduce reads for fold_t 1,
+ *   [nclip][T_out][Ho/2][Wo/2][16] fp32 or bf16, channel ((oh & 1) * 2 + (ow & 1)) * 3 + c; row k belongs to clip k of the call
+ *   (out_clip_offset is not used).  Every product g * J and every sum is rounded to fp32 on its own, in ONE order that does not depend
+ *   on the grid, on the rows a workgroup takes or on the other clips: one wave per (clip, frame, output row), lane l adds columns l,
+ *   l + 64, ... ascending from +0, the lanes fold by the shuffle tree 32 .. 1 (partials [nclip][T_out][Ho][3]); a finishing launch adds
+ *   the rows ascending from +0 and multiplies by scale (a zero scale writes +0 whatever the sum is).  No atomics: repeats are bitwise equal, and a clip's result is that of a call
+ *   holding that clip alone.  partials: flk_clip_prepare_grad_scratch_bytes(nclip, T_out, Ho) of caller scratch.  Two launches.
+ *   FLK_EINVAL (before any launch): null pointers, gx_s2d not 16-byte aligned, a bad dtype, odd Ho / Wo, and everything
+ *   flk_clip_prepare_toned refuses of a / boxes / frame_idx / T_out (out_clip_stride as there). */
+int flk_clip_prepare_toned(const flk_prepare_args* a, const flk_prep_box* boxes /* HOST [nclip], or NULL: the evaluation transform */,
+                           const int32_t* frame_idx /* DEVICE [nclip][T_out] */, int T_out, const uint8_t* tone /* DEVICE [nclip][T_out][256][3] */,
+                           float* out, void* stream);
+int flk_flicker_tone_slopes(const flk_apply_args* a, const flk_illum_args* m /* NULL: additive */, float* slope /* [B,T,256,3] */,
+                            float* scale /* [B,T,3] */, void* stream);
+int64_t flk_clip_prepare_grad_scratch_bytes(int nclip, int T_out, int Ho);
+int flk_clip_prepare_grad(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
+                          const float* scale, const void* gx_s2d, int dtype, float* gdelta /* fp32 [nclip,T_out,3] */, float* partials,
+                          void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

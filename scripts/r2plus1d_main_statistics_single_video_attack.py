@@ -70,13 +70,13 @@ def run_whole_videos(a):
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
                                  clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
                                  flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response)
+                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered)
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
     xd, yd = [torch.from_numpy(v).cuda() for v in videos], torch.from_numpy(labels).cuda()
     # train=True: fit_many_videos iterates the dataset's TRAINING loader (model.py:832); with the default flags the two splits sample alike
-    if G > 1:        # whole videos go through: fit_single_video_attack cuts each one's G evaluation clips
+    if G > 1 or a.train_delivered:        # whole videos go through: fit_single_video_attack cuts each one's G evaluation clips
         clips = ((xd[i], yd[i:i + 1], names[i]) for i in range(len(videos)))
     else:
         clips = ((learner.prepare_videos([xd[i]], train=True).clone(), yd[i:i + 1], names[i]) for i in range(len(videos)))
@@ -184,6 +184,10 @@ def main():
     ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
                     "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
                     "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
+    ap.add_argument("--train-delivered", action="store_true", help="whole-video files, --flicker-time video, --batch 1: optimise each attack on "
+                    "the DELIVERED video at its native resolution -- every step flickers the raw frames in 8 bits as the whole-video export "
+                    "does, resizes and crops the stored bytes and scores them clean, and takes the gradient back through the resampling.  "
+                    "Files of clips at the engine's size: use --quantise-train")
     ap.add_argument("--flicker-time", default="clip", choices=["clip", "video"], help="which row of the perturbation a frame carries.  clip: row t "
                     "for frame t of every clip.  video: row (frame number - phase) mod period, the frame numbers being those the clip was cut "
                     "at in its video -- the flicker the whole-video export lays over the video, so the loop trains on what is delivered "
@@ -203,6 +207,9 @@ def main():
     if a.eval_quantised == "video" and (not vs.is_video_file(a.videos_npz) or a.batch > 1 or a.attack_type != "flickering"):
         raise ValueError("--eval-quantised video needs a whole-video .npz file, --batch 1 and the flickering attack (one flicker per video, laid "
                          "over all its frames)")
+    if a.train_delivered and (not vs.is_video_file(a.videos_npz) or a.batch > 1 or a.flicker_time != "video"):
+        raise ValueError("--train-delivered needs a whole-video .npz file, --batch 1 and --flicker-time video: clips have no native resolution "
+                         "to flicker at -- for files of clips at the engine's size use --quantise-train, which trains on the same stored bytes")
     if a.clips_per_video < 1:
         raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
     if a.clips_per_video > 1 and not vs.is_video_file(a.videos_npz):

@@ -167,7 +167,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
                                  flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response)
+                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered)
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -315,6 +315,10 @@ def main():
     ap.add_argument("--quantise-train", action="store_true", help="optimise the attack on the STORED video: every adversarial forward of the "
                     "training loop sees the clip its 8-bit frames decode to (the round trip runs inside the apply kernel, straight-through "
                     "gradient), so the loop's verdicts are the stored video's.  Combines with --save-adversarial-u8 / --eval-quantised")
+    ap.add_argument("--train-delivered", action="store_true", help="whole-video files, --flicker-time video: optimise the attack on the "
+                    "DELIVERED video at its native resolution -- every training step flickers the raw frames in 8 bits as the whole-video "
+                    "export does, resizes and crops the stored bytes and scores them clean (the chain --eval-quantised video scores), and "
+                    "takes the gradient back through the resampling.  Files of clips at the engine's size: use --quantise-train")
     ap.add_argument("--flicker-time", default="clip", choices=["clip", "video"], help="which row of the perturbation a frame carries.  clip: row t "
                     "for frame t of every clip.  video: row (frame number - phase) mod period, the frame numbers being those the clip was cut "
                     "at in its video -- the flicker the whole-video export lays over the video, so the loop trains on what is delivered "
@@ -335,6 +339,11 @@ def main():
         raise ValueError("--eval-quantised video needs whole-video .npz files: a file of clips holds no whole video to flicker")
     if (a.eval_quantised == "video" or (a.save_adversarial_u8 and vs.is_video_file(a.val_npz))) and a.attack_type != "flickering":
         raise ValueError("whole videos take the flickering perturbation only (a dense perturbation belongs to the clip's size)")
+    if a.train_delivered and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
+        raise ValueError("--train-delivered needs whole-video .npz files: clips have no native resolution to flicker at -- for files of "
+                         "clips at the engine's size use --quantise-train, which trains on the same stored bytes")
+    if a.train_delivered and a.flicker_time != "video":
+        raise ValueError("--train-delivered needs --flicker-time video: the delivered video carries the flicker on its own frame numbers")
     if a.clips_per_video < 1:
         raise ValueError(f"--clips-per-video must be >= 1, got {a.clips_per_video}")
     if a.clips_per_video > 1 and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
