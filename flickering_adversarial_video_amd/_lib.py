@@ -100,7 +100,21 @@ class PrepBox(C.Structure):
     _fields_ = [("i", C.c_int), ("j", C.c_int), ("h", C.c_int), ("w", C.c_int), ("flip", C.c_int)]
 
 
+FLK_CODEC_444, FLK_CODEC_420 = 444, 420
+
+
+class CodecClip(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("T", C.c_int), ("Hs", C.c_int), ("Ws", C.c_int), ("pitch_t", C.c_int64), ("pitch_h", C.c_int64),
+                ("dst", C.c_void_p), ("dst_pitch_t", C.c_int64), ("dst_pitch_h", C.c_int64)]
+
+
+class CodecArgs(C.Structure):
+    _fields_ = [("nclip", C.c_int), ("quality", C.c_int), ("subsampling", C.c_int), ("clips", C.POINTER(CodecClip))]
+
+
 _SIGS = {
+    "flk_codec_tables": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "flk_codec_roundtrip_u8": (C.c_int, [C.POINTER(CodecArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "flk_version": (C.c_int, []),
     "flk_last_error": (C.c_char_p, []),
     "flk_conv_weights_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

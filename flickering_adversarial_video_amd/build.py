@@ -7,7 +7,7 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libflicker_hip.so")
-SOURCES = ["api.cpp", "conv_igemm.hip", "conv_pc.hip", "pool.hip", "head.hip", "attack.hip", "illum.hip", "stem_grad.hip", "stem_fwd.hip", "prepare.hip", "net.cpp", "comm.cpp"]
+SOURCES = ["api.cpp", "conv_igemm.hip", "conv_pc.hip", "pool.hip", "head.hip", "attack.hip", "illum.hip", "stem_grad.hip", "stem_fwd.hip", "prepare.hip", "codec.hip", "net.cpp", "comm.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-x", "hip"]
 

@@ -221,6 +221,49 @@ extern "C" int flk_clip_prepare_toned(const flk_prepare_args* a, const flk_prep_
   return flk_clip_prepare_launch(a, frame_idx, T_out, tone, out, (hipStream_t)stream);
 }
 
+// The codec round trip (csrc/codec.hip): every argument is checked here, on the host, before anything touches the device.
+void flk_codec_tables_host(int quality, int32_t* qluma, int32_t* qchroma);
+int flk_codec_roundtrip_launch(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
+                               hipStream_t stream);
+
+extern "C" int flk_codec_tables(int quality, int32_t* qluma, int32_t* qchroma) {
+  FLK_REQUIRE(qluma && qchroma, "flk_codec_tables: null table");
+  FLK_REQUIRE(quality >= 1 && quality <= 100, "flk_codec_tables: quality %d outside 1..100", quality);
+  flk_codec_tables_host(quality, qluma, qchroma);
+  return FLK_OK;
+}
+
+extern "C" int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
+                                      void* stream) {
+  const char* fn = "flk_codec_roundtrip_u8";
+  FLK_REQUIRE(a, "%s: null argument", fn);
+  FLK_REQUIRE(a->clips, "%s: null clip list", fn);
+  FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", fn, a->nclip, FLK_PREP_MAX_CLIPS);
+  FLK_REQUIRE(a->quality >= 1 && a->quality <= 100, "%s: quality %d outside 1..100", fn, a->quality);
+  FLK_REQUIRE(a->subsampling == FLK_CODEC_444 || a->subsampling == FLK_CODEC_420, "%s: subsampling %d is neither 444 nor 420", fn, a->subsampling);
+  FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "%s: T_out %d outside 1..65535", fn, T_out);
+  const int M = a->subsampling == FLK_CODEC_420 ? 16 : 8;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& c = a->clips[i];
+    FLK_REQUIRE(c.src && c.dst, "%s: clip %d: null source or destination", fn, i);
+    FLK_REQUIRE(c.T > 0 && c.Hs > 0 && c.Ws > 0, "%s: clip %d: source size %d x %d x %d", fn, i, c.T, c.Hs, c.Ws);
+    FLK_REQUIRE(c.Hs <= 0x3fffffff && c.Ws <= 0x1fffffff, "%s: clip %d: frame size %d x %d", fn, i, c.Hs, c.Ws);
+    FLK_REQUIRE(c.pitch_h >= (int64_t)c.Ws * 3 && c.pitch_h <= 0x7fffffff && c.pitch_t > 0,
+                "%s: clip %d: source pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i, (long long)c.pitch_t,
+                (long long)c.pitch_h);
+    FLK_REQUIRE(c.dst_pitch_h >= (int64_t)c.Ws * 3 && c.dst_pitch_h <= 0x7fffffff && c.dst_pitch_t > 0,
+                "%s: clip %d: destination pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i,
+                (long long)c.dst_pitch_t, (long long)c.dst_pitch_h);
+    FLK_REQUIRE((const uint8_t*)c.dst != c.src, "%s: clip %d: the destination is the source (an MCU reads pixels other workgroups write)", fn, i);
+    FLK_REQUIRE(frame_idx || T_out <= c.T, "%s: clip %d: T_out %d above its %d frames (no frame_idx)", fn, i, T_out, c.T);
+    if (stats) {
+      const int64_t Hp = ((int64_t)c.Hs + M - 1) / M * M, Wp = ((int64_t)c.Ws + M - 1) / M * M;
+      FLK_REQUIRE(Hp * Wp <= 5000000, "%s: clip %d: stats on a frame of %lld padded pixels (more than 5000000)", fn, i, (long long)(Hp * Wp));
+    }
+  }
+  return flk_codec_roundtrip_launch(a, frame_idx, T_out, tone, stats, (hipStream_t)stream);
+}
+
 // The gradient of a toned preparation (csrc/prepare.hip) and the slope tables it resamples (csrc/attack.hip, csrc/illum.hip)
 int flk_clip_prepare_grad_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
                                  const float* scale, const void* gx_s2d, int dtype, float* gdelta, float* partials, hipStream_t stream);

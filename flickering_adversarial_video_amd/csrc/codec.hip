@@ -1,0 +1,338 @@
+// Lossy intra-frame compression of the delivered video: a JPEG-style round trip (colour transform, chroma subsampling, 8x8 DCT,
+// quantisation and back) in ONE kernel, defined in integers only.  The definition is videoresnet_spec.codec_roundtrip_host (DESIGN.md
+// 10.8); this file performs the same integer operations, so the two agree bit for bit:
+//   tone     (optional) byte -> byte table of the output frame, tone[k][t][v][c]: the 8-bit export of a per-frame flicker
+//   colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+//            Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16;   Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+//   pad      to whole MCUs (8x8, or 16x16 with 4:2:0) by repeating the last column and row
+//   4:2:0    Cb, Cr: (a + b + c + d + 1 + (x & 1)) >> 2 over each 2x2 cell, x the output column
+//   DCT      value - 128; the "slow integer" forward transform (13-bit constants; rows, then columns; 8 x the DCT);
+//            level = sign * ((|f| + 4 Q) / (8 Q))  (half away from zero);  back: level * Q, columns then rows, + 128, clamp 0..255
+//   4:2:0    chroma repeated 2x2
+//   colour   R = Y + ((91881 Cr' + 32768) >> 16);  G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16);  B = Y + ((116130 Cb' + 32768) >> 16)
+//            (Cb' = Cb - 128, Cr' = Cr - 128), clamp 0..255; crop
+// Every intermediate fits an int32 (bounds: DESIGN.md 10.8).  Plain int32 VALU arithmetic, no MFMA: exactness is the contract.
+//
+// Mapping: workgroup = (tile of kTW columns x TH rows of one output frame of one clip), 192 threads.  TH = 32 (4:4:4) or 64 (4:2:0):
+// 192 8x8 blocks per full tile either way, ONE THREAD PER BLOCK -- the 64 values of a block stay in that thread's registers through
+// both passes of both transforms, so the transform needs no LDS transposes and no barriers.
+//   A  the source row segments under the tile into LDS as aligned dwords (the misalignment of a row kept per row, as
+//      clip_prepare_kernel does), and the frame's tone table
+//   B  bytes (through the tone) -> Y, Cb, Cr byte planes in LDS, padded by replication, chroma averaged for 4:2:0
+//   C  per block: forward DCT, quantise, (stats), dequantise, inverse DCT; the reconstructed bytes back into the block's place
+//   D  planes -> RGB bytes laid out in LDS as the destination rows lie in memory, then stored: whole aligned dwords inside a row
+//      segment, single bytes at its head and tail, so no byte outside the destination view is written
+// A block outside the padded image is not computed.  Every output byte is a pure function of its MCU: the result does not depend on
+// the tile or the grid.  Stats are integer sums (LDS and global integer atomics): exact in any order.  No allocation, no
+// synchronisation with the host.
+#include "flk_internal.h"
+
+namespace {
+
+constexpr int kTW = 128;                       // tile width in pixels
+constexpr int kSW = (kTW * 3 + 8) / 4;         // dwords per staged row: the segment plus up to 3 bytes of misalignment, whole dwords
+constexpr int kCodecThreads = 192;
+
+struct CodecClipDev {                          // 56 bytes; FLK_PREP_MAX_CLIPS of them travel by value in the kernel argument
+  const uint8_t* src;
+  uint8_t* dst;
+  long long pitch_t, dpitch_t;                 // bytes between frames
+  int pitch_h, dpitch_h;                       // bytes between rows
+  int T, Hs, Ws;
+  int ntx;                                     // tiles along W
+};
+struct CodecLaunch {
+  const int* idx;                              // device int32 [nclip][gridDim.y] or null: source frame of every output frame
+  const uint8_t* tone;                         // device uint8 [nclip][gridDim.y][256][3] or null
+  int* stats;                                  // device int32 [nclip][gridDim.y][2] or null (zeroed by the host entry)
+  int pad_;
+  unsigned short q[2][64];                     // luma, chroma
+  CodecClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(sizeof(CodecLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+constexpr int F_0_298 = 2446, F_0_390 = 3196, F_0_541 = 4433, F_0_765 = 6270, F_0_899 = 7373, F_1_175 = 9633;
+constexpr int F_1_501 = 12299, F_1_847 = 15137, F_1_961 = 16069, F_2_053 = 16819, F_2_562 = 20995, F_3_072 = 25172;
+
+__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+__device__ __forceinline__ int clamp255(int x) { return min(max(x, 0), 255); }
+
+// one 8-point forward pass in place; UP: the two sums are multiplied by 4 (pass 1), else descaled by 2 bits (pass 2)
+template <bool UP, int ODD>
+__device__ __forceinline__ void fdct8(int& d0, int& d1, int& d2, int& d3, int& d4, int& d5, int& d6, int& d7) {
+  int t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6, t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  if (UP) { d0 = (t10 + t11) * 4; d4 = (t10 - t11) * 4; }
+  else { d0 = descale(t10 + t11, 2); d4 = descale(t10 - t11, 2); }
+  int z1 = (t12 + t13) * F_0_541;
+  d2 = descale(z1 + t13 * F_0_765, ODD);
+  d6 = descale(z1 - t12 * F_1_847, ODD);
+  z1 = t4 + t7;
+  int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
+  const int z5 = (z3 + z4) * F_1_175;
+  t4 *= F_0_298; t5 *= F_2_053; t6 *= F_3_072; t7 *= F_1_501;
+  z1 = -z1 * F_0_899; z2 = -z2 * F_2_562; z3 = -z3 * F_1_961 + z5; z4 = -z4 * F_0_390 + z5;
+  d7 = descale(t4 + z1 + z3, ODD);
+  d5 = descale(t5 + z2 + z4, ODD);
+  d3 = descale(t6 + z2 + z3, ODD);
+  d1 = descale(t7 + z1 + z4, ODD);
+}
+
+// one 8-point inverse pass in place
+template <int SHIFT>
+__device__ __forceinline__ void idct8(int& c0, int& c1, int& c2, int& c3, int& c4, int& c5, int& c6, int& c7) {
+  int z2 = c2, z3 = c6;
+  int z1 = (z2 + z3) * F_0_541;
+  int t2 = z1 - z3 * F_1_847, t3 = z1 + z2 * F_0_765;
+  int t0 = (c0 + c4) * 8192, t1 = (c0 - c4) * 8192;
+  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+  t0 = c7; t1 = c5; t2 = c3; t3 = c1;
+  z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
+  int z4 = t1 + t3;
+  const int z5 = (z3 + z4) * F_1_175;
+  t0 *= F_0_298; t1 *= F_2_053; t2 *= F_3_072; t3 *= F_1_501;
+  z1 = -z1 * F_0_899; z2 = -z2 * F_2_562; z3 = -z3 * F_1_961 + z5; z4 = -z4 * F_0_390 + z5;
+  t0 += z1 + z3; t1 += z2 + z4; t2 += z2 + z3; t3 += z1 + z4;
+  c0 = descale(t10 + t3, SHIFT); c7 = descale(t10 - t3, SHIFT);
+  c1 = descale(t11 + t2, SHIFT); c6 = descale(t11 - t2, SHIFT);
+  c2 = descale(t12 + t1, SHIFT); c5 = descale(t12 - t1, SHIFT);
+  c3 = descale(t13 + t0, SHIFT); c4 = descale(t13 - t0, SHIFT);
+}
+
+// an 8x8 block of a byte plane (8-byte aligned rows `pitch` bytes apart) through the transform pair, in place.  qt / rq: the block's
+// quantisation table and the reciprocals of 8 Q (a first guess of the quotient only: the quotient is corrected to the exact one)
+__device__ __forceinline__ void codec_block(uint8_t* blk, int pitch, const int* qt, const float* rq, int& nz, int& mag) {
+  int v[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint2 w = *(const uint2*)(blk + r * pitch);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[r * 8 + k] = (int)((w.x >> (8 * k)) & 255u) - 128;
+      v[r * 8 + 4 + k] = (int)((w.y >> (8 * k)) & 255u) - 128;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) fdct8<true, 11>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) fdct8<false, 15>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int Q = qt[k], d = Q << 3, f = v[k];
+    const int n = abs(f) + (d >> 1);                   // < 2^15: exact in fp32
+    int lev = (int)((float)n * rq[k]);                 // within 1 of n / d
+    const int rem = n - lev * d;
+    lev += rem >= d ? 1 : (rem < 0 ? -1 : 0);          // the exact quotient
+    nz += lev != 0;
+    mag += lev;
+    v[k] = (f < 0 ? -lev : lev) * Q;
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) idct8<11>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    idct8<18>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+    uint2 w = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      w.x |= (unsigned)clamp255(v[r * 8 + k] + 128) << (8 * k);
+      w.y |= (unsigned)clamp255(v[r * 8 + 4 + k] + 128) << (8 * k);
+    }
+    *(uint2*)(blk + r * pitch) = w;
+  }
+}
+
+__device__ __forceinline__ void rgb_to_ycc(int R, int G, int B, int& Y, int& Cb, int& Cr) {
+  Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16;
+  Cb = (-11059 * R - 21709 * G + 32768 * B + 8388608 + 32767) >> 16;
+  Cr = (32768 * R - 27439 * G - 5329 * B + 8388608 + 32767) >> 16;
+}
+
+template <bool S420>
+__global__ __launch_bounds__(kCodecThreads) void codec_roundtrip_kernel(const CodecLaunch p) {
+  constexpr int TH = S420 ? 64 : 32;                   // tile rows
+  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;      // the chroma planes of a tile
+  __shared__ unsigned stage[TH * kSW];                 // source row segments (A, B), then the destination's (D)
+  __shared__ __attribute__((aligned(8))) uint8_t Yp[TH * kTW];
+  __shared__ __attribute__((aligned(8))) uint8_t Cbp[CH * CW];
+  __shared__ __attribute__((aligned(8))) uint8_t Crp[CH * CW];
+  __shared__ uint8_t tone_lds[768];
+  __shared__ int mis_of[TH];
+  __shared__ int qt[2][64];
+  __shared__ float rq[2][64];
+  __shared__ int red[2];
+
+  const CodecClipDev& c = p.clip[blockIdx.z];
+  constexpr int M = S420 ? 16 : 8;
+  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
+  const int nty = (Hpad + TH - 1) / TH;
+  if ((int)blockIdx.x >= c.ntx * nty) return;          // uniform over the workgroup: a clip smaller than the largest of the launch
+  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
+  const int y0 = ty * TH, x0 = tx * kTW;
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const size_t kt = (size_t)blockIdx.z * gridDim.y + t;
+  const int fsrc = p.idx ? min(max(p.idx[kt], 0), c.T - 1) : min(t, c.T - 1);
+  const uint8_t* frame = c.src + (long long)fsrc * c.pitch_t;
+  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);        // the tile's part of the image (>= 1 each)
+  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);         // ... of the padded image: whole MCUs
+  const int nbytes = ncols * 3;
+
+  // ---- A: tables, then the source row segments as aligned dwords ----
+  if (tid < 128) {
+    const int Q = p.q[tid >> 6][tid & 63];
+    qt[tid >> 6][tid & 63] = Q;
+    rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
+  }
+  if (tid < 2) red[tid] = 0;
+  if (p.tone) {
+    const uint8_t* g = p.tone + kt * 768;
+    for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
+  }
+  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+    const int r = k / kSW, w = k - r * kSW;
+    const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
+    const int mis = (int)((size_t)row & 3);
+    if (w == 0) mis_of[r] = mis;
+    if (4 * w < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * w);      // never beyond the dword of the segment's last byte
+  }
+  __syncthreads();
+
+  // ---- B: bytes -> planes over the padded part of the tile (the last column / row repeated) ----
+  const uint8_t* sb = (const uint8_t*)stage;
+  const bool toned = p.tone != nullptr;
+  auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
+    const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
+    const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
+    int R = px[0], G = px[1], B = px[2];
+    if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
+    rgb_to_ycc(R, G, B, Y, Cb, Cr);
+  };
+  if constexpr (S420) {
+    const int qc = pcol >> 1;
+    for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
+      const int r2 = k / qc, c2 = k - r2 * qc;
+      int sb_ = 0, sr_ = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        int Y, Cb, Cr;
+        ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
+        Yp[(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
+        sb_ += Cb; sr_ += Cr;
+      }
+      const int bias = 1 + (c2 & 1);                  // x0 / 2 is even: the tile's column parity is the plane's
+      Cbp[r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
+      Crp[r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
+    }
+  } else {
+    for (int k = tid; k < prow * pcol; k += kCodecThreads) {
+      const int r = k / pcol, col = k - r * pcol;
+      int Y, Cb, Cr;
+      ycc(r, col, Y, Cb, Cr);
+      Yp[r * kTW + col] = (uint8_t)Y;
+      Cbp[r * CW + col] = (uint8_t)Cb;
+      Crp[r * CW + col] = (uint8_t)Cr;
+    }
+  }
+  __syncthreads();
+
+  // ---- C: one block per thread: luma blocks first, then Cb, then Cr ----
+  {
+    constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
+    const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
+    int nz = 0, mag = 0;
+    for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
+      if (b < NBY) {
+        const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
+        if (by * 8 < prow && bx * 8 < pcol) codec_block(Yp + by * 8 * kTW + bx * 8, kTW, qt[0], rq[0], nz, mag);
+      } else {
+        const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
+        const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
+        if (by * 8 < cprow && bx * 8 < cpcol) codec_block((pl ? Crp : Cbp) + by * 8 * CW + bx * 8, CW, qt[1], rq[1], nz, mag);
+      }
+    }
+    if (p.stats && (nz | mag)) {
+      atomicAdd(&red[0], nz);
+      atomicAdd(&red[1], mag);
+    }
+  }
+  __syncthreads();
+  if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
+
+  // ---- D: planes -> RGB bytes laid out as the destination rows lie in memory, then stored ----
+  uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
+  uint8_t* ob = (uint8_t*)stage;
+  for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
+    const int r = k / ncols, col = k - r * ncols;
+    const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
+    const int Y = Yp[r * kTW + col];
+    const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
+    const int cb = (int)Cbp[ci] - 128, cr = (int)Crp[ci] - 128;
+    uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
+    o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
+    o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+    o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
+  }
+  __syncthreads();
+  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+    const int r = k / kSW, w = k - r * kSW;
+    uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
+    const int dm = (int)((size_t)row & 3);
+    const int lo = dm, hi = dm + nbytes;               // the segment's bytes within the aligned run that starts at row - dm
+    if (4 * w >= hi || 4 * w + 4 <= lo) continue;
+    if (4 * w >= lo && 4 * w + 4 <= hi) {
+      *(unsigned*)(row - dm + 4 * w) = stage[k];
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * w + b >= lo && 4 * w + b < hi) (row - dm)[4 * w + b] = ob[k * 4 + b];
+    }
+  }
+}
+
+}  // namespace
+
+// the two quantisation tables at `quality` (1..100): ITU T.81 Annex K under the IJG scaling rule, row-major
+void flk_codec_tables_host(int quality, int32_t* qluma, int32_t* qchroma) {
+  static const unsigned char base_l[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+                                           14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+                                           49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99};
+  static const unsigned char base_c[32] = {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99,
+                                           24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99};
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  for (int k = 0; k < 64; ++k) {
+    const int l = (base_l[k] * s + 50) / 100, ch = ((k < 32 ? base_c[k] : 99) * s + 50) / 100;
+    qluma[k] = l < 1 ? 1 : l > 255 ? 255 : l;
+    qchroma[k] = ch < 1 ? 1 : ch > 255 ? 255 : ch;
+  }
+}
+
+// arguments already validated (api.cpp: flk_codec_roundtrip_u8); everything here up to the launch is host arithmetic
+int flk_codec_roundtrip_launch(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
+                               hipStream_t stream) {
+  CodecLaunch p;
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
+  p.idx = frame_idx; p.tone = tone; p.stats = stats; p.pad_ = 0;
+  int32_t ql[64], qc[64];
+  flk_codec_tables_host(a->quality, ql, qc);
+  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
+  long long max_tiles = 1;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& s = a->clips[i];
+    CodecClipDev& d = p.clip[i];
+    d.src = s.src; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
+    d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
+    d.T = s.T; d.Hs = s.Hs; d.Ws = s.Ws;
+    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
+    d.ntx = (int)((Wpad + kTW - 1) / kTW);
+    const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
+    if (tiles > max_tiles) max_tiles = tiles;
+  }
+  FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_u8: a frame of more than 2^31 tiles");
+  if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_out * 2 * sizeof(int32_t), stream));
+  const dim3 grid((unsigned)max_tiles, (unsigned)T_out, (unsigned)a->nclip);
+  if (s420) FLK_LAUNCH_KERNEL(codec_roundtrip_kernel<true>, grid, dim3(kCodecThreads), 0, stream, p);
+  else FLK_LAUNCH_KERNEL(codec_roundtrip_kernel<false>, grid, dim3(kCodecThreads), 0, stream, p);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}

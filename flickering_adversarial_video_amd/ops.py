@@ -1199,6 +1199,108 @@ def prepare_clips_plan(frames, out=None, out_offset=0, im_scale=128, input_size=
     return plan, out, n
 
 
+def codec_tables(quality):
+    """flk_codec_tables: the luma and chroma quantisation tables at ``quality`` as the library makes them, int32 ``[64]`` each (host)"""
+    ql, qc = (C.c_int32 * 64)(), (C.c_int32 * 64)()
+    check(load().flk_codec_tables(int(quality), ql, qc))
+    return np.asarray(ql[:], np.int32), np.asarray(qc[:], np.int32)
+
+
+def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=False):
+    """The delivered videos after lossy intra-frame compression (flk_codec_roundtrip_u8; ``videoresnet_spec.codec_roundtrip_host`` is
+    its definition, bit for bit): one kernel launch per ``FLK_PREP_MAX_CLIPS`` videos.
+
+    ``videos``: a list of CUDA uint8 ``[N_k,H_k,W_k,3]`` whose lengths and resolutions may differ; views are read in place when a
+    pixel's bytes and a row's pixels are adjacent.  ``codec``: a ``videoresnet_spec.Codec``.  Returns the list of compressed videos,
+    uint8 ``[N_k,H_k,W_k,3]``; with ``stats`` also a list of int32 ``[N_k,2]`` (per frame: non-zero quantised coefficients, the sum
+    of their magnitudes).
+    ``frame_idx``: host integers ``[len(videos), T_out]`` (as ``prepare_clips`` takes them, checked against the videos here): only
+    the listed frames are compressed, output ``k`` is ``[T_out,H_k,W_k,3]`` -- bitwise the call on ``videos[k][frame_idx[k]]``.
+    ``tone``: CUDA uint8 ``[len(videos), T, 256, 3]`` (``flicker_tone_tables``), T the common output length: every frame goes through
+    its byte -> byte table first -- bitwise the call on the exported videos, which are never written.
+    ``out``: a list of uint8 tensors to fill, which may be views with row and frame pitches of their own; bytes outside them are
+    not touched.  Everything is refused before any device call."""
+    from .videoresnet_spec import Codec
+    what = "codec_roundtrip"
+    if not isinstance(codec, Codec):
+        raise ValueError(f"{what}: codec must be a videoresnet_spec.Codec, got {type(codec).__name__}")
+    if not isinstance(videos, (list, tuple)) or not videos:
+        raise ValueError(f"{what}: videos must be a non-empty list of CUDA uint8 tensors [N,H,W,3]")
+    vids = list(videos)
+    for k, v in enumerate(vids):
+        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.uint8 or v.dim() != 4 or v.shape[-1] != 3 or min(v.shape) < 1:
+            desc = f"{tuple(v.shape)} {v.dtype} {v.device}" if torch.is_tensor(v) else type(v).__name__
+            raise ValueError(f"{what}: video {k} must be a CUDA uint8 tensor [N,H,W,3], got {desc}")
+    n, dev = len(vids), vids[0].device
+    table = None
+    if frame_idx is not None:
+        rows = frame_idx.numpy() if torch.is_tensor(frame_idx) and not frame_idx.is_cuda else frame_idx
+        if torch.is_tensor(rows):
+            raise ValueError(f"{what}: frame_idx must be host integers (it is checked against the videos before anything is launched)")
+        rows = [np.asarray(r) for r in rows]
+        if len(rows) != n or any(r.ndim != 1 or r.shape != rows[0].shape or r.dtype.kind not in "iu" for r in rows) or not 1 <= rows[0].size <= 65535:
+            raise ValueError(f"{what}: frame_idx must hold {n} equally long rows of 1..65535 integers")
+        table = np.stack(rows).astype(np.int64)
+        for k, v in enumerate(vids):
+            if table[k].min() < 0 or table[k].max() >= v.shape[0]:
+                raise ValueError(f"{what}: video {k}: frame_idx holds {int(table[k].min())} .. {int(table[k].max())}, the video has {v.shape[0]} frames")
+    lens = [int(v.shape[0]) if table is None else table.shape[1] for v in vids]
+    if max(lens) > 65535:
+        raise ValueError(f"{what}: {max(lens)} frames in one video, more than 65535 (cut it, or give frame_idx)")
+    if tone is not None:
+        if len(set(lens)) != 1:
+            raise ValueError(f"{what}: tone needs one output length for every video (give frame_idx), got lengths {sorted(set(lens))}")
+        _check_tone(what, "tone", tone, torch.uint8, (n, lens[0], 256, 3), dev)
+    if out is None:
+        outs = [torch.empty((lens[k], v.shape[1], v.shape[2], 3), dtype=torch.uint8, device=dev) for k, v in enumerate(vids)]
+    else:
+        outs = list(out) if isinstance(out, (list, tuple)) else None
+        if outs is None or len(outs) != n:
+            raise ValueError(f"{what}: out must be a list of {n} uint8 tensors")
+    keep = []
+    for k, (v, o) in enumerate(zip(vids, outs)):
+        shape = (lens[k], int(v.shape[1]), int(v.shape[2]), 3)
+        if (not torch.is_tensor(o) or not o.is_cuda or o.dtype != torch.uint8 or tuple(o.shape) != shape or o.device != dev or o.stride(-1) != 1
+                or o.stride(-2) != 3 or o.stride(-3) < 3 * shape[2] or (shape[0] > 1 and o.stride(0) < o.stride(-3) * shape[1])):
+            desc = f"{tuple(o.shape)} {o.dtype} strides {o.stride()}" if torch.is_tensor(o) else type(o).__name__
+            raise ValueError(f"{what}: out[{k}] must be a CUDA uint8 tensor {list(shape)} with adjacent pixel bytes and pixels, rows and frames not "
+                             f"overlapping, got {desc}")
+        if v.stride(-1) != 1 or v.stride(-2) != 3 or v.stride(-3) < 3 * shape[2] or (v.shape[0] > 1 and v.stride(0) <= 0):
+            v = v.contiguous()
+        keep.append(v)
+        lo_s, hi_s = v.data_ptr(), v.data_ptr() + (v.shape[0] - 1) * max(v.stride(0), 0) + (shape[1] - 1) * v.stride(1) + 3 * shape[2]
+        lo_d, hi_d = o.data_ptr(), o.data_ptr() + (shape[0] - 1) * max(o.stride(0), 0) + (shape[1] - 1) * o.stride(1) + 3 * shape[2]
+        if lo_s < hi_d and lo_d < hi_s:
+            raise ValueError(f"{what}: out[{k}] overlaps its source (an MCU reads pixels that other workgroups write)")
+    tab_dev = None if table is None else torch.from_numpy(table.astype(np.int32)).to(dev)
+    groups = {}
+    for k in range(n):                          # one launch has one output length: videos of equal length share launches
+        groups.setdefault(lens[k], []).append(k)
+    if table is not None or tone is not None:
+        assert len(groups) == 1
+    st_out = [None] * n
+    sub = _lib.FLK_CODEC_420 if codec.subsampling == "420" else _lib.FLK_CODEC_444
+    for T_out, members in groups.items():
+        for first in range(0, len(members), FLK_PREP_MAX_CLIPS):
+            part = members[first:first + FLK_PREP_MAX_CLIPS]
+            arr = (_lib.CodecClip * len(part))()
+            for d, k in zip(arr, part):
+                v, o = keep[k], outs[k]
+                d.src, d.T, d.Hs, d.Ws = v.data_ptr(), int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
+                d.pitch_t, d.pitch_h = max(int(v.stride(0)), 1), int(v.stride(1))
+                d.dst, d.dst_pitch_t, d.dst_pitch_h = o.data_ptr(), max(int(o.stride(0)), 1), int(o.stride(1))
+            a = _lib.CodecArgs()
+            a.nclip, a.quality, a.subsampling, a.clips = len(part), codec.quality, sub, arr
+            st = torch.empty((len(part), T_out, 2), dtype=torch.int32, device=dev) if stats else None
+            # with a table or a tone the launch's members are consecutive videos: its rows of the tables start at part[0]
+            check(load().flk_codec_roundtrip_u8(C.byref(a), None if tab_dev is None else ptr(tab_dev[part[0]:]), T_out,
+                                                None if tone is None else ptr(tone[part[0]:]), ptr(st), stream_ptr()))
+            if stats:
+                for j, k in enumerate(part):
+                    st_out[k] = st[j]
+    return (outs, st_out) if stats else outs
+
+
 def pack_batch_sums(per_clip, prob_scale, out3):
     """out3 = [sum loss_b, prob_scale * sum p_label, prob_scale * sum p_max_other] from softmax_adv_loss's per-clip table"""
     assert per_clip.dtype == torch.float32 and per_clip.is_contiguous() and per_clip.shape[1] == 4 and out3.dtype == torch.float32

@@ -12,7 +12,7 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, FLICKER_MODELS, RESIZE_RULES, CaptureChannel, check_sampling, flicker_rows, illum_tables,
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, FLICKER_MODELS, RESIZE_RULES, CaptureChannel, Codec, check_sampling, flicker_rows, illum_tables,
                                resolve_model, sample_frame_indices, split_sampling, train_crop_params, u8_decode_table)
 
 FLICKER_TIMES = ("clip", "video")
@@ -519,7 +519,7 @@ class FlickerVideoResNet:
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
                  im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False, codec=None):
         from .i3d_engine import check_optimizer
         # flicker_model "illumination": the flicker LIGHTS THE SCENE instead of being added to the displayed pixels -- a pixel of linear
         # light L becomes L * (1 + m), then goes through the camera's response and 8 bits (videoresnet_spec.illum_tables(response); the
@@ -549,6 +549,18 @@ class FlickerVideoResNet:
             if capture is not None and capture.readout is not None:
                 raise ValueError("train_delivered: a capture channel with a readout (rolling shutter) gives every line of a frame its own "
                                  "flicker, which is not a per-frame byte map")
+        # codec (a videoresnet_spec.Codec; train_delivered only): the delivered video is COMPRESSED before the victim sees it.  The training
+        # forward lays the flicker over the batch's frames and compresses them in one launch (ops.codec_roundtrip(frame_idx=, tone=)) into
+        # reused uint8 buffers, prepares those and scores them clean -- the chain ``evaluate_videos(quantise="video", codec=)`` scores, bit
+        # for bit.  The backward is the train_delivered one on the source videos: straight through the codec, whose Jacobian is taken as
+        # the identity.  None (default): every launch as before
+        if codec is not None:
+            if not isinstance(codec, Codec):
+                raise ValueError(f"codec must be a videoresnet_spec.Codec or None, got {type(codec).__name__}")
+            if not self.train_delivered:
+                raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
+                                 "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")
+        self.codec = codec
         # capture (flicker_time "video"; a videoresnet_spec.CaptureChannel): the attack is trained OVER THE AIR.  Every adversarial training
         # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
         # of rows a camera records (ops.flicker_rows_mix in the gather's place); the step folds its gradient through the same tables
@@ -780,7 +792,7 @@ class FlickerVideoResNet:
             self.last_augment = {"boxes": boxes, "flips": flips}
         return clips, np.concatenate(tables), boxes, flips
 
-    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None, capture=None, capture_draws=1):
+    def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None, capture=None, capture_draws=1, codec=None):
         """``VideoLearnerAdversarial.evaluate(num_samples)`` (model.py:1227-1317) on whole videos resident on the device: every video is
         scored by the argmax of the summed logits of ``num_samples`` clips cut at uniform offsets (the test split: no shift, no jitter)
         and prepared with the evaluation transform.  ``videos``: a list of CUDA uint8 ``[N_k,H_k,W_k,3]``; ``labels``: one class per video.
@@ -806,6 +818,10 @@ class FlickerVideoResNet:
         ``capture_draws`` (the list of the N draws), ``capture_clip_logits`` fp32 ``[N, V * num_samples, classes]``, ``capture_video_logits``
         fp32 ``[N, V, classes]``, ``capture_video_fooling_ratios`` fp64 ``[N]`` and their ``capture_video_fooling_ratio_mean`` /
         ``capture_video_fooling_ratio_min``.  Everything else in the result is what it is without ``capture`` (no channel).
+        ``codec`` (a videoresnet_spec.Codec; with ``quantise="video"`` only): every exported video, those of the capture draws included,
+        goes through the lossy codec (ops.codec_roundtrip) before it is scored -- the attack as a viewer of the compressed file
+        receives it.  Adds ``codec_stats``: per video the int32 ``[N_k,2]`` table of the codec launch (non-zero quantised coefficients
+        and the sum of their magnitudes per frame: a proxy for the bit rate).  None: exactly the result without it.
         Known difference from the reference: its loop starts at video 1 (``range(1, len(ds))``, model.py:1279-1281) and so never
         scores the first video; this one evaluates every video."""
         videos = list(videos) if isinstance(videos, (list, tuple)) else None
@@ -825,6 +841,9 @@ class FlickerVideoResNet:
         if quantise not in (None, "clip", "video"):
             raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
         adversarial = adversarial or quantise is not None
+        if self._check_codec(codec, "evaluate_videos") is not None and quantise != "video":
+            raise ValueError(f"evaluate_videos: codec compresses whole delivered videos -- it needs quantise='video', got quantise={quantise!r}")
+        codec_stats = []
         if self.illumination and adversarial and quantise != "video":
             raise ValueError("evaluate_videos: flicker_model='illumination' lights the stored bytes of a video -- score it with quantise='video' "
                              "(the clips prepared here are resampled fp32 values, which the camera tables do not take)")
@@ -857,6 +876,9 @@ class FlickerVideoResNet:
                     if v not in exported:
                         exported[v], st = self.export_video(videos[v], stats=True)
                         flick.append(st[:, :, 0].cpu().numpy() / float(videos[v].shape[1] * videos[v].shape[2]))
+                        if codec is not None:
+                            (exported[v],), (cs,) = ops.codec_roundtrip([exported[v]], codec, stats=True)
+                            codec_stats.append(cs.cpu().numpy())
                 ops.prepare_clips([exported[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
                                   frame_idx=rows[ks])
                 adv.append(self.logits(x, False)[:n].cpu())
@@ -871,7 +893,7 @@ class FlickerVideoResNet:
                 n = min(B, V * S - first)
                 self.pert_model.set_frame_numbers(rows[ks])
                 if quantise == "video":
-                    exp = {v: self.export_video(videos[v], capture={k: (d[k][v] if k == "gain" else float(d[k][v])) for k in d})
+                    exp = {v: self.export_video(videos[v], capture={k: (d[k][v] if k == "gain" else float(d[k][v])) for k in d}, codec=codec)
                            for v in sorted(set(vs_.tolist()))}
                     ops.prepare_clips([exp[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
                                       rule=self.resize_rule, frame_idx=rows[ks])
@@ -909,6 +931,8 @@ class FlickerVideoResNet:
                    video_accuracy=float((vp == trues).mean()), clip_accuracy=float((cp == clip_trues).mean()))
         if quantise is not None:
             res["realised_flicker"] = np.concatenate(flick) if quantise == "clip" else flick
+        if codec is not None:
+            res["codec_stats"] = codec_stats
         if draws:
             scored = [score(parts) for parts in cap_adv]
             ratios = np.asarray([float(((s[3] != trues) & ok).sum() / ok.sum()) if ok.any() else float("nan") for s in scored], np.float64)
@@ -962,14 +986,23 @@ class FlickerVideoResNet:
             self._q_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.uint8, device=x.device)
         return self.logits(self.adversarial_frames(x, out=self._q_buf, adversarial=adversarial, capture=capture), False)
 
-    def export_video(self, video_u8, phase=0, stats=False, capture=None):
+    @staticmethod
+    def _check_codec(codec, what):
+        if codec is not None and not isinstance(codec, Codec):
+            raise ValueError(f"{what}: codec must be a videoresnet_spec.Codec or None, got {type(codec).__name__}")
+        return codec
+
+    def export_video(self, video_u8, phase=0, stats=False, capture=None, codec=None):
         """the engine's flicker laid over a WHOLE video at its own resolution: ``video_u8`` uint8 ``[N,H,W,3]`` on the device -> uint8
         ``[N,H,W,3]``, frame n perturbed by row ``(n - phase) mod P`` of the perturbation (period P = the engine's T, or the ``flicker_period``
         of an engine on video time; the flicker is uniform over a frame, so it needs no resize).  One kernel launch.  Flicker attacks with
         one shared perturbation only.  ``stats``: also the int32 ``[N,3,4]`` table of ops.export_adversarial_u8.  ``capture`` (video time):
         ONE capture channel, a dict of the scalars ``subframe`` and ``exposure`` and ``gain`` [3] -- the video a camera with that channel
         records: the perturbation exported is the channel's mix of the rows (Perturbation.captured_perturbation, one launch), so frame n
-        carries what a training step under that channel at that phase gives frame number n."""
+        carries what a training step under that channel at that phase gives frame number n.  ``codec`` (a videoresnet_spec.Codec): the
+        COMPRESSED delivered video -- the export followed by the codec launch, bit for bit ``ops.codec_roundtrip([export_video(video)],
+        codec)[0]``; the stats stay the export's."""
+        self._check_codec(codec, "export_video")
         if self.attack_type != "flickering" or self.per_clip:
             raise ValueError("export_video: the flickering attack with one shared perturbation only (a dense or per-clip perturbation belongs to its clip)")
         if not torch.is_tensor(video_u8) or video_u8.dim() != 4 or video_u8.dtype != torch.uint8 or video_u8.shape[-1] != 3 or not video_u8.is_cuda or video_u8.shape[0] < 1:
@@ -979,7 +1012,10 @@ class FlickerVideoResNet:
             res = ops.illum_export_u8(a, self.pert_model.illum, stats=stats, delta_T=self.P)
         else:
             res = ops.export_adversarial_u8(a, "torch", stats=stats, delta_T=self.P)
-        return (res[0][0], res[1][0]) if stats else res[0]
+        video = res[0][0] if stats else res[0]
+        if codec is not None:
+            video = ops.codec_roundtrip([video], codec)[0]
+        return (video, res[1][0]) if stats else video
 
     def _check_video_labels(self, labels):
         """clips_per_video > 1: one label per VIDEO"""
@@ -1042,6 +1078,23 @@ class FlickerVideoResNet:
             self._prep_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.float32, device=dev)
         ta = pm.export_args(self._ramp, True, shift_p="draw", capture=capture)      # the per-clip delta of this batch's frame numbers
         ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=self._tone)
+        if self.codec is not None:
+            # the compressed delivered video: ONE codec launch tones and compresses only the batch's B * T frames at their native
+            # resolution into uint8 buffers the engine reuses; the untoned sampled preparation of those follows (identity frame table)
+            bufs = getattr(self, "_codec_bufs", None)
+            if bufs is None:
+                bufs = self._codec_bufs = {}
+            want = [(k, int(v.shape[1]), int(v.shape[2])) for k, v in enumerate(clips)]
+            for key in [key for key in bufs if key not in want]:
+                del bufs[key]
+            for key in want:
+                if key not in bufs:
+                    bufs[key] = torch.empty((self.T, key[1], key[2], 3), dtype=torch.uint8, device=dev)
+            frames = ops.codec_roundtrip(list(clips), self.codec, frame_idx=rows, tone=self._tone, out=[bufs[key] for key in want])
+            x = ops.prepare_clips(frames, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                  boxes=boxes, flips=flips, frame_idx=np.broadcast_to(np.arange(self.T), (len(frames), self.T)))
+            self._forward(x, False)
+            return ta
         x = ops.prepare_clips(clips, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
                               boxes=boxes, flips=flips, frame_idx=rows, tone=self._tone)
         self._forward(x, False)
@@ -1561,7 +1614,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
                  attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
                  process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False, codec=None):
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1577,6 +1630,6 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
                          process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
                          clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
                          flicker_time=flicker_time, flicker_period=flicker_period, capture=capture, flicker_model=flicker_model,
-                         response=response, train_delivered=train_delivered)
+                         response=response, train_delivered=train_delivered, codec=codec)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

@@ -1151,3 +1151,195 @@ def capture_from_arguments(ap, a):
                               readout=None if a.capture_readout is None else tuple(a.capture_readout))
     except ValueError as e:
         ap.error(str(e))
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------
+# Lossy intra-frame compression of the delivered video: a JPEG-style round trip defined in integers only.  The kernel
+# (csrc/codec.hip, flk_codec_roundtrip_u8) performs the operations written here, one for one: codec_roundtrip_host is its definition.
+CODEC_SUBSAMPLINGS = ("444", "420")
+# ITU T.81 Annex K, tables K.1 (luminance) and K.2 (chrominance), row-major (natural) order
+CODEC_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                   18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+CODEC_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# the "slow integer" transform pair: round(x * 2^13) of the rotation constants; two passes, 2 extra bits kept between them
+_C_BITS, _P1_BITS = 13, 2
+_F_0_298, _F_0_390, _F_0_541, _F_0_765, _F_0_899, _F_1_175 = 2446, 3196, 4433, 6270, 7373, 9633
+_F_1_501, _F_1_847, _F_1_961, _F_2_053, _F_2_562, _F_3_072 = 12299, 15137, 16069, 16819, 20995, 25172
+
+
+def check_codec(quality, subsampling, what="codec"):
+    """the (quality, subsampling) of a codec, checked: an integer 1..100 and "444" or "420" (444 / 420 as integers are taken too)"""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= int(quality) <= 100:
+        raise ValueError(f"{what}: quality must be an integer in 1..100, got {quality!r}")
+    if str(subsampling) not in CODEC_SUBSAMPLINGS or isinstance(subsampling, bool):
+        raise ValueError(f"{what}: subsampling must be one of {CODEC_SUBSAMPLINGS}, got {subsampling!r}")
+    return int(quality), str(subsampling)
+
+
+class Codec:
+    """A lossy intra-frame codec the delivered video goes through: ``quality`` 1..100 (the IJG scale) and chroma ``subsampling``
+    "444" or "420".  A checked value object; ``ops.codec_roundtrip`` and the engines take it."""
+    __slots__ = ("quality", "subsampling")
+
+    def __init__(self, quality=75, subsampling="420"):
+        q, s = check_codec(quality, subsampling, "Codec")
+        object.__setattr__(self, "quality", q)
+        object.__setattr__(self, "subsampling", s)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Codec is immutable")
+
+    def __repr__(self):
+        return f"Codec(quality={self.quality}, subsampling={self.subsampling!r})"
+
+    def __eq__(self, other):
+        return isinstance(other, Codec) and (self.quality, self.subsampling) == (other.quality, other.subsampling)
+
+    def __hash__(self):
+        return hash((self.quality, self.subsampling))
+
+
+def codec_tables(quality):
+    """the two quantisation tables at ``quality``: int32 ``[64]`` luma and chroma, row-major -- the Annex K base tables under the IJG
+    rule  s = 5000 // q (q < 50) else 200 - 2 q;  Q = clamp((base * s + 50) // 100, 1, 255)"""
+    q, _ = check_codec(quality, "444", "codec_tables")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.asarray(b, np.int64) * s + 50) // 100, 1, 255).astype(np.int32) for b in (CODEC_BASE_LUMA, CODEC_BASE_CHROMA))
+
+
+def _descale(x, n):
+    return (x + (1 << (n - 1))) >> n          # arithmetic shift: floor((x + 2^(n-1)) / 2^n)
+
+
+def _fdct_1d(d, shift_even, shift_odd):
+    """one 8-point forward pass over axis -1 (values d[..., 0..7]); shift_even < 0: a left shift of the two sums"""
+    t0, t7, t1, t6 = d[..., 0] + d[..., 7], d[..., 0] - d[..., 7], d[..., 1] + d[..., 6], d[..., 1] - d[..., 6]
+    t2, t5, t3, t4 = d[..., 2] + d[..., 5], d[..., 2] - d[..., 5], d[..., 3] + d[..., 4], d[..., 3] - d[..., 4]
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    o = [None] * 8
+    if shift_even < 0:
+        o[0], o[4] = (t10 + t11) << -shift_even, (t10 - t11) << -shift_even
+    else:
+        o[0], o[4] = _descale(t10 + t11, shift_even), _descale(t10 - t11, shift_even)
+    z1 = (t12 + t13) * _F_0_541
+    o[2] = _descale(z1 + t13 * _F_0_765, shift_odd)
+    o[6] = _descale(z1 - t12 * _F_1_847, shift_odd)
+    z1, z2, z3, z4 = t4 + t7, t5 + t6, t4 + t6, t5 + t7
+    z5 = (z3 + z4) * _F_1_175
+    t4, t5, t6, t7 = t4 * _F_0_298, t5 * _F_2_053, t6 * _F_3_072, t7 * _F_1_501
+    z1, z2, z3, z4 = -z1 * _F_0_899, -z2 * _F_2_562, -z3 * _F_1_961 + z5, -z4 * _F_0_390 + z5
+    o[7], o[5] = _descale(t4 + z1 + z3, shift_odd), _descale(t5 + z2 + z4, shift_odd)
+    o[3], o[1] = _descale(t6 + z2 + z3, shift_odd), _descale(t7 + z1 + z4, shift_odd)
+    return np.stack(o, -1)
+
+
+def _idct_1d(c, shift):
+    """one 8-point inverse pass over axis -1"""
+    z2, z3 = c[..., 2], c[..., 6]
+    z1 = (z2 + z3) * _F_0_541
+    t2, t3 = z1 - z3 * _F_1_847, z1 + z2 * _F_0_765
+    t0, t1 = (c[..., 0] + c[..., 4]) << _C_BITS, (c[..., 0] - c[..., 4]) << _C_BITS
+    t10, t13, t11, t12 = t0 + t3, t0 - t3, t1 + t2, t1 - t2
+    t0, t1, t2, t3 = c[..., 7], c[..., 5], c[..., 3], c[..., 1]
+    z1, z2, z3, z4 = t0 + t3, t1 + t2, t0 + t2, t1 + t3
+    z5 = (z3 + z4) * _F_1_175
+    t0, t1, t2, t3 = t0 * _F_0_298, t1 * _F_2_053, t2 * _F_3_072, t3 * _F_1_501
+    z1, z2, z3, z4 = -z1 * _F_0_899, -z2 * _F_2_562, -z3 * _F_1_961 + z5, -z4 * _F_0_390 + z5
+    t0, t1, t2, t3 = t0 + z1 + z3, t1 + z2 + z4, t2 + z2 + z3, t3 + z1 + z4
+    o = [t10 + t3, t11 + t2, t12 + t1, t13 + t0, t13 - t0, t12 - t1, t11 - t2, t10 - t3]
+    return np.stack([_descale(v, shift) for v in o], -1)
+
+
+def _codec_plane(p, qt, dt):
+    """a padded plane [N, Hp, Wp] (values 0..255, Hp and Wp multiples of 8) through DCT, quantisation and back; also the levels"""
+    N, Hp, Wp = p.shape
+    b = p.reshape(N, Hp // 8, 8, Wp // 8, 8).transpose(0, 1, 3, 2, 4).astype(dt) - 128          # [N, by, bx, row, col]
+    f = _fdct_1d(b, -_P1_BITS, _C_BITS - _P1_BITS)                                              # pass 1: along the rows
+    f = _fdct_1d(f.swapaxes(-1, -2), _P1_BITS, _C_BITS + _P1_BITS).swapaxes(-1, -2)             # pass 2: down the columns; 8 x the DCT
+    d = (qt.reshape(8, 8).astype(dt) << 3)
+    mag = (np.abs(f) + (d >> 1)) // d                                                           # half away from zero
+    lev = np.where(f < 0, -mag, mag).astype(dt)
+    c = lev * qt.reshape(8, 8).astype(dt)
+    w = _idct_1d(c.swapaxes(-1, -2), _C_BITS - _P1_BITS).swapaxes(-1, -2)                       # pass 1: down the columns
+    o = np.clip(_idct_1d(w, _C_BITS + _P1_BITS + 3) + 128, 0, 255)                              # pass 2: along the rows
+    return o.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp), lev
+
+
+def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=False, _dtype=np.int32):
+    """The codec round trip on the host, in integers only: uint8 ``[N,H,W,3]`` (or one frame ``[H,W,3]``) -> uint8 of the same shape;
+    with ``stats`` also int32 ``[N,2]``: per frame the number of non-zero quantised coefficients and the sum of their magnitudes.
+    ``tone``: uint8 ``[N,256,3]`` (or ``[256,3]``), the byte -> byte table each frame goes through first.
+    Stages (every shift is arithmetic; all values in ``_dtype``, int32 -- int64 gives the same, which is the overflow check):
+      colour   Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+               Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16;   Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16
+      pad      to multiples of 8 ("444") or 16 ("420") by repeating the last column and row
+      420      Cb, Cr: (a + b + c + d + 1 + (x & 1)) >> 2 over each 2 x 2 cell, x the OUTPUT column
+      DCT      value - 128; rows then columns (_fdct_1d); level = sign * ((|f| + 4 Q) // (8 Q)); back: level * Q, columns then rows
+               (_idct_1d), + 128, clamp to 0..255
+      420      chroma repeated 2 x 2
+      colour   R = Y + ((91881 Cr' + 32768) >> 16);  G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16);  B = Y + ((116130 Cb' + 32768) >> 16)
+               with Cb' = Cb - 128, Cr' = Cr - 128; clamp to 0..255; crop"""
+    quality, subsampling = check_codec(quality, subsampling, "codec_roundtrip_host")
+    x = np.asarray(frames)
+    single = x.ndim == 3
+    if single:
+        x = x[None]
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[-1] != 3 or min(x.shape) < 1:
+        raise ValueError(f"codec_roundtrip_host: frames must be uint8 [N,H,W,3], got {x.shape} {x.dtype}")
+    N, H, W, _ = x.shape
+    if tone is not None:
+        tone = np.asarray(tone)
+        if tone.ndim == 2:
+            tone = np.broadcast_to(tone, (N, 256, 3))
+        if tone.dtype != np.uint8 or tone.shape != (N, 256, 3):
+            raise ValueError(f"codec_roundtrip_host: tone must be uint8 [{N},256,3], got {tone.shape} {tone.dtype}")
+        x = np.stack([np.stack([tone[n, :, c][x[n, :, :, c]] for c in range(3)], -1) for n in range(N)])
+    dt = _dtype
+    m = 8 if subsampling == "444" else 16
+    Hp, Wp = (H + m - 1) // m * m, (W + m - 1) // m * m
+    x = np.pad(x, ((0, 0), (0, Hp - H), (0, Wp - W), (0, 0)), mode="edge").astype(dt)
+    R, G, B = x[..., 0], x[..., 1], x[..., 2]
+    Y = (19595 * R + 38470 * G + 7471 * B + 32768) >> 16
+    Cb = (-11059 * R - 21709 * G + 32768 * B + 8388608 + 32767) >> 16
+    Cr = (32768 * R - 27439 * G - 5329 * B + 8388608 + 32767) >> 16
+    if subsampling == "420":
+        bias = (1 + (np.arange(Wp // 2) & 1)).astype(dt)
+        Cb, Cr = ((p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] + bias) >> 2 for p in (Cb, Cr))
+    ql, qc = codec_tables(quality)
+    (Y, ly), (Cb, lb), (Cr, lr) = _codec_plane(Y, ql, dt), _codec_plane(Cb, qc, dt), _codec_plane(Cr, qc, dt)
+    if subsampling == "420":
+        Cb, Cr = (p.repeat(2, 1).repeat(2, 2) for p in (Cb, Cr))
+    cb, cr = Cb - 128, Cr - 128
+    out = np.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), Y + ((116130 * cb + 32768) >> 16)], -1)
+    out = np.clip(out, 0, 255).astype(np.uint8)[:, :H, :W]
+    if single:
+        out = out[0]
+    if not stats:
+        return out
+    st = np.stack([sum((l != 0).reshape(N, -1).sum(1) for l in (ly, lb, lr)), sum(np.abs(l).reshape(N, -1).sum(1) for l in (ly, lb, lr))], -1)
+    return out, st.astype(np.int32)
+
+
+def add_codec_arguments(ap):
+    """the scripts' options of the codec the delivered video goes through; absent by default"""
+    ap.add_argument("--codec-quality", type=int, default=None, metavar="Q", help="compress the delivered video lossily, intra-frame (JPEG-style: "
+                    "colour transform, 8x8 DCT, quantisation at IJG quality Q in 1..100, and back) wherever a whole delivered video is scored, "
+                    "saved or trained on: --eval-quantised video, --save-adversarial-u8 of whole videos, --train-delivered")
+    ap.add_argument("--codec-subsampling", default=None, choices=list(CODEC_SUBSAMPLINGS), help="the codec's chroma subsampling (default 420); "
+                    "needs --codec-quality")
+
+
+def codec_from_arguments(ap, a, used):
+    """the Codec the ``--codec-*`` options describe, or None.  ``used``: whether this run has a whole delivered video to compress (the
+    caller's modes); the options anywhere else are an argparse error"""
+    if a.codec_quality is None:
+        if a.codec_subsampling is not None:
+            ap.error("--codec-subsampling needs --codec-quality")
+        return None
+    if not used:
+        ap.error("--codec-quality / --codec-subsampling act on whole delivered videos: give --eval-quantised video, --train-delivered or "
+                 "--save-adversarial-u8 with whole videos")
+    try:
+        return Codec(a.codec_quality, a.codec_subsampling or "420")
+    except ValueError as e:
+        ap.error(str(e))

@@ -602,6 +602,50 @@ int flk_clip_prepare_grad(const flk_prepare_args* a, const flk_prep_box* boxes, 
                           const float* scale, const void* gx_s2d, int dtype, float* gdelta /* fp32 [nclip,T_out,3] */, float* partials,
                           void* stream);
 
+/* Lossy intra-frame compression of the delivered video (csrc/codec.hip): a JPEG-style round trip -- colour transform, chroma
+ * subsampling, 8x8 DCT, quantisation and back -- as ONE kernel with an exact integer definition, which
+ * videoresnet_spec.codec_roundtrip_host restates in numpy bit for bit (DESIGN.md 10.8 has every constant and rounding rule).  It is
+ * exactly MJPEG and the I-frame path of a block codec minus the (lossless) entropy coder.  Per output frame, uint8 [Hs][Ws][3]:
+ *   tone (optional byte -> byte table, as flk_clip_prepare_toned takes it) -> RGB to YCbCr (JFIF full range, 16-bit fixed point) ->
+ *   pad to whole MCUs by repeating the last column and row (8x8; 16x16 with 4:2:0) -> 4:2:0 only: Cb, Cr as 2x2 box means,
+ *   (a + b + c + d + 1 + (x & 1)) >> 2, x the output column -> minus 128, forward 8x8 "slow integer" DCT (13-bit constants, two passes) ->
+ *   level = the coefficient / (8 Q), half away from zero -> level * Q, inverse DCT, plus 128, clamp to 0..255 -> chroma repeated 2x2 ->
+ *   YCbCr to RGB (16-bit fixed point, clamped) -> crop.
+ * flk_codec_tables (host only; no device work): Q = clamp((base * s + 50) / 100, 1, 255) of the two base tables of ITU T.81 Annex K
+ *   (luminance, chrominance; row-major), s = 5000 / quality for quality < 50, else 200 - 2 quality (integer division): the tables a
+ *   JPEG encoder writes at that quality.
+ * flk_codec_roundtrip_u8: one launch for up to FLK_PREP_MAX_CLIPS clips of differing resolution and pitches.  Output frame t of clip k
+ *   is made from source frame frame_idx[k * T_out + t] of clips[k] (DEVICE int32 [nclip][T_out]; every index read is clamped into
+ *   [0, clips[k].T - 1], the rule of flk_clip_prepare_sampled), or from frame t when frame_idx is null (then T_out <= clips[k].T),
+ *   and written to clips[k].dst + t * dst_pitch_t as rows dst_pitch_h bytes apart.  No byte outside the Hs x Ws x 3 views is written.
+ *   tone: DEVICE uint8 [nclip][T_out][256][3], any alignment, or null.  stats: DEVICE int32 [nclip][T_out][2] or null, zeroed here by
+ *   one hipMemsetAsync: per frame the number of non-zero quantised coefficients and the sum of their magnitudes (a proxy for the bit
+ *   rate; integer sums, exact in any order).  A frame a table repeats is computed again.  No allocation, no synchronisation; the
+ *   result does not depend on the launch geometry.
+ *   FLK_EINVAL (before any GPU call): null a / clips / src / dst, nclip outside 1..FLK_PREP_MAX_CLIPS, non-positive sizes or pitches,
+ *   a row pitch smaller than 3 * Ws (or above 2^31 - 1), quality outside 1..100, a subsampling other than FLK_CODEC_444 /
+ *   FLK_CODEC_420, T_out outside 1..65535 (or above a clip's T without frame_idx), dst == src, stats on frames of more than 5000000
+ *   padded pixels (the sum of magnitudes is at most 386 per pixel: it must fit an int32). */
+#define FLK_CODEC_444 444
+#define FLK_CODEC_420 420
+typedef struct {
+  const uint8_t* src;        /* device: uint8 [T][Hs][Ws][3], the 3 bytes of a pixel adjacent */
+  int T, Hs, Ws;
+  int64_t pitch_t, pitch_h;  /* bytes between consecutive source frames / rows */
+  uint8_t* dst;              /* device: uint8 [T_out][Hs][Ws][3] */
+  int64_t dst_pitch_t, dst_pitch_h;
+} flk_codec_clip;
+typedef struct {
+  int nclip;
+  int quality;               /* 1..100, the IJG scale */
+  int subsampling;           /* FLK_CODEC_444 or FLK_CODEC_420 */
+  const flk_codec_clip* clips; /* HOST array [nclip]; copied into the kernel argument */
+} flk_codec_args;
+int flk_codec_tables(int quality, int32_t* qluma /* [64] */, int32_t* qchroma /* [64] */);
+int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx /* DEVICE [nclip][T_out] or NULL */, int T_out,
+                           const uint8_t* tone /* DEVICE [nclip][T_out][256][3] or NULL */, int32_t* stats /* DEVICE [nclip][T_out][2] or NULL */,
+                           void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

@@ -70,8 +70,9 @@ def run_whole_videos(a):
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
                                  clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
                                  flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered)
-    dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
+                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered,
+                                 codec=a.codec if a.train_delivered else None)
+    dest =os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
     xd, yd = [torch.from_numpy(v).cuda() for v in videos], torch.from_numpy(labels).cuda()
@@ -108,7 +109,9 @@ def run_whole_videos(a):
                 continue
             learner.pert_model.init_perturbation(r["perturbation"][-1])              # the clamped final perturbation of this video ...
             learner.pert_model.dynamic_max_norm = max(learner.pert_model.max_norm, r["perturbation/inf_norm"])      # ... under its own bound
-            exported, st = learner.export_video(xd[i], stats=True)
+            exported, st = learner.export_video(xd[i], stats=True, **({} if a.codec is None else {"codec": a.codec}))
+            if a.codec is not None:             # the stored video went through the codec before it is scored
+                r["codec_quality"], r["codec_subsampling"] = a.codec.quality, a.codec.subsampling
             ev = learner.evaluate_videos([exported], labels[i:i + 1], num_samples=G, adversarial=False)
             r["quantised_video_pred"] = ev["video_preds"]
             r["quantised_video_is_adversarial"] = bool(ev["video_preds"][0] != labels[i])
@@ -200,8 +203,10 @@ def main():
                     "quantised_video_is_adversarial, realised_flicker (levels per frame and channel)")
     vs.add_capture_arguments(ap)
     vs.add_flicker_model_arguments(ap)
+    vs.add_codec_arguments(ap)
     a = ap.parse_args()
     a.capture = vs.capture_from_arguments(ap, a)
+    a.codec = vs.codec_from_arguments(ap, a, a.eval_quantised == "video" or a.train_delivered)
     if a.eval_capture_draws and not vs.is_video_file(a.videos_npz):
         ap.error("--eval-capture-draws needs a whole-video .npz file: the captures are scored on the video's evaluation clips")
     if a.eval_quantised == "video" and (not vs.is_video_file(a.videos_npz) or a.batch > 1 or a.attack_type != "flickering"):

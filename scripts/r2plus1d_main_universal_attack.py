@@ -167,7 +167,9 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
                                  flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered)
+                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered,
+                                 codec=a.codec if a.train_delivered else None)
+    codec_keys = {} if a.codec is None else {"codec_quality": np.int64(a.codec.quality), "codec_subsampling": a.codec.subsampling}
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
@@ -196,18 +198,25 @@ def run_whole_videos(a, world, rank, local_rank, augment):
             np.savez(os.path.join(dest, "video_eval.npz"), num_samples=np.int64(a.eval_num_samples), **ev)
         if a.eval_quantised:                    # the attack as 8-bit frames deliver it: video_eval_quantised.npz beside video_eval.npz
             S = max(a.eval_num_samples, 1)
-            ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=S, quantise=a.eval_quantised)
+            codec = a.codec if a.eval_quantised == "video" else None
+            ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=S, quantise=a.eval_quantised,
+                                         **({} if codec is None else {"codec": codec}))
             print(f"quantised ({a.eval_quantised}) video evaluation, {S} clips per video: adversarial video accuracy {ev['video_accuracy']:.4f} | "
-                  f"video fooling ratio {ev['video_fooling_ratio']:.4f}", flush=True)
+                  f"video fooling ratio {ev['video_fooling_ratio']:.4f}" + ("" if codec is None else f" | through {codec}"), flush=True)
             if a.eval_quantised == "video":     # one [N_k,3] table per video: stored end to end, with the videos' lengths
                 ev["realised_flicker_frames"] = np.array([len(f) for f in ev["realised_flicker"]], np.int64)
                 ev["realised_flicker"] = np.concatenate(ev["realised_flicker"])
+            if codec is not None:               # one [N_k,2] table per video, end to end like realised_flicker
+                ev["codec_stats"] = np.concatenate(ev["codec_stats"])
             os.makedirs(dest, exist_ok=True)
-            np.savez(os.path.join(dest, "video_eval_quantised.npz"), num_samples=np.int64(S), quantise=a.eval_quantised, **ev)
+            np.savez(os.path.join(dest, "video_eval_quantised.npz"), num_samples=np.int64(S), quantise=a.eval_quantised, **ev,
+                     **({} if codec is None else codec_keys))
         if a.eval_capture_draws:                # the attack as N random cameras record it: video_eval_capture.npz
             S = max(a.eval_num_samples, 1)
             ev = learner.evaluate_videos([torch.from_numpy(v).cuda() for v in vva], yva, num_samples=S, adversarial=True, quantise=a.eval_quantised,
-                                         capture=a.capture, capture_draws=a.eval_capture_draws)
+                                         capture=a.capture, capture_draws=a.eval_capture_draws,
+                                         **({"codec": a.codec} if a.codec is not None and a.eval_quantised == "video" else {}))
+            ev.pop("codec_stats", None)
             print(f"capture evaluation, {a.eval_capture_draws} draws, {S} clips per video: video fooling ratio mean "
                   f"{ev['capture_video_fooling_ratio_mean']:.4f} min {ev['capture_video_fooling_ratio_min']:.4f} (no channel: "
                   f"{ev['video_fooling_ratio']:.4f})", flush=True)
@@ -219,8 +228,9 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                      **({"capture_readout": np.stack([d["readout"] for d in draws])} if "readout" in draws[0] else {}), **ev)
         if a.save_adversarial_u8:               # the validation videos under the universal flicker, whole and at their own resolution
             os.makedirs(dest, exist_ok=True)
-            np.savez(os.path.join(dest, "adversarial_u8.npz"), labels=yva,
-                     **{f"video_{i:05d}": learner.export_video(torch.from_numpy(v).cuda()).cpu().numpy() for i, v in enumerate(vva)})
+            np.savez(os.path.join(dest, "adversarial_u8.npz"), labels=yva, **codec_keys,
+                     **{f"video_{i:05d}": learner.export_video(torch.from_numpy(v).cuda(), **({} if a.codec is None else {"codec": a.codec})).cpu().numpy()
+                        for i, v in enumerate(vva)})
 
 
 def quantised_clip_report(learner, clips, labels, batch_size, keep_frames):
@@ -331,8 +341,11 @@ def main():
                     "then the clean evaluation (video_eval_quantised.npz)")
     vs.add_capture_arguments(ap)
     vs.add_flicker_model_arguments(ap)
+    vs.add_codec_arguments(ap)
     a = ap.parse_args()
     a.capture = vs.capture_from_arguments(ap, a)
+    a.codec = vs.codec_from_arguments(ap, a, a.eval_quantised == "video" or a.train_delivered
+                                      or (a.save_adversarial_u8 and vs.is_video_file(a.val_npz)))
     if a.eval_capture_draws and not vs.is_video_file(a.val_npz):
         ap.error("--eval-capture-draws needs whole-video .npz files: the captures are scored on the validation videos' evaluation clips")
     if a.eval_quantised == "video" and not (vs.is_video_file(a.train_npz) and vs.is_video_file(a.val_npz)):      # before anything touches the GPU
