@@ -5,6 +5,7 @@ libflicker_hip.so: ``Perturbation``, ``Losses``, ``Adversarial_metrics`` and a V
 Same names, argument meaning and error behaviour as the reference classes; the arithmetic runs in the HIP kernels
 (torch dialect flags), pinned by the reference's own golden vectors (tests/golden/torch_attack_golden.npz).
 Clips are channels-last ``[B,T,H,W,3]`` on the device (the reference's NCDHW ``[B,3,T,H,W]`` permuted once at load)."""
+import os
 import random
 
 import numpy as np
@@ -46,6 +47,7 @@ def check_flicker_time(flicker_time, flicker_period, sample_length, attack_type=
 ARCH_CODES = {"r2plus1d_18": FLK_NET_R2PLUS1D_18, "r3d_18": FLK_NET_R3D_18, "mc3_18": FLK_NET_MC3_18, "r2plus1d_34": FLK_NET_R2PLUS1D_34}
 CLIP_DTYPES = (torch.float32, torch.uint8)
 _DECODE_TABLES = {}
+_INV_STD = tuple(1.0 / s for s in DEFAULT_STD)
 
 
 def check_flicker_model(flicker_model, response="srgb", attack_type="flickering", dense=False):
@@ -283,23 +285,26 @@ class Perturbation:
         x: the normalised fp32 clip, or its uint8 frames -- decoded on the device through ``decode_table`` (bitwise the fp32 clip
         ``videoresnet_spec.normalize_u8`` makes on the host).  quantise: every value goes through the 8-bit round trip of ``export_u8``
         inside the apply kernel (flk_apply_args.q_lut) -- the clip applied is the one the exported frames decode to, bit for bit"""
-        delta = self.perturbation
-        self._no_capture_on_clip_time(capture)
-        self._check_illum_clip(x, adversarial)
+        delta, kw = self.perturbation, self._shared_args(x, adversarial, capture)
         if self.video_time:
             # the roll is in the rows; a clean apply reads no perturbation (adv_flag 0), so it gathers nothing and keeps the table
             delta, shift = self.delta_clip(int(x.shape[0]), phases if adversarial else None, capture, int(x.shape[2])), 0
         else:
             shift = int(self._rng.integers(0, self.T)) if (self.cyclic_pert and adversarial) else 0   # model.py:91-92
-        inf = float("inf")
-        return ops.make_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm,
-                                   adv_flag=1.0 if adversarial else 0.0, shift_p=shift,
-                                   inv_std=tuple(1.0 / s for s in DEFAULT_STD),
-                                   lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf, fold_t=fold_t,
-                                   dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
-                                   x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None,
-                                   quantise="torch" if quantise else None, q_lut=decode_table(x.device) if quantise else None,
-                                   per_line=self.video_time and delta.dim() == 4)      # (video time has no dense delta: 4-D = per line)
+        return ops.make_apply_args(x, delta, shift_p=shift, fold_t=fold_t, quantise="torch" if quantise else None,
+                                   q_lut=decode_table(x.device) if quantise else None,
+                                   per_line=self.video_time and delta.dim() == 4, **kw)   # (video time has no dense delta: 4-D = per line)
+
+    def _shared_args(self, x, adversarial, capture):
+        """what ``apply_args`` and ``export_args`` have in common: the checks of the clip and the channel, and the keyword arguments that
+        say how the perturbation meets the clip -- the dialect, the clamp bound(s) of the perturbation, the flag and the value range of
+        an adversarial apply (a clean one has neither), 1 / std and the decode table of uint8 frames"""
+        self._no_capture_on_clip_time(capture)
+        self._check_illum_clip(x, adversarial)
+        return dict(dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0, inv_std=_INV_STD,
+                    lo=self.min_value if adversarial else -np.inf, hi=self.max_value if adversarial else np.inf,
+                    dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
+                    x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None)
 
     def export_args(self, x, adversarial=True, shift_p=0, delta_T=0, capture=None):
         """``apply_args`` for the 8-bit export (ops.make_export_apply_args): no fold, so T, H and W may be odd; no roll is drawn -- the
@@ -308,20 +313,13 @@ class Perturbation:
         the shared perturbation itself -- the kernel's own rule IS the one the rows follow.  ``capture``: the channel(s) the flicker is
         recorded through -- clips: as ``delta_clip`` takes them; a whole video: ONE channel, the perturbation exported being its mix
         over ``rows = arange(P)`` (``captured_perturbation``; the mix commutes with the row shift)"""
-        inf = float("inf")
-        delta = self.perturbation
-        self._no_capture_on_clip_time(capture)
-        self._check_illum_clip(x, adversarial)
+        delta, kw = self.perturbation, self._shared_args(x, adversarial, capture)
         if self.video_time and not delta_T:
             delta, shift_p = self.delta_clip(int(x.shape[0]), shift_p if adversarial else None, capture, int(x.shape[2])), 0
         elif capture is not None and adversarial:
             delta = self.captured_perturbation(capture, int(x.shape[2]))
-        return ops.make_export_apply_args(x, delta, dialect="torch", dclip=self.dynamic_max_norm, adv_flag=1.0 if adversarial else 0.0,
-                                          shift_p=shift_p, inv_std=tuple(1.0 / s for s in DEFAULT_STD),
-                                          lo=self.min_value if adversarial else -inf, hi=self.max_value if adversarial else inf,
-                                          dclip_dev=self.dyn_max_norm_dev if self.batch is not None else None,
-                                          x_lut=decode_table(x.device) if x.dtype == torch.uint8 else None, delta_T=delta_T,
-                                          per_line=self.video_time and delta.dim() - (0 if delta_T else 1) == 3)
+        return ops.make_export_apply_args(x, delta, shift_p=shift_p, delta_T=delta_T,
+                                          per_line=self.video_time and delta.dim() - (0 if delta_T else 1) == 3, **kw)
 
     def captured_perturbation(self, capture, H=None):
         """video time: the shared perturbation as ONE capture channel records it, fp32 [P,3] -- one ops.flicker_rows_mix launch over
@@ -338,6 +336,16 @@ class Perturbation:
         taps, gain = CaptureChannel.tables(capture, 1)
         return ops.flicker_rows_mix(self.perturbation, rows, torch.from_numpy(taps).to(dev), torch.from_numpy(gain).to(dev))
 
+    def _channels_last(self, x):
+        """a clip as ``forward`` and ``export_u8`` take it -- NCDHW or channels-last, fp32 or uint8, anywhere -- as the contiguous
+        channels-last CUDA tensor the kernels read (uint8 stays uint8, anything else becomes fp32) -> ``(clip, whether x was NCDHW)``"""
+        ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
+        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
+        xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
+        if xcl.shape[1] != self.clip_T:
+            raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.clip_T}")
+        return xcl, ncdhw
+
     def export_u8(self, x, adversarial=True, stats=False, out=None, out_offset=0, shift_p=0, capture=None):
         """the clip ``forward([x, adversarial])`` makes, as the 8-bit frames a file or a display holds: uint8 ``[B,T,H,W,3]`` on the device,
         ``rint(255 * (x_adv * std + mean))`` saturated to 0..255 (ops.export_adversarial_u8, one kernel launch; the host route
@@ -345,12 +353,7 @@ class Perturbation:
         fp32 or uint8; any T, H, W -- odd ones too).  ``adversarial=False``: the frames of the clean clip, i.e. a uint8 ``x`` itself.
         ``stats``: also int32 ``[B,T,3,4]``, per (clip, frame, channel) the sums of q - q_clean, |q - q_clean|, [q != q_clean] and
         [clamp active]; entry 0 / (H * W) is the flicker the frames really carry, in levels."""
-        ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
-        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
-        xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
-        if xcl.shape[1] != self.clip_T:
-            raise ValueError(f"clip has {xcl.shape[1]} frames, the perturbation {self.clip_T}")
-        a = self.export_args(xcl, bool(adversarial), shift_p, capture=capture)
+        a = self.export_args(self._channels_last(x)[0], bool(adversarial), shift_p, capture=capture)
         if self.illumination and adversarial:           # the bytes a camera stores of the lit scene (clean frames: the existing call)
             return ops.illum_export_u8(a, self.illum, out=out, out_offset=out_offset, stats=stats)
         return ops.export_adversarial_u8(a, "torch", out=out, out_offset=out_offset, stats=stats)
@@ -362,12 +365,8 @@ class Perturbation:
         kernel writes the (h,w)-folded tensor the network consumes (flk_perturb_apply_s2d); it is unfolded here.  A uint8 ``x`` holds
         the frames themselves: they are normalised on the device (dataset.py:28-29), the result is the fp32 clip of the normalised input."""
         x, adversarial = input
-        ncdhw = x.dim() == 5 and x.shape[1] == 3 and x.shape[-1] != 3
-        xcl = (x.permute(0, 2, 3, 4, 1) if ncdhw else x).contiguous()
-        xcl = xcl.cuda() if xcl.dtype == torch.uint8 else xcl.float().cuda()
+        xcl, ncdhw = self._channels_last(x)
         B, T, H, W, _ = xcl.shape
-        if T != self.clip_T:
-            raise ValueError(f"clip has {T} frames, the perturbation {self.clip_T}")
         a = self.apply_args(xcl, bool(adversarial), quantise=bool(quantise))
         if self.illumination and adversarial:
             folded = ops.illum_apply_s2d(a, self.illum, torch.float32)
@@ -554,12 +553,9 @@ class FlickerVideoResNet:
         # reused uint8 buffers, prepares those and scores them clean -- the chain ``evaluate_videos(quantise="video", codec=)`` scores, bit
         # for bit.  The backward is the train_delivered one on the source videos: straight through the codec, whose Jacobian is taken as
         # the identity.  None (default): every launch as before
-        if codec is not None:
-            if not isinstance(codec, Codec):
-                raise ValueError(f"codec must be a videoresnet_spec.Codec or None, got {type(codec).__name__}")
-            if not self.train_delivered:
-                raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
-                                 "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")
+        if self._check_codec(codec) is not None and not self.train_delivered:
+            raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
+                             "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")
         self.codec = codec
         # capture (flicker_time "video"; a videoresnet_spec.CaptureChannel): the attack is trained OVER THE AIR.  Every adversarial training
         # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
@@ -676,12 +672,59 @@ class FlickerVideoResNet:
             return ops.illum_grad_reduce(a, self.pert_model.illum, self._gx, out, self._scratch)
         return ops.perturb_grad_reduce(a, self._gx, out, self._scratch)
 
+    def _payload_grad(self, a, cap, delivered, out):
+        """``step``'s route from the input gradient of the last backward to ``out``, the ``[P,3]`` gradient of the shared perturbation.
+        ``a``: the apply arguments of the step's forward; ``cap``: whether it went through a capture channel; ``delivered``: the drawn
+        clips of ``step_videos``, or None"""
+        pm = self.pert_model
+        if not self.video_time:                                 # clip time: frame t carries row t, the reduce writes the rows themselves
+            return self._grad_reduce(a, out)
+        if delivered is None and a.delta_per_line:
+            # rolling shutter: the per-line gradient [B,T,H,3] (summed over w only; adv_flag, 1/std and the clamp mask applied per line),
+            # then the transpose of the lines mix the forward ran, on the same tables, to the same [P,3] payload
+            g_lines = self._buf("_g_lines", (self.B, self.T, self.H, 3))
+            scratch = self._buf("_lines_scratch", (self.B * self.T * ops.FLICKER_LINES_MAX_TAPS * 3,))
+            self._grad_reduce(a, g_lines)
+            return ops.flicker_lines_mix_grad(g_lines, pm.rows_dev, self.P, pm.taps_dev, pm.gain_dev, out=out, scratch=scratch)
+        if delivered is None:
+            # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame)
+            self._grad_reduce(a, self._g_clip)
+        else:
+            # the delivered video: the slopes of this step's tone tables, resampled as the clips were, give the per-clip gradient
+            # [B,T,3] with its finishing factors
+            clips, rows, boxes, flips = delivered
+            slope, scale = self._buf("_slope", (self.B, self.T, 256, 3)), self._buf("_scale", (self.B, self.T, 3))
+            ops.flicker_tone_slopes(a, pm.illum if self.illumination else None, slope, scale)
+            ops.prepare_clips_grad(clips, self._gx, slope, scale, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                   boxes=boxes, flips=flips, frame_idx=rows, gdelta=self._g_clip, scratch=self._pg_scratch)
+        # the frames of the per-clip gradient fold onto their rows -- under a channel by the transpose of the mix the forward ran, on the same tables
+        if cap is None:
+            return ops.flicker_rows_grad(self._g_clip, pm.rows_dev, self.P, out=out)
+        return ops.flicker_rows_mix_grad(self._g_clip, pm.rows_dev, self.P, pm.taps_dev, pm.gain_dev, out=out)
+
     def _check_x(self, x):
         """a clip is the normalised fp32 tensor or its uint8 frames (decoded on the device, bitwise the same clip)"""
         if tuple(x.shape) != (self.B, self.T, self.H, self.W, 3) or x.dtype not in CLIP_DTYPES or not x.is_cuda:
             raise ValueError(f"clip must be a CUDA float32 or uint8 channels-last tensor {(self.B, self.T, self.H, self.W, 3)}, "
                              f"got {tuple(x.shape)} {x.dtype}")
         return x.contiguous()
+
+    def _buf(self, name, shape, dtype=torch.float32):
+        """the engine's buffer ``self.<name>``, created on first use (an engine that never takes the path never holds it) and made anew
+        only when more rows are asked for than it has: it grows on demand and never shrinks.  Uninitialised: its user writes it"""
+        t = getattr(self, name, None)
+        if t is None or t.shape[0] < shape[0]:
+            t = torch.empty(shape, dtype=dtype, device=self._logits.device)
+            setattr(self, name, t)
+        return t
+
+    def _clip_buf(self, name, n=0, dtype=torch.float32):
+        """``_buf`` for clips at the engine's size: at least ``max(n, B)`` of them"""
+        return self._buf(name, (max(int(n), self.B), self.T, self.H, self.W, 3), dtype)
+
+    def _prepare_clips(self, clips, **kw):
+        """ops.prepare_clips at the engine's geometry (``im_scale``, ``image_size``, ``resize_rule``)"""
+        return ops.prepare_clips(clips, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule, **kw)
 
     def set_frame_numbers(self, table):
         """flicker_time "video": the frame numbers of the batch the next forwards see -- integers ``[B,T]``, clip b's frame t being frame
@@ -739,18 +782,21 @@ class FlickerVideoResNet:
         for k in range(len(clips)):
             if torch.is_tensor(clips[k]) and clips[k].dim() == 4 and int(clips[k].shape[0]) != self.T:
                 raise ValueError(f"clip {k} has {int(clips[k].shape[0])} frames, the engine takes {self.T}")
-        boxes = flips = None
-        if train:
-            boxes, flips = [], []
-            for x in clips:                                          # a 5-d tensor iterates over its clips
-                Hr, Wr = ops._prep_geometry(int(x.shape[-3]), int(x.shape[-2]), self.im_scale, (self.H, self.W), self.resize_rule)[:2]
-                *box, flip = train_crop_params(Hr, Wr, (self.H, self.W), self.augment["scales"], self.augment["ratio"],
-                                               self.augment["flip_ratio"], self._aug_rng)
-                boxes.append(tuple(box))
-                flips.append(flip)
-            self.last_augment = {"boxes": boxes, "flips": flips}
-        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                 rule=self.resize_rule, boxes=boxes, flips=flips)
+        boxes, flips = self._draw_boxes(clips) if train else (None, None)
+        return self._prepare_clips(clips, out=out, out_offset=out_offset, boxes=boxes, flips=flips)
+
+    def _draw_boxes(self, clips):
+        """the training transform's draw: one ``(box, flip)`` per clip, in clip order, from the engine's generator
+        (videoresnet_spec.train_crop_params on the clip's resized extent), kept on ``last_augment`` -> ``(boxes, flips)``"""
+        boxes, flips = [], []
+        for x in clips:                                              # (a 5-d tensor iterates over its clips)
+            Hr, Wr = ops._prep_geometry(int(x.shape[-3]), int(x.shape[-2]), self.im_scale, (self.H, self.W), self.resize_rule)[:2]
+            *box, flip = train_crop_params(Hr, Wr, (self.H, self.W), self.augment["scales"], self.augment["ratio"],
+                                           self.augment["flip_ratio"], self._aug_rng)
+            boxes.append(tuple(box))
+            flips.append(flip)
+        self.last_augment = {"boxes": boxes, "flips": flips}
+        return boxes, flips
 
     def prepare_videos(self, videos, train=False, num_samples=1, out=None, out_offset=0):
         """whole decoded videos -- a list of CUDA uint8 tensors ``[N_k,H_k,W_k,3]`` of any (differing) length and resolution -- to
@@ -762,16 +808,21 @@ class FlickerVideoResNet:
         ``(box, flip)`` per clip as ``prepare(train=True)`` draws them.  The tables are kept, one int64 ``[num_samples, T]`` per video,
         on ``last_sampling``; boxes and flips on ``last_augment``."""
         clips, rows, boxes, flips = self._draw_video_clips(videos, train, num_samples, "prepare_videos")
-        return ops.prepare_clips(clips, out=out, out_offset=out_offset, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                 rule=self.resize_rule, boxes=boxes, flips=flips, frame_idx=rows)
+        return self._prepare_clips(clips, out=out, out_offset=out_offset, boxes=boxes, flips=flips, frame_idx=rows)
+
+    @staticmethod
+    def _check_videos(videos, who):
+        """whole videos as every method takes them -- a non-empty list of uint8 tensors ``[N,H,W,3]`` -- as a list"""
+        videos = list(videos) if isinstance(videos, (list, tuple)) else None
+        if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
+            raise ValueError(f"{who}: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+        return videos
 
     def _draw_video_clips(self, videos, train, num_samples, who):
         """the host half of ``prepare_videos`` (and of ``step_videos``): the frame tables, boxes and flips of ``len(videos) * num_samples``
         clips drawn from the engine's generators, kept on ``last_sampling`` / ``last_augment`` and (video time) set as the batch's frame
         numbers -> ``(clips, rows, boxes, flips)``: the video of every clip, the tables stacked ``[n,T]``, the boxes / flips or None"""
-        videos = list(videos) if isinstance(videos, (list, tuple)) else None
-        if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
-            raise ValueError(f"{who}: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+        videos = self._check_videos(videos, who)
         if int(num_samples) < 1:
             raise ValueError(f"{who}: num_samples must be >= 1, got {num_samples!r}")
         kw = split_sampling(self.sampling, self.T, train)
@@ -780,16 +831,7 @@ class FlickerVideoResNet:
         if self.video_time:                                          # the batch's frame numbers, video-major and sample-minor like its clips
             self.pert_model.set_frame_numbers(np.concatenate(tables))
         clips = [v for v in videos for _ in range(int(num_samples))]
-        boxes = flips = None
-        if train and self.augment is not None:
-            boxes, flips = [], []
-            for x in clips:
-                Hr, Wr = ops._prep_geometry(int(x.shape[-3]), int(x.shape[-2]), self.im_scale, (self.H, self.W), self.resize_rule)[:2]
-                *box, flip = train_crop_params(Hr, Wr, (self.H, self.W), self.augment["scales"], self.augment["ratio"],
-                                               self.augment["flip_ratio"], self._aug_rng)
-                boxes.append(tuple(box))
-                flips.append(flip)
-            self.last_augment = {"boxes": boxes, "flips": flips}
+        boxes, flips = self._draw_boxes(clips) if train and self.augment is not None else (None, None)
         return clips, np.concatenate(tables), boxes, flips
 
     def evaluate_videos(self, videos, labels, num_samples=10, adversarial=False, quantise=None, capture=None, capture_draws=1, codec=None):
@@ -824,26 +866,20 @@ class FlickerVideoResNet:
         and the sum of their magnitudes per frame: a proxy for the bit rate).  None: exactly the result without it.
         Known difference from the reference: its loop starts at video 1 (``range(1, len(ds))``, model.py:1279-1281) and so never
         scores the first video; this one evaluates every video."""
-        videos = list(videos) if isinstance(videos, (list, tuple)) else None
-        if not videos or any(not torch.is_tensor(v) or v.dim() != 4 or v.dtype != torch.uint8 or v.shape[0] < 1 for v in videos):
-            raise ValueError("evaluate_videos: videos must be a non-empty list of uint8 tensors [N,H,W,3]")
+        videos = self._check_videos(videos, "evaluate_videos")
         trues = np.asarray(labels.cpu() if torch.is_tensor(labels) else labels, dtype=np.int64).reshape(-1)
-        S, V, B = int(num_samples), len(videos), self.B
+        S, V = int(num_samples), len(videos)
         if S < 1 or trues.shape[0] != V:
             raise ValueError(f"evaluate_videos: {V} videos, {trues.shape[0]} labels, num_samples {num_samples!r}")
         kw = split_sampling(self.sampling, self.T, False)
         tables = [sample_frame_indices(int(v.shape[0]), num_samples=S, rng=self._samp_rng, **kw) for v in videos]
         self.last_sampling = tables
         rows = np.concatenate(tables)
-        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < B:
-            self._prep_buf = torch.empty((B, self.T, self.H, self.W, 3), dtype=torch.float32, device=videos[0].device)
-        x = self._prep_buf[:B]
         if quantise not in (None, "clip", "video"):
             raise ValueError(f"evaluate_videos: quantise must be None, 'clip' or 'video', got {quantise!r}")
         adversarial = adversarial or quantise is not None
         if self._check_codec(codec, "evaluate_videos") is not None and quantise != "video":
             raise ValueError(f"evaluate_videos: codec compresses whole delivered videos -- it needs quantise='video', got quantise={quantise!r}")
-        codec_stats = []
         if self.illumination and adversarial and quantise != "video":
             raise ValueError("evaluate_videos: flicker_model='illumination' lights the stored bytes of a video -- score it with quantise='video' "
                              "(the clips prepared here are resampled fp32 values, which the camera tables do not take)")
@@ -856,56 +892,16 @@ class FlickerVideoResNet:
                 raise ValueError(f"evaluate_videos: capture_draws must be an integer >= 1, got {capture_draws!r}")
             draws = [capture.draw(V) for _ in range(int(capture_draws))]
         kept = self.pert_model.frame_numbers                            # video time: every batch below brings its own frame numbers
-        clean, adv, flick = [], [], []
-        exported = {}                                                   # quantise = "video": the flickered videos of the current batch
-        for first in range(0, V * S, B):
-            ks = [min(first + b, V * S - 1) for b in range(B)]          # the last batch repeats its last clip
-            ops.prepare_clips([videos[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                              frame_idx=rows[ks])
-            n = min(B, V * S - first)
+        clean, adv, stats, delivered = [], [], ([], []), {}
+        for ks, n, x in self._packed_batches(videos, rows, S):
             clean.append(self.logits(x, False)[:n].cpu())
-            if self.video_time:                                         # the rows of these clips' own frames, at phase 0 like the export
-                self.pert_model.set_frame_numbers(rows[ks])
-            if quantise == "clip":
-                frames, st = self.adversarial_frames(x, stats=True)
-                adv.append(self.logits(frames, False)[:n].cpu())
-                flick.append(st[:n, :, :, 0].cpu().numpy() / float(self.H * self.W))
-            elif quantise == "video":
-                exported = {v: exported[v] for v in {k // S for k in ks} if v in exported}
-                for v in sorted({k // S for k in ks}):
-                    if v not in exported:
-                        exported[v], st = self.export_video(videos[v], stats=True)
-                        flick.append(st[:, :, 0].cpu().numpy() / float(videos[v].shape[1] * videos[v].shape[2]))
-                        if codec is not None:
-                            (exported[v],), (cs,) = ops.codec_roundtrip([exported[v]], codec, stats=True)
-                            codec_stats.append(cs.cpu().numpy())
-                ops.prepare_clips([exported[k // S] for k in ks], out=x, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                                  frame_idx=rows[ks])
-                adv.append(self.logits(x, False)[:n].cpu())
-            elif adversarial:
-                adv.append(self.logits(x, True, phases=0)[:n].cpu())       # (phases: video time only -- clip time draws its roll as ever)
+            if adversarial:
+                adv.append(self._adversarial_logits(x, videos, [k // S for k in ks], rows[ks], quantise, None, codec, delivered, stats)[:n].cpu())
         cap_adv = []
         for d in draws:                                                 # the adversarial scoring again, every video through its channel
-            parts = []
-            for first in range(0, V * S, B):
-                ks = [min(first + b, V * S - 1) for b in range(B)]
-                vs_ = np.asarray([k // S for k in ks])
-                n = min(B, V * S - first)
-                self.pert_model.set_frame_numbers(rows[ks])
-                if quantise == "video":
-                    exp = {v: self.export_video(videos[v], capture={k: (d[k][v] if k == "gain" else float(d[k][v])) for k in d}, codec=codec)
-                           for v in sorted(set(vs_.tolist()))}
-                    ops.prepare_clips([exp[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                      rule=self.resize_rule, frame_idx=rows[ks])
-                    parts.append(self.logits(x, False)[:n].cpu())
-                    continue
-                ops.prepare_clips([videos[v] for v in vs_.tolist()], out=x, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                  rule=self.resize_rule, frame_idx=rows[ks])
-                per_clip = {k: d[k][vs_] for k in d}                     # one channel per clip (with its readout, if the channel has one)
-                if quantise == "clip":
-                    parts.append(self.logits(self.adversarial_frames(x, capture=per_clip), False)[:n].cpu())
-                else:
-                    parts.append(self.logits(x, True, phases=0, capture=per_clip)[:n].cpu())
+            parts, delivered = [], {}
+            for ks, n, x in self._packed_batches(videos, rows, S, prepare=quantise != "video"):
+                parts.append(self._adversarial_logits(x, videos, [k // S for k in ks], rows[ks], quantise, d, codec, delivered)[:n].cpu())
             cap_adv.append(parts)
         self.pert_model.frame_numbers = kept
 
@@ -929,10 +925,12 @@ class FlickerVideoResNet:
             clip, video, cp, vp = c_clip, c_video, c_cp, c_vp
         res.update(clip_logits=clip, video_logits=video, clip_preds=cp, video_preds=vp,
                    video_accuracy=float((vp == trues).mean()), clip_accuracy=float((cp == clip_trues).mean()))
-        if quantise is not None:
-            res["realised_flicker"] = np.concatenate(flick) if quantise == "clip" else flick
+        if quantise == "clip":                                       # (the padded rows of the last batch are its tail)
+            res["realised_flicker"] = np.concatenate([st[:, :, :, 0].cpu().numpy() / float(self.H * self.W) for st in stats[0]])[:V * S]
+        elif quantise == "video":
+            res["realised_flicker"] = [st[:, :, 0].cpu().numpy() / float(v.shape[1] * v.shape[2]) for st, v in zip(stats[0], videos)]
         if codec is not None:
-            res["codec_stats"] = codec_stats
+            res["codec_stats"] = [cs.cpu().numpy() for cs in stats[1]]
         if draws:
             scored = [score(parts) for parts in cap_adv]
             ratios = np.asarray([float(((s[3] != trues) & ok).sum() / ok.sum()) if ok.any() else float("nan") for s in scored], np.float64)
@@ -940,6 +938,58 @@ class FlickerVideoResNet:
                        capture_video_fooling_ratios=ratios, capture_video_fooling_ratio_mean=float(ratios.mean()),
                        capture_video_fooling_ratio_min=float(ratios.min()))
         return res
+
+    def _packed_batches(self, videos, rows, S, prepare=True):
+        """``evaluate_videos``' packing: the ``len(videos) * S`` clips, video-major and sample-minor (clip k belongs to video ``k // S`` and
+        is cut at ``rows[k]``), in consecutive batches of B, the last one repeating its last clip.  Per batch ``(ks, n, x)``: its clip
+        numbers, how many of them are real, and -- unless ``prepare`` is off -- its clean clips in the engine's fp32 buffer"""
+        x = self._clip_buf("_prep_buf")[:self.B]
+        last = len(videos) * S - 1
+        for first in range(0, last + 1, self.B):
+            ks = [min(first + b, last) for b in range(self.B)]
+            if prepare:
+                self._prepare_clips([videos[k // S] for k in ks], out=x, frame_idx=rows[ks])
+            yield ks, min(self.B, last + 1 - first), x
+
+    def _adversarial_logits(self, x, videos, of, frame_idx, quantise=None, channels=None, codec=None, delivered=None, stats=None):
+        """the logits of one batch under the engine's perturbation at phase 0, the way ``quantise`` delivers it.  ``x``: the batch's clean
+        clips; ``of``: the number, in ``videos``, of every clip's video; ``frame_idx``: the frames the clips were cut at.  ``channels``: a
+        draw of ``CaptureChannel.draw(len(videos))`` -- every video's flicker goes through its own channel -- or None.
+        ``quantise`` None: ``logits(x, True)``; "clip": the clips exported to 8-bit frames, scored clean; "video": every video of the batch is
+        flickered whole at its own resolution (``export_video``) and compressed by ``codec``, and its clips, cut from the stored bytes
+        into the engine's fp32 buffer (``x`` is not read), are scored clean.  ``delivered``: {video number: its delivered form}, kept by
+        the caller from batch to batch -- a video whose clips straddle two batches is exported once; videos the batch does not hold are
+        dropped.  ``stats``: a pair of lists that take the export's stats table per batch ("clip") or per exported video ("video") and
+        the codec's per video; None: none are made"""
+        if self.video_time:                                          # the rows of these clips' own frames
+            self.pert_model.set_frame_numbers(frame_idx)
+        want = stats is not None
+
+        def pair(res):                                               # (the launches return their stats only when asked)
+            return res if want else (res, None)
+
+        if quantise != "video":
+            per_clip = None if channels is None else {k: channels[k][of] for k in channels}      # (with its readout, if the channel has one)
+            if quantise is None:
+                return self.logits(x, True, phases=0, capture=per_clip)    # (phases: video time only -- clip time draws its roll as ever)
+            frames, st = pair(self.adversarial_frames(x, stats=want, capture=per_clip))
+            if want:
+                stats[0].append(st)
+            return self.logits(frames, False)
+        delivered = {} if delivered is None else delivered
+        for v in [v for v in delivered if v not in of]:
+            del delivered[v]
+        for v in sorted(set(of) - set(delivered)):
+            one = None if channels is None else {k: (channels[k][v] if k == "gain" else float(channels[k][v])) for k in channels}
+            delivered[v], st = pair(self.export_video(videos[v], stats=want, capture=one))
+            if want:
+                stats[0].append(st)
+            if codec is not None:
+                (delivered[v],), cs = pair(ops.codec_roundtrip([delivered[v]], codec, stats=want))
+                if want:
+                    stats[1].append(cs[0])
+        out = self._clip_buf("_prep_buf", len(of))
+        return self.logits(self._prepare_clips([delivered[v] for v in of], out=out, frame_idx=frame_idx), False)
 
     def _is_raw(self, x):
         """uint8 frames that are not at the engine's H x W yet (clips that are take today's path: decoded by the apply kernel)"""
@@ -950,9 +1000,7 @@ class FlickerVideoResNet:
         call).  ``train``: with the training transform (an engine built with ``augment`` only)."""
         if not self._is_raw(x):
             return x
-        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < x.shape[0]:
-            self._prep_buf = torch.empty((max(int(x.shape[0]), self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=x.device)
-        return self.prepare(x, out=self._prep_buf, train=train)
+        return self.prepare(x, out=self._clip_buf("_prep_buf", x.shape[0]), train=train)
 
     @staticmethod
     def _same_dtype(dtype, x, what):
@@ -981,15 +1029,14 @@ class FlickerVideoResNet:
     def quantised_logits(self, x, adversarial=True, capture=None):
         """the logits of the STORED adversarial video: ``x`` perturbed and written as 8-bit frames (``adversarial_frames``, into a buffer the
         engine reuses), then scored by the clean uint8 path -- ``logits(frames, False)``"""
-        x = self._check_x(x)
-        if getattr(self, "_q_buf", None) is None:
-            self._q_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.uint8, device=x.device)
-        return self.logits(self.adversarial_frames(x, out=self._q_buf, adversarial=adversarial, capture=capture), False)
+        frames = self.adversarial_frames(self._check_x(x), out=self._clip_buf("_q_buf", dtype=torch.uint8), adversarial=adversarial, capture=capture)
+        return self.logits(frames, False)
 
     @staticmethod
-    def _check_codec(codec, what):
+    def _check_codec(codec, what=None):
+        """``codec`` itself, a videoresnet_spec.Codec or None (``what``: the method the message names; None: the constructor)"""
         if codec is not None and not isinstance(codec, Codec):
-            raise ValueError(f"{what}: codec must be a videoresnet_spec.Codec or None, got {type(codec).__name__}")
+            raise ValueError(f"{what + ': ' if what else ''}codec must be a videoresnet_spec.Codec or None, got {type(codec).__name__}")
         return codec
 
     def export_video(self, video_u8, phase=0, stats=False, capture=None, codec=None):
@@ -1067,36 +1114,30 @@ class FlickerVideoResNet:
         arguments of the ramp: the step takes the slopes from the same"""
         clips, rows, boxes, flips = drawn
         pm, dev = self.pert_model, self._logits.device
-        if getattr(self, "_tone", None) is None:
+        if not hasattr(self, "_ramp"):                               # what only this chain reads: the ramp clip, the scratch of its backward
             self._ramp = ops.tone_ramp(self.B, self.T, dev)
-            self._tone = torch.empty((self.B, self.T, 256, 3), dtype=torch.uint8, device=dev)
-            self._slope = torch.empty((self.B, self.T, 256, 3), dtype=torch.float32, device=dev)
-            self._scale = torch.empty((self.B, self.T, 3), dtype=torch.float32, device=dev)
             self._pg_scratch = torch.empty(max(1, ops.load().flk_clip_prepare_grad_scratch_bytes(min(self.B, ops.FLK_PREP_MAX_CLIPS), self.T, self.H) // 4),
                                            dtype=torch.float32, device=dev)
-        if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < self.B:
-            self._prep_buf = torch.empty((self.B, self.T, self.H, self.W, 3), dtype=torch.float32, device=dev)
+        tone = self._buf("_tone", (self.B, self.T, 256, 3), torch.uint8)
         ta = pm.export_args(self._ramp, True, shift_p="draw", capture=capture)      # the per-clip delta of this batch's frame numbers
-        ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=self._tone)
+        ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=tone)
+        kw = dict(out=self._clip_buf("_prep_buf"), boxes=boxes, flips=flips)
         if self.codec is not None:
             # the compressed delivered video: ONE codec launch tones and compresses only the batch's B * T frames at their native
             # resolution into uint8 buffers the engine reuses; the untoned sampled preparation of those follows (identity frame table)
-            bufs = getattr(self, "_codec_bufs", None)
-            if bufs is None:
-                bufs = self._codec_bufs = {}
+            if not hasattr(self, "_codec_bufs"):
+                self._codec_bufs = {}
+            bufs = self._codec_bufs
             want = [(k, int(v.shape[1]), int(v.shape[2])) for k, v in enumerate(clips)]
             for key in [key for key in bufs if key not in want]:
                 del bufs[key]
             for key in want:
                 if key not in bufs:
                     bufs[key] = torch.empty((self.T, key[1], key[2], 3), dtype=torch.uint8, device=dev)
-            frames = ops.codec_roundtrip(list(clips), self.codec, frame_idx=rows, tone=self._tone, out=[bufs[key] for key in want])
-            x = ops.prepare_clips(frames, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                                  boxes=boxes, flips=flips, frame_idx=np.broadcast_to(np.arange(self.T), (len(frames), self.T)))
-            self._forward(x, False)
-            return ta
-        x = ops.prepare_clips(clips, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                              boxes=boxes, flips=flips, frame_idx=rows, tone=self._tone)
+            frames = ops.codec_roundtrip(list(clips), self.codec, frame_idx=rows, tone=tone, out=[bufs[key] for key in want])
+            x = self._prepare_clips(frames, frame_idx=np.broadcast_to(np.arange(self.T), (len(frames), self.T)), **kw)
+        else:
+            x = self._prepare_clips(clips, frame_idx=rows, tone=tone, **kw)
         self._forward(x, False)
         return ta
 
@@ -1138,38 +1179,7 @@ class FlickerVideoResNet:
             criterion.adv(labels, self._logits, gbatch, out=(sm, self._dl, pc))
         self.net.backward(self._dl, self._gx)
         n = 3 * self.P                                          # (clip time: P == T)
-        if _delivered is not None:
-            # the delivered video: the slopes of this step's tone tables, resampled as the clips were, give the per-clip gradient
-            # [B,T,3] with its finishing factors; its frames fold onto their rows as on any video-time step
-            ops.flicker_tone_slopes(a, self.pert_model.illum if self.illumination else None, self._slope, self._scale)
-            ops.prepare_clips_grad(_delivered[0], self._gx, self._slope, self._scale, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                   rule=self.resize_rule, boxes=_delivered[2], flips=_delivered[3], frame_idx=_delivered[1], gdelta=self._g_clip,
-                                   scratch=self._pg_scratch)
-            if cap is None:
-                ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
-            else:
-                ops.flicker_rows_mix_grad(self._g_clip, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
-                                          out=red[:n].view(self.P, 3))
-        elif self.video_time and a.delta_per_line:
-            # rolling shutter: the per-line gradient [B,T,H,3] (summed over w only; adv_flag, 1/std and the clamp mask applied per line),
-            # then the transpose of the lines mix the forward ran, on the same tables, to the same [P,3] payload
-            if getattr(self, "_g_lines", None) is None:
-                dev = self._logits.device
-                self._g_lines = torch.zeros((self.B, self.T, self.H, 3), dtype=torch.float32, device=dev)
-                self._lines_scratch = torch.empty(self.B * self.T * ops.FLICKER_LINES_MAX_TAPS * 3, dtype=torch.float32, device=dev)
-            self._grad_reduce(a, self._g_lines)
-            ops.flicker_lines_mix_grad(self._g_lines, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
-                                       out=red[:n].view(self.P, 3), scratch=self._lines_scratch)
-        elif self.video_time:
-            # per-clip gradient [B,T,3] (adv_flag, 1/std and the delta-clamp mask applied per frame), then its frames folded onto their rows
-            self._grad_reduce(a, self._g_clip)
-            if cap is None:
-                ops.flicker_rows_grad(self._g_clip, self.pert_model.rows_dev, self.P, out=red[:n].view(self.P, 3))
-            else:                                               # the transpose of the mix the forward ran, on the same tables
-                ops.flicker_rows_mix_grad(self._g_clip, self.pert_model.rows_dev, self.P, self.pert_model.taps_dev, self.pert_model.gain_dev,
-                                          out=red[:n].view(self.P, 3))
-        else:
-            self._grad_reduce(a, red[:n].view(self.T, 3))
+        self._payload_grad(a, cap, _delivered, red[:n].view(self.P, 3))
         ops.pack_batch_sums(pc, 1.0 / gbatch, red[n:])
         parallel.allreduce_sum_(red, self.pg)
         res = StepResult(adv_loss=red[n], softmax=sm, label_prob=pc[:, 1], _argmax_f=pc[:, 3], _labels=labels, _targeted=bool(criterion.targeted))
@@ -1305,7 +1315,7 @@ class FlickerVideoResNet:
             outputs_no_adv = self.video_logits(outputs_no_adv)
         if not bool((outputs_no_adv.argmax(1) == target).all()):
             return None
-        tot, adv_l, reg_l, thick_l, rough_l, maxp_l, corr_l, isadv_l, pert_l = [], [], [], [], [], [], [], [], []
+        hist = self._new_history()
         step, new_chance, is_adversarial = 0, 0, False
         while step < n_iter or not is_adversarial:
             if step > restart_after:
@@ -1317,33 +1327,50 @@ class FlickerVideoResNet:
             r = self.step_videos([video], target, criterion, lr=lr, train=False) if delivered else self.step(inputs, target, criterion, lr=lr)
             adv_class = r["argmax"]
             is_adversarial = bool((adv_class == target_class_id).all()) if targeted_attack else not bool(adv_class.equal(target))
-            isadv_l.append(is_adversarial)
-            tot.append(float(r["loss"])); adv_l.append(float(r["adv_loss"])); reg_l.append(float(r["reg_loss"]))
-            p = self.pert_model.get_perturbation()[0].cpu().numpy()          # after the update, like model.py:1110-1112
-            pert_l.append(p)
-            thick_l.append(float(np.abs(p).mean())); rough_l.append(float(np.abs(np.roll(p, 1, 1) - p).mean()))
-            maxp_l.append(float(r["softmax"].max())); corr_l.append(float(r["label_prob"][0]))
+            # (the perturbation after the update, like model.py:1110-1112)
+            self._record(hist, is_adversarial, r["loss"], r["adv_loss"], r["reg_loss"], self.pert_model.get_perturbation()[0].cpu().numpy(),
+                         r["softmax"].max(), r["label_prob"][0])
             if log_every and step % log_every == 0:
-                print(f"batch {step} of {n_iter} | loss = {tot[-1]:.4f} | adv loss = {adv_l[-1]:.4f} | reg loss = {reg_l[-1]:.4f} | "
-                      f"pert_thickness = {thick_l[-1]:.4f} | pert_roughness = {rough_l[-1]:.4f}", flush=True)
+                print(f"batch {step} of {n_iter} | loss = {hist['loss/total'][-1]:.4f} | adv loss = {hist['loss/adv_loss'][-1]:.4f} | "
+                      f"reg loss = {hist['loss/reg_loss'][-1]:.4f} | pert_thickness = {hist['perturbation/thickness'][-1]:.4f} | "
+                      f"pert_roughness = {hist['perturbation/roughness'][-1]:.4f}", flush=True)
             step += 1
-        p = self.pert_model.get_perturbation()[0].cpu().numpy()
-        res = {"loss/total": tot, "loss/adv_loss": adv_l, "loss/reg_loss": reg_l, "perturbation/thickness": thick_l,
-               "perturbation/roughness": rough_l, "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": pert_l,
-               "prob_clean_input": outputs_no_adv, "label": target.cpu().numpy(), "is_adversarial": isadv_l,
-               "max_prob": maxp_l, "correct_cls_prob": corr_l, "restarts": new_chance}
-        if self.video_time:                                  # the perturbations above have flicker_period rows, not sample_length
+        res = self._attack_result(hist, self.pert_model.get_perturbation()[0].cpu().numpy(), outputs_no_adv, target, new_chance)
+        if export_u8:
+            if delivered:
+                # the delivered video itself: flickered whole at its own resolution, its test-split clips cut from the stored bytes
+                kept = {}
+                ql = self._adversarial_logits(None, [video], [0] * G, np.concatenate(self.last_sampling), "video", delivered=kept)
+                frames = kept[0]
+            else:
+                frames = self.adversarial_frames(inputs)
+                ql = self.logits(frames, False)
+            res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
+        return res
+
+    @staticmethod
+    def _new_history():
+        """the per-iteration lists of one single-video attack, under the keys its result holds them by (model.py:1193-1203)"""
+        return {k: [] for k in ("loss/total", "loss/adv_loss", "loss/reg_loss", "perturbation/thickness", "perturbation/roughness", "perturbation",
+                                "is_adversarial", "max_prob", "correct_cls_prob")}
+
+    @staticmethod
+    def _record(hist, is_adversarial, loss, adv_loss, reg_loss, p, max_prob, label_prob):
+        """one iteration into ``hist``.  ``p``: the clamped perturbation after the update as a numpy array in the reference's layout
+        [3,T,1,1] -- the memory layout ``get_perturbation()`` hands over (numpy's float32 mean depends on it in the last bit)"""
+        for key, v in (("loss/total", loss), ("loss/adv_loss", adv_loss), ("loss/reg_loss", reg_loss), ("perturbation/thickness", np.abs(p).mean()),
+                       ("perturbation/roughness", np.abs(np.roll(p, 1, 1) - p).mean()), ("max_prob", max_prob), ("correct_cls_prob", label_prob)):
+            hist[key].append(float(v))
+        hist["is_adversarial"].append(is_adversarial)
+        hist["perturbation"].append(p)
+
+    def _attack_result(self, hist, p, clean, target, restarts):
+        """the result dict of one single-video attack (model.py:1193-1203): its history, the final clamped perturbation ``p``'s norm, the
+        clean logits, the label and the restarts taken"""
+        res = dict(hist, **{"perturbation/inf_norm": float(np.abs(p).max()), "prob_clean_input": clean, "label": target.cpu().numpy(),
+                            "restarts": restarts})
+        if self.video_time:                                  # the perturbations have flicker_period rows, not sample_length
             res.update(flicker_time=self.flicker_time, flicker_period=self.P)
-        if export_u8 and delivered:
-            # the delivered video itself: flickered whole at its own resolution, its test-split clips cut from the stored bytes
-            frames = self.export_video(video)
-            ql = self.logits(ops.prepare_clips([frames] * G, out=self._prep_buf, im_scale=self.im_scale, input_size=(self.H, self.W),
-                                               rule=self.resize_rule, frame_idx=np.concatenate(self.last_sampling)), False)
-            res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
-        elif export_u8:
-            frames = self.adversarial_frames(inputs)
-            ql = self.logits(frames, False)
-            res.update(self._quantised_verdict(frames, self.video_logits(ql) if G > 1 else ql, target, targeted_attack, target_class_id, export_u8))
         return res
 
     @staticmethod
@@ -1379,15 +1406,11 @@ class FlickerVideoResNet:
                 drawn = None
                 if whole and self.train_delivered:
                     # the delivered chain: ONE draw of tables / boxes / flips serves the clean reference (the untoned preparation) and the step
-                    if getattr(self, "_clean_buf", None) is None or self._clean_buf.shape[0] < len(inputs) * G:
-                        self._clean_buf = torch.empty((max(len(inputs) * G, self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
+                    out = self._clip_buf("_clean_buf", len(inputs) * G)
                     drawn = self._draw_video_clips(inputs, phase == "train", G, "train_an_epoch")
-                    inputs = ops.prepare_clips(drawn[0], out=self._clean_buf, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                                               boxes=drawn[2], flips=drawn[3], frame_idx=drawn[1])
+                    inputs = self._prepare_clips(drawn[0], out=out, boxes=drawn[2], flips=drawn[3], frame_idx=drawn[1])
                 elif whole:
-                    if getattr(self, "_prep_buf", None) is None or self._prep_buf.shape[0] < len(inputs) * G:
-                        self._prep_buf = torch.empty((max(len(inputs) * G, self.B), self.T, self.H, self.W, 3), dtype=torch.float32, device=self._logits.device)
-                    inputs = self.prepare_videos(inputs, train=(phase == "train"), num_samples=G, out=self._prep_buf)
+                    inputs = self.prepare_videos(inputs, train=(phase == "train"), num_samples=G, out=self._clip_buf("_prep_buf", len(inputs) * G))
                 xdt = self._same_dtype(xdt, inputs, f"train_an_epoch ({phase})")
                 augmenting = phase == "train" and self.augment is not None and not whole
                 if augmenting and not self._is_raw(inputs):
@@ -1427,7 +1450,6 @@ class FlickerVideoResNet:
         """``VideoLearnerAdversarial.fit`` (model.py:460-625) with the step-decay schedule (StepLR, model.py:571-573:
         lr_e = lr * gamma ** floor((e - start_epoch) / lr_step_size), default step = ceil(2/3 * epochs), model.py:496-497).
         Returns the list of per-epoch result dicts; ``save_model`` writes ``{model_name}_{epoch:03d}.npy`` (model.py:613-619)."""
-        import os
         if lr_step_size is None:
             lr_step_size = int(np.ceil(2 / 3 * epochs))
         results = []
@@ -1449,7 +1471,6 @@ class FlickerVideoResNet:
         after 4) on its own video with its own perturbation / clamp bound / step counters; a finished slot takes the next video.  Per
         video the iterations are those of the one-by-one loop (bitwise in fp32 when the optimiser state is reset per video; the
         reference's single Adam instance carried from video to video, SURVEY D.5, becomes one carried state PER SLOT here)."""
-        import os
         import itertools
         assert self.per_clip
         B, T = self.B, self.T
@@ -1475,15 +1496,9 @@ class FlickerVideoResNet:
                     return
                 inputs, target, name = nxt
                 self._same_dtype(xdt, inputs, "fit_many_videos")
-                cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
-                dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy") if model_dir else None
-                if dest and os.path.exists(dest):
-                    prev = np.load(dest, allow_pickle=True).tolist()
-                    if prev is None or np.array(prev["is_adversarial"]).any():
-                        continue
-                elif dest and save_model:
-                    os.makedirs(model_dir, exist_ok=True)
-                    np.save(dest, None)
+                dest, todo = self._open_result_file(model_dir, name, target, label_id_to_text, save_model)
+                if not todo:
+                    continue
                 self.pert_model.init_clip(b, (rng.random(self.pert_model.size, dtype=np.float32) * 2 - 1) * 0.005)     # model.py:938-947
                 if reset_optimizer_per_video:                # (pgd keeps no moments: only the counter is reset)
                     if not self.pgd:
@@ -1502,16 +1517,12 @@ class FlickerVideoResNet:
                     out[str(name)] = None                                  # model.py:1030-1032
                     continue
                 slots[b] = dict(name=str(name), dest=dest, target=target.clone(), clean=clean, step=0, new_chance=0, is_adv=False,
-                                tot=[], adv=[], reg=[], thick=[], rough=[], maxp=[], corr=[], isadv=[], pert=[])
+                                hist=self._new_history())
                 return
 
         def finish(b):
             st = slots[b]
-            p = self.pert_model.clip_perturbation_ref(b).cpu().numpy()
-            res = {"loss/total": st["tot"], "loss/adv_loss": st["adv"], "loss/reg_loss": st["reg"], "perturbation/thickness": st["thick"],
-                   "perturbation/roughness": st["rough"], "perturbation/inf_norm": float(np.abs(p).max()), "perturbation": st["pert"],
-                   "prob_clean_input": st["clean"], "label": st["target"].cpu().numpy(), "is_adversarial": st["isadv"],
-                   "max_prob": st["maxp"], "correct_cls_prob": st["corr"], "restarts": st["new_chance"]}
+            res = self._attack_result(st["hist"], self.pert_model.clip_perturbation_ref(b).cpu().numpy(), st["clean"], st["target"], st["new_chance"])
             # slot b's frames under its own perturbation, scored by the clean uint8 path.  The plan's batch is fixed, so the clean forward
             # runs over all B slots and row b is kept: one extra forward per finished video, off the default path
             if export_u8:
@@ -1519,8 +1530,7 @@ class FlickerVideoResNet:
                 res.update(self._quantised_verdict(frames[b:b + 1], self.logits(frames, False)[b:b + 1], st["target"], targeted_attack, target_class_id,
                                                    export_u8))
             out[st["name"]] = res
-            if st["dest"] and save_model:
-                np.save(st["dest"], dict(res, prob_clean_input=res["prob_clean_input"].cpu().numpy()), allow_pickle=True)
+            self._save_result(st["dest"], res, save_model)
             refill(b)
 
         for b in range(B):
@@ -1551,16 +1561,13 @@ class FlickerVideoResNet:
                     continue
                 adv_class = int(h["argmax"][b])
                 st["is_adv"] = (adv_class == target_class_id) if targeted_attack else (adv_class != int(st["target"][0]))
-                st["isadv"].append(st["is_adv"])
-                st["tot"].append(float(h["loss"][b])); st["adv"].append(float(h["adv_loss"][b])); st["reg"].append(float(h["reg_loss"][b]))
                 p = pcl[b].reshape(T, 1, 1, 3).transpose(3, 0, 1, 2)      # [3,T,1,1], the memory layout get_perturbation() hands the one-by-one loop
                                                                           # (numpy's float32 mean depends on it in the last bit)
-                st["pert"].append(p)
-                st["thick"].append(float(np.abs(p).mean())); st["rough"].append(float(np.abs(np.roll(p, 1, 1) - p).mean()))
-                st["maxp"].append(float(h["softmax"][b].max())); st["corr"].append(float(h["label_prob"][b]))
+                self._record(st["hist"], st["is_adv"], h["loss"][b], h["adv_loss"][b], h["reg_loss"][b], p, h["softmax"][b].max(), h["label_prob"][b])
                 if log_every and st["step"] % log_every == 0:
-                    print(f"[{st['name']}] batch {st['step']} of {n_iter} | loss = {st['tot'][-1]:.4f} | adv loss = {st['adv'][-1]:.4f} | "
-                          f"reg loss = {st['reg'][-1]:.4f}", flush=True)
+                    hist = st["hist"]
+                    print(f"[{st['name']}] batch {st['step']} of {n_iter} | loss = {hist['loss/total'][-1]:.4f} | "
+                          f"adv loss = {hist['loss/adv_loss'][-1]:.4f} | reg loss = {hist['loss/reg_loss'][-1]:.4f}", flush=True)
                 st["step"] += 1
         return out
 
@@ -1570,7 +1577,6 @@ class FlickerVideoResNet:
         a video whose result file already shows a success is skipped, a placeholder (None) is written before the attack, the
         perturbation restarts from U(-1,1) * 0.005 and the clamp norm from ``max_norm`` (model.py:938-947).  Result files are
         ``<name>_@<class>.npy`` (model.py:917-921).  Returns {name: result dict or None}."""
-        import os
         if self.per_clip:
             return self._fit_many_videos_batched(videos, criterion, lr, model_dir, label_id_to_text, save_model, n_iter, targeted_attack,
                                                  target_class_id, reset_optimizer_per_video=reset_optimizer_per_video, **kw)
@@ -1580,15 +1586,9 @@ class FlickerVideoResNet:
         for inputs, target, name in videos:
             # (clips_per_video > 1: a whole uint8 video, possibly as a one-element list, goes through to fit_single_video_attack)
             xdt = self._same_dtype(xdt, inputs[0] if isinstance(inputs, (list, tuple)) and len(inputs) else inputs, "fit_many_videos")
-            cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
-            dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy") if model_dir else None
-            if dest and os.path.exists(dest):
-                prev = np.load(dest, allow_pickle=True).tolist()
-                if prev is None or np.array(prev["is_adversarial"]).any():
-                    continue                                  # attacked before (None: the clean clip was misclassified / aborted run)
-            elif dest and save_model:
-                os.makedirs(model_dir, exist_ok=True)
-                np.save(dest, None)
+            dest, todo = self._open_result_file(model_dir, name, target, label_id_to_text, save_model)
+            if not todo:
+                continue
             self.pert_model.init_perturbation(((rng.random(self.pert_model.size, dtype=np.float32) * 2 - 1) * 0.005))
             self.pert_model.dynamic_max_norm = self.pert_model.max_norm
             if reset_optimizer_per_video:                       # (the reference carries ONE Adam state from video to video, SURVEY D.5: default)
@@ -1598,10 +1598,32 @@ class FlickerVideoResNet:
             res = self.fit_single_video_attack(inputs, target, criterion, lr=lr, n_iter=n_iter, targeted_attack=targeted_attack,
                                                target_class_id=target_class_id, **kw)
             out[str(name)] = res
-            if res is not None and dest and save_model:
-                res = dict(res, prob_clean_input=res["prob_clean_input"].cpu().numpy())
-                np.save(dest, res, allow_pickle=True)
+            self._save_result(dest, res, save_model)
         return out
+
+    @staticmethod
+    def _open_result_file(model_dir, name, target, label_id_to_text, save_model):
+        """the result file of one video of ``fit_many_videos`` -> ``(dest, attack)``: ``<model_dir>/<name>_@<class>.npy`` (model.py:917-921;
+        None without a ``model_dir``) and whether the video is still to be attacked -- not when the file is there and shows a success or
+        holds None (the clean clip was misclassified, or the run was aborted).  A file about to be written (``save_model``) gets its
+        placeholder, None, before the attack"""
+        cls = (label_id_to_text[int(target[0])] if label_id_to_text is not None else str(int(target[0]))).replace(" ", "_")
+        if not model_dir:
+            return None, True
+        dest = os.path.join(model_dir, f"{os.path.basename(str(name))}_@{cls}.npy")
+        if os.path.exists(dest):
+            prev = np.load(dest, allow_pickle=True).tolist()
+            return dest, not (prev is None or np.array(prev["is_adversarial"]).any())
+        if save_model:
+            os.makedirs(model_dir, exist_ok=True)
+            np.save(dest, None)
+        return dest, True
+
+    @staticmethod
+    def _save_result(dest, res, save_model):
+        """an attack's result into its file, in the placeholder's place (a misclassified clean clip keeps the placeholder)"""
+        if res is not None and dest and save_model:
+            np.save(dest, dict(res, prob_clean_input=res["prob_clean_input"].cpu().numpy()), allow_pickle=True)
 
 
 class VideoLearnerAdversarial(FlickerVideoResNet):
@@ -1612,9 +1634,9 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
     ``.pert_model``, ``.model_name``, ``.results``, ``.fit``, ``.fit_many_videos``, ``.fit_single_video_attack`` as in the reference."""
 
     def __init__(self, dataset=None, num_classes=None, base_model="r2plus1d_18", sample_length=None, cyclic_pert=False, l_inf_pert_norm=0.1,
-                 attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, image_size=112, dtype="bf16", device=0,
-                 process_group=None, optimizer="adam", sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False, codec=None):
+                 attack_type="flickering", labaels_id_to_text=None, weights=None, batch_size=None, optimizer="adam", **engine_kw):
+        # ``engine_kw``: the other keywords of the engine alone (``image_size``, ``dtype``, ``flicker_time``, ... : FlickerVideoResNet), passed
+        # on as they are -- one the engine does not know is its TypeError
         from . import videoresnet_spec as vs
         if weights is None:
             raise ValueError("weights: a torchvision state_dict ({name: array}) or a .pth / .npz path -- there is no network to download "
@@ -1625,11 +1647,7 @@ class VideoLearnerAdversarial(FlickerVideoResNet):
             weights = vs.load_weights(weights, base_model if base_model in vs.ARCHS else vs.resolve_model(base_model, sample_length)[0])
         if batch_size is None:
             batch_size = getattr(dataset, "batch_size", 1)
-        super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, image_size=image_size, dtype=dtype,
-                         device=device, l_inf_pert_norm=l_inf_pert_norm, cyclic_pert=cyclic_pert, num_classes=num_classes,
-                         process_group=process_group, attack_type=attack_type, optimizer=optimizer, sampling=sampling,
-                         clips_per_video=clips_per_video, video_reduce=video_reduce, quantise_train=quantise_train,
-                         flicker_time=flicker_time, flicker_period=flicker_period, capture=capture, flicker_model=flicker_model,
-                         response=response, train_delivered=train_delivered, codec=codec)
+        super().__init__(base_model, weights, batch_size=batch_size, sample_length=sample_length, l_inf_pert_norm=l_inf_pert_norm,
+                         cyclic_pert=cyclic_pert, num_classes=num_classes, attack_type=attack_type, optimizer=optimizer, **engine_kw)
         self.dataset, self.labaels_id_to_text = dataset, labaels_id_to_text
         self.results = {}

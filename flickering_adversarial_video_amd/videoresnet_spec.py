@@ -1343,3 +1343,13 @@ def codec_from_arguments(ap, a, used):
         return Codec(a.codec_quality, a.codec_subsampling or "420")
     except ValueError as e:
         ap.error(str(e))
+
+
+def flicker_keywords_from_arguments(a, delivered=False):
+    """the flicker keywords of ``FlickerVideoResNet`` from the scripts' parsed arguments, ``a.capture`` and ``a.codec`` being what
+    ``capture_from_arguments`` / ``codec_from_arguments`` returned.  ``delivered``: the construction of a script mode that has whole
+    videos -- it also takes ``train_delivered`` and, only with it, the codec (elsewhere the codec acts on evaluation and export)"""
+    kw = dict(flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture, flicker_model=a.flicker_model, response=a.response)
+    if delivered:
+        kw.update(train_delivered=a.train_delivered, codec=a.codec if a.train_delivered else None)
+    return kw

@@ -69,9 +69,7 @@ def run_whole_videos(a):
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, sampling=sampling,
                                  clips_per_video=G, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered,
-                                 codec=a.codec if a.train_delivered else None)
+                                 **vs.flicker_keywords_from_arguments(a, delivered=True))
     dest =os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)
@@ -246,8 +244,7 @@ def main():
     learner = FlickerVideoResNet(a.base_model, W, batch_size=a.batch, sample_length=clips.shape[1], image_size=S, dtype=a.dtype,
                                  l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type, per_clip=a.batch > 1,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response)
+                                 **vs.flicker_keywords_from_arguments(a))
     dest = os.path.join(a.results_root, learner.model_name, "single_video_attack", a.attack_type,
                         f"linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
     crit = Losses(beta_1=BETA_1, lambda_=LAMBDA, targeted=TARGETED_ATTACK, improve_loss=IMPROVE_LOSS, logits=USE_LOGITS, attack_type=a.attack_type)

@@ -166,9 +166,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule, augment=augment, sampling=sampling,
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response, train_delivered=a.train_delivered,
-                                 codec=a.codec if a.train_delivered else None)
+                                 **vs.flicker_keywords_from_arguments(a, delivered=True))
     codec_keys = {} if a.codec is None else {"codec_quality": np.int64(a.codec.quality), "codec_subsampling": a.codec.subsampling}
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
@@ -395,8 +393,7 @@ def main():
                                  device=local_rank, l_inf_pert_norm=L_INF_PERT_NORM, cyclic_pert=CYCLIC_PERT, attack_type=a.attack_type,
                                  optimizer=a.optimizer, im_scale=a.im_scale, resize_rule=a.resize_rule,
                                  augment=None if host_aug else augment, quantise_train=a.quantise_train,
-                                 flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture,
-                                 flicker_model=a.flicker_model, response=a.response)
+                                 **vs.flicker_keywords_from_arguments(a))
     host_rng = random.Random(augment["seed"] + rank) if host_aug else None
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(xtr)}_v_{len(xva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")

@@ -287,9 +287,7 @@ def main():
 
         def step_videos():
             e = engs["videos"]
-            if getattr(e, "_prep_buf", None) is None:
-                e._prep_buf = torch.empty((B, T, 112, 112, 3), dtype=torch.float32, device="cuda")
-            e.step(e.prepare_videos(videos, train=True, out=e._prep_buf), labels, crit)
+            e.step(e.prepare_videos(videos, train=True, out=e._clip_buf("_prep_buf")), labels, crit)
 
         def step_prepared():
             engs["prepared"].step(ready[it[0] % nb], labels, crit)
