@@ -1022,44 +1022,66 @@ __global__ __launch_bounds__(256) void flicker_rows_gather_kernel(const float* d
   }
 }
 
-// one thread = one output (row r, channel c): it walks the table in ascending i and adds the frames that carry its row, so every sum has
-// ONE fixed order whatever the grid.  The table is staged in LDS piece by piece by the whole workgroup (one HBM read of `rows` per
-// workgroup, at most 8 workgroups); all lanes of a wave read the same LDS entry (a broadcast).  g_clip is read only on a hit: 3*n
-// loads over the launch.  Threads past the last output still stage and meet every barrier.
-__global__ __launch_bounds__(256) void flicker_rows_grad_kernel(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows) {
+// The fold skeleton of the three transposes below (one thread = one output (row r, channel c) of [P][3]): every entry of `rows` is
+// handed to `entry(i, q)` -- i the frame's index, q its row -- in ascending i, so a sum the caller keeps has ONE fixed order whatever
+// the grid.  The table is staged in LDS piece by piece by the whole workgroup (one HBM read of `rows` per workgroup, at most 8
+// workgroups); all lanes of a wave read the same LDS entry (a broadcast).  EVERY thread of the workgroup calls this and meets every
+// barrier; only a `live` one (its output exists) walks the entries.  `entry` sees bad rows too: it must pass over a q outside [0,P).
+template <typename Entry>
+__device__ static inline void fold_rows(const int32_t* rows, int n, bool live, Entry entry) {
   __shared__ int32_t sh[ROWS_PIECE];
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  const bool live = o < 3 * P;
-  const int r = o / 3, c = o - 3 * r;
-  float s = 0.f;
   for (int base = 0; base < n; base += ROWS_PIECE) {
     const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
     for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
     __syncthreads();
     if (live)
-      for (int j = 0; j < m; ++j)
-        if (sh[j] == r) s += g_clip[(size_t)(base + j) * 3 + c];
+      for (int j = 0; j < m; ++j) entry(base + j, sh[j]);
     __syncthreads();            // sh is refilled by the next piece
   }
-  if (live) g_rows[o] = s;
 }
+
+// the row gradient: the frames that carry row r (inside [0,P), so a bad row matches none) are added in ascending order from +0.  g_clip
+// is read only on a hit: 3*n loads over the launch.
+__global__ __launch_bounds__(256) void flicker_rows_grad_kernel(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows) {
+  const int o = blockIdx.x * 256 + threadIdx.x, r = o / 3, c = o - 3 * r;
+  float s = 0.f;
+  fold_rows(rows, n, o < 3 * P, [&](int i, int q) {
+    if (q == r) s += g_clip[(size_t)i * 3 + c];
+  });
+  if (o < 3 * P) g_rows[o] = s;
+}
+
+// The range checks every entry point of this seam makes, under its own name `who` (one without clips, lines or taps passes 1 for them)
+static int check_seam(const char* who, int n, int clip_T, int H, int K, int kmax, int P) {
+  FLK_REQUIRE(n >= 1, "%s: n must be >= 1 (got %d)", who, n);
+  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "%s: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", who, clip_T, n);
+  FLK_REQUIRE(H >= 1, "%s: H (lines of a frame) must be >= 1 (got %d)", who, H);
+  FLK_REQUIRE(K >= 1 && K <= kmax, "%s: K (taps of a clip or line) must be 1 .. %d (got %d)", who, kmax, K);
+  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "%s: period P must be 1 .. %d (got %d)", who, ROWS_MAX_P, P);
+  return FLK_OK;
+}
+
+// the grid of a kernel that strides over `values` outputs: one thread each, at most 1024 workgroups of 256
+static inline dim3 strided_grid(long values) {
+  const long blocks = (values + 255) / 256;
+  return dim3((unsigned)(blocks > 1024 ? 1024 : blocks));
+}
+
+// the grid of a fold: one thread per output of [P][3]
+static inline dim3 fold_grid(int P) { return dim3((unsigned)((3 * P + 255) / 256)); }
 
 extern "C" int flk_flicker_rows_gather(const float* delta, int P, const int32_t* rows, int n, float* delta_clip, void* stream) {
   FLK_REQUIRE(delta && rows && delta_clip, "flk_flicker_rows_gather: null argument");
-  FLK_REQUIRE(n >= 1, "flk_flicker_rows_gather: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_gather: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  const long blocks = (3L * n + 255) / 256;
-  FLK_LAUNCH_KERNEL(flicker_rows_gather_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
-                     delta_clip);
+  if (int e = check_seam("flk_flicker_rows_gather", n, 1, 1, 1, 1, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_rows_gather_kernel, strided_grid(3L * n), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n, delta_clip);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
 
 extern "C" int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, int n, int P, float* g_rows, void* stream) {
   FLK_REQUIRE(g_clip && rows && g_rows, "flk_flicker_rows_grad: null argument");
-  FLK_REQUIRE(n >= 1, "flk_flicker_rows_grad: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  FLK_LAUNCH_KERNEL(flicker_rows_grad_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, P, g_rows);
+  if (int e = check_seam("flk_flicker_rows_grad", n, 1, 1, 1, 1, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_rows_grad_kernel, fold_grid(P), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, P, g_rows);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -1072,61 +1094,53 @@ extern "C" int flk_flicker_rows_grad(const float* g_clip, const int32_t* rows, i
 // restate both bit for bit; with K = 1, tap 1 and no gain (or gain 1) they are the two kernels above, bit for bit (1 * x = x).
 constexpr int ROWS_MIX_MAX_K = 4;
 
-// one thread = one value of delta_clip; raw values; the first product starts the sum (not 0 + product: a -0 stays -0)
+// The tap loop: one value of the mix, channel c of a frame (or line) of clip b whose first row is `r` and whose taps are w[0..K).
+// Raw values; a row outside [0,P) is clamped into it; the first product starts the sum (not 0 + product: a -0 stays -0); the gain comes
+// last.  The rolling-shutter mix below calls it with each line's own taps.
+__device__ static inline float mix_value(const float* delta, int P, int r, int c, const float* w, int K, const float* gain, int b) {
+  r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
+  float acc = mul_rn(w[0], delta[r * 3 + c]);
+  for (int k = 1; k < K; ++k) {
+    r = r + 1 == P ? 0 : r + 1;
+    acc = add_rn(acc, mul_rn(w[k], delta[r * 3 + c]));
+  }
+  return gain ? mul_rn(gain[(size_t)b * 3 + c], acc) : acc;
+}
+
+// one thread = one value of delta_clip
 __global__ __launch_bounds__(256) void flicker_rows_mix_kernel(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps,
                                                                int K, const float* gain, float* delta_clip) {
   const long total = 3L * n;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const int f = (int)(i / 3), c = (int)(i - 3L * f), b = f / clip_T;
-    int r = rows[f];
-    r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
-    const float* w = taps + (size_t)b * K;
-    float acc = mul_rn(w[0], delta[r * 3 + c]);
-    for (int k = 1; k < K; ++k) {
-      r = r + 1 == P ? 0 : r + 1;
-      acc = add_rn(acc, mul_rn(w[k], delta[r * 3 + c]));
-    }
-    delta_clip[i] = gain ? mul_rn(gain[(size_t)b * 3 + c], acc) : acc;
+    delta_clip[i] = mix_value(delta, P, rows[f], c, taps + (size_t)b * K, K, gain, b);
   }
 }
 
-// The transpose, in the form of flicker_rows_grad_kernel: one thread = one output (row r, channel c), the table staged in LDS piece by
-// piece, frames in ascending i and within a frame taps in ascending k, from +0.  Frame i (row q) reaches row r through the taps
-// k = (r - q) mod P, + P, + 2P, ... below K: more than one when P < K, and then all of them are added.  The clip index and the frame's
-// place in its clip are carried along (uniform over the workgroup: no division per frame).  g_clip is read only on a hit.  Threads
-// past the last output still stage and meet every barrier.
+// The transpose, a fold_rows: frames in ascending i and within a frame taps in ascending k, from +0.  Frame i (row q) reaches row r
+// through the taps k = (r - q) mod P, + P, + 2P, ... below K: more than one when P < K, and then all of them are added.  The clip index
+// and the frame's place in its clip are carried along over every entry, hit or not (no division per frame: one on a hit alone costs a
+// tenth of the kernel's time).  g_clip is read only on a hit.
 __global__ __launch_bounds__(256) void flicker_rows_mix_grad_kernel(const float* g_clip, const int32_t* rows, int n, int clip_T, const float* taps,
                                                                     int K, const float* gain, int P, float* g_rows) {
-  __shared__ int32_t sh[ROWS_PIECE];
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  const bool live = o < 3 * P;
-  const int r = o / 3, c = o - 3 * r;
+  const int o = blockIdx.x * 256 + threadIdx.x, r = o / 3, c = o - 3 * r;
   float s = 0.f;
-  for (int base = 0; base < n; base += ROWS_PIECE) {
-    const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
-    for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
-    __syncthreads();
-    if (live) {
-      int b = base / clip_T, t = base - b * clip_T;
-      for (int j = 0; j < m; ++j) {
-        const int q = sh[j];
-        if (q >= 0 && q < P) {
-          int k = r - q;
-          k = k < 0 ? k + P : k;
-          if (k < K) {
-            const float g = g_clip[(size_t)(base + j) * 3 + c];
-            for (; k < K; k += P) {
-              const float w = taps[(size_t)b * K + k];
-              s = add_rn(s, mul_rn(gain ? mul_rn(gain[(size_t)b * 3 + c], w) : w, g));
-            }
-          }
+  int b = 0, t = 0;
+  fold_rows(rows, n, o < 3 * P, [&](int i, int q) {
+    if (q >= 0 && q < P) {
+      int k = r - q;
+      k = k < 0 ? k + P : k;
+      if (k < K) {
+        const float g = g_clip[(size_t)i * 3 + c];
+        for (; k < K; k += P) {
+          const float w = taps[(size_t)b * K + k];
+          s = add_rn(s, mul_rn(gain ? mul_rn(gain[(size_t)b * 3 + c], w) : w, g));
         }
-        if (++t == clip_T) { t = 0; ++b; }
       }
     }
-    __syncthreads();            // sh is refilled by the next piece
-  }
-  if (live) g_rows[o] = s;
+    if (++t == clip_T) { t = 0; ++b; }
+  });
+  if (o < 3 * P) g_rows[o] = s;
 }
 
 extern "C" int flk_flicker_rows_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, const float* taps, int K, const float* gain,
@@ -1135,13 +1149,9 @@ extern "C" int flk_flicker_rows_mix(const float* delta, int P, const int32_t* ro
   FLK_REQUIRE(rows, "flk_flicker_rows_mix: rows is null");
   FLK_REQUIRE(taps, "flk_flicker_rows_mix: taps is null");
   FLK_REQUIRE(delta_clip, "flk_flicker_rows_mix: delta_clip is null");
-  FLK_REQUIRE(n >= 1, "flk_flicker_rows_mix: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_rows_mix: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
-  FLK_REQUIRE(K >= 1 && K <= ROWS_MIX_MAX_K, "flk_flicker_rows_mix: K (taps per clip) must be 1 .. %d (got %d)", ROWS_MIX_MAX_K, K);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_mix: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  const long blocks = (3L * n + 255) / 256;
-  FLK_LAUNCH_KERNEL(flicker_rows_mix_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
-                     clip_T, taps, K, gain, delta_clip);
+  if (int e = check_seam("flk_flicker_rows_mix", n, clip_T, 1, K, ROWS_MIX_MAX_K, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_rows_mix_kernel, strided_grid(3L * n), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n, clip_T, taps, K, gain,
+                     delta_clip);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -1152,12 +1162,8 @@ extern "C" int flk_flicker_rows_mix_grad(const float* g_clip, const int32_t* row
   FLK_REQUIRE(rows, "flk_flicker_rows_mix_grad: rows is null");
   FLK_REQUIRE(taps, "flk_flicker_rows_mix_grad: taps is null");
   FLK_REQUIRE(g_rows, "flk_flicker_rows_mix_grad: g_rows is null");
-  FLK_REQUIRE(n >= 1, "flk_flicker_rows_mix_grad: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_rows_mix_grad: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
-  FLK_REQUIRE(K >= 1 && K <= ROWS_MIX_MAX_K, "flk_flicker_rows_mix_grad: K (taps per clip) must be 1 .. %d (got %d)", ROWS_MIX_MAX_K, K);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_rows_mix_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  FLK_LAUNCH_KERNEL(flicker_rows_mix_grad_kernel, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, clip_T,
-                     taps, K, gain, P, g_rows);
+  if (int e = check_seam("flk_flicker_rows_mix_grad", n, clip_T, 1, K, ROWS_MIX_MAX_K, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_rows_mix_grad_kernel, fold_grid(P), dim3(256), 0, (hipStream_t)stream, g_clip, rows, n, clip_T, taps, K, gain, P, g_rows);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -1175,15 +1181,7 @@ __global__ __launch_bounds__(256) void flicker_lines_mix_kernel(const float* del
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
     const long fh = i / 3;
     const int c = (int)(i - 3 * fh), f = (int)(fh / H), h = (int)(fh - (long)f * H), b = f / clip_T;
-    int r = rows[f];
-    r = r < 0 ? 0 : r > P - 1 ? P - 1 : r;
-    const float* w = taps + ((size_t)b * H + h) * K;
-    float acc = mul_rn(w[0], delta[r * 3 + c]);
-    for (int k = 1; k < K; ++k) {
-      r = r + 1 == P ? 0 : r + 1;
-      acc = add_rn(acc, mul_rn(w[k], delta[r * 3 + c]));
-    }
-    out[i] = gain ? mul_rn(gain[(size_t)b * 3 + c], acc) : acc;
+    out[i] = mix_value(delta, P, rows[f], c, taps + ((size_t)b * H + h) * K, K, gain, b);
   }
 }
 
@@ -1206,30 +1204,19 @@ __global__ __launch_bounds__(256) void flicker_lines_mix_grad_stage1(const float
   }
 }
 
-// transpose, stage 2: flicker_rows_mix_grad_kernel's fold over s[n][K][3] (the coefficients are inside s already): one thread = one
-// output (row r, channel c), rows staged in LDS piece by piece, frames ascending, taps ascending, from +0
+// transpose, stage 2: flicker_rows_mix_grad_kernel's fold over s[n][K][3] (the coefficients are inside s already): frames ascending,
+// taps ascending, from +0
 __global__ __launch_bounds__(256) void flicker_lines_mix_grad_stage2(const float* sbuf, const int32_t* rows, int n, int K, int P, float* g_rows) {
-  __shared__ int32_t sh[ROWS_PIECE];
-  const int o = blockIdx.x * 256 + threadIdx.x;
-  const bool live = o < 3 * P;
-  const int r = o / 3, c = o - 3 * r;
+  const int o = blockIdx.x * 256 + threadIdx.x, r = o / 3, c = o - 3 * r;
   float s = 0.f;
-  for (int base = 0; base < n; base += ROWS_PIECE) {
-    const int m = n - base < ROWS_PIECE ? n - base : ROWS_PIECE;
-    for (int j = threadIdx.x; j < m; j += 256) sh[j] = rows[base + j];
-    __syncthreads();
-    if (live)
-      for (int j = 0; j < m; ++j) {
-        const int q = sh[j];
-        if (q >= 0 && q < P) {
-          int k = r - q;
-          k = k < 0 ? k + P : k;
-          for (; k < K; k += P) s = add_rn(s, sbuf[((size_t)(base + j) * K + k) * 3 + c]);
-        }
-      }
-    __syncthreads();            // sh is refilled by the next piece
-  }
-  if (live) g_rows[o] = s;
+  fold_rows(rows, n, o < 3 * P, [&](int i, int q) {
+    if (q >= 0 && q < P) {
+      int k = r - q;
+      k = k < 0 ? k + P : k;
+      for (; k < K; k += P) s = add_rn(s, sbuf[((size_t)i * K + k) * 3 + c]);
+    }
+  });
+  if (o < 3 * P) g_rows[o] = s;
 }
 
 extern "C" int flk_flicker_lines_mix(const float* delta, int P, const int32_t* rows, int n, int clip_T, int H, const float* taps, int K,
@@ -1238,14 +1225,9 @@ extern "C" int flk_flicker_lines_mix(const float* delta, int P, const int32_t* r
   FLK_REQUIRE(rows, "flk_flicker_lines_mix: rows is null");
   FLK_REQUIRE(taps, "flk_flicker_lines_mix: taps is null");
   FLK_REQUIRE(out, "flk_flicker_lines_mix: out is null");
-  FLK_REQUIRE(n >= 1, "flk_flicker_lines_mix: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_lines_mix: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
-  FLK_REQUIRE(H >= 1, "flk_flicker_lines_mix: H (lines of a frame) must be >= 1 (got %d)", H);
-  FLK_REQUIRE(K >= 1 && K <= LINES_MIX_MAX_K, "flk_flicker_lines_mix: K (taps per line) must be 1 .. %d (got %d)", LINES_MIX_MAX_K, K);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_lines_mix: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  const long blocks = (3L * n * H + 255) / 256;
-  FLK_LAUNCH_KERNEL(flicker_lines_mix_kernel, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n,
-                     clip_T, H, taps, K, gain, out);
+  if (int e = check_seam("flk_flicker_lines_mix", n, clip_T, H, K, LINES_MIX_MAX_K, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_kernel, strided_grid(3L * n * H), dim3(256), 0, (hipStream_t)stream, delta, P, rows, n, clip_T, H, taps, K, gain,
+                     out);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
@@ -1257,16 +1239,10 @@ extern "C" int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* r
   FLK_REQUIRE(taps, "flk_flicker_lines_mix_grad: taps is null");
   FLK_REQUIRE(scratch, "flk_flicker_lines_mix_grad: scratch is null");
   FLK_REQUIRE(g_rows, "flk_flicker_lines_mix_grad: g_rows is null");
-  FLK_REQUIRE(n >= 1, "flk_flicker_lines_mix_grad: n must be >= 1 (got %d)", n);
-  FLK_REQUIRE(clip_T >= 1 && n % clip_T == 0, "flk_flicker_lines_mix_grad: clip_T must be >= 1 and divide n (got clip_T %d, n %d)", clip_T, n);
-  FLK_REQUIRE(H >= 1, "flk_flicker_lines_mix_grad: H (lines of a frame) must be >= 1 (got %d)", H);
-  FLK_REQUIRE(K >= 1 && K <= LINES_MIX_MAX_K, "flk_flicker_lines_mix_grad: K (taps per line) must be 1 .. %d (got %d)", LINES_MIX_MAX_K, K);
-  FLK_REQUIRE(P >= 1 && P <= ROWS_MAX_P, "flk_flicker_lines_mix_grad: period P must be 1 .. %d (got %d)", ROWS_MAX_P, P);
-  const long blocks = (3L * n * K + 255) / 256;
-  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage1, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, (hipStream_t)stream, g_lines, n,
-                     clip_T, H, taps, K, gain, scratch);
-  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage2, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, (hipStream_t)stream, scratch, rows, n, K, P,
-                     g_rows);
+  if (int e = check_seam("flk_flicker_lines_mix_grad", n, clip_T, H, K, LINES_MIX_MAX_K, P)) return e;
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage1, strided_grid(3L * n * K), dim3(256), 0, (hipStream_t)stream, g_lines, n, clip_T, H, taps, K, gain,
+                     scratch);
+  FLK_LAUNCH_KERNEL(flicker_lines_mix_grad_stage2, fold_grid(P), dim3(256), 0, (hipStream_t)stream, scratch, rows, n, K, P, g_rows);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

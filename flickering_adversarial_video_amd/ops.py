@@ -21,8 +21,22 @@ def same_pad(n, k, s):
     return out, tot // 2
 
 
-class ConvWeights:
+class _HandleOwner:
+    """owns ``self.handle``, an object of the library that ``_destroy`` (the name of a C function) frees -- once, when the owner goes"""
+    _destroy = None
+
+    def __del__(self):
+        try:
+            if getattr(self, "handle", None):
+                getattr(load(), self._destroy)(self.handle)
+                self.handle = None
+        except Exception:      # interpreter shutdown
+            pass
+
+
+class ConvWeights(_HandleOwner):
     """Packed weights of one convolution operator (flk_conv_weights)."""
+    _destroy = "flk_conv_weights_destroy"
 
     def __init__(self, w_dhwio, dtype, nf, row_scale=None, transpose=False, cin_split=0):
         w = np.ascontiguousarray(w_dhwio, dtype=np.float32)
@@ -55,14 +69,6 @@ class ConvWeights:
         check(load().flk_conv_weights_create_s2d_stem(ptr(w), self.cout, self.dtype, nf, C.byref(h)))
         self.handle = h
         return self
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                load().flk_conv_weights_destroy(self.handle)
-                self.handle = None
-        except Exception:      # interpreter shutdown
-            pass
 
 
 def conv3d(x, w, **kw):
@@ -186,19 +192,15 @@ def maxpool3d_bwd(ctx, gout, mask=None, *, gout_coff=0, gin=None, gin_coff=0, ma
     return gin
 
 
-class PoolGemmWeights:
+class PoolGemmWeights(_HandleOwner):
     """MFMA-packed Wt [K][C] (a 1x1x1 unit's weight transposed x batch-norm scale) for maxpool3d_bwd_gemm"""
+    _destroy = "flk_pool_gemm_weights_destroy"
 
     def __init__(self, wt_kc):
         w = np.ascontiguousarray(wt_kc, dtype=np.float32)
         self.K, self.C = w.shape
         self.handle = C.c_void_p()
         check(load().flk_pool_gemm_weights_create(w.ctypes.data_as(C.c_void_p), self.K, self.C, C.byref(self.handle)))
-
-    def __del__(self):
-        if getattr(self, "handle", None) and self.handle.value:
-            load().flk_pool_gemm_weights_destroy(self.handle)
-            self.handle = C.c_void_p()
 
 
 def maxpool3d_bwd_gemm(ctx, g, weights, g_coff=0, *, gin=None, gin_coff=0):
@@ -319,46 +321,56 @@ def make_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=
             raise ValueError("q_lut: fp32 [256,3] on the device")
     elif q_lut is not None:
         raise ValueError("q_lut without quantise: name the dialect whose encode goes with the table")
-    B, T, H, W, c3 = x.shape
-    assert c3 == 3 and x.is_contiguous() and delta.is_contiguous() and delta.dtype == torch.float32
-    assert x.dtype in (torch.uint8, torch.float32)
-    if x_lut is not None:
-        assert x.dtype == torch.uint8 and not center, "x_lut: uint8 clips, center = False"
-        assert x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda, "x_lut: fp32 [256,3] on the device"
-    # the torch dialect's clips are normalised per channel: a uint8 clip without its table would be read as values 0..255
-    assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
-    a = ApplyArgs()
-    a.x = ptr(x)
-    a.x_is_u8 = int(x.dtype == torch.uint8)
-    # TFRecord path: x = u8/128 - 1 (pre_process_rgb_flow.py:226-234)
-    a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
-    a.delta = ptr(delta)
+    assert x_lut is None or not center, "x_lut: uint8 clips, center = False"
+    a = _fill_apply_args(x, delta, dialect, dclip, adv_flag, shift_x, shift_p, inv_std, lo, hi, dclip_dev, x_lut, per_line)
+    B, T, H, W = a.B, a.T, a.H, a.W
     if per_line:
         if tuple(delta.shape) not in ((T, H, 3), (B, T, H, 3)):
             raise ValueError(f"per_line: delta must be fp32 [{T},{H},3] or [{B},{T},{H},3], got {tuple(delta.shape)}")
         if center or fold_t not in (1, 4):
             raise ValueError(f"per_line: fold_t 1 or 4 without center (the VideoResNet layouts), got fold_t {fold_t}, center {center}")
-        a.delta_dense, a.delta_per_clip, a.delta_per_line = 0, int(delta.dim() == 4), 1
     else:
-        a.delta_dense = int(delta.dim() == 4)
-        a.delta_per_clip = int(delta.dim() == 3)
         assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
     assert not (a.delta_per_clip and (shift_x or shift_p)), "per-clip perturbations: cyclic rolls are drawn per run in the reference; not batched"
+    a.fold_t = fold_t
+    a.center = int(center)      # write x_adv - a*p' (the clean value where the clip is inactive); see Net.forward_flicker
+    if quantise is not None:    # the encode of make_export_args(quantise), the decode of q_lut
+        mul, add, levels = EXPORT_DIALECTS[quantise]
+        a.q_lut, a.q_mul, a.q_add, a.q_levels = ptr(q_lut), (C.c_float * 3)(*mul), (C.c_float * 3)(*add), levels
+        a._keepalive += (q_lut,)
+    return a
+
+
+def _fill_apply_args(x, delta, dialect, dclip, adv_flag, shift_x, shift_p, inv_std, lo, hi, dclip_dev, x_lut, per_line):
+    """the flk_apply_args that ``make_apply_args`` and ``make_export_apply_args`` share: the clip, its decode, the perturbation (its rank
+    names the form; the caller checks the shape) and the scalars of the pixel model.  The fold, ``center``, the quantiser and
+    the period stay with the callers."""
+    B, T, H, W, c3 = x.shape
+    assert c3 == 3 and x.is_contiguous() and delta.is_contiguous() and delta.dtype == torch.float32
+    assert x.dtype in (torch.uint8, torch.float32)
+    if x_lut is not None:
+        assert x.dtype == torch.uint8, "x_lut: uint8 clips, center = False"
+        assert x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda, "x_lut: fp32 [256,3] on the device"
+    # the torch dialect's clips are normalised per channel: a uint8 clip without its table would be read as values 0..255
+    assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
+    a = ApplyArgs()
+    a.x, a.x_is_u8 = ptr(x), int(x.dtype == torch.uint8)
+    # TFRecord path: x = u8/128 - 1 (pre_process_rgb_flow.py:226-234)
+    a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
+    a.delta = ptr(delta)
+    if per_line:
+        a.delta_dense, a.delta_per_clip, a.delta_per_line = 0, int(delta.dim() == 4), 1
+    else:
+        a.delta_dense, a.delta_per_clip = int(delta.dim() == 4), int(delta.dim() == 3)
     a.dclip = float(dclip)
     a.inv_std = (C.c_float * 3)(*inv_std)
     a.lo, a.hi, a.adv_flag = float(lo), float(hi), float(adv_flag)
     a.shift_x, a.shift_p = int(shift_x), int(shift_p)
     a.B, a.T, a.H, a.W = B, T, H, W
-    a.fold_t = fold_t
-    a.center = int(center)      # write x_adv - a*p' (the clean value where the clip is inactive); see Net.forward_flicker
     if dclip_dev is not None:   # per-clip clamp bounds (fp32 [B] on the device), per-clip perturbations only
         assert a.delta_per_clip and dclip_dev.dtype == torch.float32 and dclip_dev.shape == (B,) and dclip_dev.is_cuda
-    a.dclip_dev = ptr(dclip_dev)
-    a.x_lut = ptr(x_lut)
-    if quantise is not None:    # the encode of make_export_args(quantise), the decode of q_lut
-        mul, add, levels = EXPORT_DIALECTS[quantise]
-        a.q_lut, a.q_mul, a.q_add, a.q_levels = ptr(q_lut), (C.c_float * 3)(*mul), (C.c_float * 3)(*add), levels
-    a._keepalive = (x, delta, dclip_dev, x_lut, q_lut)   # the struct holds raw pointers only
+    a.dclip_dev, a.x_lut = ptr(dclip_dev), ptr(x_lut)
+    a._keepalive = (x, delta, dclip_dev, x_lut)   # the struct holds raw pointers only
     return a
 
 
@@ -391,17 +403,14 @@ def make_export_args(dialect, out_clip_stride, out_offset=0, delta_T=0):
 def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, shift_x=0, shift_p=0, inv_std=(1.0, 1.0, 1.0), lo=-1.0, hi=1.0,
                            dclip_dev=None, x_lut=None, delta_T=0, per_line=False):
     """the flk_apply_args of an 8-bit export: ``make_apply_args`` without a fold (T, H and W may be odd) and, with ``delta_T``, with a
-    flicker perturbation [delta_T,3] whose length is its period instead of the clip's T.  (The fields are filled as ``make_apply_args``
-    fills them -- a change to one belongs in the other; only the fold, ``center`` and the shape rule of ``delta`` differ, and there is no
+    flicker perturbation [delta_T,3] whose length is its period instead of the clip's T.  (The fields are filled by the filler ``make_apply_args``
+    uses, ``_fill_apply_args``; only the fold, ``center`` and the shape rule of ``delta`` differ, and there is no
     ``quantise``: the export is the quantiser itself, and ``make_apply_args(quantise=dialect)`` applies the clip these bytes decode to.)  The period is
     remembered on the result (``_delta_T``): ``export_adversarial_u8`` takes it from there.  per_line=True: delta is fp32 [T,H,3], [B,T,H,3]
     or, with ``delta_T``, [delta_T,H,3] -- one value per line of a frame (flk_apply_args.delta_per_line)."""
-    B, T, H, W, c3 = x.shape
-    assert c3 == 3 and x.is_contiguous() and x.is_cuda and delta.is_contiguous() and delta.is_cuda and delta.dtype == torch.float32
-    assert x.dtype in (torch.uint8, torch.float32) and min(B, T, H, W) > 0
-    if x_lut is not None:
-        assert x.dtype == torch.uint8 and x_lut.dtype == torch.float32 and tuple(x_lut.shape) == (256, 3) and x_lut.is_contiguous() and x_lut.is_cuda
-    assert not (dialect == "torch" and x.dtype == torch.uint8 and x_lut is None), "torch dialect: a uint8 clip needs x_lut (its decode table)"
+    B, T, H, W, _ = x.shape
+    assert x.is_cuda and delta.is_cuda and min(B, T, H, W) > 0
+    a = _fill_apply_args(x, delta, dialect, dclip, adv_flag, shift_x, shift_p, inv_std, lo, hi, dclip_dev, x_lut, per_line)
     if per_line:
         want = ((int(delta_T), H, 3),) if delta_T else ((T, H, 3), (B, T, H, 3))
         if tuple(delta.shape) not in want:
@@ -410,21 +419,6 @@ def make_export_apply_args(x, delta, *, dialect="tf", dclip=0.4, adv_flag=1.0, s
         assert tuple(delta.shape) == (int(delta_T), 3), f"delta_T = {delta_T}: the perturbation must be [{delta_T},3], got {tuple(delta.shape)}"
     else:
         assert tuple(delta.shape) in ((T, 3), (B, T, 3), (T, H, W, 3)), delta.shape
-    a = ApplyArgs()
-    a.x, a.x_is_u8 = ptr(x), int(x.dtype == torch.uint8)
-    a.x_scale, a.x_bias = (1.0 / 128.0, -1.0) if dialect == "tf" else (1.0, 0.0)
-    a.delta, a.delta_dense, a.delta_per_clip = ptr(delta), int(delta.dim() == 4), int(delta.dim() == 3)
-    if per_line:
-        a.delta_dense, a.delta_per_clip, a.delta_per_line = 0, int(delta.dim() == 4), 1
-    a.dclip = float(dclip)
-    a.inv_std = (C.c_float * 3)(*inv_std)
-    a.lo, a.hi, a.adv_flag = float(lo), float(hi), float(adv_flag)
-    a.shift_x, a.shift_p = int(shift_x), int(shift_p)
-    a.B, a.T, a.H, a.W = B, T, H, W
-    if dclip_dev is not None:
-        assert a.delta_per_clip and dclip_dev.dtype == torch.float32 and dclip_dev.shape == (B,) and dclip_dev.is_cuda
-    a.dclip_dev, a.x_lut = ptr(dclip_dev), ptr(x_lut)
-    a._keepalive = (x, delta, dclip_dev, x_lut)   # the struct holds raw pointers only
     a._delta_T = int(delta_T)                     # the kernel must wrap by the length delta really has
     return a
 
@@ -436,22 +430,30 @@ def export_adversarial_u8(args, dialect="tf", out=None, out_offset=0, stats=Fals
     int32 [B,T,3,4] table of per (clip, frame, channel) sums: q - q_clean, |q - q_clean|, [q != q_clean], [clamp active].
     ``delta_T``: the period the arguments were built with (default); naming another one is an error -- the kernel would read past a
     perturbation of ``delta_T`` rows."""
+    return _export_u8("export_adversarial_u8", args, dialect, out, out_offset, stats, delta_T,
+                      lambda e, out, st: load().flk_adv_export_u8(C.byref(args), C.byref(e), ptr(out), ptr(st), stream_ptr()))
+
+
+def _export_u8(what, args, dialect, out, out_offset, stats, delta_T, launch):
+    """the host half of the two 8-bit exports (``what`` names the caller in a refusal): the period must be the one ``args`` were built
+    with, ``out`` is allocated or checked, ``launch(export_args, out, stats_table)`` runs the kernel; returns the rows written, with
+    ``stats`` also the table"""
     B, T, H, W = args.B, args.T, args.H, args.W
     built = getattr(args, "_delta_T", 0)
     if delta_T is None:
         delta_T = built
     if int(delta_T) != built:
-        raise ValueError(f"export_adversarial_u8: delta_T = {delta_T}, but the arguments were built for delta_T = {built}")
+        raise ValueError(f"{what}: delta_T = {delta_T}, but the arguments were built for delta_T = {built}")
     dev = args._keepalive[0].device
     if out is None:
         out = torch.empty((out_offset + B, T, H, W, 3), dtype=torch.uint8, device=dev)
     if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 5
             or tuple(out.shape[1:]) != (T, H, W, 3) or out_offset < 0 or out.shape[0] < out_offset + B):
         desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
-        raise ValueError(f"export_adversarial_u8: out must be a contiguous CUDA uint8 tensor [>= {out_offset + B},{T},{H},{W},3], got {desc}")
+        raise ValueError(f"{what}: out must be a contiguous CUDA uint8 tensor [>= {out_offset + B},{T},{H},{W},3], got {desc}")
     e = make_export_args(dialect, T * H * W * 3, out_offset, delta_T)
     st = torch.empty((B, T, 3, 4), dtype=torch.int32, device=dev) if stats else None
-    check(load().flk_adv_export_u8(C.byref(args), C.byref(e), ptr(out), ptr(st), stream_ptr()))
+    check(launch(e, out, st))
     rows = out[out_offset:out_offset + B]
     return (rows, st) if stats else rows
 
@@ -505,11 +507,16 @@ def perturb_apply_quantised_host(x, delta, *, dialect="tf", dclip=0.4, adv_flag=
     return np.ascontiguousarray(quant_table_host(dialect)[q, np.arange(3)], dtype=np.float32)
 
 
+def _grad_shape(args):
+    """the shape of d(loss)/d(delta) for the delta of ``args``: per line [B,T,H,3] (the gradient kernels take per-clip lines only),
+    dense [T,H,W,3], per clip [B,T,3], shared [T,3]"""
+    return (args.B, args.T, args.H, 3) if args.delta_per_line else (args.T, args.H, args.W, 3) if args.delta_dense else \
+        (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
+
+
 def perturb_grad_reduce(args, gx_s2d, gdelta=None, scratch=None):
     if gdelta is None:
-        shape = (args.B, args.T, args.H, 3) if args.delta_per_line else (args.T, args.H, args.W, 3) if args.delta_dense else \
-            (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
-        gdelta = torch.empty(shape, dtype=torch.float32, device="cuda")
+        gdelta = torch.empty(_grad_shape(args), dtype=torch.float32, device="cuda")
     if scratch is None and not args.delta_dense and not args.delta_per_line:
         n = load().flk_perturb_grad_scratch_bytes(args.B, args.T, args.H, args.W)
         scratch = torch.empty(n // 4, dtype=torch.float32, device="cuda")
@@ -552,24 +559,9 @@ def illum_apply_s2d(args, illum, dtype, out=None):
 def illum_export_u8(args, illum, out=None, out_offset=0, stats=False, delta_T=None):
     """the bytes a camera stores of the clip of ``args`` (make_export_apply_args, or make_apply_args) lit by its flicker
     (flk_illum_export_u8); ``out`` / ``out_offset`` / ``stats`` / ``delta_T`` as ``export_adversarial_u8``"""
-    B, T, H, W = args.B, args.T, args.H, args.W
-    built = getattr(args, "_delta_T", 0)
-    if delta_T is None:
-        delta_T = built
-    if int(delta_T) != built:
-        raise ValueError(f"illum_export_u8: delta_T = {delta_T}, but the arguments were built for delta_T = {built}")
-    dev = args._keepalive[0].device
-    if out is None:
-        out = torch.empty((out_offset + B, T, H, W, 3), dtype=torch.uint8, device=dev)
-    if (not torch.is_tensor(out) or not out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() != 5
-            or tuple(out.shape[1:]) != (T, H, W, 3) or out_offset < 0 or out.shape[0] < out_offset + B):
-        desc = f"{tuple(out.shape)} {out.dtype}" if torch.is_tensor(out) else type(out).__name__
-        raise ValueError(f"illum_export_u8: out must be a contiguous CUDA uint8 tensor [>= {out_offset + B},{T},{H},{W},3], got {desc}")
-    e = make_export_args("torch", T * H * W * 3, out_offset, delta_T)       # (the encode fields are not read: the tables are the encode)
-    st = torch.empty((B, T, 3, 4), dtype=torch.int32, device=dev) if stats else None
-    check(load().flk_illum_export_u8(C.byref(args), C.byref(illum), C.byref(e), ptr(out), ptr(st), stream_ptr()))
-    rows = out[out_offset:out_offset + B]
-    return (rows, st) if stats else rows
+    # (the encode fields of the "torch" dialect are not read: the tables are the encode)
+    return _export_u8("illum_export_u8", args, "torch", out, out_offset, stats, delta_T,
+                      lambda e, out, st: load().flk_illum_export_u8(C.byref(args), C.byref(illum), C.byref(e), ptr(out), ptr(st), stream_ptr()))
 
 
 def illum_grad_reduce(args, illum, gx_s2d, gdelta=None, scratch=None):
@@ -577,8 +569,7 @@ def illum_grad_reduce(args, illum, gx_s2d, gdelta=None, scratch=None):
     the delta of ``args`` -- [T,3], [B,T,3] or, per line (per-clip only), [B,T,H,3]"""
     dev = args._keepalive[0].device
     if gdelta is None:
-        shape = (args.B, args.T, args.H, 3) if args.delta_per_line else (args.B, args.T, 3) if args.delta_per_clip else (args.T, 3)
-        gdelta = torch.empty(shape, dtype=torch.float32, device=dev)
+        gdelta = torch.empty(_grad_shape(args), dtype=torch.float32, device=dev)
     if scratch is None and not args.delta_per_line:
         scratch = torch.empty(load().flk_perturb_grad_scratch_bytes(args.B, args.T, args.H, args.W) // 4, dtype=torch.float32, device=dev)
     check(load().flk_illum_grad_reduce(C.byref(args), C.byref(illum), ptr(gx_s2d), dtype_code(gx_s2d.dtype), ptr(gdelta), ptr(scratch), stream_ptr()))
@@ -663,19 +654,50 @@ def _check_f32(what, name, t, shape, like):
         raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor {tuple(shape)} on {like.device}, got {desc}")
 
 
-def flicker_rows_gather(delta, rows, out=None, rows_host=None):
-    """delta_clip[..., c] = delta[rows[...], c] (flk_flicker_rows_gather, one launch): the shared flicker perturbation ``delta`` fp32 [P,3]
-    spread over the frames of a batch by their ``rows`` (int32 on the device, e.g. [B,T]; videoresnet_spec.flicker_rows makes the table)
-    -> fp32 ``rows.shape + (3,)``, the per-clip perturbation ``make_apply_args`` takes.  Raw values.  ``out``: the buffer to fill."""
-    what = "flicker_rows_gather"
+def _check_delta(what, delta, rows, rows_host):
+    """the shared perturbation of flk_flicker_*: fp32 [P,3], contiguous on the device of ``rows``, which ``_check_rows`` checks against
+    its period -> P"""
     if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
         raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
     P = int(delta.shape[0])
     _check_rows(what, rows, P, rows_host)
     _check_f32(what, "delta", delta, (P, 3), rows)
+    return P
+
+
+def _out_f32(what, out, shape, like):
+    """``out``, the buffer a call fills: allocated on the device of ``like`` when None, checked (``_check_f32``) when given"""
     if out is None:
-        out = torch.empty((*rows.shape, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (*rows.shape, 3), rows)
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=like.device)
+    _check_f32(what, "out", out, shape, like)
+    return out
+
+
+def _check_tables(what, rows, taps, gain, kmax, per_line=False):
+    """the channel tables of flk_flicker_rows_mix* and, ``per_line``, flk_flicker_lines_mix*: ``rows`` [B,clip_T] (or [clip_T]: one clip),
+    fp32 ``taps`` [B,K] -- per line [B,H,K] -- with K in 1..kmax and fp32 ``gain`` [B,3] or None, contiguous on rows' device
+    -> (clip_T, K), per line (clip_T, H, K)"""
+    if rows.dim() not in (1, 2):
+        raise ValueError(f"{what}: rows must be [clips,clip_T] (or [clip_T] for one clip), got {tuple(rows.shape)}")
+    nb, clip_T = (1, int(rows.shape[0])) if rows.dim() == 1 else (int(rows.shape[0]), int(rows.shape[1]))
+    if not (torch.is_tensor(taps) and taps.dim() == (3 if per_line else 2) and min(taps.shape[1:]) >= 1 and taps.shape[-1] <= kmax):
+        desc = f"{tuple(taps.shape)}" if torch.is_tensor(taps) else type(taps).__name__
+        form = f"[{nb},H,K] with K in 1..{kmax} (one table per clip)" if per_line else f"[{nb},K] with K in 1..{kmax} (one row per clip)"
+        raise ValueError(f"{what}: taps must be fp32 {form}, got {desc}")
+    dims = tuple(int(v) for v in taps.shape[1:])
+    _check_f32(what, "taps", taps, (nb, *dims), rows)
+    if gain is not None:
+        _check_f32(what, "gain", gain, (nb, 3), rows)
+    return (clip_T, *dims)
+
+
+def flicker_rows_gather(delta, rows, out=None, rows_host=None):
+    """delta_clip[..., c] = delta[rows[...], c] (flk_flicker_rows_gather, one launch): the shared flicker perturbation ``delta`` fp32 [P,3]
+    spread over the frames of a batch by their ``rows`` (int32 on the device, e.g. [B,T]; videoresnet_spec.flicker_rows makes the table)
+    -> fp32 ``rows.shape + (3,)``, the per-clip perturbation ``make_apply_args`` takes.  Raw values.  ``out``: the buffer to fill."""
+    what = "flicker_rows_gather"
+    P = _check_delta(what, delta, rows, rows_host)
+    out = _out_f32(what, out, (*rows.shape, 3), rows)
     check(load().flk_flicker_rows_gather(ptr(delta), P, ptr(rows), rows.numel(), ptr(out), stream_ptr()))
     return out
 
@@ -688,29 +710,12 @@ def flicker_rows_grad(g_clip, rows, period, out=None, rows_host=None):
     _check_rows(what, rows, period, rows_host)
     _check_f32(what, "g_clip", g_clip, (*rows.shape, 3), rows)
     P = int(period)
-    if out is None:
-        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (P, 3), rows)
+    out = _out_f32(what, out, (P, 3), rows)
     check(load().flk_flicker_rows_grad(ptr(g_clip), ptr(rows), rows.numel(), P, ptr(out), stream_ptr()))
     return out
 
 
 FLICKER_MIX_MAX_TAPS = 4      # rows of the perturbation one captured frame mixes (flk_flicker_rows_mix's K)
-
-
-def _check_mix(what, rows, taps, gain):
-    """the channel tables of flk_flicker_rows_mix*: ``rows`` [B,clip_T] (or [clip_T]: one clip), fp32 ``taps`` [B,K] with K in 1..4 and
-    fp32 ``gain`` [B,3] or None, contiguous on rows' device -> (clips, clip_T, K)"""
-    if rows.dim() not in (1, 2):
-        raise ValueError(f"{what}: rows must be [clips,clip_T] (or [clip_T] for one clip), got {tuple(rows.shape)}")
-    nb, clip_T = (1, int(rows.shape[0])) if rows.dim() == 1 else (int(rows.shape[0]), int(rows.shape[1]))
-    if not (torch.is_tensor(taps) and taps.dim() == 2 and 1 <= taps.shape[1] <= FLICKER_MIX_MAX_TAPS):
-        desc = f"{tuple(taps.shape)}" if torch.is_tensor(taps) else type(taps).__name__
-        raise ValueError(f"{what}: taps must be fp32 [{nb},K] with K in 1..{FLICKER_MIX_MAX_TAPS} (one row per clip), got {desc}")
-    _check_f32(what, "taps", taps, (nb, int(taps.shape[1])), rows)
-    if gain is not None:
-        _check_f32(what, "gain", gain, (nb, 3), rows)
-    return nb, clip_T, int(taps.shape[1])
 
 
 def flicker_rows_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
@@ -719,17 +724,10 @@ def flicker_rows_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
     fp32 [B,K] (K <= 4, videoresnet_spec.capture_taps / CaptureChannel.tables), ``gain`` fp32 [B,3] or None -> fp32 ``rows.shape + (3,)``.
     Raw values; every product and sum rounded on its own (videoresnet_spec.flicker_rows_mix restates it bit for bit)."""
     what = "flicker_rows_mix"
-    if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
-        raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
-    P = int(delta.shape[0])
-    _check_rows(what, rows, P, rows_host)
-    _check_f32(what, "delta", delta, (P, 3), rows)
-    _, clip_T, K = _check_mix(what, rows, taps, gain)
-    if out is None:
-        out = torch.empty((*rows.shape, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (*rows.shape, 3), rows)
-    check(load().flk_flicker_rows_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain) if gain is not None else None,
-                                      ptr(out), stream_ptr()))
+    P = _check_delta(what, delta, rows, rows_host)
+    clip_T, K = _check_tables(what, rows, taps, gain, FLICKER_MIX_MAX_TAPS)
+    out = _out_f32(what, out, (*rows.shape, 3), rows)
+    check(load().flk_flicker_rows_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain), ptr(out), stream_ptr()))
     return out
 
 
@@ -740,32 +738,14 @@ def flicker_rows_mix_grad(g_clip, rows, period, taps, gain=None, out=None, rows_
     what = "flicker_rows_mix_grad"
     _check_rows(what, rows, period, rows_host)
     _check_f32(what, "g_clip", g_clip, (*rows.shape, 3), rows)
-    _, clip_T, K = _check_mix(what, rows, taps, gain)
+    clip_T, K = _check_tables(what, rows, taps, gain, FLICKER_MIX_MAX_TAPS)
     P = int(period)
-    if out is None:
-        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (P, 3), rows)
-    check(load().flk_flicker_rows_mix_grad(ptr(g_clip), ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain) if gain is not None else None,
-                                           P, ptr(out), stream_ptr()))
+    out = _out_f32(what, out, (P, 3), rows)
+    check(load().flk_flicker_rows_mix_grad(ptr(g_clip), ptr(rows), rows.numel(), clip_T, ptr(taps), K, ptr(gain), P, ptr(out), stream_ptr()))
     return out
 
 
 FLICKER_LINES_MAX_TAPS = 5    # rows of the perturbation one LINE of a rolling-shutter frame mixes (flk_flicker_lines_mix's K)
-
-
-def _check_lines(what, rows, taps, gain):
-    """the tables of flk_flicker_lines_mix*: ``rows`` [B,clip_T] (or [clip_T]: one clip), fp32 ``taps`` [B,H,K] with K in 1..5 and fp32
-    ``gain`` [B,3] or None, contiguous on rows' device -> (clips, clip_T, H, K)"""
-    if rows.dim() not in (1, 2):
-        raise ValueError(f"{what}: rows must be [clips,clip_T] (or [clip_T] for one clip), got {tuple(rows.shape)}")
-    nb, clip_T = (1, int(rows.shape[0])) if rows.dim() == 1 else (int(rows.shape[0]), int(rows.shape[1]))
-    if not (torch.is_tensor(taps) and taps.dim() == 3 and taps.shape[1] >= 1 and 1 <= taps.shape[2] <= FLICKER_LINES_MAX_TAPS):
-        desc = f"{tuple(taps.shape)}" if torch.is_tensor(taps) else type(taps).__name__
-        raise ValueError(f"{what}: taps must be fp32 [{nb},H,K] with K in 1..{FLICKER_LINES_MAX_TAPS} (one table per clip), got {desc}")
-    _check_f32(what, "taps", taps, (nb, int(taps.shape[1]), int(taps.shape[2])), rows)
-    if gain is not None:
-        _check_f32(what, "gain", gain, (nb, 3), rows)
-    return nb, clip_T, int(taps.shape[1]), int(taps.shape[2])
 
 
 def flicker_lines_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
@@ -775,17 +755,10 @@ def flicker_lines_mix(delta, rows, taps, gain=None, out=None, rows_host=None):
     ``rows.shape + (H,3)``, the per-line perturbation ``make_apply_args(per_line=True)`` takes.  Raw values; every product and sum rounded
     on its own (videoresnet_spec.flicker_lines_mix restates it bit for bit)."""
     what = "flicker_lines_mix"
-    if not (torch.is_tensor(delta) and delta.dim() == 2 and delta.shape[1] == 3):
-        raise ValueError(f"{what}: delta must be fp32 [P,3] on the device")
-    P = int(delta.shape[0])
-    _check_rows(what, rows, P, rows_host)
-    _check_f32(what, "delta", delta, (P, 3), rows)
-    _, clip_T, H, K = _check_lines(what, rows, taps, gain)
-    if out is None:
-        out = torch.empty((*rows.shape, H, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (*rows.shape, H, 3), rows)
-    check(load().flk_flicker_lines_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain) if gain is not None else None,
-                                       ptr(out), stream_ptr()))
+    P = _check_delta(what, delta, rows, rows_host)
+    clip_T, H, K = _check_tables(what, rows, taps, gain, FLICKER_LINES_MAX_TAPS, per_line=True)
+    out = _out_f32(what, out, (*rows.shape, H, 3), rows)
+    check(load().flk_flicker_lines_mix(ptr(delta), P, ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain), ptr(out), stream_ptr()))
     return out
 
 
@@ -796,24 +769,23 @@ def flicker_lines_mix_grad(g_lines, rows, period, taps, gain=None, out=None, row
     atomics.  ``scratch``: fp32 with at least ``rows.numel() * K * 3`` elements on the device (allocated when None)."""
     what = "flicker_lines_mix_grad"
     _check_rows(what, rows, period, rows_host)
-    _, clip_T, H, K = _check_lines(what, rows, taps, gain)
+    clip_T, H, K = _check_tables(what, rows, taps, gain, FLICKER_LINES_MAX_TAPS, per_line=True)
     _check_f32(what, "g_lines", g_lines, (*rows.shape, H, 3), rows)
     P = int(period)
-    if out is None:
-        out = torch.empty((P, 3), dtype=torch.float32, device=rows.device)
-    _check_f32(what, "out", out, (P, 3), rows)
+    out = _out_f32(what, out, (P, 3), rows)
     need = rows.numel() * K * 3
     if scratch is None:
         scratch = torch.empty(need, dtype=torch.float32, device=rows.device)
     if not (torch.is_tensor(scratch) and scratch.dtype == torch.float32 and scratch.is_contiguous() and scratch.device == rows.device and scratch.numel() >= need):
         raise ValueError(f"{what}: scratch must be a contiguous fp32 tensor of at least {need} elements on {rows.device}")
-    check(load().flk_flicker_lines_mix_grad(ptr(g_lines), ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain) if gain is not None else None,
-                                            P, ptr(scratch), ptr(out), stream_ptr()))
+    check(load().flk_flicker_lines_mix_grad(ptr(g_lines), ptr(rows), rows.numel(), clip_T, H, ptr(taps), K, ptr(gain), P, ptr(scratch), ptr(out),
+                                            stream_ptr()))
     return out
 
 
-class StemDeltaGradWeights:
+class StemDeltaGradWeights(_HandleOwner):
     """fp32 weights of flk_stem_delta_grad: canonical stem weights [7,7,7,3,64] x folded batch-norm scale [64]"""
+    _destroy = "flk_stem_delta_grad_weights_destroy"
 
     def __init__(self, w7_dhwio, bn_scale):
         w = np.ascontiguousarray(w7_dhwio, dtype=np.float32)
@@ -822,14 +794,6 @@ class StemDeltaGradWeights:
         h = C.c_void_p()
         check(load().flk_stem_delta_grad_weights_create(ptr(w), ptr(sc), C.byref(h)))
         self.handle = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                load().flk_stem_delta_grad_weights_destroy(self.handle)
-                self.handle = None
-        except Exception:      # interpreter shutdown
-            pass
 
 
 def stem_delta_grad_chunks(B, T, H, per_clip=False):
@@ -851,8 +815,9 @@ def stem_delta_grad(args, G, weights, gdelta=None, scratch=None):
     return gdelta
 
 
-class StemFwdU8Weights:
+class StemFwdU8Weights(_HandleOwner):
     """MFMA fragments of flk_stem_fwd_u8 from the canonical stem weights [7,7,7,3,64] (37 K steps x 2 column parities)"""
+    _destroy = "flk_conv_weights_destroy"
 
     def __init__(self, w7_dhwio):
         w = np.ascontiguousarray(w7_dhwio, dtype=np.float32)
@@ -860,14 +825,6 @@ class StemFwdU8Weights:
         h = C.c_void_p()
         check(load().flk_stem_fwd_u8_weights_create(ptr(w), C.byref(h)))
         self.handle = h
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                load().flk_conv_weights_destroy(self.handle)
-                self.handle = None
-        except Exception:      # interpreter shutdown
-            pass
 
 
 def stem_delta_bias_table(args, w7_dhwio, bn_scale):
@@ -899,15 +856,22 @@ def stem_fwd_u8(args, weights, bn_scale, bn_bias, pos_bias=None, out=None):
     return out
 
 
-def perturb_reg_adam(g_adv, delta, m, v, step, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0.5, beta3=0.5,
-                     dyn_max_norm=0.0, g_scale=1.0, lr=1e-3, adam=(0.9, 0.999, 1e-8), scalars=None):
+def _flicker_opt_args(T, dialect, betas, dyn_max_norm, g_scale, lr, *, adam=(0.0, 0.0, 0.0), step=0, eps=0.0):
+    """flk_adam_args of a flicker delta [T,3] (or [B,T,3]): the regulariser weights ``betas`` (beta0..beta3) and the step size; an Adam
+    step names ``adam`` (b1, b2, eps) and, unbatched, its ``step``; a projected sign-gradient step names its radius ``eps``"""
     a = AdamArgs()
-    a.T = delta.shape[0]
+    a.T = T
     a.torch_dialect = int(dialect == "torch")
-    a.beta0, a.beta1, a.beta2, a.beta3 = beta0, beta1, beta2, beta3
+    a.beta0, a.beta1, a.beta2, a.beta3 = betas
     a.dyn_max_norm, a.g_scale, a.lr = dyn_max_norm, g_scale, lr
     a.adam_b1, a.adam_b2, a.adam_eps = adam
-    a.step = int(step)
+    a.step, a.pgd_eps = int(step), float(eps)
+    return a
+
+
+def perturb_reg_adam(g_adv, delta, m, v, step, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0.5, beta3=0.5,
+                     dyn_max_norm=0.0, g_scale=1.0, lr=1e-3, adam=(0.9, 0.999, 1e-8), scalars=None):
+    a = _flicker_opt_args(delta.shape[0], dialect, (beta0, beta1, beta2, beta3), dyn_max_norm, g_scale, lr, adam=adam, step=step)
     if scalars is None:
         scalars = torch.empty(8, dtype=torch.float32, device="cuda")
     check(load().flk_perturb_reg_adam(C.byref(a), ptr(g_adv), ptr(delta), ptr(m), ptr(v), ptr(scalars), stream_ptr()))
@@ -922,13 +886,7 @@ def perturb_reg_adam_batched(g_adv, delta, m, v, steps, active=None, *, dialect=
     assert steps.dtype == torch.int32 and steps.shape == (B,) and steps.is_cuda and (active is None or (active.dtype == torch.int32 and active.shape == (B,)))
     for t in (g_adv, delta, m, v):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * T * 3
-    a = AdamArgs()
-    a.T = T
-    a.torch_dialect = int(dialect == "torch")
-    a.beta0, a.beta1, a.beta2, a.beta3 = beta0, beta1, beta2, beta3
-    a.dyn_max_norm, a.g_scale, a.lr = dyn_max_norm, g_scale, lr
-    a.adam_b1, a.adam_b2, a.adam_eps = adam
-    a.step = 0
+    a = _flicker_opt_args(T, dialect, (beta0, beta1, beta2, beta3), dyn_max_norm, g_scale, lr, adam=adam)
     if scalars is None:
         scalars = torch.empty((B, 8), dtype=torch.float32, device="cuda")
     assert dyn_max_norm_dev is None or (dyn_max_norm_dev.dtype == torch.float32 and dyn_max_norm_dev.shape == (B,) and dyn_max_norm_dev.is_cuda)
@@ -937,33 +895,30 @@ def perturb_reg_adam_batched(g_adv, delta, m, v, steps, active=None, *, dialect=
     return scalars
 
 
-def perturb_dense_l12_adam(g_adv, delta, m, v, step, *, dialect="tf", beta=1.0, g_scale=1.0, lr=1e-3, adam=(0.9, 0.999, 1e-8),
-                           scalars=None, scratch=None, dyn_max_norm=0.0):
-    """dense delta [T,H,W,3]: L12 regulariser gradient + Adam (kinetics_i3d_L12); returns scalars {L12, thickness, roughness, max}.
-    dyn_max_norm > 0 (torch dialect): L12 of the clamped perturbation, as Losses receives it (model.py:1078)"""
+def _dense_opt_args(delta, dialect, beta, g_scale, lr, dyn_max_norm, scalars, scratch, *, adam=(0.0, 0.0, 0.0), step=0, eps=0.0):
+    """(flk_dense_adam_args of a dense delta [T,H,W,3], scalars, scratch), the two buffers allocated when None; an Adam step names
+    ``adam`` (b1, b2, eps) and its ``step``, a projected sign-gradient step its radius ``eps``"""
     T, H, W, _ = delta.shape
     a = DenseAdamArgs()
     a.T, a.H, a.W, a.torch_dialect = T, H, W, int(dialect == "torch")
     a.beta, a.g_scale, a.lr = beta, g_scale, lr
     a.adam_b1, a.adam_b2, a.adam_eps = adam
     a.step = int(step)
-    a.dyn_max_norm = float(dyn_max_norm)
+    a.dyn_max_norm, a.pgd_eps = float(dyn_max_norm), float(eps)
     if scalars is None:
         scalars = torch.empty(4, dtype=torch.float32, device="cuda")
     if scratch is None:
         scratch = torch.empty(load().flk_dense_adam_scratch_bytes(T, H, W) // 4, dtype=torch.float32, device="cuda")
+    return a, scalars, scratch
+
+
+def perturb_dense_l12_adam(g_adv, delta, m, v, step, *, dialect="tf", beta=1.0, g_scale=1.0, lr=1e-3, adam=(0.9, 0.999, 1e-8),
+                           scalars=None, scratch=None, dyn_max_norm=0.0):
+    """dense delta [T,H,W,3]: L12 regulariser gradient + Adam (kinetics_i3d_L12); returns scalars {L12, thickness, roughness, max}.
+    dyn_max_norm > 0 (torch dialect): L12 of the clamped perturbation, as Losses receives it (model.py:1078)"""
+    a, scalars, scratch = _dense_opt_args(delta, dialect, beta, g_scale, lr, dyn_max_norm, scalars, scratch, adam=adam, step=step)
     check(load().flk_perturb_dense_l12_adam(C.byref(a), ptr(g_adv), ptr(delta), ptr(m), ptr(v), ptr(scalars), ptr(scratch), stream_ptr()))
     return scalars
-
-
-def _pgd_args(T, dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps):
-    a = AdamArgs()
-    a.T = T
-    a.torch_dialect = int(dialect == "torch")
-    a.beta0, a.beta1, a.beta2, a.beta3 = beta0, beta1, beta2, beta3
-    a.dyn_max_norm, a.g_scale, a.lr = dyn_max_norm, g_scale, lr
-    a.pgd_eps = float(eps)
-    return a
 
 
 def perturb_reg_pgd(g_adv, delta, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0.5, beta3=0.5, dyn_max_norm=0.0, g_scale=1.0, lr=1e-3,
@@ -971,7 +926,7 @@ def perturb_reg_pgd(g_adv, delta, *, dialect="tf", beta0=1.0, beta1=0.5, beta2=0
     """projected sign-gradient step on the flicker delta [T,3]: delta <- clamp(delta - lr * sgn(g_tot), +-radius), g_tot formed as
     perturb_reg_adam forms it.  Radius: ``eps`` (TF dialect) or ``dyn_max_norm`` (torch dialect).  Returns the 8 scalars of the
     pre-update delta."""
-    a = _pgd_args(delta.shape[0], dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps)
+    a = _flicker_opt_args(delta.shape[0], dialect, (beta0, beta1, beta2, beta3), dyn_max_norm, g_scale, lr, eps=eps)
     if scalars is None:
         scalars = torch.empty(8, dtype=torch.float32, device="cuda")
     check(load().flk_perturb_reg_pgd(C.byref(a), ptr(g_adv), ptr(delta), ptr(scalars), stream_ptr()))
@@ -986,7 +941,7 @@ def perturb_reg_pgd_batched(g_adv, delta, steps, active=None, *, dialect="tf", b
     assert steps.dtype == torch.int32 and steps.shape == (B,) and steps.is_cuda and (active is None or (active.dtype == torch.int32 and active.shape == (B,)))
     for t in (g_adv, delta):
         assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * T * 3
-    a = _pgd_args(T, dialect, beta0, beta1, beta2, beta3, dyn_max_norm, g_scale, lr, eps)
+    a = _flicker_opt_args(T, dialect, (beta0, beta1, beta2, beta3), dyn_max_norm, g_scale, lr, eps=eps)
     if scalars is None:
         scalars = torch.empty((B, 8), dtype=torch.float32, device="cuda")
     assert dyn_max_norm_dev is None or (dyn_max_norm_dev.dtype == torch.float32 and dyn_max_norm_dev.shape == (B,) and dyn_max_norm_dev.is_cuda)
@@ -998,15 +953,7 @@ def perturb_reg_pgd_batched(g_adv, delta, steps, active=None, *, dialect="tf", b
 def perturb_dense_l12_pgd(g_adv, delta, *, dialect="tf", beta=1.0, g_scale=1.0, lr=1e-3, eps=0.0, scalars=None, scratch=None, dyn_max_norm=0.0):
     """dense delta [T,H,W,3]: L12 regulariser gradient + projected sign-gradient step; radius ``eps`` (TF dialect, required) or
     ``dyn_max_norm`` (torch dialect).  Returns scalars {L12, thickness, roughness, max} of the pre-update delta."""
-    T, H, W, _ = delta.shape
-    a = DenseAdamArgs()
-    a.T, a.H, a.W, a.torch_dialect = T, H, W, int(dialect == "torch")
-    a.beta, a.g_scale, a.lr = beta, g_scale, lr
-    a.dyn_max_norm, a.pgd_eps = float(dyn_max_norm), float(eps)
-    if scalars is None:
-        scalars = torch.empty(4, dtype=torch.float32, device="cuda")
-    if scratch is None:
-        scratch = torch.empty(load().flk_dense_adam_scratch_bytes(T, H, W) // 4, dtype=torch.float32, device="cuda")
+    a, scalars, scratch = _dense_opt_args(delta, dialect, beta, g_scale, lr, dyn_max_norm, scalars, scratch, eps=eps)
     check(load().flk_perturb_dense_l12_pgd(C.byref(a), ptr(g_adv), ptr(delta), ptr(scalars), ptr(scratch), stream_ptr()))
     return scalars
 
@@ -1408,8 +1355,9 @@ def softmax_adv_loss_video(logits, labels, clips_per_video, *, reduce="mean", di
     return sm, dl, pv, vl
 
 
-class Net:
+class Net(_HandleOwner):
     """flk_net: whole-network forward + backward-to-input plan with resident packed weights."""
+    _destroy = "flk_net_destroy"
 
     def __init__(self, arch, dtype, B, T, H, W, weights, device=0):
         self.dtype = dtype_code(dtype)
@@ -1500,11 +1448,3 @@ class Net:
         out = np.empty(tuple(dims), dtype=np.float32)
         check(load().flk_net_get_activation(self.handle, name.encode(), ptr(out), out.size, dims))
         return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "handle", None):
-                load().flk_net_destroy(self.handle)
-                self.handle = None
-        except Exception:      # interpreter shutdown
-            pass

@@ -1,6 +1,7 @@
 """flk_adv_export_u8 on the GPU: the frames are bitwise the encode of what flk_perturb_apply_s2d writes in fp32, for every source form and
 perturbation; odd shapes, misaligned clips and rows of a batch buffer against the host restatement; exact integer statistics; integer
 levels; a perturbation of period delta_T; the engines' quantised routes; the scripts' options."""
+import ctypes as C
 import glob
 import os
 import subprocess
@@ -181,6 +182,34 @@ def test_delta_T_lays_a_period_over_any_length():
         a0 = ops.make_export_apply_args(xu, full, shift_p=phase, **kw)
         a1 = ops.make_export_apply_args(xu, full, shift_p=phase, delta_T=N, **kw)
         assert torch.equal(ops.export_adversarial_u8(a0, "torch"), ops.export_adversarial_u8(a1, "torch", delta_T=N))
+
+
+def test_export_builder_fills_the_fields_as_the_apply_builder():
+    """make_export_apply_args promises the flk_apply_args of make_apply_args without a fold: every field of the struct is compared for
+    every source form and every form of delta (shared forms rolled), under non-default scalars; only fold_t may differ"""
+    from flickering_adversarial_video_amd import _lib, ops
+    from flickering_adversarial_video_amd.torch_attack import decode_table
+    B, T, H, W = 2, 4, 6, 8
+    xu = torch.from_numpy(clip_u8(B, T, H, W, seed=87)).cuda()
+    srcs = [("u8_lut", xu, dict(dialect="torch", x_lut=decode_table("cuda"))), ("u8_tf", xu, dict(dialect="tf")),
+            ("fp32", xu.to(torch.float32), dict(dialect="torch"))]
+    scalars = dict(dclip=0.3, adv_flag=0.5, inv_std=(2.0, 3.0, 4.0), lo=-0.75, hi=0.5)
+    roll = dict(shift_x=1, shift_p=3)
+    bounds = torch.linspace(0.1, 0.2, B, device="cuda")
+    forms = [((T, 3), roll), ((B, T, 3), {}), ((B, T, 3), dict(dclip_dev=bounds)), ((T, H, W, 3), roll), ((T, H, 3), dict(roll, per_line=True)),
+             ((B, T, H, 3), dict(per_line=True))]
+
+    def value(v):
+        return list(v) if isinstance(v, C.Array) else v
+
+    for sname, x, src_kw in srcs:
+        for shape, kw in forms:
+            d = torch.zeros(shape, dtype=torch.float32, device="cuda")
+            a = ops.make_apply_args(x, d, fold_t=1, **src_kw, **scalars, **kw)
+            e = ops.make_export_apply_args(x, d, **src_kw, **scalars, **kw)
+            for name, _ in _lib.ApplyArgs._fields_:
+                if name != "fold_t":
+                    assert value(getattr(a, name)) == value(getattr(e, name)), (sname, shape, sorted(kw), name)
 
 
 # ---- engines ---------------------------------------------------------------------------------------------------------------------
