@@ -233,9 +233,9 @@ extern "C" int flk_codec_tables(int quality, int32_t* qluma, int32_t* qchroma) {
   return FLK_OK;
 }
 
-extern "C" int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
-                                      void* stream) {
-  const char* fn = "flk_codec_roundtrip_u8";
+// what both codec entries check of the views, the quality and the subsampling.  have_idx: the launch names its own source frames, so
+// T_out is not held against the clips' T.  stats_pixels: the largest padded frame stats are taken on (0: no stats asked for)
+static int check_codec_args(const char* fn, const flk_codec_args* a, bool have_idx, int T_out, int64_t stats_pixels) {
   FLK_REQUIRE(a, "%s: null argument", fn);
   FLK_REQUIRE(a->clips, "%s: null clip list", fn);
   FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", fn, a->nclip, FLK_PREP_MAX_CLIPS);
@@ -255,13 +255,50 @@ extern "C" int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* fr
                 "%s: clip %d: destination pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i,
                 (long long)c.dst_pitch_t, (long long)c.dst_pitch_h);
     FLK_REQUIRE((const uint8_t*)c.dst != c.src, "%s: clip %d: the destination is the source (an MCU reads pixels other workgroups write)", fn, i);
-    FLK_REQUIRE(frame_idx || T_out <= c.T, "%s: clip %d: T_out %d above its %d frames (no frame_idx)", fn, i, T_out, c.T);
-    if (stats) {
+    FLK_REQUIRE(have_idx || T_out <= c.T, "%s: clip %d: T_out %d above its %d frames (no frame_idx)", fn, i, T_out, c.T);
+    if (stats_pixels) {
       const int64_t Hp = ((int64_t)c.Hs + M - 1) / M * M, Wp = ((int64_t)c.Ws + M - 1) / M * M;
-      FLK_REQUIRE(Hp * Wp <= 5000000, "%s: clip %d: stats on a frame of %lld padded pixels (more than 5000000)", fn, i, (long long)(Hp * Wp));
+      FLK_REQUIRE(Hp * Wp <= stats_pixels, "%s: clip %d: stats on a frame of %lld padded pixels (more than %lld)", fn, i, (long long)(Hp * Wp),
+                  (long long)stats_pixels);
     }
   }
+  return FLK_OK;
+}
+
+extern "C" int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
+                                      void* stream) {
+  if (int rc = check_codec_args("flk_codec_roundtrip_u8", a, frame_idx != nullptr, T_out, stats ? 5000000 : 0)) return rc;
   return flk_codec_roundtrip_launch(a, frame_idx, T_out, tone, stats, (hipStream_t)stream);
+}
+
+// Inter-frame prediction (csrc/codec.hip): closed GOPs over per-clip spans given as host values
+int flk_codec_inter_step_host(int quality);
+int flk_codec_roundtrip_gop_launch(const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max,
+                                   const uint8_t* tone, int32_t* stats, hipStream_t stream);
+
+extern "C" int flk_codec_inter_step(int quality, int32_t* qp) {
+  FLK_REQUIRE(qp, "flk_codec_inter_step: null result");
+  FLK_REQUIRE(quality >= 1 && quality <= 100, "flk_codec_inter_step: quality %d outside 1..100", quality);
+  *qp = flk_codec_inter_step_host(quality);
+  return FLK_OK;
+}
+
+extern "C" int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max,
+                                          const uint8_t* tone, int32_t* stats, void* stream) {
+  const char* fn = "flk_codec_roundtrip_gop_u8";
+  FLK_REQUIRE(first && count, "%s: null first or count", fn);
+  FLK_REQUIRE(gop >= 1 && gop <= 65535, "%s: gop %d outside 1..65535", fn, gop);
+  // the spans are held against the clips below: to the shared checks the launch has its own source frames (as with a frame_idx)
+  // (a P-frame's magnitudes reach 766 per padded pixel, twice an intra frame's: half the frame for the same int32)
+  if (int rc = check_codec_args(fn, a, true, T_max, stats ? 2500000 : 0)) return rc;
+  for (int i = 0; i < a->nclip; ++i) {
+    FLK_REQUIRE(first[i] >= 0 && first[i] % gop == 0, "%s: clip %d: first %d is not a non-negative multiple of gop %d (a span starts on an intra frame)",
+                fn, i, first[i], gop);
+    FLK_REQUIRE(count[i] >= 1 && count[i] <= T_max, "%s: clip %d: count %d outside 1..T_max %d", fn, i, count[i], T_max);
+    FLK_REQUIRE((int64_t)first[i] + count[i] <= a->clips[i].T, "%s: clip %d: span %d + %d beyond its %d frames", fn, i, first[i], count[i],
+                a->clips[i].T);
+  }
+  return flk_codec_roundtrip_gop_launch(a, gop, first, count, T_max, tone, stats, (hipStream_t)stream);
 }
 
 // The gradient of a toned preparation (csrc/prepare.hip) and the slope tables it resamples (csrc/attack.hip, csrc/illum.hip)

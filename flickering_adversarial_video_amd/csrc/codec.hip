@@ -25,6 +25,10 @@
 // A block outside the padded image is not computed.  Every output byte is a pure function of its MCU: the result does not depend on
 // the tile or the grid.  Stats are integer sums (LDS and global integer atomics): exact in any order.  No allocation, no
 // synchronisation with the host.
+//
+// Inter-frame prediction (codec_gop_kernel below): closed GOPs of one intra frame, coded as above, and P-frames that code
+// the residual against the previous frame's reconstruction at zero motion with one flat quantiser step.  A workgroup walks one GOP of
+// one tile with the reference planes in LDS.
 #include "flk_internal.h"
 
 namespace {
@@ -289,6 +293,234 @@ __global__ __launch_bounds__(kCodecThreads) void codec_roundtrip_kernel(const Co
   }
 }
 
+// ---- inter-frame prediction: closed GOPs of one intra frame and zero-motion P-frames ----
+// A P-frame's 8x8 block: the residual against the co-located block of the previous reconstruction through the same transform pair
+// and ONE flat quantiser step Qp (rounding offset a quarter of a step), added back onto the reference, which it replaces in place.
+// rqp: the reciprocal of 8 Qp, a first guess of the quotient as in codec_block.
+__device__ __forceinline__ void codec_block_inter(const uint8_t* cur, uint8_t* ref, int pitch, int Qp, float rqp, int& nz, int& mag) {
+  int v[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint2 w = *(const uint2*)(cur + r * pitch), u = *(const uint2*)(ref + r * pitch);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[r * 8 + k] = (int)((w.x >> (8 * k)) & 255u) - (int)((u.x >> (8 * k)) & 255u);
+      v[r * 8 + 4 + k] = (int)((w.y >> (8 * k)) & 255u) - (int)((u.y >> (8 * k)) & 255u);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) fdct8<true, 11>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) fdct8<false, 15>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+  const int d = Qp << 3;
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int f = v[k];
+    const int n = abs(f) + (d >> 2);                   // <= 16320 + 510 < 2^15: exact in fp32
+    int lev = (int)((float)n * rqp);                   // within 1 of n / d
+    const int rem = n - lev * d;
+    lev += rem >= d ? 1 : (rem < 0 ? -1 : 0);          // the exact quotient
+    nz += lev != 0;
+    mag += lev;
+    v[k] = (f < 0 ? -lev : lev) * Qp;
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) idct8<11>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    idct8<18>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+    const uint2 u = *(const uint2*)(ref + r * pitch);
+    uint2 w = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      w.x |= (unsigned)clamp255(v[r * 8 + k] + (int)((u.x >> (8 * k)) & 255u)) << (8 * k);
+      w.y |= (unsigned)clamp255(v[r * 8 + 4 + k] + (int)((u.y >> (8 * k)) & 255u)) << (8 * k);
+    }
+    *(uint2*)(ref + r * pitch) = w;
+  }
+}
+
+struct CodecGopClipDev {                       // 56 bytes, as CodecClipDev: the span's first frame is folded into src, so T is not needed
+  const uint8_t* src;                          // the span's first frame (a multiple of gop: its frame t is intra iff t % gop == 0)
+  uint8_t* dst;
+  long long pitch_t, dpitch_t;
+  int pitch_h, dpitch_h;
+  int count, Hs, Ws;                           // frames of the span
+  int ntx;
+};
+struct CodecGopLaunch {
+  const uint8_t* tone;                         // device uint8 [nclip][T_max][256][3] or null
+  int* stats;                                  // device int32 [nclip][T_max][2] or null (zeroed by the host entry)
+  int gop, T_max;
+  int qp, pad_;                                // the P-frames' step
+  unsigned short q[2][64];
+  CodecGopClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(sizeof(CodecGopLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+// Workgroup = (tile, GOP of the span, clip): it walks its GOP's frames in order, the reconstructed planes of the previous frame kept in
+// LDS (plane set 1; set 0 takes a P-frame's own planes).  Zero motion: an output byte depends on its own MCU's history within the GOP
+// alone, so there is no workspace in memory and no dependency between workgroups.  Per frame the phases are those of
+// codec_roundtrip_kernel (whose device code is left as it is, hence the restatement); C reads set 0 and set 1 and writes set 1.
+template <bool S420>
+__global__ __launch_bounds__(kCodecThreads) void codec_gop_kernel(const CodecGopLaunch p) {
+  constexpr int TH = S420 ? 64 : 32;
+  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;
+  __shared__ unsigned stage[TH * kSW];
+  __shared__ __attribute__((aligned(8))) uint8_t Yp[2][TH * kTW];
+  __shared__ __attribute__((aligned(8))) uint8_t Cbp[2][CH * CW];
+  __shared__ __attribute__((aligned(8))) uint8_t Crp[2][CH * CW];
+  __shared__ uint8_t tone_lds[768];
+  __shared__ int mis_of[TH];
+  __shared__ int qt[2][64];
+  __shared__ float rq[2][64];
+  __shared__ int red[2];
+
+  const CodecGopClipDev& c = p.clip[blockIdx.z];
+  constexpr int M = S420 ? 16 : 8;
+  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
+  const int nty = (Hpad + TH - 1) / TH;
+  const int t0 = (int)blockIdx.y * p.gop;              // gridDim.y * gop <= 65535 + gop: no overflow
+  if ((int)blockIdx.x >= c.ntx * nty || t0 >= c.count) return;              // uniform over the workgroup
+  const int t1 = min(t0 + p.gop, c.count);
+  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
+  const int y0 = ty * TH, x0 = tx * kTW;
+  const int tid = threadIdx.x;
+  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);
+  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);
+  const int nbytes = ncols * 3;
+  const int Qp = p.qp;
+  const float rqp = 1.0f / (float)(Qp << 3);
+  const bool toned = p.tone != nullptr;
+
+  if (tid < 128) {
+    const int Q = p.q[tid >> 6][tid & 63];
+    qt[tid >> 6][tid & 63] = Q;
+    rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
+  }
+
+  for (int t = t0; t < t1; ++t) {
+    const bool intra = t == t0;
+    const int w = intra ? 1 : 0;                       // the plane set phase B fills: an intra frame is transformed in place in set 1
+    const size_t kt = (size_t)blockIdx.z * p.T_max + t;
+    const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+
+    // ---- A ----
+    if (tid < 2) red[tid] = 0;
+    if (toned) {
+      const uint8_t* g = p.tone + kt * 768;
+      for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
+    }
+    for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+      const int r = k / kSW, wd = k - r * kSW;
+      const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
+      const int mis = (int)((size_t)row & 3);
+      if (wd == 0) mis_of[r] = mis;
+      if (4 * wd < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * wd);
+    }
+    __syncthreads();
+
+    // ---- B ----
+    const uint8_t* sb = (const uint8_t*)stage;
+    auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
+      const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
+      const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
+      int R = px[0], G = px[1], B = px[2];
+      if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
+      rgb_to_ycc(R, G, B, Y, Cb, Cr);
+    };
+    if constexpr (S420) {
+      const int qc = pcol >> 1;
+      for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
+        const int r2 = k / qc, c2 = k - r2 * qc;
+        int sb_ = 0, sr_ = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          int Y, Cb, Cr;
+          ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
+          Yp[w][(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
+          sb_ += Cb; sr_ += Cr;
+        }
+        const int bias = 1 + (c2 & 1);
+        Cbp[w][r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
+        Crp[w][r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
+      }
+    } else {
+      for (int k = tid; k < prow * pcol; k += kCodecThreads) {
+        const int r = k / pcol, col = k - r * pcol;
+        int Y, Cb, Cr;
+        ycc(r, col, Y, Cb, Cr);
+        Yp[w][r * kTW + col] = (uint8_t)Y;
+        Cbp[w][r * CW + col] = (uint8_t)Cb;
+        Crp[w][r * CW + col] = (uint8_t)Cr;
+      }
+    }
+    __syncthreads();
+
+    // ---- C: one block per thread; every thread keeps its blocks through the GOP ----
+    {
+      constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
+      const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
+      int nz = 0, mag = 0;
+      for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
+        if (b < NBY) {
+          const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
+          const int o = by * 8 * kTW + bx * 8;
+          if (by * 8 < prow && bx * 8 < pcol) {
+            if (intra) codec_block(Yp[1] + o, kTW, qt[0], rq[0], nz, mag);
+            else codec_block_inter(Yp[0] + o, Yp[1] + o, kTW, Qp, rqp, nz, mag);
+          }
+        } else {
+          const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
+          const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
+          const int o = by * 8 * CW + bx * 8;
+          if (by * 8 < cprow && bx * 8 < cpcol) {
+            if (intra) codec_block((pl ? Crp[1] : Cbp[1]) + o, CW, qt[1], rq[1], nz, mag);
+            else codec_block_inter((pl ? Crp[0] : Cbp[0]) + o, (pl ? Crp[1] : Cbp[1]) + o, CW, Qp, rqp, nz, mag);
+          }
+        }
+      }
+      if (p.stats && (nz | mag)) {
+        atomicAdd(&red[0], nz);
+        atomicAdd(&red[1], mag);
+      }
+    }
+    __syncthreads();
+    if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
+
+    // ---- D: the reconstruction (set 1) -> RGB bytes as the destination rows lie in memory, then stored ----
+    uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
+    uint8_t* ob = (uint8_t*)stage;
+    for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
+      const int r = k / ncols, col = k - r * ncols;
+      const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
+      const int Y = Yp[1][r * kTW + col];
+      const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
+      const int cb = (int)Cbp[1][ci] - 128, cr = (int)Crp[1][ci] - 128;
+      uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
+      o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
+      o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+      o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
+    }
+    __syncthreads();
+    for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+      const int r = k / kSW, wd = k - r * kSW;
+      uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
+      const int dm = (int)((size_t)row & 3);
+      const int lo = dm, hi = dm + nbytes;
+      if (4 * wd >= hi || 4 * wd + 4 <= lo) continue;
+      if (4 * wd >= lo && 4 * wd + 4 <= hi) {
+        *(unsigned*)(row - dm + 4 * wd) = stage[k];
+      } else {
+#pragma unroll
+        for (int b = 0; b < 4; ++b)
+          if (4 * wd + b >= lo && 4 * wd + b < hi) (row - dm)[4 * wd + b] = ob[k * 4 + b];
+      }
+    }
+    __syncthreads();                                   // the next frame stages into what this one stored from
+  }
+}
+
 }  // namespace
 
 // the two quantisation tables at `quality` (1..100): ITU T.81 Annex K under the IJG scaling rule, row-major
@@ -333,6 +565,47 @@ int flk_codec_roundtrip_launch(const flk_codec_args* a, const int32_t* frame_idx
   const dim3 grid((unsigned)max_tiles, (unsigned)T_out, (unsigned)a->nclip);
   if (s420) FLK_LAUNCH_KERNEL(codec_roundtrip_kernel<true>, grid, dim3(kCodecThreads), 0, stream, p);
   else FLK_LAUNCH_KERNEL(codec_roundtrip_kernel<false>, grid, dim3(kCodecThreads), 0, stream, p);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// the P-frames' quantiser step at `quality` (1..100): MPEG-2's flat non-intra 16 under the IJG scaling rule
+int flk_codec_inter_step_host(int quality) {
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  const int q = (16 * s + 50) / 100;
+  return q < 1 ? 1 : q > 255 ? 255 : q;
+}
+
+// arguments already validated (api.cpp: flk_codec_roundtrip_gop_u8); everything here up to the launch is host arithmetic
+int flk_codec_roundtrip_gop_launch(const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max,
+                                   const uint8_t* tone, int32_t* stats, hipStream_t stream) {
+  CodecGopLaunch p;
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
+  p.tone = tone; p.stats = stats; p.gop = gop; p.T_max = T_max; p.qp = flk_codec_inter_step_host(a->quality); p.pad_ = 0;
+  int32_t ql[64], qc[64];
+  flk_codec_tables_host(a->quality, ql, qc);
+  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
+  long long max_tiles = 1;
+  int max_gops = 1;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& s = a->clips[i];
+    CodecGopClipDev& d = p.clip[i];
+    d.src = s.src + (long long)first[i] * s.pitch_t; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
+    d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
+    d.count = count[i]; d.Hs = s.Hs; d.Ws = s.Ws;
+    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
+    d.ntx = (int)((Wpad + kTW - 1) / kTW);
+    const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
+    if (tiles > max_tiles) max_tiles = tiles;
+    const int gops = (count[i] + gop - 1) / gop;       // count <= 65535: no overflow
+    if (gops > max_gops) max_gops = gops;
+  }
+  FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_gop_u8: a frame of more than 2^31 tiles");
+  if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_max * 2 * sizeof(int32_t), stream));
+  const dim3 grid((unsigned)max_tiles, (unsigned)max_gops, (unsigned)a->nclip);
+  if (s420) FLK_LAUNCH_KERNEL(codec_gop_kernel<true>, grid, dim3(kCodecThreads), 0, stream, p);
+  else FLK_LAUNCH_KERNEL(codec_gop_kernel<false>, grid, dim3(kCodecThreads), 0, stream, p);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

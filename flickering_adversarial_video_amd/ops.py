@@ -1153,7 +1153,14 @@ def codec_tables(quality):
     return np.asarray(ql[:], np.int32), np.asarray(qc[:], np.int32)
 
 
-def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=False):
+def codec_inter_step(quality):
+    """flk_codec_inter_step: the P-frames' quantiser step at ``quality`` as the library makes it (host)"""
+    qp = C.c_int32()
+    check(load().flk_codec_inter_step(int(quality), C.byref(qp)))
+    return int(qp.value)
+
+
+def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=False, spans=None):
     """The delivered videos after lossy intra-frame compression (flk_codec_roundtrip_u8; ``videoresnet_spec.codec_roundtrip_host`` is
     its definition, bit for bit): one kernel launch per ``FLK_PREP_MAX_CLIPS`` videos.
 
@@ -1166,7 +1173,12 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
     ``tone``: CUDA uint8 ``[len(videos), T, 256, 3]`` (``flicker_tone_tables``), T the common output length: every frame goes through
     its byte -> byte table first -- bitwise the call on the exported videos, which are never written.
     ``out``: a list of uint8 tensors to fill, which may be views with row and frame pitches of their own; bytes outside them are
-    not touched.  Everything is refused before any device call."""
+    not touched.  Everything is refused before any device call.
+    A codec with ``gop`` > 1 (flk_codec_roundtrip_gop_u8: closed GOPs of zero-motion P-frames, whose frames depend on their
+    predecessors) takes no ``frame_idx`` but ``spans``: host integers ``[len(videos), 2]`` of (first, count), first a multiple of
+    ``gop``; the default is the whole video, ``(0, N_k)``.  Output ``k`` is ``[count_k,H_k,W_k,3]``, video frames first .. first +
+    count - 1 -- bitwise those frames of the whole video's result; ``stats`` are ``[count_k,2]``; ``tone`` is
+    ``[len(videos), max count (or more), 256, 3]``, row t the table of video frame first_k + t (rows past a video's count are not read)."""
     from .videoresnet_spec import Codec
     what = "codec_roundtrip"
     if not isinstance(codec, Codec):
@@ -1180,6 +1192,27 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
             raise ValueError(f"{what}: video {k} must be a CUDA uint8 tensor [N,H,W,3], got {desc}")
     n, dev = len(vids), vids[0].device
     table = None
+    gop = codec.gop
+    if gop > 1 and frame_idx is not None:
+        raise ValueError(f"{what}: a codec with gop {gop} predicts every frame from the one before it: give spans=(first, count) per video, not "
+                         f"frame_idx")
+    if spans is not None:
+        if gop == 1:
+            raise ValueError(f"{what}: spans go with a codec of gop > 1 (an intra-frame codec takes frame_idx)")
+        sp = spans.numpy() if torch.is_tensor(spans) and not spans.is_cuda else spans
+        if torch.is_tensor(sp):
+            raise ValueError(f"{what}: spans must be host integers (they are checked against the videos before anything is launched)")
+        sp = np.asarray(sp)
+        if sp.shape != (n, 2) or sp.dtype.kind not in "iu":
+            raise ValueError(f"{what}: spans must be integers [{n}, 2] of (first, count), got {sp.shape} {sp.dtype}")
+        sp = sp.astype(np.int64)
+        for k, v in enumerate(vids):
+            f, cnt = int(sp[k, 0]), int(sp[k, 1])
+            if f < 0 or f % gop or cnt < 1 or f + cnt > v.shape[0]:
+                raise ValueError(f"{what}: video {k}: span (first {f}, count {cnt}) must start on a multiple of gop {gop} and lie inside its "
+                                 f"{v.shape[0]} frames")
+    elif gop > 1:
+        sp = np.asarray([(0, int(v.shape[0])) for v in vids], np.int64)
     if frame_idx is not None:
         rows = frame_idx.numpy() if torch.is_tensor(frame_idx) and not frame_idx.is_cuda else frame_idx
         if torch.is_tensor(rows):
@@ -1191,10 +1224,13 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
         for k, v in enumerate(vids):
             if table[k].min() < 0 or table[k].max() >= v.shape[0]:
                 raise ValueError(f"{what}: video {k}: frame_idx holds {int(table[k].min())} .. {int(table[k].max())}, the video has {v.shape[0]} frames")
-    lens = [int(v.shape[0]) if table is None else table.shape[1] for v in vids]
+    lens = [int(sp[k, 1]) if gop > 1 else int(v.shape[0]) if table is None else table.shape[1] for k, v in enumerate(vids)]
     if max(lens) > 65535:
-        raise ValueError(f"{what}: {max(lens)} frames in one video, more than 65535 (cut it, or give frame_idx)")
-    if tone is not None:
+        raise ValueError(f"{what}: {max(lens)} frames in one video, more than 65535 (cut it, or give {'spans' if gop > 1 else 'frame_idx'})")
+    if tone is not None and gop > 1:               # rows past the longest span (a caller's buffer made in whole pieces) are allowed, and not read
+        more = torch.is_tensor(tone) and tone.dim() == 4 and max(lens) < tone.shape[1] <= 65535
+        _check_tone(what, "tone", tone, torch.uint8, (n, tone.shape[1] if more else max(lens), 256, 3), dev)
+    elif tone is not None:
         if len(set(lens)) != 1:
             raise ValueError(f"{what}: tone needs one output length for every video (give frame_idx), got lengths {sorted(set(lens))}")
         _check_tone(what, "tone", tone, torch.uint8, (n, lens[0], 256, 3), dev)
@@ -1219,25 +1255,43 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
         lo_d, hi_d = o.data_ptr(), o.data_ptr() + (shape[0] - 1) * max(o.stride(0), 0) + (shape[1] - 1) * o.stride(1) + 3 * shape[2]
         if lo_s < hi_d and lo_d < hi_s:
             raise ValueError(f"{what}: out[{k}] overlaps its source (an MCU reads pixels that other workgroups write)")
+    st_out = [None] * n
+    sub = _lib.FLK_CODEC_420 if codec.subsampling == "420" else _lib.FLK_CODEC_444
+
+    def clip_array(part):
+        arr = (_lib.CodecClip * len(part))()
+        for d, k in zip(arr, part):
+            v, o = keep[k], outs[k]
+            d.src, d.T, d.Hs, d.Ws = v.data_ptr(), int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
+            d.pitch_t, d.pitch_h = max(int(v.stride(0)), 1), int(v.stride(1))
+            d.dst, d.dst_pitch_t, d.dst_pitch_h = o.data_ptr(), max(int(o.stride(0)), 1), int(o.stride(1))
+        a = _lib.CodecArgs()
+        a.nclip, a.quality, a.subsampling, a.clips = len(part), codec.quality, sub, arr
+        return a, arr
+
+    if gop > 1:                                 # one launch per FLK_PREP_MAX_CLIPS consecutive videos; every launch has the rows of max count
+        T_max = max(lens) if tone is None else int(tone.shape[1])
+        for first in range(0, n, FLK_PREP_MAX_CLIPS):
+            part = list(range(first, min(first + FLK_PREP_MAX_CLIPS, n)))
+            a, arr = clip_array(part)
+            firsts, counts = ((C.c_int32 * len(part))(*[int(sp[k, j]) for k in part]) for j in (0, 1))
+            st = torch.empty((len(part), T_max, 2), dtype=torch.int32, device=dev) if stats else None
+            check(load().flk_codec_roundtrip_gop_u8(C.byref(a), gop, firsts, counts, T_max, None if tone is None else ptr(tone[first:]), ptr(st),
+                                                    stream_ptr()))
+            if stats:
+                for j, k in enumerate(part):
+                    st_out[k] = st[j, :lens[k]]
+        return (outs, st_out) if stats else outs
     tab_dev = None if table is None else torch.from_numpy(table.astype(np.int32)).to(dev)
     groups = {}
     for k in range(n):                          # one launch has one output length: videos of equal length share launches
         groups.setdefault(lens[k], []).append(k)
     if table is not None or tone is not None:
         assert len(groups) == 1
-    st_out = [None] * n
-    sub = _lib.FLK_CODEC_420 if codec.subsampling == "420" else _lib.FLK_CODEC_444
     for T_out, members in groups.items():
         for first in range(0, len(members), FLK_PREP_MAX_CLIPS):
             part = members[first:first + FLK_PREP_MAX_CLIPS]
-            arr = (_lib.CodecClip * len(part))()
-            for d, k in zip(arr, part):
-                v, o = keep[k], outs[k]
-                d.src, d.T, d.Hs, d.Ws = v.data_ptr(), int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
-                d.pitch_t, d.pitch_h = max(int(v.stride(0)), 1), int(v.stride(1))
-                d.dst, d.dst_pitch_t, d.dst_pitch_h = o.data_ptr(), max(int(o.stride(0)), 1), int(o.stride(1))
-            a = _lib.CodecArgs()
-            a.nclip, a.quality, a.subsampling, a.clips = len(part), codec.quality, sub, arr
+            a, arr = clip_array(part)
             st = torch.empty((len(part), T_out, 2), dtype=torch.int32, device=dev) if stats else None
             # with a table or a tone the launch's members are consecutive videos: its rows of the tables start at part[0]
             check(load().flk_codec_roundtrip_u8(C.byref(a), None if tab_dev is None else ptr(tab_dev[part[0]:]), T_out,

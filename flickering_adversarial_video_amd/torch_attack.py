@@ -321,6 +321,21 @@ class Perturbation:
         return ops.make_export_apply_args(x, delta, shift_p=shift_p, delta_T=delta_T,
                                           per_line=self.video_time and delta.dim() - (0 if delta_T else 1) == 3, **kw)
 
+    def export_args_like_last(self, x, frame_numbers, of, captured):
+        """video time: the export arguments of FURTHER clips ``x`` [n,clip_T,h,w,3] at ``frame_numbers`` (integers [n,clip_T]) under the
+        phase and -- ``captured`` -- the capture channel that the last adversarial apply gave clip ``of[i]`` of its batch: frame for
+        frame the perturbation that apply would have given those frame numbers.  Nothing the last apply left behind (its rows, its
+        tables, its per-clip perturbation, which its gradient still reads) is touched."""
+        dev, of = self.perturbation.device, np.asarray(of, dtype=np.int64)
+        ph = np.repeat(self.last_phases, self.clips_per_video)[of]
+        rows = torch.from_numpy(flicker_rows(np.asarray(frame_numbers), self.T, ph)).to(dev)
+        if captured:
+            taps, gain = (torch.from_numpy(np.ascontiguousarray(self.last_capture[key][of])).to(dev) for key in ("taps", "gain_rows"))
+            delta = ops.flicker_rows_mix(self.perturbation, rows, taps, gain)
+        else:
+            delta = ops.flicker_rows_gather(self.perturbation, rows)
+        return ops.make_export_apply_args(x, delta, shift_p=0, delta_T=0, per_line=False, **self._shared_args(x, True, None))
+
     def captured_perturbation(self, capture, H=None):
         """video time: the shared perturbation as ONE capture channel records it, fp32 [P,3] -- one ops.flicker_rows_mix launch over
         ``rows = arange(P)`` as one clip of P frames: row r of the result is what a frame that carries row r records.  ``capture``: a dict
@@ -552,7 +567,9 @@ class FlickerVideoResNet:
         # forward lays the flicker over the batch's frames and compresses them in one launch (ops.codec_roundtrip(frame_idx=, tone=)) into
         # reused uint8 buffers, prepares those and scores them clean -- the chain ``evaluate_videos(quantise="video", codec=)`` scores, bit
         # for bit.  The backward is the train_delivered one on the source videos: straight through the codec, whose Jacobian is taken as
-        # the identity.  None (default): every launch as before
+        # the identity.  A codec with ``gop`` > 1 compresses per clip the span from the intra frame at
+        # or before the clip's first frame (ops.codec_roundtrip(spans=, tone=)); the surrogate rec ~ cur holds for a P-frame as for an
+        # intra frame, so the backward is the same.  None (default): every launch as before
         if self._check_codec(codec) is not None and not self.train_delivered:
             raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
                              "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")
@@ -1118,28 +1135,59 @@ class FlickerVideoResNet:
             self._ramp = ops.tone_ramp(self.B, self.T, dev)
             self._pg_scratch = torch.empty(max(1, ops.load().flk_clip_prepare_grad_scratch_bytes(min(self.B, ops.FLK_PREP_MAX_CLIPS), self.T, self.H) // 4),
                                            dtype=torch.float32, device=dev)
-        tone = self._buf("_tone", (self.B, self.T, 256, 3), torch.uint8)
         ta = pm.export_args(self._ramp, True, shift_p="draw", capture=capture)      # the per-clip delta of this batch's frame numbers
-        ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=tone)
         kw = dict(out=self._clip_buf("_prep_buf"), boxes=boxes, flips=flips)
+        if self.codec is not None and self.codec.gop > 1:
+            frames, picked = self._gop_frames(clips, rows, capture is not None)
+            self._forward(self._prepare_clips(frames, frame_idx=picked, **kw), False)
+            return ta
+        tone = self._buf("_tone", (self.B, self.T, 256, 3), torch.uint8)
+        ops.flicker_tone_tables(ta, pm.illum if self.illumination else None, out=tone)
         if self.codec is not None:
             # the compressed delivered video: ONE codec launch tones and compresses only the batch's B * T frames at their native
             # resolution into uint8 buffers the engine reuses; the untoned sampled preparation of those follows (identity frame table)
-            if not hasattr(self, "_codec_bufs"):
-                self._codec_bufs = {}
-            bufs = self._codec_bufs
-            want = [(k, int(v.shape[1]), int(v.shape[2])) for k, v in enumerate(clips)]
-            for key in [key for key in bufs if key not in want]:
-                del bufs[key]
-            for key in want:
-                if key not in bufs:
-                    bufs[key] = torch.empty((self.T, key[1], key[2], 3), dtype=torch.uint8, device=dev)
-            frames = ops.codec_roundtrip(list(clips), self.codec, frame_idx=rows, tone=tone, out=[bufs[key] for key in want])
+            frames = ops.codec_roundtrip(list(clips), self.codec, frame_idx=rows, tone=tone, out=self._codec_out(clips, [self.T] * len(clips)))
             x = self._prepare_clips(frames, frame_idx=np.broadcast_to(np.arange(self.T), (len(frames), self.T)), **kw)
         else:
             x = self._prepare_clips(clips, frame_idx=rows, tone=tone, **kw)
         self._forward(x, False)
         return ta
+
+    def _gop_frames(self, clips, rows, captured):
+        """``_forward_delivered`` under a codec with GOPs: a P-frame needs every frame since its intra frame, so per clip the SPAN from
+        the intra frame at or before its first frame to its last frame is toned and compressed -- the lead-in frames in front of the
+        clip at their own frame numbers, under the phase and the capture channel the step just drew for the clip -- in ONE GOP launch
+        into reused uint8 buffers.  Returns them with the frame table that picks the clip's frames out of its span: what the untoned
+        sampled preparation takes.  (The tone tables come from one export launch on the ramp, the span cut into pieces of T frames that
+        stand in it as further clips: [B * pieces, T, 256, 3] IS [B, pieces * T, 256, 3].)"""
+        pm, dev, T, N = self.pert_model, self._logits.device, self.T, self.codec.gop
+        rows = np.asarray(rows, dtype=np.int64)
+        first = rows.min(1) // N * N
+        count = rows.max(1) - first + 1
+        pieces = int(-(-count.max() // T))
+        numbers = (first[:, None] + np.arange(pieces * T)).reshape(self.B * pieces, T)        # past a span's end: made, never read
+        if getattr(self, "_span_ramp", None) is None or self._span_ramp.shape[0] != self.B * pieces:
+            self._span_ramp = ops.tone_ramp(self.B * pieces, T, dev)
+            self._span_tone = torch.empty((self.B * pieces, T, 256, 3), dtype=torch.uint8, device=dev)
+        sa = pm.export_args_like_last(self._span_ramp, numbers, np.repeat(np.arange(self.B), pieces), captured)
+        ops.flicker_tone_tables(sa, pm.illum if self.illumination else None, out=self._span_tone)
+        frames = ops.codec_roundtrip(list(clips), self.codec, spans=np.stack([first, count], 1), tone=self._span_tone.view(self.B, pieces * T, 256, 3),
+                                     out=self._codec_out(clips, count))
+        return frames, rows - first[:, None]
+
+    def _codec_out(self, clips, lengths):
+        """the uint8 buffers the codec launch of ``_forward_delivered`` writes, one per clip of the batch at its video's resolution and
+        of ``lengths[k]`` frames: kept from step to step while the slot's resolution stays, grown when a longer span comes"""
+        if not hasattr(self, "_codec_bufs"):
+            self._codec_bufs = {}
+        bufs = self._codec_bufs
+        want = [(k, int(v.shape[1]), int(v.shape[2])) for k, v in enumerate(clips)]
+        for key in [key for key in bufs if key not in want]:
+            del bufs[key]
+        for key, n in zip(want, lengths):
+            if key not in bufs or bufs[key].shape[0] < n:
+                bufs[key] = torch.empty((int(n), key[1], key[2], 3), dtype=torch.uint8, device=self._logits.device)
+        return [bufs[key][:int(n)] for key, n in zip(want, lengths)]
 
     def step(self, x, labels, criterion, lr=1e-3, update=True, _delivered=None):
         """one iteration of fit_single_video_attack (model.py:1073-1101): forward, Losses, backward, torch-Adam step.

@@ -1176,27 +1176,36 @@ def check_codec(quality, subsampling, what="codec"):
     return int(quality), str(subsampling)
 
 
-class Codec:
-    """A lossy intra-frame codec the delivered video goes through: ``quality`` 1..100 (the IJG scale) and chroma ``subsampling``
-    "444" or "420".  A checked value object; ``ops.codec_roundtrip`` and the engines take it."""
-    __slots__ = ("quality", "subsampling")
+def check_codec_gop(gop, what="codec"):
+    """the GOP length of a codec, checked: an integer 1..65535 (1: every frame is an intra frame)"""
+    if isinstance(gop, bool) or not isinstance(gop, (int, np.integer)) or not 1 <= int(gop) <= 65535:
+        raise ValueError(f"{what}: gop must be an integer in 1..65535, got {gop!r}")
+    return int(gop)
 
-    def __init__(self, quality=75, subsampling="420"):
+
+class Codec:
+    """A lossy codec the delivered video goes through: ``quality`` 1..100 (the IJG scale), chroma ``subsampling`` "444" or "420" and
+    ``gop``, the distance between intra frames (1: intra-frame only; N > 1: closed GOPs of one intra frame and N - 1 zero-motion
+    P-frames).  A checked value object; ``ops.codec_roundtrip`` and the engines take it."""
+    __slots__ = ("quality", "subsampling", "gop")
+
+    def __init__(self, quality=75, subsampling="420", gop=1):
         q, s = check_codec(quality, subsampling, "Codec")
         object.__setattr__(self, "quality", q)
         object.__setattr__(self, "subsampling", s)
+        object.__setattr__(self, "gop", check_codec_gop(gop, "Codec"))
 
     def __setattr__(self, name, value):
         raise AttributeError("Codec is immutable")
 
     def __repr__(self):
-        return f"Codec(quality={self.quality}, subsampling={self.subsampling!r})"
+        return f"Codec(quality={self.quality}, subsampling={self.subsampling!r}" + (f", gop={self.gop})" if self.gop > 1 else ")")
 
     def __eq__(self, other):
-        return isinstance(other, Codec) and (self.quality, self.subsampling) == (other.quality, other.subsampling)
+        return isinstance(other, Codec) and (self.quality, self.subsampling, self.gop) == (other.quality, other.subsampling, other.gop)
 
     def __hash__(self):
-        return hash((self.quality, self.subsampling))
+        return hash((self.quality, self.subsampling, self.gop))
 
 
 def codec_tables(quality):
@@ -1205,6 +1214,14 @@ def codec_tables(quality):
     q, _ = check_codec(quality, "444", "codec_tables")
     s = 5000 // q if q < 50 else 200 - 2 * q
     return tuple(np.clip((np.asarray(b, np.int64) * s + 50) // 100, 1, 255).astype(np.int32) for b in (CODEC_BASE_LUMA, CODEC_BASE_CHROMA))
+
+
+def codec_inter_step(quality):
+    """the quantiser step of the P-frames at ``quality``: Qp = clamp((16 * s + 50) // 100, 1, 255), s the IJG scale -- MPEG-2's flat
+    default non-intra matrix (16 everywhere) under the rule of ``codec_tables``; one step for all 64 positions and all three planes"""
+    q, _ = check_codec(quality, "444", "codec_inter_step")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    return min(max((16 * s + 50) // 100, 1), 255)
 
 
 def _descale(x, n):
@@ -1265,7 +1282,23 @@ def _codec_plane(p, qt, dt):
     return o.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp), lev
 
 
-def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=False, _dtype=np.int32):
+def _codec_plane_inter(p, ref, qp, dt):
+    """a P-frame's padded plane [N, Hp, Wp] predicted from ``ref`` (the previous reconstruction, same shape, zero motion): the residual
+    through DCT, the flat quantiser ``qp`` (rounding offset 1/4 of a step) and back onto ``ref``; also the levels"""
+    N, Hp, Wp = p.shape
+    blocks = lambda a: a.reshape(N, Hp // 8, 8, Wp // 8, 8).transpose(0, 1, 3, 2, 4).astype(dt)   # [N, by, bx, row, col]
+    rb = blocks(ref)
+    f = _fdct_1d(blocks(p) - rb, -_P1_BITS, _C_BITS - _P1_BITS)                                  # the residual, -255..255: no -128
+    f = _fdct_1d(f.swapaxes(-1, -2), _P1_BITS, _C_BITS + _P1_BITS).swapaxes(-1, -2)
+    d = dt(qp << 3)
+    mag = (np.abs(f) + (d >> 2)) // d                                                           # a dead zone: 1/4 of a step, not 1/2
+    lev = np.where(f < 0, -mag, mag).astype(dt)
+    w = _idct_1d((lev * dt(qp)).swapaxes(-1, -2), _C_BITS - _P1_BITS).swapaxes(-1, -2)
+    o = np.clip(rb + _idct_1d(w, _C_BITS + _P1_BITS + 3), 0, 255)
+    return o.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp), lev
+
+
+def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=False, gop=1, first_frame=0, _dtype=np.int32):
     """The codec round trip on the host, in integers only: uint8 ``[N,H,W,3]`` (or one frame ``[H,W,3]``) -> uint8 of the same shape;
     with ``stats`` also int32 ``[N,2]``: per frame the number of non-zero quantised coefficients and the sum of their magnitudes.
     ``tone``: uint8 ``[N,256,3]`` (or ``[256,3]``), the byte -> byte table each frame goes through first.
@@ -1278,8 +1311,18 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
                (_idct_1d), + 128, clamp to 0..255
       420      chroma repeated 2 x 2
       colour   R = Y + ((91881 Cr' + 32768) >> 16);  G = Y + ((-22554 Cb' - 46802 Cr' + 32768) >> 16);  B = Y + ((116130 Cb' + 32768) >> 16)
-               with Cb' = Cb - 128, Cr' = Cr - 128; clamp to 0..255; crop"""
+               with Cb' = Cb - 128, Cr' = Cr - 128; clamp to 0..255; crop
+    ``gop`` > 1: frame t is video frame n = ``first_frame`` + t (``first_frame`` a multiple of ``gop``); n % gop == 0
+    is an intra frame, coded as above, every other one a P-frame predicted from the previous frame's reconstructed padded planes
+    ``ref`` at zero motion -- per plane and 8 x 8 block, in place of the DCT stage:
+      P        r = cur - ref (no - 128); the same two forward passes; level = sign * ((|f| + 2 Qp) // (8 Qp)), Qp = codec_inter_step(quality)
+               for every position and plane; rec = clamp(ref + idct(level * Qp), 0, 255) (the same two inverse passes, no + 128); ref <- rec
+    The stats of a P-frame count its levels."""
     quality, subsampling = check_codec(quality, subsampling, "codec_roundtrip_host")
+    gop = check_codec_gop(gop, "codec_roundtrip_host")
+    if isinstance(first_frame, bool) or not isinstance(first_frame, (int, np.integer)) or first_frame < 0 or first_frame % gop:
+        raise ValueError(f"codec_roundtrip_host: first_frame must be a non-negative multiple of gop {gop} (a span starts on an intra frame), "
+                         f"got {first_frame!r}")
     x = np.asarray(frames)
     single = x.ndim == 3
     if single:
@@ -1306,7 +1349,19 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
         bias = (1 + (np.arange(Wp // 2) & 1)).astype(dt)
         Cb, Cr = ((p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] + bias) >> 2 for p in (Cb, Cr))
     ql, qc = codec_tables(quality)
-    (Y, ly), (Cb, lb), (Cr, lr) = _codec_plane(Y, ql, dt), _codec_plane(Cb, qc, dt), _codec_plane(Cr, qc, dt)
+    if gop == 1:
+        (Y, ly), (Cb, lb), (Cr, lr) = _codec_plane(Y, ql, dt), _codec_plane(Cb, qc, dt), _codec_plane(Cr, qc, dt)
+    else:
+        qp = codec_inter_step(quality)
+        coded = []
+        for p, qt in ((Y, ql), (Cb, qc), (Cr, qc)):
+            rec, lev = [], []
+            for t in range(N):
+                r, l = _codec_plane(p[t:t + 1], qt, dt) if (first_frame + t) % gop == 0 else _codec_plane_inter(p[t:t + 1], rec[-1], qp, dt)
+                rec.append(r)
+                lev.append(l)
+            coded.append((np.concatenate(rec), np.concatenate(lev)))
+        (Y, ly), (Cb, lb), (Cr, lr) = coded
     if subsampling == "420":
         Cb, Cr = (p.repeat(2, 1).repeat(2, 2) for p in (Cb, Cr))
     cb, cr = Cb - 128, Cr - 128
@@ -1327,6 +1382,9 @@ def add_codec_arguments(ap):
                     "saved or trained on: --eval-quantised video, --save-adversarial-u8 of whole videos, --train-delivered")
     ap.add_argument("--codec-subsampling", default=None, choices=list(CODEC_SUBSAMPLINGS), help="the codec's chroma subsampling (default 420); "
                     "needs --codec-quality")
+    ap.add_argument("--codec-gop", type=int, default=None, metavar="N", help="the codec's distance between intra frames (default 1: every frame "
+                    "is an intra frame); N > 1 codes closed GOPs of one intra frame and N - 1 zero-motion P-frames, whose quantised temporal "
+                    "residual decides whether a flicker arrives; needs --codec-quality")
 
 
 def codec_from_arguments(ap, a, used):
@@ -1335,12 +1393,14 @@ def codec_from_arguments(ap, a, used):
     if a.codec_quality is None:
         if a.codec_subsampling is not None:
             ap.error("--codec-subsampling needs --codec-quality")
+        if a.codec_gop is not None:
+            ap.error("--codec-gop needs --codec-quality")
         return None
     if not used:
         ap.error("--codec-quality / --codec-subsampling act on whole delivered videos: give --eval-quantised video, --train-delivered or "
                  "--save-adversarial-u8 with whole videos")
     try:
-        return Codec(a.codec_quality, a.codec_subsampling or "420")
+        return Codec(a.codec_quality, a.codec_subsampling or "420", 1 if a.codec_gop is None else a.codec_gop)
     except ValueError as e:
         ap.error(str(e))
 

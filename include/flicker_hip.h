@@ -646,6 +646,28 @@ int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx /* 
                            const uint8_t* tone /* DEVICE [nclip][T_out][256][3] or NULL */, int32_t* stats /* DEVICE [nclip][T_out][2] or NULL */,
                            void* stream);
 
+/* Inter-frame prediction in the codec (csrc/codec.hip; videoresnet_spec.codec_roundtrip_host(gop=, first_frame=) is
+ * the definition, bit for bit): closed GOPs of `gop` frames.  Video frame n is an intra frame iff n % gop == 0, coded as
+ * flk_codec_roundtrip_u8 codes it; every other frame is a P-frame predicted at ZERO MOTION from the previous frame's reconstructed
+ * padded planes ref -- per plane (Y, Cb, Cr) and 8x8 block: r = cur - ref (no -128), the same forward transform,
+ * level = sign * ((|f| + 2 Qp) / (8 Qp)) (a rounding offset of 1/4 step), rec = clamp(ref + idct(level * Qp), 0, 255), ref <- rec.
+ * flk_codec_inter_step (host only): Qp = clamp((16 * s + 50) / 100, 1, 255), s the IJG scale of `quality` -- one step for all 64
+ *   positions and all three planes (MPEG-2's flat default non-intra matrix under the rule of flk_codec_tables).
+ * flk_codec_roundtrip_gop_u8: one launch for up to FLK_PREP_MAX_CLIPS clips.  Clip k's span is the count[k] video frames from
+ *   first[k] (HOST arrays; first[k] a multiple of gop, so every span starts on an intra frame); output frame t is video frame
+ *   first[k] + t, written at clips[k].dst + t * dst_pitch_t.  tone / stats rows are [k][t], T_max rows per clip; rows at or past
+ *   count[k] are not read / stay zero.  A workgroup walks one GOP of one tile with the reference planes in LDS: no workspace, no
+ *   allocation, no synchronisation; the result does not depend on the launch geometry.  gop == 1 is allowed (every frame intra).
+ *   FLK_EINVAL (before any GPU call): what flk_codec_roundtrip_u8 refuses of a / clips / quality / subsampling, stats on frames of
+ *   more than 2500000 padded pixels (a P-frame's magnitudes reach 766 per pixel, twice an intra frame's), null first or
+ *   count, gop outside 1..65535, T_max outside 1..65535, first[k] < 0 or not a multiple of gop, count[k] < 1, count[k] > T_max,
+ *   first[k] + count[k] > clips[k].T. */
+int flk_codec_inter_step(int quality, int32_t* qp);
+int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, const int32_t* first /* HOST [nclip] */,
+                               const int32_t* count /* HOST [nclip] */, int T_max,
+                               const uint8_t* tone /* DEVICE [nclip][T_max][256][3] or NULL */,
+                               int32_t* stats /* DEVICE [nclip][T_max][2] or NULL */, void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

@@ -109,7 +109,7 @@ def run_whole_videos(a):
             learner.pert_model.dynamic_max_norm = max(learner.pert_model.max_norm, r["perturbation/inf_norm"])      # ... under its own bound
             exported, st = learner.export_video(xd[i], stats=True, **({} if a.codec is None else {"codec": a.codec}))
             if a.codec is not None:             # the stored video went through the codec before it is scored
-                r["codec_quality"], r["codec_subsampling"] = a.codec.quality, a.codec.subsampling
+                r["codec_quality"], r["codec_subsampling"], r["codec_gop"] = a.codec.quality, a.codec.subsampling, a.codec.gop
             ev = learner.evaluate_videos([exported], labels[i:i + 1], num_samples=G, adversarial=False)
             r["quantised_video_pred"] = ev["video_preds"]
             r["quantised_video_is_adversarial"] = bool(ev["video_preds"][0] != labels[i])

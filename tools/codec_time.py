@@ -8,12 +8,15 @@
    moves) and the uint8 export of the same frames as one video (export_video).
 2. The mc3_18 batch-16 `step_videos` (bf16, 16 frames of 112 x 112, Adam, period 16, training transform) with and without a codec,
    in one process, stepping alternately, a HIP-event pair around every step.
-3. The no-codec step against the PARENT commit (`--parent-root PATH`: a checkout of the parent with its library built): the same
-   launches, so the trees only have to agree inside the run's spread.  A process per tree and round, alternating.
+   GOP legs (flk_codec_roundtrip_gop_u8, quality 75, `--gop` 12): `gop_launch_*` on 16 clips x (16 + 11 lead-in frames) x 240 x 320
+   beside `intra_same_*`, the intra launch of the same frames; `gop_video_*` / `intra_video_*` on one whole `--frames` video; and the
+   step with `Codec(75, "420", gop)` (`gop_420`) beside the intra one.
+3. The no-codec step and the intra launches against the PARENT commit (`--parent-root PATH`: a checkout of the parent with its library
+   built): the same launches, so the trees only have to agree inside the run's spread.  A process per tree and round, alternating.
 
 Prints one JSON line per leg and a summary line.  Needs the GPU; there is no fallback.
 
-    python tools/codec_time.py [--steps 30] [--warmup 6] [--rounds 2] [--reps 20] [--frames 300] [--parent-root PATH]"""
+    python tools/codec_time.py [--steps 30] [--warmup 6] [--rounds 2] [--reps 20] [--frames 300] [--gop 12] [--parent-root PATH]"""
 import argparse
 import json
 import os
@@ -43,7 +46,7 @@ def worker(a):
                   augment={"seed": 0}, sampling={"temporal_jitter": True, "random_shift": True, "seed": 0}, train_delivered=True)
     legs = {}
     for leg in a.legs.split(","):
-        kw = {} if leg == "delivered" else dict(codec=vs.Codec(75, leg.split("_")[1]))
+        kw = {} if leg == "delivered" else dict(codec=vs.Codec(75, leg.split("_")[1], **(dict(gop=a.gop) if leg.startswith("gop_") else {})))
         legs[leg] = FlickerVideoResNet("mc3_18", W, **common, **kw)
     first = next(iter(legs.values()))
     lab = first.logits(first.prepare_videos(videos, train=False), False).argmax(1).clone()
@@ -103,10 +106,41 @@ def launches(a, videos, eng, torch):
         calls[f"launch_{sub}_tone_idx"] = lambda a=args["videos"]: lib.flk_codec_roundtrip_u8(C.byref(a), ptr(table), T, ptr(tone), None, stream_ptr())
         # and through ops.codec_roundtrip: its checks, descriptors and the table upload included
         calls[f"wrapper_{sub}_tone_idx"] = lambda codec=vs.Codec(75, sub): ops.codec_roundtrip(videos, codec, frame_idx=rows, tone=tone, out=outs)
+    if hasattr(lib, "flk_codec_roundtrip_gop_u8"):           # (absent from a parent tree from before the GOP entry)
+        # GOPs: 16 spans of T + gop - 1 frames (a clip with the longest lead-in) from frame `gop` of every video, beside the intra launch of
+        # the same frames; and one whole video.  Spans and counts are host arrays of the call
+        L = T + a.gop - 1
+        assert a.gop + L <= a.frames, "--frames too short for the GOP legs"
+        span_outs = [torch.empty((L, 240, 320, 3), dtype=torch.uint8, device="cuda") for _ in range(B)]
+        whole_out = torch.empty_like(videos[0])
+
+        def gop_args(srcs, dsts, sub):
+            arr = (_lib.CodecClip * len(srcs))()
+            for d, v, o in zip(arr, srcs, dsts):
+                d.src, d.T, d.Hs, d.Ws, d.pitch_t, d.pitch_h = v.data_ptr(), v.shape[0], 240, 320, v.stride(0), v.stride(1)
+                d.dst, d.dst_pitch_t, d.dst_pitch_h = o.data_ptr(), o.stride(0), o.stride(1)
+            g = _lib.CodecArgs()
+            g.nclip, g.quality, g.subsampling, g.clips = len(srcs), 75, int(sub), arr
+            g._keep = arr
+            return g
+
+        def ints(v, n):
+            return (C.c_int32 * n)(*([v] * n))
+
+        for sub in vs.CODEC_SUBSAMPLINGS:
+            spans, same = gop_args(videos, span_outs, sub), gop_args([v[a.gop:a.gop + L] for v in videos], span_outs, sub)
+            whole = gop_args(videos[:1], [whole_out], sub)
+            calls[f"gop_launch_{sub}"] = lambda g=spans, f=ints(a.gop, B), c=ints(L, B): lib.flk_codec_roundtrip_gop_u8(
+                C.byref(g), a.gop, f, c, L, None, None, stream_ptr())
+            calls[f"intra_same_{sub}"] = lambda g=same: lib.flk_codec_roundtrip_u8(C.byref(g), None, L, None, None, stream_ptr())
+            calls[f"gop_video_{sub}"] = lambda g=whole, f=ints(0, 1), c=ints(a.frames, 1): lib.flk_codec_roundtrip_gop_u8(
+                C.byref(g), a.gop, f, c, a.frames, None, None, stream_ptr())
+            calls[f"intra_video_{sub}"] = lambda g=whole: lib.flk_codec_roundtrip_u8(C.byref(g), None, a.frames, None, None, stream_ptr())
     out = {}
     for name, call in calls.items():
         for _ in range(3):
-            call()
+            rc = call()
+            assert not isinstance(rc, int) or rc == 0, (name, lib.flk_last_error())
         v = []
         for _ in range(max(3, a.rounds * 3)):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -122,7 +156,7 @@ def launches(a, videos, eng, torch):
 
 def run_worker(root, legs, a, with_launches=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--legs", legs, "--steps", str(a.steps), "--warmup", str(a.warmup),
-           "--reps", str(a.reps), "--rounds", str(a.rounds), "--frames", str(a.frames)] + (["--launches"] if with_launches else [])
+           "--reps", str(a.reps), "--rounds", str(a.rounds), "--frames", str(a.frames), "--gop", str(a.gop)] + (["--launches"] if with_launches else [])
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"worker failed ({root}, {legs}):\n{r.stdout[-2000:]}{r.stderr[-4000:]}")
@@ -136,30 +170,40 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=300, help="frames of each of the 16 resident videos")
+    ap.add_argument("--gop", type=int, default=12, help="the GOP length of the GOP legs")
     ap.add_argument("--parent-root", default=None, help="a checkout of the parent commit with libflicker_hip.so built in it")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launches", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--root", default=HERE, help=argparse.SUPPRESS)
     ap.add_argument("--legs", default="delivered,codec_420,codec_444", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.gop < 2:
+        ap.error("--gop must be >= 2 (1 is the intra codec, which the other legs time)")
     if a.worker:
         return worker(a)
-    same = run_worker(HERE, "delivered,codec_420,codec_444", a, with_launches=True)
+    same = run_worker(HERE, "delivered,codec_420,codec_444,gop_420", a, with_launches=True)
     for leg, v in same.items():
         print(json.dumps({"what": "same build, one process", "leg": leg, **v}), flush=True)
     summary = {f"{leg}_minus_delivered_ms": round(same[leg]["median_ms"] - same["delivered"]["median_ms"], 4) for leg in ("codec_420", "codec_444")}
+    summary["gop_420_minus_codec_420_ms"] = round(same["gop_420"]["median_ms"] - same["codec_420"]["median_ms"], 4)
     for sub in ("444", "420"):
+        summary[f"gop_launch_{sub}_over_intra_same"] = round(same[f"gop_launch_{sub}"]["median_ms"] / same[f"intra_same_{sub}"]["median_ms"], 2)
+        summary[f"gop_video_{sub}_over_intra_video"] = round(same[f"gop_video_{sub}"]["median_ms"] / same[f"intra_video_{sub}"]["median_ms"], 2)
         summary[f"launch_{sub}_over_copy"] = round(same[f"launch_{sub}"]["median_ms"] / same["device_copy"]["median_ms"], 2)
         summary[f"launch_{sub}_over_export"] = round(same[f"launch_{sub}"]["median_ms"] / same["export_u8"]["median_ms"], 2)
     if a.parent_root:
-        med = {"this": [], "parent": []}
+        what = ("delivered", "launch_420", "launch_444")     # the no-codec step and the intra launches: the same device code in both trees
+        med = {w: {"this": [], "parent": []} for w in what}
         for k in range(a.rounds):                           # the two trees alternate, a process each; who goes first alternates too
             for tree in (("parent", "this"), ("this", "parent"))[k % 2]:
-                med[tree].append(run_worker(os.path.abspath(a.parent_root) if tree == "parent" else HERE, "delivered", a)["delivered"]["median_ms"])
-        print(json.dumps({"what": "no-codec step_videos, a process per tree and round", **{f"{t}_median_ms": v for t, v in med.items()}}), flush=True)
-        for tree, v in med.items():
-            summary[f"delivered_{tree}_ms"] = round(statistics.median(v), 4)
-            summary[f"delivered_{tree}_spread_ms"] = round(max(v) - min(v), 4)
+                legs = run_worker(os.path.abspath(a.parent_root) if tree == "parent" else HERE, "delivered", a, with_launches=True)
+                for w in what:
+                    med[w][tree].append(legs[w]["median_ms"])
+        for w in what:
+            print(json.dumps({"what": f"{w}, a process per tree and round", **{f"{t}_median_ms": v for t, v in med[w].items()}}), flush=True)
+            for tree, v in med[w].items():
+                summary[f"{w}_{tree}_ms"] = round(statistics.median(v), 4)
+                summary[f"{w}_{tree}_spread_ms"] = round(max(v) - min(v), 4)
     else:
         summary.update(parent="not measured")
     print(json.dumps({"summary": summary}), flush=True)
