@@ -118,6 +118,9 @@ _SIGS = {
     "flk_codec_inter_step": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "flk_codec_roundtrip_gop_u8": (C.c_int, [C.POINTER(CodecArgs), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
+    "flk_codec_mc_scratch_bytes": (C.c_int64, [C.POINTER(CodecArgs), C.c_int, C.POINTER(C.c_int32)]),
+    "flk_codec_roundtrip_mc_u8": (C.c_int, [C.POINTER(CodecArgs), C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "flk_version": (C.c_int, []),
     "flk_last_error": (C.c_char_p, []),
     "flk_conv_weights_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -301,6 +301,45 @@ extern "C" int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, cons
   return flk_codec_roundtrip_gop_launch(a, gop, first, count, T_max, tone, stats, (hipStream_t)stream);
 }
 
+// Motion-compensated P-frames (csrc/codec.hip): the GOP entry's contract plus the search range, the vectors and the workspace
+long long flk_codec_mc_scratch_host(const flk_codec_args* a, int gop, const int32_t* count);
+int flk_codec_roundtrip_mc_launch(const flk_codec_args* a, int gop, int search, const int32_t* first, const int32_t* count, int T_max,
+                                  const uint8_t* tone, int32_t* stats, int8_t* mv, int mv_stride, void* scratch, hipStream_t stream);
+
+extern "C" int64_t flk_codec_mc_scratch_bytes(const flk_codec_args* a, int gop, const int32_t* count) {
+  if (!a || a->nclip > FLK_PREP_MAX_CLIPS) return 0;
+  return flk_codec_mc_scratch_host(a, gop, count);
+}
+
+extern "C" int flk_codec_roundtrip_mc_u8(const flk_codec_args* a, int gop, int search, const int32_t* first, const int32_t* count, int T_max,
+                                         const uint8_t* tone, int32_t* stats, int8_t* mv, int mv_stride, void* scratch, int64_t scratch_bytes,
+                                         void* stream) {
+  const char* fn = "flk_codec_roundtrip_mc_u8";
+  FLK_REQUIRE(first && count, "%s: null first or count", fn);
+  FLK_REQUIRE(gop >= 1 && gop <= 65535, "%s: gop %d outside 1..65535", fn, gop);
+  FLK_REQUIRE(search >= 0 && search <= 15, "%s: search %d outside 0..15", fn, search);
+  if (int rc = check_codec_args(fn, a, true, T_max, stats ? 2500000 : 0)) return rc;
+  const int M = a->subsampling == FLK_CODEC_420 ? 16 : 8;
+  for (int i = 0; i < a->nclip; ++i) {
+    FLK_REQUIRE(first[i] >= 0 && first[i] % gop == 0, "%s: clip %d: first %d is not a non-negative multiple of gop %d (a span starts on an intra frame)",
+                fn, i, first[i], gop);
+    FLK_REQUIRE(count[i] >= 1 && count[i] <= T_max, "%s: clip %d: count %d outside 1..T_max %d", fn, i, count[i], T_max);
+    FLK_REQUIRE((int64_t)first[i] + count[i] <= a->clips[i].T, "%s: clip %d: span %d + %d beyond its %d frames", fn, i, first[i], count[i],
+                a->clips[i].T);
+    if (mv) {
+      const int64_t Hp = ((int64_t)a->clips[i].Hs + M - 1) / M * M, Wp = ((int64_t)a->clips[i].Ws + M - 1) / M * M;
+      const int64_t mbs = ((Hp + 15) / 16) * ((Wp + 15) / 16);
+      FLK_REQUIRE(mv_stride >= mbs, "%s: clip %d: mv_stride %d below its %lld macroblocks", fn, i, mv_stride, (long long)mbs);
+    }
+  }
+  const int64_t need = flk_codec_mc_scratch_host(a, gop, count);
+  FLK_REQUIRE(need > 0, "%s: the workspace of these clips cannot be sized (a plane set above 2^36 bytes)", fn);
+  FLK_REQUIRE(scratch && ((uintptr_t)scratch & 15) == 0, "%s: null scratch, or one not 16-byte aligned", fn);
+  FLK_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, flk_codec_mc_scratch_bytes asks for %lld", fn, (long long)scratch_bytes,
+              (long long)need);
+  return flk_codec_roundtrip_mc_launch(a, gop, search, first, count, T_max, tone, stats, mv, mv_stride, scratch, (hipStream_t)stream);
+}
+
 // The gradient of a toned preparation (csrc/prepare.hip) and the slope tables it resamples (csrc/attack.hip, csrc/illum.hip)
 int flk_clip_prepare_grad_launch(const flk_prepare_args* a, const flk_prep_box* boxes, const int32_t* frame_idx, int T_out, const float* slope,
                                  const float* scale, const void* gx_s2d, int dtype, float* gdelta, float* partials, hipStream_t stream);

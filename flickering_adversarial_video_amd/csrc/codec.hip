@@ -29,6 +29,9 @@
 // Inter-frame prediction (codec_gop_kernel below): closed GOPs of one intra frame, coded as above, and P-frames that code
 // the residual against the previous frame's reconstruction at zero motion with one flat quantiser step.  A workgroup walks one GOP of
 // one tile with the reference planes in LDS.
+//
+// Motion-compensated P-frames (codec_mc_kernel below): a full-pel block search per 16x16 macroblock in the previous
+// reconstruction, which then reaches across tiles: one launch per frame position of the GOP, the planes in a workspace in memory.
 #include "flk_internal.h"
 
 namespace {
@@ -521,6 +524,351 @@ __global__ __launch_bounds__(kCodecThreads) void codec_gop_kernel(const CodecGop
   }
 }
 
+// ---- motion-compensated P-frames: a block search per 16x16 macroblock ----
+// With vectors a block's reference comes from neighbouring tiles, so a workgroup can no longer walk its GOP alone.  ONE LAUNCH PER
+// FRAME POSITION j within the GOP: workgroup = (tile, GOP of the span, clip) handles frame j of its GOP, and the reconstructed padded
+// planes travel through a caller-supplied workspace, two plane sets per (clip, GOP), written at parity j & 1 and read at the other.
+// Launches depend on each other by stream order alone: no grid barrier, no flags.  Position 0 is the intra path plus the plane store.
+constexpr int kMcMaxClips = 48;                // clips per launch: the descriptors are 64 bytes here (the workspace offset)
+constexpr int kMaxSearch = 15;
+constexpr int kHaloX = 16;                     // columns staged left and right of the tile: whole dwords, >= kMaxSearch
+constexpr int kHP = kTW + 2 * kHaloX;          // bytes per staged reference row
+static_assert(kHaloX % 4 == 0 && kHaloX >= kMaxSearch && kHP % 4 == 0, "reference rows are staged as aligned dwords");
+
+struct CodecMcClipDev {                        // 64 bytes
+  const uint8_t* src;                          // the span's first frame, as in CodecGopClipDev
+  uint8_t* dst;
+  long long pitch_t, dpitch_t;
+  int pitch_h, dpitch_h;
+  int count, Hs, Ws;
+  int ntx;
+  long long ws_off;                            // the clip's plane sets within the workspace: [GOP][2][Y, Cb, Cr]
+};
+struct CodecMcLaunch {
+  const uint8_t* tone;                         // device uint8 [nclip][T_max][256][3] or null; rows of the whole call, clip0 the launch's first
+  int* stats;                                  // device int32 [nclip][T_max][2] or null (zeroed by the host entry)
+  signed char* mv;                             // device int8 [nclip][T_max][mv_stride][2] or null (zeroed by the host entry)
+  uint8_t* ws;
+  int gop, T_max, qp, j;                       // j: the frame position within the GOP this launch codes
+  int search, mv_stride, clip0, pad_;
+  unsigned short q[2][64];
+  CodecMcClipDev clip[kMcMaxClips];
+};
+static_assert(sizeof(CodecMcLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+__host__ __device__ inline long long mc_set_bytes(long long Hpad, long long Wpad, bool s420) {
+  return s420 ? Hpad * Wpad + 2 * (Hpad / 2) * (Wpad / 2) : 3 * Hpad * Wpad;             // a multiple of 64: every plane starts dword-aligned
+}
+
+// the vector of a macroblock's winning key SAD * 1024 + rank: rank 0 is (0, 0), rank 1 + (dy + R)(2R + 1) + (dx + R) the others
+__device__ __forceinline__ void mc_vector(unsigned key, int R, int& dy, int& dx) {
+  const int rank = (int)(key & 1023u), n = 2 * R + 1, k = max(rank - 1, 0), row = k / n;
+  dy = rank ? row - R : 0;
+  dx = rank ? k - row * n - R : 0;
+}
+
+// INTRA: frame position 0 (codec_roundtrip_kernel's phases, then the planes stored).  Otherwise a P-frame: A and B fill plane set 0
+// with the frame's own planes; H stages the luma reference under the tile plus a halo (kHaloX columns, `search` rows, coordinates
+// clamped into the plane) where the source rows were; S searches the tile's macroblocks, candidates spread over the threads and
+// folded by an integer min of SAD * 1024 + rank, which is the serial first-strictly-smaller rule whatever the mapping; P builds the
+// prediction in set 1 (luma from the halo, chroma from the workspace); C turns set 1 into the reconstruction; D stores it.
+template <bool S420, bool INTRA>
+__global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLaunch p) {
+  constexpr int TH = S420 ? 64 : 32;
+  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;
+  constexpr int NS = INTRA ? 1 : 2, S1 = NS - 1;       // S1: the set that ends as the reconstruction
+  constexpr int NMB = (TH / 16) * (kTW / 16);
+  static_assert((TH + 2 * kMaxSearch) * kHP <= TH * kSW * 4, "the staged reference takes the place of the staged source rows");
+  __shared__ unsigned stage[TH * kSW];
+  __shared__ __attribute__((aligned(16))) uint8_t Yp[NS][TH * kTW];
+  __shared__ __attribute__((aligned(8))) uint8_t Cbp[NS][CH * CW];
+  __shared__ __attribute__((aligned(8))) uint8_t Crp[NS][CH * CW];
+  __shared__ uint8_t tone_lds[768];
+  __shared__ int mis_of[TH];
+  __shared__ int qt[2][64];
+  __shared__ float rq[2][64];
+  __shared__ int red[2];
+  __shared__ unsigned best[NMB];
+  __shared__ int mvl[NMB][2];
+
+  const CodecMcClipDev& c = p.clip[blockIdx.z];
+  constexpr int M = S420 ? 16 : 8;
+  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
+  const int nty = (Hpad + TH - 1) / TH;
+  const int t = (int)blockIdx.y * p.gop + p.j;         // gridDim.y * gop <= 65535 + gop: no overflow
+  if ((int)blockIdx.x >= c.ntx * nty || t >= c.count) return;               // uniform over the workgroup
+  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
+  const int y0 = ty * TH, x0 = tx * kTW;
+  const int tid = threadIdx.x;
+  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);
+  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);
+  const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
+  const int nbytes = ncols * 3;
+  const bool toned = p.tone != nullptr;
+  const size_t kt = (size_t)(p.clip0 + blockIdx.z) * p.T_max + t;
+  const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+  // the two plane sets of this (clip, GOP): this launch writes set j & 1 and reads the other
+  const int Hc = S420 ? Hpad >> 1 : Hpad, Wc = S420 ? Wpad >> 1 : Wpad;
+  const long long ysz = (long long)Hpad * Wpad, csz = (long long)Hc * Wc, setsz = ysz + 2 * csz;
+  uint8_t* wsg = p.ws + c.ws_off + (long long)blockIdx.y * 2 * setsz;
+  uint8_t* wcur = wsg + (p.j & 1) * setsz;
+  const uint8_t* wref = wsg + ((p.j & 1) ^ 1) * setsz;
+
+  // ---- A ----
+  if (INTRA && tid < 128) {
+    const int Q = p.q[tid >> 6][tid & 63];
+    qt[tid >> 6][tid & 63] = Q;
+    rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
+  }
+  if (tid < 2) red[tid] = 0;
+  if (tid < NMB) best[tid] = 0xffffffffu;
+  if (toned) {
+    const uint8_t* g = p.tone + kt * 768;
+    for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
+  }
+  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+    const int r = k / kSW, wd = k - r * kSW;
+    const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
+    const int mis = (int)((size_t)row & 3);
+    if (wd == 0) mis_of[r] = mis;
+    if (4 * wd < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * wd);
+  }
+  __syncthreads();
+
+  // ---- B: the frame's own planes into set 0 ----
+  {
+    const uint8_t* sb = (const uint8_t*)stage;
+    auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
+      const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
+      const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
+      int R = px[0], G = px[1], B = px[2];
+      if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
+      rgb_to_ycc(R, G, B, Y, Cb, Cr);
+    };
+    if constexpr (S420) {
+      const int qc = pcol >> 1;
+      for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
+        const int r2 = k / qc, c2 = k - r2 * qc;
+        int sb_ = 0, sr_ = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          int Y, Cb, Cr;
+          ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
+          Yp[0][(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
+          sb_ += Cb; sr_ += Cr;
+        }
+        const int bias = 1 + (c2 & 1);
+        Cbp[0][r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
+        Crp[0][r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
+      }
+    } else {
+      for (int k = tid; k < prow * pcol; k += kCodecThreads) {
+        const int r = k / pcol, col = k - r * pcol;
+        int Y, Cb, Cr;
+        ycc(r, col, Y, Cb, Cr);
+        Yp[0][r * kTW + col] = (uint8_t)Y;
+        Cbp[0][r * CW + col] = (uint8_t)Cb;
+        Crp[0][r * CW + col] = (uint8_t)Cr;
+      }
+    }
+  }
+  __syncthreads();
+
+  if constexpr (!INTRA) {
+    const int R = p.search;
+    const int mbx = (pcol + 15) >> 4, nmb = ((prow + 15) >> 4) * mbx;
+    // ---- H: reference luma rows y0 - R .. y0 + prow + R - 1, columns x0 - kHaloX .. as aligned dwords; outside the plane the edge sample ----
+    {
+      const int d0 = (kHaloX - R) >> 2, nd = ((kHaloX + pcol + R + 3) >> 2) - d0;            // the dwords of a row the search can touch
+      for (int k = tid; k < (prow + 2 * R) * nd; k += kCodecThreads) {
+        const int hr = k / nd, hd = d0 + (k - hr * nd);
+        const uint8_t* row = wref + (long long)min(max(y0 - R + hr, 0), Hpad - 1) * Wpad;
+        const int gx = x0 - kHaloX + 4 * hd;           // a multiple of 4, as Wpad is: a dword is inside the plane or outside it, whole
+        stage[hr * (kHP / 4) + hd] = gx < 0 ? row[0] * 0x01010101u : gx >= Wpad ? row[Wpad - 1] * 0x01010101u : *(const unsigned*)(row + gx);
+      }
+    }
+    __syncthreads();
+
+    // ---- S: one work item = (macroblock, dy, group of the four dx whose reference rows start in one dword): the five dwords of a
+    // reference row are read once for four candidates, whose byte shifts are then constants.  The zero vector's two ranks hold one
+    // SAD, so its candidate is keyed with rank 0 and the other rank, which can never win, is not made ----
+    {
+      const int n = 2 * R + 1, g0 = (kHaloX - R) >> 2, ng = ((kHaloX + R) >> 2) - g0 + 1, per = n * ng;
+      for (int it = tid; it < nmb * per; it += kCodecThreads) {
+        const int mb = it / per, k = it - mb * per, dyi = k / ng, g = g0 + (k - dyi * ng);
+        const int my = mb / mbx, mx = mb - my * mbx;
+        const int mbh = min(16, prow - my * 16);       // 16, or 8 where a 4:4:4 plane ends on half a macroblock
+        const bool wide = pcol - mx * 16 >= 16;
+        const uint8_t* cu = Yp[0] + my * 16 * kTW + mx * 16;
+        const unsigned* h = stage + (my * 16 + dyi) * (kHP / 4) + mx * 4 + g;              // row y + dy of the plane is staged row y + dy + R
+        unsigned s0 = 0, s1 = 0, s2 = 0, s3 = 0;
+        for (int r0 = 0; r0 < mbh; r0 += 8) {
+#pragma unroll
+          for (int rr = 0; rr < 8; ++rr) {
+            const uint4 cw = *(const uint4*)(cu + (r0 + rr) * kTW);
+            const unsigned* hr = h + (r0 + rr) * (kHP / 4);
+            const unsigned a0 = hr[0], a1 = hr[1], a2 = hr[2], a3 = hr[3], a4 = hr[4];   // hr[4]: still inside the staged row (g <= 7)
+            s0 = __builtin_amdgcn_sad_u8(cw.x, a0, s0);
+            s1 = __builtin_amdgcn_sad_u8(cw.x, __builtin_amdgcn_alignbyte(a1, a0, 1), s1);
+            s2 = __builtin_amdgcn_sad_u8(cw.x, __builtin_amdgcn_alignbyte(a1, a0, 2), s2);
+            s3 = __builtin_amdgcn_sad_u8(cw.x, __builtin_amdgcn_alignbyte(a1, a0, 3), s3);
+            s0 = __builtin_amdgcn_sad_u8(cw.y, a1, s0);
+            s1 = __builtin_amdgcn_sad_u8(cw.y, __builtin_amdgcn_alignbyte(a2, a1, 1), s1);
+            s2 = __builtin_amdgcn_sad_u8(cw.y, __builtin_amdgcn_alignbyte(a2, a1, 2), s2);
+            s3 = __builtin_amdgcn_sad_u8(cw.y, __builtin_amdgcn_alignbyte(a2, a1, 3), s3);
+            if (wide) {
+              s0 = __builtin_amdgcn_sad_u8(cw.z, a2, s0);
+              s1 = __builtin_amdgcn_sad_u8(cw.z, __builtin_amdgcn_alignbyte(a3, a2, 1), s1);
+              s2 = __builtin_amdgcn_sad_u8(cw.z, __builtin_amdgcn_alignbyte(a3, a2, 2), s2);
+              s3 = __builtin_amdgcn_sad_u8(cw.z, __builtin_amdgcn_alignbyte(a3, a2, 3), s3);
+              s0 = __builtin_amdgcn_sad_u8(cw.w, a3, s0);
+              s1 = __builtin_amdgcn_sad_u8(cw.w, __builtin_amdgcn_alignbyte(a4, a3, 1), s1);
+              s2 = __builtin_amdgcn_sad_u8(cw.w, __builtin_amdgcn_alignbyte(a4, a3, 2), s2);
+              s3 = __builtin_amdgcn_sad_u8(cw.w, __builtin_amdgcn_alignbyte(a4, a3, 3), s3);
+            }
+          }
+        }
+        const unsigned sads[4] = {s0, s1, s2, s3};
+        unsigned key = 0xffffffffu;
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+          const int dx = 4 * g + s - kHaloX;           // the group's first and last may hold dx outside the range: not candidates
+          const unsigned rank = dyi == R && dx == 0 ? 0u : (unsigned)(1 + dyi * n + dx + R);
+          if (dx >= -R && dx <= R) key = min(key, sads[s] * 1024u + rank);
+        }
+        atomicMin(&best[mb], key);
+      }
+    }
+    __syncthreads();
+    if (tid < nmb) {
+      int dy, dx;
+      mc_vector(best[tid], R, dy, dx);
+      mvl[tid][0] = dy; mvl[tid][1] = dx;
+      if (p.mv) {
+        const int my = tid / mbx, mx = tid - my * mbx;
+        signed char* o = p.mv + (kt * p.mv_stride + (size_t)((y0 >> 4) + my) * ((Wpad + 15) >> 4) + (x0 >> 4) + mx) * 2;
+        o[0] = (signed char)dy; o[1] = (signed char)dx;
+      }
+    }
+    __syncthreads();
+
+    // ---- P: the prediction into set 1: luma from the staged reference, chroma from the workspace with clamped coordinates ----
+    {
+      const int qd = pcol >> 2;
+      for (int k = tid; k < prow * qd; k += kCodecThreads) {
+        const int r = k / qd, col = (k - r * qd) * 4;
+        const int mb = (r >> 4) * mbx + (col >> 4);
+        const int off = (r + mvl[mb][0] + R) * kHP + col + mvl[mb][1] + kHaloX;
+        const unsigned* h = stage + (off >> 2);
+        *(unsigned*)(Yp[1] + r * kTW + col) = __builtin_amdgcn_alignbyte(h[1], h[0], (unsigned)off & 3u);
+      }
+      const uint8_t* rcb = wref + ysz;
+      const uint8_t* rcr = rcb + csz;
+      const int cy0 = S420 ? y0 >> 1 : y0, cx0 = S420 ? x0 >> 1 : x0;
+      for (int k = tid; k < cprow * cpcol; k += kCodecThreads) {
+        const int r = k / cpcol, col = k - r * cpcol;
+        const int mb = S420 ? (r >> 3) * mbx + (col >> 3) : (r >> 4) * mbx + (col >> 4);
+        const int dy = mvl[mb][0], dx = mvl[mb][1];
+        if constexpr (S420) {
+          const int ya = min(max(cy0 + r + (dy >> 1), 0), Hc - 1), yb = min(max(cy0 + r + (dy >> 1) + 1, 0), Hc - 1);
+          const int xa = min(max(cx0 + col + (dx >> 1), 0), Wc - 1), xb = min(max(cx0 + col + (dx >> 1) + 1, 0), Wc - 1);
+          const bool hy = dy & 1, hx = dx & 1;
+          auto half = [&](const uint8_t* pl) -> int {
+            const int a = pl[(long long)ya * Wc + xa];
+            if (hy && hx) return (a + pl[(long long)ya * Wc + xb] + pl[(long long)yb * Wc + xa] + pl[(long long)yb * Wc + xb] + 2) >> 2;
+            if (hx) return (a + pl[(long long)ya * Wc + xb] + 1) >> 1;
+            if (hy) return (a + pl[(long long)yb * Wc + xa] + 1) >> 1;
+            return a;
+          };
+          Cbp[1][r * CW + col] = (uint8_t)half(rcb);
+          Crp[1][r * CW + col] = (uint8_t)half(rcr);
+        } else {
+          const long long o = (long long)min(max(cy0 + r + dy, 0), Hc - 1) * Wc + min(max(cx0 + col + dx, 0), Wc - 1);
+          Cbp[1][r * CW + col] = rcb[o];
+          Crp[1][r * CW + col] = rcr[o];
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- C: one block per thread ----
+  {
+    constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
+    const int Qp = p.qp;
+    const float rqp = 1.0f / (float)(Qp << 3);
+    int nz = 0, mag = 0;
+    for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
+      if (b < NBY) {
+        const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
+        const int o = by * 8 * kTW + bx * 8;
+        if (by * 8 < prow && bx * 8 < pcol) {
+          if constexpr (INTRA) codec_block(Yp[0] + o, kTW, qt[0], rq[0], nz, mag);
+          else codec_block_inter(Yp[0] + o, Yp[S1] + o, kTW, Qp, rqp, nz, mag);
+        }
+      } else {
+        const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
+        const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
+        const int o = by * 8 * CW + bx * 8;
+        if (by * 8 < cprow && bx * 8 < cpcol) {
+          if constexpr (INTRA) codec_block((pl ? Crp[0] : Cbp[0]) + o, CW, qt[1], rq[1], nz, mag);
+          else codec_block_inter((pl ? Crp[0] : Cbp[0]) + o, (pl ? Crp[S1] : Cbp[S1]) + o, CW, Qp, rqp, nz, mag);
+        }
+      }
+    }
+    if (p.stats && (nz | mag)) {
+      atomicAdd(&red[0], nz);
+      atomicAdd(&red[1], mag);
+    }
+  }
+  __syncthreads();
+  if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
+
+  // ---- D: the reconstruction to the workspace (whole dwords of the padded planes), and as RGB bytes to the destination ----
+  {
+    const int qd = pcol >> 2, cqd = cpcol >> 2;
+    for (int k = tid; k < prow * qd; k += kCodecThreads) {
+      const int r = k / qd, col = (k - r * qd) * 4;
+      *(unsigned*)(wcur + (long long)(y0 + r) * Wpad + x0 + col) = *(const unsigned*)(Yp[S1] + r * kTW + col);
+    }
+    const int cy0 = S420 ? y0 >> 1 : y0, cx0 = S420 ? x0 >> 1 : x0;
+    for (int k = tid; k < cprow * cqd; k += kCodecThreads) {
+      const int r = k / cqd, col = (k - r * cqd) * 4;
+      const long long o = ysz + (long long)(cy0 + r) * Wc + cx0 + col;
+      *(unsigned*)(wcur + o) = *(const unsigned*)(Cbp[S1] + r * CW + col);
+      *(unsigned*)(wcur + csz + o) = *(const unsigned*)(Crp[S1] + r * CW + col);
+    }
+  }
+  uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
+  uint8_t* ob = (uint8_t*)stage;
+  for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
+    const int r = k / ncols, col = k - r * ncols;
+    const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
+    const int Y = Yp[S1][r * kTW + col];
+    const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
+    const int cb = (int)Cbp[S1][ci] - 128, cr = (int)Crp[S1][ci] - 128;
+    uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
+    o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
+    o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
+    o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
+  }
+  __syncthreads();
+  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+    const int r = k / kSW, wd = k - r * kSW;
+    uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
+    const int dm = (int)((size_t)row & 3);
+    const int lo = dm, hi = dm + nbytes;
+    if (4 * wd >= hi || 4 * wd + 4 <= lo) continue;
+    if (4 * wd >= lo && 4 * wd + 4 <= hi) {
+      *(unsigned*)(row - dm + 4 * wd) = stage[k];
+    } else {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * wd + b >= lo && 4 * wd + b < hi) (row - dm)[4 * wd + b] = ob[k * 4 + b];
+    }
+  }
+}
+
 }  // namespace
 
 // the two quantisation tables at `quality` (1..100): ITU T.81 Annex K under the IJG scaling rule, row-major
@@ -607,5 +955,77 @@ int flk_codec_roundtrip_gop_launch(const flk_codec_args* a, int gop, const int32
   if (s420) FLK_LAUNCH_KERNEL(codec_gop_kernel<true>, grid, dim3(kCodecThreads), 0, stream, p);
   else FLK_LAUNCH_KERNEL(codec_gop_kernel<false>, grid, dim3(kCodecThreads), 0, stream, p);
   FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+
+// the workspace of flk_codec_roundtrip_mc_u8: two plane sets per (clip, GOP of its span); 0 where the arguments are not a launch's
+long long flk_codec_mc_scratch_host(const flk_codec_args* a, int gop, const int32_t* count) {
+  if (!a || !a->clips || !count || a->nclip < 1 || gop < 1 || gop > 65535) return 0;
+  if (a->subsampling != FLK_CODEC_420 && a->subsampling != FLK_CODEC_444) return 0;
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  const int M = s420 ? 16 : 8;
+  long long total = 0;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& s = a->clips[i];
+    if (s.Hs < 1 || s.Ws < 1 || count[i] < 1 || count[i] > 65535) return 0;
+    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
+    if (Hpad > (1LL << 34) / Wpad) return 0;           // a plane set of more than 2^36 bytes: no such workspace, and no overflow below
+    total += (long long)((count[i] + gop - 1) / gop) * 2 * mc_set_bytes(Hpad, Wpad, s420);
+    if (total > (1LL << 60)) return 0;
+  }
+  return total;
+}
+
+// arguments already validated (api.cpp: flk_codec_roundtrip_mc_u8); everything here up to the first launch is host arithmetic.  One
+// launch per frame position of the GOP and kMcMaxClips clips; positions follow each other on the stream, which is all the ordering
+// the reference planes need.
+int flk_codec_roundtrip_mc_launch(const flk_codec_args* a, int gop, int search, const int32_t* first, const int32_t* count, int T_max,
+                                  const uint8_t* tone, int32_t* stats, int8_t* mv, int mv_stride, void* scratch, hipStream_t stream) {
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
+  CodecMcLaunch p;
+  p.tone = tone; p.stats = stats; p.mv = (signed char*)mv; p.ws = (uint8_t*)scratch;
+  p.gop = gop; p.T_max = T_max; p.qp = flk_codec_inter_step_host(a->quality); p.search = search; p.mv_stride = mv_stride; p.pad_ = 0;
+  int32_t ql[64], qc[64];
+  flk_codec_tables_host(a->quality, ql, qc);
+  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
+  if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_max * 2 * sizeof(int32_t), stream));
+  if (mv) FLK_CHECK_HIP(hipMemsetAsync(mv, 0, (size_t)a->nclip * T_max * mv_stride * 2, stream));
+  long long ws_off = 0;
+  for (int c0 = 0; c0 < a->nclip; c0 += kMcMaxClips) {
+    const int n = a->nclip - c0 < kMcMaxClips ? a->nclip - c0 : kMcMaxClips;
+    long long max_tiles = 1;
+    int max_gops = 1, max_count = 1;
+    for (int i = 0; i < n; ++i) {
+      const flk_codec_clip& s = a->clips[c0 + i];
+      CodecMcClipDev& d = p.clip[i];
+      d.src = s.src + (long long)first[c0 + i] * s.pitch_t; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
+      d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
+      d.count = count[c0 + i]; d.Hs = s.Hs; d.Ws = s.Ws;
+      const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
+      d.ntx = (int)((Wpad + kTW - 1) / kTW);
+      const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
+      if (tiles > max_tiles) max_tiles = tiles;
+      const int gops = (d.count + gop - 1) / gop;
+      if (gops > max_gops) max_gops = gops;
+      if (d.count > max_count) max_count = d.count;
+      d.ws_off = ws_off;
+      ws_off += (long long)gops * 2 * mc_set_bytes(Hpad, Wpad, s420);
+    }
+    FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_mc_u8: a frame of more than 2^31 tiles");
+    p.clip0 = c0;
+    const dim3 grid((unsigned)max_tiles, (unsigned)max_gops, (unsigned)n);
+    for (int j = 0; j < gop && j < max_count; ++j) {
+      p.j = j;
+      if (j == 0) {
+        if (s420) FLK_LAUNCH_KERNEL((codec_mc_kernel<true, true>), grid, dim3(kCodecThreads), 0, stream, p);
+        else FLK_LAUNCH_KERNEL((codec_mc_kernel<false, true>), grid, dim3(kCodecThreads), 0, stream, p);
+      } else {
+        if (s420) FLK_LAUNCH_KERNEL((codec_mc_kernel<true, false>), grid, dim3(kCodecThreads), 0, stream, p);
+        else FLK_LAUNCH_KERNEL((codec_mc_kernel<false, false>), grid, dim3(kCodecThreads), 0, stream, p);
+      }
+      FLK_CHECK_HIP(hipGetLastError());
+    }
+  }
   return FLK_OK;
 }

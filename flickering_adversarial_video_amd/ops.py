@@ -1160,7 +1160,10 @@ def codec_inter_step(quality):
     return int(qp.value)
 
 
-def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=False, spans=None):
+_codec_mc_scratch = {}      # device -> the reused uint8 workspace of flk_codec_roundtrip_mc_u8 (grown, never shrunk)
+
+
+def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=False, spans=None, motion=False):
     """The delivered videos after lossy intra-frame compression (flk_codec_roundtrip_u8; ``videoresnet_spec.codec_roundtrip_host`` is
     its definition, bit for bit): one kernel launch per ``FLK_PREP_MAX_CLIPS`` videos.
 
@@ -1178,7 +1181,12 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
     predecessors) takes no ``frame_idx`` but ``spans``: host integers ``[len(videos), 2]`` of (first, count), first a multiple of
     ``gop``; the default is the whole video, ``(0, N_k)``.  Output ``k`` is ``[count_k,H_k,W_k,3]``, video frames first .. first +
     count - 1 -- bitwise those frames of the whole video's result; ``stats`` are ``[count_k,2]``; ``tone`` is
-    ``[len(videos), max count (or more), 256, 3]``, row t the table of video frame first_k + t (rows past a video's count are not read)."""
+    ``[len(videos), max count (or more), 256, 3]``, row t the table of video frame first_k + t (rows past a video's count are not read).
+    A codec with ``search`` > 0 (flk_codec_roundtrip_mc_u8: motion-compensated P-frames) takes the same arguments
+    and is launched once per frame position of the GOP, its reconstructed planes travelling through a workspace kept per device and
+    reused from call to call.  ``motion`` (a codec with ``gop`` > 1 only): also return, last, the list of the vectors, int8
+    ``[count_k, MBy_k, MBx_k, 2]`` as (dy, dx) per 16 x 16 macroblock of the padded luma plane -- zeros on intra frames and at ``search`` 0,
+    which then goes through the same entry."""
     from .videoresnet_spec import Codec
     what = "codec_roundtrip"
     if not isinstance(codec, Codec):
@@ -1193,6 +1201,8 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
     n, dev = len(vids), vids[0].device
     table = None
     gop = codec.gop
+    if motion and gop == 1:
+        raise ValueError(f"{what}: motion vectors go with a codec of gop > 1 (an intra-frame codec has no P-frames)")
     if gop > 1 and frame_idx is not None:
         raise ValueError(f"{what}: a codec with gop {gop} predicts every frame from the one before it: give spans=(first, count) per video, not "
                          f"frame_idx")
@@ -1255,7 +1265,7 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
         lo_d, hi_d = o.data_ptr(), o.data_ptr() + (shape[0] - 1) * max(o.stride(0), 0) + (shape[1] - 1) * o.stride(1) + 3 * shape[2]
         if lo_s < hi_d and lo_d < hi_s:
             raise ValueError(f"{what}: out[{k}] overlaps its source (an MCU reads pixels that other workgroups write)")
-    st_out = [None] * n
+    st_out, mv_out = [None] * n, [None] * n
     sub = _lib.FLK_CODEC_420 if codec.subsampling == "420" else _lib.FLK_CODEC_444
 
     def clip_array(part):
@@ -1276,12 +1286,30 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
             a, arr = clip_array(part)
             firsts, counts = ((C.c_int32 * len(part))(*[int(sp[k, j]) for k in part]) for j in (0, 1))
             st = torch.empty((len(part), T_max, 2), dtype=torch.int32, device=dev) if stats else None
-            check(load().flk_codec_roundtrip_gop_u8(C.byref(a), gop, firsts, counts, T_max, None if tone is None else ptr(tone[first:]), ptr(st),
-                                                    stream_ptr()))
+            tn = None if tone is None else ptr(tone[first:])
+            if codec.search > 0 or motion:
+                m = 8 if codec.subsampling == "444" else 16
+                mbs = [(-(-int(vids[k].shape[1]) // m) * m + 15) // 16 for k in part], [(-(-int(vids[k].shape[2]) // m) * m + 15) // 16 for k in part]
+                stride = max(y * x for y, x in zip(*mbs))
+                mv = torch.empty((len(part), T_max, stride, 2), dtype=torch.int8, device=dev) if motion else None
+                need = int(load().flk_codec_mc_scratch_bytes(C.byref(a), gop, counts))
+                if need <= 0:
+                    raise ValueError(f"{what}: the workspace of these videos cannot be sized")
+                ws = _codec_mc_scratch.get(dev)
+                if ws is None or ws.numel() < need:        # the stream orders a later call's launches after this one's: reuse is safe
+                    ws = _codec_mc_scratch[dev] = torch.empty(need, dtype=torch.uint8, device=dev)
+                check(load().flk_codec_roundtrip_mc_u8(C.byref(a), gop, codec.search, firsts, counts, T_max, tn, ptr(st), ptr(mv), stride, ptr(ws),
+                                                       ws.numel(), stream_ptr()))
+                if motion:
+                    for j, k in enumerate(part):
+                        mv_out[k] = mv[j, :lens[k], :mbs[0][j] * mbs[1][j]].reshape(lens[k], mbs[0][j], mbs[1][j], 2)
+            else:
+                check(load().flk_codec_roundtrip_gop_u8(C.byref(a), gop, firsts, counts, T_max, tn, ptr(st), stream_ptr()))
             if stats:
                 for j, k in enumerate(part):
                     st_out[k] = st[j, :lens[k]]
-        return (outs, st_out) if stats else outs
+        res = (outs,) + ((st_out,) if stats else ()) + ((mv_out,) if motion else ())
+        return res if len(res) > 1 else outs
     tab_dev = None if table is None else torch.from_numpy(table.astype(np.int32)).to(dev)
     groups = {}
     for k in range(n):                          # one launch has one output length: videos of equal length share launches

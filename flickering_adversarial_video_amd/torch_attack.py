@@ -569,7 +569,9 @@ class FlickerVideoResNet:
         # for bit.  The backward is the train_delivered one on the source videos: straight through the codec, whose Jacobian is taken as
         # the identity.  A codec with ``gop`` > 1 compresses per clip the span from the intra frame at
         # or before the clip's first frame (ops.codec_roundtrip(spans=, tone=)); the surrogate rec ~ cur holds for a P-frame as for an
-        # intra frame, so the backward is the same.  None (default): every launch as before
+        # intra frame, so the backward is the same.  A codec with ``search`` > 0 goes through the same calls: its GOPs
+        # are still closed in time, so the spans stand, and the surrogate is unchanged (motion moves the prediction, not what the
+        # reconstruction approximates).  None (default): every launch as before
         if self._check_codec(codec) is not None and not self.train_delivered:
             raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
                              "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")

@@ -1183,29 +1183,45 @@ def check_codec_gop(gop, what="codec"):
     return int(gop)
 
 
-class Codec:
-    """A lossy codec the delivered video goes through: ``quality`` 1..100 (the IJG scale), chroma ``subsampling`` "444" or "420" and
-    ``gop``, the distance between intra frames (1: intra-frame only; N > 1: closed GOPs of one intra frame and N - 1 zero-motion
-    P-frames).  A checked value object; ``ops.codec_roundtrip`` and the engines take it."""
-    __slots__ = ("quality", "subsampling", "gop")
+def check_codec_search(search, gop=None, what="codec"):
+    """the motion search range of a codec, checked: an integer 0..15 (0: zero motion); ``gop`` given: a range above 0 needs P-frames"""
+    if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 0 <= int(search) <= 15:
+        raise ValueError(f"{what}: search must be an integer in 0..15, got {search!r}")
+    if gop is not None and int(search) > 0 and int(gop) == 1:
+        raise ValueError(f"{what}: search {int(search)} needs gop > 1 (an intra-frame codec has no P-frames to search for)")
+    return int(search)
 
-    def __init__(self, quality=75, subsampling="420", gop=1):
+
+class Codec:
+    """A lossy codec the delivered video goes through: ``quality`` 1..100 (the IJG scale), chroma ``subsampling`` "444" or "420",
+    ``gop``, the distance between intra frames (1: intra-frame only; N > 1: closed GOPs of one intra frame and N - 1 P-frames,
+    DESIGN.md 10.9) and ``search``, the P-frames' motion search range in pixels (0: zero motion; R in 1..15: every 16 x 16 macroblock
+    is predicted from the best of the (2R + 1)^2 full-pel displacements of the previous reconstruction; needs
+    ``gop`` > 1).  A checked value object; ``ops.codec_roundtrip`` and the engines take it."""
+    __slots__ = ("quality", "subsampling", "gop", "search")
+
+    def __init__(self, quality=75, subsampling="420", gop=1, search=0):
         q, s = check_codec(quality, subsampling, "Codec")
         object.__setattr__(self, "quality", q)
         object.__setattr__(self, "subsampling", s)
         object.__setattr__(self, "gop", check_codec_gop(gop, "Codec"))
+        object.__setattr__(self, "search", check_codec_search(search, self.gop, "Codec"))
 
     def __setattr__(self, name, value):
         raise AttributeError("Codec is immutable")
 
     def __repr__(self):
-        return f"Codec(quality={self.quality}, subsampling={self.subsampling!r}" + (f", gop={self.gop})" if self.gop > 1 else ")")
+        return (f"Codec(quality={self.quality}, subsampling={self.subsampling!r}" + (f", gop={self.gop}" if self.gop > 1 else "")
+                + (f", search={self.search}" if self.search else "") + ")")
+
+    def _key(self):
+        return (self.quality, self.subsampling, self.gop, self.search)
 
     def __eq__(self, other):
-        return isinstance(other, Codec) and (self.quality, self.subsampling, self.gop) == (other.quality, other.subsampling, other.gop)
+        return isinstance(other, Codec) and self._key() == other._key()
 
     def __hash__(self):
-        return hash((self.quality, self.subsampling, self.gop))
+        return hash(self._key())
 
 
 def codec_tables(quality):
@@ -1298,7 +1314,64 @@ def _codec_plane_inter(p, ref, qp, dt):
     return o.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp), lev
 
 
-def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=False, gop=1, first_frame=0, _dtype=np.int32):
+def codec_motion_search(cur_Y, ref_Y, search):
+    """The P-frames' block search alone: per 16 x 16 macroblock of the padded luma plane ``cur_Y`` (cut from the
+    top-left corner; the last column or row of macroblocks may be narrower, and is searched over its own pixels) the full-pel vector
+    (dy, dx) into ``ref_Y``, the previous reconstruction of the same shape -- int8 ``[MBy, MBx, 2]``.
+      SAD(dy, dx) = sum |cur_Y[y, x] - ref_Y[clamp(y + dy, 0, Hp - 1), clamp(x + dx, 0, Wp - 1)]| over the macroblock's pixels
+    Candidates are visited in one order: (0, 0) first, then dy = -R..R (outer), dx = -R..R (inner); a candidate replaces the best only
+    if its SAD is strictly smaller -- the minimum of the integer key SAD * 1024 + rank, rank 0 the zero vector and
+    1 + (dy + R)(2R + 1) + (dx + R) the others (SAD <= 65280, rank <= 961: the key fits 27 bits)."""
+    R = check_codec_search(search, what="codec_motion_search")
+    cur, ref = np.asarray(cur_Y), np.asarray(ref_Y)
+    if cur.ndim != 2 or cur.shape != ref.shape or min(cur.shape) < 1 or cur.dtype.kind not in "iu" or ref.dtype.kind not in "iu":
+        raise ValueError(f"codec_motion_search: cur_Y and ref_Y must be integer planes of one shape [Hp, Wp], got {cur.shape} {cur.dtype} and "
+                         f"{ref.shape} {ref.dtype}")
+    if min(cur.min(), ref.min()) < 0 or max(cur.max(), ref.max()) > 255:
+        raise ValueError("codec_motion_search: the planes hold bytes, 0..255")
+    Hp, Wp = cur.shape
+    cur, pad = cur.astype(np.int32), np.pad(ref.astype(np.int32), R, mode="edge")            # the edge sample beyond the plane
+    ys, xs, n = np.arange(0, Hp, 16), np.arange(0, Wp, 16), 2 * R + 1
+
+    def key(dy, dx, rank):
+        sad = np.abs(cur - pad[R + dy:R + dy + Hp, R + dx:R + dx + Wp])
+        return np.add.reduceat(np.add.reduceat(sad, ys, 0), xs, 1) * 1024 + rank
+
+    best = key(0, 0, 0)
+    for dy in range(-R, R + 1):
+        for dx in range(-R, R + 1):
+            best = np.minimum(best, key(dy, dx, 1 + (dy + R) * n + (dx + R)))
+    rank = best & 1023
+    k = np.maximum(rank - 1, 0)
+    return np.stack([np.where(rank == 0, 0, k // n - R), np.where(rank == 0, 0, k % n - R)], -1).astype(np.int8)
+
+
+def _codec_mc_predict(ref, mv, s420):
+    """the motion-compensated prediction planes (Y, Cb, Cr) of a P-frame from the reference planes ``ref`` and the macroblock vectors
+    ``mv`` [MBy, MBx, 2]: full-pel on luma (and on 4:4:4 chroma), half the vector at half-pel precision on 4:2:0 chroma; every sample
+    read is clamped into its plane"""
+    Y, Cb, Cr = ref
+    Hp, Wp = Y.shape
+    dy, dx = (mv[..., j].astype(np.int64).repeat(16, 0).repeat(16, 1)[:Hp, :Wp] for j in (0, 1))
+    yy, xx = np.mgrid[0:Hp, 0:Wp]
+    fy, fx = np.clip(yy + dy, 0, Hp - 1), np.clip(xx + dx, 0, Wp - 1)
+    if not s420:
+        return Y[fy, fx], Cb[fy, fx], Cr[fy, fx]
+    Hc, Wc = Hp // 2, Wp // 2
+    vy, vx = (mv[..., j].astype(np.int64).repeat(8, 0).repeat(8, 1) for j in (0, 1))         # a macroblock's 8 x 8 chroma block
+    iy, hy, ix, hx = vy >> 1, (vy & 1) == 1, vx >> 1, (vx & 1) == 1                            # arithmetic shift: -3 -> -2 + 1/2
+    yy, xx = np.mgrid[0:Hc, 0:Wc]
+    y0, y1, x0, x1 = (np.clip(v, 0, m - 1) for v, m in ((yy + iy, Hc), (yy + iy + 1, Hc), (xx + ix, Wc), (xx + ix + 1, Wc)))
+
+    def half(p):
+        a, b, c, d = p[y0, x0], p[y0, x1], p[y1, x0], p[y1, x1]
+        return np.where(hy & hx, (a + b + c + d + 2) >> 2, np.where(hx, (a + b + 1) >> 1, np.where(hy, (a + c + 1) >> 1, a)))
+
+    return Y[fy, fx], half(Cb), half(Cr)
+
+
+def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=False, gop=1, first_frame=0, search=0, motion=False,
+                         _dtype=np.int32):
     """The codec round trip on the host, in integers only: uint8 ``[N,H,W,3]`` (or one frame ``[H,W,3]``) -> uint8 of the same shape;
     with ``stats`` also int32 ``[N,2]``: per frame the number of non-zero quantised coefficients and the sum of their magnitudes.
     ``tone``: uint8 ``[N,256,3]`` (or ``[256,3]``), the byte -> byte table each frame goes through first.
@@ -1317,9 +1390,17 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
     ``ref`` at zero motion -- per plane and 8 x 8 block, in place of the DCT stage:
       P        r = cur - ref (no - 128); the same two forward passes; level = sign * ((|f| + 2 Qp) // (8 Qp)), Qp = codec_inter_step(quality)
                for every position and plane; rec = clamp(ref + idct(level * Qp), 0, 255) (the same two inverse passes, no + 128); ref <- rec
-    The stats of a P-frame count its levels."""
+    The stats of a P-frame count its levels.
+    ``search`` = R > 0 (needs ``gop`` > 1): a P-frame is predicted with motion.  Its padded luma plane is cut into
+    16 x 16 macroblocks, each takes the vector ``codec_motion_search`` finds in ref's luma, and in the step above ``ref`` is replaced by
+      pred     luma (and chroma at "444"): ref[clamp(y + dy), clamp(x + dx)]; chroma at "420": the macroblock's 8 x 8 block moved by
+               half the vector, iy = dy >> 1, hy = dy & 1 (ix, hx likewise): a, (a + b + 1) >> 1 with one half flag (b the next sample
+               along that axis) or (a + b + c + d + 2) >> 2 with both; every sample read is clamped into its plane
+    so r = cur - pred, rec = clamp(pred + idct(level * Qp), 0, 255), ref <- rec.  ``motion``: also return the vectors, int8
+    ``[N, MBy, MBx, 2]`` as (dy, dx), zeros on intra frames (and everywhere at ``search`` 0), after the stats if both are asked for."""
     quality, subsampling = check_codec(quality, subsampling, "codec_roundtrip_host")
     gop = check_codec_gop(gop, "codec_roundtrip_host")
+    search = check_codec_search(search, gop, "codec_roundtrip_host")
     if isinstance(first_frame, bool) or not isinstance(first_frame, (int, np.integer)) or first_frame < 0 or first_frame % gop:
         raise ValueError(f"codec_roundtrip_host: first_frame must be a non-negative multiple of gop {gop} (a span starts on an intra frame), "
                          f"got {first_frame!r}")
@@ -1349,8 +1430,23 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
         bias = (1 + (np.arange(Wp // 2) & 1)).astype(dt)
         Cb, Cr = ((p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] + bias) >> 2 for p in (Cb, Cr))
     ql, qc = codec_tables(quality)
+    mv = np.zeros((N, (Hp + 15) // 16, (Wp + 15) // 16, 2), np.int8)
     if gop == 1:
         (Y, ly), (Cb, lb), (Cr, lr) = _codec_plane(Y, ql, dt), _codec_plane(Cb, qc, dt), _codec_plane(Cr, qc, dt)
+    elif search > 0:
+        qp = codec_inter_step(quality)
+        rec, coded = None, []
+        for t in range(N):
+            cur = (Y[t:t + 1], Cb[t:t + 1], Cr[t:t + 1])
+            if (first_frame + t) % gop == 0:
+                one = [_codec_plane(p, qt, dt) for p, qt in zip(cur, (ql, qc, qc))]
+            else:
+                mv[t] = codec_motion_search(cur[0][0], rec[0], search)
+                pred = _codec_mc_predict(rec, mv[t], subsampling == "420")
+                one = [_codec_plane_inter(p, q[None], qp, dt) for p, q in zip(cur, pred)]
+            rec = [r[0] for r, _ in one]
+            coded.append(one)
+        (Y, ly), (Cb, lb), (Cr, lr) = ((np.concatenate([c[j][0] for c in coded]), np.concatenate([c[j][1] for c in coded])) for j in range(3))
     else:
         qp = codec_inter_step(quality)
         coded = []
@@ -1369,10 +1465,13 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
     out = np.clip(out, 0, 255).astype(np.uint8)[:, :H, :W]
     if single:
         out = out[0]
-    if not stats:
-        return out
-    st = np.stack([sum((l != 0).reshape(N, -1).sum(1) for l in (ly, lb, lr)), sum(np.abs(l).reshape(N, -1).sum(1) for l in (ly, lb, lr))], -1)
-    return out, st.astype(np.int32)
+    res = (out,)
+    if stats:
+        st = np.stack([sum((l != 0).reshape(N, -1).sum(1) for l in (ly, lb, lr)), sum(np.abs(l).reshape(N, -1).sum(1) for l in (ly, lb, lr))], -1)
+        res += (st.astype(np.int32),)
+    if motion:
+        res += (mv[0] if single else mv,)
+    return res if len(res) > 1 else out
 
 
 def add_codec_arguments(ap):
@@ -1385,6 +1484,9 @@ def add_codec_arguments(ap):
     ap.add_argument("--codec-gop", type=int, default=None, metavar="N", help="the codec's distance between intra frames (default 1: every frame "
                     "is an intra frame); N > 1 codes closed GOPs of one intra frame and N - 1 zero-motion P-frames, whose quantised temporal "
                     "residual decides whether a flicker arrives; needs --codec-quality")
+    ap.add_argument("--codec-search", type=int, default=None, metavar="R", help="the P-frames' motion search range in pixels, 0..15 (default 0: "
+                    "zero motion; 7 is a usual choice): every 16x16 macroblock is predicted from the best full-pel displacement of the previous "
+                    "reconstruction, so camera and object motion is not paid for as residual; needs --codec-gop above 1")
 
 
 def codec_from_arguments(ap, a, used):
@@ -1395,12 +1497,15 @@ def codec_from_arguments(ap, a, used):
             ap.error("--codec-subsampling needs --codec-quality")
         if a.codec_gop is not None:
             ap.error("--codec-gop needs --codec-quality")
+        if a.codec_search is not None:
+            ap.error("--codec-search needs --codec-quality")
         return None
     if not used:
         ap.error("--codec-quality / --codec-subsampling act on whole delivered videos: give --eval-quantised video, --train-delivered or "
                  "--save-adversarial-u8 with whole videos")
     try:
-        return Codec(a.codec_quality, a.codec_subsampling or "420", 1 if a.codec_gop is None else a.codec_gop)
+        return Codec(a.codec_quality, a.codec_subsampling or "420", 1 if a.codec_gop is None else a.codec_gop,
+                     0 if a.codec_search is None else a.codec_search)
     except ValueError as e:
         ap.error(str(e))
 

@@ -668,6 +668,29 @@ int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, const int32_t* 
                                const uint8_t* tone /* DEVICE [nclip][T_max][256][3] or NULL */,
                                int32_t* stats /* DEVICE [nclip][T_max][2] or NULL */, void* stream);
 
+/* Motion-compensated P-frames (csrc/codec.hip; videoresnet_spec.codec_roundtrip_host(gop=, first_frame=, search=) is
+ * the definition, bit for bit).  As flk_codec_roundtrip_gop_u8, but a P-frame's padded luma plane is cut into 16x16 macroblocks from
+ * the top-left corner (at 4:4:4 the last column or row may be 8 wide or high) and each is predicted from the previous reconstruction
+ * displaced by the full-pel vector (dy, dx), |dy|, |dx| <= search, of least SAD = sum |cur_Y[y][x] - ref_Y[clamp(y + dy)][clamp(x + dx)]|;
+ * among equal SADs the first in the order (0, 0), then dy = -search..search (outer), dx = -search..search (inner) -- the minimum of
+ * SAD * 1024 + rank.  Chroma takes the same vector at 4:4:4 and half of it at half-pel precision at 4:2:0 (iy = dy >> 1, hy = dy & 1;
+ * a, (a + b + 1) >> 1 or (a + b + c + d + 2) >> 2), every read clamped into the plane.  The residual against that prediction is coded
+ * as at zero motion.  search == 0 is allowed: zero vectors, the bytes of flk_codec_roundtrip_gop_u8 through this path.
+ * One launch per frame position within the GOP (min(gop, the longest count) of them, times ceil(nclip / 48)); the reconstructed
+ * planes travel through `scratch`, two plane sets per (clip, GOP), and the launches are ordered by the stream alone.
+ * flk_codec_mc_scratch_bytes: the bytes of scratch the call with the same a / gop / count needs; 0 for arguments it would refuse.
+ * mv: DEVICE int8 [nclip][T_max][mv_stride][2] or null, zeroed here: (dy, dx) of clip k's macroblock (my, mx) of output frame t at
+ *   [k][t][my * MBx_k + mx], MBx_k = ceil(padded width / 16); intra frames and rows at or past count[k] stay zero.
+ * FLK_EINVAL (before any GPU call): what flk_codec_roundtrip_gop_u8 refuses, search outside 0..15, a null scratch, one not 16-byte
+ *   aligned or smaller than flk_codec_mc_scratch_bytes, mv_stride below a clip's macroblock count (with mv). */
+int64_t flk_codec_mc_scratch_bytes(const flk_codec_args* a, int gop, const int32_t* count /* HOST [nclip] */);
+int flk_codec_roundtrip_mc_u8(const flk_codec_args* a, int gop, int search, const int32_t* first /* HOST [nclip] */,
+                              const int32_t* count /* HOST [nclip] */, int T_max,
+                              const uint8_t* tone /* DEVICE [nclip][T_max][256][3] or NULL */,
+                              int32_t* stats /* DEVICE [nclip][T_max][2] or NULL */,
+                              int8_t* mv /* DEVICE [nclip][T_max][mv_stride][2] or NULL */, int mv_stride, void* scratch,
+                              int64_t scratch_bytes, void* stream);
+
 /* Tail of the data-parallel payload (flickering_adversarial_video_amd/parallel.py; replaces the per-iteration
  * reduce_sum / reduce_mean fetches of i3d_adversarial_main_single_video_npy.py:213-217): from the per-clip
  * outputs of flk_softmax_adv_loss ([B,4] = loss, p_label, p_max_other, argmax)

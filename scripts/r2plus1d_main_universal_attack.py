@@ -168,7 +168,7 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  clips_per_video=a.clips_per_video, video_reduce=a.video_reduce, quantise_train=a.quantise_train,
                                  **vs.flicker_keywords_from_arguments(a, delivered=True))
     codec_keys = {} if a.codec is None else {"codec_quality": np.int64(a.codec.quality), "codec_subsampling": a.codec.subsampling,
-                                                "codec_gop": np.int64(a.codec.gop)}
+                                                "codec_gop": np.int64(a.codec.gop), "codec_search": np.int64(a.codec.search)}
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")

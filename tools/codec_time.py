@@ -11,12 +11,15 @@
    GOP legs (flk_codec_roundtrip_gop_u8, quality 75, `--gop` 12): `gop_launch_*` on 16 clips x (16 + 11 lead-in frames) x 240 x 320
    beside `intra_same_*`, the intra launch of the same frames; `gop_video_*` / `intra_video_*` on one whole `--frames` video; and the
    step with `Codec(75, "420", gop)` (`gop_420`) beside the intra one.
+   Motion legs (flk_codec_roundtrip_mc_u8, `--search` 7; 0 leaves them out): `mc_launch_*` / `mc_video_*`, the launch sequence of the
+   same frames as the GOP legs (one launch per frame position, the workspace allocated once), and the step with
+   `Codec(75, "420", gop, search)` (`mc_420`).
 3. The no-codec step and the intra launches against the PARENT commit (`--parent-root PATH`: a checkout of the parent with its library
    built): the same launches, so the trees only have to agree inside the run's spread.  A process per tree and round, alternating.
 
 Prints one JSON line per leg and a summary line.  Needs the GPU; there is no fallback.
 
-    python tools/codec_time.py [--steps 30] [--warmup 6] [--rounds 2] [--reps 20] [--frames 300] [--gop 12] [--parent-root PATH]"""
+    python tools/codec_time.py [--steps 30] [--warmup 6] [--rounds 2] [--reps 20] [--frames 300] [--gop 12] [--search 7] [--parent-root PATH]"""
 import argparse
 import json
 import os
@@ -46,7 +49,8 @@ def worker(a):
                   augment={"seed": 0}, sampling={"temporal_jitter": True, "random_shift": True, "seed": 0}, train_delivered=True)
     legs = {}
     for leg in a.legs.split(","):
-        kw = {} if leg == "delivered" else dict(codec=vs.Codec(75, leg.split("_")[1], **(dict(gop=a.gop) if leg.startswith("gop_") else {})))
+        extra = dict(gop=a.gop) if leg.startswith("gop_") else dict(gop=a.gop, search=a.search) if leg.startswith("mc_") else {}
+        kw = {} if leg == "delivered" else dict(codec=vs.Codec(75, leg.split("_")[1], **extra))
         legs[leg] = FlickerVideoResNet("mc3_18", W, **common, **kw)
     first = next(iter(legs.values()))
     lab = first.logits(first.prepare_videos(videos, train=False), False).argmax(1).clone()
@@ -136,6 +140,11 @@ def launches(a, videos, eng, torch):
             calls[f"gop_video_{sub}"] = lambda g=whole, f=ints(0, 1), c=ints(a.frames, 1): lib.flk_codec_roundtrip_gop_u8(
                 C.byref(g), a.gop, f, c, a.frames, None, None, stream_ptr())
             calls[f"intra_video_{sub}"] = lambda g=whole: lib.flk_codec_roundtrip_u8(C.byref(g), None, a.frames, None, None, stream_ptr())
+            if a.search > 0 and hasattr(lib, "flk_codec_roundtrip_mc_u8"):
+                for name, g, f, c, n in ((f"mc_launch_{sub}", spans, ints(a.gop, B), ints(L, B), L), (f"mc_video_{sub}", whole, ints(0, 1), ints(a.frames, 1), a.frames)):
+                    ws = torch.empty(lib.flk_codec_mc_scratch_bytes(C.byref(g), a.gop, c), dtype=torch.uint8, device="cuda")
+                    calls[name] = lambda g=g, f=f, c=c, n=n, ws=ws: lib.flk_codec_roundtrip_mc_u8(
+                        C.byref(g), a.gop, a.search, f, c, n, None, None, None, 0, ptr(ws), ws.numel(), stream_ptr())
     out = {}
     for name, call in calls.items():
         for _ in range(3):
@@ -156,7 +165,8 @@ def launches(a, videos, eng, torch):
 
 def run_worker(root, legs, a, with_launches=False):
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--root", root, "--legs", legs, "--steps", str(a.steps), "--warmup", str(a.warmup),
-           "--reps", str(a.reps), "--rounds", str(a.rounds), "--frames", str(a.frames), "--gop", str(a.gop)] + (["--launches"] if with_launches else [])
+           "--reps", str(a.reps), "--rounds", str(a.rounds), "--frames", str(a.frames), "--gop", str(a.gop), "--search", str(a.search)]
+    cmd += ["--launches"] if with_launches else []
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"worker failed ({root}, {legs}):\n{r.stdout[-2000:]}{r.stderr[-4000:]}")
@@ -171,6 +181,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--frames", type=int, default=300, help="frames of each of the 16 resident videos")
     ap.add_argument("--gop", type=int, default=12, help="the GOP length of the GOP legs")
+    ap.add_argument("--search", type=int, default=7, help="the motion search range of the motion legs (0: none)")
     ap.add_argument("--parent-root", default=None, help="a checkout of the parent commit with libflicker_hip.so built in it")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--launches", action="store_true", help=argparse.SUPPRESS)
@@ -181,18 +192,26 @@ def main():
         ap.error("--gop must be >= 2 (1 is the intra codec, which the other legs time)")
     if a.worker:
         return worker(a)
-    same = run_worker(HERE, "delivered,codec_420,codec_444,gop_420", a, with_launches=True)
+    if not 0 <= a.search <= 15:
+        ap.error("--search must be in 0..15")
+    same = run_worker(HERE, "delivered,codec_420,codec_444,gop_420" + (",mc_420" if a.search else ""), a, with_launches=True)
     for leg, v in same.items():
         print(json.dumps({"what": "same build, one process", "leg": leg, **v}), flush=True)
     summary = {f"{leg}_minus_delivered_ms": round(same[leg]["median_ms"] - same["delivered"]["median_ms"], 4) for leg in ("codec_420", "codec_444")}
     summary["gop_420_minus_codec_420_ms"] = round(same["gop_420"]["median_ms"] - same["codec_420"]["median_ms"], 4)
+    if a.search:
+        summary["mc_420_minus_gop_420_ms"] = round(same["mc_420"]["median_ms"] - same["gop_420"]["median_ms"], 4)
     for sub in ("444", "420"):
         summary[f"gop_launch_{sub}_over_intra_same"] = round(same[f"gop_launch_{sub}"]["median_ms"] / same[f"intra_same_{sub}"]["median_ms"], 2)
         summary[f"gop_video_{sub}_over_intra_video"] = round(same[f"gop_video_{sub}"]["median_ms"] / same[f"intra_video_{sub}"]["median_ms"], 2)
+        if a.search:
+            summary[f"mc_launch_{sub}_over_gop_launch"] = round(same[f"mc_launch_{sub}"]["median_ms"] / same[f"gop_launch_{sub}"]["median_ms"], 2)
+            summary[f"mc_video_{sub}_over_gop_video"] = round(same[f"mc_video_{sub}"]["median_ms"] / same[f"gop_video_{sub}"]["median_ms"], 2)
         summary[f"launch_{sub}_over_copy"] = round(same[f"launch_{sub}"]["median_ms"] / same["device_copy"]["median_ms"], 2)
         summary[f"launch_{sub}_over_export"] = round(same[f"launch_{sub}"]["median_ms"] / same["export_u8"]["median_ms"], 2)
     if a.parent_root:
-        what = ("delivered", "launch_420", "launch_444")     # the no-codec step and the intra launches: the same device code in both trees
+        # the no-codec step, the intra launches and the zero-motion GOP launches: the same device code in both trees
+        what = ("delivered", "launch_420", "launch_444", "gop_launch_420", "gop_launch_444")
         med = {w: {"this": [], "parent": []} for w in what}
         for k in range(a.rounds):                           # the two trees alternate, a process each; who goes first alternates too
             for tree in (("parent", "this"), ("this", "parent"))[k % 2]:
