@@ -35,6 +35,11 @@ class ConvArgs(C.Structure):
                 ("pos_bias", C.c_void_p), ("splitk_ws", C.c_void_p), ("splitk_ws_bytes", C.c_int64), ("pos_bias_bstride", C.c_int64)]
 
 
+class ConvPlanInfo(C.Structure):
+    _fields_ = [("route", C.c_int), ("nf", C.c_int), ("wn", C.c_int), ("mode", C.c_int), ("template_mode", C.c_int), ("ksplit", C.c_int),
+                ("Tt", C.c_int), ("Ht", C.c_int), ("Wt", C.c_int), ("rows", C.c_int), ("halo", C.c_int), ("wgs", C.c_int64)]
+
+
 class PoolArgs(C.Structure):
     _fields_ = [("in_", C.c_void_p), ("in_ld", C.c_int), ("in_coff", C.c_int), ("C", C.c_int),
                 ("B", C.c_int), ("Ti", C.c_int), ("Hi", C.c_int), ("Wi", C.c_int),
@@ -195,6 +200,11 @@ _SIGS = {
     "flk_conv3d_pc_why_not": (C.c_char_p, [C.POINTER(ConvArgs), C.c_void_p, C.c_int]),
     "flk_conv3d_group_check": (C.c_int, [C.POINTER(C.POINTER(ConvArgs)), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int]),
     "flk_conv_layout_query": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "flk_conv_plan_query": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(ConvPlanInfo)]),
+    "flk_conv_group_plan_query": (C.c_int, [C.POINTER(C.POINTER(ConvArgs)), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
+                                            C.POINTER(ConvPlanInfo)]),
+    "flk_conv_layout_candidates": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "flk_conv3d_layout": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "flk_comm_unique_id": (C.c_int, [C.c_void_p]),
     "flk_comm_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
     "flk_allreduce_sum_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),

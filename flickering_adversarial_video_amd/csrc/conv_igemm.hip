@@ -1435,6 +1435,10 @@ static int launch(const ConvLaunch& L, hipStream_t s) {
   return FLK_OK;
 }
 
+// the MODE template argument a planned weight path runs as: the row-ahead ring (planner mode 5) writes the ring behind the barrier (MODE 6)
+// on tiles of at most 64 channels; every other mode is its own template argument
+static int conv_template_mode(int nf, int mode) { return mode == 5 && nf <= 4 ? 6 : mode; }
+
 // The launch conv_plan decided: template dispatch, the FLK_CONV_DBG line.
 static int conv_launch(const ConvLaunch& L, hipStream_t s) {
   const ConvKP& kp = L.kp;
@@ -1487,10 +1491,11 @@ static int conv_launch(const ConvLaunch& L, hipStream_t s) {
       // ring write behind the barrier (mode 6): measured on <= 64-channel tiles only (Conv3d_2c 0.2525 / 0.2467 -> 0.2478 / 0.2402 ms forward /
       // data-gradient, Mixed_3c Branch_1 0.2348 -> 0.2308, 160 -> 320 at 25 088 positions 0.0955 -> 0.0922, the (1,3,3) 64 -> 144 layer 0.1398 ->
       // 0.1315; 128- and 96-channel tiles the same: they stay mode 5)
-      if (mode == 5 && wn == 1 && nf == 2) return launch<bf16_t, 2, 1, 6>(L, s);
-      if (mode == 5 && wn == 1 && nf == 4) return launch<bf16_t, 4, 1, 6>(L, s);
-      if (mode == 5 && wn == 1 && nf == 8) return launch<bf16_t, 8, 1, 5>(L, s);
-      if (mode == 5 && wn == 1 && nf == 6) return launch<bf16_t, 6, 1, 5>(L, s);
+      const int tmode = conv_template_mode(nf, mode);
+      if (tmode == 6 && wn == 1 && nf == 2) return launch<bf16_t, 2, 1, 6>(L, s);
+      if (tmode == 6 && wn == 1 && nf == 4) return launch<bf16_t, 4, 1, 6>(L, s);
+      if (tmode == 5 && wn == 1 && nf == 8) return launch<bf16_t, 8, 1, 5>(L, s);
+      if (tmode == 5 && wn == 1 && nf == 6) return launch<bf16_t, 6, 1, 5>(L, s);
       FLK_LAUNCH0(bf16_t, 2, 1); FLK_LAUNCH0(bf16_t, 4, 1); FLK_LAUNCH0(bf16_t, 8, 1); FLK_LAUNCH0(bf16_t, 6, 1);
       FLK_LAUNCHD(bf16_t, 2, 1); FLK_LAUNCHD(bf16_t, 4, 1); FLK_LAUNCHD(bf16_t, 4, 2);
       FLK_LAUNCHD(bf16_t, 8, 2); FLK_LAUNCHD(bf16_t, 8, 4);
@@ -1512,7 +1517,7 @@ static int conv_launch(const ConvLaunch& L, hipStream_t s) {
 // compute exactly what flk_conv3d would have with that layout.  Members in the order given: put the longest K loops first.
 // plan of a grouped launch: member table, LDS size, grid, body mode (1 direct-A, 0 / 5 / 6 ring forms)
 static int group_plan(const flk_conv_args* const* a, const flk_conv_weights* const* w, int n, int nfw, int ring, int dtype, ConvGroupKP& g, size_t& lds,
-                      long& total, int& gmode) {
+                      long& total, int& gmode, ConvLaunch* plans = nullptr) {
   FLK_REQUIRE(a && w && n >= 1 && n <= FLK_MAX_GROUP, "flk_conv3d_group: 1..%d members", FLK_MAX_GROUP);
   FLK_REQUIRE(dtype == FLK_BF16 && (ring ? (nfw == 4 || nfw == 8) : (nfw == 2 || nfw == 4)),
               "flk_conv3d_group: bf16; 2 or 4 channel fragments per wave (direct-A members) or channel tiles of 4 or 8 fragments (ring members)");
@@ -1534,6 +1539,7 @@ static int group_plan(const flk_conv_args* const* a, const flk_conv_weights* con
     all5 = all5 && pl.mode == 5;
     FLK_REQUIRE((ring ? (pl.mode == 0 || pl.mode == 5) : pl.mode == 1) && pl.wn * nfw == (ring ? nfw : pl.nf),
                 "flk_conv3d_group: member %d planned as mode %d, wn %d", i, pl.mode, pl.wn);
+    if (plans) plans[i] = pl;
     g.m[i] = pl.kp;
     g.m[i].wn = pl.wn;
     g.start[i] = (int)total;
@@ -1545,7 +1551,7 @@ static int group_plan(const flk_conv_args* const* a, const flk_conv_weights* con
               pl.kp.Ht, pl.kp.Wt, pl.kp.rows, pl.kp.P, pl.grid.x, pl.lds);
   }
   FLK_REQUIRE(total < (1l << 31), "flk_conv3d_group: grid too large");
-  gmode = ring ? (all5 ? (nfw == 4 ? 6 : 5) : 0) : 1;      // (ring write behind the barrier: the 64-channel tiles)
+  gmode = ring ? (all5 ? conv_template_mode(nfw, 5) : 0) : 1;      // (ring write behind the barrier: the 64-channel tiles)
   return FLK_OK;
 }
 
@@ -1563,31 +1569,81 @@ extern "C" int flk_conv3d_group(const flk_conv_args* const* a, const flk_conv_we
   ConvGroupKP g; size_t lds; long total; int gmode;
   if (int rc = group_plan(a, w, n, nfw, ring, dtype, g, lds, total, gmode)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  static bool attr[7][FLK_MAX_DEVICES] = {};
+  static bool attr[6][FLK_MAX_DEVICES] = {};
 #define FLK_LAUNCH_GROUP(NFWv, MODEv, idx)                                                                                           \
   if (nfw == NFWv && gmode == MODEv) {                                                                                                \
     if (int rc = flk_raise_lds_limit((const void*)conv_igemm_group_kernel<bf16_t, NFWv, MODEv>, 96 * 1024, attr[idx])) return rc;    \
     FLK_LAUNCH_KERNEL((conv_igemm_group_kernel<bf16_t, NFWv, MODEv>), dim3((unsigned)total), dim3(256), lds, s, g);                  \
   }
-  FLK_LAUNCH_GROUP(2, 1, 0) FLK_LAUNCH_GROUP(4, 1, 1) FLK_LAUNCH_GROUP(4, 0, 2) FLK_LAUNCH_GROUP(8, 0, 3) FLK_LAUNCH_GROUP(4, 5, 4) FLK_LAUNCH_GROUP(8, 5, 5) FLK_LAUNCH_GROUP(4, 6, 6)
+  FLK_LAUNCH_GROUP(2, 1, 0) FLK_LAUNCH_GROUP(4, 1, 1) FLK_LAUNCH_GROUP(4, 0, 2) FLK_LAUNCH_GROUP(8, 0, 3) FLK_LAUNCH_GROUP(8, 5, 4) FLK_LAUNCH_GROUP(4, 6, 5)
 #undef FLK_LAUNCH_GROUP
   flk_last_kernel_tag = "conv_igemm_group_kernel";
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
 
+// the fields conv_plan reads of weights packed for a's operator at nf / dtype (api.cpp's packer), without the weights: stem4 the folded-stem
+// packing (49 K steps over one slab in bf16, the generic 4x4x4 packing in fp32), cin_split the first segment of a two-segment K order
+static flk_conv_weights plan_only_weights(const flk_conv_args* a, int nf, int dtype, int stem4 = 0, int cin_split = 0) {
+  flk_conv_weights w{};
+  w.dev = (void*)1; w.kt = a->kt; w.kh = a->kh; w.kw = a->kw; w.cin = a->cin; w.cout = a->cout; w.dtype = dtype; w.nf = nf;
+  const int slabc = dtype == FLK_BF16 ? 32 : 16;
+  w.nslab1 = cin_split ? (cin_split + slabc - 1) / slabc : 0;
+  w.nslab = cin_split ? w.nslab1 + (a->cin - cin_split + slabc - 1) / slabc : (a->cin + slabc - 1) / slabc;
+  if (!cin_split) w.nslab1 = w.nslab;
+  w.cin_split = cin_split;
+  w.ntaps = a->kt * a->kh * a->kw;
+  if (stem4 && dtype == FLK_BF16) { w.stem4 = 1; w.ntaps = 49; }
+  w.cout_frags = ((a->cout + 15) / 16 + nf - 1) / nf * nf;
+  return w;
+}
+
 // the (waves along N, weight path) flk_conv3d's heuristics pick for this geometry with weights packed at `nf` (plan builders decide how to
 // pack a grouped launch's members before any weights exist)
 extern "C" int flk_conv_layout_query(const flk_conv_args* a, int nf, int dtype, int force_da, int* wn_out, int* mode_out) {
   FLK_REQUIRE(a && wn_out && mode_out && nf > 0, "flk_conv_layout_query: bad argument");
-  flk_conv_weights w{};
-  w.dev = (void*)1; w.kt = a->kt; w.kh = a->kh; w.kw = a->kw; w.cin = a->cin; w.cout = a->cout; w.dtype = dtype; w.nf = nf;
-  const int epl = dtype == FLK_BF16 ? 8 : 4;
-  w.nslab = (a->cin + 4 * epl - 1) / (4 * epl); w.ntaps = a->kt * a->kh * a->kw;
-  w.cout_frags = ((a->cout + 15) / 16 + nf - 1) / nf * nf; w.nslab1 = w.nslab;
+  const flk_conv_weights w = plan_only_weights(a, nf, dtype);
   ConvLaunch pl;
   if (int rc = conv_plan(a, &w, dtype, ConvOpts{0, force_da, true}, pl)) return rc;
   *wn_out = pl.wn; *mode_out = pl.mode;
+  return FLK_OK;
+}
+
+// Plan queries (tests/test_conv_instances_cpu.py: which instantiation a case runs).  They call conv_plan / group_plan with the launch's own
+// options and report the decision; nothing is restated here but the packer's slab and fragment counts (plan_only_weights).
+static flk_conv_plan_info plan_info(const ConvLaunch& L) {
+  const ConvKP& kp = L.kp;
+  return flk_conv_plan_info{(int)L.route, L.nf, L.wn, L.mode, conv_template_mode(L.nf, L.mode), kp.ksplit, kp.Tt, kp.Ht, kp.Wt, kp.rows, kp.P, (int64_t)L.wgs};
+}
+
+extern "C" int flk_conv_plan_query(const flk_conv_args* a, int nf, int dtype, int stem4, int cin_split, int wn, int da, int splitk, flk_conv_plan_info* out) {
+  FLK_REQUIRE(a && out && (nf == 2 || nf == 4 || nf == 6 || nf == 8) && cin_split >= 0 && cin_split < a->cin, "flk_conv_plan_query: bad argument");
+  FLK_REQUIRE(!stem4 || (a->kt == 4 && a->kh == 4 && a->kw == 4 && a->cin == 32 && !cin_split), "flk_conv_plan_query: the folded stem is a 4x4x4 convolution over 32 channels");
+  const flk_conv_weights w = plan_only_weights(a, nf, dtype, stem4, cin_split);
+  flk_conv_args b = *a;          // the workspace as the caller says it will be (conv_plan reads only whether it is there and how large)
+  b.splitk_ws = splitk ? (void*)1 : nullptr;
+  b.splitk_ws_bytes = splitk ? INT64_MAX : 0;
+  ConvLaunch pl;
+  if (int rc = conv_plan(&b, &w, dtype, ConvOpts{wn, da, false}, pl)) return rc;
+  *out = plan_info(pl);
+  return FLK_OK;
+}
+
+extern "C" int flk_conv_group_plan_query(const flk_conv_args* const* a, const int* nf, int n, int nfw, int ring, int dtype, int* body_mode,
+                                         flk_conv_plan_info* members) {
+  FLK_REQUIRE(a && nf && body_mode && members && n >= 1 && n <= FLK_MAX_GROUP, "flk_conv_group_plan_query: 1..%d members", FLK_MAX_GROUP);
+  flk_conv_weights w[FLK_MAX_GROUP];
+  const flk_conv_weights* wp[FLK_MAX_GROUP];
+  for (int i = 0; i < n; ++i) {
+    FLK_REQUIRE(a[i] && nf[i] > 0, "flk_conv_group_plan_query: null member %d", i);
+    w[i] = plan_only_weights(a[i], nf[i], dtype);
+    wp[i] = &w[i];
+  }
+  ConvGroupKP g; size_t lds; long total; int gmode;
+  ConvLaunch plans[FLK_MAX_GROUP];
+  if (int rc = group_plan(a, wp, n, nfw, ring, dtype, g, lds, total, gmode, plans)) return rc;
+  for (int i = 0; i < n; ++i) members[i] = plan_info(plans[i]);
+  *body_mode = gmode;
   return FLK_OK;
 }
 
@@ -1601,6 +1657,38 @@ extern "C" int flk_conv_layout_query(const flk_conv_args* a, int nf, int dtype, 
 static thread_local int g_tuning = 0;
 extern "C" int flk_conv_set_autotune(int on) { g_tuning = on != 0; return FLK_OK; }
 
+// The layouts a tuning call times for weights packed at nf / dtype, the heuristic's choice first: the ring at wn = 1, direct A at every
+// wave count that leaves a wave 2..4 (bf16) / 1..4 (fp32) fragments.  The folded stem is never tuned.  flk_conv3d_layout accepts these only.
+static std::vector<ConvOpts> conv_candidates(int nf, int dtype, int stem4) {
+  std::vector<ConvOpts> cands;
+  cands.push_back({0, -1});                                       // the heuristic's choice
+  if (stem4) return cands;
+  const int wn_max = nf == 6 ? 1 : dtype == FLK_BF16 ? nf / 2 : nf;
+  for (int wn = 1; wn <= 4 && wn <= (wn_max < 1 ? 1 : wn_max); wn *= 2) {
+    const int nfw = nf / wn;
+    if (wn == 1) cands.push_back({1, 0});
+    if (nf != 6 && nfw <= 4 && (dtype != FLK_BF16 || nfw >= 2)) cands.push_back({wn, 1});
+  }
+  return cands;
+}
+
+extern "C" int flk_conv_layout_candidates(int nf, int dtype, int stem4, int* wn, int* da, int cap) {
+  const std::vector<ConvOpts> cands = conv_candidates(nf, dtype, stem4 && dtype == FLK_BF16);
+  for (int i = 0; i < (int)cands.size() && i < cap && wn && da; ++i) { wn[i] = cands[i].wn; da[i] = cands[i].da; }
+  return (int)cands.size();
+}
+
+extern "C" int flk_conv3d_layout(const flk_conv_args* a, const flk_conv_weights* w, int dtype, int wn, int da, void* stream) {
+  FLK_REQUIRE(a && w, "flk_conv3d_layout: null argument");
+  bool listed = false;
+  for (const ConvOpts& c : conv_candidates(w->nf, dtype, w->stem4)) listed = listed || (c.wn == wn && c.da == da);
+  FLK_REQUIRE(listed, "flk_conv3d_layout: {wn %d, da %d} is not a layout the autotuner times for nf %d, dtype %d%s", wn, da, w->nf, dtype,
+              w->stem4 ? " (folded stem)" : "");
+  ConvLaunch L;
+  if (int rc = conv_plan(a, w, dtype, ConvOpts{wn, da, false}, L)) return rc;
+  return conv_launch(L, (hipStream_t)stream);
+}
+
 extern "C" int flk_conv3d(const flk_conv_args* a, const flk_conv_weights* w, int dtype, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   auto run = [&](const ConvOpts& o) { ConvLaunch L; const int rc = conv_plan(a, w, dtype, o, L); return rc ? rc : conv_launch(L, s); };
@@ -1613,14 +1701,7 @@ extern "C" int flk_conv3d(const flk_conv_args* a, const flk_conv_weights* w, int
   hipEvent_t e0, e1;
   FLK_CHECK_HIP(hipEventCreate(&e0));
   FLK_CHECK_HIP(hipEventCreate(&e1));
-  const int nf = w->nf, wn_max = nf == 6 ? 1 : dtype == FLK_BF16 ? nf / 2 : nf;
-  std::vector<ConvOpts> cands;
-  cands.push_back({0, -1});                                       // the heuristic's choice
-  for (int wn = 1; wn <= 4 && wn <= (wn_max < 1 ? 1 : wn_max); wn *= 2) {
-    const int nfw = nf / wn;
-    if (wn == 1) cands.push_back({1, 0});
-    if (nf != 6 && nfw <= 4 && (dtype != FLK_BF16 || nfw >= 2)) cands.push_back({wn, 1});
-  }
+  const std::vector<ConvOpts> cands = conv_candidates(w->nf, dtype, w->stem4);
   float best_ms = 1e30f;
   ConvOpts best = cands[0];
   for (const ConvOpts& c : cands) {

@@ -79,6 +79,47 @@ def conv3d(x, w, **kw):
     return out
 
 
+def conv3d_layout(x, w, wn, da, **kw):
+    """conv3d with the launch layout {wn, da} of the caller (flk_conv3d_layout): one of conv_layout_candidates(w.nf, x.dtype), (0, -1)
+    being the heuristic's own launch; never the producer / consumer kernel"""
+    a, out = conv3d_args(x, w, **kw)
+    check(load().flk_conv3d_layout(C.byref(a), w.handle, dtype_code(x.dtype), wn, da, stream_ptr()))
+    return out
+
+
+def conv_layout_candidates(nf, dtype, stem4=False):
+    """[(wn, da)]: the layouts the autotuner times for weights packed at nf / dtype, the heuristic (0, -1) first (no device work)"""
+    wn, da = (C.c_int * 8)(), (C.c_int * 8)()
+    n = load().flk_conv_layout_candidates(nf, dtype_code(dtype), int(stem4), wn, da, 8)
+    assert 0 < n <= 8
+    return [(wn[i], da[i]) for i in range(n)]
+
+
+_PLAN_ROUTES = ("halo", "t3", "t3_tiled", "dma1x1")
+
+
+def _plan_dict(p):
+    return dict(route=_PLAN_ROUTES[p.route], nf=p.nf, wn=p.wn, mode=p.mode, template_mode=p.template_mode, ksplit=p.ksplit,
+                tile=(p.Tt, p.Ht, p.Wt), rows=p.rows, halo=p.halo, wgs=p.wgs)
+
+
+def conv_plan_query(a, nf, dtype, *, stem4=False, cin_split=0, wn=0, da=-1, splitk=False):
+    """what the planner decides for flk_conv3d(a, weights packed at nf / dtype) under the requested layout (flk_conv_plan_query; no
+    weights, no device work): dict(route, nf, wn, mode, template_mode, ksplit, tile, rows, halo, wgs)"""
+    p = _lib.ConvPlanInfo()
+    check(load().flk_conv_plan_query(C.byref(a), nf, dtype_code(dtype), int(stem4), cin_split, wn, da, int(splitk), C.byref(p)))
+    return _plan_dict(p)
+
+
+def conv_group_plan_query(args, nfs, nfw, ring, dtype):
+    """(body mode, [member plans]) of flk_conv3d_group over the flk_conv_args `args` with weights packed at `nfs` (no device work)"""
+    n = len(args)
+    ap = (C.POINTER(ConvArgs) * n)(*[C.pointer(a) for a in args])
+    body, plans = C.c_int(), (_lib.ConvPlanInfo * n)()
+    check(load().flk_conv_group_plan_query(ap, (C.c_int * n)(*nfs), n, nfw, int(ring), dtype_code(dtype), C.byref(body), plans))
+    return body.value, [_plan_dict(p) for p in plans]
+
+
 def conv3d_group(members, nfw, ring=False):
     """members: [(x, w, kwargs)] -- up to three multi-tap bf16 convolutions in ONE launch (flk_conv3d_group); returns their outputs.
     ring: the members take the LDS weight ring (all packed with nf == nfw) instead of direct-A weights"""

@@ -141,6 +141,36 @@ int flk_conv3d_group_check(const flk_conv_args* const* a, const flk_conv_weights
  * weights are packed at `nf` (force_da: -1 heuristic, 0 ring, 1 direct A): lets a plan builder pick the packing of a grouped launch's
  * members before any weights exist.  No device work. */
 int flk_conv_layout_query(const flk_conv_args* a, int nf, int dtype, int force_da, int* wn_out, int* mode_out);
+/* Everything the planner decides for one launch, from the geometry and the packing alone (no weights, no device work): the plan of
+ * flk_conv3d(a, weights packed at nf / dtype) under a requested layout.  route: 0 the halo kernel (conv_igemm_kernel), 1 the LDS-DMA ring
+ * over whole-T tiles (conv_t3_dma_kernel), 2 its form with 16-frame temporal tiles, 3 the 1x1x1 LDS-DMA ring (conv1x1_dma_kernel).  mode is
+ * the planner's weight path (0 ring, 1 direct A, 2 direct A of a 1x1x1, 3 ring of a 1x1x1, 4 folded stem, 5 ring with the weights a row of
+ * taps ahead), template_mode the MODE argument of the conv_igemm_kernel instance the dispatch launches (planner mode 5 runs template 6, the
+ * ring write behind the barrier, on tiles of at most 64 channels); both describe the halo kernel and are what a forced halo launch would
+ * take when route != 0.  nf / wn: channel fragments of the workgroup tile and waves along the channels as they will really run (a request
+ * the planner clamps -- direct A on 96-channel tiles, more waves than the tile has fragment pairs -- is reported clamped).  ksplit: split-K
+ * slices (1 = none); tile / rows / halo: output positions per workgroup and the cells of its input halo; wgs: workgroups. */
+typedef struct {
+  int route, nf, wn, mode, template_mode, ksplit;
+  int Tt, Ht, Wt, rows, halo;
+  int64_t wgs;
+} flk_conv_plan_info;
+/* stem4: the folded-stem packing (flk_conv_weights_create_s2d_stem; bf16 packs K steps, fp32 is the generic 4x4x4 packing); cin_split: 0 or
+ * the first segment's channels of a two-segment packing (a->in2 / a->cin1 must agree); wn / da: the requested layout (0 / -1 = heuristic,
+ * wn 1 / 2 / 4 waves along the channels, da 0 LDS ring / 1 direct A); splitk: plan as if a->splitk_ws were given (!= 0) or not (0). */
+int flk_conv_plan_query(const flk_conv_args* a, int nf, int dtype, int stem4, int cin_split, int wn, int da, int splitk, flk_conv_plan_info* out);
+/* the same for flk_conv3d_group(a, weights packed at nf[i], n, nfw, ring): members[i] as group_plan plans member i, *body_mode the MODE
+ * argument of the conv_igemm_group_kernel<NFW = nfw, MODE> instance (1 direct A; ring groups: 0, or 5 / 6 when EVERY member is planned
+ * for the row-ahead ring) */
+int flk_conv_group_plan_query(const flk_conv_args* const* a, const int* nf, int n, int nfw, int ring, int dtype, int* body_mode,
+                              flk_conv_plan_info* members);
+/* the layouts {wn, da} the autotuner times for weights packed at nf / dtype, in its order, the heuristic {0, -1} first (the folded stem is
+ * never tuned: that one only); at most cap are written, the count is returned */
+int flk_conv_layout_candidates(int nf, int dtype, int stem4, int* wn, int* da, int cap);
+/* flk_conv3d with the layout {wn, da} given by the caller: exactly the launch the autotuner times for that candidate and a tuned entry
+ * replays (not the producer / consumer kernel; {0, -1} is the heuristic's own launch, every other layout runs the halo kernel).  A
+ * layout that is not in flk_conv_layout_candidates for these weights is refused (FLK_EINVAL) before anything is launched. */
+int flk_conv3d_layout(const flk_conv_args* a, const flk_conv_weights* w, int dtype, int wn, int da, void* stream);
 
 /* tf.nn.max_pool3d SAME (i3d.py:174,189,212,252,398): padded cells never win; argmax = FIRST
  * maximum in (t,h,w) scan order (strict >), stored as a uint8 window index (tap = (dt*kh + dh)*kw + dw) for the backward pass.

@@ -81,6 +81,19 @@ static void packing() {
     flk_conv_weights* other = nullptr;
     EXPECT(flk_conv_weights_create(w7.data(), 1, 1, 1, 32, 64, nullptr, 0, FLK_BF16, 4, &other) == FLK_OK, "a 1x1x1 weight object");
     EXPECT(flk_stem_fwd_u8(&a, other, sc.data(), bi.data(), nullptr, 0, out.data(), 64, nullptr) == FLK_EINVAL, "stem-from-uint8 refuses foreign weights");
+    {
+      // flk_conv3d_layout on that object: every candidate layout of its packing is planned and launched, anything else refused first
+      std::vector<uint16_t> xin((size_t)2 * 3 * 9 * 11 * 32), yout((size_t)2 * 3 * 9 * 11 * 64);
+      flk_conv_args c{};
+      c.in = xin.data(); c.in_ld = 32; c.cin = 32; c.out = yout.data(); c.out_ld = 64; c.cout = 64;
+      c.B = 2; c.Ti = c.To = c.OT = 3; c.Hi = c.Ho = c.OH = 9; c.Wi = c.Wo = c.OW = 11;
+      c.kt = c.kh = c.kw = c.st = c.sh = c.sw = c.ost = c.osh = c.osw = 1;
+      int wn[8], da[8];
+      const int n = flk_conv_layout_candidates(4, FLK_BF16, 0, wn, da, 8);
+      for (int i = 0; i < n; ++i) EXPECT(flk_conv3d_layout(&c, other, FLK_BF16, wn[i], da[i], nullptr) == FLK_OK, "forced layout {%d, %d}", wn[i], da[i]);
+      EXPECT(flk_conv3d_layout(&c, other, FLK_BF16, 4, 1, nullptr) == FLK_EINVAL && strstr(flk_last_error(), "autotuner") != nullptr, "forced layout outside the candidates");
+      EXPECT(flk_conv3d_layout(&c, other, FLK_BF16, 2, 0, nullptr) == FLK_EINVAL, "forced ring at wn 2");
+    }
     flk_conv_weights_destroy(other);
   }
   flk_conv_weights_destroy(cw);
@@ -96,6 +109,33 @@ static void validation() {
   EXPECT(strlen(flk_last_error()) > 0, "error text");
   EXPECT(flk_conv_weights_destroy(nullptr) == FLK_OK, "destroy(null)");
   EXPECT(flk_conv3d(nullptr, nullptr, FLK_BF16, nullptr) < 0, "conv3d(null)");
+  {
+    // the plan queries and the forced-layout launch: host code only (planning over weights that exist as a description, candidate tables)
+    flk_conv_args a{};
+    a.B = 2; a.Ti = a.To = a.OT = 6; a.Hi = a.Ho = a.OH = 11; a.Wi = a.Wo = a.OW = 12;
+    a.kt = a.kh = a.kw = 3; a.st = a.sh = a.sw = a.ost = a.osh = a.osw = 1; a.pt = a.ph = a.pw = 1;
+    a.cin = 40; a.in_ld = 56; a.in_coff = 8; a.cout = 136; a.out_ld = 152; a.out_coff = 8;
+    flk_conv_plan_info pi{};
+    int wn[8], da[8];
+    for (int dtype : {FLK_BF16, FLK_F32})
+      for (int nf : {2, 4, 6, 8}) {
+        if (nf == 6 && dtype == FLK_F32) continue;
+        const int n = flk_conv_layout_candidates(nf, dtype, 0, wn, da, 8);
+        EXPECT(n >= 2 && n <= 5 && wn[0] == 0 && da[0] == -1, "candidates nf %d", nf);
+        for (int i = 0; i < n; ++i)
+          EXPECT(flk_conv_plan_query(&a, nf, dtype, 0, 0, wn[i], da[i], i & 1, &pi) == FLK_OK && pi.route == 0 && pi.nf == nf, "plan query nf %d", nf);
+      }
+    EXPECT(flk_conv_layout_candidates(4, FLK_BF16, 1, wn, da, 1) == 1 && flk_conv_layout_candidates(4, FLK_BF16, 0, nullptr, nullptr, 0) == 4, "candidate caps");
+    EXPECT(flk_conv_plan_query(&a, 3, FLK_BF16, 0, 0, 0, -1, 0, &pi) == FLK_EINVAL && flk_conv_plan_query(&a, 4, FLK_BF16, 1, 0, 0, -1, 0, &pi) == FLK_EINVAL,
+           "plan query: bad nf, a stem that is not 4x4x4x32");
+    const flk_conv_args* ap[2] = {&a, &a};
+    const int nfs[2] = {4, 4};
+    flk_conv_plan_info mi[2];
+    int body = -1;
+    EXPECT(flk_conv_group_plan_query(ap, nfs, 2, 4, 1, FLK_BF16, &body, mi) == FLK_OK && body == 6 && mi[1].mode == 5, "group plan query (body %d)", body);
+    EXPECT(flk_conv_group_plan_query(ap, nfs, 4, 4, 1, FLK_BF16, &body, mi) == FLK_EINVAL, "group plan query: too many members");
+    EXPECT(flk_conv3d_layout(&a, nullptr, FLK_BF16, 1, 0, nullptr) == FLK_EINVAL, "conv3d_layout(null weights)");
+  }
   EXPECT(flk_maxpool3d_fwd(nullptr, FLK_BF16, nullptr) < 0, "maxpool(null)");
   EXPECT(flk_perturb_apply_s2d(nullptr, nullptr, FLK_BF16, nullptr) < 0, "apply(null)");
   EXPECT(flk_softmax_adv_loss(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) < 0, "loss(null)");

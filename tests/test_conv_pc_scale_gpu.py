@@ -22,6 +22,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from conv_bound import bf16_bound_ratio
 from test_conv_pc_schedule_cpu import PC_SCALE_CASES, pc_schedule
 
 pytestmark = pytest.mark.gpu
@@ -170,7 +171,7 @@ def igemm_outputs(ops, tmp_path_factory):
 def bound_ratio(y, x, w, kt, *, scale=None, bias=None, add=None, mask=None, relu=False, bias_err=None):
     """worst |y - r| / bound of a convolution's output (y fp32 [B, T, H, W, cout]) against the fp32 oracle of x [.., cin] and the
     operator's weights w [kt, 3, 3, cin, cout]; the epilogue in the kernel's order: scale, bias, + add, ReLU, mask (> 0).  Asserts the
-    bound on every element.  bias_err: a bound on how far the bias the kernel used may be from `bias` (added to E)."""
+    bound on every element (conv_bound.bf16_bound_ratio).  bias_err: a bound on how far the bias the kernel used may be from `bias` (added to E)."""
     r = ref_conv(x, w, kt)
     S = ref_conv(x.abs(), w.abs(), kt)
     if scale is not None:
@@ -181,26 +182,7 @@ def bound_ratio(y, x, w, kt, *, scale=None, bias=None, add=None, mask=None, relu
         r = torch.relu(r)
     if mask is not None:
         r = torch.where(mask > 0, r, torch.zeros(()))
-    nK = 9 * kt * x.shape[-1]
-    s = scale.double().abs() if scale is not None else 1.0
-    b_abs = bias.double().abs() if bias is not None else 0.0
-    worst, where = 0.0, None
-    for b in range(r.shape[0]):         # float64, one clip at a time
-        rb, yb = r[b].double(), y[b].double()
-        E = nK * 2.0 ** -23 * s * S[b].double() + 2.0 ** -22 * (b_abs + (add[b].double().abs() if add is not None else 0.0))
-        if bias_err is not None:
-            E = E + bias_err.double()
-        bound = 2.0 ** -8 * rb.abs() + (1 + 2.0 ** -8) * E
-        err = (yb - rb).abs()
-        bad = ~(err <= bound)
-        if bool(bad.any()):
-            i = tuple(int(v) for v in bad.nonzero()[0])
-            raise AssertionError(f"{int(bad.sum())} elements outside the bound, the first at clip {b} {i}: y {float(yb[i])}, "
-                                 f"r {float(rb[i])}, bound {float(bound[i])}")
-        rw = float(torch.where(bound > 0, err / bound, torch.zeros((), dtype=torch.float64)).max())
-        if where is None or rw > worst:
-            worst, where = rw, b
-    return worst, where
+    return bf16_bound_ratio(y, r, S, 9 * kt * x.shape[-1], scale=scale, bias=bias, add=add, bias_err=bias_err)
 
 
 def member_bound_ratio(y, h, m):
