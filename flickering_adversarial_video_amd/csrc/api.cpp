@@ -283,6 +283,18 @@ extern "C" int flk_codec_inter_step(int quality, int32_t* qp) {
   return FLK_OK;
 }
 
+// what the two entries with spans check of them, the views already checked: clip i's span is frames first[i] .. first[i] + count[i] - 1
+static int check_codec_spans(const char* fn, const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max) {
+  for (int i = 0; i < a->nclip; ++i) {
+    FLK_REQUIRE(first[i] >= 0 && first[i] % gop == 0, "%s: clip %d: first %d is not a non-negative multiple of gop %d (a span starts on an intra frame)",
+                fn, i, first[i], gop);
+    FLK_REQUIRE(count[i] >= 1 && count[i] <= T_max, "%s: clip %d: count %d outside 1..T_max %d", fn, i, count[i], T_max);
+    FLK_REQUIRE((int64_t)first[i] + count[i] <= a->clips[i].T, "%s: clip %d: span %d + %d beyond its %d frames", fn, i, first[i], count[i],
+                a->clips[i].T);
+  }
+  return FLK_OK;
+}
+
 extern "C" int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max,
                                           const uint8_t* tone, int32_t* stats, void* stream) {
   const char* fn = "flk_codec_roundtrip_gop_u8";
@@ -291,13 +303,7 @@ extern "C" int flk_codec_roundtrip_gop_u8(const flk_codec_args* a, int gop, cons
   // the spans are held against the clips below: to the shared checks the launch has its own source frames (as with a frame_idx)
   // (a P-frame's magnitudes reach 766 per padded pixel, twice an intra frame's: half the frame for the same int32)
   if (int rc = check_codec_args(fn, a, true, T_max, stats ? 2500000 : 0)) return rc;
-  for (int i = 0; i < a->nclip; ++i) {
-    FLK_REQUIRE(first[i] >= 0 && first[i] % gop == 0, "%s: clip %d: first %d is not a non-negative multiple of gop %d (a span starts on an intra frame)",
-                fn, i, first[i], gop);
-    FLK_REQUIRE(count[i] >= 1 && count[i] <= T_max, "%s: clip %d: count %d outside 1..T_max %d", fn, i, count[i], T_max);
-    FLK_REQUIRE((int64_t)first[i] + count[i] <= a->clips[i].T, "%s: clip %d: span %d + %d beyond its %d frames", fn, i, first[i], count[i],
-                a->clips[i].T);
-  }
+  if (int rc = check_codec_spans(fn, a, gop, first, count, T_max)) return rc;
   return flk_codec_roundtrip_gop_launch(a, gop, first, count, T_max, tone, stats, (hipStream_t)stream);
 }
 
@@ -319,18 +325,12 @@ extern "C" int flk_codec_roundtrip_mc_u8(const flk_codec_args* a, int gop, int s
   FLK_REQUIRE(gop >= 1 && gop <= 65535, "%s: gop %d outside 1..65535", fn, gop);
   FLK_REQUIRE(search >= 0 && search <= 15, "%s: search %d outside 0..15", fn, search);
   if (int rc = check_codec_args(fn, a, true, T_max, stats ? 2500000 : 0)) return rc;
+  if (int rc = check_codec_spans(fn, a, gop, first, count, T_max)) return rc;
   const int M = a->subsampling == FLK_CODEC_420 ? 16 : 8;
-  for (int i = 0; i < a->nclip; ++i) {
-    FLK_REQUIRE(first[i] >= 0 && first[i] % gop == 0, "%s: clip %d: first %d is not a non-negative multiple of gop %d (a span starts on an intra frame)",
-                fn, i, first[i], gop);
-    FLK_REQUIRE(count[i] >= 1 && count[i] <= T_max, "%s: clip %d: count %d outside 1..T_max %d", fn, i, count[i], T_max);
-    FLK_REQUIRE((int64_t)first[i] + count[i] <= a->clips[i].T, "%s: clip %d: span %d + %d beyond its %d frames", fn, i, first[i], count[i],
-                a->clips[i].T);
-    if (mv) {
-      const int64_t Hp = ((int64_t)a->clips[i].Hs + M - 1) / M * M, Wp = ((int64_t)a->clips[i].Ws + M - 1) / M * M;
-      const int64_t mbs = ((Hp + 15) / 16) * ((Wp + 15) / 16);
-      FLK_REQUIRE(mv_stride >= mbs, "%s: clip %d: mv_stride %d below its %lld macroblocks", fn, i, mv_stride, (long long)mbs);
-    }
+  for (int i = 0; mv && i < a->nclip; ++i) {
+    const int64_t Hp = ((int64_t)a->clips[i].Hs + M - 1) / M * M, Wp = ((int64_t)a->clips[i].Ws + M - 1) / M * M;
+    const int64_t mbs = ((Hp + 15) / 16) * ((Wp + 15) / 16);
+    FLK_REQUIRE(mv_stride >= mbs, "%s: clip %d: mv_stride %d below its %lld macroblocks", fn, i, mv_stride, (long long)mbs);
   }
   const int64_t need = flk_codec_mc_scratch_host(a, gop, count);
   FLK_REQUIRE(need > 0, "%s: the workspace of these clips cannot be sized (a plane set above 2^36 bytes)", fn);

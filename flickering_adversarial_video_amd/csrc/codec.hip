@@ -15,13 +15,15 @@
 //
 // Mapping: workgroup = (tile of kTW columns x TH rows of one output frame of one clip), 192 threads.  TH = 32 (4:4:4) or 64 (4:2:0):
 // 192 8x8 blocks per full tile either way, ONE THREAD PER BLOCK -- the 64 values of a block stay in that thread's registers through
-// both passes of both transforms, so the transform needs no LDS transposes and no barriers.
-//   A  the source row segments under the tile into LDS as aligned dwords (the misalignment of a row kept per row, as
-//      clip_prepare_kernel does), and the frame's tone table
-//   B  bytes (through the tone) -> Y, Cb, Cr byte planes in LDS, padded by replication, chroma averaged for 4:2:0
-//   C  per block: forward DCT, quantise, (stats), dequantise, inverse DCT; the reconstructed bytes back into the block's place
-//   D  planes -> RGB bytes laid out in LDS as the destination rows lie in memory, then stored: whole aligned dwords inside a row
-//      segment, single bytes at its head and tail, so no byte outside the destination view is written
+// both passes of both transforms, so the transform needs no LDS transposes and no barriers.  The phases, each a helper below that
+// the three kernels share (the LDS arrays are the kernel's own and come as pointers; every barrier stands in the kernel):
+//   A  stage_rows, load_quant, load_tone: the source row segments under the tile into LDS as aligned dwords (the misalignment of a
+//      row kept per row, as clip_prepare_kernel does), the quantisation tables and the frame's tone table
+//   B  build_planes: bytes (through the tone) -> Y, Cb, Cr byte planes in LDS, padded by replication, chroma averaged for 4:2:0
+//   C  walk_blocks, codec_block: per block forward DCT, quantise, (stats), dequantise, inverse DCT; the reconstructed bytes back into
+//      the block's place; stats_to_global
+//   D  planes_to_rgb, store_rows: planes -> RGB bytes laid out in LDS as the destination rows lie in memory, then stored: whole
+//      aligned dwords inside a row segment, single bytes at its head and tail, so no byte outside the destination view is written
 // A block outside the padded image is not computed.  Every output byte is a pure function of its MCU: the result does not depend on
 // the tile or the grid.  Stats are integer sums (LDS and global integer atomics): exact in any order.  No allocation, no
 // synchronisation with the host.
@@ -40,14 +42,25 @@ constexpr int kTW = 128;                       // tile width in pixels
 constexpr int kSW = (kTW * 3 + 8) / 4;         // dwords per staged row: the segment plus up to 3 bytes of misalignment, whole dwords
 constexpr int kCodecThreads = 192;
 
+template <bool S420>
+struct CodecGeo {
+  static constexpr int TH = S420 ? 64 : 32;                                // tile rows
+  static constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;  // the chroma planes of a tile
+  static constexpr int M = S420 ? 16 : 8;                                  // the MCU
+};
+
 struct CodecClipDev {                          // 56 bytes; FLK_PREP_MAX_CLIPS of them travel by value in the kernel argument
-  const uint8_t* src;
+  const uint8_t* src;                          // the clip's first frame, or its span's (a multiple of gop: frame t of it is intra iff t % gop == 0)
   uint8_t* dst;
   long long pitch_t, dpitch_t;                 // bytes between frames
   int pitch_h, dpitch_h;                       // bytes between rows
-  int T, Hs, Ws;
+  int count, Hs, Ws;                           // frames of the clip, or of the span
   int ntx;                                     // tiles along W
 };
+struct CodecMcClipDev : CodecClipDev {         // 64 bytes
+  long long ws_off;                            // the clip's plane sets within the workspace: [GOP][2][Y, Cb, Cr]
+};
+static_assert(sizeof(CodecClipDev) == 56 && sizeof(CodecMcClipDev) == 64, "64 and 48 clips per launch rest on these sizes");
 struct CodecLaunch {
   const int* idx;                              // device int32 [nclip][gridDim.y] or null: source frame of every output frame
   const uint8_t* tone;                         // device uint8 [nclip][gridDim.y][256][3] or null
@@ -106,17 +119,33 @@ __device__ __forceinline__ void idct8(int& c0, int& c1, int& c2, int& c3, int& c
   c3 = descale(t13 + t0, SHIFT); c4 = descale(t13 - t0, SHIFT);
 }
 
-// an 8x8 block of a byte plane (8-byte aligned rows `pitch` bytes apart) through the transform pair, in place.  qt / rq: the block's
-// quantisation table and the reciprocals of 8 Q (a first guess of the quotient only: the quotient is corrected to the exact one)
-__device__ __forceinline__ void codec_block(uint8_t* blk, int pitch, const int* qt, const float* rq, int& nz, int& mag) {
+struct CodecQuant {
+  const int (*qt)[64];                         // luma, chroma: an intra block's table
+  const float (*rq)[64];                       // the reciprocals of 8 Q
+  int Qp;                                      // a P-frame's flat step
+  float rqp;                                   // the reciprocal of 8 Qp
+};
+
+// An 8x8 block of a byte plane (8-byte aligned rows `pitch` bytes apart) through the transform pair; `rec` is replaced in place.
+// Intra: the block of rec itself, minus 128, quantised by the table qt (rounding offset half a step), plus 128.
+// INTER, a P-frame's block: the residual of `cur` against the co-located block of the previous reconstruction `rec`, ONE flat step Qp
+// (rounding offset a quarter of a step), added back onto the reference.  The reference bytes are read a second time for that add
+// and not kept live: the kernels sit at 256 VGPRs.
+// rq / rqp are a first guess of the quotient only: the quotient is corrected to the exact one.
+template <bool INTER>
+__device__ __forceinline__ void codec_block(const uint8_t* cur, uint8_t* rec, int pitch, const int* qt, const float* rq, int Qp, float rqp,
+                                            int& nz, int& mag) {
+  auto byte = [](unsigned x, int k) { return (int)((x >> (8 * k)) & 255u); };
   int v[64];
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
-    const uint2 w = *(const uint2*)(blk + r * pitch);
+    const uint2 w = *(const uint2*)((INTER ? cur : rec) + r * pitch);
+    uint2 u = {0u, 0u};
+    if constexpr (INTER) u = *(const uint2*)(rec + r * pitch);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      v[r * 8 + k] = (int)((w.x >> (8 * k)) & 255u) - 128;
-      v[r * 8 + 4 + k] = (int)((w.y >> (8 * k)) & 255u) - 128;
+      v[r * 8 + k] = byte(w.x, k) - (INTER ? byte(u.x, k) : 128);
+      v[r * 8 + 4 + k] = byte(w.y, k) - (INTER ? byte(u.y, k) : 128);
     }
   }
 #pragma unroll
@@ -125,9 +154,9 @@ __device__ __forceinline__ void codec_block(uint8_t* blk, int pitch, const int* 
   for (int c = 0; c < 8; ++c) fdct8<false, 15>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
 #pragma unroll
   for (int k = 0; k < 64; ++k) {
-    const int Q = qt[k], d = Q << 3, f = v[k];
-    const int n = abs(f) + (d >> 1);                   // < 2^15: exact in fp32
-    int lev = (int)((float)n * rq[k]);                 // within 1 of n / d
+    const int Q = INTER ? Qp : qt[k], d = Q << 3, f = v[k];
+    const int n = abs(f) + (INTER ? d >> 2 : d >> 1);  // < 2^15 (a residual: <= 16320 + 510): exact in fp32
+    int lev = (int)((float)n * (INTER ? rqp : rq[k])); // within 1 of n / d
     const int rem = n - lev * d;
     lev += rem >= d ? 1 : (rem < 0 ? -1 : 0);          // the exact quotient
     nz += lev != 0;
@@ -139,13 +168,15 @@ __device__ __forceinline__ void codec_block(uint8_t* blk, int pitch, const int* 
 #pragma unroll
   for (int r = 0; r < 8; ++r) {
     idct8<18>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+    uint2 u = {0u, 0u};
+    if constexpr (INTER) u = *(const uint2*)(rec + r * pitch);
     uint2 w = {0u, 0u};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      w.x |= (unsigned)clamp255(v[r * 8 + k] + 128) << (8 * k);
-      w.y |= (unsigned)clamp255(v[r * 8 + 4 + k] + 128) << (8 * k);
+      w.x |= (unsigned)clamp255(v[r * 8 + k] + (INTER ? byte(u.x, k) : 128)) << (8 * k);
+      w.y |= (unsigned)clamp255(v[r * 8 + 4 + k] + (INTER ? byte(u.y, k) : 128)) << (8 * k);
     }
-    *(uint2*)(blk + r * pitch) = w;
+    *(uint2*)(rec + r * pitch) = w;
   }
 }
 
@@ -155,136 +186,184 @@ __device__ __forceinline__ void rgb_to_ycc(int R, int G, int B, int& Y, int& Cb,
   Cr = (32768 * R - 27439 * G - 5329 * B + 8388608 + 32767) >> 16;
 }
 
+// the tile of a workgroup
+struct CodecTile {
+  int y0, x0;                                  // its first row and column
+  int nrows, ncols;                            // its part of the image (>= 1 each)
+  int prow, pcol;                              // ... of the padded image: whole MCUs
+  int nbytes;                                  // of a row segment
+  int Hpad, Wpad;                              // the padded image
+};
+
+// tile b of a frame of Hs x Ws with ntx tiles along W; false: b is past the frame's tiles (a clip smaller than the largest of the launch)
 template <bool S420>
-__global__ __launch_bounds__(kCodecThreads) void codec_roundtrip_kernel(const CodecLaunch p) {
-  constexpr int TH = S420 ? 64 : 32;                   // tile rows
-  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;      // the chroma planes of a tile
-  __shared__ unsigned stage[TH * kSW];                 // source row segments (A, B), then the destination's (D)
-  __shared__ __attribute__((aligned(8))) uint8_t Yp[TH * kTW];
-  __shared__ __attribute__((aligned(8))) uint8_t Cbp[CH * CW];
-  __shared__ __attribute__((aligned(8))) uint8_t Crp[CH * CW];
-  __shared__ uint8_t tone_lds[768];
-  __shared__ int mis_of[TH];
-  __shared__ int qt[2][64];
-  __shared__ float rq[2][64];
-  __shared__ int red[2];
+__device__ __forceinline__ bool codec_tile(int Hs, int Ws, int ntx, unsigned b, CodecTile& g) {
+  constexpr int TH = CodecGeo<S420>::TH, M = CodecGeo<S420>::M;
+  g.Hpad = (Hs + M - 1) / M * M;
+  g.Wpad = (Ws + M - 1) / M * M;
+  const int nty = (g.Hpad + TH - 1) / TH;
+  if ((int)b >= ntx * nty) return false;
+  const int ty = b / ntx, tx = b - ty * ntx;
+  g.y0 = ty * TH;
+  g.x0 = tx * kTW;
+  g.nrows = min(TH, Hs - g.y0);
+  g.ncols = min(kTW, Ws - g.x0);
+  g.prow = min(TH, g.Hpad - g.y0);
+  g.pcol = min(kTW, g.Wpad - g.x0);
+  g.nbytes = g.ncols * 3;
+  return true;
+}
 
-  const CodecClipDev& c = p.clip[blockIdx.z];
-  constexpr int M = S420 ? 16 : 8;
-  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
-  const int nty = (Hpad + TH - 1) / TH;
-  if ((int)blockIdx.x >= c.ntx * nty) return;          // uniform over the workgroup: a clip smaller than the largest of the launch
-  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
-  const int y0 = ty * TH, x0 = tx * kTW;
-  const int t = blockIdx.y, tid = threadIdx.x;
-  const size_t kt = (size_t)blockIdx.z * gridDim.y + t;
-  const int fsrc = p.idx ? min(max(p.idx[kt], 0), c.T - 1) : min(t, c.T - 1);
-  const uint8_t* frame = c.src + (long long)fsrc * c.pitch_t;
-  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);        // the tile's part of the image (>= 1 each)
-  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);         // ... of the padded image: whole MCUs
-  const int nbytes = ncols * 3;
+// the tile's segment of row r of a frame whose rows lie pitch_h bytes apart
+template <class B>
+__device__ __forceinline__ B* tile_row(B* frame, int pitch_h, const CodecTile& g, int r) {
+  return frame + (long long)(g.y0 + r) * pitch_h + (long long)g.x0 * 3;
+}
 
-  // ---- A: tables, then the source row segments as aligned dwords ----
+struct CodecPlanes {                           // one plane set of a tile in LDS: rows of kTW (Y) and CodecGeo::CW (Cb, Cr) bytes
+  uint8_t *Y, *Cb, *Cr;
+};
+
+// ---- A: the tables, and the source row segments as aligned dwords ----
+__device__ __forceinline__ void load_quant(const unsigned short (&q)[2][64], int (*qt)[64], float (*rq)[64]) {
+  const int tid = threadIdx.x;
   if (tid < 128) {
-    const int Q = p.q[tid >> 6][tid & 63];
+    const int Q = q[tid >> 6][tid & 63];
     qt[tid >> 6][tid & 63] = Q;
     rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
   }
-  if (tid < 2) red[tid] = 0;
-  if (p.tone) {
-    const uint8_t* g = p.tone + kt * 768;
-    for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
+}
+
+// tone: the launch's tables or null; kt: the frame's row of them
+__device__ __forceinline__ void load_tone(const uint8_t* tone, size_t kt, uint8_t* tone_lds) {
+  if (tone) {
+    const uint8_t* g = tone + kt * 768;
+    for (int k = threadIdx.x; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
   }
-  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+}
+
+__device__ __forceinline__ void stage_rows(const uint8_t* frame, int pitch_h, const CodecTile& g, unsigned* stage, int* mis_of) {
+  for (int k = threadIdx.x; k < g.nrows * kSW; k += kCodecThreads) {
     const int r = k / kSW, w = k - r * kSW;
-    const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
+    const uint8_t* row = tile_row(frame, pitch_h, g, r);
     const int mis = (int)((size_t)row & 3);
     if (w == 0) mis_of[r] = mis;
-    if (4 * w < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * w);      // never beyond the dword of the segment's last byte
+    if (4 * w < mis + g.nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * w);    // never beyond the dword of the segment's last byte
   }
-  __syncthreads();
+}
 
-  // ---- B: bytes -> planes over the padded part of the tile (the last column / row repeated) ----
+// ---- B: staged bytes (through the tone) -> the plane set o over the padded part of the tile (the last column / row repeated) ----
+template <bool S420>
+__device__ __forceinline__ void build_planes(const unsigned* stage, const int* mis_of, const uint8_t* tone_lds, bool toned, const CodecTile& g,
+                                             const CodecPlanes& o) {
+  constexpr int CW = CodecGeo<S420>::CW;
+  const int tid = threadIdx.x;
   const uint8_t* sb = (const uint8_t*)stage;
-  const bool toned = p.tone != nullptr;
   auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
-    const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
+    const int rs = min(r, g.nrows - 1), cs = min(col, g.ncols - 1);
     const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
     int R = px[0], G = px[1], B = px[2];
     if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
     rgb_to_ycc(R, G, B, Y, Cb, Cr);
   };
   if constexpr (S420) {
-    const int qc = pcol >> 1;
-    for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
+    const int qc = g.pcol >> 1;
+    for (int k = tid; k < (g.prow >> 1) * qc; k += kCodecThreads) {
       const int r2 = k / qc, c2 = k - r2 * qc;
       int sb_ = 0, sr_ = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         int Y, Cb, Cr;
         ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
-        Yp[(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
+        o.Y[(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
         sb_ += Cb; sr_ += Cr;
       }
       const int bias = 1 + (c2 & 1);                  // x0 / 2 is even: the tile's column parity is the plane's
-      Cbp[r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
-      Crp[r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
+      o.Cb[r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
+      o.Cr[r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
     }
   } else {
-    for (int k = tid; k < prow * pcol; k += kCodecThreads) {
-      const int r = k / pcol, col = k - r * pcol;
+    for (int k = tid; k < g.prow * g.pcol; k += kCodecThreads) {
+      const int r = k / g.pcol, col = k - r * g.pcol;
       int Y, Cb, Cr;
       ycc(r, col, Y, Cb, Cr);
-      Yp[r * kTW + col] = (uint8_t)Y;
-      Cbp[r * CW + col] = (uint8_t)Cb;
-      Crp[r * CW + col] = (uint8_t)Cr;
+      o.Y[r * kTW + col] = (uint8_t)Y;
+      o.Cb[r * CW + col] = (uint8_t)Cb;
+      o.Cr[r * CW + col] = (uint8_t)Cr;
     }
   }
-  __syncthreads();
+}
 
-  // ---- C: one block per thread: luma blocks first, then Cb, then Cr ----
-  {
-    constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
-    const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
-    int nz = 0, mag = 0;
-    for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
-      if (b < NBY) {
-        const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
-        if (by * 8 < prow && bx * 8 < pcol) codec_block(Yp + by * 8 * kTW + bx * 8, kTW, qt[0], rq[0], nz, mag);
-      } else {
-        const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
-        const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
-        if (by * 8 < cprow && bx * 8 < cpcol) codec_block((pl ? Crp : Cbp) + by * 8 * CW + bx * 8, CW, qt[1], rq[1], nz, mag);
-      }
+// ---- C: one block per thread: luma blocks first, then Cb, then Cr; a block outside the padded image is not computed.  An intra
+// frame is transformed in place in `rec`; a P-frame's planes `cur` are coded against `rec`, which becomes the reconstruction.
+// Which of the two: F, or at kFrameEither the argument `intra` (uniform over the workgroup).  Stats into red[] ----
+enum CodecFrame { kFrameIntra, kFrameP, kFrameEither };
+
+template <bool S420, CodecFrame F>
+__device__ __forceinline__ void walk_blocks(bool intra, const CodecPlanes& cur, const CodecPlanes& rec, const CodecTile& g, const CodecQuant& q,
+                                            bool stats, int* red) {
+  constexpr int TH = CodecGeo<S420>::TH, CW = CodecGeo<S420>::CW, CH = CodecGeo<S420>::CH;
+  constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
+  const int cprow = S420 ? g.prow >> 1 : g.prow, cpcol = S420 ? g.pcol >> 1 : g.pcol;
+  int nz = 0, mag = 0;
+  auto block = [&](const uint8_t* c, uint8_t* r, int pitch, int tab) {
+    if constexpr (F == kFrameEither) {
+      if (intra) codec_block<false>(c, r, pitch, q.qt[tab], q.rq[tab], q.Qp, q.rqp, nz, mag);
+      else codec_block<true>(c, r, pitch, q.qt[tab], q.rq[tab], q.Qp, q.rqp, nz, mag);
+    } else {
+      codec_block<F == kFrameP>(c, r, pitch, q.qt[tab], q.rq[tab], q.Qp, q.rqp, nz, mag);
     }
-    if (p.stats && (nz | mag)) {
-      atomicAdd(&red[0], nz);
-      atomicAdd(&red[1], mag);
+  };
+  for (int b = threadIdx.x; b < NBY + 2 * NBC; b += kCodecThreads) {
+    if (b < NBY) {
+      const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
+      const int o = by * 8 * kTW + bx * 8;
+      if (by * 8 < g.prow && bx * 8 < g.pcol) block(cur.Y + o, rec.Y + o, kTW, 0);
+    } else {
+      const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
+      const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
+      const int o = by * 8 * CW + bx * 8;
+      if (by * 8 < cprow && bx * 8 < cpcol) block((pl ? cur.Cr : cur.Cb) + o, (pl ? rec.Cr : rec.Cb) + o, CW, 1);
     }
   }
-  __syncthreads();
-  if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
+  if (stats && (nz | mag)) {
+    atomicAdd(&red[0], nz);
+    atomicAdd(&red[1], mag);
+  }
+}
 
-  // ---- D: planes -> RGB bytes laid out as the destination rows lie in memory, then stored ----
-  uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
+// after the barrier that follows walk_blocks: the workgroup's sums into row kt of the launch's stats (integer atomics: exact in any order)
+__device__ __forceinline__ void stats_to_global(int* stats, size_t kt, const int* red) {
+  const int tid = threadIdx.x;
+  if (stats && tid < 2 && red[tid]) atomicAdd(stats + kt * 2 + tid, red[tid]);
+}
+
+// ---- D: the plane set s -> RGB bytes in `stage`, laid out as the destination rows lie in memory; after a barrier, stored ----
+template <bool S420>
+__device__ __forceinline__ void planes_to_rgb(const CodecPlanes& s, const uint8_t* dframe, int dpitch_h, const CodecTile& g, unsigned* stage) {
+  constexpr int CW = CodecGeo<S420>::CW;
   uint8_t* ob = (uint8_t*)stage;
-  for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
-    const int r = k / ncols, col = k - r * ncols;
-    const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
-    const int Y = Yp[r * kTW + col];
+  for (int k = threadIdx.x; k < g.nrows * g.ncols; k += kCodecThreads) {
+    const int r = k / g.ncols, col = k - r * g.ncols;
+    const int dm = (int)((size_t)tile_row(dframe, dpitch_h, g, r) & 3);
+    const int Y = s.Y[r * kTW + col];
     const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
-    const int cb = (int)Cbp[ci] - 128, cr = (int)Crp[ci] - 128;
+    const int cb = (int)s.Cb[ci] - 128, cr = (int)s.Cr[ci] - 128;
     uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
     o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
     o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
     o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
   }
-  __syncthreads();
-  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
+}
+
+// whole aligned dwords inside a row segment, single bytes at its head and tail: no byte outside the destination view is written
+__device__ __forceinline__ void store_rows(const unsigned* stage, uint8_t* dframe, int dpitch_h, const CodecTile& g) {
+  const uint8_t* ob = (const uint8_t*)stage;
+  for (int k = threadIdx.x; k < g.nrows * kSW; k += kCodecThreads) {
     const int r = k / kSW, w = k - r * kSW;
-    uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
+    uint8_t* row = tile_row(dframe, dpitch_h, g, r);
     const int dm = (int)((size_t)row & 3);
-    const int lo = dm, hi = dm + nbytes;               // the segment's bytes within the aligned run that starts at row - dm
+    const int lo = dm, hi = dm + g.nbytes;             // the segment's bytes within the aligned run that starts at row - dm
     if (4 * w >= hi || 4 * w + 4 <= lo) continue;
     if (4 * w >= lo && 4 * w + 4 <= hi) {
       *(unsigned*)(row - dm + 4 * w) = stage[k];
@@ -296,230 +375,101 @@ __global__ __launch_bounds__(kCodecThreads) void codec_roundtrip_kernel(const Co
   }
 }
 
-// ---- inter-frame prediction: closed GOPs of one intra frame and zero-motion P-frames (DESIGN.md 10.9) ----
-// A P-frame's 8x8 block: the residual against the co-located block of the previous reconstruction through the same transform pair
-// and ONE flat quantiser step Qp (rounding offset a quarter of a step), added back onto the reference, which it replaces in place.
-// rqp: the reciprocal of 8 Qp, a first guess of the quotient as in codec_block.
-__device__ __forceinline__ void codec_block_inter(const uint8_t* cur, uint8_t* ref, int pitch, int Qp, float rqp, int& nz, int& mag) {
-  int v[64];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const uint2 w = *(const uint2*)(cur + r * pitch), u = *(const uint2*)(ref + r * pitch);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      v[r * 8 + k] = (int)((w.x >> (8 * k)) & 255u) - (int)((u.x >> (8 * k)) & 255u);
-      v[r * 8 + 4 + k] = (int)((w.y >> (8 * k)) & 255u) - (int)((u.y >> (8 * k)) & 255u);
-    }
-  }
-#pragma unroll
-  for (int r = 0; r < 8; ++r) fdct8<true, 11>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) fdct8<false, 15>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
-  const int d = Qp << 3;
-#pragma unroll
-  for (int k = 0; k < 64; ++k) {
-    const int f = v[k];
-    const int n = abs(f) + (d >> 2);                   // <= 16320 + 510 < 2^15: exact in fp32
-    int lev = (int)((float)n * rqp);                   // within 1 of n / d
-    const int rem = n - lev * d;
-    lev += rem >= d ? 1 : (rem < 0 ? -1 : 0);          // the exact quotient
-    nz += lev != 0;
-    mag += lev;
-    v[k] = (f < 0 ? -lev : lev) * Qp;
-  }
-#pragma unroll
-  for (int c = 0; c < 8; ++c) idct8<11>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    idct8<18>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
-    const uint2 u = *(const uint2*)(ref + r * pitch);
-    uint2 w = {0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      w.x |= (unsigned)clamp255(v[r * 8 + k] + (int)((u.x >> (8 * k)) & 255u)) << (8 * k);
-      w.y |= (unsigned)clamp255(v[r * 8 + 4 + k] + (int)((u.y >> (8 * k)) & 255u)) << (8 * k);
-    }
-    *(uint2*)(ref + r * pitch) = w;
-  }
+template <bool S420>
+__global__ __launch_bounds__(kCodecThreads) void codec_roundtrip_kernel(const CodecLaunch p) {
+  using G = CodecGeo<S420>;
+  __shared__ unsigned stage[G::TH * kSW];              // source row segments (A, B), then the destination's (D)
+  __shared__ __attribute__((aligned(8))) uint8_t Yp[G::TH * kTW];
+  __shared__ __attribute__((aligned(8))) uint8_t Cbp[G::CH * G::CW];
+  __shared__ __attribute__((aligned(8))) uint8_t Crp[G::CH * G::CW];
+  __shared__ uint8_t tone_lds[768];
+  __shared__ int mis_of[G::TH];
+  __shared__ int qt[2][64];
+  __shared__ float rq[2][64];
+  __shared__ int red[2];
+
+  const CodecClipDev& c = p.clip[blockIdx.z];
+  CodecTile g;
+  if (!codec_tile<S420>(c.Hs, c.Ws, c.ntx, blockIdx.x, g)) return;         // uniform over the workgroup
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const size_t kt = (size_t)blockIdx.z * gridDim.y + t;
+  const int fsrc = p.idx ? min(max(p.idx[kt], 0), c.count - 1) : min(t, c.count - 1);
+  const CodecPlanes set = {Yp, Cbp, Crp};
+
+  // A
+  load_quant(p.q, qt, rq);
+  if (tid < 2) red[tid] = 0;
+  load_tone(p.tone, kt, tone_lds);
+  stage_rows(c.src + (long long)fsrc * c.pitch_t, c.pitch_h, g, stage, mis_of);
+  __syncthreads();
+  // B
+  build_planes<S420>(stage, mis_of, tone_lds, p.tone != nullptr, g, set);
+  __syncthreads();
+  // C: in place
+  walk_blocks<S420, kFrameIntra>(true, set, set, g, {qt, rq, 0, 0.0f}, p.stats != nullptr, red);
+  __syncthreads();
+  stats_to_global(p.stats, kt, red);
+  // D
+  uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
+  planes_to_rgb<S420>(set, dframe, c.dpitch_h, g, stage);
+  __syncthreads();
+  store_rows(stage, dframe, c.dpitch_h, g);
 }
 
-struct CodecGopClipDev {                       // 56 bytes, as CodecClipDev: the span's first frame is folded into src, so T is not needed
-  const uint8_t* src;                          // the span's first frame (a multiple of gop: its frame t is intra iff t % gop == 0)
-  uint8_t* dst;
-  long long pitch_t, dpitch_t;
-  int pitch_h, dpitch_h;
-  int count, Hs, Ws;                           // frames of the span
-  int ntx;
-};
+// ---- inter-frame prediction: closed GOPs of one intra frame and zero-motion P-frames (DESIGN.md 10.9) ----
 struct CodecGopLaunch {
   const uint8_t* tone;                         // device uint8 [nclip][T_max][256][3] or null
   int* stats;                                  // device int32 [nclip][T_max][2] or null (zeroed by the host entry)
   int gop, T_max;
   int qp, pad_;                                // the P-frames' step
   unsigned short q[2][64];
-  CodecGopClipDev clip[FLK_PREP_MAX_CLIPS];
+  CodecClipDev clip[FLK_PREP_MAX_CLIPS];       // the span's first frame is folded into src
 };
 static_assert(sizeof(CodecGopLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
 
 // Workgroup = (tile, GOP of the span, clip): it walks its GOP's frames in order, the reconstructed planes of the previous frame kept in
 // LDS (plane set 1; set 0 takes a P-frame's own planes).  Zero motion: an output byte depends on its own MCU's history within the GOP
 // alone, so there is no workspace in memory and no dependency between workgroups.  Per frame the phases are those of
-// codec_roundtrip_kernel (whose device code is left as it is, hence the restatement); C reads set 0 and set 1 and writes set 1.
+// codec_roundtrip_kernel; C reads set 0 and set 1 and writes set 1.
 template <bool S420>
 __global__ __launch_bounds__(kCodecThreads) void codec_gop_kernel(const CodecGopLaunch p) {
-  constexpr int TH = S420 ? 64 : 32;
-  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;
-  __shared__ unsigned stage[TH * kSW];
-  __shared__ __attribute__((aligned(8))) uint8_t Yp[2][TH * kTW];
-  __shared__ __attribute__((aligned(8))) uint8_t Cbp[2][CH * CW];
-  __shared__ __attribute__((aligned(8))) uint8_t Crp[2][CH * CW];
+  using G = CodecGeo<S420>;
+  __shared__ unsigned stage[G::TH * kSW];
+  __shared__ __attribute__((aligned(8))) uint8_t Yp[2][G::TH * kTW];
+  __shared__ __attribute__((aligned(8))) uint8_t Cbp[2][G::CH * G::CW];
+  __shared__ __attribute__((aligned(8))) uint8_t Crp[2][G::CH * G::CW];
   __shared__ uint8_t tone_lds[768];
-  __shared__ int mis_of[TH];
+  __shared__ int mis_of[G::TH];
   __shared__ int qt[2][64];
   __shared__ float rq[2][64];
   __shared__ int red[2];
 
-  const CodecGopClipDev& c = p.clip[blockIdx.z];
-  constexpr int M = S420 ? 16 : 8;
-  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
-  const int nty = (Hpad + TH - 1) / TH;
+  const CodecClipDev& c = p.clip[blockIdx.z];
+  CodecTile g;
   const int t0 = (int)blockIdx.y * p.gop;              // gridDim.y * gop <= 65535 + gop: no overflow
-  if ((int)blockIdx.x >= c.ntx * nty || t0 >= c.count) return;              // uniform over the workgroup
+  if (!codec_tile<S420>(c.Hs, c.Ws, c.ntx, blockIdx.x, g) || t0 >= c.count) return;          // uniform over the workgroup
   const int t1 = min(t0 + p.gop, c.count);
-  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
-  const int y0 = ty * TH, x0 = tx * kTW;
   const int tid = threadIdx.x;
-  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);
-  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);
-  const int nbytes = ncols * 3;
-  const int Qp = p.qp;
-  const float rqp = 1.0f / (float)(Qp << 3);
-  const bool toned = p.tone != nullptr;
+  const CodecQuant quant = {qt, rq, p.qp, 1.0f / (float)(p.qp << 3)};
+  const CodecPlanes own = {Yp[0], Cbp[0], Crp[0]}, rec = {Yp[1], Cbp[1], Crp[1]};
 
-  if (tid < 128) {
-    const int Q = p.q[tid >> 6][tid & 63];
-    qt[tid >> 6][tid & 63] = Q;
-    rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
-  }
-
+  load_quant(p.q, qt, rq);
   for (int t = t0; t < t1; ++t) {
     const bool intra = t == t0;
-    const int w = intra ? 1 : 0;                       // the plane set phase B fills: an intra frame is transformed in place in set 1
     const size_t kt = (size_t)blockIdx.z * p.T_max + t;
-    const uint8_t* frame = c.src + (long long)t * c.pitch_t;
-
-    // ---- A ----
     if (tid < 2) red[tid] = 0;
-    if (toned) {
-      const uint8_t* g = p.tone + kt * 768;
-      for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
-    }
-    for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
-      const int r = k / kSW, wd = k - r * kSW;
-      const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
-      const int mis = (int)((size_t)row & 3);
-      if (wd == 0) mis_of[r] = mis;
-      if (4 * wd < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * wd);
-    }
+    load_tone(p.tone, kt, tone_lds);
+    stage_rows(c.src + (long long)t * c.pitch_t, c.pitch_h, g, stage, mis_of);
     __syncthreads();
-
-    // ---- B ----
-    const uint8_t* sb = (const uint8_t*)stage;
-    auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
-      const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
-      const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
-      int R = px[0], G = px[1], B = px[2];
-      if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
-      rgb_to_ycc(R, G, B, Y, Cb, Cr);
-    };
-    if constexpr (S420) {
-      const int qc = pcol >> 1;
-      for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
-        const int r2 = k / qc, c2 = k - r2 * qc;
-        int sb_ = 0, sr_ = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int Y, Cb, Cr;
-          ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
-          Yp[w][(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
-          sb_ += Cb; sr_ += Cr;
-        }
-        const int bias = 1 + (c2 & 1);
-        Cbp[w][r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
-        Crp[w][r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
-      }
-    } else {
-      for (int k = tid; k < prow * pcol; k += kCodecThreads) {
-        const int r = k / pcol, col = k - r * pcol;
-        int Y, Cb, Cr;
-        ycc(r, col, Y, Cb, Cr);
-        Yp[w][r * kTW + col] = (uint8_t)Y;
-        Cbp[w][r * CW + col] = (uint8_t)Cb;
-        Crp[w][r * CW + col] = (uint8_t)Cr;
-      }
-    }
+    build_planes<S420>(stage, mis_of, tone_lds, p.tone != nullptr, g, intra ? rec : own);     // an intra frame is transformed in place in set 1
     __syncthreads();
-
-    // ---- C: one block per thread; every thread keeps its blocks through the GOP ----
-    {
-      constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
-      const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
-      int nz = 0, mag = 0;
-      for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
-        if (b < NBY) {
-          const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
-          const int o = by * 8 * kTW + bx * 8;
-          if (by * 8 < prow && bx * 8 < pcol) {
-            if (intra) codec_block(Yp[1] + o, kTW, qt[0], rq[0], nz, mag);
-            else codec_block_inter(Yp[0] + o, Yp[1] + o, kTW, Qp, rqp, nz, mag);
-          }
-        } else {
-          const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
-          const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
-          const int o = by * 8 * CW + bx * 8;
-          if (by * 8 < cprow && bx * 8 < cpcol) {
-            if (intra) codec_block((pl ? Crp[1] : Cbp[1]) + o, CW, qt[1], rq[1], nz, mag);
-            else codec_block_inter((pl ? Crp[0] : Cbp[0]) + o, (pl ? Crp[1] : Cbp[1]) + o, CW, Qp, rqp, nz, mag);
-          }
-        }
-      }
-      if (p.stats && (nz | mag)) {
-        atomicAdd(&red[0], nz);
-        atomicAdd(&red[1], mag);
-      }
-    }
+    walk_blocks<S420, kFrameEither>(intra, own, rec, g, quant, p.stats != nullptr, red);      // every thread keeps its blocks through the GOP
     __syncthreads();
-    if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
-
-    // ---- D: the reconstruction (set 1) -> RGB bytes as the destination rows lie in memory, then stored ----
+    stats_to_global(p.stats, kt, red);
     uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
-    uint8_t* ob = (uint8_t*)stage;
-    for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
-      const int r = k / ncols, col = k - r * ncols;
-      const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
-      const int Y = Yp[1][r * kTW + col];
-      const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
-      const int cb = (int)Cbp[1][ci] - 128, cr = (int)Crp[1][ci] - 128;
-      uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
-      o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
-      o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-      o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
-    }
+    planes_to_rgb<S420>(rec, dframe, c.dpitch_h, g, stage);
     __syncthreads();
-    for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
-      const int r = k / kSW, wd = k - r * kSW;
-      uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
-      const int dm = (int)((size_t)row & 3);
-      const int lo = dm, hi = dm + nbytes;
-      if (4 * wd >= hi || 4 * wd + 4 <= lo) continue;
-      if (4 * wd >= lo && 4 * wd + 4 <= hi) {
-        *(unsigned*)(row - dm + 4 * wd) = stage[k];
-      } else {
-#pragma unroll
-        for (int b = 0; b < 4; ++b)
-          if (4 * wd + b >= lo && 4 * wd + b < hi) (row - dm)[4 * wd + b] = ob[k * 4 + b];
-      }
-    }
+    store_rows(stage, dframe, c.dpitch_h, g);
     __syncthreads();                                   // the next frame stages into what this one stored from
   }
 }
@@ -535,15 +485,6 @@ constexpr int kHaloX = 16;                     // columns staged left and right 
 constexpr int kHP = kTW + 2 * kHaloX;          // bytes per staged reference row
 static_assert(kHaloX % 4 == 0 && kHaloX >= kMaxSearch && kHP % 4 == 0, "reference rows are staged as aligned dwords");
 
-struct CodecMcClipDev {                        // 64 bytes
-  const uint8_t* src;                          // the span's first frame, as in CodecGopClipDev
-  uint8_t* dst;
-  long long pitch_t, dpitch_t;
-  int pitch_h, dpitch_h;
-  int count, Hs, Ws;
-  int ntx;
-  long long ws_off;                            // the clip's plane sets within the workspace: [GOP][2][Y, Cb, Cr]
-};
 struct CodecMcLaunch {
   const uint8_t* tone;                         // device uint8 [nclip][T_max][256][3] or null; rows of the whole call, clip0 the launch's first
   int* stats;                                  // device int32 [nclip][T_max][2] or null (zeroed by the host entry)
@@ -574,8 +515,8 @@ __device__ __forceinline__ void mc_vector(unsigned key, int R, int& dy, int& dx)
 // prediction in set 1 (luma from the halo, chroma from the workspace); C turns set 1 into the reconstruction; D stores it.
 template <bool S420, bool INTRA>
 __global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLaunch p) {
-  constexpr int TH = S420 ? 64 : 32;
-  constexpr int CW = S420 ? kTW / 2 : kTW, CH = S420 ? TH / 2 : TH;
+  using G = CodecGeo<S420>;
+  constexpr int TH = G::TH, CW = G::CW, CH = G::CH;
   constexpr int NS = INTRA ? 1 : 2, S1 = NS - 1;       // S1: the set that ends as the reconstruction
   constexpr int NMB = (TH / 16) * (kTW / 16);
   static_assert((TH + 2 * kMaxSearch) * kHP <= TH * kSW * 4, "the staged reference takes the place of the staged source rows");
@@ -592,21 +533,14 @@ __global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLa
   __shared__ int mvl[NMB][2];
 
   const CodecMcClipDev& c = p.clip[blockIdx.z];
-  constexpr int M = S420 ? 16 : 8;
-  const int Hpad = (c.Hs + M - 1) / M * M, Wpad = (c.Ws + M - 1) / M * M;
-  const int nty = (Hpad + TH - 1) / TH;
+  CodecTile g;
   const int t = (int)blockIdx.y * p.gop + p.j;         // gridDim.y * gop <= 65535 + gop: no overflow
-  if ((int)blockIdx.x >= c.ntx * nty || t >= c.count) return;               // uniform over the workgroup
-  const int ty = blockIdx.x / c.ntx, tx = blockIdx.x - ty * c.ntx;
-  const int y0 = ty * TH, x0 = tx * kTW;
-  const int tid = threadIdx.x;
-  const int nrows = min(TH, c.Hs - y0), ncols = min(kTW, c.Ws - x0);
-  const int prow = min(TH, Hpad - y0), pcol = min(kTW, Wpad - x0);
+  if (!codec_tile<S420>(c.Hs, c.Ws, c.ntx, blockIdx.x, g) || t >= c.count) return;           // uniform over the workgroup
+  const int y0 = g.y0, x0 = g.x0, prow = g.prow, pcol = g.pcol, Hpad = g.Hpad, Wpad = g.Wpad;
   const int cprow = S420 ? prow >> 1 : prow, cpcol = S420 ? pcol >> 1 : pcol;
-  const int nbytes = ncols * 3;
-  const bool toned = p.tone != nullptr;
+  const int tid = threadIdx.x;
   const size_t kt = (size_t)(p.clip0 + blockIdx.z) * p.T_max + t;
-  const uint8_t* frame = c.src + (long long)t * c.pitch_t;
+  const CodecPlanes own = {Yp[0], Cbp[0], Crp[0]}, rec = {Yp[S1], Cbp[S1], Crp[S1]};
   // the two plane sets of this (clip, GOP): this launch writes set j & 1 and reads the other
   const int Hc = S420 ? Hpad >> 1 : Hpad, Wc = S420 ? Wpad >> 1 : Wpad;
   const long long ysz = (long long)Hpad * Wpad, csz = (long long)Hc * Wc, setsz = ysz + 2 * csz;
@@ -614,64 +548,14 @@ __global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLa
   uint8_t* wcur = wsg + (p.j & 1) * setsz;
   const uint8_t* wref = wsg + ((p.j & 1) ^ 1) * setsz;
 
-  // ---- A ----
-  if (INTRA && tid < 128) {
-    const int Q = p.q[tid >> 6][tid & 63];
-    qt[tid >> 6][tid & 63] = Q;
-    rq[tid >> 6][tid & 63] = 1.0f / (float)(Q << 3);
-  }
+  // ---- A, and B: the frame's own planes into set 0 ----
+  if constexpr (INTRA) load_quant(p.q, qt, rq);
   if (tid < 2) red[tid] = 0;
   if (tid < NMB) best[tid] = 0xffffffffu;
-  if (toned) {
-    const uint8_t* g = p.tone + kt * 768;
-    for (int k = tid; k < 768; k += kCodecThreads) tone_lds[k] = g[k];
-  }
-  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
-    const int r = k / kSW, wd = k - r * kSW;
-    const uint8_t* row = frame + (long long)(y0 + r) * c.pitch_h + (long long)x0 * 3;
-    const int mis = (int)((size_t)row & 3);
-    if (wd == 0) mis_of[r] = mis;
-    if (4 * wd < mis + nbytes) stage[k] = *(const unsigned*)(row - mis + 4 * wd);
-  }
+  load_tone(p.tone, kt, tone_lds);
+  stage_rows(c.src + (long long)t * c.pitch_t, c.pitch_h, g, stage, mis_of);
   __syncthreads();
-
-  // ---- B: the frame's own planes into set 0 ----
-  {
-    const uint8_t* sb = (const uint8_t*)stage;
-    auto ycc = [&](int r, int col, int& Y, int& Cb, int& Cr) {
-      const int rs = min(r, nrows - 1), cs = min(col, ncols - 1);
-      const uint8_t* px = sb + rs * (kSW * 4) + mis_of[rs] + cs * 3;
-      int R = px[0], G = px[1], B = px[2];
-      if (toned) { R = tone_lds[R * 3]; G = tone_lds[G * 3 + 1]; B = tone_lds[B * 3 + 2]; }
-      rgb_to_ycc(R, G, B, Y, Cb, Cr);
-    };
-    if constexpr (S420) {
-      const int qc = pcol >> 1;
-      for (int k = tid; k < (prow >> 1) * qc; k += kCodecThreads) {
-        const int r2 = k / qc, c2 = k - r2 * qc;
-        int sb_ = 0, sr_ = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          int Y, Cb, Cr;
-          ycc(2 * r2 + (j >> 1), 2 * c2 + (j & 1), Y, Cb, Cr);
-          Yp[0][(2 * r2 + (j >> 1)) * kTW + 2 * c2 + (j & 1)] = (uint8_t)Y;
-          sb_ += Cb; sr_ += Cr;
-        }
-        const int bias = 1 + (c2 & 1);
-        Cbp[0][r2 * CW + c2] = (uint8_t)((sb_ + bias) >> 2);
-        Crp[0][r2 * CW + c2] = (uint8_t)((sr_ + bias) >> 2);
-      }
-    } else {
-      for (int k = tid; k < prow * pcol; k += kCodecThreads) {
-        const int r = k / pcol, col = k - r * pcol;
-        int Y, Cb, Cr;
-        ycc(r, col, Y, Cb, Cr);
-        Yp[0][r * kTW + col] = (uint8_t)Y;
-        Cbp[0][r * CW + col] = (uint8_t)Cb;
-        Crp[0][r * CW + col] = (uint8_t)Cr;
-      }
-    }
-  }
+  build_planes<S420>(stage, mis_of, tone_lds, p.tone != nullptr, g, own);
   __syncthreads();
 
   if constexpr (!INTRA) {
@@ -792,37 +676,10 @@ __global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLa
     __syncthreads();
   }
 
-  // ---- C: one block per thread ----
-  {
-    constexpr int NBY = (TH / 8) * (kTW / 8), NBC = (CH / 8) * (CW / 8);
-    const int Qp = p.qp;
-    const float rqp = 1.0f / (float)(Qp << 3);
-    int nz = 0, mag = 0;
-    for (int b = tid; b < NBY + 2 * NBC; b += kCodecThreads) {
-      if (b < NBY) {
-        const int by = b / (kTW / 8), bx = b - by * (kTW / 8);
-        const int o = by * 8 * kTW + bx * 8;
-        if (by * 8 < prow && bx * 8 < pcol) {
-          if constexpr (INTRA) codec_block(Yp[0] + o, kTW, qt[0], rq[0], nz, mag);
-          else codec_block_inter(Yp[0] + o, Yp[S1] + o, kTW, Qp, rqp, nz, mag);
-        }
-      } else {
-        const int b2 = b - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
-        const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
-        const int o = by * 8 * CW + bx * 8;
-        if (by * 8 < cprow && bx * 8 < cpcol) {
-          if constexpr (INTRA) codec_block((pl ? Crp[0] : Cbp[0]) + o, CW, qt[1], rq[1], nz, mag);
-          else codec_block_inter((pl ? Crp[0] : Cbp[0]) + o, (pl ? Crp[S1] : Cbp[S1]) + o, CW, Qp, rqp, nz, mag);
-        }
-      }
-    }
-    if (p.stats && (nz | mag)) {
-      atomicAdd(&red[0], nz);
-      atomicAdd(&red[1], mag);
-    }
-  }
+  // ---- C: set S1 becomes the reconstruction ----
+  walk_blocks<S420, INTRA ? kFrameIntra : kFrameP>(INTRA, own, rec, g, {qt, rq, p.qp, 1.0f / (float)(p.qp << 3)}, p.stats != nullptr, red);
   __syncthreads();
-  if (p.stats && tid < 2 && red[tid]) atomicAdd(p.stats + kt * 2 + tid, red[tid]);
+  stats_to_global(p.stats, kt, red);
 
   // ---- D: the reconstruction to the workspace (whole dwords of the padded planes), and as RGB bytes to the destination ----
   {
@@ -840,33 +697,9 @@ __global__ __launch_bounds__(kCodecThreads) void codec_mc_kernel(const CodecMcLa
     }
   }
   uint8_t* dframe = c.dst + (long long)t * c.dpitch_t;
-  uint8_t* ob = (uint8_t*)stage;
-  for (int k = tid; k < nrows * ncols; k += kCodecThreads) {
-    const int r = k / ncols, col = k - r * ncols;
-    const int dm = (int)((size_t)(dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3) & 3);
-    const int Y = Yp[S1][r * kTW + col];
-    const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
-    const int cb = (int)Cbp[S1][ci] - 128, cr = (int)Crp[S1][ci] - 128;
-    uint8_t* o = ob + r * (kSW * 4) + dm + col * 3;
-    o[0] = (uint8_t)clamp255(Y + ((91881 * cr + 32768) >> 16));
-    o[1] = (uint8_t)clamp255(Y + ((-22554 * cb - 46802 * cr + 32768) >> 16));
-    o[2] = (uint8_t)clamp255(Y + ((116130 * cb + 32768) >> 16));
-  }
+  planes_to_rgb<S420>(rec, dframe, c.dpitch_h, g, stage);
   __syncthreads();
-  for (int k = tid; k < nrows * kSW; k += kCodecThreads) {
-    const int r = k / kSW, wd = k - r * kSW;
-    uint8_t* row = dframe + (long long)(y0 + r) * c.dpitch_h + (long long)x0 * 3;
-    const int dm = (int)((size_t)row & 3);
-    const int lo = dm, hi = dm + nbytes;
-    if (4 * wd >= hi || 4 * wd + 4 <= lo) continue;
-    if (4 * wd >= lo && 4 * wd + 4 <= hi) {
-      *(unsigned*)(row - dm + 4 * wd) = stage[k];
-    } else {
-#pragma unroll
-      for (int b = 0; b < 4; ++b)
-        if (4 * wd + b >= lo && 4 * wd + b < hi) (row - dm)[4 * wd + b] = ob[k * 4 + b];
-    }
-  }
+  store_rows(stage, dframe, c.dpitch_h, g);
 }
 
 }  // namespace
@@ -886,28 +719,43 @@ void flk_codec_tables_host(int quality, int32_t* qluma, int32_t* qchroma) {
   }
 }
 
+// the P-frames' quantiser step at `quality` (1..100): MPEG-2's flat non-intra 16 under the IJG scaling rule
+int flk_codec_inter_step_host(int quality) {
+  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
+  const int q = (16 * s + 50) / 100;
+  return q < 1 ? 1 : q > 255 ? 255 : q;
+}
+
+// the q[2][64] of a launch descriptor
+static void fill_quant(int quality, unsigned short (*q)[64]) {
+  int32_t ql[64], qc[64];
+  flk_codec_tables_host(quality, ql, qc);
+  for (int k = 0; k < 64; ++k) { q[0][k] = (unsigned short)ql[k]; q[1][k] = (unsigned short)qc[k]; }
+}
+
+static long long padded(long long n, bool s420) { return s420 ? (n + 15) / 16 * 16 : (n + 7) / 8 * 8; }    // to whole MCUs
+
+// the descriptor of the `count` frames of clip s from its frame `first`; returns the number of tiles of one of its frames
+static long long fill_clip(CodecClipDev& d, const flk_codec_clip& s, int first, int count, bool s420) {
+  d.src = s.src + (long long)first * s.pitch_t; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
+  d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
+  d.count = count; d.Hs = s.Hs; d.Ws = s.Ws;
+  d.ntx = (int)((padded(s.Ws, s420) + kTW - 1) / kTW);
+  const int TH = s420 ? 64 : 32;
+  return d.ntx * ((padded(s.Hs, s420) + TH - 1) / TH);
+}
+
+static long long max_of(long long a, long long b) { return a > b ? a : b; }
+
 // arguments already validated (api.cpp: flk_codec_roundtrip_u8); everything here up to the launch is host arithmetic
 int flk_codec_roundtrip_launch(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int32_t* stats,
                                hipStream_t stream) {
   CodecLaunch p;
   const bool s420 = a->subsampling == FLK_CODEC_420;
-  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
   p.idx = frame_idx; p.tone = tone; p.stats = stats; p.pad_ = 0;
-  int32_t ql[64], qc[64];
-  flk_codec_tables_host(a->quality, ql, qc);
-  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
+  fill_quant(a->quality, p.q);
   long long max_tiles = 1;
-  for (int i = 0; i < a->nclip; ++i) {
-    const flk_codec_clip& s = a->clips[i];
-    CodecClipDev& d = p.clip[i];
-    d.src = s.src; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
-    d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
-    d.T = s.T; d.Hs = s.Hs; d.Ws = s.Ws;
-    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
-    d.ntx = (int)((Wpad + kTW - 1) / kTW);
-    const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
-    if (tiles > max_tiles) max_tiles = tiles;
-  }
+  for (int i = 0; i < a->nclip; ++i) max_tiles = max_of(max_tiles, fill_clip(p.clip[i], a->clips[i], 0, a->clips[i].T, s420));
   FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_u8: a frame of more than 2^31 tiles");
   if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_out * 2 * sizeof(int32_t), stream));
   const dim3 grid((unsigned)max_tiles, (unsigned)T_out, (unsigned)a->nclip);
@@ -917,37 +765,17 @@ int flk_codec_roundtrip_launch(const flk_codec_args* a, const int32_t* frame_idx
   return FLK_OK;
 }
 
-// the P-frames' quantiser step at `quality` (1..100): MPEG-2's flat non-intra 16 under the IJG scaling rule
-int flk_codec_inter_step_host(int quality) {
-  const int s = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-  const int q = (16 * s + 50) / 100;
-  return q < 1 ? 1 : q > 255 ? 255 : q;
-}
-
 // arguments already validated (api.cpp: flk_codec_roundtrip_gop_u8); everything here up to the launch is host arithmetic
 int flk_codec_roundtrip_gop_launch(const flk_codec_args* a, int gop, const int32_t* first, const int32_t* count, int T_max,
                                    const uint8_t* tone, int32_t* stats, hipStream_t stream) {
   CodecGopLaunch p;
   const bool s420 = a->subsampling == FLK_CODEC_420;
-  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
   p.tone = tone; p.stats = stats; p.gop = gop; p.T_max = T_max; p.qp = flk_codec_inter_step_host(a->quality); p.pad_ = 0;
-  int32_t ql[64], qc[64];
-  flk_codec_tables_host(a->quality, ql, qc);
-  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
-  long long max_tiles = 1;
-  int max_gops = 1;
+  fill_quant(a->quality, p.q);
+  long long max_tiles = 1, max_gops = 1;
   for (int i = 0; i < a->nclip; ++i) {
-    const flk_codec_clip& s = a->clips[i];
-    CodecGopClipDev& d = p.clip[i];
-    d.src = s.src + (long long)first[i] * s.pitch_t; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
-    d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
-    d.count = count[i]; d.Hs = s.Hs; d.Ws = s.Ws;
-    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
-    d.ntx = (int)((Wpad + kTW - 1) / kTW);
-    const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
-    if (tiles > max_tiles) max_tiles = tiles;
-    const int gops = (count[i] + gop - 1) / gop;       // count <= 65535: no overflow
-    if (gops > max_gops) max_gops = gops;
+    max_tiles = max_of(max_tiles, fill_clip(p.clip[i], a->clips[i], first[i], count[i], s420));
+    max_gops = max_of(max_gops, (count[i] + gop - 1) / gop);                // count <= 65535: no overflow
   }
   FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_gop_u8: a frame of more than 2^31 tiles");
   if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_max * 2 * sizeof(int32_t), stream));
@@ -963,12 +791,11 @@ long long flk_codec_mc_scratch_host(const flk_codec_args* a, int gop, const int3
   if (!a || !a->clips || !count || a->nclip < 1 || gop < 1 || gop > 65535) return 0;
   if (a->subsampling != FLK_CODEC_420 && a->subsampling != FLK_CODEC_444) return 0;
   const bool s420 = a->subsampling == FLK_CODEC_420;
-  const int M = s420 ? 16 : 8;
   long long total = 0;
   for (int i = 0; i < a->nclip; ++i) {
     const flk_codec_clip& s = a->clips[i];
     if (s.Hs < 1 || s.Ws < 1 || count[i] < 1 || count[i] > 65535) return 0;
-    const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
+    const long long Hpad = padded(s.Hs, s420), Wpad = padded(s.Ws, s420);
     if (Hpad > (1LL << 34) / Wpad) return 0;           // a plane set of more than 2^36 bytes: no such workspace, and no overflow below
     total += (long long)((count[i] + gop - 1) / gop) * 2 * mc_set_bytes(Hpad, Wpad, s420);
     if (total > (1LL << 60)) return 0;
@@ -982,35 +809,24 @@ long long flk_codec_mc_scratch_host(const flk_codec_args* a, int gop, const int3
 int flk_codec_roundtrip_mc_launch(const flk_codec_args* a, int gop, int search, const int32_t* first, const int32_t* count, int T_max,
                                   const uint8_t* tone, int32_t* stats, int8_t* mv, int mv_stride, void* scratch, hipStream_t stream) {
   const bool s420 = a->subsampling == FLK_CODEC_420;
-  const int TH = s420 ? 64 : 32, M = s420 ? 16 : 8;
   CodecMcLaunch p;
   p.tone = tone; p.stats = stats; p.mv = (signed char*)mv; p.ws = (uint8_t*)scratch;
   p.gop = gop; p.T_max = T_max; p.qp = flk_codec_inter_step_host(a->quality); p.search = search; p.mv_stride = mv_stride; p.pad_ = 0;
-  int32_t ql[64], qc[64];
-  flk_codec_tables_host(a->quality, ql, qc);
-  for (int k = 0; k < 64; ++k) { p.q[0][k] = (unsigned short)ql[k]; p.q[1][k] = (unsigned short)qc[k]; }
+  fill_quant(a->quality, p.q);
   if (stats) FLK_CHECK_HIP(hipMemsetAsync(stats, 0, (size_t)a->nclip * T_max * 2 * sizeof(int32_t), stream));
   if (mv) FLK_CHECK_HIP(hipMemsetAsync(mv, 0, (size_t)a->nclip * T_max * mv_stride * 2, stream));
   long long ws_off = 0;
   for (int c0 = 0; c0 < a->nclip; c0 += kMcMaxClips) {
     const int n = a->nclip - c0 < kMcMaxClips ? a->nclip - c0 : kMcMaxClips;
-    long long max_tiles = 1;
-    int max_gops = 1, max_count = 1;
+    long long max_tiles = 1, max_gops = 1, max_count = 1;
     for (int i = 0; i < n; ++i) {
       const flk_codec_clip& s = a->clips[c0 + i];
-      CodecMcClipDev& d = p.clip[i];
-      d.src = s.src + (long long)first[c0 + i] * s.pitch_t; d.dst = s.dst; d.pitch_t = s.pitch_t; d.dpitch_t = s.dst_pitch_t;
-      d.pitch_h = (int)s.pitch_h; d.dpitch_h = (int)s.dst_pitch_h;
-      d.count = count[c0 + i]; d.Hs = s.Hs; d.Ws = s.Ws;
-      const long long Hpad = ((long long)s.Hs + M - 1) / M * M, Wpad = ((long long)s.Ws + M - 1) / M * M;
-      d.ntx = (int)((Wpad + kTW - 1) / kTW);
-      const long long tiles = d.ntx * ((Hpad + TH - 1) / TH);
-      if (tiles > max_tiles) max_tiles = tiles;
-      const int gops = (d.count + gop - 1) / gop;
-      if (gops > max_gops) max_gops = gops;
-      if (d.count > max_count) max_count = d.count;
-      d.ws_off = ws_off;
-      ws_off += (long long)gops * 2 * mc_set_bytes(Hpad, Wpad, s420);
+      const int cnt = count[c0 + i], gops = (cnt + gop - 1) / gop;
+      max_tiles = max_of(max_tiles, fill_clip(p.clip[i], s, first[c0 + i], cnt, s420));
+      max_gops = max_of(max_gops, gops);
+      max_count = max_of(max_count, cnt);
+      p.clip[i].ws_off = ws_off;
+      ws_off += (long long)gops * 2 * mc_set_bytes(padded(s.Hs, s420), padded(s.Ws, s420), s420);
     }
     FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_roundtrip_mc_u8: a frame of more than 2^31 tiles");
     p.clip0 = c0;

@@ -1,5 +1,6 @@
 """The contents and the case list the motion-compensation tests share: tests/test_codec_mc_gpu.py runs the kernel on them against the
-restatement, tests/test_codec_mc_cpu.py checks (without a GPU) that their restated vectors cover what the kernel can get wrong."""
+restatement, tests/test_codec_mc_cpu.py checks (without a GPU) that their restated vectors cover what the kernel can get wrong.  Also
+the view geometry across tile seams that the intra, GOP and motion-compensation view tests share (check_views_across_tile_seams)."""
 import numpy as np
 
 SUBS = ("444", "420")
@@ -49,6 +50,44 @@ def stripes(N, H, W, step=3):
 
 def flat(N, H, W, grey=160):
     return np.full((N, H, W, 3), grey, np.uint8)
+
+
+# the geometries of the three test_source_and_destination_views: the one-tile view of each test, and the view across tile seams below
+VIEW_GEOMETRIES = [(s, g) for g in ("tile", "seams") for s in SUBS]
+VIEW_IDS = [s if g == "tile" else f"{s}-{g}" for s, g in VIEW_GEOMETRIES]
+
+
+def check_views_across_tile_seams(ops, vs, sub, **codec_kw):
+    """The second geometry of the three test_source_and_destination_views (intra, GOP, motion compensation; ``codec_kw`` is gop= and
+    search=): a 70 x 133 view, which is two tiles along W with a 5-column second tile, three tile rows at 4:4:4 and two at 4:2:0 with
+    a 6-row remainder.  The source lies in a 75 x 141 buffer one byte off a 4-byte boundary, so the row pitch is 423 bytes and rows take
+    all four misalignments; the destination in a 0xA5-filled 74 x 139 buffer (row pitch 417) two bytes off.  5 frames through a tone table,
+    with stats: output and stats bit for bit the restatement's, every guard byte still 0xA5, the bytes around the buffer unchanged."""
+    import torch
+    big = moving(6, 75, 141, seed=17)
+    buf = torch.empty(big.size + 8, dtype=torch.uint8, device="cuda")
+    whole = buf[1:1 + big.size].view(big.shape)
+    whole.copy_(torch.from_numpy(big))
+    src = whole[1:6, 2:72, 4:137]
+    assert src.stride(1) == 423 and src.data_ptr() % 4 == (buf.data_ptr() + 1 + 75 * 423 + 2 * 423 + 12) % 4
+    assert {(src.data_ptr() + r * 423) % 4 for r in range(4)} == {0, 1, 2, 3}
+    tone = np.sort(np.random.RandomState(5).randint(0, 256, (1, 5, 256, 3)).astype(np.uint8), axis=2)
+    exp, exp_st = vs.codec_roundtrip_host(big[1:6, 2:72, 4:137], 60, sub, tone=tone[0], stats=True, **codec_kw)
+    n = 5 * 74 * 139 * 3
+    dbuf = torch.full((n + 8,), 0xA5, dtype=torch.uint8, device="cuda")
+    dwhole = dbuf[2:2 + n].view(5, 74, 139, 3)
+    dst = dwhole[:, 3:73, 2:135]
+    assert dst.stride(1) == 417 and dst.data_ptr() % 4 == (dbuf.data_ptr() + 2 + 3 * 417 + 6) % 4
+    before = dbuf.clone()
+    out, st = ops.codec_roundtrip([src], vs.Codec(60, sub, **codec_kw), tone=torch.from_numpy(tone).cuda(), stats=True, out=[dst])
+    got, got_st = dst.cpu().numpy(), st[0].cpu().numpy()
+    assert out[0].data_ptr() == dst.data_ptr()
+    assert got.dtype == exp.dtype and got.shape == exp.shape and np.array_equal(got, exp)
+    assert got_st.dtype == exp_st.dtype and got_st.shape == exp_st.shape and np.array_equal(got_st, exp_st), (got_st, exp_st)
+    mask = torch.zeros_like(dwhole, dtype=torch.bool)
+    mask[:, 3:73, 2:135] = True
+    assert bool((dwhole[~mask] == 0xA5).all())
+    assert torch.equal(dbuf[:2], before[:2]) and torch.equal(dbuf[2 + n:], before[2 + n:])
 
 
 def case_videos(content, size, search):

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import codec_mc_cases as cases
+
 pytestmark = pytest.mark.gpu
 SUBS = ("444", "420")
 QUALITIES = (1, 50, 75, 100)
@@ -161,11 +163,14 @@ def test_more_than_64_videos(env):
         assert same_bits(outs[k], exp) and same_bits(sts[k], exp_st), k
 
 
-@pytest.mark.parametrize("sub", SUBS)
-def test_source_and_destination_views(env, sub):
+@pytest.mark.parametrize("sub,geom", cases.VIEW_GEOMETRIES, ids=cases.VIEW_IDS)
+def test_source_and_destination_views(env, sub, geom):
     """the source a view of a wider and longer video one byte off a 4-byte boundary, the span inside it; the destination a view with
-    pitches of its own, also off alignment: the result is the restatement's and no byte outside the destination view changes"""
+    pitches of its own, also off alignment: the result is the restatement's and no byte outside the destination view changes.
+    "seams": a view of several tiles, the last ones partial (codec_mc_cases.check_views_across_tile_seams)"""
     ops, vs = env["ops"], env["vs"]
+    if geom == "seams":
+        return cases.check_views_across_tile_seams(ops, vs, sub, gop=3)
     codec = vs.Codec(60, sub, gop=3)
     big = moving(9, 30, 150, seed=11)
     buf = torch.empty(big.size + 8, dtype=torch.uint8, device="cuda")

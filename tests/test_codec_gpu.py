@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+import codec_mc_cases as cases
+
 pytestmark = pytest.mark.gpu
 SUBS = ("444", "420")
 QUALITIES = (1, 50, 75, 95, 100)
@@ -98,11 +100,14 @@ def test_extreme_contents(env, sub):
 
 
 # ---- views ---------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("sub", SUBS)
-def test_source_and_destination_views(env, sub):
+@pytest.mark.parametrize("sub,geom", cases.VIEW_GEOMETRIES, ids=cases.VIEW_IDS)
+def test_source_and_destination_views(env, sub, geom):
     """the source a view of a wider and longer video, starting 0..3 bytes off a 4-byte boundary; the destination a view with pitches of
-    its own, also off alignment: the result is the contiguous call's and no byte outside the destination view changes"""
+    its own, also off alignment: the result is the contiguous call's and no byte outside the destination view changes.  "seams": a
+    view of several tiles, the last ones partial (codec_mc_cases.check_views_across_tile_seams)"""
     ops, vs = env["ops"], env["vs"]
+    if geom == "seams":
+        return cases.check_views_across_tile_seams(ops, vs, sub)
     codec = vs.Codec(60, sub)
     big = smooth(5, 30, 150, seed=11)
     for off in (0, 1, 2, 3):

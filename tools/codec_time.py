@@ -14,7 +14,7 @@
    Motion legs (flk_codec_roundtrip_mc_u8, `--search` 7; 0 leaves them out): `mc_launch_*` / `mc_video_*`, the launch sequence of the
    same frames as the GOP legs (one launch per frame position, the workspace allocated once), and the step with
    `Codec(75, "420", gop, search)` (`mc_420`).
-3. The no-codec step and the intra launches against the PARENT commit (`--parent-root PATH`: a checkout of the parent with its library
+3. The no-codec step and the intra, GOP and (with `--search` above 0) motion launches against the PARENT commit (`--parent-root PATH`: a checkout of the parent with its library
    built): the same launches, so the trees only have to agree inside the run's spread.  A process per tree and round, alternating.
 
 Prints one JSON line per leg and a summary line.  Needs the GPU; there is no fallback.
@@ -210,8 +210,8 @@ def main():
         summary[f"launch_{sub}_over_copy"] = round(same[f"launch_{sub}"]["median_ms"] / same["device_copy"]["median_ms"], 2)
         summary[f"launch_{sub}_over_export"] = round(same[f"launch_{sub}"]["median_ms"] / same["export_u8"]["median_ms"], 2)
     if a.parent_root:
-        # the no-codec step, the intra launches and the zero-motion GOP launches: the same device code in both trees
-        what = ("delivered", "launch_420", "launch_444", "gop_launch_420", "gop_launch_444")
+        # the no-codec step and the launches of every codec kernel instantiation, which the parent has as well
+        what = ("delivered", "launch_420", "launch_444", "gop_launch_420", "gop_launch_444") + (("mc_launch_420", "mc_launch_444") if a.search else ())
         med = {w: {"this": [], "parent": []} for w in what}
         for k in range(a.rounds):                           # the two trees alternate, a process each; who goes first alternates too
             for tree in (("parent", "this"), ("this", "parent"))[k % 2]:
