@@ -4,9 +4,10 @@
 //             (i3d.py:174,189,212,252,398); the winning window index is kept as one byte.
 //             Values are compared as numbers: -0.0 == +0.0 (the first of them in scan order wins), a window of -inf only records
 //             tap 0.  relu_input: windows whose maximum is <= 0 record 255 ("no cell").  One deviation: the bf16 sortable-key
-//             kernels (3x3x3 / 1) rank +0.0 above -0.0, so among tied zeros of both signs the first +0.0 wins (see bf16x2_to_keys).
-//             Dispatch: stride-1 SAME windows of >= 8 taps stage a halo box in LDS (maxpool_s1_tiled_fwd; bf16 3x3x3 takes the
-//             sortable-key kernels maxpool_s1_wrun_fwd_bf16 / maxpool_s1_tiled_fwd_bf16); every other geometry takes one thread per
+//             kernel (3x3x3 / 1, SAME pad-before 1) ranks +0.0 above -0.0, so among tied zeros of both signs the first +0.0 wins (see
+//             bf16x2_to_keys); every other route, bf16 3x3x3 / 1 at another pad-before included, keeps the rule above.
+//             Dispatch: stride-1 SAME windows of >= 8 taps stage a halo box in LDS (maxpool_s1_tiled_fwd; bf16 3x3x3 with pad-before 1
+//             takes the sortable-key W-run kernel maxpool_s1_wrun_fwd_bf16); every other geometry takes one thread per
 //             output (maxpool_fwd_kernel_k for the I3D windows, maxpool_fwd_kernel for the rest).
 //   backward: the three strided I3D geometries take the owner form (maxpool_strided_bwd, both dtypes: every cell written once, fixed
 //             order).  Everything else: bf16 takes the scatter form (maxpool_scatter_bwd): a workgroup owns a tile of INPUT cells in
@@ -44,6 +45,19 @@ struct PoolKP {
   int kt, kh, kw, st, sh, sw, pt, ph, pw;
   int relu_input;
 };
+
+// position addressing, stated once: linear position of (b, t, h, w) in a [B, T, H, W] grid, and the byte address of channel c of a position
+// in a channel slice (channels [coff, coff + C) of rows ld wide).  idx rows are C wide.
+__device__ static inline size_t pool_pos(int b, int t, int h, int w, int T, int H, int W) { return (((size_t)(b * T + t) * H + h) * W + w); }
+__device__ static inline size_t in_pos(const PoolKP& k, int b, int t, int h, int w) { return pool_pos(b, t, h, w, k.Ti, k.Hi, k.Wi); }
+__device__ static inline size_t out_pos(const PoolKP& k, int b, int t, int h, int w) { return pool_pos(b, t, h, w, k.To, k.Ho, k.Wo); }
+template <typename T> __device__ static inline size_t slice_off(size_t pos, int ld, int coff, int c) { return (pos * ld + coff + c) * sizeof(T); }
+template <typename T> __device__ static inline const char* in_at(const PoolKP& k, size_t pos, int c) { return k.in + slice_off<T>(pos, k.in_ld, k.in_coff, c); }
+template <typename T> __device__ static inline char* out_at(const PoolKP& k, size_t pos, int c) { return k.out + slice_off<T>(pos, k.out_ld, k.out_coff, c); }
+template <typename T> __device__ static inline const char* gout_at(const PoolKP& k, size_t pos, int c) { return k.gout + slice_off<T>(pos, k.gout_ld, k.gout_coff, c); }
+template <typename T> __device__ static inline char* gin_at(const PoolKP& k, size_t pos, int c) { return k.gin + slice_off<T>(pos, k.gin_ld, k.gin_coff, c); }
+template <typename T> __device__ static inline const char* mask_at(const PoolKP& k, size_t pos, int c) { return k.mask + slice_off<T>(pos, k.mask_ld, k.mask_coff, c); }
+__device__ static inline uint8_t* idx_at(const PoolKP& k, size_t pos, int c) { return k.idx + pos * k.C + c; }
 
 template <typename T> struct PV;
 template <> struct PV<bf16_t> {
@@ -88,15 +102,47 @@ template <> struct PV<float> {
   }
 };
 
-// grid: x = chunks of 256 over (w, channel group) of one output row; y = h; z = b*T + t  (32-bit index math only)
+// The one-thread-per-position kernels.  grid: x = chunks of 256 over (w, channel group) of one row of a [B, Tn, ., Wn] grid (the output
+// grid, or the input grid for maxpool_bwd_kernel); y = h; z = b * Tn + t  (32-bit index math only).  live = false: the thread is past the row.
+struct PoolTask { bool live; int b, t, h, w, cg; };
+template <typename T>
+__device__ static inline PoolTask simple_grid_task(const PoolKP& p, int Tn, int Wn) {
+  PoolTask k;
+  const int ng = p.C / PV<T>::EPL;
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  k.live = i < (unsigned)(Wn * ng);
+  k.w = i / ng; k.cg = i - k.w * ng;
+  k.h = blockIdx.y; k.t = blockIdx.z % Tn; k.b = blockIdx.z / Tn;
+  return k;
+}
+
+// the end of a forward: a window's maxima and argmax bytes (channels [c, c + EPL) of output position opos)
+template <typename T>
+__device__ static inline void store_out_idx(const PoolKP& k, size_t opos, int c, const float (&best)[PV<T>::EPL], const int (&bi)[PV<T>::EPL]) {
+  PV<T>::st(out_at<T>(k, opos, c), best);
+  PV<T>::stidx(idx_at(k, opos, c), bi);
+}
+
+// the end of a maskable backward: the gradient of channels [c, c + EPL) of input cell ipos, zeroed where the producing layer's ReLU was
+// off (mask <= 0), stored once.  (strided_owner_resolve, which may have loaded the mask operand ahead, keeps this tail written out.)
+template <typename T>
+__device__ static inline void mask_and_store(const PoolKP& k, size_t ipos, int c, float (&g)[PV<T>::EPL], bool masked) {
+  constexpr int EPL = PV<T>::EPL;
+  if (masked) {
+    float mk[EPL];
+    PV<T>::ld(mask_at<T>(k, ipos, c), mk);
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) g[e] = mk[e] > 0.f ? g[e] : 0.f;
+  }
+  PV<T>::st(gin_at<T>(k, ipos, c), g);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolKP p) {
   constexpr int EPL = PV<T>::EPL;
-  const int ng = p.C / EPL;
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= (unsigned)(p.Wo * ng)) return;
-  const int ow = i / ng, cg = i - ow * ng;
-  const int oh = blockIdx.y, ot = blockIdx.z % p.To, b = blockIdx.z / p.To;
+  const PoolTask o = simple_grid_task<T>(p, p.To, p.Wo);
+  if (!o.live) return;
+  const int ow = o.w, cg = o.cg, oh = o.h, ot = o.t, b = o.b;
   float best[EPL];
   int bi[EPL];
 #pragma unroll
@@ -110,7 +156,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolKP p) {
         const int iw = ow * p.sw - p.pw + dw;
         if ((unsigned)it >= (unsigned)p.Ti || (unsigned)ih >= (unsigned)p.Hi || (unsigned)iw >= (unsigned)p.Wi) continue;
         float v[EPL];
-        PV<T>::ld(p.in + ((((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw) * p.in_ld + p.in_coff + cg * EPL) * sizeof(T), v);
+        PV<T>::ld(in_at<T>(p, in_pos(p, b, it, ih, iw), cg * EPL), v);
 #pragma unroll
         for (int e = 0; e < EPL; ++e)
           if (v[e] > best[e]) { best[e] = v[e]; bi[e] = tap; }
@@ -121,9 +167,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const PoolKP p) {
 #pragma unroll
     for (int e = 0; e < EPL; ++e) bi[e] = best[e] > 0.f ? bi[e] : 255;
   }
-  const size_t opos = (((size_t)(b * p.To + ot) * p.Ho + oh) * p.Wo + ow);
-  PV<T>::st(p.out + (opos * p.out_ld + p.out_coff + cg * EPL) * sizeof(T), best);
-  PV<T>::stidx(p.idx + opos * p.C + cg * EPL, bi);
+  store_out_idx<T>(p, out_pos(p, b, ot, oh, ow), cg * EPL, best, bi);
 }
 
 // The window scan of one (position, channel group) over its NT raw 16-byte taps (ok[tap]: the tap is an in-bounds cell): first maximum in
@@ -162,11 +206,9 @@ __device__ static inline void pool_window_scan(const uint4 (&raw)[NT], const boo
 template <typename T, int KT, int KH, int KW>
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel_k(const PoolKP p) {
   constexpr int EPL = PV<T>::EPL, NT = KT * KH * KW;
-  const int ng = p.C / EPL;
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= (unsigned)(p.Wo * ng)) return;
-  const int ow = i / ng, cg = i - ow * ng;
-  const int oh = blockIdx.y, ot = blockIdx.z % p.To, b = blockIdx.z / p.To;
+  const PoolTask o = simple_grid_task<T>(p, p.To, p.Wo);
+  if (!o.live) return;
+  const int ow = o.w, cg = o.cg, oh = o.h, ot = o.t, b = o.b;
   uint4 raw[NT];
   bool ok[NT];
 #pragma unroll
@@ -178,32 +220,28 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel_k(const PoolKP p) {
         const int tap = (dt * KH + dh) * KW + dw;
         const int it = ot * p.st - p.pt + dt, ih = oh * p.sh - p.ph + dh, iw = ow * p.sw - p.pw + dw;
         ok[tap] = (unsigned)it < (unsigned)p.Ti && (unsigned)ih < (unsigned)p.Hi && (unsigned)iw < (unsigned)p.Wi;
-        const size_t pos = ok[tap] ? (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw) : 0;      // (position 0 is always readable)
-        raw[tap] = *(const uint4*)(p.in + (pos * p.in_ld + p.in_coff + cg * EPL) * sizeof(T));
+        const size_t pos = ok[tap] ? in_pos(p, b, it, ih, iw) : 0;      // (position 0 is always readable)
+        raw[tap] = *(const uint4*)in_at<T>(p, pos, cg * EPL);
       }
   float best[EPL];
   int bi[EPL];
   pool_window_scan<T, NT>(raw, ok, p.relu_input, best, bi);
-  const size_t opos = (((size_t)(b * p.To + ot) * p.Ho + oh) * p.Wo + ow);
-  PV<T>::st(p.out + (opos * p.out_ld + p.out_coff + cg * EPL) * sizeof(T), best);
-  PV<T>::stidx(p.idx + opos * p.C + cg * EPL, bi);
+  store_out_idx<T>(p, out_pos(p, b, ot, oh, ow), cg * EPL, best, bi);
 }
 
-// grid: x = chunks of 256 over (w, channel group) of one INPUT row; y = h; z = b*T + t
+// the gather form over the INPUT grid
 template <typename T>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const PoolKP p) {
   constexpr int EPL = PV<T>::EPL;
-  const int ng = p.C / EPL;
   {
-    const unsigned i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= (unsigned)(p.Wi * ng)) return;
-    const int iw = i / ng, cg = i - iw * ng;
-    const int ih = blockIdx.y, it = blockIdx.z % p.Ti, b = blockIdx.z / p.Ti;
-    const size_t ipos = (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw);
+    const PoolTask c = simple_grid_task<T>(p, p.Ti, p.Wi);
+    if (!c.live) return;
+    const int iw = c.w, cg = c.cg, ih = c.h, it = c.t, b = c.b;
+    const size_t ipos = in_pos(p, b, it, ih, iw);
     float g[EPL];
 #pragma unroll
     for (int e = 0; e < EPL; ++e) g[e] = 0.f;
-    if (p.add) PV<T>::ld(p.add + (ipos * p.gin_ld + p.gin_coff + cg * EPL) * sizeof(T), g);
+    if (p.add) PV<T>::ld(p.add + slice_off<T>(ipos, p.gin_ld, p.gin_coff, cg * EPL), g);
     // windows containing this cell: o in [ceil((i+p-k+1)/s), floor((i+p)/s)] per dim; its tap index d = i+p-o*s
     const int ot_lo = max(0, (it + p.pt - p.kt + p.st) / p.st), ot_hi = min(p.To - 1, (it + p.pt) / p.st);
     const int oh_lo = max(0, (ih + p.ph - p.kh + p.sh) / p.sh), oh_hi = min(p.Ho - 1, (ih + p.ph) / p.sh);
@@ -212,26 +250,20 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const PoolKP p) {
       for (int oh = oh_lo; oh <= oh_hi; ++oh)
         for (int ow = ow_lo; ow <= ow_hi; ++ow) {
           const int tap = ((it + p.pt - ot * p.st) * p.kh + (ih + p.ph - oh * p.sh)) * p.kw + (iw + p.pw - ow * p.sw);
-          const size_t opos = (((size_t)(b * p.To + ot) * p.Ho + oh) * p.Wo + ow);
+          const size_t opos = out_pos(p, b, ot, oh, ow);
           int id[EPL];
-          PV<T>::ldidx(p.idx + opos * p.C + cg * EPL, id);
+          PV<T>::ldidx(idx_at(p, opos, cg * EPL), id);
           bool any = false;
 #pragma unroll
           for (int e = 0; e < EPL; ++e) any |= id[e] == tap;
           if (!any) continue;
           float go[EPL];
-          PV<T>::ld(p.gout + (opos * p.gout_ld + p.gout_coff + cg * EPL) * sizeof(T), go);
+          PV<T>::ld(gout_at<T>(p, opos, cg * EPL), go);
 #pragma unroll
           for (int e = 0; e < EPL; ++e)
             if (id[e] == tap) g[e] += go[e];
         }
-    if (p.mask) {
-      float mk[EPL];
-      PV<T>::ld(p.mask + (ipos * p.mask_ld + p.mask_coff + cg * EPL) * sizeof(T), mk);
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) g[e] = mk[e] > 0.f ? g[e] : 0.f;
-    }
-    PV<T>::st(p.gin + (ipos * p.gin_ld + p.gin_coff + cg * EPL) * sizeof(T), g);
+    mask_and_store<T>(p, ipos, cg * EPL, g, p.mask != nullptr);
   }
 }
 
@@ -265,8 +297,7 @@ __device__ static inline void strided_owner_resolve(const PoolKP& p, int b, int 
 #pragma unroll
         for (int aw = 0; aw < SW; ++aw) {
           const int it = min(max(ot * ST - p.pt + at, 0), p.Ti - 1), ih = min(max(oh * SH - p.ph + ah, 0), p.Hi - 1), iw = min(max(ow * SW - p.pw + aw, 0), p.Wi - 1);
-          const size_t ipos = (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw);
-          PV<T>::ld(p.mask + (ipos * p.mask_ld + p.mask_coff + cg * EPL) * sizeof(T), mk[(at * SH + ah) * SW + aw]);
+          PV<T>::ld(mask_at<T>(p, in_pos(p, b, it, ih, iw), cg * EPL), mk[(at * SH + ah) * SW + aw]);
         }
   }
 #pragma unroll
@@ -294,13 +325,15 @@ __device__ static inline void strided_owner_resolve(const PoolKP& p, int b, int 
 #pragma unroll
               for (int e = 0; e < EPL; ++e) g[e] += id[w][e] == tap ? go[w][e] : 0.f;
             }
-        const size_t ipos = (((size_t)(b * p.Ti + it) * p.Hi + ih) * p.Wi + iw);
+        // (mask_and_store written out: through the helper hipcc emits 4 - 16 % more instructions for the six owner kernels and the 1x3x3 one
+        // measured 137.4 against 128.9 us on MaxPool3d_3a, DESIGN_LOG.md)
+        const size_t ipos = in_pos(p, b, it, ih, iw);
         if (MASKABLE && p.mask) {
-          if (!HOIST) PV<T>::ld(p.mask + (ipos * p.mask_ld + p.mask_coff + cg * EPL) * sizeof(T), mk[0]);
+          if (!HOIST) PV<T>::ld(mask_at<T>(p, ipos, cg * EPL), mk[0]);
 #pragma unroll
           for (int e = 0; e < EPL; ++e) g[e] = mk[HOIST ? (at * SH + ah) * SW + aw : 0][e] > 0.f ? g[e] : 0.f;
         }
-        PV<T>::st(p.gin + (ipos * p.gin_ld + p.gin_coff + cg * EPL) * sizeof(T), g);
+        PV<T>::st(gin_at<T>(p, ipos, cg * EPL), g);
       }
 }
 
@@ -309,11 +342,9 @@ __global__ __launch_bounds__(256) void maxpool_strided_bwd(const PoolKP p) {
   constexpr int EPL = PV<T>::EPL;
   constexpr int NT = KT > ST ? 2 : 1, NH = KH > SH ? 2 : 1, NW = KW > SW ? 2 : 1;     // candidate windows per dimension
   static_assert(KT <= 2 * ST && KH <= 2 * SH && KW <= 2 * SW, "a cell may see at most two windows per dimension");
-  const int ng = p.C / EPL;
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= (unsigned)(p.Wo * ng)) return;
-  const int ow = i / ng, cg = i - ow * ng;
-  const int oh = blockIdx.y, ot = blockIdx.z % p.To, b = blockIdx.z / p.To;
+  const PoolTask o = simple_grid_task<T>(p, p.To, p.Wo);
+  if (!o.live) return;
+  const int ow = o.w, cg = o.cg, oh = o.h, ot = o.t, b = o.b;
   int id[NT * NH * NW][EPL];
   float go[NT * NH * NW][EPL];
   bool ok[NT * NH * NW];
@@ -325,18 +356,25 @@ __global__ __launch_bounds__(256) void maxpool_strided_bwd(const PoolKP p) {
       for (int dw = 0; dw < NW; ++dw) {
         const int w = (dt * NH + dh) * NW + dw;
         ok[w] = ot - dt >= 0 && oh - dh >= 0 && ow - dw >= 0;
-        const size_t opos = (((size_t)(b * p.To + max(ot - dt, 0)) * p.Ho + max(oh - dh, 0)) * p.Wo + max(ow - dw, 0));
-        PV<T>::ldidx(p.idx + opos * p.C + cg * EPL, id[w]);
-        PV<T>::ld(p.gout + (opos * p.gout_ld + p.gout_coff + cg * EPL) * sizeof(T), go[w]);
+        const size_t opos = out_pos(p, b, max(ot - dt, 0), max(oh - dh, 0), max(ow - dw, 0));
+        PV<T>::ldidx(idx_at(p, opos, cg * EPL), id[w]);
+        PV<T>::ld(gout_at<T>(p, opos, cg * EPL), go[w]);
       }
   strided_owner_resolve<T, KT, KH, KW, ST, SH, SW, true>(p, b, ot, oh, ow, cg, id, go, ok);
 }
 
+// grid of the one-thread-per-position kernels (simple_grid_task) over the input or the output grid; who: the entry point, for the message
+static int simple_grid(const flk_pool_args* a, int epl, bool over_input, const char* who, dim3& grid) {
+  const int Tn = over_input ? a->Ti : a->To, Hn = over_input ? a->Hi : a->Ho, Wn = over_input ? a->Wi : a->Wo;
+  FLK_REQUIRE(Hn < 65536 && (long)a->B * Tn < 65536, "%s: grid too large", who);
+  grid = dim3((unsigned)((Wn * (a->C / epl) + 255) / 256), (unsigned)Hn, (unsigned)(a->B * Tn));
+  return FLK_OK;
+}
+
 template <typename T, int KT, int KH, int KW, int ST, int SH, int SW>
 static int launch_strided_bwd(const PoolKP& kp, const flk_pool_args* a, hipStream_t s) {
-  constexpr int EPL = PV<T>::EPL;
-  FLK_REQUIRE(a->Ho < 65536 && (long)a->B * a->To < 65536, "flk_maxpool3d_bwd: grid too large");
-  const dim3 grid((unsigned)((a->Wo * (a->C / EPL) + 255) / 256), (unsigned)a->Ho, (unsigned)(a->B * a->To));
+  dim3 grid;
+  if (int rc = simple_grid(a, PV<T>::EPL, false, "flk_maxpool3d_bwd", grid)) return rc;
   FLK_LAUNCH_KERNEL((maxpool_strided_bwd<T, KT, KH, KW, ST, SH, SW>), grid, dim3(256), 0, s, kp);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
@@ -367,14 +405,32 @@ __device__ static inline int pplane_off(int c, int plane_b) { return c * plane_b
 // are still in that XCD's L2 (a slab is only 64 B of a position's row).
 // Tile i sits on XCD i % 8 (dealing the tiles to the XCDs in contiguous chunks, as the convolutions do, measured 6.81 against 6.77-6.79 ms
 // per step: DESIGN_LOG.md).
-__device__ static inline bool tile_slab_of_block(const PoolTP& p, int nslab, int& tile, int& slab) {
+__device__ static inline bool tile_slab_of_block(const PoolTP& p, int& tile, int& slab) {
   const int bid = blockIdx.x, xcd = bid & 7, r = bid >> 3;
-  slab = r % nslab;
-  tile = (r / nslab) * 8 + xcd;                              // (the host sizes the grid as 8 * ceil(ntiles / 8) * nslab)
+  slab = r % p.nslab;
+  tile = (r / p.nslab) * 8 + xcd;                            // (the host sizes the grid as 8 * ceil(ntiles / 8) * nslab: tile_grid)
   return tile < p.ntiles;
 }
-__device__ static inline bool tile_slab_of_block(const PoolTP& p, int& tile, int& slab) { return tile_slab_of_block(p, p.nslab, tile, slab); }
 
+// Workgroup -> its tile, the start of every tiled kernel: batch b, the tile's origin (t0, h0, w0) in the grid the kernel tiles (outputs for
+// the forwards, input cells for the backwards), channel slab cslab of slabc channels, and this thread's 16-byte chunk of it (channels
+// [c0, c0 + slabc / 4); chvalid: the chunk exists, c0 < C).  ok = false: a tail block of the XCD dealing, no tile.  WT: the tile's width
+// where it is a compile-time constant (the W-run forward), else p.Wt.
+struct PoolTileCtx { bool ok; int b, t0, h0, w0, cslab, c0; bool chvalid; };
+template <int WT = 0>
+__device__ static inline PoolTileCtx pool_tile(const PoolTP& p, int slabc) {
+  PoolTileCtx c;
+  int bid;
+  c.ok = tile_slab_of_block(p, bid, c.cslab);
+  const int tw = bid % p.nTw; bid /= p.nTw;
+  const int th = bid % p.nTh; bid /= p.nTh;
+  const int tt = bid % p.nTt;
+  c.b = bid / p.nTt;
+  c.c0 = c.cslab * slabc + (threadIdx.x & 3) * (slabc / 4);
+  c.chvalid = c.c0 < p.k.C;
+  c.t0 = tt * p.Tt; c.h0 = th * p.Ht; c.w0 = tw * (WT ? WT : p.Wt);
+  return c;
+}
 // x / d for 0 <= x < 2^20 and a small run-time divisor d, inv = 1.0f / d: (x + 0.5) / d is never within 0.5 / d of an integer, so the float
 // quotient truncates exactly -- 3 VALU operations instead of the ~40 of a 32-bit integer division (which made the index arithmetic of the
 // staging / write-out loops below as expensive as the pooling itself)
@@ -389,15 +445,10 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd(const PoolTP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const PoolKP& k = p.k;
   const int tid = threadIdx.x, ch = tid & 3;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int c0 = cslab * SLABC + ch * EPL;
-  const bool chvalid = c0 < k.C;
-  const int ot0 = tt * p.Tt, oh0 = th * p.Ht, ow0 = tw * p.Wt;
+  const PoolTileCtx tc = pool_tile(p, SLABC);
+  if (!tc.ok) return;
+  const int b = tc.b, c0 = tc.c0, ot0 = tc.t0, oh0 = tc.h0, ow0 = tc.w0;
+  const bool chvalid = tc.chvalid;
   const int it0 = ot0 - k.pt, ih0 = oh0 - k.ph, iw0 = ow0 - k.pw;
   const int HW = p.Hh * p.Wh;
   // stage the halo (-inf outside the tensor: padded cells never win)
@@ -408,7 +459,7 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd(const PoolTP p) {
 #pragma unroll
     for (int e = 0; e < EPL; ++e) v[e] = -INFINITY;
     if (chvalid && (unsigned)it < (unsigned)k.Ti && (unsigned)ih < (unsigned)k.Hi && (unsigned)iw < (unsigned)k.Wi)
-      PV<T>::ld(k.in + ((((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw) * k.in_ld + k.in_coff + c0) * sizeof(T), v);
+      PV<T>::ld(in_at<T>(k, in_pos(k, b, it, ih, iw), c0), v);
     PV<T>::st(smem + pplane_off(ch, p.plane_b) + hp * 16, v);
   }
   __syncthreads();
@@ -437,15 +488,13 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd(const PoolTP p) {
 #pragma unroll
       for (int e = 0; e < EPL; ++e) bi[e] = best[e] > 0.f ? bi[e] : 255;
     }
-    const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-    PV<T>::st(k.out + (opos * k.out_ld + k.out_coff + c0) * sizeof(T), best);
-    PV<T>::stidx(k.idx + opos * k.C + c0, bi);
+    store_out_idx<T>(k, out_pos(k, b, ot, oh, ow), c0, best, bi);
   }
 }
 
-// bf16 fast path of the tiled forward: the halo holds SORTABLE 16-bit keys (key = bits ^ (sign ? 0xffff : 0x8000): unsigned
-// order == float order); one element-tap costs 2 VALU ops: pack (key << 16 | 255 - tap) and v_max_u32 -- the larger low
-// byte wins among equal keys, i.e. the FIRST maximum in scan order.  Taps are compile-time so the LDS reads batch.
+// bf16 3x3x3 fast path (the W-run kernel below): the halo holds SORTABLE 16-bit keys (key = bits ^ (sign ? 0xffff : 0x8000): unsigned
+// order == float order); one element-tap costs 2 VALU ops: pack (key << 16 | tag), the tag falling with the tap, and v_max_u32 -- the
+// larger low byte wins among equal keys, i.e. the FIRST maximum in scan order.  Taps are compile-time so the LDS reads batch.
 // DEVIATION from "values compare as numbers": key(-0.0) = 0x7fff < key(+0.0) = 0x8000, so in a window whose maximum is zero a +0.0
 // beats an EARLIER -0.0 (the float kernels and torch take the first of the two).  The recorded tap still names an in-bounds cell whose
 // value equals the window maximum, and out is a zero; only which of the tied zero cells receives the gradient differs.  Inputs here
@@ -461,75 +510,6 @@ __device__ static inline uint32_t keys_to_bf16x2(uint32_t k) {
   return k ^ (flip | 0x80008000u);
 }
 
-template <int KT, int KH, int KW>
-__global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd_bf16(const PoolTP p) {
-  constexpr int EPL = 8, SLABC = 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const PoolKP& k = p.k;
-  const int tid = threadIdx.x, ch = tid & 3;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int c0 = cslab * SLABC + ch * EPL;
-  const bool chvalid = c0 < k.C;
-  const int ot0 = tt * p.Tt, oh0 = th * p.Ht, ow0 = tw * p.Wt;
-  const int it0 = ot0 - k.pt, ih0 = oh0 - k.ph, iw0 = ow0 - k.pw;
-  const int HW = p.Hh * p.Wh;
-  for (int hp = tid >> 2; hp < p.P; hp += 64) {
-    int a, bq, c; split3(hp, HW, 1.0f / (float)HW, p.Wh, 1.0f / (float)p.Wh, a, bq, c);
-    const int it = it0 + a, ih = ih0 + bq, iw = iw0 + c;
-    uint4 v = make_uint4(0xff80ff80u, 0xff80ff80u, 0xff80ff80u, 0xff80ff80u);     // -inf
-    if (chvalid && (unsigned)it < (unsigned)k.Ti && (unsigned)ih < (unsigned)k.Hi && (unsigned)iw < (unsigned)k.Wi)
-      v = *(const uint4*)(k.in + ((((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw) * k.in_ld + k.in_coff + c0) * 2);
-    v.x = bf16x2_to_keys(v.x); v.y = bf16x2_to_keys(v.y); v.z = bf16x2_to_keys(v.z); v.w = bf16x2_to_keys(v.w);
-    *(uint4*)(smem + pplane_off(ch, p.plane_b) + hp * 16) = v;
-  }
-  __syncthreads();
-  if (!chvalid) return;
-  const int hw = p.Ht * p.Wt;
-  for (int r = tid >> 2; r < p.rows; r += 64) {
-    int rt, rh, rw; split3(r, hw, 1.0f / (float)hw, p.Wt, 1.0f / (float)p.Wt, rt, rh, rw);
-    const int ot = ot0 + rt, oh = oh0 + rh, ow = ow0 + rw;
-    if (ot >= k.To || oh >= k.Ho || ow >= k.Wo) continue;
-    const char* base = smem + pplane_off(ch, p.plane_b) + ((rt * p.Hh + rh) * p.Wh + rw) * 16;
-    uint32_t best[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int dt = 0; dt < KT; ++dt)
-#pragma unroll
-      for (int dh = 0; dh < KH; ++dh)
-#pragma unroll
-        for (int dw = 0; dw < KW; ++dw) {
-          const uint32_t tag = 255u - (uint32_t)((dt * KH + dh) * KW + dw);
-          const uint4 v = *(const uint4*)(base + ((dt * p.Hh + dh) * p.Wh + dw) * 16);
-          const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            best[2 * i] = max(best[2 * i], (w[i] << 16) | tag);
-            best[2 * i + 1] = max(best[2 * i + 1], (w[i] & 0xffff0000u) | tag);
-          }
-        }
-    uint4 o;
-    o.x = keys_to_bf16x2((best[0] >> 16) | (best[1] & 0xffff0000u));
-    o.y = keys_to_bf16x2((best[2] >> 16) | (best[3] & 0xffff0000u));
-    o.z = keys_to_bf16x2((best[4] >> 16) | (best[5] & 0xffff0000u));
-    o.w = keys_to_bf16x2((best[6] >> 16) | (best[7] & 0xffff0000u));
-    if (k.relu_input) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        if ((best[e] >> 16) <= 0x8000u) best[e] &= ~255u;      // tag 0 -> idx 255 ("no cell")
-    }
-    uint2 id;
-    id.x = (255u - (best[0] & 255u)) | ((255u - (best[1] & 255u)) << 8) | ((255u - (best[2] & 255u)) << 16) | ((255u - (best[3] & 255u)) << 24);
-    id.y = (255u - (best[4] & 255u)) | ((255u - (best[5] & 255u)) << 8) | ((255u - (best[6] & 255u)) << 16) | ((255u - (best[7] & 255u)) << 24);
-    const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-    *(uint4*)(k.out + (opos * k.out_ld + k.out_coff + c0) * 2) = o;
-    *(uint2*)(k.idx + opos * k.C + c0) = id;
-  }
-}
-
 // W-run form of the bf16 3x3x3 forward: a thread owns one (t, h) of the tile, 8 channels and the whole run of WT outputs along w.  The
 // 9-tap maximum over (dt, dh) of a halo column is computed ONCE and shared by the three outputs whose windows contain it -- (WT+2) * 9
 // element-taps per WT outputs instead of WT * 27 (2.1x fewer VALU operations at WT = 7; the pool is VALU-bound).  Tie rule unchanged:
@@ -541,21 +521,36 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_fwd_bf16(const PoolTP
 // per plane PAIR of pplane_off put chunks 0 / 1 and 2 / 3 on the same banks: rocprofv3 counted SQ_LDS_BANK_CONFLICT = 65 % of this
 // kernel's SQ_LDS_IDX_ACTIVE (four passes per read), as many LDS cycles per column as its VALU cycles.
 __device__ static inline int wplane_off(int c, int plane_b) { return c * (plane_b + 64); }
+
+// the key epilogue: 8 winners (key << 16 | tag, tag = 27 - tap) -> the bf16 x 8 maxima and the argmax bytes; relu_input: a maximum <= 0
+// (key <= 0x8000) clears the tag, and tag 0 -> 255 ("no cell")
+__device__ static inline void keys_to_out_idx(uint32_t (&best)[8], int relu_input, uint4& o, uint2& id) {
+  o.x = keys_to_bf16x2((best[0] >> 16) | (best[1] & 0xffff0000u));
+  o.y = keys_to_bf16x2((best[2] >> 16) | (best[3] & 0xffff0000u));
+  o.z = keys_to_bf16x2((best[4] >> 16) | (best[5] & 0xffff0000u));
+  o.w = keys_to_bf16x2((best[6] >> 16) | (best[7] & 0xffff0000u));
+  if (relu_input) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if ((best[e] >> 16) <= 0x8000u) best[e] &= ~255u;
+  }
+  uint32_t ix[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) { const uint32_t tg = best[e] & 255u; ix[e] = tg ? 27u - tg : 255u; }
+  id.x = ix[0] | (ix[1] << 8) | (ix[2] << 16) | (ix[3] << 24);
+  id.y = ix[4] | (ix[5] << 8) | (ix[6] << 16) | (ix[7] << 24);
+}
+
 template <int WT>
 __global__ __launch_bounds__(256, 2) void maxpool_s1_wrun_fwd_bf16(const PoolTP p) {
-  constexpr int EPL = 8, SLABC = 32;
+  constexpr int SLABC = 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const PoolKP& k = p.k;
   const int tid = threadIdx.x, ch = tid & 3;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int c0 = cslab * SLABC + ch * EPL;
-  const bool chvalid = c0 < k.C;
-  const int ot0 = tt * p.Tt, oh0 = th * p.Ht, ow0 = tw * WT;
+  const PoolTileCtx tc = pool_tile<WT>(p, SLABC);
+  if (!tc.ok) return;
+  const int b = tc.b, c0 = tc.c0, ot0 = tc.t0, oh0 = tc.h0, ow0 = tc.w0;
+  const bool chvalid = tc.chvalid;
   const int it0 = ot0 - 1, ih0 = oh0 - 1, iw0 = ow0 - 1;
   constexpr int WH = WT + 2;                                   // = p.Wh
   const int HW = p.Hh * WH;
@@ -572,7 +567,7 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_wrun_fwd_bf16(const PoolTP 
       const int it = it0 + a, ih = ih0 + bq, iw = iw0 + c;
       v[u] = make_uint4(0xff80ff80u, 0xff80ff80u, 0xff80ff80u, 0xff80ff80u);     // -inf
       if (hp < p.P && chvalid && (unsigned)it < (unsigned)k.Ti && (unsigned)ih < (unsigned)k.Hi && (unsigned)iw < (unsigned)k.Wi && !PF_DBG(1))
-        v[u] = *(const uint4*)(k.in + ((((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw) * k.in_ld + k.in_coff + c0) * 2);
+        v[u] = *(const uint4*)in_at<bf16_t>(k, in_pos(k, b, it, ih, iw), c0);
     }
 #pragma unroll
     for (int u = 0; u < SU; ++u) {
@@ -634,27 +629,30 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_wrun_fwd_bf16(const PoolTP 
 #pragma unroll
       for (int e = 0; e < 8; ++e) best[e] = max(max(l[e], m[e] - 1u), r[e] - 2u);
       uint4 o;
-      o.x = keys_to_bf16x2((best[0] >> 16) | (best[1] & 0xffff0000u));
-      o.y = keys_to_bf16x2((best[2] >> 16) | (best[3] & 0xffff0000u));
-      o.z = keys_to_bf16x2((best[4] >> 16) | (best[5] & 0xffff0000u));
-      o.w = keys_to_bf16x2((best[6] >> 16) | (best[7] & 0xffff0000u));
-      if (k.relu_input) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e)
-          if ((best[e] >> 16) <= 0x8000u) best[e] &= ~255u;      // tag 0 -> idx 255 ("no cell")
-      }
-      uint32_t ix[8];                                                // tag 27 - tap -> tap; tag 0 -> 255 ("no cell")
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { const uint32_t tg = best[e] & 255u; ix[e] = tg ? 27u - tg : 255u; }
       uint2 id;
-      id.x = ix[0] | (ix[1] << 8) | (ix[2] << 16) | (ix[3] << 24);
-      id.y = ix[4] | (ix[5] << 8) | (ix[6] << 16) | (ix[7] << 24);
-      const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-      if PF_DBG(4) { if (o.x == 0x12345u && id.x == 0x777u) *(uint2*)(k.idx + opos * k.C + c0) = id; continue; }
-      *(uint4*)(k.out + (opos * k.out_ld + k.out_coff + c0) * 2) = o;
-      *(uint2*)(k.idx + opos * k.C + c0) = id;
+      keys_to_out_idx(best, k.relu_input, o, id);
+      const size_t opos = out_pos(k, b, ot, oh, ow);
+      if PF_DBG(4) { if (o.x == 0x12345u && id.x == 0x777u) *(uint2*)idx_at(k, opos, c0) = id; continue; }
+      *(uint4*)out_at<bf16_t>(k, opos, c0) = o;
+      *(uint2*)idx_at(k, opos, c0) = id;
     }
   }
+}
+
+// Host side of pool_tile: the tile fields of tp for tiles t over the input or the output grid and channel slabs of slabc channels.  Returns
+// the 1-D grid, 8 * ceil(ntiles / 8) * nslab workgroups (tile_slab_of_block).
+static dim3 tile_grid(PoolTP& tp, const flk_pool_args* a, flk_tile t, bool over_input, int slabc) {
+  const int Tn = over_input ? a->Ti : a->To, Hn = over_input ? a->Hi : a->Ho, Wn = over_input ? a->Wi : a->Wo;
+  tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
+  tp.nTt = (Tn + t.Tt - 1) / t.Tt; tp.nTh = (Hn + t.Ht - 1) / t.Ht; tp.nTw = (Wn + t.Wt - 1) / t.Wt;
+  tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + slabc - 1) / slabc;
+  return dim3((unsigned)((tp.ntiles + 7) / 8 * 8 * tp.nslab));
+}
+// the halo box of a stride-1 tile and the size of its LDS plane (16 bytes per position and channel chunk)
+static void tile_halo(PoolTP& tp, const flk_pool_args* a) {
+  tp.Th = tp.Tt + a->kt - 1; tp.Hh = tp.Ht + a->kh - 1; tp.Wh = tp.Wt + a->kw - 1;
+  tp.P = tp.Th * tp.Hh * tp.Wh;
+  tp.plane_b = (tp.P * 16 + 255) / 256 * 256;
 }
 
 // tile of the W-run kernel: WT outputs along w, (Tt, Ht) with Tt*Ht <= 64 (one (t,h) pair per thread quad) and a halo <= 1008 positions
@@ -673,17 +671,12 @@ static int launch_wrun_fwd(const PoolKP& kp, const flk_pool_args* a, hipStream_t
       const double score = eff * (double)(Tt * Ht * WT) / (double)halo * (Tt * Ht >= 48 ? 1.0 : (double)(Tt * Ht) / 48.0);
       if (score > bestScore) { bestScore = score; bestT = Tt; bestH = Ht; }
     }
-  tp.Tt = bestT; tp.Ht = bestH; tp.Wt = WT; tp.rows = bestT * bestH * WT;
-  tp.nTt = (a->To + tp.Tt - 1) / tp.Tt; tp.nTh = (a->Ho + tp.Ht - 1) / tp.Ht; tp.nTw = (a->Wo + WT - 1) / WT;
-  tp.Th = tp.Tt + 2; tp.Hh = tp.Ht + 2; tp.Wh = WT + 2;
-  tp.P = tp.Th * tp.Hh * tp.Wh;
-  tp.plane_b = (tp.P * 16 + 255) / 256 * 256;
+  const dim3 grid = tile_grid(tp, a, flk_tile{bestT, bestH, WT}, false, 32);
+  tile_halo(tp, a);                                              // (3x3x3: Tt + 2, Ht + 2, WT + 2)
   const size_t lds = 4 * (size_t)tp.plane_b + 256;               // (wplane_off: 64 bytes of skew per plane)
-  tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + 31) / 32;
 #ifdef FLK_ABLATE
   tp.dbg = flk_ablate_env("FLK_PF_DBG");
 #endif
-  const dim3 grid((unsigned)((tp.ntiles + 7) / 8 * 8 * tp.nslab));
   static bool attr_set[FLK_MAX_DEVICES] = {};
   if (int rc = flk_raise_lds_limit((const void*)maxpool_s1_wrun_fwd_bf16<WT>, 96 * 1024, attr_set)) return rc;
   FLK_LAUNCH_KERNEL((maxpool_s1_wrun_fwd_bf16<WT>), grid, dim3(256), lds, s, tp);
@@ -698,16 +691,11 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_bwd(const PoolTP p) {
   const PoolKP& k = p.k;
   char* const sidx = smem + 4 * p.plane_b + 64;            // [chunk][halo position][EPL bytes]
   const int tid = threadIdx.x, ch = tid & 3;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int c0 = cslab * SLABC + ch * EPL;
-  const bool chvalid = c0 < k.C;
+  const PoolTileCtx tc = pool_tile(p, SLABC);
+  if (!tc.ok) return;
+  const int b = tc.b, c0 = tc.c0, i_t0 = tc.t0, i_h0 = tc.h0, i_w0 = tc.w0;
+  const bool chvalid = tc.chvalid;
   // tile of INPUT cells [i0, i0+tile); windows o with o - pad <= i <= o - pad + k-1  ->  o in [i - (k-1-pad), i + pad]
-  const int i_t0 = tt * p.Tt, i_h0 = th * p.Ht, i_w0 = tw * p.Wt;
   const int o_t0 = i_t0 - (k.kt - 1 - k.pt), o_h0 = i_h0 - (k.kh - 1 - k.ph), o_w0 = i_w0 - (k.kw - 1 - k.pw);
   const int HW = p.Hh * p.Wh;
   for (int hp = tid >> 2; hp < p.P; hp += 64) {
@@ -718,9 +706,9 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_bwd(const PoolTP p) {
 #pragma unroll
     for (int e = 0; e < EPL; ++e) id[e] = 255;                // never matches a tap
     if (chvalid && (unsigned)ot < (unsigned)k.To && (unsigned)oh < (unsigned)k.Ho && (unsigned)ow < (unsigned)k.Wo) {
-      const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-      g = *(const uint4*)(k.gout + (opos * k.gout_ld + k.gout_coff + c0) * sizeof(T));
-      PV<T>::ldidx(k.idx + opos * k.C + c0, id);
+      const size_t opos = out_pos(k, b, ot, oh, ow);
+      g = *(const uint4*)gout_at<T>(k, opos, c0);
+      PV<T>::ldidx(idx_at(k, opos, c0), id);
     }
     *(uint4*)(smem + pplane_off(ch, p.plane_b) + hp * 16) = g;
     PV<T>::stidx((uint8_t*)sidx + ((size_t)ch * p.P + hp) * EPL, id);
@@ -753,14 +741,7 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_bwd(const PoolTP p) {
           for (int e = 0; e < EPL; ++e)
             if (id[e] == tap) g[e] += go[e];
         }
-    const size_t ipos = (((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw);
-    if (k.mask) {
-      float mk[EPL];
-      PV<T>::ld(k.mask + (ipos * k.mask_ld + k.mask_coff + c0) * sizeof(T), mk);
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) g[e] = mk[e] > 0.f ? g[e] : 0.f;
-    }
-    PV<T>::st(k.gin + (ipos * k.gin_ld + k.gin_coff + c0) * sizeof(T), g);
+    mask_and_store<T>(k, in_pos(k, b, it, ih, iw), c0, g, k.mask != nullptr);
   }
 }
 
@@ -768,6 +749,89 @@ __global__ __launch_bounds__(256, 2) void maxpool_s1_tiled_bwd(const PoolTP p) {
 // one LDS atomic per element instead of kt*kh*kw index compares per input cell (the gather form above is VALU-bound).
 // A workgroup owns a tile of INPUT cells (accumulators in LDS) and walks the windows that can reach it, reading
 // idx / gout straight from global memory.
+// ---- the phases the three scatter kernels (maxpool_scatter_bwd, maxpool_scatter_gemm_bwd, maxpool_scatter_gemm_bwd_reg) share ----
+
+// The windows that reach a tile of INPUT cells with origin (i_t0, i_h0, i_w0): o in [ceil((i0 + pad - k + 1) / s),
+// floor((i0 + tile - 1 + pad) / s)] per dimension, clipped to the grid -- a box of P = nt * nh * nw windows, walked by a linear index hp.
+struct PoolReach {
+  int i_t0, i_h0, i_w0, o_t0, o_h0, o_w0, nw, nhw, P;
+  float inv_hw, inv_w;
+  // window hp (0 <= hp < P) -> its linear output position and its origin relative to the tile's (window o covers cells o * s - pad + d)
+  __device__ inline void decode(const PoolKP& k, int b, int hp, size_t& opos, int& lt0, int& lh0, int& lw0) const {
+    const int a = (int)(((float)hp + 0.5f) * inv_hw), rem = hp - a * nhw;        // (qdiv: the float quotients truncate exactly)
+    const int bq = (int)(((float)rem + 0.5f) * inv_w), c = rem - bq * nw;
+    const int ot = o_t0 + a, oh = o_h0 + bq, ow = o_w0 + c;
+    opos = out_pos(k, b, ot, oh, ow);
+    lt0 = ot * k.st - k.pt - i_t0; lh0 = oh * k.sh - k.ph - i_h0; lw0 = ow * k.sw - k.pw - i_w0;
+  }
+};
+__device__ static inline PoolReach pool_reach(const PoolKP& k, int i_t0, int i_h0, int i_w0, int Tt, int Ht, int Wt) {
+  PoolReach r;
+  r.i_t0 = i_t0; r.i_h0 = i_h0; r.i_w0 = i_w0;
+  r.o_t0 = max(0, (i_t0 + k.pt - k.kt + k.st) / k.st); const int o_t1 = min(k.To - 1, (i_t0 + Tt - 1 + k.pt) / k.st);
+  r.o_h0 = max(0, (i_h0 + k.ph - k.kh + k.sh) / k.sh); const int o_h1 = min(k.Ho - 1, (i_h0 + Ht - 1 + k.ph) / k.sh);
+  r.o_w0 = max(0, (i_w0 + k.pw - k.kw + k.sw) / k.sw); const int o_w1 = min(k.Wo - 1, (i_w0 + Wt - 1 + k.pw) / k.sw);
+  const int nt = max(0, o_t1 - r.o_t0 + 1), nh = max(0, o_h1 - r.o_h0 + 1);
+  r.nw = max(0, o_w1 - r.o_w0 + 1);
+  r.nhw = nh * r.nw; r.P = nt * r.nhw;
+  r.inv_hw = 1.0f / (float)max(r.nhw, 1); r.inv_w = 1.0f / (float)max(r.nw, 1);
+  return r;
+}
+
+// The bf16 forms accumulate in 32-bit FIXED POINT with a per-workgroup power-of-two scale: ds_add_f32 (and
+// ds_cmpst_rtn_b32) run ~10x slower than the integer LDS atomics on gfx950 (measured: 0.28 ms vs 0.12 ms for the
+// Mixed_3c pool), and integer sums are associative, so the result does not depend on the order the waves arrive in.
+// Scale = 2^E / 2^floor(log2 max|gout|) over the windows this workgroup reads: |v * scale| < 2^(E+1) (a bf16 value times a power
+// of two: an integer multiple of 2^(E-7), never rounded up to 2^(E+1)).  A cell receives at most n = ceil(kt/st) * ceil(kh/sh) *
+// ceil(kw/sw) addends, and the host picks E = min(24, 30 - ceil(log2 n)) (fixed_point_exponent), so |sum| < n * 2^(E+1) <= 2^31:
+// E = 24 for n <= 64 (every I3D pool: 27 addends < 2^30), 23 for n <= 128, 22 for n <= 255.  A bf16 gradient (8 significant bits)
+// within 2^-(E-7) of the largest one is represented exactly; every addend is off by at most 2^-(E+1) * max|gout| and a cell by
+// less than n * 2^-(E+1) * max|gout| (27 * 2^-25 * max|gout| for 3x3x3 / 1), far below the bf16 rounding of the stored result.
+// fp32 mode (the parity mode) keeps exact float atomics.
+// Magnitudes travel as fp32 bit patterns (they order like unsigned integers): fx_wave_max is the wave's largest, which lane 0 of every
+// wave then publishes with atomicMax into the workgroup's word smax; fx_scale turns that word into the scale and its inverse.
+__device__ static inline unsigned fx_wave_max(unsigned mx) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
+  return mx;
+}
+__device__ static inline void fx_scale(unsigned smax, int fx_e, float& scale, float& inv_scale) {
+  int ex = (int)(smax >> 23);                                  // biased exponent of the largest magnitude
+  ex = min(max(ex, 26), 254);                                  // (inf/nan gradients are not representable; clamp)
+  scale = __uint_as_float((unsigned)(127 + fx_e + 127 - ex) << 23);
+  inv_scale = __uint_as_float((unsigned)(127 - fx_e - 127 + ex) << 23);
+}
+
+// Tap (an argmax byte) of the window whose origin is (lt0, lh0, lw0) relative to the tile: add(cell) with the cell's index in the tile,
+// unless the cell lies outside the tile or the byte is 255 ("no cell": it decodes to dt >= kt).  m_khkw / m_kw = magic(kh * kw) /
+// magic(kw): tap / d as (tap * m) >> 20.
+template <typename F>
+__device__ static inline void scatter_tap_cell(const PoolTP& p, int tap, unsigned m_khkw, unsigned m_kw, int lt0, int lh0, int lw0, F add) {
+  const PoolKP& k = p.k;
+  const int dt = (int)(((unsigned)tap * m_khkw) >> 20), r2 = tap - dt * (k.kh * k.kw);
+  const int dh = (int)(((unsigned)r2 * m_kw) >> 20), dw = r2 - dh * k.kw;
+  const int lt = lt0 + dt, lh = lh0 + dh, lw = lw0 + dw;
+  if ((unsigned)lt < (unsigned)p.Tt && (unsigned)lh < (unsigned)p.Ht && (unsigned)lw < (unsigned)p.Wt && dt < k.kt) add((lt * p.Ht + lh) * p.Wt + lw);
+}
+
+// Write the tile: thread = (cell r, 16-byte channel chunk); cells past the tensor's edge are skipped.  Element e of cell r sits at
+// acc0[e * es + r] (acc0: this chunk's first accumulator plane), as a fixed-point integer (FIXED) or a float.
+template <typename T, bool FIXED, bool MASKABLE>
+__device__ static inline void write_tile(const PoolTP& p, const PoolTileCtx& tc, const float* acc0, int es, float inv_scale) {
+  constexpr int EPL = PV<T>::EPL;
+  const PoolKP& k = p.k;
+  const int hw = p.Ht * p.Wt;
+  for (int r = threadIdx.x >> 2; r < p.rows; r += 64) {
+    int rt, rh, rw; split3(r, hw, 1.0f / (float)hw, p.Wt, 1.0f / (float)p.Wt, rt, rh, rw);
+    const int it = tc.t0 + rt, ih = tc.h0 + rh, iw = tc.w0 + rw;
+    if (it >= k.Ti || ih >= k.Hi || iw >= k.Wi) continue;
+    float g[EPL];
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) g[e] = FIXED ? (float)(int)__float_as_uint(acc0[e * es + r]) * inv_scale : acc0[e * es + r];
+    mask_and_store<T>(k, in_pos(k, tc.b, it, ih, iw), tc.c0, g, MASKABLE && k.mask);
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, unsigned m_khkw, unsigned m_kw) {
   constexpr int EPL = PV<T>::EPL, SLABC = 4 * EPL, UNR = 4;
@@ -778,34 +842,14 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
   const int RS = p.plane_b;
   const PoolKP& k = p.k;
   const int tid = threadIdx.x, ch = tid & 3;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int c0 = cslab * SLABC + ch * EPL;
-  const bool chvalid = c0 < k.C;
-  const int i_t0 = tt * p.Tt, i_h0 = th * p.Ht, i_w0 = tw * p.Wt;
-  // windows that touch the tile: o in [ceil((i0 + pad - k + 1) / s), floor((i0 + tile - 1 + pad) / s)], clipped to the grid
-  const int o_t0 = max(0, (i_t0 + k.pt - k.kt + k.st) / k.st), o_t1 = min(k.To - 1, (i_t0 + p.Tt - 1 + k.pt) / k.st);
-  const int o_h0 = max(0, (i_h0 + k.ph - k.kh + k.sh) / k.sh), o_h1 = min(k.Ho - 1, (i_h0 + p.Ht - 1 + k.ph) / k.sh);
-  const int o_w0 = max(0, (i_w0 + k.pw - k.kw + k.sw) / k.sw), o_w1 = min(k.Wo - 1, (i_w0 + p.Wt - 1 + k.pw) / k.sw);
-  const int nt = max(0, o_t1 - o_t0 + 1), nh = max(0, o_h1 - o_h0 + 1), nw = max(0, o_w1 - o_w0 + 1);
-  const int nhw = nh * nw, P = nt * nhw;
-  const float inv_hw = 1.0f / (float)max(nhw, 1), inv_w = 1.0f / (float)max(nw, 1);
+  const PoolTileCtx tc = pool_tile(p, SLABC);
+  if (!tc.ok) return;
+  const int b = tc.b, c0 = tc.c0;
+  const bool chvalid = tc.chvalid;
+  const PoolReach rc = pool_reach(k, tc.t0, tc.h0, tc.w0, p.Tt, p.Ht, p.Wt);
+  const int P = rc.P;
   for (int i = tid; i < 4 * RS * EPL; i += 256) acc[i] = 0.f;
-  // bf16 mode accumulates in 32-bit FIXED POINT with a per-workgroup power-of-two scale: ds_add_f32 (and
-  // ds_cmpst_rtn_b32) run ~10x slower than the integer LDS atomics on gfx950 (measured: 0.28 ms vs 0.12 ms for the
-  // Mixed_3c pool), and integer sums are associative, so the result does not depend on the order the waves arrive in.
-  // Scale = 2^E / 2^floor(log2 max|gout|) over the windows this workgroup reads: |v * scale| < 2^(E+1) (a bf16 value times a power
-  // of two: an integer multiple of 2^(E-7), never rounded up to 2^(E+1)).  A cell receives at most n = ceil(kt/st) * ceil(kh/sh) *
-  // ceil(kw/sw) addends, and the host picks E = min(24, 30 - ceil(log2 n)) (fixed_point_exponent), so |sum| < n * 2^(E+1) <= 2^31:
-  // E = 24 for n <= 64 (every I3D pool: 27 addends < 2^30), 23 for n <= 128, 22 for n <= 255.  A bf16 gradient (8 significant bits)
-  // within 2^-(E-7) of the largest one is represented exactly; every addend is off by at most 2^-(E+1) * max|gout| and a cell by
-  // less than n * 2^-(E+1) * max|gout| (27 * 2^-25 * max|gout| for 3x3x3 / 1), far below the bf16 rounding of the stored result.
-  // fp32 mode (the parity mode) keeps exact float atomics.
-  constexpr bool FIXED = sizeof(T) == 2;
+  constexpr bool FIXED = sizeof(T) == 2;                     // (fixed point: see fx_scale)
   float scale = 1.f, inv_scale = 1.f;
   if (FIXED) {
     unsigned* const smax = (unsigned*)(acc + 4 * RS * EPL);
@@ -814,26 +858,20 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
     unsigned mx = 0u;
     if (chvalid)
       for (int hp = tid >> 2; hp < P; hp += 64) {
-        const int a = (int)(((float)hp + 0.5f) * inv_hw), rem = hp - a * nhw;
-        const int bq = (int)(((float)rem + 0.5f) * inv_w), c = rem - bq * nw;
-        const size_t opos = (((size_t)(b * k.To + o_t0 + a) * k.Ho + o_h0 + bq) * k.Wo + o_w0 + c);
-        const uint4 g = *(const uint4*)(k.gout + (opos * k.gout_ld + k.gout_coff + c0) * sizeof(T));
-        // largest |bf16| of the 8 packed values, as an fp32 bit pattern (magnitudes order like unsigned integers)
+        size_t opos; int lt0, lh0, lw0;
+        rc.decode(k, b, hp, opos, lt0, lh0, lw0);
+        const uint4 g = *(const uint4*)gout_at<T>(k, opos, c0);
+        // largest |bf16| of the 8 packed values, as an fp32 bit pattern
         const unsigned w[4] = {g.x, g.y, g.z, g.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) mx = max(mx, max((w[i] << 16) & 0x7fffffffu, w[i] & 0x7fff0000u));
       }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
+    mx = fx_wave_max(mx);
     if ((tid & 63) == 0) atomicMax(smax, mx);
     __syncthreads();
-    int ex = (int)(*smax >> 23);                               // biased exponent of the largest magnitude
-    ex = min(max(ex, 26), 254);                                // (inf/nan gradients are not representable; clamp)
-    scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
-    inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
+    fx_scale(*smax, p.fx_e, scale, inv_scale);
   }
   __syncthreads();
-  const int khkw = k.kh * k.kw;
   float* const myacc = acc + ch * RS;
   if (chvalid)
     for (int base = tid >> 2; base < P; base += 64 * UNR) {
@@ -843,52 +881,26 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_bwd(const PoolTP p, un
       // all loads of the UNR positions are issued before the first atomic: one memory round trip per UNR positions
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
-        const int hp = min(base + u * 64, P - 1);
-        const int a = (int)(((float)hp + 0.5f) * inv_hw), rem = hp - a * nhw;
-        const int bq = (int)(((float)rem + 0.5f) * inv_w), c = rem - bq * nw;
-        const int ot = o_t0 + a, oh = o_h0 + bq, ow = o_w0 + c;
-        const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-        PV<T>::ldidx(k.idx + opos * k.C + c0, id[u]);
-        PV<T>::ld(k.gout + (opos * k.gout_ld + k.gout_coff + c0) * sizeof(T), go[u]);
-        // window o covers cells o*s - pad + d; local cell = that - tile origin
-        lt0[u] = ot * k.st - k.pt - i_t0; lh0[u] = oh * k.sh - k.ph - i_h0; lw0[u] = ow * k.sw - k.pw - i_w0;
+        size_t opos;
+        rc.decode(k, b, min(base + u * 64, P - 1), opos, lt0[u], lh0[u], lw0[u]);
+        PV<T>::ldidx(idx_at(k, opos, c0), id[u]);
+        PV<T>::ld(gout_at<T>(k, opos, c0), go[u]);
       }
 #pragma unroll
       for (int u = 0; u < UNR; ++u) {
         if (base + u * 64 >= P) break;
 #pragma unroll
         for (int e = 0; e < EPL; ++e) {
-          const int tap = id[u][e];                                    // 255 ("no cell") decodes out of range below
-          const int dt = (int)(((unsigned)tap * m_khkw) >> 20), r2 = tap - dt * khkw;
-          const int dh = (int)(((unsigned)r2 * m_kw) >> 20), dw = r2 - dh * k.kw;
-          const int lt = lt0[u] + dt, lh = lh0[u] + dh, lw = lw0[u] + dw;
-          if ((unsigned)lt < (unsigned)p.Tt && (unsigned)lh < (unsigned)p.Ht && (unsigned)lw < (unsigned)p.Wt && dt < k.kt) {
-            float* const cell = &myacc[e * 4 * RS + (lt * p.Ht + lh) * p.Wt + lw];
-            if (FIXED) atomicAdd((unsigned*)cell, (unsigned)__float2int_rn(go[u][e] * scale));
-            else atomicAdd(cell, go[u][e]);
-          }
+          scatter_tap_cell(p, id[u][e], m_khkw, m_kw, lt0[u], lh0[u], lw0[u], [&](int cell) {
+            if (FIXED) atomicAdd((unsigned*)&myacc[e * 4 * RS + cell], (unsigned)__float2int_rn(go[u][e] * scale));
+            else atomicAdd(&myacc[e * 4 * RS + cell], go[u][e]);
+          });
         }
       }
     }
   __syncthreads();
   if (!chvalid) return;
-  const int hw = p.Ht * p.Wt;
-  for (int r = tid >> 2; r < p.rows; r += 64) {
-    int rt, rh, rw; split3(r, hw, 1.0f / (float)hw, p.Wt, 1.0f / (float)p.Wt, rt, rh, rw);
-    const int it = i_t0 + rt, ih = i_h0 + rh, iw = i_w0 + rw;
-    if (it >= k.Ti || ih >= k.Hi || iw >= k.Wi) continue;
-    float g[EPL];
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) g[e] = FIXED ? (float)(int)__float_as_uint(myacc[e * 4 * RS + r]) * inv_scale : myacc[e * 4 * RS + r];
-    const size_t ipos = (((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw);
-    if (k.mask) {
-      float mk[EPL];
-      PV<T>::ld(k.mask + (ipos * k.mask_ld + k.mask_coff + c0) * sizeof(T), mk);
-#pragma unroll
-      for (int e = 0; e < EPL; ++e) g[e] = mk[e] > 0.f ? g[e] : 0.f;
-    }
-    PV<T>::st(k.gin + (ipos * k.gin_ld + k.gin_coff + c0) * sizeof(T), g);
-  }
+  write_tile<T, FIXED, true>(p, tc, myacc, 4 * RS, inv_scale);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -915,54 +927,45 @@ struct PoolGemmP {
   int dbg;                                    // timing experiments only (FLK_PG_DBG): 1 = no atomics, 2 = no tile write, 4 = no g loads, 8 = no index loads, 16 = no zeroing
 };
 
+// MFMA operands of the two fused forms.  A: the weights of slab cslab, channels [32 cslab, +32), all K (flk_pool_gemm_weights_create's
+// packing).  B: the g row of output position opos, lane (q, m) = 16 bytes of position m per k-step.
+typedef __bf16 frag8 __attribute__((ext_vector_type(8)));
+template <int KS>
+__device__ static inline void load_wpack(const char* wpack, int cslab, int lane, frag8 (&af)[KS][2]) {
+  const char* wp = wpack + ((size_t)cslab * KS * 2 * 64 + lane) * 16;
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks)
+#pragma unroll
+    for (int f = 0; f < 2; ++f) af[ks][f] = *(const frag8*)(wp + (size_t)(ks * 2 + f) * 1024);
+}
+template <int KS>
+__device__ static inline void load_g(const PoolGemmP& pg, size_t opos, int q, frag8 (&bf)[KS]) {
+  const char* gp = pg.g + slice_off<bf16_t>(opos, pg.g_ld, pg.g_coff, q * 8);
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) bf[ks] = *(const frag8*)(gp + ks * 64);
+}
+
 template <int KS>
 __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGemmP pg, unsigned m_khkw, unsigned m_kw) {
-  typedef __bf16 frag8 __attribute__((ext_vector_type(8)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* const acc = (unsigned*)smem;     // [32 channels][RS cells] fixed-point accumulators
   const PoolTP& p = pg.t;
   const PoolKP& k = p.k;
   const int RS = p.plane_b;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, m = lane & 15;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int i_t0 = tt * p.Tt, i_h0 = th * p.Ht, i_w0 = tw * p.Wt;
-  const int o_t0 = max(0, (i_t0 + k.pt - k.kt + k.st) / k.st), o_t1 = min(k.To - 1, (i_t0 + p.Tt - 1 + k.pt) / k.st);
-  const int o_h0 = max(0, (i_h0 + k.ph - k.kh + k.sh) / k.sh), o_h1 = min(k.Ho - 1, (i_h0 + p.Ht - 1 + k.ph) / k.sh);
-  const int o_w0 = max(0, (i_w0 + k.pw - k.kw + k.sw) / k.sw), o_w1 = min(k.Wo - 1, (i_w0 + p.Wt - 1 + k.pw) / k.sw);
-  const int nt = max(0, o_t1 - o_t0 + 1), nh = max(0, o_h1 - o_h0 + 1), nw = max(0, o_w1 - o_w0 + 1);
-  const int nhw = nh * nw, P = nt * nhw;
-  const float inv_hw = 1.0f / (float)max(nhw, 1), inv_w = 1.0f / (float)max(nw, 1);
+  const PoolTileCtx tc = pool_tile(p, 32);
+  if (!tc.ok) return;
+  const int b = tc.b, cslab = tc.cslab;
+  const PoolReach rc = pool_reach(k, tc.t0, tc.h0, tc.w0, p.Tt, p.Ht, p.Wt);
+  const int P = rc.P;
   for (int i = tid; i < 32 * RS; i += 256) acc[i] = 0u;
   unsigned* const smax = acc + 32 * RS;
   if (tid == 0) *smax = 0u;
-
-  // A fragments of this slab: channels [32 cslab, +32), all K
   frag8 af[KS][2];
-  {
-    const char* wp = pg.wpack + ((size_t)cslab * KS * 2 * 64 + lane) * 16;
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int f = 0; f < 2; ++f) af[ks][f] = *(const frag8*)(wp + (size_t)(ks * 2 + f) * 1024);
-  }
-  // window position hp -> linear output position and its origin relative to the tile
-  auto decode = [&](int hp, size_t& opos, int& lt0, int& lh0, int& lw0) {
-    const int a = (int)(((float)hp + 0.5f) * inv_hw), rem = hp - a * nhw;
-    const int bq = (int)(((float)rem + 0.5f) * inv_w), c = rem - bq * nw;
-    const int ot = o_t0 + a, oh = o_h0 + bq, ow = o_w0 + c;
-    opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-    lt0 = ot * k.st - k.pt - i_t0; lh0 = oh * k.sh - k.ph - i_h0; lw0 = ow * k.sw - k.pw - i_w0;
-  };
+  load_wpack<KS>(pg.wpack, cslab, lane, af);
   auto product = [&](size_t opos, f32x4 (&v)[2]) {
-    const char* gp = pg.g + (opos * pg.g_ld + pg.g_coff + q * 8) * 2;
     frag8 bf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf[ks] = *(const frag8*)(gp + ks * 64);
+    load_g<KS>(pg, opos, q, bf);
     v[0] = f32x4{0.f, 0.f, 0.f, 0.f}; v[1] = v[0];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -974,9 +977,8 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
   // ---- pass 1: the largest |value| this workgroup will add (as an fp32 bit pattern: magnitudes order like unsigned integers) ----
   unsigned mx = 0u;
   for (int base = wave * 16; base < P; base += 64) {
-    const int hp = min(base + m, P - 1);
     size_t opos; int lt0, lh0, lw0;
-    decode(hp, opos, lt0, lh0, lw0);
+    rc.decode(k, b, min(base + m, P - 1), opos, lt0, lh0, lw0);
     f32x4 v[2];
     product(opos, v);
 #pragma unroll
@@ -984,24 +986,19 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
 #pragma unroll
       for (int j = 0; j < 4; ++j) mx = max(mx, __float_as_uint(v[f][j]) & 0x7fffffffu);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
+  mx = fx_wave_max(mx);
   if (lane == 0) atomicMax(smax, mx);
   __syncthreads();
-  int ex = (int)(*smax >> 23);
-  ex = min(max(ex, 26), 254);
-  const float scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
-  const float inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
+  float scale, inv_scale;
+  fx_scale(*smax, p.fx_e, scale, inv_scale);
   // ---- pass 2: the same products, scattered ----
-  const int khkw = k.kh * k.kw;
   for (int base = wave * 16; base < P; base += 64) {
-    const int hp = min(base + m, P - 1);
     const bool live = base + m < P;
     size_t opos; int lt0, lh0, lw0;
-    decode(hp, opos, lt0, lh0, lw0);
+    rc.decode(k, b, min(base + m, P - 1), opos, lt0, lh0, lw0);
     unsigned ib[2];
 #pragma unroll
-    for (int f = 0; f < 2; ++f) ib[f] = *(const unsigned*)(k.idx + opos * k.C + cslab * 32 + f * 16 + q * 4);
+    for (int f = 0; f < 2; ++f) ib[f] = *(const unsigned*)idx_at(k, opos, cslab * 32 + f * 16 + q * 4);
     f32x4 v[2];
     product(opos, v);
     if (!live) continue;
@@ -1009,29 +1006,13 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
     for (int f = 0; f < 2; ++f)
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const int tap = (int)((ib[f] >> (8 * j)) & 255u);              // 255 ("no cell") decodes out of range below
-        const int dt = (int)(((unsigned)tap * m_khkw) >> 20), r2 = tap - dt * khkw;
-        const int dh = (int)(((unsigned)r2 * m_kw) >> 20), dw = r2 - dh * k.kw;
-        const int lt = lt0 + dt, lh = lh0 + dh, lw = lw0 + dw;
-        if ((unsigned)lt < (unsigned)p.Tt && (unsigned)lh < (unsigned)p.Ht && (unsigned)lw < (unsigned)p.Wt && dt < k.kt)
-          atomicAdd(&acc[(f * 16 + q * 4 + j) * RS + (lt * p.Ht + lh) * p.Wt + lw], (unsigned)__float2int_rn(v[f][j] * scale));
+        scatter_tap_cell(p, (int)((ib[f] >> (8 * j)) & 255u), m_khkw, m_kw, lt0, lh0, lw0,
+                         [&](int cell) { atomicAdd(&acc[(f * 16 + q * 4 + j) * RS + cell], (unsigned)__float2int_rn(v[f][j] * scale)); });
       }
   }
   __syncthreads();
-  // ---- write the tile: thread = (cell, 16-byte channel chunk) ----
-  const int ch = tid & 3, c0 = cslab * 32 + ch * 8;
-  if (c0 >= k.C) return;
-  const int hw = p.Ht * p.Wt;
-  for (int r = tid >> 2; r < p.rows; r += 64) {
-    int rt, rh, rw; split3(r, hw, 1.0f / (float)hw, p.Wt, 1.0f / (float)p.Wt, rt, rh, rw);
-    const int it = i_t0 + rt, ih = i_h0 + rh, iw = i_w0 + rw;
-    if (it >= k.Ti || ih >= k.Hi || iw >= k.Wi) continue;
-    float g[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)(int)acc[(ch * 8 + e) * RS + r] * inv_scale;
-    const size_t ipos = (((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw);
-    PV<bf16_t>::st(k.gin + (ipos * k.gin_ld + k.gin_coff + c0) * 2, g);
-  }
+  if (!tc.chvalid) return;
+  write_tile<bf16_t, true, false>(p, tc, (const float*)acc + (tid & 3) * 8 * RS, RS, inv_scale);
 }
 
 // The same kernel for tiles reached by at most 64 * NIT windows (the (4,7,7) tiles of the I3D blocks: 486): a wave's NIT passes are
@@ -1041,7 +1022,7 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
 // scatter's per-element decode (tap -> (dt,dh,dw), three bound checks, address: ~27 instructions x 8 elements x 8 passes per lane, one wave
 // per SIMD and workgroup).  3x3x3 windows only: which taps of a window land inside the tile is a 27-bit mask computed once per window
 // (8 elements share it), and a tap's cell offset comes from a 256-entry table in LDS: ~12 instructions per element.
-// Measured (Mixed_3c, 8 x 32 x 28 x 28 x 256 channels, K = 64; tools/pool_gemm_time.py, FLK_PG_DBG ablations): loop form 192 us, this form
+// Measured (Mixed_3c, 8 x 32 x 28 x 28 x 256 channels, K = 64; tools/pool_time.py, FLK_PG_DBG ablations): loop form 192 us, this form
 // 161 us; without atomics 137, without the tile write 138, without g loads 145, without index loads 138, without all of them and the
 // zeroing 80 us -- what is left is the decode of 486 windows x 32 channels per 196-cell tile (2.48x the cells: the windows that reach a
 // tile overlap its neighbours'), ~45 us of VALU time at ~12 instructions per element, plus the per-workgroup chain.  Tried and dropped:
@@ -1051,26 +1032,17 @@ __global__ __launch_bounds__(256, 4) void maxpool_scatter_gemm_bwd(const PoolGem
 // weights / index bytes prefetched (169 us: 246 VGPRs, two workgroups per CU).
 template <int KS, int NIT, int NB>
 __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd_reg(const PoolGemmP pg, unsigned m_khkw, unsigned m_kw) {
-  typedef __bf16 frag8 __attribute__((ext_vector_type(8)));
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned* const acc = (unsigned*)smem;     // [32 channels][RS cells] fixed-point accumulators
   const PoolTP& p = pg.t;
   const PoolKP& k = p.k;
   const int RS = p.plane_b;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, m = lane & 15;
-  int bid, cslab;
-  if (!tile_slab_of_block(p, bid, cslab)) return;
-  const int tw = bid % p.nTw; bid /= p.nTw;
-  const int th = bid % p.nTh; bid /= p.nTh;
-  const int tt = bid % p.nTt;
-  const int b = bid / p.nTt;
-  const int i_t0 = tt * p.Tt, i_h0 = th * p.Ht, i_w0 = tw * p.Wt;
-  const int o_t0 = max(0, (i_t0 + k.pt - k.kt + k.st) / k.st), o_t1 = min(k.To - 1, (i_t0 + p.Tt - 1 + k.pt) / k.st);
-  const int o_h0 = max(0, (i_h0 + k.ph - k.kh + k.sh) / k.sh), o_h1 = min(k.Ho - 1, (i_h0 + p.Ht - 1 + k.ph) / k.sh);
-  const int o_w0 = max(0, (i_w0 + k.pw - k.kw + k.sw) / k.sw), o_w1 = min(k.Wo - 1, (i_w0 + p.Wt - 1 + k.pw) / k.sw);
-  const int nt = max(0, o_t1 - o_t0 + 1), nh = max(0, o_h1 - o_h0 + 1), nw = max(0, o_w1 - o_w0 + 1);
-  const int nhw = nh * nw, P = nt * nhw;                       // <= 64 * NIT (the host checks the tile)
-  const float inv_hw = 1.0f / (float)max(nhw, 1), inv_w = 1.0f / (float)max(nw, 1);
+  const PoolTileCtx tc = pool_tile(p, 32);
+  if (!tc.ok) return;
+  const int b = tc.b, cslab = tc.cslab;
+  const PoolReach rc = pool_reach(k, tc.t0, tc.h0, tc.w0, p.Tt, p.Ht, p.Wt);
+  const int P = rc.P;                                          // <= 64 * NIT (the host checks the tile)
   if (!PG_DBG(16)) for (int i = tid; i < 32 * RS; i += 256) acc[i] = 0u;
   unsigned* const smax = acc + 32 * RS;
   if (tid == 0) *smax = 0u;
@@ -1086,13 +1058,7 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
   unsigned mx = 0u;
   if (P > 0) {
     frag8 af[KS][2];
-    {
-      const char* wp = pg.wpack + ((size_t)cslab * KS * 2 * 64 + lane) * 16;
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-        for (int f = 0; f < 2; ++f) af[ks][f] = *(const frag8*)(wp + (size_t)(ks * 2 + f) * 1024);
-    }
+    load_wpack<KS>(pg.wpack, cslab, lane, af);
 #pragma unroll
     for (int i0 = 0; i0 < NIT; i0 += NB) {
       frag8 bf[NB][KS];
@@ -1101,12 +1067,8 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
         const int i = i0 + u;
         const int hp = wave * 16 + 64 * i + m;
         const bool live = hp < P;
-        const int hc = min(hp, P - 1);
-        const int a = (int)(((float)hc + 0.5f) * inv_hw), rem = hc - a * nhw;
-        const int bq = (int)(((float)rem + 0.5f) * inv_w), c = rem - bq * nw;
-        const int ot = o_t0 + a, oh = o_h0 + bq, ow = o_w0 + c;
-        const size_t opos = (((size_t)(b * k.To + ot) * k.Ho + oh) * k.Wo + ow);
-        const int lt0 = ot * k.st - k.pt - i_t0, lh0 = oh * k.sh - k.ph - i_h0, lw0 = ow * k.sw - k.pw - i_w0;
+        size_t opos; int lt0, lh0, lw0;
+        rc.decode(k, b, min(hp, P - 1), opos, lt0, lh0, lw0);
         org[i] = ((lt0 * p.Ht + lh0) * p.Wt + lw0) * 4;
         // taps d = 0..2 of a dimension with 0 <= l0 + d < n, as 3 bits; the 27-bit mask is their outer product (bit (dt*3 + dh)*3 + dw)
         auto bits3 = [](int l0, int n) { return (7u << min(max(-l0, 0), 3)) & 7u & ((1u << min(max(n - l0, 0), 3)) - 1u); };
@@ -1115,10 +1077,11 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
         const unsigned et = (bt3 & 1u) | ((bt3 & 2u) << 8) | ((bt3 & 4u) << 16);         // spread by 9
         okm[i] = live ? bw3 * eh * et : 0u;
 #pragma unroll
-        for (int f = 0; f < 2; ++f) ib[i][f] = PG_DBG(8) ? (unsigned)(m * 0x01010101u) & 0x0f0f0f0fu : *(const unsigned*)(k.idx + opos * k.C + cslab * 32 + f * 16 + q * 4);
-        const char* gp = pg.g + (opos * pg.g_ld + pg.g_coff + q * 8) * 2;
+        for (int f = 0; f < 2; ++f) ib[i][f] = PG_DBG(8) ? (unsigned)(m * 0x01010101u) & 0x0f0f0f0fu : *(const unsigned*)idx_at(k, opos, cslab * 32 + f * 16 + q * 4);
+        if (PG_DBG(4)) {
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) bf[u][ks] = PG_DBG(4) ? af[ks][0] : *(const frag8*)(gp + ks * 64);
+          for (int ks = 0; ks < KS; ++ks) bf[u][ks] = af[ks][0];
+        } else load_g<KS>(pg, opos, q, bf[u]);
       }
 #pragma unroll
       for (int u = 0; u < NB; ++u) {
@@ -1136,15 +1099,12 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, off));
+  mx = fx_wave_max(mx);
   __syncthreads();                                             // the accumulators and *smax are zero
   if (lane == 0) atomicMax(smax, mx);
   __syncthreads();
-  int ex = (int)(*smax >> 23);
-  ex = min(max(ex, 26), 254);
-  const float scale = __uint_as_float((unsigned)(127 + p.fx_e + 127 - ex) << 23);
-  const float inv_scale = __uint_as_float((unsigned)(127 - p.fx_e - 127 + ex) << 23);
+  float scale, inv_scale;
+  fx_scale(*smax, p.fx_e, scale, inv_scale);
   if (P > 0) {
     // Branch-free: the 8 table reads of a window are requested together, and an element whose cell is outside the tile adds into a
     // dummy word of its own thread instead of being skipped.  (Written as  if (inside) atomicAdd(.. + lut[tap] ..)  hipcc emitted, per
@@ -1173,21 +1133,16 @@ __global__ __launch_bounds__(256, KS >= 3 ? 2 : 3) void maxpool_scatter_gemm_bwd
     }
   }
   __syncthreads();
-  // ---- write the tile: thread = (cell, 16-byte channel chunk) ----
-  const int ch = tid & 3, c0 = cslab * 32 + ch * 8;
-  if (c0 >= k.C || PG_DBG(2)) return;
-  const int hw = p.Ht * p.Wt;
-  for (int r = tid >> 2; r < p.rows; r += 64) {
-    int rt, rh, rw; split3(r, hw, 1.0f / (float)hw, p.Wt, 1.0f / (float)p.Wt, rt, rh, rw);
-    const int it = i_t0 + rt, ih = i_h0 + rh, iw = i_w0 + rw;
-    if (it >= k.Ti || ih >= k.Hi || iw >= k.Wi) continue;
-    float g[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = (float)(int)acc[(ch * 8 + e) * RS + r] * inv_scale;
-    const size_t ipos = (((size_t)(b * k.Ti + it) * k.Hi + ih) * k.Wi + iw);
-    PV<bf16_t>::st(k.gin + (ipos * k.gin_ld + k.gin_coff + c0) * 2, g);
-  }
+  if (!tc.chvalid || PG_DBG(2)) return;
+  write_tile<bf16_t, true, false>(p, tc, (const float*)acc + (tid & 3) * 8 * RS, RS, inv_scale);
 }
+
+// the most windows that reach a (Tt, Ht, Wt) tile of input cells (pool_reach's box at its largest)
+static long tile_reach(const flk_pool_args* a, int Tt, int Ht, int Wt) {
+  return (long)((Tt + a->kt - 2) / a->st + 1) * ((Ht + a->kh - 2) / a->sh + 1) * ((Wt + a->kw - 2) / a->sw + 1);
+}
+// x / d as (x * magic(d)) >> 20 for the tap decode (x <= 255: scatter_tap_cell)
+static unsigned magic(int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); }
 
 // input-cell tile for the scatter backward: minimise bytes moved per useful cell (tile writes + the windows read,
 // which overlap between neighbouring tiles) plus a fixed per-workgroup cost
@@ -1202,7 +1157,7 @@ static flk_tile choose_scatter_tile(const flk_pool_args* a, long max_reach = 0) 
       const int wmax = 256 / (Tt * Ht) < a->Wi ? 256 / (Tt * Ht) : a->Wi;
       for (int Wt = 1; Wt <= wmax; ++Wt) {
         const double tiles = (double)((a->Ti + Tt - 1) / Tt) * ((a->Hi + Ht - 1) / Ht) * ((a->Wi + Wt - 1) / Wt);
-        const double outs = (double)((Tt + a->kt - 2) / a->st + 1) * ((Ht + a->kh - 2) / a->sh + 1) * ((Wt + a->kw - 2) / a->sw + 1);
+        const double outs = (double)tile_reach(a, Tt, Ht, Wt);
         if (max_reach > 0 && outs > (double)max_reach) continue;
         const double passes = (double)(((long)outs + 255) / 256);           // 64 position threads x 4-deep unroll
         const double cost = tiles * (Tt * Ht * Wt * 16.0 + outs * 24.0 + passes * 2048.0 + 2048.0);
@@ -1227,12 +1182,7 @@ static int launch_scatter_bwd(const PoolKP& kp, const flk_pool_args* a, hipStrea
   PoolTP tp{};
   tp.k = kp;
   tp.fx_e = fixed_point_exponent(a);
-  const flk_tile t = choose_scatter_tile(a);
-  tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
-  tp.nTt = (a->Ti + t.Tt - 1) / t.Tt; tp.nTh = (a->Hi + t.Ht - 1) / t.Ht; tp.nTw = (a->Wi + t.Wt - 1) / t.Wt;
-  tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + 4 * EPL - 1) / (4 * EPL);
-  const dim3 grid((unsigned)((tp.ntiles + 7) / 8 * 8 * tp.nslab));
-  auto magic = [](int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); };
+  const dim3 grid = tile_grid(tp, a, choose_scatter_tile(a), true, 4 * EPL);
   tp.plane_b = (tp.rows + 47) / 64 * 64 + 16;                         // accumulator plane stride in floats, = 16 (mod 64)
   const size_t lds = (size_t)(4 * tp.plane_b * EPL + 256) * sizeof(float);    // <= 35 KiB (+ one dummy word per thread)
   FLK_LAUNCH_KERNEL(maxpool_scatter_bwd<T>, grid, dim3(256), lds, s, tp, magic(a->kh * a->kw), magic(a->kw));
@@ -1251,27 +1201,18 @@ template <typename T>
 static int launch_tiled(const PoolKP& kp, const flk_pool_args* a, bool bwd, hipStream_t s) {
   PoolTP tp{};
   tp.k = kp;
-  const flk_tile t = flk_choose_tile(a->To, a->Ho, a->Wo, a->kt, a->kh, a->kw, 1, 1, 1, 256, 768);   // 2 workgroups per CU
-  tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
-  tp.nTt = (a->To + t.Tt - 1) / t.Tt; tp.nTh = (a->Ho + t.Ht - 1) / t.Ht; tp.nTw = (a->Wo + t.Wt - 1) / t.Wt;
-  tp.Th = t.Tt + a->kt - 1; tp.Hh = t.Ht + a->kh - 1; tp.Wh = t.Wt + a->kw - 1;
-  tp.P = tp.Th * tp.Hh * tp.Wh;
-  FLK_REQUIRE(tp.P <= FLK_MAX_HALO, "maxpool tiled: halo %d too large", tp.P);
-  tp.plane_b = (tp.P * 16 + 255) / 256 * 256;
   constexpr int EPL = PV<T>::EPL;
+  const flk_tile t = flk_choose_tile(a->To, a->Ho, a->Wo, a->kt, a->kh, a->kw, 1, 1, 1, 256, 768);   // 2 workgroups per CU
+  const dim3 grid = tile_grid(tp, a, t, false, 4 * EPL);       // (To == Ti ..: the same tiles over the input grid for the backward)
+  tile_halo(tp, a);
+  FLK_REQUIRE(tp.P <= FLK_MAX_HALO, "maxpool tiled: halo %d too large", tp.P);
   const size_t lds = 4 * (size_t)tp.plane_b + 64 + (bwd ? (size_t)4 * tp.P * EPL + 16 : 0);
-  tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + 4 * EPL - 1) / (4 * EPL);
-  const dim3 grid((unsigned)((tp.ntiles + 7) / 8 * 8 * tp.nslab));
   static bool attr_fwd[FLK_MAX_DEVICES] = {}, attr_bwd[FLK_MAX_DEVICES] = {};
   if (int rc = flk_raise_lds_limit((const void*)maxpool_s1_tiled_fwd<T>, 96 * 1024, attr_fwd)) return rc;
   if (int rc = flk_raise_lds_limit((const void*)maxpool_s1_tiled_bwd<T>, 96 * 1024, attr_bwd)) return rc;
   if (bwd) FLK_LAUNCH_KERNEL(maxpool_s1_tiled_bwd<T>, grid, dim3(256), lds, s, tp);
   else if (sizeof(T) == 2 && a->kt == 3 && a->kh == 3 && a->kw == 3 && a->pt == 1 && a->ph == 1 && a->pw == 1) {
     return a->Wo % 7 == 0 ? launch_wrun_fwd<7>(kp, a, s) : launch_wrun_fwd<8>(kp, a, s);
-  } else if (sizeof(T) == 2 && a->kt == 3 && a->kh == 3 && a->kw == 3) {
-    static bool attr2[FLK_MAX_DEVICES] = {};
-    if (int rc = flk_raise_lds_limit((const void*)maxpool_s1_tiled_fwd_bf16<3, 3, 3>, 96 * 1024, attr2)) return rc;
-    FLK_LAUNCH_KERNEL((maxpool_s1_tiled_fwd_bf16<3, 3, 3>), grid, dim3(256), lds, s, tp);
   } else FLK_LAUNCH_KERNEL(maxpool_s1_tiled_fwd<T>, grid, dim3(256), lds, s, tp);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
@@ -1299,9 +1240,25 @@ static void fill(PoolKP& kp, const flk_pool_args* a) {
   kp.relu_input = a->relu_input;
 }
 
-static unsigned grid_for(long total) {
-  long g = (total + 255) / 256;
-  return (unsigned)(g < 1 ? 1 : (g > 16384 ? 16384 : g));
+// one thread per output: the I3D windows take the unrolled kernel (fp32 3x3x3, met only in the parity mode, keeps the generic one)
+template <typename T>
+static int launch_simple_fwd(const PoolKP& kp, const flk_pool_args* a, hipStream_t s) {
+  dim3 grid;
+  if (int rc = simple_grid(a, PV<T>::EPL, false, "flk_maxpool3d_fwd", grid)) return rc;
+  const int kcode = a->kt * 100 + a->kh * 10 + a->kw;
+#define FLK_FWD_K(KT, KH, KW)                                                                               \
+  if (kcode == KT * 100 + KH * 10 + KW) {                                                                   \
+    FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<T, KT, KH, KW>), grid, dim3(256), 0, s, kp);                    \
+    FLK_CHECK_HIP(hipGetLastError());                                                                       \
+    return FLK_OK;                                                                                          \
+  }
+  FLK_FWD_K(1, 3, 3)
+  if constexpr (sizeof(T) == 2) FLK_FWD_K(3, 3, 3)
+  FLK_FWD_K(2, 2, 2)
+#undef FLK_FWD_K
+  FLK_LAUNCH_KERNEL(maxpool_fwd_kernel<T>, grid, dim3(256), 0, s, kp);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
 }
 
 extern "C" int flk_maxpool3d_fwd(const flk_pool_args* a, int dtype, void* stream) {
@@ -1312,22 +1269,7 @@ extern "C" int flk_maxpool3d_fwd(const flk_pool_args* a, int dtype, void* stream
   fill(kp, a);
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_maxpool3d_fwd: bad dtype");
   if (use_tiled(a)) return dtype == FLK_BF16 ? launch_tiled<bf16_t>(kp, a, false, (hipStream_t)stream) : launch_tiled<float>(kp, a, false, (hipStream_t)stream);
-  const int epl = dtype == FLK_BF16 ? 8 : 4;
-  FLK_REQUIRE(a->Ho < 65536 && (long)a->B * a->To < 65536, "flk_maxpool3d_fwd: grid too large");
-  const dim3 grid((unsigned)((a->Wo * (a->C / epl) + 255) / 256), (unsigned)a->Ho, (unsigned)(a->B * a->To));
-  const int kcode = a->kt * 100 + a->kh * 10 + a->kw;
-  if (dtype == FLK_BF16) {
-    if (kcode == 133) FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<bf16_t, 1, 3, 3>), grid, dim3(256), 0, (hipStream_t)stream, kp);
-    else if (kcode == 333) FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<bf16_t, 3, 3, 3>), grid, dim3(256), 0, (hipStream_t)stream, kp);
-    else if (kcode == 222) FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<bf16_t, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, kp);
-    else FLK_LAUNCH_KERNEL(maxpool_fwd_kernel<bf16_t>, grid, dim3(256), 0, (hipStream_t)stream, kp);
-  } else {
-    if (kcode == 133) FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<float, 1, 3, 3>), grid, dim3(256), 0, (hipStream_t)stream, kp);
-    else if (kcode == 222) FLK_LAUNCH_KERNEL((maxpool_fwd_kernel_k<float, 2, 2, 2>), grid, dim3(256), 0, (hipStream_t)stream, kp);
-    else FLK_LAUNCH_KERNEL(maxpool_fwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, kp);
-  }
-  FLK_CHECK_HIP(hipGetLastError());
-  return FLK_OK;
+  return dtype == FLK_BF16 ? launch_simple_fwd<bf16_t>(kp, a, (hipStream_t)stream) : launch_simple_fwd<float>(kp, a, (hipStream_t)stream);
 }
 
 extern "C" int flk_maxpool3d_bwd(const flk_pool_args* a, const void* gout, int gout_ld, int gout_coff,
@@ -1359,9 +1301,8 @@ extern "C" int flk_maxpool3d_bwd(const flk_pool_args* a, const void* gout, int g
   // scatter form (32-bit fixed-point integer LDS atomics: order-independent, bitwise reproducible as well)
   if (dtype == FLK_BF16) return launch_scatter_bwd<bf16_t>(kp, a, (hipStream_t)stream);
   if (use_tiled(a)) return launch_tiled<float>(kp, a, true, (hipStream_t)stream);
-  const int epl = dtype == FLK_BF16 ? 8 : 4;
-  FLK_REQUIRE(a->Hi < 65536 && (long)a->B * a->Ti < 65536, "flk_maxpool3d_bwd: grid too large");
-  const dim3 grid((unsigned)((a->Wi * (a->C / epl) + 255) / 256), (unsigned)a->Hi, (unsigned)(a->B * a->Ti));
+  dim3 grid;
+  if (int rc = simple_grid(a, PV<float>::EPL, true, "flk_maxpool3d_bwd", grid)) return rc;
   FLK_LAUNCH_KERNEL(maxpool_bwd_kernel<float>, grid, dim3(256), 0, (hipStream_t)stream, kp);
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
@@ -1427,11 +1368,7 @@ extern "C" int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int
   const flk_tile t = choose_scatter_tile(a, reg_able ? 512 : 0);
   PoolTP& tp = pg.t;
   tp.fx_e = fixed_point_exponent(a);
-  tp.Tt = t.Tt; tp.Ht = t.Ht; tp.Wt = t.Wt; tp.rows = t.Tt * t.Ht * t.Wt;
-  tp.nTt = (a->Ti + t.Tt - 1) / t.Tt; tp.nTh = (a->Hi + t.Ht - 1) / t.Ht; tp.nTw = (a->Wi + t.Wt - 1) / t.Wt;
-  tp.ntiles = a->B * tp.nTt * tp.nTh * tp.nTw; tp.nslab = (a->C + 31) / 32;
-  const dim3 grid((unsigned)((tp.ntiles + 7) / 8 * 8 * tp.nslab));
-  auto magic = [](int d) { return (unsigned)(((1u << 20) + (unsigned)d - 1) / (unsigned)d); };
+  const dim3 grid = tile_grid(tp, a, t, true, 32);
   { // accumulator plane stride in words: 4 (mod 64) -- the four lane groups q of an atomic (planes 4 q + j) start 16 banks apart
     // (16 (mod 64), the stride of maxpool_scatter_bwd, puts all four on the same banks)
     constexpr int res = 4;
@@ -1441,8 +1378,7 @@ extern "C" int flk_maxpool3d_bwd_gemm(const flk_pool_args* a, const void* g, int
   hipStream_t s = (hipStream_t)stream;
   const unsigned m1 = magic(a->kh * a->kw), m2 = magic(a->kw);
   // windows that can reach a tile: at most 64 * 8 -> the register-resident form
-  const long reach = (long)((t.Tt + a->kt - 2) / a->st + 1) * ((t.Ht + a->kh - 2) / a->sh + 1) * ((t.Wt + a->kw - 2) / a->sw + 1);
-  if (reg_able && reach <= 512) {
+  if (reg_able && tile_reach(a, t.Tt, t.Ht, t.Wt) <= 512) {
     const size_t lds_reg = lds + (size_t)(64 + 256 + 256) * sizeof(unsigned);      // + the tap table + one dummy word per thread
     switch (pg.KS) {
       case 1: FLK_LAUNCH_KERNEL((maxpool_scatter_gemm_bwd_reg<1, 8, 4>), grid, dim3(256), lds_reg, s, pg, m1, m2); break;

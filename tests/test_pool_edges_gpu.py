@@ -16,6 +16,7 @@ What is asserted, and where the bounds come from (nothing here is measured):
 The fused Branch_3 backward is always fed g and Wt made of small integers and powers of two, so that every product and K-sum is exact in
 fp32 in any order and the bounds above apply to it unchanged."""
 import copy
+import ctypes
 import functools
 import math
 
@@ -89,11 +90,16 @@ def fx_e(n):
 
 
 class Ref:
-    """float64 max-pool (SAME, -inf padding) of x [B,T,H,W,C]: .out [B,To,Ho,Wo,C] float64, .tap uint8 (the expected idx), .bwd(gout)"""
+    """float64 max-pool (SAME, -inf padding) of x [B,T,H,W,C]: .out [B,To,Ho,Wo,C] float64, .tap uint8 (the expected idx), .bwd(gout).
+    pad_before: an explicit pad-before per dimension instead of SAME's (stride 1: the output grid is the input grid and the pad-after is
+    k - 1 - pad_before)"""
 
-    def __init__(self, x, k, s, relu_input=False):
+    def __init__(self, x, k, s, relu_input=False, pad_before=None):
         B, T, H, W, C = x.shape
         g = [same(n, kk, ss) for n, kk, ss in zip((T, H, W), k, s)]
+        if pad_before is not None:
+            assert tuple(s) == (1, 1, 1)
+            g = [(n, pb, kk - 1 - pb) for n, kk, pb in zip((T, H, W), k, pad_before)]
         self.shape, self.pb = (B, T, H, W, C), [a[1] for a in g]
         xp = F.pad(cf(x).double(), [g[2][1], g[2][2], g[1][1], g[1][2], g[0][1], g[0][2]], value=-INF)
         y, fi = F.max_pool3d(xp, k, s, return_indices=True)
@@ -334,8 +340,8 @@ def assert_slice(buf, coff, C_, contiguous, what):
 
 
 # forward families: _k (2a, 5a, bf16 4a), generic (311_s211, fp32 4a), LDS-tiled (fp32 b3_*), W-run 7 / 8 (bf16 b3_w7 / b3_w8).
-# maxpool_s1_tiled_fwd_bf16<3,3,3> is NOT reached by any test: it takes bf16 3x3x3 / 1 with a pad-before other than 1, which SAME
-# padding (all the wrappers compute) never gives; its key encoding is covered only through the helpers it shares with the W-run kernel.
+# bf16 3x3x3 / 1 with a pad-before other than 1, which SAME padding (all the wrappers compute) never gives, takes the LDS-tiled float
+# forward maxpool_s1_tiled_fwd<bf16_t> like every other tiled window: test_explicit_pad_before calls the C ABI with such pads.
 # backward families: owner (2a, 4a, 5a), gather (fp32 311_s211 / 333_s122), tiled gather (fp32 b3_*), scatter (every other bf16 one)
 @DTYPES
 @pytest.mark.parametrize("C_", [8, 40, 72])
@@ -570,3 +576,37 @@ def test_relu_input_fused(ops, form, monkeypatch):
     assert torch.equal(got.float(), torch.where(x > 0, plain.float(), torch.tensor(0.0)))
     assert torch.equal(bits(got)[x > 0], bits(plain)[x > 0])
     check_bwd(got, Ref(x, k, s), g.double() @ wt.double(), k, s, BF16, mask=x, fused=True)
+
+
+# ---- H: explicit pad-before (the C ABI accepts any pad below the window; SAME gives 1 for 3x3x3 / 1) --------------------------------------
+
+PADS = [(0, 0, 0), (2, 2, 2), (0, 2, 1)]
+
+
+@functools.lru_cache(maxsize=None)
+def pad_case(pad, dtype, kind):
+    """as case(): 3x3x3 / 1 over B = 2, (3, 7, 9), C = 24 (a slab tail) with the reference at pad-before `pad` (read-only)"""
+    x = make_input(kind, (2, 3, 7, 9, 24), dtype, 120 + PADS.index(pad))
+    return x, Ref(x, (3, 3, 3), (1, 1, 1), relu_input=kind == "relu_input", pad_before=pad)
+
+
+@DTYPES
+@pytest.mark.parametrize("pad", PADS, ids=lambda p: "pad" + "".join(map(str, p)))
+@pytest.mark.parametrize("kind", ["signed", "relu_input"])
+def test_explicit_pad_before(ops, pad, dtype, kind):
+    """flk_maxpool3d_fwd / _bwd called with a pad-before no wrapper computes (To, Ho, Wo = Ti, Hi, Wi): the LDS-tiled forward of both
+    dtypes and the fp32 tiled backward at a window origin other than i - 1, the bf16 scatter backward at the same pads.  Neither data
+    kind holds a -0.0, so out and idx are bit for bit the reference's under either tie rule."""
+    k, s = (3, 3, 3), (1, 1, 1)
+    x, ref = pad_case(pad, dtype, kind)
+    xd = dev(x, dtype)
+    out = torch.empty_like(xd)
+    idx = torch.empty(tuple(xd.shape), dtype=torch.uint8, device="cuda")
+    a = ops._pool_args(xd, 24, k, s, pad, out, idx)
+    a.relu_input = int(kind == "relu_input")
+    ops.check(ops.load().flk_maxpool3d_fwd(ctypes.byref(a), ops.dtype_code(dtype), ops.stream_ptr()))
+    check_fwd(out, idx, ref)
+    ctx = (xd, 24, k, s, pad, out, idx, 0, 0)                       # maxpool3d's context: _pool_args + load().flk_maxpool3d_bwd
+    g = q(rnd(tuple(ref.out.shape), 9), dtype)
+    check_bwd(ops.maxpool3d_bwd(ctx, dev(g, dtype)), ref, g, k, s, dtype)
+    check_bwd(ops.maxpool3d_bwd(ctx, dev(g, dtype), mask=xd), ref, g, k, s, dtype, mask=x)
