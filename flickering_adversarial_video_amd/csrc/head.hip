@@ -6,6 +6,11 @@
 // with wt[t] = (#pool windows covering frame t) / (2*7*7*T').  VideoResNet (AdaptiveAvgPool3d(1) +
 // Linear, torchvision 0.5.0) is the same form with wt = 1/(T*H*W).  Backward:
 //     gy[b,t,h,w,c] = wt[t] * sum_n dlogits[b,n] W[c,n], masked by y > 0 (ReluGrad of the producer).
+// The mask is a comparison of the stored number: +0.0, -0.0, negatives and NaN give a zero gradient, +inf and DENORMALS pass -- the
+// smallest positive denormal of either storage format is > 0 here (fp32 denormals are not flushed in this build; a bf16 one widens to an
+// fp32 denormal).  All sums are fp32 in a fixed order without atomics: bitwise repeatable, and a clip's rows do not depend on the rest of
+// the batch.  flk_head_forward / flk_head_backward (include/flicker_hip.h) are exported so that tests/test_head_edges_gpu.py can run
+// these four kernels on their own, at the seams of their loops and guards.
 //
 // Loss head (kinetics_i3d_utils.py:152-169,253-307; model.py:177-250): one workgroup per clip computes
 // softmax, label / max-non-label statistics, the adversarial loss and d(loss)/d(logits) in closed form.
@@ -137,9 +142,27 @@ __global__ __launch_bounds__(256) void head_pool_bwd_kernel(const char* y, int l
   }
 }
 
-int flk_head_forward(const void* y, int ld, int coff, int C, int B, int Tn, int HW, const float* wt, const float* W,
-                     const float* bias, int N, float* feat, float* logits, int dtype, hipStream_t s) {
-  FLK_REQUIRE(C <= 2048 && N <= 1024, "head: C<=2048, N<=1024 supported");
+// what both entry points refuse alike (include/flicker_hip.h); `what` names the entry point in the message
+static int head_check_dims(const char* what, int C, int B, int Tn, int HW, int N, int ld, int coff, int dtype) {
+  FLK_REQUIRE(dtype == FLK_F32 || dtype == FLK_BF16, "%s: dtype must be FLK_F32 or FLK_BF16, got %d", what, dtype);
+  FLK_REQUIRE(B >= 1, "%s: B must be >= 1, got %d", what, B);
+  FLK_REQUIRE(B <= 65535, "%s: B must be <= 65535 (one grid row per clip), got %d", what, B);
+  FLK_REQUIRE(C >= 1, "%s: C must be >= 1, got %d", what, C);
+  FLK_REQUIRE(Tn >= 1, "%s: Tn must be >= 1, got %d", what, Tn);
+  FLK_REQUIRE(HW >= 1, "%s: HW must be >= 1, got %d", what, HW);
+  FLK_REQUIRE(N >= 1, "%s: N must be >= 1, got %d", what, N);
+  FLK_REQUIRE(N <= 1024, "%s: N must be <= 1024, got %d", what, N);
+  FLK_REQUIRE((long)Tn * HW < (1l << 31), "%s: Tn * HW = %ld positions overflow 31 bits", what, (long)Tn * HW);
+  FLK_REQUIRE(coff >= 0 && (long)coff + C <= ld, "%s: channels [coff, coff + C) = [%d, %ld) are outside ld = %d", what, coff, (long)coff + C, ld);
+  return FLK_OK;
+}
+
+extern "C" int flk_head_forward(const void* y, int ld, int coff, int C, int B, int Tn, int HW, const float* wt, const float* W,
+                                const float* bias, int N, float* feat, float* logits, int dtype, void* stream) {
+  FLK_REQUIRE(y && wt && W && feat && logits, "flk_head_forward: null argument");
+  if (int rc = head_check_dims("flk_head_forward", C, B, Tn, HW, N, ld, coff, dtype)) return rc;
+  FLK_REQUIRE(C <= 2048, "flk_head_forward: C must be <= 2048, got %d", C);
+  hipStream_t s = (hipStream_t)stream;
   dim3 g1((C + 63) / 64, B);
   if (dtype == FLK_BF16) FLK_LAUNCH_KERNEL(head_pool_kernel<bf16_t>, g1, dim3(256), 0, s, (const char*)y, ld, coff, C, Tn, HW, wt, feat);
   else FLK_LAUNCH_KERNEL(head_pool_kernel<float>, g1, dim3(256), 0, s, (const char*)y, ld, coff, C, Tn, HW, wt, feat);
@@ -148,14 +171,25 @@ int flk_head_forward(const void* y, int ld, int coff, int C, int B, int Tn, int 
   return FLK_OK;
 }
 
-int flk_head_backward(const void* y, int ld, int coff, void* gy, int gld, int gcoff, int C, int B, int Tn, int HW,
-                      const float* wt, const float* W, int N, const float* dlogits, float* dfeat, int use_mask, int dtype,
-                      hipStream_t s) {
+extern "C" int flk_head_backward(const void* y, int ld, int coff, void* gy, int gld, int gcoff, int C, int B, int Tn, int HW,
+                                 const float* wt, const float* W, int N, const float* dlogits, float* dfeat, int use_mask, int dtype,
+                                 void* stream) {
+  FLK_REQUIRE((y || !use_mask) && gy && wt && W && dlogits && dfeat, "flk_head_backward: null argument");
+  if (int rc = head_check_dims("flk_head_backward", C, B, Tn, HW, N, ld, coff, dtype)) return rc;
   const int epl = dtype == FLK_BF16 ? 8 : 4;
-  FLK_REQUIRE(C % epl == 0 && ld % epl == 0 && coff % epl == 0 && gld % epl == 0 && gcoff % epl == 0 && N <= 1024 &&
-              (long)B * Tn * HW * (C / epl) < (1l << 31), "head backward: channel counts / strides must be multiples of %d", epl);
-  FLK_LAUNCH_KERNEL(head_fc_bwd_kernel, dim3((C + 15) / 16, B), dim3(256), 0, s, dlogits, W, C, N, dfeat);
+  FLK_REQUIRE(C % epl == 0, "flk_head_backward: C = %d must be a multiple of %d", C, epl);
+  FLK_REQUIRE(ld % epl == 0, "flk_head_backward: ld = %d must be a multiple of %d", ld, epl);
+  FLK_REQUIRE(coff % epl == 0, "flk_head_backward: coff = %d must be a multiple of %d", coff, epl);
+  FLK_REQUIRE(gld % epl == 0, "flk_head_backward: gld = %d must be a multiple of %d", gld, epl);
+  FLK_REQUIRE(gcoff % epl == 0, "flk_head_backward: gcoff = %d must be a multiple of %d", gcoff, epl);
+  FLK_REQUIRE(gcoff >= 0 && (long)gcoff + C <= gld, "flk_head_backward: channels [gcoff, gcoff + C) = [%d, %ld) are outside gld = %d", gcoff,
+              (long)gcoff + C, gld);
   const long total = (long)B * Tn * HW * (C / epl);
+  FLK_REQUIRE(total < (1l << 31), "flk_head_backward: B * Tn * HW * (C / %d) = %ld 16-byte groups overflow 31 bits", epl, total);
+  FLK_REQUIRE(!use_mask || (uintptr_t)y % 16 == 0, "flk_head_backward: y = %p must be 16-byte aligned (use_mask)", y);
+  FLK_REQUIRE((uintptr_t)gy % 16 == 0, "flk_head_backward: gy = %p must be 16-byte aligned", gy);
+  hipStream_t s = (hipStream_t)stream;
+  FLK_LAUNCH_KERNEL(head_fc_bwd_kernel, dim3((C + 15) / 16, B), dim3(256), 0, s, dlogits, W, C, N, dfeat);
   const unsigned grid = (unsigned)((total + 255) / 256 > 8192 ? 8192 : (total + 255) / 256);
   if (dtype == FLK_BF16)
     FLK_LAUNCH_KERNEL(head_pool_bwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, (const char*)y, ld, coff, (char*)gy, gld, gcoff, C, Tn, HW, B, wt, dfeat, use_mask);

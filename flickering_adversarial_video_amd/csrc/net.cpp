@@ -15,12 +15,6 @@
 #include <memory>
 #include "flk_internal.h"
 
-int flk_head_forward(const void* y, int ld, int coff, int C, int B, int Tn, int HW, const float* wt, const float* W,
-                     const float* bias, int N, float* feat, float* logits, int dtype, hipStream_t s);
-int flk_head_backward(const void* y, int ld, int coff, void* gy, int gld, int gcoff, int C, int B, int Tn, int HW,
-                      const float* wt, const float* W, int N, const float* dlogits, float* dfeat, int use_mask, int dtype,
-                      hipStream_t s);
-
 // stem_grad.hip: the fused delta-gradient on a slice of the batch / its stage 2 (flk_stem_delta_grad = mask + one slice + stage 2)
 int flk_stem_delta_grad_part(const flk_apply_args* a, int b0, int nb, const void* G, int g_ld, const float* wf_dev, float* scratch, hipStream_t s);
 int flk_stem_delta_grad_finish(const flk_apply_args* a, int nb, float* scratch, float* gdelta, hipStream_t s);

@@ -1371,6 +1371,43 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
     return (outs, st_out) if stats else outs
 
 
+def _head_check(y, wt, W, C_, coff):
+    assert y.dim() == 4 and y.is_contiguous() and y.is_cuda and y.dtype in (torch.float32, torch.bfloat16)
+    B, Tn, HW, ld = y.shape
+    C_ = ld - coff if C_ is None else C_
+    assert 0 <= coff and coff + C_ <= ld
+    assert wt.dtype == torch.float32 and wt.is_contiguous() and wt.is_cuda and tuple(wt.shape) == (Tn,)
+    assert W.dtype == torch.float32 and W.is_contiguous() and W.is_cuda and W.dim() == 2 and W.shape[0] == C_
+    return B, Tn, HW, ld, C_, W.shape[1]
+
+
+def head_forward(y, wt, W, bias, *, C=None, coff=0):
+    """the classifier head (flk_head_forward) on channels [coff, coff + C) of y [B,Tn,HW,ld] (fp32 / bf16): frame weights wt [Tn], fc weight
+    W [C,N], bias [N] or None -> (feat [B,C], logits [B,N]), fp32"""
+    B, Tn, HW, ld, C_, N = _head_check(y, wt, W, C, coff)
+    assert bias is None or (bias.dtype == torch.float32 and bias.is_contiguous() and bias.is_cuda and tuple(bias.shape) == (N,))
+    feat = torch.empty((B, C_), dtype=torch.float32, device=y.device)
+    logits = torch.empty((B, N), dtype=torch.float32, device=y.device)
+    check(load().flk_head_forward(ptr(y), ld, coff, C_, B, Tn, HW, ptr(wt), ptr(W), ptr(bias), N, ptr(feat), ptr(logits), dtype_code(y.dtype),
+                                  stream_ptr()))
+    return feat, logits
+
+
+def head_backward(y, wt, W, dlogits, *, gy=None, C=None, coff=0, gcoff=0, use_mask=True):
+    """the head's gradient (flk_head_backward): dlogits [B,N] -> (gy, dfeat [B,C]); channels [gcoff, gcoff + C) of gy [B,Tn,HW,gld] (default: a
+    fresh [.., gcoff + C] tensor of y's dtype) receive wt[t] * dfeat, zero where use_mask and not y > 0; its other channels are left alone"""
+    B, Tn, HW, ld, C_, N = _head_check(y, wt, W, C, coff)
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and dlogits.is_cuda and tuple(dlogits.shape) == (B, N)
+    if gy is None:
+        gy = torch.empty((B, Tn, HW, gcoff + C_), dtype=y.dtype, device=y.device)
+    assert tuple(gy.shape[:3]) == (B, Tn, HW) and gy.dim() == 4 and gy.dtype == y.dtype and gy.is_contiguous() and gy.is_cuda
+    assert 0 <= gcoff and gcoff + C_ <= gy.shape[3]
+    dfeat = torch.empty((B, C_), dtype=torch.float32, device=y.device)
+    check(load().flk_head_backward(ptr(y), ld, coff, ptr(gy), gy.shape[3], gcoff, C_, B, Tn, HW, ptr(wt), ptr(W), N, ptr(dlogits), ptr(dfeat),
+                                   int(bool(use_mask)), dtype_code(y.dtype), stream_ptr()))
+    return gy, dfeat
+
+
 def pack_batch_sums(per_clip, prob_scale, out3):
     """out3 = [sum loss_b, prob_scale * sum p_label, prob_scale * sum p_max_other] from softmax_adv_loss's per-clip table"""
     assert per_clip.dtype == torch.float32 and per_clip.is_contiguous() and per_clip.shape[1] == 4 and out3.dtype == torch.float32

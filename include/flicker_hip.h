@@ -803,6 +803,27 @@ int flk_perturb_dense_l12_adam(const flk_dense_adam_args* a, const float* g_adv,
 int flk_perturb_dense_l12_pgd(const flk_dense_adam_args* a, const float* g_adv, float* delta, float* scalars, float* scratch,
                               void* stream);
 
+/* Classifier head (csrc/head.hip): time-weighted average pool + linear layer, and its gradient.  What every flk_net runs between its
+ * last activation and the loss head (I3D Logits endpoint, i3d.py:459-474; VideoResNet avgpool + fc), callable on its own.
+ *   feat[b,c]   = sum_{t,p} wt[t] * y[b,t,p,coff+c]                  (p over the HW positions of frame t)
+ *   logits[b,n] = bias[n] + sum_c feat[b,c] * W[c,n]                 (bias == NULL: no bias)
+ *   dfeat[b,c]  = sum_n dlogits[b,n] * W[c,n]
+ *   gy[b,t,p,gcoff+c] = wt[t] * dfeat[b,c], and 0 where use_mask and not y[b,t,p,coff+c] > 0 (-0.0, +0.0, negatives and NaN give 0;
+ *                       denormals and +inf pass).  Channels of gy outside [gcoff, gcoff+C) are not written.
+ * All pointers are DEVICE pointers.  y: [B,Tn,HW,ld] and gy: [B,Tn,HW,gld] of `dtype` (FLK_F32 / FLK_BF16), channels innermost;
+ * wt: fp32 [Tn]; W: fp32 [C,N]; bias: fp32 [N] or NULL; feat, dfeat: fp32 [B,C]; logits, dlogits: fp32 [B,N].  All arithmetic is
+ * fp32 in a fixed order: no atomics, results bitwise repeatable and row b independent of the other rows of the batch; bf16 gy is
+ * the fp32 product rounded to nearest even once.
+ * Limits: B, C, Tn, HW, N >= 1; B <= 65535; N <= 1024; forward: C <= 2048, any coff >= 0 with coff + C <= ld; backward: C, ld, coff,
+ * gld, gcoff multiples of EPL = 4 (fp32) / 8 (bf16), gcoff + C <= gld, B*Tn*HW*(C/EPL) < 2^31, gy 16-byte aligned, and with use_mask y
+ * 16-byte aligned (use_mask == 0: y is not read and may be NULL).  FLK_EINVAL naming the argument and its value otherwise, before any
+ * GPU call.  Two launches each. */
+int flk_head_forward(const void* y, int ld, int coff, int C, int B, int Tn, int HW, const float* wt, const float* W,
+                     const float* bias, int N, float* feat, float* logits, int dtype, void* stream);
+int flk_head_backward(const void* y, int ld, int coff, void* gy, int gld, int gcoff, int C, int B, int Tn, int HW,
+                      const float* wt, const float* W, int N, const float* dlogits, float* dfeat, int use_mask, int dtype,
+                      void* stream);
+
 /* Loss head: softmax + adversarial loss + d(loss)/d(logits) (kinetics_i3d_utils.py:152-169,253-307;
  * model.py:177-250).  per_clip[b*4..] = {loss_b, label_prob, max_non_label_prob, argmax}. */
 typedef struct {
