@@ -30,7 +30,9 @@ ATTACK_SECTIONS = ("SINGLE_VIDEO_ATTACK", "CLASS_GEN_ATTACK", "UNIVERSAL_ATTACK"
 # (None: 0.4, the apply clip, for the flickering perturbation; required for the dense one)
 # SAVE_ADV_U8: also store the adversarial clip as 8-bit frames (uint8, one kernel launch); EVAL_QUANTISED: also score those frames -- is
 # the STORED video still adversarial?  Both off by default: the result files then keep the reference's keys
-DEFAULT_ATTACK = {"OPTIMIZER": "adam", "PGD_EPS": None, "SAVE_ADV_U8": False, "EVAL_QUANTISED": False}
+# QUANTISE_TRAIN: optimise on the stored video -- every adversarial forward sees the 8-bit frames decoded again
+# (FlickerI3D(quantise_train=True)); the flickering perturbation only.  Off by default
+DEFAULT_ATTACK = {"OPTIMIZER": "adam", "PGD_EPS": None, "SAVE_ADV_U8": False, "EVAL_QUANTISED": False, "QUANTISE_TRAIN": False}
 OPTIMIZERS = ("adam", "pgd")
 
 
@@ -47,6 +49,8 @@ def load_config(yml_path):
             cfg[sec].setdefault(k, v)
         if cfg[sec].OPTIMIZER not in OPTIMIZERS:
             raise ValueError(f"{sec}.OPTIMIZER must be one of {OPTIMIZERS}, got {cfg[sec].OPTIMIZER!r}")
+        if not isinstance(cfg[sec].QUANTISE_TRAIN, bool):
+            raise ValueError(f"{sec}.QUANTISE_TRAIN must be True or False, got {cfg[sec].QUANTISE_TRAIN!r}")
     return cfg
 
 

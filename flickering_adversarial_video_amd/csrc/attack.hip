@@ -6,6 +6,7 @@
 // 198-209, 868.  Closed forms: SURVEY Appendix C.
 #include "flk_internal.h"
 #include "perturb_common.h"
+#include "quant_encode.h"
 
 // Space-to-depth layouts (template FT = flk_apply_args.fold_t, 0 -> 2):
 //   FT = 1: fold (h,w) only,   16 channels: (qh*2+qw)*3 + c, 12..15 zero          (VideoResNet stems)
@@ -50,12 +51,8 @@ __device__ static inline float applied(const flk_apply_args& a, float x, float p
   return (u < a.lo || u > a.hi) ? clipf(u, a.lo, a.hi) - pv : x;
 }
 
-// ---- 8-bit encode (flk_export_args; include/flicker_hip.h): the export kernel's quantiser, and the quantised apply's -------------
-// y = x_adv * mul + add; z = y * levels; q = z >= 0 ? min(rint(z), 255) : 0 -- every operation rounded on its own; NaN -> 0
-__device__ static inline int encode_q(float v, float mul, float add, float levels) {
-  const float z = __fmul_rn(__fadd_rn(__fmul_rn(v, mul), add), levels);
-  return z >= 0.f ? (int)fminf(rintf(z), 255.f) : 0;
-}
+// ---- 8-bit encode (flk_export_args; include/flicker_hip.h): the export kernel's quantiser, and the quantised apply's: encode_q of
+// quant_encode.h, shared with the quantised uint8 stem (stem_fwd.hip) ----------------------------------------------------------------
 // Quantised apply (flk_apply_args.q_lut, template QUANT of the apply kernels): the value a kernel writes is the one the STORED video
 // decodes to -- v = applied(...) encoded to its byte, the byte decoded through the table.  NO second clamp: a value the clamp holds at a
 // bound is stored as the level nearest the bound, and a clean forward of the stored frames (clamp bounds -inf / +inf) sees that level.

@@ -143,9 +143,18 @@ struct flk_net {
   flk_conv_weights* stem_u8_w = nullptr;
   flk_conv_weights* stem_hilo_w = nullptr;      // VideoResNet stems in bf16: forward weights over the two-bf16-numbers-per-value input (fold_t = 4)
   int in_ch = 16;                               // VideoResNet plans: channels of the input tensor (16, or 32 in bf16)
+  // Quantised apply arguments (q_lut, center = 0, the TF encode and decode -- what flk_stem_fwd_u8 takes with q_lut) go the same way:
+  // the stem stages the stored byte itself and there is no position-class bias.  Any other quantised arguments (the torch encode, an fp32
+  // clip, FLK_STEM_U8=0) take the generic quantised apply + the folded stem.
+  static bool tf_quantised(const flk_apply_args& a) {
+    return a.q_lut && a.center == 0 && a.q_levels == 128.f && a.q_mul[0] == 1.f && a.q_mul[1] == 1.f && a.q_mul[2] == 1.f &&
+           a.q_add[0] == 1.f && a.q_add[1] == 1.f && a.q_add[2] == 1.f && a.x_scale == 1.f / 128.f && a.x_bias == -1.f && !a.x_lut;
+  }
   bool stem_from_u8() const {
-    return stem_u8_w && cur_apply && cur_pos_bias && cur_apply->x_is_u8 && cur_apply->center == 1 && !cur_apply->delta_dense &&
-           !(getenv("FLK_STEM_U8") && atoi(getenv("FLK_STEM_U8")) == 0);
+    if (!(stem_u8_w && cur_apply && cur_apply->x_is_u8 && !cur_apply->delta_dense)) return false;
+    if (getenv("FLK_STEM_U8") && atoi(getenv("FLK_STEM_U8")) == 0) return false;
+    if (cur_apply->q_lut) return !cur_pos_bias && !cur_apply->delta_per_line && tf_quantised(*cur_apply);
+    return cur_pos_bias && cur_apply->center == 1;
   }
   // head
   float *d_fcw = nullptr, *d_fcb = nullptr, *d_wt = nullptr, *d_feat = nullptr, *d_dfeat = nullptr;
@@ -1459,6 +1468,16 @@ static bool same_mask_args(const flk_apply_args& p, const flk_apply_args& q) {
          p.dclip_dev == q.dclip_dev && p.x_lut == q.x_lut && p.delta_per_line == q.delta_per_line;
 }
 
+// Quantised apply arguments (q_lut) in the fused stem delta-gradient: the gradient is straight through the clip mask 1[lo <= x + a p <= hi],
+// which stem_grad.hip builds from x, delta and the bounds alone -- so the kernels get the same arguments with the quantiser cleared and
+// give the bits they give without it.  center must be 0, as for every quantised apply (`fn`: the entry point, for the message).
+static int straight_through_args(const flk_apply_args* a, const char* fn, flk_apply_args* out) {
+  FLK_REQUIRE(!a->q_lut || a->center == 0, "%s: q_lut (quantised apply) needs center = 0", fn);
+  *out = *a;
+  out->q_lut = nullptr;
+  return FLK_OK;
+}
+
 // start the clip-mask pre-pass of the fused stem delta-gradient on the net's mask stream, behind everything queued on `s` so far (the
 // previous update of delta, the previous GEMM's reads of the scratch); ev_mask_done fires when the mask is in `scratch`
 static int start_mask_prepass(flk_net* n, const flk_apply_args* a, float* scratch, hipStream_t s) {
@@ -1478,7 +1497,8 @@ extern "C" int flk_net_backward_delta(flk_net* n, const float* dlogits, const fl
   if (int rc = check_apply_geometry(n, a, "flk_net_backward_delta")) return rc;
   if (!n->fwd_done) { flk_set_error("flk_net_backward_delta: no forward pass to differentiate"); return FLK_ESTATE; }
   n->dlogits_in = dlogits; n->gx_in = nullptr;
-  const flk_apply_args ac = *a;
+  flk_apply_args ac;
+  if (int rc = straight_through_args(a, "flk_net_backward_delta", &ac)) return rc;
   hipStream_t s = (hipStream_t)stream;
   // the clip mask depends on the clip and on delta only: it runs on a side stream beside the whole backward pass and is joined
   // right in front of the GEMM that consumes it (serial mode: inline)
@@ -1521,8 +1541,10 @@ extern "C" int flk_net_prepare_backward_delta(flk_net* n, const flk_apply_args* 
   if (int rc = check_apply_geometry(n, a, "flk_net_prepare_backward_delta")) return rc;
   n->premask = false;
   if (!(n->multi_stream && n->mask_stream && !n->profile)) return FLK_OK;
-  if (int rc = start_mask_prepass(n, a, scratch, (hipStream_t)stream)) return rc;
-  n->premask = true; n->premask_scratch = scratch; n->premask_args = *a;
+  flk_apply_args ac;
+  if (int rc = straight_through_args(a, "flk_net_prepare_backward_delta", &ac)) return rc;
+  if (int rc = start_mask_prepass(n, &ac, scratch, (hipStream_t)stream)) return rc;
+  n->premask = true; n->premask_scratch = scratch; n->premask_args = ac;
   return FLK_OK;
 }
 

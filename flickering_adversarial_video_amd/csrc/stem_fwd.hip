@@ -34,6 +34,7 @@
 #include <stdlib.h>
 #include <new>
 #include "flk_internal.h"
+#include "quant_encode.h"
 
 namespace {
 
@@ -114,7 +115,13 @@ __device__ inline unsigned pack_bf16(float lo, float hi) {
 #define SF_ON(bit) true
 #endif
 
-template <int NI>
+// QUANT (flk_apply_args.q_lut set, center = 0): the value staged is the one the STORED video holds -- the adversarial byte
+// q = encode_q(clip(x + p, lo, hi)) of flk_adv_export_u8, decoded by the clip's own scalars, q * x_scale + x_bias = (q - 128) / 128: eight
+// significant bits, exact in bf16, so there is no centred clip to protect and nothing for the position-class bias to carry (the caller
+// passes pos_bias = nullptr; the epilogue is the plain one and adds +0, as it does for the all-zero table of adv_flag = 0).  The frame table
+// holds p[0..2] where the plain kernel holds the six clamp bounds; decode by scalars, no table in LDS: the same 52 160 bytes.  A
+// template parameter: the plain instantiations contain none of this.
+template <int NI, bool QUANT>
 __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const StemFwdKP p) {
   typedef SfGeo<NI> G;
   constexpr int SF_HH = G::HH, SF_PP = G::PP, SF_HALO = G::HALO, SF_TASKS = G::TASKS, SF_HT = G::HT;
@@ -152,7 +159,7 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
   glds16(wvoff0, p.w, ring_lds + (unsigned)(wv * 1024));
   glds16(wvoff1, p.w, ring_lds + (unsigned)(wv * 1024) + 4096u);
 
-  // ---- per-frame table: clamp bounds lo - p[c], hi - p[c], source frame, validity ----
+  // ---- per-frame table: clamp bounds lo - p[c], hi - p[c] (QUANT: p[c] itself), source frame, validity ----
   if (tid < SF_TH) {
     const int t = 2 * ot0 - 2 + tid;
     const bool valid = t >= 0 && t < a.T;
@@ -172,8 +179,13 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
       }
     }
     float* e = tab + tid * 8;
-    e[0] = a.lo - pv[0]; e[1] = a.lo - pv[1]; e[2] = a.lo - pv[2];
-    e[3] = a.hi - pv[0]; e[4] = a.hi - pv[1]; e[5] = a.hi - pv[2];
+    if constexpr (QUANT) {
+      e[0] = pv[0]; e[1] = pv[1]; e[2] = pv[2];
+      e[3] = 0.f; e[4] = 0.f; e[5] = 0.f;
+    } else {
+      e[0] = a.lo - pv[0]; e[1] = a.lo - pv[1]; e[2] = a.lo - pv[2];
+      e[3] = a.hi - pv[0]; e[4] = a.hi - pv[1]; e[5] = a.hi - pv[2];
+    }
     e[6] = __int_as_float(tx); e[7] = __int_as_float(valid ? 1 : 0);
   }
   __syncthreads();
@@ -211,17 +223,35 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
         const float* e = tab + pl * 8;
         // byte i of the group has channel (1 + 2 grp + i) mod 3 (the row image starts at byte 48 tw - 8 = 1 mod 3 of a pixel row)
         const int c0 = grp % 3 == 0 ? 1 : grp % 3 == 1 ? 0 : 2;
-        const float l0 = e[0], l1 = e[1], l2 = e[2], h0 = e[3], h1 = e[4], h2 = e[5];
-        float L[3], H[3];
-        L[0] = c0 == 0 ? l0 : c0 == 1 ? l1 : l2; H[0] = c0 == 0 ? h0 : c0 == 1 ? h1 : h2;
-        L[1] = c0 == 0 ? l1 : c0 == 1 ? l2 : l0; H[1] = c0 == 0 ? h1 : c0 == 1 ? h2 : h0;
-        L[2] = c0 == 0 ? l2 : c0 == 1 ? l0 : l1; H[2] = c0 == 0 ? h2 : c0 == 1 ? h0 : h1;
         const unsigned w2[2] = {raw[k].x, raw[k].y};
         float v[8];
+        if constexpr (QUANT) {
+          // the arithmetic of adv_export_u8_kernel, operation by operation: applied() with center = 0, the shared encode, the scalar decode
+          const float p0 = e[0], p1 = e[1], p2 = e[2];
+          float P[3], M[3], A[3];
+          P[0] = c0 == 0 ? p0 : c0 == 1 ? p1 : p2; P[1] = c0 == 0 ? p1 : c0 == 1 ? p2 : p0; P[2] = c0 == 0 ? p2 : c0 == 1 ? p0 : p1;
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const float x = (float)((w2[i >> 2] >> (8 * (i & 3))) & 255u) * a.x_scale + a.x_bias;
-          v[i] = __builtin_amdgcn_fmed3f(x, L[i % 3], H[i % 3]);
+          for (int j = 0; j < 3; ++j) {
+            M[j] = c0 == 0 ? a.q_mul[j] : c0 == 1 ? a.q_mul[(j + 1) % 3] : a.q_mul[(j + 2) % 3];
+            A[j] = c0 == 0 ? a.q_add[j] : c0 == 1 ? a.q_add[(j + 1) % 3] : a.q_add[(j + 2) % 3];
+          }
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const float x = (float)((w2[i >> 2] >> (8 * (i & 3))) & 255u) * a.x_scale + a.x_bias;
+            const float u = clipf(x + P[i % 3], a.lo, a.hi);
+            v[i] = (float)encode_q(u, M[i % 3], A[i % 3], a.q_levels) * a.x_scale + a.x_bias;
+          }
+        } else {
+          const float l0 = e[0], l1 = e[1], l2 = e[2], h0 = e[3], h1 = e[4], h2 = e[5];
+          float L[3], H[3];
+          L[0] = c0 == 0 ? l0 : c0 == 1 ? l1 : l2; H[0] = c0 == 0 ? h0 : c0 == 1 ? h1 : h2;
+          L[1] = c0 == 0 ? l1 : c0 == 1 ? l2 : l0; H[1] = c0 == 0 ? h1 : c0 == 1 ? h2 : h0;
+          L[2] = c0 == 0 ? l2 : c0 == 1 ? l0 : l1; H[2] = c0 == 0 ? h2 : c0 == 1 ? h0 : h1;
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const float x = (float)((w2[i >> 2] >> (8 * (i & 3))) & 255u) * a.x_scale + a.x_bias;
+            v[i] = __builtin_amdgcn_fmed3f(x, L[i % 3], H[i % 3]);
+          }
         }
         unsigned d[4];
 #pragma unroll
@@ -376,11 +406,20 @@ extern "C" int flk_stem_fwd_u8_weights_create(const float* w7, flk_conv_weights*
 extern "C" int flk_stem_fwd_u8(const flk_apply_args* a, const flk_conv_weights* w, const float* bn_scale, const float* bn_bias,
                                const float* pos_bias, int64_t pos_bias_bstride, void* out, int out_ld, void* stream) {
   FLK_REQUIRE(!a || !a->x_lut, "flk_stem_fwd_u8: x_lut (per-channel decode table) is not supported: the I3D stem decodes x_scale / x_bias");
-  FLK_REQUIRE(!a || !a->q_lut, "flk_stem_fwd_u8: q_lut (quantised apply) is not supported: the I3D stem takes the centred clip");
+  const bool quant = a && a->q_lut;       // the QUANT instantiation: the stored byte is staged itself (the table's contents are not read)
+  FLK_REQUIRE(!quant || a->center == 0, "flk_stem_fwd_u8: q_lut (quantised stem) needs center = 0: the stored value has no centred form");
+  FLK_REQUIRE(!quant || !a->delta_dense, "flk_stem_fwd_u8: q_lut (quantised stem) with delta_dense: flicker perturbation [T,3] only");
+  FLK_REQUIRE(!quant || (a->q_levels == 128.f && a->q_mul[0] == 1.f && a->q_mul[1] == 1.f && a->q_mul[2] == 1.f && a->q_add[0] == 1.f &&
+                         a->q_add[1] == 1.f && a->q_add[2] == 1.f),
+              "flk_stem_fwd_u8: q_lut (quantised stem) needs the TF encode q_mul = q_add = 1, q_levels = 128 (got q_levels %g, q_mul %g %g %g, "
+              "q_add %g %g %g)", quant ? a->q_levels : 0.f, quant ? a->q_mul[0] : 0.f, quant ? a->q_mul[1] : 0.f, quant ? a->q_mul[2] : 0.f,
+              quant ? a->q_add[0] : 0.f, quant ? a->q_add[1] : 0.f, quant ? a->q_add[2] : 0.f);
+  FLK_REQUIRE(!quant || (a->x_scale == 1.f / 128.f && a->x_bias == -1.f), "flk_stem_fwd_u8: q_lut (quantised stem) needs the TF decode x_scale = 1/128, "
+              "x_bias = -1, under which a stored byte is exact in bf16 (got x_scale %g, x_bias %g)", quant ? a->x_scale : 0.f, quant ? a->x_bias : 0.f);
   FLK_REQUIRE(!a || !a->delta_per_line, "flk_stem_fwd_u8: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   FLK_REQUIRE(a && w && w->dev && bn_scale && bn_bias && out, "flk_stem_fwd_u8: null argument");
-  FLK_REQUIRE(a->x && a->delta && a->x_is_u8 && a->center == 1 && !a->delta_dense, "flk_stem_fwd_u8: needs a uint8 clip and a flicker "
-              "perturbation applied with center = 1");
+  FLK_REQUIRE(a->x && a->delta && a->x_is_u8 && (quant || a->center == 1) && !a->delta_dense, "flk_stem_fwd_u8: needs a uint8 clip and a flicker "
+              "perturbation applied with center = 1 (center = 0 with q_lut only)");
   FLK_REQUIRE(a->H == 224 && a->W == 224 && a->T >= 2 && a->T % 2 == 0 && a->B > 0, "flk_stem_fwd_u8: clip must be [B, even T, 224, 224, 3] (got %d,%d,%d,%d)",
               a->B, a->T, a->H, a->W);
   FLK_REQUIRE(a->lo <= a->hi, "flk_stem_fwd_u8: lo > hi");
@@ -409,10 +448,15 @@ extern "C" int flk_stem_fwd_u8(const flk_apply_args* a, const flk_conv_weights* 
 #endif
   kp.ntiles = a->B * kp.nTt * SfGeo<NI>::NTH * 14;
   kp.chunk = (kp.ntiles + 7) / 8;
-  static bool attr_set[FLK_MAX_DEVICES] = {};
-  if (int rc = flk_raise_lds_limit((const void*)stem_fwd_u8_kernel<NI>, SfGeo<NI>::LDS, attr_set)) return rc;
-  FLK_LAUNCH_KERNEL(stem_fwd_u8_kernel<NI>, dim3((unsigned)(kp.chunk * 8)), dim3(256), SfGeo<NI>::LDS, st, kp);
+  static bool attr_set[2][FLK_MAX_DEVICES] = {};
+  if (quant) {
+    if (int rc = flk_raise_lds_limit((const void*)stem_fwd_u8_kernel<NI, true>, SfGeo<NI>::LDS, attr_set[1])) return rc;
+    FLK_LAUNCH_KERNEL((stem_fwd_u8_kernel<NI, true>), dim3((unsigned)(kp.chunk * 8)), dim3(256), SfGeo<NI>::LDS, st, kp);
+  } else {
+    if (int rc = flk_raise_lds_limit((const void*)stem_fwd_u8_kernel<NI, false>, SfGeo<NI>::LDS, attr_set[0])) return rc;
+    FLK_LAUNCH_KERNEL((stem_fwd_u8_kernel<NI, false>), dim3((unsigned)(kp.chunk * 8)), dim3(256), SfGeo<NI>::LDS, st, kp);
+  }
   FLK_CHECK_HIP(hipGetLastError());
-  flk_last_kernel_tag = "stem_fwd_u8_kernel";
+  flk_last_kernel_tag = quant ? "stem_fwd_u8_kernel<quant>" : "stem_fwd_u8_kernel";
   return FLK_OK;
 }

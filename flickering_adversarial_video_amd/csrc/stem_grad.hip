@@ -484,7 +484,10 @@ static int sg_check(const flk_apply_args* a) {
   FLK_REQUIRE(a && a->x && a->delta, "flk_stem_delta_grad: null argument");
   FLK_REQUIRE(!a->delta_dense, "flk_stem_delta_grad: flicker perturbation [T,3] only (the dense attack needs the per-pixel gradient)");
   FLK_REQUIRE(!a->x_lut, "flk_stem_delta_grad: x_lut (per-channel decode table) is not supported: the I3D stem decodes x_scale / x_bias");
-  FLK_REQUIRE(!a->q_lut, "flk_stem_delta_grad: q_lut (quantised apply) is not supported: the I3D stem takes the centred clip");
+  // (the straight-through estimator of the quantised stem IS the clip mask below, which reads x, delta and the bounds only: a caller that
+  //  trains on the stored clip passes the same arguments with q_lut cleared, as flk_net_backward_delta does)
+  FLK_REQUIRE(!a->q_lut, "flk_stem_delta_grad: q_lut (quantised apply) is not taken here: the straight-through gradient is the clip mask of the "
+              "same arguments without it");
   FLK_REQUIRE(!a->delta_per_line, "flk_stem_delta_grad: delta_per_line (one value per line of a frame) is not supported by the I3D stem");
   if (int rc = sg_check_sizes(a->B, a->T, a->H, a->W)) return rc;
   FLK_REQUIRE(a->lo <= a->hi, "flk_stem_delta_grad: lo > hi");

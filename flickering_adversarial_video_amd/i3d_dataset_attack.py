@@ -132,7 +132,8 @@ def main(default_section, argv=None):
     eng = FlickerI3D(W, batch_size=B, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, device=local_rank, dense_delta=dense,
                      cyclic_flag_default_c=float(bool(c.CYCLIC_ATTACK)),
                      cyclic_pert_flag_default_c=float(bool(c.get("CYCLIC_PERTURBATION_ATTACK", False))),
-                     optimizer=c.OPTIMIZER, pgd_eps=c.PGD_EPS if c.OPTIMIZER == "pgd" else None)
+                     optimizer=c.OPTIMIZER, pgd_eps=c.PGD_EPS if c.OPTIMIZER == "pgd" else None,
+                     quantise_train=bool(c.get("QUANTISE_TRAIN", False)))     # [new] steps and evaluations on the stored video
     train_files = tio.list_tfrecords(c.TF_RECORDS_TRAIN_PATH, c.get("NUM_OF_TRAIN_TF_RECORDS"))
     val_files = tio.list_tfrecords(c.TF_RECORDS_VAL_PATH, c.get("NUM_OF_VAL_TF_RECORDS"))
     if not train_files:

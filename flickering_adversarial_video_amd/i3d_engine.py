@@ -93,12 +93,24 @@ class FlickerI3D:
     (``lr`` is the step size alpha; ``pgd_eps`` defaults to 0.4, the apply clip of kinetics_i3d_utils.py:104, and is required for
     the dense perturbation, which has no apply clip).  It keeps no state: there are no moment buffers (``adam_m`` / ``adam_v`` are
     None).  Data-parallel: the sign is taken after the all-reduce, so every rank takes the identical step.
+
+    ``quantise_train=True`` (flicker perturbation only; default off: nothing changes, launch for launch) trains and scores on the
+    STORED clip: the 8-bit frames ``adversarial_inputs_u8`` holds, decoded again -- see the constructor.
     """
 
     def __init__(self, weights, batch_size=1, frames=SAMPLE_VIDEO_FRAMES, dtype="bf16", device=0, dense_delta=False,
                  cyclic_flag_default_c=0.0, cyclic_pert_flag_default_c=0.0, default_adv_flag_c=1.0, process_group=None,
-                 seed=0, kinetics_classes=None, per_clip_delta=False, optimizer="adam", pgd_eps=None):
+                 seed=0, kinetics_classes=None, per_clip_delta=False, optimizer="adam", pgd_eps=None, quantise_train=False):
         self.optimizer = check_optimizer(optimizer)
+        # quantise_train: the attack is optimised on the STORED video.  Every forward that applies the perturbation (``step`` in all its
+        # variants, ``logits``, ``__call__``, ``autotune``) puts each value through the 8-bit export's encode and decode
+        # (flk_apply_args.q_lut, TF dialect), so its logits are bit for bit those of the frames ``adversarial_inputs_u8`` /
+        # ``quantised_logits`` deliver, and a step's softmax / label_prob / argmax are the stored clip's verdict at no extra forward
+        # pass; the gradient is straight through the clip mask (the delta-gradient kernels as they are).  bf16 plan, uint8 clip: the
+        # stem stages the stored byte itself (csrc/stem_fwd.hip, QUANT); every other plan or clip: the quantised apply + the folded stem.
+        self.quantise_train = bool(quantise_train)
+        if self.quantise_train and dense_delta:
+            raise ValueError("quantise_train: flicker perturbation only (dense_delta is the reference's L12 baseline, not the delivered flicker)")
         if not torch.cuda.is_available():
             raise RuntimeError("FlickerI3D needs an MI355X (HIP) device; there is no CPU fallback")
         torch.cuda.set_device(device)
@@ -204,12 +216,19 @@ class FlickerI3D:
             return self.eps_rgb.view(self.B, self.T, 1, 1, 3)
         return self.eps_rgb if self.dense else self.eps_rgb.view(self.T, 1, 1, 3)
 
+    def _apply_mode(self):
+        """how the plan's input is formed (keywords of ops.make_apply_args): the stored value (quantise_train), else the centred clip
+        where the plan has the exact perturbation path"""
+        if self.quantise_train:
+            return dict(quantise="tf", center=False)
+        return dict(center=self.exact_delta_forward)
+
     def _apply_args(self, x, adv_flag, cyclic, cyclic_pert):
         sx = int(self._rng.integers(0, self.T)) if cyclic else 0          # one shift per step for the whole batch
         sp = int(self._rng.integers(0, self.T)) if cyclic_pert else 0     # (kinetics_i3d_utils.py:115,130)
         self._last_x, self._last_shifts = x, (sx, sp)
         return ops.make_apply_args(x, self.eps_rgb, dialect="tf", dclip=0.0 if self.dense else 0.4, adv_flag=adv_flag,
-                                   shift_x=sx, shift_p=sp, fold_t=ops.I3D_FOLD, center=self.exact_delta_forward)
+                                   shift_x=sx, shift_p=sp, fold_t=ops.I3D_FOLD, **self._apply_mode())
 
     def _forward(self, a):
         """apply + network forward into self._logits: one call -- the plan applies each half of the batch on the stream that half's
@@ -485,8 +504,8 @@ class FlickerI3DInference(FlickerI3D):
         self.last_shift_p = int(self._rng.integers(0, self.T)) if cyclic_eps_flag else 0
         if quantise:
             frames = self._export_u8(x, float(adv_flag), self.last_shift_x, self.last_shift_p, 0.0)
-            a = ops.make_apply_args(frames, self.eps_rgb, dialect="tf", dclip=0.0, adv_flag=0.0, fold_t=ops.I3D_FOLD, center=self.exact_delta_forward)
+            a = ops.make_apply_args(frames, self.eps_rgb, dialect="tf", dclip=0.0, adv_flag=0.0, fold_t=ops.I3D_FOLD, **self._apply_mode())
             return torch.softmax(self._forward(a), -1)
         a = ops.make_apply_args(x, self.eps_rgb, dialect="tf", dclip=0.0, adv_flag=float(adv_flag), shift_x=self.last_shift_x,
-                                shift_p=self.last_shift_p, fold_t=ops.I3D_FOLD, center=self.exact_delta_forward)
+                                shift_p=self.last_shift_p, fold_t=ops.I3D_FOLD, **self._apply_mode())
         return torch.softmax(self._forward(a), -1)

@@ -86,6 +86,31 @@ def encode_u8(x):
     return q.astype(np.uint8)
 
 
+def quantised_stem_bytes(xu, delta, *, dclip, adv_flag, shift_x, shift_p, dclip_dev=None):
+    """The byte the quantised uint8 stem stages for every value of the clip (csrc/stem_fwd.hip, QUANT; also what flk_adv_export_u8 stores
+    for the same arguments in the TF dialect), restated in numpy float32 with one rounding per operation:
+        x = u8 / 128 - 1 (exact);  p = adv_flag * clip(delta, +-dclip);  u = clip(x + p, -1, 1);  q = encode_u8(u)       (np.rint: half to even)
+    under the rolls x'[t] = x[(t - shift_x) mod T], p'[t] = p[(t - shift_p) mod T].  xu: uint8 [B,T,H,W,3]; delta: fp32 [T,3] or [B,T,3] (one
+    per clip); dclip <= 0: no clamp of delta; dclip_dev: fp32 [B], per-clip bounds replacing dclip.  Returns uint8 [B,T,H,W,3]; the value the
+    network sees is q / 128 - 1 = (q - 128) / 128, exact in bf16."""
+    f32 = np.float32
+    xu = np.asarray(xu)
+    assert xu.dtype == np.uint8 and xu.ndim == 5 and xu.shape[-1] == 3
+    B, T = xu.shape[:2]
+    x = xu.astype(f32) * f32(1.0 / 128.0) + f32(-1.0)
+    x = np.roll(x, shift_x, axis=1)
+    d = np.asarray(delta, dtype=f32).reshape(-1, T, 3)
+    if dclip_dev is not None:
+        dc = np.asarray(dclip_dev, dtype=f32).reshape(B, 1, 1)
+        d = np.where(dc > 0, np.minimum(np.maximum(d, -dc), dc), d)
+    elif dclip > 0:
+        d = np.minimum(np.maximum(d, -f32(dclip)), f32(dclip))
+    p = (d * f32(1.0)).astype(f32)                       # inv_std = 1 in the TF dialect
+    p = np.roll(f32(adv_flag) * p, shift_p, axis=1) if adv_flag != 0 else np.zeros_like(p)
+    u = (x + p[:, :, None, None, :]).astype(f32)
+    return encode_u8(np.minimum(np.maximum(u, f32(-1.0)), f32(1.0)))
+
+
 def load_i3d_weights(model_cfg):
     """Weights for FlickerI3D from the MODEL section of run_config.yml: ``WEIGHTS_NPZ`` ({variable name: array} archive) if
     set, else the TF checkpoint ``CKPT_PATH`` (the reference's ``init_model``, kinetics_i3d_utils.py:41-62, read without

@@ -307,8 +307,10 @@ typedef struct {
                                 (TF: x_scale / x_bias).  x_q is NOT clamped again: a value the clamp holds at lo or hi is stored as the
                                 level nearest the bound (the torch dialect's bounds are byte values of one channel only), and the stored
                                 video decodes to that level, up to half a level outside [lo, hi].
-                                FLK_EINVAL before any GPU call with center != 0 or q_levels <= 0; refused by the I3D-only entry points as
-                                x_lut is.  flk_adv_export_u8 ignores the four fields: it already is the quantiser.
+                                FLK_EINVAL before any GPU call with center != 0 or q_levels <= 0.  Of the I3D-only entry points
+                                flk_stem_fwd_u8 takes it in the TF dialect (its quantised instantiation: see there) and the others
+                                refuse it as they refuse x_lut -- flk_net_forward_apply / flk_net_backward_delta route such arguments
+                                themselves.  flk_adv_export_u8 ignores the four fields: it already is the quantiser.
                                 Gradient: the straight-through estimator d(x_q)/d(u) := 1[lo <= u <= hi], u = x + a p' -- exactly the mask
                                 flk_perturb_grad_reduce computes from x, delta and the clamp bounds; its kernels do not read the four
                                 fields and give the same bits with and without them.  (The four fields sit in front of x_lut, which
@@ -504,7 +506,17 @@ int flk_stem_delta_bias(const flk_apply_args* a, const float* sums_dev, float* t
  * convolution is clamp(x, lo - p, hi - p) = clip(x + p, lo, hi) - p; the perturbation's own contribution comes from pos_bias =
  * flk_stem_delta_bias's table, per clip when pos_bias_bstride != 0, or NULL).  weights: flk_stem_fwd_u8_weights_create from the
  * canonical [7,7,7,3,64] array (destroy with flk_conv_weights_destroy); bn_scale / bn_bias: fp32 [64];
- * out: bf16 [B,T/2,112,112,out_ld], channels [0,64).  bf16 only (the fp32 parity mode keeps the two-kernel path). */
+ * out: bf16 [B,T/2,112,112,out_ld], channels [0,64).  bf16 only (the fp32 parity mode keeps the two-kernel path).
+ * Quantised stem (a->q_lut != NULL, a->center = 0): the value fed to the convolution is the one the STORED video holds,
+ *   x = u8 * x_scale + x_bias;  u = clip(x + p, lo, hi);  q = the encode of flk_export_args on u (the device function flk_adv_export_u8
+ *   uses);  v = q * x_scale + x_bias
+ * -- the TF dialect only: q_mul = q_add = 1, q_levels = 128, x_scale = 1/128, x_bias = -1, where v = (q - 128) / 128 has eight
+ * significant bits and is exact in bf16, so nothing is left for the centred clip to protect and the perturbation contributes nothing
+ * through pos_bias (pass NULL, or the all-zero table).  q_lut only SELECTS the mode here: its contents are not read (the decode is the two
+ * scalars).  The output is, bit for bit, that of the plain call on the bytes flk_adv_export_u8 writes for the same arguments, with
+ * adv_flag = 0.  Positions outside the clip (SAME padding) stay zero.  FLK_EINVAL before any GPU call, naming the field: q_lut with
+ * center != 0, with delta_dense, with another encode (q_levels, q_mul, q_add) or another decode (x_scale, x_bias); center = 0 without q_lut.
+ * Gradient: straight through the clip mask -- flk_stem_delta_grad on the same arguments with q_lut cleared. */
 int flk_stem_fwd_u8_weights_create(const float* w7_dhwio, flk_conv_weights** out);
 int flk_stem_fwd_u8(const flk_apply_args* a, const flk_conv_weights* w, const float* bn_scale, const float* bn_bias,
                     const float* pos_bias, int64_t pos_bias_bstride, void* out, int out_ld, void* stream);
@@ -880,14 +892,20 @@ int flk_net_forward_flicker(flk_net* n, const void* x_in, const flk_apply_args* 
  * a->fold_t must be the plan's layout, flk_net_input_fold(): 3 for I3D; VideoResNet plans 1 in fp32 (16 channels) and 4 in bf16 (32 channels:
  * every value as two bf16 numbers, [hi(16) | lo(16)]).  Same logits as apply followed by flk_net_forward[_flicker].
  * x_s2d_out is SCRATCH: when the stem reads the uint8 clip itself (I3D plan in bf16, a->x_is_u8 with a->center = 1 -- the default
- * engine path) it is left untouched, so a caller that needs the space-to-depth tensor calls flk_perturb_apply_s2d itself. */
+ * engine path) it is left untouched, so a caller that needs the space-to-depth tensor calls flk_perturb_apply_s2d itself.
+ * Quantised arguments (a->q_lut, a->center = 0: the plan sees the STORED clip): on the I3D plan in bf16 at 224 x 224, a uint8 clip with a
+ * flicker delta in the TF dialect goes to the quantised instantiation of flk_stem_fwd_u8 -- half-batch streams and per-clip slices as in
+ * the plain mode, x_s2d_out untouched; every other plan or clip (fp32 plans, an fp32 clip, FLK_STEM_U8=0, the torch encode) takes the
+ * quantised flk_perturb_apply_s2d into x_s2d_out and the folded stem. */
 int flk_net_forward_apply(flk_net* n, const flk_apply_args* a, void* x_s2d_out, float* logits, void* stream);
 /* dlogits fp32 [B,C] -> gradient w.r.t. the network input: dtype of x_in; layout of x_in for I3D ([B,T/2,H/2,W/2,32]); VideoResNet plans ALWAYS
  * [B,T,H/2,W/2,16] -- the gradient of x_adv -- also where the bf16 input has 32 channels (hi | lo) */
 int flk_net_backward(flk_net* n, const float* dlogits, void* gx_in, void* stream);
 /* backward straight to the flickering perturbation: the plan without the stem's data-gradient, then flk_stem_delta_grad on the
  * stem's output gradient.  gdelta fp32 [T,3]; scratch: flk_stem_delta_grad_scratch_bytes(B, T, H).  I3D in bf16 only
- * (flk_net_has_backward_delta() tells); `a` = the flk_apply_args the clip of this forward pass was applied with. */
+ * (flk_net_has_backward_delta() tells); `a` = the flk_apply_args the clip of this forward pass was applied with.  Quantised arguments
+ * (a->q_lut with a->center = 0; also flk_net_prepare_backward_delta): the straight-through gradient -- the clip mask of the same arguments,
+ * the same bits as without q_lut; center != 0 with q_lut is FLK_EINVAL. */
 int flk_net_has_backward_delta(const flk_net* n);
 int flk_net_backward_delta(flk_net* n, const float* dlogits, const flk_apply_args* a, float* gdelta, float* scratch, void* stream);
 /* optional, before the forward pass of the same iteration: start the clip-mask pre-pass of the coming flk_net_backward_delta(a, scratch)

@@ -81,6 +81,11 @@ def attack_clip(eng, x, label_id, c, max_steps, target_id=None, log_every=100):
     res.update(correct_cls_prob=float(clean[label_id]), softmax_init=clean.cpu().numpy(), total_steps=step,
                fatness=float(np.abs(d).mean() / 2 * 100), smoothness=float(np.abs(d - np.roll(d, 1, 0)).mean() / 2 * 100),
                adv_video=None, beta_0=c.LAMBDA, beta_1=c.BETA_1, beta_2=c.BETA_2, beta_3=beta3)
+    # [new] QUANTISE_TRAIN: every forward above saw the stored clip, so the verification that ended the loop IS the verdict on the 8-bit
+    # frames; with SAVE_ADV_U8 it is stored beside them (the keys of EVAL_QUANTISED, at no extra forward pass)
+    if getattr(eng, "quantise_train", False) and c.get("SAVE_ADV_U8", False):
+        res["quantised_pred"] = int(sm.argmax())
+        res["quantised_is_adversarial"] = bool(is_adv(sm))
     return res
 
 
@@ -172,6 +177,9 @@ def attack_clips_batched(eng, videos, c, max_steps, target_id=None, log_every=10
                 res.update(correct_cls_prob=float(st["clean"][st["label"]]), softmax_init=st["clean"].cpu().numpy(), total_steps=st["step"],
                            fatness=float(np.abs(d).mean() / 2 * 100), smoothness=float(np.abs(d - np.roll(d, 1, 0)).mean() / 2 * 100),
                            adv_video=eng.adversarial_inputs_rgb[b:b + 1].cpu().numpy(), beta_0=c.LAMBDA, beta_1=c.BETA_1, beta_2=c.BETA_2, beta_3=beta3)
+                if getattr(eng, "quantise_train", False) and c.get("SAVE_ADV_U8", False):      # [new] as in attack_clip
+                    res["quantised_pred"] = int(sm_all[b].argmax())
+                    res["quantised_is_adversarial"] = bool(is_adv(b, sm_all[b]))
                 add_u8_results(eng, res, c, st["label"], target_id if targeted else None, b)
                 yield st["tag"], res
                 yield from refill(b)
@@ -199,6 +207,8 @@ def main():
     ap.add_argument("--max-steps", type=int, default=None)
     ap.add_argument("--frames", type=int, default=None)
     ap.add_argument("--dtype", default=None)
+    ap.add_argument("--quantise-train", action="store_true", help="optimise on the stored video: every step and the stop criterion see the "
+                    "8-bit frames, decoded again (QUANTISE_TRAIN: True of the config section)")
     a = ap.parse_args()
     cfg = cfgmod.load_config(a.config)
     c = cfg.SINGLE_VIDEO_ATTACK
@@ -211,6 +221,8 @@ def main():
     max_steps = a.max_steps if a.max_steps is not None else c.MAX_NUM_STEP
     # [new] OPTIMIZER: pgd -- projected sign-gradient steps of radius PGD_EPS instead of Adam
     opt = dict(optimizer=c.OPTIMIZER, pgd_eps=c.PGD_EPS if c.OPTIMIZER == "pgd" else None)
+    # [new] QUANTISE_TRAIN / --quantise-train: the engine applies, steps and verifies on the stored video
+    opt["quantise_train"] = bool(a.quantise_train or c.QUANTISE_TRAIN)
     if a.batch > 1:
         eng = FlickerI3D(W, batch_size=a.batch, frames=T, dtype=a.dtype or cfg.MODEL.DTYPE, per_clip_delta=True, **opt)
         meta = {}
