@@ -106,6 +106,7 @@ class PrepBox(C.Structure):
 
 
 FLK_CODEC_444, FLK_CODEC_420 = 444, 420
+FLK_CODEC_GRAD_STE, FLK_CODEC_GRAD_CUBIC = 1, 2
 
 
 class CodecClip(C.Structure):
@@ -117,9 +118,19 @@ class CodecArgs(C.Structure):
     _fields_ = [("nclip", C.c_int), ("quality", C.c_int), ("subsampling", C.c_int), ("clips", C.POINTER(CodecClip))]
 
 
+class GradImageClip(C.Structure):
+    _fields_ = [("dst", C.c_void_p), ("pitch_t", C.c_int64), ("pitch_h", C.c_int64), ("Hs", C.c_int), ("Ws", C.c_int), ("tab_h", C.c_int64),
+                ("tab_w", C.c_int64)]
+
+
 _SIGS = {
     "flk_codec_tables": (C.c_int, [C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "flk_codec_roundtrip_u8": (C.c_int, [C.POINTER(CodecArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_codec_grad_scratch_bytes": (C.c_int64, [C.POINTER(CodecArgs), C.c_int]),
+    "flk_codec_grad": (C.c_int, [C.POINTER(CodecArgs), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "flk_clip_prepare_grad_image": (C.c_int, [C.c_int, C.POINTER(GradImageClip), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_int, C.c_void_p]),
     "flk_codec_inter_step": (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     "flk_codec_roundtrip_gop_u8": (C.c_int, [C.POINTER(CodecArgs), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),

@@ -235,7 +235,8 @@ extern "C" int flk_codec_tables(int quality, int32_t* qluma, int32_t* qchroma) {
 
 // what both codec entries check of the views, the quality and the subsampling.  have_idx: the launch names its own source frames, so
 // T_out is not held against the clips' T.  stats_pixels: the largest padded frame stats are taken on (0: no stats asked for)
-static int check_codec_args(const char* fn, const flk_codec_args* a, bool have_idx, int T_out, int64_t stats_pixels) {
+// need_dst: the entry writes the clips' dst views (flk_codec_grad reads the sources only and leaves dst unused)
+static int check_codec_args(const char* fn, const flk_codec_args* a, bool have_idx, int T_out, int64_t stats_pixels, bool need_dst = true) {
   FLK_REQUIRE(a, "%s: null argument", fn);
   FLK_REQUIRE(a->clips, "%s: null clip list", fn);
   FLK_REQUIRE(a->nclip >= 1 && a->nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", fn, a->nclip, FLK_PREP_MAX_CLIPS);
@@ -245,16 +246,16 @@ static int check_codec_args(const char* fn, const flk_codec_args* a, bool have_i
   const int M = a->subsampling == FLK_CODEC_420 ? 16 : 8;
   for (int i = 0; i < a->nclip; ++i) {
     const flk_codec_clip& c = a->clips[i];
-    FLK_REQUIRE(c.src && c.dst, "%s: clip %d: null source or destination", fn, i);
+    FLK_REQUIRE(c.src && (c.dst || !need_dst), "%s: clip %d: null source or destination", fn, i);
     FLK_REQUIRE(c.T > 0 && c.Hs > 0 && c.Ws > 0, "%s: clip %d: source size %d x %d x %d", fn, i, c.T, c.Hs, c.Ws);
     FLK_REQUIRE(c.Hs <= 0x3fffffff && c.Ws <= 0x1fffffff, "%s: clip %d: frame size %d x %d", fn, i, c.Hs, c.Ws);
     FLK_REQUIRE(c.pitch_h >= (int64_t)c.Ws * 3 && c.pitch_h <= 0x7fffffff && c.pitch_t > 0,
                 "%s: clip %d: source pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i, (long long)c.pitch_t,
                 (long long)c.pitch_h);
-    FLK_REQUIRE(c.dst_pitch_h >= (int64_t)c.Ws * 3 && c.dst_pitch_h <= 0x7fffffff && c.dst_pitch_t > 0,
+    FLK_REQUIRE(!need_dst || (c.dst_pitch_h >= (int64_t)c.Ws * 3 && c.dst_pitch_h <= 0x7fffffff && c.dst_pitch_t > 0),
                 "%s: clip %d: destination pitches (frame %lld, row %lld bytes) must be positive, a row at least 3 * Ws", fn, i,
                 (long long)c.dst_pitch_t, (long long)c.dst_pitch_h);
-    FLK_REQUIRE((const uint8_t*)c.dst != c.src, "%s: clip %d: the destination is the source (an MCU reads pixels other workgroups write)", fn, i);
+    FLK_REQUIRE(!need_dst || (const uint8_t*)c.dst != c.src, "%s: clip %d: the destination is the source (an MCU reads pixels other workgroups write)", fn, i);
     FLK_REQUIRE(have_idx || T_out <= c.T, "%s: clip %d: T_out %d above its %d frames (no frame_idx)", fn, i, T_out, c.T);
     if (stats_pixels) {
       const int64_t Hp = ((int64_t)c.Hs + M - 1) / M * M, Wp = ((int64_t)c.Ws + M - 1) / M * M;
@@ -338,6 +339,55 @@ extern "C" int flk_codec_roundtrip_mc_u8(const flk_codec_args* a, int gop, int s
   FLK_REQUIRE(scratch_bytes >= need, "%s: scratch of %lld bytes, flk_codec_mc_scratch_bytes asks for %lld", fn, (long long)scratch_bytes,
               (long long)need);
   return flk_codec_roundtrip_mc_launch(a, gop, search, first, count, T_max, tone, stats, mv, mv_stride, scratch, (hipStream_t)stream);
+}
+
+// The codec's backward (csrc/codec.hip): flk_codec_roundtrip_u8's contract on the sources, the gradient images packed clip after clip
+long long flk_codec_grad_tiles_host(const flk_codec_args* a);
+int flk_codec_grad_launch(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int mode, const float* g_out,
+                          const float* slope, const float* scale, float* gdelta, float* g_in, float* partials, hipStream_t stream);
+
+extern "C" int64_t flk_codec_grad_scratch_bytes(const flk_codec_args* a, int T_out) {
+  if (!a || a->nclip > FLK_PREP_MAX_CLIPS || T_out < 1 || T_out > 65535) return 0;
+  return (int64_t)flk_codec_grad_tiles_host(a) * a->nclip * T_out * 3 * (int64_t)sizeof(float);
+}
+
+extern "C" int flk_codec_grad(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int mode, const float* g_out,
+                              const float* slope, const float* scale, float* gdelta, float* g_in, float* partials, void* stream) {
+  const char* fn = "flk_codec_grad";
+  FLK_REQUIRE(mode == FLK_CODEC_GRAD_STE || mode == FLK_CODEC_GRAD_CUBIC, "%s: mode %d is neither FLK_CODEC_GRAD_STE nor FLK_CODEC_GRAD_CUBIC", fn, mode);
+  FLK_REQUIRE(slope && scale && gdelta, "%s: null slope, scale or gdelta", fn);
+  FLK_REQUIRE(g_out && partials, "%s: null g_out or partials", fn);
+  FLK_REQUIRE(g_in != g_out, "%s: g_in is g_out (a block reads gradients other workgroups' pixels wrote)", fn);
+  if (int rc = check_codec_args(fn, a, frame_idx != nullptr, T_out, 0, false)) return rc;
+  return flk_codec_grad_launch(a, frame_idx, T_out, tone, mode, g_out, slope, scale, gdelta, g_in, partials, (hipStream_t)stream);
+}
+
+// The transpose of the resampling on images (csrc/prepare.hip)
+int flk_clip_prepare_grad_image_launch(int nclip, const flk_grad_image_clip* clips, int T_out, int Ho, int Wo, int K, const int32_t* tables,
+                                       const void* gx_s2d, int dtype, hipStream_t stream);
+
+extern "C" int flk_clip_prepare_grad_image(int nclip, const flk_grad_image_clip* clips, int T_out, int Ho, int Wo, int K, const int32_t* tables,
+                                           int64_t table_words, const void* gx_s2d, int dtype, void* stream) {
+  static const char* who = "flk_clip_prepare_grad_image";
+  FLK_REQUIRE(clips && tables && gx_s2d, "%s: null clips, tables or gx_s2d", who);
+  FLK_REQUIRE(nclip >= 1 && nclip <= FLK_PREP_MAX_CLIPS, "%s: nclip %d outside 1..%d", who, nclip, FLK_PREP_MAX_CLIPS);
+  FLK_REQUIRE(T_out >= 1 && T_out <= 65535, "%s: T_out %d outside 1..65535", who, T_out);
+  FLK_REQUIRE(Ho > 0 && Wo > 0 && Ho % 2 == 0 && Wo % 2 == 0, "%s: Ho and Wo must be positive and even (the folded gradient layout), got %d x %d", who, Ho, Wo);
+  FLK_REQUIRE(K >= 1 && K <= Ho + Wo, "%s: K %d outside 1..Ho + Wo", who, K);
+  FLK_REQUIRE(((size_t)gx_s2d & 15) == 0, "%s: gx_s2d must be 16-byte aligned (got %p)", who, gx_s2d);
+  FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "%s: bad dtype", who);
+  for (int i = 0; i < nclip; ++i) {
+    const flk_grad_image_clip& c = clips[i];
+    FLK_REQUIRE(c.dst, "%s: clip %d: null destination", who, i);
+    FLK_REQUIRE(c.Hs > 0 && c.Ws > 0 && c.Ws <= 0x1fffffff, "%s: clip %d: source size %d x %d", who, i, c.Hs, c.Ws);
+    FLK_REQUIRE(c.pitch_h >= (int64_t)c.Ws * 3 && c.pitch_t >= c.pitch_h * (c.Hs - 1) + (int64_t)c.Ws * 3,
+                "%s: clip %d: pitches (frame %lld, row %lld floats) must hold a row of 3 * Ws and a frame of Hs rows", who, i, (long long)c.pitch_t,
+                (long long)c.pitch_h);
+    FLK_REQUIRE(c.tab_h >= 0 && c.tab_w >= 0 && c.tab_h + (int64_t)c.Hs * (2 + K) <= table_words && c.tab_w + (int64_t)c.Ws * (2 + K) <= table_words,
+                "%s: clip %d: its tables (rows at word %lld, columns at %lld, %d words an entry) leave the %lld words given", who, i,
+                (long long)c.tab_h, (long long)c.tab_w, 2 + K, (long long)table_words);
+  }
+  return flk_clip_prepare_grad_image_launch(nclip, clips, T_out, Ho, Wo, K, tables, gx_s2d, dtype, (hipStream_t)stream);
 }
 
 // The gradient of a toned preparation (csrc/prepare.hip) and the slope tables it resamples (csrc/attack.hip, csrc/illum.hip)

@@ -34,6 +34,9 @@
 //
 // Motion-compensated P-frames (codec_mc_kernel below): a full-pel block search per 16x16 macroblock in the previous
 // reconstruction, which then reaches across tiles: one launch per frame position of the GOP, the planes in a workspace in memory.
+//
+// The backward of the intra codec (codec_grad_kernel at the end of the file): a surrogate differentiated per frame, its
+// constants taken from the integer forward of each block, which is recomputed with the phases A, B and the transform passes above.
 #include "flk_internal.h"
 
 namespace {
@@ -843,5 +846,420 @@ int flk_codec_roundtrip_mc_launch(const flk_codec_args* a, int gop, int search, 
       FLK_CHECK_HIP(hipGetLastError());
     }
   }
+  return FLK_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The codec's backward (flk_codec_grad; videoresnet_spec.codec_grad_host is the definition in float64).  The forward
+// stays the integer codec above; the backward differentiates a surrogate of it, per frame, whose constants come from the integer
+// forward of each block, recomputed here and not stored:
+//   colour   the derivative of the fixed-point definitions: the integer constants over 2^16 (dyadic, exact in fp32); rounding: 1
+//   clamps   the plane clamp after the inverse transform and the RGB clamp pass the gradient where the UNCLAMPED integer lies in 0..255
+//   pad      the transpose of the replication: the padded pixels' gradients are added onto the last row and column
+//   4:2:0    the box mean gives 1/4 to each of its four pixels; the replication on decode sums its four pixels
+//   DCT      the orthonormal 8x8 DCT-II matrix C in fp32 (kDct): G = C g C^T is the transpose of the inverse, C^T G C of the forward
+//            (the forward's x 8 and the quantiser's 8 Q cancel)
+//   quant    per coefficient f with level lev: r = (f - lev * 8 Q) / (8 Q) in [-1/2, 1/2] from the integers; the factor d is 1
+//            (FLK_CODEC_GRAD_STE) or 3 r^2 (FLK_CODEC_GRAD_CUBIC: the rounding u -> round(u) + (u - round(u))^3)
+// g_out [Hs][Ws][3] -> RGB mask, M_dec^T, chroma 2x2 sum, plane mask, C . C^T, x d, C^T . C, chroma 1/4 spread, padding fold, M_enc^T
+// -> g_in [Hs][Ws][3];   gdelta[k][t][c] = scale[k][t][c] * sum over pixels of g_in(p, c) * slope[k][t][v(p, c)][c], v the SOURCE byte.
+// Mapping: the forward's tiling and its phases A and B unchanged; every thread owns exactly one 8x8 block of the tile (192 blocks), so
+// what the integer forward of a block leaves for its backward -- the remainders f - lev * 8 Q, two int16 to a register, and the 64
+// bits of the plane mask -- stays in that thread's registers across the barriers:
+//   C1  codec_grad_block_forward: the block's integer forward; the reconstruction in place (the RGB mask reads all three planes)
+//   D1  per pixel: unclamped RGB from the reconstruction, g_out through the mask and M_dec^T into the fp32 gradient planes (4:2:0:
+//       one thread per chroma sample, its four pixels in the order of build_planes)
+//   C2  codec_grad_block: the block's gradient through mask, C . C^T, d, C^T . C, in place
+//   E   per image pixel: spread, fold (rows outer, columns inner, ascending from +0), M_enc^T, optional g_in store, times the slope of
+//       its source byte; a thread adds its pixels k = tid, tid + 192, .. ascending from +0; lanes fold by the shuffle tree 32 .. 1, the
+//       three waves ascending from +0: partials[k][t][tile][c].  The finishing launch adds a frame's tiles ascending from +0 and
+//       multiplies by scale (a zero scale writes +0).  No atomics: repeats are bitwise equal, a clip's result is that of a call with
+//       it alone (the tile sums do not see the grid).
+// The gradient planes are fp32 in LDS, BLOCK-MAJOR: block b at b * kGB floats, kGB = 64 + 4 -- a thread reads its block as sixteen
+// 16-byte accesses whose lanes lie 272 bytes apart (4 banks on from lane to lane: sixteen lanes cover the 64 banks once), where a
+// row-major plane would put lanes 32 bytes apart, two to a bank.
+namespace {
+
+constexpr int kGB = 68;                        // floats between the blocks of a gradient plane
+
+struct CodecGradLaunch {
+  const int* idx;                              // device int32 [nclip][gridDim.y] or null
+  const uint8_t* tone;                         // device uint8 [nclip][gridDim.y][256][3] or null
+  const float* slope;                          // device fp32 [nclip][gridDim.y][256][3]
+  float* partials;                             // device fp32 [nclip][gridDim.y][max_tiles][3]
+  const float* g_out;                          // the packed gradient images; a clip's dst is its first frame IN g_out, its pitches floats
+  float* g_in;                                 // packed as g_out, or null
+  int mode, max_tiles;
+  unsigned short q[2][64];
+  CodecClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(sizeof(CodecGradLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+// one 8-point pass in place with the fp32 orthonormal DCT-II matrix C[u][x] = a(u) cos((2 x + 1) u pi / 16) (a(0) = sqrt(1/8), else
+// 1/2; float64 values rounded once): y = C x, or with T y = C^T x; every output the chain fma(c7, x7, .. fma(c1, x1, c0 * x0))
+template <bool T>
+__device__ __forceinline__ void dct8f(float& x0, float& x1, float& x2, float& x3, float& x4, float& x5, float& x6, float& x7) {
+  constexpr float C[8][8] = {
+      {0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f},
+      {0.490392625f, 0.415734798f, 0.277785122f, 0.0975451618f, -0.0975451618f, -0.277785122f, -0.415734798f, -0.490392625f},
+      {0.461939752f, 0.191341713f, -0.191341713f, -0.461939752f, -0.461939752f, -0.191341713f, 0.191341713f, 0.461939752f},
+      {0.415734798f, -0.0975451618f, -0.490392625f, -0.277785122f, 0.277785122f, 0.490392625f, 0.0975451618f, -0.415734798f},
+      {0.353553385f, -0.353553385f, -0.353553385f, 0.353553385f, 0.353553385f, -0.353553385f, -0.353553385f, 0.353553385f},
+      {0.277785122f, -0.490392625f, 0.0975451618f, 0.415734798f, -0.415734798f, -0.0975451618f, 0.490392625f, -0.277785122f},
+      {0.191341713f, -0.461939752f, 0.461939752f, -0.191341713f, -0.191341713f, 0.461939752f, -0.461939752f, 0.191341713f},
+      {0.0975451618f, -0.277785122f, 0.415734798f, -0.490392625f, 0.490392625f, -0.415734798f, 0.277785122f, -0.0975451618f}};
+  const float x[8] = {x0, x1, x2, x3, x4, x5, x6, x7};
+  float y[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float s = (T ? C[0][j] : C[j][0]) * x[0];
+#pragma unroll
+    for (int i = 1; i < 8; ++i) s = fmaf(T ? C[i][j] : C[j][i], x[i], s);
+    y[j] = s;
+  }
+  x0 = y[0]; x1 = y[1]; x2 = y[2]; x3 = y[3]; x4 = y[4]; x5 = y[5]; x6 = y[6]; x7 = y[7];
+}
+
+// The integer forward of one intra block, as codec_block<false> runs it, for the backward: `rec` (8-byte aligned rows `pitch` bytes
+// apart) is replaced by its reconstruction in place.  Left for codec_grad_block: rem, per coefficient f - lev * 8 Q with lev signed
+// (in [-4 Q, 4 Q], |.| <= 1020: two int16 to a register), and keep, bit 8 r + c set where the reconstruction of pixel (r, c) BEFORE its
+// clamp lies in 0..255.
+__device__ __forceinline__ void codec_grad_block_forward(uint8_t* rec, int pitch, const int* qt, const float* rq, unsigned (&rem)[32],
+                                                         unsigned long long& keep) {
+  auto byte = [](unsigned x, int k) { return (int)((x >> (8 * k)) & 255u); };
+  int v[64];
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    const uint2 w = *(const uint2*)(rec + r * pitch);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[r * 8 + k] = byte(w.x, k) - 128;
+      v[r * 8 + 4 + k] = byte(w.y, k) - 128;
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) fdct8<true, 11>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) fdct8<false, 15>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+#pragma unroll
+  for (int k = 0; k < 64; ++k) {
+    const int Q = qt[k], d = Q << 3, f = v[k];
+    const int n = abs(f) + (d >> 1);
+    int lev = (int)((float)n * rq[k]);                 // within 1 of n / d
+    const int over = n - lev * d;
+    lev += over >= d ? 1 : (over < 0 ? -1 : 0);        // the exact quotient
+    const int sl = f < 0 ? -lev : lev;
+    const unsigned rm = (unsigned)(f - sl * d) & 0xffffu;
+    if (k & 1) rem[k >> 1] |= rm << 16;
+    else rem[k >> 1] = rm;
+    v[k] = sl * Q;
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) idct8<11>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+  keep = 0ull;
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    idct8<18>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+    uint2 w = {0u, 0u};
+    unsigned bits = 0u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int o = v[r * 8 + k] + 128;
+      bits |= ((unsigned)o <= 255u ? 1u : 0u) << k;
+      if (k < 4) w.x |= (unsigned)clamp255(o) << (8 * k);
+      else w.y |= (unsigned)clamp255(o) << (8 * (k - 4));
+    }
+    keep |= (unsigned long long)bits << (8 * r);
+    *(uint2*)(rec + r * pitch) = w;
+  }
+}
+
+// The backward of one intra block, in place on its 64 gradients g (block-major, 16-byte aligned): plane mask, G = C g C^T, times the
+// quantiser's factor d (1, or 3 r^2 with r = rem / (8 Q): rq holds the reciprocals), C^T G C.  The unit a reverse walk of a GOP calls.
+__device__ __forceinline__ void codec_grad_block(float* g, const unsigned (&rem)[32], unsigned long long keep, const float* rq, bool cubic) {
+  float v[64];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const float4 w = *(const float4*)(g + 4 * k);
+    v[4 * k] = (keep >> (4 * k)) & 1ull ? w.x : 0.f;
+    v[4 * k + 1] = (keep >> (4 * k + 1)) & 1ull ? w.y : 0.f;
+    v[4 * k + 2] = (keep >> (4 * k + 2)) & 1ull ? w.z : 0.f;
+    v[4 * k + 3] = (keep >> (4 * k + 3)) & 1ull ? w.w : 0.f;
+  }
+#pragma unroll
+  for (int r = 0; r < 8; ++r) dct8f<false>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) dct8f<false>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+  if (cubic) {
+#pragma unroll
+    for (int k = 0; k < 64; ++k) {
+      const int rm = (int)(short)(k & 1 ? rem[k >> 1] >> 16 : rem[k >> 1] & 0xffffu);
+      const float r = (float)rm * rq[k];
+      v[k] *= 3.f * (r * r);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 8; ++c) dct8f<true>(v[c], v[8 + c], v[16 + c], v[24 + c], v[32 + c], v[40 + c], v[48 + c], v[56 + c]);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) dct8f<true>(v[r * 8], v[r * 8 + 1], v[r * 8 + 2], v[r * 8 + 3], v[r * 8 + 4], v[r * 8 + 5], v[r * 8 + 6], v[r * 8 + 7]);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) *(float4*)(g + 4 * k) = make_float4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
+}
+
+// pixel (r, col) of a block-major gradient plane of `bw` blocks to the row
+__device__ __forceinline__ int grad_at(int r, int col, int bw) { return ((r >> 3) * bw + (col >> 3)) * kGB + (r & 7) * 8 + (col & 7); }
+
+// the derivatives of the two colour transforms: the integer constants over 2^16
+constexpr float kCs = 1.0f / 65536.0f;
+constexpr float kDecRCr = 91881 * kCs, kDecGCb = -22554 * kCs, kDecGCr = -46802 * kCs, kDecBCb = 116130 * kCs;
+constexpr float kEncYR = 19595 * kCs, kEncYG = 38470 * kCs, kEncYB = 7471 * kCs;
+constexpr float kEncCbR = -11059 * kCs, kEncCbG = -21709 * kCs, kEncCbB = 32768 * kCs;
+constexpr float kEncCrR = 32768 * kCs, kEncCrG = -27439 * kCs, kEncCrB = -5329 * kCs;
+
+template <bool S420>
+struct CodecGradLds {                          // byte offsets into the dynamic LDS of codec_grad_kernel
+  using G = CodecGeo<S420>;
+  static constexpr int NBY = (G::TH / 8) * (kTW / 8), NBC = (G::CH / 8) * (G::CW / 8);
+  static constexpr int stage = 0;
+  static constexpr int Yp = stage + G::TH * kSW * 4;
+  static constexpr int Cbp = Yp + G::TH * kTW;
+  static constexpr int Crp = Cbp + G::CH * G::CW;
+  static constexpr int gY = Crp + G::CH * G::CW;
+  static constexpr int gCb = gY + NBY * kGB * 4;
+  static constexpr int gCr = gCb + NBC * kGB * 4;
+  static constexpr int slope = gCr + NBC * kGB * 4;
+  static constexpr int tone = slope + 768 * 4;
+  static constexpr int mis = tone + 768;
+  static constexpr int qt = mis + G::TH * 4;
+  static constexpr int rq = qt + 128 * 4;
+  static constexpr int wsum = rq + 128 * 4;
+  static constexpr int bytes = wsum + 16 * 4;
+  static_assert(NBY + 2 * NBC == kCodecThreads, "one block per thread: its remainders and mask stay in registers across the barriers");
+  static_assert(Yp % 16 == 0 && Cbp % 8 == 0 && Crp % 8 == 0 && gY % 16 == 0 && gCb % 16 == 0 && gCr % 16 == 0 && slope % 4 == 0 && mis % 4 == 0,
+                "alignment of the LDS arrays");
+  static_assert(bytes <= 160 * 1024, "the LDS of a CU");
+};
+
+template <bool S420>
+__global__ __launch_bounds__(kCodecThreads) void codec_grad_kernel(const CodecGradLaunch p) {
+  using G = CodecGeo<S420>;
+  using L = CodecGradLds<S420>;
+  constexpr int CW = G::CW, NBY = L::NBY, NBC = L::NBC;
+  extern __shared__ __attribute__((aligned(16))) char codec_grad_lds[];
+  unsigned* stage = (unsigned*)(codec_grad_lds + L::stage);
+  uint8_t* Yp = (uint8_t*)(codec_grad_lds + L::Yp);
+  uint8_t* Cbp = (uint8_t*)(codec_grad_lds + L::Cbp);
+  uint8_t* Crp = (uint8_t*)(codec_grad_lds + L::Crp);
+  float* gY = (float*)(codec_grad_lds + L::gY);
+  float* gCb = (float*)(codec_grad_lds + L::gCb);
+  float* gCr = (float*)(codec_grad_lds + L::gCr);
+  float* slope_lds = (float*)(codec_grad_lds + L::slope);
+  uint8_t* tone_lds = (uint8_t*)(codec_grad_lds + L::tone);
+  int* mis_of = (int*)(codec_grad_lds + L::mis);
+  int (*qt)[64] = (int (*)[64])(codec_grad_lds + L::qt);
+  float (*rq)[64] = (float (*)[64])(codec_grad_lds + L::rq);
+  float* wsum = (float*)(codec_grad_lds + L::wsum);
+
+  const CodecClipDev& c = p.clip[blockIdx.z];
+  CodecTile g;
+  if (!codec_tile<S420>(c.Hs, c.Ws, c.ntx, blockIdx.x, g)) return;         // uniform over the workgroup
+  const int t = blockIdx.y, tid = threadIdx.x;
+  const size_t kt = (size_t)blockIdx.z * gridDim.y + t;
+  const int fsrc = p.idx ? min(max(p.idx[kt], 0), c.count - 1) : min(t, c.count - 1);
+  const CodecPlanes set = {Yp, Cbp, Crp};
+  const int cprow = S420 ? g.prow >> 1 : g.prow, cpcol = S420 ? g.pcol >> 1 : g.pcol;
+
+  // A
+  load_quant(p.q, qt, rq);
+  load_tone(p.tone, kt, tone_lds);
+  for (int k = tid; k < 768; k += kCodecThreads) slope_lds[k] = p.slope[kt * 768 + k];
+  stage_rows(c.src + (long long)fsrc * c.pitch_t, c.pitch_h, g, stage, mis_of);
+  __syncthreads();
+  // B
+  build_planes<S420>(stage, mis_of, tone_lds, p.tone != nullptr, g, set);
+  __syncthreads();
+
+  // C1: this thread's block (walk_blocks' numbering: luma, then Cb, then Cr); one outside the padded image is not computed
+  unsigned rem[32];
+  unsigned long long keep = 0ull;
+  float* gblk;
+  bool live;
+  int tab;
+  {
+    uint8_t* blk;
+    int pitch;
+    if (tid < NBY) {
+      const int by = tid / (kTW / 8), bx = tid - by * (kTW / 8);
+      blk = Yp + by * 8 * kTW + bx * 8; pitch = kTW; tab = 0;
+      gblk = gY + tid * kGB;
+      live = by * 8 < g.prow && bx * 8 < g.pcol;
+    } else {
+      const int b2 = tid - NBY, pl = b2 / NBC, b3 = b2 - pl * NBC;
+      const int by = b3 / (CW / 8), bx = b3 - by * (CW / 8);
+      blk = (pl ? Crp : Cbp) + by * 8 * CW + bx * 8; pitch = CW; tab = 1;
+      gblk = (pl ? gCr : gCb) + b3 * kGB;
+      live = by * 8 < cprow && bx * 8 < cpcol;
+    }
+#pragma unroll
+    for (int k = 0; k < 32; ++k) rem[k] = 0u;
+    if (live) codec_grad_block_forward(blk, pitch, qt[tab], rq[tab], rem, keep);
+  }
+  __syncthreads();
+
+  // D1: g_out through the RGB mask and M_dec^T into the gradient planes; a padded pixel has no output, hence no gradient
+  {
+    const float* gframe = (const float*)c.dst + (long long)t * c.dpitch_t;
+    auto pixel = [&](int r, int col, float& gy, float& gcb, float& gcr) {
+      gy = gcb = gcr = 0.f;
+      if (r < g.nrows && col < g.ncols) {
+        const int Y = Yp[r * kTW + col];
+        const int ci = S420 ? (r >> 1) * CW + (col >> 1) : r * CW + col;
+        const int cb = (int)Cbp[ci] - 128, cr = (int)Crp[ci] - 128;
+        const int R = Y + ((91881 * cr + 32768) >> 16), Gn = Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), B = Y + ((116130 * cb + 32768) >> 16);
+        const float* go = gframe + (long long)(g.y0 + r) * c.dpitch_h + (long long)(g.x0 + col) * 3;
+        const float gr = (unsigned)R <= 255u ? go[0] : 0.f, gg = (unsigned)Gn <= 255u ? go[1] : 0.f, gb = (unsigned)B <= 255u ? go[2] : 0.f;
+        gy = (gr + gg) + gb;
+        gcb = fmaf(kDecBCb, gb, kDecGCb * gg);
+        gcr = fmaf(kDecGCr, gg, kDecRCr * gr);
+      }
+    };
+    if constexpr (S420) {
+      const int qc = g.pcol >> 1;
+      for (int k = tid; k < (g.prow >> 1) * qc; k += kCodecThreads) {
+        const int r2 = k / qc, c2 = k - r2 * qc;
+        float sb = 0.f, sr = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float gy, gcb, gcr;
+          pixel(2 * r2 + (j >> 1), 2 * c2 + (j & 1), gy, gcb, gcr);
+          gY[grad_at(2 * r2 + (j >> 1), 2 * c2 + (j & 1), kTW / 8)] = gy;
+          sb += gcb; sr += gcr;
+        }
+        gCb[grad_at(r2, c2, CW / 8)] = sb;
+        gCr[grad_at(r2, c2, CW / 8)] = sr;
+      }
+    } else {
+      for (int k = tid; k < g.prow * g.pcol; k += kCodecThreads) {
+        const int r = k / g.pcol, col = k - r * g.pcol;
+        float gy, gcb, gcr;
+        pixel(r, col, gy, gcb, gcr);
+        const int o = grad_at(r, col, kTW / 8);
+        gY[o] = gy; gCb[o] = gcb; gCr[o] = gcr;
+      }
+    }
+  }
+  __syncthreads();
+
+  // C2
+  if (live) codec_grad_block(gblk, rem, keep, rq[tab], p.mode == FLK_CODEC_GRAD_CUBIC);
+  __syncthreads();
+
+  // E: spread, fold, M_enc^T, the slope of the source byte
+  float acc[3] = {0.f, 0.f, 0.f};
+  {
+    const uint8_t* sb = (const uint8_t*)stage;
+    float* iframe = p.g_in ? p.g_in + (((const float*)c.dst - p.g_out) + (long long)t * c.dpitch_t) : nullptr;
+    for (int k = tid; k < g.nrows * g.ncols; k += kCodecThreads) {
+      const int r = k / g.ncols, col = k - r * g.ncols;
+      const int r1 = r == g.nrows - 1 ? g.prow : r + 1, c1 = col == g.ncols - 1 ? g.pcol : col + 1;     // the last row / column takes the padding's
+      float gy = 0.f, gcb = 0.f, gcr = 0.f;
+      for (int rr = r; rr < r1; ++rr)
+        for (int cc = col; cc < c1; ++cc) {
+          gy += gY[grad_at(rr, cc, kTW / 8)];
+          const int o = S420 ? grad_at(rr >> 1, cc >> 1, CW / 8) : grad_at(rr, cc, CW / 8);
+          gcb += S420 ? 0.25f * gCb[o] : gCb[o];
+          gcr += S420 ? 0.25f * gCr[o] : gCr[o];
+        }
+      float gi[3];
+      gi[0] = fmaf(kEncCrR, gcr, fmaf(kEncCbR, gcb, kEncYR * gy));
+      gi[1] = fmaf(kEncCrG, gcr, fmaf(kEncCbG, gcb, kEncYG * gy));
+      gi[2] = fmaf(kEncCrB, gcr, fmaf(kEncCbB, gcb, kEncYB * gy));
+      const uint8_t* px = sb + r * (kSW * 4) + mis_of[r] + col * 3;
+      float* io = iframe ? iframe + (long long)(g.y0 + r) * c.dpitch_h + (long long)(g.x0 + col) * 3 : nullptr;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        if (io) io[ch] = gi[ch];
+        acc[ch] = fmaf(gi[ch], slope_lds[px[ch] * 3 + ch], acc[ch]);
+      }
+    }
+  }
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    float v = acc[ch];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((tid & 63) == 0) wsum[(tid >> 6) * 3 + ch] = v;
+  }
+  __syncthreads();
+  if (tid < 3) {
+    float s = 0.f;
+#pragma unroll
+    for (int w = 0; w < kCodecThreads / 64; ++w) s += wsum[w * 3 + tid];
+    p.partials[(kt * p.max_tiles + blockIdx.x) * 3 + tid] = s;
+  }
+}
+
+// one thread per (clip, frame, channel): the frame's tiles ascending from +0, then the finishing factor
+__global__ __launch_bounds__(256) void codec_grad_finish(const CodecGradLaunch p, const float* scale, int T_out, int n3, bool s420, float* gdelta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n3) return;
+  const int kt = i / 3, ch = i - kt * 3;
+  const CodecClipDev& c = p.clip[kt / T_out];
+  const int M = s420 ? 16 : 8, TH = s420 ? 64 : 32;
+  const int ntiles = c.ntx * (((c.Hs + M - 1) / M * M + TH - 1) / TH);
+  float s = 0.f;
+  for (int b = 0; b < ntiles; ++b) s += p.partials[((size_t)kt * p.max_tiles + b) * 3 + ch];
+  const float sc = scale[i];
+  gdelta[i] = sc == 0.f ? 0.f : s * sc;
+}
+
+}  // namespace
+
+// the tiles of the largest frame of a call: what partials holds per (clip, frame); 0 where the arguments are not a launch's
+long long flk_codec_grad_tiles_host(const flk_codec_args* a) {
+  if (!a || !a->clips || a->nclip < 1 || (a->subsampling != FLK_CODEC_420 && a->subsampling != FLK_CODEC_444)) return 0;
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  long long max_tiles = 0;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& s = a->clips[i];
+    if (s.Hs < 1 || s.Ws < 1) return 0;
+    const long long ntx = (padded(s.Ws, s420) + kTW - 1) / kTW, TH = s420 ? 64 : 32;
+    max_tiles = max_of(max_tiles, ntx * ((padded(s.Hs, s420) + TH - 1) / TH));
+  }
+  return max_tiles;
+}
+
+// arguments already validated (api.cpp: flk_codec_grad); everything here up to the first launch is host arithmetic.  Clip k's images
+// lie in g_out (and g_in) behind those of the clips before it, [T_out][Hs][Ws][3] fp32 each
+int flk_codec_grad_launch(const flk_codec_args* a, const int32_t* frame_idx, int T_out, const uint8_t* tone, int mode, const float* g_out,
+                          const float* slope, const float* scale, float* gdelta, float* g_in, float* partials, hipStream_t stream) {
+  CodecGradLaunch p;
+  const bool s420 = a->subsampling == FLK_CODEC_420;
+  p.idx = frame_idx; p.tone = tone; p.slope = slope; p.partials = partials; p.g_out = g_out; p.g_in = g_in; p.mode = mode;
+  fill_quant(a->quality, p.q);
+  long long max_tiles = 1, off = 0;
+  for (int i = 0; i < a->nclip; ++i) {
+    const flk_codec_clip& s = a->clips[i];
+    max_tiles = max_of(max_tiles, fill_clip(p.clip[i], s, 0, s.T, s420));
+    p.clip[i].dst = (uint8_t*)(g_out + off);
+    p.clip[i].dpitch_h = s.Ws * 3;
+    p.clip[i].dpitch_t = (long long)s.Hs * s.Ws * 3;
+    off += (long long)T_out * s.Hs * s.Ws * 3;
+  }
+  FLK_REQUIRE(max_tiles <= 0x7fffffffLL, "flk_codec_grad: a frame of more than 2^31 tiles");
+  p.max_tiles = (int)max_tiles;
+  const dim3 grid((unsigned)max_tiles, (unsigned)T_out, (unsigned)a->nclip);
+  if (s420) {
+    static bool done[FLK_MAX_DEVICES];
+    if (int rc = flk_raise_lds_limit((const void*)codec_grad_kernel<true>, CodecGradLds<true>::bytes, done)) return rc;
+    FLK_LAUNCH_KERNEL(codec_grad_kernel<true>, grid, dim3(kCodecThreads), CodecGradLds<true>::bytes, stream, p);
+  } else {
+    static bool done[FLK_MAX_DEVICES];
+    if (int rc = flk_raise_lds_limit((const void*)codec_grad_kernel<false>, CodecGradLds<false>::bytes, done)) return rc;
+    FLK_LAUNCH_KERNEL(codec_grad_kernel<false>, grid, dim3(kCodecThreads), CodecGradLds<false>::bytes, stream, p);
+  }
+  const int n3 = a->nclip * T_out * 3;
+  FLK_LAUNCH_KERNEL(codec_grad_finish, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, stream, p, scale, T_out, n3, s420, gdelta);
+  FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }

@@ -759,3 +759,83 @@ int flk_clip_prepare_grad_launch(const flk_prepare_args* a, const flk_prep_box* 
   FLK_CHECK_HIP(hipGetLastError());
   return FLK_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// The transpose of the resampling on images (flk_clip_prepare_grad_image): the gradient with respect to every SOURCE pixel.  The
+// resampling is separable, out = A_h V A_w^T, A = S2 S1 per axis; the host (videoresnet_spec.prepare_adjoint_tables) builds both
+// composite matrices per clip from the forward's own indices and lambdas and stores them by source index as (first_out, count, w[K])
+// -- the outputs that read one source index are a contiguous range.
+//   g_src[k][t][y][x][c] = sum over a, b of wh[y][a] * ww[x][b] * g(first_h[y] + a, first_w[x] + b, c)
+// Order (fixed; no atomics; independent of the grid and of the other clips): b inner, a outer, both ascending from +0 -- a row sum is
+// the chain fma(ww[b], g, .), the pixel the chain fma(wh[a], row, .).  A source pixel no output reads gets +0.
+// Layout: workgroup = (256 consecutive pixels of one source row, frame, clip); a thread owns one pixel, its three channels.  The
+// row's table entry is uniform over the workgroup; the ranges are clamped into the output image before they address g.
+namespace {
+
+struct PrepGradImageClipDev {  // 48 bytes
+  float* dst;
+  long long pitch_t, pitch_h;  // floats
+  int Hs, Ws;
+  long long tab_h, tab_w;      // words
+};
+struct PrepGradImageLaunch {
+  const int* tables;
+  const void* gx;              // device [nclip][T_out][Ho/2][Wo/2][16], fp32 or bf16
+  int Ho, Wo, K, pad_;
+  PrepGradImageClipDev clip[FLK_PREP_MAX_CLIPS];
+};
+static_assert(sizeof(PrepGradImageLaunch) <= 4096, "the launch descriptor must fit the kernel-argument segment");
+
+template <typename TI>
+__global__ __launch_bounds__(256) void clip_prepare_grad_image_kernel(const PrepGradImageLaunch p) {
+  const PrepGradImageClipDev& c = p.clip[blockIdx.z];
+  const int nxb = (c.Ws + 255) >> 8;
+  const int y = blockIdx.x / nxb, x = (int)(blockIdx.x - y * nxb) * 256 + (int)threadIdx.x;
+  if (y >= c.Hs || x >= c.Ws) return;                     // a clip smaller than the largest of the launch
+  const int t = blockIdx.y, E = 2 + p.K;
+  const size_t kt = (size_t)blockIdx.z * gridDim.y + t;
+  const int* eh = p.tables + c.tab_h + (long long)y * E;
+  const int* ew = p.tables + c.tab_w + (long long)x * E;
+  const int oh0 = min(max(eh[0], 0), p.Ho), nh = min(max(eh[1], 0), min(p.K, p.Ho - oh0));
+  const int ow0 = min(max(ew[0], 0), p.Wo), nw = min(max(ew[1], 0), min(p.K, p.Wo - ow0));
+  float acc[3] = {0.f, 0.f, 0.f};
+  for (int a = 0; a < nh; ++a) {
+    const int oh = oh0 + a;
+    float row[3] = {0.f, 0.f, 0.f};
+    for (int b = 0; b < nw; ++b) {
+      const int ow = ow0 + b;
+      const float w = __int_as_float(ew[2 + b]);
+      const size_t gi = (((kt * (p.Ho >> 1) + (oh >> 1)) * (p.Wo >> 1) + (ow >> 1)) << 4) + ((oh & 1) * 2 + (ow & 1)) * 3;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) row[ch] = fmaf(w, prep_grad_load<TI>(p.gx, gi + ch), row[ch]);
+    }
+    const float w = __int_as_float(eh[2 + a]);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) acc[ch] = fmaf(w, row[ch], acc[ch]);
+  }
+  float* o = c.dst + (long long)t * c.pitch_t + (long long)y * c.pitch_h + (long long)x * 3;
+  o[0] = acc[0]; o[1] = acc[1]; o[2] = acc[2];
+}
+
+}  // namespace
+
+// arguments already validated (api.cpp: flk_clip_prepare_grad_image); everything here up to the launch is host arithmetic
+int flk_clip_prepare_grad_image_launch(int nclip, const flk_grad_image_clip* clips, int T_out, int Ho, int Wo, int K, const int32_t* tables,
+                                       const void* gx_s2d, int dtype, hipStream_t stream) {
+  PrepGradImageLaunch p;
+  p.tables = tables; p.gx = gx_s2d; p.Ho = Ho; p.Wo = Wo; p.K = K; p.pad_ = 0;
+  long long blocks = 1;
+  for (int i = 0; i < nclip; ++i) {
+    const flk_grad_image_clip& s = clips[i];
+    PrepGradImageClipDev& d = p.clip[i];
+    d.dst = s.dst; d.pitch_t = s.pitch_t; d.pitch_h = s.pitch_h; d.Hs = s.Hs; d.Ws = s.Ws; d.tab_h = s.tab_h; d.tab_w = s.tab_w;
+    const long long n = (long long)s.Hs * ((s.Ws + 255) / 256);
+    if (n > blocks) blocks = n;
+  }
+  FLK_REQUIRE(blocks <= 0x7fffffffLL, "flk_clip_prepare_grad_image: a frame of more than 2^31 row segments");
+  const dim3 grid((unsigned)blocks, (unsigned)T_out, (unsigned)nclip);
+  if (dtype == FLK_BF16) FLK_LAUNCH_KERNEL(clip_prepare_grad_image_kernel<bf16_t>, grid, dim3(256), 0, stream, p);
+  else FLK_LAUNCH_KERNEL(clip_prepare_grad_image_kernel<float>, grid, dim3(256), 0, stream, p);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}

@@ -1371,6 +1371,160 @@ def codec_roundtrip(videos, codec, frame_idx=None, tone=None, out=None, stats=Fa
     return (outs, st_out) if stats else outs
 
 
+def _packed_images(what, name, t, shapes, dev):
+    """the packed fp32 gradient images of a call as ONE flat tensor and its per-clip views: ``t`` is that flat tensor, or the list of
+    ``[T_out,H_k,W_k,3]`` tensors -- taken in place when they lie one after the other in memory (views of one buffer), copied into
+    one buffer otherwise"""
+    sizes = [int(np.prod(s)) for s in shapes]
+    ends = np.cumsum(sizes)
+    if isinstance(t, (list, tuple)):
+        if len(t) != len(shapes) or any(not torch.is_tensor(v) or v.dtype != torch.float32 or tuple(v.shape) != tuple(s) or v.device != dev
+                                        for v, s in zip(t, shapes)):
+            raise ValueError(f"{what}: {name} must be a list of fp32 tensors {[list(s) for s in shapes][:4]}.. on {dev}")
+        packed = all(v.is_contiguous() and v.data_ptr() == t[0].data_ptr() + 4 * (e - n) for v, n, e in zip(t, sizes, ends))
+        if packed:                              # one flat tensor over the same memory
+            t = torch.as_strided(t[0], (int(ends[-1]),), (1,))
+        else:
+            t = torch.cat([v.reshape(-1) for v in t])
+    if not (torch.is_tensor(t) and t.dtype == torch.float32 and t.dim() == 1 and t.is_contiguous() and t.device == dev and t.numel() >= ends[-1]):
+        raise ValueError(f"{what}: {name} must be a contiguous fp32 tensor of {int(ends[-1])} elements on {dev} (the clips' images packed one "
+                         f"after the other), or the list of them")
+    return t, [t[e - n:e].view(*s) for s, n, e in zip(shapes, sizes, ends)]
+
+
+def prepare_clips_grad_image(frames, gx_s2d, im_scale=128, input_size=112, rule="sizes", boxes=None, flips=None, frame_idx=None, out=None):
+    """The transpose of the resampling on images (flk_clip_prepare_grad_image): the gradient with respect to every SOURCE pixel of the
+    frames the clips were prepared from -- a list of fp32 ``[T_out,H_k,W_k,3]``.  ``frames`` (a list of videos ``[N_k,H_k,W_k,3]``, of
+    which the resolutions are read), ``im_scale`` / ``input_size`` / ``rule``, ``boxes`` / ``flips`` and ``frame_idx`` (required: it
+    gives T_out; output frame t has its own image whatever source frame it names) as the ``prepare_clips`` call whose clips went into
+    the network; ``gx_s2d`` as ``prepare_clips_grad`` takes it.  ``out``: the list of images to write, which may be views with row and
+    frame pitches (in whole floats) of their own.  The composite matrices come from ``videoresnet_spec.prepare_adjoint_tables``, one
+    upload per call.  One fixed summation order: repeats are bitwise equal and a clip's images are those of a call with it alone."""
+    from .videoresnet_spec import prepare_adjoint_tables
+    what = "prepare_clips_grad_image"
+    if frame_idx is None:
+        raise ValueError(f"{what}: frame_idx is required (the clips are cut from whole videos)")
+    if not torch.is_tensor(gx_s2d) or not gx_s2d.is_cuda:
+        raise ValueError(f"{what}: gx_s2d must be a CUDA tensor")
+    if not isinstance(frames, (list, tuple)) or not frames or any(not torch.is_tensor(v) or v.dim() != 4 or v.shape[-1] != 3 for v in frames):
+        raise ValueError(f"{what}: frames must be a non-empty list of videos [N,H,W,3]")
+    dev, n = gx_s2d.device, len(frames)
+    Ho, Wo = (int(input_size), int(input_size)) if np.isscalar(input_size) else (int(input_size[0]), int(input_size[1]))
+    if Ho % 2 or Wo % 2:
+        raise ValueError(f"{what}: the output size must be even (the folded gradient layout), got {Ho} x {Wo}")
+    rows = np.asarray(frame_idx.numpy() if torch.is_tensor(frame_idx) else frame_idx)
+    if rows.ndim != 2 or rows.shape[0] != n or not 1 <= rows.shape[1] <= 65535:
+        raise ValueError(f"{what}: frame_idx must hold {n} equally long rows of 1..65535 integers, got {rows.shape}")
+    T_out = rows.shape[1]
+    if gx_s2d.dtype not in (torch.float32, torch.bfloat16) or tuple(gx_s2d.shape) != (n, T_out, Ho // 2, Wo // 2, 16) or not gx_s2d.is_contiguous():
+        raise ValueError(f"{what}: gx_s2d must be a contiguous fp32 or bf16 tensor [{n},{T_out},{Ho // 2},{Wo // 2},16], got "
+                         f"{tuple(gx_s2d.shape)} {gx_s2d.dtype}")
+    sizes = [(int(v.shape[1]), int(v.shape[2])) for v in frames]
+    if out is None:
+        out = [torch.empty((T_out, h, w, 3), dtype=torch.float32, device=dev) for h, w in sizes]
+    out = list(out)
+    for k, (o, (h, w)) in enumerate(zip(out, sizes)):
+        if (len(out) != n or not torch.is_tensor(o) or o.dtype != torch.float32 or tuple(o.shape) != (T_out, h, w, 3) or o.device != dev or o.stride(3) != 1
+                or o.stride(2) != 3 or o.stride(1) < 3 * w or (T_out > 1 and o.stride(0) < o.stride(1) * (h - 1) + 3 * w)):
+            raise ValueError(f"{what}: out[{k}] must be an fp32 tensor {[T_out, h, w, 3]} on {dev} with adjacent channels and pixels, rows and "
+                             f"frames not overlapping")
+    for first in range(0, n, FLK_PREP_MAX_CLIPS):
+        part = range(first, min(first + FLK_PREP_MAX_CLIPS, n))
+        words, offsets, K = prepare_adjoint_tables([sizes[k] for k in part], None if boxes is None else [boxes[k] for k in part],
+                                                   None if flips is None else [flips[k] for k in part], im_scale, (Ho, Wo), rule)
+        tab = torch.from_numpy(words).to(dev)
+        arr = (_lib.GradImageClip * len(part))()
+        for d, k, (th, tw) in zip(arr, part, offsets):
+            o = out[k]
+            d.dst, d.pitch_t, d.pitch_h = o.data_ptr(), max(int(o.stride(0)), 1), int(o.stride(1))
+            d.Hs, d.Ws, d.tab_h, d.tab_w = sizes[k][0], sizes[k][1], th, tw
+        check(load().flk_clip_prepare_grad_image(len(part), arr, T_out, Ho, Wo, K, ptr(tab), tab.numel(), ptr(gx_s2d[first:]),
+                                                 dtype_code(gx_s2d.dtype), stream_ptr()))
+    return out
+
+
+CODEC_GRAD_MODES = {"ste": _lib.FLK_CODEC_GRAD_STE, "cubic": _lib.FLK_CODEC_GRAD_CUBIC}
+
+
+def codec_grad(videos, codec, g_out, slope, scale, mode, frame_idx=None, tone=None, gdelta=None, g_in=None, scratch=None):
+    """The backward of the intra codec (flk_codec_grad; ``videoresnet_spec.codec_grad_host`` is its definition): fp32 ``[n,T_out,3]``,
+    d(loss)/d(delta_clip) through the surrogate of ``codec_roundtrip(videos, codec, frame_idx=, tone=)``.  ``videos``, ``codec`` (gop 1),
+    ``frame_idx`` and ``tone`` as that call took them; ``g_out``: d(loss)/d(decoded frames), the list of fp32 ``[T_out,H_k,W_k,3]``
+    (``prepare_clips_grad_image`` writes it) or one flat fp32 tensor holding them one after the other; ``slope`` / ``scale`` from
+    ``flicker_tone_slopes``; ``mode``: "ste" or "cubic".  ``g_in``: True, or a flat fp32 buffer: also return, second, the list of
+    gradients with respect to the codec's input frames.  ``scratch``: fp32, flk_codec_grad_scratch_bytes / 4 elements per launch.
+    One launch pair per ``FLK_PREP_MAX_CLIPS`` videos; one fixed summation order."""
+    from .videoresnet_spec import Codec
+    what = "codec_grad"
+    if not isinstance(codec, Codec) or codec.gop != 1:
+        raise ValueError(f"{what}: codec must be an intra-frame videoresnet_spec.Codec (gop 1), got {codec!r}")
+    if mode not in CODEC_GRAD_MODES:
+        raise ValueError(f"{what}: mode must be one of {tuple(CODEC_GRAD_MODES)}, got {mode!r}")
+    if not isinstance(videos, (list, tuple)) or not videos:
+        raise ValueError(f"{what}: videos must be a non-empty list of CUDA uint8 tensors [N,H,W,3]")
+    vids = []
+    for k, v in enumerate(videos):
+        if not torch.is_tensor(v) or not v.is_cuda or v.dtype != torch.uint8 or v.dim() != 4 or v.shape[-1] != 3 or min(v.shape) < 1:
+            desc = f"{tuple(v.shape)} {v.dtype} {v.device}" if torch.is_tensor(v) else type(v).__name__
+            raise ValueError(f"{what}: video {k} must be a CUDA uint8 tensor [N,H,W,3], got {desc}")
+        if v.stride(-1) != 1 or v.stride(-2) != 3 or v.stride(-3) < 3 * v.shape[2] or (v.shape[0] > 1 and v.stride(0) <= 0):
+            v = v.contiguous()
+        vids.append(v)
+    n, dev = len(vids), vids[0].device
+    table = None
+    if frame_idx is not None:
+        table = np.asarray(frame_idx.numpy() if torch.is_tensor(frame_idx) else frame_idx)
+        if table.ndim != 2 or table.shape[0] != n or table.dtype.kind not in "iu" or not 1 <= table.shape[1] <= 65535:
+            raise ValueError(f"{what}: frame_idx must hold {n} equally long rows of 1..65535 integers")
+        for k, v in enumerate(vids):
+            if table[k].min() < 0 or table[k].max() >= v.shape[0]:
+                raise ValueError(f"{what}: video {k}: frame_idx holds {int(table[k].min())} .. {int(table[k].max())}, the video has {v.shape[0]} frames")
+        T_out = table.shape[1]
+    else:
+        if len({int(v.shape[0]) for v in vids}) != 1 or vids[0].shape[0] > 65535:
+            raise ValueError(f"{what}: without frame_idx the videos have one length, at most 65535 frames")
+        T_out = int(vids[0].shape[0])
+    if tone is not None:
+        _check_tone(what, "tone", tone, torch.uint8, (n, T_out, 256, 3), dev)
+    _check_tone(what, "slope", slope, torch.float32, (n, T_out, 256, 3), dev)
+    _check_tone(what, "scale", scale, torch.float32, (n, T_out, 3), dev)
+    if gdelta is None:
+        gdelta = torch.empty((n, T_out, 3), dtype=torch.float32, device=dev)
+    _check_tone(what, "gdelta", gdelta, torch.float32, (n, T_out, 3), dev)
+    shapes = [(T_out, int(v.shape[1]), int(v.shape[2]), 3) for v in vids]
+    flat, _ = _packed_images(what, "g_out", g_out, shapes, dev)
+    gin_flat = gin_views = None
+    if g_in is not None and g_in is not False:
+        if g_in is True:
+            g_in = torch.empty(sum(int(np.prod(s)) for s in shapes), dtype=torch.float32, device=dev)
+        if not torch.is_tensor(g_in):
+            raise ValueError(f"{what}: g_in must be True or one flat fp32 buffer")
+        gin_flat, gin_views = _packed_images(what, "g_in", g_in, shapes, dev)
+    tab_dev = None if table is None else torch.from_numpy(table.astype(np.int32)).to(dev)
+    sub = _lib.FLK_CODEC_420 if codec.subsampling == "420" else _lib.FLK_CODEC_444
+    off = 0
+    for first in range(0, n, FLK_PREP_MAX_CLIPS):
+        part = range(first, min(first + FLK_PREP_MAX_CLIPS, n))
+        arr = (_lib.CodecClip * len(part))()
+        for d, k in zip(arr, part):
+            v = vids[k]
+            d.src, d.T, d.Hs, d.Ws = v.data_ptr(), int(v.shape[0]), int(v.shape[1]), int(v.shape[2])
+            d.pitch_t, d.pitch_h = max(int(v.stride(0)), 1), int(v.stride(1))
+        a = _lib.CodecArgs()
+        a.nclip, a.quality, a.subsampling, a.clips = len(part), codec.quality, sub, arr
+        need = int(load().flk_codec_grad_scratch_bytes(C.byref(a), T_out)) // 4
+        if need <= 0:
+            raise ValueError(f"{what}: the scratch of these videos cannot be sized")
+        ws = torch.empty(need, dtype=torch.float32, device=dev) if scratch is None else scratch
+        if not (torch.is_tensor(ws) and ws.dtype == torch.float32 and ws.is_contiguous() and ws.device == dev and ws.numel() >= need):
+            raise ValueError(f"{what}: scratch must be a contiguous fp32 tensor of at least {need} elements on {dev}")
+        check(load().flk_codec_grad(C.byref(a), None if tab_dev is None else ptr(tab_dev[first:]), T_out, None if tone is None else ptr(tone[first:]),
+                                    CODEC_GRAD_MODES[mode], C.c_void_p(flat.data_ptr() + 4 * off), ptr(slope[first:]), ptr(scale[first:]), ptr(gdelta[first:]),
+                                    None if gin_flat is None else C.c_void_p(gin_flat.data_ptr() + 4 * off), ptr(ws), stream_ptr()))
+        off += sum(int(np.prod(shapes[k])) for k in part)
+    return gdelta if gin_views is None else (gdelta, gin_views)
+
+
 def _head_check(y, wt, W, C_, coff):
     assert y.dim() == 4 and y.is_contiguous() and y.is_cuda and y.dtype in (torch.float32, torch.bfloat16)
     B, Tn, HW, ld = y.shape

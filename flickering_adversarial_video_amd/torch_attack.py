@@ -13,7 +13,7 @@ import torch
 
 from . import ops, parallel
 from ._lib import FLK_NET_MC3_18, FLK_NET_R2PLUS1D_18, FLK_NET_R2PLUS1D_34, FLK_NET_R3D_18
-from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, FLICKER_MODELS, RESIZE_RULES, CaptureChannel, Codec, check_sampling, flicker_rows, illum_tables,
+from .videoresnet_spec import (DEFAULT_MEAN, DEFAULT_STD, FLICKER_MODELS, RESIZE_RULES, CaptureChannel, Codec, check_codec_grad, check_sampling, flicker_rows, illum_tables,
                                resolve_model, sample_frame_indices, split_sampling, train_crop_params, u8_decode_table)
 
 FLICKER_TIMES = ("clip", "video")
@@ -533,7 +533,8 @@ class FlickerVideoResNet:
     def __init__(self, base_model, weights, batch_size=1, sample_length=16, image_size=112, dtype="bf16", device=0, l_inf_pert_norm=0.2,
                  cyclic_pert=False, num_classes=None, process_group=None, attack_type="flickering", per_clip=False, optimizer="adam",
                  im_scale=128, resize_rule="sizes", augment=None, sampling=None, clips_per_video=1, video_reduce="mean", quantise_train=False,
-                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False, codec=None):
+                 flicker_time="clip", flicker_period=None, capture=None, flicker_model="additive", response="srgb", train_delivered=False, codec=None,
+                 codec_grad="identity"):
         from .i3d_engine import check_optimizer
         # flicker_model "illumination": the flicker LIGHTS THE SCENE instead of being added to the displayed pixels -- a pixel of linear
         # light L becomes L * (1 + m), then goes through the camera's response and 8 bits (videoresnet_spec.illum_tables(response); the
@@ -576,6 +577,19 @@ class FlickerVideoResNet:
             raise ValueError("codec: an engine built with train_delivered=True only (the codec compresses whole delivered frames; "
                              "evaluate_videos(quantise='video', codec=) and export_video(codec=) take one on any engine)")
         self.codec = codec
+        # codec_grad: the codec's Jacobian in that backward.  "identity" (default): straight through, every launch as before.  "ste" /
+        # "cubic" (an intra-frame codec only): the input gradient goes back through the resampling to the decoded
+        # frames (ops.prepare_clips_grad_image) and through the codec's own transpose -- colour transforms, chroma subsampling, clamps,
+        # the transform pair, the quantiser straight through or by the cubic rounding surrogate -- to the tone slopes (ops.codec_grad).
+        # The forward is the same integer codec under all three
+        if codec_grad != "identity":
+            check_codec_grad(codec_grad, "codec_grad")
+            if codec is None:
+                raise ValueError(f"codec_grad={codec_grad!r} differentiates a codec: give codec=Codec(...) (and train_delivered=True)")
+            if codec.gop > 1 or codec.search > 0:
+                raise ValueError(f"codec_grad={codec_grad!r} differentiates the intra codec (gop 1, search 0); {codec!r} keeps "
+                                 "codec_grad='identity'")
+        self.codec_grad = codec_grad
         # capture (flicker_time "video"; a videoresnet_spec.CaptureChannel): the attack is trained OVER THE AIR.  Every adversarial training
         # forward (``step``) draws one capture channel per video -- sub-frame phase, exposure, colour gain -- and perturbs frame t by the mix
         # of rows a camera records (ops.flicker_rows_mix in the gather's place); the step folds its gradient through the same tables
@@ -714,8 +728,21 @@ class FlickerVideoResNet:
             clips, rows, boxes, flips = delivered
             slope, scale = self._buf("_slope", (self.B, self.T, 256, 3)), self._buf("_scale", (self.B, self.T, 3))
             ops.flicker_tone_slopes(a, pm.illum if self.illumination else None, slope, scale)
-            ops.prepare_clips_grad(clips, self._gx, slope, scale, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
-                                   boxes=boxes, flips=flips, frame_idx=rows, gdelta=self._g_clip, scratch=self._pg_scratch)
+            if self.codec_grad != "identity":
+                # through the codec: the gradient images of the decoded frames (the clips were prepared from the codec's output under
+                # the identity frame table), packed one after the other in one reused buffer, then the codec's transpose on the source
+                # frames under this step's tone tables
+                shapes = [(self.T, int(v.shape[1]), int(v.shape[2]), 3) for v in clips]
+                ends = np.cumsum([int(np.prod(s)) for s in shapes])
+                flat = self._buf("_g_img", (int(ends[-1]),))
+                images = [flat[e - int(np.prod(s)):e].view(*s) for s, e in zip(shapes, ends)]
+                ops.prepare_clips_grad_image(list(clips), self._gx, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                             boxes=boxes, flips=flips, frame_idx=np.broadcast_to(np.arange(self.T), (len(clips), self.T)), out=images)
+                ops.codec_grad(list(clips), self.codec, flat, slope, scale, self.codec_grad, frame_idx=rows, tone=self._tone[:self.B],
+                               gdelta=self._g_clip)
+            else:
+                ops.prepare_clips_grad(clips, self._gx, slope, scale, im_scale=self.im_scale, input_size=(self.H, self.W), rule=self.resize_rule,
+                                       boxes=boxes, flips=flips, frame_idx=rows, gdelta=self._g_clip, scratch=self._pg_scratch)
         # the frames of the per-clip gradient fold onto their rows -- under a channel by the transpose of the mix the forward ran, on the same tables
         if cap is None:
             return ops.flicker_rows_grad(self._g_clip, pm.rows_dev, self.P, out=out)

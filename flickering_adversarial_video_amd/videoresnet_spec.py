@@ -927,6 +927,93 @@ def prepare_grad_host(video, frame_idx, gx, slope, scale, box=None, flip=False, 
     return (g, mag, Ho * Wo) if bound else g
 
 
+def _axis_matrix(i0, i1, lam, n_in):
+    """one bilinear stage along an axis as a float64 matrix [len(i0), n_in]: row d holds float32(1 - lambda) at i0 and lambda at i1
+    (added where the two coincide), the weights ``_blend_axis`` uses"""
+    A = np.zeros((len(i0), n_in))
+    rows = np.arange(len(i0))
+    np.add.at(A, (rows, i0), (np.float32(1.0) - lam).astype(np.float32).astype(np.float64))
+    np.add.at(A, (rows, i1), lam.astype(np.float64))
+    return A
+
+
+def prepare_adjoint_matrices(Hs, Ws, box=None, flip=False, im_scale=128, input_size=112, rule="sizes"):
+    """The resampling of csrc/prepare.hip as two matrices: ``prepare_resample_host(V) = A_h V A_w^T`` per channel.  ``(A_h [Ho,Hs],
+    A_w [Wo,Ws])`` float32: per axis the composite ``S2 S1`` of the two bilinear stages (``_prep_axis`` indices and lambdas of the
+    forward; stage 2 skipped for a box of the output size, as there; the flip is the reversed row order of A_w), formed in float64
+    and rounded ONCE to float32."""
+    Hs, Ws = int(Hs), int(Ws)
+    Ho, Wo = _pair(input_size)
+    Hr, Wr, step_h, step_w, ci, cj = prepare_geometry(Hs, Ws, im_scale, input_size, rule)
+    i, j, h, w = (ci, cj, Ho, Wo) if box is None else (int(b) for b in box)
+    if h < 1 or w < 1 or i < 0 or j < 0 or i + h > Hr or j + w > Wr:
+        raise ValueError(f"prepare_adjoint_matrices: box ({i},{j})+{h}x{w} outside the resized image {Hr} x {Wr}")
+    A_h = _axis_matrix(*_prep_axis(step_h, i + np.arange(h), Hs), Hs)
+    A_w = _axis_matrix(*_prep_axis(step_w, j + np.arange(w), Ws), Ws)
+    if (h, w) != (Ho, Wo):
+        A_h = _axis_matrix(*_prep_axis(np.float32(h) / np.float32(Ho), np.arange(Ho), h), h) @ A_h
+        A_w = _axis_matrix(*_prep_axis(np.float32(w) / np.float32(Wo), np.arange(Wo), w), w) @ A_w
+    if flip:
+        A_w = A_w[::-1]
+    return np.ascontiguousarray(A_h.astype(np.float32)), np.ascontiguousarray(A_w.astype(np.float32))
+
+
+def _adjoint_ranges(A):
+    """a matrix [n_out, n_in] by SOURCE index: (first_out [n_in], count [n_in]) of the outputs with a non-zero weight -- a contiguous
+    range, both stages being monotone (zeros inside it are kept); a source index no output reads has count 0"""
+    nz = A != 0
+    any_ = nz.any(0)
+    first = np.where(any_, nz.argmax(0), 0)
+    last = np.where(any_, A.shape[0] - 1 - nz[::-1].argmax(0), -1)
+    return first.astype(np.int64), (last - first + 1).astype(np.int64)
+
+
+def prepare_adjoint_tables(sizes, boxes=None, flips=None, im_scale=128, input_size=112, rule="sizes"):
+    """The tables flk_clip_prepare_grad_image reads, for the clips of one call: ``sizes`` a list of ``(Hs, Ws)``, ``boxes`` / ``flips`` as
+    ``ops.prepare_clips`` takes them (None: the evaluation transform).  Returns ``(words, offsets, K)``: ``words`` int32, per clip its
+    row table then its column table, entry s of a table being ``2 + K`` words ``(first_out, count, w[K] as float32 bits)`` -- column s
+    of ``prepare_adjoint_matrices``' A_h or A_w over its range, zero-filled to K; ``offsets[k] = (tab_h, tab_w)`` in words; ``K`` the
+    largest count of the call."""
+    if (boxes is None) != (flips is None):
+        raise ValueError("prepare_adjoint_tables: boxes and flips go together")
+    mats = [prepare_adjoint_matrices(Hs, Ws, None if boxes is None else boxes[k], False if flips is None else bool(flips[k]), im_scale,
+                                     input_size, rule) for k, (Hs, Ws) in enumerate(sizes)]
+    ranges = [[_adjoint_ranges(A) for A in pair] for pair in mats]
+    K = max(1, max(int(cnt.max()) for pair in ranges for _, cnt in pair))
+    parts, offsets, at = [], [], 0
+    for pair, rng in zip(mats, ranges):
+        off = []
+        for A, (first, cnt) in zip(pair, rng):
+            e = np.zeros((A.shape[1], 2 + K), np.int32)
+            e[:, 0], e[:, 1] = first, cnt
+            take = np.minimum(first[:, None] + np.arange(K)[None], A.shape[0] - 1)
+            w = np.where(np.arange(K)[None] < cnt[:, None], A[take, np.arange(A.shape[1])[:, None]], np.float32(0.0)).astype(np.float32)
+            e[:, 2:] = w.view(np.int32)
+            parts.append(e.reshape(-1))
+            off.append(at)
+            at += e.size
+        offsets.append(tuple(off))
+    return np.concatenate(parts), offsets, K
+
+
+def prepare_grad_image_host(g, Hs, Ws, box=None, flip=False, im_scale=128, input_size=112, rule="sizes", bound=False):
+    """flk_clip_prepare_grad_image restated in float64 for ONE frame: ``g`` = d(loss)/d(prepared frame) ``[Ho,Wo,3]`` -> the gradient
+    with respect to the source frame ``[Hs,Ws,3]``, ``A_h^T g A_w`` with the float32 matrices of ``prepare_adjoint_matrices`` (the
+    kernel's tables).  ``bound``: also the same product on magnitudes and the number of float32 roundings of an output in the
+    kernel's order (count_h * count_w fused row terms and count_h fused column terms, at their largest)."""
+    g = np.asarray(g, dtype=np.float64)
+    Ho, Wo = _pair(input_size)
+    if g.shape != (Ho, Wo, 3):
+        raise ValueError(f"prepare_grad_image_host: g must be [{Ho},{Wo},3], got {g.shape}")
+    A_h, A_w = (A.astype(np.float64) for A in prepare_adjoint_matrices(Hs, Ws, box, flip, im_scale, input_size, rule))
+    back = lambda Ah, v, Aw: np.tensordot(np.tensordot(Ah, v, axes=(0, 0)), Aw, axes=(1, 0)).transpose(0, 2, 1)      # [Hs,Ws,3]
+    out = back(A_h, g, A_w)
+    if not bound:
+        return out
+    kh, kw = (int(_adjoint_ranges(A)[1].max()) for A in (A_h, A_w))
+    return out, back(np.abs(A_h), np.abs(g), np.abs(A_w)), kh * kw + kh
+
+
 def _capture_range(name, v, lo_bound, hi_bound):
     pair = (v, v) if np.ndim(v) == 0 else tuple(v)
     if len(pair) != 2:
@@ -1285,6 +1372,12 @@ def _idct_1d(c, shift):
 
 def _codec_plane(p, qt, dt):
     """a padded plane [N, Hp, Wp] (values 0..255, Hp and Wp multiples of 8) through DCT, quantisation and back; also the levels"""
+    return _codec_plane_parts(p, qt, dt)[:2]
+
+
+def _codec_plane_parts(p, qt, dt):
+    """``_codec_plane`` with what the codec's backward takes from the integer forward: ``(plane, levels, f, raw)`` -- f the forward
+    coefficients [N, by, bx, 8, 8] and raw the reconstruction before its clamp, as a plane"""
     N, Hp, Wp = p.shape
     b = p.reshape(N, Hp // 8, 8, Wp // 8, 8).transpose(0, 1, 3, 2, 4).astype(dt) - 128          # [N, by, bx, row, col]
     f = _fdct_1d(b, -_P1_BITS, _C_BITS - _P1_BITS)                                              # pass 1: along the rows
@@ -1294,8 +1387,9 @@ def _codec_plane(p, qt, dt):
     lev = np.where(f < 0, -mag, mag).astype(dt)
     c = lev * qt.reshape(8, 8).astype(dt)
     w = _idct_1d(c.swapaxes(-1, -2), _C_BITS - _P1_BITS).swapaxes(-1, -2)                       # pass 1: down the columns
-    o = np.clip(_idct_1d(w, _C_BITS + _P1_BITS + 3) + 128, 0, 255)                              # pass 2: along the rows
-    return o.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp), lev
+    raw = _idct_1d(w, _C_BITS + _P1_BITS + 3) + 128                                             # pass 2: along the rows
+    plane = lambda a: a.transpose(0, 1, 3, 2, 4).reshape(N, Hp, Wp)
+    return plane(np.clip(raw, 0, 255)), lev, f, plane(raw)
 
 
 def _codec_plane_inter(p, ref, qp, dt):
@@ -1474,6 +1568,155 @@ def codec_roundtrip_host(frames, quality, subsampling="420", tone=None, stats=Fa
     return res if len(res) > 1 else out
 
 
+# ----------------------------------------------------------------------------------------------------------------------------------
+# The codec's backward (csrc/codec.hip, flk_codec_grad).  The forward stays the integer codec above.  The backward
+# differentiates a SURROGATE of the intra codec (gop = 1), per frame, with constants taken from the integer forward:
+#   colour   the derivative of the fixed-point definitions: the integer constants over 2^16 (dyadic, exact in float32); rounding: 1
+#   clamps   the plane clamp after the inverse DCT and the RGB clamp pass the gradient where the UNCLAMPED integer lies in 0..255
+#   pad      padding repeats the last row and column: the transpose adds the padded pixels' gradients onto that row and column
+#   420      the box mean gives 1/4 to each of its four pixels; the replication on decode sums its four pixels
+#   DCT      the orthonormal 8 x 8 DCT-II matrix C in float32: G = C g C^T is the transpose of the inverse, C^T G C of the forward
+#            (the forward's x 8 and the quantiser's 8 Q cancel)
+#   quant    per coefficient f of level lev: r = (f - lev * 8 Q) / (8 Q) in [-1/2, 1/2] from the integers; the factor d is 1 ("ste") or
+#            3 r^2 ("cubic": Shin & Song's differentiable-JPEG rounding round(u) + (u - round(u))^3 -- 0 at a bin centre, 3/4 at an edge)
+# g_out [H,W,3] -> RGB mask, M_dec^T, chroma 2 x 2 sum, plane mask, C . C^T, x d, C^T . C, chroma 1/4 spread, padding fold, M_enc^T ->
+# g_in [H,W,3];  gdelta[t][c] = scale[t][c] * sum over pixels of g_in(p, c) * slope[t][v(p, c)][c], v the SOURCE byte before the tone.
+CODEC_GRAD_MODES = ("ste", "cubic")
+CODEC_TILE_W, CODEC_TILE_H, CODEC_THREADS = 128, {"444": 32, "420": 64}, 192      # the tiling of csrc/codec.hip (kTW, CodecGeo::TH)
+# [R, G, B] = _CODEC_DEC @ [Y, Cb - 128, Cr - 128] and [Y, Cb, Cr] = _CODEC_ENC @ [R, G, B] (+ offsets), the integer constants over 2^16
+_CODEC_DEC = np.array([[65536, 0, 91881], [65536, -22554, -46802], [65536, 116130, 0]], np.float64) / 65536.0
+_CODEC_ENC = np.array([[19595, 38470, 7471], [-11059, -21709, 32768], [32768, -27439, -5329]], np.float64) / 65536.0
+
+
+def check_codec_grad(mode, what="codec_grad"):
+    if mode not in CODEC_GRAD_MODES:
+        raise ValueError(f"{what}: the codec gradient must be one of {CODEC_GRAD_MODES}, got {mode!r}")
+    return mode
+
+
+def codec_dct_matrix():
+    """the orthonormal 8 x 8 DCT-II matrix, C[u][x] = a(u) cos((2 x + 1) u pi / 16), a(0) = sqrt(1/8), else 1/2, rounded to float32"""
+    u, x = np.mgrid[0:8, 0:8]
+    return np.where(u == 0, np.sqrt(1 / 8), 0.5 * np.cos((2 * x + 1) * u * np.pi / 16)).astype(np.float32)
+
+
+def _codec_grad_frames(what, frames, tone):
+    x = np.asarray(frames)
+    if x.dtype != np.uint8 or x.ndim != 4 or x.shape[-1] != 3 or min(x.shape) < 1:
+        raise ValueError(f"{what}: frames must be uint8 [N,H,W,3], got {x.shape} {x.dtype}")
+    if tone is not None:
+        tone = np.asarray(tone)
+        if tone.ndim == 2:
+            tone = np.broadcast_to(tone, (x.shape[0], 256, 3))
+        if tone.dtype != np.uint8 or tone.shape != (x.shape[0], 256, 3):
+            raise ValueError(f"{what}: tone must be uint8 [{x.shape[0]},256,3], got {tone.shape} {tone.dtype}")
+    return x, tone
+
+
+def codec_quant_slopes_host(frames, quality, subsampling="420", tone=None, mode="cubic"):
+    """What the codec's backward takes from the INTEGER forward of ``codec_roundtrip_host(frames, quality, subsampling, tone)``:
+    ``(d, plane_mask, rgb_mask)``.  ``d``: three float64 planes (Y, Cb, Cr; padded, chroma at its own size), the quantiser's factor of
+    coefficient (u, v) of block (by, bx) at [n, 8 by + u, 8 bx + v] -- 1 under "ste", 3 r^2 under "cubic", r = (f - lev * 8 Q) / (8 Q)
+    formed from the integers.  ``plane_mask``: three bool planes, True where the reconstruction before its clamp lies in 0..255.
+    ``rgb_mask``: bool [N,H,W,3], True where the decoded channel before its clamp lies in 0..255."""
+    quality, subsampling = check_codec(quality, subsampling, "codec_quant_slopes_host")
+    check_codec_grad(mode, "codec_quant_slopes_host")
+    x, tone = _codec_grad_frames("codec_quant_slopes_host", frames, tone)
+    N, H, W, _ = x.shape
+    if tone is not None:
+        x = np.stack([np.stack([tone[n, :, c][x[n, :, :, c]] for c in range(3)], -1) for n in range(N)])
+    dt = np.int64
+    m = 8 if subsampling == "444" else 16
+    Hp, Wp = (H + m - 1) // m * m, (W + m - 1) // m * m
+    x = np.pad(x, ((0, 0), (0, Hp - H), (0, Wp - W), (0, 0)), mode="edge").astype(dt)
+    R, G, B = x[..., 0], x[..., 1], x[..., 2]
+    planes = [(19595 * R + 38470 * G + 7471 * B + 32768) >> 16, (-11059 * R - 21709 * G + 32768 * B + 8388608 + 32767) >> 16,
+              (32768 * R - 27439 * G - 5329 * B + 8388608 + 32767) >> 16]
+    if subsampling == "420":
+        bias = (1 + (np.arange(Wp // 2) & 1)).astype(dt)
+        planes[1:] = [(p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] + bias) >> 2 for p in planes[1:]]
+    ql, qc = codec_tables(quality)
+    d, keep, rec = [], [], []
+    for p, qt in zip(planes, (ql, qc, qc)):
+        o, lev, f, raw = _codec_plane_parts(p, qt, dt)
+        q8 = qt.reshape(8, 8).astype(dt) << 3
+        r = (f - lev * q8).astype(np.float64) / q8
+        dd = 3.0 * r * r if mode == "cubic" else np.ones(r.shape)
+        d.append(dd.transpose(0, 1, 3, 2, 4).reshape(p.shape))
+        keep.append((raw >= 0) & (raw <= 255))
+        rec.append(o)
+    Y, Cb, Cr = rec
+    if subsampling == "420":
+        Cb, Cr = (p.repeat(2, 1).repeat(2, 2) for p in (Cb, Cr))
+    cb, cr = Cb - 128, Cr - 128
+    out = np.stack([Y + ((91881 * cr + 32768) >> 16), Y + ((-22554 * cb - 46802 * cr + 32768) >> 16), Y + ((116130 * cb + 32768) >> 16)], -1)
+    return tuple(d), tuple(keep), ((out >= 0) & (out <= 255))[:, :H, :W]
+
+
+def _codec_grad_chain(g, d, keep, rgb_mask, s420, magnitudes):
+    """the linear chain of the codec's backward on g [N,H,W,3] in float64; ``magnitudes``: every matrix by its absolute values"""
+    mat = np.abs if magnitudes else (lambda a: a)
+    C = mat(codec_dct_matrix().astype(np.float64))
+    N, H, W, _ = g.shape
+    Hp, Wp = d[0].shape[1:]
+    g = np.pad(g * rgb_mask, ((0, 0), (0, Hp - H), (0, Wp - W), (0, 0))) @ mat(_CODEC_DEC)           # M_dec^T: [.., Y, Cb, Cr]
+    planes = [g[..., 0], g[..., 1], g[..., 2]]
+    if s420:
+        planes[1:] = [p[:, 0::2, 0::2] + p[:, 0::2, 1::2] + p[:, 1::2, 0::2] + p[:, 1::2, 1::2] for p in planes[1:]]
+    for j, p in enumerate(planes):
+        n, hp, wp = p.shape
+        blocks = lambda a: a.reshape(n, hp // 8, 8, wp // 8, 8).transpose(0, 1, 3, 2, 4)
+        b = C @ blocks(p * keep[j]) @ C.T
+        b = C.T @ (b * blocks(d[j])) @ C
+        planes[j] = b.transpose(0, 1, 3, 2, 4).reshape(n, hp, wp)
+    if s420:
+        planes[1:] = [0.25 * p.repeat(2, 1).repeat(2, 2) for p in planes[1:]]
+    p = np.stack(planes, -1)
+    out = p[:, :H, :W].copy()                                                                        # the padding folds onto the last row and column
+    out[:, H - 1, :] += p[:, H:, :W].sum(1)
+    out[:, :, W - 1] += p[:, :H, W:].sum(2)
+    out[:, H - 1, W - 1] += p[:, H:, W:].sum((1, 2))
+    return out @ mat(_CODEC_ENC)                                                                     # M_enc^T: [.., R, G, B]
+
+
+def codec_grad_host(frames, quality, subsampling, tone, mode, g_out, slope=None, scale=None, bound=False, consts=None):
+    """flk_codec_grad restated in float64: ``frames`` uint8 [N,H,W,3] (the SOURCE frames, frame n under ``tone[n]``), ``g_out`` =
+    d(loss)/d(decoded RGB) [N,H,W,3].  Returns a dict: ``g_in`` [N,H,W,3], the gradient with respect to the codec's input frame, and,
+    with ``slope`` [N,256,3] and ``scale`` [N,3] (``tone_slopes_host``), ``gdelta`` [N,3] = scale * sum over pixels of g_in * slope[source
+    byte].  ``consts``: ``codec_quant_slopes_host``'s result, if the caller has it.  ``bound``: also ``g_in_mag`` / ``gdelta_mag``, the
+    chain run on magnitudes (|matrices|, |g|, |slope|, |scale|), and ``g_in_roundings`` / ``gdelta_roundings``, the float32 roundings on
+    the longest path to an output in the kernel's statement order: 3 (M_dec^T), 3 (2 x 2 sum), 32 (four 8-point passes), 5 (d), 5
+    (M_enc^T), 8 spare for the float32 reciprocal of 8 Q and the first-order form of the bound, plus the (Hp - H + 1)(Wp - W + 1) terms of
+    the fold; for gdelta also the product with the slope, a thread's pixels of a tile, the shuffle tree and the waves, the tiles of
+    the frame and the scale.  |device - host| <= roundings * 2^-24 * magnitude, per element."""
+    quality, subsampling = check_codec(quality, subsampling, "codec_grad_host")
+    check_codec_grad(mode, "codec_grad_host")
+    x, tone = _codec_grad_frames("codec_grad_host", frames, tone)
+    g = np.asarray(g_out, dtype=np.float64)
+    if g.shape != x.shape:
+        raise ValueError(f"codec_grad_host: g_out must be {x.shape}, got {g.shape}")
+    d, keep, rgb_mask = codec_quant_slopes_host(x, quality, subsampling, tone, mode) if consts is None else consts
+    s420 = subsampling == "420"
+    N, H, W, _ = x.shape
+    res = {"g_in": _codec_grad_chain(g, d, keep, rgb_mask, s420, False)}
+    if bound:
+        Hp, Wp = d[0].shape[1:]
+        res["g_in_mag"] = _codec_grad_chain(np.abs(g), d, keep, rgb_mask, s420, True)
+        res["g_in_roundings"] = 56 + (Hp - H + 1) * (Wp - W + 1)
+    if slope is not None:
+        slope, scale = np.asarray(slope, dtype=np.float64), np.asarray(scale, dtype=np.float64)
+        if slope.shape != (N, 256, 3) or scale.shape != (N, 3):
+            raise ValueError(f"codec_grad_host: slope [{N},256,3] and scale [{N},3]; got {slope.shape}, {scale.shape}")
+        s = np.stack([slope[n][x[n], np.arange(3)] for n in range(N)])                               # [N,H,W,3]: the slope of the source byte
+        res["gdelta"] = (res["g_in"] * s).sum((1, 2)) * scale
+        if bound:
+            th = CODEC_TILE_H[subsampling]
+            tiles = -(-Hp // th) * -(-Wp // CODEC_TILE_W)
+            res["gdelta_mag"] = (res["g_in_mag"] * np.abs(s)).sum((1, 2)) * np.abs(scale)
+            res["gdelta_roundings"] = res["g_in_roundings"] + 1 + -(-th * CODEC_TILE_W // CODEC_THREADS) + 6 + 3 + tiles + 1
+    return res
+
+
 def add_codec_arguments(ap):
     """the scripts' options of the codec the delivered video goes through; absent by default"""
     ap.add_argument("--codec-quality", type=int, default=None, metavar="Q", help="compress the delivered video lossily, intra-frame (JPEG-style: "
@@ -1487,6 +1730,10 @@ def add_codec_arguments(ap):
     ap.add_argument("--codec-search", type=int, default=None, metavar="R", help="the P-frames' motion search range in pixels, 0..15 (default 0: "
                     "zero motion; 7 is a usual choice): every 16x16 macroblock is predicted from the best full-pel displacement of the previous "
                     "reconstruction, so camera and object motion is not paid for as residual; needs --codec-gop above 1")
+    ap.add_argument("--codec-grad", default=None, choices=["identity"] + list(CODEC_GRAD_MODES), help="the codec's Jacobian in the backward of "
+                    "--train-delivered (default identity: straight through); ste and cubic differentiate the intra codec itself -- chroma "
+                    "subsampling, clamps and the transform pair, the quantiser straight through (ste) or by the cubic rounding surrogate, which "
+                    "passes nothing at a bin centre (cubic); needs --codec-quality, an intra-frame codec and --train-delivered")
 
 
 def codec_from_arguments(ap, a, used):
@@ -1499,15 +1746,23 @@ def codec_from_arguments(ap, a, used):
             ap.error("--codec-gop needs --codec-quality")
         if a.codec_search is not None:
             ap.error("--codec-search needs --codec-quality")
+        if getattr(a, "codec_grad", None) not in (None, "identity"):
+            ap.error("--codec-grad needs --codec-quality")
         return None
     if not used:
         ap.error("--codec-quality / --codec-subsampling act on whole delivered videos: give --eval-quantised video, --train-delivered or "
                  "--save-adversarial-u8 with whole videos")
     try:
-        return Codec(a.codec_quality, a.codec_subsampling or "420", 1 if a.codec_gop is None else a.codec_gop,
-                     0 if a.codec_search is None else a.codec_search)
+        codec = Codec(a.codec_quality, a.codec_subsampling or "420", 1 if a.codec_gop is None else a.codec_gop,
+                      0 if a.codec_search is None else a.codec_search)
     except ValueError as e:
         ap.error(str(e))
+    if getattr(a, "codec_grad", None) not in (None, "identity"):
+        if codec.gop > 1:
+            ap.error("--codec-grad ste / cubic differentiate the intra codec: not with --codec-gop above 1")
+        if not getattr(a, "train_delivered", False):
+            ap.error("--codec-grad acts on the backward of --train-delivered")
+    return codec
 
 
 def flicker_keywords_from_arguments(a, delivered=False):
@@ -1517,4 +1772,6 @@ def flicker_keywords_from_arguments(a, delivered=False):
     kw = dict(flicker_time=a.flicker_time, flicker_period=a.flicker_period, capture=a.capture, flicker_model=a.flicker_model, response=a.response)
     if delivered:
         kw.update(train_delivered=a.train_delivered, codec=a.codec if a.train_delivered else None)
+        if getattr(a, "codec_grad", None) not in (None, "identity"):
+            kw.update(codec_grad=a.codec_grad)
     return kw

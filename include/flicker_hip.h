@@ -644,6 +644,30 @@ int flk_clip_prepare_grad(const flk_prepare_args* a, const flk_prep_box* boxes, 
                           const float* scale, const void* gx_s2d, int dtype, float* gdelta /* fp32 [nclip,T_out,3] */, float* partials,
                           void* stream);
 
+/* The transpose of the resampling on IMAGES (csrc/prepare.hip, clip_prepare_grad_image_kernel): the gradient with respect to every
+ * source pixel, where flk_clip_prepare_grad pushes per-byte slopes forward.  The resampling is separable, out = A_h V A_w^T with
+ * A = S2 S1 per axis (flip included along W); videoresnet_spec.prepare_adjoint_tables builds both composite matrices per clip from
+ * the forward's own indices and lambdas in float64, rounds them once to fp32 and stores them BY SOURCE INDEX: entry y of a table is
+ * 2 + K 32-bit words (first_out, count, w[K] fp32) -- the outputs that read a source index are a contiguous range, both stages
+ * being monotone; K is the largest count of the call.
+ *   g_src[k][t][y][x][c] = sum over a < count_h[y], b < count_w[x] of wh[y][a] * ww[x][b] * g(first_h[y] + a, first_w[x] + b, c)
+ * with b inner and a outer, both ascending from +0: row sums fma(ww[b], g, .), then fma(wh[a], row, .).  g: the gx_s2d layout of
+ * flk_clip_prepare_grad (fp32 or bf16), row k of it clip k of the call.  g_src: fp32, clip k at clips[k].dst as [T_out][Hs][Ws][3]
+ * with pitches in floats; a source pixel no output reads gets +0.  tables: DEVICE, table_words words; every range read from it is
+ * clamped into the output image, so a bad table gives wrong sums but no read outside g.  One launch, no atomics, one fixed order: a
+ * clip's result is that of a call holding it alone.
+ * FLK_EINVAL (before any GPU call): null pointers, nclip outside 1..FLK_PREP_MAX_CLIPS, T_out outside 1..65535, odd or non-positive
+ * Ho / Wo, K outside 1..Ho + Wo, gx_s2d not 16-byte aligned, a bad dtype, non-positive sizes, pitches that do not hold a row / a
+ * frame, tables that leave table_words. */
+typedef struct {
+  float* dst;                /* device: fp32 [T_out][Hs][Ws][3] */
+  int64_t pitch_t, pitch_h;  /* FLOATS between consecutive frames / rows */
+  int Hs, Ws;
+  int64_t tab_h, tab_w;      /* word offsets of the clip's row and column tables: Hs and Ws entries of 2 + K words */
+} flk_grad_image_clip;
+int flk_clip_prepare_grad_image(int nclip, const flk_grad_image_clip* clips /* HOST [nclip] */, int T_out, int Ho, int Wo, int K,
+                                const int32_t* tables /* DEVICE */, int64_t table_words, const void* gx_s2d, int dtype, void* stream);
+
 /* Lossy intra-frame compression of the delivered video (csrc/codec.hip): a JPEG-style round trip -- colour transform, chroma
  * subsampling, 8x8 DCT, quantisation and back -- as ONE kernel with an exact integer definition, which
  * videoresnet_spec.codec_roundtrip_host restates in numpy bit for bit (DESIGN.md 10.8 has every constant and rounding rule).  It is
@@ -687,6 +711,30 @@ int flk_codec_tables(int quality, int32_t* qluma /* [64] */, int32_t* qchroma /*
 int flk_codec_roundtrip_u8(const flk_codec_args* a, const int32_t* frame_idx /* DEVICE [nclip][T_out] or NULL */, int T_out,
                            const uint8_t* tone /* DEVICE [nclip][T_out][256][3] or NULL */, int32_t* stats /* DEVICE [nclip][T_out][2] or NULL */,
                            void* stream);
+
+/* The codec's backward (csrc/codec.hip, codec_grad_kernel; videoresnet_spec.codec_grad_host is the definition in
+ * float64).  The forward stays the integer codec; the backward differentiates a surrogate of it per frame, whose constants the kernel
+ * takes from the integer forward of each block, recomputed and not stored: colour transforms by their integer constants over 2^16;
+ * the plane clamp and the RGB clamp pass the gradient where the UNCLAMPED integer lies in 0..255; the padding folds onto the last
+ * row and column; the 4:2:0 box mean gives 1/4 to each pixel, the replication sums; the DCT pair is the orthonormal 8x8 matrix C in
+ * fp32 (G = C g C^T, then C^T G C); the quantiser's factor per coefficient f of level lev, r = (f - lev * 8 Q) / (8 Q):
+ *   FLK_CODEC_GRAD_STE    d = 1
+ *   FLK_CODEC_GRAD_CUBIC  d = 3 r^2  (the rounding u -> round(u) + (u - round(u))^3: 0 at a bin centre, 3/4 at a bin edge)
+ * g_out: DEVICE fp32, d(loss)/d(decoded RGB), the clips packed one after the other, clip k as [T_out][Hs_k][Ws_k][3]; g_in: the same
+ * layout or NULL, d(loss)/d(the codec's input frame).  gdelta[k][t][c] = scale[k][t][c] * sum over pixels of g_in(p, c) *
+ * slope[k][t][v(p, c)][c], v the SOURCE byte before the tone table; slope fp32 [nclip][T_out][256][3] and scale fp32 [nclip][T_out][3]
+ * as flk_flicker_tone_slopes writes them.  a, frame_idx, T_out and tone as flk_codec_roundtrip_u8 takes them, clips[k].dst and its
+ * pitches unused.  One workgroup per tile of the forward's tiling; per-tile sums in partials (flk_codec_grad_scratch_bytes(a, T_out)
+ * of caller scratch; 0 for arguments the call would refuse), a finishing launch adds a frame's tiles ascending from +0 and multiplies
+ * by scale (a zero scale writes +0).  No atomics: repeats are bitwise equal and a clip's result is that of a call holding it alone.
+ * FLK_EINVAL (before any GPU call): what flk_codec_roundtrip_u8 refuses of a / T_out (but for dst), a mode other than the two, null
+ * slope / scale / gdelta / g_out / partials, g_in == g_out. */
+#define FLK_CODEC_GRAD_STE 1
+#define FLK_CODEC_GRAD_CUBIC 2
+int64_t flk_codec_grad_scratch_bytes(const flk_codec_args* a, int T_out);
+int flk_codec_grad(const flk_codec_args* a, const int32_t* frame_idx /* DEVICE [nclip][T_out] or NULL */, int T_out,
+                   const uint8_t* tone /* DEVICE [nclip][T_out][256][3] or NULL */, int mode, const float* g_out, const float* slope,
+                   const float* scale, float* gdelta /* fp32 [nclip][T_out][3] */, float* g_in /* optional */, float* partials, void* stream);
 
 /* Inter-frame prediction in the codec (csrc/codec.hip; videoresnet_spec.codec_roundtrip_host(gop=, first_frame=) is
  * the definition, bit for bit): closed GOPs of `gop` frames.  Video frame n is an intra frame iff n % gop == 0, coded as

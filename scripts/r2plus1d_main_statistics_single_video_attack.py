@@ -111,6 +111,8 @@ def run_whole_videos(a):
             if a.codec is not None:             # the stored video went through the codec before it is scored
                 r["codec_quality"], r["codec_subsampling"], r["codec_gop"] = a.codec.quality, a.codec.subsampling, a.codec.gop
                 r["codec_search"] = a.codec.search
+                if a.codec_grad not in (None, "identity"):
+                    r["codec_grad"] = a.codec_grad
             ev = learner.evaluate_videos([exported], labels[i:i + 1], num_samples=G, adversarial=False)
             r["quantised_video_pred"] = ev["video_preds"]
             r["quantised_video_is_adversarial"] = bool(ev["video_preds"][0] != labels[i])

@@ -169,6 +169,8 @@ def run_whole_videos(a, world, rank, local_rank, augment):
                                  **vs.flicker_keywords_from_arguments(a, delivered=True))
     codec_keys = {} if a.codec is None else {"codec_quality": np.int64(a.codec.quality), "codec_subsampling": a.codec.subsampling,
                                                 "codec_gop": np.int64(a.codec.gop), "codec_search": np.int64(a.codec.search)}
+    if a.codec_grad not in (None, "identity"):          # (only when set: the default's result files keep their keys)
+        codec_keys["codec_grad"] = a.codec_grad
     nvid = a.batch_size // a.clips_per_video          # videos per batch
     dest = os.path.join(a.results_root, learner.model_name, "generalization", "universal", "val_test", f"all_cls_shuffle_{a.attack_type}",
                         f"t_{len(vtr)}_v_{len(vva)}_linf_{L_INF_PERT_NORM}_lambda_{LAMBDA}_beta1_{BETA_1}_")
