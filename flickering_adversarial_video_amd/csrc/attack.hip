@@ -21,70 +21,64 @@ template <int FT> struct S2D {
   __device__ static constexpr int ch(int qt, int qh, int k) {   // k = qw*3 + c
     return FT == 3 ? (qt * 2 + qh) * 8 + k : (qt * 4 + qh * 2) * 3 + k;
   }
+  __device__ static void put(float* v, int qt, int qh, int k, float u) { v[ch(qt, qh, k)] = u; }
+};
+// fold_t = 4: the (h,w) fold of fold_t = 1 with every value split into TWO bf16 numbers, [B,T,H/2,W/2,32]: channel k = bf16(x_adv),
+// channel 16 + k = bf16(x_adv - channel k).  The VideoResNet stems (bf16 plans) read both halves against the same weights, i.e. they
+// see the perturbed clip to ~16 mantissa bits at the MFMA cost of the 16 -> 32 channel padding their K step had anyway: rounding
+// x + delta/std to ONE bf16 swallows a small flicker perturbation (|delta| = 1e-4 moved the logits with the wrong sign), and the
+// centred-clip + position-bias form of the I3D stem is exact only where the clamp bounds are bf16 numbers -- here 5-8 % of the
+// values of a clip sit AT a bound, and bf16(bound - p) jumps by a whole ulp for all of them at once (measured: wrong sign at
+// |delta| = 5e-4).
+struct HiLo {
+  static constexpr int F = 1, NCH = 32;
+  __device__ static void put(float* v, int, int qh, int k, float u) {
+    const float hi = (float)(bf16_t)u;
+    v[S2D<1>::ch(0, qh, k)] = hi;                        // (stored again as bf16: exact)
+    v[16 + S2D<1>::ch(0, qh, k)] = u - hi;
+  }
 };
 
-// six consecutive values x[b,t,h,2*w2 .. 2*w2+1, 0..2]
+// six consecutive values x[b,t,h,2*w2 .. 2*w2+1, 0..2] (value i is channel i % 3); off = 6*k: a uint8 clip is read with 2-byte loads,
+// an fp32 clip with 8-byte loads
 __device__ static inline void load6(const flk_apply_args& a, size_t off, float* x) {
   if (a.x_is_u8) {
-    const uint16_t* p = (const uint16_t*)((const uint8_t*)a.x + off);   // off = 6*k: 2-byte aligned
-    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-    const uint32_t by[6] = {w0 & 255, w0 >> 8, w1 & 255, w1 >> 8, w2 & 255, w2 >> 8};
-    if (a.x_lut) {                                                      // per-channel table: value i is channel i % 3
+    uint32_t by[6];
+    load_bytes<1>((const uint8_t*)a.x + off, by);
+    if (a.x_lut) {                                                      // (the branch hoisted out of decode_u8's loop)
 #pragma unroll
       for (int i = 0; i < 6; ++i) x[i] = a.x_lut[by[i] * 3 + i % 3];
     } else {
 #pragma unroll
-      for (int i = 0; i < 6; ++i) x[i] = (float)by[i] * a.x_scale + a.x_bias;
+      for (int i = 0; i < 6; ++i) x[i] = decode_scaled(a, by[i]);
     }
   } else {
-    const float2* p = (const float2*)((const float*)a.x + off);        // off = 6*k: 8-byte aligned
+    const float2* p = (const float2*)((const float*)a.x + off);
     const float2 a0 = p[0], a1 = p[1], a2 = p[2];
     x[0] = a0.x; x[1] = a0.y; x[2] = a1.x; x[3] = a1.y; x[4] = a2.x; x[5] = a2.y;
   }
 }
 
-// value written for a pixel x with perturbation pv: the clipped sum, or (flk_apply_args.center) the sum minus pv -- i.e. x itself
-// wherever the clip is inactive
-__device__ static inline float applied(const flk_apply_args& a, float x, float pv) {
-  const float u = x + pv;
-  if (!a.center) return clipf(u, a.lo, a.hi);
-  return (u < a.lo || u > a.hi) ? clipf(u, a.lo, a.hi) - pv : x;
-}
-
-// ---- 8-bit encode (flk_export_args; include/flicker_hip.h): the export kernel's quantiser, and the quantised apply's: encode_q of
-// quant_encode.h, shared with the quantised uint8 stem (stem_fwd.hip) ----------------------------------------------------------------
-// Quantised apply (flk_apply_args.q_lut, template QUANT of the apply kernels): the value a kernel writes is the one the STORED video
-// decodes to -- v = applied(...) encoded to its byte, the byte decoded through the table.  NO second clamp: a value the clamp holds at a
-// bound is stored as the level nearest the bound, and a clean forward of the stored frames (clamp bounds -inf / +inf) sees that level.
-// ql: the 768-entry table in LDS (stage_q_lut); c: the value's channel.  QUANT = false is the identity: the plain instantiations
-// contain none of this.
-template <bool QUANT> __device__ static inline float quantised(const flk_apply_args& a, const float* ql, float v, int c) {
-  if constexpr (QUANT) return ql[encode_q(v, a.q_mul[c], a.q_add[c], a.q_levels) * 3 + c];
-  else return v;
-}
-// every thread of the workgroup calls this once, before any early return
-__device__ static inline void stage_q_lut(const flk_apply_args& a, float* ql) {
-  for (int i = threadIdx.x; i < 768; i += 256) ql[i] = a.q_lut[i];
-  __syncthreads();
-}
-
-// perturbation added at frame t (before adv_flag): p'[t] = p[(t - shift_p) mod T] (tf.roll), p = clip(delta)/std
-// (delta_per_clip: clip b has its own [T,3] perturbation; delta_per_line: one value per line of a frame, [Bd,T,H,3] -- a branch that
-// is uniform over the launch; the callers that hoist the three values of a frame take the per-element route for it, as for dense)
+// perturbation added at frame t (before adv_flag): flicker_pert's over every form of delta -- the flicker [T,3] / [B,T,3], one value per
+// line of a frame (delta_per_line, [Bd,T,H,3]) or per element (delta_dense, [T,H,W,3]); a branch that is uniform over the launch; the
+// callers that hoist the three values of a frame take the per-element route for the last two
 __device__ static inline float pert_at(const flk_apply_args& a, int b, int t, int h, int w, int c) {
   const int ts = wrap(t - a.shift_p, a.T);
   float d;
   if (a.delta_per_line) d = a.delta[(((size_t)(a.delta_per_clip ? b : 0) * a.T + ts) * a.H + h) * 3 + c];
-  else d = a.delta_dense ? a.delta[(((size_t)ts * a.H + h) * a.W + w) * 3 + c] : a.delta[(a.delta_per_clip ? b * a.T : 0) * 3 + ts * 3 + c];
-  const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;       // (per-clip clamp bound)
-  if (dc > 0.f) d = clipf(d, -dc, dc);
-  return d * a.inv_std[c];
+  else d = a.delta_dense ? a.delta[(((size_t)ts * a.H + h) * a.W + w) * 3 + c] : a.delta[flicker_index(a, b, ts, c)];
+  return pert_of(a, b, d, c);
+}
+// the same with adv_flag: the select keeps the product's rounding apart from the sum that applied() forms
+__device__ static inline float adv_pert_at(const flk_apply_args& a, int b, int t, int h, int w, int c) {
+  return a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, h, w, c) : 0.f;
 }
 
-// ---- apply: one thread = one space-to-depth output position (FT x 2 x 2 input cells x 3 channels) ----
-template <typename TO, int FTL, bool QUANT>
+// ---- apply: one thread = one space-to-depth output position (L::F x 2 x 2 input cells x 3 channels); L = S2D<1|2|3> or HiLo.
+// A 1-D grid capped by the host; the workgroups stride over the positions ----
+template <typename TO, typename L, bool QUANT>
 __global__ __launch_bounds__(256) void apply_s2d_kernel(const flk_apply_args a, char* out) {
-  constexpr int FT = S2D<FTL>::F, NCH = S2D<FTL>::NCH;
+  constexpr int FT = L::F, NCH = L::NCH;
   __shared__ float ql[QUANT ? 768 : 1];
   if constexpr (QUANT) stage_q_lut(a, ql);
   const int T2 = a.T / FT, H2 = a.H / 2, W2 = a.W / 2;
@@ -108,165 +102,73 @@ __global__ __launch_bounds__(256) void apply_s2d_kernel(const flk_apply_args a, 
         float x[6];
         load6(a, ((((size_t)b * a.T + tx) * a.H + h) * a.W + 2 * w2) * 3, x);
 #pragma unroll
-        for (int qw = 0; qw < 2; ++qw)
+        for (int qw = 0; qw < 2; ++qw)              // (this nest, not one loop over k = qw*3 + c: DESIGN_LOG.md, the strided legs)
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const float pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, h, 2 * w2 + qw, c) : 0.f;
-            v[S2D<FTL>::ch(qt, qh, qw * 3 + c)] = quantised<QUANT>(a, ql, applied(a, x[qw * 3 + c], pv), c);
-          }
+          for (int c = 0; c < 3; ++c)
+            L::put(v, qt, qh, qw * 3 + c, perturbed<QUANT>(a, ql, x[qw * 3 + c], adv_pert_at(a, b, t, h, 2 * w2 + qw, c), c));
       }
     }
     store_ch<TO, NCH>(out + (size_t)gid * NCH * sizeof(TO), v);
   }
 }
 
-// fold_t = 4: the (h,w) fold of fold_t = 1 with every value split into TWO bf16 numbers, [B,T,H/2,W/2,32]: channel k = bf16(x_adv),
-// channel 16 + k = bf16(x_adv - channel k).  The VideoResNet stems (bf16 plans) read both halves against the same weights, i.e. they
-// see the perturbed clip to ~16 mantissa bits at the MFMA cost of the 16 -> 32 channel padding their K step had anyway: rounding
-// x + delta/std to ONE bf16 swallows a small flicker perturbation (|delta| = 1e-4 moved the logits with the wrong sign), and the
-// centred-clip + position-bias form of the I3D stem is exact only where the clamp bounds are bf16 numbers -- here 5-8 % of the
-// values of a clip sit AT a bound, and bf16(bound - p) jumps by a whole ulp for all of them at once (measured: wrong sign at
-// |delta| = 5e-4).
-template <bool QUANT>
-__global__ __launch_bounds__(256) void apply_s2d_hilo_kernel(const flk_apply_args a, char* out) {
+// Fast path of the uint8 clips with W % 8 == 0 (fold_t 2 / 3 flicker by scalars: the headline configuration; fold_t 4 through the decode
+// table: the input of the bf16 VideoResNet plans read straight from the resident clip): one thread = 4 consecutive output positions of
+// one (clip, folded frame, row pair).  It reads its 24 source bytes (8 pixels) of each of the 2 F (frame, row) pairs as three aligned
+// 8-byte loads (the strided kernel above issues 2-byte loads) and decodes its position with 32-bit arithmetic from a 3-D grid
+// (positions, folded frame, clip).  TABLE: decode through x_lut, staged in LDS once per workgroup (else the scalars; no table is
+// reserved).  DENSE: the [T,H,W,3] or per-line [Bd,T,H,3] perturbation, per element; else [T,3] / [B,T,3], the 3 F values evaluated
+// once.  Same arithmetic per element as the strided kernel, so the bytes written equal that kernel's.
+template <typename TO, typename L, bool TABLE, bool DENSE, bool QUANT>
+__global__ __launch_bounds__(256) void apply_s2d_u8x4_kernel(const flk_apply_args a, char* out) {
+  constexpr int F = L::F, NCH = L::NCH;
+  __shared__ float lut[TABLE ? 768 : 1];
   __shared__ float ql[QUANT ? 768 : 1];
-  if constexpr (QUANT) stage_q_lut(a, ql);
-  const int H2 = a.H / 2, W2 = a.W / 2;
-  const long total = (long)a.B * a.T * H2 * W2;
-  for (long gid = (long)blockIdx.x * 256 + threadIdx.x; gid < total; gid += (long)gridDim.x * 256) {
-    long r = gid;
-    const int w2 = r % W2; r /= W2;
-    const int h2 = r % H2; r /= H2;
-    const int t = r % a.T;
-    const int b = r / a.T;
-    const int tx = wrap(t - a.shift_x, a.T);
-    float v[32];
-#pragma unroll
-    for (int i = 0; i < 32; ++i) v[i] = 0.f;
-#pragma unroll
-    for (int qh = 0; qh < 2; ++qh) {
-      const int h = 2 * h2 + qh;
-      float x[6];
-      load6(a, ((((size_t)b * a.T + tx) * a.H + h) * a.W + 2 * w2) * 3, x);
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const float pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, h, 2 * w2 + k / 3, k % 3) : 0.f;
-        const float u = quantised<QUANT>(a, ql, applied(a, x[k], pv), k % 3);
-        const float hi = (float)(bf16_t)u;
-        v[S2D<1>::ch(0, qh, k)] = hi;                    // (stored again as bf16: exact)
-        v[16 + S2D<1>::ch(0, qh, k)] = u - hi;
-      }
-    }
-    store_ch<bf16_t, 32>(out + (size_t)gid * 32 * sizeof(bf16_t), v);
-  }
-}
-
-// Fast path of the headline configuration (uint8 clip, flicker delta [T,3], FT = 2, W % 8 == 0): one thread = 4
-// consecutive output positions.  It reads its 24 source bytes of each of the 4 (frame, row) pairs as three aligned
-// 8-byte loads (the generic kernel above issues 2-byte loads), evaluates the 6 perturbation values (2 frames x RGB) once,
-// and decodes its position with 32-bit arithmetic from a 3-D grid.  Same arithmetic per element as the generic kernel.
-template <typename TO, int FTL, bool QUANT>
-__global__ __launch_bounds__(256) void apply_s2d_u8_flicker_kernel(const flk_apply_args a, char* out) {
-  constexpr int NCH = 32;
-  __shared__ float ql[QUANT ? 768 : 1];
-  if constexpr (QUANT) stage_q_lut(a, ql);
+  if constexpr (TABLE)
+    for (int i = threadIdx.x; i < 768; i += 256) lut[i] = a.x_lut[i];
+  if constexpr (QUANT) stage_q_lut(a, ql);        // (its barrier covers lut too)
+  else if constexpr (TABLE) __syncthreads();
   const int H2 = a.H / 2, W2 = a.W / 2, WG = W2 / 4;
   const unsigned i = blockIdx.x * 256u + threadIdx.x;
   if (i >= (unsigned)(H2 * WG)) return;
   const int h2 = i / WG, wg = i - h2 * WG;
   const int t2 = blockIdx.y, b = blockIdx.z;
-  float pv[2][3];
+  float pv[F][3];
+  if constexpr (!DENSE) {
 #pragma unroll
-  for (int qt = 0; qt < 2; ++qt)
+    for (int qt = 0; qt < F; ++qt)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pv[qt][c] = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, 2 * t2 + qt, 0, 0, c) : 0.f;
-  uint2 raw[2][2][3];
-#pragma unroll
-  for (int qt = 0; qt < 2; ++qt) {
-    const int tx = wrap(2 * t2 + qt - a.shift_x, a.T);
-#pragma unroll
-    for (int qh = 0; qh < 2; ++qh) {
-      const uint2* src = (const uint2*)((const uint8_t*)a.x + ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 8 * wg) * 3);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) raw[qt][qh][k] = src[k];
-    }
+      for (int c = 0; c < 3; ++c) pv[qt][c] = adv_pert_at(a, b, F * t2 + qt, 0, 0, c);
   }
-  char* dst = out + ((((size_t)b * (a.T / 2) + t2) * H2 + h2) * W2 + 4 * wg) * NCH * sizeof(TO);
+  uint32_t by[F][2][24];
+#pragma unroll
+  for (int qt = 0; qt < F; ++qt) {
+    const int tx = wrap(F * t2 + qt - a.shift_x, a.T);
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh)
+      load_bytes<4>((const uint8_t*)a.x + ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 8 * wg) * 3, by[qt][qh]);
+  }
+  char* dst = out + ((((size_t)b * (a.T / F) + t2) * H2 + h2) * W2 + 4 * wg) * NCH * sizeof(TO);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {                   // output position 4*wg + j: source pixels 2j, 2j+1 of the 8-pixel run
     float v[NCH];
 #pragma unroll
     for (int k = 0; k < NCH; ++k) v[k] = 0.f;
 #pragma unroll
-    for (int qt = 0; qt < 2; ++qt)
+    for (int qt = 0; qt < F; ++qt)
 #pragma unroll
-      for (int qh = 0; qh < 2; ++qh) {
-        const uint32_t w[6] = {raw[qt][qh][0].x, raw[qt][qh][0].y, raw[qt][qh][1].x, raw[qt][qh][1].y, raw[qt][qh][2].x, raw[qt][qh][2].y};
+      for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
-        for (int e = 0; e < 6; ++e) {              // byte 6j + e of the 24-byte run
-          const int bi = 6 * j + e;
-          const float x = (float)((w[bi >> 2] >> (8 * (bi & 3))) & 255u) * a.x_scale + a.x_bias;
-          v[S2D<FTL>::ch(qt, qh, e)] = quantised<QUANT>(a, ql, applied(a, x, pv[qt][e % 3]), e % 3);
+        for (int e = 0; e < 6; ++e) {              // byte 6j + e of the 24-byte run: pixel 8wg + 2j + e/3, channel e % 3
+          const uint32_t byte = by[qt][qh][6 * j + e];
+          float x, p;
+          if constexpr (TABLE) x = lut[byte * 3 + e % 3];
+          else x = decode_scaled(a, byte);
+          if constexpr (DENSE) p = adv_pert_at(a, b, F * t2 + qt, 2 * h2 + qh, 8 * wg + 2 * j + e / 3, e % 3);
+          else p = pv[qt][e % 3];
+          L::put(v, qt, qh, e, perturbed<QUANT>(a, ql, x, p, e % 3));
         }
-      }
     store_ch<TO, NCH>(dst + (size_t)j * NCH * sizeof(TO), v);
-  }
-}
-
-// fold_t = 4 from a uint8 clip with the decode table (W % 8 == 0): the input of the bf16 VideoResNet plans read straight from the
-// resident uint8 clip.  Laid out like apply_s2d_u8_flicker_kernel: one thread = 4 consecutive output positions of one (clip, frame,
-// row pair), each of its two source rows read as three aligned 8-byte loads (24 bytes = 8 pixels); the 768-entry table is staged in
-// LDS once per workgroup.  Per element the arithmetic of apply_s2d_hilo_kernel on the decoded value, so the bytes written equal
-// that kernel's on the fp32 clip x_lut[u8].  DENSE: the [T,H,W,3] or per-line [Bd,T,H,3] perturbation (per element); else [T,3] /
-// [B,T,3] (3 values).
-template <bool DENSE, bool QUANT>
-__global__ __launch_bounds__(256) void apply_s2d_hilo_u8_kernel(const flk_apply_args a, char* out) {
-  __shared__ float lut[768];
-  __shared__ float ql[QUANT ? 768 : 1];
-  for (int i = threadIdx.x; i < 768; i += 256) lut[i] = a.x_lut[i];
-  if constexpr (QUANT) stage_q_lut(a, ql);        // (its barrier covers lut too)
-  else __syncthreads();
-  const int H2 = a.H / 2, W2 = a.W / 2, WG = W2 / 4;
-  const unsigned i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= (unsigned)(H2 * WG)) return;
-  const int h2 = i / WG, wg = i - h2 * WG;
-  const int t = blockIdx.y, b = blockIdx.z;
-  const int tx = wrap(t - a.shift_x, a.T);
-  float pv[3];
-  if constexpr (!DENSE) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) pv[c] = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, 0, 0, c) : 0.f;
-  }
-  uint2 raw[2][3];
-#pragma unroll
-  for (int qh = 0; qh < 2; ++qh) {
-    const uint2* src = (const uint2*)((const uint8_t*)a.x + ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 8 * wg) * 3);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) raw[qh][k] = src[k];
-  }
-  char* dst = out + ((((size_t)b * a.T + t) * H2 + h2) * W2 + 4 * wg) * 32 * sizeof(bf16_t);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {                   // output position 4*wg + j: source pixels 2j, 2j+1 of the 8-pixel run
-    float v[32];
-#pragma unroll
-    for (int k = 0; k < 32; ++k) v[k] = 0.f;
-#pragma unroll
-    for (int qh = 0; qh < 2; ++qh) {
-      const uint32_t w[6] = {raw[qh][0].x, raw[qh][0].y, raw[qh][1].x, raw[qh][1].y, raw[qh][2].x, raw[qh][2].y};
-#pragma unroll
-      for (int e = 0; e < 6; ++e) {              // byte 6j + e of the 24-byte run: pixel 8wg + 2j + e/3, channel e % 3
-        const int bi = 6 * j + e;
-        const float x = lut[((w[bi >> 2] >> (8 * (bi & 3))) & 255u) * 3 + e % 3];
-        float p;
-        if constexpr (DENSE) p = a.adv_flag != 0.f ? a.adv_flag * pert_at(a, b, t, 2 * h2 + qh, 8 * wg + 2 * j + e / 3, e % 3) : 0.f;
-        else p = pv[e % 3];
-        const float u = quantised<QUANT>(a, ql, applied(a, x, p), e % 3);
-        const float hi = (float)(bf16_t)u;
-        v[S2D<1>::ch(0, qh, e)] = hi;
-        v[16 + S2D<1>::ch(0, qh, e)] = u - hi;
-      }
-    }
-    store_ch<bf16_t, 32>(dst + (size_t)j * 32 * sizeof(bf16_t), v);
   }
 }
 
@@ -289,110 +191,85 @@ static int check_apply(const flk_apply_args* a) {
   return FLK_OK;
 }
 
+// the strided kernel: a 1-D grid of at most 16384 workgroups
+template <typename TO, typename L>
+static int launch_apply(const flk_apply_args* a, void* out, hipStream_t st) {
+  const long total = (long)a->B * (a->T / L::F) * (a->H / 2) * (a->W / 2);
+  const dim3 grid((unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256));
+  if (a->q_lut) FLK_LAUNCH_KERNEL((apply_s2d_kernel<TO, L, true>), grid, dim3(256), 0, st, *a, (char*)out);
+  else FLK_LAUNCH_KERNEL((apply_s2d_kernel<TO, L, false>), grid, dim3(256), 0, st, *a, (char*)out);      // (untouched by the option)
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+// the four-positions kernel: grid (positions of a folded frame / 4 / 256, folded frames, clips)
+template <typename TO, typename L, bool TABLE, bool DENSE>
+static int launch_apply_u8x4(const flk_apply_args* a, void* out, hipStream_t st) {
+  const dim3 grid((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)(a->T / L::F), (unsigned)a->B);
+  if (a->q_lut) FLK_LAUNCH_KERNEL((apply_s2d_u8x4_kernel<TO, L, TABLE, DENSE, true>), grid, dim3(256), 0, st, *a, (char*)out);
+  else FLK_LAUNCH_KERNEL((apply_s2d_u8x4_kernel<TO, L, TABLE, DENSE, false>), grid, dim3(256), 0, st, *a, (char*)out);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+// fold_t 0 .. 3: the layout is a template argument
+template <typename TO>
+static int dispatch_apply(const flk_apply_args* a, void* out, hipStream_t st) {
+  const int ftl = fold_layout(a->fold_t);
+  if (ftl != 1 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T / 2 < 65536 && a->B < 65536)
+    return ftl == 2 ? launch_apply_u8x4<TO, S2D<2>, false, false>(a, out, st) : launch_apply_u8x4<TO, S2D<3>, false, false>(a, out, st);
+  return ftl == 1 ? launch_apply<TO, S2D<1>>(a, out, st) : ftl == 2 ? launch_apply<TO, S2D<2>>(a, out, st) : launch_apply<TO, S2D<3>>(a, out, st);
+}
+
 extern "C" int flk_perturb_apply_s2d(const flk_apply_args* a, void* out, int dtype, void* stream) {
   int rc = check_apply(a);
   if (rc) return rc;
   FLK_REQUIRE(out, "flk_perturb_apply_s2d: null out");
   FLK_REQUIRE(((size_t)out & 15) == 0, "flk_perturb_apply_s2d: out must be 16-byte aligned (got %p)", out);
-  const int ftl = (a->fold_t == 1 || a->fold_t == 4) ? 1 : a->fold_t == 3 ? 3 : 2, ft = ftl == 1 ? 1 : 2;
-  const long total = (long)a->B * (a->T / ft) * (a->H / 2) * (a->W / 2);
-  const unsigned grid = (unsigned)((total + 255) / 256 > 16384 ? 16384 : (total + 255) / 256);
   hipStream_t st = (hipStream_t)stream;
-  const bool quant = a->q_lut != nullptr;          // the QUANT instantiations: the plain ones are untouched by the option
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_perturb_apply_s2d: bad dtype");
   if (a->fold_t == 4) {
     FLK_REQUIRE(dtype == FLK_BF16 && !a->center, "flk_perturb_apply_s2d: fold_t = 4 (two bf16 numbers per value) writes bf16, uncentred");
-    if (a->x_lut && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T < 65536 && a->B < 65536) {
-      const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)a->T, (unsigned)a->B);
-#define FLK_HILO_U8(D) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, true>), g3, dim3(256), 0, st, *a, (char*)out); \
-                           else FLK_LAUNCH_KERNEL((apply_s2d_hilo_u8_kernel<D, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
-      if (a->delta_dense || a->delta_per_line) FLK_HILO_U8(true); else FLK_HILO_U8(false);
-#undef FLK_HILO_U8
-    } else if (quant) {
-      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel<true>, dim3(grid), dim3(256), 0, st, *a, (char*)out);
-    } else {
-      FLK_LAUNCH_KERNEL(apply_s2d_hilo_kernel<false>, dim3(grid), dim3(256), 0, st, *a, (char*)out);
-    }
-    FLK_CHECK_HIP(hipGetLastError());
-    return FLK_OK;
+    if (a->x_lut && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T < 65536 && a->B < 65536)
+      return (a->delta_dense || a->delta_per_line) ? launch_apply_u8x4<bf16_t, HiLo, true, true>(a, out, st)
+                                                   : launch_apply_u8x4<bf16_t, HiLo, true, false>(a, out, st);
+    return launch_apply<bf16_t, HiLo>(a, out, st);
   }
-  const bool bf = dtype == FLK_BF16;
-  if (ft == 2 && a->x_is_u8 && !a->x_lut && !a->delta_dense && a->W % 8 == 0 && ((size_t)a->x & 7) == 0 && a->T / 2 < 65536 && a->B < 65536) {
-    const dim3 g3((unsigned)(((a->H / 2) * (a->W / 8) + 255) / 256), (unsigned)(a->T / 2), (unsigned)a->B);
-#define FLK_U8F(TT, L) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, true>), g3, dim3(256), 0, st, *a, (char*)out); \
-                            else FLK_LAUNCH_KERNEL((apply_s2d_u8_flicker_kernel<TT, L, false>), g3, dim3(256), 0, st, *a, (char*)out); } while (0)
-    if (bf && ftl == 2) FLK_U8F(bf16_t, 2);
-    else if (bf) FLK_U8F(bf16_t, 3);
-    else if (ftl == 2) FLK_U8F(float, 2);
-    else FLK_U8F(float, 3);
-#undef FLK_U8F
-    FLK_CHECK_HIP(hipGetLastError());
-    return FLK_OK;
-  }
-#define FLK_APPLY(TT, L) do { if (quant) FLK_LAUNCH_KERNEL((apply_s2d_kernel<TT, L, true>), dim3(grid), dim3(256), 0, st, *a, (char*)out); \
-                              else FLK_LAUNCH_KERNEL((apply_s2d_kernel<TT, L, false>), dim3(grid), dim3(256), 0, st, *a, (char*)out); } while (0)
-  if (bf) { if (ftl == 1) FLK_APPLY(bf16_t, 1); else if (ftl == 2) FLK_APPLY(bf16_t, 2); else FLK_APPLY(bf16_t, 3); }
-  else { if (ftl == 1) FLK_APPLY(float, 1); else if (ftl == 2) FLK_APPLY(float, 2); else FLK_APPLY(float, 3); }
-#undef FLK_APPLY
-  FLK_CHECK_HIP(hipGetLastError());
-  return FLK_OK;
+  return dtype == FLK_BF16 ? dispatch_apply<bf16_t>(a, out, st) : dispatch_apply<float>(a, out, st);
 }
 
-// ---- 8-bit export: x_adv of the apply kernels encoded to the bytes of a frame (include/flicker_hip.h; encode_q is above, shared with
-// the quantised apply) -----------------------------------------------------------------------------------------------------------
-// one value of the clip, as load6 decodes it: byte `by` of channel c
-__device__ static inline float decode1(const flk_apply_args& a, uint32_t by, int c) {
-  return a.x_lut ? a.x_lut[by * 3 + c] : (float)by * a.x_scale + a.x_bias;
-}
-
-// Work item = (clip b, frame t, chunk of 256 units of that frame); one thread = one unit of the DESTINATION frame: unit 0 the bytes in
-// front of its first 4-byte boundary (0..3), units 1..nw its aligned words, unit nw + 1 the bytes behind the last whole word (0..3).
-// A word is built in a register and stored once; the source is read as one word / float4 where it is aligned too, else per value.
-// Workgroups stride over the items, so the bytes do not depend on the grid.  STATS: per item the 12 sums (3 channels x 4 statistics)
-// are reduced in the wave, then through LDS, and thread k adds sum k to stats[b][t][k] with one integer atomic.
+// ---- 8-bit export: x_adv of the apply kernels encoded to the bytes of a frame (include/flicker_hip.h; encode_q is the quantised
+// apply's) ---------------------------------------------------------------------------------------------------------------------------
+// One thread = one unit of the destination frame (ExportUnit, perturb_common.h).  A word is built in a register and stored once; the
+// source is read as one word / float4 where it is aligned too, else per value.  Workgroups stride over the items, so the bytes do not
+// depend on the grid.  STATS: per item the 12 sums are folded by export_stats_fold into stats[b][t][0..11].
 template <bool STATS>
 __global__ __launch_bounds__(256) void adv_export_u8_kernel(const flk_apply_args a, const flk_export_args e, uint8_t* out, int32_t* stats, int chunks,
                                                             long nitems) {
   flk_apply_args ap = a;          // what pert_at sees: the perturbation's own period
   ap.T = e.delta_T;
   const int F = a.H * a.W * 3;
-  __shared__ int red[4][12];
+  __shared__ int red[4 * 12];
   for (long item = blockIdx.x; item < nitems; item += gridDim.x) {
     long r = item;
     const int chunk = (int)(r % chunks); r /= chunks;
     const int t = (int)(r % a.T);
     const int b = (int)(r / a.T);
     uint8_t* dst = out + (size_t)(e.out_clip_offset + b) * (size_t)e.out_clip_stride + (size_t)t * F;
-    int head = (4 - (int)((uintptr_t)dst & 3)) & 3;
-    if (head > F) head = F;
-    const int nw = (F - head) >> 2, tail = (F - head) & 3;
-    const int u = chunk * 256 + (int)threadIdx.x;
-    int start = 0, cnt = 0;
-    if (u == 0) cnt = head;
-    else if (u <= nw) { start = head + 4 * (u - 1); cnt = 4; }
-    else if (u == nw + 1) { start = head + 4 * nw; cnt = tail; }
+    ExportUnit un(dst, F, a.W, chunk);
+    const int start = un.start, cnt = un.cnt;
     int acc[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     if (cnt > 0) {
       const int tx = wrap(t - a.shift_x, a.T);      // x'[t] = x[(t - shift_x) mod T]
       const size_t soff = ((size_t)b * a.T + tx) * F + start;
-      int pix = start / 3, c = start - pix * 3;
-      int h = pix / a.W, w = pix - h * a.W;
       float pvf[3] = {0.f, 0.f, 0.f};
       const bool per_element = a.delta_dense || a.delta_per_line;     // (per line: a unit of four bytes may span two lines)
       if (!per_element) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) pvf[k] = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, 0, 0, k) : 0.f;
+        for (int k = 0; k < 3; ++k) pvf[k] = adv_pert_at(ap, b, t, 0, 0, k);
       }
       uint32_t by[4] = {0, 0, 0, 0};
       float xs[4] = {0.f, 0.f, 0.f, 0.f};
       if (a.x_is_u8) {
-        const uint8_t* s = (const uint8_t*)a.x + soff;
-        if (cnt == 4 && ((uintptr_t)s & 3) == 0) {
-          const uint32_t v = *(const uint32_t*)s;
-          by[0] = v & 255; by[1] = (v >> 8) & 255; by[2] = (v >> 16) & 255; by[3] = v >> 24;
-        } else {
-          for (int j = 0; j < cnt; ++j) by[j] = s[j];
-        }
+        export_load_u8((const uint8_t*)a.x + soff, cnt, by);
       } else {
         const float* s = (const float*)a.x + soff;
         if (cnt == 4 && ((uintptr_t)s & 15) == 0) {
@@ -406,46 +283,31 @@ __global__ __launch_bounds__(256) void adv_export_u8_kernel(const flk_apply_args
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < cnt) {
-          const float x = a.x_is_u8 ? decode1(a, by[j], c) : xs[j];
+          const int c = un.c;
+          const float x = a.x_is_u8 ? decode_u8(a, by[j], c) : xs[j];
           float pv;
-          if (per_element) pv = a.adv_flag != 0.f ? a.adv_flag * pert_at(ap, b, t, h, w, c) : 0.f;
+          if (per_element) pv = adv_pert_at(ap, b, t, un.h, un.w, c);
           else pv = c == 0 ? pvf[0] : c == 1 ? pvf[1] : pvf[2];
           const float mul = c == 0 ? e.mul[0] : c == 1 ? e.mul[1] : e.mul[2];
           const float add = c == 0 ? e.add[0] : c == 1 ? e.add[1] : e.add[2];
-          const int q = encode_q(applied(a, x, pv), mul, add, e.levels);
+          const int q = encode_q(perturbed<false>(a, nullptr, x, pv, c), mul, add, e.levels);
           if (cnt == 4) packed |= (uint32_t)q << (8 * j);
           else dst[start + j] = (uint8_t)q;
           if constexpr (STATS) {
-            const int qc = a.x_is_u8 ? (int)by[j] : encode_q(x, mul, add, e.levels);
-            const int d = q - qc;
-            // the sum applied() clamps.  Exactly that sum for adv_flag 0 or 1 (adv_flag * p is then exact, so a contraction at either site
-            // changes nothing); for other adv_flag values the two sites may round adv_flag * p + x differently in the last bit
-            const float uu = x + pv;
-            const int cl = (uu < a.lo || uu > a.hi) ? 1 : 0;
+            // clamped: the sum applied() clamps.  Exactly that sum for adv_flag 0 or 1 (adv_flag * p is then exact, so a contraction at either
+            // site changes nothing); for other adv_flag values the two sites may round adv_flag * p + x differently in the last bit
+            const int d = q - (a.x_is_u8 ? (int)by[j] : encode_q(x, mul, add, e.levels));
+            const int cl = clamps(a, x + pv) ? 1 : 0;
 #pragma unroll
             for (int k = 0; k < 3; ++k)
               if (c == k) { acc[k][0] += d; acc[k][1] += d < 0 ? -d : d; acc[k][2] += d != 0; acc[k][3] += cl; }
           }
-          if (++c == 3) { c = 0; if (++w == a.W) { w = 0; ++h; } }
+          un.next(a.W);
         }
       }
       if (cnt == 4) *(uint32_t*)(dst + start) = packed;
     }
-    if constexpr (STATS) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        int v = acc[k >> 2][k & 3];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-      }
-      __syncthreads();
-      if (threadIdx.x < 12) {
-        const int s = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (s != 0) atomicAdd(stats + ((size_t)b * a.T + t) * 12 + threadIdx.x, s);
-      }
-      __syncthreads();            // red is reused by the next item
-    }
+    if constexpr (STATS) export_stats_fold(acc, red, stats + ((size_t)b * a.T + t) * 12);
   }
 }
 
@@ -505,8 +367,7 @@ __global__ __launch_bounds__(256) void grad_reduce_stage1(const flk_apply_args a
         for (int qw = 0; qw < 2; ++qw)
 #pragma unroll
           for (int c = 0; c < 3; ++c) {
-            const float u = x[qw * 3 + c] + a.adv_flag * pert_at(a, b, t, h, 2 * w2 + qw, c);
-            if (u >= a.lo && u <= a.hi) acc[qt * 3 + c] += g[S2D<FTL>::ch(qt, qh, qw * 3 + c)];
+            if (passes(a, x[qw * 3 + c], pert_at(a, b, t, h, 2 * w2 + qw, c))) acc[qt * 3 + c] += g[S2D<FTL>::ch(qt, qh, qw * 3 + c)];
           }
       }
     }
@@ -514,9 +375,7 @@ __global__ __launch_bounds__(256) void grad_reduce_stage1(const flk_apply_args a
   __shared__ float red[4][6];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    float v = acc[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    const float v = wave_sum(acc[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
   }
   __syncthreads();
@@ -530,7 +389,7 @@ __global__ __launch_bounds__(256) void grad_reduce_stage1(const flk_apply_args a
 __global__ void grad_reduce_stage2(const flk_apply_args a, int nchunk, const float* partials, float* gdelta) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= a.T * 3) return;
-  const int FT = (a.fold_t == 1 || a.fold_t == 4) ? 1 : 2;      // frames per folded position (fold_t 0, 2, 3: two)
+  const int FT = fold_frames(a.fold_t);
   const int t = i / 3, c = i % 3, t2 = t / FT, qt = t % FT, T2 = a.T / FT;
   const int b_lo = a.delta_per_clip ? (int)blockIdx.y : 0, b_hi = a.delta_per_clip ? b_lo + 1 : a.B;
   float s = 0.f;
@@ -540,8 +399,7 @@ __global__ void grad_reduce_stage2(const flk_apply_args a, int nchunk, const flo
   const size_t dbase = a.delta_per_clip ? (size_t)b_lo * a.T * 3 : 0;
   const float d = a.delta[dbase + ts * 3 + c];
   const float dc = a.dclip_dev ? a.dclip_dev[b_lo] : a.dclip;
-  const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-  gdelta[dbase + ts * 3 + c] = pass ? s * a.adv_flag * a.inv_std[c] : 0.f;
+  gdelta[dbase + ts * 3 + c] = delta_grad_out(d, dc, s, a.adv_flag, a.inv_std[c]);
 }
 
 // stage 2 alone, for producers of stage-1 partials outside this file (stem_grad.hip)
@@ -577,8 +435,7 @@ __global__ __launch_bounds__(256) void grad_dense_kernel(const flk_apply_args a,
           load6(a, ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 2 * w2) * 3, x);
 #pragma unroll
           for (int k = 0; k < 6; ++k) {
-            const float u = x[k] + a.adv_flag * pert_at(a, b, t, 2 * h2 + qh, 2 * w2 + k / 3, k % 3);
-            if (u >= a.lo && u <= a.hi) acc[S2D<FTL>::ch(qt, qh, k)] += g[S2D<FTL>::ch(qt, qh, k)];
+            if (passes(a, x[k], pert_at(a, b, t, 2 * h2 + qh, 2 * w2 + k / 3, k % 3))) acc[S2D<FTL>::ch(qt, qh, k)] += g[S2D<FTL>::ch(qt, qh, k)];
           }
         }
       }
@@ -591,9 +448,7 @@ __global__ __launch_bounds__(256) void grad_dense_kernel(const flk_apply_args a,
         for (int k = 0; k < 6; ++k) {
           const int t = FT * t2 + qt, ts = wrap(t - a.shift_p, a.T), c = k % 3;
           const size_t di = (((size_t)ts * a.H + 2 * h2 + qh) * a.W + 2 * w2 + k / 3) * 3 + c;
-          const float d = a.delta[di];
-          const bool pass = !(a.dclip > 0.f) || (d >= -a.dclip && d <= a.dclip);
-          gdelta[di] = pass ? acc[S2D<FTL>::ch(qt, qh, k)] * a.adv_flag * a.inv_std[c] : 0.f;
+          gdelta[di] = delta_grad_out(a.delta[di], a.dclip, acc[S2D<FTL>::ch(qt, qh, k)], a.adv_flag, a.inv_std[c]);
         }
   }
 }
@@ -628,8 +483,7 @@ __global__ __launch_bounds__(256) void grad_lines_kernel(const flk_apply_args a,
         load6(a, ((((size_t)b * a.T + tx) * a.H + 2 * h2 + qh) * a.W + 2 * w2) * 3, x);
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
-          const float u = x[k] + a.adv_flag * p[qh][k % 3];
-          if (u >= a.lo && u <= a.hi) acc[qh][k % 3] += g[S2D<1>::ch(0, qh, k)];
+          if (passes(a, x[k], p[qh][k % 3])) acc[qh][k % 3] += g[S2D<1>::ch(0, qh, k)];
         }
       }
     }
@@ -639,14 +493,10 @@ __global__ __launch_bounds__(256) void grad_lines_kernel(const flk_apply_args a,
     for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float v = acc[qh][c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        const float v = wave_sum(acc[qh][c]);
         if (lane == 0) {
           const size_t di = ((((size_t)b * a.T + ts) * a.H) + 2 * h2 + qh) * 3 + c;
-          const float d = a.delta[di];
-          const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-          gdelta[di] = pass ? v * a.adv_flag * a.inv_std[c] : 0.f;
+          gdelta[di] = delta_grad_out(a.delta[di], dc, v, a.adv_flag, a.inv_std[c]);
         }
       }
   }
@@ -658,6 +508,41 @@ extern "C" int64_t flk_perturb_grad_scratch_bytes(int B, int T, int H, int W) {
   return (int64_t)B * T * grad_nchunk(1, T, H) * 6 * sizeof(float);   // covers both fold_t settings and the per-clip chunking (batch-1 chunk count)
 }
 
+// (fold_t = 4: the clip went in as two bf16 numbers per value; its gradient comes back in the 16-channel fold_t = 1 layout)
+template <typename TI, int FTL>
+static int launch_grad_dense(const flk_apply_args* a, const char* gx, float* gdelta, hipStream_t s) {
+  const long total = (long)(a->T / S2D<FTL>::F) * (a->H / 2) * (a->W / 2);
+  FLK_LAUNCH_KERNEL((grad_dense_kernel<TI, FTL>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *a, gx, gdelta);
+  FLK_CHECK_HIP(hipGetLastError());
+  return FLK_OK;
+}
+template <typename TI, int FTL>
+static int launch_grad_reduce(const flk_apply_args* a, const char* gx, float* gdelta, float* partials, hipStream_t s) {
+  // per-clip perturbations: the chunking (= summation order) of a batch-1 call, so that clip b of a batch follows the same
+  // trajectory, bit for bit in fp32, as the same clip attacked alone
+  const int nchunk = grad_nchunk(a->delta_per_clip ? 1 : a->B, a->T, a->H);
+  const unsigned grid = (unsigned)(a->B * (a->T / S2D<FTL>::F) * nchunk);
+  FLK_LAUNCH_KERNEL((grad_reduce_stage1<TI, FTL>), dim3(grid), dim3(256), 0, s, *a, gx, nchunk, partials);
+  return flk_grad_reduce_stage2_launch(a, nchunk, partials, gdelta, s);
+}
+template <typename TI>
+static int dispatch_grad(const flk_apply_args* a, const char* gx, float* gdelta, float* partials, hipStream_t s) {
+  const int ftl = fold_layout(a->fold_t);
+  if (a->delta_per_line) {
+    FLK_REQUIRE(a->delta_per_clip, "flk_perturb_grad_reduce: delta_per_line needs delta_per_clip (the gradient comes back per clip, [B,T,H,3])");
+    const long waves = (long)a->B * a->T * (a->H / 2);
+    const unsigned grid = (unsigned)((waves + 3) / 4 > 262144 ? 262144 : (waves + 3) / 4);
+    FLK_LAUNCH_KERNEL(grad_lines_kernel<TI>, dim3(grid), dim3(256), 0, s, *a, gx, gdelta);
+    FLK_CHECK_HIP(hipGetLastError());
+    return FLK_OK;
+  }
+  if (a->delta_dense)
+    return ftl == 1 ? launch_grad_dense<TI, 1>(a, gx, gdelta, s) : ftl == 2 ? launch_grad_dense<TI, 2>(a, gx, gdelta, s) : launch_grad_dense<TI, 3>(a, gx, gdelta, s);
+  FLK_REQUIRE(partials, "flk_perturb_grad_reduce: null scratch");
+  return ftl == 1 ? launch_grad_reduce<TI, 1>(a, gx, gdelta, partials, s)
+       : ftl == 2 ? launch_grad_reduce<TI, 2>(a, gx, gdelta, partials, s) : launch_grad_reduce<TI, 3>(a, gx, gdelta, partials, s);
+}
+
 extern "C" int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s2d, int dtype, float* gdelta,
                                        float* partials, void* stream) {
   int rc = check_apply(a);
@@ -665,37 +550,8 @@ extern "C" int flk_perturb_grad_reduce(const flk_apply_args* a, const void* gx_s
   FLK_REQUIRE(gx_s2d && gdelta, "flk_perturb_grad_reduce: null argument");
   FLK_REQUIRE(((size_t)gx_s2d & 15) == 0, "flk_perturb_grad_reduce: gx_s2d must be 16-byte aligned (got %p)", gx_s2d);
   FLK_REQUIRE(dtype == FLK_BF16 || dtype == FLK_F32, "flk_perturb_grad_reduce: bad dtype");
-  hipStream_t s = (hipStream_t)stream;
-  // (fold_t = 4: the clip went in as two bf16 numbers per value; its gradient comes back in the 16-channel fold_t = 1 layout)
-  const int ftl = (a->fold_t == 1 || a->fold_t == 4) ? 1 : a->fold_t == 3 ? 3 : 2, ft = ftl == 1 ? 1 : 2;
-  const bool bf = dtype == FLK_BF16;
-  if (a->delta_per_line) {
-    FLK_REQUIRE(a->delta_per_clip, "flk_perturb_grad_reduce: delta_per_line needs delta_per_clip (the gradient comes back per clip, [B,T,H,3])");
-    const long waves = (long)a->B * a->T * (a->H / 2);
-    const unsigned grid = (unsigned)((waves + 3) / 4 > 262144 ? 262144 : (waves + 3) / 4);
-    if (bf) FLK_LAUNCH_KERNEL(grad_lines_kernel<bf16_t>, dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta);
-    else FLK_LAUNCH_KERNEL(grad_lines_kernel<float>, dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta);
-  } else if (a->delta_dense) {
-    const long total = (long)(a->T / ft) * (a->H / 2) * (a->W / 2);
-    const unsigned grid = (unsigned)((total + 255) / 256);
-#define FLK_GD(TT, L) FLK_LAUNCH_KERNEL((grad_dense_kernel<TT, L>), dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, gdelta)
-    if (bf) { if (ftl == 1) FLK_GD(bf16_t, 1); else if (ftl == 2) FLK_GD(bf16_t, 2); else FLK_GD(bf16_t, 3); }
-    else { if (ftl == 1) FLK_GD(float, 1); else if (ftl == 2) FLK_GD(float, 2); else FLK_GD(float, 3); }
-#undef FLK_GD
-  } else {
-    FLK_REQUIRE(partials, "flk_perturb_grad_reduce: null scratch");
-    // per-clip perturbations: the chunking (= summation order) of a batch-1 call, so that clip b of a batch follows the same
-    // trajectory, bit for bit in fp32, as the same clip attacked alone
-    const int nchunk = grad_nchunk(a->delta_per_clip ? 1 : a->B, a->T, a->H);
-    const unsigned grid = (unsigned)(a->B * (a->T / ft) * nchunk);
-#define FLK_GR(TT, L) FLK_LAUNCH_KERNEL((grad_reduce_stage1<TT, L>), dim3(grid), dim3(256), 0, s, *a, (const char*)gx_s2d, nchunk, partials)
-    if (bf) { if (ftl == 1) FLK_GR(bf16_t, 1); else if (ftl == 2) FLK_GR(bf16_t, 2); else FLK_GR(bf16_t, 3); }
-    else { if (ftl == 1) FLK_GR(float, 1); else if (ftl == 2) FLK_GR(float, 2); else FLK_GR(float, 3); }
-#undef FLK_GR
-    FLK_LAUNCH_KERNEL(grad_reduce_stage2, dim3((a->T * 3 + 127) / 128, a->delta_per_clip ? a->B : 1), dim3(128), 0, s, *a, nchunk, partials, gdelta);
-  }
-  FLK_CHECK_HIP(hipGetLastError());
-  return FLK_OK;
+  return dtype == FLK_BF16 ? dispatch_grad<bf16_t>(a, (const char*)gx_s2d, gdelta, partials, (hipStream_t)stream)
+                           : dispatch_grad<float>(a, (const char*)gx_s2d, gdelta, partials, (hipStream_t)stream);
 }
 
 __global__ void pack_batch_sums_kernel(const float* per_clip, int B, float prob_scale, float* out3) {
@@ -715,8 +571,7 @@ extern "C" int flk_pack_batch_sums(const float* per_clip, int B, float prob_scal
 
 // ---- regulariser gradient + Adam / projected sign-gradient step: one workgroup, delta is [T,3] ----------------------------------
 __device__ static inline float block_sum(float v, float* sh) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  v = wave_sum(v);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -1251,15 +1106,10 @@ extern "C" int flk_flicker_lines_mix_grad(const float* g_lines, const int32_t* r
 __global__ __launch_bounds__(256) void tone_slopes_kernel(const flk_apply_args a, float* slope, float* scale) {
   const int bt = blockIdx.x, b = bt / a.T, t = bt - b * a.T, v = threadIdx.x;
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float u = a.x_lut[v * 3 + c] + a.adv_flag * pert_at(a, b, t, 0, 0, c);
-    slope[((size_t)bt * 256 + v) * 3 + c] = (u >= a.lo && u <= a.hi) ? 1.f : 0.f;
-  }
+  for (int c = 0; c < 3; ++c) slope[((size_t)bt * 256 + v) * 3 + c] = passes(a, a.x_lut[v * 3 + c], pert_at(a, b, t, 0, 0, c)) ? 1.f : 0.f;
   if (v < 3) {
-    const float d = a.delta[(size_t)bt * 3 + v];
     const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
-    const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-    scale[(size_t)bt * 3 + v] = pass ? a.adv_flag * a.inv_std[v] : 0.f;
+    scale[(size_t)bt * 3 + v] = delta_unclamped(a.delta[(size_t)bt * 3 + v], dc) ? a.adv_flag * a.inv_std[v] : 0.f;
   }
 }
 

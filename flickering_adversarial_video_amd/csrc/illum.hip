@@ -4,8 +4,8 @@
 // tables live in LDS (dec 3 KB, enc 4 (N + 1) bytes: 16 KB at N = 4096, beside the 3 KB of q_lut), staged once per workgroup, so every
 // kernel here runs a CAPPED grid whose workgroups stride over the work: the staging is paid a few times per CU, not once per 256
 // positions.  The per-value arithmetic is spelt with mul_rn / add_rn (nothing contracts to an fma): videoresnet_spec.illum_apply_host,
-// illum_export_host and illum_grad_host restate it on the host.  The layouts, the byte loads, the export's unit scheme and the two-stage
-// gradient follow csrc/attack.hip, whose kernels are left alone; the helpers both files need are in perturb_common.h.
+// illum_export_host and illum_grad_host restate it on the host.  The layouts and the two-stage gradient follow csrc/attack.hip; the byte
+// loads, the export's unit scheme and statistics fold, the wave sum and the gradient's tail are the helpers of perturb_common.h.
 #include "flk_internal.h"
 #include "perturb_common.h"
 
@@ -77,24 +77,8 @@ __device__ inline bool illum_weight(const Curve& cv, uint32_t by, int c, float s
   return true;
 }
 
-// the 6 * NP bytes x[b,tx,h, NP * 2 * wg .. , 0..2]: NP = 4 as three aligned 8-byte loads (W % 8 == 0, x 8-byte aligned), NP = 1 as three
-// 2-byte loads (x 2-byte aligned)
-template <int NP> __device__ inline void load_bytes(const uint8_t* src, uint32_t* by) {
-  if constexpr (NP == 4) {
-    const uint2* p = (const uint2*)src;
-    const uint2 r0 = p[0], r1 = p[1], r2 = p[2];
-    const uint32_t w[6] = {r0.x, r0.y, r1.x, r1.y, r2.x, r2.y};
-#pragma unroll
-    for (int k = 0; k < 24; ++k) by[k] = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-  } else {
-    const uint16_t* p = (const uint16_t*)src;
-    const uint32_t w0 = p[0], w1 = p[1], w2 = p[2];
-    by[0] = w0 & 255; by[1] = w0 >> 8; by[2] = w1 & 255; by[3] = w1 >> 8; by[4] = w2 & 255; by[5] = w2 >> 8;
-  }
-}
-
 // ---- apply: one thread = NP consecutive positions of the (h,w) fold, [B,T,H/2,W/2,16] (channel (qh*2+qw)*3+c) or, HILO (fold_t 4),
-// [B,T,H/2,W/2,32] with every value as two bf16 numbers -- the layouts of apply_s2d_kernel<.,1,.> / apply_s2d_hilo_kernel ----------
+// [B,T,H/2,W/2,32] with every value as two bf16 numbers -- the layouts S2D<1> / HiLo of apply_s2d_kernel (attack.hip) ----------
 template <typename TO, bool HILO, bool QUANT, int NP>
 __global__ __launch_bounds__(256) void illum_apply_kernel(const flk_apply_args a, const flk_illum_args m, char* out) {
   extern __shared__ float smem[];
@@ -147,8 +131,8 @@ __global__ __launch_bounds__(256) void illum_apply_kernel(const flk_apply_args a
   }
 }
 
-// ---- export: the unit scheme of adv_export_u8_kernel (work item = (clip, frame, chunk of 256 units of the DESTINATION frame); unit 0 the
-// bytes in front of the first 4-byte boundary, then the aligned words, then the tail); workgroups stride over the items ---------------
+// ---- export: work item = (clip, frame, chunk of 256 units of the DESTINATION frame), one thread = one unit (ExportUnit,
+// perturb_common.h: adv_export_u8_kernel's scheme); workgroups stride over the items ------------------------------------------------------
 template <bool STATS>
 __global__ __launch_bounds__(256) void illum_export_kernel(const flk_apply_args a, const flk_illum_args m, const flk_export_args e, uint8_t* out,
                                                            int32_t* stats, int chunks, long nitems) {
@@ -165,37 +149,25 @@ __global__ __launch_bounds__(256) void illum_export_kernel(const flk_apply_args 
     const int t = (int)(r % a.T);
     const int b = (int)(r / a.T);
     uint8_t* dst = out + (size_t)(e.out_clip_offset + b) * (size_t)e.out_clip_stride + (size_t)t * F;
-    int head = (4 - (int)((uintptr_t)dst & 3)) & 3;
-    if (head > F) head = F;
-    const int nw = (F - head) >> 2, tail = (F - head) & 3;
-    const int u = chunk * 256 + (int)threadIdx.x;
-    int start = 0, cnt = 0;
-    if (u == 0) cnt = head;
-    else if (u <= nw) { start = head + 4 * (u - 1); cnt = 4; }
-    else if (u == nw + 1) { start = head + 4 * nw; cnt = tail; }
+    ExportUnit un(dst, F, a.W, chunk);
+    const int start = un.start, cnt = un.cnt;
     int acc[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
     if (cnt > 0) {
       const int tx = wrap(t - a.shift_x, a.T);
       const uint8_t* src = (const uint8_t*)a.x + ((size_t)b * a.T + tx) * F + start;
-      int pix = start / 3, c = start - pix * 3;
-      int h = pix / a.W, w = pix - h * a.W;
       float sf[3] = {1.f, 1.f, 1.f};
       if (!a.delta_per_line) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) sf[k] = illum_s(a, e.delta_T, b, t, 0, k);
       }
       uint32_t by[4] = {0, 0, 0, 0};
-      if (cnt == 4 && ((uintptr_t)src & 3) == 0) {
-        const uint32_t v = *(const uint32_t*)src;
-        by[0] = v & 255; by[1] = (v >> 8) & 255; by[2] = (v >> 16) & 255; by[3] = v >> 24;
-      } else {
-        for (int j = 0; j < cnt; ++j) by[j] = src[j];
-      }
+      export_load_u8(src, cnt, by);
       uint32_t packed = 0;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (j < cnt) {
-          const float s = a.delta_per_line ? illum_s(a, e.delta_T, b, t, h, c) : (c == 0 ? sf[0] : c == 1 ? sf[1] : sf[2]);
+          const int c = un.c;
+          const float s = a.delta_per_line ? illum_s(a, e.delta_T, b, t, un.h, c) : (c == 0 ? sf[0] : c == 1 ? sf[1] : sf[2]);
           bool outside;
           const int q = illum_byte(illum_display(cv, by[j], c, s, &outside));
           if (cnt == 4) packed |= (uint32_t)q << (8 * j);
@@ -206,26 +178,12 @@ __global__ __launch_bounds__(256) void illum_export_kernel(const flk_apply_args 
             for (int k = 0; k < 3; ++k)
               if (c == k) { acc[k][0] += d; acc[k][1] += d < 0 ? -d : d; acc[k][2] += d != 0; acc[k][3] += outside ? 1 : 0; }
           }
-          if (++c == 3) { c = 0; if (++w == a.W) { w = 0; ++h; } }
+          un.next(a.W);
         }
       }
       if (cnt == 4) *(uint32_t*)(dst + start) = packed;
     }
-    if constexpr (STATS) {
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        int v = acc[k >> 2][k & 3];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * 12 + k] = v;
-      }
-      __syncthreads();
-      if (threadIdx.x < 12) {
-        const int s = red[threadIdx.x] + red[12 + threadIdx.x] + red[24 + threadIdx.x] + red[36 + threadIdx.x];
-        if (s != 0) atomicAdd(stats + ((size_t)b * a.T + t) * 12 + threadIdx.x, s);      // integer sums: exact in any order
-      }
-      __syncthreads();            // red is reused by the next item
-    }
+    if constexpr (STATS) export_stats_fold(acc, red, stats + ((size_t)b * a.T + t) * 12);
   }
 }
 
@@ -280,9 +238,7 @@ __global__ __launch_bounds__(256) void illum_grad_stage1(const flk_apply_args a,
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      float v = acc[c];
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+      const float v = wave_sum(acc[c]);
       if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * 3 + c] = v;
     }
     __syncthreads();
@@ -303,10 +259,8 @@ __global__ void illum_grad_stage2(const flk_apply_args a, const flk_illum_args m
     for (int k = 0; k < nchunk; ++k) s += partials[(((size_t)b * a.T + t) * nchunk + k) * 3 + c];
   const int ts = wrap(t - a.shift_p, a.T);
   const size_t di = (a.delta_per_clip ? (size_t)b_lo * a.T * 3 : 0) + (size_t)ts * 3 + c;
-  const float d = a.delta[di];
   const float dc = a.dclip_dev ? a.dclip_dev[b_lo] : a.dclip;
-  const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-  gdelta[di] = pass ? s * a.adv_flag * m.out_mul[c] : 0.f;
+  gdelta[di] = delta_grad_out(a.delta[di], dc, s, a.adv_flag, m.out_mul[c]);
 }
 
 // per line (delta_per_line with delta_per_clip): one wave owns one (clip, frame, row pair) and produces its 2 lines x 3 channels: lane l
@@ -354,14 +308,10 @@ __global__ __launch_bounds__(256) void illum_grad_lines_kernel(const flk_apply_a
     for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        float v = acc[qh][c];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        const float v = wave_sum(acc[qh][c]);
         if (lane == 0) {
           const size_t di = ((((size_t)b * a.T + ts) * a.H) + 2 * h2 + qh) * 3 + c;
-          const float d = a.delta[di];
-          const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-          gdelta[di] = pass ? v * a.adv_flag * m.out_mul[c] : 0.f;
+          gdelta[di] = delta_grad_out(a.delta[di], dc, v, a.adv_flag, m.out_mul[c]);
         }
       }
   }
@@ -385,10 +335,8 @@ __global__ __launch_bounds__(256) void illum_tone_slopes_kernel(const flk_apply_
       slope[((size_t)bt * 256 + v) * 3 + c] = illum_weight(cv, (uint32_t)v, c, illum_s(a, a.T, b, t, 0, c), &w) ? w : 0.f;
     }
     if (v < 3) {
-      const float d = a.delta[(size_t)bt * 3 + v];
       const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
-      const bool pass = !(dc > 0.f) || (d >= -dc && d <= dc);
-      scale[(size_t)bt * 3 + v] = pass ? mul_rn(a.adv_flag, m.out_mul[v]) : 0.f;
+      scale[(size_t)bt * 3 + v] = delta_unclamped(a.delta[(size_t)bt * 3 + v], dc) ? mul_rn(a.adv_flag, m.out_mul[v]) : 0.f;
     }
   }
 }

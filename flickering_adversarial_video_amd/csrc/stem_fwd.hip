@@ -34,7 +34,7 @@
 #include <stdlib.h>
 #include <new>
 #include "flk_internal.h"
-#include "quant_encode.h"
+#include "perturb_common.h"
 
 namespace {
 
@@ -85,8 +85,6 @@ typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline unsigned lds_addr(const void* p) { return (unsigned)(size_t)(__attribute__((address_space(3))) const char*)p; }
-__device__ inline int wrapT(int t, int T) { t %= T; return t < 0 ? t + T : t; }
-__device__ inline float clipf(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
 
 // one LDS-DMA wave instruction: lane l moves 16 bytes from sbase + voff (per lane) to LDS byte lds_base + 16 l (lds_base wave-uniform)
 __device__ inline void glds16(unsigned voff, const char* sbase, unsigned lds_base) {
@@ -166,16 +164,10 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
     float pv[3] = {0.f, 0.f, 0.f};
     int tx = 0;
     if (valid) {
-      tx = wrapT(t - a.shift_x, a.T);                            // x'[t] = x[(t - shift_x) mod T]
+      tx = wrap(t - a.shift_x, a.T);                             // x'[t] = x[(t - shift_x) mod T]
       if (a.adv_flag != 0.f) {
-        const int ts = wrapT(t - a.shift_p, a.T);                // p'[t] = p[(t - shift_p) mod T]
-        const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          float d = a.delta[(a.delta_per_clip ? b * a.T : 0) * 3 + ts * 3 + c];
-          if (dc > 0.f) d = clipf(d, -dc, dc);
-          pv[c] = a.adv_flag * (d * a.inv_std[c]);
-        }
+        for (int c = 0; c < 3; ++c) pv[c] = a.adv_flag * flicker_pert(a, b, t, c);
       }
     }
     float* e = tab + tid * 8;
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
           }
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            const float x = (float)((w2[i >> 2] >> (8 * (i & 3))) & 255u) * a.x_scale + a.x_bias;
+            const float x = decode_scaled(a, byte_of(w2, i));
             const float u = clipf(x + P[i % 3], a.lo, a.hi);
             v[i] = (float)encode_q(u, M[i % 3], A[i % 3], a.q_levels) * a.x_scale + a.x_bias;
           }
@@ -249,7 +241,7 @@ __global__ __launch_bounds__(256, NI == 4 ? 3 : 2) void stem_fwd_u8_kernel(const
           L[2] = c0 == 0 ? l2 : c0 == 1 ? l0 : l1; H[2] = c0 == 0 ? h2 : c0 == 1 ? h0 : h1;
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            const float x = (float)((w2[i >> 2] >> (8 * (i & 3))) & 255u) * a.x_scale + a.x_bias;
+            const float x = decode_scaled(a, byte_of(w2, i));
             v[i] = __builtin_amdgcn_fmed3f(x, L[i % 3], H[i % 3]);
           }
         }

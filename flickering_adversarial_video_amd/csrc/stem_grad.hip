@@ -41,6 +41,7 @@
 // fixed order, roll, 1/std, delta-clip mask) is reused unchanged.
 #include <stdlib.h>
 #include "flk_internal.h"
+#include "perturb_common.h"
 
 // timing ablations (WRONG results) only in -DFLK_ABLATE builds; compile-time zero in the product library
 #ifdef FLK_ABLATE
@@ -91,16 +92,6 @@ struct StemGradKP {
   int dbg;                             // timing experiments only (FLK_SG_DBG): 1 = no mask stream, 2 = no MFMA phase, 4 = no G stream
 };
 
-__device__ inline int sg_wrap(int t, int T) { t %= T; return t < 0 ? t + T : t; }
-__device__ inline float sg_clip(float v, float lo, float hi) { return fminf(fmaxf(v, lo), hi); }
-// perturbation added at frame t (flicker delta only) -- the same expression as attack.hip: pert_at
-__device__ inline float sg_pert(const flk_apply_args& a, int b, int t, int c) {
-  float d = a.delta[(a.delta_per_clip ? b * a.T : 0) * 3 + sg_wrap(t - a.shift_p, a.T) * 3 + c];
-  const float dc = a.dclip_dev ? a.dclip_dev[b] : a.dclip;
-  if (dc > 0.f) d = sg_clip(d, -dc, dc);
-  return d * a.inv_std[c];
-}
-
 // ---- 1. the clip mask, de-interleaved ----
 // Per (clip, frame, row) the mask is kept as 6 byte sequences (channel c, pixel parity): byte SG_MPAD + i of sequence (c, par) is the pass
 // byte (0x40 = pass, 0x00 = clipped) of pixel w = 2 i + par, zero padded on both sides = beyond the frame.  Column (c, kw) of the GEMM's B
@@ -125,14 +116,14 @@ __global__ __launch_bounds__(256) void stem_mask_kernel(const flk_apply_args a, 
   }
   const int r = tid / SM_GROUPS, j = tid - r * SM_GROUPS;          // this thread's row and pixel group
   if (r < nr) {
-    const size_t src = ((((size_t)b * a.T + sg_wrap(t - a.shift_x, a.T)) * a.H + h0 + r) * a.W) * 3 + 24 * j;   // x'[t] = x[(t - shift_x) mod T]
+    const size_t src = ((((size_t)b * a.T + wrap(t - a.shift_x, a.T)) * a.H + h0 + r) * a.W) * 3 + 24 * j;   // x'[t] = x[(t - shift_x) mod T]
     float xv[24];
     if (a.x_is_u8) {
       unsigned xu[6];
 #pragma unroll
       for (int k = 0; k < 6; ++k) xu[k] = *(const unsigned*)((const unsigned char*)a.x + src + 4 * k);
 #pragma unroll
-      for (int e = 0; e < 24; ++e) xv[e] = (float)((xu[e >> 2] >> (8 * (e & 3))) & 255u) * a.x_scale + a.x_bias;
+      for (int e = 0; e < 24; ++e) xv[e] = decode_scaled(a, byte_of(xu, e));
     } else {
 #pragma unroll
       for (int k = 0; k < 6; ++k) {
@@ -142,7 +133,7 @@ __global__ __launch_bounds__(256) void stem_mask_kernel(const flk_apply_args a, 
     }
     float pv[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) pv[c] = a.adv_flag * sg_pert(a, b, t, c);
+    for (int c = 0; c < 3; ++c) pv[c] = a.adv_flag * flicker_pert(a, b, t, c);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -643,7 +634,7 @@ __global__ __launch_bounds__(64) void stem_delta_bias_kernel(const flk_apply_arg
     const int t = 2 * ot + kt - 2;
     if (t < 0 || t >= a.T) continue;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) acc += a.adv_flag * sg_pert(a, b, t, c) * S[(((size_t)kt * 16 + cls) * 3 + c) * SG_CO + co];
+    for (int c = 0; c < 3; ++c) acc += a.adv_flag * flicker_pert(a, b, t, c) * S[(((size_t)kt * 16 + cls) * 3 + c) * SG_CO + co];
   }
   tab[(((size_t)b * (a.T / 2) + ot) * 16 + cls) * SG_CO + co] = acc;
 }

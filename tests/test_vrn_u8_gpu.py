@@ -38,7 +38,7 @@ def apply_pair(xu, xf, d, **kw):
 @pytest.mark.parametrize("W", [112, 100])
 @pytest.mark.parametrize("fold_t", [1, 4])
 def test_apply_and_grad_reduce_u8_is_bitwise_the_fp32_clip(W, fold_t):
-    """W = 112: the bf16 input (fold_t 4) comes from apply_s2d_hilo_u8_kernel; W = 100 (not a multiple of 8): the generic kernels"""
+    """W = 112: the bf16 input (fold_t 4) comes from apply_s2d_u8x4_kernel<bf16, HiLo, TABLE>; W = 100 (not a multiple of 8): the generic kernels"""
     from flickering_adversarial_video_amd import ops
     B, T, H = 2, 4, 6
     xu, xf = clips(B, T, H, W, seed=7)
